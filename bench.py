@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X-native render path (see BASELINE.json / SURVEY section 8(d)).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--static-camera]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--static-camera] [--full] [--dump-outputs DIR]
 
 Prints ONE JSON line (rank 0).  Inputs are resident in HBM when the timed region starts.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`, ...).
+--full adds everything else the line has carried: per-kernel durations and the roofline figures (runs of their own after the
+timed steps), the static-camera and host-path rates, the CPU baselines and, with no --workload, the `sub_results`.
+--dump-outputs DIR writes the last frame of the last timed step to DIR/frame_rgb.npy (float32 R, G, B in 0..255; frames over
+64 MB as a seeded sample of pixels, their flat indices in DIR/frame_pixel_index.npy).  The timed loop ends on the same view
+whatever the number of frames per step, so runs with the same arguments render the same last frame.
 
 A STEP is a batch of `frames_per_step` frames of the hot path (chosen so that the K timed steps last >= ~60 ms: a single
 Cornell frame takes 25 us, and 20 of them would time launch noise).  The camera MOVES: every frame has its own yaw (an orbit
@@ -19,8 +26,8 @@ Workloads (BASELINE.json `configs`):
     cornell500   (configs[0]) the reference's own 500x500 case
     soup1m8k     (configs[4]) 1M random triangles, 7680x4320 (meant for 8 GPUs)
     cornell1080soft16 / cornell1080aa3 / cornell1080dof8 / raster4kdof8   SURVEY 8(f) ranks 1-3 switched on
-With no --workload the line is soup100k (binned: bit-identical to brute force, tests/test_gpu_baseline_configs.py) and carries
-`sub_results` for cornell1080, raster4k, soup1m8k and `soup100k_brute` -- ONE frame of the same workload through the LDS-tiled
+With no --workload the line is soup100k (binned: bit-identical to brute force, tests/test_gpu_baseline_configs.py); with --full it
+also carries `sub_results` for cornell1080, raster4k, soup1m8k and `soup100k_brute` -- ONE frame of the same workload through the LDS-tiled
 brute-force kernel, the literal wording of configs[2] and the one kernel whose flop count is the reference's (rays x triangles x 60).
 
 With --gpus N > 1 (`python bench.py --gpus N` starts its own ranks; under the driver's torch.distributed.run it reads RANK /
@@ -371,9 +378,12 @@ class Env:
         return [float(x) for x in t.tolist()]
 
 
-def run_workload(env, name, steps, warmup, mode_name, moving, want_cpu, target_s=0.06, extras=True, quick=False):
+def run_workload(env, name, steps, warmup, mode_name, moving, want_cpu, target_s=0.06, extras=True, quick=False, detail=True,
+                 keep_frame=False):
     """Times `steps` steps of workload `name` and returns its result dict (rank 0; None elsewhere).  quick: a handful of frames
-    around the timed ones instead of dozens (frames that take a sixth of a second: the brute-force kernel on 100 k triangles)."""
+    around the timed ones instead of dozens (frames that take a sixth of a second: the brute-force kernel on 100 k triangles).
+    detail=False: the headline figures only -- no per-kernel, roofline, static-camera, host-path or CPU measurement after the
+    timed steps.  keep_frame: the last frame of the timed loop, (H, W) XRGB words on the host, goes into the dict as `_frame`."""
     torch, dist, mirt = env.torch, env.dist, env.mirt
     from mirt.sharding import BandGather
     world, rank, dev = env.world, env.rank, env.dev
@@ -437,6 +447,7 @@ def run_workload(env, name, steps, warmup, mode_name, moving, want_cpu, target_s
     rendered = [torch.cuda.Event() for _ in range(depth)]      # band buffer k holds a finished batch
     gathered = [torch.cuda.Event() for _ in range(depth)]      # band buffer k has been sent and may be overwritten
     frame_no = [0]
+    view_offset = [0]                                     # frame i renders view (i + offset) % nviews
 
     def flush(k):
         """The batch in band buffer k is complete: gather it on the communication stream."""
@@ -460,7 +471,7 @@ def run_workload(env, name, steps, warmup, mode_name, moving, want_cpu, target_s
     def frame():
         i = frame_no[0]
         frame_no[0] += 1
-        v = i % nviews
+        v = (i + view_offset[0]) % nviews
         if native:
             if i % batch == 0:
                 if cullers is not None:
@@ -494,14 +505,41 @@ def run_workload(env, name, steps, warmup, mode_name, moving, want_cpu, target_s
             flush((frame_no[0] // batch) % depth)
         frame_no[0] = 0
 
-    def timed(nframes):
+    def prepare(nframes):
+        """Makes the closures frame() will call for the next nframes frames (the pattern repeats within nviews x depth x batch)."""
+        for i in range(min(nframes, nviews * depth * batch)):
+            v = (i + view_offset[0]) % nviews
+            if native:
+                if i % batch == 0:
+                    sharded_fn(v, (i // batch) % depth)
+            elif world == 1:
+                render_fn(v, i % depth, 0)
+            else:
+                render_fn(v, (i // batch) % depth, i % batch)
+
+    def timed(nframes, end_view=None):
+        """end_view: the last of the nframes frames renders this view, whatever nframes is (the orbit is entered where it has to
+        be), so that the last frame of the timed loop is the same from run to run."""
+        if end_view is not None:
+            view_offset[0] = (end_view - (nframes - 1)) % nviews
+            prepare(nframes)
         env.fence()
         t0 = time.perf_counter()
         for _ in range(nframes):
             frame()
         finish_batch()
         env.fence()
+        view_offset[0] = 0
         return time.perf_counter() - t0
+
+    def last_frame(nframes):
+        """The (H, W) XRGB frame the last of nframes frames of a timed() call left on rank 0 (device tensor, not a copy)."""
+        n = nframes - 1
+        if native:
+            return root_frames[(n // batch) % depth][n % batch]
+        if world == 1:
+            return bands.slot(n % depth, 0)
+        return bands.frames[last_batch[0] - 1] if batch > 1 else bands.frame
 
     # calibrate the batch: frames per step so that the timed region lasts >= target_s (agreed over the ranks)
     timed(2 if quick else max(2 * batch, 12))          # (also past the frames after which the light-cube grid settles: mirt_capi light_cache_ensure)
@@ -521,8 +559,9 @@ def run_workload(env, name, steps, warmup, mode_name, moving, want_cpu, target_s
                 fps_step = int(np.ceil(fps_step * 1.2 * target_s / max(dw * steps, 1e-9)))
                 if world > 1:
                     fps_step = ((fps_step + batch - 1) // batch) * batch
-    dt = timed(steps * fps_step)
+    dt = timed(steps * fps_step, end_view=nviews - 1)
     st = mirt.stats()
+    kept_frame = last_frame(steps * fps_step).cpu().numpy() if keep_frame and rank == 0 else None
     dt = env.reduce([dt], dist.ReduceOp.MAX)[0] if world > 1 else dt
     rays_rank = float(st["primary_rays"] + st["shadow_rays"]) if kind == "rt" else 0.0
     rays_frame, tests_frame, shadow_frame = env.reduce([rays_rank, float(st["tests"]), float(st["shadow_rays"])], dist.ReduceOp.SUM)
@@ -530,7 +569,7 @@ def run_workload(env, name, steps, warmup, mode_name, moving, want_cpu, target_s
     if env.rehearsal and rank == 0:
         # the frames rank 0 assembled from every rank's bands against one full-frame render of the same view (interior
         # words; the border is never written by the ray tracer)
-        vlast = (steps * fps_step - 1) % nviews
+        vlast = nviews - 1                               # (the timed loop's end_view)
         full = torch.zeros((H, W), dtype=torch.int32, device=dev)
         torch.cuda.synchronize()                         # (torch fills on ITS stream; the library's streams are not ordered with it)
         if cullers is not None:
@@ -540,12 +579,11 @@ def run_workload(env, name, steps, warmup, mode_name, moving, want_cpu, target_s
         else:
             mirt.rasterise_device(views[vlast], LIGHT, INDIRECT, 0, H, 0, full.data_ptr(), W * 4)
         mirt.sync()
+        got = last_frame(steps * fps_step)
         if native:
-            got = root_frames[((steps * fps_step - 1) // batch) % depth][(steps * fps_step - 1) % batch].clone()
+            got = got.clone()
             if kind == "rt":                             # border words: never written by the ray tracer (received bands carry 0)
                 got[0, :] = full[0, :]; got[-1, :] = full[-1, :]; got[:, 0] = full[:, 0]; got[:, -1] = full[:, -1]
-        else:
-            got = bands.frames[last_batch[0] - 1] if batch > 1 else bands.frame
         same = bool(torch.equal(got, full))
         print("rehearsal %s: the last gathered frame is identical to the single-GPU frame: %s" % (name, same), file=sys.stderr, flush=True)
         if not same:
@@ -553,47 +591,48 @@ def run_workload(env, name, steps, warmup, mode_name, moving, want_cpu, target_s
             raise SystemExit("rehearsal: gathered frame differs from the single-GPU frame (%d words in %d rows, first row %d, last row %d; bands %s)"
                              % (int((got != full).sum()), int(bad_rows.numel()), int(bad_rows[0]), int(bad_rows[-1]), [mirt.band_of(r, world, H) for r in range(world)]))
 
-    # per-kernel durations of this rank IN THE SAME MODE as the timed loop (same frames in flight, same moving camera):
-    # the library brackets every launch with hipEvents on the stream it runs on
-    # -- with two frames in flight the frame measured is the one BEFORE the last of a run of frames queued back to back
-    # (mirt_get_previous_kernel_ms): its kernels ran between the frames on both sides of it, as every frame of the timed loop
-    # does; the last frame of a run drains alone and would read like a single-stream launch.
-    mirt.set_profiling(True)
-    kacc, kn = {}, 0
+    kernel_ms, kernel_ms_alone, st_prof = {}, None, None
     overlapped = in_flight >= 2 and not native and batch == 1
-    for i in range(1 if quick else max(4, min(steps * fps_step, 64) // 4)):
-        for _ in range((3 if quick else 6) if overlapped else 1):
-            frame()
-        if overlapped:
-            kms, _ = mirt.previous_kernel_ms()
-        else:
-            mirt.sync()
-            kms = mirt.stats()["kernel_ms"]
-        for k, v in kms.items():
-            kacc[k] = kacc.get(k, 0.0) + v
-        kn += 1
-    finish_batch()
-    env.fence()
-    kernel_ms = {k: v / kn for k, v in kacc.items() if v > 0}
-    # ... and the same launches ALONE on the device (a sync after every frame): what the kernel takes when nothing shares the
-    # chip with it -- beside the line's figures, never in them
-    kernel_ms_alone = None
-    if overlapped:
-        aacc, an = {}, 0
-        for i in range(2 if quick else 12):
-            frame()
-            mirt.sync()
-            for k, v in mirt.stats()["kernel_ms"].items():
-                aacc[k] = aacc.get(k, 0.0) + v
-            an += 1
+    if detail:
+        # per-kernel durations of this rank IN THE SAME MODE as the timed loop (same frames in flight, same moving camera):
+        # the library brackets every launch with hipEvents on the stream it runs on
+        # -- with two frames in flight the frame measured is the one BEFORE the last of a run of frames queued back to back
+        # (mirt_get_previous_kernel_ms): its kernels ran between the frames on both sides of it, as every frame of the timed loop
+        # does; the last frame of a run drains alone and would read like a single-stream launch.
+        mirt.set_profiling(True)
+        kacc, kn = {}, 0
+        for i in range(1 if quick else max(4, min(steps * fps_step, 64) // 4)):
+            for _ in range((3 if quick else 6) if overlapped else 1):
+                frame()
+            if overlapped:
+                kms, _ = mirt.previous_kernel_ms()
+            else:
+                mirt.sync()
+                kms = mirt.stats()["kernel_ms"]
+            for k, v in kms.items():
+                kacc[k] = kacc.get(k, 0.0) + v
+            kn += 1
         finish_batch()
         env.fence()
-        kernel_ms_alone = {k: v / an for k, v in aacc.items() if v > 0}
-    # the binned kernel keeps its own counts (tests executed, candidates offered) only for frames rendered with profiling on --
-    # five scalar instructions per filter step that the frames of the timed loop do without: the last profiled frame has them
-    mirt.sync()
-    st_prof = mirt.stats()
-    mirt.set_profiling(False)
+        kernel_ms = {k: v / kn for k, v in kacc.items() if v > 0}
+        # ... and the same launches ALONE on the device (a sync after every frame): what the kernel takes when nothing shares the
+        # chip with it -- beside the line's figures, never in them
+        if overlapped:
+            aacc, an = {}, 0
+            for i in range(2 if quick else 12):
+                frame()
+                mirt.sync()
+                for k, v in mirt.stats()["kernel_ms"].items():
+                    aacc[k] = aacc.get(k, 0.0) + v
+                an += 1
+            finish_batch()
+            env.fence()
+            kernel_ms_alone = {k: v / an for k, v in aacc.items() if v > 0}
+        # the binned kernel keeps its own counts (tests executed, candidates offered) only for frames rendered with profiling on --
+        # five scalar instructions per filter step that the frames of the timed loop do without: the last profiled frame has them
+        mirt.sync()
+        st_prof = mirt.stats()
+        mirt.set_profiling(False)
 
     static = None
     if extras and moving and world == 1:
@@ -623,7 +662,7 @@ def run_workload(env, name, steps, warmup, mode_name, moving, want_cpu, target_s
         host = host_path_rate(mirt, kind, views, mode, W, H, t_frame)
 
     covered = None
-    if kind == "raster" and rank == 0 and world == 1:
+    if detail and kind == "raster" and rank == 0 and world == 1:
         z = torch.zeros((H, W), dtype=torch.float32, device=dev)
         torch.cuda.synchronize()                             # (torch fills on ITS stream; the library's streams are not ordered with it)
         mirt.cull_device(views[0], 3)
@@ -642,8 +681,11 @@ def run_workload(env, name, steps, warmup, mode_name, moving, want_cpu, target_s
             "frames_per_s": round(nframes / dt, 3), "frames_in_flight": in_flight,
             "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "runtime default (4)"),
             "camera": ("orbit: yaw += %g rad per frame, %d views" % (ORBIT_STEP, nviews)) if moving else "static",
-            "kernel_ms_rank0": {k: round(v, 5) for k, v in kernel_ms.items()},
         }
+        if detail:
+            out["kernel_ms_rank0"] = {k: round(v, 5) for k, v in kernel_ms.items()}
+        if kept_frame is not None:
+            out["_frame"] = kept_frame
         if kernel_ms_alone:
             out["kernel_ms_alone_rank0"] = {k: round(v, 5) for k, v in kernel_ms_alone.items()}
         if static:
@@ -665,6 +707,15 @@ def run_workload(env, name, steps, warmup, mode_name, moving, want_cpu, target_s
                            "primary_rays": W * H * aa * aa, "shadow_rays": int(shadow_frame), "mode": ["auto", "brute", "binned"][st["mode_used"]],
                            "parallelism": ("bands%d%s+%s" % (world, "(cost-weighted)" if weighted else "", "rccl-p2p-gather(libmirt)" if native else "torch-gather") + ("x%d" % batch if batch > 1 else "")) if world > 1 else "1gpu"},
             })
+        else:
+            out.update({
+                "metric": "frames/s (rasteriser)", "unit": "frames/s", "dtype": "f32", "value": round(nframes / dt, 3),
+                "config": {"workload": name, "scene": "cornell-30", "triangles": int(len(tris)), "visible_triangles": int((culled0 == 0).sum()),
+                           "width": W, "height": H, "lights": 1, "dof_kernel": dof, "covered_pixels": covered,
+                           "parallelism": ("bands%d+%s" % (world, "rccl-p2p-gather(libmirt)" if native else "torch-gather")) if world > 1 else "1gpu"},
+            })
+        # the roofline figures: from the per-kernel durations above and the committed counters (--full)
+        if kind == "rt" and detail:
             kt = kernel_ms.get("trace", 0.0)
             kname = {mirt.RT_BRUTE: "k_rt_tile2" if len(tris) <= 64 else ("k_rt_small" if len(tris) * 48 * 3 + 16 <= 48 * 1024 else "k_rt_brute"),
                      mirt.RT_BINNED: "k_rt_trace2"}[st["mode_used"]]
@@ -730,13 +781,7 @@ def run_workload(env, name, steps, warmup, mode_name, moving, want_cpu, target_s
                                        "algorithmic_bytes": int(algo_bytes),
                                        "note": "algorithmic bytes = 4*W*rows framebuffer + 60*N triangle list; far below the HBM roof by "
                                                "construction; frame_traffic = every per-frame kernel (the PMC pass saw it more than twice), weighted by its launches per frame"}
-        else:
-            out.update({
-                "metric": "frames/s (rasteriser)", "unit": "frames/s", "dtype": "f32", "value": round(nframes / dt, 3),
-                "config": {"workload": name, "scene": "cornell-30", "triangles": int(len(tris)), "visible_triangles": int((culled0 == 0).sum()),
-                           "width": W, "height": H, "lights": 1, "dof_kernel": dof, "covered_pixels": covered,
-                           "parallelism": ("bands%d+%s" % (world, "rccl-p2p-gather(libmirt)" if native else "torch-gather")) if world > 1 else "1gpu"},
-            })
+        elif kind == "raster" and detail:
             band_px = W * (y1 - y0)
             cov = covered if covered is not None else band_px
             tr = kernel_ms.get("raster_resolve", 0.0)
@@ -924,6 +969,25 @@ def host_path_rate(mirt, kind, views, mode, W, H, t_frame):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 21          # frames whose R, G, B floats exceed DUMP_LIMIT_BYTES: this many pixels, seeded
+
+
+def dump_frame(out_dir, xrgb):
+    """The XRGB words of one frame as float32 R, G, B (0..255), (H, W, 3); a frame over DUMP_LIMIT_BYTES as a fixed, seeded
+    sample of its pixels, (n, 3), beside their flat indices (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    words = np.ascontiguousarray(xrgb).view(np.uint32)
+    rgb = np.stack([(words >> 16) & 0xFF, (words >> 8) & 0xFF, words & 0xFF], axis=-1).astype(np.float32)
+    if rgb.nbytes > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(words.size, DUMP_SAMPLE_PIXELS, replace=False))
+        rgb = rgb.reshape(-1, 3)[idx]
+        np.save(os.path.join(out_dir, "frame_pixel_index.npy"), idx.astype(np.float64))
+    elif os.path.exists(os.path.join(out_dir, "frame_pixel_index.npy")):
+        os.remove(os.path.join(out_dir, "frame_pixel_index.npy"))          # (left by an earlier, sampled dump)
+    np.save(os.path.join(out_dir, "frame_rgb.npy"), rgb)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -934,6 +998,10 @@ def main():
     ap.add_argument("--static-camera", action="store_true", help="one fixed view for every frame (the sizing caches always hit)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sub-results", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel and roofline figures, static-camera and host-path rates, CPU baselines, sub_results")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last frame of the last timed step to DIR/frame_rgb.npy (float32)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` launches its own ranks: one process per GPU under torch.distributed.run, started HERE, before
@@ -954,8 +1022,10 @@ def main():
     # the timed region lasts a second at least (an activity sampler beside the run sees it); MIRT_BENCH_TARGET_S overrides
     target = float(os.environ.get("MIRT_BENCH_TARGET_S", "1.0")) if args.mode != "brute" else 0.0
     heavy_brute = args.mode == "brute" and WORKLOADS[name][1][0] == "soup"
-    out = run_workload(env, name, steps, warmup, args.mode, not args.static_camera, not args.no_cpu_baseline, target_s=target, quick=heavy_brute)
-    if args.workload is None and not args.no_sub_results:
+    out = run_workload(env, name, steps, warmup, args.mode, not args.static_camera, args.full and not args.no_cpu_baseline, target_s=target,
+                       extras=args.full, quick=heavy_brute, detail=args.full, keep_frame=args.dump_outputs is not None)
+    frame = out.pop("_frame", None) if out is not None else None
+    if args.full and args.workload is None and not args.no_sub_results:
         subs = {}
         keep = ("metric", "value", "unit", "ms_per_frame", "frames_per_s", "frames_per_step", "steps", "timed_region_s",
                 "kernel_ms_rank0", "kernel_ms_alone_rank0", "config", "roofline", "_cpu_leg")
@@ -979,6 +1049,8 @@ def main():
         if leg is not None:
             rec["cpu_baseline"] = leg()
     if env.rank == 0:
+        if frame is not None:
+            dump_frame(args.dump_outputs, frame)
         print(json.dumps(out), flush=True)
     if env.world > 1:
         env.dist.barrier()

@@ -6,6 +6,9 @@ only the expected outputs come from the reference.
 
 Frames are the sizes the reference itself can render: 500x500, and 150x150 (its -DREALTIME build) for the ray tracer.
 """
+import lzma
+import os
+
 import numpy as np
 
 L0 = [0.0, -0.5, -0.7, 1.0, 1.0, 1.0, 14.0]                 # AddLight(vec3(0,-0.5f,-0.7f), vec3(1,1,1), 14), raytracer.cpp:116
@@ -44,3 +47,14 @@ def build_scene(oracle, spec):
 
 def lights_array(lights):
     return np.array(lights, np.float32).reshape(-1, 7)
+
+
+def reference_asset(directory):
+    """Writes the reference's own mesh (rasteriser/Source/enemy1.stl, stored as data in tests/golden/enemy1.stl.xz) to
+    <directory>/Source/enemy1.stl, the relative path the reference's loader opens, and returns that path."""
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "enemy1.stl.xz")
+    os.makedirs(os.path.join(str(directory), "Source"), exist_ok=True)
+    path = os.path.join(str(directory), "Source", "enemy1.stl")
+    with lzma.open(src, "rb") as f, open(path, "wb") as g:
+        g.write(f.read())
+    return path

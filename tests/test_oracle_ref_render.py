@@ -11,13 +11,12 @@ Still NOT covered by this pin, because their text names an SDL type (they stay o
 tests/test_oracle_pin.py): PutPixelSDL (SDLauxiliary.h:70-81), the surface clear in the rasteriser's Update() (:183-192).
 """
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
 import ref_render
-from ref_cases import RT_CASES, RASTER_CASES, build_scene, lights_array
+from ref_cases import RT_CASES, RASTER_CASES, build_scene, lights_array, reference_asset
 
 pytestmark = pytest.mark.skipif(not ref_render.available(), reason="oracle/_ref not built (needs /root/reference; make -C oracle ref)")
 
@@ -219,12 +218,10 @@ def test_raster_depth_of_field_blur_loops(oracle, raster, K):
     assert same(got[4:496, 1:499], want[4:496, 1:499])
 
 
-def test_stl_loader_on_the_reference_asset(oracle, raster):
+def test_stl_loader_on_the_reference_asset(oracle, raster, tmp_path):
     """LoadSTL::LoadSTLFile (LoadSTL.cpp:17-97) run on the reference's own mesh == the restated loader, bit for bit."""
-    d = "/root/reference/rasteriser"
-    if not os.path.exists(os.path.join(d, "Source", "enemy1.stl")):
-        pytest.skip("reference tree not present")
-    got = raster.load_stl(d)
-    want = oracle.load_stl(os.path.join(d, "Source", "enemy1.stl"))
+    path = reference_asset(tmp_path)
+    got = raster.load_stl(str(tmp_path))
+    want = oracle.load_stl(path)
     assert got.shape == want.shape == (9028, 15)
     assert np.array_equal(bits(got), bits(want))

@@ -8,6 +8,7 @@ import pytest
 
 import mirt
 from mirt_oracle import DEFAULT_LIGHT
+from ref_cases import reference_asset
 
 
 def write_stl(path, tris, eol="\n", extra_spaces=False):
@@ -62,14 +63,19 @@ def test_oracle_loader_follows_the_reference_parser(oracle, tmp_path):
         oracle.load_stl(str(broken))
 
 
-def test_reference_asset_facet_count(oracle):
-    """The reference's own mesh (read as data, where the reference tree is present): 9 028 facets."""
-    path = "/root/reference/rasteriser/Source/enemy1.stl"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present")
-    t = oracle.load_stl(path)
+def test_reference_asset_facet_count(oracle, tmp_path):
+    """The reference's own mesh (read as data): 9 028 facets."""
+    t = oracle.load_stl(reference_asset(tmp_path))
     assert t.shape == (9028, 15)
     assert np.isfinite(t[:, :9]).all() and np.abs(t[:, :9]).max() < 10.0
+
+
+def test_product_loader_on_the_reference_asset(oracle, tmp_path):
+    """mirt_scene_load_stl on the reference's own mesh: bit-identical to the oracle's restatement."""
+    path = reference_asset(tmp_path)
+    got = mirt.scene_load_stl(path)
+    assert got.shape == (9028, 15)
+    assert np.array_equal(got.view(np.uint32), oracle.load_stl(path).view(np.uint32))
 
 
 def test_product_loader_matches_oracle_without_a_gpu(oracle, tmp_path):

@@ -36,11 +36,14 @@ elif [ "$stage" = fuzz ]; then
   python tools/fuzz_sequence.py 0 200 > gpurun_out/fuzz_call_sequences.txt 2>&1; echo "fuzz sequences rc=$?"
   python tools/fuzz_raster_sequence.py 0 200 > gpurun_out/fuzz_raster_call_sequences.txt 2>&1; echo "fuzz raster sequences rc=$?"
 else
-  python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err; echo "bench default rc=$?"
+  # the full bench lines (--full: sub_results, roofline, cpu_baseline) go to $RESULTS_DIR (default results/); point it at the
+  # directory the other stages write to when tools/store_profiles.py is to copy them into profiles/
+  res="${RESULTS_DIR:-results}"; mkdir -p "$res"
+  python bench.py --full > "$res/bench_default.json" 2> "$res/bench_default.err"; echo "bench default rc=$?"
   for w in soup100k cornell1080 raster4k cornell500 cornell1080soft16 cornell1080aa3 cornell1080dof8 raster4kdof8; do
-    python bench.py --workload $w > gpurun_out/bench_$w.json 2> gpurun_out/bench_$w.err; echo "bench $w rc=$?"
+    python bench.py --full --workload $w > "$res/bench_$w.json" 2> "$res/bench_$w.err"; echo "bench $w rc=$?"
   done
-  python bench.py --workload soup1m8k --steps 5 --warmup 2 --no-cpu-baseline > gpurun_out/bench_soup1m8k.json 2>/dev/null; echo "bench soup1m8k rc=$?"
-  python bench.py --workload soup100k --mode brute --steps 2 --warmup 1 --no-cpu-baseline --static-camera > gpurun_out/bench_soup100k_brute.json 2>/dev/null; echo "bench soup100k brute rc=$?"
+  python bench.py --full --workload soup1m8k --steps 5 --warmup 2 --no-cpu-baseline > "$res/bench_soup1m8k.json" 2>/dev/null; echo "bench soup1m8k rc=$?"
+  python bench.py --full --workload soup100k --mode brute --steps 2 --warmup 1 --no-cpu-baseline --static-camera > "$res/bench_soup100k_brute.json" 2>/dev/null; echo "bench soup100k brute rc=$?"
 fi
 echo done

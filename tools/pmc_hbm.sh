@@ -8,7 +8,7 @@ tag="$1"; shift
 out="gpurun_out/pmc_$tag"
 mkdir -p "$out"
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/fetch" -- python3 bench.py --no-cpu-baseline "$@" > "$out/bench_fetch.json" 2> "$out/fetch.err"
+rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/fetch" -- python3 bench.py --full --no-cpu-baseline "$@" > "$out/bench_fetch.json" 2> "$out/fetch.err"
 echo "fetch rc=$?"
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$out/write" -- python3 bench.py --no-cpu-baseline "$@" > "$out/bench_write.json" 2> "$out/write.err"
+rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$out/write" -- python3 bench.py --full --no-cpu-baseline "$@" > "$out/bench_write.json" 2> "$out/write.err"
 echo "write rc=$?"
