@@ -1,0 +1,645 @@
+// binned.cpp -- the binned ray tracer's host side: binning passes (selection, pairs, sort, offsets), the light-cube tables (the
+// shared cache, or a frame's own pass for lights that move), the tile order, and the trace kernel over them.
+#include "capi.hpp"
+
+namespace mirt {
+
+// ---- binned ray tracing ---------------------------------------------------------------------------------------------
+
+// Makes room for `cap` (bin, triangle) pairs in a stream's pair list, its sorted copy and the sort's scratch.
+int ensure_pairs(RtScratch &S, size_t cap)
+{
+    int r;
+    if ((r = dev_realloc(&S.d_entries, cap)) || (r = dev_realloc(&S.d_pair_keys, cap)) || (r = dev_realloc(&S.d_pair_vals, cap)) ||
+        (r = dev_realloc(&S.d_sorted_keys, cap)) || (r = dev_realloc(&S.d_tmp_vals, cap))) { S.cap_entries = 0; return r; }
+    S.cap_entries = (uint32_t)cap;
+    return MIRT_OK;
+}
+
+// Most sort keys (bin * depth shells + shell) one binning pass may use: the two-level counting sort keeps one LDS counter per
+// bucket of at most 1024 keys (bin_bucket_sort.hip).  The callers choose their grids and shell counts to stay below it.
+constexpr uint32_t BIN_MAX_KEYS = BUCKET_SORT_MAX_BUCKETS * 1024u - 1u;
+
+// Picks up the pair count an earlier frame of the stream has published (pinned word + event), if it has landed.
+void poll_pair_count(RtScratch &S)
+{
+    if (S.count_pending && hipEventQuery(S.ev_count) == hipSuccess) {
+        S.known_pairs = *S.h_count; S.have_known = true; S.count_pending = false;
+    }
+    (void)hipGetLastError();                                 // (hipErrorNotReady of the query is not an error)
+}
+
+// One binning pass on g.stream: (key, triangle) pairs of `bs`' frames into S' pair list, ordered by key into S.d_entries /
+// S.d_sorted_keys, offsets into bin_off.  `counter` (device, zeroed by the caller's previous kernel) receives the pair
+// count.  The list is sized from a count only the device knows: when `fresh` it is read back (4 bytes + one sync of this
+// stream) and the pass repeated if the list was too small; otherwise *npairs, the count of the identical pass before, holds.
+// A pass that may not read back (`may_guess`) sizes the list from the count an earlier pass published and publishes its own;
+// a list that turns out too small makes the frame's kernels take the brute-force path (k_rt_trace2) and the NEXT pass grow it.
+int bin_pass(RtScratch &S, BinSet bs, const OriginRow *cam_tab, const OriginRow *light_tab, uint32_t *counter, uint32_t *bin_off,
+             bool fresh, uint32_t *npairs, bool may_guess = false)
+{
+    int rc;
+    poll_pair_count(S);                                      // a count an earlier frame left behind?
+    // A pass identical to the one before it (same view, same scene) normally reuses that pass's count without looking; but if
+    // that pass was itself a guess and its published count shows the list was too small, the frame fell back to brute force
+    // and so would every later frame of this view: treat it as fresh again so that the list grows.
+    if (!fresh && may_guess && S.have_known && S.known_pairs > S.cap_used) fresh = true;
+    const bool guess = fresh && may_guess && S.have_known;
+    if (!S.d_entries || !S.cap_entries) {
+        // first capacity of the pair list (grown on demand below); MIRT_BIN_INITIAL_PAIRS lets a test start small
+        static const size_t initial = [] { const long v = env_int("MIRT_BIN_INITIAL_PAIRS", 0); return v > 0 ? (size_t)v : (size_t)1 << 20; }();
+        if ((rc = ensure_pairs(S, initial))) return rc;
+    }
+    if (bs.nbins > BIN_MAX_KEYS) return fail(MIRT_ERR_INVALID_ARGUMENT, "binning: %u sort keys exceed the %u the bucket sort holds", bs.nbins, BIN_MAX_KEYS);
+    // workgroups striding over the (256-triangle chunk, frame) work items: 8 per CU (52 KiB of LDS and 512 threads each, 3 resident; 1 M
+    // triangles at 8K: 4.06 -> 3.53 ms per frame against 3 per CU)
+    bs.chunk_tris = 256;                                // (64 measured slower on the 100 k soup: 86 vs 74 us for the whole binning, more flushes)
+    const dim3 bin_grid((unsigned)std::min<long long>((long long)((g.n + bs.chunk_tris - 1) / bs.chunk_tris) * bs.nframes, (long long)g.cu_count * 8));
+    bs.counters = counter;
+    // order the pairs by key with the two-level counting sort (bin_bucket_sort.hip: k_bin_pairs counts the pairs per bucket,
+    // two more launches sort)
+    const uint32_t nbuckets = bucket_sort_buckets(bs.nbins);
+    if (nbuckets + 1 > S.cap_buckets) {
+        S.cap_buckets = 0;
+        if ((rc = dev_realloc(&S.d_bucket, (size_t)3 * (nbuckets + 1)))) return rc;
+        HIP_TRY(hipMemsetAsync(S.d_bucket, 0, sizeof(uint32_t) * 3 * (nbuckets + 1), g.stream));
+        S.cap_buckets = nbuckets + 1;
+        S.bucket_dirty = false;
+    }
+    uint32_t *bcnt = S.d_bucket, *bbase = S.d_bucket + S.cap_buckets, *bcur = S.d_bucket + 2 * (size_t)S.cap_buckets;
+    bs.bucket_cnt = bcnt; bs.nbuckets = nbuckets; bs.bucket_shift = bucket_sort_shift(bs.nbins);
+    const size_t bin_lds = (size_t)nbuckets * sizeof(uint32_t);
+    {   // k_bin_pairs: ~52 KB of static LDS + up to 32 KB of bucket counters: past the 64 KB a launch may use by default
+        static const bool once = [] {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bin_pairs<512>), hipFuncAttributeMaxDynamicSharedMemorySize, 48 * 1024);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bin_pairs<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 48 * 1024);
+            return true; }();
+        (void)once;
+    }
+    // workgroups of 256 threads where the frame's kernels overlap with its neighbours' -- three or four frames in flight, a scene small
+    // enough for that to matter --, of 512 for the large scenes and for the frame that runs alone, whose latency they serve (rt_binned.hip)
+    static const int bin_wg_env = (int)env_int("MIRT_BIN_WG", 0);
+    const int bin_wg = (bin_wg_env == 256 || bin_wg_env == 512) ? bin_wg_env : ((g.n < 400000 && g.in_flight >= 3) ? 256 : 512);
+    if (guess) {
+        // room for half as many pairs again as the last frame seen produced; growing needs this stream idle (rare)
+        const size_t want = (size_t)S.known_pairs + S.known_pairs / 2 + 4096;
+        if (want > S.cap_entries) {
+            HIP_TRY(hipStreamSynchronize(g.stream));
+            if ((rc = ensure_pairs(S, want + want / 4))) return rc;
+        }
+    }
+    bool publish_count = false;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        // MIRT_TEST_PAIR_CAP (tests only): a guessed list pretends to be this small, so that the overflow path runs
+        static const uint32_t test_cap = [] { const long v = env_int("MIRT_TEST_PAIR_CAP", 0); return v > 0 ? (uint32_t)v : 0u; }();
+        S.cap_used = (guess && test_cap && test_cap < S.cap_entries) ? test_cap : S.cap_entries;
+        BinPairs pairs = { S.d_pair_keys, S.d_pair_vals, S.cap_used };
+        bs.entries = S.d_entries; bs.cap_entries = S.cap_used;
+        if (attempt) HIP_TRY(hipMemsetAsync(counter, 0, 4, g.stream));
+        if (attempt || S.bucket_dirty) HIP_TRY(hipMemsetAsync(S.d_bucket, 0, sizeof(uint32_t) * 3 * (size_t)S.cap_buckets, g.stream));
+        S.bucket_dirty = true;                               // bucket counts pending until k_bs_local has consumed them
+        if (bin_wg == 256) hipLaunchKernelGGL(k_bin_pairs<256>, bin_grid, dim3(256), bin_lds, g.stream, g.d_tris, cam_tab, light_tab, g.n, bs, pairs);
+        else hipLaunchKernelGGL(k_bin_pairs<512>, bin_grid, dim3(512), bin_lds, g.stream, g.d_tris, cam_tab, light_tab, g.n, bs, pairs);
+        if (!fresh) break;
+        if (guess) {
+            // no sync: k_bs_scatter stores the count into a pinned word behind the kernel and a later frame picks it up
+            if (!S.h_count) {
+                HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&S.h_count), 64, hipHostMallocDefault));
+                HIP_TRY(hipEventCreateWithFlags(&S.ev_count, hipEventDisableTiming));
+            }
+            if (!S.count_pending) publish_count = true;
+            *npairs = S.known_pairs;
+            break;
+        }
+        uint32_t total = 0;
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        HIP_TRY(hipMemcpy(&total, counter, 4, hipMemcpyDeviceToHost));
+        *npairs = total;
+        S.known_pairs = total; S.have_known = true;
+        S.count_pending = false;                             // (a count still on its way belongs to an earlier pass, maybe of another kind)
+        if (total <= S.cap_entries) break;
+        if (attempt == 1) return fail(MIRT_ERR_HIP, "binning produced %u pairs twice with room for %u", total, S.cap_entries);
+        if ((rc = ensure_pairs(S, (size_t)total + total / 8 + 4096))) return rc;
+    }
+#ifdef MIRT_BIN_STATS
+    if (fresh) {
+        uint32_t c[16];
+        (void)hipMemcpy(c, counter, 64, hipMemcpyDeviceToHost);
+        fprintf(stderr, "[mirt bin stats] flattened tests=%u max per work item=%u direct items=%u | huge: box valid=%u no box=%u (camera frame %u)\n", c[8], c[9], c[10], c[11], c[12], c[14]);
+        fprintf(stderr, "[mirt bin stats] tris=%d frames=%d  pairs=%u  bins=%u | large items walked=%u level-1 rounds=%u level-2 steps=%u pairs=%u max steps/item=%u items>100 steps=%u\n",
+                g.n, bs.nframes, *npairs, bs.nbins, c[2], c[3], c[4], c[5], c[6], c[7]);
+        (void)hipMemset(counter + 2, 0, 56);
+    }
+#endif
+    uint32_t *count_out = nullptr;
+    if (publish_count) HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&count_out), S.h_count, 0));
+    HIP_TRY(bucket_sort_pairs(S.d_pair_keys, S.d_pair_vals, counter, S.cap_used, *npairs, bs.nbins, S.d_sorted_keys, S.d_tmp_vals,
+                              bcnt, bbase, bcur, bin_off, S.d_entries, g.cu_count, g.stream, count_out));
+    S.bucket_dirty = false;                                  // k_bs_local leaves the counts and cursors zero
+    // (the event that tells a later frame the count has landed is recorded by the caller BEHIND the frame's trace kernel: an event
+    // record between two kernels of the chain is a barrier packet of its own, ~5 us of the single frame's latency)
+    if (publish_count) S.count_event_due = true;
+    return MIRT_OK;
+}
+
+// Key of what the light-cube bins depend on: the scene and the light positions.
+uint64_t light_key_of(const float *origins, int nlights)
+{
+    uint64_t key = 0xcbf29ce484222325ull ^ g.scene_version;
+    auto mix = [&](const void *p, size_t nb) { const unsigned char *b = (const unsigned char *)p; for (size_t i = 0; i < nb; i++) { key ^= b[i]; key *= 0x100000001b3ull; } };
+    mix(origins + 3, sizeof(float) * 3 * nlights); mix(&nlights, 4); mix(&g.n, 4);
+    return key;
+}
+
+// Nearest and farthest distance from `pos` to the scene's bounding box: the range the depth shells of a ray family divide.
+bool shell_range(const float *pos, double *dn, double *df)
+{
+    double n2 = 0.0, f2 = 0.0;
+    for (int c = 0; c < 3; c++) {
+        const double p = pos[c], lo = g.bbox_lo[c], hi = g.bbox_hi[c];
+        const double near = p < lo ? lo - p : (p > hi ? p - hi : 0.0), far = std::max(std::fabs(p - lo), std::fabs(p - hi));
+        n2 += near * near; f2 += far * far;
+    }
+    *dn = std::sqrt(n2); *df = std::sqrt(f2);
+    return std::isfinite(*dn) && std::isfinite(*df) && *df > *dn;
+}
+
+// Frame descriptors of the light cubes: six faces of B x B bins around every light position, every bin's list ordered in
+// `shells` depth shells of the candidates' `near` bound (sort key = (base + bin) * shells + shell; `base_bins` = where light 0's
+// face 0 starts, in bins of `shells` keys).  A shadow ray walks only the shells up to the one its 0.99 r falls into (k_rt_trace2).
+void fill_light_frames(BinFrameDesc *frames, const RtFrame &f, int nlights, int cube_bins, int shells, uint32_t base_bins)
+{
+    memset(frames, 0, sizeof(BinFrameDesc) * 6 * nlights);
+    for (int k = 0; k < nlights; k++) {
+        double dn = 0.0, df = 0.0;
+        const bool okr = shell_range(f.lpos[k], &dn, &df);
+        for (int face = 0; face < 6; face++) {
+            BinFrameDesc &d = frames[k * 6 + face];
+            const int ax = face >> 1;
+            d.P0[ax] = (face & 1) ? -1.0f : 1.0f;         // negD ~ s*e_k + u*e_(k+1) + v*e_(k+2)
+            d.Pu[(ax + 1) % 3] = 1.0f;
+            d.Pv[(ax + 2) % 3] = 1.0f;
+            d.rw[ax] = d.P0[ax]; d.ru[(ax + 1) % 3] = 1.0f; d.rv[(ax + 2) % 3] = 1.0f;   // g = m*(s e_k + u e_k1 + v e_k2)
+            memcpy(d.S, f.lpos[k], 12);                       // light position k (jittered sample with soft shadows)
+            d.dmax = 2.0f;
+            d.ulo = -1.0f; d.vlo = -1.0f; d.du = 2.0f / (float)cube_bins; d.dv = 2.0f / (float)cube_bins;
+            d.pad_lo = -3.814697265625e-06f; d.pad_hi = 3.814697265625e-06f;
+            d.nbu = cube_bins; d.nbv = cube_bins; d.j0 = 0; d.j1 = cube_bins;
+            d.base = base_bins; d.tab = 1 + k;
+            // every face of every light carries `shells` keys per bin (the key layout needs one count for all); a light whose
+            // range is degenerate puts everything into shell 0
+            d.nshell = shells;
+            d.shell_d0 = (float)dn;
+            d.shell_iw = okr ? (float)(shells / (df - dn)) : 0.0f;
+            base_bins += (uint32_t)(cube_bins * cube_bins);
+        }
+    }
+}
+
+// Depth shells per light-cube bin: as many as the sort's key space allows, at most 16 (a bin's list grows with the square of
+// the distance from the light; 16 shells leave a ray at a quarter of the scene's depth ~2 % of it).
+int light_shells_for(int nlights, int cube_bins, uint32_t keys_in_front)
+{
+    static const int env = (int)env_int("MIRT_LIGHT_SHELLS", 0);
+    const long long bins = 6ll * cube_bins * cube_bins * std::max(nlights, 1);
+    int ns = (env >= 1 && env <= 64) ? env : 16;
+    while (ns > 1 && bins * ns + keys_in_front + 64 > (long long)BIN_MAX_KEYS) ns >>= 1;
+    return ns;
+}
+
+constexpr size_t LIGHT_COUNTER_BYTES = sizeof(uint32_t) * (128 + 6 * MIRT_MAX_LIGHTS);
+// Room for the face lists of `nlights` light cubes (k_select_faces) in a stream's LIGHT scratch set; the stream must be idle when they grow.
+int ensure_face_lists(RtScratch &S, int nlights)
+{
+    int rc;
+    if (!S.d_bin_counters) {
+        // the light pass's counters and the face lists' lengths in ONE block (a pass zeroes it with one fill): words 0..127 as in the
+        // camera's block, 128.. the face counts
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_bin_counters), LIGHT_COUNTER_BYTES));
+        HIP_TRY(hipMemsetAsync(S.d_bin_counters, 0, LIGHT_COUNTER_BYTES, g.stream));
+        S.d_face_counts = S.d_bin_counters + 128;
+    }
+    const size_t want = (size_t)6 * (size_t)nlights * (size_t)g.n;
+    if (want > S.cap_face_sel) {
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        S.cap_face_sel = 0;
+        if ((rc = dev_realloc(&S.d_face_sel, want))) return rc;
+        S.cap_face_sel = want;
+    }
+    return MIRT_OK;
+}
+
+// The SHARED light-cube bins and their expanded rows, for lights that stand still: built on g.stream as a barrier call -- the
+// frames of both streams read the tables -- whenever the scene, a light position or the grid differs from what is held.  (Lights
+// that just moved do not come here: binned_pass bins their cubes together with the camera frame, on the frame's own stream.)
+int light_cache_ensure(RtScratch &S, const RtFrame &f, const float *origins, int nlights, int cube_bins)
+{
+    int rc;
+    LightCache &C = g.lc;
+    const uint64_t key = light_key_of(origins, nlights);
+    if (C.valid && C.key == key && C.cube_bins == cube_bins) return MIRT_OK;
+    C.valid = false;
+    for (int o = 0; o < g.in_flight; o++)                  // frames of the other streams may still read the old tables
+        if (o != g.si) {
+            HIP_TRY(hipEventRecord(g.streams[o].ev_order, g.streams[o].stream));
+            HIP_TRY(hipStreamWaitEvent(g.stream, g.streams[o].ev_order, 0));
+        }
+    const int shells = light_shells_for(nlights, cube_bins, 0u);
+    const uint32_t per_light = 6u * (uint32_t)(cube_bins * cube_bins) * (uint32_t)shells, nkeys = per_light * (uint32_t)nlights;
+    if ((size_t)nlights * g.n > C.cap_tab) {
+        C.cap_tab = 0;
+        if ((rc = dev_realloc(&C.d_light_tab, (size_t)nlights * g.n))) return rc;
+        C.cap_tab = (size_t)nlights * g.n;
+    }
+    if (nkeys + 1 > C.cap_bins) {
+        C.cap_bins = 0;
+        if ((rc = dev_realloc(&C.d_off, (size_t)nkeys + 1))) return rc;
+        C.cap_bins = nkeys + 1;
+    }
+    if (!C.d_frames) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&C.d_frames), sizeof(BinFrameDesc) * 6 * MIRT_MAX_LIGHTS));
+    if (!C.d_origins) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&C.d_origins), sizeof(float) * 3 * (1 + MIRT_MAX_LIGHTS)));
+    if (!C.d_counter) { HIP_TRY(hipMalloc(reinterpret_cast<void **>(&C.d_counter), 512)); HIP_TRY(hipMemsetAsync(C.d_counter, 0, 512, g.stream)); }   // (k_prep_origin zeroes words 0 and 16..79 of a pass's counter block)   // (ON the stream: see zero-fill note at S.d_bin_counters)
+    C.nbins = nkeys;
+    C.nrows = 0;
+    C.shells = shells;
+    if (nlights > 0) {
+        BinFrameDesc frames[6 * MIRT_MAX_LIGHTS];
+        fill_light_frames(frames, f, nlights, cube_bins, shells, 0u);
+        HIP_TRY(upload_small(C.d_frames, frames, sizeof(BinFrameDesc) * 6 * nlights, g.stream));
+        HIP_TRY(upload_small(C.d_origins, origins, sizeof(float) * 3 * (1 + nlights), g.stream));
+        // the lights' origin rows, and per face the triangles it can see (k_select_faces); the build's pair counter is zeroed on the way
+        if ((rc = ensure_face_lists(S, nlights))) return rc;
+        HIP_TRY(hipMemsetAsync(S.d_face_counts, 0, sizeof(uint32_t) * 6 * nlights, g.stream));
+        HIP_TRY(hipMemsetAsync(C.d_counter, 0, 512, g.stream));
+        S.count_event_due = false;
+        hipLaunchKernelGGL(k_select_faces, dim3((unsigned)std::min<long long>(((long long)g.n + 1023) / 1024, (long long)g.cu_count), nlights), dim3(1024), 0, g.stream,
+                           g.d_tris, g.n, C.d_origins, C.d_frames, C.d_light_tab, S.d_face_sel, (uint32_t)g.n, S.d_face_counts);
+        BinSet bs;
+        memset(&bs, 0, sizeof bs);
+        bs.frames = C.d_frames; bs.nframes = 6 * nlights; bs.nbins = nkeys; bs.bin_off = C.d_off;
+        bs.face_lists = S.d_face_sel; bs.face_counts = S.d_face_counts; bs.face_stride = (uint32_t)g.n;
+        uint32_t npairs = 0;
+        if ((rc = bin_pass(S, bs, nullptr, C.d_light_tab, C.d_counter, C.d_off, true, &npairs))) return rc;
+        S.count_event_due = false;                           // (a fresh pass without a guess reads its count back: nothing was published)
+        if (npairs > C.cap_rows) {
+            C.cap_rows = 0;
+            if ((rc = dev_realloc(&C.d_rows, (size_t)npairs + npairs / 8 + 1024))) return rc;
+            if ((rc = dev_realloc(&C.d_row_tri, (size_t)npairs + npairs / 8 + 1024))) return rc;
+            C.cap_rows = npairs + npairs / 8 + 1024;
+        }
+        C.nrows = npairs;
+        if (npairs)
+            hipLaunchKernelGGL(k_expand_light_rows, dim3((unsigned)std::min<uint32_t>((npairs + 255) / 256, 4096u)), dim3(256), 0, g.stream,
+                               C.d_off, S.d_entries, nlights, per_light, C.d_light_tab, g.n, C.d_rows, (const uint32_t *)nullptr, 0u, C.d_row_tri);
+        HIP_TRY(hipGetLastError());
+        S.bin_key_valid = false;                             // the stream's pair list now holds the light pass
+        S.last_bin_mode = -1;
+    } else {
+        HIP_TRY(hipMemsetAsync(C.d_off, 0, 4, g.stream));
+    }
+    if (g.in_flight > 1) {                                   // later frames of the other streams wait for the build
+        HIP_TRY(hipEventRecord(g.cur().ev_order, g.stream));
+        for (int o = 0; o < g.in_flight; o++)
+            if (o != g.si) HIP_TRY(hipStreamWaitEvent(g.streams[o].stream, g.cur().ev_order, 0));
+    }
+    C.key = key;
+    C.cube_bins = cube_bins;
+    C.valid = true;
+    return MIRT_OK;
+}
+
+// Depth shells of the camera bins for a frame of `tiles` bins (the tiles' lists come out of the sort roughly front to back).
+int camera_shells_for(long long tiles)
+{
+    static const int shells_env = (int)env_int("MIRT_CAM_SHELLS", 0);
+    int ns = (int)std::min<long long>(8, std::max<long long>(1, (4ll << 20) / std::max<long long>(tiles, 1)));
+    if (shells_env >= 1 && shells_env <= 64) ns = shells_env;
+    while (ns > 1 && tiles * ns + 64 > (long long)BIN_MAX_KEYS) ns >>= 1;
+    return ns;
+}
+
+// Can a frame of this size be binned at all?  (one sort key per 8 x 8-pixel tile at least)
+bool frame_fits_binning(int W, int H)
+{
+    const long long tiles = (long long)((W + BIN_TILE - 1) / BIN_TILE) * ((H + BIN_TILE - 1) / BIN_TILE);
+    return tiles + 64 <= (long long)BIN_MAX_KEYS;
+}
+
+// A binned frame: camera origin rows, camera-tile bins, trace.  The light-cube bins come from the shared cache when the lights
+// stand still -- the only per-frame binning is then the camera's -- or, for lights that moved within the last
+// LIGHT_STABLE_FRAMES frames, from this frame's own pass: their cubes (CUBE_BINS_MIN bins per side) are binned TOGETHER with the
+// camera frame into the stream's pair list and expanded into the stream's rows.  Nothing of that is shared, so a moving light
+// needs no barrier between the streams and no host sync (the list is sized like the camera's: from an earlier frame's count).
+// The reference moves the light with keys as readily as the camera (raytracer.cpp:152-162).
+constexpr int LIGHT_STABLE_FRAMES = 4;
+
+
+// The cubes of lights that MOVE, binned by the frame itself (64 x 64 bins per face): a pass of its own in the stream's light
+// scratch set L -- the lights' origin rows and per-face selection lists (k_select_faces), pairs, sort, expanded rows --, apart from
+// the camera's pass, so that each is kept while only the other one's inputs change: a light key with the camera at rest
+// (raytracer.cpp:152-162, 385-537) re-bins the cubes and nothing else; the camera moving under lights that have not settled into the
+// shared cube yet re-bins the camera frame and nothing else.  *kept: the pass was not run.
+int transient_light_pass(RtScratch &L, const RtFrame &f, const float *origins, int nlights, int cube_bins, int tshells, uint32_t per_light, uint64_t lkey, bool *kept,
+                         unsigned long long *zero_hits /* nullable: the frame's hit counters, zeroed by the pass's first launch when it runs */)
+{
+    int rc;
+    *kept = false;
+    uint64_t key = 0xcbf29ce484222325ull ^ g.scene_version;
+    {
+        auto mix = [&](const void *p, size_t nb) { const unsigned char *b = (const unsigned char *)p; for (size_t i = 0; i < nb; i++) { key ^= b[i]; key *= 0x100000001b3ull; } };
+        mix(&lkey, 8); mix(&cube_bins, 4); mix(&tshells, 4); mix(&g.n, 4); mix(&nlights, 4);
+    }
+    poll_pair_count(L);
+    bool fresh = !L.bin_key_valid || L.bin_key != key;
+    const bool may_guess = L.last_bin_mode == nlights;
+    if (!fresh && L.have_known && L.known_pairs > L.cap_used) fresh = true;   // (a kept list that turned out too small is rebuilt, so that it grows)
+    static const bool reuse_off = env_int("MIRT_BIN_REUSE", 1) == 0;
+    if (!fresh && !reuse_off) { *kept = true; return MIRT_OK; }
+    if ((rc = ensure_face_lists(L, nlights))) return rc;
+    if (nlights > L.light_tab_lights || L.light_tab_n != g.n) {
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        L.light_tab_lights = 0;
+        if ((rc = dev_realloc(&L.d_light_tab, (size_t)nlights * g.n))) return rc;
+        L.light_tab_lights = nlights;
+        L.light_tab_n = g.n;
+    }
+    const uint32_t nkeys = per_light * (uint32_t)nlights;
+    if (nkeys + 1 > L.cap_bins) {
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        L.cap_bins = 0;
+        if ((rc = dev_realloc(&L.d_bin_off, (size_t)nkeys + 1))) return rc;
+        L.cap_bins = nkeys + 1;
+    }
+    // frame descriptors of the cubes and the origins in ONE buffer, one upload: [6 * nlights descriptors | (1 + nlights) x 3 floats]
+    if (!L.d_frames) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&L.d_frames), sizeof(BinFrameDesc) * (6 * MIRT_MAX_LIGHTS) + sizeof(float) * 3 * (1 + MIRT_MAX_LIGHTS)));
+    struct { BinFrameDesc frames[6 * MIRT_MAX_LIGHTS]; float origins[3 * (1 + MIRT_MAX_LIGHTS)]; } up;
+    static_assert(sizeof(BinFrameDesc) % 4 == 0, "descriptors are uploaded as words");
+    fill_light_frames(up.frames, f, nlights, cube_bins, tshells, 0u);
+    float *d_origins = reinterpret_cast<float *>(L.d_frames + 6 * nlights);
+    memcpy(reinterpret_cast<char *>(up.frames + 6 * nlights), origins, sizeof(float) * 3 * (1 + nlights));      // (right behind the descriptors in use)
+    // (the same launch zeroes the pass's pair counter and the face lists' lengths)
+    const ZeroJob zj = { L.d_bin_counters, (int)(LIGHT_COUNTER_BYTES / 4), reinterpret_cast<uint32_t *>(zero_hits), zero_hits ? 2 * HIT_SHARDS * HIT_SHARD_STRIDE : 0 };
+    HIP_TRY(upload_small(L.d_frames, &up, sizeof(BinFrameDesc) * 6 * nlights + sizeof(float) * 3 * (1 + nlights), g.stream, &zj));
+    hipLaunchKernelGGL(k_select_faces, dim3((unsigned)std::min<long long>(((long long)g.n + 1023) / 1024, (long long)g.cu_count), nlights), dim3(1024), 0, g.stream,
+                       g.d_tris, g.n, d_origins, L.d_frames, L.d_light_tab, L.d_face_sel, (uint32_t)g.n, L.d_face_counts);
+    BinSet bs;
+    memset(&bs, 0, sizeof bs);
+    bs.frames = L.d_frames; bs.nframes = 6 * nlights; bs.nbins = nkeys; bs.bin_off = L.d_bin_off;
+    bs.face_lists = L.d_face_sel; bs.face_counts = L.d_face_counts; bs.face_stride = (uint32_t)g.n;
+    if ((rc = bin_pass(L, bs, nullptr, L.d_light_tab, L.d_bin_counters, L.d_bin_off, true, &L.bin_entries, may_guess))) return rc;
+    L.last_bin_mode = nlights;
+    L.bin_key = key;
+    L.bin_key_valid = true;
+    if (L.cap_light_rows < L.cap_entries) {                  // one row per pair at most; grown with the pair list (rare)
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        L.cap_light_rows = 0;
+        if ((rc = dev_realloc(&L.d_light_rows, (size_t)L.cap_entries))) return rc;
+        L.cap_light_rows = L.cap_entries;
+    }
+    const uint32_t expect = std::max<uint32_t>(L.bin_entries, 1u);
+    hipLaunchKernelGGL(k_expand_light_rows, dim3((unsigned)std::min<uint32_t>((expect + 255) / 256, 4096u)), dim3(256), 0, g.stream,
+                       L.d_bin_off, L.d_entries, nlights, per_light, L.d_light_tab, g.n, L.d_light_rows, L.d_bin_counters, L.cap_used, (uint32_t *)nullptr);
+    return MIRT_OK;
+}
+
+// The binning pass of a binned frame, up to the trace kernel: the light-cube tables (the shared cache, or this frame's own pass on
+// the side stream), then the camera's selection, binning and tile order -- or nothing at all when the stream still holds the pass.
+int binned_pass(const RtFrame &f, const mirt_view *view, RtScratch &S, RtScratch &L, const float *origins, int nlights, int y0, int y1, BinnedPass *bp)
+{
+    int rc;
+    g.stats.mode_used = MIRT_RT_BINNED;
+    g.stats_sel_count = nullptr;
+    // light-cube resolution: bins per face side.  Finer grids shorten the shadow lists; the shared bins are built once per
+    // (scene, lights), not per frame, so what they cost is memory (48 bytes per (bin, triangle) pair) and ~1 ms of build for
+    // 100 k triangles.  Measured on the 100 k soup at 1080p (round 2's trace kernel, lists not yet ordered by depth): 64: 153 us,
+    // 128: 125 us, 256: 105 us.  MIRT_CUBE_BINS=64|128|256 fixes the grid (and keeps every frame on the shared cache).
+    static const int cube_override = (int)env_int("MIRT_CUBE_BINS", 0);
+    int fine_bins = g.n < 2000 ? CUBE_BINS_MIN : (g.n < 20000 ? 2 * CUBE_BINS_MIN : 4 * CUBE_BINS_MIN);
+    const bool fixed_grid = cube_override == 64 || cube_override == 128 || cube_override == 256;
+    if (fixed_grid) fine_bins = cube_override;
+    // (many light positions -- 16 soft-shadow samples of two lights -- at the finest grid are more keys than one sort pass holds)
+    while (fine_bins > CUBE_BINS_MIN && 6ll * fine_bins * fine_bins * nlights * 4 > (long long)BIN_MAX_KEYS) fine_bins /= 2;
+
+    const uint64_t lkey = light_key_of(origins, nlights);
+    if (g.lc.track_key == lkey) g.lc.stable++;
+    else { g.lc.track_key = lkey; g.lc.stable = 0; }
+    const bool cached = g.lc.valid && g.lc.key == lkey && g.lc.cube_bins == fine_bins;
+    const bool transient = nlights > 0 && !fixed_grid && !cached && g.lc.stable < LIGHT_STABLE_FRAMES;
+
+    k_begin(MIRT_K_BIN);
+    if (!transient && (rc = light_cache_ensure(L, f, origins, nlights, fine_bins))) return rc;   // (in the light pass's scratch: the camera's tables stay)
+    const int cube_bins = transient ? CUBE_BINS_MIN : fine_bins;
+
+    BinSet bs;
+    memset(&bs, 0, sizeof bs);
+    bs.frame0 = make_camera_frame(view, y0, y1, g.aa);
+    bs.frames = nullptr; bs.nframes = 1;
+    // The camera's sort keys are LOCAL to the rows the call renders: tile (i, j) of a band that starts at tile row j0 has bin
+    // (j - j0) * nbu + i (the frame's `base` is -j0 * nbu, modulo 2^32), so a band of a sharded frame sorts an eighth of the keys
+    // -- buckets an eighth as wide, spread over all the sort's workgroups -- and writes an eighth of the offsets.  (With the whole
+    // frame's key space a band's pairs sat in an eighth of the buckets: k_bs_local took 94 us for a middle band of the 1 M-triangle
+    // frame at 8K against 112 us for the whole frame.)  The kernels that index the offsets by the frame's tile number get the
+    // array's base shifted accordingly (cam_off below).
+    const int band_tile_rows = bs.frame0.j1 - bs.frame0.j0;
+    const uint32_t key_shift_tiles = (uint32_t)bs.frame0.j0 * (uint32_t)bs.frame0.nbu;
+    bs.frame0.base = 0u - key_shift_tiles;
+    {
+        // depth shells: the tiles' lists come out of the sort roughly front to back (key = bin * shells + shell of the
+        // candidate's `near` bound, uniform steps between the nearest and the farthest point of the scene's box)
+        const int ns = camera_shells_for((long long)bs.frame0.nbu * band_tile_rows);
+        double dn = 0.0, df = 0.0;
+        const bool okr = shell_range(view->pos, &dn, &df);
+        bs.frame0.nshell = okr ? ns : 1;
+        bs.frame0.shell_d0 = (float)dn;
+        bs.frame0.shell_iw = okr ? (float)(ns / (df - dn)) : 0.0f;
+    }
+    const uint32_t cam_keys = (uint32_t)bs.frame0.nbu * (uint32_t)band_tile_rows * (uint32_t)bs.frame0.nshell;
+    // this frame's own light cubes (moving lights) are a pass of their own, with keys of their own (below)
+    const int tshells = transient ? light_shells_for(nlights, cube_bins, 0u) : 1;
+    const uint32_t per_light = 6u * (uint32_t)(cube_bins * cube_bins) * (uint32_t)tshells;
+    bs.nbins = cam_keys;
+    if (bs.nbins + 1 > S.cap_bins) {
+        const size_t cap = (size_t)bs.nbins + 1;
+        HIP_TRY(hipStreamSynchronize(g.stream));             // (a frame of this stream may still read the old array)
+        if ((rc = dev_realloc(&S.d_bin_off, cap))) { S.cap_bins = 0; return rc; }
+        S.cap_bins = (uint32_t)cap;
+        S.bin_key_valid = false;
+    }
+    // Zero-fill ON the stream that uses the buffer: hipMemset runs on the null stream, which the library's non-blocking streams
+    // are not ordered with -- with several processes on one device (three ranks rehearsing a sharded run) such a fill has been seen
+    // to land AFTER the first kernels of g.stream had started counting, which cut the pair count short (a light cube built from
+    // it kept wrong shadows until the lights moved; a camera pass failed with "produced N pairs twice").
+    if (!S.d_bin_counters) { HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_bin_counters), 512)); HIP_TRY(hipMemsetAsync(S.d_bin_counters, 0, 512, g.stream)); }
+    if (S.sel_n != g.n) {
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        S.sel_n = 0;
+        if ((rc = dev_realloc(&S.d_sel, (size_t)g.n))) return rc;
+        S.sel_n = g.n;
+        S.bin_key_valid = false;
+    }
+    bs.bin_off = S.d_bin_off;
+
+    uint64_t key = 0xcbf29ce484222325ull ^ g.scene_version;
+    {
+        auto mix = [&](const void *p, size_t nb) { const unsigned char *b = (const unsigned char *)p; for (size_t i = 0; i < nb; i++) { key ^= b[i]; key *= 0x100000001b3ull; } };
+        mix(view, sizeof *view); mix(&y0, 4); mix(&y1, 4); mix(&g.n, 4); mix(&g.aa, 4);
+    }
+    const int bin_mode = 0;                                  // (the camera's pass bins the camera frame alone)
+    StreamState &ss = g.cur();
+    ss.hits_clean[ss.hits_tog] = false;
+    if (!S.d_frames) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_frames), sizeof(BinFrameDesc) * (1 + 6 * MIRT_MAX_LIGHTS)));
+    // The pair count is read back (4 bytes + one sync of this stream) only when the inputs that determine it changed AND no
+    // count of an earlier pass of the same kind is at hand (a camera-only count says nothing about camera + light cubes).
+    // When NOTHING the pass depends on has changed since this stream's last pass -- the view stands still while a light key, a
+    // toggle or nothing at all asks for a frame (raytracer.cpp:385-537 set isUpdated without touching cameraPos / yaw) -- the
+    // stream still holds that pass's tables: origin rows, selection, sorted lists, offsets, tile order, and with them the rows
+    // of lights binned by the frame.  The frame then starts at the trace kernel.  (A kept pass whose list turned out too small
+    // -- its published count says so -- is redone, so that the list grows: bin_pass.)
+    poll_pair_count(S);
+    bool fresh = !S.bin_key_valid || S.bin_key != key;
+    const bool may_guess = S.last_bin_mode == bin_mode;
+    if (!fresh && S.have_known && S.known_pairs > S.cap_used) fresh = true;
+    static const bool reuse_off = env_int("MIRT_BIN_REUSE", 1) == 0;
+    const bool reuse = !fresh && !reuse_off;
+    const uint32_t pairs_x = (uint32_t)((bs.frame0.nbu + 1) / 2);
+    uint32_t group_rows[ORDER_GROUPS] = { 0 };
+    for (int j = bs.frame0.j0; j < bs.frame0.j1; j++) group_rows[((uint32_t)j >> ORDER_STRIPE_SHIFT) & (ORDER_GROUPS - 1)]++;
+    const uint32_t order_seg = pairs_x * *std::max_element(group_rows, group_rows + ORDER_GROUPS);
+    const uint32_t *cam_off = S.d_bin_off - (size_t)key_shift_tiles * (size_t)bs.frame0.nshell;   // indexed by the FRAME's tile number
+    // The cubes of lights that moved within the last frames: a pass of their own (transient_light_pass), kept while the lights stand
+    // still.  When the camera's pass runs as well, the light pass goes FIRST and onto the stream's side stream: the two chains
+    // share nothing until the trace kernel and are each bound by the latency of their launches, so side by side they take the longer
+    // one's time instead of the sum (one frame in flight, camera and light moving: 0.268 ms one after the other, see
+    // profiles/r04_moving_light.txt for the figure side by side).  The side stream starts behind everything the main stream has
+    // queued (the previous frame's trace kernel reads the tables the pass rewrites) and is joined in front of this frame's.
+    bool lights_kept = false, forked = false;
+    if (transient) {
+        static const bool side_off = env_int("MIRT_LIGHT_SIDE_STREAM", 1) == 0;
+        hipStream_t main_stream = g.stream;
+        forked = !reuse && !side_off;
+        if (forked) {
+            HIP_TRY(hipEventRecord(ss.ev_fork, main_stream));
+            HIP_TRY(hipStreamWaitEvent(ss.aux, ss.ev_fork, 0));
+            g.stream = ss.aux;
+        }
+        // (with the camera's pass kept nothing else runs in front of the trace kernel: the light pass's first launch zeroes the hit counters too)
+        rc = transient_light_pass(L, f, origins, nlights, cube_bins, tshells, per_light, lkey, &lights_kept, reuse ? g.d_hits : nullptr);
+        g.stream = main_stream;
+        if (rc) return rc;
+        if (forked) HIP_TRY(hipEventRecord(ss.ev_join, ss.aux));
+    }
+    if (reuse) {
+        // (the first kernel of a pass zeroes the frame's hit counters on the way; here nothing runs in front of the trace kernel --
+        // unless the light pass has just run and done it)
+        if (!(transient && !lights_kept)) HIP_TRY(hipMemsetAsync(g.d_hits, 0, HIT_BYTES, g.stream));
+        g.stats.bins_reused = 1;
+    } else {
+        // first kernel of the frame: the camera's origin rows for the triangles the rows of this call can see, and their list
+        // (k_prep_select); it also zeroes the hit counters and the pass's counters
+        S.sel_parity ^= 1;
+        SelectOut so;
+        memset(&so, 0, sizeof so);
+        so.cam_tab = S.d_cam_tab; so.sel = S.d_sel;
+        so.sel_count = S.d_bin_counters + SEL_COUNT0 + S.sel_parity; so.sel_count_next = S.d_bin_counters + SEL_COUNT0 + (S.sel_parity ^ 1);
+        so.zero_hits = g.d_hits; so.zero_counter = S.d_bin_counters;
+        if ((rc = hist_prepare(S, bs.frame0, &so))) return rc;
+        // one workgroup of 1024 threads per CU: a workgroup reserves its slice of the list with ONE atomic (rt_binned.hip)
+        const unsigned sel_grid = (unsigned)std::min<long long>(((long long)g.n + 1023) / 1024, (long long)g.cu_count);
+        hipLaunchKernelGGL(k_prep_select, dim3(sel_grid), dim3(1024), 0, g.stream, g.d_tris, g.n, bs.frame0, so);
+        if ((rc = hist_publish(S))) return rc;
+        bs.sel = S.d_sel; bs.sel_count = so.sel_count;
+        g.stats_sel_count = so.sel_count;
+        if ((rc = bin_pass(S, bs, S.d_cam_tab, nullptr, S.d_bin_counters, S.d_bin_off, true, &S.bin_entries, may_guess))) return rc;
+        S.last_bin_mode = bin_mode;
+        S.bin_key = key;
+        S.bin_key_valid = true;
+        // the order the trace kernel's waves take the tile pairs in: per XCD group (pairs of tile rows dealt round-robin), longest
+        // lists first
+        if ((size_t)order_seg > S.cap_order) {
+            HIP_TRY(hipStreamSynchronize(g.stream));
+            S.cap_order = 0;
+            if ((rc = dev_realloc(&S.d_order, (size_t)ORDER_GROUPS * ORDER_CLASSES * order_seg))) return rc;
+            S.cap_order = order_seg;
+        }
+        hipLaunchKernelGGL(k_tile_order, dim3((pairs_x + 63) / 64, (unsigned)(bs.frame0.j1 - bs.frame0.j0)), dim3(64), 0, g.stream, cam_off, bs.frame0.nshell,
+                           bs.frame0.nbu, bs.frame0.j0, bs.frame0.j1, S.d_bin_counters, S.cap_used, S.d_order, order_seg);
+    }
+    if (forked) HIP_TRY(hipStreamWaitEvent(g.stream, ss.ev_join, 0));
+    k_end(MIRT_K_BIN);
+
+    bp->cam_off = cam_off;
+    bp->tiles_x = bs.frame0.nbu;
+    bp->cam_shells = bs.frame0.nshell;
+    bp->order_seg = order_seg;
+    bp->transient = transient;
+    bp->cube_bins = cube_bins;
+    bp->light_shells = transient ? tshells : g.lc.shells;
+    return MIRT_OK;
+}
+
+// The trace kernel of a binned frame over the tables binned_pass left: the camera's in S, the light cubes' in L (transient) or
+// in the shared cache.
+int binned_trace(const RtFrame &f, RtScratch &S, RtScratch &L, const BinnedPass &bp)
+{
+    const bool transient = bp.transient;
+    RtTraceFrame tf;
+    memset(&tf, 0, sizeof tf);
+    tf.f = f;
+    tf.f.cam_tab = S.d_cam_tab;
+    // (a frame whose pair list overflowed walks the origin tables themselves: every triangle for every ray)
+    tf.f.light_tab = transient ? L.d_light_tab : g.lc.d_light_tab;
+    tf.f.unsafe = nullptr;
+    tf.cam_off = bp.cam_off;
+    tf.cam_entries = S.d_entries;
+    tf.sel = S.d_sel; tf.sel_count = S.d_bin_counters + SEL_COUNT0 + S.sel_parity;
+    // geometry rows staged with every candidate while the scene's tables fit the caches, fetched by the exact stage beyond (rt_trace.hip);
+    // MIRT_LAZY_GEO=0|1 fixes the choice
+    static const int lazy_env = (int)env_int("MIRT_LAZY_GEO", -1);
+    tf.lazy_geo = lazy_env >= 0 ? (lazy_env != 0) : (g.n >= 400000);
+    tf.geo = g.d_geo;
+    tf.shade = g.d_shade;
+    tf.light_off = transient ? L.d_bin_off : g.lc.d_off;
+    tf.light_rows = transient ? L.d_light_rows : g.lc.d_rows;
+    tf.light_tri = transient ? L.d_entries : g.lc.d_row_tri;
+    tf.light_frames = transient ? L.d_frames : g.lc.d_frames;
+    tf.tiles_x = bp.tiles_x;
+    tf.cube_bins = bp.cube_bins;
+    tf.cam_shells = bp.cam_shells;
+    tf.light_shells = bp.light_shells;
+    tf.pair_count = S.d_bin_counters;
+    tf.pair_cap = S.cap_used;
+    // (lights binned by the frame: their own pass's count; the shared cube's tables are complete by construction)
+    tf.light_pair_count = transient ? L.d_bin_counters : nullptr;
+    tf.light_pair_cap = L.cap_used;
+    // one wave per pair of 8 x 8 tiles
+    tf.order = S.d_order; tf.order_count = S.d_bin_counters + 16; tf.order_seg = bp.order_seg;
+    // (waves never synchronise with each other: one-wave workgroups are the finest scheduling unit; 84 / 87 / 89 us with 1 / 2 / 4)
+    const dim3 tgrid(ORDER_GROUPS * bp.order_seg);          // (workgroup id % 8 = XCD group, id / 8 = the wave among the group's)
+    const size_t lds = rt_trace_lds_bytes(1);
+    k_begin(MIRT_K_TRACE);
+    // (the kernel's own statistics -- tests, candidates, steps, drains -- only for frames rendered with profiling on: rt_trace.hip)
+    g.pending_counted = g.profiling;
+    if (f.aa > 1) {
+        if (g.profiling) hipLaunchKernelGGL((k_rt_trace2<true, true>), tgrid, dim3(64), lds, g.stream, tf);
+        else hipLaunchKernelGGL((k_rt_trace2<true, false>), tgrid, dim3(64), lds, g.stream, tf);
+    } else {
+        // five waves per SIMD (the 96-VGPR instantiation) for the large scenes and for the frame that runs alone, four (98 VGPRs) for
+        // the small scenes' frames in flight: rt_trace.hip says why; MIRT_TR_WAVES5=0|1 fixes the choice
+        static const int waves5_env = (int)env_int("MIRT_TR_WAVES5", -1);
+        const bool waves5 = waves5_env >= 0 ? (waves5_env != 0) : (g.n >= 400000 || g.in_flight <= 2);
+        if (g.profiling) hipLaunchKernelGGL((k_rt_trace2<false, true>), tgrid, dim3(64), lds, g.stream, tf);
+        else if (waves5) hipLaunchKernelGGL((k_rt_trace2<false, false, 5>), tgrid, dim3(64), lds, g.stream, tf);
+        else hipLaunchKernelGGL((k_rt_trace2<false, false>), tgrid, dim3(64), lds, g.stream, tf);
+    }
+    k_end(MIRT_K_TRACE);
+    HIP_TRY(hipGetLastError());
+    for (RtScratch *P : { &S, &L })
+        if (P->count_event_due) {
+            P->count_event_due = false;
+            HIP_TRY(hipEventRecord(P->ev_count, g.stream));
+            P->count_pending = true;
+        }
+    return MIRT_OK;
+}
+
+}  // namespace mirt

@@ -1,0 +1,451 @@
+// capi.hpp -- the host side of the C-ABI (csrc/mirt_capi.hip and the files of this directory): the library's state, one
+// StreamState per frame in flight inside one Ctx, and the helpers the topic files share.  Host code only: every kernel is
+// defined under csrc/ (tools/check_spills.py compiles those files); the ones launched from here are declared below.
+#pragma once
+
+#include "../csrc/bin_sort.hpp"
+#include "../csrc/comm.hpp"
+#include "../csrc/cull.hpp"
+#include "../csrc/dof.hpp"
+#include "../csrc/rt_common.hpp"
+#include "../csrc/raster_common.hpp"
+#include "../csrc/rt_binned.hpp"
+#include "../csrc/scan.hpp"
+#include "env.hpp"
+
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+// (a kernel DECLARATION: the definitions live in csrc/)
+#define MIRT_KERNEL __attribute__((global))
+
+namespace mirt {
+
+// ---- kernels (rt_kernels.hip, rt_tile.hip, rt_trace.hip, rt_binned.hip, raster_kernels.hip) ----
+MIRT_KERNEL void k_prep_origin(const float *, int, const float *, v3, int, OriginRow *, OriginRow *, uint32_t *, unsigned long long *, uint32_t *);
+template <int P> MIRT_KERNEL void k_rt_brute(const RtFrame);
+template <int P> MIRT_KERNEL void k_rt_small(const RtFrame, int);
+MIRT_KERNEL void k_rt_wave(const RtFrame);
+struct RtTileFrame {
+    RtFrame f;
+    BinFrameDesc cam;
+    int tiles_x, tiles_y;
+    unsigned long long *clear_hits;
+    float4 *tables;
+};
+MIRT_KERNEL void k_tile_tables(const RtTileFrame);
+template <int TW, bool AA> MIRT_KERNEL void k_rt_tile2(const RtTileFrame);
+template <int WG> MIRT_KERNEL void k_bin_pairs(const float *, const OriginRow *, const OriginRow *, int, BinSet, BinPairs);
+struct TilePairRec { uint32_t tile, beg, nA, nB; };
+constexpr int ORDER_CLASSES = 8, ORDER_GROUPS = 8;
+struct RtTraceFrame {                            // (rt_trace.hip)
+    RtFrame f;
+    const uint32_t *cam_off;
+    const uint32_t *cam_entries;
+    const GeoRow *geo;
+    const ShadeRow *shade;
+    const uint32_t *light_off;
+    const LightRow *light_rows;
+    const uint32_t *light_tri;
+    const BinFrameDesc *light_frames;
+    int tiles_x;
+    int cube_bins;
+    int cam_shells;
+    int light_shells;
+    const uint32_t *pair_count;
+    uint32_t pair_cap;
+    const TilePairRec *order;
+    const uint32_t *order_count;
+    uint32_t order_seg;
+    const uint32_t *sel;
+    const uint32_t *sel_count;
+    int lazy_geo;
+    const uint32_t *light_pair_count;
+    uint32_t light_pair_cap;
+};
+template <bool AA, bool STATS, int WAVES = 4> MIRT_KERNEL void k_rt_trace2(const RtTraceFrame);
+MIRT_KERNEL void k_prep_select(const float *, int, const BinFrameDesc, const SelectOut);
+MIRT_KERNEL void k_select_faces(const float *, int, const float *, const BinFrameDesc *, OriginRow *, uint32_t *, uint32_t, uint32_t *);
+MIRT_KERNEL void k_tile_order(const uint32_t *, int, int, int, int, uint32_t *, uint32_t, TilePairRec *, uint32_t);
+MIRT_KERNEL void k_geo_table(const float *, int, GeoRow *, ShadeRow *);
+MIRT_KERNEL void k_expand_light_rows(const uint32_t *, const uint32_t *, int, uint32_t, const OriginRow *, int, LightRow *, const uint32_t *, uint32_t, uint32_t *);
+MIRT_KERNEL void k_cull(const float *, int, const CullParams, uint8_t *);
+size_t rt_trace_lds_bytes(int waves);
+int launch_raster(RasterFrame &f, RasterScratch &s, uint64_t scene_version, hipStream_t stream, hipEvent_t *ev, bool *ev_used);
+
+// ---- errors ----
+extern char g_err[512];
+int fail(int code, const char *fmt, ...);
+
+#define HIP_TRY(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return fail(MIRT_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+enum { EV_CALL0 = 0, EV_CALL1 = 1, EV_K0 = 2, EV_COUNT = 2 + 2 * 8 };
+constexpr int MAX_FLIGHT = 4;                    // most frames in flight (mirt_set_frames_in_flight): one HIP stream and one set of scratch each
+constexpr int SEL_COUNT0 = 80;                   // word of d_bin_counters where the two selection counters start
+constexpr int HIST_RING = 4;
+constexpr size_t HIT_BYTES = sizeof(unsigned long long) * HIT_SHARDS * HIT_SHARD_STRIDE;   // one hit-counter buffer (rt_common.hpp: count_hits)
+
+// What a frame of the brute-force / binned ray-trace paths writes besides the caller's planes: one set per stream, so
+// that two frames in flight never share any of it.
+struct RtScratch {
+    OriginRow *d_cam_tab = nullptr;              // n rows (cam_tab_n)
+    OriginRow *d_light_tab = nullptr;            // light_tab_lights x n rows
+    int cam_tab_n = 0, light_tab_n = 0, light_tab_lights = 0;
+    float *d_origins = nullptr;                  // (1 + MIRT_MAX_LIGHTS) x 3
+    uint32_t *d_flags = nullptr;                 // [0] = unsafe flag
+    // binned ray tracing: frame descriptors, per-bin offsets, the (bin, triangle) pair list and its sorted copy
+    BinFrameDesc *d_frames = nullptr;
+    uint32_t *d_bin_off = nullptr, *d_bin_counters = nullptr;
+    uint32_t *d_entries = nullptr;               // triangle ids ordered by bin (the sorted pair values)
+    uint32_t *d_pair_keys = nullptr, *d_pair_vals = nullptr, *d_sorted_keys = nullptr;   // unsorted pairs, sorted bin ids
+    uint32_t *d_tmp_vals = nullptr;              // bucket sort: the pairs partitioned by bucket (keys go to d_sorted_keys)
+    uint32_t *d_bucket = nullptr;                // bucket sort: counts | bases (+1) | cursors, cap_buckets each
+    uint32_t cap_buckets = 0;
+    bool bucket_dirty = false;                   // d_bucket may hold counts of a pass whose sort never ran
+    // sizing the pair list without a host sync: the count of a frame is copied to pinned memory behind it and looked at by a
+    // LATER frame of this stream; meanwhile the list is sized from the last count seen, with a device-side fallback if that
+    // was too small (k_rt_trace2 then takes every triangle for every tile)
+    uint32_t *h_count = nullptr;                 // pinned
+    hipEvent_t ev_count = nullptr;
+    bool count_pending = false;
+    bool count_event_due = false;                // bin_pass published a count: the caller records ev_count behind the frame's last kernel
+    bool have_known = false;
+    uint32_t known_pairs = 0;
+    uint32_t cap_bins = 0, cap_entries = 0;
+    uint32_t cap_used = 0;                       // capacity the last binning pass told its kernels (== cap_entries outside tests)
+    uint64_t bin_key = 0;
+    uint32_t bin_entries = 0;                    // pairs of the current binning
+    bool bin_key_valid = false;
+    // lights that moved: this stream's own light-cube pass (transient_light_pass), rows in the order of the pair list
+    LightRow *d_light_rows = nullptr;
+    uint32_t cap_light_rows = 0;
+    // the frame's tile pairs ordered longest lists first (k_tile_order): ORDER_CLASSES segments of cap_order records
+    TilePairRec *d_order = nullptr;
+    uint32_t cap_order = 0;
+    int last_bin_mode = -1;                      // what the last pass binned (camera alone / camera + n light cubes): a guessed
+                                                 // list size only carries over between passes of the same kind
+    // k_prep_select: the triangles the frame may see (indices, sel_n slots) and the two counters its passes use in turn (the pass
+    // that counts into one zeroes the other: d_bin_counters[SEL_COUNT0 + parity])
+    uint32_t *d_sel = nullptr;
+    int sel_n = 0;
+    int sel_parity = 0;
+    // k_select_faces: per face of the light cubes this stream bins (its own frames' moving lights, or the shared cube's build) the
+    // triangles the face can see -- list i at d_face_sel + i * n -- and the lists' lengths
+    uint32_t *d_face_sel = nullptr;
+    size_t cap_face_sel = 0;                     // slots
+    uint32_t *d_face_counts = nullptr;           // 6 * MIRT_MAX_LIGHTS words (inside d_bin_counters' block)
+    // the cost histogram of the whole frame (weighted partition): device words, and where they travel for the host to read --
+    // HIST_RING pinned copies taken in turn, an event behind each
+    uint32_t *d_hist = nullptr;
+    uint32_t *h_hist = nullptr;                  // pinned: HIST_RING x SEL_HIST_MAX words
+    hipEvent_t ev_hist[HIST_RING] = {};
+    uint64_t hist_key[HIST_RING] = {};           // what frame (view, scene) each copy belongs to; 0 = none
+    int hist_rows[HIST_RING] = {}, hist_shift[HIST_RING] = {};
+    int hist_next = 0;
+
+    void forget_scene() { bin_key_valid = false; have_known = false; count_pending = false; }   // tables and pair counts belong to the old scene
+    void release();
+};
+
+// The light-cube bins of the binned ray tracer: they depend on the scene and the light positions only, not on the camera,
+// so they are built once per (scene version, light positions, grid) and shared by the frames of every stream.
+struct LightCache {
+    bool valid = false;
+    uint64_t key = 0;                            // scene version + light positions (not the grid)
+    int cube_bins = 0;                           // bins per face side of the tables held
+    uint64_t track_key = 0;                      // the lights of the most recent binned frame ...
+    int stable = 0;                              // ... and for how many frames in a row they have been the same
+    OriginRow *d_light_tab = nullptr;            // nl x n origin rows
+    size_t cap_tab = 0;
+    BinFrameDesc *d_frames = nullptr;            // 6 x nl frame descriptors
+    uint32_t *d_off = nullptr;                   // nbins + 1
+    uint32_t cap_bins = 0, nbins = 0;
+    LightRow *d_rows = nullptr;                  // expanded candidates in key order
+    uint32_t *d_row_tri = nullptr;               // the triangle of each row
+    uint32_t cap_rows = 0, nrows = 0;
+    int shells = 1;                              // depth shells per bin of the tables held
+    float *d_origins = nullptr;                  // (1 + MIRT_MAX_LIGHTS) x 3
+    uint32_t *d_counter = nullptr;               // pair counter of the build
+
+    void release();
+};
+
+// Depth of field: the planes the render kernels write for a band plus the halo its blur reaches into (render_with_dof).
+struct DofPlanes {
+    float *rgb = nullptr, *fd = nullptr;         // pixelColours / focalDistances of the band + halo
+    uint32_t *xrgb = nullptr;                    // unblurred words the render kernels emit (discarded)
+    int32_t *index = nullptr;
+    float *zinv = nullptr;
+    size_t cap_px = 0;
+
+    int ensure(size_t px);
+    void release();
+};
+
+// Everything a frame in flight owns: its stream and the scratch its kernels write.  A frame reads the scene and writes the
+// caller's planes plus its own stream's state, so frames on different streams need no ordering among themselves (call_begin).
+struct StreamState {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_order = nullptr;               // orders work of another stream after what this one has queued so far
+    // the side stream: the light-cube pass of a frame whose camera AND lights moved runs there, beside the camera's pass (two
+    // latency-bound chains that share nothing until the trace kernel)
+    hipStream_t aux = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // profiling events, one set per stream, so that the times of a frame survive the frames that follow it on the other streams
+    // (mirt_get_previous_kernel_ms: the frame before the last one overlapped its neighbours on both sides)
+    hipEvent_t ev[EV_COUNT] = {};
+    bool ev_used[8] = {};
+    bool call_timed = false;                     // the stream's last call recorded its start / end events (profiling was on)
+    RtScratch rt;                                // tables of the non-tile ray-trace paths
+    RtScratch rt_lt;                             // the pair lists, offsets and rows of a LIGHT-cube pass -- the cubes of lights that move
+                                                 // (binned by the frame) and the scratch of the shared cube's build -- apart from the
+                                                 // camera's, so that either pass is kept while only the other one's inputs change
+    // hit counters (HIT_SHARDS sharded counters each): two used alternately, so that a kernel can clear the one the NEXT frame on
+    // this stream will use
+    unsigned long long *d_hits[2] = {};
+    bool hits_clean[2] = {};                     // buffer is all zero (the tile kernel clears the other one itself)
+    int hits_tog = 0;                            // the buffer of the stream's current frame
+    float4 *d_tile_tab = nullptr;                // tables of the tile ray tracer (k_tile_tables)
+    DofPlanes dof;
+    void *d_async = nullptr;                     // the XRGB plane of an asynchronous frame (async_plane)
+    RasterScratch raster;
+    // cull flags: what this stream's copy of d_culled holds -- the number of the cull call (or upload) it comes from --, and the
+    // copies OUT of other streams' copies it has made: the event is re-recorded behind every such copy ...
+    uint64_t culled_ver = 0;
+    hipEvent_t ev_cull_read = nullptr;
+    uint32_t cull_read_src = 0;                  // ... bit c: the stream has copied out of copy c since a cull step into c last waited for it
+                                                 // (a stream runs in order: waiting for the latest record covers every earlier read)
+
+    int create();                                // the streams and their events (mirt_init allocates the rest)
+    void release();
+};
+
+struct Ctx {
+    bool init = false;
+    bool profiling = false;
+    int device = -1;
+    int cu_count = 256;                          // multiProcessorCount of the device
+    StreamState streams[MAX_FLIGHT];
+    hipStream_t stream = nullptr;                // the stream work is queued on now (the current call's, or its side stream)
+    int in_flight = 1;                           // frames that may be in flight at once (mirt_set_frames_in_flight)
+    uint64_t frame_no = 0;                       // device calls so far
+    int si = 0;                                  // index of the stream of the current / most recent call: calls take the streams in turn
+    int ev_cur = 0;                              // the stream whose events the most recent call recorded (mirt_get_stats reads them)
+    StreamState &cur() { return streams[si]; }
+
+    // scene
+    int n = 0;
+    float *d_tris = nullptr;
+    uint8_t *d_culled = nullptr;                 // isCulled flags: one copy of n per stream, [i * n, (i + 1) * n) for frames on streams[i]
+    int culled_latest = 0;                       // which copy the most recent cull call wrote (mirt_scene_get_culled reads it)
+    uint64_t cull_calls = 0;
+    GeoRow *d_geo = nullptr;                     // n geometry rows (built by mirt_scene_upload)
+    ShadeRow *d_shade = nullptr;                 // n shading rows (likewise)
+    float bbox_lo[3] = { 0, 0, 0 }, bbox_hi[3] = { 0, 0, 0 };   // the scene's bounding box (host side, mirt_scene_upload)
+    LightCache lc;
+    unsigned long long *d_hits = nullptr;        // the hit-counter buffer of the current ray-traced frame (one of its stream's d_hits)
+    bool scene_finite = true;                    // all vertex coordinates below MIRT_SAFE_MAG
+    uint64_t scene_version = 0;                  // bumped whenever the triangles change
+    uint64_t cull_version = 0;                   // bumped whenever the cull flags change (rasteriser sizing only)
+    int soft_samples = 1;                        // soft-shadow samples per light (1 = hard shadows)
+    int aa = 1;                                  // realSamples of Draw(): AA_SAMPLES when AA_ENABLED, else 1
+    int dof_k = 0;                               // DOF_KERNEL_SIZE when DOF_ENABLED, else 0
+    float dof_focal = 0.0f;                      // FOCAL_LENGTH
+    int soft_npos = 0;
+    float soft_pos[MIRT_MAX_LIGHTS * 3] = {};    // jittered light positions, [light*samples + i]
+
+    // host surfaces the caller registered (mirt_surface_register): pinned + mapped, so the frame reaches them at link speed
+    struct HostSurface { char *host = nullptr; char *dev = nullptr; size_t bytes = 0; } surf[4];
+
+    // staging for the host-buffer entry points: all planes share ONE capacity (cap_px pixels)
+    void *d_xrgb = nullptr, *d_rgb = nullptr, *d_index = nullptr, *d_zinv = nullptr, *d_pos = nullptr;
+    size_t cap_px = 0;
+    size_t async_cap_px = 0;                     // pixels of every stream's asynchronous plane
+
+    // several GPUs: this process's place among the ranks that shard a frame, and its band buffers (two: the gather of one
+    // batch overlaps the render of the next)
+    Comm *comm = nullptr;
+    hipStream_t comm_stream = nullptr;
+    hipEvent_t ev_rendered = nullptr, ev_sent[2] = { nullptr, nullptr };
+    char *d_band[2] = { nullptr, nullptr };
+    size_t band_bytes[2] = { 0, 0 };
+    int band_slot = 0;
+    int strip_rows = 0;                          // partition of a sharded frame: 0 = contiguous bands, > 0 = interleaved strips of that many rows,
+                                                 // MIRT_PARTITION_WEIGHTED = bands of equal estimated cost (mirt_set_partition)
+    bool want_hist = false;                      // binned ray-traced frames leave their cost histogram (mirt_set_cost_histogram, or the weighted partition)
+    uint64_t shard_calls = 0;                    // sharded calls so far: what a cost histogram is filed under
+    bool hist_taken = false;                     // the current sharded call has filed its histogram (the first binned pass of a call does)
+    bool in_sharded = false;
+    bool hist_armed = false;                     // hist_prepare armed the pass that is being enqueued
+
+    // statistics of the last call
+    mirt_stats stats = {};
+    bool stats_pending = false;
+    bool raster_since_sync = false;              // rasteriser frames were queued since the last mirt_sync (overflow check there)
+    hipStream_t stats_stream = nullptr;          // the stream the last call ran on
+    uint64_t pending_primary = 0;
+    int pending_nlights = 0;
+    bool pending_is_rt = false;
+    bool pending_counted = false;                // the kernel counted its executed tests itself (tile / binned)
+    bool pending_empty = false;                  // the last ray-trace call rendered no rows (no counters to read)
+    const uint32_t *stats_sel_count = nullptr;   // binned frame that ran a pass: where its selection count is (device)
+};
+
+extern Ctx g;
+
+// ---- what every call does (state.cpp, mirt_capi.hip) ----
+int need_init();
+// Frees *p and allocates `bytes` in its place (nothing for 0); MIRT_ERR_OUT_OF_MEMORY when that fails.
+int dev_realloc_bytes(void **p, size_t bytes);
+template <typename T> int dev_realloc(T **p, size_t count) { return dev_realloc_bytes(reinterpret_cast<void **>(p), count * sizeof(T)); }
+// The arguments every frame entry point checks before it touches the device.  need_scene: the call renders right away (the
+// depth-of-field and staging layers leave that check to the render call); [y0, y1): the row band it renders (the entry points
+// that render the whole frame pass an empty band).
+int check_frame_args(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect, const void *xrgb, int pitch_bytes,
+                     bool need_scene = false, int y0 = 0, int y1 = 0);
+hipError_t sync_all();
+int next_si();
+void call_begin();
+void call_end();
+inline void k_begin(int k) { if (g.profiling) { (void)hipEventRecord(g.cur().ev[EV_K0 + 2 * k], g.stream); g.cur().ev_used[k] = true; } }
+inline void k_end(int k) { if (g.profiling) (void)hipEventRecord(g.cur().ev[EV_K0 + 2 * k + 1], g.stream); }
+// Small parameter blocks for the device, carried in the kernel arguments of a one-workgroup kernel (mirt_capi.hip); the optional
+// zero job clears up to two regions in the same launch.
+struct ZeroJob { uint32_t *a; int na; uint32_t *b; int nb; };
+hipError_t upload_small(void *dst, const void *src, size_t bytes, hipStream_t stream, const ZeroJob *zero = nullptr);
+void hist_out(uint32_t *hist, uint32_t *host_copy, hipStream_t stream);       // k_hist_out: a cost histogram to its pinned copy
+
+// ---- ray tracer (rt_frame.cpp, binned.cpp) ----
+int rt_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect, int mode,
+               int y0, int y1, int row_origin, void *d_xrgb, int pitch_bytes, void *d_rgb, void *d_index, void *d_fd = nullptr,
+               void *d_dist = nullptr, void *d_pos = nullptr);
+BinFrameDesc make_camera_frame(const mirt_view *view, int y0, int y1, int aa);
+bool frame_fits_binning(int W, int H);
+// What the trace kernel of a binned frame takes from the frame's binning pass (binned_pass -> binned_trace).
+struct BinnedPass {
+    const uint32_t *cam_off;                     // camera offsets, indexed by the FRAME's tile number
+    int tiles_x, cam_shells;
+    uint32_t order_seg;                          // tile-pair records per (XCD group, class) segment of the order
+    bool transient;                              // light tables: this frame's own pass (the stream's rt_lt), or the shared cache
+    int cube_bins, light_shells;
+};
+int binned_pass(const RtFrame &f, const mirt_view *view, RtScratch &S, RtScratch &L, const float *origins, int nlights, int y0, int y1, BinnedPass *bp);
+int binned_trace(const RtFrame &f, RtScratch &S, RtScratch &L, const BinnedPass &bp);
+
+// ---- rasteriser (raster.cpp) ----
+int raster_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect,
+                   int y0, int y1, int row_origin, void *d_xrgb, int pitch_bytes, void *d_rgb, void *d_zinv,
+                   void *d_index, void *d_fd = nullptr);
+int cull_copy_wait_readers(int dst, hipStream_t st);
+
+// ---- partition and sharded frames (sharded.cpp) ----
+// The cost histogram of a binned frame's pass (k_prep_select): hist_prepare points the pass at it when one is wanted,
+// hist_publish files it behind the pass.
+int hist_prepare(RtScratch &S, const BinFrameDesc &cam, SelectOut *so);
+int hist_publish(RtScratch &S);
+const uint32_t *hist_lookup(uint64_t max_key, int *rows, int *shift);
+void current_bounds(int world, int W, int H, std::vector<int> &bounds);
+unsigned part_tile_weight();
+// Copies a gather plan (part_gather_plan) out to the caller's arrays, any of which may be NULL; returns the plan's length.
+int plan_out(int world, int root, int width, int height, int nviews, int strip_rows, const int *bounds, uint64_t *root_offset,
+             uint64_t *band_offset, uint64_t *bytes, int32_t *peer, int max_pieces);
+int render_sharded(const mirt_view *views, int nviews, int root, void *d_frames, int pitch_bytes, bool raster,
+                   const mirt_light *lights, int nlights, const float *indirect, int mode);
+
+// ---- delivery: staging, registered surfaces, asynchronous frames, depth of field (delivery.cpp) ----
+struct HostPlane { void *host; void **staging; size_t bpp; };
+int ensure_staging(size_t px, const HostPlane *planes, int nplanes);
+char *registered_alias(const void *host, size_t pitch, int H);
+bool host_direct();
+int copy_plane_interior(void *dst, int dst_pitch, const void *src, int src_pitch, int W, int H);
+int async_plane(size_t px, void **plane);
+int async_target(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect, uint32_t *out_xrgb, int pitch_bytes, char **alias);
+int dof_resolve(const DofPlanes &D, const mirt_view *view, int y0, int y1, int row_origin, int ry0, int ry1, void *d_xrgb, int pitch_bytes,
+                void *user_rgb, void *user_index, void *user_zinv, bool clear_border);
+
+// Depth of field (CalculateDOF with DOF_ENABLED, raytracer.cpp:613-640 / rasteriser.cpp:494-513): the render kernels
+// write pixelColours + focalDistances for the band AND the rows its blur taps reach into library-owned planes, then
+// k_dof resolves the band into the caller's surface.  `render(ry0, ry1, xrgb, rgb, fd, index, zinv)` runs the path.
+template <class Render>
+int render_with_dof(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect, int y0, int y1, int row_origin,
+                    void *d_xrgb, int pitch_bytes, void *user_rgb, void *user_index, void *user_zinv, bool clear_border, Render render)
+{
+    int rc;
+    // the caller's surface reaches the blur kernel directly: validate it here, before anything is allocated or launched
+    // (rt_enqueue / raster_enqueue only see the library-owned planes)
+    if ((rc = check_frame_args(view, lights, nlights, indirect, d_xrgb, pitch_bytes, false, y0, y1))) return rc;
+    const int W = view->width, H = view->height, K = g.dof_k;
+    const int zlo = (int)std::ceil((float)K / -2.0f), zhi = (int)std::ceil((float)K / 2.0f);
+    const int reach = std::max(-zlo, zhi - 1) + 1;           // +1: a tap column outside the row wraps into the next row
+    const int ry0 = std::max(0, y0 - reach), ry1 = std::min(H, y1 + reach);
+    // the stream call_begin() will give this frame (it is self-contained: its planes are this stream's own)
+    DofPlanes &D = g.streams[next_si()].dof;
+    if ((rc = D.ensure((size_t)W * (size_t)(ry1 - ry0)))) return rc;
+    // the kernels index their planes with full-frame pixel numbers: shift the bases so that row ry0 is the first stored
+    const ptrdiff_t shift = (ptrdiff_t)ry0 * W;
+    if ((rc = render(ry0, ry1, (void *)D.xrgb, (void *)(D.rgb - 3 * shift), (void *)(D.fd - shift), user_index ? (void *)(D.index - shift) : nullptr,
+                     user_zinv ? (void *)(D.zinv - shift) : nullptr))) return rc;
+    return dof_resolve(D, view, y0, y1, row_origin, ry0, ry1, d_xrgb, pitch_bytes, user_rgb, user_index, user_zinv, clear_border);
+}
+
+// A whole frame into the caller's host buffers and back before the call returns.  writes_every_word: the render fills every word
+// of the surface (rasteriser), or only its interior (ray tracer: copy_plane_interior).  planes: the extra outputs as (host
+// pointer or NULL, its staging plane, bytes per pixel), in the order the render call takes their device planes;
+// `render(xrgb, pitch, device planes)` enqueues the frame.
+template <int N, class Render>
+int deliver_host(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect, uint32_t *out_xrgb, int pitch_bytes,
+                 bool writes_every_word, const HostPlane (&planes)[N], Render render)
+{
+    int rc;
+    if ((rc = check_frame_args(view, lights, nlights, indirect, out_xrgb, pitch_bytes))) return rc;
+    const int W = view->width, H = view->height;
+    const size_t px = (size_t)W * H;
+    if ((rc = ensure_staging(px, planes, N))) return rc;
+    char *alias = registered_alias(out_xrgb, (size_t)pitch_bytes, H);
+    const bool direct = alias && host_direct();
+    void *dev[N];
+    for (int i = 0; i < N; i++) dev[i] = planes[i].host ? *planes[i].staging : nullptr;
+    if ((rc = render(direct ? (void *)alias : g.d_xrgb, direct ? pitch_bytes : W * 4, dev))) return rc;
+    if (!direct) {
+        if (writes_every_word) HIP_TRY(hipMemcpy2DAsync(out_xrgb, pitch_bytes, g.d_xrgb, (size_t)W * 4, (size_t)W * 4, H, hipMemcpyDeviceToHost, g.stream));
+        else if ((rc = copy_plane_interior(out_xrgb, pitch_bytes, g.d_xrgb, W * 4, W, H))) return rc;
+    }
+    for (int i = 0; i < N; i++)
+        if (planes[i].host) HIP_TRY(hipMemcpyAsync(planes[i].host, dev[i], px * planes[i].bpp, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return MIRT_OK;
+}
+
+// ---- asynchronous delivery into a registered host surface ----
+// Render into one of the library-owned planes, then ONE stream-ordered DMA copy into the pinned surface; no host sync.  With
+// two frames in flight the copy of frame i (the DMA engine) runs while frame i + 1 renders, so a loop that presents one
+// surface while the next one is drawn moves frames at the rate of the link alone.  `render(xrgb, pitch)` enqueues the frame.
+template <class Render>
+int deliver_async(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect, uint32_t *out_xrgb, int pitch_bytes,
+                  bool writes_every_word, Render render)
+{
+    int rc;
+    char *alias = nullptr;
+    if ((rc = async_target(view, lights, nlights, indirect, out_xrgb, pitch_bytes, &alias))) return rc;
+    const int W = view->width, H = view->height;
+    if (host_direct()) return render((void *)alias, pitch_bytes);
+    void *plane = nullptr;
+    if ((rc = async_plane((size_t)W * H, &plane))) return rc;
+    if ((rc = render(plane, W * 4))) return rc;
+    // (on the stream the frame was queued on)
+    if (!writes_every_word) return copy_plane_interior(out_xrgb, pitch_bytes, plane, W * 4, W, H);
+    HIP_TRY(hipMemcpy2DAsync(out_xrgb, pitch_bytes, plane, (size_t)W * 4, (size_t)W * 4, H, hipMemcpyDeviceToHost, g.stream));
+    return MIRT_OK;
+}
+
+}  // namespace mirt

@@ -1,0 +1,278 @@
+// rt_frame.cpp -- a ray-traced frame: its parameter block, the choice of path (tile kernel, small-scene kernel, origin tables +
+// wave / brute kernel, binned), and the launches of the paths that are not binned (binned.cpp holds those).
+#include "capi.hpp"
+
+namespace mirt {
+
+// The camera ray family negD = -(R0*(x - W/2) + R1*(y - H/2) + R2*f) as a bin frame: (u, v) = pixel (x, y), bins =
+// 8x8-pixel tiles; also carries the inverse map for the bounding boxes (rt_binned.hpp).
+BinFrameDesc make_camera_frame(const mirt_view *view, int y0, int y1, int aa)
+{
+    const int W = view->width, H = view->height;
+    BinFrameDesc c;
+    memset(&c, 0, sizeof c);
+    {
+        const float *R = view->rot;                       // column-major: column j = R[3j..3j+2]
+        const float hw = (float)W / 2.0f, hh = (float)H / 2.0f;
+        for (int i = 0; i < 3; i++) {
+            c.Pu[i] = -R[0 + i];
+            c.Pv[i] = -R[3 + i];
+            c.P0[i] = -(R[6 + i] * view->focal - R[0 + i] * hw - R[3 + i] * hh);
+        }
+        float dm = 0.0f;
+        for (int i = 0; i < 3; i++)
+            dm = fmaxf(dm, fabsf(R[0 + i]) * (hw + 1.0f) + fabsf(R[3 + i]) * (hh + 1.0f) + fabsf(R[6 + i]) * fabsf(view->focal));
+        c.dmax = dm;
+        // inverse map for the bounding boxes: h = R^-1 (P - S) = lambda * (x - W/2, y - H/2, f), so with g = S - P
+        //   w = -(R^-1 row 2 . g) / f,  u = (-(R^-1 row 0 . g) + (W/2) f w / f ... ) -> rows below; computed in double
+        {
+            double M[9], inv[9];
+            for (int i = 0; i < 9; i++) M[i] = R[i];
+#define MM(cc, rr) M[(cc) * 3 + (rr)]
+            const double det = MM(0, 0) * (MM(1, 1) * MM(2, 2) - MM(2, 1) * MM(1, 2)) - MM(1, 0) * (MM(0, 1) * MM(2, 2) - MM(2, 1) * MM(0, 2)) +
+                               MM(2, 0) * (MM(0, 1) * MM(1, 2) - MM(1, 1) * MM(0, 2));
+            // inv is row-major here: inv[r*3+c] = (R^-1)(r, c)
+            inv[0] = (MM(1, 1) * MM(2, 2) - MM(2, 1) * MM(1, 2)) / det; inv[1] = -(MM(1, 0) * MM(2, 2) - MM(2, 0) * MM(1, 2)) / det; inv[2] = (MM(1, 0) * MM(2, 1) - MM(2, 0) * MM(1, 1)) / det;
+            inv[3] = -(MM(0, 1) * MM(2, 2) - MM(2, 1) * MM(0, 2)) / det; inv[4] = (MM(0, 0) * MM(2, 2) - MM(2, 0) * MM(0, 2)) / det; inv[5] = -(MM(0, 0) * MM(2, 1) - MM(2, 0) * MM(0, 1)) / det;
+            inv[6] = (MM(0, 1) * MM(1, 2) - MM(1, 1) * MM(0, 2)) / det; inv[7] = -(MM(0, 0) * MM(1, 2) - MM(1, 0) * MM(0, 2)) / det; inv[8] = (MM(0, 0) * MM(1, 1) - MM(1, 0) * MM(0, 1)) / det;
+#undef MM
+            const bool ok = std::isfinite(det) && det != 0.0 && view->focal != 0.0f;
+            for (int i = 0; i < 3; i++) {
+                const double rwd = ok ? -inv[6 + i] / (double)view->focal : 0.0;       // w = h.z / f, h = -R^-1 g
+                c.rw[i] = (float)rwd;
+                c.ru[i] = (float)(ok ? -inv[0 + i] + (double)hw * rwd : 0.0);          // u*w = h.x + (W/2) w
+                c.rv[i] = (float)(ok ? -inv[3 + i] + (double)hh * rwd : 0.0);
+            }
+        }
+        memcpy(c.S, view->pos, 12);
+        c.ulo = 0.0f; c.vlo = 0.0f; c.du = (float)BIN_TILE; c.dv = (float)BIN_TILE;
+        // bin i covers the rays of pixels 8i .. 8i+7: exactly their centres, or with supersampling half a pixel around them
+        c.pad_lo = aa > 1 ? -0.5f : 0.0f; c.pad_hi = aa > 1 ? -0.5f : -1.0f;
+        c.nbu = (W + BIN_TILE - 1) / BIN_TILE; c.nbv = (H + BIN_TILE - 1) / BIN_TILE;
+        c.j0 = y0 / BIN_TILE; c.j1 = (y1 + BIN_TILE - 1) / BIN_TILE;
+        c.base = 0; c.tab = 0;
+    }
+    return c;
+}
+
+// The frame's parameter block, apart from what its stream supplies (hit counters, origin tables); `origins` receives the camera
+// and the light positions the shadow rays start from (1 + f.nlights rows of 3).
+static void make_rt_frame(RtFrame &f, float *origins, const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect,
+                          int y0, int y1, int row_origin, void *d_xrgb, int pitch_bytes, void *d_rgb, void *d_index, void *d_fd, void *d_dist, void *d_pos)
+{
+    memset(&f, 0, sizeof f);
+    f.tris15 = g.d_tris;
+    f.n = g.n;
+    memcpy(f.cam, view->pos, sizeof f.cam);
+    memcpy(f.rot, view->rot, sizeof f.rot);
+    f.focal = view->focal;
+    f.W = view->width;
+    f.H = view->height;
+    // Light positions the shadow rays start from: the lights themselves, or with soft shadows `samples` jittered
+    // positions per light (randomPositions[k*SOFT_SHADOWS_SAMPLES + i], raytracer.cpp:286), each carrying the
+    // light's colour*intensity (:282) which light_term() divides by samples (:296).
+    const int samples = g.soft_samples > 1 ? g.soft_samples : 1;
+    const int npos = nlights * samples;
+    f.nlights = npos;
+    f.samples = samples;
+    f.aa = g.aa > 1 ? g.aa : 1;
+    memcpy(origins, view->pos, 12);
+    for (int j = 0; j < npos; j++) {
+        const int k = j / samples;
+        const float *pos = samples > 1 ? g.soft_pos + 3 * j : lights[k].pos;
+        memcpy(f.lpos[j], pos, 12);
+        memcpy(origins + 3 * (j + 1), pos, 12);
+        // P = (color * intensity) / samples (raytracer.cpp:282, :296): uniform per light, so the division happens once here
+        // (host float division is the same IEEE operation the kernels would run per pixel)
+        for (int c = 0; c < 3; c++) f.lcol[j][c] = (lights[k].color[c] * lights[k].intensity) / (float)f.samples;
+    }
+    f.lights_in_range = 1;
+    for (int j = 0; j < npos; j++) f.lights_in_range &= light_colour_in_range(f.lcol[j]) ? 1 : 0;
+    memcpy(f.indirect, indirect, 12);
+    f.y0 = y0; f.y1 = y1; f.row_origin = row_origin;
+    f.xrgb = static_cast<uint32_t *>(d_xrgb);
+    f.pitch_words = pitch_bytes / 4;
+    f.rgb = static_cast<float *>(d_rgb);
+    f.index = static_cast<int32_t *>(d_index);
+    f.fd = static_cast<float *>(d_fd);
+    f.dist = static_cast<float *>(d_dist);
+    f.pos = static_cast<float *>(d_pos);
+    f.focal_plane = g.dof_focal;
+}
+
+static bool finite_below(const float *p, int n, float lim)
+{
+    for (int i = 0; i < n; i++) if (!(fabsf(p[i]) < lim)) return false;
+    return true;
+}
+
+// The frames that are not binned.  Scenes of at most 64 triangles (the reference's Cornell box has 30): per-tile candidate
+// masks, one lane per triangle (rt_tile.hip), when the operands are inside the filter's proven range; other small scenes: one
+// launch, every table built in LDS by the workgroup itself -- no origin-table kernel, no global loads inside the loops; the
+// rest: the stream's origin tables (k_prep_origin), then a wave per ray (few rays, many triangles) or the brute-force kernel.
+static int rt_dispatch_brute(RtFrame &f, const mirt_view *view, RtScratch &S, const float *origins, int nlights, bool safe, bool tile_path, size_t tile_lds)
+{
+    StreamState &ss = g.cur();
+    const int rows = f.y1 - f.y0;
+    if (tile_path) {
+        RtTileFrame tf;
+        memset(&tf, 0, sizeof tf);
+        tf.f = f;
+        tf.cam = make_camera_frame(view, f.y0, f.y1, g.aa);
+        // a wave owns a 16 x 8-pixel tile, two pixels per lane (packed FP32, rt_tile.hip); workgroups of 4 waves, one workgroup
+        // per 4 tiles.  Tile cost varies several-fold (candidates, shadowed or lit), and the hardware's dynamic workgroup dispatch
+        // balances that better than any static assignment (measured on the Cornell box at 1080p: 40.5 us with one tile per wave,
+        // 46 us with a resident grid striding over the tiles, 49 us with 3 tiles per wave).
+        const int tw = 16, th = 8, wpb = 4;
+        tf.tiles_x = (view->width + tw - 1) / tw;
+        tf.tiles_y = (rows + th - 1) / th;
+        const long long ntiles = (long long)tf.tiles_x * tf.tiles_y;
+        const unsigned blocks = (unsigned)((ntiles + wpb - 1) / wpb);
+        if (!ss.hits_clean[ss.hits_tog]) HIP_TRY(hipMemsetAsync(g.d_hits, 0, HIT_BYTES, g.stream));
+        ss.hits_clean[ss.hits_tog] = false;
+        g.pending_counted = true;
+        tf.clear_hits = ss.d_hits[ss.hits_tog ^ 1];      // zeroed by this launch for the next frame on this stream: no memset node per frame
+        ss.hits_clean[ss.hits_tog ^ 1] = true;
+        // Tables: built once per frame by k_tile_tables when the frame has enough workgroups to make rebuilding them in
+        // each one the larger cost; small frames are bound by the launch rate and keep the single launch.
+        tf.tables = blocks >= 1024u ? ss.d_tile_tab : nullptr;
+        if (tf.tables) {
+            k_begin(MIRT_K_PREP);
+            hipLaunchKernelGGL(k_tile_tables, dim3(1), dim3(64), 0, g.stream, tf);
+            k_end(MIRT_K_PREP);
+        }
+        k_begin(MIRT_K_TRACE);
+        if (f.aa > 1) hipLaunchKernelGGL((k_rt_tile2<16, true>), dim3(blocks), dim3(64 * wpb), tile_lds, g.stream, tf);
+        else hipLaunchKernelGGL((k_rt_tile2<16, false>), dim3(blocks), dim3(64 * wpb), tile_lds, g.stream, tf);
+        k_end(MIRT_K_TRACE);
+        HIP_TRY(hipGetLastError());
+        return MIRT_OK;
+    }
+
+    const size_t small_lds = 16 + (size_t)g.n * sizeof(OriginRow) * (2 + nlights);
+    if (small_lds <= 48 * 1024) {
+        HIP_TRY(hipMemsetAsync(g.d_hits, 0, HIT_BYTES, g.stream));
+        ss.hits_clean[ss.hits_tog] = false;
+        k_begin(MIRT_K_TRACE);
+        // (two rays per lane, packed FP32 filter: 188 -> 163 ms on the 100 k soup against one)
+        hipLaunchKernelGGL(k_rt_small<2>, dim3((view->width + 127) / 128, (rows + 3) / 4), dim3(256), small_lds, g.stream, f, safe ? 0 : 1);
+        k_end(MIRT_K_TRACE);
+        HIP_TRY(hipGetLastError());
+        return MIRT_OK;
+    }
+
+    const uint32_t flags_init[4] = { safe ? 0u : 1u, 0u, 0u, 0u };
+    HIP_TRY(upload_small(S.d_flags, flags_init, sizeof flags_init, g.stream));
+    S.bin_key_valid = false;                     // (k_prep_origin below overwrites the camera rows a kept binning pass would count on)
+    ss.hits_clean[ss.hits_tog] = false;
+    HIP_TRY(upload_small(S.d_origins, origins, sizeof(float) * 3 * (1 + nlights), g.stream));
+
+    k_begin(MIRT_K_PREP);
+    hipLaunchKernelGGL(k_prep_origin, dim3((g.n + 255) / 256, 1 + nlights), dim3(256), 0, g.stream,
+                       g.d_tris, g.n, S.d_origins, V3(0.0f, 0.0f, 0.0f), 0, S.d_cam_tab, S.d_light_tab, S.d_flags, g.d_hits, (uint32_t *)nullptr);
+    k_end(MIRT_K_PREP);
+
+    k_begin(MIRT_K_TRACE);
+    if (g.aa <= 1 && (long long)view->width * rows <= 4096 && g.n >= 1024) {
+        // few rays, many triangles: one wave per ray, lanes over triangles, wavefront min-t reduce
+        const long long nrays = (long long)view->width * rows;
+        hipLaunchKernelGGL(k_rt_wave, dim3((unsigned)((nrays + 3) / 4)), dim3(256), 0, g.stream, f);
+    } else {
+        const size_t lds = (size_t)(g.n < RT_CHUNK_ROWS ? g.n : RT_CHUNK_ROWS) * sizeof(OriginRow);
+        hipLaunchKernelGGL(k_rt_brute<2>, dim3((view->width + 127) / 128, (rows + 3) / 4), dim3(256), lds, g.stream, f);
+    }
+    k_end(MIRT_K_TRACE);
+    HIP_TRY(hipGetLastError());
+    return MIRT_OK;
+}
+
+int rt_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect, int mode,
+               int y0, int y1, int row_origin, void *d_xrgb, int pitch_bytes, void *d_rgb, void *d_index, void *d_fd,
+               void *d_dist, void *d_pos)
+{
+    int rc;
+    if ((rc = check_frame_args(view, lights, nlights, indirect, d_xrgb, pitch_bytes, true, y0, y1))) return rc;
+    if (mode != MIRT_RT_AUTO && mode != MIRT_RT_BRUTE && mode != MIRT_RT_BINNED) return fail(MIRT_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
+    const int samples = g.soft_samples > 1 ? g.soft_samples : 1;
+    const int light_positions = nlights * samples;           // shadow-ray origins
+    if (light_positions > MIRT_MAX_LIGHTS)
+        return fail(MIRT_ERR_INVALID_ARGUMENT, "%d lights x %d soft-shadow samples exceed %d light positions", nlights, samples, MIRT_MAX_LIGHTS);
+    if (samples > 1 && light_positions > g.soft_npos)
+        return fail(MIRT_ERR_INVALID_ARGUMENT, "%d jittered positions needed, %d were set (mirt_set_soft_shadows)", light_positions, g.soft_npos);
+
+    RtFrame f;
+    float origins[(1 + MIRT_MAX_LIGHTS) * 3];
+    make_rt_frame(f, origins, view, lights, nlights, indirect, y0, y1, row_origin, d_xrgb, pitch_bytes, d_rgb, d_index, d_fd, d_dist, d_pos);
+    nlights = light_positions;                   // from here on "lights" means light positions
+    // The pre-reject filter is proven for finite, moderate operands only (rt_common.hpp); anything else
+    // (absurd coordinates, NaN/Inf) renders through the exact-only path.  Ray directions of the primary
+    // rays are bounded by 3 * max|rot| * max(W, H, |focal|).
+    float rmax = 0.0f;
+    for (int i = 0; i < 9; i++) rmax = fmaxf(rmax, fabsf(view->rot[i]));
+    const float dmax = 3.0f * rmax * fmaxf(fmaxf((float)view->width, (float)view->height), fabsf(view->focal));
+    const bool safe = g.scene_finite && finite_below(view->rot, 9, 1.0e6f) && (dmax < 1.0e6f) &&
+                      finite_below(origins, 3 * (1 + nlights), 1.0e8f);      // camera and light positions
+
+    // ---- mode: brute force for small scenes, binned otherwise; unsafe operands always render exact brute ----
+    // MIRT_RT_AUTO bins when the scene is beyond the tile kernel (65 triangles or more) and the brute-force work, pixels x
+    // triangles, is above ~4e7: binning + sorting costs ~40 us whatever the scene, brute force ~7.5e-10 ms per pixel-triangle
+    // (tools/threshold_sweep.py at 1080p: 65 triangles 0.099 vs 0.043 ms, 300: 0.47 vs 0.079, 800: 1.13 vs 0.097).
+    static const int auto_threshold = (int)env_int("MIRT_BIN_THRESHOLD", 65);
+    bool binned = (mode == MIRT_RT_BINNED) ||
+                  (mode == MIRT_RT_AUTO && g.n >= auto_threshold && (long long)view->width * (y1 - y0) > 4096 &&
+                   (long long)view->width * (y1 - y0) * g.n >= 40000000LL);
+    if (!safe) binned = false;
+    if (binned && !frame_fits_binning(view->width, view->height)) {
+        // more 8 x 8-pixel tiles than one sort pass has keys (a frame beyond ~23 000 x 23 000 pixels)
+        if (mode == MIRT_RT_BINNED) return fail(MIRT_ERR_INVALID_ARGUMENT, "frame %dx%d has more tiles than the binned path can key; use MIRT_RT_AUTO or row bands of a smaller frame", view->width, view->height);
+        binned = false;
+    }
+    const size_t tile_lds = (size_t)g.n * 16 * (12 + 3 * nlights);
+    const bool tile_path = !binned && safe && g.n <= 64 && tile_lds <= 64 * 1024;
+
+    // A frame reads the scene and writes the caller's planes plus its stream's own tables, counters and depth-of-field
+    // planes, so frames may overlap (call_begin).
+    call_begin();
+    g.pending_is_rt = true;
+    g.pending_primary = (uint64_t)view->width * (uint64_t)(y1 - y0) * (uint64_t)((g.aa > 1 ? g.aa : 1) * (g.aa > 1 ? g.aa : 1));
+    g.pending_nlights = light_positions;
+    g.stats.mode_used = MIRT_RT_BRUTE;
+    g.pending_empty = (y1 == y0);
+    g.pending_counted = false;
+    if (y1 == y0) { call_end(); return MIRT_OK; }
+    // hit counters: the stream's two buffers in turn (the tile kernel clears the one the stream's next frame will use)
+    StreamState &ss = g.cur();
+    ss.hits_tog ^= 1;
+    g.d_hits = ss.d_hits[ss.hits_tog];
+    f.hit_count = g.d_hits;
+    RtScratch &S = ss.rt;
+    if (!tile_path) {                            // origin tables of this stream, sized for the scene and the light positions
+        if (S.cam_tab_n != g.n) {
+            S.cam_tab_n = 0;
+            if ((rc = dev_realloc(&S.d_cam_tab, (size_t)g.n))) return rc;
+            S.cam_tab_n = g.n;
+        }
+        if (!binned && (light_positions > S.light_tab_lights || S.light_tab_n != g.n)) {   // (binned frames read the shared light cache)
+            S.light_tab_lights = 0;
+            if ((rc = dev_realloc(&S.d_light_tab, (size_t)light_positions * g.n))) return rc;
+            S.light_tab_lights = light_positions;
+            S.light_tab_n = g.n;
+        }
+        if (!S.d_origins) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_origins), sizeof(float) * 3 * (1 + MIRT_MAX_LIGHTS)));
+        if (!S.d_flags) { HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_flags), 16)); HIP_TRY(hipMemsetAsync(S.d_flags, 0, 16, g.stream)); }
+    }
+    f.cam_tab = S.d_cam_tab;
+    f.light_tab = S.d_light_tab;
+    f.unsafe = S.d_flags;
+
+    if (binned) {
+        BinnedPass bp;
+        if ((rc = binned_pass(f, view, S, ss.rt_lt, origins, nlights, y0, y1, &bp)) || (rc = binned_trace(f, S, ss.rt_lt, bp))) return rc;
+    } else if ((rc = rt_dispatch_brute(f, view, S, origins, nlights, safe, tile_path, tile_lds))) {
+        return rc;
+    }
+    call_end();
+    return MIRT_OK;
+}
+
+}  // namespace mirt

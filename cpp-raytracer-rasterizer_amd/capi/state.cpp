@@ -1,0 +1,122 @@
+// state.cpp -- the library's state (capi.hpp): what each part of it owns and gives back (create / release; a buffer is freed
+// by the struct that holds its pointer), and what every device call does with it: the argument checks, the stream it takes, its
+// start and its end.
+#include "capi.hpp"
+
+namespace mirt {
+
+int dev_realloc_bytes(void **p, size_t bytes)
+{
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+    if (bytes == 0) return MIRT_OK;
+    hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) { *p = nullptr; return fail(MIRT_ERR_OUT_OF_MEMORY, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e)); }
+    return MIRT_OK;
+}
+
+int check_frame_args(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect, const void *xrgb, int pitch_bytes,
+                     bool need_scene, int y0, int y1)
+{
+    int rc;
+    if ((rc = need_init())) return rc;
+    if (!view || !indirect) return fail(MIRT_ERR_INVALID_ARGUMENT, "view / indirect must not be NULL");
+    if (view->width < 1 || view->height < 1 || view->width > 32768 || view->height > 32768)
+        return fail(MIRT_ERR_INVALID_ARGUMENT, "frame size %dx%d out of range [1,32768]", view->width, view->height);
+    if (nlights < 0 || nlights > MIRT_MAX_LIGHTS) return fail(MIRT_ERR_INVALID_ARGUMENT, "nlights %d out of range [0,%d]", nlights, MIRT_MAX_LIGHTS);
+    if (nlights > 0 && !lights) return fail(MIRT_ERR_INVALID_ARGUMENT, "lights must not be NULL when nlights > 0");
+    if (need_scene && g.n <= 0) return fail(MIRT_ERR_NO_SCENE, "no scene uploaded (mirt_scene_upload)");
+    if (!xrgb) return fail(MIRT_ERR_INVALID_ARGUMENT, "xrgb output must not be NULL");
+    if (y0 < 0 || y1 > view->height || y0 > y1) return fail(MIRT_ERR_INVALID_ARGUMENT, "row band [%d,%d) outside [0,%d)", y0, y1, view->height);
+    if (pitch_bytes < view->width * 4 || (pitch_bytes & 3)) return fail(MIRT_ERR_INVALID_ARGUMENT, "pitch %d bytes too small for width %d or not a multiple of 4", pitch_bytes, view->width);
+    return MIRT_OK;
+}
+
+// Waits for every call enqueued so far (all streams).
+hipError_t sync_all()
+{
+    hipError_t e = hipSuccess;
+    for (const StreamState &ss : g.streams)
+        if (ss.stream) { const hipError_t r = hipStreamSynchronize(ss.stream); if (r != hipSuccess) e = r; }
+    for (const StreamState &ss : g.streams)
+        if (ss.aux) { const hipError_t r = hipStreamSynchronize(ss.aux); if (r != hipSuccess) e = r; }
+    if (g.comm_stream) { const hipError_t r = hipStreamSynchronize(g.comm_stream); if (r != hipSuccess) e = r; }
+    return e;
+}
+
+// The stream the NEXT device call will take: calls take the in_flight streams in turn.
+int next_si() { return g.in_flight > 1 ? (g.si + 1) % g.in_flight : 0; }
+
+// Every device call starts here.  With several frames in flight consecutive calls take the streams in turn, so frame i+1 is
+// dispatched -- and its kernels run, where the device has room -- while frame i still drains: no dispatch gap, no idle tail,
+// and the latency-bound chains of consecutive frames (binning, sort, trace; vertex, edges, fragments, resolve) fill each
+// other's gaps.  A frame reads the scene and writes the caller's planes plus its OWN stream's state (origin tables, bins,
+// raster keys, depth-of-field planes, counters), so frames need no ordering among themselves; frames i and i + in_flight,
+// which a caller cycling through in_flight sets of planes gives the same planes, share a stream.
+void call_begin()
+{
+    g.si = next_si();
+    StreamState &ss = g.cur();
+    g.stream = ss.stream;
+    g.frame_no++;
+    (void)hipGetLastError();                     // drop a stale error of another HIP user in this thread (torch polls events:
+                                                 // hipErrorNotReady) so that the launch checks below report our own launches only
+    memset(&g.stats, 0, sizeof g.stats);
+    g.stats_sel_count = nullptr;
+    g.ev_cur = g.si;
+    memset(ss.ev_used, 0, sizeof ss.ev_used);
+    // the call's own start / end events only when profiling is on: an event record costs ~2.7 us of host time, a quarter of
+    // a 500 x 500 Cornell frame (12.9 -> 7.x us per frame without the two of them)
+    ss.call_timed = g.profiling;
+    if (ss.call_timed) (void)hipEventRecord(ss.ev[EV_CALL0], g.stream);
+}
+void call_end() { if (g.cur().call_timed) (void)hipEventRecord(g.cur().ev[EV_CALL1], g.stream); g.stats_stream = g.stream; g.stats_pending = true; }
+
+// ---- what the state owns ----------------------------------------------------------------------------------------
+// (a buffer is freed by the struct that holds its pointer)
+
+void RtScratch::release()
+{
+    for (void *p : { (void *)d_cam_tab, (void *)d_light_tab, (void *)d_origins, (void *)d_flags, (void *)d_frames, (void *)d_light_rows, (void *)d_order, (void *)d_bin_off,
+                     (void *)d_bin_counters, (void *)d_entries, (void *)d_pair_keys, (void *)d_pair_vals, (void *)d_sorted_keys, (void *)d_tmp_vals, (void *)d_bucket,
+                     (void *)d_sel, (void *)d_face_sel, (void *)d_hist })     // (d_face_counts lies inside d_bin_counters' block)
+        if (p) (void)hipFree(p);
+    if (h_count) (void)hipHostFree(h_count);
+    if (ev_count) (void)hipEventDestroy(ev_count);
+    if (h_hist) (void)hipHostFree(h_hist);
+    for (hipEvent_t e : ev_hist) if (e) (void)hipEventDestroy(e);
+    *this = RtScratch();
+}
+
+void LightCache::release()
+{
+    for (void *p : { (void *)d_light_tab, (void *)d_frames, (void *)d_off, (void *)d_rows, (void *)d_row_tri, (void *)d_origins, (void *)d_counter })
+        if (p) (void)hipFree(p);
+    *this = LightCache();
+}
+
+int StreamState::create()
+{
+    HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&ev_order, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&ev_cull_read, hipEventDisableTiming));
+    HIP_TRY(hipStreamCreateWithFlags(&aux, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+    return MIRT_OK;
+}
+
+void StreamState::release()
+{
+    rt.release();
+    rt_lt.release();
+    raster_scratch_free(raster);
+    dof.release();
+    for (void *p : { (void *)d_hits[0], (void *)d_hits[1], (void *)d_tile_tab, d_async }) if (p) (void)hipFree(p);
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : { ev_order, ev_cull_read, ev_fork, ev_join }) if (e) (void)hipEventDestroy(e);
+    if (aux) (void)hipStreamDestroy(aux);
+    if (stream) (void)hipStreamDestroy(stream);
+    *this = StreamState();
+}
+
+}  // namespace mirt

@@ -9,6 +9,7 @@
 //         rehearsal of the control flow).  Synchronous, slow, and never the measured path.
 // No HIP kernels here; plain host code.
 #include "comm.hpp"
+#include "../capi/env.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -128,11 +129,6 @@ void part_weighted_bounds(const uint32_t *hist, int hist_rows, int shift, int wi
     for (int r = 1; r <= world; r++) bounds[r] = std::max(bounds[r], bounds[r - 1]);
 }
 
-int band_gather_plan(int world, int root, int width, int height, int nviews, BandPiece *out, int max_pieces)
-{
-    return part_gather_plan(world, root, width, height, nviews, 0, out, max_pieces);
-}
-
 namespace {
 
 struct Rccl {
@@ -167,11 +163,7 @@ struct Rccl {
 
 Rccl g_rccl;
 
-bool use_shm()
-{
-    const char *e = getenv("MIRT_COMM");
-    return e && !strcmp(e, "shm");
-}
+bool use_shm() { return env_is("MIRT_COMM", "shm"); }
 
 }  // namespace
 

@@ -38,10 +38,9 @@ int comm_world(const Comm *c);
 
 // The messages of one gather as offsets: on the root, `bytes` from rank `peer` land at root_offset of its frame buffer
 // (nviews frames of height * width * 4 bytes); on rank `peer`, they are the `bytes` at band_offset of its band buffer (nviews
-// bands of its rows).  Returns the number of pieces written (at most max_pieces); pure arithmetic.
+// bands of its rows), one piece per (rank, view, segment) of either partition.  Returns the number of pieces written (at most
+// max_pieces); pure arithmetic.
 struct BandPiece { size_t root_offset, band_offset, bytes; int peer; };
-int band_gather_plan(int world, int root, int width, int height, int nviews, BandPiece *out, int max_pieces);
-// ... for either partition: one piece per (rank, view, segment)
 int part_gather_plan(int world, int root, int width, int height, int nviews, int strip_rows, BandPiece *out, int max_pieces, const int *bounds = nullptr);
 
 // One message of the gather.  On the root: `bytes` from rank `peer` land at `ptr`; elsewhere: `bytes` at `ptr` go to the root.

@@ -195,7 +195,7 @@ __device__ __forceinline__ void bin_walk_large(const BinItem &u, uint32_t utri, 
 // The histogram (optional): every boxed triangle adds the bins of its box, row by row, to the coarse tile rows of the WHOLE
 // frame -- whatever rows this call renders -- an estimate of where the frame's (tile, triangle) pairs lie that every rank of a
 // sharded frame computes identically (integer sums), so that all of them derive the same cost-weighted bands without exchanging
-// anything (mirt_capi.hip: weighted partition).  Kept in LDS per workgroup, flushed once.
+// anything (capi/sharded.cpp: weighted partition).  Kept in LDS per workgroup, flushed once.
 constexpr int SEL_WG = 1024;                          // threads of a k_prep_select workgroup: one workgroup per CU, 4 waves per SIMD
 constexpr int SEL_STAGE = 8192;                       // indices a workgroup stages in LDS between hand-overs to the global list (32 KiB)
 
@@ -472,7 +472,7 @@ __global__ __launch_bounds__(WG) void k_bin_pairs(const float *__restrict__ tris
 #endif
             // t = e1e2b / e1e2d passes `t >= 0` with the "wrong" sign of e1e2d only if it comes out as -0, i.e. e1e2b is
             // zero or the quotient underflows past the smallest subnormal 2^-149.  Binning runs only for operands the host
-            // has bounded (|coordinate| < 1e8, |negD| < 1e6: mirt_capi.hip `safe`), so |e1e2d| < 2^79 and the quotient
+            // has bounded (|coordinate| < 1e8, |negD| < 1e6: capi/rt_frame.cpp `safe`), so |e1e2d| < 2^79 and the quotient
             // cannot underflow unless |e1e2b| < 2^-70: below 2^-69 either sign of e1e2d is allowed.  (rect_may_hit keeps
             // the scene-independent 2^-22; with that here, the handful of triangles of a 100 k soup whose plane passes
             // within 1e-4 of the camera were put into every bin of the screen.)
@@ -661,7 +661,7 @@ __global__ __launch_bounds__(WG) void k_bin_pairs(const float *__restrict__ tris
 // all eight -- and 256, where every wave sets up and tests.  The smaller one holds no idle waves during the set-up, which leaves the
 // frames in flight beside it more of the chip (100 k triangles at 1080p: 63.8 against 65.7 us per frame with four in flight, 122
 // against 118 us with one); the larger one halves the rounds of the tests, which is what a 1 M-triangle frame wants (1.15 against
-// 1.23 ms at 8K).  mirt_capi.hip picks by the size of the scene and the frames in flight (MIRT_BIN_WG overrides).
+// 1.23 ms at 8K).  capi/binned.cpp picks by the size of the scene and the frames in flight (MIRT_BIN_WG overrides).
 template __global__ void k_bin_pairs<512>(const float *, const OriginRow *, const OriginRow *, int, BinSet, BinPairs);
 template __global__ void k_bin_pairs<256>(const float *, const OriginRow *, const OriginRow *, int, BinSet, BinPairs);
 

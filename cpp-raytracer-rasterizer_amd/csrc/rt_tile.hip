@@ -362,7 +362,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(AA ? 3 : MI
     const TileTables tab = tile_tables_load(tf, s_all);
     const long long ntiles = (long long)tf.tiles_x * tf.tiles_y;
     const int waves = blockDim.x >> 6;
-    // (one tile per wave: the launch has a wave for every tile -- mirt_capi.hip --, and written as a loop over a wave's tiles
+    // (one tile per wave: the launch has a wave for every tile -- capi/rt_frame.cpp --, and written as a loop over a wave's tiles
     // everything the body computes from the frame's parameters alone stays live across the whole body for a next round that never comes)
     const long long tile = (long long)blockIdx.x * waves + (threadIdx.x >> 6);
     if (tile < ntiles) tile_body2<TW, AA>(tf, (int)(tile % tf.tiles_x), (int)(tile / tf.tiles_x), tab);

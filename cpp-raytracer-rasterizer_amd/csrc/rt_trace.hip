@@ -24,7 +24,7 @@
 //     into -- every later candidate has near > 0.99 r and cannot occlude (:313).  A bin's list grows with the square of the
 //     distance from the light, so this drops most of it.  A lane walks the list of its pixel A and then that of its pixel B
 //     back to back (the wave's steps are max(lenA + lenB) over its lanes, not max(lenA) + max(lenB));
-//   * a frame whose pair list overflowed (sized from an earlier frame's count, mirt_capi.hip) is rendered by the SAME kernel
+//   * a frame whose pair list overflowed (sized from an earlier frame's count, capi/binned.cpp) is rendered by the SAME kernel
 //     with "every triangle" as each tile's list -- brute force, same bits -- instead of by a guard launch behind it;
 //   * workgroups are mapped to screen blocks so that the blocks an XCD (private L2) works on are neighbours.
 //
@@ -329,7 +329,7 @@ __global__ __launch_bounds__(64) void k_tile_order(const uint32_t *__restrict__ 
 // -- is one atomic per wave and always kept.
 // ... and FIVE (<= 96 VGPRs) for the instantiation the large scenes' frames run: the 1 M-triangle frame at 8K gains 4-5 % from the fifth
 // wave (1.09 against 1.13-1.17 ms per frame), the 100 k-triangle frame with four in flight loses 2 % to it (65.3 against 63.9 us: five
-// trace waves per SIMD leave the binning kernels of the frames beside it less room), so mirt_capi.hip launches it from 400 k
+// trace waves per SIMD leave the binning kernels of the frames beside it less room), so capi/binned.cpp launches it from 400 k
 // triangles on and for the frame that runs alone (115.6 against 117.6 us).  Asking for 10 KiB of LDS per wave to hold the 96-register
 // code at four waves was tried instead of a second instantiation: 66.7 us per frame -- the LDS the trace waves then sit on is what
 // the binning kernels of the frames beside them need.  (Round 3 and the first half of round 4 "measured" a fifth wave with builds of 98 VGPRs -- which the hardware runs at
@@ -733,7 +733,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
 }
 
 template __global__ void k_rt_trace2<false, false>(const RtTraceFrame);         // the frames of the loop: four waves per SIMD ...
-template __global__ void k_rt_trace2<false, false, 5>(const RtTraceFrame);      // ... or five (mirt_capi.hip)
+template __global__ void k_rt_trace2<false, false, 5>(const RtTraceFrame);      // ... or five (capi/binned.cpp)
 template __global__ void k_rt_trace2<false, true>(const RtTraceFrame);
 template __global__ void k_rt_trace2<true, false>(const RtTraceFrame);
 template __global__ void k_rt_trace2<true, true>(const RtTraceFrame);

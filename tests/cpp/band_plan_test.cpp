@@ -1,6 +1,6 @@
 // World-size-2 (and 3, 5) test of the band partition and the gather plan of the sharded entry points, on the CPU: one
 // process per rank (fork), the bands travel through pipes exactly as the plan lists them (csrc/comm.cpp: band_of,
-// band_gather_plan -- the arithmetic mirt_*_sharded hands to RCCL), and the root checks every word of every frame.
+// part_gather_plan -- the arithmetic mirt_*_sharded hands to RCCL), and the root checks every word of every frame.
 #include "../../cpp-raytracer-rasterizer_amd/csrc/comm.hpp"
 
 #include <sys/wait.h>
