@@ -577,6 +577,42 @@ int binned_pass(const RtFrame &f, const mirt_view *view, RtScratch &S, RtScratch
     return MIRT_OK;
 }
 
+// k_prep_select over a frame of no rows, for its histogram of the whole frame, filed like a binned pass's.  It still writes the
+// origin rows and the indices of the triangles it cannot rule out into the stream's tables -- the pass the stream held is gone
+// (bin_key_valid) -- and counts them into words of its own (HIST_SEL_COUNT, zeroed first), so that the selection count of the
+// stream's last binned frame, which mirt_get_stats reads, stays what it was.
+int hist_only_pass(const mirt_view *view)
+{
+    int rc;
+    g.stream = g.cur().stream;
+    RtScratch &S = g.cur().rt;
+    if (S.cam_tab_n != g.n) {
+        S.cam_tab_n = 0;
+        if ((rc = dev_realloc(&S.d_cam_tab, (size_t)g.n))) return rc;
+        S.cam_tab_n = g.n;
+    }
+    if (S.sel_n != g.n) {
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        S.sel_n = 0;
+        if ((rc = dev_realloc(&S.d_sel, (size_t)g.n))) return rc;
+        S.sel_n = g.n;
+    }
+    if (!S.d_bin_counters) { HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_bin_counters), 512)); HIP_TRY(hipMemsetAsync(S.d_bin_counters, 0, 512, g.stream)); }
+    S.bin_key_valid = false;
+    const BinFrameDesc fr = make_camera_frame(view, 0, 0, g.aa);
+    SelectOut so;
+    memset(&so, 0, sizeof so);
+    so.cam_tab = S.d_cam_tab; so.sel = S.d_sel;
+    so.sel_count = S.d_bin_counters + HIST_SEL_COUNT; so.sel_count_next = S.d_bin_counters + HIST_SEL_COUNT + 1;
+    if ((rc = hist_prepare(S, fr, &so))) return rc;
+    if (!g.hist_armed) return MIRT_OK;
+    HIP_TRY(hipMemsetAsync(so.sel_count, 0, 4, g.stream));
+    const unsigned sel_grid = (unsigned)std::min<long long>(((long long)g.n + 1023) / 1024, (long long)g.cu_count);
+    if (sel_grid) hipLaunchKernelGGL(k_prep_select, dim3(sel_grid), dim3(1024), 0, g.stream, g.d_tris, g.n, fr, so);
+    HIP_TRY(hipGetLastError());
+    return hist_publish(S);
+}
+
 // The trace kernel of a binned frame over the tables binned_pass left: the camera's in S, the light cubes' in L (transient) or
 // in the shared cache.
 int binned_trace(const RtFrame &f, RtScratch &S, RtScratch &L, const BinnedPass &bp)

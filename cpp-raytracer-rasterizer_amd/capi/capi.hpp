@@ -92,7 +92,9 @@ int fail(int code, const char *fmt, ...);
 enum { EV_CALL0 = 0, EV_CALL1 = 1, EV_K0 = 2, EV_COUNT = 2 + 2 * 8 };
 constexpr int MAX_FLIGHT = 4;                    // most frames in flight (mirt_set_frames_in_flight): one HIP stream and one set of scratch each
 constexpr int SEL_COUNT0 = 80;                   // word of d_bin_counters where the two selection counters start
-constexpr int HIST_RING = 4;
+constexpr int HIST_SEL_COUNT = 82;               // ... and the two of a histogram-only pass (hist_only_pass), apart from a frame's
+constexpr int HIST_RING = 4;                     // pinned copies of the cost histograms sharded calls file (the weighted partition reads them) ...
+constexpr int HIST_SLOTS = HIST_RING + 1;        // ... and one behind them for frames outside sharded calls (mirt_cost_histogram only)
 constexpr size_t HIT_BYTES = sizeof(unsigned long long) * HIT_SHARDS * HIT_SHARD_STRIDE;   // one hit-counter buffer (rt_common.hpp: count_hits)
 
 // What a frame of the brute-force / binned ray-trace paths writes besides the caller's planes: one set per stream, so
@@ -145,13 +147,14 @@ struct RtScratch {
     size_t cap_face_sel = 0;                     // slots
     uint32_t *d_face_counts = nullptr;           // 6 * MIRT_MAX_LIGHTS words (inside d_bin_counters' block)
     // the cost histogram of the whole frame (weighted partition): device words, and where they travel for the host to read --
-    // HIST_RING pinned copies taken in turn, an event behind each
+    // HIST_RING pinned copies that sharded calls take in turn, and slot HIST_RING for frames outside them; an event behind each
     uint32_t *d_hist = nullptr;
-    uint32_t *h_hist = nullptr;                  // pinned: HIST_RING x SEL_HIST_MAX words
-    hipEvent_t ev_hist[HIST_RING] = {};
-    uint64_t hist_key[HIST_RING] = {};           // what frame (view, scene) each copy belongs to; 0 = none
-    int hist_rows[HIST_RING] = {}, hist_shift[HIST_RING] = {};
-    int hist_next = 0;
+    uint32_t *h_hist = nullptr;                  // pinned: HIST_SLOTS x SEL_HIST_MAX words
+    hipEvent_t ev_hist[HIST_SLOTS] = {};
+    uint64_t hist_key[HIST_SLOTS] = {};          // the sharded call a copy was filed under + 1 (slot HIST_RING: any non-zero); 0 = none
+    uint64_t hist_seq[HIST_SLOTS] = {};          // when it was filed (Ctx::hist_seq): the newest copy of all streams is mirt_cost_histogram's
+    int hist_rows[HIST_SLOTS] = {}, hist_shift[HIST_SLOTS] = {};
+    int hist_next = 0;                           // the ring's next slot
 
     void forget_scene() { bin_key_valid = false; have_known = false; count_pending = false; }   // tables and pair counts belong to the old scene
     void release();
@@ -284,7 +287,8 @@ struct Ctx {
                                                  // MIRT_PARTITION_WEIGHTED = bands of equal estimated cost (mirt_set_partition)
     bool want_hist = false;                      // binned ray-traced frames leave their cost histogram (mirt_set_cost_histogram, or the weighted partition)
     uint64_t shard_calls = 0;                    // sharded calls so far: what a cost histogram is filed under
-    bool hist_taken = false;                     // the current sharded call has filed its histogram (the first binned pass of a call does)
+    bool hist_call = false;                      // inside a sharded call: the pass being enqueued files the call's histogram (render_sharded)
+    uint64_t hist_seq = 0;                       // cost histograms filed so far, on any stream
     bool in_sharded = false;
     bool hist_armed = false;                     // hist_prepare armed the pass that is being enqueued
 
@@ -341,6 +345,10 @@ struct BinnedPass {
 };
 int binned_pass(const RtFrame &f, const mirt_view *view, RtScratch &S, RtScratch &L, const float *origins, int nlights, int y0, int y1, BinnedPass *bp);
 int binned_trace(const RtFrame &f, RtScratch &S, RtScratch &L, const BinnedPass &bp);
+// Would rt_enqueue bin the WHOLE frame of this view (mode, scene size, operands in range, frame size)?  The same answer on every rank.
+bool rt_bins_whole_frame(const mirt_view *view, const mirt_light *lights, int nlights, int mode);
+// The cost histogram of a view's whole frame and nothing else, on the current stream (render_sharded).
+int hist_only_pass(const mirt_view *view);
 
 // ---- rasteriser (raster.cpp) ----
 int raster_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect,

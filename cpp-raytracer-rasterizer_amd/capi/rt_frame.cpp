@@ -106,6 +106,40 @@ static bool finite_below(const float *p, int n, float lim)
     return true;
 }
 
+// The pre-reject filter is proven for finite, moderate operands only (rt_common.hpp); anything else (absurd coordinates, NaN/Inf)
+// renders through the exact-only path.  Ray directions of the primary rays are bounded by 3 * max|rot| * max(W, H, |focal|).
+// `origins`: the camera and the npos light positions.
+static bool operands_safe(const mirt_view *view, const float *origins, int npos)
+{
+    float rmax = 0.0f;
+    for (int i = 0; i < 9; i++) rmax = fmaxf(rmax, fabsf(view->rot[i]));
+    const float dmax = 3.0f * rmax * fmaxf(fmaxf((float)view->width, (float)view->height), fabsf(view->focal));
+    return g.scene_finite && finite_below(view->rot, 9, 1.0e6f) && (dmax < 1.0e6f) &&
+           finite_below(origins, 3 * (1 + npos), 1.0e8f);      // camera and light positions
+}
+
+// MIRT_RT_AUTO bins when the scene is beyond the tile kernel (65 triangles or more) and the brute-force work, pixels x
+// triangles, is above ~4e7: binning + sorting costs ~40 us whatever the scene, brute force ~7.5e-10 ms per pixel-triangle
+// (tools/threshold_sweep.py at 1080p: 65 triangles 0.099 vs 0.043 ms, 300: 0.47 vs 0.079, 800: 1.13 vs 0.097).
+static bool mode_bins(const mirt_view *view, int mode, int rows)
+{
+    static const int auto_threshold = (int)env_int("MIRT_BIN_THRESHOLD", 65);
+    return (mode == MIRT_RT_BINNED) ||
+           (mode == MIRT_RT_AUTO && g.n >= auto_threshold && (long long)view->width * rows > 4096 &&
+            (long long)view->width * rows * g.n >= 40000000LL);
+}
+
+bool rt_bins_whole_frame(const mirt_view *view, const mirt_light *lights, int nlights, int mode)
+{
+    const int samples = g.soft_samples > 1 ? g.soft_samples : 1;
+    const int npos = nlights * samples;
+    if (!view || nlights < 0 || (nlights && !lights) || npos > MIRT_MAX_LIGHTS || (samples > 1 && npos > g.soft_npos)) return false;
+    float origins[(1 + MIRT_MAX_LIGHTS) * 3];
+    memcpy(origins, view->pos, 12);
+    for (int j = 0; j < npos; j++) memcpy(origins + 3 * (j + 1), samples > 1 ? g.soft_pos + 3 * j : lights[j / samples].pos, 12);
+    return mode_bins(view, mode, view->height) && operands_safe(view, origins, npos) && frame_fits_binning(view->width, view->height);
+}
+
 // The frames that are not binned.  Scenes of at most 64 triangles (the reference's Cornell box has 30): per-tile candidate
 // masks, one lane per triangle (rt_tile.hip), when the operands are inside the filter's proven range; other small scenes: one
 // launch, every table built in LDS by the workgroup itself -- no origin-table kernel, no global loads inside the loops; the
@@ -204,23 +238,10 @@ int rt_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, con
     float origins[(1 + MIRT_MAX_LIGHTS) * 3];
     make_rt_frame(f, origins, view, lights, nlights, indirect, y0, y1, row_origin, d_xrgb, pitch_bytes, d_rgb, d_index, d_fd, d_dist, d_pos);
     nlights = light_positions;                   // from here on "lights" means light positions
-    // The pre-reject filter is proven for finite, moderate operands only (rt_common.hpp); anything else
-    // (absurd coordinates, NaN/Inf) renders through the exact-only path.  Ray directions of the primary
-    // rays are bounded by 3 * max|rot| * max(W, H, |focal|).
-    float rmax = 0.0f;
-    for (int i = 0; i < 9; i++) rmax = fmaxf(rmax, fabsf(view->rot[i]));
-    const float dmax = 3.0f * rmax * fmaxf(fmaxf((float)view->width, (float)view->height), fabsf(view->focal));
-    const bool safe = g.scene_finite && finite_below(view->rot, 9, 1.0e6f) && (dmax < 1.0e6f) &&
-                      finite_below(origins, 3 * (1 + nlights), 1.0e8f);      // camera and light positions
+    const bool safe = operands_safe(view, origins, nlights);
 
     // ---- mode: brute force for small scenes, binned otherwise; unsafe operands always render exact brute ----
-    // MIRT_RT_AUTO bins when the scene is beyond the tile kernel (65 triangles or more) and the brute-force work, pixels x
-    // triangles, is above ~4e7: binning + sorting costs ~40 us whatever the scene, brute force ~7.5e-10 ms per pixel-triangle
-    // (tools/threshold_sweep.py at 1080p: 65 triangles 0.099 vs 0.043 ms, 300: 0.47 vs 0.079, 800: 1.13 vs 0.097).
-    static const int auto_threshold = (int)env_int("MIRT_BIN_THRESHOLD", 65);
-    bool binned = (mode == MIRT_RT_BINNED) ||
-                  (mode == MIRT_RT_AUTO && g.n >= auto_threshold && (long long)view->width * (y1 - y0) > 4096 &&
-                   (long long)view->width * (y1 - y0) * g.n >= 40000000LL);
+    bool binned = mode_bins(view, mode, y1 - y0);
     if (!safe) binned = false;
     if (binned && !frame_fits_binning(view->width, view->height)) {
         // more 8 x 8-pixel tiles than one sort pass has keys (a frame beyond ~23 000 x 23 000 pixels)

@@ -5,12 +5,15 @@
 
 namespace mirt {
 
-// The cost histogram of a binned pass (k_prep_select).  // Wanted when the caller asked for it or the partition is the weighted one, and then from ONE pass per sharded call -- the
-// first -- so that every rank files the same sequence.  hist_prepare points the pass at the device words (zero between passes:
-// k_hist_out leaves them so); hist_publish sends them to the next pinned copy of the ring, tagged with the sharded call they
-// belong to, an event behind them.
-static bool hist_wanted() { return (g.want_hist || g.strip_rows == MIRT_PARTITION_WEIGHTED) && !(g.in_sharded && g.hist_taken); }
+// The cost histogram of a binned pass (k_prep_select).  Outside sharded calls: wanted when the caller asked for it or the partition
+// is the weighted one, filed into a slot of its own that only mirt_cost_histogram reads.  Inside a sharded call: render_sharded
+// decides (g.hist_call) -- view 0's histogram, exactly once per call, into the ring the weighted partition reads -- so that what a
+// rank files depends on the call and the settings alone, never on its band, on what its stream binned before or on frames it
+// rendered outside sharded calls.  hist_prepare points the pass at the device words (zero between passes: k_hist_out leaves them
+// so); hist_publish sends them to the pinned copy, tagged with the sharded call they belong to, an event behind them.
+static bool hist_wanted() { return g.in_sharded ? g.hist_call : (g.want_hist || g.strip_rows == MIRT_PARTITION_WEIGHTED); }
 static int hist_shift_for(int tile_rows) { int sh = 0; while (((tile_rows - 1) >> sh) + 1 > SEL_HIST_MAX) sh++; return sh; }
+static int hist_slot(const RtScratch &S) { return g.in_sharded ? S.hist_next : HIST_RING; }
 int hist_prepare(RtScratch &S, const BinFrameDesc &cam, SelectOut *so)
 {
     g.hist_armed = false;
@@ -18,13 +21,14 @@ int hist_prepare(RtScratch &S, const BinFrameDesc &cam, SelectOut *so)
     if (!S.d_hist) {
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_hist), sizeof(uint32_t) * SEL_HIST_MAX));
         HIP_TRY(hipMemsetAsync(S.d_hist, 0, sizeof(uint32_t) * SEL_HIST_MAX, g.stream));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&S.h_hist), sizeof(uint32_t) * SEL_HIST_MAX * HIST_RING, hipHostMallocDefault));
-        for (int i = 0; i < HIST_RING; i++) HIP_TRY(hipEventCreateWithFlags(&S.ev_hist[i], hipEventDisableTiming));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&S.h_hist), sizeof(uint32_t) * SEL_HIST_MAX * HIST_SLOTS, hipHostMallocDefault));
+        for (int i = 0; i < HIST_SLOTS; i++) HIP_TRY(hipEventCreateWithFlags(&S.ev_hist[i], hipEventDisableTiming));
     }
     so->hist = S.d_hist;
     so->hist_shift = hist_shift_for(cam.nbv);
-    const int slot = S.hist_next;
-    // (the copy about to be overwritten was filed HIST_RING passes ago; a reader only ever looks at copies whose event has fired)
+    const int slot = hist_slot(S);
+    // (the copy about to be overwritten was filed HIST_RING sharded calls ago, or is the stream's previous one outside them; a
+    // reader only ever looks at copies whose event has fired)
     S.hist_key[slot] = 0;
     S.hist_rows[slot] = ((cam.nbv - 1) >> so->hist_shift) + 1;
     S.hist_shift[slot] = so->hist_shift;
@@ -35,33 +39,39 @@ int hist_publish(RtScratch &S)
 {
     if (!g.hist_armed) return MIRT_OK;
     g.hist_armed = false;
-    const int slot = S.hist_next;
+    const int slot = hist_slot(S);
     uint32_t *dst = nullptr;
     HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&dst), S.h_hist + (size_t)slot * SEL_HIST_MAX, 0));
     hist_out(S.d_hist, dst, g.stream);
     HIP_TRY(hipEventRecord(S.ev_hist[slot], g.stream));
     S.hist_key[slot] = g.shard_calls + 1;        // filed under the sharded call in progress (+1: 0 means "no copy"); outside one, the calls so far
-    S.hist_next = (slot + 1) % HIST_RING;
-    if (g.in_sharded) g.hist_taken = true;
+    S.hist_seq[slot] = ++g.hist_seq;
+    if (g.in_sharded) {
+        S.hist_next = (slot + 1) % HIST_RING;
+        g.hist_call = false;
+    }
     return MIRT_OK;
 }
 
-// The newest cost histogram of stream 0's ring that was filed under a sharded call <= max_key (0: any) -- waiting for its
-// event if it has not fired yet.  NULL when there is none.
+// max_key > 0: the newest cost histogram a sharded call <= max_key filed (the ring); 0: the newest one filed at all, in or outside
+// sharded calls -- on any stream, waiting for its event if it has not fired yet.  NULL when there is none.  (Sharded calls file
+// in call order, so the copy filed last is also the one of the latest call.)
 const uint32_t *hist_lookup(uint64_t max_key, int *rows, int *shift)
 {
-    RtScratch &S = g.streams[0].rt;
+    RtScratch *B = nullptr;
     int best = -1;
-    for (int i = 0; i < HIST_RING; i++) {
-        // ring order breaks ties between copies of one key (outside sharded calls every copy carries the same one): the one filed last
-        const int slot = (S.hist_next + HIST_RING - 1 - i) % HIST_RING;
-        if (!S.h_hist || S.hist_key[slot] == 0 || (max_key && S.hist_key[slot] > max_key)) continue;
-        if (best < 0 || S.hist_key[slot] > S.hist_key[best]) best = slot;
+    for (StreamState &ss : g.streams) {
+        RtScratch &S = ss.rt;
+        if (!S.h_hist) continue;
+        for (int slot = 0; slot < (max_key ? HIST_RING : HIST_SLOTS); slot++) {
+            if (S.hist_key[slot] == 0 || (max_key && S.hist_key[slot] > max_key)) continue;
+            if (!B || S.hist_seq[slot] > B->hist_seq[best]) { B = &S; best = slot; }
+        }
     }
-    if (best < 0) return nullptr;
-    if (hipEventSynchronize(S.ev_hist[best]) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    *rows = S.hist_rows[best]; *shift = S.hist_shift[best];
-    return S.h_hist + (size_t)best * SEL_HIST_MAX;
+    if (!B) return nullptr;
+    if (hipEventSynchronize(B->ev_hist[best]) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    *rows = B->hist_rows[best]; *shift = B->hist_shift[best];
+    return B->h_hist + (size_t)best * SEL_HIST_MAX;
 }
 
 // pairs-equivalents a tile costs whatever its list holds (part_weighted_bounds); MIRT_PART_TILE_WEIGHT overrides
@@ -73,10 +83,9 @@ unsigned part_tile_weight()
 
 // The bands of the sharded call about to be issued (call number g.shard_calls): equal bands, or -- weighted partition -- bands of
 // equal estimated cost from the histogram filed under the call before the previous one (or an earlier one).  Every rank of a group
-// issues the same calls with the same views, files a histogram in the first binned pass of each call and looks TWO calls back,
-// by which time that pass has long run: same histogram on every rank (integer sums over the same triangles), same integer
-// arithmetic, same bands -- no exchange.  A rank that skipped a pass because nothing had changed (rt_enqueue_binned: reuse) holds an
-// older copy of the SAME view's histogram, i.e. the same numbers.
+// issues the same calls with the same views; a ray-traced call whose whole frame would be binned files view 0's histogram on
+// every rank (render_sharded), and the bands look TWO calls back, by which time that pass has long run: same histogram on every
+// rank (integer sums over the same triangles, whatever rows a rank renders), same integer arithmetic, same bands -- no exchange.
 void current_bounds(int world, int W, int H, std::vector<int> &bounds)
 {
     bounds.assign((size_t)world + 1, 0);
@@ -128,12 +137,22 @@ int render_sharded(const mirt_view *views, int nviews, int root, void *d_frames,
     const size_t frame_bytes = (size_t)H * (size_t)pitch_bytes;
     // (a sharded call is what cost histograms are filed under, one per call: current_bounds)
     struct CallScope {
-        CallScope() { g.in_sharded = true; g.hist_taken = false; }
-        ~CallScope() { g.in_sharded = false; g.shard_calls++; }
+        CallScope() { g.in_sharded = true; g.hist_call = false; }
+        ~CallScope() { g.in_sharded = false; g.hist_call = false; g.shard_calls++; }
     } scope;
+    // The call's histogram: view 0's whole frame, filed when the call's arguments and the settings say so -- the same on every
+    // rank.  The pass of this rank's own rows of view 0 files it when it bins afresh (the histogram does not depend on the rows a
+    // pass renders); a band that is rendered brute force, keeps its stream's pass or is empty gets a histogram-only pass right
+    // behind view 0 instead (before the later views' passes, which the next call may keep).  No other pass of the call files one.
+    g.hist_call = !raster && (g.want_hist || g.strip_rows == MIRT_PARTITION_WEIGHTED) && rt_bins_whole_frame(&views[0], lights, nlights, mode);
+    auto view_done = [&](int v) -> int {
+        const int r = (v == 0 && g.hist_call) ? hist_only_pass(&views[0]) : MIRT_OK;
+        g.hist_call = false;
+        return r;
+    };
     if (world == 1) {
         for (int v = 0; v < nviews; v++)
-            if ((rc = render(&views[v], 0, H, 0, static_cast<char *>(d_frames) + (size_t)v * frame_bytes, pitch_bytes))) return rc;
+            if ((rc = render(&views[v], 0, H, 0, static_cast<char *>(d_frames) + (size_t)v * frame_bytes, pitch_bytes)) || (rc = view_done(v))) return rc;
         return MIRT_OK;
     }
     // this rank's rows: one contiguous band -- an equal share of the rows, or of the estimated cost (weighted partition) --, or
@@ -148,12 +167,14 @@ int render_sharded(const mirt_view *views, int nviews, int root, void *d_frames,
     g.band_slot ^= 1;
     if (rank == root) {
         // the root's own rows are rendered in place; the other ranks' rows arrive straight at their places
-        for (int v = 0; v < nviews; v++)
+        for (int v = 0; v < nviews; v++) {
             for (int k = 0; k < segs; k++) {
                 int y0, y1;
                 part_segment(rank, world, H, strips, k, &y0, &y1, bounds);
                 if (y1 > y0 && (rc = render(&views[v], y0, y1, 0, static_cast<char *>(d_frames) + (size_t)v * frame_bytes, pitch_bytes))) return rc;
             }
+            if ((rc = view_done(v))) return rc;
+        }
     } else {
         const size_t need = my_bytes * (size_t)nviews;
         HIP_TRY(hipStreamWaitEvent(g.stream, g.ev_sent[slot], 0));         // the gather that last read this buffer has finished
@@ -175,6 +196,7 @@ int render_sharded(const mirt_view *views, int nviews, int root, void *d_frames,
                 if (y1 > y0 && (rc = render(&views[v], y0, y1, y0 - before, g.d_band[slot] + (size_t)v * my_bytes, (int)band_row))) return rc;
                 before += y1 - y0;
             }
+            if ((rc = view_done(v))) return rc;
         }
     }
     // the one exchange step: every band to the root, on the communication stream, overlapping the next call's render

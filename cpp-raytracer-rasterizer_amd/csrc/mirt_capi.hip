@@ -616,8 +616,9 @@ extern "C" int mirt_bounds_plan(int world, int root, int width, int height, int 
 {
     if (world < 1 || root < 0 || root >= world || width < 1 || height < 0 || nviews < 1 || max_pieces < 0 || !bounds)
         return fail(MIRT_ERR_INVALID_ARGUMENT, "bounds plan: world %d root %d frame %dx%d views %d", world, root, width, height, nviews);
+    if (bounds[0] != 0 || bounds[world] != height) return fail(MIRT_ERR_INVALID_ARGUMENT, "bounds plan: boundaries must start at 0 and end at %d", height);
     for (int r = 0; r < world; r++)
-        if (bounds[r] < 0 || bounds[r + 1] < bounds[r] || bounds[r + 1] > height) return fail(MIRT_ERR_INVALID_ARGUMENT, "bounds plan: boundaries must rise from 0 to %d", height);
+        if (bounds[r + 1] < bounds[r]) return fail(MIRT_ERR_INVALID_ARGUMENT, "bounds plan: boundaries must rise from 0 to %d", height);
     return plan_out(world, root, width, height, nviews, 0, bounds, root_offset, band_offset, bytes, peer, max_pieces);
 }
 

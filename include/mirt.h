@@ -300,14 +300,20 @@ MIRT_API int mirt_band_plan(int world, int root, int width, int height, int nvie
  *   MIRT_PARTITION_WEIGHTED   contiguous bands of equal ESTIMATED COST instead of equal height: the counterpart of
  *                     `schedule(auto)` for a frame whose rows differ in what they cost (a triangle soup seen in perspective: the
  *                     middle bands of BASELINE configs[4] hold twice the candidates of the outer ones).  The first kernel of
- *                     a binned ray-traced frame leaves an estimate of the (tile, triangle) pairs per tile row of the WHOLE frame;
- *                     every rank computes the same numbers from the same scene and view, and the bands of sharded call c come
- *                     from the histogram of call c - 2 by integer arithmetic -- identical on every rank, nothing exchanged.
- *                     Equal bands until a histogram exists (the first two calls, frames that take another path).
+ *                     a binned ray-traced frame leaves an estimate of the (tile, triangle) pairs per tile row of the WHOLE frame,
+ *                     whatever rows it renders.  A ray-traced sharded call whose whole frame would be binned (its mode, the scene,
+ *                     the frame size and the settings decide: the same on every rank) files view 0's estimate on every rank --
+ *                     from the pass of the rank's own band, or from a histogram-only pass where that band is rendered brute
+ *                     force, keeps the pass of an earlier call or is empty; no other pass of the call files one, and frames
+ *                     outside sharded calls never do.  The bands of sharded call c come from the newest estimate filed by a
+ *                     call before c - 1, by integer arithmetic -- identical on every rank, nothing exchanged.  Equal bands
+ *                     until a histogram exists (the first two calls, calls that file none).
  * mirt_weighted_bounds: that arithmetic as a pure function (world + 1 boundaries, multiples of 8 rows, from a histogram of
  * hist_rows coarse tile rows of (1 << hist_shift) tile rows each); mirt_partition_bounds: the boundaries the NEXT sharded call
- * will use; mirt_bounds_plan: the gather's messages for explicit boundaries; mirt_set_cost_histogram(1) makes binned frames
- * leave the histogram outside sharded calls too and mirt_cost_histogram returns the latest one (returns its row count, 0: none). */
+ * will use; mirt_bounds_plan: the gather's messages for explicit boundaries (bounds[0] == 0 <= ... <= bounds[world] == height);
+ * mirt_set_cost_histogram(1) makes binned frames leave the histogram outside sharded calls too (into a copy of its own that the
+ * partition never reads) and mirt_cost_histogram returns the newest one, whichever stream filed it (returns its row count,
+ * 0: none). */
 #define MIRT_PARTITION_WEIGHTED (-1)
 MIRT_API int mirt_set_partition(int strip_rows);
 MIRT_API int mirt_set_cost_histogram(int on);

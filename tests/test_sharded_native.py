@@ -8,6 +8,7 @@ single-GPU frames byte for byte -- ray tracer (tile and binned kernels) and rast
 GPU CAN run of the RCCL transport: a group of one rank -- the library is loaded (beside PyTorch's copy too), the communicator
 created, a grouped ncclSend + ncclRecv to the rank itself compared byte for byte (mirt_comm_selfcheck), a sharded call made.
 """
+import json
 import os
 import subprocess
 import sys
@@ -174,6 +175,18 @@ def test_explicit_bounds_and_their_gather_plan(world, root, W, H, nviews):
         mirt.bounds_plan(world, root, W, H, nviews, [0] + [H + 8] * world)
 
 
+@pytest.mark.parametrize("world,H", [(2, 40), (3, 100), (1, 9)])
+def test_bounds_plan_rejects_boundaries_that_do_not_span_the_frame(world, H):
+    """Boundaries that leave rows out at the top or the bottom are no partition of the frame: a plan built from them would gather a
+    frame with rows nobody sends."""
+    inner = [min(8 * r, H) for r in range(1, world)]
+    plan = mirt.bounds_plan(world, 0, 16, H, 1, [0] + inner + [H])
+    assert sum(p[2] for p in plan) == (H - inner[0] if inner else 0) * 16 * 4
+    for bad in ([8] + inner + [H], [0] + inner + [H - 1], [1] + inner + [H - 1], [0] + inner + [max(inner + [0])]):
+        with pytest.raises(mirt.MirtError):
+            mirt.bounds_plan(world, 0, 16, H, 1, bad)
+
+
 def test_cpp_world_size_2_partition_and_assembly(tmp_path):
     """tests/cpp/band_plan_test.cpp: one process per rank, bands through pipes in plan order, every word checked."""
     exe = str(tmp_path / "band_plan_test")
@@ -275,6 +288,183 @@ def test_sharded_frames_through_the_loopback_transport(tmp_path, world, root, st
     assert all(p.returncode == 0 for p in procs), "\n".join(outs)
 
 
+AGREE_CODE = r"""
+import json, os, sys, time, numpy as np
+sys.path[:0] = [%(pkg)r, %(tests)r]
+import mirt
+from devbuf import DeviceArray
+rank, world, root, idfile, logdir, seq = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]), sys.argv[4], sys.argv[5], sys.argv[6]
+mirt.init(rank if os.environ.get("MIRT_TEST_DEVICE_PER_RANK") == "1" else 0)
+if rank == 0:
+    cid = mirt.comm_create_id()
+    with open(idfile + ".tmp", "wb") as f: f.write(cid)
+    os.rename(idfile + ".tmp", idfile)
+else:
+    while not os.path.exists(idfile): time.sleep(0.01)
+    cid = open(idfile, "rb").read()
+mirt.comm_init(cid, rank, world)
+mirt.set_frames_in_flight(1)
+mirt.set_partition(mirt.PARTITION_WEIGHTED)
+L = np.array([[0.0, -0.5, -0.7, 1, 1, 1, 14]], np.float32)
+IND = (0.2, 0.2, 0.2)
+# about 2 000 triangles packed in a horizontal slab above the middle of the frame: most of the cost lies in a few tile rows near
+# the top, so the weighted bands there are thin and the bottom one is tall
+tris = mirt.scene_soup(7, 2000, 0.06)
+for k in (1, 4, 7):
+    tris[:, k] = tris[:, k] * np.float32(0.08) - np.float32(0.45)
+W, H = (160 if world == 2 else 320), 240      # (two ranks: a narrow frame, whose MIRT_RT_AUTO threshold -- 125 rows -- the top band stays below)
+nviews, mode, ncalls = 1, mirt.RT_AUTO, 12
+if seq == "b":
+    nviews, mode = 2, mirt.RT_BINNED
+elif seq == "c":
+    mode = mirt.RT_BINNED
+    if os.environ.get("MIRT_TEST_HIST") == "1" and rank == 0:
+        mirt.set_cost_histogram(1)
+elif seq == "d":
+    mode, H, ncalls = mirt.RT_BINNED, 8 * (world - 1) - 1, 10    # fewer tile rows than ranks: some band is empty
+mirt.scene_upload(tris)
+def view(i):
+    # the camera moves every call: sideways, turning, and up and down so that the slab (and with it the cost) moves between rows
+    return mirt.make_view((0.03 * i, 0.35 * np.sin(0.7 * i), -2.6), mirt.rot_from_yaw(0.02 * i, 1.0), 200.0, W, H)
+def kind_of(c):
+    return "raster" if seq == "d" and c == 5 else "rt"
+def check_agreement(c, bounds):
+    with open(os.path.join(logdir, "c%%d_r%%d.tmp" %% (c, rank)), "w") as f: json.dump(bounds, f)
+    os.rename(os.path.join(logdir, "c%%d_r%%d.tmp" %% (c, rank)), os.path.join(logdir, "c%%d_r%%d.json" %% (c, rank)))
+    deadline, table = time.time() + 60.0, {}
+    while len(table) < world:
+        for r in range(world):
+            p = os.path.join(logdir, "c%%d_r%%d.json" %% (c, r))
+            if r not in table and os.path.exists(p):
+                table[r] = json.load(open(p))
+        if len(table) < world:
+            if time.time() > deadline:
+                print("rank %%d: call %%d: no bounds from ranks %%s within 60 s" %% (rank, c, sorted(set(range(world)) - set(table))), flush=True)
+                os._exit(4)
+            time.sleep(0.005)
+    if any(table[r] != table[0] for r in range(world)):
+        # a plan the ranks disagree on must never reach the gather: the grouped send / receive would wait forever
+        print("rank %%d: call %%d (%%s, seq %%s): the ranks derived different bounds:" %% (rank, c, kind_of(c), seq), flush=True)
+        for r in range(world):
+            print("  rank %%d: %%s" %% (r, table[r]), flush=True)
+        os._exit(3)
+frames, calls = [], []
+for c in range(ncalls):
+    views = [view(c + k) for k in range(nviews)]              # (seq b: view 1 of call c is view 0 of call c + 1)
+    bounds = mirt.partition_bounds(world, W, H)
+    check_agreement(c, bounds)
+    kind = kind_of(c)
+    buf = DeviceArray((nviews, H, W), np.uint32, 0x33) if rank == root else None
+    mirt.prepared_sharded(kind, views, L, IND, mode, root, buf.ptr if buf else None, W * 4)()
+    frames.append(buf)
+    calls.append((kind, views, bounds))
+    if seq == "c" and rank == 0 and c in (3, 6):
+        # frames outside sharded calls, on rank 0 alone: one, later five in a row (binned, whole frames, views of their own)
+        with DeviceArray((H, W), np.uint32) as own:
+            for k in range(1 if c == 3 else 5):
+                mirt.raytrace_device(view(40 + 3 * k + c), L, IND, mirt.RT_BINNED, 0, H, 0, own.ptr, W * 4)
+            mirt.sync()
+mirt.sync()
+ok = True
+if rank == root:
+    for c, ((kind, views, bounds), buf) in enumerate(zip(calls, frames)):
+        got = buf.read()
+        for i, v in enumerate(views):
+            with DeviceArray((H, W), np.uint32, 0x33) as ref:
+                if kind == "rt":
+                    mirt.raytrace_device(v, L, IND, mode, 0, H, 0, ref.ptr, W * 4)
+                else:
+                    mirt.rasterise_device(v, L, IND, 0, H, 0, ref.ptr, W * 4)
+                want = ref.read()
+            if kind == "rt":
+                # border words: the ray tracer never writes them -- the root's own rows keep the caller's fill, received bands carry 0
+                border = np.zeros((H, W), bool)
+                border[0, :] = border[-1, :] = True; border[:, 0] = border[:, -1] = True
+                own = np.zeros((H, W), bool)
+                own[bounds[root]:bounds[root + 1]] = True
+                want[border & own] = 0x33333333
+                want[border & ~own] = 0
+            if not np.array_equal(got[i], want):
+                ok = False
+                print("MISMATCH call", c, kind, "view", i, int((got[i] != want).sum()), "bounds", bounds, flush=True)
+        buf.free()
+mirt.comm_shutdown()
+mirt.shutdown()
+print("rank %%d done ok=%%s" %% (rank, ok), flush=True)
+sys.exit(0 if ok else 1)
+"""
+
+
+def _run_ranks(code, world, args, env, timeout=600):
+    procs = [subprocess.Popen([sys.executable, "-c", code, str(r), str(world)] + list(args), env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+             for r in range(world)]
+    outs = []
+    for p in procs:
+        try:
+            out, _ = p.communicate(timeout=timeout)
+        except subprocess.TimeoutExpired:
+            for q in procs:
+                q.kill()
+            raise
+        outs.append(out)
+    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+
+
+def _logged_bounds(logdir, world):
+    """The bounds every call used, as the ranks logged them before the call (they agree, or the run has failed already)."""
+    calls = []
+    while os.path.exists(os.path.join(logdir, "c%d_r0.json" % len(calls))):
+        calls.append(json.load(open(os.path.join(logdir, "c%d_r0.json" % len(calls)))))
+    return calls
+
+
+def _auto_bins(rows, W, n=2000):
+    """capi/rt_frame.cpp: the rows of a band that MIRT_RT_AUTO bins (what decides whether a band's pass files anything)."""
+    return n >= 65 and W * rows > 4096 and W * rows * n >= 40000000
+
+
+def _assert_trigger(seq, world, calls):
+    """That the situation each sequence is about really arose -- decided from the logged bounds (the inputs of every rank's
+    choice), not from what the library did with them."""
+    bands = [[b[r + 1] - b[r] for r in range(world)] for b in calls]
+    equal = [mirt.band_of(r, world, 240)[0] for r in range(world)] + [240]
+    if seq == "a":
+        # in some call, one rank's band is binned by MIRT_RT_AUTO and another's is rendered brute force (AGREE_CODE's frame width)
+        W = 160 if world == 2 else 320
+        assert any(len({_auto_bins(rows, W) for rows in rs}) == 2 for rs in bands), calls
+    elif seq == "b":
+        # in some call, one rank's band is the one it had in the call before (its pass of view 0 can be kept) and another's moved
+        assert any(any(a[r:r + 2] == b[r:r + 2] for r in range(world)) and any(a[r:r + 2] != b[r:r + 2] for r in range(world))
+                   for a, b in zip(calls, calls[1:])), calls
+    elif seq == "c":
+        # the calls after rank 0's frames of its own used cost-weighted bands
+        assert all(b != equal for b in calls[8:]), calls
+    elif seq == "d":
+        # some rank's band is empty
+        assert any(0 in rs for rs in bands), calls
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seq,world,root,hist", [("a", 2, 0, 0), ("a", 3, 2, 0), ("b", 3, 0, 0), ("b", 3, 1, 0),
+                                                  ("c", 2, 1, 0), ("c", 3, 0, 1), ("c", 2, 0, 1), ("d", 2, 1, 0), ("d", 3, 0, 0)])
+def test_ranks_derive_the_same_weighted_bounds_on_every_call(tmp_path, seq, world, root, hist):
+    """MIRT_PARTITION_WEIGHTED: every rank derives the band boundaries of every sharded call from its own copy of the cost
+    histogram, nothing exchanged.  Before each call every rank logs mirt_partition_bounds and waits for the
+    others'; ranks that disagree stop there, before a plan they disagree on can reach the gather.  The sequences are the ways a
+    rank's own history could make it file other histograms than its peers: (a) MIRT_RT_AUTO with bands on both sides of the
+    binning threshold; (b) two views per call, the second the next call's first, so that a rank whose band did not move could keep
+    its pass of view 0; (c) frames rank 0 alone renders between sharded calls, with and without mirt_set_cost_histogram(1); (d) a
+    frame shorter than 8 rows per rank (empty bands) and a rasterised call in the ray-traced sequence.  Each asserts that its
+    situation arose; the root's frames must equal single-GPU frames.  (Sequence (b) needs three ranks: with two, both bands move
+    whenever the one boundary does.)"""
+    code = AGREE_CODE % {"pkg": os.path.join(ROOT, "cpp-raytracer-rasterizer_amd"), "tests": os.path.join(ROOT, "tests")}
+    env = dict(os.environ, MIRT_COMM="shm", MIRT_TEST_HIST=str(hist))
+    logdir = tmp_path / "bounds"
+    logdir.mkdir()
+    _run_ranks(code, world, [str(root), str(tmp_path / "comm_id"), str(logdir), seq], env)
+    _assert_trigger(seq, world, _logged_bounds(str(logdir), world))
+
+
 SELF_CODE = r"""
 import os, sys, numpy as np
 sys.path[:0] = [%(pkg)r, %(tests)r]
@@ -350,6 +540,14 @@ def test_sharded_frames_over_rccl_on_two_devices(tmp_path, strip):
             raise
         outs.append(out)
     assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+    if strip == -1:
+        # and every rank derives the same weighted bounds on every call over RCCL too (the sequences of the loopback test above)
+        code = AGREE_CODE % {"pkg": os.path.join(ROOT, "cpp-raytracer-rasterizer_amd"), "tests": os.path.join(ROOT, "tests")}
+        for seq in ("a", "c", "d"):
+            logdir = tmp_path / ("bounds_" + seq)
+            logdir.mkdir()
+            _run_ranks(code, 2, ["0", str(tmp_path / ("comm_id_" + seq)), str(logdir), seq], dict(env, MIRT_TEST_HIST="1"))
+            _assert_trigger(seq, 2, _logged_bounds(str(logdir), 2))
 
 
 @pytest.mark.gpu
