@@ -1,6 +1,7 @@
 // capi.hpp -- the host side of the C-ABI (csrc/mirt_capi.hip and the files of this directory): the library's state, one
-// StreamState per frame in flight inside one Ctx, and the helpers the topic files share.  Host code only: every kernel is
-// defined under csrc/ (tools/check_spills.py compiles those files); the ones launched from here are declared below.
+// StreamState per frame in flight inside one Ctx, and the helpers the topic files share.  Host code only: the frame kernels are
+// defined under csrc/ and the ray-query kernels under query/ (tools/check_spills.py compiles both directories); the ones
+// launched from here are declared below and in query/rt_query.hpp.
 #pragma once
 
 #include "../csrc/bin_sort.hpp"
@@ -11,6 +12,7 @@
 #include "../csrc/raster_common.hpp"
 #include "../csrc/rt_binned.hpp"
 #include "../csrc/scan.hpp"
+#include "../query/rt_query.hpp"
 #include "env.hpp"
 
 #include <cstdarg>
@@ -21,7 +23,7 @@
 #include <cmath>
 #include <vector>
 
-// (a kernel DECLARATION: the definitions live in csrc/)
+// (a kernel DECLARATION: the definitions live in csrc/ and query/)
 #define MIRT_KERNEL __attribute__((global))
 
 namespace mirt {
@@ -195,6 +197,33 @@ struct DofPlanes {
     void release();
 };
 
+// What a DirectLight query (query.cpp) writes besides the caller's colours: the origin tables of its light positions, apart from
+// the stream's frame tables, so that a query between two frames disturbs nothing a kept binning pass counts on.
+struct QueryScratch {
+    OriginRow *d_light_tab = nullptr;            // tab_lights x tab_n rows
+    int tab_n = 0, tab_lights = 0;
+    float *d_origins = nullptr;                  // (1 + MIRT_MAX_LIGHTS) x 3; row 0 (the camera's place) is unused
+    uint32_t *d_flags = nullptr;                 // [0] = unsafe flag
+    uint64_t rows_seen = 0;                      // the QueryRows::version this stream is already ordered behind (0 = none)
+
+    void release();
+};
+
+// The ray-independent rows of ClosestIntersection (k_query_rows): built once per scene version on the stream of the query that
+// finds them missing, shared by every stream; a query on another stream waits for ev_built, not for the device.
+struct QueryRows {
+    QueryRow *d_rows = nullptr;
+    int n = 0;                                   // rows allocated
+    uint32_t *d_max = nullptr;                   // QMAX_WORDS words: scene-wide maxima
+    uint64_t version = 0;                        // scene_version the rows were built for (0 = none)
+    hipEvent_t ev_built = nullptr;
+    // staging of the host-buffer entry points (mirt_intersect, mirt_direct_light)
+    void *d_rays = nullptr, *d_hits = nullptr, *d_rgb = nullptr;
+    size_t cap = 0;                              // rays / records each holds
+
+    void release();
+};
+
 // Everything a frame in flight owns: its stream and the scratch its kernels write.  A frame reads the scene and writes the
 // caller's planes plus its own stream's state, so frames on different streams need no ordering among themselves (call_begin).
 struct StreamState {
@@ -222,6 +251,7 @@ struct StreamState {
     DofPlanes dof;
     void *d_async = nullptr;                     // the XRGB plane of an asynchronous frame (async_plane)
     RasterScratch raster;
+    QueryScratch query;
     // cull flags: what this stream's copy of d_culled holds -- the number of the cull call (or upload) it comes from --, and the
     // copies OUT of other streams' copies it has made: the event is re-recorded behind every such copy ...
     uint64_t culled_ver = 0;
@@ -256,6 +286,7 @@ struct Ctx {
     ShadeRow *d_shade = nullptr;                 // n shading rows (likewise)
     float bbox_lo[3] = { 0, 0, 0 }, bbox_hi[3] = { 0, 0, 0 };   // the scene's bounding box (host side, mirt_scene_upload)
     LightCache lc;
+    QueryRows qrows;
     unsigned long long *d_hits = nullptr;        // the hit-counter buffer of the current ray-traced frame (one of its stream's d_hits)
     bool scene_finite = true;                    // all vertex coordinates below MIRT_SAFE_MAG
     uint64_t scene_version = 0;                  // bumped whenever the triangles change
@@ -319,6 +350,7 @@ int check_frame_args(const mirt_view *view, const mirt_light *lights, int nlight
                      bool need_scene = false, int y0 = 0, int y1 = 0);
 hipError_t sync_all();
 int next_si();
+void stream_begin();                             // the part of call_begin() that takes the next stream (calls that leave the statistics alone)
 void call_begin();
 void call_end();
 inline void k_begin(int k) { if (g.profiling) { (void)hipEventRecord(g.cur().ev[EV_K0 + 2 * k], g.stream); g.cur().ev_used[k] = true; } }
@@ -349,6 +381,12 @@ int binned_trace(const RtFrame &f, RtScratch &S, RtScratch &L, const BinnedPass 
 bool rt_bins_whole_frame(const mirt_view *view, const mirt_light *lights, int nlights, int mode);
 // The cost histogram of a view's whole frame and nothing else, on the current stream (render_sharded).
 int hist_only_pass(const mirt_view *view);
+
+// ---- ray queries (query.cpp) ----
+int query_intersect(const void *d_rays, int nrays, void *d_hits);
+int query_intersect_host(const mirt_ray *rays, int nrays, mirt_hit *hits);
+int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_rgb);
+int query_direct_light_host(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, float *out_rgb);
 
 // ---- rasteriser (raster.cpp) ----
 int raster_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect,

@@ -1,0 +1,218 @@
+// query.cpp -- ray queries: ClosestIntersection and DirectLight for the caller's own rays and records (mirt_intersect*,
+// mirt_direct_light*; the kernels: ../query/rt_query.hip).  The ray-independent rows of the scene are built once per scene
+// version and shared by the streams; a query takes the next stream as a frame does (mirt_set_frames_in_flight, mirt_sync) but
+// leaves the statistics of the last render call alone.
+#include "capi.hpp"
+
+namespace mirt {
+
+// Which kernel answers mirt_intersect*: one wave per ray while the rays are at most MIRT_QUERY_WAVE_RAYS (0: never; a huge value:
+// always), a lane per ray beyond.  A wave per ray finishes a ray's triangle list 64 lanes wide, so it is ahead until the lane-per-ray
+// grid fills the chip too; both kernels walk the same list, so the triangle count hardly moves the crossing.  The default is the
+// frame path's figure for its own wave kernel (rt_frame.cpp: at most 4096 rays); tools/ray_query_bench.py sweeps both kernels over
+// 1 .. 2^20 rays and reports where the curves cross (profiles/ray_query_bench.txt).
+constexpr long QUERY_WAVE_RAYS_DEFAULT = 4096;
+static long query_wave_rays()
+{
+    static const long v = env_int("MIRT_QUERY_WAVE_RAYS", QUERY_WAVE_RAYS_DEFAULT);
+    return v;
+}
+
+// The rows of the current scene on the current stream: built here when the scene changed (mirt_scene_upload waited for every
+// stream, so nothing still reads the old ones), otherwise this stream is ordered behind the build once, by its event.
+static int query_rows()
+{
+    int rc;
+    QueryRows &Q = g.qrows;
+    QueryScratch &S = g.cur().query;
+    if (Q.version != g.scene_version) {
+        Q.version = 0;
+        if (Q.n != g.n) {
+            Q.n = 0;
+            if ((rc = dev_realloc(&Q.d_rows, (size_t)g.n))) return rc;
+            Q.n = g.n;
+        }
+        if (!Q.d_max) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&Q.d_max), sizeof(uint32_t) * QMAX_WORDS));
+        if (!Q.ev_built) HIP_TRY(hipEventCreateWithFlags(&Q.ev_built, hipEventDisableTiming));
+        HIP_TRY(hipMemsetAsync(Q.d_max, 0, sizeof(uint32_t) * QMAX_WORDS, g.stream));
+        hipLaunchKernelGGL(k_query_rows, dim3((unsigned)((g.n + 255) / 256)), dim3(256), 0, g.stream, g.d_tris, g.n, Q.d_rows, Q.d_max);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(Q.ev_built, g.stream));
+        Q.version = g.scene_version;
+        S.rows_seen = Q.version;
+    } else if (S.rows_seen != Q.version) {
+        HIP_TRY(hipStreamWaitEvent(g.stream, Q.ev_built, 0));
+        S.rows_seen = Q.version;
+    }
+    return MIRT_OK;
+}
+
+static int check_query_args(const void *in, int count, const void *out, const char *what)
+{
+    int rc;
+    if ((rc = need_init())) return rc;
+    if (count < 0) return fail(MIRT_ERR_INVALID_ARGUMENT, "%s count %d is negative", what, count);
+    if (count > 0 && (!in || !out)) return fail(MIRT_ERR_INVALID_ARGUMENT, "%s arrays must not be NULL when the count is > 0", what);
+    return MIRT_OK;
+}
+
+static int need_scene()
+{
+    if (g.n <= 0) return fail(MIRT_ERR_NO_SCENE, "no scene uploaded (mirt_scene_upload)");
+    return MIRT_OK;
+}
+
+int query_intersect(const void *d_rays, int nrays, void *d_hits)
+{
+    int rc;
+    if ((rc = check_query_args(d_rays, nrays, d_hits, "ray"))) return rc;
+    if (nrays == 0) return MIRT_OK;
+    if ((rc = need_scene())) return rc;
+    stream_begin();
+    if ((rc = query_rows())) return rc;
+    QueryFrame q;
+    q.rows = g.qrows.d_rows;
+    q.n = g.n;
+    q.scene_max = g.qrows.d_max;
+    q.scene_finite = g.scene_finite ? 1 : 0;
+    q.rays = static_cast<const float *>(d_rays);
+    q.nrays = nrays;
+    q.hits = static_cast<uint32_t *>(d_hits);
+    if ((long)nrays <= query_wave_rays()) {
+        hipLaunchKernelGGL(k_query_closest_wave, dim3((unsigned)((nrays + 3) / 4)), dim3(256), 0, g.stream, q);
+    } else {
+        const size_t lds = (size_t)(g.n < RT_CHUNK_ROWS ? g.n : RT_CHUNK_ROWS) * sizeof(QueryRow);
+        hipLaunchKernelGGL(k_query_closest<QUERY_P>, dim3((unsigned)((nrays + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), lds, g.stream, q);
+    }
+    HIP_TRY(hipGetLastError());
+    return MIRT_OK;
+}
+
+// The checks rt_enqueue makes on the lights and the soft-shadow state, with its messages.
+static int check_lights(const mirt_light *lights, int nlights, int *light_positions)
+{
+    if (nlights < 0 || nlights > MIRT_MAX_LIGHTS) return fail(MIRT_ERR_INVALID_ARGUMENT, "nlights %d out of range [0,%d]", nlights, MIRT_MAX_LIGHTS);
+    if (nlights > 0 && !lights) return fail(MIRT_ERR_INVALID_ARGUMENT, "lights must not be NULL when nlights > 0");
+    const int samples = g.soft_samples > 1 ? g.soft_samples : 1;
+    *light_positions = nlights * samples;                    // shadow-ray origins
+    if (*light_positions > MIRT_MAX_LIGHTS)
+        return fail(MIRT_ERR_INVALID_ARGUMENT, "%d lights x %d soft-shadow samples exceed %d light positions", nlights, samples, MIRT_MAX_LIGHTS);
+    if (samples > 1 && *light_positions > g.soft_npos)
+        return fail(MIRT_ERR_INVALID_ARGUMENT, "%d jittered positions needed, %d were set (mirt_set_soft_shadows)", *light_positions, g.soft_npos);
+    return MIRT_OK;
+}
+
+int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_rgb)
+{
+    int rc, npos = 0;
+    if ((rc = check_query_args(d_hits, nhits, d_rgb, "hit"))) return rc;
+    if ((rc = check_lights(lights, nlights, &npos))) return rc;
+    if (nhits == 0) return MIRT_OK;
+    if ((rc = need_scene())) return rc;
+
+    QueryLightFrame q;
+    memset(&q, 0, sizeof q);
+    RtFrame &f = q.f;
+    f.tris15 = g.d_tris;
+    f.n = g.n;
+    // the light positions the shadow rays start from and their share of the light's power, as a frame sets them up
+    // (rt_frame.cpp: make_rt_frame; raytracer.cpp:282-296)
+    const int samples = g.soft_samples > 1 ? g.soft_samples : 1;
+    f.nlights = npos;
+    f.samples = samples;
+    float origins[(1 + MIRT_MAX_LIGHTS) * 3] = {};
+    bool safe = g.scene_finite;
+    for (int j = 0; j < npos; j++) {
+        const int k = j / samples;
+        const float *pos = samples > 1 ? g.soft_pos + 3 * j : lights[k].pos;
+        memcpy(f.lpos[j], pos, 12);
+        memcpy(origins + 3 * (j + 1), pos, 12);
+        for (int c = 0; c < 3; c++) {
+            f.lcol[j][c] = (lights[k].color[c] * lights[k].intensity) / (float)samples;
+            if (!(fabsf(pos[c]) < MIRT_QUERY_START_MAX)) safe = false;      // a shadow ray's start (rt_frame.cpp: operands_safe)
+        }
+    }
+    q.hits = static_cast<const uint32_t *>(d_hits);
+    q.nhits = nhits;
+    q.rgb = static_cast<float *>(d_rgb);
+
+    stream_begin();
+    // origin tables of the query's own: k_prep_origin into the stream's frame tables would overwrite the camera rows a kept
+    // binning pass counts on (rt_frame.cpp: rt_dispatch_brute)
+    QueryScratch &S = g.cur().query;
+    if (npos > S.tab_lights || S.tab_n != g.n) {
+        S.tab_lights = 0;
+        if ((rc = dev_realloc(&S.d_light_tab, (size_t)npos * g.n))) return rc;
+        S.tab_lights = npos;
+        S.tab_n = g.n;
+    }
+    if (!S.d_origins) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_origins), sizeof origins));
+    if (!S.d_flags) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_flags), 16));
+    f.light_tab = S.d_light_tab;
+    f.unsafe = S.d_flags;
+    const uint32_t flags_init[4] = { safe ? 0u : 1u, 0u, 0u, 0u };
+    HIP_TRY(upload_small(S.d_flags, flags_init, sizeof flags_init, g.stream));
+    if (npos > 0) {
+        HIP_TRY(upload_small(S.d_origins, origins, sizeof(float) * 3 * (1 + npos), g.stream));
+        // origins 1 .. npos only: the launch never touches a camera table
+        hipLaunchKernelGGL(k_prep_origin, dim3((unsigned)((g.n + 255) / 256), (unsigned)npos), dim3(256), 0, g.stream,
+                           g.d_tris, g.n, S.d_origins, V3(0.0f, 0.0f, 0.0f), 1, (OriginRow *)nullptr, S.d_light_tab, S.d_flags,
+                           (unsigned long long *)nullptr, (uint32_t *)nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    const size_t lds = (size_t)(g.n < RT_CHUNK_ROWS ? g.n : RT_CHUNK_ROWS) * sizeof(OriginRow);
+    hipLaunchKernelGGL(k_query_direct_light<QUERY_P>, dim3((unsigned)((nhits + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), lds, g.stream, q);
+    HIP_TRY(hipGetLastError());
+    return MIRT_OK;
+}
+
+// ---- host buffers: staged through library-owned device arrays, complete on return ----
+
+static int query_staging(size_t count)
+{
+    int rc;
+    QueryRows &Q = g.qrows;
+    if (count <= Q.cap) return MIRT_OK;
+    Q.cap = 0;
+    if ((rc = dev_realloc_bytes(&Q.d_rays, count * sizeof(mirt_ray)))) return rc;
+    if ((rc = dev_realloc_bytes(&Q.d_hits, count * sizeof(mirt_hit)))) return rc;
+    if ((rc = dev_realloc_bytes(&Q.d_rgb, count * 3 * sizeof(float)))) return rc;
+    Q.cap = count;
+    return MIRT_OK;
+}
+
+int query_intersect_host(const mirt_ray *rays, int nrays, mirt_hit *hits)
+{
+    int rc;
+    if ((rc = check_query_args(rays, nrays, hits, "ray"))) return rc;
+    if (nrays == 0) return MIRT_OK;
+    if ((rc = need_scene())) return rc;
+    if ((rc = query_staging((size_t)nrays))) return rc;
+    QueryRows &Q = g.qrows;
+    hipStream_t st = g.streams[next_si()].stream;            // the stream the query below will take
+    HIP_TRY(hipMemcpyAsync(Q.d_rays, rays, (size_t)nrays * sizeof(mirt_ray), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(Q.d_hits, hits, (size_t)nrays * sizeof(mirt_hit), hipMemcpyHostToDevice, st));
+    if ((rc = query_intersect(Q.d_rays, nrays, Q.d_hits))) return rc;
+    HIP_TRY(hipMemcpyAsync(hits, Q.d_hits, (size_t)nrays * sizeof(mirt_hit), hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return MIRT_OK;
+}
+
+int query_direct_light_host(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, float *out_rgb)
+{
+    int rc, npos = 0;
+    if ((rc = check_query_args(hits, nhits, out_rgb, "hit"))) return rc;
+    if ((rc = check_lights(lights, nlights, &npos))) return rc;
+    if (nhits == 0) return MIRT_OK;
+    if ((rc = need_scene())) return rc;
+    if ((rc = query_staging((size_t)nhits))) return rc;
+    QueryRows &Q = g.qrows;
+    hipStream_t st = g.streams[next_si()].stream;
+    HIP_TRY(hipMemcpyAsync(Q.d_hits, hits, (size_t)nhits * sizeof(mirt_hit), hipMemcpyHostToDevice, st));
+    if ((rc = query_direct_light(Q.d_hits, nhits, lights, nlights, Q.d_rgb))) return rc;
+    HIP_TRY(hipMemcpyAsync(out_rgb, Q.d_rgb, (size_t)nhits * 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return MIRT_OK;
+}
+
+}  // namespace mirt

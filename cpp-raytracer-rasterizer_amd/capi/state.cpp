@@ -52,14 +52,18 @@ int next_si() { return g.in_flight > 1 ? (g.si + 1) % g.in_flight : 0; }
 // other's gaps.  A frame reads the scene and writes the caller's planes plus its OWN stream's state (origin tables, bins,
 // raster keys, depth-of-field planes, counters), so frames need no ordering among themselves; frames i and i + in_flight,
 // which a caller cycling through in_flight sets of planes gives the same planes, share a stream.
-void call_begin()
+void stream_begin()
 {
     g.si = next_si();
-    StreamState &ss = g.cur();
-    g.stream = ss.stream;
+    g.stream = g.cur().stream;
     g.frame_no++;
     (void)hipGetLastError();                     // drop a stale error of another HIP user in this thread (torch polls events:
                                                  // hipErrorNotReady) so that the launch checks below report our own launches only
+}
+void call_begin()
+{
+    stream_begin();
+    StreamState &ss = g.cur();
     memset(&g.stats, 0, sizeof g.stats);
     g.stats_sel_count = nullptr;
     g.ev_cur = g.si;
@@ -87,6 +91,19 @@ void RtScratch::release()
     *this = RtScratch();
 }
 
+void QueryScratch::release()
+{
+    for (void *p : { (void *)d_light_tab, (void *)d_origins, (void *)d_flags }) if (p) (void)hipFree(p);
+    *this = QueryScratch();
+}
+
+void QueryRows::release()
+{
+    for (void *p : { (void *)d_rows, (void *)d_max, d_rays, d_hits, d_rgb }) if (p) (void)hipFree(p);
+    if (ev_built) (void)hipEventDestroy(ev_built);
+    *this = QueryRows();
+}
+
 void LightCache::release()
 {
     for (void *p : { (void *)d_light_tab, (void *)d_frames, (void *)d_off, (void *)d_rows, (void *)d_row_tri, (void *)d_origins, (void *)d_counter })
@@ -110,6 +127,7 @@ void StreamState::release()
     rt.release();
     rt_lt.release();
     raster_scratch_free(raster);
+    query.release();
     dof.release();
     for (void *p : { (void *)d_hits[0], (void *)d_hits[1], (void *)d_tile_tab, d_async }) if (p) (void)hipFree(p);
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);

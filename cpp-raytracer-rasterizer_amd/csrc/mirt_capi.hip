@@ -146,6 +146,7 @@ extern "C" void mirt_shutdown(void)
     comm_destroy(g.comm);
     for (StreamState &ss : g.streams) ss.release();
     g.lc.release();
+    g.qrows.release();
     for (void *p : { (void *)g.d_tris, (void *)g.d_culled, (void *)g.d_geo, (void *)g.d_shade, g.d_xrgb, g.d_rgb, g.d_index, g.d_zinv, g.d_pos,
                      (void *)g.d_band[0], (void *)g.d_band[1] })
         if (p) (void)hipFree(p);
@@ -428,6 +429,19 @@ extern "C" int mirt_raytrace_async(const mirt_view *view, const mirt_light *ligh
     return deliver_async(view, lights, nlights, indirect, out_xrgb, pitch_bytes, false, [&](void *x, int pitch) {
         return mirt_raytrace_device_ex(view, lights, nlights, indirect, mode, 0, view->height, 0, x, pitch, nullptr, nullptr, nullptr, nullptr);
     });
+}
+
+// ---- ray queries (../capi/query.cpp; the kernels: ../query/rt_query.hip) ------------------------------------------------
+
+extern "C" int mirt_intersect(const mirt_ray *rays, int nrays, mirt_hit *hits) { return query_intersect_host(rays, nrays, hits); }
+extern "C" int mirt_intersect_device(const void *d_rays, int nrays, void *d_hits) { return query_intersect(d_rays, nrays, d_hits); }
+extern "C" int mirt_direct_light(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, float *out_rgb)
+{
+    return query_direct_light_host(hits, nhits, lights, nlights, out_rgb);
+}
+extern "C" int mirt_direct_light_device(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_rgb)
+{
+    return query_direct_light(d_hits, nhits, lights, nlights, d_rgb);
 }
 
 // ---- rasteriser -------------------------------------------------------------------------------------

@@ -48,6 +48,10 @@ static_assert(sizeof(RasterTriangle) == 64, "rasteriser Triangle is 64 bytes");
 struct Light { vec3 position, color; float intensity; };
 static_assert(sizeof(Light) == sizeof(mirt_light), "Light must match mirt_light");
 
+// struct Intersection of the ray tracer (raytracer.cpp:91-96): 20 bytes, what mirt_intersect / mirt_direct_light take as they are
+struct Intersection { vec3 position; float distance; int triangleIndex; };
+static_assert(sizeof(Intersection) == sizeof(mirt_hit), "Intersection must match mirt_hit");
+
 // the fields of SDL_Surface that PutPixelSDL uses (SDLauxiliary.h:72-79)
 struct Surface { uint32_t *pixels; int w, h; int pitch; };
 
@@ -136,13 +140,35 @@ struct RayTracer {
     }
     static void Present() { check(mirt_sync(), "mirt_sync"); }
 
+    // ClosestIntersection(start, dir, triangles, closestIntersection) (:202-257) for n rays of the caller's own: closest[k] is the
+    // in/out record of the call for ray k -- Update()'s reset (distance = FLT_MAX, :335-339) for a fresh query, or the record an
+    // earlier ray left -- and comes back as n calls of the reference would leave it.
+    void ClosestIntersection(const vec3 *start, const vec3 *dir, Intersection *closest, int n)
+    {
+        upload_scene();
+        std::vector<mirt_ray> rays((size_t)n);
+        for (int k = 0; k < n; k++) { std::memcpy(rays[k].start, &start[k].x, 12); std::memcpy(rays[k].dir, &dir[k].x, 12); }
+        check(mirt_intersect(rays.data(), n, reinterpret_cast<mirt_hit *>(closest)), "mirt_intersect");
+    }
+    // DirectLight(i) (:265-327) for n records, with the lights and the soft-shadow toggle as they stand: result[k] = DirectLight(i[k]).
+    void DirectLight(const Intersection *i, vec3 *result, int n)
+    {
+        marshal();
+        check(mirt_direct_light(reinterpret_cast<const mirt_hit *>(i), n, reinterpret_cast<const mirt_light *>(lights), NUM_LIGHTS, &result[0].x),
+              "mirt_direct_light");
+    }
+
 private:
-    mirt_view marshal()                                            // the globals -> the POD arguments of mirt.h
+    void upload_scene()
     {
         if (scene_dirty) {
             check(mirt_scene_upload(&triangles[0].v0.x, nullptr, (int)triangles.size()), "mirt_scene_upload");
             scene_dirty = false;
         }
+    }
+    mirt_view marshal()                                            // the globals -> the POD arguments of mirt.h
+    {
+        upload_scene();
         check(mirt_set_antialiasing(AA_ENABLED ? AA_SAMPLES : 1), "mirt_set_antialiasing");   // realSamples (:549-554)
         if (SOFT_SHADOWS_ENABLED)                                  // DirectLight's `samples` (:272-275)
             check(mirt_set_soft_shadows(SOFT_SHADOWS_SAMPLES, &randomPositions[0].x, NUM_LIGHTS * SOFT_SHADOWS_SAMPLES), "mirt_set_soft_shadows");

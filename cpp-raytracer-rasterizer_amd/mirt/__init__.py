@@ -24,6 +24,7 @@ EXPORTS = (
     "mirt_rasterise_device", "mirt_get_stats", "mirt_get_previous_kernel_ms", "mirt_surface_register", "mirt_surface_unregister", "mirt_raytrace_async", "mirt_rasterise_async",
     "mirt_band_of", "mirt_band_plan", "mirt_set_partition", "mirt_partition_segments", "mirt_partition_plan",
     "mirt_set_cost_histogram", "mirt_cost_histogram", "mirt_weighted_bounds", "mirt_partition_bounds", "mirt_bounds_plan", "mirt_comm_create_id", "mirt_comm_init", "mirt_comm_shutdown", "mirt_comm_selfcheck", "mirt_raytrace_sharded", "mirt_rasterise_sharded",
+    "mirt_intersect", "mirt_intersect_device", "mirt_direct_light", "mirt_direct_light_device",
 )
 
 
@@ -46,6 +47,20 @@ class Stats(C.Structure):
                 ("steps_primary", C.c_uint64), ("steps_shadow", C.c_uint64), ("drains", C.c_uint64),
                 ("bins_reused", C.c_uint32), ("selected_triangles", C.c_uint32)]
 
+
+class Ray(C.Structure):
+    """mirt_ray: the `start` and `dir` arguments of one ClosestIntersection call (24 bytes)."""
+    _fields_ = [("start", C.c_float * 3), ("dir", C.c_float * 3)]
+
+
+class Hit(C.Structure):
+    """mirt_hit == struct Intersection (raytracer.cpp:91-96): position, distance, triangleIndex (20 bytes)."""
+    _fields_ = [("position", C.c_float * 3), ("distance", C.c_float), ("index", C.c_int32)]
+
+
+# the same two layouts for numpy: arrays of rays / hit records travel as they are
+RAY_DTYPE = np.dtype([("start", np.float32, 3), ("dir", np.float32, 3)])
+HIT_DTYPE = np.dtype([("position", np.float32, 3), ("distance", np.float32), ("index", np.int32)])
 
 _vp = C.c_void_p
 _lib = None
@@ -104,6 +119,10 @@ def load():
     lib.mirt_comm_selfcheck.argtypes = [C.c_size_t]
     lib.mirt_raytrace_sharded.argtypes = [C.POINTER(View), C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int]
     lib.mirt_rasterise_sharded.argtypes = [C.POINTER(View), C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int]
+    lib.mirt_intersect.argtypes = [_vp, C.c_int, _vp]
+    lib.mirt_intersect_device.argtypes = [_vp, C.c_int, _vp]
+    lib.mirt_direct_light.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp]
+    lib.mirt_direct_light_device.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp]
     _lib = lib
     return lib
 
@@ -390,6 +409,62 @@ def prepared_async(kind, view, lights7, indirect, mode, surface):
         if rc:
             _check(rc)
     return launch
+
+
+# ---- ray queries: ClosestIntersection / DirectLight for the caller's own rays -------------------------
+
+def make_rays(start, direction):
+    """(n, 3) starts and directions (either may be one vector for all) -> n rays (RAY_DTYPE)."""
+    s, d = np.asarray(start, np.float32), np.asarray(direction, np.float32)
+    n = max(s.reshape(-1, 3).shape[0], d.reshape(-1, 3).shape[0])
+    rays = np.zeros(n, RAY_DTYPE)
+    rays["start"], rays["dir"] = s, d
+    return rays
+
+
+def fresh_hits(n):
+    """n records as Update() resets them (raytracer.cpp:335-339): distance FLT_MAX, index -1, position 0."""
+    hits = np.zeros(int(n), HIT_DTYPE)
+    hits["distance"] = np.finfo(np.float32).max
+    hits["index"] = -1
+    return hits
+
+
+def _as_rays(rays):
+    rays = np.asarray(rays)
+    if rays.dtype != RAY_DTYPE:
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6).view(RAY_DTYPE).reshape(-1)
+    return np.ascontiguousarray(rays)
+
+
+def intersect(rays, hits=None):
+    """One ClosestIntersection call per ray against the uploaded scene (mirt_intersect).  rays: RAY_DTYPE or (n, 6) floats;
+    hits: the in/out records (HIT_DTYPE; fresh ones when None).  Returns the records after the calls (a new array)."""
+    rays = _as_rays(rays)
+    hits = fresh_hits(len(rays)) if hits is None else np.ascontiguousarray(hits, HIT_DTYPE).copy()
+    if len(hits) != len(rays):
+        raise ValueError("%d rays but %d hit records" % (len(rays), len(hits)))
+    _check(load().mirt_intersect(_ptr(rays), len(rays), _ptr(hits)))
+    return hits
+
+
+def intersect_device(d_rays, nrays, d_hits):
+    """The same on device arrays (raw pointers), queued like a *_device frame; mirt.sync() completes it."""
+    _check(load().mirt_intersect_device(d_rays, int(nrays), d_hits))
+
+
+def direct_light(hits, lights7):
+    """DirectLight(hits[i]) for every record (mirt_direct_light): (n, 3) float32."""
+    hits = np.ascontiguousarray(hits, HIT_DTYPE)
+    larr, nl = make_lights(lights7)
+    out = np.zeros((len(hits), 3), np.float32)
+    _check(load().mirt_direct_light(_ptr(hits), len(hits), larr, nl, _ptr(out)))
+    return out
+
+
+def direct_light_device(d_hits, nhits, lights7, d_rgb):
+    larr, nl = make_lights(lights7)
+    _check(load().mirt_direct_light_device(d_hits, int(nhits), larr, nl, d_rgb))
 
 
 # ---- several GPUs: band sharding with the gather inside the library ------------------------------------

@@ -1,0 +1,390 @@
+// rt_query.hip -- hand-written gfx950 kernels for ray queries: ClosestIntersection (raytracer/Source/raytracer.cpp:202-257) and
+// DirectLight (:265-327) as the free functions they are in the reference, called with rays and Intersection records of the
+// caller's own (a mirror bounce, a pick, an occlusion probe, a second light pass) instead of the camera's.
+//
+// The frame kernels (csrc/) hoist everything of a test that depends on the ray ORIGIN into a per-origin table, because all their
+// rays leave one point.  Caller rays share no origin, so here only what depends on no ray at all is hoisted -- v0, e1, e2 and
+// e1e2 = cross(e1, e2), one 48-byte QueryRow per triangle (k_query_rows) -- and b = start - v0, be2, e1b and e1e2b are computed
+// per (ray, triangle), in the reference's order: 41 non-fused operations a test against 15 of the frame kernels.  The accept
+// arithmetic, the conservative filter in front of it and the wave reduction are the shared primitives of csrc/rt_common.hpp.
+// Built with -ffp-contract=off like every kernel of the library.
+//
+// Filter safety.  maybe_hit (rt_common.hpp) never rejects a test the reference accepts PROVIDED every operand of the three dot
+// products is finite and below MIRT_SAFE_MAG = 1e18 in magnitude.  The frame path establishes that on the
+// host; rays that live in device memory cannot be inspected there, so each kernel decides per ray, once, outside the triangle
+// loop (ray_exact_only):
+//   * the rows: with V = max |v0|, E1 = max |e1|, E2 = max |e2| over all components of the scene (k_query_rows leaves them as
+//     float bits, a NaN ordering above everything) and |start| < 1e8 per component, every |b| component is below B = 1e8 + V, so
+//     every component of be2 = cross(b, e2) is below 2 B E2 and of e1b = cross(e1, b) below 2 E1 B (two products each); the
+//     scene passes when 2 B max(E1, E2) < 1e18 and max |e1e2| < 1e18 (with all coordinates below 1e8 -- scene_finite -- both hold:
+//     B < 2e8, E < 2e8, so 8e16).  e1e2b only feeds t = e1e2b / e1e2d and is not an operand of the filter.
+//   * the ray: every |dir| component below 1e6, so each product of a dot is below 1e24 and each sum finite.
+// These are the bounds of the frame path (rt_frame.cpp: operands_safe, rt_common.hpp: origin_row_safe).  A ray outside them --
+// huge, infinite or NaN components -- runs every test through the exact divisions (its filter verdict is overridden, whatever
+// it was).  The filter only ever skips tests the exact path would reject, so no result depends on which path a ray took.
+#include "rt_query.hpp"
+
+#include <float.h>
+
+namespace mirt {
+
+// ---- k_query_rows: the ray-independent part of ClosestIntersection, once per scene ----------------------------------
+// One thread per triangle.  scene_max (QMAX_WORDS words, zeroed before the launch) receives the largest |component| of each of
+// the four vectors as float bits: a butterfly over the wave, then one atomic per wave and word.
+__global__ __launch_bounds__(256) void k_query_rows(const float *__restrict__ tris15, int n, QueryRow *__restrict__ rows,
+                                                    uint32_t *__restrict__ scene_max)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t m[QMAX_WORDS] = { 0u, 0u, 0u, 0u };
+    if (i < n) {
+        const float *t = tris15 + (size_t)15 * i;
+        const v3 v0 = ld3(t), v1 = ld3(t + 3), v2 = ld3(t + 6);
+        const v3 e1 = sub3(v1, v0), e2 = sub3(v2, v0);             // :216-217
+        const v3 e1e2 = cross3(e1, e2);                            // :225
+        QueryRow r;
+        r.a = make_float4(v0.x, v0.y, v0.z, e1.x);
+        r.b = make_float4(e1.y, e1.z, e2.x, e2.y);
+        r.c = make_float4(e2.z, e1e2.x, e1e2.y, e1e2.z);
+        rows[i] = r;
+        const v3 vec[QMAX_WORDS] = { v0, e1, e2, e1e2 };
+#pragma unroll
+        for (int k = 0; k < QMAX_WORDS; k++) {
+            const uint32_t x = __float_as_uint(vec[k].x) & 0x7fffffffu, y = __float_as_uint(vec[k].y) & 0x7fffffffu,
+                           z = __float_as_uint(vec[k].z) & 0x7fffffffu;
+            m[k] = max(max(x, y), z);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < QMAX_WORDS; k++) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) m[k] = max(m[k], (uint32_t)__shfl_xor((int)m[k], d));
+        if ((threadIdx.x & 63) == 0 && m[k]) atomicMax(scene_max + k, m[k]);
+    }
+}
+
+// Whether the rows of the scene are inside the filter's range for every start below MIRT_QUERY_START_MAX (header comment);
+// wave-uniform: four scalar loads and a handful of scalar-unit operations.
+__device__ __forceinline__ bool scene_rows_in_range(const QueryFrame &q)
+{
+    const float V = __uint_as_float(q.scene_max[QMAX_V0]), E1 = __uint_as_float(q.scene_max[QMAX_E1]),
+                E2 = __uint_as_float(q.scene_max[QMAX_E2]), X = __uint_as_float(q.scene_max[QMAX_E1E2]);
+    const float B = MIRT_QUERY_START_MAX + V;
+    // (comparisons are false for NaN: a NaN anywhere in the scene sends every ray down the exact path)
+    return q.scene_finite && 2.0f * B * E1 < MIRT_SAFE_MAG && 2.0f * B * E2 < MIRT_SAFE_MAG && X < MIRT_SAFE_MAG;
+}
+
+// A ray whose operands are not provably inside the filter's range: it takes the exact path for every triangle.
+__device__ __forceinline__ bool ray_exact_only(bool scene_ok, v3 start, v3 dir)
+{
+    const bool in_range = fabsf(start.x) < MIRT_QUERY_START_MAX && fabsf(start.y) < MIRT_QUERY_START_MAX && fabsf(start.z) < MIRT_QUERY_START_MAX &&
+                          fabsf(dir.x) < MIRT_QUERY_DIR_MAX && fabsf(dir.y) < MIRT_QUERY_DIR_MAX && fabsf(dir.z) < MIRT_QUERY_DIR_MAX;
+    return !(scene_ok && in_range);
+}
+
+struct RowVecs { v3 v0, e1, e2, e1e2; };
+__device__ __forceinline__ RowVecs unpack_row(const float4 &a, const float4 &b, const float4 &c)
+{
+    RowVecs r;
+    r.v0 = V3(a.x, a.y, a.z); r.e1 = V3(a.w, b.x, b.y); r.e2 = V3(b.z, b.w, c.x); r.e1e2 = V3(c.y, c.z, c.w);
+    return r;
+}
+
+// One ray against one row: b, be2, e1b, e1e2b (:218, :226-227, :231), then the three dots against negD (:232-234).
+__device__ __forceinline__ TestDots ray_dots(const RowVecs &r, v3 start, v3 nd, float *e1e2b)
+{
+    const v3 b = sub3(start, r.v0);
+    const v3 be2 = cross3(b, r.e2), e1b = cross3(r.e1, b);
+    *e1e2b = r.e1e2.x * b.x + r.e1e2.y * b.y + r.e1e2.z * b.z;
+    TestDots d;
+    d.den = r.e1e2.x * nd.x + r.e1e2.y * nd.y + r.e1e2.z * nd.z;
+    d.pu = be2.x * nd.x + be2.y * nd.y + be2.z * nd.z;
+    d.qv = e1b.x * nd.x + e1b.y * nd.y + e1b.z * nd.z;
+    return d;
+}
+
+// glm::cross for two rays per lane: x.y * y.z - y.y * x.z, ... (mirt_math.hpp: cross3), every operation packed.
+__device__ __forceinline__ v3p cross3p(const v3p &x, const v3p &y)
+{
+    return V3P(x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y);
+}
+
+// The same for the two rays of a lane, packed FP32: each v_pk_* rounds its halves like the scalar instruction.
+__device__ __forceinline__ TestDots2 ray_dots2(const RowVecs &r, const v3p &start, const v3p &nd, f2 *e1e2b)
+{
+    const v3p e1 = splat3(r.e1), e2 = splat3(r.e2), x = splat3(r.e1e2);
+    // (b one half at a time: written as a packed subtraction of splat(v0) the compiler pairs the neighbouring words of the row's
+    // 128-bit reads and realigns the odd pairs through 16 bytes of scratch; v_sub_f32 rounds like either half of v_pk_add_f32)
+    v3p b;
+    b.x = (f2){ start.x.x - r.v0.x, start.x.y - r.v0.x };
+    b.y = (f2){ start.y.x - r.v0.y, start.y.y - r.v0.y };
+    b.z = (f2){ start.z.x - r.v0.z, start.z.y - r.v0.z };
+    const v3p be2 = cross3p(b, e2), e1b = cross3p(e1, b);
+    *e1e2b = x.x * b.x + x.y * b.y + x.z * b.z;
+    TestDots2 d;
+    d.den = x.x * nd.x + x.y * nd.y + x.z * nd.z;
+    d.pu = be2.x * nd.x + be2.y * nd.y + be2.z * nd.z;
+    d.qv = e1b.x * nd.x + e1b.y * nd.y + e1b.z * nd.z;
+    return d;
+}
+
+// The accept test, hit point and distance as the reference computes them (:237-242), from the row alone.
+__device__ __forceinline__ bool exact_hit_row(const TestDots &d, float e1e2b, const RowVecs &r, v3 start, v3 *pos, float *dist)
+{
+    const float t = e1e2b / d.den, u = d.pu / d.den, v = d.qv / d.den;
+    if (u + v <= 1.0f && u >= 0.0f && v >= 0.0f && t >= 0.0f) {
+        const v3 p = add3(add3(r.v0, scale3(r.e1, u)), scale3(r.e2, v));
+        *pos = p;
+        *dist = distance3(start, p);
+        return true;
+    }
+    return false;
+}
+
+// ---- k_query_closest: one lane per P rays, every ray tests every triangle --------------------------------------------
+//
+// Workgroup = 256 lanes; lane t of block b owns rays (b * P + p) * 256 + t.  The rows are staged through LDS in chunks of
+// RT_CHUNK_ROWS (48 KiB) and read as wave-uniform broadcasts, three ds_read_b128 per triangle shared by the lane's P rays.
+// hits[ray] is the reference's in/out `closestIntersection`: the update is the reference's own sequential one in index order,
+// `if (record.distance >= distance)` (:243), started from the incoming record -- which is what the packed min-t key encodes
+// (rt_common.hpp) and needs no key while one lane sees the triangles in order: ties go to the later index, an incoming record
+// loses every tie, a negative or NaN incoming distance is never replaced and +inf by any hit.  A record nothing replaced is
+// not written at all.
+template <int P>
+__global__ __launch_bounds__(256) void k_query_closest(const QueryFrame q)
+{
+    extern __shared__ __attribute__((aligned(16))) float4 s_rows[];
+    const bool scene_ok = scene_rows_in_range(q);
+
+    long long ray[P];
+    bool ok[P], exact_only[P], replaced[P];
+    v3 start[P], nd[P], pos[P];
+    v3p startp, ndp;
+    float best_d[P];
+    int best_i[P];
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+        ray[p] = ((long long)blockIdx.x * P + p) * 256 + threadIdx.x;
+        ok[p] = ray[p] < q.nrays;
+        const float *r = q.rays + (size_t)RAY_WORDS * (ok[p] ? ray[p] : 0);
+        start[p] = ld3(r);
+        const v3 dir = ld3(r + 3);
+        nd[p] = neg3(dir);                                         // negD = -dir (:229); dir is used as given
+        exact_only[p] = ray_exact_only(scene_ok, start[p], dir);
+        // a lane without a ray carries a record nothing can replace
+        best_d[p] = ok[p] ? __uint_as_float(q.hits[(size_t)HIT_WORDS * ray[p] + 3]) : -1.0f;
+        best_i[p] = -1;
+        pos[p] = V3(0.0f, 0.0f, 0.0f);
+        replaced[p] = false;
+        if constexpr (P == 2) {
+            startp.x[p] = start[p].x; startp.y[p] = start[p].y; startp.z[p] = start[p].z;
+            ndp.x[p] = nd[p].x; ndp.y[p] = nd[p].y; ndp.z[p] = nd[p].z;
+        }
+    }
+
+    for (int base = 0; base < q.n; base += RT_CHUNK_ROWS) {
+        const int cnt = min(RT_CHUNK_ROWS, q.n - base);
+        __syncthreads();
+        {
+            const float4 *src = reinterpret_cast<const float4 *>(q.rows + base);
+            for (int k = threadIdx.x; k < cnt * 3; k += 256) s_rows[k] = src[k];
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (int j = 0; j < cnt; j++) {
+            const RowVecs r = unpack_row(s_rows[3 * j], s_rows[3 * j + 1], s_rows[3 * j + 2]);
+            TestDots d[P];
+            float e1e2b[P];
+            bool maybe[P];
+            if constexpr (P == 2) {
+                f2 eb;
+                const TestDots2 t = ray_dots2(r, startp, ndp, &eb);
+                maybe_hit2(t, &maybe[0], &maybe[1]);
+                d[0] = dots_half(t, 0); d[1] = dots_half(t, 1);
+                e1e2b[0] = eb.x; e1e2b[1] = eb.y;
+            } else {
+#pragma unroll
+                for (int p = 0; p < P; p++) {
+                    d[p] = ray_dots(r, start[p], nd[p], &e1e2b[p]);
+                    maybe[p] = maybe_hit(d[p]);
+                }
+            }
+#pragma unroll
+            for (int p = 0; p < P; p++) {
+                if (maybe[p] || exact_only[p]) {
+                    v3 hp;
+                    float dist;
+                    if (exact_hit_row(d[p], e1e2b[p], r, start[p], &hp, &dist)) {
+                        if (best_d[p] >= dist) { best_d[p] = dist; best_i[p] = base + j; pos[p] = hp; replaced[p] = true; }   // :243-247
+                    }
+                }
+            }
+        }
+    }
+
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+        if (!ok[p] || !replaced[p]) continue;
+        uint32_t *h = q.hits + (size_t)HIT_WORDS * ray[p];
+        h[0] = __float_as_uint(pos[p].x); h[1] = __float_as_uint(pos[p].y); h[2] = __float_as_uint(pos[p].z);
+        h[3] = __float_as_uint(best_d[p]);
+        h[4] = (uint32_t)best_i[p];
+    }
+}
+
+template __global__ void k_query_closest<QUERY_P>(const QueryFrame);
+
+// ---- k_query_closest_wave: one WAVE per ray, lanes over triangles ------------------------------------------------------
+//
+// For few rays against many triangles (a pick, a handful of probes) a lane per ray leaves the chip empty and walks the whole
+// triangle list serially.  Here the 64 lanes of a wave stride over the rows (coalesced 48-byte rows from global memory), each
+// keeps the best of its own triangles, and the wave reduces them with the packed min-t key (rt_common.hpp: wave_min_key); the
+// lane that owns the winner broadcasts its hit point, as in k_rt_wave.
+// The sequential rule in key form: the record only ever moves to a distance that is <= the incoming one, so the final record is
+// the smallest accepted distance d with `incoming >= d` -- the latest index among equals -- or the incoming record when there is
+// none.  Such d are >= 0 and not NaN (+inf only under an incoming +inf), so their bits order as unsigned integers; "no candidate"
+// is the all-ones key, above every one of them.
+constexpr unsigned long long QUERY_KEY_NONE = ~0ull;
+
+__global__ __launch_bounds__(256) void k_query_closest_wave(const QueryFrame q)
+{
+    const int lane = threadIdx.x & 63;
+    const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= q.nrays) return;                                    // (the whole wave)
+    const float *rp = q.rays + (size_t)RAY_WORDS * ray;
+    const v3 start = ld3(rp), dir = ld3(rp + 3);
+    const v3 nd = neg3(dir);                                       // :229
+    const bool exact_only = ray_exact_only(scene_rows_in_range(q), start, dir);
+    uint32_t *h = q.hits + (size_t)HIT_WORDS * ray;
+    const float incoming = __uint_as_float(h[3]);
+
+    unsigned long long key = QUERY_KEY_NONE;
+    v3 pos = V3(0.0f, 0.0f, 0.0f);
+    for (int i = lane; i < q.n; i += 64) {
+        const float4 *src = reinterpret_cast<const float4 *>(q.rows + i);
+        const RowVecs r = unpack_row(src[0], src[1], src[2]);
+        float e1e2b;
+        const TestDots td = ray_dots(r, start, nd, &e1e2b);
+        if (maybe_hit(td) || exact_only) {
+            v3 hp;
+            float dist;
+            if (exact_hit_row(td, e1e2b, r, start, &hp, &dist) && incoming >= dist) {
+                const unsigned long long k = min_t_key(dist, i);
+                if (k < key) { key = k; pos = hp; }                // lane-local: smallest distance, then largest index
+            }
+        }
+    }
+    const unsigned long long best = wave_min_key(key);
+    if (best == QUERY_KEY_NONE) return;                            // nothing replaces the record: all 20 bytes stay
+    const int owner = __builtin_ctzll(__ballot(key == best) | (1ull << 63));
+    pos.x = __shfl(pos.x, owner); pos.y = __shfl(pos.y, owner); pos.z = __shfl(pos.z, owner);
+    if (lane != 0) return;
+    h[0] = __float_as_uint(pos.x); h[1] = __float_as_uint(pos.y); h[2] = __float_as_uint(pos.z);
+    h[3] = (uint32_t)(best >> 32);
+    h[4] = (uint32_t)min_t_index(best);
+}
+
+// ---- k_query_direct_light: DirectLight per hit record -----------------------------------------------------------------
+//
+// One lane per P records.  Per light position k (the lights, or their jittered soft-shadow positions): the light term
+// (light_term, :294-304), then the shadow ray -- start = the light, dir = -rDir (:310) -- swept over light k's origin table
+// (k_prep_origin: shadow rays DO share their origin), staged through LDS in chunks; a lane stops testing at its first
+// occluder closer than 0.99 r (any-hit is exact: SURVEY A-5).  result += D per position, result2 += result after each
+// light's samples (the reference's double count, :319-322), and the return value result2 * colour (:325-326).
+// Filter range: the tables' rows are checked by k_prep_origin (f.unsafe, wave-uniform); rDir is a unit vector unless the
+// record's position is not finite, which the lane checks per light (|rDir| components below MIRT_QUERY_DIR_MAX, false for NaN).
+// A record whose index is outside [0, n) -- the reference would read outside `triangles` -- yields (0, 0, 0).
+template <int P, bool FILTER>
+__device__ __forceinline__ void direct_light_body(const QueryLightFrame &q, float4 *s_tab)
+{
+    const RtFrame &f = q.f;
+    long long rec[P];
+    bool ok[P], valid[P];
+    v3 pos[P], nDir[P], tcol[P], result[P], result2[P];
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+        rec[p] = ((long long)blockIdx.x * P + p) * 256 + threadIdx.x;
+        ok[p] = rec[p] < q.nhits;
+        const uint32_t *h = q.hits + (size_t)HIT_WORDS * (ok[p] ? rec[p] : 0);
+        pos[p] = V3(__uint_as_float(h[0]), __uint_as_float(h[1]), __uint_as_float(h[2]));
+        const int idx = (int)h[4];
+        valid[p] = ok[p] && idx >= 0 && idx < f.n;
+        const float *t = f.tris15 + (size_t)15 * (valid[p] ? idx : 0);
+        nDir[p] = normalize3(ld3(t + 9));                          // glm::normalize(triangles[i.triangleIndex].normal) (:300)
+        tcol[p] = ld3(t + 12);
+        result[p] = result2[p] = V3(0.0f, 0.0f, 0.0f);
+    }
+
+    for (int k = 0; k < f.nlights; k++) {
+        const v3 L = ld3(f.lpos[k]);
+        v3 D[P];
+        RayDirs<P> rd;
+        float thr[P];
+        bool live[P], exact_only[P];
+        bool any_live = false;
+#pragma unroll
+        for (int p = 0; p < P; p++) {
+            float r;
+            v3 rdp;
+            D[p] = light_term(f, k, pos[p], nDir[p], &rdp, &r);
+            rd.set(p, rdp);                                        // shadow ray: dir = -rDir, so negD = rDir (:310, :229)
+            thr[p] = r * 0.99f;                                    // j.distance < r*0.99f (:313)
+            live[p] = valid[p];
+            exact_only[p] = !(fabsf(rdp.x) < MIRT_QUERY_DIR_MAX && fabsf(rdp.y) < MIRT_QUERY_DIR_MAX && fabsf(rdp.z) < MIRT_QUERY_DIR_MAX);
+            any_live |= live[p];
+        }
+        const OriginRow *tab = f.light_tab + (size_t)k * f.n;
+        // every wave of the block takes part in the staging barriers; a wave with nothing left to test skips the inner loop
+        for (int base = 0; base < f.n; base += RT_CHUNK_ROWS) {
+            const int cnt = min(RT_CHUNK_ROWS, f.n - base);
+            __syncthreads();
+            {
+                const float4 *src = reinterpret_cast<const float4 *>(tab + base);
+                for (int j = threadIdx.x; j < cnt * 3; j += 256) s_tab[j] = src[j];
+            }
+            __syncthreads();
+            if (!__any(any_live)) continue;
+#pragma unroll 2
+            for (int j = 0; j < cnt; j++) {
+                const float4 r0 = s_tab[3 * j], r1 = s_tab[3 * j + 1], r2 = s_tab[3 * j + 2];
+                TestDots d[P];
+                bool maybe[P];
+                test_rays<P, FILTER>(r0, r1, r2, rd, d, maybe);
+#pragma unroll
+                for (int p = 0; p < P; p++) {
+                    if (live[p] && (maybe[p] || exact_only[p])) {
+                        v3 hp;
+                        float dist;
+                        if (exact_hit(d[p], r0.w, f.tris15 + (size_t)15 * (base + j), L, &hp, &dist))
+                            if (dist < thr[p]) live[p] = false, D[p] = V3(0.0f, 0.0f, 0.0f);      // :313-314
+                    }
+                }
+            }
+            any_live = false;
+#pragma unroll
+            for (int p = 0; p < P; p++) any_live |= live[p];
+        }
+#pragma unroll
+        for (int p = 0; p < P; p++) {
+            result[p] = add3(result[p], D[p]);                                             // :319
+            if ((k + 1) % f.samples == 0) result2[p] = add3(result2[p], result[p]);        // :322
+        }
+    }
+
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+        if (!ok[p]) continue;
+        st3(q.rgb + 3 * (size_t)rec[p], valid[p] ? mul3(result2[p], tcol[p]) : V3(0.0f, 0.0f, 0.0f));   // :325-326
+    }
+}
+
+template <int P>
+__global__ __launch_bounds__(256) void k_query_direct_light(const QueryLightFrame q)
+{
+    extern __shared__ __attribute__((aligned(16))) float4 s_tab[];
+    if (__builtin_amdgcn_readfirstlane(*q.f.unsafe) == 0u) direct_light_body<P, true>(q, s_tab);
+    else direct_light_body<P, false>(q, s_tab);
+}
+
+template __global__ void k_query_direct_light<QUERY_P>(const QueryLightFrame);
+
+}  // namespace mirt

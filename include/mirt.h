@@ -239,6 +239,31 @@ MIRT_API int mirt_raytrace_device_ex(const mirt_view *view, const mirt_light *li
                                      void *d_xrgb, int pitch_bytes, void *d_rgb, void *d_index,
                                      void *d_distance, void *d_position);
 
+/* ---- ray queries: ClosestIntersection (raytracer.cpp:202-257) and DirectLight (:265-327) for the caller's own rays ---- */
+
+/* The two workhorses of the reference are free functions, and Draw() is only one of their callers: a mirror bounce, a mouse pick,
+ * an occlusion probe or a second light pass calls them with rays of its own.  These entry points are those two functions, one
+ * call per array element, against the uploaded scene (brute force, as ClosestIntersection is). */
+typedef struct mirt_ray { float start[3]; float dir[3]; } mirt_ray;                      /* 24 bytes */
+/* struct Intersection (raytracer.cpp:91-96), same field order and size (20 bytes). */
+typedef struct mirt_hit { float position[3]; float distance; int32_t index; } mirt_hit;
+
+/* hits[i] is the in/out `closestIntersection` argument of one ClosestIntersection(rays[i].start, rays[i].dir, triangles, hits[i])
+ * call: the caller puts in Update()'s reset (distance = FLT_MAX, :335-339; index = -1) for a fresh query, or the record an earlier
+ * ray left.  A triangle the reference accepts replaces the record when record.distance >= distance (:243): equal distances go to
+ * the later index, an incoming record loses every tie, an incoming distance that is negative or NaN is never replaced and +inf
+ * by any hit; a ray that accepts nothing closer leaves all 20 bytes of its record untouched.  dir is used as given, not
+ * normalised (:229 negates it).  mirt_intersect: host arrays, complete on return.  mirt_intersect_device: device arrays, queued
+ * like the *_device frames (the streams of mirt_set_frames_in_flight in turn; mirt_sync() completes it).  nrays == 0 does nothing.
+ * Queries leave mirt_get_stats alone: it keeps reporting the last render call. */
+MIRT_API int mirt_intersect(const mirt_ray *rays, int nrays, mirt_hit *hits);
+MIRT_API int mirt_intersect_device(const void *d_rays, int nrays, void *d_hits);
+/* out_rgb[3*i ..] = DirectLight(hits[i]) for the given lights, with the reference's `result2 += result` double count (:319-322)
+ * and the final multiply by the triangle's colour (:325-326), under the current mirt_set_soft_shadows state.  Only position and
+ * index of a record are read; an index outside [0, n) -- the reference would index outside `triangles` -- yields (0, 0, 0). */
+MIRT_API int mirt_direct_light(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, float *out_rgb);
+MIRT_API int mirt_direct_light_device(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_rgb);
+
 /* ---- rasteriser: replaces Update()'s clear + Draw() + CalculateDOF() of rasteriser.cpp:183-192,461-529 */
 
 /* One frame into host buffers.  Every word of out_xrgb is written: the whole surface is cleared to black

@@ -1,0 +1,486 @@
+"""Ray queries on the GPU: mirt_intersect* / mirt_direct_light* against the CPU oracle's ClosestIntersection and DirectLight
+(oracle.closest_intersection / oracle.direct_light, themselves pinned to the reference's text by tests/test_oracle_ref_render.py).
+
+Every comparison is bit-exact and covers every ray of its batch: `index` equal, `distance`, `position` and colours compared as
+uint32 views (NaN payloads count).  No sampling, no tolerance."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import mirt
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FLT_MAX = np.finfo(np.float32).max
+LIGHTS3 = np.array([[0, -0.5, -0.7, 1, 1, 1, 14], [0.5, 0.3, -0.9, 1, 0.5, 0.2, 6], [-0.6, -0.2, 0.1, 0.3, 0.9, 0.4, 9]], np.float32)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def device():
+    mirt.init(0)
+    yield
+    mirt.shutdown()
+
+
+def make_batch(n, a, b, seed=7):
+    """start ~ U[-a, a]^3, dir = target - start, target ~ U[-b, b]^3."""
+    rng = np.random.default_rng(seed)
+    start = rng.uniform(-a, a, (n, 3)).astype(np.float32)
+    target = rng.uniform(-b, b, (n, 3)).astype(np.float32)
+    return mirt.make_rays(start, (target - start).astype(np.float32))
+
+
+def oracle_intersect(oracle, tris, rays, hits=None):
+    """One oracle ClosestIntersection call per ray on its in/out record."""
+    out = mirt.fresh_hits(len(rays)) if hits is None else hits.copy()
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1, 15)
+    for i in range(len(rays)):
+        _, p, d, ix = oracle.closest_intersection(tris, rays["start"][i], rays["dir"][i], pos=out["position"][i],
+                                                  distance=float(out["distance"][i]), index=int(out["index"][i]))
+        # a NaN distance that came back unchanged keeps the caller's bits (float -> C float -> float may quieten a payload)
+        if not (np.isnan(d) and np.isnan(out["distance"][i])):
+            out["distance"][i] = d
+        out["position"][i], out["index"][i] = p, ix
+    return out
+
+
+def oracle_direct_light(oracle, tris, hits, lights, samples=1, jitter=None):
+    out = np.zeros((len(hits), 3), np.float32)
+    for i, h in enumerate(hits):
+        if 0 <= h["index"] < len(tris):                      # outside: the reference indexes out of bounds; the library yields 0
+            out[i] = oracle.direct_light(tris, h["position"], float(h["distance"]), int(h["index"]), lights, samples=samples, jitter=jitter)
+    return out
+
+
+def same_hits(got, want, what=""):
+    assert np.array_equal(got["index"], want["index"]), "%s: index differs for %d rays" % (what, int((got["index"] != want["index"]).sum()))
+    assert np.array_equal(got["distance"].view(np.uint32), want["distance"].view(np.uint32)), "%s: distance not bit-identical" % what
+    assert np.array_equal(got["position"].view(np.uint32), want["position"].view(np.uint32)), "%s: position not bit-identical" % what
+    assert got.tobytes() == want.tobytes(), what
+
+
+def same_bits(got, want, what=""):
+    assert np.array_equal(np.ascontiguousarray(got).view(np.uint32), np.ascontiguousarray(want).view(np.uint32)), "%s: not bit-identical" % what
+
+
+def scene_of(oracle, name):
+    if name == "cornell":
+        return mirt.scene_cornell(), 0.9, 3.0
+    if name == "soup2000":
+        return mirt.scene_soup(41, 2000, 0.2), 1.5, 1.0
+    if name == "soup65":
+        return mirt.scene_soup(5, 65, 0.5), 1.5, 1.0
+    if name == "one":
+        return mirt.scene_soup(9, 1, 0.8), 1.5, 0.3
+    raise KeyError(name)
+
+
+def test_smoke_cornell_1024_rays(oracle):
+    """The query path's smoke line: Cornell box, 1024 rays, closest hits and one light against the oracle."""
+    tris = mirt.scene_cornell()
+    rays = make_batch(1024, 0.9, 3.0)
+    mirt.scene_upload(tris)
+    hits = mirt.intersect(rays)
+    same_hits(hits, oracle_intersect(oracle, tris, rays), "smoke")
+    same_bits(mirt.direct_light(hits, mirt.DEFAULT_LIGHT), oracle_direct_light(oracle, tris, hits, mirt.DEFAULT_LIGHT), "smoke")
+
+
+# ---- case 1: closest hit against the oracle --------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", ["cornell", "soup2000", "soup65", "one"])
+def test_closest_hit_matches_oracle(oracle, name):
+    tris, a, b = scene_of(oracle, name)
+    rays = make_batch(4096, a, b)
+    mirt.scene_upload(tris)
+    got = mirt.intersect(rays)
+    want = oracle_intersect(oracle, tris, rays)
+    same_hits(got, want, name)
+    share = float((got["index"] >= 0).mean())
+    print("%s: %.3f of the rays hit" % (name, share))
+    if name.startswith("soup"):
+        assert 0.05 <= share <= 0.95, share                  # neither branch is vacuous
+    if name == "cornell":
+        assert share > 0.5 and set(got["index"][got["index"] >= 0].tolist()) == set(range(30))
+    # a miss leaves the fresh record as it was
+    miss = got["index"] < 0
+    assert np.all(got["distance"][miss] == FLT_MAX) and not got["position"][miss].any()
+
+
+# ---- case 2: exact ties -------------------------------------------------------------------------------------------
+
+def test_exact_ties_go_to_the_later_index(oracle):
+    box = mirt.scene_cornell()
+    tris = np.concatenate([box, box])
+    rays = make_batch(4096, 0.9, 3.0)
+    mirt.scene_upload(tris)
+    got = mirt.intersect(rays)
+    hit = got["index"] >= 0
+    assert hit.sum() > 2000 and np.all(got["index"][hit] >= 30)          # every hit names the later copy
+    same_hits(got[:1024], oracle_intersect(oracle, tris, rays[:1024]), "cornell x 2")
+    single = oracle_intersect(oracle, box, rays)
+    assert np.array_equal(np.where(hit, got["index"] - 30, -1), single["index"])
+    same_bits(got["distance"], single["distance"], "cornell x 2 distance")
+
+    tris = np.concatenate([mirt.scene_soup(41, 3000, 0.2), box])        # as test_rt_wave_per_ray_min_t
+    rays = make_batch(4096, 1.2, 1.0)
+    mirt.scene_upload(tris)
+    same_hits(mirt.intersect(rays), oracle_intersect(oracle, tris, rays), "soup + cornell")
+
+
+# ---- case 3: carried records ---------------------------------------------------------------------------------------
+
+def test_carried_records(oracle):
+    tris = np.concatenate([mirt.scene_soup(41, 2000, 0.2), mirt.scene_cornell()])
+    rays = make_batch(2048, 1.2, 1.0)
+    mirt.scene_upload(tris)
+    fresh = mirt.intersect(rays)
+    same_hits(fresh, oracle_intersect(oracle, tris, rays), "fresh")
+    hit = fresh["index"] >= 0
+    assert hit.sum() > 500
+
+    def carried(distance, index=7):
+        h = mirt.fresh_hits(len(rays))
+        h["position"], h["distance"], h["index"] = (9, 9, 9), distance, index
+        return h
+
+    below = np.nextafter(fresh["distance"], np.float32(0)).astype(np.float32)
+    cases = {"zero": carried(np.float32(0)), "equal": carried(fresh["distance"]), "below": carried(below), "nan": carried(np.float32("nan")),
+             "negative": carried(np.float32(-1)), "inf": carried(np.float32("inf"))}
+    for name, rec in cases.items():
+        got = mirt.intersect(rays, rec)
+        same_hits(got, oracle_intersect(oracle, tris, rays, rec), name)
+        if name == "equal":                                 # an incoming record loses the tie, whatever its index
+            same_hits(got[hit], fresh[hit], "equal: replaced")
+        if name in ("below", "nan", "negative"):            # nothing is closer: all 20 bytes stay
+            assert got.tobytes() == rec.tobytes(), name
+        if name == "zero":
+            keep = ~(hit & (fresh["distance"] == 0))
+            assert got[keep].tobytes() == rec[keep].tobytes()
+        if name == "inf":                                   # +inf is replaced by any finite hit; a miss keeps it
+            same_hits(got[hit], fresh[hit], "inf: replaced")
+            assert got[~hit].tobytes() == rec[~hit].tobytes()
+    # a record carried from one ray to the next: two rays, one record
+    rays2 = make_batch(2048, 1.2, 1.0, seed=8)
+    got = mirt.intersect(rays2, fresh)
+    same_hits(got, oracle_intersect(oracle, tris, rays2, fresh), "second ray")
+
+
+# ---- case 4: operands outside the filter's range, mixed among ordinary rays -------------------------------------
+
+@pytest.mark.parametrize("name", ["soup2000", "cornell"])
+def test_rays_outside_the_filter_range(oracle, name):
+    tris, a, b = scene_of(oracle, name)
+    rays = make_batch(4096, a, b)
+    rng = np.random.default_rng(11)
+    odd = rng.permutation(len(rays))[:1200]                   # scattered, so that waves hold both kinds
+    for k, i in enumerate(odd):
+        kind = k % 6
+        if kind == 0:
+            rays["start"][i] = np.float32(1e20) * np.sign(rays["start"][i])
+        elif kind == 1:
+            rays["start"][i][k % 3] = np.float32(1e20)
+        elif kind == 2:
+            rays["dir"][i][k % 3] = np.float32("nan")
+        elif kind == 3:
+            rays["dir"][i][k % 3] = np.float32("inf") * (1 if k % 2 else -1)
+        elif kind == 4:
+            rays["dir"][i] = 0
+        else:
+            rays["dir"][i] = rays["dir"][i] * np.float32(1e7)        # beyond the direction bound: same line, exact-only path
+    mirt.scene_upload(tris)
+    got = mirt.intersect(rays)
+    same_hits(got, oracle_intersect(oracle, tris, rays), name)
+    scaled = odd[5::6]
+    assert (got["index"][scaled] >= 0).any()                  # the exact-only path does find hits
+
+
+# ---- case 5: both kernels over the same input ----------------------------------------------------------------------
+
+CHILD = r'''
+import sys, numpy as np
+sys.path.insert(0, %r)
+import mirt
+d = np.load(sys.argv[1])
+mirt.init(0)
+mirt.scene_upload(mirt.scene_soup(1, 100000, 0.05))
+out = {}
+for key in ("small", "large"):
+    rays = d[key].view(mirt.RAY_DTYPE).reshape(-1)
+    out[key] = mirt.intersect(rays).view(np.uint32).reshape(-1, 5)
+np.savez(sys.argv[2], **out)
+mirt.shutdown()
+print("ok")
+'''
+
+
+def test_both_kernels_agree(oracle, tmp_path):
+    """The soup100k scene fills [-1, 1]^3 so densely that rays aimed into that cube (b = 1) all hit (1.00 of 300 on the CPU oracle);
+    with targets in [-3, 3]^3 about a third of the rays pass beside it (hit share 0.61 - 0.66 on the CPU oracle), so both the
+    replaced and the untouched records are compared."""
+    tris = mirt.scene_soup(1, 100000, 0.05)
+    small, large = make_batch(512, 1.5, 3.0), make_batch(40000, 1.5, 3.0, seed=8)
+    inp = str(tmp_path / "rays.npz")
+    np.savez(inp, small=small.view(np.float32).reshape(-1, 6), large=large.view(np.float32).reshape(-1, 6))
+    res = {}
+    mirt.shutdown()                      # the child processes own the GPU context for this test
+    try:
+        for knob in ("0", "2000000000"):
+            out = str(tmp_path / ("hits_%s.npz" % knob))
+            r = subprocess.run([sys.executable, "-c", CHILD % os.path.join(ROOT, "cpp-raytracer-rasterizer_amd"), inp, out],
+                               env=dict(os.environ, MIRT_QUERY_WAVE_RAYS=knob), capture_output=True, text=True, timeout=600)
+            assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-2000:]
+            res[knob] = np.load(out)
+    finally:
+        mirt.init(0)
+    lane, wave = res["0"], res["2000000000"]
+    assert np.array_equal(lane["small"], wave["small"])
+    assert np.array_equal(lane["large"], wave["large"])      # all 40 000 records, all 20 bytes
+    as_hits = lambda w: np.ascontiguousarray(w).view(mirt.HIT_DTYPE).reshape(-1)
+    same_hits(as_hits(lane["small"]), oracle_intersect(oracle, tris, small), "512 rays")
+    same_hits(as_hits(lane["large"])[:2048], oracle_intersect(oracle, tris, large[:2048]), "first 2048 of 40 000 rays")
+    share = float((as_hits(lane["large"])["index"] >= 0).mean())
+    assert 0.05 <= share <= 0.95, share
+
+
+@pytest.mark.parametrize("knob", ["0", "2000000000"])
+def test_cases_under_either_kernel(knob):
+    """MIRT_QUERY_WAVE_RAYS is read once per process, and a batch's size alone decides which kernel a default run gives it: the
+    closest-hit cases of this file once more in a process where every batch takes the lane-per-ray kernel, and in one where
+    every batch takes the wave-per-ray kernel."""
+    select = "smoke or closest_hit or exact_ties or carried or filter_range or frame_path"
+    mirt.shutdown()
+    try:
+        r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-m", "gpu", "-k", select, "-p", "no:cacheprovider"],
+                           env=dict(os.environ, MIRT_QUERY_WAVE_RAYS=knob), cwd=ROOT, capture_output=True, text=True, timeout=1200)
+    finally:
+        mirt.init(0)
+    assert r.returncode == 0 and " passed" in r.stdout and "failed" not in r.stdout, r.stdout[-3000:] + r.stderr[-1000:]
+
+
+# ---- case 6: agreement with the frame path ----------------------------------------------------------------------------
+
+def primary_rays(oracle, cam, rot, focal, W, H):
+    """The primary rays of Draw() (raytracer.cpp:579-580): d = (x - W/2, y - H/2, focalLength), dir = cameraRot * d."""
+    rays = np.zeros(W * H, mirt.RAY_DTYPE)
+    rays["start"] = np.asarray(cam, np.float32)
+    rot = np.ascontiguousarray(rot, np.float32)
+    out = np.zeros(3, np.float32)
+    for y in range(H):
+        for x in range(W):
+            d = np.array([np.float32(x) - np.float32(W) / np.float32(2), np.float32(y) - np.float32(H) / np.float32(2), np.float32(focal)], np.float32)
+            oracle.lib.mirt_oracle_mat3_mul_vec(rot, d, out)
+            rays["dir"][y * W + x] = out
+    return rays
+
+
+@pytest.mark.parametrize("name", ["soup2000+cornell", "cornell"])
+def test_queries_equal_the_frame_path(oracle, name):
+    W, H, cam, focal = 96, 80, (0.1, -0.05, -2.0), 60.0
+    rot = oracle.rot_from_yaw(0.15, 1.0)
+    tris = mirt.scene_cornell() if name == "cornell" else np.concatenate([mirt.scene_soup(41, 2000, 0.2), mirt.scene_cornell()])
+    lights, indirect = LIGHTS3[:2], np.array([0.2, 0.25, 0.3], np.float32)
+    mirt.scene_upload(tris)
+    frame = mirt.raytrace(mirt.make_view(cam, rot, focal, W, H), lights, indirect=indirect, mode=mirt.RT_BRUTE, want_intersection=True)
+    hits = mirt.intersect(primary_rays(oracle, cam, rot, focal, W, H))
+    assert np.array_equal(hits["index"], frame["index"].ravel())
+    same_bits(hits["distance"], frame["dist"].ravel(), "distance plane")
+    same_bits(hits["position"], frame["pos"].reshape(-1, 3), "position plane")
+    D = mirt.direct_light(hits, lights)
+    colour = tris[np.maximum(hits["index"], 0), 12:15]
+    rgb = (colour * (D + indirect)).astype(np.float32)        # colour * (DirectLight + indirectLight) (:584-591)
+    hit = hits["index"] >= 0
+    assert hit.sum() > 1000
+    same_bits(rgb[hit], frame["rgb"].reshape(-1, 3)[hit], "rgb plane")
+
+
+# ---- case 7: DirectLight against the oracle ------------------------------------------------------------------------------
+
+def _jitter(oracle, lights, samples, seed=1):
+    C.CDLL(None).srand(seed)
+    return np.concatenate([oracle.jitter(l[0:3], samples) for l in np.asarray(lights, np.float32).reshape(-1, 7)])
+
+
+@pytest.mark.parametrize("name", ["cornell", "soup2000", "cornell x 2"])
+def test_direct_light_matches_oracle(oracle, name):
+    if name == "cornell x 2":
+        tris, a, b = np.concatenate([mirt.scene_cornell(), mirt.scene_cornell()]), 0.9, 3.0
+    else:
+        tris, a, b = scene_of(oracle, name)
+    n = len(tris)
+    rays = make_batch(1024, a, b)
+    mirt.scene_upload(tris)
+    hits = mirt.intersect(rays)
+    same_hits(hits, oracle_intersect(oracle, tris, rays), name)
+    assert (hits["index"] >= 0).sum() > 100
+    # records outside the scene yield zeros: the misses (-1) and an index one past the end
+    hits["index"][5::97] = n
+    for nl in (1, 2, 3):                                     # 2 and 3 lights: the result2 += result double count
+        got = mirt.direct_light(hits, LIGHTS3[:nl])
+        same_bits(got, oracle_direct_light(oracle, tris, hits, LIGHTS3[:nl]), "%s, %d lights" % (name, nl))
+        assert not got[(hits["index"] < 0) | (hits["index"] >= n)].any()
+        assert got.any()
+    same_bits(mirt.direct_light(hits, np.zeros((0, 7), np.float32)), np.zeros((len(hits), 3), np.float32), "no lights")
+    # soft shadows, 4 samples per light
+    jit = _jitter(oracle, LIGHTS3[:2], 4)
+    mirt.set_soft_shadows(4, jit)
+    try:
+        got = mirt.direct_light(hits, LIGHTS3[:2])
+        with pytest.raises(mirt.MirtError, match="jittered positions needed"):
+            mirt.direct_light(hits, LIGHTS3)                 # 12 positions needed, 8 set: rt_enqueue's check and message
+    finally:
+        mirt.set_soft_shadows(1)
+    same_bits(got, oracle_direct_light(oracle, tris, hits, LIGHTS3[:2], samples=4, jitter=jit), name + ", soft shadows")
+    # a record whose position is not finite takes the exact path for its shadow rays; whatever comes out is the oracle's
+    odd = hits[:64].copy()
+    odd["position"][::2] = np.float32(3e19)
+    same_bits(mirt.direct_light(odd, LIGHTS3[:1]), oracle_direct_light(oracle, tris, odd, LIGHTS3[:1]), name + ", far positions")
+
+
+# ---- errors ------------------------------------------------------------------------------------------------------------------
+
+def test_argument_validation():
+    lib = mirt.load()
+    rays, hits, rgb = make_batch(4, 1, 1), mirt.fresh_hits(4), np.zeros((4, 3), np.float32)
+    larr, _ = mirt.make_lights(LIGHTS3)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    mirt.scene_upload(mirt.scene_cornell())
+    INVALID = -3
+    assert lib.mirt_intersect(None, 4, p(hits)) == INVALID and lib.mirt_intersect(p(rays), 4, None) == INVALID
+    assert lib.mirt_intersect(p(rays), -1, p(hits)) == INVALID
+    assert lib.mirt_intersect_device(None, 4, None) == INVALID and lib.mirt_intersect_device(None, -2, None) == INVALID
+    assert lib.mirt_direct_light(None, 4, larr, 3, p(rgb)) == INVALID and lib.mirt_direct_light(p(hits), 4, larr, 3, None) == INVALID
+    assert lib.mirt_direct_light(p(hits), -1, larr, 3, p(rgb)) == INVALID
+    assert lib.mirt_direct_light(p(hits), 4, larr, -1, p(rgb)) == INVALID
+    assert lib.mirt_direct_light(p(hits), 4, larr, mirt.MAX_LIGHTS + 1, p(rgb)) == INVALID
+    assert lib.mirt_direct_light(p(hits), 4, None, 2, p(rgb)) == INVALID
+    assert lib.mirt_direct_light_device(None, 4, larr, 3, None) == INVALID
+    # n == 0 succeeds and does nothing, NULL arrays included
+    assert lib.mirt_intersect(None, 0, None) == 0 and lib.mirt_intersect_device(None, 0, None) == 0
+    assert lib.mirt_direct_light(None, 0, None, 0, None) == 0 and lib.mirt_direct_light_device(None, 0, larr, 3, None) == 0
+    assert hits.tobytes() == mirt.fresh_hits(4).tobytes() and not rgb.any()
+
+
+def test_no_scene():
+    mirt.shutdown()
+    mirt.init(0)
+    with pytest.raises(mirt.MirtError, match="no scene uploaded"):
+        mirt.intersect(make_batch(4, 1, 1))
+    with pytest.raises(mirt.MirtError, match="no scene uploaded"):
+        mirt.direct_light(mirt.fresh_hits(4), LIGHTS3)
+
+
+def test_queries_leave_the_statistics_alone(oracle):
+    tris = mirt.scene_cornell()
+    mirt.scene_upload(tris)
+    frame = mirt.raytrace(mirt.make_view((0, 0, -2), oracle.rot_from_yaw(0.0, 1.0), 32.0, 64, 64), mirt.DEFAULT_LIGHT)
+    before = mirt.stats()
+    assert before == frame["stats"] and before["primary_rays"] == 64 * 64
+    hits = mirt.intersect(make_batch(1000, 0.9, 3.0))
+    mirt.direct_light(hits, LIGHTS3)
+    assert mirt.stats() == before
+
+
+# ---- case 8: streams and caches ------------------------------------------------------------------------------------------
+
+def _to_device(arr):
+    from devbuf import DeviceArray, hip
+    a = np.ascontiguousarray(arr)
+    d = DeviceArray((a.nbytes,), np.uint8)
+    assert hip().hipMemcpy(d.ptr, a.ctypes.data_as(C.c_void_p), a.nbytes, 1) == 0
+    assert hip().hipDeviceSynchronize() == 0
+    return d
+
+
+@pytest.mark.parametrize("in_flight", [1, 2, 3, 4])
+def test_device_queries_between_frames_in_flight(oracle, in_flight):
+    from devbuf import DeviceArray
+    tris = np.concatenate([mirt.scene_soup(41, 2000, 0.2), mirt.scene_cornell()])
+    W, H = 160, 120
+    view = mirt.make_view((0, 0, -2), oracle.rot_from_yaw(0.1, 1.0), 80.0, W, H)
+    mirt.scene_upload(tris)              # (a new scene version: the first query of the loop below builds the rows on its stream)
+    want_frame = mirt.raytrace(view, LIGHTS3[:2], mode=mirt.RT_BRUTE)["xrgb"]
+    batches = [make_batch(n, 1.2, 1.0, seed=20 + i) for i, n in enumerate((1500, 3, 700, 5000, 64, 2049))]
+    want = [oracle_intersect(oracle, tris, b) for b in batches[:3]]
+    bufs = []
+    try:
+        mirt.set_frames_in_flight(in_flight)
+        for b in batches:
+            d_rays, d_hits = _to_device(b), _to_device(mirt.fresh_hits(len(b)))
+            d_rgb = DeviceArray((len(b), 3), np.float32, 0x11)
+            x = DeviceArray((H, W), np.uint32, 0)
+            bufs.append((d_rays, d_hits, d_rgb, x))
+            mirt.intersect_device(d_rays.ptr, len(b), d_hits.ptr)
+            mirt.raytrace_device(view, LIGHTS3[:2], (0.2, 0.2, 0.2), mirt.RT_BRUTE, 0, H, 0, x.ptr, W * 4)
+            if in_flight > 1:
+                mirt.sync()                                 # the light pass reads the records a query on another stream writes
+            mirt.direct_light_device(d_hits.ptr, len(b), LIGHTS3[:2], d_rgb.ptr)
+        mirt.sync()
+        mirt.set_frames_in_flight(1)
+        for i, (b, (d_rays, d_hits, d_rgb, x)) in enumerate(zip(batches, bufs)):
+            got = d_hits.read().view(mirt.HIT_DTYPE).reshape(-1)
+            same_hits(got, mirt.intersect(b), "batch %d: device form vs host form" % i)
+            if i < len(want):
+                same_hits(got, want[i], "batch %d" % i)
+            same_bits(d_rgb.read(), mirt.direct_light(got, LIGHTS3[:2]), "batch %d: direct light" % i)
+            frame = x.read()
+            assert np.array_equal(frame[1:-1, 1:-1], want_frame[1:-1, 1:-1]), "frame %d" % i
+    finally:
+        mirt.set_frames_in_flight(1)
+        for t in bufs:
+            for d in t:
+                d.free()
+
+
+def test_rows_follow_the_scene_version(oracle):
+    rays = make_batch(512, 1.5, 1.0)
+    for tris in (mirt.scene_soup(5, 65, 0.5), mirt.scene_soup(6, 65, 0.5), mirt.scene_soup(41, 2000, 0.2), mirt.scene_soup(5, 65, 0.5)):
+        mirt.scene_upload(tris)          # same size / another size: the row table is rebuilt either way
+        hits = mirt.intersect(rays)
+        same_hits(hits, oracle_intersect(oracle, tris, rays), "after re-upload")
+        same_bits(mirt.direct_light(hits, LIGHTS3[:1]), oracle_direct_light(oracle, tris, hits, LIGHTS3[:1]), "after re-upload")
+
+
+@pytest.mark.parametrize("in_flight", [1, 2])
+def test_light_queries_between_binned_frames_of_a_standing_view(in_flight):
+    """A DirectLight query builds origin tables with k_prep_origin; the camera rows a kept binning pass counts on must survive it:
+    the binned frames of a view that stands still stay equal to brute force whether they keep their pass or not."""
+    from devbuf import DeviceArray
+    tris = mirt.scene_soup(41, 26000, 0.06)
+    rot = np.zeros(9, np.float32); rot[0] = rot[4] = rot[8] = 1
+    W, H = 320, 200
+    view = mirt.make_view((0.0, 0.0, -1.7), rot, 160.0, W, H)
+    light = np.array([[0.1, -0.4, -0.6, 1, 1, 1, 14]], np.float32)
+    mirt.scene_upload(tris)
+    hits = mirt.intersect(make_batch(3000, 1.2, 0.8))
+    first = mirt.direct_light(hits, LIGHTS3)
+    assert (hits["index"] >= 0).sum() > 300 and first.any()
+    x = DeviceArray((H, W), np.uint32, 0x11)
+    try:
+        mirt.raytrace_device(view, light, (0.2, 0.2, 0.2), mirt.RT_BRUTE, 0, H, 0, x.ptr, W * 4)
+        want = x.read()
+        mirt.set_frames_in_flight(in_flight)
+        reused = 0
+        for i in range(8):
+            assert hip_fill(x, 0x11)
+            mirt.raytrace_device(view, light, (0.2, 0.2, 0.2), mirt.RT_BINNED, 0, H, 0, x.ptr, W * 4)
+            st = mirt.stats()
+            assert st["mode_used"] == mirt.RT_BINNED and st["bins_reused"] in (0, 1)
+            reused += st["bins_reused"]
+            assert np.array_equal(x.read(), want), "binned frame %d changed" % i
+            same_bits(mirt.direct_light(hits, LIGHTS3), first, "query %d" % i)
+            assert mirt.stats() == st
+        print("binned frames that kept their pass: %d of 8" % reused)
+    finally:
+        mirt.set_frames_in_flight(1)
+        x.free()
+
+
+def hip_fill(dev, byte):
+    from devbuf import hip
+    mirt.sync()
+    return hip().hipMemset(dev.ptr, byte, dev.nbytes) == 0 and hip().hipDeviceSynchronize() == 0

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/check_spills.py -- compiles every kernel source of the library for gfx950 (device side only, the Makefile's flags) and lists
+"""tools/check_spills.py -- compiles every kernel source of the library (csrc/ and query/) for gfx950 (device side only, the Makefile's flags) and lists
 each kernel's VGPR count, occupancy and scratch bytes (and which kernels sit within eight registers of another wave per SIMD); exits non-zero if any kernel spills to scratch (private segment != 0).
 __graft_entry__.build() runs it: a spill in a hot loop is a silent 2-3x."""
 import os
@@ -9,16 +9,16 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cpp-raytracer-rasterizer_amd", "csrc")
+DIRS = [os.path.join(ROOT, "cpp-raytracer-rasterizer_amd", d) for d in ("csrc", "query")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-x", "hip", "--cuda-device-only", "-S"]
 bad = []
 rows = []
 with tempfile.TemporaryDirectory() as tmp:
-    for name in sorted(os.listdir(CSRC)):
+    for src_dir, name in [(d, f) for d in DIRS for f in sorted(os.listdir(d))]:
         if not name.endswith(".hip"):
             continue
         out = os.path.join(tmp, name + ".s")
-        cc = subprocess.run(["hipcc"] + FLAGS + ["-c", os.path.join(CSRC, name), "-o", out], capture_output=True, text=True)
+        cc = subprocess.run(["hipcc"] + FLAGS + ["-c", os.path.join(src_dir, name), "-o", out], capture_output=True, text=True)
         if cc.returncode != 0:
             sys.stderr.write(cc.stderr)
             sys.exit("tools/check_spills.py: hipcc failed on %s (rc %d)" % (name, cc.returncode))
@@ -43,7 +43,8 @@ for r in rows:
     hint = "   (%d VGPRs above %d waves per SIMD)" % (over, w + 1) if 0 < over <= 8 else ""
     print("%-22s %-44s vgprs %3d scratch %4d occupancy %d%s" % (r + (hint,)))
 # the gate must not pass vacuously: should the backend's resource comments change shape, the pattern above matches nothing
-EXPECT = ("k_rt_trace2", "k_rt_tile2", "k_rt_brute", "k_bin_pairs", "k_raster_small", "k_raster_resolve", "k_dof_tile", "k_bs_local")
+EXPECT = ("k_rt_trace2", "k_rt_tile2", "k_rt_brute", "k_bin_pairs", "k_raster_small", "k_raster_resolve", "k_dof_tile", "k_bs_local",
+          "k_query_rows", "k_query_closest<", "k_query_closest_wave", "k_query_direct_light")
 missing = [k for k in EXPECT if not any(k in r[1] for r in rows)]
 if missing or len(rows) < 20:
     sys.exit("tools/check_spills.py: resource summaries found for %d kernels only; missing %s -- the pattern no longer matches the backend's output"

@@ -1,0 +1,268 @@
+#!/usr/bin/env python3
+"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep]
+
+The three measurements of the ray-query kernels (query/rt_query.hip), written to one text file:
+
+  issue + throughput   the lane-per-ray kernel over the 2 073 600 primary rays of soup100k at 1080p (generated on the host, through
+                       mirt_intersect_device) beside one BRUTE frame of the same view in the same process (k_rt_brute).  The EXPECTED
+                       ratio of the two comes from the code: the vector instructions every test executes -- from a row's LDS reads to
+                       the filter's branch -- of either kernel, priced with the issue classes of tools/issue_mix.py.
+  sweep                time against the number of rays, 1 .. 2^20 in powers of two, at n = 100 000 and n = 2 000, with
+                       MIRT_QUERY_WAVE_RAYS = 0 (lane per ray) and huge (wave per ray): where the curves cross is the knob's default.
+  occupancy            tools/check_spills.py's lines for the query kernels: VGPRs, scratch, waves per SIMD.
+
+The knob is read once per process, so every GPU step is a child process of its own, under its own `timeout`; a step that fails
+ends the run."""
+import argparse
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "cpp-raytracer-rasterizer_amd")
+sys.path.insert(0, PKG)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+HUGE = "2000000000"
+W, H, CAM, FOCAL = 1920, 1080, (0.0, 0.0, -2.0), 540.0
+
+
+# ---- static: the per-test instructions of a kernel ---------------------------------------------------------------------
+
+def test_segments(asm_kernel_lines):
+    """The straight-line code every test runs: from the first ds_read_b128 of a row to the next branch (what follows is the exact
+    path, entered only by the lanes the filter lets through).  Returns [(valu, packed, issue cycles)] in text order."""
+    import issue_mix as im
+    out, cur = [], None
+    for t in asm_kernel_lines:
+        t = t.strip()
+        if t.startswith("ds_read_b128") and cur is None:
+            cur = {"valu": 0, "packed": 0, "cycles": 0.0}
+        elif cur is not None and t.startswith(("s_cbranch", "s_branch")):
+            out.append((cur["valu"], cur["packed"], cur["cycles"]))
+            cur = None
+        elif cur is not None and t.startswith("v_"):
+            cur["valu"] += 1
+            cur["packed"] += t.startswith("v_pk_")
+            cur["cycles"] += im.CYCLES[im.classify(t)]
+    return out
+
+
+def kernel_text(path, flags, want):
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "k.s")
+        subprocess.run(["hipcc"] + flags + ["-c", path, "-o", out], check=True, capture_output=True)
+        lines = open(out).read().split("\n")
+    start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\S*%s\S*:" % want, l))
+    end = next(i for i in range(start, len(lines)) if ".Lfunc_end" in lines[i])
+    return lines[start:end]
+
+
+def step_issue(p):
+    import issue_mix as im
+    q = test_segments(kernel_text(os.path.join(PKG, "query", "rt_query.hip"), im.FLAGS, "k_query_closestILi2"))
+    b = test_segments(kernel_text(os.path.join(PKG, "csrc", "rt_kernels.hip"), im.FLAGS, "k_rt_bruteILi2"))
+    p("== issue: vector instructions per test of two rays (one LDS row, both rays of the lane; static, from the assembly) ==")
+    p("k_query_closest<2>   segments (valu, packed, issue cycles): %s" % ", ".join("(%d, %d, %.1f)" % s for s in q))
+    p("k_rt_brute<2>        segments (valu, packed, issue cycles): %s" % ", ".join("(%d, %d, %.1f)" % s for s in b))
+    # the loops that run the filter are the packed ones; k_rt_brute's text holds them for the primary and the shadow sweep of
+    # either supersampling variant, and exact-only variants without a packed instruction
+    qf = [s for s in q if s[1] > 0]
+    bf = [s for s in b if s[1] > 0]
+    # ... of which the shadow sweep carries a `live` mask besides: the primary sweep, which the throughput step times, is the shortest
+    qs, bs = min(qf, key=lambda s: s[2]), min(bf, key=lambda s: s[2])
+    qc, bc = qs[2], bs[2]
+    p("filtered test of the primary sweep: query %.1f issue cycles (%d valu, %d packed), brute %.1f (%d valu, %d packed)" % (qc, qs[0], qs[1], bc, bs[0], bs[1]))
+    p("expected_ratio query/brute per test = %.2f" % (qc / bc))
+    p("")
+    return qc / bc
+
+
+# ---- occupancy -------------------------------------------------------------------------------------------------------------
+
+def step_occupancy(p):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_spills.py")], capture_output=True, text=True, check=True)
+    p("== occupancy (tools/check_spills.py) ==")
+    for line in r.stdout.split("\n"):
+        if "k_query_" in line or "k_rt_brute" in line or "k_rt_wave" in line or line.startswith("no kernel spills"):
+            p(line)
+    p("")
+
+
+# ---- GPU steps (children) --------------------------------------------------------------------------------------------------
+
+def hip():
+    h = C.CDLL("libamdhip64.so")
+    h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    h.hipFree.argtypes = [C.c_void_p]
+    return h
+
+
+def dev_alloc(h, nbytes, src=None):
+    ptr = C.c_void_p()
+    assert h.hipMalloc(C.byref(ptr), max(int(nbytes), 16)) == 0
+    if src is not None:
+        assert h.hipMemcpy(ptr, src.ctypes.data_as(C.c_void_p), src.nbytes, 1) == 0
+    assert h.hipDeviceSynchronize() == 0
+    return ptr
+
+
+def primary_rays(mirt, rot):
+    """Draw()'s rays (raytracer.cpp:579-580) in float32, operation by operation: d = (x - W/2, y - H/2, f), dir = R * d."""
+    x = (np.arange(W, dtype=np.float32) - np.float32(W) / np.float32(2))[None, :].repeat(H, 0)
+    y = (np.arange(H, dtype=np.float32) - np.float32(H) / np.float32(2))[:, None].repeat(W, 1)
+    f = np.float32(FOCAL)
+    rays = np.zeros(W * H, mirt.RAY_DTYPE)
+    rays["start"] = np.asarray(CAM, np.float32)
+    for r in range(3):
+        rays["dir"][:, r] = (rot[r] * x + rot[3 + r] * y + rot[6 + r] * f).ravel()
+    return rays
+
+
+def timed(mirt, fn, reps):
+    fn(); mirt.sync()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn(); mirt.sync()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts))
+
+
+def child_throughput():
+    import mirt
+    h = hip()
+    mirt.init(0)
+    mirt.scene_upload(mirt.scene_soup(1, 100000, 0.05))
+    rot = mirt.rot_from_yaw(0.0, 1.0)
+    view = mirt.make_view(CAM, rot, FOCAL, W, H)
+    rays = primary_rays(mirt, rot)
+    fresh = mirt.fresh_hits(len(rays))
+    d_rays, d_hits = dev_alloc(h, rays.nbytes, rays), dev_alloc(h, fresh.nbytes, fresh)
+    d_x, d_idx = dev_alloc(h, W * H * 4), dev_alloc(h, W * H * 4)
+
+    def query():
+        assert h.hipMemcpy(d_hits, fresh.ctypes.data_as(C.c_void_p), fresh.nbytes, 1) == 0
+        t0 = time.perf_counter()
+        mirt.intersect_device(d_rays, len(rays), d_hits); mirt.sync()
+        return (time.perf_counter() - t0) * 1e3
+    query()
+    q_ms = float(np.median([query() for _ in range(3)]))
+    b_ms = timed(mirt, lambda: mirt.raytrace_device(view, np.zeros((0, 7), np.float32), (0.2, 0.2, 0.2), mirt.RT_BRUTE, 0, H, 0, d_x, W * 4, None, d_idx), 3)
+    lit_ms = timed(mirt, lambda: mirt.raytrace_device(view, mirt.DEFAULT_LIGHT, (0.2, 0.2, 0.2), mirt.RT_BRUTE, 0, H, 0, d_x, W * 4, None, d_idx), 2)
+    got, idx = np.zeros(len(rays), mirt.HIT_DTYPE), np.zeros(W * H, np.int32)
+    assert h.hipMemcpy(got.ctypes.data_as(C.c_void_p), d_hits, got.nbytes, 2) == 0
+    assert h.hipMemcpy(idx.ctypes.data_as(C.c_void_p), d_idx, idx.nbytes, 2) == 0
+    assert np.array_equal(got["index"], idx), "query and frame disagree"
+    tests = len(rays) * 100000.0
+    print("RESULT rays %d triangles 100000 knob %s" % (len(rays), os.environ.get("MIRT_QUERY_WAVE_RAYS", "default")))
+    print("RESULT k_query_closest<2>: %.2f ms (%.1f G tests/s), every index equal to the frame's" % (q_ms, tests / q_ms * 1e-6))
+    print("RESULT BRUTE frame without lights (k_prep_origin + k_rt_brute<2>, primary rays only): %.2f ms (%.1f G tests/s)" % (b_ms, tests / b_ms * 1e-6))
+    print("RESULT BRUTE frame with the default light (primary + shadow sweep): %.2f ms" % lit_ms)
+    print("RESULT measured_ratio query/brute(primary only) = %.3f" % (q_ms / b_ms))
+    mirt.shutdown()
+
+
+def child_sweep(n):
+    import mirt
+    h = hip()
+    mirt.init(0)
+    mirt.scene_upload(mirt.scene_soup(1, n, 0.05 if n >= 50000 else 0.2))
+    rng = np.random.default_rng(7)
+    top = 1 << 20
+    start = rng.uniform(-1.5, 1.5, (top, 3)).astype(np.float32)
+    target = rng.uniform(-1.0, 1.0, (top, 3)).astype(np.float32)
+    rays = mirt.make_rays(start, target - start)
+    d_rays, d_hits = dev_alloc(h, rays.nbytes, rays), dev_alloc(h, top * 20, mirt.fresh_hits(top))
+    k = 1
+    while k <= top:
+        reps = 9 if k <= 65536 else 3
+        ms = timed(mirt, lambda: mirt.intersect_device(d_rays, k, d_hits), reps)
+        print("RESULT n %6d knob %-10s rays %8d  %9.4f ms" % (n, os.environ.get("MIRT_QUERY_WAVE_RAYS"), k, ms))
+        sys.stdout.flush()
+        k *= 2
+    mirt.shutdown()
+
+
+def run_child(p, args, env, limit):
+    cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__)] + args
+    r = subprocess.run(cmd, env=dict(os.environ, **env), capture_output=True, text=True)
+    for line in r.stdout.split("\n"):
+        if line.startswith("RESULT "):
+            p(line[7:])
+    if r.returncode != 0:
+        p("step %s failed with status %d" % (" ".join(args), r.returncode))
+        sys.stderr.write(r.stderr[-4000:])
+        sys.exit(1)                      # nothing more is started on the GPU
+    return r.stdout
+
+
+def step_throughput(p, expected):
+    p("== throughput: the primary rays of soup100k at 1080p, lane per ray, beside the BRUTE frame of the same view ==")
+    out = run_child(p, ["--child", "throughput"], {"MIRT_QUERY_WAVE_RAYS": "0"}, 300)
+    m = re.search(r"measured_ratio query/brute\(primary only\) = ([0-9.]+)", out)
+    if m and expected:
+        p("expected_ratio (static issue cycles per test) = %.2f; measured / expected = %.2f" % (expected, float(m.group(1)) / expected))
+    p("")
+
+
+def step_sweep(p):
+    p("== sweep: ms per mirt_intersect_device call (host clock around call + mirt_sync, median) ==")
+    table = {}
+    for n in (100000, 2000):
+        for knob in ("0", HUGE):
+            out = run_child(lambda s: None, ["--child", "sweep", str(n)], {"MIRT_QUERY_WAVE_RAYS": knob}, 420)
+            for m in re.finditer(r"RESULT n\s+(\d+) knob (\S+)\s+rays\s+(\d+)\s+([0-9.]+) ms", out):
+                table[(int(m.group(1)), m.group(2), int(m.group(3)))] = float(m.group(4))
+    for n in (100000, 2000):
+        p("n = %d triangles" % n)
+        p("%10s %14s %14s   faster" % ("rays", "lane per ray", "wave per ray"))
+        k, cross = 1, None
+        while (n, "0", k) in table:
+            a, b = table[(n, "0", k)], table[(n, HUGE, k)]
+            p("%10d %11.4f ms %11.4f ms   %s" % (k, a, b, "wave" if b < a else "lane"))
+            if b < a:
+                cross = k
+            k *= 2
+        p("largest batch where a wave per ray is faster: %s rays" % cross)
+        p("")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ray_query_bench.txt"))
+    ap.add_argument("--steps", default="issue,occupancy,throughput,sweep")
+    ap.add_argument("--append", action="store_true")
+    ap.add_argument("--child", nargs="+")
+    a = ap.parse_args()
+    if a.child:
+        return child_throughput() if a.child[0] == "throughput" else child_sweep(int(a.child[1]))
+    lines = []
+
+    def p(s):
+        print(s)
+        sys.stdout.flush()
+        lines.append(s)
+    steps = a.steps.split(",")
+    expected = step_issue(p) if "issue" in steps else None
+    if "occupancy" in steps:
+        step_occupancy(p)
+    try:
+        if "throughput" in steps:
+            step_throughput(p, expected)
+        if "sweep" in steps:
+            step_sweep(p)
+    finally:
+        with open(a.out, "a" if a.append else "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
