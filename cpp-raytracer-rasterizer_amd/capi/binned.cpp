@@ -434,6 +434,8 @@ int binned_pass(const RtFrame &f, const mirt_view *view, RtScratch &S, RtScratch
     memset(&bs, 0, sizeof bs);
     bs.frame0 = make_camera_frame(view, y0, y1, g.aa);
     bs.frames = nullptr; bs.nframes = 1;
+    // (a tile-pair record carries its tile's column and row in 16 bits each: rt_trace.hip)
+    if (bs.frame0.nbu > 0xFFFF || bs.frame0.nbv > 0xFFFF) return fail(MIRT_ERR_INVALID_ARGUMENT, "binned frame of %d x %d tiles", bs.frame0.nbu, bs.frame0.nbv);
     // The camera's sort keys are LOCAL to the rows the call renders: tile (i, j) of a band that starts at tile row j0 has bin
     // (j - j0) * nbu + i (the frame's `base` is -j0 * nbu, modulo 2^32), so a band of a sharded frame sorts an eighth of the keys
     // -- buckets an eighth as wide, spread over all the sort's workgroups -- and writes an eighth of the offsets.  (With the whole
@@ -644,9 +646,10 @@ int binned_trace(const RtFrame &f, RtScratch &S, RtScratch &L, const BinnedPass 
     tf.light_shells = bp.light_shells;
     tf.pair_count = S.d_bin_counters;
     tf.pair_cap = S.cap_used;
-    // (lights binned by the frame: their own pass's count; the shared cube's tables are complete by construction)
-    tf.light_pair_count = transient ? L.d_bin_counters : nullptr;
-    tf.light_pair_cap = L.cap_used;
+    // (lights binned by the frame: their own pass's count; the shared cube's tables are complete by construction -- the kernel reads
+    // the word with its other counters, without a branch, so it gets one that is there and a cap no count exceeds)
+    tf.light_pair_count = transient ? L.d_bin_counters : S.d_bin_counters;
+    tf.light_pair_cap = transient ? L.cap_used : 0xFFFFFFFFu;
     // one wave per pair of 8 x 8 tiles
     tf.order = S.d_order; tf.order_count = S.d_bin_counters + 16; tf.order_seg = bp.order_seg;
     // (waves never synchronise with each other: one-wave workgroups are the finest scheduling unit; 84 / 87 / 89 us with 1 / 2 / 4)

@@ -43,7 +43,7 @@ struct RtTileFrame {
 MIRT_KERNEL void k_tile_tables(const RtTileFrame);
 template <int TW, bool AA> MIRT_KERNEL void k_rt_tile2(const RtTileFrame);
 template <int WG> MIRT_KERNEL void k_bin_pairs(const float *, const OriginRow *, const OriginRow *, int, BinSet, BinPairs);
-struct TilePairRec { uint32_t tile, beg, nA, nB; };
+struct TilePairRec { uint32_t txy, beg, nA, nB; };
 constexpr int ORDER_CLASSES = 8, ORDER_GROUPS = 8;
 struct RtTraceFrame {                            // (rt_trace.hip)
     RtFrame f;

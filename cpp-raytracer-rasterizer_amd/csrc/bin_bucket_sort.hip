@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace mirt {
 
@@ -111,6 +112,20 @@ __global__ __launch_bounds__(256) void k_bs_scatter(const uint32_t *__restrict__
     }
 }
 
+// f(j) for j = 0 .. min(rounds, N) - 1, j a compile-time constant in every call (the arrays the rounds index stay in registers) and the
+// calls nested: one scalar test per round that runs, and the first round beyond `rounds` ends the chain.  (A `break` in an unrolled
+// loop reads the same, but the compiler rolls it up again and indexes the arrays at run time.)
+template <int J, int N, class F>
+__device__ __forceinline__ void bs_rounds(int rounds, F &&f)
+{
+    if constexpr (J < N) {
+        if (J < rounds) {
+            f(std::integral_constant<int, J>());
+            bs_rounds<J + 1, N>(rounds, f);
+        }
+    }
+}
+
 // One workgroup per bucket of (1 << shift) <= BS_MAX_BUCKET_KEYS keys.  Leaves bucket_cnt[bucket] = cursor[bucket] = 0 for the next sort.
 __global__ __launch_bounds__(256) void k_bs_local(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals,
                                                   const uint32_t *__restrict__ total_ptr, uint32_t cap,
@@ -127,17 +142,22 @@ __global__ __launch_bounds__(256) void k_bs_local(const uint32_t *__restrict__ k
     for (uint32_t i = threadIdx.x; i < nb; i += 256) s_cnt[i] = 0u;
     __syncthreads();
     const bool small = end - beg <= 256u * BS_LOCAL_PER_THREAD;
+    // Rounds of 256 pairs the bucket fills: the three unrolled loops of the register-resident path stop there.  The bound comes from
+    // bucket_base alone, so it is the same in every wave and the test is a scalar branch (a bucket of the 100 k soup's camera frame
+    // holds ~500 pairs: two rounds, where sixteen predicated ones were issued).
+    const int rounds = (int)((end - beg + 255u) >> 8);
     uint32_t lo[BS_LOCAL_PER_THREAD], v[BS_LOCAL_PER_THREAD], rank[BS_LOCAL_PER_THREAD];
     if (small) {
-#pragma unroll
-        for (int j = 0; j < BS_LOCAL_PER_THREAD; j++) {
+        bs_rounds<0, BS_LOCAL_PER_THREAD>(rounds, [&](auto jc) {
+            constexpr int j = decltype(jc)::value;
             const uint32_t i = beg + threadIdx.x + 256u * j;
             lo[j] = 0xFFFFFFFFu; v[j] = 0u; rank[j] = 0u;
-            if (i < end) { lo[j] = keys[i] & mask; v[j] = vals[i]; }
-        }
-#pragma unroll
-        for (int j = 0; j < BS_LOCAL_PER_THREAD; j++)
-            if (lo[j] != 0xFFFFFFFFu) rank[j] = atomicAdd(&s_cnt[lo[j]], 1u);
+            if (i < end) { lo[j] = keys[i]; v[j] = vals[i]; }       // (the whole key: masked below, so that no round waits for its load here)
+        });
+        bs_rounds<0, BS_LOCAL_PER_THREAD>(rounds, [&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            if (lo[j] != 0xFFFFFFFFu) { lo[j] &= mask; rank[j] = atomicAdd(&s_cnt[lo[j]], 1u); }   // (a key is a bin number: never all ones)
+        });
     } else {
         for (uint32_t i = beg + threadIdx.x; i < end; i += 256) atomicAdd(&s_cnt[keys[i] & mask], 1u);
     }
@@ -158,9 +178,10 @@ __global__ __launch_bounds__(256) void k_bs_local(const uint32_t *__restrict__ k
     }
     __syncthreads();
     if (small) {
-#pragma unroll
-        for (int j = 0; j < BS_LOCAL_PER_THREAD; j++)
+        bs_rounds<0, BS_LOCAL_PER_THREAD>(rounds, [&](auto jc) {
+            constexpr int j = decltype(jc)::value;
             if (lo[j] != 0xFFFFFFFFu) entries[s_cnt[lo[j]] + rank[j]] = v[j];
+        });
     } else {
         for (uint32_t i = beg + threadIdx.x; i < end; i += 256) {
             const uint32_t at = atomicAdd(&s_cnt[keys[i] & mask], 1u);

@@ -229,9 +229,9 @@ __device__ __forceinline__ void cube_bin_of2(const v3p &rd, uint32_t face_base0,
     }
 }
 
-// A tile pair as the trace kernel's waves pick it up: the first tile's camera bin, where its list starts (the second tile's
-// follows it), and the two lengths.
-struct TilePairRec { uint32_t tile, beg, nA, nB; };
+// A tile pair as the trace kernel's waves pick it up: the first tile's place in the frame (column | row << 16, in tiles: the wave
+// divides nothing; capi/binned.cpp refuses a frame of more than 65535 tiles either way), where its list starts (the second tile's follows it), and the two lengths.
+struct TilePairRec { uint32_t txy, beg, nA, nB; };
 constexpr int ORDER_CLASSES = 8;                 // classes of max(nA, nB) / ORDER_CLASS_STEP, the last one open-ended
 constexpr int ORDER_GROUPS = 8;                  // one list per XCD group (workgroup id % 8)
 constexpr uint32_t ORDER_CLASS_STEP = 16;        // = TR_STAGE: a class is a number of staging chunks
@@ -260,8 +260,8 @@ struct RtTraceFrame {
     const uint32_t *sel_count;        // back to brute force walks (their origin rows are the ones the frame has built)
     int lazy_geo;                     // 1: geometry rows are fetched by the exact stage, for the pairs it accepts, instead of being staged
                                       // with every candidate (scenes whose tables no longer fit the caches: see the staging code)
-    const uint32_t *light_pair_count; // the same for the light-cube lists when a pass of their own built them (nullable: the shared,
-    uint32_t light_pair_cap;          // cached cube never overflows): beyond it the shadow rays walk the lights' origin tables
+    const uint32_t *light_pair_count; // the same for the light-cube lists when a pass of their own built them (the shared, cached cube never
+    uint32_t light_pair_cap;          // overflows: any readable word and a cap of 2^32 - 1): beyond it the shadow rays walk the lights' origin tables
 };
 
 // One wave renders one PAIR of horizontally adjacent tiles.  Two things decide which wave takes which pair:
@@ -289,12 +289,13 @@ __global__ __launch_bounds__(64) void k_tile_order(const uint32_t *__restrict__ 
     TilePairRec r = { 0u, 0u, 0u, 0u };
     int cls = -1;
     if (px < pairs_x) {
-        r.tile = (uint32_t)(ty * tiles_x + 2 * px);
+        const uint32_t tile = (uint32_t)(ty * tiles_x + 2 * px);
+        r.txy = (uint32_t)(2 * px) | ((uint32_t)ty << 16);
         cls = 0;
         if (counters[0] <= pair_cap) {
-            const uint32_t b0 = cam_off[(size_t)r.tile * cam_shells], b1 = cam_off[(size_t)(r.tile + 1) * cam_shells];
+            const uint32_t b0 = cam_off[(size_t)tile * cam_shells], b1 = cam_off[(size_t)(tile + 1) * cam_shells];
             r.beg = b0; r.nA = b1 - b0;
-            r.nB = 2 * px + 1 < tiles_x ? cam_off[(size_t)(r.tile + 2) * cam_shells] - b1 : 0u;
+            r.nB = 2 * px + 1 < tiles_x ? cam_off[(size_t)(tile + 2) * cam_shells] - b1 : 0u;
             cls = (int)min(max(r.nA, r.nB) / ORDER_CLASS_STEP, (uint32_t)(ORDER_CLASSES - 1));
         }
     }
@@ -340,31 +341,46 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
 {
     extern __shared__ __attribute__((aligned(16))) float4 s_all[];
     const RtFrame &f = tf.f;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // (the wave's index is the same in every lane: said once, so that everything derived from it stays on the scalar unit)
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     TrWaveLds &s = reinterpret_cast<TrWaveLds *>(s_all)[wave];
 
     // Wave -> tile pair: record w of its XCD group's list (k_tile_order), longest lists first.  (Waves never synchronise with each other, so a
     // workgroup is just a scheduling unit of 1, 2 or 4 of them.)
     const uint32_t group = blockIdx.x & (ORDER_GROUPS - 1);                       // = this workgroup's XCD group
     uint32_t w = (blockIdx.x >> 3) * (blockDim.x >> 6) + (uint32_t)wave;          // this wave among the group's
-    TilePairRec rec = { 0u, 0u, 0u, 0u };
+    // Everything the wave reads before its first chunk besides the record is wave-uniform and asked for HERE, together, and waited for
+    // once: the group's eight class counts (32 bytes, 32-byte aligned: one scalar load), the pair counts of the camera's and the
+    // lights' passes and the selection's count (used by an overflowed frame only; its word is always there).  One after the other,
+    // each behind its own wait, they were seven dependent round trips and ~50 exec-masked vector instructions in every wave.
+    const uint4 *cp = reinterpret_cast<const uint4 *>(__builtin_assume_aligned(tf.order_count + group * ORDER_CLASSES, 32));
+    const uint4 c0 = cp[0], c1 = cp[1];
+    const uint32_t npairs = *tf.pair_count, nlpairs = *tf.light_pair_count, nsel = *tf.sel_count;
+    const int W = f.W, H = f.H;                            // (kernel-argument words the stores at the end want: not re-read inside their branches)
+    TilePairRec rec;
     {
-        bool found = false;
+        // the class and the place in it by scalar arithmetic, the record by a scalar load: the wave's last indirection.  Classes are
+        // taken longest first: class c's records end at `sum`; a wave at or past that belongs to a later (shorter) class, which starts there.
+        const uint32_t cnt[ORDER_CLASSES] = { c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w };
+        uint32_t sum = 0, first = 0;
+        int cls = ORDER_CLASSES - 1;
 #pragma unroll
         for (int c = ORDER_CLASSES - 1; c >= 0; c--) {
-            const uint32_t cnt = tf.order_count[group * ORDER_CLASSES + c];
-            if (!found && w < cnt) { rec = tf.order[((size_t)group * ORDER_CLASSES + c) * tf.order_seg + w]; found = true; }
-            if (!found) w -= cnt;
+            sum += cnt[c];
+            const bool past = w >= sum;
+            first = past ? sum : first;
+            cls = past ? c - 1 : cls;
         }
-        if (!found) return;                                // beyond the group's pairs
+        if (cls < 0) return;                               // beyond the group's pairs
+        const uint32_t at = w - first;
+        const uint4 r4 = *reinterpret_cast<const uint4 *>(tf.order + ((size_t)group * ORDER_CLASSES + (uint32_t)cls) * tf.order_seg + at);
+        rec.txy = r4.x; rec.beg = r4.y; rec.nA = r4.z; rec.nB = r4.w;
     }
-    rec.tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec.tile); rec.beg = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec.beg);
-    rec.nA = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec.nA); rec.nB = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec.nB);
-    const int txA = (int)(rec.tile % (uint32_t)tf.tiles_x), ty = (int)(rec.tile / (uint32_t)tf.tiles_x);
+    const int txA = (int)(rec.txy & 0xFFFFu), ty = (int)(rec.txy >> 16);          // (packed by k_tile_order: nothing to divide)
     const bool enB = txA + 1 < tf.tiles_x;
     const int xA = txA * BIN_TILE + (lane & 7), xB = xA + BIN_TILE, y = ty * BIN_TILE + (lane >> 3);
     const bool okY = y >= f.y0 && y < f.y1;
-    const bool okA = okY && xA < f.W, okB = enB && okY && xB < f.W;
+    const bool okA = okY && xA < W, okB = enB && okY && xB < W;
     const unsigned long long okmA = wballot(okA), okmB = wballot(okB);
     const unsigned nokA = (unsigned)__popcll(okmA), nokB = (unsigned)__popcll(okmB);
 #ifdef MIRT_TR_TIMING
@@ -376,14 +392,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
 #define TM_SEG(i)
 #endif
     // the pair list overflowed (it was sized from an earlier frame's count): no lists -- every tile takes every triangle
-    const bool brute = (uint32_t)__builtin_amdgcn_readfirstlane((int)*tf.pair_count) > tf.pair_cap;
-    // ... and the light lists: their own pass's count where there was one
-    const bool brute_l = tf.light_pair_count ? (uint32_t)__builtin_amdgcn_readfirstlane((int)*tf.light_pair_count) > tf.light_pair_cap : false;
+    const bool brute = npairs > tf.pair_cap;
+    // ... and the light lists: their own pass's count where there was one (the shared cube's never overflow: capi/binned.cpp passes a
+    // cap no count exceeds)
+    const bool brute_l = nlpairs > tf.light_pair_cap;
     const v3 cam = ld3(f.cam);
     const int rs = AA ? f.aa : 1;                          // realSamples (:549-554); compile-time 1 without supersampling
 
     const uint32_t begA = rec.beg, begB = rec.beg + rec.nA;
-    const uint32_t nall = brute ? min((uint32_t)__builtin_amdgcn_readfirstlane((int)*tf.sel_count), (uint32_t)f.n) : 0u;
+    const uint32_t nall = brute ? min(nsel, (uint32_t)f.n) : 0u;
     const uint32_t nA = brute ? nall : rec.nA, nB = brute ? (enB ? nall : 0u) : rec.nB;
     const uint32_t nmax = max(nA, nB);
     const float4 *geo4 = reinterpret_cast<const float4 *>(tf.geo);
@@ -397,7 +414,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
     unsigned ntests = 0, ncand = 0, nsteps_p = 0, nsteps_s = 0, ndrains = 0;     // wave-uniform counters
     unsigned ncand_l = 0;                                  // per lane: shadow candidates offered
     int qn = 0;                                            // queued pairs (wave-uniform)
-    const float hw = (float)f.W / 2.0f, hh = (float)f.H / 2.0f;
+    const float hw = (float)W / 2.0f, hh = (float)H / 2.0f;
 
     f2 y1 = splat2(aa_start(y, rs));                       // :566-569
     for (int z = 0; z < rs; z++) {
@@ -712,22 +729,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
     }
     if (okA) {
         const v3 c = half0(avg);
-        const size_t px = (size_t)y * f.W + xA;
+        const size_t px = (size_t)y * W + xA;
         if (f.rgb) st3(f.rgb + 3 * px, c);
         if (f.index) f.index[px] = biA;
         if (f.fd) f.fd[px] = biA >= 0 ? bdA - f.focal_plane : 0.0f;            // focalDistances (:248-249)
         store_intersection(f, px, biA, bdA, posA);
-        if (xA >= 1 && xA < f.W - 1 && y >= 1 && y < f.H - 1)      // (:618-620)
+        if (xA >= 1 && xA < W - 1 && y >= 1 && y < H - 1)      // (:618-620)
             f.xrgb[(size_t)(y - f.row_origin) * f.pitch_words + xA] = pack_xrgb(c);
     }
     if (okB) {
         const v3 c = half1(avg);
-        const size_t px = (size_t)y * f.W + xB;
+        const size_t px = (size_t)y * W + xB;
         if (f.rgb) st3(f.rgb + 3 * px, c);
         if (f.index) f.index[px] = biB;
         if (f.fd) f.fd[px] = biB >= 0 ? bdB - f.focal_plane : 0.0f;
         store_intersection(f, px, biB, bdB, posB);
-        if (xB >= 1 && xB < f.W - 1 && y >= 1 && y < f.H - 1)
+        if (xB >= 1 && xB < W - 1 && y >= 1 && y < H - 1)
             f.xrgb[(size_t)(y - f.row_origin) * f.pitch_words + xB] = pack_xrgb(c);
     }
 }
