@@ -847,6 +847,7 @@ int launch_raster(RasterFrame &f, RasterScratch &s, uint64_t scene_version, hipS
         const int threads = lds_rows > 512 ? 1024 : 256;
         hipLaunchKernelGGL(k_raster_edges_lds, dim3(f.n), dim3(threads), (size_t)15 * 4 * (((lds_rows + 3) & ~3) + 4), stream, f, lds_rows);
     }
+    // (both launches in one frame, and the chunked kernel with several chunks: tests/test_gpu_raster_tall.py)
     if (tall) hipLaunchKernelGGL(k_raster_edges, dim3(f.n), dim3(256), 0, stream, f, lds_rows);
     end(MIRT_K_RASTER_SETUP);
 

@@ -684,7 +684,18 @@ def test_raster_triangles_crossing_the_camera_plane(oracle):
 
 def test_raster_two_lights_and_band(oracle):
     lights = np.array([[0, -0.5, -0.7, 1, 1, 1, 14], [0.5, 0.4, -1.5, 0.2, 0.9, 0.5, 9]], np.float32)
-    _raster_compare(oracle, mirt.scene_cornell(), (0.1, 0, -3), oracle.rot_from_yaw(0.15, 1.01), 300.0, 320, 300, lights)
+    from devbuf import DeviceArray
+    W, H = 320, 300
+    cam, rot = (0.1, 0, -3), oracle.rot_from_yaw(0.15, 1.01)
+    _, ref = _raster_compare(oracle, mirt.scene_cornell(), cam, rot, 300.0, W, H, lights)
+    # the same view (scene and cull flags as _raster_compare uploaded them) in two bands that split the frame on an odd row
+    view = mirt.make_view(cam, rot, 300.0, W, H)
+    for (y0, y1) in [(0, 113), (113, 300)]:
+        with DeviceArray((H, W), np.uint32, 0x5A) as surf:
+            mirt.rasterise_device(view, lights, (0.2, 0.2, 0.2), y0, y1, 0, surf.ptr, W * 4)
+            got = surf.read()
+        assert np.array_equal(got[y0:y1], ref["xrgb"][y0:y1]), "band [%d, %d): %d words differ" % (y0, y1, int((got[y0:y1] != ref["xrgb"][y0:y1]).sum()))
+        assert (got[:y0] == 0x5A5A5A5A).all() and (got[y1:] == 0x5A5A5A5A).all()
 
 
 # ---- depth of field (parity unpinned: no recorded reference output) ---------------
