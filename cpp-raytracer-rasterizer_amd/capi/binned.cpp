@@ -572,6 +572,7 @@ int binned_pass(const RtFrame &f, const mirt_view *view, RtScratch &S, RtScratch
     bp->cam_off = cam_off;
     bp->tiles_x = bs.frame0.nbu;
     bp->cam_shells = bs.frame0.nshell;
+    bp->shell_d0 = bs.frame0.shell_d0; bp->shell_iw = bs.frame0.shell_iw;
     bp->order_seg = order_seg;
     bp->transient = transient;
     bp->cube_bins = cube_bins;
@@ -644,6 +645,10 @@ int binned_trace(const RtFrame &f, RtScratch &S, RtScratch &L, const BinnedPass 
     tf.cube_bins = bp.cube_bins;
     tf.cam_shells = bp.cam_shells;
     tf.light_shells = bp.light_shells;
+    tf.shell_d0 = bp.shell_d0; tf.shell_iw = bp.shell_iw;
+    // a tile's list ends at the depth shell of the tile's farthest record (rt_trace.hip); MIRT_TR_LIST_END=0 walks every list to its end
+    static const int list_end_env = (int)env_int("MIRT_TR_LIST_END", 1);
+    tf.list_end = list_end_env != 0;
     tf.pair_count = S.d_bin_counters;
     tf.pair_cap = S.cap_used;
     // (lights binned by the frame: their own pass's count; the shared cube's tables are complete by construction -- the kernel reads

@@ -59,6 +59,8 @@ struct RtTraceFrame {                            // (rt_trace.hip)
     int cube_bins;
     int cam_shells;
     int light_shells;
+    float shell_d0, shell_iw;
+    int list_end;
     const uint32_t *pair_count;
     uint32_t pair_cap;
     const TilePairRec *order;
@@ -371,6 +373,7 @@ bool frame_fits_binning(int W, int H);
 struct BinnedPass {
     const uint32_t *cam_off;                     // camera offsets, indexed by the FRAME's tile number
     int tiles_x, cam_shells;
+    float shell_d0, shell_iw;                    // the camera frame's depth-shell parameters: what the tiles' lists were sorted with
     uint32_t order_seg;                          // tile-pair records per (XCD group, class) segment of the order
     bool transient;                              // light tables: this frame's own pass (the stream's rt_lt), or the shared cache
     int cube_bins, light_shells;

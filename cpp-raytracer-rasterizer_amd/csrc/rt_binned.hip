@@ -464,7 +464,7 @@ __global__ __launch_bounds__(WG) void k_bin_pairs(const float *__restrict__ tris
         uint32_t shell = 0;                               // depth shell of the triangle in this frame (orders the bins' lists)
         if (tri < (uint32_t)n && fj1 > fj0) {
             const OriginRow &row = (fr.tab == 0) ? cam_tab[tri] : light_tab[(size_t)(fr.tab - 1) * n + tri];
-            shell = bin_shell_of(fr, row.r1.w);
+            shell = bin_shell_of(row.r1.w, fr.shell_d0, fr.shell_iw, fr.nshell);
             TriBinFns t = make_bin_fns(row, fr);
             add_bbox(t, tris15 + (size_t)15 * tri, fr);
 #ifdef MIRT_BIN_STATS

@@ -55,11 +55,22 @@ struct BinFrameDesc {
     float shell_d0, shell_iw;    // shell = clamp((int)((near - shell_d0) * shell_iw), 0, nshell - 1)
 };
 
-__device__ __forceinline__ uint32_t bin_shell_of(const BinFrameDesc &fr, float near)
+// The one formula: the sort key's shell (k_bin_pairs) and every consumer that ends a list by shell (the shadow walk and the
+// primary loop of rt_trace.hip) call it, so a candidate's shell is the same number wherever it is asked for.  A subtraction, a
+// multiplication by iw >= 0 and a saturating conversion: monotone in `near`, i.e. near <= bound implies shell(near) <=
+// shell(bound) -- a candidate of a later shell than the bound's lies beyond the bound.  NaN maps to shell 0 (never skipped).
+// The device's float-to-int conversion saturates and turns NaN into 0; the host's is undefined out of range, so the host twin
+// clamps first -- same value for every input (tests/cpp/shell_end_test.cpp).
+MIRT_HD uint32_t bin_shell_of(float near, float d0, float iw, int nshell)
 {
-    if (fr.nshell <= 1) return 0u;
-    const float s = (near - fr.shell_d0) * fr.shell_iw;
-    return (uint32_t)min(max((int)s, 0), fr.nshell - 1);         // NaN converts to 0
+    if (nshell <= 1) return 0u;
+    const float s = (near - d0) * iw;
+#ifdef __HIP_DEVICE_COMPILE__
+    return (uint32_t)min(max((int)s, 0), nshell - 1);
+#else
+    if (!(s >= 0.0f)) return 0u;                                 // negative or NaN
+    return s >= (float)(nshell - 1) ? (uint32_t)(nshell - 1) : (uint32_t)(int)s;
+#endif
 }
 
 // Geometry row of a triangle: {v0.xyz, e1.x | e1.yz, e2.xy | e2.z, 0, 0, 0} -- what the accept path needs to rebuild the hit

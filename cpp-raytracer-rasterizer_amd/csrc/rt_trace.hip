@@ -250,6 +250,8 @@ struct RtTraceFrame {
     int cube_bins;                    // B: light-cube bins per face side
     int cam_shells;                   // depth shells per camera bin: bin b's list is cam_off[b * cam_shells] .. cam_off[(b + 1) * cam_shells]
     int light_shells;                 // depth shells per light-cube bin
+    float shell_d0, shell_iw;         // the camera frame's shell parameters (BinFrameDesc): what the tiles' lists were sorted with
+    int list_end;                     // 1: a tile's list ends at the shell of the tile's farthest record (the primary loop below); MIRT_TR_LIST_END
     const uint32_t *pair_count;       // pairs this frame's binning produced / room in the pair list: beyond it the lists are
     uint32_t pair_cap;                // incomplete and every tile takes the whole triangle list instead (brute force)
     const TilePairRec *order;         // the frame's tile pairs by XCD group and list-length class (k_tile_order): ORDER_GROUPS x ORDER_CLASSES
@@ -402,9 +404,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
     const uint32_t begA = rec.beg, begB = rec.beg + rec.nA;
     const uint32_t nall = brute ? min(nsel, (uint32_t)f.n) : 0u;
     const uint32_t nA = brute ? nall : rec.nA, nB = brute ? (enB ? nall : 0u) : rec.nB;
-    const uint32_t nmax = max(nA, nB);
     const float4 *geo4 = reinterpret_cast<const float4 *>(tf.geo);
     const bool lazy = tf.lazy_geo != 0;
+    const bool list_end = tf.list_end != 0 && !brute;
     TM_SEG(0)
 
     float bdA = FLT_MAX, bdB = FLT_MAX;                    // Update() reset (:335-339), once per frame
@@ -432,14 +434,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
             // drains most of a list is skipped.  The records are only updated by drains, i.e. the bounds lag -- never the result.
             s.best[lane] = MIN_T_NONE; s.best[lane + 64] = MIN_T_NONE;
             s.flag[lane] = 0; s.flag[lane + 64] = 0;
-            if (STATS) ncand += nokA * nA + nokB * nB;
             // distance of the sub-ray's record so far; -inf for a lane without a pixel (outside the frame or the rows of this call):
             // every candidate's `near` lies beyond it, so such a lane never passes the near test below and needs no mask of its own
             float lbA = okA ? FLT_MAX : -__builtin_huge_valf(), lbB = okB ? FLT_MAX : -__builtin_huge_valf();
             float tbA = FLT_MAX, tbB = FLT_MAX;            // their maxima over the tile's pixels (wave-uniform)
-            for (uint32_t base = 0; base < nmax; base += TR_STAGE) {
-                const int cntA = (int)min((uint32_t)TR_STAGE, nA > base ? nA - base : 0u);
-                const int cntB = (int)min((uint32_t)TR_STAGE, nB > base ? nB - base : 0u);
+            // How much of each list this sub-ray still walks (wave-uniform).  A list is sorted by the depth shell of its candidates'
+            // `near` (k_bin_pairs: key = bin * shells + bin_shell_of(near)), so once a staged candidate j lies in a later shell than
+            // the tile's farthest record tb, every candidate c behind it does too: shell(c) >= shell(j) > shell(tb), and since
+            // bin_shell_of is monotone, near(c) > tb >= the record of every pixel of the tile.  `near` is a lower bound of any hit
+            // distance on the triangle, so c cannot replace a record, not even by the `>=` tie, and every pixel has a record (tb <
+            // FLT_MAX's shell), so ClosestIntersection's return value is settled too: the list ends with the chunk that holds j.
+            // The records only fall, so a tb that lags is safe.  tb = FLT_MAX (a pixel without a hit) is the last shell and ends
+            // nothing, as does one shell; a NaN `near` is shell 0 and never ends a list.  An overflowed frame walks the selection,
+            // which is not sorted: no early end there (list_end below).
+            uint32_t liveA = nA, liveB = nB;
+            for (uint32_t base = 0; base < max(liveA, liveB); base += TR_STAGE) {
+                const int cntA = (int)min((uint32_t)TR_STAGE, liveA > base ? liveA - base : 0u);
+                const int cntB = (int)min((uint32_t)TR_STAGE, liveB > base ? liveB - base : 0u);
+                if (STATS) ncand += nokA * (unsigned)cntA + nokB * (unsigned)cntB;       // offered: what is staged
                 wave_lds_fence();                          // the previous chunk's row reads are done
                 float my_near = 0.0f;
                 const int sh = lane >> 4, sj = lane & 15;  // lanes 0..15 stage tile A's candidates, 16..31 tile B's
@@ -537,12 +549,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
                 // the chunk's queued pairs are settled before the next chunk replaces the staged rows (their geometry lives there);
                 // the records they leave prune the next chunk
                 TM_SEG(2)
+                const bool more = base + TR_STAGE < max(liveA, liveB);
                 if (qn) {
                     tr_drain<false>(s, lane, qn, geo4, cam, nullptr, lazy); qn = 0; if (STATS) ndrains++;
-                    if (base + TR_STAGE < nmax) {
+                    if (more) {
                         lbA = okA ? min_t_dist(s.best[lane]) : lbA; lbB = okB ? min_t_dist(s.best[lane + 64]) : lbB;
                         tbA = wave_max_f(lbA); tbB = wave_max_f(lbB);
                     }
+                }
+                // the early end, judged once per chunk where the bounds are freshest -- behind the chunk's drains, the staging
+                // lanes' `near` still in its register (with no drain in the chunk these are the bounds it was staged under)
+                if (more && list_end) {
+                    const bool later = stage && bin_shell_of(my_near, tf.shell_d0, tf.shell_iw, tf.cam_shells) >
+                                                bin_shell_of(sh ? tbB : tbA, tf.shell_d0, tf.shell_iw, tf.cam_shells);
+                    const uint32_t lm = (uint32_t)wballot(later);
+                    if (lm & 0xFFFFu) liveA = min(liveA, base + (uint32_t)TR_STAGE);
+                    if (lm >> 16) liveB = min(liveB, base + (uint32_t)TR_STAGE);
                 }
                 TM_SEG(3)
             }
@@ -601,12 +623,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
                         rows4 = reinterpret_cast<const float4 *>(tf.light_rows);
                         uint32_t binA, binB;
                         cube_bin_of2(rd, (uint32_t)k * 6u * (uint32_t)(tf.cube_bins * tf.cube_bins), tf.cube_bins, &binA, &binB);
-                        // (shell of 0.99 r: bin_shell_of's formula on wave-uniform parameters, loaded once per light)
+                        // (shell of 0.99 r: bin_shell_of on wave-uniform parameters, loaded once per light)
                         const BinFrameDesc *lf = tf.light_frames + 6 * k;
                         const int ns = tf.light_shells;
                         const float sd0 = lf->shell_d0, siw = lf->shell_iw;
-                        const uint32_t shA = ns > 1 ? (uint32_t)min(max((int)((thr.x - sd0) * siw), 0), ns - 1) : 0u;
-                        const uint32_t shB = ns > 1 ? (uint32_t)min(max((int)((thr.y - sd0) * siw), 0), ns - 1) : 0u;
+                        const uint32_t shA = bin_shell_of(thr.x, sd0, siw, ns), shB = bin_shell_of(thr.y, sd0, siw, ns);
                         if (hitA) {
                             const uint32_t key = binA * (uint32_t)ns;
                             eA = tf.light_off[key]; endA = tf.light_off[key + shA + 1u];

@@ -79,8 +79,9 @@ typedef struct mirt_stats {
     float gpu_ms;                 /* hipEvent time of the call's device work; 0 unless profiling is on   */
     float kernel_ms[8];           /* per-kernel time of the call when profiling is on (see below)    */
     int32_t mode_used;            /* mirt_rt_mode actually used                                      */
-    uint64_t candidates;          /* ray-candidate pairs the frame's lists offered (>= tests: the binned kernel skips
-                                     candidates that cannot matter before it tests them); == tests elsewhere */
+    uint64_t candidates;          /* ray-candidate pairs offered to the rays after the early end (a tile's list ends at the depth
+                                     shell of the tile's farthest hit; >= tests: the binned kernel skips candidates that cannot
+                                     matter before it tests them); == tests elsewhere */
     /* the binned ray tracer's own loop counts (0 elsewhere): wave-level steps of the two filter loops -- one step = one
      * candidate row tested by the lanes of a wave -- and exact-stage drains; what the kernel's instruction count scales with */
     uint64_t steps_primary;
