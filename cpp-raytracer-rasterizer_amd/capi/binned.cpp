@@ -232,12 +232,14 @@ int ensure_face_lists(RtScratch &S, int nlights)
 // The SHARED light-cube bins and their expanded rows, for lights that stand still: built on g.stream as a barrier call -- the
 // frames of both streams read the tables -- whenever the scene, a light position or the grid differs from what is held.  (Lights
 // that just moved do not come here: binned_pass bins their cubes together with the camera frame, on the frame's own stream.)
-int light_cache_ensure(RtScratch &S, const RtFrame &f, const float *origins, int nlights, int cube_bins)
+// C: the frame path's shared cube (g.lc) or the queries' (g.qrows.cube); either is read by the work of every stream.
+int light_cache_ensure(LightCache &C, RtScratch &S, const RtFrame &f, const float *origins, int nlights, int cube_bins, bool *built)
 {
     int rc;
-    LightCache &C = g.lc;
     const uint64_t key = light_key_of(origins, nlights);
+    if (built) *built = false;
     if (C.valid && C.key == key && C.cube_bins == cube_bins) return MIRT_OK;
+    if (built) *built = true;
     C.valid = false;
     for (int o = 0; o < g.in_flight; o++)                  // frames of the other streams may still read the old tables
         if (o != g.si) {
@@ -306,6 +308,26 @@ int light_cache_ensure(RtScratch &S, const RtFrame &f, const float *origins, int
     C.cube_bins = cube_bins;
     C.valid = true;
     return MIRT_OK;
+}
+
+// The grid of a light cube: finer grids shorten the shadow lists; the bins are built once per (scene, lights), not per frame, so what
+// they cost is memory (48 bytes per (bin, triangle) pair) and ~1 ms of build for 100 k triangles.  Measured on the 100 k soup at 1080p
+// (round 2's trace kernel, lists not yet ordered by depth): 64: 153 us, 128: 125 us, 256: 105 us.  MIRT_CUBE_BINS=64|128|256 fixes
+// the grid (and keeps every frame on the shared cache).
+int light_cube_bins_for(int nlights, bool *fixed_grid)
+{
+    static const int cube_override = (int)env_int("MIRT_CUBE_BINS", 0);
+    int fine_bins = g.n < 2000 ? CUBE_BINS_MIN : (g.n < 20000 ? 2 * CUBE_BINS_MIN : 4 * CUBE_BINS_MIN);
+    *fixed_grid = cube_override == 64 || cube_override == 128 || cube_override == 256;
+    if (*fixed_grid) fine_bins = cube_override;
+    // (many light positions -- 16 soft-shadow samples of two lights -- at the finest grid are more keys than one sort pass holds)
+    while (fine_bins > CUBE_BINS_MIN && 6ll * fine_bins * fine_bins * nlights * 4 > (long long)BIN_MAX_KEYS) fine_bins /= 2;
+    return fine_bins;
+}
+
+bool light_keys_fit(int nlights, int cube_bins)
+{
+    return 6ll * cube_bins * cube_bins * std::max(nlights, 1) + 64 <= (long long)BIN_MAX_KEYS;
 }
 
 // Depth shells of the camera bins for a frame of `tiles` bins (the tiles' lists come out of the sort roughly front to back).
@@ -409,16 +431,9 @@ int binned_pass(const RtFrame &f, const mirt_view *view, RtScratch &S, RtScratch
     int rc;
     g.stats.mode_used = MIRT_RT_BINNED;
     g.stats_sel_count = nullptr;
-    // light-cube resolution: bins per face side.  Finer grids shorten the shadow lists; the shared bins are built once per
-    // (scene, lights), not per frame, so what they cost is memory (48 bytes per (bin, triangle) pair) and ~1 ms of build for
-    // 100 k triangles.  Measured on the 100 k soup at 1080p (round 2's trace kernel, lists not yet ordered by depth): 64: 153 us,
-    // 128: 125 us, 256: 105 us.  MIRT_CUBE_BINS=64|128|256 fixes the grid (and keeps every frame on the shared cache).
-    static const int cube_override = (int)env_int("MIRT_CUBE_BINS", 0);
-    int fine_bins = g.n < 2000 ? CUBE_BINS_MIN : (g.n < 20000 ? 2 * CUBE_BINS_MIN : 4 * CUBE_BINS_MIN);
-    const bool fixed_grid = cube_override == 64 || cube_override == 128 || cube_override == 256;
-    if (fixed_grid) fine_bins = cube_override;
-    // (many light positions -- 16 soft-shadow samples of two lights -- at the finest grid are more keys than one sort pass holds)
-    while (fine_bins > CUBE_BINS_MIN && 6ll * fine_bins * fine_bins * nlights * 4 > (long long)BIN_MAX_KEYS) fine_bins /= 2;
+    // light-cube resolution: bins per face side (light_cube_bins_for)
+    bool fixed_grid = false;
+    const int fine_bins = light_cube_bins_for(nlights, &fixed_grid);
 
     const uint64_t lkey = light_key_of(origins, nlights);
     if (g.lc.track_key == lkey) g.lc.stable++;
@@ -427,7 +442,7 @@ int binned_pass(const RtFrame &f, const mirt_view *view, RtScratch &S, RtScratch
     const bool transient = nlights > 0 && !fixed_grid && !cached && g.lc.stable < LIGHT_STABLE_FRAMES;
 
     k_begin(MIRT_K_BIN);
-    if (!transient && (rc = light_cache_ensure(L, f, origins, nlights, fine_bins))) return rc;   // (in the light pass's scratch: the camera's tables stay)
+    if (!transient && (rc = light_cache_ensure(g.lc, L, f, origins, nlights, fine_bins))) return rc;   // (in the light pass's scratch: the camera's tables stay)
     const int cube_bins = transient ? CUBE_BINS_MIN : fine_bins;
 
     BinSet bs;

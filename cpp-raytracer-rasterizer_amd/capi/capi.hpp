@@ -207,6 +207,7 @@ struct QueryScratch {
     float *d_origins = nullptr;                  // (1 + MIRT_MAX_LIGHTS) x 3; row 0 (the camera's place) is unused
     uint32_t *d_flags = nullptr;                 // [0] = unsafe flag
     uint64_t rows_seen = 0;                      // the QueryRows::version this stream is already ordered behind (0 = none)
+    unsigned long long *d_stats = nullptr;       // QSTAT_WORDS counters of the stream's last binned DirectLight query (profiling on)
 
     void release();
 };
@@ -222,8 +223,13 @@ struct QueryRows {
     // staging of the host-buffer entry points (mirt_intersect, mirt_direct_light)
     void *d_rays = nullptr, *d_hits = nullptr, *d_rgb = nullptr;
     size_t cap = 0;                              // rays / records each holds
+    // The light cube of the DirectLight queries: a LightCache like the frame path's g.lc, keyed alike (scene version + the light
+    // positions in use, and the grid -- so a new scene forgets it), kept across calls, shared by the streams and ordered among
+    // them by light_cache_ensure's events.  A query whose lights are the ones the frame path's valid cube holds reads g.lc and
+    // leaves this one as it is; no query ever writes g.lc or what the frame path tracks in it.
+    LightCache cube;
 
-    void release();
+    void release();                              // (the cube's tables too)
 };
 
 // Everything a frame in flight owns: its stream and the scratch its kernels write.  A frame reads the scene and writes the
@@ -289,6 +295,10 @@ struct Ctx {
     float bbox_lo[3] = { 0, 0, 0 }, bbox_hi[3] = { 0, 0, 0 };   // the scene's bounding box (host side, mirt_scene_upload)
     LightCache lc;
     QueryRows qrows;
+    int query_mode = MIRT_QUERY_AUTO;            // mirt_set_query_mode
+    mirt_query_stats qstats = {};                // the last DirectLight query: how it was answered (mirt_get_query_stats) ...
+    hipStream_t qstats_stream = nullptr;         // ... the stream it ran on ...
+    const unsigned long long *qstats_dev = nullptr;   // ... and where its kernel's counters are (device; profiling on, binned)
     unsigned long long *d_hits = nullptr;        // the hit-counter buffer of the current ray-traced frame (one of its stream's d_hits)
     bool scene_finite = true;                    // all vertex coordinates below MIRT_SAFE_MAG
     uint64_t scene_version = 0;                  // bumped whenever the triangles change
@@ -378,6 +388,14 @@ struct BinnedPass {
     bool transient;                              // light tables: this frame's own pass (the stream's rt_lt), or the shared cache
     int cube_bins, light_shells;
 };
+// A light cube's tables in C for `nlights` light positions (origins[3 ..]) on a grid of cube_bins, built on g.stream in S -- a
+// stream's LIGHT scratch set, whose kept pass the build invalidates -- unless C holds them already; *built says which.
+int light_cache_ensure(LightCache &C, RtScratch &S, const RtFrame &f, const float *origins, int nlights, int cube_bins, bool *built = nullptr);
+uint64_t light_key_of(const float *origins, int nlights);
+// Bins per face side of the cubes of `nlights` light positions under the frame path's rules (scene size, MIRT_CUBE_BINS, the
+// sort's key space); *fixed_grid: the environment fixed it.  light_keys_fit: one sort pass holds such a cube's keys at all.
+int light_cube_bins_for(int nlights, bool *fixed_grid);
+bool light_keys_fit(int nlights, int cube_bins);
 int binned_pass(const RtFrame &f, const mirt_view *view, RtScratch &S, RtScratch &L, const float *origins, int nlights, int y0, int y1, BinnedPass *bp);
 int binned_trace(const RtFrame &f, RtScratch &S, RtScratch &L, const BinnedPass &bp);
 // Would rt_enqueue bin the WHOLE frame of this view (mode, scene size, operands in range, frame size)?  The same answer on every rank.

@@ -1,7 +1,8 @@
 // query.cpp -- ray queries: ClosestIntersection and DirectLight for the caller's own rays and records (mirt_intersect*,
 // mirt_direct_light*; the kernels: ../query/rt_query.hip).  The ray-independent rows of the scene are built once per scene
-// version and shared by the streams; a query takes the next stream as a frame does (mirt_set_frames_in_flight, mirt_sync) but
-// leaves the statistics of the last render call alone.
+// version and shared by the streams, and so is the light cube whose bins the shadow rays of DirectLight walk (per scene version
+// and light positions); a query takes the next stream as a frame does (mirt_set_frames_in_flight, mirt_sync) but leaves the
+// statistics of the last render call alone (DirectLight has its own: mirt_set_query_mode, mirt_get_query_stats, defined here).
 #include "capi.hpp"
 
 namespace mirt {
@@ -102,6 +103,82 @@ static int check_lights(const mirt_light *lights, int nlights, int *light_positi
     return MIRT_OK;
 }
 
+// ---- DirectLight: which kernel, which cube ----------------------------------------------------------------------------------
+
+// AUTO bins under the frame path's own rule (rt_frame.cpp: mode_bins) with the query's shadow work in the place of the frame's
+// pixels x triangles: a scene of MIRT_BIN_THRESHOLD triangles or more and records x light positions x triangles >= 4e7 -- below it
+// the cube's build (a binning pass and a sort, with one host read-back) costs more than the sweep it saves.
+// tools/ray_query_bench.py sweeps the record count for the crossing (profiles/ray_query_bench.txt).
+static bool auto_bins(int nhits, int npos)
+{
+    static const int auto_threshold = (int)env_int("MIRT_BIN_THRESHOLD", 65);
+    return g.n >= auto_threshold && (long long)nhits * npos * g.n >= 40000000LL;
+}
+
+// The brute-force kernel over origin tables of the query's own: k_prep_origin into the stream's frame tables would overwrite the
+// camera rows a kept binning pass counts on (rt_frame.cpp: rt_dispatch_brute).
+static int direct_light_brute(QueryLightFrame &q, const float *origins, int npos, bool safe)
+{
+    int rc;
+    RtFrame &f = q.f;
+    QueryScratch &S = g.cur().query;
+    if (npos > S.tab_lights || S.tab_n != g.n) {
+        S.tab_lights = 0;
+        if ((rc = dev_realloc(&S.d_light_tab, (size_t)npos * g.n))) return rc;
+        S.tab_lights = npos;
+        S.tab_n = g.n;
+    }
+    if (!S.d_origins) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_origins), sizeof(float) * 3 * (1 + MIRT_MAX_LIGHTS)));
+    if (!S.d_flags) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_flags), 16));
+    f.light_tab = S.d_light_tab;
+    f.unsafe = S.d_flags;
+    const uint32_t flags_init[4] = { safe ? 0u : 1u, 0u, 0u, 0u };
+    HIP_TRY(upload_small(S.d_flags, flags_init, sizeof flags_init, g.stream));
+    if (npos > 0) {
+        HIP_TRY(upload_small(S.d_origins, origins, sizeof(float) * 3 * (1 + npos), g.stream));
+        // origins 1 .. npos only: the launch never touches a camera table
+        hipLaunchKernelGGL(k_prep_origin, dim3((unsigned)((g.n + 255) / 256), (unsigned)npos), dim3(256), 0, g.stream,
+                           g.d_tris, g.n, S.d_origins, V3(0.0f, 0.0f, 0.0f), 1, (OriginRow *)nullptr, S.d_light_tab, S.d_flags,
+                           (unsigned long long *)nullptr, (uint32_t *)nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    const size_t lds = (size_t)(g.n < RT_CHUNK_ROWS ? g.n : RT_CHUNK_ROWS) * sizeof(OriginRow);
+    hipLaunchKernelGGL(k_query_direct_light<QUERY_P>, dim3((unsigned)((q.nhits + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), lds, g.stream, q);
+    HIP_TRY(hipGetLastError());
+    return MIRT_OK;
+}
+
+// The binned kernel over the cube C (the frame path's, or the queries' own after light_cache_ensure).
+static int direct_light_binned(QueryLightFrame &q, const LightCache &C)
+{
+    QueryScratch &S = g.cur().query;
+    QueryBinnedFrame b;
+    memset(&b, 0, sizeof b);
+    b.q = q;
+    b.q.f.light_tab = C.d_light_tab;             // (the records the bins do not cover sweep the cube's own origin table)
+    b.q.f.unsafe = nullptr;
+    b.light_off = C.d_off;
+    // (a lane with no row left still loads row 0 each step and ignores it: a cube without a single pair has no row table, so the
+    // loads are pointed at the origin table, which always has a row)
+    b.light_rows = C.nrows ? C.d_rows : C.d_light_tab;
+    b.light_tri = C.d_row_tri;
+    b.light_frames = C.d_frames;
+    b.cube_bins = C.cube_bins;
+    b.shells = C.shells;
+    const dim3 grid((unsigned)((q.nhits + 256 * QUERY_BIN_P - 1) / (256 * QUERY_BIN_P)));
+    if (g.profiling) {
+        if (!S.d_stats) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_stats), sizeof(unsigned long long) * QSTAT_WORDS));
+        HIP_TRY(hipMemsetAsync(S.d_stats, 0, sizeof(unsigned long long) * QSTAT_WORDS, g.stream));
+        b.stats = S.d_stats;
+        g.qstats_dev = S.d_stats;
+        hipLaunchKernelGGL((k_query_direct_light_binned<QUERY_BIN_P, true>), grid, dim3(256), 0, g.stream, b);
+    } else {
+        hipLaunchKernelGGL((k_query_direct_light_binned<QUERY_BIN_P, false>), grid, dim3(256), 0, g.stream, b);
+    }
+    HIP_TRY(hipGetLastError());
+    return MIRT_OK;
+}
+
 int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_rgb)
 {
     int rc, npos = 0;
@@ -136,33 +213,68 @@ int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, 
     q.nhits = nhits;
     q.rgb = static_cast<float *>(d_rgb);
 
+    // Binned or brute.  The frame path does not bin what lies outside the filter's proven range (rt_enqueue: operands_safe -- the
+    // scene, a light position; here that is the `unsafe` flag the brute kernel would be given) or what the sort cannot key; nor
+    // does a query, whatever the mode.  The cube: the frame path's when it holds these very lights on this very grid (read, never
+    // written -- nor its tracking of the frames' lights), else the queries' own, built now if need be.
+    bool fixed_grid = false;
+    const int cube_bins = light_cube_bins_for(npos, &fixed_grid);
+    const bool may_bin = safe && npos > 0 && light_keys_fit(npos, cube_bins);
+    const uint64_t lkey = may_bin ? light_key_of(origins, npos) : 0;
+    LightCache &own = g.qrows.cube;
+    const bool frames_cube = may_bin && g.lc.valid && g.lc.key == lkey && g.lc.cube_bins == cube_bins;
+    const bool own_cube = may_bin && own.valid && own.key == lkey && own.cube_bins == cube_bins;
+    const bool binned = may_bin && g.query_mode != MIRT_QUERY_BRUTE &&
+                        (g.query_mode == MIRT_QUERY_BINNED || frames_cube || own_cube || auto_bins(nhits, npos));
+
     stream_begin();
-    // origin tables of the query's own: k_prep_origin into the stream's frame tables would overwrite the camera rows a kept
-    // binning pass counts on (rt_frame.cpp: rt_dispatch_brute)
-    QueryScratch &S = g.cur().query;
-    if (npos > S.tab_lights || S.tab_n != g.n) {
-        S.tab_lights = 0;
-        if ((rc = dev_realloc(&S.d_light_tab, (size_t)npos * g.n))) return rc;
-        S.tab_lights = npos;
-        S.tab_n = g.n;
+    memset(&g.qstats, 0, sizeof g.qstats);
+    g.qstats.mode_used = binned ? MIRT_QUERY_BINNED : MIRT_QUERY_BRUTE;
+    g.qstats_stream = g.stream;
+    g.qstats_dev = nullptr;
+    if (!binned) return direct_light_brute(q, origins, npos, safe);
+
+    const LightCache *C = &g.lc;
+    int source = 3;
+    if (!frames_cube) {
+        // (in the stream's LIGHT scratch set, as the shared cube's build: the pass that set kept for moving lights is invalidated there)
+        bool built = false;
+        if ((rc = light_cache_ensure(own, g.cur().rt_lt, f, origins, npos, cube_bins, &built))) return rc;
+        C = &own;
+        source = built ? 1 : 2;
     }
-    if (!S.d_origins) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_origins), sizeof origins));
-    if (!S.d_flags) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_flags), 16));
-    f.light_tab = S.d_light_tab;
-    f.unsafe = S.d_flags;
-    const uint32_t flags_init[4] = { safe ? 0u : 1u, 0u, 0u, 0u };
-    HIP_TRY(upload_small(S.d_flags, flags_init, sizeof flags_init, g.stream));
-    if (npos > 0) {
-        HIP_TRY(upload_small(S.d_origins, origins, sizeof(float) * 3 * (1 + npos), g.stream));
-        // origins 1 .. npos only: the launch never touches a camera table
-        hipLaunchKernelGGL(k_prep_origin, dim3((unsigned)((g.n + 255) / 256), (unsigned)npos), dim3(256), 0, g.stream,
-                           g.d_tris, g.n, S.d_origins, V3(0.0f, 0.0f, 0.0f), 1, (OriginRow *)nullptr, S.d_light_tab, S.d_flags,
-                           (unsigned long long *)nullptr, (uint32_t *)nullptr);
-        HIP_TRY(hipGetLastError());
+    g.qstats.cube_source = source;
+    g.qstats.cube_bins = C->cube_bins;
+    g.qstats.shells = C->shells;
+    return direct_light_binned(q, *C);
+}
+
+int query_set_mode(int mode)
+{
+    int rc;
+    if ((rc = need_init())) return rc;
+    if (mode != MIRT_QUERY_AUTO && mode != MIRT_QUERY_BRUTE && mode != MIRT_QUERY_BINNED)
+        return fail(MIRT_ERR_INVALID_ARGUMENT, "unknown query mode %d", mode);
+    g.query_mode = mode;
+    return MIRT_OK;
+}
+
+int query_get_stats(mirt_query_stats *out)
+{
+    int rc;
+    if ((rc = need_init())) return rc;
+    if (!out) return fail(MIRT_ERR_INVALID_ARGUMENT, "out must not be NULL");
+    if (g.qstats_stream) HIP_TRY(hipStreamSynchronize(g.qstats_stream));
+    if (g.qstats_dev) {
+        unsigned long long c[QSTAT_WORDS] = {};
+        HIP_TRY(hipMemcpy(c, g.qstats_dev, sizeof c, hipMemcpyDeviceToHost));
+        g.qstats.shadow_rays = c[QSTAT_SHADOW_RAYS];
+        g.qstats.candidates = c[QSTAT_CANDIDATES];
+        g.qstats.tests = c[QSTAT_TESTS];
+        g.qstats.fallback_records = c[QSTAT_FALLBACK];
+        g.qstats_dev = nullptr;                  // (read once: a later query on the stream zeroes the words again)
     }
-    const size_t lds = (size_t)(g.n < RT_CHUNK_ROWS ? g.n : RT_CHUNK_ROWS) * sizeof(OriginRow);
-    hipLaunchKernelGGL(k_query_direct_light<QUERY_P>, dim3((unsigned)((nhits + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), lds, g.stream, q);
-    HIP_TRY(hipGetLastError());
+    *out = g.qstats;
     return MIRT_OK;
 }
 
@@ -216,3 +328,6 @@ int query_direct_light_host(const mirt_hit *hits, int nhits, const mirt_light *l
 }
 
 }  // namespace mirt
+
+extern "C" int mirt_set_query_mode(int mode) { return mirt::query_set_mode(mode); }
+extern "C" int mirt_get_query_stats(mirt_query_stats *out) { return mirt::query_get_stats(out); }

@@ -93,7 +93,7 @@ void RtScratch::release()
 
 void QueryScratch::release()
 {
-    for (void *p : { (void *)d_light_tab, (void *)d_origins, (void *)d_flags }) if (p) (void)hipFree(p);
+    for (void *p : { (void *)d_light_tab, (void *)d_origins, (void *)d_flags, (void *)d_stats }) if (p) (void)hipFree(p);
     *this = QueryScratch();
 }
 
@@ -101,6 +101,7 @@ void QueryRows::release()
 {
     for (void *p : { (void *)d_rows, (void *)d_max, d_rays, d_hits, d_rgb }) if (p) (void)hipFree(p);
     if (ev_built) (void)hipEventDestroy(ev_built);
+    cube.release();
     *this = QueryRows();
 }
 

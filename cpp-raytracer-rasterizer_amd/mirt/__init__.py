@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "libmirt.so")
 
 MAX_LIGHTS = 32
 RT_AUTO, RT_BRUTE, RT_BINNED = 0, 1, 2
+QUERY_AUTO, QUERY_BRUTE, QUERY_BINNED = 0, 1, 2
 KERNEL_NAMES = ("prep", "bin", "trace", "dof", "raster_setup", "raster_frag", "raster_resolve", "clear")
 
 # every symbol include/mirt.h declares (checked by tests/test_capi_symbols.py)
@@ -25,6 +26,7 @@ EXPORTS = (
     "mirt_band_of", "mirt_band_plan", "mirt_set_partition", "mirt_partition_segments", "mirt_partition_plan",
     "mirt_set_cost_histogram", "mirt_cost_histogram", "mirt_weighted_bounds", "mirt_partition_bounds", "mirt_bounds_plan", "mirt_comm_create_id", "mirt_comm_init", "mirt_comm_shutdown", "mirt_comm_selfcheck", "mirt_raytrace_sharded", "mirt_rasterise_sharded",
     "mirt_intersect", "mirt_intersect_device", "mirt_direct_light", "mirt_direct_light_device",
+    "mirt_set_query_mode", "mirt_get_query_stats",
 )
 
 
@@ -46,6 +48,12 @@ class Stats(C.Structure):
                 ("gpu_ms", C.c_float), ("kernel_ms", C.c_float * 8), ("mode_used", C.c_int32), ("candidates", C.c_uint64),
                 ("steps_primary", C.c_uint64), ("steps_shadow", C.c_uint64), ("drains", C.c_uint64),
                 ("bins_reused", C.c_uint32), ("selected_triangles", C.c_uint32)]
+
+
+class QueryStats(C.Structure):
+    """mirt_query_stats: how the last DirectLight query was answered."""
+    _fields_ = [("mode_used", C.c_int32), ("cube_source", C.c_int32), ("cube_bins", C.c_int32), ("shells", C.c_int32),
+                ("shadow_rays", C.c_uint64), ("candidates", C.c_uint64), ("tests", C.c_uint64), ("fallback_records", C.c_uint64)]
 
 
 class Ray(C.Structure):
@@ -123,6 +131,8 @@ def load():
     lib.mirt_intersect_device.argtypes = [_vp, C.c_int, _vp]
     lib.mirt_direct_light.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp]
     lib.mirt_direct_light_device.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp]
+    lib.mirt_set_query_mode.argtypes = [C.c_int]
+    lib.mirt_get_query_stats.argtypes = [C.POINTER(QueryStats)]
     _lib = lib
     return lib
 
@@ -465,6 +475,19 @@ def direct_light(hits, lights7):
 def direct_light_device(d_hits, nhits, lights7, d_rgb):
     larr, nl = make_lights(lights7)
     _check(load().mirt_direct_light_device(d_hits, int(nhits), larr, nl, d_rgb))
+
+
+def set_query_mode(mode):
+    """QUERY_AUTO / QUERY_BRUTE / QUERY_BINNED: how direct_light* walks its shadow rays (mirt_set_query_mode)."""
+    _check(load().mirt_set_query_mode(int(mode)))
+
+
+def query_stats():
+    """The last DirectLight query (mirt_get_query_stats): mode_used, cube_source (0 none, 1 built by the call, 2 kept from an
+    earlier query, 3 the frame path's), cube_bins, shells and -- with profiling on -- the binned kernel's counters."""
+    s = QueryStats()
+    _check(load().mirt_get_query_stats(C.byref(s)))
+    return {name: int(getattr(s, name)) for name, _ in QueryStats._fields_}
 
 
 # ---- several GPUs: band sharding with the gather inside the library ------------------------------------

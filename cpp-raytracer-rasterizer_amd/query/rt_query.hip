@@ -293,6 +293,23 @@ __global__ __launch_bounds__(256) void k_query_closest_wave(const QueryFrame q)
 // Filter range: the tables' rows are checked by k_prep_origin (f.unsafe, wave-uniform); rDir is a unit vector unless the
 // record's position is not finite, which the lane checks per light (|rDir| components below MIRT_QUERY_DIR_MAX, false for NaN).
 // A record whose index is outside [0, n) -- the reference would read outside `triangles` -- yields (0, 0, 0).
+// NaN colours.  A record whose position is not finite, or is the light itself, shades to NaN (:294-304: inf * 0, 0 / 0), and the
+// bits of a NaN are outside IEEE 754: the reference is an x86 program, whose invalid operations GENERATE the default NaN with the
+// sign bit set (0xffc00000) and whose operations on a NaN operand hand that operand on, quieted, sign and payload as they came;
+// what this hardware generates and what its negated operands do to a NaN's sign is its own affair.  So a NaN component is stored
+// as the reference's: the record's first NaN coordinate, quieted, when the NaN came in with the position -- every later operation
+// only hands it on --, the generated default otherwise (an infinite coordinate, a position equal to the light).  Light and triangle
+// data are finite wherever a NaN could come from nowhere else (scene_finite, the lights' range; a NaN in them takes its own course).
+__device__ __forceinline__ v3 reference_nan(v3 c, v3 pos)
+{
+    uint32_t q = 0xffc00000u;
+    if (pos.z != pos.z) q = __float_as_uint(pos.z) | 0x00400000u;
+    if (pos.y != pos.y) q = __float_as_uint(pos.y) | 0x00400000u;
+    if (pos.x != pos.x) q = __float_as_uint(pos.x) | 0x00400000u;
+    const float n = __uint_as_float(q);
+    return V3(c.x != c.x ? n : c.x, c.y != c.y ? n : c.y, c.z != c.z ? n : c.z);
+}
+
 template <int P, bool FILTER>
 __device__ __forceinline__ void direct_light_body(const QueryLightFrame &q, float4 *s_tab)
 {
@@ -373,7 +390,7 @@ __device__ __forceinline__ void direct_light_body(const QueryLightFrame &q, floa
 #pragma unroll
     for (int p = 0; p < P; p++) {
         if (!ok[p]) continue;
-        st3(q.rgb + 3 * (size_t)rec[p], valid[p] ? mul3(result2[p], tcol[p]) : V3(0.0f, 0.0f, 0.0f));   // :325-326
+        st3(q.rgb + 3 * (size_t)rec[p], valid[p] ? reference_nan(mul3(result2[p], tcol[p]), pos[p]) : V3(0.0f, 0.0f, 0.0f));   // :325-326
     }
 }
 
@@ -386,5 +403,135 @@ __global__ __launch_bounds__(256) void k_query_direct_light(const QueryLightFram
 }
 
 template __global__ void k_query_direct_light<QUERY_P>(const QueryLightFrame);
+
+// ---- k_query_direct_light_binned: DirectLight per hit record, every shadow ray through its light-cube bin ------------------
+//
+// A shadow ray of DirectLight starts at a light position whatever the record (:310), so the ray family of that position's cube
+// -- negD = rDir ~ s e_k + u e_k1 + v e_k2 over six faces (rt_binned.hpp) -- holds the shadow ray of EVERY record: a triangle the
+// reference's test accepts for rDir is on the list of rDir's bin, and of a list only the shells up to
+// the one 0.99 r falls into can hold a row whose `near` bound is below 0.99 r (bin_shell_of is monotone).  Per row: skipped when
+// its `near` is beyond 0.99 r; the filter; a certain hit (sure_hit) of a triangle no point of which is farther than 0.99 r
+// (`far`, r2.w) occludes without the divisions; anything else is decided by exact_hit, the arithmetic of k_query_direct_light.
+// Any-hit is exact (SURVEY A-5): which occluder ends a ray does not show in the result, only whether there is one.
+//
+// One lane per record.  Lists differ per lane, so nothing is staged: every lane reads its own rows from global memory, three
+// 16-byte loads a row.  Records that neighbour each other in a G-buffer fall into the same or neighbouring bins, whose lanes
+// then read the same 48 bytes in the same step -- one request to the cache -- and walk lists of similar length.  The walk is
+// k_rt_trace2's: its state lives in plain integer registers, every step is straight-line code for every lane (row 0 is loaded
+// where a lane has none left), and only the exact stage -- a few steps in a thousand -- sits in a divergent branch.
+//
+// What the bins do not cover.  The proof needs rDir to be a direction: finite, with its largest component near 1 (the margins
+// of the edge functions scale with it, dmax = 2).  rDir = normalize(L - pos) is that unless pos is not finite (a NaN or an
+// infinite component: NaN in rDir), lies so far out that |L - pos|^2 overflows (rDir = 0), or equals L up to underflow (0 / 0,
+// or infinite components).  Such a lane (`formed` false, or r * 0.99 not finite) sweeps light k's whole origin table after the
+// wave's walk, as brute_l does in k_rt_trace2 and with the loop body of k_query_direct_light, the per-ray exact-only override
+// included -- it can only be set on such a lane: a formed rDir is below 1.5 per component, far inside MIRT_QUERY_DIR_MAX.  The
+// scene's and the lights' range is the host's to check (query.cpp): outside it the call takes k_query_direct_light.
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+template <int P, bool STATS>
+__global__ __launch_bounds__(256) void k_query_direct_light_binned(const QueryBinnedFrame b)
+{
+    const QueryLightFrame &q = b.q;
+    const RtFrame &f = q.f;
+    const float4 *rows4 = reinterpret_cast<const float4 *>(b.light_rows);
+    const uint32_t face_bins = (uint32_t)(b.cube_bins * b.cube_bins) * 6u;
+    unsigned long long n_rays = 0, n_cand = 0, n_tests = 0, n_fall = 0;
+#pragma unroll 1
+    for (int p = 0; p < P; p++) {
+        const long long rec = ((long long)blockIdx.x * P + p) * 256 + threadIdx.x;
+        const bool ok = rec < q.nhits;
+        const uint32_t *h = q.hits + (size_t)HIT_WORDS * (ok ? rec : 0);
+        const v3 pos = V3(__uint_as_float(h[0]), __uint_as_float(h[1]), __uint_as_float(h[2]));
+        const int idx = (int)h[4];
+        const bool valid = ok && idx >= 0 && idx < f.n;
+        const float *t = f.tris15 + (size_t)15 * (valid ? idx : 0);
+        const v3 nDir = normalize3(ld3(t + 9));                    // glm::normalize(triangles[i.triangleIndex].normal) (:300)
+        v3 result = V3(0.0f, 0.0f, 0.0f), result2 = result;
+        bool fell = false;
+        for (int k = 0; k < f.nlights; k++) {
+            const v3 L = ld3(f.lpos[k]);
+            v3 rd;
+            float r;
+            v3 D = light_term(f, k, pos, nDir, &rd, &r);
+            const float thr = r * 0.99f;                           // j.distance < r*0.99f (:313)
+            const float ax = fabsf(rd.x), ay = fabsf(rd.y), az = fabsf(rd.z);
+            // (every comparison is false for NaN)
+            const bool formed = ax <= 1.5f && ay <= 1.5f && az <= 1.5f && fmaxf(fmaxf(ax, ay), az) >= 0.5f && thr <= FLT_MAX;
+            const bool binned = valid && formed, swept = valid && !formed;
+            uint32_t e = 0u, end = 0u;
+            if (binned) {
+                const uint32_t bin = cube_bin_of(rd, (uint32_t)k * face_bins, b.cube_bins);
+                const BinFrameDesc *lf = b.light_frames + 6 * k;
+                const uint32_t key = bin * (uint32_t)b.shells;
+                e = b.light_off[key];
+                end = b.light_off[key + bin_shell_of(thr, lf->shell_d0, lf->shell_iw, b.shells) + 1u];
+            }
+            if (STATS) { n_rays += valid ? 1u : 0u; n_cand += end - e; }
+            int occluded = 0;
+            float4 c0, c1, c2;
+            { const float4 *src = rows4 + (size_t)(e < end ? e : 0u) * 3; c0 = src[0]; c1 = src[1]; c2 = src[2]; }
+            for (;;) {
+                const int act = (int)(e < end);
+                if (!__any(act)) break;
+                if (STATS) n_tests += (unsigned)act;
+                const TestDots td = test_dots(c0, c1, c2, rd);     // negD = rDir (:310, :229)
+                // a candidate none of whose points is closer to the light than 0.99 r cannot occlude (:313)
+                const int pass = act & (int)!(c1.w > thr) & (int)maybe_hit(td);
+                const int sure = pass & (int)(c2.w < thr) & (int)sure_hit(td, c0.w);
+                int done = sure;
+                if (pass & (sure ^ 1)) {
+                    v3 hp;
+                    float dist;
+                    if (exact_hit(td, c0.w, f.tris15 + (size_t)15 * b.light_tri[e], L, &hp, &dist)) done = (int)(dist < thr);   // :313
+                }
+                occluded |= done;
+                const int cont = act & (done ^ 1) & (int)(e + 1u < end);
+                e = cont ? e + 1u : end;                           // (done, or the list's end: the lane is through)
+                const float4 *src = rows4 + (size_t)(cont ? e : 0u) * 3;
+                c0 = src[0]; c1 = src[1]; c2 = src[2];
+            }
+            if (__any(swept)) {
+                // (rare) the lanes the bins do not cover: light k's full origin table, k_query_direct_light's loop body
+                const OriginRow *tab = f.light_tab + (size_t)k * f.n;
+                const bool exact_only = !(ax < MIRT_QUERY_DIR_MAX && ay < MIRT_QUERY_DIR_MAX && az < MIRT_QUERY_DIR_MAX);
+                bool live = swept;
+                if (STATS && swept) { n_cand += (unsigned)f.n; fell = true; }
+                for (int j = 0; j < f.n; j++) {
+                    if (!__any(live)) break;
+                    const float4 r0 = tab[j].r0, r1 = tab[j].r1, r2 = tab[j].r2;
+                    const TestDots td = test_dots(r0, r1, r2, rd);
+                    if (STATS) n_tests += live ? 1u : 0u;
+                    if (live && (maybe_hit(td) || exact_only)) {
+                        v3 hp;
+                        float dist;
+                        if (exact_hit(td, r0.w, f.tris15 + (size_t)15 * j, L, &hp, &dist))
+                            if (dist < thr) live = false, occluded = 1;                    // :313-314
+                    }
+                }
+            }
+            if (occluded) D = V3(0.0f, 0.0f, 0.0f);                                        // :314
+            result = add3(result, D);                                                      // :319
+            if ((k + 1) % f.samples == 0) result2 = add3(result2, result);                 // :322
+        }
+        if (STATS) n_fall += fell ? 1u : 0u;
+        if (ok) st3(q.rgb + 3 * (size_t)rec, valid ? reference_nan(mul3(result2, ld3(t + 12)), pos) : V3(0.0f, 0.0f, 0.0f));   // :325-326
+    }
+    if (STATS) {
+        const unsigned long long sums[QSTAT_WORDS] = { wave_sum64(n_rays), wave_sum64(n_cand), wave_sum64(n_tests), wave_sum64(n_fall) };
+        if ((threadIdx.x & 63) == 0)
+#pragma unroll
+            for (int w = 0; w < QSTAT_WORDS; w++)
+                if (sums[w]) atomicAdd(b.stats + w, sums[w]);
+    }
+}
+
+template __global__ void k_query_direct_light_binned<QUERY_BIN_P, false>(const QueryBinnedFrame);
+template __global__ void k_query_direct_light_binned<QUERY_BIN_P, true>(const QueryBinnedFrame);
 
 }  // namespace mirt

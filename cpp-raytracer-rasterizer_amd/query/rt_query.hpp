@@ -4,6 +4,7 @@
 #pragma once
 
 #include "../csrc/rt_common.hpp"
+#include "../csrc/rt_binned.hpp"
 
 namespace mirt {
 
@@ -46,6 +47,20 @@ struct QueryLightFrame {
     float *rgb;                 // nhits x 3
 };
 
+// DirectLight for `nhits` records with every shadow ray walking its light-cube bin (k_query_direct_light_binned): q.f.light_tab
+// is the CUBE's origin table (k_select_faces: one row per (light position, triangle)), which the records the bins do not cover
+// sweep instead; the rest is what the trace kernel of a binned frame reads of a light cube (capi.hpp: LightCache).
+enum { QSTAT_SHADOW_RAYS = 0, QSTAT_CANDIDATES = 1, QSTAT_TESTS = 2, QSTAT_FALLBACK = 3, QSTAT_WORDS = 4 };
+struct QueryBinnedFrame {
+    QueryLightFrame q;
+    const uint32_t *light_off;          // nlights * 6 * B * B * shells + 1: first row of every (bin, shell) key
+    const LightRow *light_rows;         // the candidates' origin rows in key order, `far` in r2.w (k_expand_light_rows)
+    const uint32_t *light_tri;          // the triangle of each row
+    const BinFrameDesc *light_frames;   // 6 per light position: shell_d0 / shell_iw of the position's depth shells
+    int cube_bins, shells;
+    unsigned long long *stats;          // QSTAT_WORDS counters (the STATS instantiation only)
+};
+
 // Rays (hits) per workgroup of the lane-per-ray kernels: 256 lanes x P.
 constexpr int QUERY_P = 2;
 constexpr int QUERY_BLOCK_RAYS = 256 * QUERY_P;
@@ -54,5 +69,7 @@ __attribute__((global)) void k_query_rows(const float *, int, QueryRow *, uint32
 template <int P> __attribute__((global)) void k_query_closest(const QueryFrame);
 __attribute__((global)) void k_query_closest_wave(const QueryFrame);
 template <int P> __attribute__((global)) void k_query_direct_light(const QueryLightFrame);
+constexpr int QUERY_BIN_P = 1;                    // records per lane of the binned DirectLight kernel: lists differ per lane
+template <int P, bool STATS = false> __attribute__((global)) void k_query_direct_light_binned(const QueryBinnedFrame);
 
 }  // namespace mirt

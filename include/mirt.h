@@ -244,7 +244,8 @@ MIRT_API int mirt_raytrace_device_ex(const mirt_view *view, const mirt_light *li
 
 /* The two workhorses of the reference are free functions, and Draw() is only one of their callers: a mirror bounce, a mouse pick,
  * an occlusion probe or a second light pass calls them with rays of its own.  These entry points are those two functions, one
- * call per array element, against the uploaded scene (brute force, as ClosestIntersection is). */
+ * call per array element, against the uploaded scene (mirt_intersect* by brute force, as ClosestIntersection is; the shadow rays
+ * of mirt_direct_light* through the light-cube bins where that pays: mirt_set_query_mode). */
 typedef struct mirt_ray { float start[3]; float dir[3]; } mirt_ray;                      /* 24 bytes */
 /* struct Intersection (raytracer.cpp:91-96), same field order and size (20 bytes). */
 typedef struct mirt_hit { float position[3]; float distance; int32_t index; } mirt_hit;
@@ -264,6 +265,34 @@ MIRT_API int mirt_intersect_device(const void *d_rays, int nrays, void *d_hits);
  * index of a record are read; an index outside [0, n) -- the reference would index outside `triangles` -- yields (0, 0, 0). */
 MIRT_API int mirt_direct_light(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, float *out_rgb);
 MIRT_API int mirt_direct_light_device(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_rgb);
+
+/* How mirt_direct_light* walks its shadow rays.  A shadow ray of DirectLight starts at a light position whatever the record, so the
+ * six-face light cubes of the binned frame path hold every one of a query's shadow rays: BINNED lets each ray test only the
+ * triangles of its cube bin (bit-identical results); the cube of (scene, light positions) is built by the first call that needs it,
+ * kept for later calls and shared by the streams -- or it is the frame path's own cube, when the binned frames hold one for the
+ * same lights.  BRUTE sweeps every triangle for every shadow ray.  AUTO bins when the scene has MIRT_BIN_THRESHOLD triangles or
+ * more and records x light positions x triangles >= 4e7 (the frame path's rule), or when a cube for the call's lights is already
+ * held.  Whatever the mode, a call the frame path would not bin (a scene or light position outside the filter's proven range)
+ * takes the brute-force kernel.  Context state: mirt_shutdown puts it back to AUTO. */
+typedef enum mirt_query_mode { MIRT_QUERY_AUTO = 0, MIRT_QUERY_BRUTE = 1, MIRT_QUERY_BINNED = 2 } mirt_query_mode;
+MIRT_API int mirt_set_query_mode(int mode);
+/* The last mirt_direct_light* call (mirt_get_stats stays with the last render call).  cube_source: 0 no cube (brute force), 1 built
+ * by this call, 2 kept from an earlier query, 3 the frame path's.  The four counters are filled for a binned call made with
+ * mirt_set_profiling(1) and zero otherwise: shadow rays (records inside the scene x light positions), candidate rows offered to
+ * them, tests executed, and records for which a light position swept its whole table because the cube's ray family does not
+ * cover their shadow ray (a position that is not finite, equals the light or lies beyond float range of it). */
+typedef struct mirt_query_stats {
+    int32_t mode_used;                /* MIRT_QUERY_BRUTE or MIRT_QUERY_BINNED                   */
+    int32_t cube_source;
+    int32_t cube_bins;                /* bins per face side, 0 without a cube                     */
+    int32_t shells;                   /* depth shells per bin                                     */
+    uint64_t shadow_rays;
+    uint64_t candidates;
+    uint64_t tests;
+    uint64_t fallback_records;
+} mirt_query_stats;
+/* Waits for the stream of the last DirectLight query. */
+MIRT_API int mirt_get_query_stats(mirt_query_stats *out);
 
 /* ---- rasteriser: replaces Update()'s clear + Draw() + CalculateDOF() of rasteriser.cpp:183-192,461-529 */
 

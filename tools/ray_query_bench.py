@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep]
+"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight]
 
-The three measurements of the ray-query kernels (query/rt_query.hip), written to one text file:
+The measurements of the ray-query kernels (query/rt_query.hip), written to one text file:
 
   issue + throughput   the lane-per-ray kernel over the 2 073 600 primary rays of soup100k at 1080p (generated on the host, through
                        mirt_intersect_device) beside one BRUTE frame of the same view in the same process (k_rt_brute).  The EXPECTED
@@ -10,6 +10,11 @@ The three measurements of the ray-query kernels (query/rt_query.hip), written to
   sweep                time against the number of rays, 1 .. 2^20 in powers of two, at n = 100 000 and n = 2 000, with
                        MIRT_QUERY_WAVE_RAYS = 0 (lane per ray) and huge (wave per ray): where the curves cross is the knob's default.
   occupancy            tools/check_spills.py's lines for the query kernels: VGPRs, scratch, waves per SIMD.
+  directlight          mirt_direct_light_device over the closest-hit records of soup100k's primary rays at 1080p (mirt_intersect_device
+                       of the view's rays) and the default light: MIRT_QUERY_BRUTE, MIRT_QUERY_BINNED with the cube built by the call
+                       (the light moves by one ulp between the calls) and with the cube kept; every run's colours hashed and
+                       compared.  Then the record count swept in powers of two at n = 100 000 and n = 2 000: the smallest call from
+                       which binned-with-build stays ahead of brute force is where MIRT_QUERY_AUTO should switch.
 
 The knob is read once per process, so every GPU step is a child process of its own, under its own `timeout`; a step that fails
 ends the run."""
@@ -191,6 +196,135 @@ def child_sweep(n):
     mirt.shutdown()
 
 
+def closest_records(mirt, h, n, s):
+    """soup(1, n, s) uploaded, and the closest-hit records of the view's primary rays on the device: (d_hits, count)."""
+    mirt.scene_upload(mirt.scene_soup(1, n, s))
+    rays = primary_rays(mirt, mirt.rot_from_yaw(0.0, 1.0))
+    fresh = mirt.fresh_hits(len(rays))
+    d_rays, d_hits = dev_alloc(h, rays.nbytes, rays), dev_alloc(h, fresh.nbytes, fresh)
+    mirt.intersect_device(d_rays, len(rays), d_hits); mirt.sync()
+    h.hipFree(d_rays)
+    return d_hits, len(rays)
+
+
+def nudged(light, i):
+    """The default light, its x moved by i ulps: another cube key, the same work."""
+    l = np.array(light, np.float32).copy()
+    for _ in range(i):
+        l[0, 0] = np.nextafter(l[0, 0], np.float32(1))
+    return l
+
+
+def child_directlight(mode):
+    import hashlib
+    import mirt
+    h = hip()
+    mirt.init(0)
+    d_hits, count = closest_records(mirt, h, 100000, 0.05)
+    d_rgb = dev_alloc(h, count * 12)
+    rgb = np.zeros((count, 3), np.float32)
+
+    def digest():
+        assert h.hipMemcpy(rgb.ctypes.data_as(C.c_void_p), d_rgb, rgb.nbytes, 2) == 0
+        return hashlib.sha1(rgb.tobytes()).hexdigest()[:16]
+    mirt.set_query_mode(mirt.QUERY_BRUTE if mode == "brute" else mirt.QUERY_BINNED)
+    if mode == "brute":
+        ms = timed(mirt, lambda: mirt.direct_light_device(d_hits, count, mirt.DEFAULT_LIGHT, d_rgb), 2)
+        assert mirt.query_stats()["mode_used"] == mirt.QUERY_BRUTE
+        print("RESULT records %d triangles 100000 lights 1" % count)
+        print("RESULT BRUTE  (k_prep_origin + k_query_direct_light<2>): %.3f ms  digest %s" % (ms, digest()))
+    else:
+        built = []
+        for i in range(1, 6):                    # a cube of its own per call
+            l = nudged(mirt.DEFAULT_LIGHT, i)
+            t0 = time.perf_counter()
+            mirt.direct_light_device(d_hits, count, l, d_rgb); mirt.sync()
+            built.append((time.perf_counter() - t0) * 1e3)
+            assert mirt.query_stats()["cube_source"] == 1
+        mirt.direct_light_device(d_hits, count, mirt.DEFAULT_LIGHT, d_rgb); mirt.sync()
+        kept = timed(mirt, lambda: mirt.direct_light_device(d_hits, count, mirt.DEFAULT_LIGHT, d_rgb), 9)
+        st = mirt.query_stats()
+        assert st["mode_used"] == mirt.QUERY_BINNED and st["cube_source"] == 2
+        dg = digest()
+        mirt.set_profiling(True)
+        mirt.direct_light_device(d_hits, count, mirt.DEFAULT_LIGHT, d_rgb)
+        st = mirt.query_stats()
+        mirt.set_profiling(False)
+        print("RESULT BINNED, cube built by the call (median of %d, first %.3f ms): %.3f ms" % (len(built), built[0], float(np.median(built[1:]))))
+        print("RESULT BINNED, cube kept: %.3f ms  digest %s" % (kept, dg))
+        print("RESULT cube %d bins per side, %d shells; shadow rays %d, rows offered %d (%.1f per ray, of 100000), tests %d, fallback records %d"
+              % (st["cube_bins"], st["shells"], st["shadow_rays"], st["candidates"], st["candidates"] / max(st["shadow_rays"], 1), st["tests"], st["fallback_records"]))
+    mirt.shutdown()
+
+
+def child_dlsweep(mode, n):
+    import mirt
+    h = hip()
+    mirt.init(0)
+    d_hits, count = closest_records(mirt, h, n, 0.05 if n >= 50000 else 0.2)
+    # records in pixel order would make a small call one corner of the frame: a fixed shuffle instead, so that every call samples the frame
+    rec = np.zeros(count, mirt.HIT_DTYPE)
+    assert h.hipMemcpy(rec.ctypes.data_as(C.c_void_p), d_hits, rec.nbytes, 2) == 0
+    rec = np.ascontiguousarray(rec[np.random.default_rng(5).permutation(count)])
+    assert h.hipMemcpy(d_hits, rec.ctypes.data_as(C.c_void_p), rec.nbytes, 1) == 0
+    d_rgb = dev_alloc(h, count * 12)
+    mirt.set_query_mode(mirt.QUERY_BRUTE if mode == "brute" else mirt.QUERY_BINNED)
+    k, nudge = 1, 0
+    while k <= count:
+        reps = 5 if k <= 65536 else 3
+        if mode == "built":
+            ts = []
+            for _ in range(reps + 1):
+                nudge += 1
+                l = nudged(mirt.DEFAULT_LIGHT, 1 + nudge % 7)            # (never the key of the call before: the one cube held is another's)
+                t0 = time.perf_counter()
+                mirt.direct_light_device(d_hits, k, l, d_rgb); mirt.sync()
+                ts.append((time.perf_counter() - t0) * 1e3)
+                assert mirt.query_stats()["cube_source"] == 1
+            ms = float(np.median(ts[1:]))
+        else:
+            ms = timed(mirt, lambda: mirt.direct_light_device(d_hits, k, mirt.DEFAULT_LIGHT, d_rgb), reps)
+        print("RESULT dl n %6d mode %-6s records %8d  %9.4f ms" % (n, mode, k, ms))
+        sys.stdout.flush()
+        k *= 2
+    mirt.shutdown()
+
+
+def step_directlight(p):
+    p("== directlight: mirt_direct_light_device over the closest hits of soup100k's primary rays at 1080p, one light (host clock around call + mirt_sync) ==")
+    outs = [run_child(p, ["--child", "directlight", m], {}, 300) for m in ("brute", "binned")]
+    b = re.search(r"BRUTE .*?: ([0-9.]+) ms  digest (\w+)", outs[0])
+    bb = re.search(r"cube built by the call .*?: ([0-9.]+) ms\n", outs[1])
+    bk = re.search(r"cube kept: ([0-9.]+) ms  digest (\w+)", outs[1])
+    if b and bb and bk:
+        p("colours bit-identical (sha1 of all %s): %s" % ("records", "yes" if b.group(2) == bk.group(2) else "NO: %s vs %s" % (b.group(2), bk.group(2))))
+        p("ratio brute / binned with the build = %.1f; brute / binned with the cube kept = %.1f" % (float(b.group(1)) / float(bb.group(1)), float(b.group(1)) / float(bk.group(1))))
+        if b.group(2) != bk.group(2):
+            sys.exit(1)
+    p("")
+    p("== directlight sweep: ms per call against the record count (records of the frame in a fixed shuffled order) ==")
+    table = {}
+    for n in (100000, 2000):
+        for mode in ("brute", "built", "kept"):
+            out = run_child(lambda s: None, ["--child", "dlsweep", mode, str(n)], {}, 420)
+            for m in re.finditer(r"RESULT dl n\s+(\d+) mode (\S+)\s+records\s+(\d+)\s+([0-9.]+) ms", out):
+                table[(int(m.group(1)), m.group(2), int(m.group(3)))] = float(m.group(4))
+    for n in (100000, 2000):
+        p("n = %d triangles, 1 light" % n)
+        p("%10s %14s %14s %14s   records x lights x n" % ("records", "brute", "binned+build", "binned kept"))
+        k, cross = 1, None
+        while (n, "brute", k) in table:
+            a, b2, c = table[(n, "brute", k)], table[(n, "built", k)], table[(n, "kept", k)]
+            p("%10d %11.4f ms %11.4f ms %11.4f ms   %.1e%s" % (k, a, b2, c, float(k) * n, "   binned+build ahead" if b2 < a else ""))
+            if b2 >= a:
+                cross = None
+            elif cross is None:
+                cross = k
+            k *= 2
+        p("binned with the build stays ahead from %s records on: records x lights x n = %s" % (cross, "%.1e" % (float(cross) * n) if cross else "never"))
+        p("")
+
+
 def run_child(p, args, env, limit):
     cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__)] + args
     r = subprocess.run(cmd, env=dict(os.environ, **env), capture_output=True, text=True)
@@ -238,11 +372,15 @@ def step_sweep(p):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ray_query_bench.txt"))
-    ap.add_argument("--steps", default="issue,occupancy,throughput,sweep")
+    ap.add_argument("--steps", default="issue,occupancy,throughput,sweep,directlight")
     ap.add_argument("--append", action="store_true")
     ap.add_argument("--child", nargs="+")
     a = ap.parse_args()
     if a.child:
+        if a.child[0] == "directlight":
+            return child_directlight(a.child[1])
+        if a.child[0] == "dlsweep":
+            return child_dlsweep(a.child[1], int(a.child[2]))
         return child_throughput() if a.child[0] == "throughput" else child_sweep(int(a.child[1]))
     lines = []
 
@@ -259,6 +397,8 @@ def main():
             step_throughput(p, expected)
         if "sweep" in steps:
             step_sweep(p)
+        if "directlight" in steps:
+            step_directlight(p)
     finally:
         with open(a.out, "a" if a.append else "w") as f:
             f.write("\n".join(lines) + "\n")
