@@ -208,6 +208,7 @@ struct QueryScratch {
     uint32_t *d_flags = nullptr;                 // [0] = unsafe flag
     uint64_t rows_seen = 0;                      // the QueryRows::version this stream is already ordered behind (0 = none)
     unsigned long long *d_stats = nullptr;       // QSTAT_WORDS counters of the stream's last binned DirectLight query (profiling on)
+    unsigned long long *d_fan_stats = nullptr;   // ... and of its last binned origin fan (mirt_intersect_from*)
 
     void release();
 };
@@ -221,15 +222,19 @@ struct QueryRows {
     uint64_t version = 0;                        // scene_version the rows were built for (0 = none)
     hipEvent_t ev_built = nullptr;
     // staging of the host-buffer entry points (mirt_intersect, mirt_direct_light)
-    void *d_rays = nullptr, *d_hits = nullptr, *d_rgb = nullptr;
-    size_t cap = 0;                              // rays / records each holds
+    void *d_rays = nullptr, *d_hits = nullptr, *d_rgb = nullptr, *d_dirs = nullptr;
+    size_t cap = 0;                              // rays / records / directions each holds
     // The light cube of the DirectLight queries: a LightCache like the frame path's g.lc, keyed alike (scene version + the light
     // positions in use, and the grid -- so a new scene forgets it), kept across calls, shared by the streams and ordered among
     // them by light_cache_ensure's events.  A query whose lights are the ones the frame path's valid cube holds reads g.lc and
     // leaves this one as it is; no query ever writes g.lc or what the frame path tracks in it.
     LightCache cube;
+    // The cube of the origin fans (mirt_intersect_from*): the same structure around the fan's origin, a one-position list -- keyed by
+    // scene version and origin (light_key_of), built by light_cache_ensure under the same protocol.  Apart from `cube`, so that a
+    // probe does not evict DirectLight's lights nor a DirectLight query the probe's origin.
+    LightCache fan;
 
-    void release();                              // (the cube's tables too)
+    void release();                              // (the cubes' tables too)
 };
 
 // Everything a frame in flight owns: its stream and the scratch its kernels write.  A frame reads the scene and writes the
@@ -299,6 +304,9 @@ struct Ctx {
     mirt_query_stats qstats = {};                // the last DirectLight query: how it was answered (mirt_get_query_stats) ...
     hipStream_t qstats_stream = nullptr;         // ... the stream it ran on ...
     const unsigned long long *qstats_dev = nullptr;   // ... and where its kernel's counters are (device; profiling on, binned)
+    mirt_query_stats fstats = {};                // the same three for the last origin fan (mirt_get_fan_stats)
+    hipStream_t fstats_stream = nullptr;
+    const unsigned long long *fstats_dev = nullptr;
     unsigned long long *d_hits = nullptr;        // the hit-counter buffer of the current ray-traced frame (one of its stream's d_hits)
     bool scene_finite = true;                    // all vertex coordinates below MIRT_SAFE_MAG
     uint64_t scene_version = 0;                  // bumped whenever the triangles change
@@ -408,6 +416,8 @@ int query_intersect(const void *d_rays, int nrays, void *d_hits);
 int query_intersect_host(const mirt_ray *rays, int nrays, mirt_hit *hits);
 int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_rgb);
 int query_direct_light_host(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, float *out_rgb);
+int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, void *d_hits);
+int query_intersect_from_host(const float *origin, const float *dirs3, int nrays, mirt_hit *hits);
 
 // ---- rasteriser (raster.cpp) ----
 int raster_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect,

@@ -3,6 +3,7 @@
 // version and shared by the streams, and so is the light cube whose bins the shadow rays of DirectLight walk (per scene version
 // and light positions); a query takes the next stream as a frame does (mirt_set_frames_in_flight, mirt_sync) but leaves the
 // statistics of the last render call alone (DirectLight has its own: mirt_set_query_mode, mirt_get_query_stats, defined here).
+// Many rays from ONE origin (mirt_intersect_from*) walk a cube of the same kind around that origin, kept apart from DirectLight's.
 #include "capi.hpp"
 
 namespace mirt {
@@ -115,12 +116,11 @@ static bool auto_bins(int nhits, int npos)
     return g.n >= auto_threshold && (long long)nhits * npos * g.n >= 40000000LL;
 }
 
-// The brute-force kernel over origin tables of the query's own: k_prep_origin into the stream's frame tables would overwrite the
-// camera rows a kept binning pass counts on (rt_frame.cpp: rt_dispatch_brute).
-static int direct_light_brute(QueryLightFrame &q, const float *origins, int npos, bool safe)
+// Origin tables of the query's own for origins[3 ..] (npos positions) on the current stream, and their `unsafe` flag: k_prep_origin
+// into the stream's frame tables would overwrite the camera rows a kept binning pass counts on (rt_frame.cpp: rt_dispatch_brute).
+static int query_origin_tables(const float *origins, int npos, bool safe)
 {
     int rc;
-    RtFrame &f = q.f;
     QueryScratch &S = g.cur().query;
     if (npos > S.tab_lights || S.tab_n != g.n) {
         S.tab_lights = 0;
@@ -130,8 +130,6 @@ static int direct_light_brute(QueryLightFrame &q, const float *origins, int npos
     }
     if (!S.d_origins) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_origins), sizeof(float) * 3 * (1 + MIRT_MAX_LIGHTS)));
     if (!S.d_flags) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_flags), 16));
-    f.light_tab = S.d_light_tab;
-    f.unsafe = S.d_flags;
     const uint32_t flags_init[4] = { safe ? 0u : 1u, 0u, 0u, 0u };
     HIP_TRY(upload_small(S.d_flags, flags_init, sizeof flags_init, g.stream));
     if (npos > 0) {
@@ -142,6 +140,16 @@ static int direct_light_brute(QueryLightFrame &q, const float *origins, int npos
                            (unsigned long long *)nullptr, (uint32_t *)nullptr);
         HIP_TRY(hipGetLastError());
     }
+    return MIRT_OK;
+}
+
+// The brute-force kernel over those tables.
+static int direct_light_brute(QueryLightFrame &q, const float *origins, int npos, bool safe)
+{
+    int rc;
+    if ((rc = query_origin_tables(origins, npos, safe))) return rc;
+    q.f.light_tab = g.cur().query.d_light_tab;
+    q.f.unsafe = g.cur().query.d_flags;
     const size_t lds = (size_t)(g.n < RT_CHUNK_ROWS ? g.n : RT_CHUNK_ROWS) * sizeof(OriginRow);
     hipLaunchKernelGGL(k_query_direct_light<QUERY_P>, dim3((unsigned)((q.nhits + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), lds, g.stream, q);
     HIP_TRY(hipGetLastError());
@@ -249,6 +257,121 @@ int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, 
     return direct_light_binned(q, *C);
 }
 
+// ---- origin fans: ClosestIntersection for many directions from one origin (mirt_intersect_from*) -----------------------------
+
+// AUTO for a fan.  Measured (tools/ray_query_bench.py --steps fan, profiles/ray_query_bench.txt; soup scenes, the rays of a 1080p
+// frame in shuffled order, 1 .. 2^20 rays): at n = 2 000 and at n = 100 000 the binned call WITH its cube's build (0.13 / 0.26 ms at
+// few rays) is ahead of the sweep (0.34 / 16 ms: one lane walks the whole table) from a single ray on, so from FAN_AUTO_TRIANGLES
+// triangles on AUTO bins whatever the ray count.  Below that the sweep was not measured -- its table is short, the build's fixed
+// cost is not -- and the frame path's rule stays, with rays x triangles in the place of pixels x triangles: a scene of
+// MIRT_BIN_THRESHOLD triangles or more and rays x triangles >= 4e7, UNMEASURED for this use.
+constexpr int FAN_AUTO_TRIANGLES = 2000;
+static bool auto_bins_fan(int nrays)
+{
+    static const int auto_threshold = (int)env_int("MIRT_BIN_THRESHOLD", 65);
+    return g.n >= auto_threshold && (g.n >= FAN_AUTO_TRIANGLES || (long long)nrays * g.n >= 40000000LL);
+}
+
+int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, void *d_hits)
+{
+    int rc;
+    if ((rc = check_query_args(d_dirs3, nrays, d_hits, "direction"))) return rc;
+    if (nrays == 0) return MIRT_OK;
+    if (!origin) return fail(MIRT_ERR_INVALID_ARGUMENT, "origin must not be NULL when the count is > 0");
+    if ((rc = need_scene())) return rc;
+
+    QueryFanFrame q;
+    memset(&q, 0, sizeof q);
+    q.tris15 = g.d_tris;
+    q.n = g.n;
+    memcpy(q.origin, origin, 12);
+    q.dirs = static_cast<const float *>(d_dirs3);
+    q.nrays = nrays;
+    q.hits = static_cast<uint32_t *>(d_hits);
+    float origins[6] = {};
+    memcpy(origins + 3, origin, 12);
+    bool safe = g.scene_finite;
+    for (int c = 0; c < 3; c++)
+        if (!(fabsf(origin[c]) < MIRT_QUERY_START_MAX)) safe = false;       // the rays' start (rt_frame.cpp: operands_safe)
+
+    // Binned or brute, as a DirectLight query decides it: never what the frame path would not bin, whatever the mode.
+    bool fixed_grid = false;
+    const int cube_bins = light_cube_bins_for(1, &fixed_grid);
+    const bool may_bin = safe && light_keys_fit(1, cube_bins);
+    LightCache &C = g.qrows.fan;
+    const bool held = may_bin && C.valid && C.key == light_key_of(origins, 1) && C.cube_bins == cube_bins;
+    const bool binned = may_bin && g.query_mode != MIRT_QUERY_BRUTE && (g.query_mode == MIRT_QUERY_BINNED || held || auto_bins_fan(nrays));
+
+    stream_begin();
+    QueryScratch &S = g.cur().query;
+    memset(&g.fstats, 0, sizeof g.fstats);
+    g.fstats.mode_used = binned ? MIRT_QUERY_BINNED : MIRT_QUERY_BRUTE;
+    g.fstats_stream = g.stream;
+    g.fstats_dev = nullptr;
+    if (!binned) {
+        if ((rc = query_origin_tables(origins, 1, safe))) return rc;
+        q.tab = S.d_light_tab;
+        q.unsafe = S.d_flags;
+        const size_t lds = (size_t)(g.n < RT_CHUNK_ROWS ? g.n : RT_CHUNK_ROWS) * sizeof(OriginRow);
+        hipLaunchKernelGGL(k_query_fan<QUERY_P>, dim3((unsigned)((nrays + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), lds, g.stream, q);
+        HIP_TRY(hipGetLastError());
+        return MIRT_OK;
+    }
+
+    // (the cube's build reads of the frame only the scene and the position; in the stream's LIGHT scratch set, as the shared cube's)
+    RtFrame f;
+    memset(&f, 0, sizeof f);
+    f.tris15 = g.d_tris;
+    f.n = g.n;
+    f.nlights = 1;
+    f.samples = 1;
+    memcpy(f.lpos[0], origin, 12);
+    bool built = false;
+    if ((rc = light_cache_ensure(C, g.cur().rt_lt, f, origins, 1, cube_bins, &built))) return rc;
+    g.fstats.cube_source = built ? 1 : 2;
+    g.fstats.cube_bins = C.cube_bins;
+    g.fstats.shells = C.shells;
+    q.tab = C.d_light_tab;
+    q.light_off = C.d_off;
+    // (a cube without a single pair has no row table: the idle loads are pointed at the origin table, which always has a row)
+    q.light_rows = C.nrows ? C.d_rows : C.d_light_tab;
+    q.light_tri = C.d_row_tri;
+    q.light_frames = C.d_frames;
+    q.cube_bins = C.cube_bins;
+    q.shells = C.shells;
+    const dim3 grid((unsigned)((nrays + 255) / 256));
+    if (g.profiling) {
+        if (!S.d_fan_stats) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_fan_stats), sizeof(unsigned long long) * QSTAT_WORDS));
+        HIP_TRY(hipMemsetAsync(S.d_fan_stats, 0, sizeof(unsigned long long) * QSTAT_WORDS, g.stream));
+        q.stats = S.d_fan_stats;
+        g.fstats_dev = S.d_fan_stats;
+        hipLaunchKernelGGL(k_query_fan_binned<true>, grid, dim3(256), 0, g.stream, q);
+    } else {
+        hipLaunchKernelGGL(k_query_fan_binned<false>, grid, dim3(256), 0, g.stream, q);
+    }
+    HIP_TRY(hipGetLastError());
+    return MIRT_OK;
+}
+
+int query_get_fan_stats(mirt_query_stats *out)
+{
+    int rc;
+    if ((rc = need_init())) return rc;
+    if (!out) return fail(MIRT_ERR_INVALID_ARGUMENT, "out must not be NULL");
+    if (g.fstats_stream) HIP_TRY(hipStreamSynchronize(g.fstats_stream));
+    if (g.fstats_dev) {
+        unsigned long long c[QSTAT_WORDS] = {};
+        HIP_TRY(hipMemcpy(c, g.fstats_dev, sizeof c, hipMemcpyDeviceToHost));
+        g.fstats.shadow_rays = c[QSTAT_SHADOW_RAYS];
+        g.fstats.candidates = c[QSTAT_CANDIDATES];
+        g.fstats.tests = c[QSTAT_TESTS];
+        g.fstats.fallback_records = c[QSTAT_FALLBACK];
+        g.fstats_dev = nullptr;                  // (read once: a later fan on the stream zeroes the words again)
+    }
+    *out = g.fstats;
+    return MIRT_OK;
+}
+
 int query_set_mode(int mode)
 {
     int rc;
@@ -289,6 +412,7 @@ static int query_staging(size_t count)
     if ((rc = dev_realloc_bytes(&Q.d_rays, count * sizeof(mirt_ray)))) return rc;
     if ((rc = dev_realloc_bytes(&Q.d_hits, count * sizeof(mirt_hit)))) return rc;
     if ((rc = dev_realloc_bytes(&Q.d_rgb, count * 3 * sizeof(float)))) return rc;
+    if ((rc = dev_realloc_bytes(&Q.d_dirs, count * 3 * sizeof(float)))) return rc;
     Q.cap = count;
     return MIRT_OK;
 }
@@ -327,7 +451,28 @@ int query_direct_light_host(const mirt_hit *hits, int nhits, const mirt_light *l
     return MIRT_OK;
 }
 
+int query_intersect_from_host(const float *origin, const float *dirs3, int nrays, mirt_hit *hits)
+{
+    int rc;
+    if ((rc = check_query_args(dirs3, nrays, hits, "direction"))) return rc;
+    if (nrays == 0) return MIRT_OK;
+    if (!origin) return fail(MIRT_ERR_INVALID_ARGUMENT, "origin must not be NULL when the count is > 0");
+    if ((rc = need_scene())) return rc;
+    if ((rc = query_staging((size_t)nrays))) return rc;
+    QueryRows &Q = g.qrows;
+    hipStream_t st = g.streams[next_si()].stream;            // the stream the query below will take
+    HIP_TRY(hipMemcpyAsync(Q.d_dirs, dirs3, (size_t)nrays * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(Q.d_hits, hits, (size_t)nrays * sizeof(mirt_hit), hipMemcpyHostToDevice, st));
+    if ((rc = query_intersect_from(origin, Q.d_dirs, nrays, Q.d_hits))) return rc;
+    HIP_TRY(hipMemcpyAsync(hits, Q.d_hits, (size_t)nrays * sizeof(mirt_hit), hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return MIRT_OK;
+}
+
 }  // namespace mirt
 
+extern "C" int mirt_intersect_from(const float origin[3], const float *dirs3, int nrays, mirt_hit *hits) { return mirt::query_intersect_from_host(origin, dirs3, nrays, hits); }
+extern "C" int mirt_intersect_from_device(const float origin[3], const void *d_dirs3, int nrays, void *d_hits) { return mirt::query_intersect_from(origin, d_dirs3, nrays, d_hits); }
+extern "C" int mirt_get_fan_stats(mirt_query_stats *out) { return mirt::query_get_fan_stats(out); }
 extern "C" int mirt_set_query_mode(int mode) { return mirt::query_set_mode(mode); }
 extern "C" int mirt_get_query_stats(mirt_query_stats *out) { return mirt::query_get_stats(out); }

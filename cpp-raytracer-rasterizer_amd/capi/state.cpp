@@ -93,15 +93,16 @@ void RtScratch::release()
 
 void QueryScratch::release()
 {
-    for (void *p : { (void *)d_light_tab, (void *)d_origins, (void *)d_flags, (void *)d_stats }) if (p) (void)hipFree(p);
+    for (void *p : { (void *)d_light_tab, (void *)d_origins, (void *)d_flags, (void *)d_stats, (void *)d_fan_stats }) if (p) (void)hipFree(p);
     *this = QueryScratch();
 }
 
 void QueryRows::release()
 {
-    for (void *p : { (void *)d_rows, (void *)d_max, d_rays, d_hits, d_rgb }) if (p) (void)hipFree(p);
+    for (void *p : { (void *)d_rows, (void *)d_max, d_rays, d_hits, d_rgb, d_dirs }) if (p) (void)hipFree(p);
     if (ev_built) (void)hipEventDestroy(ev_built);
     cube.release();
+    fan.release();
     *this = QueryRows();
 }
 

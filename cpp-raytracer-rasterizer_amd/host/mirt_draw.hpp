@@ -150,6 +150,15 @@ struct RayTracer {
         for (int k = 0; k < n; k++) { std::memcpy(rays[k].start, &start[k].x, 12); std::memcpy(rays[k].dir, &dir[k].x, 12); }
         check(mirt_intersect(rays.data(), n, reinterpret_cast<mirt_hit *>(closest)), "mirt_intersect");
     }
+    // The same for n rays that share their start -- a probe's cube map, a fan from the eye or from a light: closest[k] comes back as
+    // ClosestIntersection(start, dir[k], triangles, closest[k]) leaves it, each ray walking its bin of a cube around `start` where
+    // that pays (mirt_intersect_from, mirt_set_query_mode).
+    void ClosestIntersection(vec3 start, const vec3 *dir, Intersection *closest, int n)
+    {
+        upload_scene();
+        static_assert(sizeof(vec3) == 12, "directions travel as they are");
+        check(mirt_intersect_from(&start.x, n > 0 ? &dir[0].x : nullptr, n, reinterpret_cast<mirt_hit *>(closest)), "mirt_intersect_from");
+    }
     // DirectLight(i) (:265-327) for n records, with the lights and the soft-shadow toggle as they stand: result[k] = DirectLight(i[k]).
     void DirectLight(const Intersection *i, vec3 *result, int n)
     {

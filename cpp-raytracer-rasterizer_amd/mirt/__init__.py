@@ -27,6 +27,7 @@ EXPORTS = (
     "mirt_set_cost_histogram", "mirt_cost_histogram", "mirt_weighted_bounds", "mirt_partition_bounds", "mirt_bounds_plan", "mirt_comm_create_id", "mirt_comm_init", "mirt_comm_shutdown", "mirt_comm_selfcheck", "mirt_raytrace_sharded", "mirt_rasterise_sharded",
     "mirt_intersect", "mirt_intersect_device", "mirt_direct_light", "mirt_direct_light_device",
     "mirt_set_query_mode", "mirt_get_query_stats",
+    "mirt_intersect_from", "mirt_intersect_from_device", "mirt_get_fan_stats",
 )
 
 
@@ -133,6 +134,9 @@ def load():
     lib.mirt_direct_light_device.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp]
     lib.mirt_set_query_mode.argtypes = [C.c_int]
     lib.mirt_get_query_stats.argtypes = [C.POINTER(QueryStats)]
+    lib.mirt_intersect_from.argtypes = [_vp, _vp, C.c_int, _vp]
+    lib.mirt_intersect_from_device.argtypes = [_vp, _vp, C.c_int, _vp]
+    lib.mirt_get_fan_stats.argtypes = [C.POINTER(QueryStats)]
     _lib = lib
     return lib
 
@@ -487,6 +491,34 @@ def query_stats():
     earlier query, 3 the frame path's), cube_bins, shells and -- with profiling on -- the binned kernel's counters."""
     s = QueryStats()
     _check(load().mirt_get_query_stats(C.byref(s)))
+    return {name: int(getattr(s, name)) for name, _ in QueryStats._fields_}
+
+
+def intersect_from(origin, dirs, hits=None):
+    """ClosestIntersection(origin, dirs[i]) for every direction (mirt_intersect_from): what intersect() returns for the rays
+    {origin, dirs[i]}, bit for bit, each ray walking its bin of a cube around the origin where that pays (set_query_mode).
+    dirs: (n, 3) floats, used as given; hits: the in/out records (HIT_DTYPE; fresh ones when None).  Returns a new array."""
+    origin = np.ascontiguousarray(origin, np.float32).reshape(3)
+    dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    hits = fresh_hits(len(dirs)) if hits is None else np.ascontiguousarray(hits, HIT_DTYPE).copy()
+    if len(hits) != len(dirs):
+        raise ValueError("%d directions but %d hit records" % (len(dirs), len(hits)))
+    _check(load().mirt_intersect_from(_ptr(origin), _ptr(dirs), len(dirs), _ptr(hits)))
+    return hits
+
+
+def intersect_from_device(origin, d_dirs, nrays, d_hits):
+    """The same on device arrays (raw pointers; the origin is host data), queued like a *_device frame; mirt.sync() completes it."""
+    origin = np.ascontiguousarray(origin, np.float32).reshape(3)
+    _check(load().mirt_intersect_from_device(_ptr(origin), d_dirs, int(nrays), d_hits))
+
+
+def fan_stats():
+    """The last intersect_from* call (mirt_get_fan_stats), in mirt_query_stats' fields: mode_used, cube_source (0 none, 1 built by
+    the call, 2 kept), cube_bins, shells and -- profiling on, binned -- shadow_rays = rays, candidates = rows stepped over, tests =
+    rows tested, fallback_records = rays that swept the whole table."""
+    s = QueryStats()
+    _check(load().mirt_get_fan_stats(C.byref(s)))
     return {name: int(getattr(s, name)) for name, _ in QueryStats._fields_}
 
 

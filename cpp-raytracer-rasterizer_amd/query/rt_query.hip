@@ -534,4 +534,181 @@ __global__ __launch_bounds__(256) void k_query_direct_light_binned(const QueryBi
 template __global__ void k_query_direct_light_binned<QUERY_BIN_P, false>(const QueryBinnedFrame);
 template __global__ void k_query_direct_light_binned<QUERY_BIN_P, true>(const QueryBinnedFrame);
 
+// ---- k_query_fan: ClosestIntersection for many directions from one origin, every ray tests every triangle ------------------
+//
+// Rays of one origin share the per-origin hoist of the frame kernels (rt_common.hpp: OriginRow, 15 operations a test against the
+// 41 of k_query_closest); the table is the query's own (k_prep_origin with first origin 1) or the cube's.  One lane per P rays,
+// rows staged through LDS in chunks of RT_CHUNK_ROWS and read as wave-uniform broadcasts, the sweep written from the header
+// primitives like k_query_direct_light's.  The record rule is k_query_closest's, sequentially in index order from the incoming
+// record: `if (record.distance >= distance)` (:243).  The rows are inside the filter's range unless *unsafe says otherwise
+// (k_prep_origin, or the host for a scene or origin beyond 1e8: every test through the exact divisions then); a ray with a
+// |dir| component not below MIRT_QUERY_DIR_MAX -- NaN included -- has its verdicts overridden per ray.
+template <int P, bool FILTER>
+__device__ __forceinline__ void fan_body(const QueryFanFrame &q, float4 *s_tab)
+{
+    const v3 S = ld3(q.origin);
+    long long ray[P];
+    bool ok[P], exact_only[P], replaced[P];
+    RayDirs<P> rd;
+    v3 pos[P];
+    float best_d[P];
+    int best_i[P];
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+        ray[p] = ((long long)blockIdx.x * P + p) * 256 + threadIdx.x;
+        ok[p] = ray[p] < q.nrays;
+        const v3 dir = ld3(q.dirs + 3 * (size_t)(ok[p] ? ray[p] : 0));
+        rd.set(p, neg3(dir));                                      // negD = -dir (:229); dir is used as given
+        exact_only[p] = !(fabsf(dir.x) < MIRT_QUERY_DIR_MAX && fabsf(dir.y) < MIRT_QUERY_DIR_MAX && fabsf(dir.z) < MIRT_QUERY_DIR_MAX);
+        // a lane without a ray carries a record nothing can replace
+        best_d[p] = ok[p] ? __uint_as_float(q.hits[(size_t)HIT_WORDS * ray[p] + 3]) : -1.0f;
+        best_i[p] = -1;
+        pos[p] = V3(0.0f, 0.0f, 0.0f);
+        replaced[p] = false;
+    }
+    for (int base = 0; base < q.n; base += RT_CHUNK_ROWS) {
+        const int cnt = min(RT_CHUNK_ROWS, q.n - base);
+        __syncthreads();
+        {
+            const float4 *src = reinterpret_cast<const float4 *>(q.tab + base);
+            for (int j = threadIdx.x; j < cnt * 3; j += 256) s_tab[j] = src[j];
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (int j = 0; j < cnt; j++) {
+            const float4 r0 = s_tab[3 * j], r1 = s_tab[3 * j + 1], r2 = s_tab[3 * j + 2];
+            TestDots d[P];
+            bool maybe[P];
+            test_rays<P, FILTER>(r0, r1, r2, rd, d, maybe);
+#pragma unroll
+            for (int p = 0; p < P; p++) {
+                if (maybe[p] || exact_only[p]) {
+                    v3 hp;
+                    float dist;
+                    if (exact_hit(d[p], r0.w, q.tris15 + (size_t)15 * (base + j), S, &hp, &dist))
+                        if (best_d[p] >= dist) { best_d[p] = dist; best_i[p] = base + j; pos[p] = hp; replaced[p] = true; }   // :243-247
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+        if (!ok[p] || !replaced[p]) continue;
+        uint32_t *h = q.hits + (size_t)HIT_WORDS * ray[p];
+        h[0] = __float_as_uint(pos[p].x); h[1] = __float_as_uint(pos[p].y); h[2] = __float_as_uint(pos[p].z);
+        h[3] = __float_as_uint(best_d[p]);
+        h[4] = (uint32_t)best_i[p];
+    }
+}
+
+template <int P>
+__global__ __launch_bounds__(256) void k_query_fan(const QueryFanFrame q)
+{
+    extern __shared__ __attribute__((aligned(16))) float4 s_tab[];
+    if (__builtin_amdgcn_readfirstlane(*q.unsafe) == 0u) fan_body<P, true>(q, s_tab);
+    else fan_body<P, false>(q, s_tab);
+}
+
+template __global__ void k_query_fan<QUERY_P>(const QueryFanFrame);
+
+// ---- k_query_fan_binned: the same, every ray through its bin of the cube around the origin ------------------------------------
+//
+// The cube of a point (capi.hpp: LightCache, built by light_cache_ensure for a one-position list) holds every direction from it:
+// a triangle the reference accepts for negD is on the list of the bin of d' = negD * 2^k (rt_query.hpp: fan_dir_of; DESIGN.md
+// section 5.1).  A bin's list is ordered front to back in depth shells of the rows' `near` bound, and `near` bounds the distance
+// the reference computes whatever the direction's length -- pos = v0 + u e1 + v e2 lies on the triangle --, so of a list only the
+// shells up to the one the ray's current record distance (`bound`) falls into can hold a row with near <= bound (bin_shell_of is
+// monotone), and every other row fails `bound >= d`.  The list ends there, and the end moves in with every replacement.
+//
+// Record rule.  The reference's loop moves the record only to distances <= the incoming one, ties to the later index, so its
+// result is (smallest accepted d with incoming >= d, largest index among equals), or the incoming record when there is none:
+// order-independent, which a walk in shell order needs.  Kept as running (bound, best_i): an accepted d replaces them when
+// bound > d, or bound == d and its index is larger -- best_i = -1 stands for the incoming record, which so loses every tie.  A
+// row is skipped only when near > bound, strictly: a row with d == bound has near <= bound and is tested.  An incoming distance
+// that is negative or NaN is replaced by nothing (`>=` is false): the lane takes no list at all.
+//
+// One lane per ray, no LDS; the walk is k_query_direct_light_binned's: state in plain integer registers, every step straight-line
+// code (a lane with no row left loads row 0 and ignores it), verdicts as integers combined with `&`, only the exact stage in a
+// divergent branch.  Lanes the bins do not cover (fan_dir_of: not formed) sweep the origin's full table after the wave's walk,
+// with k_query_fan's loop body and per-ray override.
+template <bool STATS>
+__global__ __launch_bounds__(256) void k_query_fan_binned(const QueryFanFrame q)
+{
+    const float4 *rows4 = reinterpret_cast<const float4 *>(q.light_rows);
+    const long long ray = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool ok = ray < q.nrays;
+    const v3 S = ld3(q.origin);
+    const v3 dir = ld3(q.dirs + 3 * (size_t)(ok ? ray : 0));
+    const v3 nd = neg3(dir);                                       // negD = -dir (:229); dir is used as given
+    uint32_t *h = q.hits + (size_t)HIT_WORDS * (ok ? ray : 0);
+    float bound = __uint_as_float(h[3]);
+    const bool open = ok && bound >= 0.0f;                         // (false for NaN)
+    const FanDir fd = fan_dir_of(nd);
+    const bool binned = open && fd.formed, swept = open && !fd.formed;
+    const float d0 = q.light_frames[0].shell_d0, iw = q.light_frames[0].shell_iw;
+    uint32_t e = 0u, end = 0u, key = 0u;
+    if (binned) {
+        key = cube_bin_of(fd.d, 0u, q.cube_bins) * (uint32_t)q.shells;
+        e = q.light_off[key];
+        end = q.light_off[key + bin_shell_of(bound, d0, iw, q.shells) + 1u];
+    }
+    unsigned long long n_cand = 0, n_tests = 0;
+    int best_i = -1, replaced = 0;
+    v3 pos = V3(0.0f, 0.0f, 0.0f);
+    float4 c0, c1, c2;
+    { const float4 *src = rows4 + (size_t)(e < end ? e : 0u) * 3; c0 = src[0]; c1 = src[1]; c2 = src[2]; }
+    for (;;) {
+        const int act = (int)(e < end);
+        if (!__any(act)) break;
+        const TestDots td = test_dots(c0, c1, c2, nd);
+        const int near_ok = act & (int)!(c1.w > bound);            // strictly beyond the record: cannot pass `bound >= d`
+        if (STATS) { n_cand += (unsigned)act; n_tests += (unsigned)near_ok; }
+        if (near_ok & (int)maybe_hit(td)) {
+            const int tri = (int)q.light_tri[e];
+            v3 hp;
+            float dist;
+            if (exact_hit(td, c0.w, q.tris15 + (size_t)15 * tri, S, &hp, &dist)) {
+                if ((bound > dist) | ((bound == dist) & (tri > best_i))) {
+                    bound = dist; best_i = tri; pos = hp; replaced = 1;
+                    end = min(end, q.light_off[key + bin_shell_of(dist, d0, iw, q.shells) + 1u]);
+                }
+            }
+        }
+        const int cont = act & (int)(e + 1u < end);
+        e = cont ? e + 1u : end;                                   // (the list's end, old or new: the lane is through)
+        const float4 *src = rows4 + (size_t)(cont ? e : 0u) * 3;
+        c0 = src[0]; c1 = src[1]; c2 = src[2];
+    }
+    if (__any(swept)) {
+        // (rare) the lanes the bins do not cover: the origin's full table in index order, the sequential rule itself
+        const bool exact_only = !(fabsf(dir.x) < MIRT_QUERY_DIR_MAX && fabsf(dir.y) < MIRT_QUERY_DIR_MAX && fabsf(dir.z) < MIRT_QUERY_DIR_MAX);
+        if (STATS && swept) { n_cand += (unsigned)q.n; n_tests += (unsigned)q.n; }
+        for (int j = 0; j < q.n; j++) {
+            const float4 r0 = q.tab[j].r0, r1 = q.tab[j].r1, r2 = q.tab[j].r2;
+            const TestDots td = test_dots(r0, r1, r2, nd);
+            if (swept && (maybe_hit(td) || exact_only)) {
+                v3 hp;
+                float dist;
+                if (exact_hit(td, r0.w, q.tris15 + (size_t)15 * j, S, &hp, &dist))
+                    if (bound >= dist) { bound = dist; best_i = j; pos = hp; replaced = 1; }        // :243-247
+            }
+        }
+    }
+    if (ok && replaced) {
+        h[0] = __float_as_uint(pos.x); h[1] = __float_as_uint(pos.y); h[2] = __float_as_uint(pos.z);
+        h[3] = __float_as_uint(bound);
+        h[4] = (uint32_t)best_i;
+    }
+    if (STATS) {
+        const unsigned long long sums[QSTAT_WORDS] = { wave_sum64(ok ? 1u : 0u), wave_sum64(n_cand), wave_sum64(n_tests), wave_sum64(swept ? 1u : 0u) };
+        if ((threadIdx.x & 63) == 0)
+#pragma unroll
+            for (int w = 0; w < QSTAT_WORDS; w++)
+                if (sums[w]) atomicAdd(q.stats + w, sums[w]);
+    }
+}
+
+template __global__ void k_query_fan_binned<false>(const QueryFanFrame);
+template __global__ void k_query_fan_binned<true>(const QueryFanFrame);
+
 }  // namespace mirt

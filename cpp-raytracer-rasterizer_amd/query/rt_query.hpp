@@ -6,6 +6,8 @@
 #include "../csrc/rt_common.hpp"
 #include "../csrc/rt_binned.hpp"
 
+#include <string.h>
+
 namespace mirt {
 
 // What ClosestIntersection computes per triangle before it looks at the ray (:216-217, :225): 12 floats,
@@ -61,6 +63,76 @@ struct QueryBinnedFrame {
     unsigned long long *stats;          // QSTAT_WORDS counters (the STATS instantiation only)
 };
 
+// ---- origin fans: ClosestIntersection for many directions from ONE origin (mirt_intersect_from*) ---------------------------
+//
+// The cube around the origin is a ray family of directions whose largest component is 1 (rt_binned.hpp: negD ~ s e_k + u e_k1 +
+// v e_k2, dmax = 2); a caller's direction has any length.  fan_dir_of scales negD by a power of two so that its largest component
+// lies in [0.5, 1): d' = negD * 2^k.  The bin is chosen from d'; every test runs on negD itself.
+//
+// Why the bin of d' holds every triangle the reference accepts for negD (DESIGN.md section 5.1 has the full argument).  The row
+// operands of the three dots are below 2^57 (scene_finite and the origin below 1e8: 8e16), so with the largest |negD| component in
+// [2^(FAN_EXP_MIN - 1), 2^FAN_EXP_MAX) no product or sum overflows (below 2^78), and multiplying by 2^k commutes with every rounding
+// whose result is normal: the dots of negD are 2^-k times the dots of d', bit for bit, and the quotients t, u, v -- hence the
+// verdict -- are the same.  Subnormal results: a sum of two floats that lands in the subnormal range is exact; a product that
+// does is off by at most 2^-150 of its own scale, so the dots of negD, scaled by 2^k, are the dots of d' up to the ordinary
+// rounding of a dot product plus at most 3 * 2^-150 * (1 + 2^k) <= 2^-116 -- both inside the margin the edge functions of
+// section 3.2 carry (2^-17 M dmax + 2^-20).  The absolute thresholds of the accept test in units of d': u >= 0 lets a < 0 pass
+// only when |a| / D underflows, |a'| < 2^-150 D' < 2^-91, likewise v and t: tighter than the 2^-22 the margins were sized for.
+// The upper end keeps negD inside the filter's own range (MIRT_QUERY_DIR_MAX = 1e6 > 2^19), so maybe_hit needs no override on
+// a lane that takes a bin.  Outside the window -- zero, NaN, infinite, tiny or huge -- a ray takes no bin and sweeps the table.
+constexpr int FAN_EXP_MIN = -31;                  // largest |component| = f * 2^e with f in [0.5, 1): e in [FAN_EXP_MIN, FAN_EXP_MAX],
+constexpr int FAN_EXP_MAX = 19;                   // i.e. 2^-32 <= largest |component| < 2^19
+
+struct FanDir { int formed; v3 d; };
+MIRT_HD uint32_t fan_bits(float x)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return __float_as_uint(x);
+#else
+    uint32_t u; memcpy(&u, &x, 4); return u;
+#endif
+}
+// formed: every component finite and the largest inside the window; d = nd * 2^k then, each component the correctly rounded
+// product (exact unless a component more than 2^107 below the largest drops into the subnormal range under k < 0: that moves
+// (u, v) of the bin by less than 2^-125, the bins' pad is 2^-18).  Signs and zero components are kept.  Not formed: d = nd.
+// (The largest component is found on the integer bits: a NaN or infinity orders above every finite value and has exponent
+// field 255, outside the window like zero and the subnormals with field 0.)
+MIRT_HD FanDir fan_dir_of(v3 nd)
+{
+    const uint32_t bx = fan_bits(nd.x) & 0x7fffffffu, by = fan_bits(nd.y) & 0x7fffffffu, bz = fan_bits(nd.z) & 0x7fffffffu;
+    const uint32_t bm = bx > by ? (bx > bz ? bx : bz) : (by > bz ? by : bz);
+    const int E = (int)(bm >> 23);                // largest |component| in [2^(E - 127), 2^(E - 126)): e = E - 126
+    FanDir r;
+    r.formed = (int)(E >= FAN_EXP_MIN + 126) & (int)(E <= FAN_EXP_MAX + 126);
+    const uint32_t sb = (uint32_t)(253 - (r.formed ? E : 126)) << 23;          // 2^(126 - E) = 2^k; 1.0 when not formed
+#ifdef __HIP_DEVICE_COMPILE__
+    const float s = __uint_as_float(sb);
+#else
+    float s; memcpy(&s, &sb, 4);
+#endif
+    r.d = r.formed ? V3(nd.x * s, nd.y * s, nd.z * s) : nd;
+    return r;
+}
+
+// One origin, nrays directions, the in/out records.  tab: the origin's table, one row per triangle (the cube's own, written by
+// k_select_faces, or the query's, written by k_prep_origin); the cube fields are read by k_query_fan_binned only.
+struct QueryFanFrame {
+    const float *tris15;
+    int n;
+    const OriginRow *tab;
+    const uint32_t *unsafe;             // k_query_fan: != 0 runs every test through the exact path
+    float origin[3];
+    const float *dirs;                  // nrays x 3, used as given
+    int nrays;
+    uint32_t *hits;                     // nrays x HIT_WORDS, in/out
+    const uint32_t *light_off;          // 6 * B * B * shells + 1
+    const LightRow *light_rows;
+    const uint32_t *light_tri;
+    const BinFrameDesc *light_frames;   // 6: shell_d0 / shell_iw of the origin's depth shells
+    int cube_bins, shells;
+    unsigned long long *stats;          // QSTAT_WORDS counters (the STATS instantiation only): rays, rows offered, rows tested, rays that swept
+};
+
 // Rays (hits) per workgroup of the lane-per-ray kernels: 256 lanes x P.
 constexpr int QUERY_P = 2;
 constexpr int QUERY_BLOCK_RAYS = 256 * QUERY_P;
@@ -71,5 +143,7 @@ __attribute__((global)) void k_query_closest_wave(const QueryFrame);
 template <int P> __attribute__((global)) void k_query_direct_light(const QueryLightFrame);
 constexpr int QUERY_BIN_P = 1;                    // records per lane of the binned DirectLight kernel: lists differ per lane
 template <int P, bool STATS = false> __attribute__((global)) void k_query_direct_light_binned(const QueryBinnedFrame);
+template <int P> __attribute__((global)) void k_query_fan(const QueryFanFrame);
+template <bool STATS> __attribute__((global)) void k_query_fan_binned(const QueryFanFrame);
 
 }  // namespace mirt

@@ -245,7 +245,8 @@ MIRT_API int mirt_raytrace_device_ex(const mirt_view *view, const mirt_light *li
 /* The two workhorses of the reference are free functions, and Draw() is only one of their callers: a mirror bounce, a mouse pick,
  * an occlusion probe or a second light pass calls them with rays of its own.  These entry points are those two functions, one
  * call per array element, against the uploaded scene (mirt_intersect* by brute force, as ClosestIntersection is; the shadow rays
- * of mirt_direct_light* through the light-cube bins where that pays: mirt_set_query_mode). */
+ * of mirt_direct_light* through the light-cube bins where that pays: mirt_set_query_mode; rays that share their origin through a
+ * cube around it: mirt_intersect_from*, below). */
 typedef struct mirt_ray { float start[3]; float dir[3]; } mirt_ray;                      /* 24 bytes */
 /* struct Intersection (raytracer.cpp:91-96), same field order and size (20 bytes). */
 typedef struct mirt_hit { float position[3]; float distance; int32_t index; } mirt_hit;
@@ -293,6 +294,33 @@ typedef struct mirt_query_stats {
 } mirt_query_stats;
 /* Waits for the stream of the last DirectLight query. */
 MIRT_API int mirt_get_query_stats(mirt_query_stats *out);
+
+/* ---- origin fans: ClosestIntersection for many directions from ONE origin ---- */
+
+/* ClosestIntersection(origin, dirs[i], triangles, hits[i]) for i in [0, nrays): exactly mirt_intersect with
+ * rays[i] = { origin, dirs[i] }, bit for bit, for every ray and every incoming record.  A cube-map or environment probe, an
+ * omnidirectional camera, a point light's shadow map, a visibility fan from a probe point, a pick from the eye: rays that share their
+ * origin share the frame path's per-origin tables, and a six-face cube around the origin holds every direction, so each ray tests
+ * only the triangles of its cube bin, nearest depth shells first, and stops where nothing closer than its record can follow.
+ * dirs3: nrays x 3 floats, used as given and not normalised.  hits: the in/out records of mirt_intersect, with its rules (ties
+ * to the later index, an incoming record loses every tie, a negative or NaN incoming distance is never replaced, +inf by any hit,
+ * a ray that accepts nothing closer leaves all 20 bytes unwritten).  nrays == 0 does nothing.  The _device form is queued like
+ * mirt_intersect_device (the streams in turn, mirt_sync() completes it); neither form touches mirt_get_stats or
+ * mirt_get_query_stats.  mirt_set_query_mode governs these calls too: BRUTE sweeps the origin's table for every ray and never builds
+ * a cube; BINNED builds the cube of (scene, origin) when it is not held -- one cube is kept, apart from DirectLight's --; AUTO bins
+ * when the scene has 2000 triangles or more (measured: with its build the binned call is ahead of the sweep from one ray on at
+ * 2000 and at 100 000 triangles), when it has MIRT_BIN_THRESHOLD triangles or more and rays x triangles >= 4e7 (the frame path's
+ * figure, not measured for this use), or when the cube of this origin is already held.  A call the frame path would not bin (a scene or origin
+ * coordinate beyond 1e8) sweeps under every mode; so does, per ray, a direction that is zero, not finite, or whose largest
+ * component lies outside [2^-32, 2^19). */
+MIRT_API int mirt_intersect_from(const float origin[3], const float *dirs3, int nrays, mirt_hit *hits);
+MIRT_API int mirt_intersect_from_device(const float origin[3], const void *d_dirs3, int nrays, void *d_hits);
+/* The last mirt_intersect_from* call; mirt_get_query_stats stays with the last DirectLight query, mirt_get_stats with the last
+ * frame.  The struct's field names are DirectLight's: here cube_source is 0 none, 1 built by this call, 2 kept from an earlier
+ * call; with profiling on and a binned call, shadow_rays = rays of the call, candidates = rows a ray stepped over before its
+ * list's (moving) end, tests = those of them not beyond the ray's record, fallback_records = rays that swept the whole table.
+ * Waits for the stream of that call. */
+MIRT_API int mirt_get_fan_stats(mirt_query_stats *out);
 
 /* ---- rasteriser: replaces Update()'s clear + Draw() + CalculateDOF() of rasteriser.cpp:183-192,461-529 */
 

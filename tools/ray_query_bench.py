@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight]
+"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan]
 
 The measurements of the ray-query kernels (query/rt_query.hip), written to one text file:
 
@@ -15,6 +15,12 @@ The measurements of the ray-query kernels (query/rt_query.hip), written to one t
                        (the light moves by one ulp between the calls) and with the cube kept; every run's colours hashed and
                        compared.  Then the record count swept in powers of two at n = 100 000 and n = 2 000: the smallest call from
                        which binned-with-build stays ahead of brute force is where MIRT_QUERY_AUTO should switch.
+  fan                  the primary rays of soup100k at 1080p as a fan from the camera: mirt_intersect_device on {camera, dir} rays (the
+                       yardstick), mirt_intersect_from_device under MIRT_QUERY_BRUTE, under MIRT_QUERY_BINNED with the cube built by
+                       the call (the origin moves by one ulp between the calls) and with the cube kept; all records of every run
+                       hashed and compared.  Then the ray count swept in powers of two at n = 100 000 and n = 2 000 (rays of the
+                       frame in a fixed shuffled order): the smallest call from which binned-with-build stays ahead of the fan's own
+                       sweep is where MIRT_QUERY_AUTO should switch for fans (it starts from the frame path's 4e7, unmeasured).
 
 The knob is read once per process, so every GPU step is a child process of its own, under its own `timeout`; a step that fails
 ends the run."""
@@ -325,6 +331,154 @@ def step_directlight(p):
         p("")
 
 
+def nudged_origin(i):
+    """The camera position, its x moved by i ulps: another cube key, the same work."""
+    o = np.array(CAM, np.float32)
+    for _ in range(i):
+        o[0] = np.nextafter(o[0], np.float32(1))
+    return o
+
+
+def fan_inputs(mirt, h, n, s, shuffle):
+    """soup(1, n, s) uploaded; the view's primary rays as rays and as bare directions on the device, and fresh records on the host."""
+    mirt.scene_upload(mirt.scene_soup(1, n, s))
+    rays = primary_rays(mirt, mirt.rot_from_yaw(0.0, 1.0))
+    if shuffle:                              # rays in pixel order would make a small call one corner of the frame
+        rays = np.ascontiguousarray(rays[np.random.default_rng(5).permutation(len(rays))])
+    dirs = np.ascontiguousarray(rays["dir"])
+    fresh = mirt.fresh_hits(len(rays))
+    return dev_alloc(h, rays.nbytes, rays), dev_alloc(h, dirs.nbytes, dirs), dev_alloc(h, fresh.nbytes, fresh), fresh
+
+
+def child_fan(mode):
+    import hashlib
+    import mirt
+    h = hip()
+    mirt.init(0)
+    d_rays, d_dirs, d_hits, fresh = fan_inputs(mirt, h, 100000, 0.05, False)
+    count = len(fresh)
+    got = np.zeros(count, mirt.HIT_DTYPE)
+    cam = np.array(CAM, np.float32)
+
+    def reset():
+        assert h.hipMemcpy(d_hits, fresh.ctypes.data_as(C.c_void_p), fresh.nbytes, 1) == 0
+
+    def run(fn):
+        reset()
+        t0 = time.perf_counter()
+        fn(); mirt.sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    def digest():
+        assert h.hipMemcpy(got.ctypes.data_as(C.c_void_p), d_hits, got.nbytes, 2) == 0
+        return hashlib.sha1(got.tobytes()).hexdigest()[:16], float((got["index"] >= 0).mean())
+    if mode == "query":
+        f = lambda: mirt.intersect_device(d_rays, count, d_hits)
+        run(f)
+        ms = float(np.median([run(f) for _ in range(3)]))
+        print("RESULT rays %d triangles 100000, one origin" % count)
+        print("RESULT mirt_intersect_device (k_query_closest<2>, the yardstick): %.3f ms  digest %s  hit share %.3f" % ((ms,) + digest()))
+    elif mode == "brute":
+        mirt.set_query_mode(mirt.QUERY_BRUTE)
+        f = lambda: mirt.intersect_from_device(cam, d_dirs, count, d_hits)
+        run(f)
+        ms = float(np.median([run(f) for _ in range(3)]))
+        assert mirt.fan_stats()["mode_used"] == mirt.QUERY_BRUTE
+        print("RESULT fan BRUTE  (k_prep_origin + k_query_fan<2>): %.3f ms  digest %s" % ((ms,) + digest()[:1]))
+    else:
+        mirt.set_query_mode(mirt.QUERY_BINNED)
+        built = []
+        for i in range(1, 6):                    # a cube of its own per call
+            o = nudged_origin(i)
+            built.append(run(lambda: mirt.intersect_from_device(o, d_dirs, count, d_hits)))
+            assert mirt.fan_stats()["cube_source"] == 1
+        f = lambda: mirt.intersect_from_device(cam, d_dirs, count, d_hits)
+        run(f)
+        kept = float(np.median([run(f) for _ in range(9)]))
+        st = mirt.fan_stats()
+        assert st["mode_used"] == mirt.QUERY_BINNED and st["cube_source"] == 2
+        dg = digest()[0]
+        mirt.set_profiling(True)
+        run(f)
+        st = mirt.fan_stats()
+        mirt.set_profiling(False)
+        print("RESULT fan BINNED, cube built by the call (median of %d, first %.3f ms): %.3f ms" % (len(built) - 1, built[0], float(np.median(built[1:]))))
+        print("RESULT fan BINNED, cube kept: %.3f ms  digest %s" % (kept, dg))
+        print("RESULT cube %d bins per side, %d shells; rays %d, rows stepped over %d (%.2f per ray, of 100000), rows tested %d, rays that swept %d"
+              % (st["cube_bins"], st["shells"], st["shadow_rays"], st["candidates"], st["candidates"] / max(st["shadow_rays"], 1), st["tests"], st["fallback_records"]))
+    mirt.shutdown()
+
+
+def child_fansweep(mode, n):
+    import mirt
+    h = hip()
+    mirt.init(0)
+    d_rays, d_dirs, d_hits, fresh = fan_inputs(mirt, h, n, 0.05 if n >= 50000 else 0.2, True)
+    count = len(fresh)
+    cam = np.array(CAM, np.float32)
+    mirt.set_query_mode(mirt.QUERY_BINNED if mode in ("built", "kept") else mirt.QUERY_BRUTE)
+    k, nudge = 1, 0
+    while k <= count:
+        reps = 5 if k <= 65536 else 3
+        ts = []
+        for _ in range(reps + 1):
+            assert h.hipMemcpy(d_hits, fresh.ctypes.data_as(C.c_void_p), 20 * k, 1) == 0
+            nudge += 1
+            o = nudged_origin(1 + nudge % 7) if mode == "built" else cam      # (never the key of the call before: the one cube held is another's)
+            t0 = time.perf_counter()
+            if mode == "query":
+                mirt.intersect_device(d_rays, k, d_hits)
+            else:
+                mirt.intersect_from_device(o, d_dirs, k, d_hits)
+            mirt.sync()
+            ts.append((time.perf_counter() - t0) * 1e3)
+            if mode == "built":
+                assert mirt.fan_stats()["cube_source"] == 1
+        print("RESULT fan n %6d mode %-6s rays %8d  %9.4f ms" % (n, mode, k, float(np.median(ts[1:]))))
+        sys.stdout.flush()
+        k *= 2
+    mirt.shutdown()
+
+
+def step_fan(p):
+    p("== fan: the 2 073 600 primary rays of soup100k at 1080p as a fan from the camera (host clock around call + mirt_sync) ==")
+    outs = [run_child(p, ["--child", "fan", m], {}, 300) for m in ("query", "brute", "binned")]
+    q = re.search(r"yardstick\): ([0-9.]+) ms  digest (\w+)", outs[0])
+    b = re.search(r"fan BRUTE .*?: ([0-9.]+) ms  digest (\w+)", outs[1])
+    bb = re.search(r"cube built by the call .*?: ([0-9.]+) ms\n", outs[2])
+    bk = re.search(r"cube kept: ([0-9.]+) ms  digest (\w+)", outs[2])
+    if q and b and bb and bk:
+        same = q.group(2) == b.group(2) == bk.group(2)
+        p("records bit-identical (sha1 of all records): %s" % ("yes" if same else "NO: %s / %s / %s" % (q.group(2), b.group(2), bk.group(2))))
+        p("mirt_intersect_device / fan: brute %.1f, binned with the build %.1f, binned with the cube kept %.1f"
+          % (float(q.group(1)) / float(b.group(1)), float(q.group(1)) / float(bb.group(1)), float(q.group(1)) / float(bk.group(1))))
+        if not same:
+            sys.exit(1)
+    p("")
+    p("== fan sweep: ms per call against the ray count (rays of the frame in a fixed shuffled order) ==")
+    table = {}
+    modes = ("query", "brute", "built", "kept")
+    for n in (100000, 2000):
+        for mode in modes:
+            out = run_child(lambda s: None, ["--child", "fansweep", mode, str(n)], {}, 420)
+            for m in re.finditer(r"RESULT fan n\s+(\d+) mode (\S+)\s+rays\s+(\d+)\s+([0-9.]+) ms", out):
+                table[(int(m.group(1)), m.group(2), int(m.group(3)))] = float(m.group(4))
+    for n in (100000, 2000):
+        p("n = %d triangles" % n)
+        p("%10s %16s %14s %14s %14s   rays x n" % ("rays", "mirt_intersect", "fan brute", "binned+build", "binned kept"))
+        k, cross = 1, None
+        while (n, "brute", k) in table:
+            q2, a, b2, c = (table[(n, m, k)] for m in modes)
+            p("%10d %13.4f ms %11.4f ms %11.4f ms %11.4f ms   %.1e%s" % (k, q2, a, b2, c, float(k) * n, "   binned+build ahead" if b2 < a else ""))
+            if b2 >= a:
+                cross = None
+            elif cross is None:
+                cross = k
+            k *= 2
+        p("binned with the build stays ahead of the fan's sweep from %s rays on: rays x n = %s" % (cross, "%.1e" % (float(cross) * n) if cross else "never"))
+        p("")
+
+
 def run_child(p, args, env, limit):
     cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__)] + args
     r = subprocess.run(cmd, env=dict(os.environ, **env), capture_output=True, text=True)
@@ -381,6 +535,10 @@ def main():
             return child_directlight(a.child[1])
         if a.child[0] == "dlsweep":
             return child_dlsweep(a.child[1], int(a.child[2]))
+        if a.child[0] == "fan":
+            return child_fan(a.child[1])
+        if a.child[0] == "fansweep":
+            return child_fansweep(a.child[1], int(a.child[2]))
         return child_throughput() if a.child[0] == "throughput" else child_sweep(int(a.child[1]))
     lines = []
 
@@ -399,6 +557,8 @@ def main():
             step_sweep(p)
         if "directlight" in steps:
             step_directlight(p)
+        if "fan" in steps:
+            step_fan(p)
     finally:
         with open(a.out, "a" if a.append else "w") as f:
             f.write("\n".join(lines) + "\n")
