@@ -1,6 +1,6 @@
 // capi.hpp -- the host side of the C-ABI (csrc/mirt_capi.hip and the files of this directory): the library's state, one
 // StreamState per frame in flight inside one Ctx, and the helpers the topic files share.  Host code only: the frame kernels are
-// defined under csrc/ and the ray-query kernels under query/ (tools/check_spills.py compiles both directories); the ones
+// defined under csrc/, the ray-query kernels under query/ and the scene kernels under scene/ (tools/check_spills.py compiles all three); the ones
 // launched from here are declared below and in query/rt_query.hpp.
 #pragma once
 
@@ -297,6 +297,9 @@ struct Ctx {
     uint64_t cull_calls = 0;
     GeoRow *d_geo = nullptr;                     // n geometry rows (built by mirt_scene_upload)
     ShadeRow *d_shade = nullptr;                 // n shading rows (likewise)
+    uint32_t *d_scene_bounds = nullptr;          // the SceneBounds words the scene kernels leave (scene.cpp)
+    float *d_scene_stage = nullptr;              // staging of mirt_scene_update's host rows (scene_stage_cap floats)
+    size_t scene_stage_cap = 0;
     float bbox_lo[3] = { 0, 0, 0 }, bbox_hi[3] = { 0, 0, 0 };   // the scene's bounding box (host side, mirt_scene_upload)
     LightCache lc;
     QueryRows qrows;
@@ -410,6 +413,18 @@ int binned_trace(const RtFrame &f, RtScratch &S, RtScratch &L, const BinnedPass 
 bool rt_bins_whole_frame(const mirt_view *view, const mirt_light *lights, int nlights, int mode);
 // The cost histogram of a view's whole frame and nothing else, on the current stream (render_sharded).
 int hist_only_pass(const mirt_view *view);
+
+// ---- device-resident scenes (scene.cpp; the kernels: ../scene/scene_kernels.hip) ----
+// What every call that changes the triangles does to the host's state last: the streams' kept passes, tables and pair counts and the
+// cost histograms are forgotten, the shared light cube is dropped, the cull flags get a new number when they changed, and
+// scene_version -- which keys every other cache: the query rows, the query cubes, the rasteriser's frame key -- moves on.
+void scene_commit(bool flags_changed);
+int scene_upload_device(const void *d_tris15, const void *d_culled, int n);
+int scene_update_device(int first, int count, const void *d_tris15);
+int scene_update_host(int first, int count, const float *tris15);
+int scene_transform(int first, int count, const float *rot9, const float *translate3);
+int scene_download(int first, int count, float *tris15);
+int scene_info(struct mirt_scene_info *out);
 
 // ---- ray queries (query.cpp) ----
 int query_intersect(const void *d_rays, int nrays, void *d_hits);

@@ -147,7 +147,7 @@ extern "C" void mirt_shutdown(void)
     for (StreamState &ss : g.streams) ss.release();
     g.lc.release();
     g.qrows.release();
-    for (void *p : { (void *)g.d_tris, (void *)g.d_culled, (void *)g.d_geo, (void *)g.d_shade, g.d_xrgb, g.d_rgb, g.d_index, g.d_zinv, g.d_pos,
+    for (void *p : { (void *)g.d_tris, (void *)g.d_culled, (void *)g.d_geo, (void *)g.d_shade, (void *)g.d_scene_bounds, (void *)g.d_scene_stage, g.d_xrgb, g.d_rgb, g.d_index, g.d_zinv, g.d_pos,
                      (void *)g.d_band[0], (void *)g.d_band[1] })
         if (p) (void)hipFree(p);
     for (Ctx::HostSurface &r : g.surf) if (r.host) (void)hipHostUnregister(r.host);
@@ -255,17 +255,10 @@ extern "C" int mirt_scene_upload(const float *tris15, const uint8_t *culled, int
     g.n = 0;
     if ((rc = dev_realloc(&g.d_tris, (size_t)n * 15))) return rc;
     if ((rc = dev_realloc(&g.d_culled, (size_t)MAX_FLIGHT * n))) return rc;
-    for (StreamState &ss : g.streams) {
-        ss.rt.forget_scene();
-        ss.rt_lt.forget_scene();
-        for (uint64_t &k : ss.rt.hist_key) k = 0;                   // ... and so do the cost histograms
-    }
     HIP_TRY(hipMemcpy(g.d_tris, tris15, (size_t)n * 15 * sizeof(float), hipMemcpyHostToDevice));
-    g.cull_calls++;
     for (int h = 0; h < MAX_FLIGHT; h++) {
         if (culled) HIP_TRY(hipMemcpy(g.d_culled + (size_t)h * n, culled, (size_t)n, hipMemcpyHostToDevice));
         else HIP_TRY(hipMemset(g.d_culled + (size_t)h * n, 0, (size_t)n));
-        g.streams[h].culled_ver = g.cull_calls;
     }
     if ((rc = dev_realloc(&g.d_geo, (size_t)n))) return rc;
     if ((rc = dev_realloc(&g.d_shade, (size_t)n))) return rc;
@@ -275,7 +268,6 @@ extern "C" int mirt_scene_upload(const float *tris15, const uint8_t *culled, int
     hipLaunchKernelGGL(k_geo_table, dim3((n + 255) / 256), dim3(256), 0, g.stream, g.d_tris, n, g.d_geo, g.d_shade);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g.stream));
-    g.lc.valid = false;
     g.scene_finite = true;
     for (size_t i = 0; i < (size_t)n * 15 && g.scene_finite; i++)
         if (!(fabsf(tris15[i]) < 1.0e8f)) g.scene_finite = false;   // generous: |coord| < 1e8 keeps cross products < 1e18
@@ -286,9 +278,21 @@ extern "C" int mirt_scene_upload(const float *tris15, const uint8_t *culled, int
             g.bbox_lo[v % 3] = fminf(g.bbox_lo[v % 3], x); g.bbox_hi[v % 3] = fmaxf(g.bbox_hi[v % 3], x);
         }
     g.n = n;
-    g.scene_version++;
+    scene_commit(true);                          // (capi/scene.cpp: shared with the device forms)
     return MIRT_OK;
 }
+
+// ---- device-resident scenes (../capi/scene.cpp; the kernels: ../scene/scene_kernels.hip) ---------------------------------
+
+extern "C" int mirt_scene_upload_device(const void *d_tris15, const void *d_culled, int n) { return scene_upload_device(d_tris15, d_culled, n); }
+extern "C" int mirt_scene_update_device(int first, int count, const void *d_tris15) { return scene_update_device(first, count, d_tris15); }
+extern "C" int mirt_scene_update(int first, int count, const float *tris15) { return scene_update_host(first, count, tris15); }
+extern "C" int mirt_scene_transform(int first, int count, const float rot9[9], const float translate3[3])
+{
+    return scene_transform(first, count, rot9, translate3);
+}
+extern "C" int mirt_scene_download(int first, int count, float *tris15) { return scene_download(first, count, tris15); }
+extern "C" int mirt_scene_info(struct mirt_scene_info *out) { return scene_info(out); }
 
 extern "C" int mirt_scene_set_culled(const uint8_t *culled, int n)
 {

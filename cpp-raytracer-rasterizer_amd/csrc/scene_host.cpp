@@ -5,6 +5,7 @@
 #include "../../include/mirt.h"
 
 #include "cull.hpp"
+#include "../scene/scene_xform.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -211,5 +212,15 @@ extern "C" int mirt_cull(const float *tris15, int n, const mirt_view *view, int 
     CullParams cp;
     cull_setup(view, flags, &cp);
     for (int i = 0; i < n; i++) culled[i] = cull_one(tris15 + (size_t)15 * i, cp);
+    return MIRT_OK;
+}
+
+// What mirt_scene_transform does to a range of the uploaded scene, on a host array: the same functions (scene/scene_xform.hpp),
+// so a host mirror moved here and the device scene moved there hold the same bits.
+extern "C" int mirt_transform(float *tris15, int n, const float rot9[9], const float translate3[3])
+{
+    if (n < 0 || (n > 0 && !tris15) || !rot9 || !translate3) return MIRT_ERR_INVALID_ARGUMENT;
+    const v3 tr = ld3(translate3);
+    for (int i = 0; i < n; i++) transform_tri(tris15 + (size_t)15 * i, rot9, tr);
     return MIRT_OK;
 }

@@ -28,6 +28,8 @@ EXPORTS = (
     "mirt_intersect", "mirt_intersect_device", "mirt_direct_light", "mirt_direct_light_device",
     "mirt_set_query_mode", "mirt_get_query_stats",
     "mirt_intersect_from", "mirt_intersect_from_device", "mirt_get_fan_stats",
+    "mirt_scene_upload_device", "mirt_scene_update_device", "mirt_scene_update", "mirt_scene_transform", "mirt_transform",
+    "mirt_scene_download", "mirt_scene_info",
 )
 
 
@@ -65,6 +67,12 @@ class Ray(C.Structure):
 class Hit(C.Structure):
     """mirt_hit == struct Intersection (raytracer.cpp:91-96): position, distance, triangleIndex (20 bytes)."""
     _fields_ = [("position", C.c_float * 3), ("distance", C.c_float), ("index", C.c_int32)]
+
+
+class SceneInfo(C.Structure):
+    """struct mirt_scene_info: the values the library decides with (40 bytes)."""
+    _fields_ = [("n", C.c_int32), ("finite", C.c_int32), ("bbox_lo", C.c_float * 3), ("bbox_hi", C.c_float * 3),
+                ("version", C.c_uint64)]
 
 
 # the same two layouts for numpy: arrays of rays / hit records travel as they are
@@ -137,6 +145,13 @@ def load():
     lib.mirt_intersect_from.argtypes = [_vp, _vp, C.c_int, _vp]
     lib.mirt_intersect_from_device.argtypes = [_vp, _vp, C.c_int, _vp]
     lib.mirt_get_fan_stats.argtypes = [C.POINTER(QueryStats)]
+    lib.mirt_scene_upload_device.argtypes = [_vp, _vp, C.c_int]
+    lib.mirt_scene_update_device.argtypes = [C.c_int, C.c_int, _vp]
+    lib.mirt_scene_update.argtypes = [C.c_int, C.c_int, _vp]
+    lib.mirt_scene_transform.argtypes = [C.c_int, C.c_int, _vp, _vp]
+    lib.mirt_transform.argtypes = [_vp, C.c_int, _vp, _vp]
+    lib.mirt_scene_download.argtypes = [C.c_int, C.c_int, _vp]
+    lib.mirt_scene_info.argtypes = [C.POINTER(SceneInfo)]
     _lib = lib
     return lib
 
@@ -283,6 +298,58 @@ def scene_upload(tris, culled=None):
 def scene_set_culled(culled):
     culled = np.ascontiguousarray(culled, np.uint8)
     _check(load().mirt_scene_set_culled(_ptr(culled), len(culled)))
+
+
+# ---- moving and device-resident scenes (device arrays: raw pointers, e.g. torch.Tensor.data_ptr()) --------
+
+def scene_upload_device(d_tris, n, d_culled=None):
+    """scene_upload with both arrays in device memory (mirt_scene_upload_device): n x 15 floats, and n bytes or None."""
+    _check(load().mirt_scene_upload_device(d_tris, d_culled, int(n)))
+
+
+def scene_update_device(first, count, d_tris):
+    """Replaces triangles [first, first + count) with count x 15 floats in device memory (mirt_scene_update_device)."""
+    _check(load().mirt_scene_update_device(int(first), int(count), d_tris))
+
+
+def scene_update(first, tris):
+    """Replaces triangles [first, first + len(tris)) with the rows of a host array (mirt_scene_update)."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1, 15)
+    _check(load().mirt_scene_update(int(first), len(tris), _ptr(tris)))
+
+
+def scene_transform(first, count, rot9, translate3=(0.0, 0.0, 0.0)):
+    """Moves triangles [first, first + count) in place on the device: v -> rot9 * v + translate3 (GLM column-major mat3), normals
+    recomputed (mirt_scene_transform)."""
+    r = np.ascontiguousarray(rot9, np.float32).reshape(9)
+    t = np.ascontiguousarray(translate3, np.float32).reshape(3)
+    _check(load().mirt_scene_transform(int(first), int(count), _ptr(r), _ptr(t)))
+
+
+def transform(tris, rot9, translate3=(0.0, 0.0, 0.0)):
+    """The arithmetic of scene_transform on a host array (mirt_transform; no device): a new (n, 15) array."""
+    out = np.array(tris, np.float32, order="C").reshape(-1, 15)
+    r = np.ascontiguousarray(rot9, np.float32).reshape(9)
+    t = np.ascontiguousarray(translate3, np.float32).reshape(3)
+    _check(load().mirt_transform(_ptr(out), len(out), _ptr(r), _ptr(t)))
+    return out
+
+
+def scene_download(first=0, count=None):
+    """Triangles [first, first + count) of the uploaded scene (to its end when count is None): (count, 15) float32."""
+    if count is None:
+        count = load().mirt_scene_size() - int(first)
+    out = np.zeros((max(int(count), 0), 15), np.float32)
+    _check(load().mirt_scene_download(int(first), int(count), _ptr(out)))
+    return out
+
+
+def scene_info():
+    """n, finite, bbox_lo, bbox_hi (float32 arrays) and version of the uploaded scene (mirt_scene_info)."""
+    s = SceneInfo()
+    _check(load().mirt_scene_info(C.byref(s)))
+    return {"n": int(s.n), "finite": int(s.finite), "bbox_lo": np.array(list(s.bbox_lo), np.float32),
+            "bbox_hi": np.array(list(s.bbox_hi), np.float32), "version": int(s.version)}
 
 
 def set_depth_of_field(kernel_size, focal_length=0.0):

@@ -189,6 +189,57 @@ MIRT_API int mirt_scene_get_culled(uint8_t *culled, int n);
  * writes the first max_tris of them when tris15 is not NULL (call with NULL first to size the array). */
 MIRT_API int mirt_scene_load_stl(const char *path, float scale, const float *colour3, float *tris15, int max_tris);
 
+/* ---- moving and device-resident scenes ------------------------------------------------------------- */
+
+/* The reference changes `triangles` in place whenever it likes (LoadTestModel scales and flips its vertices, TestModel.h:172-191;
+ * LoadSTL scales the mesh; a game loop would move enemy1.stl every frame) and recomputes the normals afterwards.  These calls are
+ * that for the uploaded scene, without a trip through host memory.
+ *
+ * Ordering, for the four calls that change the scene (mirt_scene_upload_device, mirt_scene_update_device, mirt_scene_update,
+ * mirt_scene_transform): each begins as mirt_scene_upload does -- it waits for every library stream and for the device, so frames in
+ * flight finish on the OLD scene and a source buffer in device memory is complete whatever stream wrote it -- and returns with the
+ * scene, its per-triangle tables, its bounding box and its finiteness flag current (one 32-byte read-back behind the kernels).
+ * Every frame or query queued afterwards, on any stream, sees the new scene; every cache the library keeps (binning passes, light
+ * and query cubes, query rows, rasteriser sizing) is keyed by the scene's version and is rebuilt, not refitted.  A double-buffered
+ * scene, which would let an update overlap frames in flight, is not provided.
+ *
+ * Arguments are checked before anything touches the device: MIRT_ERR_NOT_INITIALISED first; MIRT_ERR_INVALID_ARGUMENT for
+ * first < 0, count < 0, a NULL array with count > 0 or an array that is not 4-byte aligned; MIRT_ERR_NO_SCENE without a scene;
+ * MIRT_ERR_INVALID_ARGUMENT for first + count > n.  count == 0 then does nothing and returns MIRT_OK. */
+
+/* mirt_scene_upload with both arrays in DEVICE memory (d_culled nullable, n bytes): the scene, tables and flags that result are
+ * those of uploading the same values from the host.  A new n reallocates as the host upload does. */
+MIRT_API int mirt_scene_upload_device(const void *d_tris15, const void *d_culled, int n);
+/* Replaces triangles [first, first + count) of the uploaded scene with count x 15 floats from device / host memory (the host form is
+ * staged through the device); n and the cull flags stay as they are.  The bounding box is taken over the whole scene again: it
+ * can shrink. */
+MIRT_API int mirt_scene_update_device(int first, int count, const void *d_tris15);
+MIRT_API int mirt_scene_update(int first, int count, const float *tris15);
+/* Moves triangles [first, first + count) in place, on the device: each of the three vertices becomes rot9 * v + translate3 -- GLM's
+ * column-major mat3 * vec3 in its written order (per row: three products summed left to right), then one add per component, no
+ * contraction; Draw() does the same to its ray direction (cameraRot * d, raytracer.cpp:580) -- and the normal is recomputed by
+ * Triangle::ComputeNormal, normalize(cross(v2 - v0, v1 - v0)) (TestModel.h:26-31).  The colour is untouched.  Repeated calls
+ * compound their rounding: a caller who needs a drift-free pose keeps the rest pose and sends the posed rows with
+ * mirt_scene_update*. */
+MIRT_API int mirt_scene_transform(int first, int count, const float rot9[9], const float translate3[3]);
+/* The same arithmetic on n triangles of a HOST array, bit for bit (pure arithmetic, no device: to mirt_scene_transform what mirt_cull
+ * is to mirt_cull_device) -- for a caller that keeps a host mirror of the scene. */
+MIRT_API int mirt_transform(float *tris15, int n, const float rot9[9], const float translate3[3]);
+/* Reads triangles [first, first + count) back into count x 15 floats; complete on return. */
+MIRT_API int mirt_scene_download(int first, int count, float *tris15);
+/* The values the library decides with, whichever way the scene arrived: finite = every one of the 15 n floats is below 1e8 in
+ * magnitude (a scene that is not takes the brute-force paths); the box is fminf / fmaxf over the vertex coordinates (a NaN is
+ * skipped, an infinity counts, an axis without a number stays at +inf / -inf); version changes with every change of the triangles.
+ * (A struct tag, not a typedef: C keeps tags apart from function names, as with stat.) */
+struct mirt_scene_info {
+    int32_t n;
+    int32_t finite;
+    float bbox_lo[3];
+    float bbox_hi[3];
+    uint64_t version;
+};
+MIRT_API int mirt_scene_info(struct mirt_scene_info *out);
+
 /* Soft shadows (SOFT_SHADOWS_ENABLED / SOFT_SHADOWS_SAMPLES / randomPositions, raytracer.cpp:40-41,84,186-190,
  * 272-287): when samples > 1 every light k is replaced in DirectLight by `samples` jittered positions
  * positions[(k*samples + i)*3 .. +2] with 1/samples of its power each.  The caller generates the positions (the

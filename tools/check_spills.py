@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/check_spills.py -- compiles every kernel source of the library (csrc/ and query/) for gfx950 (device side only, the Makefile's flags) and lists
+"""tools/check_spills.py -- compiles every kernel source of the library (csrc/, query/ and scene/) for gfx950 (device side only, the Makefile's flags) and lists
 each kernel's VGPR count, occupancy and scratch bytes (and which kernels sit within eight registers of another wave per SIMD); exits non-zero if any kernel spills to scratch (private segment != 0).
 __graft_entry__.build() runs it: a spill in a hot loop is a silent 2-3x."""
 import os
@@ -9,7 +9,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIRS = [os.path.join(ROOT, "cpp-raytracer-rasterizer_amd", d) for d in ("csrc", "query")]
+DIRS = [os.path.join(ROOT, "cpp-raytracer-rasterizer_amd", d) for d in ("csrc", "query", "scene")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-x", "hip", "--cuda-device-only", "-S"]
 bad = []
 rows = []
@@ -45,7 +45,8 @@ for r in rows:
 # the gate must not pass vacuously: should the backend's resource comments change shape, the pattern above matches nothing
 EXPECT = ("k_rt_trace2", "k_rt_tile2", "k_rt_brute", "k_bin_pairs", "k_raster_small", "k_raster_resolve", "k_dof_tile", "k_bs_local",
           "k_query_rows", "k_query_closest<", "k_query_closest_wave", "k_query_direct_light<", "k_query_direct_light_binned",
-          "k_query_fan<", "k_query_fan_binned<false>", "k_query_fan_binned<true>")
+          "k_query_fan<", "k_query_fan_binned<false>", "k_query_fan_binned<true>",
+          "k_scene_bounds_init", "k_scene_range<1>", "k_scene_range<3>", "k_scene_range<5>", "k_scene_range<7>", "k_scene_range<4>")
 missing = [k for k in EXPECT if not any(k in r[1] for r in rows)]
 if missing or len(rows) < 20:
     sys.exit("tools/check_spills.py: resource summaries found for %d kernels only; missing %s -- the pattern no longer matches the backend's output"
