@@ -125,7 +125,7 @@ int bin_pass(RtScratch &S, BinSet bs, const OriginRow *cam_tab, const OriginRow 
     if (fresh) {
         uint32_t c[16];
         (void)hipMemcpy(c, counter, 64, hipMemcpyDeviceToHost);
-        fprintf(stderr, "[mirt bin stats] flattened tests=%u max per work item=%u direct items=%u | huge: box valid=%u no box=%u (camera frame %u)\n", c[8], c[9], c[10], c[11], c[12], c[14]);
+        fprintf(stderr, "[mirt bin stats] flattened units=%u max per work item=%u direct items=%u | huge: box valid=%u no box=%u (camera frame %u) waves in the joint test=%u\n", c[8], c[9], c[10], c[11], c[12], c[14], c[15]);
         fprintf(stderr, "[mirt bin stats] tris=%d frames=%d  pairs=%u  bins=%u | large items walked=%u level-1 rounds=%u level-2 steps=%u pairs=%u max steps/item=%u items>100 steps=%u\n",
                 g.n, bs.nframes, *npairs, bs.nbins, c[2], c[3], c[4], c[5], c[6], c[7]);
         (void)hipMemset(counter + 2, 0, 56);

@@ -105,7 +105,17 @@ __device__ __forceinline__ bool bin_jointly_empty(const BinLin (&G)[4], float u0
 struct BinFrameGrid { int nbu, fj0, fj1, cells_x, cy0, ncell; uint32_t fbase, nshell; };
 
 constexpr int BIN_PAIR_BUF = 4096;                    // pairs a workgroup stages in LDS between flushes (32 KiB)
-constexpr int BIN_TESTS_PER_THREAD = 2;               // flattened bin tests a thread runs per round (independent chains: their LDS latencies overlap)
+// The flattened tests of the direct items come in UNITS of BIN_UNIT consecutive bins of one box row: a thread finds its item, loads
+// the item's constants and derives (i, j) and the key of the unit's first bin once, then steps through the unit's bins -- what a
+// bin costs beyond that is its own two FMAs per function and the compares.  (2, 4 and 8 were timed: DESIGN.md section 5.)
+#ifndef MIRT_BIN_UNIT
+#define MIRT_BIN_UNIT 4
+#endif
+constexpr int BIN_UNIT = MIRT_BIN_UNIT;
+static_assert(BIN_UNIT == 2 || BIN_UNIT == 4 || BIN_UNIT == 8, "a unit is 2, 4 or 8 bins");
+// Units a thread runs per round (independent chains: their LDS latencies overlap).  A round may append WG * units * BIN_UNIT pairs and
+// asks for that much room in front: half the staging buffer where that leaves a whole unit per thread, all of it otherwise.
+template <int WG> constexpr int bin_units_per_thread() { return BIN_PAIR_BUF / 2 / (WG * BIN_UNIT) > 0 ? BIN_PAIR_BUF / 2 / (WG * BIN_UNIT) : 1; }
 constexpr int BIN_DIRECT_SIDE = 32;                   // boxes up to 32 x 32 bins are tested bin by bin, flattened over the workgroup
 
 // Where the pairs of the huge items go: the workgroup's LDS buffer, allocated with an LDS atomic per level-2 step, and
@@ -359,8 +369,9 @@ __global__ __launch_bounds__(WG) void k_bin_pairs(const float *__restrict__ tris
     __shared__ float4 s_A2[256], s_Bu[256], s_Bv[256], s_box[256];
     __shared__ uint32_t s_org[256];                   // i_lo | j_lo << 16 of a direct item's box
     __shared__ uint32_t s_ni[256];                    // its width in bins
+    __shared__ uint32_t s_upr[256];                   // its units per row, and the reciprocal that divides by them
     __shared__ uint32_t s_tri[256];                   // its triangle
-    __shared__ uint32_t s_pre[257];                   // exclusive prefix of the box sizes
+    __shared__ uint32_t s_pre[257];                   // exclusive prefix of the boxes' units (rows x units per row)
     __shared__ uint32_t s_wave[4];
     __shared__ uint32_t s_base, s_fill, s_valid;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -458,6 +469,7 @@ __global__ __launch_bounds__(WG) void k_bin_pairs(const float *__restrict__ tris
         int kind = 0;                                     // 0: no bin can hold a hit, 1: direct (box of at most 32 x 32 bins), 2: huge (wave walks)
 #ifdef MIRT_BIN_STATS
         int dbg_state = 0;
+        bool dbg_joint = false;
 #endif
         int i_lo = 0, i_hi = -1, j_lo = 0, j_hi = -1;
         unsigned long long cells = 0;                     // huge items: level-0 cells (first 64) that may hold a hit
@@ -493,11 +505,11 @@ __global__ __launch_bounds__(WG) void k_bin_pairs(const float *__restrict__ tris
                 it.A2[k] = both ? inf : base + corner(su, fr.pad_lo, fr.du + fr.pad_hi) + corner(sv, fr.pad_lo, fr.dv + fr.pad_hi);
             }
             if (t.bstate == BOX_VALID) {
-                // bin-index ranges, widened by 2^-18 (relative) against the rounding of this conversion
-                it.lou = (t.bu0 - fr.ulo - fr.pad_hi) / fr.du; it.hiu = (t.bu1 - fr.ulo - fr.pad_lo) / fr.du;
-                it.lov = (t.bv0 - fr.vlo - fr.pad_hi) / fr.dv; it.hiv = (t.bv1 - fr.vlo - fr.pad_lo) / fr.dv;
-                it.lou -= 3.814697265625e-06f * (1.0f + fabsf(it.lou)); it.hiu += 3.814697265625e-06f * (1.0f + fabsf(it.hiu));
-                it.lov -= 3.814697265625e-06f * (1.0f + fabsf(it.lov)); it.hiv += 3.814697265625e-06f * (1.0f + fabsf(it.hiv));
+                // bin-index ranges, widened by 2^-18 (relative) against the rounding of this conversion and by 2^-20 more for the
+                // reciprocals that stand for its four divisions (off by less than 2^-22 with their multiplication)
+                // (box_to_bins, rt_binned.hpp)
+                box_to_bins(t.bu0, t.bu1, fr.ulo, fr.pad_lo, fr.pad_hi, bin_rcp(fr.du), &it.lou, &it.hiu);
+                box_to_bins(t.bv0, t.bv1, fr.vlo, fr.pad_lo, fr.pad_hi, bin_rcp(fr.dv), &it.lov, &it.hiv);
             } else if (t.bstate == BOX_EMPTY) {
                 it.lou = it.lov = inf; it.hiu = it.hiv = -inf;
             } else {
@@ -522,6 +534,9 @@ __global__ __launch_bounds__(WG) void k_bin_pairs(const float *__restrict__ tris
                 if (!cells) kind = 0;
                 // ... and the joint test: is there ANY point of the frame where all four functions hold at once?
                 if (kind == 2 && !both) {
+#ifdef MIRT_BIN_STATS
+                    dbg_joint = true;
+#endif
                     BinLin G[4];
 #pragma unroll
                     for (int k = 0; k < 4; k++) { G[k].a = sgn * fn[k]->c0 + fn[k]->m; G[k].bu = sgn * fn[k]->cu; G[k].bv = sgn * fn[k]->cv; }
@@ -537,7 +552,8 @@ __global__ __launch_bounds__(WG) void k_bin_pairs(const float *__restrict__ tris
         STAMP(st_setup)
         // ---- direct items: constants to LDS, exclusive prefix of their box sizes over the workgroup ----
         const uint32_t ni = (uint32_t)(i_hi - i_lo + 1);
-        const uint32_t nb = kind == 1 ? ni * (uint32_t)(j_hi - j_lo + 1) : 0u;
+        const uint32_t upr = (ni + (uint32_t)(BIN_UNIT - 1)) / (uint32_t)BIN_UNIT;            // units per row: at most 32 / BIN_UNIT
+        const uint32_t nb = kind == 1 ? upr * (uint32_t)(j_hi - j_lo + 1) : 0u;
         uint32_t incl = nb;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
@@ -553,6 +569,7 @@ __global__ __launch_bounds__(WG) void k_bin_pairs(const float *__restrict__ tris
             s_box[threadIdx.x] = make_float4(it.lou, it.hiu, it.lov, it.hiv);
             s_org[threadIdx.x] = (uint32_t)i_lo | ((uint32_t)j_lo << 16);
             s_ni[threadIdx.x] = ni | (shell << 8);
+            s_upr[threadIdx.x] = upr | ((65536u / upr + 1u) << 8);   // b / upr == (b * recip) >> 16: exact for b < 1024 and upr <= 32; here b < 32 * upr and upr <= 32 / BIN_UNIT
             s_tri[threadIdx.x] = tri;
         }
         __syncthreads();
@@ -565,22 +582,26 @@ __global__ __launch_bounds__(WG) void k_bin_pairs(const float *__restrict__ tris
         if (kind == 2) { atomicAdd(&bs.counters[11 + dbg_state], 1u); if (frame == 0) atomicAdd(&bs.counters[14], 1u); }
         if (threadIdx.x == 0) { atomicAdd(&bs.counters[8], T); atomicMax(&bs.counters[9], T); }
         { const unsigned long long md = __ballot(kind == 1); if (lane == 0) atomicAdd(&bs.counters[10], (uint32_t)__popcll(md)); }
+        { const unsigned long long mj = __ballot(dbg_joint); if (lane == 0 && mj) atomicAdd(&bs.counters[15], 1u); }     // waves that ran the joint test
 #endif
         STAMP(st_prefix)
-        // ---- flattened bin-by-bin tests: thread t of a round takes tests t, t + WG, ... ----
-        constexpr int TPT = BIN_TESTS_PER_THREAD;
-        for (uint32_t r0 = 0; r0 < T; r0 += WG * TPT) {
+        // ---- flattened tests, in units of BIN_UNIT bins of a row: thread t of a round takes units t, t + WG, ... ----
+        constexpr int UPT = bin_units_per_thread<WG>();
+        constexpr uint32_t ROUND_PAIRS = (uint32_t)(WG * UPT * BIN_UNIT);
+        static_assert(ROUND_PAIRS <= (uint32_t)BIN_PAIR_BUF, "a round's pairs must fit the staging buffer");
+        for (uint32_t r0 = 0; r0 < T; r0 += WG * UPT) {
 #ifdef MIRT_BIN_STAMPS
             st_nrounds++;
 #endif
             __syncthreads();                          // s_pre written / the previous round's appends counted
-            if (s_fill + (uint32_t)(WG * TPT) > (uint32_t)BIN_PAIR_BUF) flush();
-            bool pass[TPT];
-            uint32_t key[TPT], val[TPT];
+            const uint32_t fill = s_fill;             // read by every wave BEFORE any wave of this round appends: the barrier below keeps
+            __syncthreads();                          // a fast wave's atomicAdd away from a slow wave's read, so all take the same branch
+            if (fill + ROUND_PAIRS > (uint32_t)BIN_PAIR_BUF) flush();
+            uint32_t pm[UPT], key0[UPT], val[UPT];    // pm: bit b = bin b of the unit passes; key0: the key of its first bin
 #pragma unroll
-            for (int q = 0; q < TPT; q++) {
+            for (int q = 0; q < UPT; q++) {
                 const uint32_t t = r0 + (uint32_t)(q * WG) + threadIdx.x;
-                pass[q] = false; key[q] = 0; val[q] = 0;
+                pm[q] = 0; key0[q] = 0; val[q] = 0;
                 if (t < T) {
                     uint32_t lo = 0, hi = 256;            // the item whose range [s_pre[i], s_pre[i+1]) holds t
 #pragma unroll
@@ -589,42 +610,52 @@ __global__ __launch_bounds__(WG) void k_bin_pairs(const float *__restrict__ tris
                         if (s_pre[mid] <= t) lo = mid; else hi = mid;
                     }
                     const uint32_t nis = s_ni[lo], wi = nis & 0xFFu, sh = nis >> 8;
-                    const uint32_t b = t - s_pre[lo], org = s_org[lo];
-                    const uint32_t recip = 65536u / wi + 1u;             // b / wi == (b * recip) >> 16 for b < 1024, wi <= 32
-                    const uint32_t dj = (b * recip) >> 16, di = b - dj * wi;
-                    const int i = (int)(org & 0xFFFFu) + (int)di, j = (int)(org >> 16) + (int)dj;
+                    const uint32_t ur = s_upr[lo], b = t - s_pre[lo], org = s_org[lo];
+                    const uint32_t dj = (b * (ur >> 8)) >> 16, di = (b - dj * (ur & 0xFFu)) * (uint32_t)BIN_UNIT;
+                    const int i0 = (int)(org & 0xFFFFu) + (int)di, j = (int)(org >> 16) + (int)dj;
+                    const int here = (int)wi - (int)di;   // bins of the row from i0 on: the unit ends with the row
                     const float4 A2 = s_A2[lo], Bu = s_Bu[lo], Bv = s_Bv[lo], box = s_box[lo];
-                    const float FI = (float)i, FJ = (float)j;
-                    pass[q] = (__builtin_fmaf(FJ, Bv.x, __builtin_fmaf(FI, Bu.x, A2.x)) >= 0.0f) &&
-                              (__builtin_fmaf(FJ, Bv.y, __builtin_fmaf(FI, Bu.y, A2.y)) >= 0.0f) &&
-                              (__builtin_fmaf(FJ, Bv.z, __builtin_fmaf(FI, Bu.z, A2.z)) >= 0.0f) &&
-                              (__builtin_fmaf(FJ, Bv.w, __builtin_fmaf(FI, Bu.w, A2.w)) >= 0.0f) &&
-                              (FI + 1.0f >= box.x) && (FI <= box.y) && (FJ + 1.0f >= box.z) && (FJ <= box.w);   // = cell_may_hit(.., A2, i, j, 1)
-                    key[q] = (gr.fbase + (uint32_t)j * (uint32_t)nbu + (uint32_t)i) * gr.nshell + sh;
+                    const float FJ = (float)j;
+                    const bool row = (FJ + 1.0f >= box.z) && (FJ <= box.w);
+#pragma unroll
+                    for (int k = 0; k < BIN_UNIT; k++) {
+                        const float FI = (float)(i0 + k);
+                        const bool ok = (__builtin_fmaf(FJ, Bv.x, __builtin_fmaf(FI, Bu.x, A2.x)) >= 0.0f) &&
+                                        (__builtin_fmaf(FJ, Bv.y, __builtin_fmaf(FI, Bu.y, A2.y)) >= 0.0f) &&
+                                        (__builtin_fmaf(FJ, Bv.z, __builtin_fmaf(FI, Bu.z, A2.z)) >= 0.0f) &&
+                                        (__builtin_fmaf(FJ, Bv.w, __builtin_fmaf(FI, Bu.w, A2.w)) >= 0.0f) &&
+                                        (FI + 1.0f >= box.x) && (FI <= box.y) && row;     // = cell_may_hit(.., A2, i0 + k, j, 1)
+                        if (ok && k < here) pm[q] |= 1u << k;
+                    }
+                    key0[q] = (gr.fbase + (uint32_t)j * (uint32_t)nbu + (uint32_t)i0) * gr.nshell + sh;
                     val[q] = s_tri[lo];
                 }
             }
-            // one LDS atomic per wave and round hands out the slots of all its passing tests
-            unsigned long long m[TPT];
-            uint32_t off[TPT], cnt = 0;
+            // one LDS atomic per wave and round hands out the slots of all its passing bins
+            unsigned long long m[UPT][BIN_UNIT];
+            uint32_t off[UPT][BIN_UNIT], cnt = 0;
 #pragma unroll
-            for (int q = 0; q < TPT; q++) { m[q] = __ballot(pass[q]); off[q] = cnt; cnt += (uint32_t)__popcll(m[q]); }
+            for (int q = 0; q < UPT; q++)
+#pragma unroll
+                for (int k = 0; k < BIN_UNIT; k++) { m[q][k] = __ballot((pm[q] >> k) & 1u); off[q][k] = cnt; cnt += (uint32_t)__popcll(m[q][k]); }
             if (cnt) {
                 uint32_t at0 = 0;
                 if (lane == 0) at0 = atomicAdd(&s_fill, cnt);
                 at0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)at0);
 #pragma unroll
-                for (int q = 0; q < TPT; q++)
-                    if (pass[q]) {
-                        const uint32_t at = at0 + off[q] + (uint32_t)__popcll(m[q] & ((1ull << lane) - 1ull));
-                        s_keys[at] = key[q]; s_vals[at] = val[q];         // fits: the round started with room for WG * TPT
-                    }
+                for (int q = 0; q < UPT; q++)
+#pragma unroll
+                    for (int k = 0; k < BIN_UNIT; k++)
+                        if ((pm[q] >> k) & 1u) {
+                            const uint32_t at = at0 + off[q][k] + (uint32_t)__popcll(m[q][k] & ((1ull << lane) - 1ull));
+                            s_keys[at] = key0[q] + (uint32_t)k * gr.nshell; s_vals[at] = val[q];      // fits: the round started with room for ROUND_PAIRS
+                        }
             }
         }
 
         STAMP(st_rounds)
         // ---- huge items: the wave walks them one at a time, pairs into the same LDS buffer ----
-        __syncthreads();                              // no flattened round (which counts on its WG * TPT free slots) is still appending
+        __syncthreads();                              // no flattened round (which counts on its ROUND_PAIRS free slots) is still appending
         {
             BinLargeSink sink = { s_keys, s_vals, &s_fill, &s_valid, &bs.counters[0], out, bs.bucket_cnt, bs.bucket_shift };
             for (unsigned long long ml = __ballot(kind == 2); ml;) {

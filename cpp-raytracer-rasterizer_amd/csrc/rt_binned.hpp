@@ -134,7 +134,7 @@ struct BinPairs {
 // affine edge function over (u,v) with its safety margin
 struct EdgeFn { float c0, cu, cv, m; };
 
-__device__ __forceinline__ EdgeFn make_edge_fn(float gx, float gy, float gz, const BinFrameDesc &fr)
+MIRT_HD EdgeFn make_edge_fn(float gx, float gy, float gz, const BinFrameDesc &fr)
 {
     EdgeFn e;
     e.c0 = gx * fr.P0[0] + gy * fr.P0[1] + gz * fr.P0[2];
@@ -152,7 +152,7 @@ struct TriBinFns {
 };
 enum { BOX_NONE = 0, BOX_VALID = 1, BOX_EMPTY = 2 };
 
-__device__ __forceinline__ TriBinFns make_bin_fns(const OriginRow &r, const BinFrameDesc &fr)
+MIRT_HD TriBinFns make_bin_fns(const OriginRow &r, const BinFrameDesc &fr)
 {
     TriBinFns t;
     t.n = make_edge_fn(r.r0.x, r.r0.y, r.r0.z, fr);
@@ -188,8 +188,46 @@ __device__ __forceinline__ TriBinFns make_bin_fns(const OriginRow &r, const BinF
 //    d < r_in/2 (r_in bounded from below) no ray of this family can be accepted at all (BOX_EMPTY);
 //  * anything else (a vertex near the plane, degenerate projections, NaN) keeps BOX_NONE and relies on the edge
 //    functions, which are always valid.
-__device__ __forceinline__ void add_bbox(TriBinFns &t, const float *t15, const BinFrameDesc &fr)
+//
+// Rounding.  Of the 21 divisions and 9 square roots this construction asks for, only the six vertex quotients un/w, vn/w are
+// IEEE divisions.  Everything else goes through the hardware's one-ulp reciprocal and reciprocal square root (bin_rcp, bin_rsq
+// below; with the multiplication that follows, off by less than 2^-21 where the IEEE operations were off by 2^-23), and every
+// such value is moved to its safe side by 1 + 2^-19, sixteen times that error:
+//  * pad (1/|w| is a reciprocal) and the margin distances m * rsq(cu^2 + cv^2) are raised, so d is from above -- which is the safe
+//    side for the pushed-out box and for BOX_EMPTY alike;
+//  * BOX_EMPTY compares d with half the inradius from BELOW: the area from below (with the raised pad and perimeter) times the
+//    reciprocal of the perimeter from above (edge lengths s * rsq(s), raised), lowered by 2^-19;
+//  * the corner offsets k_i = dd / |e_a x e_b| are from above: the cross product of two unit vectors cancels, for a needle almost
+//    entirely, so 2^-19 of its two products -- twice what unit vectors that are each off by 2^-21 can move it -- is taken off its
+//    magnitude first.  A corner so sharp that nothing is left (an angle below ~1e-5) keeps BOX_NONE;
+//  * the box takes the corners at these (larger) k_i AND the vertices themselves; a corner offset by any smaller k_i along the same
+//    direction lies between the two.  What the direction e_a + e_b itself may be off by, 2^-20 * k_i, and the rounding of the
+//    corner's own evaluation go into `slack` as 2^-18 * max(k_i) + 2^-21 * max(|u|, |v|).
+// The vertex quotients stay exact because the corner offsets are not a well-conditioned function of them: a needle of aspect
+// 1:1000 at u ~ 1000 turns by several per cent when its vertices move by 2^-22 * u, and no fixed widening covers that.  With them
+// exact every step above is monotone, and the box contains the one IEEE arithmetic throughout would give: tests/cpp/bin_box_test.cpp
+// holds the two side by side on the host, with reciprocals that are off by 2^-22 either way.
+// NaN and infinities (a vanishing edge, a denormal the hardware flushes before its reciprocal) fail the comparisons below and end
+// in BOX_NONE, never in BOX_EMPTY.
+// frame_may_see() further down no longer contains this box for the sharpest needles (it never forms unit vectors, so it has no
+// cancellation to allow for).  It does not need to: its displacement bounds the exact pushed-out triangle by an argument of its
+// own, which is what makes a rejection by k_prep_select valid; what this box adds beyond the exact one are false positives only.
+#ifdef __HIP_DEVICE_COMPILE__
+MIRT_HD float bin_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+MIRT_HD float bin_rsq(float x) { return __builtin_amdgcn_rsqf(x); }
+#else
+// the host side exists for tests, which may put twins of their own behind the two hooks
+#ifndef MIRT_BIN_HOST_RCP
+#define MIRT_BIN_HOST_RCP(x) (1.0f / (x))
+#define MIRT_BIN_HOST_RSQ(x) (1.0f / sqrtf(x))
+#endif
+MIRT_HD float bin_rcp(float x) { return MIRT_BIN_HOST_RCP(x); }
+MIRT_HD float bin_rsq(float x) { return MIRT_BIN_HOST_RSQ(x); }
+#endif
+
+MIRT_HD void add_bbox(TriBinFns &t, const float *t15, const BinFrameDesc &fr)
 {
+    const float UP = 1.0000019073486328125f, DOWN = 0.99999809265136719f;      // 1 + 2^-19, 1 - 2^-19
     float us[3], vs[3], pad = 0.0f;
     int front = 0, behind = 0;
 #pragma unroll
@@ -205,49 +243,67 @@ __device__ __forceinline__ void add_bbox(TriBinFns &t, const float *t15, const B
         us[j] = un / w; vs[j] = vn / w;
         // rounding of the projection: un, vn, w each carry <= 2^-22 of their term sums (3 products, 2 sums), the
         // quotient 2^-24 more:  |du| <= (2^-22*um + |u|*2^-22*wm)/|w| + 2^-24*|u|; doubled for comfort
-        const float iw = 1.0f / fabsf(w);
+        const float iw = bin_rcp(fabsf(w));
         pad = fmaxf(pad, 4.76837158203125e-07f * ((um + fabsf(us[j]) * wm) * iw + (vm + fabsf(vs[j]) * wm) * iw) +
                              2.384185791015625e-07f * (fabsf(us[j]) + fabsf(vs[j])));
     }
+    pad *= UP;
     if (front != 3 && behind != 3) return;
     const float u0 = fminf(fminf(us[0], us[1]), us[2]), u1 = fmaxf(fmaxf(us[0], us[1]), us[2]);
     const float v0 = fminf(fminf(vs[0], vs[1]), vs[2]), v1 = fmaxf(fmaxf(vs[0], vs[1]), vs[2]);
     const float ext = fmaxf(u1 - u0, v1 - v0);
-    // inradius = 2*area / perimeter of the projected triangle
     const float ax = us[1] - us[0], ay = vs[1] - vs[0], bx = us[2] - us[0], by = vs[2] - vs[0], cx = us[2] - us[1], cy = vs[2] - vs[1];
-    const float area2 = fabsf(ax * by - ay * bx);
-    const float per = sqrtf(ax * ax + ay * ay) + sqrtf(bx * bx + by * by) + sqrtf(cx * cx + cy * cy);
+    const float s01 = ax * ax + ay * ay, s02 = bx * bx + by * by, s12 = cx * cx + cy * cy;
+    const float r01 = bin_rsq(s01), r02 = bin_rsq(s02), r12 = bin_rsq(s12);
     // margin distances of the three edge functions, in (u,v) units
-    const float dp = t.p.m / sqrtf(t.p.cu * t.p.cu + t.p.cv * t.p.cv);
-    const float dq = t.q.m / sqrtf(t.q.cu * t.q.cu + t.q.cv * t.q.cv);
-    const float ds = t.s.m / sqrtf(t.s.cu * t.s.cu + t.s.cv * t.s.cv);
-    const float d = fmaxf(fmaxf(dp, dq), ds) + pad;
+    const float dp = t.p.m * bin_rsq(t.p.cu * t.p.cu + t.p.cv * t.p.cv);
+    const float dq = t.q.m * bin_rsq(t.q.cu * t.q.cu + t.q.cv * t.q.cv);
+    const float ds = t.s.m * bin_rsq(t.s.cu * t.s.cu + t.s.cv * t.s.cv);
+    const float d = fmaxf(fmaxf(dp, dq), ds) * UP + pad;
     if (behind == 3) {
         // needs d < r_in = 2*area/perimeter.  r_in is taken from below: every vertex may be off by `pad` (area changes by
         // at most pad*perimeter, doubled) and the cross product cancels (2^-21 of its two products); half of that bound
         // is the threshold.  NaN or a vanishing area keep BOX_NONE.
-        const float area_lo = area2 - 2.0f * pad * per - 4.76837158203125e-07f * (fabsf(ax * by) + fabsf(ay * bx));
-        if (d < 0.5f * (area_lo / per)) t.bstate = BOX_EMPTY;
+        const float t1 = ax * by, t2 = ay * bx;
+        const float per = (s01 * r01 + s02 * r02 + s12 * r12) * UP;
+        const float area_lo = fabsf(t1 - t2) - 2.0f * pad * per - 4.76837158203125e-07f * (fabsf(t1) + fabsf(t2));
+        if (d < 0.5f * (area_lo * bin_rcp(per)) * DOWN) t.bstate = BOX_EMPTY;
         return;
     }
     // front: the region {dist_i >= -d} is the triangle with every edge line pushed out by d, i.e. the triangle whose
     // vertex i sits at  V_i - d*(ua + ub)/|ua x ub|  (ua, ub = unit vectors along the two edges leaving V_i; the
     // offset is d/sin(angle/2) along the outward bisector).  Its box is tight even for needles, whose tip runs far
     // out along the needle only.  Degenerate corners give a non-finite offset and keep BOX_NONE.
-    const float l01 = sqrtf(ax * ax + ay * ay), l02 = sqrtf(bx * bx + by * by), l12 = sqrtf(cx * cx + cy * cy);
-    const float e01x = ax / l01, e01y = ay / l01, e02x = bx / l02, e02y = by / l02, e12x = cx / l12, e12y = cy / l12;
+    const float e01x = ax * r01, e01y = ay * r01, e02x = bx * r02, e02y = by * r02, e12x = cx * r12, e12y = cy * r12;
     const float dd = 1.25f * d;
-    const float k0 = dd / fabsf(e01x * e02y - e01y * e02x), k1 = dd / fabsf(e01x * e12y - e01y * e12x), k2 = dd / fabsf(e02x * e12y - e02y * e12x);
+    const float c0a = e01x * e02y, c0b = e01y * e02x, c1a = e01x * e12y, c1b = e01y * e12x, c2a = e02x * e12y, c2b = e02y * e12x;
+    const float c0 = fabsf(c0a - c0b) - 1.9073486328125e-06f * (fabsf(c0a) + fabsf(c0b));
+    const float c1 = fabsf(c1a - c1b) - 1.9073486328125e-06f * (fabsf(c1a) + fabsf(c1b));
+    const float c2 = fabsf(c2a - c2b) - 1.9073486328125e-06f * (fabsf(c2a) + fabsf(c2b));
+    if (!(c0 > 0.0f && c1 > 0.0f && c2 > 0.0f)) return;                                   // also NaN
+    const float k0 = dd * bin_rcp(c0) * UP, k1 = dd * bin_rcp(c1) * UP, k2 = dd * bin_rcp(c2) * UP;
     const float px0 = us[0] - k0 * (e01x + e02x), py0 = vs[0] - k0 * (e01y + e02y);
     const float px1 = us[1] - k1 * (e12x - e01x), py1 = vs[1] - k1 * (e12y - e01y);
     const float px2 = us[2] + k2 * (e02x + e12x), py2 = vs[2] + k2 * (e02y + e12y);
-    const float slack = 2.0f * pad + 1.0e-6f * ext;
+    const float slack = 2.0f * pad + 1.0e-6f * ext + 3.814697265625e-06f * fmaxf(fmaxf(k0, k1), k2) +
+                        4.76837158203125e-07f * fmaxf(fmaxf(fabsf(u0), fabsf(u1)), fmaxf(fabsf(v0), fabsf(v1)));
     const float bu0 = fminf(fminf(px0, px1), px2) - slack, bu1 = fmaxf(fmaxf(px0, px1), px2) + slack;
     const float bv0 = fminf(fminf(py0, py1), py2) - slack, bv1 = fmaxf(fmaxf(py0, py1), py2) + slack;
     if (!(bu0 > -1.0e30f && bu1 < 1.0e30f && bv0 > -1.0e30f && bv1 < 1.0e30f)) return;     // also NaN
     // the pushed-out triangle contains the original one; keep that explicit against rounding of the offsets
     t.bu0 = fminf(bu0, u0 - slack); t.bu1 = fmaxf(bu1, u1 + slack); t.bv0 = fminf(bv0, v0 - slack); t.bv1 = fmaxf(bv1, v1 + slack);
     t.bstate = BOX_VALID;
+}
+
+// The box as a range of bin indices along one axis: bin i (covering [org + i*step + pad_lo, org + (i+1)*step + pad_hi]) overlaps
+// [b0, b1] iff i + 1 >= lo && i <= hi.  `istep` = bin_rcp(step): with its multiplication the quotient is off by less than 2^-22, so
+// the range is widened by 2^-18 (relative: the rounding of the conversion itself) and 2^-20 more -- it contains the range a division
+// and 2^-18 give (tests/cpp/bin_box_test.cpp).
+MIRT_HD void box_to_bins(float b0, float b1, float org, float pad_lo, float pad_hi, float istep, float *lo, float *hi)
+{
+    float l = (b0 - org - pad_hi) * istep, h = (b1 - org - pad_lo) * istep;
+    l -= 4.76837158203125e-06f * (1.0f + fabsf(l)); h += 4.76837158203125e-06f * (1.0f + fabsf(h));
+    *lo = l; *hi = h;
 }
 
 // ---- the cheap pre-test in front of all that (k_prep_select) -------------------------------------------------------------------
@@ -259,10 +315,11 @@ __device__ __forceinline__ void add_bbox(TriBinFns &t, const float *t15, const B
 // edge functions; vertex i of that pushed-out triangle sits d / sin(angle_i / 2) from the projected vertex, and
 //     sin(angle_i / 2) >= sin(angle_i) / 2 = area2 / (2 * l_a * l_b) >= area2 / (2 * (extu^2 + extv^2))
 // bounds every such offset by  disp = 2 * dd * (extu^2 + extv^2) / area2  (dd = 1.25 * d as in add_bbox) without a square root
-// or a division per corner.  The box [u0 - disp, u1 + disp] x [v0 - disp, v1 + disp] therefore CONTAINS add_bbox()'s; a frame
-// whose rows and columns it misses (by a whole bin more than add_bbox()'s own conversion would ask for) holds no pair of the
-// triangle.  Reciprocals and reciprocal square roots are the hardware's one-ulp approximations; the projection's pad carries
-// 2^-21 per quotient instead of add_bbox()'s 2^-22 for them, margin distances and the displacement are raised by 2^-19.
+// or a division per corner.  The box [u0 - disp, u1 + disp] x [v0 - disp, v1 + disp] therefore CONTAINS the exact pushed-out triangle
+// add_bbox() boxes (add_bbox()'s own box may reach further where it allows for the cancellation in its corner offsets: false
+// positives of its own); a frame whose rows and columns it misses (by a whole bin more than add_bbox()'s own conversion would ask
+// for) holds no pair of the triangle.  Reciprocals and reciprocal square roots are the hardware's one-ulp approximations; the projection's pad carries
+// 2^-21 per quotient instead of the 2^-22 of add_bbox()'s exact quotients, margin distances and the displacement are raised by 2^-19.
 // A triangle whose three vertices lie clearly BEHIND the plane -- what five of the six faces of a light's cube see of most triangles
 // -- cannot be hit at all while d stays below half its projected inradius (add_bbox's BOX_EMPTY, with the inradius bounded from
 // below by area_lo over the box's perimeter).
