@@ -167,12 +167,14 @@ bool shell_range(const float *pos, double *dn, double *df)
 // Frame descriptors of the light cubes: six faces of B x B bins around every light position, every bin's list ordered in
 // `shells` depth shells of the candidates' `near` bound (sort key = (base + bin) * shells + shell; `base_bins` = where light 0's
 // face 0 starts, in bins of `shells` keys).  A shadow ray walks only the shells up to the one its 0.99 r falls into (k_rt_trace2).
-void fill_light_frames(BinFrameDesc *frames, const RtFrame &f, int nlights, int cube_bins, int shells, uint32_t base_bins)
+// Light position k is origins[3 * (k + 1) ..]: row 0 is the camera's.
+void fill_light_frames(BinFrameDesc *frames, const float *origins, int nlights, int cube_bins, int shells, uint32_t base_bins)
 {
     memset(frames, 0, sizeof(BinFrameDesc) * 6 * nlights);
     for (int k = 0; k < nlights; k++) {
+        const float *lpos = origins + 3 * (k + 1);
         double dn = 0.0, df = 0.0;
-        const bool okr = shell_range(f.lpos[k], &dn, &df);
+        const bool okr = shell_range(lpos, &dn, &df);
         for (int face = 0; face < 6; face++) {
             BinFrameDesc &d = frames[k * 6 + face];
             const int ax = face >> 1;
@@ -180,7 +182,7 @@ void fill_light_frames(BinFrameDesc *frames, const RtFrame &f, int nlights, int 
             d.Pu[(ax + 1) % 3] = 1.0f;
             d.Pv[(ax + 2) % 3] = 1.0f;
             d.rw[ax] = d.P0[ax]; d.ru[(ax + 1) % 3] = 1.0f; d.rv[(ax + 2) % 3] = 1.0f;   // g = m*(s e_k + u e_k1 + v e_k2)
-            memcpy(d.S, f.lpos[k], 12);                       // light position k (jittered sample with soft shadows)
+            memcpy(d.S, lpos, 12);                            // light position k (jittered sample with soft shadows)
             d.dmax = 2.0f;
             d.ulo = -1.0f; d.vlo = -1.0f; d.du = 2.0f / (float)cube_bins; d.dv = 2.0f / (float)cube_bins;
             d.pad_lo = -3.814697265625e-06f; d.pad_hi = 3.814697265625e-06f;
@@ -233,7 +235,7 @@ int ensure_face_lists(RtScratch &S, int nlights)
 // frames of both streams read the tables -- whenever the scene, a light position or the grid differs from what is held.  (Lights
 // that just moved do not come here: binned_pass bins their cubes together with the camera frame, on the frame's own stream.)
 // C: the frame path's shared cube (g.lc) or the queries' (g.qrows.cube); either is read by the work of every stream.
-int light_cache_ensure(LightCache &C, RtScratch &S, const RtFrame &f, const float *origins, int nlights, int cube_bins, bool *built)
+int light_cache_ensure(LightCache &C, RtScratch &S, const float *origins, int nlights, int cube_bins, bool *built)
 {
     int rc;
     const uint64_t key = light_key_of(origins, nlights);
@@ -266,7 +268,7 @@ int light_cache_ensure(LightCache &C, RtScratch &S, const RtFrame &f, const floa
     C.shells = shells;
     if (nlights > 0) {
         BinFrameDesc frames[6 * MIRT_MAX_LIGHTS];
-        fill_light_frames(frames, f, nlights, cube_bins, shells, 0u);
+        fill_light_frames(frames, origins, nlights, cube_bins, shells, 0u);
         HIP_TRY(upload_small(C.d_frames, frames, sizeof(BinFrameDesc) * 6 * nlights, g.stream));
         HIP_TRY(upload_small(C.d_origins, origins, sizeof(float) * 3 * (1 + nlights), g.stream));
         // the lights' origin rows, and per face the triangles it can see (k_select_faces); the build's pair counter is zeroed on the way
@@ -361,7 +363,7 @@ constexpr int LIGHT_STABLE_FRAMES = 4;
 // the camera's pass, so that each is kept while only the other one's inputs change: a light key with the camera at rest
 // (raytracer.cpp:152-162, 385-537) re-bins the cubes and nothing else; the camera moving under lights that have not settled into the
 // shared cube yet re-bins the camera frame and nothing else.  *kept: the pass was not run.
-int transient_light_pass(RtScratch &L, const RtFrame &f, const float *origins, int nlights, int cube_bins, int tshells, uint32_t per_light, uint64_t lkey, bool *kept,
+int transient_light_pass(RtScratch &L, const float *origins, int nlights, int cube_bins, int tshells, uint32_t per_light, uint64_t lkey, bool *kept,
                          unsigned long long *zero_hits /* nullable: the frame's hit counters, zeroed by the pass's first launch when it runs */)
 {
     int rc;
@@ -396,7 +398,7 @@ int transient_light_pass(RtScratch &L, const RtFrame &f, const float *origins, i
     if (!L.d_frames) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&L.d_frames), sizeof(BinFrameDesc) * (6 * MIRT_MAX_LIGHTS) + sizeof(float) * 3 * (1 + MIRT_MAX_LIGHTS)));
     struct { BinFrameDesc frames[6 * MIRT_MAX_LIGHTS]; float origins[3 * (1 + MIRT_MAX_LIGHTS)]; } up;
     static_assert(sizeof(BinFrameDesc) % 4 == 0, "descriptors are uploaded as words");
-    fill_light_frames(up.frames, f, nlights, cube_bins, tshells, 0u);
+    fill_light_frames(up.frames, origins, nlights, cube_bins, tshells, 0u);
     float *d_origins = reinterpret_cast<float *>(L.d_frames + 6 * nlights);
     memcpy(reinterpret_cast<char *>(up.frames + 6 * nlights), origins, sizeof(float) * 3 * (1 + nlights));      // (right behind the descriptors in use)
     // (the same launch zeroes the pass's pair counter and the face lists' lengths)
@@ -426,7 +428,7 @@ int transient_light_pass(RtScratch &L, const RtFrame &f, const float *origins, i
 
 // The binning pass of a binned frame, up to the trace kernel: the light-cube tables (the shared cache, or this frame's own pass on
 // the side stream), then the camera's selection, binning and tile order -- or nothing at all when the stream still holds the pass.
-int binned_pass(const RtFrame &f, const mirt_view *view, RtScratch &S, RtScratch &L, const float *origins, int nlights, int y0, int y1, BinnedPass *bp)
+int binned_pass(const mirt_view *view, RtScratch &S, RtScratch &L, const float *origins, int nlights, int y0, int y1, BinnedPass *bp)
 {
     int rc;
     g.stats.mode_used = MIRT_RT_BINNED;
@@ -442,7 +444,7 @@ int binned_pass(const RtFrame &f, const mirt_view *view, RtScratch &S, RtScratch
     const bool transient = nlights > 0 && !fixed_grid && !cached && g.lc.stable < LIGHT_STABLE_FRAMES;
 
     k_begin(MIRT_K_BIN);
-    if (!transient && (rc = light_cache_ensure(g.lc, L, f, origins, nlights, fine_bins))) return rc;   // (in the light pass's scratch: the camera's tables stay)
+    if (!transient && (rc = light_cache_ensure(g.lc, L, origins, nlights, fine_bins))) return rc;   // (in the light pass's scratch: the camera's tables stay)
     const int cube_bins = transient ? CUBE_BINS_MIN : fine_bins;
 
     BinSet bs;
@@ -540,7 +542,7 @@ int binned_pass(const RtFrame &f, const mirt_view *view, RtScratch &S, RtScratch
             g.stream = ss.aux;
         }
         // (with the camera's pass kept nothing else runs in front of the trace kernel: the light pass's first launch zeroes the hit counters too)
-        rc = transient_light_pass(L, f, origins, nlights, cube_bins, tshells, per_light, lkey, &lights_kept, reuse ? g.d_hits : nullptr);
+        rc = transient_light_pass(L, origins, nlights, cube_bins, tshells, per_light, lkey, &lights_kept, reuse ? g.d_hits : nullptr);
         g.stream = main_stream;
         if (rc) return rc;
         if (forked) HIP_TRY(hipEventRecord(ss.ev_join, ss.aux));

@@ -199,6 +199,16 @@ struct DofPlanes {
     void release();
 };
 
+// The queries that walk a cube and keep statistics: DirectLight (mirt_get_query_stats) and origin fans (mirt_get_fan_stats).
+enum { QUERY_DIRECT_LIGHT = 0, QUERY_FAN = 1, QUERY_KINDS = 2 };
+// The last query of a kind: how it was answered, the stream it ran on and where its kernel's counters are (device; profiling on,
+// binned -- read once, query_get_stats).
+struct QueryStats {
+    mirt_query_stats s = {};
+    hipStream_t stream = nullptr;
+    const unsigned long long *dev = nullptr;
+};
+
 // What a DirectLight query (query.cpp) writes besides the caller's colours: the origin tables of its light positions, apart from
 // the stream's frame tables, so that a query between two frames disturbs nothing a kept binning pass counts on.
 struct QueryScratch {
@@ -207,8 +217,7 @@ struct QueryScratch {
     float *d_origins = nullptr;                  // (1 + MIRT_MAX_LIGHTS) x 3; row 0 (the camera's place) is unused
     uint32_t *d_flags = nullptr;                 // [0] = unsafe flag
     uint64_t rows_seen = 0;                      // the QueryRows::version this stream is already ordered behind (0 = none)
-    unsigned long long *d_stats = nullptr;       // QSTAT_WORDS counters of the stream's last binned DirectLight query (profiling on)
-    unsigned long long *d_fan_stats = nullptr;   // ... and of its last binned origin fan (mirt_intersect_from*)
+    unsigned long long *d_stats[QUERY_KINDS] = {};   // QSTAT_WORDS counters of the stream's last binned query of each kind (profiling on)
 
     void release();
 };
@@ -304,12 +313,7 @@ struct Ctx {
     LightCache lc;
     QueryRows qrows;
     int query_mode = MIRT_QUERY_AUTO;            // mirt_set_query_mode
-    mirt_query_stats qstats = {};                // the last DirectLight query: how it was answered (mirt_get_query_stats) ...
-    hipStream_t qstats_stream = nullptr;         // ... the stream it ran on ...
-    const unsigned long long *qstats_dev = nullptr;   // ... and where its kernel's counters are (device; profiling on, binned)
-    mirt_query_stats fstats = {};                // the same three for the last origin fan (mirt_get_fan_stats)
-    hipStream_t fstats_stream = nullptr;
-    const unsigned long long *fstats_dev = nullptr;
+    QueryStats qstats[QUERY_KINDS];              // the last DirectLight query and the last origin fan
     unsigned long long *d_hits = nullptr;        // the hit-counter buffer of the current ray-traced frame (one of its stream's d_hits)
     bool scene_finite = true;                    // all vertex coordinates below MIRT_SAFE_MAG
     uint64_t scene_version = 0;                  // bumped whenever the triangles change
@@ -401,14 +405,30 @@ struct BinnedPass {
 };
 // A light cube's tables in C for `nlights` light positions (origins[3 ..]) on a grid of cube_bins, built on g.stream in S -- a
 // stream's LIGHT scratch set, whose kept pass the build invalidates -- unless C holds them already; *built says which.
-int light_cache_ensure(LightCache &C, RtScratch &S, const RtFrame &f, const float *origins, int nlights, int cube_bins, bool *built = nullptr);
+int light_cache_ensure(LightCache &C, RtScratch &S, const float *origins, int nlights, int cube_bins, bool *built = nullptr);
 uint64_t light_key_of(const float *origins, int nlights);
 // Bins per face side of the cubes of `nlights` light positions under the frame path's rules (scene size, MIRT_CUBE_BINS, the
 // sort's key space); *fixed_grid: the environment fixed it.  light_keys_fit: one sort pass holds such a cube's keys at all.
 int light_cube_bins_for(int nlights, bool *fixed_grid);
 bool light_keys_fit(int nlights, int cube_bins);
-int binned_pass(const RtFrame &f, const mirt_view *view, RtScratch &S, RtScratch &L, const float *origins, int nlights, int y0, int y1, BinnedPass *bp);
+int binned_pass(const mirt_view *view, RtScratch &S, RtScratch &L, const float *origins, int nlights, int y0, int y1, BinnedPass *bp);
 int binned_trace(const RtFrame &f, RtScratch &S, RtScratch &L, const BinnedPass &bp);
+// The checks every call makes on its lights and the soft-shadow state; *light_positions: lights x soft-shadow samples, the
+// shadow-ray origins.  fill_light_positions: where each of them is (the light itself, or its jittered sample: randomPositions[k *
+// SOFT_SHADOWS_SAMPLES + i], raytracer.cpp:286), its share of the light's power, P = (color * intensity) / samples (:282, :296),
+// and its origin row -- lpos / lcol: npos rows; origins: rows 1 .. npos (row 0 is the camera's); any of the three may be NULL.
+inline int soft_samples() { return g.soft_samples > 1 ? g.soft_samples : 1; }
+int check_lights(const mirt_light *lights, int nlights, int *light_positions);
+void fill_light_positions(const mirt_light *lights, int npos, float (*lpos)[3], float (*lcol)[3], float *origins);
+// MIRT_RT_AUTO / MIRT_QUERY_AUTO bin nothing below this many triangles (MIRT_BIN_THRESHOLD; the tile kernel takes up to 64).
+int auto_bin_threshold();
+// A start point -- a camera, a light position, a fan's origin -- inside the filter's proven range (rt_query.hpp; false for NaN).
+inline bool start_in_filter_range(const float *p)
+{
+    return fabsf(p[0]) < MIRT_QUERY_START_MAX && fabsf(p[1]) < MIRT_QUERY_START_MAX && fabsf(p[2]) < MIRT_QUERY_START_MAX;
+}
+// LDS of a kernel that sweeps the scene's 48-byte rows (OriginRow, QueryRow) in chunks of RT_CHUNK_ROWS.
+inline size_t sweep_lds_bytes() { return (size_t)(g.n < RT_CHUNK_ROWS ? g.n : RT_CHUNK_ROWS) * sizeof(OriginRow); }
 // Would rt_enqueue bin the WHOLE frame of this view (mode, scene size, operands in range, frame size)?  The same answer on every rank.
 bool rt_bins_whole_frame(const mirt_view *view, const mirt_light *lights, int nlights, int mode);
 // The cost histogram of a view's whole frame and nothing else, on the current stream (render_sharded).

@@ -83,24 +83,77 @@ int query_intersect(const void *d_rays, int nrays, void *d_hits)
     if ((long)nrays <= query_wave_rays()) {
         hipLaunchKernelGGL(k_query_closest_wave, dim3((unsigned)((nrays + 3) / 4)), dim3(256), 0, g.stream, q);
     } else {
-        const size_t lds = (size_t)(g.n < RT_CHUNK_ROWS ? g.n : RT_CHUNK_ROWS) * sizeof(QueryRow);
-        hipLaunchKernelGGL(k_query_closest<QUERY_P>, dim3((unsigned)((nrays + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), lds, g.stream, q);
+        hipLaunchKernelGGL(k_query_closest<QUERY_P>, dim3((unsigned)((nrays + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), sweep_lds_bytes(), g.stream, q);
     }
     HIP_TRY(hipGetLastError());
     return MIRT_OK;
 }
 
-// The checks rt_enqueue makes on the lights and the soft-shadow state, with its messages.
-static int check_lights(const mirt_light *lights, int nlights, int *light_positions)
+// ---- what the queries that walk a cube share: its view, their statistics ------------------------------------------------------
+
+// What a walk kernel reads of the cube C.  A lane with no row left still loads row 0 each step and ignores it, and a cube without a
+// single pair has no row table: the loads are pointed at the cube's origin table then, which always has a row.  (The trace
+// kernel's version of this rule: ADVICE.md.)
+static CubeView cube_view(const LightCache &C)
 {
-    if (nlights < 0 || nlights > MIRT_MAX_LIGHTS) return fail(MIRT_ERR_INVALID_ARGUMENT, "nlights %d out of range [0,%d]", nlights, MIRT_MAX_LIGHTS);
-    if (nlights > 0 && !lights) return fail(MIRT_ERR_INVALID_ARGUMENT, "lights must not be NULL when nlights > 0");
-    const int samples = g.soft_samples > 1 ? g.soft_samples : 1;
-    *light_positions = nlights * samples;                    // shadow-ray origins
-    if (*light_positions > MIRT_MAX_LIGHTS)
-        return fail(MIRT_ERR_INVALID_ARGUMENT, "%d lights x %d soft-shadow samples exceed %d light positions", nlights, samples, MIRT_MAX_LIGHTS);
-    if (samples > 1 && *light_positions > g.soft_npos)
-        return fail(MIRT_ERR_INVALID_ARGUMENT, "%d jittered positions needed, %d were set (mirt_set_soft_shadows)", *light_positions, g.soft_npos);
+    CubeView v;
+    v.light_off = C.d_off;
+    v.light_rows = C.nrows ? C.d_rows : C.d_light_tab;
+    v.light_tri = C.d_row_tri;
+    v.light_frames = C.d_frames;
+    v.cube_bins = C.cube_bins;
+    v.shells = C.shells;
+    return v;
+}
+
+// A query of `kind` starts on the current stream: its statistics begin afresh.
+static QueryStats &stats_begin(int kind, bool binned)
+{
+    QueryStats &Q = g.qstats[kind];
+    memset(&Q.s, 0, sizeof Q.s);
+    Q.s.mode_used = binned ? MIRT_QUERY_BINNED : MIRT_QUERY_BRUTE;
+    Q.stream = g.stream;
+    Q.dev = nullptr;
+    return Q;
+}
+// ... and the cube its walk takes, noted.
+static void stats_cube(QueryStats &Q, const LightCache &C, int source)
+{
+    Q.s.cube_source = source;
+    Q.s.cube_bins = C.cube_bins;
+    Q.s.shells = C.shells;
+}
+
+// With profiling on, the stream's counters of `kind` zeroed on the stream and noted for query_get_stats: *counters is what the
+// STATS instantiation of the walk kernel counts into, NULL says to launch the plain one.
+static int stats_arm(int kind, unsigned long long **counters)
+{
+    *counters = nullptr;
+    if (!g.profiling) return MIRT_OK;
+    unsigned long long *&d = g.cur().query.d_stats[kind];
+    if (!d) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(unsigned long long) * QSTAT_WORDS));
+    HIP_TRY(hipMemsetAsync(d, 0, sizeof(unsigned long long) * QSTAT_WORDS, g.stream));
+    g.qstats[kind].dev = *counters = d;
+    return MIRT_OK;
+}
+
+int query_get_stats(int kind, mirt_query_stats *out)
+{
+    int rc;
+    if ((rc = need_init())) return rc;
+    if (!out) return fail(MIRT_ERR_INVALID_ARGUMENT, "out must not be NULL");
+    QueryStats &Q = g.qstats[kind];
+    if (Q.stream) HIP_TRY(hipStreamSynchronize(Q.stream));
+    if (Q.dev) {
+        unsigned long long c[QSTAT_WORDS] = {};
+        HIP_TRY(hipMemcpy(c, Q.dev, sizeof c, hipMemcpyDeviceToHost));
+        Q.s.shadow_rays = c[QSTAT_SHADOW_RAYS];
+        Q.s.candidates = c[QSTAT_CANDIDATES];
+        Q.s.tests = c[QSTAT_TESTS];
+        Q.s.fallback_records = c[QSTAT_FALLBACK];
+        Q.dev = nullptr;                         // (read once: a later query of the kind on the stream zeroes the words again)
+    }
+    *out = Q.s;
     return MIRT_OK;
 }
 
@@ -112,8 +165,7 @@ static int check_lights(const mirt_light *lights, int nlights, int *light_positi
 // tools/ray_query_bench.py sweeps the record count for the crossing (profiles/ray_query_bench.txt).
 static bool auto_bins(int nhits, int npos)
 {
-    static const int auto_threshold = (int)env_int("MIRT_BIN_THRESHOLD", 65);
-    return g.n >= auto_threshold && (long long)nhits * npos * g.n >= 40000000LL;
+    return g.n >= auto_bin_threshold() && (long long)nhits * npos * g.n >= 40000000LL;
 }
 
 // Origin tables of the query's own for origins[3 ..] (npos positions) on the current stream, and their `unsafe` flag: k_prep_origin
@@ -150,8 +202,7 @@ static int direct_light_brute(QueryLightFrame &q, const float *origins, int npos
     if ((rc = query_origin_tables(origins, npos, safe))) return rc;
     q.f.light_tab = g.cur().query.d_light_tab;
     q.f.unsafe = g.cur().query.d_flags;
-    const size_t lds = (size_t)(g.n < RT_CHUNK_ROWS ? g.n : RT_CHUNK_ROWS) * sizeof(OriginRow);
-    hipLaunchKernelGGL(k_query_direct_light<QUERY_P>, dim3((unsigned)((q.nhits + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), lds, g.stream, q);
+    hipLaunchKernelGGL(k_query_direct_light<QUERY_P>, dim3((unsigned)((q.nhits + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), sweep_lds_bytes(), g.stream, q);
     HIP_TRY(hipGetLastError());
     return MIRT_OK;
 }
@@ -159,30 +210,17 @@ static int direct_light_brute(QueryLightFrame &q, const float *origins, int npos
 // The binned kernel over the cube C (the frame path's, or the queries' own after light_cache_ensure).
 static int direct_light_binned(QueryLightFrame &q, const LightCache &C)
 {
-    QueryScratch &S = g.cur().query;
+    int rc;
     QueryBinnedFrame b;
     memset(&b, 0, sizeof b);
     b.q = q;
     b.q.f.light_tab = C.d_light_tab;             // (the records the bins do not cover sweep the cube's own origin table)
     b.q.f.unsafe = nullptr;
-    b.light_off = C.d_off;
-    // (a lane with no row left still loads row 0 each step and ignores it: a cube without a single pair has no row table, so the
-    // loads are pointed at the origin table, which always has a row)
-    b.light_rows = C.nrows ? C.d_rows : C.d_light_tab;
-    b.light_tri = C.d_row_tri;
-    b.light_frames = C.d_frames;
-    b.cube_bins = C.cube_bins;
-    b.shells = C.shells;
+    b.cube = cube_view(C);
+    if ((rc = stats_arm(QUERY_DIRECT_LIGHT, &b.stats))) return rc;
     const dim3 grid((unsigned)((q.nhits + 256 * QUERY_BIN_P - 1) / (256 * QUERY_BIN_P)));
-    if (g.profiling) {
-        if (!S.d_stats) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_stats), sizeof(unsigned long long) * QSTAT_WORDS));
-        HIP_TRY(hipMemsetAsync(S.d_stats, 0, sizeof(unsigned long long) * QSTAT_WORDS, g.stream));
-        b.stats = S.d_stats;
-        g.qstats_dev = S.d_stats;
-        hipLaunchKernelGGL((k_query_direct_light_binned<QUERY_BIN_P, true>), grid, dim3(256), 0, g.stream, b);
-    } else {
-        hipLaunchKernelGGL((k_query_direct_light_binned<QUERY_BIN_P, false>), grid, dim3(256), 0, g.stream, b);
-    }
+    if (b.stats) hipLaunchKernelGGL((k_query_direct_light_binned<QUERY_BIN_P, true>), grid, dim3(256), 0, g.stream, b);
+    else hipLaunchKernelGGL((k_query_direct_light_binned<QUERY_BIN_P, false>), grid, dim3(256), 0, g.stream, b);
     HIP_TRY(hipGetLastError());
     return MIRT_OK;
 }
@@ -201,22 +239,12 @@ int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, 
     f.tris15 = g.d_tris;
     f.n = g.n;
     // the light positions the shadow rays start from and their share of the light's power, as a frame sets them up
-    // (rt_frame.cpp: make_rt_frame; raytracer.cpp:282-296)
-    const int samples = g.soft_samples > 1 ? g.soft_samples : 1;
     f.nlights = npos;
-    f.samples = samples;
+    f.samples = soft_samples();
     float origins[(1 + MIRT_MAX_LIGHTS) * 3] = {};
+    fill_light_positions(lights, npos, f.lpos, f.lcol, origins);
     bool safe = g.scene_finite;
-    for (int j = 0; j < npos; j++) {
-        const int k = j / samples;
-        const float *pos = samples > 1 ? g.soft_pos + 3 * j : lights[k].pos;
-        memcpy(f.lpos[j], pos, 12);
-        memcpy(origins + 3 * (j + 1), pos, 12);
-        for (int c = 0; c < 3; c++) {
-            f.lcol[j][c] = (lights[k].color[c] * lights[k].intensity) / (float)samples;
-            if (!(fabsf(pos[c]) < MIRT_QUERY_START_MAX)) safe = false;      // a shadow ray's start (rt_frame.cpp: operands_safe)
-        }
-    }
+    for (int j = 0; j < npos; j++) safe = safe && start_in_filter_range(f.lpos[j]);    // a shadow ray's start (rt_frame.cpp: operands_safe)
     q.hits = static_cast<const uint32_t *>(d_hits);
     q.nhits = nhits;
     q.rgb = static_cast<float *>(d_rgb);
@@ -236,10 +264,7 @@ int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, 
                         (g.query_mode == MIRT_QUERY_BINNED || frames_cube || own_cube || auto_bins(nhits, npos));
 
     stream_begin();
-    memset(&g.qstats, 0, sizeof g.qstats);
-    g.qstats.mode_used = binned ? MIRT_QUERY_BINNED : MIRT_QUERY_BRUTE;
-    g.qstats_stream = g.stream;
-    g.qstats_dev = nullptr;
+    QueryStats &stats = stats_begin(QUERY_DIRECT_LIGHT, binned);
     if (!binned) return direct_light_brute(q, origins, npos, safe);
 
     const LightCache *C = &g.lc;
@@ -247,13 +272,11 @@ int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, 
     if (!frames_cube) {
         // (in the stream's LIGHT scratch set, as the shared cube's build: the pass that set kept for moving lights is invalidated there)
         bool built = false;
-        if ((rc = light_cache_ensure(own, g.cur().rt_lt, f, origins, npos, cube_bins, &built))) return rc;
+        if ((rc = light_cache_ensure(own, g.cur().rt_lt, origins, npos, cube_bins, &built))) return rc;
         C = &own;
         source = built ? 1 : 2;
     }
-    g.qstats.cube_source = source;
-    g.qstats.cube_bins = C->cube_bins;
-    g.qstats.shells = C->shells;
+    stats_cube(stats, *C, source);
     return direct_light_binned(q, *C);
 }
 
@@ -268,8 +291,7 @@ int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, 
 constexpr int FAN_AUTO_TRIANGLES = 2000;
 static bool auto_bins_fan(int nrays)
 {
-    static const int auto_threshold = (int)env_int("MIRT_BIN_THRESHOLD", 65);
-    return g.n >= auto_threshold && (g.n >= FAN_AUTO_TRIANGLES || (long long)nrays * g.n >= 40000000LL);
+    return g.n >= auto_bin_threshold() && (g.n >= FAN_AUTO_TRIANGLES || (long long)nrays * g.n >= 40000000LL);
 }
 
 int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, void *d_hits)
@@ -290,9 +312,7 @@ int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, vo
     q.hits = static_cast<uint32_t *>(d_hits);
     float origins[6] = {};
     memcpy(origins + 3, origin, 12);
-    bool safe = g.scene_finite;
-    for (int c = 0; c < 3; c++)
-        if (!(fabsf(origin[c]) < MIRT_QUERY_START_MAX)) safe = false;       // the rays' start (rt_frame.cpp: operands_safe)
+    const bool safe = g.scene_finite && start_in_filter_range(origin);     // the rays' start (rt_frame.cpp: operands_safe)
 
     // Binned or brute, as a DirectLight query decides it: never what the frame path would not bin, whatever the mode.
     bool fixed_grid = false;
@@ -303,72 +323,28 @@ int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, vo
     const bool binned = may_bin && g.query_mode != MIRT_QUERY_BRUTE && (g.query_mode == MIRT_QUERY_BINNED || held || auto_bins_fan(nrays));
 
     stream_begin();
-    QueryScratch &S = g.cur().query;
-    memset(&g.fstats, 0, sizeof g.fstats);
-    g.fstats.mode_used = binned ? MIRT_QUERY_BINNED : MIRT_QUERY_BRUTE;
-    g.fstats_stream = g.stream;
-    g.fstats_dev = nullptr;
+    QueryStats &stats = stats_begin(QUERY_FAN, binned);
     if (!binned) {
+        QueryScratch &S = g.cur().query;
         if ((rc = query_origin_tables(origins, 1, safe))) return rc;
         q.tab = S.d_light_tab;
         q.unsafe = S.d_flags;
-        const size_t lds = (size_t)(g.n < RT_CHUNK_ROWS ? g.n : RT_CHUNK_ROWS) * sizeof(OriginRow);
-        hipLaunchKernelGGL(k_query_fan<QUERY_P>, dim3((unsigned)((nrays + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), lds, g.stream, q);
+        hipLaunchKernelGGL(k_query_fan<QUERY_P>, dim3((unsigned)((nrays + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), sweep_lds_bytes(), g.stream, q);
         HIP_TRY(hipGetLastError());
         return MIRT_OK;
     }
 
-    // (the cube's build reads of the frame only the scene and the position; in the stream's LIGHT scratch set, as the shared cube's)
-    RtFrame f;
-    memset(&f, 0, sizeof f);
-    f.tris15 = g.d_tris;
-    f.n = g.n;
-    f.nlights = 1;
-    f.samples = 1;
-    memcpy(f.lpos[0], origin, 12);
+    // (in the stream's LIGHT scratch set, as the shared cube's build)
     bool built = false;
-    if ((rc = light_cache_ensure(C, g.cur().rt_lt, f, origins, 1, cube_bins, &built))) return rc;
-    g.fstats.cube_source = built ? 1 : 2;
-    g.fstats.cube_bins = C.cube_bins;
-    g.fstats.shells = C.shells;
+    if ((rc = light_cache_ensure(C, g.cur().rt_lt, origins, 1, cube_bins, &built))) return rc;
+    stats_cube(stats, C, built ? 1 : 2);
     q.tab = C.d_light_tab;
-    q.light_off = C.d_off;
-    // (a cube without a single pair has no row table: the idle loads are pointed at the origin table, which always has a row)
-    q.light_rows = C.nrows ? C.d_rows : C.d_light_tab;
-    q.light_tri = C.d_row_tri;
-    q.light_frames = C.d_frames;
-    q.cube_bins = C.cube_bins;
-    q.shells = C.shells;
+    q.cube = cube_view(C);
+    if ((rc = stats_arm(QUERY_FAN, &q.stats))) return rc;
     const dim3 grid((unsigned)((nrays + 255) / 256));
-    if (g.profiling) {
-        if (!S.d_fan_stats) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_fan_stats), sizeof(unsigned long long) * QSTAT_WORDS));
-        HIP_TRY(hipMemsetAsync(S.d_fan_stats, 0, sizeof(unsigned long long) * QSTAT_WORDS, g.stream));
-        q.stats = S.d_fan_stats;
-        g.fstats_dev = S.d_fan_stats;
-        hipLaunchKernelGGL(k_query_fan_binned<true>, grid, dim3(256), 0, g.stream, q);
-    } else {
-        hipLaunchKernelGGL(k_query_fan_binned<false>, grid, dim3(256), 0, g.stream, q);
-    }
+    if (q.stats) hipLaunchKernelGGL(k_query_fan_binned<true>, grid, dim3(256), 0, g.stream, q);
+    else hipLaunchKernelGGL(k_query_fan_binned<false>, grid, dim3(256), 0, g.stream, q);
     HIP_TRY(hipGetLastError());
-    return MIRT_OK;
-}
-
-int query_get_fan_stats(mirt_query_stats *out)
-{
-    int rc;
-    if ((rc = need_init())) return rc;
-    if (!out) return fail(MIRT_ERR_INVALID_ARGUMENT, "out must not be NULL");
-    if (g.fstats_stream) HIP_TRY(hipStreamSynchronize(g.fstats_stream));
-    if (g.fstats_dev) {
-        unsigned long long c[QSTAT_WORDS] = {};
-        HIP_TRY(hipMemcpy(c, g.fstats_dev, sizeof c, hipMemcpyDeviceToHost));
-        g.fstats.shadow_rays = c[QSTAT_SHADOW_RAYS];
-        g.fstats.candidates = c[QSTAT_CANDIDATES];
-        g.fstats.tests = c[QSTAT_TESTS];
-        g.fstats.fallback_records = c[QSTAT_FALLBACK];
-        g.fstats_dev = nullptr;                  // (read once: a later fan on the stream zeroes the words again)
-    }
-    *out = g.fstats;
     return MIRT_OK;
 }
 
@@ -379,25 +355,6 @@ int query_set_mode(int mode)
     if (mode != MIRT_QUERY_AUTO && mode != MIRT_QUERY_BRUTE && mode != MIRT_QUERY_BINNED)
         return fail(MIRT_ERR_INVALID_ARGUMENT, "unknown query mode %d", mode);
     g.query_mode = mode;
-    return MIRT_OK;
-}
-
-int query_get_stats(mirt_query_stats *out)
-{
-    int rc;
-    if ((rc = need_init())) return rc;
-    if (!out) return fail(MIRT_ERR_INVALID_ARGUMENT, "out must not be NULL");
-    if (g.qstats_stream) HIP_TRY(hipStreamSynchronize(g.qstats_stream));
-    if (g.qstats_dev) {
-        unsigned long long c[QSTAT_WORDS] = {};
-        HIP_TRY(hipMemcpy(c, g.qstats_dev, sizeof c, hipMemcpyDeviceToHost));
-        g.qstats.shadow_rays = c[QSTAT_SHADOW_RAYS];
-        g.qstats.candidates = c[QSTAT_CANDIDATES];
-        g.qstats.tests = c[QSTAT_TESTS];
-        g.qstats.fallback_records = c[QSTAT_FALLBACK];
-        g.qstats_dev = nullptr;                  // (read once: a later query on the stream zeroes the words again)
-    }
-    *out = g.qstats;
     return MIRT_OK;
 }
 
@@ -417,6 +374,23 @@ static int query_staging(size_t count)
     return MIRT_OK;
 }
 
+// One host-buffer entry point around its device form `call`: every `in` array goes to its staging array on the stream the call
+// will take, every `out` array comes back on the stream it took, and the host waits for that stream.
+struct HostArray { void *host; void *staging; size_t bytes; bool in, out; };
+template <int N, class Call>
+static int with_host_arrays(const HostArray (&a)[N], Call call)
+{
+    int rc;
+    hipStream_t st = g.streams[next_si()].stream;            // the stream the query below will take
+    for (const HostArray &x : a)
+        if (x.in) HIP_TRY(hipMemcpyAsync(x.staging, x.host, x.bytes, hipMemcpyHostToDevice, st));
+    if ((rc = call())) return rc;
+    for (const HostArray &x : a)
+        if (x.out) HIP_TRY(hipMemcpyAsync(x.host, x.staging, x.bytes, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return MIRT_OK;
+}
+
 int query_intersect_host(const mirt_ray *rays, int nrays, mirt_hit *hits)
 {
     int rc;
@@ -425,13 +399,9 @@ int query_intersect_host(const mirt_ray *rays, int nrays, mirt_hit *hits)
     if ((rc = need_scene())) return rc;
     if ((rc = query_staging((size_t)nrays))) return rc;
     QueryRows &Q = g.qrows;
-    hipStream_t st = g.streams[next_si()].stream;            // the stream the query below will take
-    HIP_TRY(hipMemcpyAsync(Q.d_rays, rays, (size_t)nrays * sizeof(mirt_ray), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(Q.d_hits, hits, (size_t)nrays * sizeof(mirt_hit), hipMemcpyHostToDevice, st));
-    if ((rc = query_intersect(Q.d_rays, nrays, Q.d_hits))) return rc;
-    HIP_TRY(hipMemcpyAsync(hits, Q.d_hits, (size_t)nrays * sizeof(mirt_hit), hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return MIRT_OK;
+    const HostArray a[] = { { (void *)rays, Q.d_rays, (size_t)nrays * sizeof(mirt_ray), true, false },
+                            { hits, Q.d_hits, (size_t)nrays * sizeof(mirt_hit), true, true } };
+    return with_host_arrays(a, [&] { return query_intersect(Q.d_rays, nrays, Q.d_hits); });
 }
 
 int query_direct_light_host(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, float *out_rgb)
@@ -443,12 +413,9 @@ int query_direct_light_host(const mirt_hit *hits, int nhits, const mirt_light *l
     if ((rc = need_scene())) return rc;
     if ((rc = query_staging((size_t)nhits))) return rc;
     QueryRows &Q = g.qrows;
-    hipStream_t st = g.streams[next_si()].stream;
-    HIP_TRY(hipMemcpyAsync(Q.d_hits, hits, (size_t)nhits * sizeof(mirt_hit), hipMemcpyHostToDevice, st));
-    if ((rc = query_direct_light(Q.d_hits, nhits, lights, nlights, Q.d_rgb))) return rc;
-    HIP_TRY(hipMemcpyAsync(out_rgb, Q.d_rgb, (size_t)nhits * 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return MIRT_OK;
+    const HostArray a[] = { { (void *)hits, Q.d_hits, (size_t)nhits * sizeof(mirt_hit), true, false },
+                            { out_rgb, Q.d_rgb, (size_t)nhits * 3 * sizeof(float), false, true } };
+    return with_host_arrays(a, [&] { return query_direct_light(Q.d_hits, nhits, lights, nlights, Q.d_rgb); });
 }
 
 int query_intersect_from_host(const float *origin, const float *dirs3, int nrays, mirt_hit *hits)
@@ -460,19 +427,15 @@ int query_intersect_from_host(const float *origin, const float *dirs3, int nrays
     if ((rc = need_scene())) return rc;
     if ((rc = query_staging((size_t)nrays))) return rc;
     QueryRows &Q = g.qrows;
-    hipStream_t st = g.streams[next_si()].stream;            // the stream the query below will take
-    HIP_TRY(hipMemcpyAsync(Q.d_dirs, dirs3, (size_t)nrays * 3 * sizeof(float), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(Q.d_hits, hits, (size_t)nrays * sizeof(mirt_hit), hipMemcpyHostToDevice, st));
-    if ((rc = query_intersect_from(origin, Q.d_dirs, nrays, Q.d_hits))) return rc;
-    HIP_TRY(hipMemcpyAsync(hits, Q.d_hits, (size_t)nrays * sizeof(mirt_hit), hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return MIRT_OK;
+    const HostArray a[] = { { (void *)dirs3, Q.d_dirs, (size_t)nrays * 3 * sizeof(float), true, false },
+                            { hits, Q.d_hits, (size_t)nrays * sizeof(mirt_hit), true, true } };
+    return with_host_arrays(a, [&] { return query_intersect_from(origin, Q.d_dirs, nrays, Q.d_hits); });
 }
 
 }  // namespace mirt
 
 extern "C" int mirt_intersect_from(const float origin[3], const float *dirs3, int nrays, mirt_hit *hits) { return mirt::query_intersect_from_host(origin, dirs3, nrays, hits); }
 extern "C" int mirt_intersect_from_device(const float origin[3], const void *d_dirs3, int nrays, void *d_hits) { return mirt::query_intersect_from(origin, d_dirs3, nrays, d_hits); }
-extern "C" int mirt_get_fan_stats(mirt_query_stats *out) { return mirt::query_get_fan_stats(out); }
+extern "C" int mirt_get_fan_stats(mirt_query_stats *out) { return mirt::query_get_stats(mirt::QUERY_FAN, out); }
 extern "C" int mirt_set_query_mode(int mode) { return mirt::query_set_mode(mode); }
-extern "C" int mirt_get_query_stats(mirt_query_stats *out) { return mirt::query_get_stats(out); }
+extern "C" int mirt_get_query_stats(mirt_query_stats *out) { return mirt::query_get_stats(mirt::QUERY_DIRECT_LIGHT, out); }

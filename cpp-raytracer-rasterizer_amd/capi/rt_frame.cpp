@@ -55,6 +55,33 @@ BinFrameDesc make_camera_frame(const mirt_view *view, int y0, int y1, int aa)
     return c;
 }
 
+int check_lights(const mirt_light *lights, int nlights, int *light_positions)
+{
+    if (nlights < 0 || nlights > MIRT_MAX_LIGHTS) return fail(MIRT_ERR_INVALID_ARGUMENT, "nlights %d out of range [0,%d]", nlights, MIRT_MAX_LIGHTS);
+    if (nlights > 0 && !lights) return fail(MIRT_ERR_INVALID_ARGUMENT, "lights must not be NULL when nlights > 0");
+    const int samples = soft_samples();
+    *light_positions = nlights * samples;
+    if (*light_positions > MIRT_MAX_LIGHTS)
+        return fail(MIRT_ERR_INVALID_ARGUMENT, "%d lights x %d soft-shadow samples exceed %d light positions", nlights, samples, MIRT_MAX_LIGHTS);
+    if (samples > 1 && *light_positions > g.soft_npos)
+        return fail(MIRT_ERR_INVALID_ARGUMENT, "%d jittered positions needed, %d were set (mirt_set_soft_shadows)", *light_positions, g.soft_npos);
+    return MIRT_OK;
+}
+
+void fill_light_positions(const mirt_light *lights, int npos, float (*lpos)[3], float (*lcol)[3], float *origins)
+{
+    const int samples = soft_samples();
+    for (int j = 0; j < npos; j++) {
+        const mirt_light &l = lights[j / samples];
+        const float *pos = samples > 1 ? g.soft_pos + 3 * j : l.pos;
+        if (lpos) memcpy(lpos[j], pos, 12);
+        if (origins) memcpy(origins + 3 * (j + 1), pos, 12);
+        // uniform per light, so the division happens once here (host float division is the same IEEE operation the kernels
+        // would run per pixel)
+        if (lcol) for (int c = 0; c < 3; c++) lcol[j][c] = (l.color[c] * l.intensity) / (float)samples;
+    }
+}
+
 // The frame's parameter block, apart from what its stream supplies (hit counters, origin tables); `origins` receives the camera
 // and the light positions the shadow rays start from (1 + f.nlights rows of 3).
 static void make_rt_frame(RtFrame &f, float *origins, const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect,
@@ -68,24 +95,12 @@ static void make_rt_frame(RtFrame &f, float *origins, const mirt_view *view, con
     f.focal = view->focal;
     f.W = view->width;
     f.H = view->height;
-    // Light positions the shadow rays start from: the lights themselves, or with soft shadows `samples` jittered
-    // positions per light (randomPositions[k*SOFT_SHADOWS_SAMPLES + i], raytracer.cpp:286), each carrying the
-    // light's colour*intensity (:282) which light_term() divides by samples (:296).
-    const int samples = g.soft_samples > 1 ? g.soft_samples : 1;
-    const int npos = nlights * samples;
+    const int npos = nlights * soft_samples();
     f.nlights = npos;
-    f.samples = samples;
+    f.samples = soft_samples();
     f.aa = g.aa > 1 ? g.aa : 1;
     memcpy(origins, view->pos, 12);
-    for (int j = 0; j < npos; j++) {
-        const int k = j / samples;
-        const float *pos = samples > 1 ? g.soft_pos + 3 * j : lights[k].pos;
-        memcpy(f.lpos[j], pos, 12);
-        memcpy(origins + 3 * (j + 1), pos, 12);
-        // P = (color * intensity) / samples (raytracer.cpp:282, :296): uniform per light, so the division happens once here
-        // (host float division is the same IEEE operation the kernels would run per pixel)
-        for (int c = 0; c < 3; c++) f.lcol[j][c] = (lights[k].color[c] * lights[k].intensity) / (float)f.samples;
-    }
+    fill_light_positions(lights, npos, f.lpos, f.lcol, origins);
     f.lights_in_range = 1;
     for (int j = 0; j < npos; j++) f.lights_in_range &= light_colour_in_range(f.lcol[j]) ? 1 : 0;
     memcpy(f.indirect, indirect, 12);
@@ -121,22 +136,26 @@ static bool operands_safe(const mirt_view *view, const float *origins, int npos)
 // MIRT_RT_AUTO bins when the scene is beyond the tile kernel (65 triangles or more) and the brute-force work, pixels x
 // triangles, is above ~4e7: binning + sorting costs ~40 us whatever the scene, brute force ~7.5e-10 ms per pixel-triangle
 // (tools/threshold_sweep.py at 1080p: 65 triangles 0.099 vs 0.043 ms, 300: 0.47 vs 0.079, 800: 1.13 vs 0.097).
+int auto_bin_threshold()
+{
+    static const int v = (int)env_int("MIRT_BIN_THRESHOLD", 65);
+    return v;
+}
 static bool mode_bins(const mirt_view *view, int mode, int rows)
 {
-    static const int auto_threshold = (int)env_int("MIRT_BIN_THRESHOLD", 65);
     return (mode == MIRT_RT_BINNED) ||
-           (mode == MIRT_RT_AUTO && g.n >= auto_threshold && (long long)view->width * rows > 4096 &&
+           (mode == MIRT_RT_AUTO && g.n >= auto_bin_threshold() && (long long)view->width * rows > 4096 &&
             (long long)view->width * rows * g.n >= 40000000LL);
 }
 
 bool rt_bins_whole_frame(const mirt_view *view, const mirt_light *lights, int nlights, int mode)
 {
-    const int samples = g.soft_samples > 1 ? g.soft_samples : 1;
-    const int npos = nlights * samples;
+    const int samples = soft_samples(), npos = nlights * samples;
+    // (check_lights' conditions, without its messages: the question is asked, not a frame)
     if (!view || nlights < 0 || (nlights && !lights) || npos > MIRT_MAX_LIGHTS || (samples > 1 && npos > g.soft_npos)) return false;
     float origins[(1 + MIRT_MAX_LIGHTS) * 3];
     memcpy(origins, view->pos, 12);
-    for (int j = 0; j < npos; j++) memcpy(origins + 3 * (j + 1), samples > 1 ? g.soft_pos + 3 * j : lights[j / samples].pos, 12);
+    fill_light_positions(lights, npos, nullptr, nullptr, origins);
     return mode_bins(view, mode, view->height) && operands_safe(view, origins, npos) && frame_fits_binning(view->width, view->height);
 }
 
@@ -212,8 +231,7 @@ static int rt_dispatch_brute(RtFrame &f, const mirt_view *view, RtScratch &S, co
         const long long nrays = (long long)view->width * rows;
         hipLaunchKernelGGL(k_rt_wave, dim3((unsigned)((nrays + 3) / 4)), dim3(256), 0, g.stream, f);
     } else {
-        const size_t lds = (size_t)(g.n < RT_CHUNK_ROWS ? g.n : RT_CHUNK_ROWS) * sizeof(OriginRow);
-        hipLaunchKernelGGL(k_rt_brute<2>, dim3((view->width + 127) / 128, (rows + 3) / 4), dim3(256), lds, g.stream, f);
+        hipLaunchKernelGGL(k_rt_brute<2>, dim3((view->width + 127) / 128, (rows + 3) / 4), dim3(256), sweep_lds_bytes(), g.stream, f);
     }
     k_end(MIRT_K_TRACE);
     HIP_TRY(hipGetLastError());
@@ -227,12 +245,8 @@ int rt_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, con
     int rc;
     if ((rc = check_frame_args(view, lights, nlights, indirect, d_xrgb, pitch_bytes, true, y0, y1))) return rc;
     if (mode != MIRT_RT_AUTO && mode != MIRT_RT_BRUTE && mode != MIRT_RT_BINNED) return fail(MIRT_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
-    const int samples = g.soft_samples > 1 ? g.soft_samples : 1;
-    const int light_positions = nlights * samples;           // shadow-ray origins
-    if (light_positions > MIRT_MAX_LIGHTS)
-        return fail(MIRT_ERR_INVALID_ARGUMENT, "%d lights x %d soft-shadow samples exceed %d light positions", nlights, samples, MIRT_MAX_LIGHTS);
-    if (samples > 1 && light_positions > g.soft_npos)
-        return fail(MIRT_ERR_INVALID_ARGUMENT, "%d jittered positions needed, %d were set (mirt_set_soft_shadows)", light_positions, g.soft_npos);
+    int light_positions = 0;                                 // shadow-ray origins
+    if ((rc = check_lights(lights, nlights, &light_positions))) return rc;
 
     RtFrame f;
     float origins[(1 + MIRT_MAX_LIGHTS) * 3];
@@ -288,7 +302,7 @@ int rt_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, con
 
     if (binned) {
         BinnedPass bp;
-        if ((rc = binned_pass(f, view, S, ss.rt_lt, origins, nlights, y0, y1, &bp)) || (rc = binned_trace(f, S, ss.rt_lt, bp))) return rc;
+        if ((rc = binned_pass(view, S, ss.rt_lt, origins, nlights, y0, y1, &bp)) || (rc = binned_trace(f, S, ss.rt_lt, bp))) return rc;
     } else if ((rc = rt_dispatch_brute(f, view, S, origins, nlights, safe, tile_path, tile_lds))) {
         return rc;
     }

@@ -93,7 +93,7 @@ void RtScratch::release()
 
 void QueryScratch::release()
 {
-    for (void *p : { (void *)d_light_tab, (void *)d_origins, (void *)d_flags, (void *)d_stats, (void *)d_fan_stats }) if (p) (void)hipFree(p);
+    for (void *p : { (void *)d_light_tab, (void *)d_origins, (void *)d_flags, (void *)d_stats[QUERY_DIRECT_LIGHT], (void *)d_stats[QUERY_FAN] }) if (p) (void)hipFree(p);
     *this = QueryScratch();
 }
 

@@ -73,12 +73,56 @@ __device__ __forceinline__ bool scene_rows_in_range(const QueryFrame &q)
     return q.scene_finite && 2.0f * B * E1 < MIRT_SAFE_MAG && 2.0f * B * E2 < MIRT_SAFE_MAG && X < MIRT_SAFE_MAG;
 }
 
+// The ray's part of the filter's range: every |dir| component below MIRT_QUERY_DIR_MAX (false for NaN).  A ray outside it has
+// its filter verdicts overridden, per ray.
+__device__ __forceinline__ bool dir_in_filter_range(v3 d)
+{
+    return fabsf(d.x) < MIRT_QUERY_DIR_MAX && fabsf(d.y) < MIRT_QUERY_DIR_MAX && fabsf(d.z) < MIRT_QUERY_DIR_MAX;
+}
+
 // A ray whose operands are not provably inside the filter's range: it takes the exact path for every triangle.
 __device__ __forceinline__ bool ray_exact_only(bool scene_ok, v3 start, v3 dir)
 {
     const bool in_range = fabsf(start.x) < MIRT_QUERY_START_MAX && fabsf(start.y) < MIRT_QUERY_START_MAX && fabsf(start.z) < MIRT_QUERY_START_MAX &&
-                          fabsf(dir.x) < MIRT_QUERY_DIR_MAX && fabsf(dir.y) < MIRT_QUERY_DIR_MAX && fabsf(dir.z) < MIRT_QUERY_DIR_MAX;
+                          dir_in_filter_range(dir);
     return !(scene_ok && in_range);
+}
+
+// A chunk of `cnt` 48-byte rows (QueryRow, OriginRow: three float4 each) into LDS, by the whole workgroup of 256 between two barriers.
+template <class Row>
+__device__ __forceinline__ void stage_rows(float4 *s_rows, const Row *rows, int cnt)
+{
+    static_assert(sizeof(Row) == 48, "rows are staged as three float4");
+    __syncthreads();
+    const float4 *src = reinterpret_cast<const float4 *>(rows);
+    for (int k = threadIdx.x; k < cnt * 3; k += 256) s_rows[k] = src[k];
+    __syncthreads();
+}
+
+// struct Intersection (raytracer.cpp:91-96) to its HIT_WORDS words: position, distance (as bits), triangleIndex.
+__device__ __forceinline__ void store_record(uint32_t *h, v3 pos, uint32_t dist_bits, uint32_t tri)
+{
+    h[0] = __float_as_uint(pos.x); h[1] = __float_as_uint(pos.y); h[2] = __float_as_uint(pos.z);
+    h[3] = dist_bits;
+    h[4] = tri;
+}
+
+// The in/out `closestIntersection` of a ray while one lane sees the triangles in index order: the reference's own sequential
+// update, `if (record.distance >= distance)` (:243), started from the incoming record -- which is what the packed min-t key
+// encodes (rt_common.hpp) and needs no key here: ties go to the later index, an incoming record loses every tie, a negative or
+// NaN incoming distance is never replaced and +inf by any hit.  The state -- distance, index (-1: still the incoming record),
+// position, whether anything replaced the record -- stays in the kernels' own registers.
+template <class Flag>
+__device__ __forceinline__ void closest_offer(float &best_d, int &best_i, v3 &pos, Flag &replaced, float dist, int tri, v3 hp)
+{
+    if (best_d >= dist) { best_d = dist; best_i = tri; pos = hp; replaced = Flag(1); }   // :243-247
+}
+// Ray p of the P that lane t of block b owns: (b * P + p) * 256 + t; its incoming distance -- a lane without a ray carries a record
+// nothing can replace --; and the write-back: a record nothing replaced is not written at all.
+template <int P> __device__ __forceinline__ long long lane_ray(int p) { return ((long long)blockIdx.x * P + p) * 256 + threadIdx.x; }
+__device__ __forceinline__ float incoming_distance(const uint32_t *hits, long long ray, bool ok)
+{
+    return ok ? __uint_as_float(hits[(size_t)HIT_WORDS * ray + 3]) : -1.0f;
 }
 
 struct RowVecs { v3 v0, e1, e2, e1e2; };
@@ -144,11 +188,7 @@ __device__ __forceinline__ bool exact_hit_row(const TestDots &d, float e1e2b, co
 //
 // Workgroup = 256 lanes; lane t of block b owns rays (b * P + p) * 256 + t.  The rows are staged through LDS in chunks of
 // RT_CHUNK_ROWS (48 KiB) and read as wave-uniform broadcasts, three ds_read_b128 per triangle shared by the lane's P rays.
-// hits[ray] is the reference's in/out `closestIntersection`: the update is the reference's own sequential one in index order,
-// `if (record.distance >= distance)` (:243), started from the incoming record -- which is what the packed min-t key encodes
-// (rt_common.hpp) and needs no key while one lane sees the triangles in order: ties go to the later index, an incoming record
-// loses every tie, a negative or NaN incoming distance is never replaced and +inf by any hit.  A record nothing replaced is
-// not written at all.
+// hits[ray] is the reference's in/out `closestIntersection`, updated sequentially in index order (closest_offer).
 template <int P>
 __global__ __launch_bounds__(256) void k_query_closest(const QueryFrame q)
 {
@@ -163,15 +203,14 @@ __global__ __launch_bounds__(256) void k_query_closest(const QueryFrame q)
     int best_i[P];
 #pragma unroll
     for (int p = 0; p < P; p++) {
-        ray[p] = ((long long)blockIdx.x * P + p) * 256 + threadIdx.x;
+        ray[p] = lane_ray<P>(p);
         ok[p] = ray[p] < q.nrays;
         const float *r = q.rays + (size_t)RAY_WORDS * (ok[p] ? ray[p] : 0);
         start[p] = ld3(r);
         const v3 dir = ld3(r + 3);
         nd[p] = neg3(dir);                                         // negD = -dir (:229); dir is used as given
         exact_only[p] = ray_exact_only(scene_ok, start[p], dir);
-        // a lane without a ray carries a record nothing can replace
-        best_d[p] = ok[p] ? __uint_as_float(q.hits[(size_t)HIT_WORDS * ray[p] + 3]) : -1.0f;
+        best_d[p] = incoming_distance(q.hits, ray[p], ok[p]);
         best_i[p] = -1;
         pos[p] = V3(0.0f, 0.0f, 0.0f);
         replaced[p] = false;
@@ -183,12 +222,7 @@ __global__ __launch_bounds__(256) void k_query_closest(const QueryFrame q)
 
     for (int base = 0; base < q.n; base += RT_CHUNK_ROWS) {
         const int cnt = min(RT_CHUNK_ROWS, q.n - base);
-        __syncthreads();
-        {
-            const float4 *src = reinterpret_cast<const float4 *>(q.rows + base);
-            for (int k = threadIdx.x; k < cnt * 3; k += 256) s_rows[k] = src[k];
-        }
-        __syncthreads();
+        stage_rows(s_rows, q.rows + base, cnt);
 #pragma unroll 2
         for (int j = 0; j < cnt; j++) {
             const RowVecs r = unpack_row(s_rows[3 * j], s_rows[3 * j + 1], s_rows[3 * j + 2]);
@@ -213,22 +247,15 @@ __global__ __launch_bounds__(256) void k_query_closest(const QueryFrame q)
                 if (maybe[p] || exact_only[p]) {
                     v3 hp;
                     float dist;
-                    if (exact_hit_row(d[p], e1e2b[p], r, start[p], &hp, &dist)) {
-                        if (best_d[p] >= dist) { best_d[p] = dist; best_i[p] = base + j; pos[p] = hp; replaced[p] = true; }   // :243-247
-                    }
+                    if (exact_hit_row(d[p], e1e2b[p], r, start[p], &hp, &dist)) closest_offer(best_d[p], best_i[p], pos[p], replaced[p], dist, base + j, hp);
                 }
             }
         }
     }
 
 #pragma unroll
-    for (int p = 0; p < P; p++) {
-        if (!ok[p] || !replaced[p]) continue;
-        uint32_t *h = q.hits + (size_t)HIT_WORDS * ray[p];
-        h[0] = __float_as_uint(pos[p].x); h[1] = __float_as_uint(pos[p].y); h[2] = __float_as_uint(pos[p].z);
-        h[3] = __float_as_uint(best_d[p]);
-        h[4] = (uint32_t)best_i[p];
-    }
+    for (int p = 0; p < P; p++)
+        if (ok[p] && replaced[p]) store_record(q.hits + (size_t)HIT_WORDS * ray[p], pos[p], __float_as_uint(best_d[p]), (uint32_t)best_i[p]);
 }
 
 template __global__ void k_query_closest<QUERY_P>(const QueryFrame);
@@ -278,9 +305,7 @@ __global__ __launch_bounds__(256) void k_query_closest_wave(const QueryFrame q)
     const int owner = __builtin_ctzll(__ballot(key == best) | (1ull << 63));
     pos.x = __shfl(pos.x, owner); pos.y = __shfl(pos.y, owner); pos.z = __shfl(pos.z, owner);
     if (lane != 0) return;
-    h[0] = __float_as_uint(pos.x); h[1] = __float_as_uint(pos.y); h[2] = __float_as_uint(pos.z);
-    h[3] = (uint32_t)(best >> 32);
-    h[4] = (uint32_t)min_t_index(best);
+    store_record(h, pos, (uint32_t)(best >> 32), (uint32_t)min_t_index(best));
 }
 
 // ---- k_query_direct_light: DirectLight per hit record -----------------------------------------------------------------
@@ -346,19 +371,14 @@ __device__ __forceinline__ void direct_light_body(const QueryLightFrame &q, floa
             rd.set(p, rdp);                                        // shadow ray: dir = -rDir, so negD = rDir (:310, :229)
             thr[p] = r * 0.99f;                                    // j.distance < r*0.99f (:313)
             live[p] = valid[p];
-            exact_only[p] = !(fabsf(rdp.x) < MIRT_QUERY_DIR_MAX && fabsf(rdp.y) < MIRT_QUERY_DIR_MAX && fabsf(rdp.z) < MIRT_QUERY_DIR_MAX);
+            exact_only[p] = !dir_in_filter_range(rdp);
             any_live |= live[p];
         }
         const OriginRow *tab = f.light_tab + (size_t)k * f.n;
         // every wave of the block takes part in the staging barriers; a wave with nothing left to test skips the inner loop
         for (int base = 0; base < f.n; base += RT_CHUNK_ROWS) {
             const int cnt = min(RT_CHUNK_ROWS, f.n - base);
-            __syncthreads();
-            {
-                const float4 *src = reinterpret_cast<const float4 *>(tab + base);
-                for (int j = threadIdx.x; j < cnt * 3; j += 256) s_tab[j] = src[j];
-            }
-            __syncthreads();
+            stage_rows(s_tab, tab + base, cnt);
             if (!__any(any_live)) continue;
 #pragma unroll 2
             for (int j = 0; j < cnt; j++) {
@@ -434,13 +454,38 @@ __device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
     return v;
 }
 
+// The step of a cube walk: on to row e + 1 where the lane continues (`cont`), else to the list's end and row 0 -- loaded and
+// ignored, so that every step is straight-line code for every lane (CubeView: the row table is never NULL).
+__device__ __forceinline__ void walk_row(const float4 *rows4, uint32_t e, float4 &c0, float4 &c1, float4 &c2)
+{
+    const float4 *src = rows4 + (size_t)e * 3;
+    c0 = src[0]; c1 = src[1]; c2 = src[2];
+}
+__device__ __forceinline__ void walk_step(const float4 *rows4, uint32_t &e, uint32_t end, int cont, float4 &c0, float4 &c1, float4 &c2)
+{
+    e = cont ? e + 1u : end;
+    walk_row(rows4, cont ? e : 0u, c0, c1, c2);
+}
+
+// The QSTAT_WORDS counters of a STATS kernel: summed over the wave, one atomic per wave and non-zero word.
+__device__ __forceinline__ void flush_query_stats(unsigned long long *stats, unsigned long long rays, unsigned long long cand,
+                                                  unsigned long long tests, unsigned long long fallback)
+{
+    const unsigned long long sums[QSTAT_WORDS] = { wave_sum64(rays), wave_sum64(cand), wave_sum64(tests), wave_sum64(fallback) };
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int w = 0; w < QSTAT_WORDS; w++)
+            if (sums[w]) atomicAdd(stats + w, sums[w]);
+}
+
 template <int P, bool STATS>
 __global__ __launch_bounds__(256) void k_query_direct_light_binned(const QueryBinnedFrame b)
 {
     const QueryLightFrame &q = b.q;
     const RtFrame &f = q.f;
-    const float4 *rows4 = reinterpret_cast<const float4 *>(b.light_rows);
-    const uint32_t face_bins = (uint32_t)(b.cube_bins * b.cube_bins) * 6u;
+    const CubeView &cv = b.cube;
+    const float4 *rows4 = reinterpret_cast<const float4 *>(cv.light_rows);
+    const uint32_t face_bins = (uint32_t)(cv.cube_bins * cv.cube_bins) * 6u;
     unsigned long long n_rays = 0, n_cand = 0, n_tests = 0, n_fall = 0;
 #pragma unroll 1
     for (int p = 0; p < P; p++) {
@@ -466,16 +511,16 @@ __global__ __launch_bounds__(256) void k_query_direct_light_binned(const QueryBi
             const bool binned = valid && formed, swept = valid && !formed;
             uint32_t e = 0u, end = 0u;
             if (binned) {
-                const uint32_t bin = cube_bin_of(rd, (uint32_t)k * face_bins, b.cube_bins);
-                const BinFrameDesc *lf = b.light_frames + 6 * k;
-                const uint32_t key = bin * (uint32_t)b.shells;
-                e = b.light_off[key];
-                end = b.light_off[key + bin_shell_of(thr, lf->shell_d0, lf->shell_iw, b.shells) + 1u];
+                const uint32_t bin = cube_bin_of(rd, (uint32_t)k * face_bins, cv.cube_bins);
+                const BinFrameDesc *lf = cv.light_frames + 6 * k;
+                const uint32_t key = bin * (uint32_t)cv.shells;
+                e = cv.light_off[key];
+                end = cv.light_off[key + bin_shell_of(thr, lf->shell_d0, lf->shell_iw, cv.shells) + 1u];
             }
             if (STATS) { n_rays += valid ? 1u : 0u; n_cand += end - e; }
             int occluded = 0;
             float4 c0, c1, c2;
-            { const float4 *src = rows4 + (size_t)(e < end ? e : 0u) * 3; c0 = src[0]; c1 = src[1]; c2 = src[2]; }
+            walk_row(rows4, e < end ? e : 0u, c0, c1, c2);
             for (;;) {
                 const int act = (int)(e < end);
                 if (!__any(act)) break;
@@ -488,18 +533,15 @@ __global__ __launch_bounds__(256) void k_query_direct_light_binned(const QueryBi
                 if (pass & (sure ^ 1)) {
                     v3 hp;
                     float dist;
-                    if (exact_hit(td, c0.w, f.tris15 + (size_t)15 * b.light_tri[e], L, &hp, &dist)) done = (int)(dist < thr);   // :313
+                    if (exact_hit(td, c0.w, f.tris15 + (size_t)15 * cv.light_tri[e], L, &hp, &dist)) done = (int)(dist < thr);   // :313
                 }
                 occluded |= done;
-                const int cont = act & (done ^ 1) & (int)(e + 1u < end);
-                e = cont ? e + 1u : end;                           // (done, or the list's end: the lane is through)
-                const float4 *src = rows4 + (size_t)(cont ? e : 0u) * 3;
-                c0 = src[0]; c1 = src[1]; c2 = src[2];
+                walk_step(rows4, e, end, act & (done ^ 1) & (int)(e + 1u < end), c0, c1, c2);     // (done, or the list's end: the lane is through)
             }
             if (__any(swept)) {
                 // (rare) the lanes the bins do not cover: light k's full origin table, k_query_direct_light's loop body
                 const OriginRow *tab = f.light_tab + (size_t)k * f.n;
-                const bool exact_only = !(ax < MIRT_QUERY_DIR_MAX && ay < MIRT_QUERY_DIR_MAX && az < MIRT_QUERY_DIR_MAX);
+                const bool exact_only = !dir_in_filter_range(rd);
                 bool live = swept;
                 if (STATS && swept) { n_cand += (unsigned)f.n; fell = true; }
                 for (int j = 0; j < f.n; j++) {
@@ -522,13 +564,7 @@ __global__ __launch_bounds__(256) void k_query_direct_light_binned(const QueryBi
         if (STATS) n_fall += fell ? 1u : 0u;
         if (ok) st3(q.rgb + 3 * (size_t)rec, valid ? reference_nan(mul3(result2, ld3(t + 12)), pos) : V3(0.0f, 0.0f, 0.0f));   // :325-326
     }
-    if (STATS) {
-        const unsigned long long sums[QSTAT_WORDS] = { wave_sum64(n_rays), wave_sum64(n_cand), wave_sum64(n_tests), wave_sum64(n_fall) };
-        if ((threadIdx.x & 63) == 0)
-#pragma unroll
-            for (int w = 0; w < QSTAT_WORDS; w++)
-                if (sums[w]) atomicAdd(b.stats + w, sums[w]);
-    }
+    if (STATS) flush_query_stats(b.stats, n_rays, n_cand, n_tests, n_fall);
 }
 
 template __global__ void k_query_direct_light_binned<QUERY_BIN_P, false>(const QueryBinnedFrame);
@@ -555,25 +591,19 @@ __device__ __forceinline__ void fan_body(const QueryFanFrame &q, float4 *s_tab)
     int best_i[P];
 #pragma unroll
     for (int p = 0; p < P; p++) {
-        ray[p] = ((long long)blockIdx.x * P + p) * 256 + threadIdx.x;
+        ray[p] = lane_ray<P>(p);
         ok[p] = ray[p] < q.nrays;
         const v3 dir = ld3(q.dirs + 3 * (size_t)(ok[p] ? ray[p] : 0));
         rd.set(p, neg3(dir));                                      // negD = -dir (:229); dir is used as given
-        exact_only[p] = !(fabsf(dir.x) < MIRT_QUERY_DIR_MAX && fabsf(dir.y) < MIRT_QUERY_DIR_MAX && fabsf(dir.z) < MIRT_QUERY_DIR_MAX);
-        // a lane without a ray carries a record nothing can replace
-        best_d[p] = ok[p] ? __uint_as_float(q.hits[(size_t)HIT_WORDS * ray[p] + 3]) : -1.0f;
+        exact_only[p] = !dir_in_filter_range(dir);
+        best_d[p] = incoming_distance(q.hits, ray[p], ok[p]);
         best_i[p] = -1;
         pos[p] = V3(0.0f, 0.0f, 0.0f);
         replaced[p] = false;
     }
     for (int base = 0; base < q.n; base += RT_CHUNK_ROWS) {
         const int cnt = min(RT_CHUNK_ROWS, q.n - base);
-        __syncthreads();
-        {
-            const float4 *src = reinterpret_cast<const float4 *>(q.tab + base);
-            for (int j = threadIdx.x; j < cnt * 3; j += 256) s_tab[j] = src[j];
-        }
-        __syncthreads();
+        stage_rows(s_tab, q.tab + base, cnt);
 #pragma unroll 2
         for (int j = 0; j < cnt; j++) {
             const float4 r0 = s_tab[3 * j], r1 = s_tab[3 * j + 1], r2 = s_tab[3 * j + 2];
@@ -586,19 +616,14 @@ __device__ __forceinline__ void fan_body(const QueryFanFrame &q, float4 *s_tab)
                     v3 hp;
                     float dist;
                     if (exact_hit(d[p], r0.w, q.tris15 + (size_t)15 * (base + j), S, &hp, &dist))
-                        if (best_d[p] >= dist) { best_d[p] = dist; best_i[p] = base + j; pos[p] = hp; replaced[p] = true; }   // :243-247
+                        closest_offer(best_d[p], best_i[p], pos[p], replaced[p], dist, base + j, hp);
                 }
             }
         }
     }
 #pragma unroll
-    for (int p = 0; p < P; p++) {
-        if (!ok[p] || !replaced[p]) continue;
-        uint32_t *h = q.hits + (size_t)HIT_WORDS * ray[p];
-        h[0] = __float_as_uint(pos[p].x); h[1] = __float_as_uint(pos[p].y); h[2] = __float_as_uint(pos[p].z);
-        h[3] = __float_as_uint(best_d[p]);
-        h[4] = (uint32_t)best_i[p];
-    }
+    for (int p = 0; p < P; p++)
+        if (ok[p] && replaced[p]) store_record(q.hits + (size_t)HIT_WORDS * ray[p], pos[p], __float_as_uint(best_d[p]), (uint32_t)best_i[p]);
 }
 
 template <int P>
@@ -634,7 +659,8 @@ template __global__ void k_query_fan<QUERY_P>(const QueryFanFrame);
 template <bool STATS>
 __global__ __launch_bounds__(256) void k_query_fan_binned(const QueryFanFrame q)
 {
-    const float4 *rows4 = reinterpret_cast<const float4 *>(q.light_rows);
+    const CubeView &cv = q.cube;
+    const float4 *rows4 = reinterpret_cast<const float4 *>(cv.light_rows);
     const long long ray = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool ok = ray < q.nrays;
     const v3 S = ld3(q.origin);
@@ -645,18 +671,18 @@ __global__ __launch_bounds__(256) void k_query_fan_binned(const QueryFanFrame q)
     const bool open = ok && bound >= 0.0f;                         // (false for NaN)
     const FanDir fd = fan_dir_of(nd);
     const bool binned = open && fd.formed, swept = open && !fd.formed;
-    const float d0 = q.light_frames[0].shell_d0, iw = q.light_frames[0].shell_iw;
+    const float d0 = cv.light_frames[0].shell_d0, iw = cv.light_frames[0].shell_iw;
     uint32_t e = 0u, end = 0u, key = 0u;
     if (binned) {
-        key = cube_bin_of(fd.d, 0u, q.cube_bins) * (uint32_t)q.shells;
-        e = q.light_off[key];
-        end = q.light_off[key + bin_shell_of(bound, d0, iw, q.shells) + 1u];
+        key = cube_bin_of(fd.d, 0u, cv.cube_bins) * (uint32_t)cv.shells;
+        e = cv.light_off[key];
+        end = cv.light_off[key + bin_shell_of(bound, d0, iw, cv.shells) + 1u];
     }
     unsigned long long n_cand = 0, n_tests = 0;
     int best_i = -1, replaced = 0;
     v3 pos = V3(0.0f, 0.0f, 0.0f);
     float4 c0, c1, c2;
-    { const float4 *src = rows4 + (size_t)(e < end ? e : 0u) * 3; c0 = src[0]; c1 = src[1]; c2 = src[2]; }
+    walk_row(rows4, e < end ? e : 0u, c0, c1, c2);
     for (;;) {
         const int act = (int)(e < end);
         if (!__any(act)) break;
@@ -664,24 +690,21 @@ __global__ __launch_bounds__(256) void k_query_fan_binned(const QueryFanFrame q)
         const int near_ok = act & (int)!(c1.w > bound);            // strictly beyond the record: cannot pass `bound >= d`
         if (STATS) { n_cand += (unsigned)act; n_tests += (unsigned)near_ok; }
         if (near_ok & (int)maybe_hit(td)) {
-            const int tri = (int)q.light_tri[e];
+            const int tri = (int)cv.light_tri[e];
             v3 hp;
             float dist;
             if (exact_hit(td, c0.w, q.tris15 + (size_t)15 * tri, S, &hp, &dist)) {
                 if ((bound > dist) | ((bound == dist) & (tri > best_i))) {
                     bound = dist; best_i = tri; pos = hp; replaced = 1;
-                    end = min(end, q.light_off[key + bin_shell_of(dist, d0, iw, q.shells) + 1u]);
+                    end = min(end, cv.light_off[key + bin_shell_of(dist, d0, iw, cv.shells) + 1u]);
                 }
             }
         }
-        const int cont = act & (int)(e + 1u < end);
-        e = cont ? e + 1u : end;                                   // (the list's end, old or new: the lane is through)
-        const float4 *src = rows4 + (size_t)(cont ? e : 0u) * 3;
-        c0 = src[0]; c1 = src[1]; c2 = src[2];
+        walk_step(rows4, e, end, act & (int)(e + 1u < end), c0, c1, c2);   // (the list's end, old or new: the lane is through)
     }
     if (__any(swept)) {
         // (rare) the lanes the bins do not cover: the origin's full table in index order, the sequential rule itself
-        const bool exact_only = !(fabsf(dir.x) < MIRT_QUERY_DIR_MAX && fabsf(dir.y) < MIRT_QUERY_DIR_MAX && fabsf(dir.z) < MIRT_QUERY_DIR_MAX);
+        const bool exact_only = !dir_in_filter_range(dir);
         if (STATS && swept) { n_cand += (unsigned)q.n; n_tests += (unsigned)q.n; }
         for (int j = 0; j < q.n; j++) {
             const float4 r0 = q.tab[j].r0, r1 = q.tab[j].r1, r2 = q.tab[j].r2;
@@ -689,23 +712,12 @@ __global__ __launch_bounds__(256) void k_query_fan_binned(const QueryFanFrame q)
             if (swept && (maybe_hit(td) || exact_only)) {
                 v3 hp;
                 float dist;
-                if (exact_hit(td, r0.w, q.tris15 + (size_t)15 * j, S, &hp, &dist))
-                    if (bound >= dist) { bound = dist; best_i = j; pos = hp; replaced = 1; }        // :243-247
+                if (exact_hit(td, r0.w, q.tris15 + (size_t)15 * j, S, &hp, &dist)) closest_offer(bound, best_i, pos, replaced, dist, j, hp);
             }
         }
     }
-    if (ok && replaced) {
-        h[0] = __float_as_uint(pos.x); h[1] = __float_as_uint(pos.y); h[2] = __float_as_uint(pos.z);
-        h[3] = __float_as_uint(bound);
-        h[4] = (uint32_t)best_i;
-    }
-    if (STATS) {
-        const unsigned long long sums[QSTAT_WORDS] = { wave_sum64(ok ? 1u : 0u), wave_sum64(n_cand), wave_sum64(n_tests), wave_sum64(swept ? 1u : 0u) };
-        if ((threadIdx.x & 63) == 0)
-#pragma unroll
-            for (int w = 0; w < QSTAT_WORDS; w++)
-                if (sums[w]) atomicAdd(q.stats + w, sums[w]);
-    }
+    if (ok && replaced) store_record(h, pos, __float_as_uint(bound), (uint32_t)best_i);
+    if (STATS) flush_query_stats(q.stats, ok ? 1u : 0u, n_cand, n_tests, swept ? 1u : 0u);
 }
 
 template __global__ void k_query_fan_binned<false>(const QueryFanFrame);

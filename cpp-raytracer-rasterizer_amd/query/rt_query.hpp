@@ -53,13 +53,18 @@ struct QueryLightFrame {
 // is the CUBE's origin table (k_select_faces: one row per (light position, triangle)), which the records the bins do not cover
 // sweep instead; the rest is what the trace kernel of a binned frame reads of a light cube (capi.hpp: LightCache).
 enum { QSTAT_SHADOW_RAYS = 0, QSTAT_CANDIDATES = 1, QSTAT_TESTS = 2, QSTAT_FALLBACK = 3, QSTAT_WORDS = 4 };
-struct QueryBinnedFrame {
-    QueryLightFrame q;
-    const uint32_t *light_off;          // nlights * 6 * B * B * shells + 1: first row of every (bin, shell) key
+// What a walk kernel reads of a light cube (capi.hpp: LightCache; made by cube_view, query.cpp).  light_rows is never NULL: a lane
+// with no row left still loads row 0.
+struct CubeView {
+    const uint32_t *light_off;          // positions * 6 * B * B * shells + 1: first row of every (bin, shell) key
     const LightRow *light_rows;         // the candidates' origin rows in key order, `far` in r2.w (k_expand_light_rows)
     const uint32_t *light_tri;          // the triangle of each row
-    const BinFrameDesc *light_frames;   // 6 per light position: shell_d0 / shell_iw of the position's depth shells
+    const BinFrameDesc *light_frames;   // 6 per position: shell_d0 / shell_iw of the position's depth shells
     int cube_bins, shells;
+};
+struct QueryBinnedFrame {
+    QueryLightFrame q;
+    CubeView cube;
     unsigned long long *stats;          // QSTAT_WORDS counters (the STATS instantiation only)
 };
 
@@ -115,7 +120,7 @@ MIRT_HD FanDir fan_dir_of(v3 nd)
 }
 
 // One origin, nrays directions, the in/out records.  tab: the origin's table, one row per triangle (the cube's own, written by
-// k_select_faces, or the query's, written by k_prep_origin); the cube fields are read by k_query_fan_binned only.
+// k_select_faces, or the query's, written by k_prep_origin); the cube is read by k_query_fan_binned only.
 struct QueryFanFrame {
     const float *tris15;
     int n;
@@ -125,11 +130,7 @@ struct QueryFanFrame {
     const float *dirs;                  // nrays x 3, used as given
     int nrays;
     uint32_t *hits;                     // nrays x HIT_WORDS, in/out
-    const uint32_t *light_off;          // 6 * B * B * shells + 1
-    const LightRow *light_rows;
-    const uint32_t *light_tri;
-    const BinFrameDesc *light_frames;   // 6: shell_d0 / shell_iw of the origin's depth shells
-    int cube_bins, shells;
+    CubeView cube;                      // the cube around the origin: one position
     unsigned long long *stats;          // QSTAT_WORDS counters (the STATS instantiation only): rays, rows offered, rows tested, rays that swept
 };
 
