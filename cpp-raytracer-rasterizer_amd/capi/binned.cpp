@@ -16,9 +16,7 @@ int ensure_pairs(RtScratch &S, size_t cap)
     return MIRT_OK;
 }
 
-// Most sort keys (bin * depth shells + shell) one binning pass may use: the two-level counting sort keeps one LDS counter per
-// bucket of at most 1024 keys (bin_bucket_sort.hip).  The callers choose their grids and shell counts to stay below it.
-constexpr uint32_t BIN_MAX_KEYS = BUCKET_SORT_MAX_BUCKETS * 1024u - 1u;
+// (BIN_MAX_KEYS, the most sort keys one binning pass may use: cube_plan.hpp)
 
 // Picks up the pair count an earlier frame of the stream has published (pinned word + event), if it has landed.
 void poll_pair_count(RtScratch &S)
@@ -316,20 +314,21 @@ int light_cache_ensure(LightCache &C, RtScratch &S, const float *origins, int nl
 // they cost is memory (48 bytes per (bin, triangle) pair) and ~1 ms of build for 100 k triangles.  Measured on the 100 k soup at 1080p
 // (round 2's trace kernel, lists not yet ordered by depth): 64: 153 us, 128: 125 us, 256: 105 us.  MIRT_CUBE_BINS=64|128|256 fixes
 // the grid (and keeps every frame on the shared cache).
-int light_cube_bins_for(int nlights, bool *fixed_grid)
+// (the arithmetic: cube_plan.hpp, cube_bins_rule and cube_keys_fit)
+int cube_bins_override()
 {
     static const int cube_override = (int)env_int("MIRT_CUBE_BINS", 0);
-    int fine_bins = g.n < 2000 ? CUBE_BINS_MIN : (g.n < 20000 ? 2 * CUBE_BINS_MIN : 4 * CUBE_BINS_MIN);
-    *fixed_grid = cube_override == 64 || cube_override == 128 || cube_override == 256;
-    if (*fixed_grid) fine_bins = cube_override;
-    // (many light positions -- 16 soft-shadow samples of two lights -- at the finest grid are more keys than one sort pass holds)
-    while (fine_bins > CUBE_BINS_MIN && 6ll * fine_bins * fine_bins * nlights * 4 > (long long)BIN_MAX_KEYS) fine_bins /= 2;
-    return fine_bins;
+    return cube_override;
+}
+
+int light_cube_bins_for(int nlights, bool *fixed_grid)
+{
+    return cube_bins_rule(g.n, nlights, cube_bins_override(), fixed_grid);
 }
 
 bool light_keys_fit(int nlights, int cube_bins)
 {
-    return 6ll * cube_bins * cube_bins * std::max(nlights, 1) + 64 <= (long long)BIN_MAX_KEYS;
+    return cube_keys_fit(nlights, cube_bins);
 }
 
 // Depth shells of the camera bins for a frame of `tiles` bins (the tiles' lists come out of the sort roughly front to back).

@@ -13,6 +13,7 @@
 #include "../csrc/rt_binned.hpp"
 #include "../csrc/scan.hpp"
 #include "../query/rt_query.hpp"
+#include "cube_plan.hpp"
 #include "env.hpp"
 
 #include <cstdarg>
@@ -218,6 +219,10 @@ struct QueryScratch {
     uint32_t *d_flags = nullptr;                 // [0] = unsafe flag
     uint64_t rows_seen = 0;                      // the QueryRows::version this stream is already ordered behind (0 = none)
     unsigned long long *d_stats[QUERY_KINDS] = {};   // QSTAT_WORDS counters of the stream's last binned query of each kind (profiling on)
+    // mirt_intersect_fans* by brute force: the call's origins and its rays written out for k_query_closest* (k_query_fans_expand)
+    float *d_fan_origins = nullptr;              // fan_origins_cap x 3
+    float *d_fan_rays = nullptr;                 // fan_rays_cap x RAY_WORDS
+    size_t fan_origins_cap = 0, fan_rays_cap = 0;
 
     void release();
 };
@@ -231,8 +236,8 @@ struct QueryRows {
     uint64_t version = 0;                        // scene_version the rows were built for (0 = none)
     hipEvent_t ev_built = nullptr;
     // staging of the host-buffer entry points (mirt_intersect, mirt_direct_light)
-    void *d_rays = nullptr, *d_hits = nullptr, *d_rgb = nullptr, *d_dirs = nullptr;
-    size_t cap = 0;                              // rays / records / directions each holds
+    void *d_rays = nullptr, *d_hits = nullptr, *d_rgb = nullptr, *d_dirs = nullptr, *d_origin_of = nullptr;
+    size_t cap = 0;                              // rays / records / directions / origin indices each holds
     // The light cube of the DirectLight queries: a LightCache like the frame path's g.lc, keyed alike (scene version + the light
     // positions in use, and the grid -- so a new scene forgets it), kept across calls, shared by the streams and ordered among
     // them by light_cache_ensure's events.  A query whose lights are the ones the frame path's valid cube holds reads g.lc and
@@ -242,6 +247,11 @@ struct QueryRows {
     // scene version and origin (light_key_of), built by light_cache_ensure under the same protocol.  Apart from `cube`, so that a
     // probe does not evict DirectLight's lights nor a DirectLight query the probe's origin.
     LightCache fan;
+    // The cube of the many-origin fans (mirt_intersect_fans*): up to MIRT_MAX_LIGHTS of the call's origins as its positions, keyed
+    // by scene version, positions and their order (light_key_of), built by light_cache_ensure under the same protocol.  A call of
+    // several passes leaves the last range's cube here.  Apart from `fan` and `cube`: the call evicts neither, and a pass whose
+    // positions are the ones g.lc or `cube` holds reads that cube instead (query.cpp: fans_foreign_cube).
+    LightCache fans;
 
     void release();                              // (the cubes' tables too)
 };
@@ -410,6 +420,7 @@ uint64_t light_key_of(const float *origins, int nlights);
 // Bins per face side of the cubes of `nlights` light positions under the frame path's rules (scene size, MIRT_CUBE_BINS, the
 // sort's key space); *fixed_grid: the environment fixed it.  light_keys_fit: one sort pass holds such a cube's keys at all.
 int light_cube_bins_for(int nlights, bool *fixed_grid);
+int cube_bins_override();                        // MIRT_CUBE_BINS as read once (0: not set)
 bool light_keys_fit(int nlights, int cube_bins);
 int binned_pass(const mirt_view *view, RtScratch &S, RtScratch &L, const float *origins, int nlights, int y0, int y1, BinnedPass *bp);
 int binned_trace(const RtFrame &f, RtScratch &S, RtScratch &L, const BinnedPass &bp);
@@ -453,6 +464,8 @@ int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, 
 int query_direct_light_host(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, float *out_rgb);
 int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, void *d_hits);
 int query_intersect_from_host(const float *origin, const float *dirs3, int nrays, mirt_hit *hits);
+int query_intersect_fans(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, void *d_hits);
+int query_intersect_fans_host(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, mirt_hit *hits);
 
 // ---- rasteriser (raster.cpp) ----
 int raster_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect,

@@ -3,7 +3,8 @@
 // version and shared by the streams, and so is the light cube whose bins the shadow rays of DirectLight walk (per scene version
 // and light positions); a query takes the next stream as a frame does (mirt_set_frames_in_flight, mirt_sync) but leaves the
 // statistics of the last render call alone (DirectLight has its own: mirt_set_query_mode, mirt_get_query_stats, defined here).
-// Many rays from ONE origin (mirt_intersect_from*) walk a cube of the same kind around that origin, kept apart from DirectLight's.
+// Many rays from ONE origin (mirt_intersect_from*) walk a cube of the same kind around that origin, kept apart from DirectLight's;
+// rays from SEVERAL origins in one call (mirt_intersect_fans*) walk cubes that hold up to MIRT_MAX_LIGHTS of the origins each.
 #include "capi.hpp"
 
 namespace mirt {
@@ -64,13 +65,10 @@ static int need_scene()
     return MIRT_OK;
 }
 
-int query_intersect(const void *d_rays, int nrays, void *d_hits)
+// ClosestIntersection by brute force for nrays > 0 rays on the current stream: the scene's rows, then one of the two kernels.
+static int intersect_launch(const void *d_rays, int nrays, void *d_hits)
 {
     int rc;
-    if ((rc = check_query_args(d_rays, nrays, d_hits, "ray"))) return rc;
-    if (nrays == 0) return MIRT_OK;
-    if ((rc = need_scene())) return rc;
-    stream_begin();
     if ((rc = query_rows())) return rc;
     QueryFrame q;
     q.rows = g.qrows.d_rows;
@@ -87,6 +85,16 @@ int query_intersect(const void *d_rays, int nrays, void *d_hits)
     }
     HIP_TRY(hipGetLastError());
     return MIRT_OK;
+}
+
+int query_intersect(const void *d_rays, int nrays, void *d_hits)
+{
+    int rc;
+    if ((rc = check_query_args(d_rays, nrays, d_hits, "ray"))) return rc;
+    if (nrays == 0) return MIRT_OK;
+    if ((rc = need_scene())) return rc;
+    stream_begin();
+    return intersect_launch(d_rays, nrays, d_hits);
 }
 
 // ---- what the queries that walk a cube share: its view, their statistics ------------------------------------------------------
@@ -348,6 +356,152 @@ int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, vo
     return MIRT_OK;
 }
 
+// ---- origin fans from many origins in one call (mirt_intersect_fans*) ----------------------------------------------------------
+//
+// The call's origins go into cubes of up to MIRT_MAX_LIGHTS positions each, as the lights of a DirectLight query do, in passes over
+// consecutive ranges of the list (cube_plan.hpp: fan_pass_plan); every pass launches k_query_fans_binned over ALL rays, and a lane
+// whose origin lies outside the pass's range retires after reading its index.  Every ray belongs to exactly one pass, so records
+// never meet; no pass is skipped, because which origins the rays name is device data.  The cube of a pass: the frame path's (g.lc)
+// or DirectLight's (g.qrows.cube) when it holds these very positions on this very grid -- read, never written, nor their tracking
+// --, else the call's own (g.qrows.fans), built now if need be in the stream's LIGHT scratch set; a call of several passes leaves
+// the last range's cube there.
+
+// AUTO for a many-origin call: the single fan's rule (auto_bins_fan), which is MEASURED FOR ONE ORIGIN ONLY, and one condition more
+// that tools/ray_query_bench.py --steps fans showed (profiles/ray_query_bench.txt, section `fans`; K = 1 .. 128 origins, soup100k and
+// the soup of 2000).  This call's brute path is mirt_intersect's, not the fan's sweep: up to MIRT_QUERY_WAVE_RAYS rays it answers a
+// wave per ray, and in every cell of at most 4096 rays it was ahead of binning with the builds (n = 2000: 0.03 ms against 0.32 ..
+// 0.54 ms; n = 100 000: 0.6 ms against 0.83 .. 2.4 ms).  Beyond that many rays binning with its builds was ahead in every cell at n =
+// 100 000 (9 .. 11 ms against 22 .. 681 ms) and in all but two at n = 2000 -- 4 origins x 4096 rays (0.60 against 0.53 ms) and
+// 128 origins x 64 rays (four builds: 1.30 against 0.53 ms) --, where AUTO stays behind brute force.
+static bool auto_bins_fans(int nrays)
+{
+    return auto_bins_fan(nrays) && (long)nrays > query_wave_rays();
+}
+
+static int check_fans_args(const float *origins3, int norigins, const void *origin_of, const void *dirs3, int nrays, const void *hits)
+{
+    int rc;
+    if ((rc = need_init())) return rc;
+    if (norigins < 0) return fail(MIRT_ERR_INVALID_ARGUMENT, "origin count %d is negative", norigins);
+    if (nrays < 0) return fail(MIRT_ERR_INVALID_ARGUMENT, "direction count %d is negative", nrays);
+    if (nrays > 0 && (!dirs3 || !hits)) return fail(MIRT_ERR_INVALID_ARGUMENT, "direction arrays must not be NULL when the count is > 0");
+    if (norigins > 0 && !origins3) return fail(MIRT_ERR_INVALID_ARGUMENT, "origins must not be NULL when their count is > 0");
+    if (norigins == 0 && nrays > 0) return fail(MIRT_ERR_INVALID_ARGUMENT, "%d rays but no origin", nrays);
+    if (norigins > 1 && !origin_of) return fail(MIRT_ERR_INVALID_ARGUMENT, "origin_of may be NULL only for a single origin, not for %d", norigins);
+    return MIRT_OK;
+}
+
+// The cube list of a pass: row 0 is the camera's place (light_key_of, light_cache_ensure), rows 1 .. count the pass's origins.
+static void fans_pass_origins(const float *origins3, const FanPass &p, float *po)
+{
+    po[0] = po[1] = po[2] = 0.0f;
+    memcpy(po + 3, origins3 + 3 * (size_t)p.first, sizeof(float) * 3 * p.count);
+}
+
+// A cube somebody else holds for the pass's positions and grid: the frame path's (*source = 3), DirectLight's (4), or none.
+static const LightCache *fans_foreign_cube(uint64_t key, int cube_bins, int *source)
+{
+    if (g.lc.valid && g.lc.key == key && g.lc.cube_bins == cube_bins) { *source = 3; return &g.lc; }
+    const LightCache &D = g.qrows.cube;
+    if (D.valid && D.key == key && D.cube_bins == cube_bins) { *source = 4; return &D; }
+    return nullptr;
+}
+
+// By definition the call is mirt_intersect on the expanded rays: they are written out on the device (k_query_fans_expand) into
+// the stream's query scratch and go through query_intersect's kernels, whose per-ray filter safety and choice of kernel come along.
+static int fans_brute(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, void *d_hits)
+{
+    int rc;
+    QueryScratch &S = g.cur().query;
+    if ((size_t)norigins > S.fan_origins_cap) {
+        S.fan_origins_cap = 0;
+        if ((rc = dev_realloc(&S.d_fan_origins, (size_t)norigins * 3))) return rc;
+        S.fan_origins_cap = (size_t)norigins;
+    }
+    if ((size_t)nrays > S.fan_rays_cap) {
+        S.fan_rays_cap = 0;
+        if ((rc = dev_realloc(&S.d_fan_rays, (size_t)nrays * RAY_WORDS))) return rc;
+        S.fan_rays_cap = (size_t)nrays;
+    }
+    HIP_TRY(upload_small(S.d_fan_origins, origins3, sizeof(float) * 3 * (size_t)norigins, g.stream));
+    QueryFansExpand x;
+    x.origins = S.d_fan_origins;
+    x.norigins = norigins;
+    x.origin_of = static_cast<const int32_t *>(d_origin_of);
+    x.dirs = static_cast<const float *>(d_dirs3);
+    x.nrays = nrays;
+    x.rays = S.d_fan_rays;
+    hipLaunchKernelGGL(k_query_fans_expand, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, g.stream, x);
+    HIP_TRY(hipGetLastError());
+    return intersect_launch(S.d_fan_rays, nrays, d_hits);
+}
+
+int query_intersect_fans(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, void *d_hits)
+{
+    int rc;
+    if ((rc = check_fans_args(origins3, norigins, d_origin_of, d_dirs3, nrays, d_hits))) return rc;
+    if (nrays == 0) return MIRT_OK;
+    if ((rc = need_scene())) return rc;
+
+    // Binned or brute, as the single fan decides it: never what the frame path would not bin, whatever the mode -- and the call is
+    // one: an origin outside the filter's range (NaN included) among ordinary ones sends all of it to the brute-force kernels.
+    bool safe = g.scene_finite;
+    for (int k = 0; k < norigins; k++) safe = safe && start_in_filter_range(origins3 + 3 * (size_t)k);
+    std::vector<FanPass> plan;
+    const bool may_bin = safe && fan_pass_plan(norigins, g.n, cube_bins_override(), &plan);
+    float po[(1 + MIRT_MAX_LIGHTS) * 3];
+    bool held = may_bin;
+    for (size_t i = 0; held && i < plan.size(); i++) {
+        fans_pass_origins(origins3, plan[i], po);
+        const uint64_t key = light_key_of(po, plan[i].count);
+        const LightCache &own = g.qrows.fans;
+        int source = 0;
+        held = fans_foreign_cube(key, plan[i].cube_bins, &source) || (own.valid && own.key == key && own.cube_bins == plan[i].cube_bins);
+    }
+    const bool binned = may_bin && g.query_mode != MIRT_QUERY_BRUTE && (g.query_mode == MIRT_QUERY_BINNED || held || auto_bins_fans(nrays));
+
+    stream_begin();
+    QueryStats &stats = stats_begin(QUERY_FAN, binned);
+    if (!binned) return fans_brute(origins3, norigins, d_origin_of, d_dirs3, nrays, d_hits);
+
+    QueryFansFrame q;
+    memset(&q, 0, sizeof q);
+    q.f.tris15 = g.d_tris;
+    q.f.n = g.n;
+    q.f.dirs = static_cast<const float *>(d_dirs3);
+    q.f.nrays = nrays;
+    q.f.hits = static_cast<uint32_t *>(d_hits);
+    q.origin_of = static_cast<const int32_t *>(d_origin_of);
+    if ((rc = stats_arm(QUERY_FAN, &q.f.stats))) return rc;          // (once: the passes' kernels add up in the same words)
+    const dim3 grid((unsigned)((nrays + 255) / 256));
+    int source_all = 0;
+    for (size_t i = 0; i < plan.size(); i++) {
+        const FanPass &p = plan[i];
+        fans_pass_origins(origins3, p, po);
+        int source = 0;
+        const LightCache *C = fans_foreign_cube(light_key_of(po, p.count), p.cube_bins, &source);
+        if (!C) {
+            // (in the stream's LIGHT scratch set, as the shared cube's build; behind the previous pass's kernel on this stream)
+            bool built = false;
+            if ((rc = light_cache_ensure(g.qrows.fans, g.cur().rt_lt, po, p.count, p.cube_bins, &built))) return rc;
+            C = &g.qrows.fans;
+            source = built ? 1 : 2;
+        }
+        // 1 as soon as a pass built; else what every pass read when that is one kind of cube; else 2: all were held
+        source_all = i == 0 ? source : (source_all == 1 || source == 1 ? 1 : (source_all == source ? source : 2));
+        stats_cube(stats, *C, source_all);
+        q.f.tab = C->d_light_tab;
+        q.f.cube = cube_view(*C);
+        q.origins = C->d_origins;
+        q.first = p.first;
+        q.count = p.count;
+        if (q.f.stats) hipLaunchKernelGGL(k_query_fans_binned<true>, grid, dim3(256), 0, g.stream, q);
+        else hipLaunchKernelGGL(k_query_fans_binned<false>, grid, dim3(256), 0, g.stream, q);
+        HIP_TRY(hipGetLastError());
+    }
+    return MIRT_OK;
+}
+
 int query_set_mode(int mode)
 {
     int rc;
@@ -370,6 +524,7 @@ static int query_staging(size_t count)
     if ((rc = dev_realloc_bytes(&Q.d_hits, count * sizeof(mirt_hit)))) return rc;
     if ((rc = dev_realloc_bytes(&Q.d_rgb, count * 3 * sizeof(float)))) return rc;
     if ((rc = dev_realloc_bytes(&Q.d_dirs, count * 3 * sizeof(float)))) return rc;
+    if ((rc = dev_realloc_bytes(&Q.d_origin_of, count * sizeof(int32_t)))) return rc;
     Q.cap = count;
     return MIRT_OK;
 }
@@ -432,8 +587,30 @@ int query_intersect_from_host(const float *origin, const float *dirs3, int nrays
     return with_host_arrays(a, [&] { return query_intersect_from(origin, Q.d_dirs, nrays, Q.d_hits); });
 }
 
+// The host form looks at every index before anything touches the device; the device form cannot (its kernels leave such a ray's
+// record unwritten).
+int query_intersect_fans_host(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, mirt_hit *hits)
+{
+    int rc;
+    if ((rc = check_fans_args(origins3, norigins, origin_of, dirs3, nrays, hits))) return rc;
+    if (nrays == 0) return MIRT_OK;
+    if (origin_of)
+        for (int i = 0; i < nrays; i++)
+            if (origin_of[i] < 0 || origin_of[i] >= norigins)
+                return fail(MIRT_ERR_INVALID_ARGUMENT, "origin_of[%d] = %d is outside [0, %d)", i, (int)origin_of[i], norigins);
+    if ((rc = need_scene())) return rc;
+    if ((rc = query_staging((size_t)nrays))) return rc;
+    QueryRows &Q = g.qrows;
+    const HostArray a[] = { { (void *)dirs3, Q.d_dirs, (size_t)nrays * 3 * sizeof(float), true, false },
+                            { hits, Q.d_hits, (size_t)nrays * sizeof(mirt_hit), true, true },
+                            { (void *)origin_of, Q.d_origin_of, (size_t)nrays * sizeof(int32_t), origin_of != nullptr, false } };
+    return with_host_arrays(a, [&] { return query_intersect_fans(origins3, norigins, origin_of ? Q.d_origin_of : nullptr, Q.d_dirs, nrays, Q.d_hits); });
+}
+
 }  // namespace mirt
 
+extern "C" int mirt_intersect_fans(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, mirt_hit *hits) { return mirt::query_intersect_fans_host(origins3, norigins, origin_of, dirs3, nrays, hits); }
+extern "C" int mirt_intersect_fans_device(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, void *d_hits) { return mirt::query_intersect_fans(origins3, norigins, d_origin_of, d_dirs3, nrays, d_hits); }
 extern "C" int mirt_intersect_from(const float origin[3], const float *dirs3, int nrays, mirt_hit *hits) { return mirt::query_intersect_from_host(origin, dirs3, nrays, hits); }
 extern "C" int mirt_intersect_from_device(const float origin[3], const void *d_dirs3, int nrays, void *d_hits) { return mirt::query_intersect_from(origin, d_dirs3, nrays, d_hits); }
 extern "C" int mirt_get_fan_stats(mirt_query_stats *out) { return mirt::query_get_stats(mirt::QUERY_FAN, out); }

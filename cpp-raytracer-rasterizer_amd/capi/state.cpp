@@ -93,16 +93,18 @@ void RtScratch::release()
 
 void QueryScratch::release()
 {
-    for (void *p : { (void *)d_light_tab, (void *)d_origins, (void *)d_flags, (void *)d_stats[QUERY_DIRECT_LIGHT], (void *)d_stats[QUERY_FAN] }) if (p) (void)hipFree(p);
+    for (void *p : { (void *)d_light_tab, (void *)d_origins, (void *)d_flags, (void *)d_stats[QUERY_DIRECT_LIGHT], (void *)d_stats[QUERY_FAN],
+                     (void *)d_fan_origins, (void *)d_fan_rays }) if (p) (void)hipFree(p);
     *this = QueryScratch();
 }
 
 void QueryRows::release()
 {
-    for (void *p : { (void *)d_rows, (void *)d_max, d_rays, d_hits, d_rgb, d_dirs }) if (p) (void)hipFree(p);
+    for (void *p : { (void *)d_rows, (void *)d_max, d_rays, d_hits, d_rgb, d_dirs, d_origin_of }) if (p) (void)hipFree(p);
     if (ev_built) (void)hipEventDestroy(ev_built);
     cube.release();
     fan.release();
+    fans.release();
     *this = QueryRows();
 }
 

@@ -159,6 +159,16 @@ struct RayTracer {
         static_assert(sizeof(vec3) == 12, "directions travel as they are");
         check(mirt_intersect_from(&start.x, n > 0 ? &dir[0].x : nullptr, n, reinterpret_cast<mirt_hit *>(closest)), "mirt_intersect_from");
     }
+    // The same for n rays from `nstarts` shared starts -- a grid of probes, the shadow maps of all point lights: closest[k] comes back
+    // as ClosestIntersection(starts[start_of[k]], dir[k], triangles, closest[k]) leaves it; up to MIRT_MAX_LIGHTS starts share one
+    // cube and one build (mirt_intersect_fans, mirt_set_query_mode).  start_of may be null for a single start.
+    void ClosestIntersection(const vec3 *starts, int nstarts, const int32_t *start_of, const vec3 *dir, Intersection *closest, int n)
+    {
+        upload_scene();
+        static_assert(sizeof(vec3) == 12, "starts and directions travel as they are");
+        check(mirt_intersect_fans(nstarts > 0 ? &starts[0].x : nullptr, nstarts, start_of, n > 0 ? &dir[0].x : nullptr, n,
+                                  reinterpret_cast<mirt_hit *>(closest)), "mirt_intersect_fans");
+    }
     // DirectLight(i) (:265-327) for n records, with the lights and the soft-shadow toggle as they stand: result[k] = DirectLight(i[k]).
     void DirectLight(const Intersection *i, vec3 *result, int n)
     {

@@ -28,6 +28,7 @@ EXPORTS = (
     "mirt_intersect", "mirt_intersect_device", "mirt_direct_light", "mirt_direct_light_device",
     "mirt_set_query_mode", "mirt_get_query_stats",
     "mirt_intersect_from", "mirt_intersect_from_device", "mirt_get_fan_stats",
+    "mirt_intersect_fans", "mirt_intersect_fans_device",
     "mirt_scene_upload_device", "mirt_scene_update_device", "mirt_scene_update", "mirt_scene_transform", "mirt_transform",
     "mirt_scene_download", "mirt_scene_info",
 )
@@ -145,6 +146,8 @@ def load():
     lib.mirt_intersect_from.argtypes = [_vp, _vp, C.c_int, _vp]
     lib.mirt_intersect_from_device.argtypes = [_vp, _vp, C.c_int, _vp]
     lib.mirt_get_fan_stats.argtypes = [C.POINTER(QueryStats)]
+    lib.mirt_intersect_fans.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp]
+    lib.mirt_intersect_fans_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp]
     lib.mirt_scene_upload_device.argtypes = [_vp, _vp, C.c_int]
     lib.mirt_scene_update_device.argtypes = [C.c_int, C.c_int, _vp]
     lib.mirt_scene_update.argtypes = [C.c_int, C.c_int, _vp]
@@ -578,6 +581,32 @@ def intersect_from_device(origin, d_dirs, nrays, d_hits):
     """The same on device arrays (raw pointers; the origin is host data), queued like a *_device frame; mirt.sync() completes it."""
     origin = np.ascontiguousarray(origin, np.float32).reshape(3)
     _check(load().mirt_intersect_from_device(_ptr(origin), d_dirs, int(nrays), d_hits))
+
+
+def intersect_fans(origins, origin_of, dirs, hits=None):
+    """ClosestIntersection(origins[origin_of[i]], dirs[i]) for every ray (mirt_intersect_fans): what intersect() returns for the
+    rays {origins[origin_of[i]], dirs[i]}, bit for bit, the origins sharing cubes of up to MAX_LIGHTS positions (set_query_mode).
+    origins: (k, 3) floats; origin_of: one int32 per ray, or None for a single origin; dirs: (n, 3) floats, used as given; hits:
+    the in/out records (HIT_DTYPE; fresh ones when None).  Returns a new array."""
+    origins = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    hits = fresh_hits(len(dirs)) if hits is None else np.ascontiguousarray(hits, HIT_DTYPE).copy()
+    if len(hits) != len(dirs):
+        raise ValueError("%d directions but %d hit records" % (len(dirs), len(hits)))
+    if origin_of is not None:
+        origin_of = np.ascontiguousarray(origin_of, np.int32).reshape(-1)
+        if len(origin_of) != len(dirs):
+            raise ValueError("%d directions but %d origin indices" % (len(dirs), len(origin_of)))
+    _check(load().mirt_intersect_fans(_ptr(origins), len(origins), None if origin_of is None else _ptr(origin_of), _ptr(dirs), len(dirs),
+                                      _ptr(hits)))
+    return hits
+
+
+def intersect_fans_device(origins, d_origin_of, d_dirs, nrays, d_hits):
+    """The same on device arrays (raw pointers; the origins are host data, d_origin_of may be None for a single origin), queued like
+    a *_device frame; mirt.sync() completes it."""
+    origins = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    _check(load().mirt_intersect_fans_device(_ptr(origins), len(origins), d_origin_of, d_dirs, int(nrays), d_hits))
 
 
 def fan_stats():

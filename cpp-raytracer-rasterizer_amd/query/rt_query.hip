@@ -723,4 +723,107 @@ __global__ __launch_bounds__(256) void k_query_fan_binned(const QueryFanFrame q)
 template __global__ void k_query_fan_binned<false>(const QueryFanFrame);
 template __global__ void k_query_fan_binned<true>(const QueryFanFrame);
 
+// ---- k_query_fans_binned: fans from many origins, every ray through its bin of ITS origin's cube ---------------------------------
+//
+// One pass of mirt_intersect_fans* (rt_query.hpp: QueryFansFrame): the cube holds `count` of the call's origins as its positions,
+// as DirectLight's cube holds the lights, and the walk is k_query_fan_binned's with what that kernel takes per launch taken per
+// lane -- the position k, S, the shell descriptor light_frames[6 k], the bin cube_bin_of(d', k 6 B B, B), the sweep table tab + k n.
+// Each ray's argument is the single fan's, unchanged: position k of a many-position cube is built by the same kernels from the
+// same descriptors as the one position of a fan's cube (fill_light_frames), only its keys start at k 6 B B shells.  Lanes of a wave
+// may hold different origins: their lists differ per lane anyway.  A lane whose index lies outside [first, first + count) -- another
+// pass's ray, or an index outside the call's list -- takes no list, sweeps nothing and writes nothing; it reads position 0's
+// values so that every load stays inside the cube's tables.
+template <bool STATS>
+__global__ __launch_bounds__(256) void k_query_fans_binned(const QueryFansFrame qf)
+{
+    const QueryFanFrame &q = qf.f;
+    const CubeView &cv = q.cube;
+    const float4 *rows4 = reinterpret_cast<const float4 *>(cv.light_rows);
+    const uint32_t face_bins = (uint32_t)(cv.cube_bins * cv.cube_bins) * 6u;
+    const long long ray = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool ok = ray < q.nrays;
+    const uint32_t idx = qf.origin_of ? (uint32_t)qf.origin_of[ok ? ray : 0] : 0u;
+    const uint32_t rel = idx - (uint32_t)qf.first;                 // (modulo 2^32: a negative or huge index lands beyond count)
+    const bool mine = ok && rel < (uint32_t)qf.count;
+    const uint32_t k = mine ? rel : 0u;
+    const v3 S = ld3(qf.origins + 3 * (size_t)(1u + k));
+    const v3 dir = ld3(q.dirs + 3 * (size_t)(ok ? ray : 0));
+    const v3 nd = neg3(dir);                                       // negD = -dir (:229); dir is used as given
+    uint32_t *h = q.hits + (size_t)HIT_WORDS * (ok ? ray : 0);
+    float bound = __uint_as_float(h[3]);
+    const bool open = mine && bound >= 0.0f;                       // (false for NaN)
+    const FanDir fd = fan_dir_of(nd);
+    const bool binned = open && fd.formed, swept = open && !fd.formed;
+    const BinFrameDesc *lf = cv.light_frames + 6 * (size_t)k;
+    const float d0 = lf->shell_d0, iw = lf->shell_iw;
+    uint32_t e = 0u, end = 0u, key = 0u;
+    if (binned) {
+        key = cube_bin_of(fd.d, k * face_bins, cv.cube_bins) * (uint32_t)cv.shells;
+        e = cv.light_off[key];
+        end = cv.light_off[key + bin_shell_of(bound, d0, iw, cv.shells) + 1u];
+    }
+    unsigned long long n_cand = 0, n_tests = 0;
+    int best_i = -1, replaced = 0;
+    v3 pos = V3(0.0f, 0.0f, 0.0f);
+    float4 c0, c1, c2;
+    walk_row(rows4, e < end ? e : 0u, c0, c1, c2);
+    for (;;) {
+        const int act = (int)(e < end);
+        if (!__any(act)) break;
+        const TestDots td = test_dots(c0, c1, c2, nd);
+        const int near_ok = act & (int)!(c1.w > bound);            // strictly beyond the record: cannot pass `bound >= d`
+        if (STATS) { n_cand += (unsigned)act; n_tests += (unsigned)near_ok; }
+        if (near_ok & (int)maybe_hit(td)) {
+            const int tri = (int)cv.light_tri[e];
+            v3 hp;
+            float dist;
+            if (exact_hit(td, c0.w, q.tris15 + (size_t)15 * tri, S, &hp, &dist)) {
+                if ((bound > dist) | ((bound == dist) & (tri > best_i))) {
+                    bound = dist; best_i = tri; pos = hp; replaced = 1;
+                    end = min(end, cv.light_off[key + bin_shell_of(dist, d0, iw, cv.shells) + 1u]);
+                }
+            }
+        }
+        walk_step(rows4, e, end, act & (int)(e + 1u < end), c0, c1, c2);   // (the list's end, old or new: the lane is through)
+    }
+    if (__any(swept)) {
+        // (rare) the lanes the bins do not cover: their origin's full table in index order, the sequential rule itself
+        const OriginRow *tab = q.tab + (size_t)k * q.n;
+        const bool exact_only = !dir_in_filter_range(dir);
+        if (STATS && swept) { n_cand += (unsigned)q.n; n_tests += (unsigned)q.n; }
+        for (int j = 0; j < q.n; j++) {
+            const float4 r0 = tab[j].r0, r1 = tab[j].r1, r2 = tab[j].r2;
+            const TestDots td = test_dots(r0, r1, r2, nd);
+            if (swept && (maybe_hit(td) || exact_only)) {
+                v3 hp;
+                float dist;
+                if (exact_hit(td, r0.w, q.tris15 + (size_t)15 * j, S, &hp, &dist)) closest_offer(bound, best_i, pos, replaced, dist, j, hp);
+            }
+        }
+    }
+    if (mine && replaced) store_record(h, pos, __float_as_uint(bound), (uint32_t)best_i);
+    if (STATS) flush_query_stats(q.stats, mine ? 1u : 0u, n_cand, n_tests, swept ? 1u : 0u);
+}
+
+template __global__ void k_query_fans_binned<false>(const QueryFansFrame);
+template __global__ void k_query_fans_binned<true>(const QueryFansFrame);
+
+// ---- k_query_fans_expand: the rays of a many-origin call written out for k_query_closest* ---------------------------------------
+// One lane per ray: { origins[origin_of[i]], dirs[i] } as the caller gave them.  An index outside [0, norigins) reads no origin and
+// becomes a ray that no triangle accepts, whatever the scene -- a NaN start makes every u, v and t of the accept test NaN, and
+// ray_exact_only sends it past the filter --, so its record stays unwritten as in the binned kernel.
+__global__ __launch_bounds__(256) void k_query_fans_expand(const QueryFansExpand x)
+{
+    const long long ray = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (ray >= x.nrays) return;
+    const uint32_t idx = x.origin_of ? (uint32_t)x.origin_of[ray] : 0u;
+    const bool valid = idx < (uint32_t)x.norigins;
+    const float qnan = __uint_as_float(0x7fc00000u);
+    const v3 S = valid ? ld3(x.origins + 3 * (size_t)idx) : V3(qnan, qnan, qnan);
+    const v3 d = valid ? ld3(x.dirs + 3 * (size_t)ray) : V3(0.0f, 0.0f, 0.0f);
+    float *r = x.rays + (size_t)RAY_WORDS * ray;
+    st3(r, S);
+    st3(r + 3, d);
+}
+
 }  // namespace mirt

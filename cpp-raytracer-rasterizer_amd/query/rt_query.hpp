@@ -134,6 +134,31 @@ struct QueryFanFrame {
     unsigned long long *stats;          // QSTAT_WORDS counters (the STATS instantiation only): rays, rows offered, rows tested, rays that swept
 };
 
+// ---- origin fans from MANY origins in one call (mirt_intersect_fans*) ---------------------------------------------------------
+//
+// One pass of the call: the cube `f.cube` holds the origins [first, first + count) of the call's list as its positions 0 .. count - 1
+// (capi.hpp: LightCache for a many-position list, as DirectLight's), and ray i belongs to the pass when origin_of[i] lies in that
+// range.  Everything k_query_fan_binned takes per launch of the ONE origin is taken per lane here: the position k = origin_of[i] -
+// first, S = origins[3 (1 + k) ..] (the cube's own list: slot 0 is the camera's place), the shell descriptor cube.light_frames[6 k],
+// the bin base k * 6 B B and the sweep table f.tab + k * n.  f.origin and f.unsafe are not read.
+struct QueryFansFrame {
+    QueryFanFrame f;
+    const float *origins;               // (1 + count) x 3: the cube's origin list
+    const int32_t *origin_of;           // nrays indices into the CALL's origins; NULL: every ray takes origin 0
+    int first, count;                   // the pass's range of the call's origins
+};
+
+// The rays of such a call written out for k_query_closest*: ray i = { origins[3 origin_of[i] ..], dirs[3 i ..] }, RAY_WORDS words
+// each; an index outside [0, norigins) gives a ray no triangle accepts (k_query_fans_expand).
+struct QueryFansExpand {
+    const float *origins;               // norigins x 3
+    int norigins;
+    const int32_t *origin_of;           // nrays, or NULL: origin 0
+    const float *dirs;                  // nrays x 3
+    int nrays;
+    float *rays;                        // nrays x RAY_WORDS
+};
+
 // Rays (hits) per workgroup of the lane-per-ray kernels: 256 lanes x P.
 constexpr int QUERY_P = 2;
 constexpr int QUERY_BLOCK_RAYS = 256 * QUERY_P;
@@ -146,5 +171,7 @@ constexpr int QUERY_BIN_P = 1;                    // records per lane of the bin
 template <int P, bool STATS = false> __attribute__((global)) void k_query_direct_light_binned(const QueryBinnedFrame);
 template <int P> __attribute__((global)) void k_query_fan(const QueryFanFrame);
 template <bool STATS> __attribute__((global)) void k_query_fan_binned(const QueryFanFrame);
+template <bool STATS> __attribute__((global)) void k_query_fans_binned(const QueryFansFrame);
+__attribute__((global)) void k_query_fans_expand(const QueryFansExpand);
 
 }  // namespace mirt

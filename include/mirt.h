@@ -373,6 +373,43 @@ MIRT_API int mirt_intersect_from_device(const float origin[3], const void *d_dir
  * Waits for the stream of that call. */
 MIRT_API int mirt_get_fan_stats(mirt_query_stats *out);
 
+/* ---- origin fans from MANY origins in one call (additions to ABI 4) ---- */
+
+/* ClosestIntersection(origins[origin_of[i]], dirs[i], triangles, hits[i]) for i in [0, nrays): exactly mirt_intersect on the rays
+ * { origins3[3 * origin_of[i] ..], dirs3[3 * i ..] }, bit for bit, for every ray and every incoming record.  A grid of light
+ * probes, the shadow maps of all of a scene's point lights, an omnidirectional camera at several stations, visibility fans from a
+ * handful of points: one call instead of one mirt_intersect_from* call -- one cube build, one host read-back -- per origin.
+ * origins3: a HOST array of norigins x 3 floats in both forms (as `origin` of mirt_intersect_from_device).  origin_of: one int32
+ * per ray; it may be NULL only when norigins == 1 (every ray takes origin 0: the call equals mirt_intersect_from*).  Rays come in
+ * any order; the lanes of a wave may hold different origins.  Records and directions: mirt_intersect's rules to the letter, as
+ * above.  Checks, in this order: MIRT_ERR_NOT_INITIALISED; MIRT_ERR_INVALID_ARGUMENT for norigins < 0, nrays < 0, a NULL array with
+ * a positive count, norigins == 0 with nrays > 0, a NULL origin_of with norigins > 1; MIRT_ERR_NO_SCENE.  nrays == 0 does
+ * nothing.  The host form also checks every origin_of[i] against [0, norigins) before anything touches the device
+ * (MIRT_ERR_INVALID_ARGUMENT, nothing written); the device form cannot look: there a ray whose index lies outside the range reads
+ * nothing out of bounds and leaves its record's 20 bytes unwritten.  The _device form is queued like mirt_intersect_from_device;
+ * neither form touches mirt_get_stats or mirt_get_query_stats.
+ * How it is answered.  The origins go into cubes of up to MIRT_MAX_LIGHTS positions each (fewer where the sort's key space
+ * allows fewer at the scene's grid), built in one binning chain per cube; a call with more origins runs in passes over consecutive
+ * ranges of the list, each pass over all rays.  One cube is kept for these calls, apart from mirt_intersect_from*'s and
+ * DirectLight's, keyed by scene version, positions and their order; a pass whose positions are exactly those the frame path's or
+ * DirectLight's cube holds reads that cube and builds nothing.  mirt_set_query_mode: BRUTE never builds a cube (the rays are
+ * written out on the device and go through mirt_intersect_device's kernels); BINNED bins whenever the frame path would; AUTO uses
+ * the single fan's rule -- 2000 triangles or more, or MIRT_BIN_THRESHOLD triangles or more and nrays x triangles >= 4e7, or the
+ * cubes of these origins are held -- which is MEASURED FOR ONE ORIGIN ONLY, with one condition more that the measurement of
+ * several origins showed (profiles/ray_query_bench.txt, section `fans`): unless the cubes are held, a call of at most
+ * MIRT_QUERY_WAVE_RAYS rays (4096) does not bin -- the brute path answers those a wave per ray and was ahead of every build.
+ * Measured there (1 .. 128 origins x 64 .. 65536 rays each, 2000 and 100 000 triangles): one call with its builds was behind K
+ * mirt_intersect_from_device calls on the same rays nowhere (K = 32: 9 to 30 times ahead); under AUTO it stayed behind
+ * BRUTE in two cells at 2000 triangles, 4 origins x 4096 rays (0.60 against 0.53 ms) and 128 origins x 64 rays (1.30 against 0.53
+ * ms).  Whatever the mode, the WHOLE call takes the brute path when the frame path would not bin one of its parts: a scene
+ * coordinate, or any component of any origin, that is not finite or not below 1e8. */
+MIRT_API int mirt_intersect_fans(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, mirt_hit *hits);
+MIRT_API int mirt_intersect_fans_device(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, void *d_hits);
+/* mirt_get_fan_stats reports the last call of EITHER fan entry point.  For mirt_intersect_fans* the four counters are summed over
+ * the passes (fallback_records: the rays that swept), cube_bins and shells are the last pass's, and cube_source is 0 none, 1 some
+ * pass built a cube, 2 every pass's cube was held from an earlier call, 3 every pass read the frame path's cube, 4 every pass read
+ * DirectLight's cube.  mirt_intersect_from* keeps reporting 0 - 2. */
+
 /* ---- rasteriser: replaces Update()'s clear + Draw() + CalculateDOF() of rasteriser.cpp:183-192,461-529 */
 
 /* One frame into host buffers.  Every word of out_xrgb is written: the whole surface is cleared to black

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan]
+"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans]
 
 The measurements of the ray-query kernels (query/rt_query.hip), written to one text file:
 
@@ -21,6 +21,11 @@ The measurements of the ray-query kernels (query/rt_query.hip), written to one t
                        hashed and compared.  Then the ray count swept in powers of two at n = 100 000 and n = 2 000 (rays of the
                        frame in a fixed shuffled order): the smallest call from which binned-with-build stays ahead of the fan's own
                        sweep is where MIRT_QUERY_AUTO should switch for fans (it starts from the frame path's 4e7, unmeasured).
+  fans                 mirt_intersect_fans_device on soup100k and on the soup of 2000: K = 1, 4, 32, 128 origins inside the scene x 64,
+                       4096, 65536 rays per origin (grouped by origin), under MIRT_QUERY_BINNED with every pass's cube built by the call
+                       (origin 0 moves by one ulp between the calls), with the cube kept (K <= 32) and under MIRT_QUERY_BRUTE, beside
+                       the yardstick: K consecutive mirt_intersect_from_device calls on the same rays.  One digest over all records of
+                       every variant; where the one call is behind the K calls, and where AUTO's rule is behind brute force, is listed.
 
 The knob is read once per process, so every GPU step is a child process of its own, under its own `timeout`; a step that fails
 ends the run."""
@@ -479,6 +484,119 @@ def step_fan(p):
         p("")
 
 
+FANS_K = (1, 4, 32, 128)
+FANS_R = (64, 4096, 65536)
+
+
+def child_fans(n):
+    """mirt_intersect_fans_device against K consecutive mirt_intersect_from_device calls on the same rays, grouped by origin."""
+    import hashlib
+    import mirt
+    h = hip()
+    mirt.init(0)
+    mirt.scene_upload(mirt.scene_soup(1, n, 0.05 if n >= 50000 else 0.2))
+    rng = np.random.default_rng(9)
+    all_origins = rng.uniform(-0.5, 0.5, (max(FANS_K), 3)).astype(np.float32)          # inside the scene
+    for K in FANS_K:
+        for R in FANS_R:
+            origins = np.ascontiguousarray(all_origins[:K])
+            count = K * R
+            of = np.repeat(np.arange(K, dtype=np.int32), R)
+            dirs = np.ascontiguousarray(rng.uniform(-1.0, 1.0, (count, 3)).astype(np.float32) - origins[of])
+            fresh = mirt.fresh_hits(count)
+            d_of, d_dirs, d_hits = dev_alloc(h, of.nbytes, of), dev_alloc(h, dirs.nbytes, dirs), dev_alloc(h, fresh.nbytes, fresh)
+            got = np.zeros(count, mirt.HIT_DTYPE)
+            reps = 5 if count <= 1 << 18 else 3
+
+            def nudged(i):
+                """Origin 0 moved by i ulps: other cube keys, the same work."""
+                o = origins.copy()
+                for _ in range(i):
+                    o[0, 0] = np.nextafter(o[0, 0], np.float32(1))
+                return o
+
+            def one_call(o):
+                mirt.intersect_fans_device(o, d_of, d_dirs, count, d_hits)
+
+            def k_calls(o):
+                for k in range(K):
+                    mirt.intersect_from_device(o[k], C.c_void_p(d_dirs.value + 12 * k * R), R, C.c_void_p(d_hits.value + 20 * k * R))
+
+            def run(fn, o):
+                assert h.hipMemcpy(d_hits, fresh.ctypes.data_as(C.c_void_p), fresh.nbytes, 1) == 0
+                t0 = time.perf_counter()
+                fn(o); mirt.sync()
+                return (time.perf_counter() - t0) * 1e3
+
+            def digest():
+                assert h.hipMemcpy(got.ctypes.data_as(C.c_void_p), d_hits, got.nbytes, 2) == 0
+                return hashlib.sha1(got.tobytes()).hexdigest()[:16]
+
+            ms, dg = {}, {}
+            mirt.set_query_mode(mirt.QUERY_BINNED)
+            ts = []
+            for i in range(reps + 1):                   # (never the keys of the call before: every pass builds its cube)
+                ts.append(run(one_call, nudged(1 + i)))
+                assert mirt.fan_stats()["cube_source"] == 1
+            ms["built"] = float(np.median(ts[1:]))
+            run(one_call, origins)
+            st = mirt.fan_stats()
+            dg["built"] = digest()
+            if K <= mirt.MAX_LIGHTS:                     # (more origins than a cube holds: only the last range's cube is kept)
+                ts = [run(one_call, origins) for _ in range(reps + 1)]
+                assert mirt.fan_stats()["cube_source"] == 2
+                ms["kept"] = float(np.median(ts[1:]))
+                dg["kept"] = digest()
+            mirt.set_query_mode(mirt.QUERY_BRUTE)
+            ts = [run(one_call, origins) for _ in range(reps + 1)]
+            assert mirt.fan_stats()["mode_used"] == mirt.QUERY_BRUTE
+            ms["brute"] = float(np.median(ts[1:]))
+            dg["brute"] = digest()
+            mirt.set_query_mode(mirt.QUERY_AUTO)         # the yardstick as a caller of the single fan meets it
+            ts = [run(k_calls, nudged(1 + i)) for i in range(reps + 1)]
+            ms["yard"] = float(np.median(ts[1:]))
+            run(k_calls, origins)
+            yard_mode = mirt.fan_stats()["mode_used"]
+            dg["yard"] = digest()
+            same = len(set(dg.values())) == 1
+            print("RESULT fans n %6d K %3d rays/origin %6d grid %3d  built %10.4f  kept %s  brute %10.4f  K calls (%s) %10.4f ms  digest %s %s"
+                  % (n, K, R, st["cube_bins"], ms["built"], "%10.4f" % ms["kept"] if "kept" in ms else "         -", ms["brute"],
+                     "binned" if yard_mode == mirt.QUERY_BINNED else "brute", ms["yard"], dg["yard"], "same" if same else "DIFFERENT %r" % dg))
+            sys.stdout.flush()
+            for d in (d_of, d_dirs, d_hits):
+                h.hipFree(d)
+            if not same:
+                sys.exit(1)
+    mirt.shutdown()
+
+
+def step_fans(p):
+    p("== fans: mirt_intersect_fans_device, K origins inside the scene x rays per origin, rays grouped by origin (host clock around call + mirt_sync, medians) ==")
+    p("built: BINNED, every pass builds its cube; kept: BINNED, the cube held (K <= 32); brute: BRUTE (expansion + mirt_intersect_device's kernels);")
+    p("K calls: the yardstick, K consecutive mirt_intersect_from_device calls under AUTO, a cube built per call.  One digest over all records of every variant.")
+    out = "".join(run_child(p, ["--child", "fans", str(n)], {}, 540) for n in (100000, 2000))
+    fans_summary(out, p)
+
+
+FANS_ROW = re.compile(r"fans n\s+(\d+) K\s+(\d+) rays/origin\s+(\d+) grid\s+\d+  built\s+([0-9.]+)  kept\s+\S+  brute\s+([0-9.]+)  K calls \(\w+\)\s+([0-9.]+) ms")
+
+
+def fans_summary(text, p):
+    """Where the one call is behind the K calls, and where binning with the builds is behind the brute path -- apart for the calls
+    AUTO bins without a cube held (more than MIRT_QUERY_WAVE_RAYS = 4096 rays at these scene sizes) and those it does not."""
+    rows = [(int(m.group(1)), int(m.group(2)), int(m.group(3)), float(m.group(4)), float(m.group(5)), float(m.group(6))) for m in FANS_ROW.finditer(text)]
+    cell = lambda n, K, R: "n %d K %d rays/origin %d" % (n, K, R)
+    behind = ["%s: %.3f ms against %.3f ms" % (cell(n, K, R), b, y) for n, K, R, b, _, y in rows if K > 1 and b > y]
+    p("one call with its builds behind the K calls (K > 1), of %d cells: %s" % (len(rows), "; ".join(behind) if behind else "nowhere"))
+    small = [(n, K, R, b, br) for n, K, R, b, br, _ in rows if K * R <= 4096]
+    large = [(n, K, R, b, br) for n, K, R, b, br, _ in rows if K * R > 4096]
+    p("calls of at most 4096 rays (AUTO takes the brute path unless the cubes are held): brute ahead of binning with the builds in %d of %d cells"
+      % (sum(br < b for _, _, _, b, br in small), len(small)))
+    wrong = ["%s: built %.3f ms, brute %.3f ms" % (cell(n, K, R), b, br) for n, K, R, b, br in large if b > br]
+    p("calls of more than 4096 rays (AUTO bins): binning with the builds behind brute at: %s" % ("; ".join(wrong) if wrong else "nowhere"))
+    p("")
+
+
 def run_child(p, args, env, limit):
     cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__)] + args
     r = subprocess.run(cmd, env=dict(os.environ, **env), capture_output=True, text=True)
@@ -539,6 +657,8 @@ def main():
             return child_fan(a.child[1])
         if a.child[0] == "fansweep":
             return child_fansweep(a.child[1], int(a.child[2]))
+        if a.child[0] == "fans":
+            return child_fans(int(a.child[1]))
         return child_throughput() if a.child[0] == "throughput" else child_sweep(int(a.child[1]))
     lines = []
 
@@ -559,6 +679,8 @@ def main():
             step_directlight(p)
         if "fan" in steps:
             step_fan(p)
+        if "fans" in steps:
+            step_fans(p)
     finally:
         with open(a.out, "a" if a.append else "w") as f:
             f.write("\n".join(lines) + "\n")
