@@ -6,47 +6,64 @@ namespace mirt {
 
 // ---- binned ray tracing ---------------------------------------------------------------------------------------------
 
-// Makes room for `cap` (bin, triangle) pairs in a stream's pair list, its sorted copy and the sort's scratch.
-int ensure_pairs(RtScratch &S, size_t cap)
+int PairList::ensure(size_t cap)
 {
     int r;
-    if ((r = dev_realloc(&S.d_entries, cap)) || (r = dev_realloc(&S.d_pair_keys, cap)) || (r = dev_realloc(&S.d_pair_vals, cap)) ||
-        (r = dev_realloc(&S.d_sorted_keys, cap)) || (r = dev_realloc(&S.d_tmp_vals, cap))) { S.cap_entries = 0; return r; }
-    S.cap_entries = (uint32_t)cap;
+    if ((r = dev_realloc(&d_entries, cap)) || (r = dev_realloc(&d_pair_keys, cap)) || (r = dev_realloc(&d_pair_vals, cap)) ||
+        (r = dev_realloc(&d_sorted_keys, cap)) || (r = dev_realloc(&d_tmp_vals, cap))) { cap_entries = 0; return r; }
+    cap_entries = (uint32_t)cap;
     return MIRT_OK;
 }
 
 // (BIN_MAX_KEYS, the most sort keys one binning pass may use: cube_plan.hpp)
 
-// Picks up the pair count an earlier frame of the stream has published (pinned word + event), if it has landed.
-void poll_pair_count(RtScratch &S)
+void PairList::poll()
 {
-    if (S.count_pending && hipEventQuery(S.ev_count) == hipSuccess) {
-        S.known_pairs = *S.h_count; S.have_known = true; S.count_pending = false;
+    if (count_pending && hipEventQuery(ev_count) == hipSuccess) {
+        known_pairs = *h_count; have_known = true; count_pending = false;
     }
     (void)hipGetLastError();                                 // (hipErrorNotReady of the query is not an error)
 }
 
-// One binning pass on g.stream: (key, triangle) pairs of `bs`' frames into S' pair list, ordered by key into S.d_entries /
+// (the event that tells a later frame the count has landed is recorded BEHIND the frame's trace kernel: an event record between
+// two kernels of the chain is a barrier packet of its own, ~5 us of the single frame's latency)
+int PairList::record_count()
+{
+    if (!count_event_due) return MIRT_OK;
+    count_event_due = false;
+    HIP_TRY(hipEventRecord(ev_count, g.stream));
+    count_pending = true;
+    return MIRT_OK;
+}
+
+// The one decision about the pass a stream holds.  When NOTHING a pass depends on has changed since the stream's last one -- the
+// view stands still while a light key, a toggle or nothing at all asks for a frame (raytracer.cpp:385-537 set isUpdated without
+// touching cameraPos / yaw) -- the stream still holds that pass's tables and the frame starts at the trace kernel
+// (MIRT_BIN_REUSE=0: never); the rules: pass_plan.hpp.
+PassPlan KeptPass::plan_for(uint64_t key, int mode, PairList &P) const
+{
+    static const bool reuse_off = env_int("MIRT_BIN_REUSE", 1) == 0;
+    P.poll();
+    return kept_pass_plan(bin_key_valid, bin_key == key, P.have_known, P.known_pairs > P.cap_used, last_bin_mode == mode, reuse_off);
+}
+
+// One binning pass on g.stream: (key, triangle) pairs of `bs`' frames into the pair list S, ordered by key into S.d_entries /
 // S.d_sorted_keys, offsets into bin_off.  `counter` (device, zeroed by the caller's previous kernel) receives the pair
-// count.  The list is sized from a count only the device knows: when `fresh` it is read back (4 bytes + one sync of this
-// stream) and the pass repeated if the list was too small; otherwise *npairs, the count of the identical pass before, holds.
+// count.  The list is sized from a count only the device knows: it is read back (4 bytes + one sync of this stream) and the
+// pass repeated if the list was too small, and *npairs is the count.
 // A pass that may not read back (`may_guess`) sizes the list from the count an earlier pass published and publishes its own;
 // a list that turns out too small makes the frame's kernels take the brute-force path (k_rt_trace2) and the NEXT pass grow it.
-int bin_pass(RtScratch &S, BinSet bs, const OriginRow *cam_tab, const OriginRow *light_tab, uint32_t *counter, uint32_t *bin_off,
-             bool fresh, uint32_t *npairs, bool may_guess = false)
+int bin_pass(PairList &S, BinSet bs, const OriginRow *cam_tab, const OriginRow *light_tab, uint32_t *counter, uint32_t *bin_off,
+             uint32_t *npairs, bool may_guess = false)
 {
     int rc;
-    poll_pair_count(S);                                      // a count an earlier frame left behind?
-    // A pass identical to the one before it (same view, same scene) normally reuses that pass's count without looking; but if
-    // that pass was itself a guess and its published count shows the list was too small, the frame fell back to brute force
-    // and so would every later frame of this view: treat it as fresh again so that the list grows.
-    if (!fresh && may_guess && S.have_known && S.known_pairs > S.cap_used) fresh = true;
-    const bool guess = fresh && may_guess && S.have_known;
+    S.count_event_due = false;
+    S.poll();                                                // a count an earlier frame left behind?
+    const bool guess = may_guess && S.have_known;
     if (!S.d_entries || !S.cap_entries) {
         // first capacity of the pair list (grown on demand below); MIRT_BIN_INITIAL_PAIRS lets a test start small
         static const size_t initial = [] { const long v = env_int("MIRT_BIN_INITIAL_PAIRS", 0); return v > 0 ? (size_t)v : (size_t)1 << 20; }();
-        if ((rc = ensure_pairs(S, initial))) return rc;
+        if ((rc = S.ensure(initial))) return rc;
     }
     if (bs.nbins > BIN_MAX_KEYS) return fail(MIRT_ERR_INVALID_ARGUMENT, "binning: %u sort keys exceed the %u the bucket sort holds", bs.nbins, BIN_MAX_KEYS);
     // workgroups striding over the (256-triangle chunk, frame) work items: 8 per CU (52 KiB of LDS and 512 threads each, 3 resident; 1 M
@@ -58,10 +75,8 @@ int bin_pass(RtScratch &S, BinSet bs, const OriginRow *cam_tab, const OriginRow 
     // two more launches sort)
     const uint32_t nbuckets = bucket_sort_buckets(bs.nbins);
     if (nbuckets + 1 > S.cap_buckets) {
-        S.cap_buckets = 0;
-        if ((rc = dev_realloc(&S.d_bucket, (size_t)3 * (nbuckets + 1)))) return rc;
+        if ((rc = dev_grow(&S.d_bucket, &S.cap_buckets, nbuckets + 1, (size_t)3 * (nbuckets + 1), false))) return rc;
         HIP_TRY(hipMemsetAsync(S.d_bucket, 0, sizeof(uint32_t) * 3 * (nbuckets + 1), g.stream));
-        S.cap_buckets = nbuckets + 1;
         S.bucket_dirty = false;
     }
     uint32_t *bcnt = S.d_bucket, *bbase = S.d_bucket + S.cap_buckets, *bcur = S.d_bucket + 2 * (size_t)S.cap_buckets;
@@ -78,13 +93,10 @@ int bin_pass(RtScratch &S, BinSet bs, const OriginRow *cam_tab, const OriginRow 
     // enough for that to matter --, of 512 for the large scenes and for the frame that runs alone, whose latency they serve (rt_binned.hip)
     static const int bin_wg_env = (int)env_int("MIRT_BIN_WG", 0);
     const int bin_wg = (bin_wg_env == 256 || bin_wg_env == 512) ? bin_wg_env : ((g.n < 400000 && g.in_flight >= 3) ? 256 : 512);
-    if (guess) {
-        // room for half as many pairs again as the last frame seen produced; growing needs this stream idle (rare)
-        const size_t want = (size_t)S.known_pairs + S.known_pairs / 2 + 4096;
-        if (want > S.cap_entries) {
-            HIP_TRY(hipStreamSynchronize(g.stream));
-            if ((rc = ensure_pairs(S, want + want / 4))) return rc;
-        }
+    // a guessed list: room for half as many pairs again as the last frame seen produced; growing needs this stream idle (rare)
+    if (guess && pairs_wanted(S.known_pairs) > S.cap_entries) {
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        if ((rc = S.ensure(pairs_grown(pairs_wanted(S.known_pairs))))) return rc;
     }
     bool publish_count = false;
     for (int attempt = 0; attempt < 2; attempt++) {
@@ -98,7 +110,6 @@ int bin_pass(RtScratch &S, BinSet bs, const OriginRow *cam_tab, const OriginRow 
         S.bucket_dirty = true;                               // bucket counts pending until k_bs_local has consumed them
         if (bin_wg == 256) hipLaunchKernelGGL(k_bin_pairs<256>, bin_grid, dim3(256), bin_lds, g.stream, g.d_tris, cam_tab, light_tab, g.n, bs, pairs);
         else hipLaunchKernelGGL(k_bin_pairs<512>, bin_grid, dim3(512), bin_lds, g.stream, g.d_tris, cam_tab, light_tab, g.n, bs, pairs);
-        if (!fresh) break;
         if (guess) {
             // no sync: k_bs_scatter stores the count into a pinned word behind the kernel and a later frame picks it up
             if (!S.h_count) {
@@ -117,10 +128,10 @@ int bin_pass(RtScratch &S, BinSet bs, const OriginRow *cam_tab, const OriginRow 
         S.count_pending = false;                             // (a count still on its way belongs to an earlier pass, maybe of another kind)
         if (total <= S.cap_entries) break;
         if (attempt == 1) return fail(MIRT_ERR_HIP, "binning produced %u pairs twice with room for %u", total, S.cap_entries);
-        if ((rc = ensure_pairs(S, (size_t)total + total / 8 + 4096))) return rc;
+        if ((rc = S.ensure(pairs_after_readback(total)))) return rc;
     }
 #ifdef MIRT_BIN_STATS
-    if (fresh) {
+    {
         uint32_t c[16];
         (void)hipMemcpy(c, counter, 64, hipMemcpyDeviceToHost);
         fprintf(stderr, "[mirt bin stats] flattened units=%u max per work item=%u direct items=%u | huge: box valid=%u no box=%u (camera frame %u) waves in the joint test=%u\n", c[8], c[9], c[10], c[11], c[12], c[14], c[15]);
@@ -134,111 +145,61 @@ int bin_pass(RtScratch &S, BinSet bs, const OriginRow *cam_tab, const OriginRow 
     HIP_TRY(bucket_sort_pairs(S.d_pair_keys, S.d_pair_vals, counter, S.cap_used, *npairs, bs.nbins, S.d_sorted_keys, S.d_tmp_vals,
                               bcnt, bbase, bcur, bin_off, S.d_entries, g.cu_count, g.stream, count_out));
     S.bucket_dirty = false;                                  // k_bs_local leaves the counts and cursors zero
-    // (the event that tells a later frame the count has landed is recorded by the caller BEHIND the frame's trace kernel: an event
-    // record between two kernels of the chain is a barrier packet of its own, ~5 us of the single frame's latency)
-    if (publish_count) S.count_event_due = true;
+    S.count_event_due = publish_count;                       // (record_count, behind the frame's trace kernel)
     return MIRT_OK;
 }
 
 // Key of what the light-cube bins depend on: the scene and the light positions.
 uint64_t light_key_of(const float *origins, int nlights)
 {
-    uint64_t key = 0xcbf29ce484222325ull ^ g.scene_version;
-    auto mix = [&](const void *p, size_t nb) { const unsigned char *b = (const unsigned char *)p; for (size_t i = 0; i < nb; i++) { key ^= b[i]; key *= 0x100000001b3ull; } };
-    mix(origins + 3, sizeof(float) * 3 * nlights); mix(&nlights, 4); mix(&g.n, 4);
-    return key;
+    return Fnv(g.scene_version).mix(origins + 3, sizeof(float) * 3 * nlights).mix(&nlights, 4).mix(&g.n, 4).h;
 }
 
-// Nearest and farthest distance from `pos` to the scene's bounding box: the range the depth shells of a ray family divide.
-bool shell_range(const float *pos, double *dn, double *df)
-{
-    double n2 = 0.0, f2 = 0.0;
-    for (int c = 0; c < 3; c++) {
-        const double p = pos[c], lo = g.bbox_lo[c], hi = g.bbox_hi[c];
-        const double near = p < lo ? lo - p : (p > hi ? p - hi : 0.0), far = std::max(std::fabs(p - lo), std::fabs(p - hi));
-        n2 += near * near; f2 += far * far;
-    }
-    *dn = std::sqrt(n2); *df = std::sqrt(f2);
-    return std::isfinite(*dn) && std::isfinite(*df) && *df > *dn;
-}
-
-// Frame descriptors of the light cubes: six faces of B x B bins around every light position, every bin's list ordered in
-// `shells` depth shells of the candidates' `near` bound (sort key = (base + bin) * shells + shell; `base_bins` = where light 0's
-// face 0 starts, in bins of `shells` keys).  A shadow ray walks only the shells up to the one its 0.99 r falls into (k_rt_trace2).
-// Light position k is origins[3 * (k + 1) ..]: row 0 is the camera's.
-void fill_light_frames(BinFrameDesc *frames, const float *origins, int nlights, int cube_bins, int shells, uint32_t base_bins)
-{
-    memset(frames, 0, sizeof(BinFrameDesc) * 6 * nlights);
-    for (int k = 0; k < nlights; k++) {
-        const float *lpos = origins + 3 * (k + 1);
-        double dn = 0.0, df = 0.0;
-        const bool okr = shell_range(lpos, &dn, &df);
-        for (int face = 0; face < 6; face++) {
-            BinFrameDesc &d = frames[k * 6 + face];
-            const int ax = face >> 1;
-            d.P0[ax] = (face & 1) ? -1.0f : 1.0f;         // negD ~ s*e_k + u*e_(k+1) + v*e_(k+2)
-            d.Pu[(ax + 1) % 3] = 1.0f;
-            d.Pv[(ax + 2) % 3] = 1.0f;
-            d.rw[ax] = d.P0[ax]; d.ru[(ax + 1) % 3] = 1.0f; d.rv[(ax + 2) % 3] = 1.0f;   // g = m*(s e_k + u e_k1 + v e_k2)
-            memcpy(d.S, lpos, 12);                            // light position k (jittered sample with soft shadows)
-            d.dmax = 2.0f;
-            d.ulo = -1.0f; d.vlo = -1.0f; d.du = 2.0f / (float)cube_bins; d.dv = 2.0f / (float)cube_bins;
-            d.pad_lo = -3.814697265625e-06f; d.pad_hi = 3.814697265625e-06f;
-            d.nbu = cube_bins; d.nbv = cube_bins; d.j0 = 0; d.j1 = cube_bins;
-            d.base = base_bins; d.tab = 1 + k;
-            // every face of every light carries `shells` keys per bin (the key layout needs one count for all); a light whose
-            // range is degenerate puts everything into shell 0
-            d.nshell = shells;
-            d.shell_d0 = (float)dn;
-            d.shell_iw = okr ? (float)(shells / (df - dn)) : 0.0f;
-            base_bins += (uint32_t)(cube_bins * cube_bins);
-        }
-    }
-}
-
-// Depth shells per light-cube bin: as many as the sort's key space allows, at most 16 (a bin's list grows with the square of
-// the distance from the light; 16 shells leave a ray at a quarter of the scene's depth ~2 % of it).
+// (shell_range, fill_light_frames and the shell counts' rules: pass_plan.hpp)
 int light_shells_for(int nlights, int cube_bins, uint32_t keys_in_front)
 {
     static const int env = (int)env_int("MIRT_LIGHT_SHELLS", 0);
-    const long long bins = 6ll * cube_bins * cube_bins * std::max(nlights, 1);
-    int ns = (env >= 1 && env <= 64) ? env : 16;
-    while (ns > 1 && bins * ns + keys_in_front + 64 > (long long)BIN_MAX_KEYS) ns >>= 1;
-    return ns;
+    return light_shells_rule(nlights, cube_bins, keys_in_front, env);
 }
 
-constexpr size_t LIGHT_COUNTER_BYTES = sizeof(uint32_t) * (128 + 6 * MIRT_MAX_LIGHTS);
-// Room for the face lists of `nlights` light cubes (k_select_faces) in a stream's LIGHT scratch set; the stream must be idle when they grow.
-int ensure_face_lists(RtScratch &S, int nlights)
+// Room for the face lists of `nlights` light cubes (k_select_faces) in a stream's light pass; the stream must be idle when they grow.
+int ensure_face_lists(LightPass &S, int nlights)
 {
     int rc;
-    if (!S.d_bin_counters) {
-        // the light pass's counters and the face lists' lengths in ONE block (a pass zeroes it with one fill): words 0..127 as in the
-        // camera's block, 128.. the face counts
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_bin_counters), LIGHT_COUNTER_BYTES));
-        HIP_TRY(hipMemsetAsync(S.d_bin_counters, 0, LIGHT_COUNTER_BYTES, g.stream));
-        S.d_face_counts = S.d_bin_counters + 128;
-    }
+    // the light pass's counters and the face lists' lengths in ONE block (a pass zeroes it with one fill): words 0..127 as in the
+    // camera's block, 128.. the face counts
+    if ((rc = S.ensure_counters(LIGHT_COUNTER_BYTES))) return rc;
+    S.d_face_counts = S.d_bin_counters + 128;
     const size_t want = (size_t)6 * (size_t)nlights * (size_t)g.n;
-    if (want > S.cap_face_sel) {
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        S.cap_face_sel = 0;
-        if ((rc = dev_realloc(&S.d_face_sel, want))) return rc;
-        S.cap_face_sel = want;
-    }
+    if (want > S.cap_face_sel && (rc = dev_grow(&S.d_face_sel, &S.cap_face_sel, want, want, true))) return rc;
     return MIRT_OK;
+}
+
+// The build chain of `nlights` light cubes on g.stream in the light pass S, from the descriptors and origins the caller has
+// uploaded: the lights' origin rows into light_tab and per face the triangles it can see (k_select_faces), then the binning pass
+// over those lists -- nkeys keys, offsets into bin_off, the pair count into `counter` (zeroed by the caller) and *npairs.
+static int cube_bin_chain(LightPass &S, const BinFrameDesc *d_frames, const float *d_origins, int nlights, uint32_t nkeys, OriginRow *light_tab,
+                          uint32_t *bin_off, uint32_t *counter, uint32_t *npairs, bool may_guess)
+{
+    hipLaunchKernelGGL(k_select_faces, dim3((unsigned)std::min<long long>(((long long)g.n + 1023) / 1024, (long long)g.cu_count), nlights), dim3(1024), 0, g.stream,
+                       g.d_tris, g.n, d_origins, d_frames, light_tab, S.d_face_sel, (uint32_t)g.n, S.d_face_counts);
+    BinSet bs;
+    memset(&bs, 0, sizeof bs);
+    bs.frames = d_frames; bs.nframes = 6 * nlights; bs.nbins = nkeys; bs.bin_off = bin_off;
+    bs.face_lists = S.d_face_sel; bs.face_counts = S.d_face_counts; bs.face_stride = (uint32_t)g.n;
+    return bin_pass(S.pairs, bs, nullptr, light_tab, counter, bin_off, npairs, may_guess);
 }
 
 // The SHARED light-cube bins and their expanded rows, for lights that stand still: built on g.stream as a barrier call -- the
 // frames of both streams read the tables -- whenever the scene, a light position or the grid differs from what is held.  (Lights
 // that just moved do not come here: binned_pass bins their cubes together with the camera frame, on the frame's own stream.)
 // C: the frame path's shared cube (g.lc) or the queries' (g.qrows.cube); either is read by the work of every stream.
-int light_cache_ensure(LightCache &C, RtScratch &S, const float *origins, int nlights, int cube_bins, bool *built)
+int light_cache_ensure(LightCache &C, LightPass &S, const float *origins, int nlights, int cube_bins, bool *built)
 {
     int rc;
     const uint64_t key = light_key_of(origins, nlights);
     if (built) *built = false;
-    if (C.valid && C.key == key && C.cube_bins == cube_bins) return MIRT_OK;
+    if (C.holds(key, cube_bins)) return MIRT_OK;
     if (built) *built = true;
     C.valid = false;
     for (int o = 0; o < g.in_flight; o++)                  // frames of the other streams may still read the old tables
@@ -248,16 +209,9 @@ int light_cache_ensure(LightCache &C, RtScratch &S, const float *origins, int nl
         }
     const int shells = light_shells_for(nlights, cube_bins, 0u);
     const uint32_t per_light = 6u * (uint32_t)(cube_bins * cube_bins) * (uint32_t)shells, nkeys = per_light * (uint32_t)nlights;
-    if ((size_t)nlights * g.n > C.cap_tab) {
-        C.cap_tab = 0;
-        if ((rc = dev_realloc(&C.d_light_tab, (size_t)nlights * g.n))) return rc;
-        C.cap_tab = (size_t)nlights * g.n;
-    }
-    if (nkeys + 1 > C.cap_bins) {
-        C.cap_bins = 0;
-        if ((rc = dev_realloc(&C.d_off, (size_t)nkeys + 1))) return rc;
-        C.cap_bins = nkeys + 1;
-    }
+    const size_t tab_rows = (size_t)nlights * g.n;
+    if (tab_rows > C.cap_tab && (rc = dev_grow(&C.d_light_tab, &C.cap_tab, tab_rows, tab_rows, false))) return rc;
+    if (nkeys + 1 > C.cap_bins && (rc = dev_grow(&C.d_off, &C.cap_bins, nkeys + 1, (size_t)nkeys + 1, false))) return rc;
     if (!C.d_frames) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&C.d_frames), sizeof(BinFrameDesc) * 6 * MIRT_MAX_LIGHTS));
     if (!C.d_origins) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&C.d_origins), sizeof(float) * 3 * (1 + MIRT_MAX_LIGHTS)));
     if (!C.d_counter) { HIP_TRY(hipMalloc(reinterpret_cast<void **>(&C.d_counter), 512)); HIP_TRY(hipMemsetAsync(C.d_counter, 0, 512, g.stream)); }   // (k_prep_origin zeroes words 0 and 16..79 of a pass's counter block)   // (ON the stream: see zero-fill note at S.d_bin_counters)
@@ -266,36 +220,27 @@ int light_cache_ensure(LightCache &C, RtScratch &S, const float *origins, int nl
     C.shells = shells;
     if (nlights > 0) {
         BinFrameDesc frames[6 * MIRT_MAX_LIGHTS];
-        fill_light_frames(frames, origins, nlights, cube_bins, shells, 0u);
+        fill_light_frames(frames, origins, nlights, cube_bins, shells, 0u, g.bbox_lo, g.bbox_hi);
         HIP_TRY(upload_small(C.d_frames, frames, sizeof(BinFrameDesc) * 6 * nlights, g.stream));
         HIP_TRY(upload_small(C.d_origins, origins, sizeof(float) * 3 * (1 + nlights), g.stream));
-        // the lights' origin rows, and per face the triangles it can see (k_select_faces); the build's pair counter is zeroed on the way
+        // the face lists' lengths and the build's pair counter are zeroed on the way
         if ((rc = ensure_face_lists(S, nlights))) return rc;
         HIP_TRY(hipMemsetAsync(S.d_face_counts, 0, sizeof(uint32_t) * 6 * nlights, g.stream));
         HIP_TRY(hipMemsetAsync(C.d_counter, 0, 512, g.stream));
-        S.count_event_due = false;
-        hipLaunchKernelGGL(k_select_faces, dim3((unsigned)std::min<long long>(((long long)g.n + 1023) / 1024, (long long)g.cu_count), nlights), dim3(1024), 0, g.stream,
-                           g.d_tris, g.n, C.d_origins, C.d_frames, C.d_light_tab, S.d_face_sel, (uint32_t)g.n, S.d_face_counts);
-        BinSet bs;
-        memset(&bs, 0, sizeof bs);
-        bs.frames = C.d_frames; bs.nframes = 6 * nlights; bs.nbins = nkeys; bs.bin_off = C.d_off;
-        bs.face_lists = S.d_face_sel; bs.face_counts = S.d_face_counts; bs.face_stride = (uint32_t)g.n;
-        uint32_t npairs = 0;
-        if ((rc = bin_pass(S, bs, nullptr, C.d_light_tab, C.d_counter, C.d_off, true, &npairs))) return rc;
-        S.count_event_due = false;                           // (a fresh pass without a guess reads its count back: nothing was published)
+        uint32_t npairs = 0;                                 // (read back: a build never guesses)
+        if ((rc = cube_bin_chain(S, C.d_frames, C.d_origins, nlights, nkeys, C.d_light_tab, C.d_off, C.d_counter, &npairs, false))) return rc;
         if (npairs > C.cap_rows) {
+            const size_t rows = (size_t)npairs + npairs / 8 + 1024;
             C.cap_rows = 0;
-            if ((rc = dev_realloc(&C.d_rows, (size_t)npairs + npairs / 8 + 1024))) return rc;
-            if ((rc = dev_realloc(&C.d_row_tri, (size_t)npairs + npairs / 8 + 1024))) return rc;
-            C.cap_rows = npairs + npairs / 8 + 1024;
+            if ((rc = dev_realloc(&C.d_rows, rows)) || (rc = dev_realloc(&C.d_row_tri, rows))) return rc;
+            C.cap_rows = (uint32_t)rows;
         }
         C.nrows = npairs;
         if (npairs)
             hipLaunchKernelGGL(k_expand_light_rows, dim3((unsigned)std::min<uint32_t>((npairs + 255) / 256, 4096u)), dim3(256), 0, g.stream,
-                               C.d_off, S.d_entries, nlights, per_light, C.d_light_tab, g.n, C.d_rows, (const uint32_t *)nullptr, 0u, C.d_row_tri);
+                               C.d_off, S.pairs.d_entries, nlights, per_light, C.d_light_tab, g.n, C.d_rows, (const uint32_t *)nullptr, 0u, C.d_row_tri);
         HIP_TRY(hipGetLastError());
-        S.bin_key_valid = false;                             // the stream's pair list now holds the light pass
-        S.last_bin_mode = -1;
+        S.kept = KeptPass();                                 // the stream's pair list now holds the build, a pass of no kind a frame runs
     } else {
         HIP_TRY(hipMemsetAsync(C.d_off, 0, 4, g.stream));
     }
@@ -331,23 +276,6 @@ bool light_keys_fit(int nlights, int cube_bins)
     return cube_keys_fit(nlights, cube_bins);
 }
 
-// Depth shells of the camera bins for a frame of `tiles` bins (the tiles' lists come out of the sort roughly front to back).
-int camera_shells_for(long long tiles)
-{
-    static const int shells_env = (int)env_int("MIRT_CAM_SHELLS", 0);
-    int ns = (int)std::min<long long>(8, std::max<long long>(1, (4ll << 20) / std::max<long long>(tiles, 1)));
-    if (shells_env >= 1 && shells_env <= 64) ns = shells_env;
-    while (ns > 1 && tiles * ns + 64 > (long long)BIN_MAX_KEYS) ns >>= 1;
-    return ns;
-}
-
-// Can a frame of this size be binned at all?  (one sort key per 8 x 8-pixel tile at least)
-bool frame_fits_binning(int W, int H)
-{
-    const long long tiles = (long long)((W + BIN_TILE - 1) / BIN_TILE) * ((H + BIN_TILE - 1) / BIN_TILE);
-    return tiles + 64 <= (long long)BIN_MAX_KEYS;
-}
-
 // A binned frame: camera origin rows, camera-tile bins, trace.  The light-cube bins come from the shared cache when the lights
 // stand still -- the only per-frame binning is then the camera's -- or, for lights that moved within the last
 // LIGHT_STABLE_FRAMES frames, from this frame's own pass: their cubes (CUBE_BINS_MIN bins per side) are binned TOGETHER with the
@@ -356,80 +284,91 @@ bool frame_fits_binning(int W, int H)
 // The reference moves the light with keys as readily as the camera (raytracer.cpp:152-162).
 constexpr int LIGHT_STABLE_FRAMES = 4;
 
-
 // The cubes of lights that MOVE, binned by the frame itself (64 x 64 bins per face): a pass of its own in the stream's light
 // scratch set L -- the lights' origin rows and per-face selection lists (k_select_faces), pairs, sort, expanded rows --, apart from
 // the camera's pass, so that each is kept while only the other one's inputs change: a light key with the camera at rest
 // (raytracer.cpp:152-162, 385-537) re-bins the cubes and nothing else; the camera moving under lights that have not settled into the
 // shared cube yet re-bins the camera frame and nothing else.  *kept: the pass was not run.
-int transient_light_pass(RtScratch &L, const float *origins, int nlights, int cube_bins, int tshells, uint32_t per_light, uint64_t lkey, bool *kept,
+int transient_light_pass(LightPass &L, const float *origins, int nlights, int cube_bins, int tshells, uint32_t per_light, uint64_t lkey, bool *kept,
                          unsigned long long *zero_hits /* nullable: the frame's hit counters, zeroed by the pass's first launch when it runs */)
 {
     int rc;
-    *kept = false;
-    uint64_t key = 0xcbf29ce484222325ull ^ g.scene_version;
-    {
-        auto mix = [&](const void *p, size_t nb) { const unsigned char *b = (const unsigned char *)p; for (size_t i = 0; i < nb; i++) { key ^= b[i]; key *= 0x100000001b3ull; } };
-        mix(&lkey, 8); mix(&cube_bins, 4); mix(&tshells, 4); mix(&g.n, 4); mix(&nlights, 4);
-    }
-    poll_pair_count(L);
-    bool fresh = !L.bin_key_valid || L.bin_key != key;
-    const bool may_guess = L.last_bin_mode == nlights;
-    if (!fresh && L.have_known && L.known_pairs > L.cap_used) fresh = true;   // (a kept list that turned out too small is rebuilt, so that it grows)
-    static const bool reuse_off = env_int("MIRT_BIN_REUSE", 1) == 0;
-    if (!fresh && !reuse_off) { *kept = true; return MIRT_OK; }
+    const uint64_t key = Fnv(g.scene_version).mix(&lkey, 8).mix(&cube_bins, 4).mix(&tshells, 4).mix(&g.n, 4).mix(&nlights, 4).h;
+    const PassPlan plan = L.kept.plan_for(key, nlights, L.pairs);
+    *kept = plan.reuse;
+    if (plan.reuse) return MIRT_OK;
     if ((rc = ensure_face_lists(L, nlights))) return rc;
     if (nlights > L.light_tab_lights || L.light_tab_n != g.n) {
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        L.light_tab_lights = 0;
-        if ((rc = dev_realloc(&L.d_light_tab, (size_t)nlights * g.n))) return rc;
-        L.light_tab_lights = nlights;
+        if ((rc = dev_grow(&L.d_light_tab, &L.light_tab_lights, nlights, (size_t)nlights * g.n, true))) return rc;
         L.light_tab_n = g.n;
     }
     const uint32_t nkeys = per_light * (uint32_t)nlights;
-    if (nkeys + 1 > L.cap_bins) {
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        L.cap_bins = 0;
-        if ((rc = dev_realloc(&L.d_bin_off, (size_t)nkeys + 1))) return rc;
-        L.cap_bins = nkeys + 1;
-    }
+    if (nkeys + 1 > L.cap_bins && (rc = dev_grow(&L.d_bin_off, &L.cap_bins, nkeys + 1, (size_t)nkeys + 1, true))) return rc;
     // frame descriptors of the cubes and the origins in ONE buffer, one upload: [6 * nlights descriptors | (1 + nlights) x 3 floats]
     if (!L.d_frames) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&L.d_frames), sizeof(BinFrameDesc) * (6 * MIRT_MAX_LIGHTS) + sizeof(float) * 3 * (1 + MIRT_MAX_LIGHTS)));
     struct { BinFrameDesc frames[6 * MIRT_MAX_LIGHTS]; float origins[3 * (1 + MIRT_MAX_LIGHTS)]; } up;
     static_assert(sizeof(BinFrameDesc) % 4 == 0, "descriptors are uploaded as words");
-    fill_light_frames(up.frames, origins, nlights, cube_bins, tshells, 0u);
+    fill_light_frames(up.frames, origins, nlights, cube_bins, tshells, 0u, g.bbox_lo, g.bbox_hi);
     float *d_origins = reinterpret_cast<float *>(L.d_frames + 6 * nlights);
     memcpy(reinterpret_cast<char *>(up.frames + 6 * nlights), origins, sizeof(float) * 3 * (1 + nlights));      // (right behind the descriptors in use)
     // (the same launch zeroes the pass's pair counter and the face lists' lengths)
     const ZeroJob zj = { L.d_bin_counters, (int)(LIGHT_COUNTER_BYTES / 4), reinterpret_cast<uint32_t *>(zero_hits), zero_hits ? 2 * HIT_SHARDS * HIT_SHARD_STRIDE : 0 };
     HIP_TRY(upload_small(L.d_frames, &up, sizeof(BinFrameDesc) * 6 * nlights + sizeof(float) * 3 * (1 + nlights), g.stream, &zj));
-    hipLaunchKernelGGL(k_select_faces, dim3((unsigned)std::min<long long>(((long long)g.n + 1023) / 1024, (long long)g.cu_count), nlights), dim3(1024), 0, g.stream,
-                       g.d_tris, g.n, d_origins, L.d_frames, L.d_light_tab, L.d_face_sel, (uint32_t)g.n, L.d_face_counts);
-    BinSet bs;
-    memset(&bs, 0, sizeof bs);
-    bs.frames = L.d_frames; bs.nframes = 6 * nlights; bs.nbins = nkeys; bs.bin_off = L.d_bin_off;
-    bs.face_lists = L.d_face_sel; bs.face_counts = L.d_face_counts; bs.face_stride = (uint32_t)g.n;
-    if ((rc = bin_pass(L, bs, nullptr, L.d_light_tab, L.d_bin_counters, L.d_bin_off, true, &L.bin_entries, may_guess))) return rc;
-    L.last_bin_mode = nlights;
-    L.bin_key = key;
-    L.bin_key_valid = true;
-    if (L.cap_light_rows < L.cap_entries) {                  // one row per pair at most; grown with the pair list (rare)
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        L.cap_light_rows = 0;
-        if ((rc = dev_realloc(&L.d_light_rows, (size_t)L.cap_entries))) return rc;
-        L.cap_light_rows = L.cap_entries;
-    }
-    const uint32_t expect = std::max<uint32_t>(L.bin_entries, 1u);
+    if ((rc = cube_bin_chain(L, L.d_frames, d_origins, nlights, nkeys, L.d_light_tab, L.d_bin_off, L.d_bin_counters, &L.kept.bin_entries, plan.may_guess))) return rc;
+    L.kept.keep(key, nlights);
+    // one row per pair at most; grown with the pair list (rare)
+    if (L.cap_light_rows < L.pairs.cap_entries && (rc = dev_grow(&L.d_light_rows, &L.cap_light_rows, L.pairs.cap_entries, (size_t)L.pairs.cap_entries, true))) return rc;
+    const uint32_t expect = std::max<uint32_t>(L.kept.bin_entries, 1u);
     hipLaunchKernelGGL(k_expand_light_rows, dim3((unsigned)std::min<uint32_t>((expect + 255) / 256, 4096u)), dim3(256), 0, g.stream,
-                       L.d_bin_off, L.d_entries, nlights, per_light, L.d_light_tab, g.n, L.d_light_rows, L.d_bin_counters, L.cap_used, (uint32_t *)nullptr);
+                       L.d_bin_off, L.pairs.d_entries, nlights, per_light, L.d_light_tab, g.n, L.d_light_rows, L.d_bin_counters, L.pairs.cap_used, (uint32_t *)nullptr);
     return MIRT_OK;
+}
+
+// ---- the camera pass's set-up, shared by a binned frame and a histogram-only pass ----
+
+int OriginTables::ensure_cam_rows() { return cam_tab_n == g.n ? MIRT_OK : dev_grow(&d_cam_tab, &cam_tab_n, g.n, (size_t)g.n, false); }
+
+// Zero-fill ON the stream that uses the buffer: hipMemset runs on the null stream, which the library's non-blocking streams
+// are not ordered with -- with several processes on one device (three ranks rehearsing a sharded run) such a fill has been seen
+// to land AFTER the first kernels of g.stream had started counting, which cut the pair count short (a light cube built from
+// it kept wrong shadows until the lights moved; a camera pass failed with "produced N pairs twice").
+int BinPass::ensure_counters(size_t bytes)
+{
+    if (!d_bin_counters) { HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_bin_counters), bytes)); HIP_TRY(hipMemsetAsync(d_bin_counters, 0, bytes, g.stream)); }
+    return MIRT_OK;
+}
+
+int CameraPass::ensure_sel()
+{
+    if (sel_n == g.n) return MIRT_OK;
+    kept.forget();
+    return dev_grow(&d_sel, &sel_n, g.n, (size_t)g.n, true);
+}
+
+SelectOut CameraPass::select_out(const OriginTables &T, int count_word) const
+{
+    SelectOut so;
+    memset(&so, 0, sizeof so);
+    so.cam_tab = T.d_cam_tab; so.sel = d_sel;
+    so.sel_count = d_bin_counters + count_word; so.sel_count_next = d_bin_counters + (count_word ^ 1);
+    return so;
+}
+
+// k_prep_select on g.stream: one workgroup of 1024 threads per CU -- a workgroup reserves its slice of the list with ONE atomic
+// (rt_binned.hip)
+static void launch_prep_select(const BinFrameDesc &frame, const SelectOut &so)
+{
+    const unsigned sel_grid = (unsigned)std::min<long long>(((long long)g.n + 1023) / 1024, (long long)g.cu_count);
+    if (sel_grid) hipLaunchKernelGGL(k_prep_select, dim3(sel_grid), dim3(1024), 0, g.stream, g.d_tris, g.n, frame, so);
 }
 
 // The binning pass of a binned frame, up to the trace kernel: the light-cube tables (the shared cache, or this frame's own pass on
 // the side stream), then the camera's selection, binning and tile order -- or nothing at all when the stream still holds the pass.
-int binned_pass(const mirt_view *view, RtScratch &S, RtScratch &L, const float *origins, int nlights, int y0, int y1, BinnedPass *bp)
+int binned_pass(const mirt_view *view, StreamState &ss, const float *origins, int nlights, int y0, int y1, BinnedPass *bp)
 {
     int rc;
+    CameraPass &S = ss.cam;
+    LightPass &L = ss.lt;
     g.stats.mode_used = MIRT_RT_BINNED;
     g.stats_sel_count = nullptr;
     // light-cube resolution: bins per face side (light_cube_bins_for)
@@ -439,8 +378,7 @@ int binned_pass(const mirt_view *view, RtScratch &S, RtScratch &L, const float *
     const uint64_t lkey = light_key_of(origins, nlights);
     if (g.lc.track_key == lkey) g.lc.stable++;
     else { g.lc.track_key = lkey; g.lc.stable = 0; }
-    const bool cached = g.lc.valid && g.lc.key == lkey && g.lc.cube_bins == fine_bins;
-    const bool transient = nlights > 0 && !fixed_grid && !cached && g.lc.stable < LIGHT_STABLE_FRAMES;
+    const bool transient = nlights > 0 && !fixed_grid && !g.lc.holds(lkey, fine_bins) && g.lc.stable < LIGHT_STABLE_FRAMES;
 
     k_begin(MIRT_K_BIN);
     if (!transient && (rc = light_cache_ensure(g.lc, L, origins, nlights, fine_bins))) return rc;   // (in the light pass's scratch: the camera's tables stay)
@@ -464,9 +402,10 @@ int binned_pass(const mirt_view *view, RtScratch &S, RtScratch &L, const float *
     {
         // depth shells: the tiles' lists come out of the sort roughly front to back (key = bin * shells + shell of the
         // candidate's `near` bound, uniform steps between the nearest and the farthest point of the scene's box)
-        const int ns = camera_shells_for((long long)bs.frame0.nbu * band_tile_rows);
+        static const int shells_env = (int)env_int("MIRT_CAM_SHELLS", 0);
+        const int ns = camera_shells_rule((long long)bs.frame0.nbu * band_tile_rows, shells_env);
         double dn = 0.0, df = 0.0;
-        const bool okr = shell_range(view->pos, &dn, &df);
+        const bool okr = shell_range(view->pos, g.bbox_lo, g.bbox_hi, &dn, &df);
         bs.frame0.nshell = okr ? ns : 1;
         bs.frame0.shell_d0 = (float)dn;
         bs.frame0.shell_iw = okr ? (float)(ns / (df - dn)) : 0.0f;
@@ -476,49 +415,20 @@ int binned_pass(const mirt_view *view, RtScratch &S, RtScratch &L, const float *
     const int tshells = transient ? light_shells_for(nlights, cube_bins, 0u) : 1;
     const uint32_t per_light = 6u * (uint32_t)(cube_bins * cube_bins) * (uint32_t)tshells;
     bs.nbins = cam_keys;
-    if (bs.nbins + 1 > S.cap_bins) {
-        const size_t cap = (size_t)bs.nbins + 1;
-        HIP_TRY(hipStreamSynchronize(g.stream));             // (a frame of this stream may still read the old array)
-        if ((rc = dev_realloc(&S.d_bin_off, cap))) { S.cap_bins = 0; return rc; }
-        S.cap_bins = (uint32_t)cap;
-        S.bin_key_valid = false;
+    if (bs.nbins + 1 > S.cap_bins) {                         // (a frame of this stream may still read the old array)
+        if ((rc = dev_grow(&S.d_bin_off, &S.cap_bins, bs.nbins + 1, (size_t)bs.nbins + 1, true))) return rc;
+        S.kept.forget();
     }
-    // Zero-fill ON the stream that uses the buffer: hipMemset runs on the null stream, which the library's non-blocking streams
-    // are not ordered with -- with several processes on one device (three ranks rehearsing a sharded run) such a fill has been seen
-    // to land AFTER the first kernels of g.stream had started counting, which cut the pair count short (a light cube built from
-    // it kept wrong shadows until the lights moved; a camera pass failed with "produced N pairs twice").
-    if (!S.d_bin_counters) { HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_bin_counters), 512)); HIP_TRY(hipMemsetAsync(S.d_bin_counters, 0, 512, g.stream)); }
-    if (S.sel_n != g.n) {
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        S.sel_n = 0;
-        if ((rc = dev_realloc(&S.d_sel, (size_t)g.n))) return rc;
-        S.sel_n = g.n;
-        S.bin_key_valid = false;
-    }
+    if ((rc = S.ensure_counters(512)) || (rc = S.ensure_sel())) return rc;
     bs.bin_off = S.d_bin_off;
 
-    uint64_t key = 0xcbf29ce484222325ull ^ g.scene_version;
-    {
-        auto mix = [&](const void *p, size_t nb) { const unsigned char *b = (const unsigned char *)p; for (size_t i = 0; i < nb; i++) { key ^= b[i]; key *= 0x100000001b3ull; } };
-        mix(view, sizeof *view); mix(&y0, 4); mix(&y1, 4); mix(&g.n, 4); mix(&g.aa, 4);
-    }
+    const uint64_t key = Fnv(g.scene_version).mix(view, sizeof *view).mix(&y0, 4).mix(&y1, 4).mix(&g.n, 4).mix(&g.aa, 4).h;
     const int bin_mode = 0;                                  // (the camera's pass bins the camera frame alone)
-    StreamState &ss = g.cur();
     ss.hits_clean[ss.hits_tog] = false;
     if (!S.d_frames) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_frames), sizeof(BinFrameDesc) * (1 + 6 * MIRT_MAX_LIGHTS)));
     // The pair count is read back (4 bytes + one sync of this stream) only when the inputs that determine it changed AND no
-    // count of an earlier pass of the same kind is at hand (a camera-only count says nothing about camera + light cubes).
-    // When NOTHING the pass depends on has changed since this stream's last pass -- the view stands still while a light key, a
-    // toggle or nothing at all asks for a frame (raytracer.cpp:385-537 set isUpdated without touching cameraPos / yaw) -- the
-    // stream still holds that pass's tables: origin rows, selection, sorted lists, offsets, tile order, and with them the rows
-    // of lights binned by the frame.  The frame then starts at the trace kernel.  (A kept pass whose list turned out too small
-    // -- its published count says so -- is redone, so that the list grows: bin_pass.)
-    poll_pair_count(S);
-    bool fresh = !S.bin_key_valid || S.bin_key != key;
-    const bool may_guess = S.last_bin_mode == bin_mode;
-    if (!fresh && S.have_known && S.known_pairs > S.cap_used) fresh = true;
-    static const bool reuse_off = env_int("MIRT_BIN_REUSE", 1) == 0;
-    const bool reuse = !fresh && !reuse_off;
+    // count of an earlier pass of the same kind is at hand; and the stream may still hold the whole pass (KeptPass::plan_for).
+    const PassPlan plan = S.kept.plan_for(key, bin_mode, S.pairs);
     const uint32_t pairs_x = (uint32_t)((bs.frame0.nbu + 1) / 2);
     uint32_t group_rows[ORDER_GROUPS] = { 0 };
     for (int j = bs.frame0.j0; j < bs.frame0.j1; j++) group_rows[((uint32_t)j >> ORDER_STRIPE_SHIFT) & (ORDER_GROUPS - 1)]++;
@@ -534,19 +444,19 @@ int binned_pass(const mirt_view *view, RtScratch &S, RtScratch &L, const float *
     if (transient) {
         static const bool side_off = env_int("MIRT_LIGHT_SIDE_STREAM", 1) == 0;
         hipStream_t main_stream = g.stream;
-        forked = !reuse && !side_off;
+        forked = !plan.reuse && !side_off;
         if (forked) {
             HIP_TRY(hipEventRecord(ss.ev_fork, main_stream));
             HIP_TRY(hipStreamWaitEvent(ss.aux, ss.ev_fork, 0));
             g.stream = ss.aux;
         }
         // (with the camera's pass kept nothing else runs in front of the trace kernel: the light pass's first launch zeroes the hit counters too)
-        rc = transient_light_pass(L, origins, nlights, cube_bins, tshells, per_light, lkey, &lights_kept, reuse ? g.d_hits : nullptr);
+        rc = transient_light_pass(L, origins, nlights, cube_bins, tshells, per_light, lkey, &lights_kept, plan.reuse ? g.d_hits : nullptr);
         g.stream = main_stream;
         if (rc) return rc;
         if (forked) HIP_TRY(hipEventRecord(ss.ev_join, ss.aux));
     }
-    if (reuse) {
+    if (plan.reuse) {
         // (the first kernel of a pass zeroes the frame's hit counters on the way; here nothing runs in front of the trace kernel --
         // unless the light pass has just run and done it)
         if (!(transient && !lights_kept)) HIP_TRY(hipMemsetAsync(g.d_hits, 0, HIT_BYTES, g.stream));
@@ -555,32 +465,20 @@ int binned_pass(const mirt_view *view, RtScratch &S, RtScratch &L, const float *
         // first kernel of the frame: the camera's origin rows for the triangles the rows of this call can see, and their list
         // (k_prep_select); it also zeroes the hit counters and the pass's counters
         S.sel_parity ^= 1;
-        SelectOut so;
-        memset(&so, 0, sizeof so);
-        so.cam_tab = S.d_cam_tab; so.sel = S.d_sel;
-        so.sel_count = S.d_bin_counters + SEL_COUNT0 + S.sel_parity; so.sel_count_next = S.d_bin_counters + SEL_COUNT0 + (S.sel_parity ^ 1);
+        SelectOut so = S.select_out(ss.tabs, SEL_COUNT0 + S.sel_parity);
         so.zero_hits = g.d_hits; so.zero_counter = S.d_bin_counters;
-        if ((rc = hist_prepare(S, bs.frame0, &so))) return rc;
-        // one workgroup of 1024 threads per CU: a workgroup reserves its slice of the list with ONE atomic (rt_binned.hip)
-        const unsigned sel_grid = (unsigned)std::min<long long>(((long long)g.n + 1023) / 1024, (long long)g.cu_count);
-        hipLaunchKernelGGL(k_prep_select, dim3(sel_grid), dim3(1024), 0, g.stream, g.d_tris, g.n, bs.frame0, so);
-        if ((rc = hist_publish(S))) return rc;
+        if ((rc = hist_prepare(ss.hist, bs.frame0, &so))) return rc;
+        launch_prep_select(bs.frame0, so);
+        if ((rc = hist_publish(ss.hist))) return rc;
         bs.sel = S.d_sel; bs.sel_count = so.sel_count;
         g.stats_sel_count = so.sel_count;
-        if ((rc = bin_pass(S, bs, S.d_cam_tab, nullptr, S.d_bin_counters, S.d_bin_off, true, &S.bin_entries, may_guess))) return rc;
-        S.last_bin_mode = bin_mode;
-        S.bin_key = key;
-        S.bin_key_valid = true;
+        if ((rc = bin_pass(S.pairs, bs, ss.tabs.d_cam_tab, nullptr, S.d_bin_counters, S.d_bin_off, &S.kept.bin_entries, plan.may_guess))) return rc;
+        S.kept.keep(key, bin_mode);
         // the order the trace kernel's waves take the tile pairs in: per XCD group (pairs of tile rows dealt round-robin), longest
         // lists first
-        if ((size_t)order_seg > S.cap_order) {
-            HIP_TRY(hipStreamSynchronize(g.stream));
-            S.cap_order = 0;
-            if ((rc = dev_realloc(&S.d_order, (size_t)ORDER_GROUPS * ORDER_CLASSES * order_seg))) return rc;
-            S.cap_order = order_seg;
-        }
+        if (order_seg > S.cap_order && (rc = dev_grow(&S.d_order, &S.cap_order, order_seg, (size_t)ORDER_GROUPS * ORDER_CLASSES * order_seg, true))) return rc;
         hipLaunchKernelGGL(k_tile_order, dim3((pairs_x + 63) / 64, (unsigned)(bs.frame0.j1 - bs.frame0.j0)), dim3(64), 0, g.stream, cam_off, bs.frame0.nshell,
-                           bs.frame0.nbu, bs.frame0.j0, bs.frame0.j1, S.d_bin_counters, S.cap_used, S.d_order, order_seg);
+                           bs.frame0.nbu, bs.frame0.j0, bs.frame0.j1, S.d_bin_counters, S.pairs.cap_used, S.d_order, order_seg);
     }
     if (forked) HIP_TRY(hipStreamWaitEvent(g.stream, ss.ev_join, 0));
     k_end(MIRT_K_BIN);
@@ -590,62 +488,52 @@ int binned_pass(const mirt_view *view, RtScratch &S, RtScratch &L, const float *
     bp->cam_shells = bs.frame0.nshell;
     bp->shell_d0 = bs.frame0.shell_d0; bp->shell_iw = bs.frame0.shell_iw;
     bp->order_seg = order_seg;
-    bp->transient = transient;
-    bp->cube_bins = cube_bins;
-    bp->light_shells = transient ? tshells : g.lc.shells;
+    // the light tables: this frame's own pass with its count, or the shared cube's, which are complete by construction -- the trace
+    // kernel reads the count with its other counters, without a branch, so it gets a word that is there and a cap no count exceeds
+    bp->cube = transient ? cube_view(L, cube_bins, tshells) : cube_view(g.lc);
+    bp->light_tab = transient ? L.d_light_tab : g.lc.d_light_tab;
+    bp->light_pair_count = transient ? L.d_bin_counters : S.d_bin_counters;
+    bp->light_pair_cap = transient ? L.pairs.cap_used : 0xFFFFFFFFu;
     return MIRT_OK;
 }
 
 // k_prep_select over a frame of no rows, for its histogram of the whole frame, filed like a binned pass's.  It still writes the
-// origin rows and the indices of the triangles it cannot rule out into the stream's tables -- the pass the stream held is gone
-// (bin_key_valid) -- and counts them into words of its own (HIST_SEL_COUNT, zeroed first), so that the selection count of the
-// stream's last binned frame, which mirt_get_stats reads, stays what it was.
+// origin rows and the indices of the triangles it cannot rule out into the stream's tables -- the pass the stream held is gone --
+// and counts them into words of its own (HIST_SEL_COUNT, zeroed first), so that the selection count of the stream's last binned
+// frame, which mirt_get_stats reads, stays what it was.
 int hist_only_pass(const mirt_view *view)
 {
     int rc;
     g.stream = g.cur().stream;
-    RtScratch &S = g.cur().rt;
-    if (S.cam_tab_n != g.n) {
-        S.cam_tab_n = 0;
-        if ((rc = dev_realloc(&S.d_cam_tab, (size_t)g.n))) return rc;
-        S.cam_tab_n = g.n;
-    }
-    if (S.sel_n != g.n) {
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        S.sel_n = 0;
-        if ((rc = dev_realloc(&S.d_sel, (size_t)g.n))) return rc;
-        S.sel_n = g.n;
-    }
-    if (!S.d_bin_counters) { HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_bin_counters), 512)); HIP_TRY(hipMemsetAsync(S.d_bin_counters, 0, 512, g.stream)); }
-    S.bin_key_valid = false;
+    StreamState &ss = g.cur();
+    CameraPass &S = ss.cam;
+    if ((rc = ss.tabs.ensure_cam_rows()) || (rc = S.ensure_sel()) || (rc = S.ensure_counters(512))) return rc;
+    S.kept.forget();
     const BinFrameDesc fr = make_camera_frame(view, 0, 0, g.aa);
-    SelectOut so;
-    memset(&so, 0, sizeof so);
-    so.cam_tab = S.d_cam_tab; so.sel = S.d_sel;
-    so.sel_count = S.d_bin_counters + HIST_SEL_COUNT; so.sel_count_next = S.d_bin_counters + HIST_SEL_COUNT + 1;
-    if ((rc = hist_prepare(S, fr, &so))) return rc;
+    SelectOut so = S.select_out(ss.tabs, HIST_SEL_COUNT);
+    if ((rc = hist_prepare(ss.hist, fr, &so))) return rc;
     if (!g.hist_armed) return MIRT_OK;
     HIP_TRY(hipMemsetAsync(so.sel_count, 0, 4, g.stream));
-    const unsigned sel_grid = (unsigned)std::min<long long>(((long long)g.n + 1023) / 1024, (long long)g.cu_count);
-    if (sel_grid) hipLaunchKernelGGL(k_prep_select, dim3(sel_grid), dim3(1024), 0, g.stream, g.d_tris, g.n, fr, so);
+    launch_prep_select(fr, so);
     HIP_TRY(hipGetLastError());
-    return hist_publish(S);
+    return hist_publish(ss.hist);
 }
 
-// The trace kernel of a binned frame over the tables binned_pass left: the camera's in S, the light cubes' in L (transient) or
-// in the shared cache.
-int binned_trace(const RtFrame &f, RtScratch &S, RtScratch &L, const BinnedPass &bp)
+// The trace kernel of a binned frame over the tables binned_pass left: the camera's in the stream's tables and camera pass, the
+// light cubes' as bp's view shows them.
+int binned_trace(const RtFrame &f, StreamState &ss, const BinnedPass &bp)
 {
-    const bool transient = bp.transient;
+    int rc;
+    CameraPass &S = ss.cam;
     RtTraceFrame tf;
     memset(&tf, 0, sizeof tf);
     tf.f = f;
-    tf.f.cam_tab = S.d_cam_tab;
+    tf.f.cam_tab = ss.tabs.d_cam_tab;
     // (a frame whose pair list overflowed walks the origin tables themselves: every triangle for every ray)
-    tf.f.light_tab = transient ? L.d_light_tab : g.lc.d_light_tab;
+    tf.f.light_tab = bp.light_tab;
     tf.f.unsafe = nullptr;
     tf.cam_off = bp.cam_off;
-    tf.cam_entries = S.d_entries;
+    tf.cam_entries = S.pairs.d_entries;
     tf.sel = S.d_sel; tf.sel_count = S.d_bin_counters + SEL_COUNT0 + S.sel_parity;
     // geometry rows staged with every candidate while the scene's tables fit the caches, fetched by the exact stage beyond (rt_trace.hip);
     // MIRT_LAZY_GEO=0|1 fixes the choice
@@ -653,24 +541,22 @@ int binned_trace(const RtFrame &f, RtScratch &S, RtScratch &L, const BinnedPass 
     tf.lazy_geo = lazy_env >= 0 ? (lazy_env != 0) : (g.n >= 400000);
     tf.geo = g.d_geo;
     tf.shade = g.d_shade;
-    tf.light_off = transient ? L.d_bin_off : g.lc.d_off;
-    tf.light_rows = transient ? L.d_light_rows : g.lc.d_rows;
-    tf.light_tri = transient ? L.d_entries : g.lc.d_row_tri;
-    tf.light_frames = transient ? L.d_frames : g.lc.d_frames;
+    tf.light_off = bp.cube.light_off;
+    tf.light_rows = bp.cube.light_rows;
+    tf.light_tri = bp.cube.light_tri;
+    tf.light_frames = bp.cube.light_frames;
     tf.tiles_x = bp.tiles_x;
-    tf.cube_bins = bp.cube_bins;
+    tf.cube_bins = bp.cube.cube_bins;
     tf.cam_shells = bp.cam_shells;
-    tf.light_shells = bp.light_shells;
+    tf.light_shells = bp.cube.shells;
     tf.shell_d0 = bp.shell_d0; tf.shell_iw = bp.shell_iw;
     // a tile's list ends at the depth shell of the tile's farthest record (rt_trace.hip); MIRT_TR_LIST_END=0 walks every list to its end
     static const int list_end_env = (int)env_int("MIRT_TR_LIST_END", 1);
     tf.list_end = list_end_env != 0;
     tf.pair_count = S.d_bin_counters;
-    tf.pair_cap = S.cap_used;
-    // (lights binned by the frame: their own pass's count; the shared cube's tables are complete by construction -- the kernel reads
-    // the word with its other counters, without a branch, so it gets one that is there and a cap no count exceeds)
-    tf.light_pair_count = transient ? L.d_bin_counters : S.d_bin_counters;
-    tf.light_pair_cap = transient ? L.cap_used : 0xFFFFFFFFu;
+    tf.pair_cap = S.pairs.cap_used;
+    tf.light_pair_count = bp.light_pair_count;
+    tf.light_pair_cap = bp.light_pair_cap;
     // one wave per pair of 8 x 8 tiles
     tf.order = S.d_order; tf.order_count = S.d_bin_counters + 16; tf.order_seg = bp.order_seg;
     // (waves never synchronise with each other: one-wave workgroups are the finest scheduling unit; 84 / 87 / 89 us with 1 / 2 / 4)
@@ -693,13 +579,7 @@ int binned_trace(const RtFrame &f, RtScratch &S, RtScratch &L, const BinnedPass 
     }
     k_end(MIRT_K_TRACE);
     HIP_TRY(hipGetLastError());
-    for (RtScratch *P : { &S, &L })
-        if (P->count_event_due) {
-            P->count_event_due = false;
-            HIP_TRY(hipEventRecord(P->ev_count, g.stream));
-            P->count_pending = true;
-        }
-    return MIRT_OK;
+    return (rc = S.pairs.record_count()) ? rc : ss.lt.pairs.record_count();
 }
 
 }  // namespace mirt

@@ -14,6 +14,7 @@
 #include "../csrc/scan.hpp"
 #include "../query/rt_query.hpp"
 #include "cube_plan.hpp"
+#include "pass_plan.hpp"
 #include "env.hpp"
 
 #include <cstdarg>
@@ -102,57 +103,113 @@ constexpr int HIST_RING = 4;                     // pinned copies of the cost hi
 constexpr int HIST_SLOTS = HIST_RING + 1;        // ... and one behind them for frames outside sharded calls (mirt_cost_histogram only)
 constexpr size_t HIT_BYTES = sizeof(unsigned long long) * HIT_SHARDS * HIT_SHARD_STRIDE;   // one hit-counter buffer (rt_common.hpp: count_hits)
 
-// What a frame of the brute-force / binned ray-trace paths writes besides the caller's planes: one set per stream, so
-// that two frames in flight never share any of it.
-struct RtScratch {
+// What the ray-trace frames of a stream write besides the caller's planes, by role: one set per stream, so that two frames in
+// flight never share any of it.
+//
+// The origin tables: the brute-force path's camera and light rows (k_prep_origin), a histogram-only pass's camera rows, and the
+// camera rows of a binned frame (k_prep_select).
+struct OriginTables {
     OriginRow *d_cam_tab = nullptr;              // n rows (cam_tab_n)
     OriginRow *d_light_tab = nullptr;            // light_tab_lights x n rows
     int cam_tab_n = 0, light_tab_n = 0, light_tab_lights = 0;
     float *d_origins = nullptr;                  // (1 + MIRT_MAX_LIGHTS) x 3
     uint32_t *d_flags = nullptr;                 // [0] = unsafe flag
-    // binned ray tracing: frame descriptors, per-bin offsets, the (bin, triangle) pair list and its sorted copy
-    BinFrameDesc *d_frames = nullptr;
-    uint32_t *d_bin_off = nullptr, *d_bin_counters = nullptr;
+
+    int ensure_cam_rows();                       // d_cam_tab for the scene's n triangles
+    void release();
+};
+
+// The (bin, triangle) pair list of a binning pass, its sorted copy and the sort's scratch (bin_pass).
+// Sizing the list without a host sync: the count of a frame is copied to pinned memory behind it and looked at by a LATER frame
+// of this stream; meanwhile the list is sized from the last count seen, with a device-side fallback if that was too small
+// (k_rt_trace2 then takes every triangle for every tile).
+struct PairList {
     uint32_t *d_entries = nullptr;               // triangle ids ordered by bin (the sorted pair values)
     uint32_t *d_pair_keys = nullptr, *d_pair_vals = nullptr, *d_sorted_keys = nullptr;   // unsorted pairs, sorted bin ids
     uint32_t *d_tmp_vals = nullptr;              // bucket sort: the pairs partitioned by bucket (keys go to d_sorted_keys)
     uint32_t *d_bucket = nullptr;                // bucket sort: counts | bases (+1) | cursors, cap_buckets each
     uint32_t cap_buckets = 0;
     bool bucket_dirty = false;                   // d_bucket may hold counts of a pass whose sort never ran
-    // sizing the pair list without a host sync: the count of a frame is copied to pinned memory behind it and looked at by a
-    // LATER frame of this stream; meanwhile the list is sized from the last count seen, with a device-side fallback if that
-    // was too small (k_rt_trace2 then takes every triangle for every tile)
+    uint32_t cap_entries = 0;
+    uint32_t cap_used = 0;                       // capacity the last binning pass told its kernels (== cap_entries outside tests)
     uint32_t *h_count = nullptr;                 // pinned
     hipEvent_t ev_count = nullptr;
     bool count_pending = false;
-    bool count_event_due = false;                // bin_pass published a count: the caller records ev_count behind the frame's last kernel
+    bool count_event_due = false;                // bin_pass published a count: record_count() records ev_count behind the frame's last kernel
     bool have_known = false;
     uint32_t known_pairs = 0;
-    uint32_t cap_bins = 0, cap_entries = 0;
-    uint32_t cap_used = 0;                       // capacity the last binning pass told its kernels (== cap_entries outside tests)
+
+    int ensure(size_t cap);                      // room for `cap` pairs
+    void poll();                                 // picks up the count an earlier frame has published, if it has landed
+    int record_count();                          // the event of a published count, on g.stream
+    void forget_scene() { have_known = false; count_pending = false; }        // the counts belong to the old scene
+    void release();
+};
+
+// The pass a stream holds: what it binned, so that a frame whose pass would be the same starts at the trace kernel.
+struct KeptPass {
     uint64_t bin_key = 0;
-    uint32_t bin_entries = 0;                    // pairs of the current binning
     bool bin_key_valid = false;
-    // lights that moved: this stream's own light-cube pass (transient_light_pass), rows in the order of the pair list
-    LightRow *d_light_rows = nullptr;
-    uint32_t cap_light_rows = 0;
-    // the frame's tile pairs ordered longest lists first (k_tile_order): ORDER_CLASSES segments of cap_order records
-    TilePairRec *d_order = nullptr;
-    uint32_t cap_order = 0;
-    int last_bin_mode = -1;                      // what the last pass binned (camera alone / camera + n light cubes): a guessed
+    int last_bin_mode = -1;                      // what the last pass binned (0: the camera frame / n: n light cubes): a guessed
                                                  // list size only carries over between passes of the same kind
+    uint32_t bin_entries = 0;                    // pairs of the current binning
+
+    PassPlan plan_for(uint64_t key, int mode, PairList &P) const;   // picks up P's published count first (binned.cpp)
+    void keep(uint64_t key, int mode) { bin_key = key; last_bin_mode = mode; bin_key_valid = true; }
+    void forget() { bin_key_valid = false; }                        // the tables it counts on are overwritten
+};
+
+// What the two binning passes of a stream have in common: the list, the pass held, the offsets of the sorted list and a block of
+// counters the pass's first kernel zeroes.
+struct BinPass {
+    PairList pairs;
+    KeptPass kept;
+    uint32_t *d_bin_off = nullptr;
+    uint32_t cap_bins = 0;                       // keys + 1 of d_bin_off
+    uint32_t *d_bin_counters = nullptr;          // [0] pairs, [16] tile pairs in order, ... (512 bytes / LIGHT_COUNTER_BYTES)
+    BinFrameDesc *d_frames = nullptr;            // descriptor buffer
+
+    int ensure_counters(size_t bytes);           // d_bin_counters, zero
+    void forget_scene() { kept.forget(); pairs.forget_scene(); }
+};
+
+// The camera's binning pass of a binned frame: selection, pairs by tile and shell, offsets, tile order.
+struct CameraPass : BinPass {
     // k_prep_select: the triangles the frame may see (indices, sel_n slots) and the two counters its passes use in turn (the pass
     // that counts into one zeroes the other: d_bin_counters[SEL_COUNT0 + parity])
     uint32_t *d_sel = nullptr;
     int sel_n = 0;
     int sel_parity = 0;
-    // k_select_faces: per face of the light cubes this stream bins (its own frames' moving lights, or the shared cube's build) the
-    // triangles the face can see -- list i at d_face_sel + i * n -- and the lists' lengths
+    // the frame's tile pairs ordered longest lists first (k_tile_order): ORDER_CLASSES segments of cap_order records
+    TilePairRec *d_order = nullptr;
+    uint32_t cap_order = 0;
+
+    int ensure_sel();                            // (the stream must be idle when the list grows; the kept pass goes with it)
+    SelectOut select_out(const OriginTables &T, int count_word) const;   // rows, list and the counter pair at count_word
+    void release();
+};
+
+// A LIGHT-cube pass of a stream -- the cubes of lights that move, binned by the frame (transient_light_pass), and the scratch of
+// every shared cube's build (light_cache_ensure) -- apart from the camera's, so that either pass is kept while only the other
+// one's inputs change.  Its counter block: words 0 .. 127 as in the camera's, 128 .. the face counts; its descriptor buffer:
+// [6 * nlights descriptors | (1 + nlights) x 3 origins] of the lights that move.
+constexpr size_t LIGHT_COUNTER_BYTES = sizeof(uint32_t) * (128 + 6 * MIRT_MAX_LIGHTS);
+struct LightPass : BinPass {
+    uint32_t *d_face_counts = nullptr;           // 6 * MIRT_MAX_LIGHTS words (inside d_bin_counters' block)
+    // k_select_faces: per face of the light cubes the triangles the face can see -- list i at d_face_sel + i * n
     uint32_t *d_face_sel = nullptr;
     size_t cap_face_sel = 0;                     // slots
-    uint32_t *d_face_counts = nullptr;           // 6 * MIRT_MAX_LIGHTS words (inside d_bin_counters' block)
-    // the cost histogram of the whole frame (weighted partition): device words, and where they travel for the host to read --
-    // HIST_RING pinned copies that sharded calls take in turn, and slot HIST_RING for frames outside them; an event behind each
+    OriginRow *d_light_tab = nullptr;            // light_tab_lights x n origin rows of the lights that move
+    int light_tab_n = 0, light_tab_lights = 0;
+    LightRow *d_light_rows = nullptr;            // their rows in the order of the pair list
+    uint32_t cap_light_rows = 0;
+
+    void release();
+};
+
+// The cost histogram of a stream's binned frames (weighted partition): device words, and where they travel for the host to read --
+// HIST_RING pinned copies that sharded calls take in turn, and slot HIST_RING for frames outside them; an event behind each
+struct CostHist {
     uint32_t *d_hist = nullptr;
     uint32_t *h_hist = nullptr;                  // pinned: HIST_SLOTS x SEL_HIST_MAX words
     hipEvent_t ev_hist[HIST_SLOTS] = {};
@@ -161,7 +218,7 @@ struct RtScratch {
     int hist_rows[HIST_SLOTS] = {}, hist_shift[HIST_SLOTS] = {};
     int hist_next = 0;                           // the ring's next slot
 
-    void forget_scene() { bin_key_valid = false; have_known = false; count_pending = false; }   // tables and pair counts belong to the old scene
+    void forget_scene() { for (uint64_t &k : hist_key) k = 0; }
     void release();
 };
 
@@ -185,6 +242,7 @@ struct LightCache {
     float *d_origins = nullptr;                  // (1 + MIRT_MAX_LIGHTS) x 3
     uint32_t *d_counter = nullptr;               // pair counter of the build
 
+    bool holds(uint64_t k, int bins) const { return valid && key == k && cube_bins == bins; }
     void release();
 };
 
@@ -270,10 +328,10 @@ struct StreamState {
     hipEvent_t ev[EV_COUNT] = {};
     bool ev_used[8] = {};
     bool call_timed = false;                     // the stream's last call recorded its start / end events (profiling was on)
-    RtScratch rt;                                // tables of the non-tile ray-trace paths
-    RtScratch rt_lt;                             // the pair lists, offsets and rows of a LIGHT-cube pass -- the cubes of lights that move
-                                                 // (binned by the frame) and the scratch of the shared cube's build -- apart from the
-                                                 // camera's, so that either pass is kept while only the other one's inputs change
+    OriginTables tabs;
+    CameraPass cam;
+    LightPass lt;
+    CostHist hist;
     // hit counters (HIT_SHARDS sharded counters each): two used alternately, so that a kernel can clear the one the NEXT frame on
     // this stream will use
     unsigned long long *d_hits[2] = {};
@@ -380,6 +438,16 @@ int need_init();
 // Frees *p and allocates `bytes` in its place (nothing for 0); MIRT_ERR_OUT_OF_MEMORY when that fails.
 int dev_realloc_bytes(void **p, size_t bytes);
 template <typename T> int dev_realloc(T **p, size_t count) { return dev_realloc_bytes(reinterpret_cast<void **>(p), count * sizeof(T)); }
+// A buffer outgrown: `count` elements in *p (what it held is gone), noted as *cap = want -- 0 while the buffer is not there.
+// sync_first: work queued on g.stream may still read the old buffer, which is freed only once that stream is idle.
+template <typename T, typename N> int dev_grow(T **p, N *cap, N want, size_t count, bool sync_first)
+{
+    if (sync_first) HIP_TRY(hipStreamSynchronize(g.stream));
+    *cap = 0;
+    const int rc = dev_realloc(p, count);
+    if (!rc) *cap = want;
+    return rc;
+}
 // The arguments every frame entry point checks before it touches the device.  need_scene: the call renders right away (the
 // depth-of-field and staging layers leave that check to the render call); [y0, y1): the row band it renders (the entry points
 // that render the whole frame pass an empty band).
@@ -403,27 +471,37 @@ int rt_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, con
                int y0, int y1, int row_origin, void *d_xrgb, int pitch_bytes, void *d_rgb, void *d_index, void *d_fd = nullptr,
                void *d_dist = nullptr, void *d_pos = nullptr);
 BinFrameDesc make_camera_frame(const mirt_view *view, int y0, int y1, int aa);
-bool frame_fits_binning(int W, int H);
 // What the trace kernel of a binned frame takes from the frame's binning pass (binned_pass -> binned_trace).
 struct BinnedPass {
     const uint32_t *cam_off;                     // camera offsets, indexed by the FRAME's tile number
     int tiles_x, cam_shells;
     float shell_d0, shell_iw;                    // the camera frame's depth-shell parameters: what the tiles' lists were sorted with
     uint32_t order_seg;                          // tile-pair records per (XCD group, class) segment of the order
-    bool transient;                              // light tables: this frame's own pass (the stream's rt_lt), or the shared cache
-    int cube_bins, light_shells;
+    // the light tables -- this frame's own pass (the stream's LightPass) or the shared cache --, the origin table behind them and
+    // the pair count and cap that say whether they are complete
+    CubeView cube;
+    const OriginRow *light_tab;
+    const uint32_t *light_pair_count;
+    uint32_t light_pair_cap;
 };
+// The view of a cube's tables (pass_plan.hpp: make_cube_view): of a cache, and of a stream's light pass binned on a grid of
+// cube_bins with `shells` depth shells (its row table is there once a pass has run).
+inline CubeView cube_view(const LightCache &C) { return make_cube_view(C.d_off, C.d_rows, C.nrows != 0, C.d_light_tab, C.d_row_tri, C.d_frames, C.cube_bins, C.shells); }
+inline CubeView cube_view(const LightPass &L, int cube_bins, int shells)
+{
+    return make_cube_view(L.d_bin_off, L.d_light_rows, L.d_light_rows != nullptr, L.d_light_tab, L.pairs.d_entries, L.d_frames, cube_bins, shells);
+}
 // A light cube's tables in C for `nlights` light positions (origins[3 ..]) on a grid of cube_bins, built on g.stream in S -- a
-// stream's LIGHT scratch set, whose kept pass the build invalidates -- unless C holds them already; *built says which.
-int light_cache_ensure(LightCache &C, RtScratch &S, const float *origins, int nlights, int cube_bins, bool *built = nullptr);
+// stream's light pass, whose kept pass the build evicts -- unless C holds them already; *built says which.
+int light_cache_ensure(LightCache &C, LightPass &S, const float *origins, int nlights, int cube_bins, bool *built = nullptr);
 uint64_t light_key_of(const float *origins, int nlights);
 // Bins per face side of the cubes of `nlights` light positions under the frame path's rules (scene size, MIRT_CUBE_BINS, the
 // sort's key space); *fixed_grid: the environment fixed it.  light_keys_fit: one sort pass holds such a cube's keys at all.
 int light_cube_bins_for(int nlights, bool *fixed_grid);
 int cube_bins_override();                        // MIRT_CUBE_BINS as read once (0: not set)
 bool light_keys_fit(int nlights, int cube_bins);
-int binned_pass(const mirt_view *view, RtScratch &S, RtScratch &L, const float *origins, int nlights, int y0, int y1, BinnedPass *bp);
-int binned_trace(const RtFrame &f, RtScratch &S, RtScratch &L, const BinnedPass &bp);
+int binned_pass(const mirt_view *view, StreamState &ss, const float *origins, int nlights, int y0, int y1, BinnedPass *bp);
+int binned_trace(const RtFrame &f, StreamState &ss, const BinnedPass &bp);
 // The checks every call makes on its lights and the soft-shadow state; *light_positions: lights x soft-shadow samples, the
 // shadow-ray origins.  fill_light_positions: where each of them is (the light itself, or its jittered sample: randomPositions[k *
 // SOFT_SHADOWS_SAMPLES + i], raytracer.cpp:286), its share of the light's power, P = (color * intensity) / samples (:282, :296),
@@ -476,8 +554,8 @@ int cull_copy_wait_readers(int dst, hipStream_t st);
 // ---- partition and sharded frames (sharded.cpp) ----
 // The cost histogram of a binned frame's pass (k_prep_select): hist_prepare points the pass at it when one is wanted,
 // hist_publish files it behind the pass.
-int hist_prepare(RtScratch &S, const BinFrameDesc &cam, SelectOut *so);
-int hist_publish(RtScratch &S);
+int hist_prepare(CostHist &S, const BinFrameDesc &cam, SelectOut *so);
+int hist_publish(CostHist &S);
 const uint32_t *hist_lookup(uint64_t max_key, int *rows, int *shift);
 void current_bounds(int world, int W, int H, std::vector<int> &bounds);
 unsigned part_tile_weight();

@@ -30,11 +30,7 @@ static int query_rows()
     QueryScratch &S = g.cur().query;
     if (Q.version != g.scene_version) {
         Q.version = 0;
-        if (Q.n != g.n) {
-            Q.n = 0;
-            if ((rc = dev_realloc(&Q.d_rows, (size_t)g.n))) return rc;
-            Q.n = g.n;
-        }
+        if (Q.n != g.n && (rc = dev_grow(&Q.d_rows, &Q.n, g.n, (size_t)g.n, false))) return rc;
         if (!Q.d_max) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&Q.d_max), sizeof(uint32_t) * QMAX_WORDS));
         if (!Q.ev_built) HIP_TRY(hipEventCreateWithFlags(&Q.ev_built, hipEventDisableTiming));
         HIP_TRY(hipMemsetAsync(Q.d_max, 0, sizeof(uint32_t) * QMAX_WORDS, g.stream));
@@ -99,20 +95,7 @@ int query_intersect(const void *d_rays, int nrays, void *d_hits)
 
 // ---- what the queries that walk a cube share: its view, their statistics ------------------------------------------------------
 
-// What a walk kernel reads of the cube C.  A lane with no row left still loads row 0 each step and ignores it, and a cube without a
-// single pair has no row table: the loads are pointed at the cube's origin table then, which always has a row.  (The trace
-// kernel's version of this rule: ADVICE.md.)
-static CubeView cube_view(const LightCache &C)
-{
-    CubeView v;
-    v.light_off = C.d_off;
-    v.light_rows = C.nrows ? C.d_rows : C.d_light_tab;
-    v.light_tri = C.d_row_tri;
-    v.light_frames = C.d_frames;
-    v.cube_bins = C.cube_bins;
-    v.shells = C.shells;
-    return v;
-}
+// (the view of a cube's tables, cube_view: capi.hpp)
 
 // A query of `kind` starts on the current stream: its statistics begin afresh.
 static QueryStats &stats_begin(int kind, bool binned)
@@ -183,9 +166,7 @@ static int query_origin_tables(const float *origins, int npos, bool safe)
     int rc;
     QueryScratch &S = g.cur().query;
     if (npos > S.tab_lights || S.tab_n != g.n) {
-        S.tab_lights = 0;
-        if ((rc = dev_realloc(&S.d_light_tab, (size_t)npos * g.n))) return rc;
-        S.tab_lights = npos;
+        if ((rc = dev_grow(&S.d_light_tab, &S.tab_lights, npos, (size_t)npos * g.n, false))) return rc;
         S.tab_n = g.n;
     }
     if (!S.d_origins) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_origins), sizeof(float) * 3 * (1 + MIRT_MAX_LIGHTS)));
@@ -266,8 +247,8 @@ int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, 
     const bool may_bin = safe && npos > 0 && light_keys_fit(npos, cube_bins);
     const uint64_t lkey = may_bin ? light_key_of(origins, npos) : 0;
     LightCache &own = g.qrows.cube;
-    const bool frames_cube = may_bin && g.lc.valid && g.lc.key == lkey && g.lc.cube_bins == cube_bins;
-    const bool own_cube = may_bin && own.valid && own.key == lkey && own.cube_bins == cube_bins;
+    const bool frames_cube = may_bin && g.lc.holds(lkey, cube_bins);
+    const bool own_cube = may_bin && own.holds(lkey, cube_bins);
     const bool binned = may_bin && g.query_mode != MIRT_QUERY_BRUTE &&
                         (g.query_mode == MIRT_QUERY_BINNED || frames_cube || own_cube || auto_bins(nhits, npos));
 
@@ -280,7 +261,7 @@ int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, 
     if (!frames_cube) {
         // (in the stream's LIGHT scratch set, as the shared cube's build: the pass that set kept for moving lights is invalidated there)
         bool built = false;
-        if ((rc = light_cache_ensure(own, g.cur().rt_lt, origins, npos, cube_bins, &built))) return rc;
+        if ((rc = light_cache_ensure(own, g.cur().lt, origins, npos, cube_bins, &built))) return rc;
         C = &own;
         source = built ? 1 : 2;
     }
@@ -327,7 +308,7 @@ int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, vo
     const int cube_bins = light_cube_bins_for(1, &fixed_grid);
     const bool may_bin = safe && light_keys_fit(1, cube_bins);
     LightCache &C = g.qrows.fan;
-    const bool held = may_bin && C.valid && C.key == light_key_of(origins, 1) && C.cube_bins == cube_bins;
+    const bool held = may_bin && C.holds(light_key_of(origins, 1), cube_bins);
     const bool binned = may_bin && g.query_mode != MIRT_QUERY_BRUTE && (g.query_mode == MIRT_QUERY_BINNED || held || auto_bins_fan(nrays));
 
     stream_begin();
@@ -344,7 +325,7 @@ int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, vo
 
     // (in the stream's LIGHT scratch set, as the shared cube's build)
     bool built = false;
-    if ((rc = light_cache_ensure(C, g.cur().rt_lt, origins, 1, cube_bins, &built))) return rc;
+    if ((rc = light_cache_ensure(C, g.cur().lt, origins, 1, cube_bins, &built))) return rc;
     stats_cube(stats, C, built ? 1 : 2);
     q.tab = C.d_light_tab;
     q.cube = cube_view(C);
@@ -401,9 +382,9 @@ static void fans_pass_origins(const float *origins3, const FanPass &p, float *po
 // A cube somebody else holds for the pass's positions and grid: the frame path's (*source = 3), DirectLight's (4), or none.
 static const LightCache *fans_foreign_cube(uint64_t key, int cube_bins, int *source)
 {
-    if (g.lc.valid && g.lc.key == key && g.lc.cube_bins == cube_bins) { *source = 3; return &g.lc; }
+    if (g.lc.holds(key, cube_bins)) { *source = 3; return &g.lc; }
     const LightCache &D = g.qrows.cube;
-    if (D.valid && D.key == key && D.cube_bins == cube_bins) { *source = 4; return &D; }
+    if (D.holds(key, cube_bins)) { *source = 4; return &D; }
     return nullptr;
 }
 
@@ -413,16 +394,8 @@ static int fans_brute(const float *origins3, int norigins, const void *d_origin_
 {
     int rc;
     QueryScratch &S = g.cur().query;
-    if ((size_t)norigins > S.fan_origins_cap) {
-        S.fan_origins_cap = 0;
-        if ((rc = dev_realloc(&S.d_fan_origins, (size_t)norigins * 3))) return rc;
-        S.fan_origins_cap = (size_t)norigins;
-    }
-    if ((size_t)nrays > S.fan_rays_cap) {
-        S.fan_rays_cap = 0;
-        if ((rc = dev_realloc(&S.d_fan_rays, (size_t)nrays * RAY_WORDS))) return rc;
-        S.fan_rays_cap = (size_t)nrays;
-    }
+    if ((size_t)norigins > S.fan_origins_cap && (rc = dev_grow(&S.d_fan_origins, &S.fan_origins_cap, (size_t)norigins, (size_t)norigins * 3, false))) return rc;
+    if ((size_t)nrays > S.fan_rays_cap && (rc = dev_grow(&S.d_fan_rays, &S.fan_rays_cap, (size_t)nrays, (size_t)nrays * RAY_WORDS, false))) return rc;
     HIP_TRY(upload_small(S.d_fan_origins, origins3, sizeof(float) * 3 * (size_t)norigins, g.stream));
     QueryFansExpand x;
     x.origins = S.d_fan_origins;
@@ -456,7 +429,7 @@ int query_intersect_fans(const float *origins3, int norigins, const void *d_orig
         const uint64_t key = light_key_of(po, plan[i].count);
         const LightCache &own = g.qrows.fans;
         int source = 0;
-        held = fans_foreign_cube(key, plan[i].cube_bins, &source) || (own.valid && own.key == key && own.cube_bins == plan[i].cube_bins);
+        held = fans_foreign_cube(key, plan[i].cube_bins, &source) || own.holds(key, plan[i].cube_bins);
     }
     const bool binned = may_bin && g.query_mode != MIRT_QUERY_BRUTE && (g.query_mode == MIRT_QUERY_BINNED || held || auto_bins_fans(nrays));
 
@@ -483,7 +456,7 @@ int query_intersect_fans(const float *origins3, int norigins, const void *d_orig
         if (!C) {
             // (in the stream's LIGHT scratch set, as the shared cube's build; behind the previous pass's kernel on this stream)
             bool built = false;
-            if ((rc = light_cache_ensure(g.qrows.fans, g.cur().rt_lt, po, p.count, p.cube_bins, &built))) return rc;
+            if ((rc = light_cache_ensure(g.qrows.fans, g.cur().lt, po, p.count, p.cube_bins, &built))) return rc;
             C = &g.qrows.fans;
             source = built ? 1 : 2;
         }

@@ -163,7 +163,7 @@ bool rt_bins_whole_frame(const mirt_view *view, const mirt_light *lights, int nl
 // masks, one lane per triangle (rt_tile.hip), when the operands are inside the filter's proven range; other small scenes: one
 // launch, every table built in LDS by the workgroup itself -- no origin-table kernel, no global loads inside the loops; the
 // rest: the stream's origin tables (k_prep_origin), then a wave per ray (few rays, many triangles) or the brute-force kernel.
-static int rt_dispatch_brute(RtFrame &f, const mirt_view *view, RtScratch &S, const float *origins, int nlights, bool safe, bool tile_path, size_t tile_lds)
+static int rt_dispatch_brute(RtFrame &f, const mirt_view *view, OriginTables &S, const float *origins, int nlights, bool safe, bool tile_path, size_t tile_lds)
 {
     StreamState &ss = g.cur();
     const int rows = f.y1 - f.y0;
@@ -216,7 +216,7 @@ static int rt_dispatch_brute(RtFrame &f, const mirt_view *view, RtScratch &S, co
 
     const uint32_t flags_init[4] = { safe ? 0u : 1u, 0u, 0u, 0u };
     HIP_TRY(upload_small(S.d_flags, flags_init, sizeof flags_init, g.stream));
-    S.bin_key_valid = false;                     // (k_prep_origin below overwrites the camera rows a kept binning pass would count on)
+    ss.cam.kept.forget();                        // (k_prep_origin below overwrites the camera rows a kept binning pass would count on)
     ss.hits_clean[ss.hits_tog] = false;
     HIP_TRY(upload_small(S.d_origins, origins, sizeof(float) * 3 * (1 + nlights), g.stream));
 
@@ -280,17 +280,11 @@ int rt_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, con
     ss.hits_tog ^= 1;
     g.d_hits = ss.d_hits[ss.hits_tog];
     f.hit_count = g.d_hits;
-    RtScratch &S = ss.rt;
+    OriginTables &S = ss.tabs;
     if (!tile_path) {                            // origin tables of this stream, sized for the scene and the light positions
-        if (S.cam_tab_n != g.n) {
-            S.cam_tab_n = 0;
-            if ((rc = dev_realloc(&S.d_cam_tab, (size_t)g.n))) return rc;
-            S.cam_tab_n = g.n;
-        }
+        if ((rc = S.ensure_cam_rows())) return rc;
         if (!binned && (light_positions > S.light_tab_lights || S.light_tab_n != g.n)) {   // (binned frames read the shared light cache)
-            S.light_tab_lights = 0;
-            if ((rc = dev_realloc(&S.d_light_tab, (size_t)light_positions * g.n))) return rc;
-            S.light_tab_lights = light_positions;
+            if ((rc = dev_grow(&S.d_light_tab, &S.light_tab_lights, light_positions, (size_t)light_positions * g.n, false))) return rc;
             S.light_tab_n = g.n;
         }
         if (!S.d_origins) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_origins), sizeof(float) * 3 * (1 + MIRT_MAX_LIGHTS)));
@@ -302,7 +296,7 @@ int rt_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, con
 
     if (binned) {
         BinnedPass bp;
-        if ((rc = binned_pass(view, S, ss.rt_lt, origins, nlights, y0, y1, &bp)) || (rc = binned_trace(f, S, ss.rt_lt, bp))) return rc;
+        if ((rc = binned_pass(view, ss, origins, nlights, y0, y1, &bp)) || (rc = binned_trace(f, ss, bp))) return rc;
     } else if ((rc = rt_dispatch_brute(f, view, S, origins, nlights, safe, tile_path, tile_lds))) {
         return rc;
     }

@@ -14,9 +14,9 @@ static_assert(SCENE_CULL_COPIES == MAX_FLIGHT, "one copy of the cull flags per s
 void scene_commit(bool flags_changed)
 {
     for (StreamState &ss : g.streams) {
-        ss.rt.forget_scene();                                       // tables, kept passes and pair counts belong to the old scene
-        ss.rt_lt.forget_scene();
-        for (uint64_t &k : ss.rt.hist_key) k = 0;                   // ... and so do the cost histograms
+        ss.cam.forget_scene();                                      // tables, kept passes and pair counts belong to the old scene
+        ss.lt.forget_scene();
+        ss.hist.forget_scene();                                     // ... and so do the cost histograms
     }
     g.lc.valid = false;
     if (flags_changed) {
@@ -126,11 +126,7 @@ int scene_update_host(int first, int count, const float *tris15)
     if (count == 0) return MIRT_OK;
     if ((rc = begin_change())) return rc;
     const size_t words = (size_t)count * 15;
-    if (g.scene_stage_cap < words) {
-        g.scene_stage_cap = 0;
-        if ((rc = dev_realloc(&g.d_scene_stage, words))) return rc;
-        g.scene_stage_cap = words;
-    }
+    if (g.scene_stage_cap < words && (rc = dev_grow(&g.d_scene_stage, &g.scene_stage_cap, words, words, false))) return rc;
     HIP_TRY(hipMemcpy(g.d_scene_stage, tris15, words * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(hipDeviceSynchronize());             // (a null-stream copy, as in mirt_scene_upload: landed before a kernel of our streams reads it)
     if ((rc = change_rows(first, count, g.n, g.d_scene_stage, nullptr, nullptr, false, nullptr))) return rc;

@@ -13,8 +13,8 @@ namespace mirt {
 // so); hist_publish sends them to the pinned copy, tagged with the sharded call they belong to, an event behind them.
 static bool hist_wanted() { return g.in_sharded ? g.hist_call : (g.want_hist || g.strip_rows == MIRT_PARTITION_WEIGHTED); }
 static int hist_shift_for(int tile_rows) { int sh = 0; while (((tile_rows - 1) >> sh) + 1 > SEL_HIST_MAX) sh++; return sh; }
-static int hist_slot(const RtScratch &S) { return g.in_sharded ? S.hist_next : HIST_RING; }
-int hist_prepare(RtScratch &S, const BinFrameDesc &cam, SelectOut *so)
+static int hist_slot(const CostHist &S) { return g.in_sharded ? S.hist_next : HIST_RING; }
+int hist_prepare(CostHist &S, const BinFrameDesc &cam, SelectOut *so)
 {
     g.hist_armed = false;
     if (!hist_wanted()) return MIRT_OK;
@@ -35,7 +35,7 @@ int hist_prepare(RtScratch &S, const BinFrameDesc &cam, SelectOut *so)
     g.hist_armed = true;
     return MIRT_OK;
 }
-int hist_publish(RtScratch &S)
+int hist_publish(CostHist &S)
 {
     if (!g.hist_armed) return MIRT_OK;
     g.hist_armed = false;
@@ -58,10 +58,10 @@ int hist_publish(RtScratch &S)
 // in call order, so the copy filed last is also the one of the latest call.)
 const uint32_t *hist_lookup(uint64_t max_key, int *rows, int *shift)
 {
-    RtScratch *B = nullptr;
+    CostHist *B = nullptr;
     int best = -1;
     for (StreamState &ss : g.streams) {
-        RtScratch &S = ss.rt;
+        CostHist &S = ss.hist;
         if (!S.h_hist) continue;
         for (int slot = 0; slot < (max_key ? HIST_RING : HIST_SLOTS); slot++) {
             if (S.hist_key[slot] == 0 || (max_key && S.hist_key[slot] > max_key)) continue;

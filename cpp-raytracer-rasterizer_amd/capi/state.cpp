@@ -78,29 +78,40 @@ void call_end() { if (g.cur().call_timed) (void)hipEventRecord(g.cur().ev[EV_CAL
 // ---- what the state owns ----------------------------------------------------------------------------------------
 // (a buffer is freed by the struct that holds its pointer)
 
-void RtScratch::release()
+static void dev_free(std::initializer_list<void *> ptrs) { for (void *p : ptrs) if (p) (void)hipFree(p); }
+
+void OriginTables::release() { dev_free({ d_cam_tab, d_light_tab, d_origins, d_flags }); *this = OriginTables(); }
+
+void PairList::release()
 {
-    for (void *p : { (void *)d_cam_tab, (void *)d_light_tab, (void *)d_origins, (void *)d_flags, (void *)d_frames, (void *)d_light_rows, (void *)d_order, (void *)d_bin_off,
-                     (void *)d_bin_counters, (void *)d_entries, (void *)d_pair_keys, (void *)d_pair_vals, (void *)d_sorted_keys, (void *)d_tmp_vals, (void *)d_bucket,
-                     (void *)d_sel, (void *)d_face_sel, (void *)d_hist })     // (d_face_counts lies inside d_bin_counters' block)
-        if (p) (void)hipFree(p);
+    dev_free({ d_entries, d_pair_keys, d_pair_vals, d_sorted_keys, d_tmp_vals, d_bucket });
     if (h_count) (void)hipHostFree(h_count);
     if (ev_count) (void)hipEventDestroy(ev_count);
+    *this = PairList();
+}
+
+void CameraPass::release() { pairs.release(); dev_free({ d_bin_off, d_bin_counters, d_frames, d_sel, d_order }); *this = CameraPass(); }
+
+// (d_face_counts lies inside d_bin_counters' block)
+void LightPass::release() { pairs.release(); dev_free({ d_bin_off, d_bin_counters, d_frames, d_face_sel, d_light_tab, d_light_rows }); *this = LightPass(); }
+
+void CostHist::release()
+{
+    dev_free({ d_hist });
     if (h_hist) (void)hipHostFree(h_hist);
     for (hipEvent_t e : ev_hist) if (e) (void)hipEventDestroy(e);
-    *this = RtScratch();
+    *this = CostHist();
 }
 
 void QueryScratch::release()
 {
-    for (void *p : { (void *)d_light_tab, (void *)d_origins, (void *)d_flags, (void *)d_stats[QUERY_DIRECT_LIGHT], (void *)d_stats[QUERY_FAN],
-                     (void *)d_fan_origins, (void *)d_fan_rays }) if (p) (void)hipFree(p);
+    dev_free({ d_light_tab, d_origins, d_flags, d_stats[QUERY_DIRECT_LIGHT], d_stats[QUERY_FAN], d_fan_origins, d_fan_rays });
     *this = QueryScratch();
 }
 
 void QueryRows::release()
 {
-    for (void *p : { (void *)d_rows, (void *)d_max, d_rays, d_hits, d_rgb, d_dirs, d_origin_of }) if (p) (void)hipFree(p);
+    dev_free({ d_rows, d_max, d_rays, d_hits, d_rgb, d_dirs, d_origin_of });
     if (ev_built) (void)hipEventDestroy(ev_built);
     cube.release();
     fan.release();
@@ -108,12 +119,7 @@ void QueryRows::release()
     *this = QueryRows();
 }
 
-void LightCache::release()
-{
-    for (void *p : { (void *)d_light_tab, (void *)d_frames, (void *)d_off, (void *)d_rows, (void *)d_row_tri, (void *)d_origins, (void *)d_counter })
-        if (p) (void)hipFree(p);
-    *this = LightCache();
-}
+void LightCache::release() { dev_free({ d_light_tab, d_frames, d_off, d_rows, d_row_tri, d_origins, d_counter }); *this = LightCache(); }
 
 int StreamState::create()
 {
@@ -128,12 +134,14 @@ int StreamState::create()
 
 void StreamState::release()
 {
-    rt.release();
-    rt_lt.release();
+    tabs.release();
+    cam.release();
+    lt.release();
+    hist.release();
     raster_scratch_free(raster);
     query.release();
     dof.release();
-    for (void *p : { (void *)d_hits[0], (void *)d_hits[1], (void *)d_tile_tab, d_async }) if (p) (void)hipFree(p);
+    dev_free({ d_hits[0], d_hits[1], d_tile_tab, d_async });
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : { ev_order, ev_cull_read, ev_fork, ev_join }) if (e) (void)hipEventDestroy(e);
     if (aux) (void)hipStreamDestroy(aux);

@@ -359,3 +359,89 @@ def test_auto_follows_the_frame_paths_rule(oracle):
     out, st = light_query(small, far, mirt.QUERY_BINNED)
     assert st["mode_used"] == mirt.QUERY_BRUTE
     rq.same_bits(out, rq.oracle_direct_light(oracle, tris, small, far), "light out of range")
+
+
+# ---- the three users of a stream's light scratch set, in turn -------------------------------------------------------------
+
+_evict = {}
+
+
+def _evict_case(oracle):
+    """Scene, view, 256 closest-hit records of the frame's primary rays, and the brute-force frame and colours: computed once."""
+    if not _evict:
+        from devbuf import DeviceArray
+        tris = mirt.scene_soup(17, 2500, 0.08)
+        W, H, cam, focal = 160, 96, (0.0, 0.0, -2.5), 120.0
+        rot = oracle.rot_from_yaw(0.1, 1.0)
+        view = mirt.make_view(cam, rot, focal, W, H)
+        L0, L1 = LIGHTS[0:1], LIGHTS[1:2]
+        mirt.scene_upload(tris)
+        hits = mirt.intersect(rq.primary_rays(oracle, cam, rot, focal, W, H))
+        hit_ids = np.flatnonzero(hits["index"] >= 0)
+        assert len(hit_ids) >= 256
+        recs = np.ascontiguousarray(hits[hit_ids[:: len(hit_ids) // 256][:256]])
+        with DeviceArray((H, W), np.uint32, 0x11) as x:
+            mirt.raytrace_device(view, L0, (0.2, 0.2, 0.2), mirt.RT_BRUTE, 0, H, 0, x.ptr, W * 4)
+            want_frame = x.read()
+        want_rgb, sb = light_query(recs, L1, mirt.QUERY_BRUTE)
+        assert sb["mode_used"] == mirt.QUERY_BRUTE and want_rgb.any()
+        want_frame.setflags(write=False)
+        want_rgb.setflags(write=False)
+        _evict.update(tris=tris, view=view, W=W, H=H, L0=L0, L1=L1, recs=recs, want_frame=want_frame, want_rgb=want_rgb)
+    return _evict
+
+
+@pytest.mark.parametrize("in_flight", [1, 2])
+def test_frames_and_queries_take_the_light_scratch_in_turn(oracle, in_flight):
+    """A stream's light scratch set has three users that evict one another: a frame's moving-light pass, the frame path's shared
+    cube build and a query's cube build.  Frames under L0 and DirectLight queries under L1 take them in turn; every frame equals
+    the brute-force frame and both queries the brute-force colours, bit for bit.  One frame in flight with a sync after each call,
+    and two in flight with one sync at the end.  (A kept pass belongs to a stream: with two in flight the frame that comes back to
+    the first frame's stream is the third, so step 2 renders `in_flight` frames and the last of them must have kept its pass.)"""
+    from devbuf import DeviceArray
+    c = _evict_case(oracle)
+    W, H, view, L0, L1, recs = c["W"], c["H"], c["view"], c["L0"], c["L1"], c["recs"]
+    mirt.scene_upload(c["tris"])                              # (a new scene version: no pass, no cube is held)
+    d_hits = rq._to_device(recs)
+    planes, outs = [], []
+
+    def frame():
+        x = DeviceArray((H, W), np.uint32, 0x11)
+        planes.append(x)
+        mirt.raytrace_device(view, L0, (0.2, 0.2, 0.2), mirt.RT_BINNED, 0, H, 0, x.ptr, W * 4)
+        if in_flight == 1:
+            mirt.sync()
+
+    def query():
+        d_rgb = DeviceArray((len(recs), 3), np.float32, 0x11)
+        outs.append(d_rgb)
+        mirt.direct_light_device(d_hits.ptr, len(recs), L1, d_rgb.ptr)
+        st = mirt.query_stats()
+        if in_flight == 1:
+            mirt.sync()
+        return st
+
+    mirt.set_query_mode(mirt.QUERY_BINNED)
+    try:
+        mirt.set_frames_in_flight(in_flight)
+        frame()                                               # 1. new lights: the frame's own pass
+        assert mirt.stats()["mode_used"] == mirt.RT_BINNED
+        for _ in range(in_flight):                            # 2. the same frame again, back on the first frame's stream
+            frame()
+        assert mirt.stats()["bins_reused"] == 1
+        st = query()                                          # 3. L1's cube is built in the same scratch set
+        assert st["mode_used"] == mirt.QUERY_BINNED and st["cube_source"] == 1
+        for _ in range(5):                                    # 4. the lights settle into the shared cube
+            frame()
+        st = query()                                          # 5. L1's cube is held
+        assert st["mode_used"] == mirt.QUERY_BINNED and st["cube_source"] == 2
+        mirt.sync()
+        for i, x in enumerate(planes):
+            assert np.array_equal(x.read(), c["want_frame"]), "frame %d of %d in flight" % (i, in_flight)
+        for i, d in enumerate(outs):
+            rq.same_bits(d.read(), c["want_rgb"], "query %d of %d in flight" % (i, in_flight))
+    finally:
+        mirt.set_query_mode(mirt.QUERY_AUTO)
+        mirt.set_frames_in_flight(1)
+        for d in planes + outs + [d_hits]:
+            d.free()
