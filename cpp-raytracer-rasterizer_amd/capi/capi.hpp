@@ -308,7 +308,7 @@ struct QueryRows {
     // The cube of the many-origin fans (mirt_intersect_fans*): up to MIRT_MAX_LIGHTS of the call's origins as its positions, keyed
     // by scene version, positions and their order (light_key_of), built by light_cache_ensure under the same protocol.  A call of
     // several passes leaves the last range's cube here.  Apart from `fan` and `cube`: the call evicts neither, and a pass whose
-    // positions are the ones g.lc or `cube` holds reads that cube instead (query.cpp: fans_foreign_cube).
+    // positions are the ones g.lc or `cube` holds reads that cube instead (query.cpp: walk_cube).
     LightCache fans;
 
     void release();                              // (the cubes' tables too)

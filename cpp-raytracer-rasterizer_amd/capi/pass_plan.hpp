@@ -1,7 +1,7 @@
 // pass_plan.hpp -- the decisions of the binned ray tracer's host side that are pure arithmetic, free of library state: whether a
 // kept pass still serves, how a pair list is sized, how many depth shells fit the sort's keys, the frame descriptors of the light
-// cubes, and the view a walk kernel gets of a cube's tables.  binned.cpp applies them to the streams' state and the uploaded scene;
-// tests/cpp/pass_plan_test.cpp checks them on the CPU.
+// cubes, whether a ray query bins, and the view a walk kernel gets of a cube's tables.  binned.cpp and query.cpp apply them to the
+// streams' state and the uploaded scene; tests/cpp/pass_plan_test.cpp checks them on the CPU.
 #pragma once
 
 #include "../query/rt_query.hpp"
@@ -110,6 +110,15 @@ inline void fill_light_frames(BinFrameDesc *frames, const float *origins, int nl
             base_bins += (uint32_t)(cube_bins * cube_bins);
         }
     }
+}
+
+// ---- a query: through a cube's bins, or by brute force ----
+// The one rule of DirectLight, the single fan and the many-origin call.  may_bin: the call is inside what the frame path would bin
+// (the filter's proven range, keys the sort can hold) -- outside it nothing bins, whatever the mode; held: the cube of every pass
+// of the call is there already, so that binning costs no build; auto_bins: the call's own AUTO rule (query.cpp).
+inline bool query_bins(bool may_bin, int mode, bool held, bool auto_bins)
+{
+    return may_bin && mode != MIRT_QUERY_BRUTE && (mode == MIRT_QUERY_BINNED || held || auto_bins);
 }
 
 // ---- the view of a cube's tables ----

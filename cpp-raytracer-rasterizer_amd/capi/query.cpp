@@ -55,6 +55,15 @@ static int check_query_args(const void *in, int count, const void *out, const ch
     return MIRT_OK;
 }
 
+// ... of mirt_intersect_from*: check_query_args, then the origin (a call without rays needs none).
+static int check_from_args(const float *origin, const void *dirs3, int nrays, const void *hits)
+{
+    int rc;
+    if ((rc = check_query_args(dirs3, nrays, hits, "direction"))) return rc;
+    if (nrays > 0 && !origin) return fail(MIRT_ERR_INVALID_ARGUMENT, "origin must not be NULL when the count is > 0");
+    return MIRT_OK;
+}
+
 static int need_scene()
 {
     if (g.n <= 0) return fail(MIRT_ERR_NO_SCENE, "no scene uploaded (mirt_scene_upload)");
@@ -125,6 +134,50 @@ static int stats_arm(int kind, unsigned long long **counters)
     if (!d) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(unsigned long long) * QSTAT_WORDS));
     HIP_TRY(hipMemsetAsync(d, 0, sizeof(unsigned long long) * QSTAT_WORDS, g.stream));
     g.qstats[kind].dev = *counters = d;
+    return MIRT_OK;
+}
+
+// The STATS or the plain instantiation of a walk kernel over `f` on the current stream, as stats_arm decided.
+template <class Frame>
+static int launch_walk(void (*plain)(Frame), void (*counting)(Frame), bool stats, dim3 grid, const Frame &f)
+{
+    hipLaunchKernelGGL(stats ? counting : plain, grid, dim3(256), 0, g.stream, f);
+    HIP_TRY(hipGetLastError());
+    return MIRT_OK;
+}
+
+// Whether the scene and every one of the npos start points pos3 are inside the filter's proven range (rt_frame.cpp: operands_safe):
+// what is not, is never binned, whatever the mode -- the frame path does not bin it either (rt_enqueue).
+static bool starts_safe(const float *pos3, int npos)
+{
+    bool safe = g.scene_finite;
+    for (int k = 0; k < npos; k++) safe = safe && start_in_filter_range(pos3 + 3 * (size_t)k);
+    return safe;
+}
+
+// The cube a walk from the npos positions origins[3 ..] reads on a grid of cube_bins, and the cube_source that makes.  A cube
+// somebody else holds for these very positions on this very grid comes first -- `foreign`, in the caller's order, each with its
+// source code; read, never written, nor its owner's tracking --, else the caller's own.  held_cube builds nothing and answers
+// with no cube when none is held (the `held` of AUTO); walk_cube builds the caller's own if need be, in the stream's LIGHT
+// scratch set as the shared cube's build (the pass that set kept for moving lights is invalidated there).  An own cube that is
+// held is returned without a call of light_cache_ensure: for a held cube that function returns at once, built = false, having
+// touched nothing (binned.cpp) -- should it ever do more for a held cube, walk_cube has to call it in that case too.
+struct CubeChoice { const LightCache *cube; int source; };
+static CubeChoice held_cube(std::initializer_list<CubeChoice> foreign, const LightCache &own, const float *origins, int npos, int cube_bins)
+{
+    const uint64_t key = light_key_of(origins, npos);
+    for (const CubeChoice &f : foreign)
+        if (f.cube->holds(key, cube_bins)) return f;
+    return CubeChoice{ own.holds(key, cube_bins) ? &own : nullptr, 2 };
+}
+static int walk_cube(std::initializer_list<CubeChoice> foreign, LightCache &own, const float *origins, int npos, int cube_bins, CubeChoice *out)
+{
+    int rc;
+    *out = held_cube(foreign, own, origins, npos, cube_bins);
+    if (out->cube) return MIRT_OK;
+    bool built = false;
+    if ((rc = light_cache_ensure(own, g.cur().lt, origins, npos, cube_bins, &built))) return rc;
+    *out = CubeChoice{ &own, built ? 1 : 2 };
     return MIRT_OK;
 }
 
@@ -208,10 +261,7 @@ static int direct_light_binned(QueryLightFrame &q, const LightCache &C)
     b.cube = cube_view(C);
     if ((rc = stats_arm(QUERY_DIRECT_LIGHT, &b.stats))) return rc;
     const dim3 grid((unsigned)((q.nhits + 256 * QUERY_BIN_P - 1) / (256 * QUERY_BIN_P)));
-    if (b.stats) hipLaunchKernelGGL((k_query_direct_light_binned<QUERY_BIN_P, true>), grid, dim3(256), 0, g.stream, b);
-    else hipLaunchKernelGGL((k_query_direct_light_binned<QUERY_BIN_P, false>), grid, dim3(256), 0, g.stream, b);
-    HIP_TRY(hipGetLastError());
-    return MIRT_OK;
+    return launch_walk(k_query_direct_light_binned<QUERY_BIN_P, false>, k_query_direct_light_binned<QUERY_BIN_P, true>, b.stats != nullptr, grid, b);
 }
 
 int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_rgb)
@@ -232,41 +282,27 @@ int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, 
     f.samples = soft_samples();
     float origins[(1 + MIRT_MAX_LIGHTS) * 3] = {};
     fill_light_positions(lights, npos, f.lpos, f.lcol, origins);
-    bool safe = g.scene_finite;
-    for (int j = 0; j < npos; j++) safe = safe && start_in_filter_range(f.lpos[j]);    // a shadow ray's start (rt_frame.cpp: operands_safe)
+    const bool safe = starts_safe(origins + 3, npos);        // the shadow rays' starts (f.lpos, as origins holds them too)
     q.hits = static_cast<const uint32_t *>(d_hits);
     q.nhits = nhits;
     q.rgb = static_cast<float *>(d_rgb);
 
-    // Binned or brute.  The frame path does not bin what lies outside the filter's proven range (rt_enqueue: operands_safe -- the
-    // scene, a light position; here that is the `unsafe` flag the brute kernel would be given) or what the sort cannot key; nor
-    // does a query, whatever the mode.  The cube: the frame path's when it holds these very lights on this very grid (read, never
-    // written -- nor its tracking of the frames' lights), else the queries' own, built now if need be.
+    // Binned or brute.  Never what lies outside the filter's proven range (`safe`: here that is the `unsafe` flag the brute kernel
+    // would be given) or what the sort cannot key.  The cube: the frame path's when it holds these very lights, else the queries' own.
     bool fixed_grid = false;
     const int cube_bins = light_cube_bins_for(npos, &fixed_grid);
     const bool may_bin = safe && npos > 0 && light_keys_fit(npos, cube_bins);
-    const uint64_t lkey = may_bin ? light_key_of(origins, npos) : 0;
-    LightCache &own = g.qrows.cube;
-    const bool frames_cube = may_bin && g.lc.holds(lkey, cube_bins);
-    const bool own_cube = may_bin && own.holds(lkey, cube_bins);
-    const bool binned = may_bin && g.query_mode != MIRT_QUERY_BRUTE &&
-                        (g.query_mode == MIRT_QUERY_BINNED || frames_cube || own_cube || auto_bins(nhits, npos));
+    const bool held = may_bin && held_cube({ { &g.lc, 3 } }, g.qrows.cube, origins, npos, cube_bins).cube != nullptr;
+    const bool binned = query_bins(may_bin, g.query_mode, held, auto_bins(nhits, npos));
 
     stream_begin();
     QueryStats &stats = stats_begin(QUERY_DIRECT_LIGHT, binned);
     if (!binned) return direct_light_brute(q, origins, npos, safe);
 
-    const LightCache *C = &g.lc;
-    int source = 3;
-    if (!frames_cube) {
-        // (in the stream's LIGHT scratch set, as the shared cube's build: the pass that set kept for moving lights is invalidated there)
-        bool built = false;
-        if ((rc = light_cache_ensure(own, g.cur().lt, origins, npos, cube_bins, &built))) return rc;
-        C = &own;
-        source = built ? 1 : 2;
-    }
-    stats_cube(stats, *C, source);
-    return direct_light_binned(q, *C);
+    CubeChoice c;
+    if ((rc = walk_cube({ { &g.lc, 3 } }, g.qrows.cube, origins, npos, cube_bins, &c))) return rc;
+    stats_cube(stats, *c.cube, c.source);
+    return direct_light_binned(q, *c.cube);
 }
 
 // ---- origin fans: ClosestIntersection for many directions from one origin (mirt_intersect_from*) -----------------------------
@@ -283,33 +319,38 @@ static bool auto_bins_fan(int nrays)
     return g.n >= auto_bin_threshold() && (g.n >= FAN_AUTO_TRIANGLES || (long long)nrays * g.n >= 40000000LL);
 }
 
-int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, void *d_hits)
+// What the frames of both fan calls share: the scene, the caller's directions and records; everything else zero.
+static QueryFanFrame fan_frame(const void *d_dirs3, int nrays, void *d_hits)
 {
-    int rc;
-    if ((rc = check_query_args(d_dirs3, nrays, d_hits, "direction"))) return rc;
-    if (nrays == 0) return MIRT_OK;
-    if (!origin) return fail(MIRT_ERR_INVALID_ARGUMENT, "origin must not be NULL when the count is > 0");
-    if ((rc = need_scene())) return rc;
-
     QueryFanFrame q;
     memset(&q, 0, sizeof q);
     q.tris15 = g.d_tris;
     q.n = g.n;
-    memcpy(q.origin, origin, 12);
     q.dirs = static_cast<const float *>(d_dirs3);
     q.nrays = nrays;
     q.hits = static_cast<uint32_t *>(d_hits);
+    return q;
+}
+
+int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, void *d_hits)
+{
+    int rc;
+    if ((rc = check_from_args(origin, d_dirs3, nrays, d_hits))) return rc;
+    if (nrays == 0) return MIRT_OK;
+    if ((rc = need_scene())) return rc;
+
+    QueryFanFrame q = fan_frame(d_dirs3, nrays, d_hits);
+    memcpy(q.origin, origin, 12);
     float origins[6] = {};
     memcpy(origins + 3, origin, 12);
-    const bool safe = g.scene_finite && start_in_filter_range(origin);     // the rays' start (rt_frame.cpp: operands_safe)
+    const bool safe = starts_safe(origin, 1);
 
-    // Binned or brute, as a DirectLight query decides it: never what the frame path would not bin, whatever the mode.
+    // Binned or brute, as a DirectLight query decides it.  The cube is the fans' own, whoever else holds one for this point.
     bool fixed_grid = false;
     const int cube_bins = light_cube_bins_for(1, &fixed_grid);
     const bool may_bin = safe && light_keys_fit(1, cube_bins);
-    LightCache &C = g.qrows.fan;
-    const bool held = may_bin && C.holds(light_key_of(origins, 1), cube_bins);
-    const bool binned = may_bin && g.query_mode != MIRT_QUERY_BRUTE && (g.query_mode == MIRT_QUERY_BINNED || held || auto_bins_fan(nrays));
+    const bool held = may_bin && held_cube({}, g.qrows.fan, origins, 1, cube_bins).cube != nullptr;
+    const bool binned = query_bins(may_bin, g.query_mode, held, auto_bins_fan(nrays));
 
     stream_begin();
     QueryStats &stats = stats_begin(QUERY_FAN, binned);
@@ -323,18 +364,13 @@ int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, vo
         return MIRT_OK;
     }
 
-    // (in the stream's LIGHT scratch set, as the shared cube's build)
-    bool built = false;
-    if ((rc = light_cache_ensure(C, g.cur().lt, origins, 1, cube_bins, &built))) return rc;
-    stats_cube(stats, C, built ? 1 : 2);
-    q.tab = C.d_light_tab;
-    q.cube = cube_view(C);
+    CubeChoice c;
+    if ((rc = walk_cube({}, g.qrows.fan, origins, 1, cube_bins, &c))) return rc;
+    stats_cube(stats, *c.cube, c.source);
+    q.tab = c.cube->d_light_tab;
+    q.cube = cube_view(*c.cube);
     if ((rc = stats_arm(QUERY_FAN, &q.stats))) return rc;
-    const dim3 grid((unsigned)((nrays + 255) / 256));
-    if (q.stats) hipLaunchKernelGGL(k_query_fan_binned<true>, grid, dim3(256), 0, g.stream, q);
-    else hipLaunchKernelGGL(k_query_fan_binned<false>, grid, dim3(256), 0, g.stream, q);
-    HIP_TRY(hipGetLastError());
-    return MIRT_OK;
+    return launch_walk(k_query_fan_binned<false>, k_query_fan_binned<true>, q.stats != nullptr, dim3((unsigned)((nrays + 255) / 256)), q);
 }
 
 // ---- origin fans from many origins in one call (mirt_intersect_fans*) ----------------------------------------------------------
@@ -379,15 +415,6 @@ static void fans_pass_origins(const float *origins3, const FanPass &p, float *po
     memcpy(po + 3, origins3 + 3 * (size_t)p.first, sizeof(float) * 3 * p.count);
 }
 
-// A cube somebody else holds for the pass's positions and grid: the frame path's (*source = 3), DirectLight's (4), or none.
-static const LightCache *fans_foreign_cube(uint64_t key, int cube_bins, int *source)
-{
-    if (g.lc.holds(key, cube_bins)) { *source = 3; return &g.lc; }
-    const LightCache &D = g.qrows.cube;
-    if (D.holds(key, cube_bins)) { *source = 4; return &D; }
-    return nullptr;
-}
-
 // By definition the call is mirt_intersect on the expanded rays: they are written out on the device (k_query_fans_expand) into
 // the stream's query scratch and go through query_intersect's kernels, whose per-ray filter safety and choice of kernel come along.
 static int fans_brute(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, void *d_hits)
@@ -418,20 +445,16 @@ int query_intersect_fans(const float *origins3, int norigins, const void *d_orig
 
     // Binned or brute, as the single fan decides it: never what the frame path would not bin, whatever the mode -- and the call is
     // one: an origin outside the filter's range (NaN included) among ordinary ones sends all of it to the brute-force kernels.
-    bool safe = g.scene_finite;
-    for (int k = 0; k < norigins; k++) safe = safe && start_in_filter_range(origins3 + 3 * (size_t)k);
     std::vector<FanPass> plan;
-    const bool may_bin = safe && fan_pass_plan(norigins, g.n, cube_bins_override(), &plan);
+    const bool may_bin = starts_safe(origins3, norigins) && fan_pass_plan(norigins, g.n, cube_bins_override(), &plan);
+    const std::initializer_list<CubeChoice> foreign = { { &g.lc, 3 }, { &g.qrows.cube, 4 } };
     float po[(1 + MIRT_MAX_LIGHTS) * 3];
-    bool held = may_bin;
+    bool held = may_bin;                                                     // (every pass's cube, that is)
     for (size_t i = 0; held && i < plan.size(); i++) {
         fans_pass_origins(origins3, plan[i], po);
-        const uint64_t key = light_key_of(po, plan[i].count);
-        const LightCache &own = g.qrows.fans;
-        int source = 0;
-        held = fans_foreign_cube(key, plan[i].cube_bins, &source) || own.holds(key, plan[i].cube_bins);
+        held = held_cube(foreign, g.qrows.fans, po, plan[i].count, plan[i].cube_bins).cube != nullptr;
     }
-    const bool binned = may_bin && g.query_mode != MIRT_QUERY_BRUTE && (g.query_mode == MIRT_QUERY_BINNED || held || auto_bins_fans(nrays));
+    const bool binned = query_bins(may_bin, g.query_mode, held, auto_bins_fans(nrays));
 
     stream_begin();
     QueryStats &stats = stats_begin(QUERY_FAN, binned);
@@ -439,11 +462,7 @@ int query_intersect_fans(const float *origins3, int norigins, const void *d_orig
 
     QueryFansFrame q;
     memset(&q, 0, sizeof q);
-    q.f.tris15 = g.d_tris;
-    q.f.n = g.n;
-    q.f.dirs = static_cast<const float *>(d_dirs3);
-    q.f.nrays = nrays;
-    q.f.hits = static_cast<uint32_t *>(d_hits);
+    q.f = fan_frame(d_dirs3, nrays, d_hits);
     q.origin_of = static_cast<const int32_t *>(d_origin_of);
     if ((rc = stats_arm(QUERY_FAN, &q.f.stats))) return rc;          // (once: the passes' kernels add up in the same words)
     const dim3 grid((unsigned)((nrays + 255) / 256));
@@ -451,26 +470,17 @@ int query_intersect_fans(const float *origins3, int norigins, const void *d_orig
     for (size_t i = 0; i < plan.size(); i++) {
         const FanPass &p = plan[i];
         fans_pass_origins(origins3, p, po);
-        int source = 0;
-        const LightCache *C = fans_foreign_cube(light_key_of(po, p.count), p.cube_bins, &source);
-        if (!C) {
-            // (in the stream's LIGHT scratch set, as the shared cube's build; behind the previous pass's kernel on this stream)
-            bool built = false;
-            if ((rc = light_cache_ensure(g.qrows.fans, g.cur().lt, po, p.count, p.cube_bins, &built))) return rc;
-            C = &g.qrows.fans;
-            source = built ? 1 : 2;
-        }
+        CubeChoice c;                                                        // (a build: behind the previous pass's kernel on this stream)
+        if ((rc = walk_cube(foreign, g.qrows.fans, po, p.count, p.cube_bins, &c))) return rc;
         // 1 as soon as a pass built; else what every pass read when that is one kind of cube; else 2: all were held
-        source_all = i == 0 ? source : (source_all == 1 || source == 1 ? 1 : (source_all == source ? source : 2));
-        stats_cube(stats, *C, source_all);
-        q.f.tab = C->d_light_tab;
-        q.f.cube = cube_view(*C);
-        q.origins = C->d_origins;
+        source_all = i == 0 ? c.source : (source_all == 1 || c.source == 1 ? 1 : (source_all == c.source ? c.source : 2));
+        stats_cube(stats, *c.cube, source_all);
+        q.f.tab = c.cube->d_light_tab;
+        q.f.cube = cube_view(*c.cube);
+        q.origins = c.cube->d_origins;
         q.first = p.first;
         q.count = p.count;
-        if (q.f.stats) hipLaunchKernelGGL(k_query_fans_binned<true>, grid, dim3(256), 0, g.stream, q);
-        else hipLaunchKernelGGL(k_query_fans_binned<false>, grid, dim3(256), 0, g.stream, q);
-        HIP_TRY(hipGetLastError());
+        if ((rc = launch_walk(k_query_fans_binned<false>, k_query_fans_binned<true>, q.f.stats != nullptr, grid, q))) return rc;
     }
     return MIRT_OK;
 }
@@ -502,82 +512,76 @@ static int query_staging(size_t count)
     return MIRT_OK;
 }
 
-// One host-buffer entry point around its device form `call`: every `in` array goes to its staging array on the stream the call
-// will take, every `out` array comes back on the stream it took, and the host waits for that stream.
-struct HostArray { void *host; void *staging; size_t bytes; bool in, out; };
+// One host-buffer entry point around its device form `call`, given the verdict of that form's argument checks and the call's
+// `count` of rays or records: nothing to do for none, then the scene, then staging room for `count`; every `in` array goes to its
+// staging array (a member of g.qrows) on the stream the call will take, every `out` array comes back on the stream it took, and
+// the host waits for that stream.
+struct HostArray { void *host; void *QueryRows::*staging; size_t bytes; bool in, out; };
 template <int N, class Call>
-static int with_host_arrays(const HostArray (&a)[N], Call call)
+static int with_host_arrays(int checked, int count, const HostArray (&a)[N], Call call)
 {
     int rc;
+    if (checked) return checked;
+    if (count == 0) return MIRT_OK;
+    if ((rc = need_scene())) return rc;
+    if ((rc = query_staging((size_t)count))) return rc;
     hipStream_t st = g.streams[next_si()].stream;            // the stream the query below will take
     for (const HostArray &x : a)
-        if (x.in) HIP_TRY(hipMemcpyAsync(x.staging, x.host, x.bytes, hipMemcpyHostToDevice, st));
+        if (x.in) HIP_TRY(hipMemcpyAsync(g.qrows.*x.staging, x.host, x.bytes, hipMemcpyHostToDevice, st));
     if ((rc = call())) return rc;
     for (const HostArray &x : a)
-        if (x.out) HIP_TRY(hipMemcpyAsync(x.host, x.staging, x.bytes, hipMemcpyDeviceToHost, g.stream));
+        if (x.out) HIP_TRY(hipMemcpyAsync(x.host, g.qrows.*x.staging, x.bytes, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     return MIRT_OK;
 }
 
 int query_intersect_host(const mirt_ray *rays, int nrays, mirt_hit *hits)
 {
-    int rc;
-    if ((rc = check_query_args(rays, nrays, hits, "ray"))) return rc;
-    if (nrays == 0) return MIRT_OK;
-    if ((rc = need_scene())) return rc;
-    if ((rc = query_staging((size_t)nrays))) return rc;
     QueryRows &Q = g.qrows;
-    const HostArray a[] = { { (void *)rays, Q.d_rays, (size_t)nrays * sizeof(mirt_ray), true, false },
-                            { hits, Q.d_hits, (size_t)nrays * sizeof(mirt_hit), true, true } };
-    return with_host_arrays(a, [&] { return query_intersect(Q.d_rays, nrays, Q.d_hits); });
+    const HostArray a[] = { { (void *)rays, &QueryRows::d_rays, (size_t)nrays * sizeof(mirt_ray), true, false },
+                            { hits, &QueryRows::d_hits, (size_t)nrays * sizeof(mirt_hit), true, true } };
+    return with_host_arrays(check_query_args(rays, nrays, hits, "ray"), nrays, a, [&] { return query_intersect(Q.d_rays, nrays, Q.d_hits); });
 }
 
 int query_direct_light_host(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, float *out_rgb)
 {
-    int rc, npos = 0;
-    if ((rc = check_query_args(hits, nhits, out_rgb, "hit"))) return rc;
-    if ((rc = check_lights(lights, nlights, &npos))) return rc;
-    if (nhits == 0) return MIRT_OK;
-    if ((rc = need_scene())) return rc;
-    if ((rc = query_staging((size_t)nhits))) return rc;
+    int npos = 0, checked = check_query_args(hits, nhits, out_rgb, "hit");
+    if (!checked) checked = check_lights(lights, nlights, &npos);
     QueryRows &Q = g.qrows;
-    const HostArray a[] = { { (void *)hits, Q.d_hits, (size_t)nhits * sizeof(mirt_hit), true, false },
-                            { out_rgb, Q.d_rgb, (size_t)nhits * 3 * sizeof(float), false, true } };
-    return with_host_arrays(a, [&] { return query_direct_light(Q.d_hits, nhits, lights, nlights, Q.d_rgb); });
+    const HostArray a[] = { { (void *)hits, &QueryRows::d_hits, (size_t)nhits * sizeof(mirt_hit), true, false },
+                            { out_rgb, &QueryRows::d_rgb, (size_t)nhits * 3 * sizeof(float), false, true } };
+    return with_host_arrays(checked, nhits, a, [&] { return query_direct_light(Q.d_hits, nhits, lights, nlights, Q.d_rgb); });
 }
 
 int query_intersect_from_host(const float *origin, const float *dirs3, int nrays, mirt_hit *hits)
 {
-    int rc;
-    if ((rc = check_query_args(dirs3, nrays, hits, "direction"))) return rc;
-    if (nrays == 0) return MIRT_OK;
-    if (!origin) return fail(MIRT_ERR_INVALID_ARGUMENT, "origin must not be NULL when the count is > 0");
-    if ((rc = need_scene())) return rc;
-    if ((rc = query_staging((size_t)nrays))) return rc;
     QueryRows &Q = g.qrows;
-    const HostArray a[] = { { (void *)dirs3, Q.d_dirs, (size_t)nrays * 3 * sizeof(float), true, false },
-                            { hits, Q.d_hits, (size_t)nrays * sizeof(mirt_hit), true, true } };
-    return with_host_arrays(a, [&] { return query_intersect_from(origin, Q.d_dirs, nrays, Q.d_hits); });
+    const HostArray a[] = { { (void *)dirs3, &QueryRows::d_dirs, (size_t)nrays * 3 * sizeof(float), true, false },
+                            { hits, &QueryRows::d_hits, (size_t)nrays * sizeof(mirt_hit), true, true } };
+    return with_host_arrays(check_from_args(origin, dirs3, nrays, hits), nrays, a, [&] { return query_intersect_from(origin, Q.d_dirs, nrays, Q.d_hits); });
 }
 
 // The host form looks at every index before anything touches the device; the device form cannot (its kernels leave such a ray's
 // record unwritten).
-int query_intersect_fans_host(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, mirt_hit *hits)
+static int check_fans_host_args(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, const mirt_hit *hits)
 {
     int rc;
     if ((rc = check_fans_args(origins3, norigins, origin_of, dirs3, nrays, hits))) return rc;
-    if (nrays == 0) return MIRT_OK;
     if (origin_of)
         for (int i = 0; i < nrays; i++)
             if (origin_of[i] < 0 || origin_of[i] >= norigins)
                 return fail(MIRT_ERR_INVALID_ARGUMENT, "origin_of[%d] = %d is outside [0, %d)", i, (int)origin_of[i], norigins);
-    if ((rc = need_scene())) return rc;
-    if ((rc = query_staging((size_t)nrays))) return rc;
+    return MIRT_OK;
+}
+
+int query_intersect_fans_host(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, mirt_hit *hits)
+{
     QueryRows &Q = g.qrows;
-    const HostArray a[] = { { (void *)dirs3, Q.d_dirs, (size_t)nrays * 3 * sizeof(float), true, false },
-                            { hits, Q.d_hits, (size_t)nrays * sizeof(mirt_hit), true, true },
-                            { (void *)origin_of, Q.d_origin_of, (size_t)nrays * sizeof(int32_t), origin_of != nullptr, false } };
-    return with_host_arrays(a, [&] { return query_intersect_fans(origins3, norigins, origin_of ? Q.d_origin_of : nullptr, Q.d_dirs, nrays, Q.d_hits); });
+    const HostArray a[] = { { (void *)dirs3, &QueryRows::d_dirs, (size_t)nrays * 3 * sizeof(float), true, false },
+                            { hits, &QueryRows::d_hits, (size_t)nrays * sizeof(mirt_hit), true, true },
+                            { (void *)origin_of, &QueryRows::d_origin_of, (size_t)nrays * sizeof(int32_t), origin_of != nullptr, false } };
+    return with_host_arrays(check_fans_host_args(origins3, norigins, origin_of, dirs3, nrays, hits), nrays, a,
+                            [&] { return query_intersect_fans(origins3, norigins, origin_of ? Q.d_origin_of : nullptr, Q.d_dirs, nrays, Q.d_hits); });
 }
 
 }  // namespace mirt

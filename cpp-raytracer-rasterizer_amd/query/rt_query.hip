@@ -335,6 +335,19 @@ __device__ __forceinline__ v3 reference_nan(v3 c, v3 pos)
     return V3(c.x != c.x ? n : c.x, c.y != c.y ? n : c.y, c.z != c.z ? n : c.z);
 }
 
+// Record `rec` as DirectLight reads it (record 0 for a lane without one): its position, its triangle's 15 words and unit normal,
+// and whether it names a triangle of the scene at all (triangle 0's words are read where it does not).
+__device__ __forceinline__ bool light_record(const QueryLightFrame &q, long long rec, bool ok, v3 *pos, const float **t, v3 *nDir)
+{
+    const uint32_t *h = q.hits + (size_t)HIT_WORDS * (ok ? rec : 0);
+    *pos = V3(__uint_as_float(h[0]), __uint_as_float(h[1]), __uint_as_float(h[2]));
+    const int idx = (int)h[4];
+    const bool valid = ok && idx >= 0 && idx < q.f.n;
+    *t = q.f.tris15 + (size_t)15 * (valid ? idx : 0);
+    *nDir = normalize3(ld3(*t + 9));                               // glm::normalize(triangles[i.triangleIndex].normal) (:300)
+    return valid;
+}
+
 template <int P, bool FILTER>
 __device__ __forceinline__ void direct_light_body(const QueryLightFrame &q, float4 *s_tab)
 {
@@ -344,14 +357,10 @@ __device__ __forceinline__ void direct_light_body(const QueryLightFrame &q, floa
     v3 pos[P], nDir[P], tcol[P], result[P], result2[P];
 #pragma unroll
     for (int p = 0; p < P; p++) {
-        rec[p] = ((long long)blockIdx.x * P + p) * 256 + threadIdx.x;
+        rec[p] = lane_ray<P>(p);
         ok[p] = rec[p] < q.nhits;
-        const uint32_t *h = q.hits + (size_t)HIT_WORDS * (ok[p] ? rec[p] : 0);
-        pos[p] = V3(__uint_as_float(h[0]), __uint_as_float(h[1]), __uint_as_float(h[2]));
-        const int idx = (int)h[4];
-        valid[p] = ok[p] && idx >= 0 && idx < f.n;
-        const float *t = f.tris15 + (size_t)15 * (valid[p] ? idx : 0);
-        nDir[p] = normalize3(ld3(t + 9));                          // glm::normalize(triangles[i.triangleIndex].normal) (:300)
+        const float *t;
+        valid[p] = light_record(q, rec[p], ok[p], &pos[p], &t, &nDir[p]);
         tcol[p] = ld3(t + 12);
         result[p] = result2[p] = V3(0.0f, 0.0f, 0.0f);
     }
@@ -489,14 +498,11 @@ __global__ __launch_bounds__(256) void k_query_direct_light_binned(const QueryBi
     unsigned long long n_rays = 0, n_cand = 0, n_tests = 0, n_fall = 0;
 #pragma unroll 1
     for (int p = 0; p < P; p++) {
-        const long long rec = ((long long)blockIdx.x * P + p) * 256 + threadIdx.x;
+        const long long rec = lane_ray<P>(p);
         const bool ok = rec < q.nhits;
-        const uint32_t *h = q.hits + (size_t)HIT_WORDS * (ok ? rec : 0);
-        const v3 pos = V3(__uint_as_float(h[0]), __uint_as_float(h[1]), __uint_as_float(h[2]));
-        const int idx = (int)h[4];
-        const bool valid = ok && idx >= 0 && idx < f.n;
-        const float *t = f.tris15 + (size_t)15 * (valid ? idx : 0);
-        const v3 nDir = normalize3(ld3(t + 9));                    // glm::normalize(triangles[i.triangleIndex].normal) (:300)
+        v3 pos, nDir;
+        const float *t;
+        const bool valid = light_record(q, rec, ok, &pos, &t, &nDir);
         v3 result = V3(0.0f, 0.0f, 0.0f), result2 = result;
         bool fell = false;
         for (int k = 0; k < f.nlights; k++) {
@@ -636,9 +642,9 @@ __global__ __launch_bounds__(256) void k_query_fan(const QueryFanFrame q)
 
 template __global__ void k_query_fan<QUERY_P>(const QueryFanFrame);
 
-// ---- k_query_fan_binned: the same, every ray through its bin of the cube around the origin ------------------------------------
+// ---- k_query_fan_binned, k_query_fans_binned: the same, every ray through its bin of the cube around its origin -----------------
 //
-// The cube of a point (capi.hpp: LightCache, built by light_cache_ensure for a one-position list) holds every direction from it:
+// The cube of a point (capi.hpp: LightCache, built by light_cache_ensure for a list of positions) holds every direction from it:
 // a triangle the reference accepts for negD is on the list of the bin of d' = negD * 2^k (rt_query.hpp: fan_dir_of; DESIGN.md
 // section 5.1).  A bin's list is ordered front to back in depth shells of the rows' `near` bound, and `near` bounds the distance
 // the reference computes whatever the direction's length -- pos = v0 + u e1 + v e2 lies on the triangle --, so of a list only the
@@ -652,101 +658,27 @@ template __global__ void k_query_fan<QUERY_P>(const QueryFanFrame);
 // row is skipped only when near > bound, strictly: a row with d == bound has near <= bound and is tested.  An incoming distance
 // that is negative or NaN is replaced by nothing (`>=` is false): the lane takes no list at all.
 //
-// One lane per ray, no LDS; the walk is k_query_direct_light_binned's: state in plain integer registers, every step straight-line
-// code (a lane with no row left loads row 0 and ignores it), verdicts as integers combined with `&`, only the exact stage in a
-// divergent branch.  Lanes the bins do not cover (fan_dir_of: not formed) sweep the origin's full table after the wave's walk,
-// with k_query_fan's loop body and per-ray override.
-template <bool STATS>
-__global__ __launch_bounds__(256) void k_query_fan_binned(const QueryFanFrame q)
-{
-    const CubeView &cv = q.cube;
-    const float4 *rows4 = reinterpret_cast<const float4 *>(cv.light_rows);
-    const long long ray = (long long)blockIdx.x * 256 + threadIdx.x;
-    const bool ok = ray < q.nrays;
-    const v3 S = ld3(q.origin);
-    const v3 dir = ld3(q.dirs + 3 * (size_t)(ok ? ray : 0));
-    const v3 nd = neg3(dir);                                       // negD = -dir (:229); dir is used as given
-    uint32_t *h = q.hits + (size_t)HIT_WORDS * (ok ? ray : 0);
-    float bound = __uint_as_float(h[3]);
-    const bool open = ok && bound >= 0.0f;                         // (false for NaN)
-    const FanDir fd = fan_dir_of(nd);
-    const bool binned = open && fd.formed, swept = open && !fd.formed;
-    const float d0 = cv.light_frames[0].shell_d0, iw = cv.light_frames[0].shell_iw;
-    uint32_t e = 0u, end = 0u, key = 0u;
-    if (binned) {
-        key = cube_bin_of(fd.d, 0u, cv.cube_bins) * (uint32_t)cv.shells;
-        e = cv.light_off[key];
-        end = cv.light_off[key + bin_shell_of(bound, d0, iw, cv.shells) + 1u];
-    }
-    unsigned long long n_cand = 0, n_tests = 0;
-    int best_i = -1, replaced = 0;
-    v3 pos = V3(0.0f, 0.0f, 0.0f);
-    float4 c0, c1, c2;
-    walk_row(rows4, e < end ? e : 0u, c0, c1, c2);
-    for (;;) {
-        const int act = (int)(e < end);
-        if (!__any(act)) break;
-        const TestDots td = test_dots(c0, c1, c2, nd);
-        const int near_ok = act & (int)!(c1.w > bound);            // strictly beyond the record: cannot pass `bound >= d`
-        if (STATS) { n_cand += (unsigned)act; n_tests += (unsigned)near_ok; }
-        if (near_ok & (int)maybe_hit(td)) {
-            const int tri = (int)cv.light_tri[e];
-            v3 hp;
-            float dist;
-            if (exact_hit(td, c0.w, q.tris15 + (size_t)15 * tri, S, &hp, &dist)) {
-                if ((bound > dist) | ((bound == dist) & (tri > best_i))) {
-                    bound = dist; best_i = tri; pos = hp; replaced = 1;
-                    end = min(end, cv.light_off[key + bin_shell_of(dist, d0, iw, cv.shells) + 1u]);
-                }
-            }
-        }
-        walk_step(rows4, e, end, act & (int)(e + 1u < end), c0, c1, c2);   // (the list's end, old or new: the lane is through)
-    }
-    if (__any(swept)) {
-        // (rare) the lanes the bins do not cover: the origin's full table in index order, the sequential rule itself
-        const bool exact_only = !dir_in_filter_range(dir);
-        if (STATS && swept) { n_cand += (unsigned)q.n; n_tests += (unsigned)q.n; }
-        for (int j = 0; j < q.n; j++) {
-            const float4 r0 = q.tab[j].r0, r1 = q.tab[j].r1, r2 = q.tab[j].r2;
-            const TestDots td = test_dots(r0, r1, r2, nd);
-            if (swept && (maybe_hit(td) || exact_only)) {
-                v3 hp;
-                float dist;
-                if (exact_hit(td, r0.w, q.tris15 + (size_t)15 * j, S, &hp, &dist)) closest_offer(bound, best_i, pos, replaced, dist, j, hp);
-            }
-        }
-    }
-    if (ok && replaced) store_record(h, pos, __float_as_uint(bound), (uint32_t)best_i);
-    if (STATS) flush_query_stats(q.stats, ok ? 1u : 0u, n_cand, n_tests, swept ? 1u : 0u);
-}
-
-template __global__ void k_query_fan_binned<false>(const QueryFanFrame);
-template __global__ void k_query_fan_binned<true>(const QueryFanFrame);
-
-// ---- k_query_fans_binned: fans from many origins, every ray through its bin of ITS origin's cube ---------------------------------
+// One lane per ray, no LDS; the walk (fan_walk) is k_query_direct_light_binned's: state in plain integer registers, every step
+// straight-line code (a lane with no row left loads row 0 and ignores it), verdicts as integers combined with `&`, only the exact
+// stage in a divergent branch.  Lanes the bins do not cover (fan_dir_of: not formed) sweep their origin's full table after the
+// wave's walk, with k_query_fan's loop body and per-ray override.
 //
-// One pass of mirt_intersect_fans* (rt_query.hpp: QueryFansFrame): the cube holds `count` of the call's origins as its positions,
-// as DirectLight's cube holds the lights, and the walk is k_query_fan_binned's with what that kernel takes per launch taken per
-// lane -- the position k, S, the shell descriptor light_frames[6 k], the bin cube_bin_of(d', k 6 B B, B), the sweep table tab + k n.
-// Each ray's argument is the single fan's, unchanged: position k of a many-position cube is built by the same kernels from the
-// same descriptors as the one position of a fan's cube (fill_light_frames), only its keys start at k 6 B B shells.  Lanes of a wave
-// may hold different origins: their lists differ per lane anyway.  A lane whose index lies outside [first, first + count) -- another
-// pass's ray, or an index outside the call's list -- takes no list, sweeps nothing and writes nothing; it reads position 0's
-// values so that every load stays inside the cube's tables.
+// Two entries call the one walk with the position k of the ray's origin in the cube, the origin S, the first bin of position k
+// and its sweep table; the shell descriptor is light_frames[6 k].  k_query_fan_binned has one position, so all of these are
+// launch-uniform: k and the bin base are literal 0 and S comes from the kernel's arguments.  k_query_fans_binned is one pass of
+// mirt_intersect_fans* (rt_query.hpp: QueryFansFrame): the cube holds `count` of the call's origins as its positions, as
+// DirectLight's cube holds the lights, and each lane takes k from origin_of, so lanes of a wave may hold different origins --
+// their lists differ per lane anyway.  Each ray's argument is the single fan's, unchanged: position k of a many-position cube is
+// built by the same kernels from the same descriptors as the one position of a fan's cube (fill_light_frames), only its keys
+// start at k 6 B B shells.  A lane whose index lies outside [first, first + count) -- another pass's ray, or an index outside the
+// call's list -- is not `mine`: it takes no list, sweeps nothing and writes nothing; it reads position 0's values so that every
+// load stays inside the cube's tables.
 template <bool STATS>
-__global__ __launch_bounds__(256) void k_query_fans_binned(const QueryFansFrame qf)
+__device__ __forceinline__ void fan_walk(const QueryFanFrame &q, long long ray, bool ok, bool mine, uint32_t k, v3 S, uint32_t bin_base,
+                                         const OriginRow *tab)
 {
-    const QueryFanFrame &q = qf.f;
     const CubeView &cv = q.cube;
     const float4 *rows4 = reinterpret_cast<const float4 *>(cv.light_rows);
-    const uint32_t face_bins = (uint32_t)(cv.cube_bins * cv.cube_bins) * 6u;
-    const long long ray = (long long)blockIdx.x * 256 + threadIdx.x;
-    const bool ok = ray < q.nrays;
-    const uint32_t idx = qf.origin_of ? (uint32_t)qf.origin_of[ok ? ray : 0] : 0u;
-    const uint32_t rel = idx - (uint32_t)qf.first;                 // (modulo 2^32: a negative or huge index lands beyond count)
-    const bool mine = ok && rel < (uint32_t)qf.count;
-    const uint32_t k = mine ? rel : 0u;
-    const v3 S = ld3(qf.origins + 3 * (size_t)(1u + k));
     const v3 dir = ld3(q.dirs + 3 * (size_t)(ok ? ray : 0));
     const v3 nd = neg3(dir);                                       // negD = -dir (:229); dir is used as given
     uint32_t *h = q.hits + (size_t)HIT_WORDS * (ok ? ray : 0);
@@ -758,7 +690,7 @@ __global__ __launch_bounds__(256) void k_query_fans_binned(const QueryFansFrame 
     const float d0 = lf->shell_d0, iw = lf->shell_iw;
     uint32_t e = 0u, end = 0u, key = 0u;
     if (binned) {
-        key = cube_bin_of(fd.d, k * face_bins, cv.cube_bins) * (uint32_t)cv.shells;
+        key = cube_bin_of(fd.d, bin_base, cv.cube_bins) * (uint32_t)cv.shells;
         e = cv.light_off[key];
         end = cv.light_off[key + bin_shell_of(bound, d0, iw, cv.shells) + 1u];
     }
@@ -788,7 +720,6 @@ __global__ __launch_bounds__(256) void k_query_fans_binned(const QueryFansFrame 
     }
     if (__any(swept)) {
         // (rare) the lanes the bins do not cover: their origin's full table in index order, the sequential rule itself
-        const OriginRow *tab = q.tab + (size_t)k * q.n;
         const bool exact_only = !dir_in_filter_range(dir);
         if (STATS && swept) { n_cand += (unsigned)q.n; n_tests += (unsigned)q.n; }
         for (int j = 0; j < q.n; j++) {
@@ -803,6 +734,31 @@ __global__ __launch_bounds__(256) void k_query_fans_binned(const QueryFansFrame 
     }
     if (mine && replaced) store_record(h, pos, __float_as_uint(bound), (uint32_t)best_i);
     if (STATS) flush_query_stats(q.stats, mine ? 1u : 0u, n_cand, n_tests, swept ? 1u : 0u);
+}
+
+template <bool STATS>
+__global__ __launch_bounds__(256) void k_query_fan_binned(const QueryFanFrame q)
+{
+    const long long ray = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool ok = ray < q.nrays;
+    fan_walk<STATS>(q, ray, ok, ok, 0u, ld3(q.origin), 0u, q.tab);
+}
+
+template __global__ void k_query_fan_binned<false>(const QueryFanFrame);
+template __global__ void k_query_fan_binned<true>(const QueryFanFrame);
+
+template <bool STATS>
+__global__ __launch_bounds__(256) void k_query_fans_binned(const QueryFansFrame qf)
+{
+    const QueryFanFrame &q = qf.f;
+    const uint32_t face_bins = (uint32_t)(q.cube.cube_bins * q.cube.cube_bins) * 6u;
+    const long long ray = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool ok = ray < q.nrays;
+    const uint32_t idx = qf.origin_of ? (uint32_t)qf.origin_of[ok ? ray : 0] : 0u;
+    const uint32_t rel = idx - (uint32_t)qf.first;                 // (modulo 2^32: a negative or huge index lands beyond count)
+    const bool mine = ok && rel < (uint32_t)qf.count;
+    const uint32_t k = mine ? rel : 0u;
+    fan_walk<STATS>(q, ray, ok, mine, k, ld3(qf.origins + 3 * (size_t)(1u + k)), k * face_bins, q.tab + (size_t)k * q.n);
 }
 
 template __global__ void k_query_fans_binned<false>(const QueryFansFrame);

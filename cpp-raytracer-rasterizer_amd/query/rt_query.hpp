@@ -120,7 +120,7 @@ MIRT_HD FanDir fan_dir_of(v3 nd)
 }
 
 // One origin, nrays directions, the in/out records.  tab: the origin's table, one row per triangle (the cube's own, written by
-// k_select_faces, or the query's, written by k_prep_origin); the cube is read by k_query_fan_binned only.
+// k_select_faces, or the query's, written by k_prep_origin); the cube is read by the binned walk (rt_query.hip: fan_walk) only.
 struct QueryFanFrame {
     const float *tris15;
     int n;
@@ -138,9 +138,9 @@ struct QueryFanFrame {
 //
 // One pass of the call: the cube `f.cube` holds the origins [first, first + count) of the call's list as its positions 0 .. count - 1
 // (capi.hpp: LightCache for a many-position list, as DirectLight's), and ray i belongs to the pass when origin_of[i] lies in that
-// range.  Everything k_query_fan_binned takes per launch of the ONE origin is taken per lane here: the position k = origin_of[i] -
-// first, S = origins[3 (1 + k) ..] (the cube's own list: slot 0 is the camera's place), the shell descriptor cube.light_frames[6 k],
-// the bin base k * 6 B B and the sweep table f.tab + k * n.  f.origin and f.unsafe are not read.
+// range.  k_query_fans_binned hands the walk of k_query_fan_binned (rt_query.hip: fan_walk) per lane what that kernel has per launch:
+// the position k = origin_of[i] - first, S = origins[3 (1 + k) ..] (the cube's own list: slot 0 is the camera's place), the bin base
+// k * 6 B B and the sweep table f.tab + k * n; the shell descriptor is cube.light_frames[6 k].  f.origin and f.unsafe are not read.
 struct QueryFansFrame {
     QueryFanFrame f;
     const float *origins;               // (1 + count) x 3: the cube's origin list

@@ -9,7 +9,9 @@
 //      shell_iw == 0 for a degenerate range;
 //   5. the view makers' empty-cube rule: without rows the row pointer is the origin table's, with rows the row table's (fake
 //      addresses, nothing is dereferenced);
-//   6. the FNV helper: the published FNV-1a value of "a", and mixing in pieces equals mixing at once.
+//   6. the FNV helper: the published FNV-1a value of "a", and mixing in pieces equals mixing at once;
+//   7. whether a ray query bins (query_bins), over every mode and every combination of its three conditions: what each mode
+//      promises, stated per mode.
 #include "../../cpp-raytracer-rasterizer_amd/capi/pass_plan.hpp"
 
 #include <cstdio>
@@ -157,9 +159,24 @@ static int fnv_cases()
     return 0;
 }
 
+static int query_bins_cases()
+{
+    for (int mode : { (int)MIRT_QUERY_AUTO, (int)MIRT_QUERY_BRUTE, (int)MIRT_QUERY_BINNED })
+        for (int m = 0; m < 8; m++) {
+            const bool may_bin = m & 1, held = m & 2, auto_says = m & 4;
+            const bool got = query_bins(may_bin, mode, held, auto_says);
+            // nothing bins what the frame path would not, BRUTE never bins, BINNED bins whatever it may, and AUTO bins what it may
+            // when the cube is held or its rule says so, and nothing else: between them the three decide all 24 cases
+            if (!may_bin || mode == MIRT_QUERY_BRUTE) CHECK(!got);
+            if (may_bin && mode == MIRT_QUERY_BINNED) CHECK(got);
+            if (mode == MIRT_QUERY_AUTO) CHECK(got == (may_bin && (held || auto_says)));
+        }
+    return 0;
+}
+
 int main()
 {
-    if (kept_pass_cases() || capacity_cases() || shell_cases() || frame_cases() || view_cases() || fnv_cases()) return 1;
+    if (kept_pass_cases() || capacity_cases() || shell_cases() || frame_cases() || view_cases() || fnv_cases() || query_bins_cases()) return 1;
     printf("ok\n");
     return 0;
 }

@@ -51,3 +51,19 @@ class DeviceArray:
 
     def __exit__(self, *exc):
         self.free()
+
+
+def to_device(arr):
+    """The bytes of a host array in a device buffer of their own."""
+    a = np.ascontiguousarray(arr)
+    d = DeviceArray((a.nbytes,), np.uint8)
+    assert hip().hipMemcpy(d.ptr, a.ctypes.data_as(C.c_void_p), a.nbytes, 1) == 0
+    assert hip().hipDeviceSynchronize() == 0
+    return d
+
+
+def hip_fill(dev, byte):
+    """Every byte of a device buffer set to `byte`, once the library's streams are idle."""
+    import mirt
+    mirt.sync()
+    return hip().hipMemset(dev.ptr, byte, dev.nbytes) == 0 and hip().hipDeviceSynchronize() == 0

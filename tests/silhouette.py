@@ -55,6 +55,39 @@ def outside_the_fan_window(dirs):
     return ~(np.isfinite(d).all(axis=1) & (m >= np.float32(2.0 ** -32)) & (m < np.float32(2.0 ** 19)))
 
 
+_scenes = {}
+
+
+def scene_of(oracle, name):
+    """The probed scenes by name: (triangles, indices of the target triangles or None for all, crossings per edge, scale)."""
+    if name not in _scenes:
+        if name == "shell":
+            v = scene_shell(), None, 4, 1.0
+        elif name == "shell_dense":
+            v = scene_shell_dense(), range(150), 4, 1.0
+        elif name == "needles":
+            v = scene_needles(), None, 4, 1.0
+        elif name == "walls":
+            v = scene_walls(), None, 24, 1.0
+        elif name == "grazing":
+            v = scene_grazing(), None, 4, 1.0
+        elif name == "tips":
+            v = scene_tips(), None, 2, 1.0
+        elif name == "soup150":
+            v = oracle.soup(41, 2000, 0.2)[:150].copy(), None, 4, 1.0
+        elif name == "soup2000":
+            v = oracle.soup(41, 2000, 0.2), range(150), 4, 1.0
+        elif name == "shell x 3e-4":
+            v = scene_shell(3e-4), None, 4, 3e-4
+        elif name == "shell x 3e5":
+            v = scene_shell(3e5), None, 4, 3e5
+        else:
+            raise KeyError(name)
+        v[0].setflags(write=False)
+        _scenes[name] = v
+    return _scenes[name]
+
+
 # ---- probes ------------------------------------------------------------------------------------------------------------------------
 
 _LINES = (np.repeat(np.arange(3), 4), np.tile([1.0, 1.0, -1.0, -1.0], 3), (np.repeat(np.arange(3), 4) + np.tile([1, 2, 1, 2], 3)) % 3)

@@ -11,14 +11,15 @@ import numpy as np
 import pytest
 
 import mirt
+from devbuf import hip_fill, to_device
+from query_helpers import INSIDE, LIGHTS, OUTSIDE, oracle_intersect, primary_rays, same_hits, seam_directions
+from query_helpers import fan_scene_of as scene_of
 
 pytestmark = pytest.mark.gpu
 
 FLT_MAX = np.finfo(np.float32).max
-LIGHTS = np.array([[0, -0.5, -0.75, 1, 1, 1, 14], [0.5, 0.25, -0.875, 1, 0.5, 0.25, 6]], np.float32)
 NDIRS = 4096
 ORACLE_RAYS = 1024
-_scene_cache = {}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -31,104 +32,11 @@ def device():
     mirt.shutdown()
 
 
-# ---- helpers (as in test_gpu_ray_query.py) -----------------------------------------------------------------------------
-
-def oracle_intersect(oracle, tris, rays, hits=None):
-    """One oracle ClosestIntersection call per ray on its in/out record."""
-    out = mirt.fresh_hits(len(rays)) if hits is None else hits.copy()
-    tris = np.ascontiguousarray(tris, np.float32).reshape(-1, 15)
-    for i in range(len(rays)):
-        _, p, d, ix = oracle.closest_intersection(tris, rays["start"][i], rays["dir"][i], pos=out["position"][i],
-                                                  distance=float(out["distance"][i]), index=int(out["index"][i]))
-        # a NaN distance that came back unchanged keeps the caller's bits (float -> C float -> float may quieten a payload)
-        if not (np.isnan(d) and np.isnan(out["distance"][i])):
-            out["distance"][i] = d
-        out["position"][i], out["index"][i] = p, ix
-    return out
-
-
-def same_hits(got, want, what=""):
-    assert np.array_equal(got["index"], want["index"]), "%s: index differs for %d rays" % (what, int((got["index"] != want["index"]).sum()))
-    assert np.array_equal(got["distance"].view(np.uint32), want["distance"].view(np.uint32)), "%s: distance not bit-identical" % what
-    assert np.array_equal(got["position"].view(np.uint32), want["position"].view(np.uint32)), "%s: position not bit-identical" % what
-    assert got.tobytes() == want.tobytes(), what
-
-
-def primary_rays(oracle, cam, rot, focal, W, H):
-    """The primary rays of Draw() (raytracer.cpp:579-580): d = (x - W/2, y - H/2, focalLength), dir = cameraRot * d."""
-    rays = np.zeros(W * H, mirt.RAY_DTYPE)
-    rays["start"] = np.asarray(cam, np.float32)
-    rot = np.ascontiguousarray(rot, np.float32)
-    out = np.zeros(3, np.float32)
-    for y in range(H):
-        for x in range(W):
-            d = np.array([np.float32(x) - np.float32(W) / np.float32(2), np.float32(y) - np.float32(H) / np.float32(2), np.float32(focal)], np.float32)
-            oracle.lib.mirt_oracle_mat3_mul_vec(rot, d, out)
-            rays["dir"][y * W + x] = out
-    return rays
-
-
-def to_device(arr):
-    from devbuf import DeviceArray, hip
-    a = np.ascontiguousarray(arr)
-    d = DeviceArray((a.nbytes,), np.uint8)
-    assert hip().hipMemcpy(d.ptr, a.ctypes.data_as(C.c_void_p), a.nbytes, 1) == 0
-    assert hip().hipDeviceSynchronize() == 0
-    return d
-
-
-def hip_fill(dev, byte):
-    from devbuf import hip
-    mirt.sync()
-    return hip().hipMemset(dev.ptr, byte, dev.nbytes) == 0 and hip().hipDeviceSynchronize() == 0
-
-
 # ---- scenes, origins, directions -----------------------------------------------------------------------------------------
-
-def scene_of(name):
-    """(triangles, b): the scenes of test_gpu_ray_query.py and cornell + soup2000; directions aim at U[-b, b]^3."""
-    if name not in _scene_cache:
-        if name == "cornell":
-            v = mirt.scene_cornell(), 3.0
-        elif name == "soup2000":
-            v = mirt.scene_soup(41, 2000, 0.2), 1.0
-        elif name == "soup65":
-            v = mirt.scene_soup(5, 65, 0.5), 1.0
-        elif name == "one":
-            v = mirt.scene_soup(9, 1, 0.8), 0.3
-        elif name == "cornell+soup2000":
-            v = np.concatenate([mirt.scene_cornell(), mirt.scene_soup(41, 2000, 0.2)]), 1.0
-        elif name == "cornell x 2":
-            v = np.concatenate([mirt.scene_cornell(), mirt.scene_cornell()]), 3.0
-        else:
-            raise KeyError(name)
-        v[0].setflags(write=False)
-        _scene_cache[name] = v
-    return _scene_cache[name]
-
-
-INSIDE = np.array([0.125, -0.0625, 0.1875], np.float32)
-OUTSIDE = np.array([2.5, 0.75, -1.5], np.float32)
-
 
 def origins_of(tris):
     """Inside the scene, outside its box, and exactly on a vertex of triangle 0."""
     return {"inside": INSIDE, "outside": OUTSIDE, "vertex": np.array(tris[0, 0:3], np.float32)}
-
-
-def seam_directions():
-    """The 26 axis, face-diagonal and corner directions, and each with one component moved one ulp up or down (a zero component
-    to the smallest subnormal of either sign): on, and to either side of, every face seam and face centre of cube_bin_of."""
-    base = [np.array([x, y, z], np.float32) for x in (-1, 0, 1) for y in (-1, 0, 1) for z in (-1, 0, 1) if x or y or z]
-    out = []
-    for d in base:
-        out.append(d)
-        for c in range(3):
-            for to in (np.float32("inf"), np.float32("-inf")):
-                e = d.copy()
-                e[c] = np.nextafter(d[c], to)
-                out.append(e)
-    return np.array(out, np.float32)
 
 
 def directions_from(origin, b, n=NDIRS, seed=7):

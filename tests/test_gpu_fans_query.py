@@ -3,7 +3,7 @@ in a cube of up to 32 origins (k_query_fans_binned), in passes when the call has
 mirt_intersect's kernels (k_query_fans_expand) -- against mirt_intersect on the expanded rays {origins[origin_of[i]], dirs[i]} and
 against the CPU oracle's ClosestIntersection.
 
-Every comparison is bit-exact over all 20 bytes of every record (same_hits of test_gpu_fan_query.py).  The reference of a batch is
+Every comparison is bit-exact over all 20 bytes of every record (same_hits of query_helpers.py).  The reference of a batch is
 computed once and shared by the modes and forms that are compared with it."""
 import ctypes as C
 
@@ -11,7 +11,9 @@ import numpy as np
 import pytest
 
 import mirt
-from test_gpu_fan_query import INSIDE, LIGHTS, OUTSIDE, hip_fill, oracle_intersect, same_hits, scene_of, seam_directions, to_device
+from devbuf import hip_fill, to_device
+from query_helpers import INSIDE, LIGHTS, OUTSIDE, oracle_intersect, same_hits, seam_directions
+from query_helpers import fan_scene_of as scene_of
 
 pytestmark = pytest.mark.gpu
 
@@ -293,6 +295,49 @@ def test_single_origin_without_indices():
     d_dirs.free(), d_hits.free()
 
 
+def test_single_fan_and_one_origin_fans_are_one_walk():
+    """k_query_fan_binned and k_query_fans_binned are two entries to one walk: for one origin mirt.intersect_from and
+    mirt.intersect_fans without indices return the same bytes and, with profiling on, count the same rays, rows stepped over and
+    swept rays on the same grid -- with ordinary directions, and with 64 of them replaced by directions the bins do not cover
+    (zero, a NaN component, scaled by 2^20), whose rays sweep the origin's table.
+
+    `tests`, the rows tested, is NOT compared.  The two calls walk two cubes (g.qrows.fan and g.qrows.fans), each built by its
+    call, and a build does not fix the order of the rows inside a depth shell; a row is tested when its `near` is not beyond the
+    record's distance at that moment, which depends on which rows of the shell came before it.  Measured on this scene from
+    this origin, 6000 directions towards U[-1, 1]^3, four builds of either cube by one library: 8480 / 8485 / 8477 / 8483 for the single fan, 8486 / 8480 / 8476
+    / 8477 for the many-origin call.  `candidates` does not depend on that order: a row of shell s has near in s and its hit is
+    no nearer than near, so a replacement never moves the list's end in front of the shell being walked, and every lane steps
+    over whole shells up to the one its final distance falls into (9123 in all of those builds)."""
+    import silhouette as sil
+    tris, origins, of, dirs, want = batch_of("soup2000", 1)
+    swept = dirs.copy()
+    ordinary = np.flatnonzero((np.abs(dirs).max(axis=1) >= 0.5) & (np.abs(dirs).max(axis=1) < 1e3))
+    odd = np.random.default_rng(13).permutation(ordinary)[:64]
+    swept[odd[0::3]] = 0
+    swept[odd[1::3], 1] = np.float32("nan")
+    swept[odd[2::3]] = dirs[odd[2::3]] * np.float32(2.0 ** 20)
+    assert not sil.outside_the_fan_window(dirs).any() and int(sil.outside_the_fan_window(swept).sum()) == 64
+    mirt.set_profiling(True)
+    mirt.set_query_mode(mirt.QUERY_BINNED)
+    try:
+        for what, d, nswept in (("ordinary directions", dirs, 0), ("64 swept directions", swept, 64)):
+            one = mirt.intersect_from(origins[0], d)
+            st1 = mirt.fan_stats()
+            many = mirt.intersect_fans(origins, None, d)
+            stn = mirt.fan_stats()
+            assert one.tobytes() == many.tobytes(), what
+            assert st1["mode_used"] == stn["mode_used"] == mirt.QUERY_BINNED, (what, st1, stn)
+            for key in ("shadow_rays", "candidates", "fallback_records", "cube_bins", "shells"):
+                assert st1[key] == stn[key], (what, key, st1, stn)
+            assert st1["shadow_rays"] == len(d) and st1["fallback_records"] == nswept and 0 < st1["tests"] <= st1["candidates"], (what, st1)
+            assert 0 < stn["tests"] <= stn["candidates"], (what, stn)
+            if nswept == 0:
+                same_hits(one, want, what)
+    finally:
+        mirt.set_query_mode(mirt.QUERY_AUTO)
+        mirt.set_profiling(False)
+
+
 # ---- 7. caches -------------------------------------------------------------------------------------------------------------------------
 
 def test_caches(oracle):
@@ -420,8 +465,7 @@ def test_frames_in_flight(in_flight):
 @pytest.mark.parametrize("name", ["shell", "walls", "soup150"])
 def test_silhouette_probes_from_three_origins(oracle, name):
     import silhouette as sil
-    import test_silhouette_probes_host as host
-    tris, targets, crossings, scale = host.scene_of(oracle, name)
+    tris, targets, crossings, scale = sil.scene_of(oracle, name)
     mirt.scene_upload(tris)
     named = sil.origins_of(tris, scale)
     origins = np.ascontiguousarray(np.array(list(named.values()), np.float32))

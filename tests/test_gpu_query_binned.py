@@ -2,7 +2,7 @@
 brute-force kernel and the CPU oracle's DirectLight, bit for bit and for every record; that the bins are really walked; the
 queries' cube cache and the frame path's cube; streams; and what MIRT_QUERY_AUTO chooses.
 
-Scenes, ray batches and comparison helpers are those of test_gpu_ray_query.py.  The records are closest hits of mirt.intersect
+Scenes, ray batches and comparison helpers are those of test_gpu_ray_query.py (query_helpers.py).  The records are closest hits of mirt.intersect
 plus records of the caller's own kind: misses, an index one past the scene, positions the cube's ray family does not cover (3e19,
 NaN, inf, the light itself), positions behind an occluder, and positions at L + t d for d along the axes, the face diagonals and
 the cube diagonals -- the face ties and bin borders of cube_bin_of.  Lights sit on dyadic coordinates so that those ties are exact."""
@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 import mirt
-import test_gpu_ray_query as rq
+import query_helpers as rq
+from devbuf import hip_fill, to_device
 
 pytestmark = pytest.mark.gpu
 
@@ -37,7 +38,7 @@ def device():
 def scene(name):
     if name == "cornell x 2":
         return np.concatenate([mirt.scene_cornell(), mirt.scene_cornell()]), 0.9, 3.0
-    return rq.scene_of(None, name)
+    return rq.scene_of(name)
 
 
 def directions():
@@ -159,7 +160,7 @@ def case(oracle, name):
         rq.same_hits(hits[:256], rq.oracle_intersect(oracle, tris, rays[:256]), name)
         recs, nodd = build_records(tris, hits, LIGHTS)
         assert 1024 <= len(recs) <= 4096
-        jit = rq._jitter(oracle, LIGHTS[:2], 4)
+        jit = rq.jitter(oracle, LIGHTS[:2], 4)
         want = {nl: rq.oracle_direct_light(oracle, tris, recs, LIGHTS[:nl]) for nl in (1, 2, 3)}
         want["soft"] = rq.oracle_direct_light(oracle, tris, recs, LIGHTS[:2], samples=4, jitter=jit)
         for v in want.values():
@@ -268,7 +269,7 @@ def test_cube_cache(oracle):
     try:
         frames = []
         for i in range(7):
-            assert rq.hip_fill(x, 0x11)
+            assert hip_fill(x, 0x11)
             mirt.raytrace_device(view, LIGHTS[:2], (0.2, 0.2, 0.2), mirt.RT_BINNED, 0, H, 0, x.ptr, W * 4)
             mirt.sync()
             frames.append(x.read())
@@ -280,7 +281,7 @@ def test_cube_cache(oracle):
         out, st = light_query(recs, LIGHTS[:2], mirt.QUERY_AUTO)
         assert st["cube_source"] == 3
         assert mirt.stats() == frame_stats
-        assert rq.hip_fill(x, 0x11)
+        assert hip_fill(x, 0x11)
         mirt.raytrace_device(view, LIGHTS[:2], (0.2, 0.2, 0.2), mirt.RT_BINNED, 0, H, 0, x.ptr, W * 4)
         mirt.sync()
         assert np.array_equal(x.read(), frames[-1]), "the frame after the query changed"
@@ -303,7 +304,7 @@ def test_device_queries_between_frames_in_flight(oracle, in_flight):
     for nl, w in sync_want.items():
         rq.same_bits(w, want[nl], "synchronous, %d lights" % nl)
     want_frame = mirt.raytrace(view, LIGHTS[:1], mode=mirt.RT_BRUTE)["xrgb"]
-    d_hits = rq._to_device(recs)
+    d_hits = to_device(recs)
     outs, planes = [], []
     mirt.set_query_mode(mirt.QUERY_BINNED)
     try:
@@ -320,7 +321,7 @@ def test_device_queries_between_frames_in_flight(oracle, in_flight):
         # a standing view: every stream holds its pass by now; queries between its frames leave the passes alone
         x = planes[0]
         for i in range(2 * in_flight):
-            assert rq.hip_fill(x, 0x11)
+            assert hip_fill(x, 0x11)
             mirt.raytrace_device(view, LIGHTS[:1], (0.2, 0.2, 0.2), mirt.RT_BINNED, 0, H, 0, x.ptr, W * 4)
             st = mirt.stats()
             assert st["mode_used"] == mirt.RT_BINNED and st["bins_reused"] == 1, (i, st)
@@ -402,7 +403,7 @@ def test_frames_and_queries_take_the_light_scratch_in_turn(oracle, in_flight):
     c = _evict_case(oracle)
     W, H, view, L0, L1, recs = c["W"], c["H"], c["view"], c["L0"], c["L1"], c["recs"]
     mirt.scene_upload(c["tris"])                              # (a new scene version: no pass, no cube is held)
-    d_hits = rq._to_device(recs)
+    d_hits = to_device(recs)
     planes, outs = [], []
 
     def frame():

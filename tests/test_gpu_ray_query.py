@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 
 import mirt
+from devbuf import hip_fill, to_device
+from query_helpers import jitter, make_batch, oracle_direct_light, oracle_intersect, primary_rays, same_bits, same_hits, scene_of
 
 pytestmark = pytest.mark.gpu
 
@@ -25,59 +27,6 @@ def device():
     mirt.init(0)
     yield
     mirt.shutdown()
-
-
-def make_batch(n, a, b, seed=7):
-    """start ~ U[-a, a]^3, dir = target - start, target ~ U[-b, b]^3."""
-    rng = np.random.default_rng(seed)
-    start = rng.uniform(-a, a, (n, 3)).astype(np.float32)
-    target = rng.uniform(-b, b, (n, 3)).astype(np.float32)
-    return mirt.make_rays(start, (target - start).astype(np.float32))
-
-
-def oracle_intersect(oracle, tris, rays, hits=None):
-    """One oracle ClosestIntersection call per ray on its in/out record."""
-    out = mirt.fresh_hits(len(rays)) if hits is None else hits.copy()
-    tris = np.ascontiguousarray(tris, np.float32).reshape(-1, 15)
-    for i in range(len(rays)):
-        _, p, d, ix = oracle.closest_intersection(tris, rays["start"][i], rays["dir"][i], pos=out["position"][i],
-                                                  distance=float(out["distance"][i]), index=int(out["index"][i]))
-        # a NaN distance that came back unchanged keeps the caller's bits (float -> C float -> float may quieten a payload)
-        if not (np.isnan(d) and np.isnan(out["distance"][i])):
-            out["distance"][i] = d
-        out["position"][i], out["index"][i] = p, ix
-    return out
-
-
-def oracle_direct_light(oracle, tris, hits, lights, samples=1, jitter=None):
-    out = np.zeros((len(hits), 3), np.float32)
-    for i, h in enumerate(hits):
-        if 0 <= h["index"] < len(tris):                      # outside: the reference indexes out of bounds; the library yields 0
-            out[i] = oracle.direct_light(tris, h["position"], float(h["distance"]), int(h["index"]), lights, samples=samples, jitter=jitter)
-    return out
-
-
-def same_hits(got, want, what=""):
-    assert np.array_equal(got["index"], want["index"]), "%s: index differs for %d rays" % (what, int((got["index"] != want["index"]).sum()))
-    assert np.array_equal(got["distance"].view(np.uint32), want["distance"].view(np.uint32)), "%s: distance not bit-identical" % what
-    assert np.array_equal(got["position"].view(np.uint32), want["position"].view(np.uint32)), "%s: position not bit-identical" % what
-    assert got.tobytes() == want.tobytes(), what
-
-
-def same_bits(got, want, what=""):
-    assert np.array_equal(np.ascontiguousarray(got).view(np.uint32), np.ascontiguousarray(want).view(np.uint32)), "%s: not bit-identical" % what
-
-
-def scene_of(oracle, name):
-    if name == "cornell":
-        return mirt.scene_cornell(), 0.9, 3.0
-    if name == "soup2000":
-        return mirt.scene_soup(41, 2000, 0.2), 1.5, 1.0
-    if name == "soup65":
-        return mirt.scene_soup(5, 65, 0.5), 1.5, 1.0
-    if name == "one":
-        return mirt.scene_soup(9, 1, 0.8), 1.5, 0.3
-    raise KeyError(name)
 
 
 def test_smoke_cornell_1024_rays(oracle):
@@ -94,7 +43,7 @@ def test_smoke_cornell_1024_rays(oracle):
 
 @pytest.mark.parametrize("name", ["cornell", "soup2000", "soup65", "one"])
 def test_closest_hit_matches_oracle(oracle, name):
-    tris, a, b = scene_of(oracle, name)
+    tris, a, b = scene_of(name)
     rays = make_batch(4096, a, b)
     mirt.scene_upload(tris)
     got = mirt.intersect(rays)
@@ -174,7 +123,7 @@ def test_carried_records(oracle):
 
 @pytest.mark.parametrize("name", ["soup2000", "cornell"])
 def test_rays_outside_the_filter_range(oracle, name):
-    tris, a, b = scene_of(oracle, name)
+    tris, a, b = scene_of(name)
     rays = make_batch(4096, a, b)
     rng = np.random.default_rng(11)
     odd = rng.permutation(len(rays))[:1200]                   # scattered, so that waves hold both kinds
@@ -264,20 +213,6 @@ def test_cases_under_either_kernel(knob):
 
 # ---- case 6: agreement with the frame path ----------------------------------------------------------------------------
 
-def primary_rays(oracle, cam, rot, focal, W, H):
-    """The primary rays of Draw() (raytracer.cpp:579-580): d = (x - W/2, y - H/2, focalLength), dir = cameraRot * d."""
-    rays = np.zeros(W * H, mirt.RAY_DTYPE)
-    rays["start"] = np.asarray(cam, np.float32)
-    rot = np.ascontiguousarray(rot, np.float32)
-    out = np.zeros(3, np.float32)
-    for y in range(H):
-        for x in range(W):
-            d = np.array([np.float32(x) - np.float32(W) / np.float32(2), np.float32(y) - np.float32(H) / np.float32(2), np.float32(focal)], np.float32)
-            oracle.lib.mirt_oracle_mat3_mul_vec(rot, d, out)
-            rays["dir"][y * W + x] = out
-    return rays
-
-
 @pytest.mark.parametrize("name", ["soup2000+cornell", "cornell"])
 def test_queries_equal_the_frame_path(oracle, name):
     W, H, cam, focal = 96, 80, (0.1, -0.05, -2.0), 60.0
@@ -300,17 +235,12 @@ def test_queries_equal_the_frame_path(oracle, name):
 
 # ---- case 7: DirectLight against the oracle ------------------------------------------------------------------------------
 
-def _jitter(oracle, lights, samples, seed=1):
-    C.CDLL(None).srand(seed)
-    return np.concatenate([oracle.jitter(l[0:3], samples) for l in np.asarray(lights, np.float32).reshape(-1, 7)])
-
-
 @pytest.mark.parametrize("name", ["cornell", "soup2000", "cornell x 2"])
 def test_direct_light_matches_oracle(oracle, name):
     if name == "cornell x 2":
         tris, a, b = np.concatenate([mirt.scene_cornell(), mirt.scene_cornell()]), 0.9, 3.0
     else:
-        tris, a, b = scene_of(oracle, name)
+        tris, a, b = scene_of(name)
     n = len(tris)
     rays = make_batch(1024, a, b)
     mirt.scene_upload(tris)
@@ -326,7 +256,7 @@ def test_direct_light_matches_oracle(oracle, name):
         assert got.any()
     same_bits(mirt.direct_light(hits, np.zeros((0, 7), np.float32)), np.zeros((len(hits), 3), np.float32), "no lights")
     # soft shadows, 4 samples per light
-    jit = _jitter(oracle, LIGHTS3[:2], 4)
+    jit = jitter(oracle, LIGHTS3[:2], 4)
     mirt.set_soft_shadows(4, jit)
     try:
         got = mirt.direct_light(hits, LIGHTS3[:2])
@@ -387,15 +317,6 @@ def test_queries_leave_the_statistics_alone(oracle):
 
 # ---- case 8: streams and caches ------------------------------------------------------------------------------------------
 
-def _to_device(arr):
-    from devbuf import DeviceArray, hip
-    a = np.ascontiguousarray(arr)
-    d = DeviceArray((a.nbytes,), np.uint8)
-    assert hip().hipMemcpy(d.ptr, a.ctypes.data_as(C.c_void_p), a.nbytes, 1) == 0
-    assert hip().hipDeviceSynchronize() == 0
-    return d
-
-
 @pytest.mark.parametrize("in_flight", [1, 2, 3, 4])
 def test_device_queries_between_frames_in_flight(oracle, in_flight):
     from devbuf import DeviceArray
@@ -410,7 +331,7 @@ def test_device_queries_between_frames_in_flight(oracle, in_flight):
     try:
         mirt.set_frames_in_flight(in_flight)
         for b in batches:
-            d_rays, d_hits = _to_device(b), _to_device(mirt.fresh_hits(len(b)))
+            d_rays, d_hits = to_device(b), to_device(mirt.fresh_hits(len(b)))
             d_rgb = DeviceArray((len(b), 3), np.float32, 0x11)
             x = DeviceArray((H, W), np.uint32, 0)
             bufs.append((d_rays, d_hits, d_rgb, x))
@@ -479,8 +400,3 @@ def test_light_queries_between_binned_frames_of_a_standing_view(in_flight):
         mirt.set_frames_in_flight(1)
         x.free()
 
-
-def hip_fill(dev, byte):
-    from devbuf import hip
-    mirt.sync()
-    return hip().hipMemset(dev.ptr, byte, dev.nbytes) == 0 and hip().hipDeviceSynchronize() == 0

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import mirt
-from devbuf import DeviceArray, hip
+from devbuf import DeviceArray, to_device
 from mirt_oracle import DEFAULT_LIGHT
 
 pytestmark = pytest.mark.gpu
@@ -77,14 +77,6 @@ RAYS, DIRS = query_inputs()
 
 def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
-
-
-def to_device(arr):
-    a = np.ascontiguousarray(arr)
-    d = DeviceArray((a.nbytes,), np.uint8)
-    assert hip().hipMemcpy(d.ptr, a.ctypes.data_as(C.c_void_p), a.nbytes, 1) == 0
-    assert hip().hipDeviceSynchronize() == 0
-    return d
 
 
 def upload_device(tris, culled=None):

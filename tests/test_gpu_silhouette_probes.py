@@ -75,9 +75,8 @@ def fan(mirt, origin, dirs, mode, hits=None):
 def check_fans(mirt, oracle, name, with_oracle=True):
     """Every origin of one scene; returns per origin the shares of probes whose closest hit, by brute force, is their target."""
     import silhouette as sil
-    import test_silhouette_probes_host as host
-    from test_gpu_fan_query import oracle_intersect
-    tris, targets, crossings, scale = host.scene_of(oracle, name)
+    from query_helpers import oracle_intersect
+    tris, targets, crossings, scale = sil.scene_of(oracle, name)
     bins = expected_bins(len(tris))
     mirt.scene_upload(tris)
     out = {}
@@ -199,8 +198,7 @@ def light_query(mirt, recs, lights, mode):
 def check_shadows(mirt, oracle, name, with_oracle=True, origins=("inside", "outside", "vertex")):
     """The probe origins as lights, one at a time; returns the share of lit records (brute force) per light."""
     import silhouette as sil
-    import test_silhouette_probes_host as host
-    tris, targets, crossings, scale = host.scene_of(oracle, name)
+    tris, targets, crossings, scale = sil.scene_of(oracle, name)
     scene, first = sil.with_receivers(tris, scale)
     bins = expected_bins(len(scene))
     mirt.scene_upload(scene)
@@ -226,7 +224,7 @@ def check_shadows(mirt, oracle, name, with_oracle=True, origins=("inside", "outs
         assert st["mode_used"] == mirt.QUERY_BINNED and st["shadow_rays"] == len(p) and st["fallback_records"] == 0, (what, st)
         same_light(counted, brute, p, rec, tris, L, bins, what + ": binned with counters vs brute")
         if with_oracle:
-            from test_gpu_ray_query import oracle_direct_light
+            from query_helpers import oracle_direct_light
             some = np.sort(np.random.default_rng(2).permutation(len(p))[:ORACLE_RAYS])
             same_light(binned[some], oracle_direct_light(oracle, scene, rec[some], lights), p[some], rec[some], tris, L, bins, what + ": binned vs oracle")
         assert np.isfinite(brute).all() and (brute >= 0).all()

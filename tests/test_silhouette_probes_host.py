@@ -27,41 +27,11 @@ import silhouette as sil
 _cache = {}
 
 
-def scene_of(oracle, name):
-    """The probed scenes by name: (triangles, indices of the target triangles or None for all, crossings per edge, scale)."""
-    if name not in _cache:
-        if name == "shell":
-            v = sil.scene_shell(), None, 4, 1.0
-        elif name == "shell_dense":
-            v = sil.scene_shell_dense(), range(150), 4, 1.0
-        elif name == "needles":
-            v = sil.scene_needles(), None, 4, 1.0
-        elif name == "walls":
-            v = sil.scene_walls(), None, 24, 1.0
-        elif name == "grazing":
-            v = sil.scene_grazing(), None, 4, 1.0
-        elif name == "tips":
-            v = sil.scene_tips(), None, 2, 1.0
-        elif name == "soup150":
-            v = oracle.soup(41, 2000, 0.2)[:150].copy(), None, 4, 1.0
-        elif name == "soup2000":
-            v = oracle.soup(41, 2000, 0.2), range(150), 4, 1.0
-        elif name == "shell x 3e-4":
-            v = sil.scene_shell(3e-4), None, 4, 3e-4
-        elif name == "shell x 3e5":
-            v = sil.scene_shell(3e5), None, 4, 3e5
-        else:
-            raise KeyError(name)
-        v[0].setflags(write=False)
-        _cache[name] = v
-    return _cache[name]
-
-
 def inside_case(oracle, name):
     """The scene's probes from the inside origin and the oracle's closest-hit index of each: computed once."""
     key = ("inside", name)
     if key not in _cache:
-        tris, targets, crossings, scale = scene_of(oracle, name)
+        tris, targets, crossings, scale = sil.scene_of(oracle, name)
         O = sil.origins_of(tris, scale)["inside"]
         p = sil.probes(tris, O, targets, crossings)
         idx = sil.oracle_index(oracle, tris, O, p["dir"])
@@ -96,7 +66,7 @@ def test_probes_reach_and_straddle_their_targets(oracle, name):
 
 def test_soup150_inside_the_full_soup(oracle):
     """Most of the first 150 triangles are hidden inside the 2000: equality only, no share asked (measured: 0.21 of inside twins)."""
-    tris, targets, crossings, _ = scene_of(oracle, "soup2000")
+    tris, targets, crossings, _ = sil.scene_of(oracle, "soup2000")
     p = sil.probes(tris, sil.INSIDE, targets, crossings)
     alone = inside_case(oracle, "soup150")[2]
     assert np.array_equal(p["dir"], alone["dir"]) and p["target"].max() == 149
@@ -105,8 +75,8 @@ def test_soup150_inside_the_full_soup(oracle):
 def test_every_grid_and_both_bin_tests_are_reached(oracle):
     """Scene sizes on either side of the 2000 triangles at which the cube takes 128 bins a side, and walls whose boxes are more
     than 32 bins (the limit of the bin-by-bin test) and more than 64 bins of a face wide, across seams, with a vertex behind."""
-    assert len(scene_of(oracle, "shell")[0]) == 150 and len(scene_of(oracle, "shell_dense")[0]) >= 2000 == len(scene_of(oracle, "soup2000")[0])
-    walls = scene_of(oracle, "walls")[0].astype(np.float64)
+    assert len(sil.scene_of(oracle, "shell")[0]) == 150 and len(sil.scene_of(oracle, "shell_dense")[0]) >= 2000 == len(sil.scene_of(oracle, "soup2000")[0])
+    walls = sil.scene_of(oracle, "walls")[0].astype(np.float64)
     spans, behind = [], 0
     for t in walls:
         g = t[:9].reshape(3, 3) - sil.INSIDE
@@ -118,12 +88,12 @@ def test_every_grid_and_both_bin_tests_are_reached(oracle):
             spans.append(((u.max() - u.min()) * 32, (v.max() - v.min()) * 32))
     spans = np.array(spans)
     assert ((spans > 32).all(axis=1) & (spans < 64).all(axis=1)).sum() >= 12 and (spans > 64).all(axis=1).sum() >= 6 and behind >= 6, (spans, behind)
-    needles = scene_of(oracle, "needles")[0].astype(np.float64)
+    needles = sil.scene_of(oracle, "needles")[0].astype(np.float64)
     e = np.stack([needles[:, 3:6] - needles[:, 0:3], needles[:, 6:9] - needles[:, 3:6], needles[:, 0:3] - needles[:, 6:9]], axis=1)
     length = np.linalg.norm(e, axis=2).max(axis=1)
     height = np.linalg.norm(np.cross(e[:, 0], e[:, 1]), axis=1) / length
     assert np.median(length / height) >= 1000
-    graz = scene_of(oracle, "grazing")[0].astype(np.float64)
+    graz = sil.scene_of(oracle, "grazing")[0].astype(np.float64)
     n = np.cross(graz[:, 3:6] - graz[:, 0:3], graz[:, 6:9] - graz[:, 0:3])
     h = np.abs(((graz[:, 0:3] - sil.INSIDE) * n).sum(axis=1)) / np.linalg.norm(n, axis=1)
     assert h.max() < 1.1e-3 and h.min() > 0.5e-6 and (h < 2e-6).sum() >= 8, (h.min(), h.max())
@@ -131,8 +101,8 @@ def test_every_grid_and_both_bin_tests_are_reached(oracle):
 
 def test_scaled_shells_keep_their_shape(oracle):
     for name, scale in (("shell x 3e-4", 3e-4), ("shell x 3e5", 3e5)):
-        tris = scene_of(oracle, name)[0]
-        assert np.allclose(tris[:, :9], scene_of(oracle, "shell")[0][:, :9].astype(np.float64) * scale, rtol=1e-6, atol=0)
+        tris = sil.scene_of(oracle, name)[0]
+        assert np.allclose(tris[:, :9], sil.scene_of(oracle, "shell")[0][:, :9].astype(np.float64) * scale, rtol=1e-6, atol=0)
         O = sil.origins_of(tris, scale)["inside"]
         p = sil.probes(tris, O)
         assert np.array_equal(p["target"], inside_case(oracle, "shell")[2]["target"])
