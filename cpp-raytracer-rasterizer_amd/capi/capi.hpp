@@ -15,6 +15,7 @@
 #include "../query/rt_query.hpp"
 #include "cube_plan.hpp"
 #include "pass_plan.hpp"
+#include "object_plan.hpp"
 #include "env.hpp"
 
 #include <cstdarg>
@@ -377,6 +378,15 @@ struct Ctx {
     uint32_t *d_scene_bounds = nullptr;          // the SceneBounds words the scene kernels leave (scene.cpp)
     float *d_scene_stage = nullptr;              // staging of mirt_scene_update's host rows (scene_stage_cap floats)
     size_t scene_stage_cap = 0;
+    // posed scenes (scene.cpp): the declared objects, the rest pose they are posed from, and the table of one pose -- on the device
+    // and where the host fills it (pinned: it travels stream-ordered in front of the launch).  Keyed by nothing: mirt_scene_set_objects
+    // puts them there, an upload forgets them, updates and transforms leave them alone.
+    std::vector<mirt_object> objects;
+    float *d_rest = nullptr;                     // rest_cap floats, nrest rows in use
+    size_t rest_cap = 0;
+    int nrest = 0;
+    uint32_t *d_pose_table = nullptr, *h_pose_table = nullptr;   // pose_table_cap words each (object_plan.hpp: pose_table_words)
+    size_t pose_table_cap = 0;
     float bbox_lo[3] = { 0, 0, 0 }, bbox_hi[3] = { 0, 0, 0 };   // the scene's bounding box (host side, mirt_scene_upload)
     LightCache lc;
     QueryRows qrows;
@@ -533,6 +543,10 @@ int scene_update_device(int first, int count, const void *d_tris15);
 int scene_update_host(int first, int count, const float *tris15);
 int scene_transform(int first, int count, const float *rot9, const float *translate3);
 int scene_download(int first, int count, float *tris15);
+int scene_set_objects(const mirt_object *objects, int nobjects, const float *rest15, int nrest);
+int scene_pose(const int32_t *which, int count, const float *xforms12);
+// The declared objects and the rest pose go (with their memory: the pose table's too) -- what an upload and mirt_shutdown do to them.
+void scene_forget_objects();
 int scene_info(struct mirt_scene_info *out);
 
 // ---- ray queries (query.cpp) ----

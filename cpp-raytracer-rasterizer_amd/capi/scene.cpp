@@ -1,6 +1,7 @@
 // scene.cpp -- scenes that live on the device: triangles uploaded from device memory (mirt_scene_upload_device), replaced in part
-// (mirt_scene_update*), moved in place (mirt_scene_transform), read back (mirt_scene_download) and described (mirt_scene_info); the
-// kernels: ../scene/scene_kernels.hip.  Every call that changes the scene starts as mirt_scene_upload does -- it waits for every
+// (mirt_scene_update*), moved in place (mirt_scene_transform), posed object by object from a rest pose the library keeps
+// (mirt_scene_set_objects, mirt_scene_pose), read back (mirt_scene_download) and described (mirt_scene_info); the kernels:
+// ../scene/scene_kernels.hip.  Every call that changes the scene starts as mirt_scene_upload does -- it waits for every
 // library stream and for the device, so frames in flight finish on the old scene and the caller's source is complete whatever
 // stream wrote it -- and returns with the scene, its tables, its bounding box and its finiteness flag current: one 32-byte
 // read-back behind the kernels.  scene_commit is what all of them, mirt_scene_upload included, do to the host's state last.
@@ -60,34 +61,53 @@ template <int MODE> static void launch_range(const SceneRange &a)
     hipLaunchKernelGGL(k_scene_range<MODE>, dim3((unsigned)((a.count + SCENE_BLOCK_ROWS - 1) / SCENE_BLOCK_ROWS)), dim3(SCENE_BLOCK_ROWS), 0, g.stream, a);
 }
 
-// Rows [first, first + count) of g.d_tris from d_src (NULL: the scene's own rows moved by rot / tr), their table entries, the
-// bounds of the whole scene and the host's copy of them: three launches, two when the range is the whole scene.
-static int change_rows(int first, int count, int n, const float *d_src, const float *rot9, const float *tr3, bool set_culled, const uint8_t *d_culled_src)
+// What every pass over the scene starts from: the scene's arrays, and the bounds block at its initial values (one launch).
+static int range_begin(int n, SceneRange *a)
 {
     if (!g.d_scene_bounds) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g.d_scene_bounds), sizeof(SceneBounds)));
-    SceneBounds *db = reinterpret_cast<SceneBounds *>(g.d_scene_bounds);
-    SceneRange a = {};
-    a.src = d_src; a.tris = g.d_tris; a.geo = g.d_geo; a.shade = g.d_shade;
-    a.first = first; a.count = count; a.n = n;
-    a.culled = set_culled ? g.d_culled : nullptr; a.culled_src = d_culled_src;
-    if (rot9) { memcpy(a.rot, rot9, sizeof a.rot); memcpy(a.tr, tr3, sizeof a.tr); }
-    a.bounds = db;
-    hipLaunchKernelGGL(k_scene_bounds_init, dim3(1), dim3(8), 0, g.stream, db);
-    const bool whole = first == 0 && count == n;
-    if (whole) {
-        if (rot9) launch_range<SCENE_INGEST | SCENE_XFORM | SCENE_BOUNDS>(a); else launch_range<SCENE_INGEST | SCENE_BOUNDS>(a);
-    } else {
-        if (rot9) launch_range<SCENE_INGEST | SCENE_XFORM>(a); else launch_range<SCENE_INGEST>(a);
-        a.first = 0; a.count = n;
+    *a = SceneRange{};
+    a->tris = g.d_tris; a->geo = g.d_geo; a->shade = g.d_shade;
+    a->n = n;
+    a->bounds = reinterpret_cast<SceneBounds *>(g.d_scene_bounds);
+    hipLaunchKernelGGL(k_scene_bounds_init, dim3(1), dim3(8), 0, g.stream, a->bounds);
+    return MIRT_OK;
+}
+
+// ... and ends with: the bounds of the whole scene behind the launches that changed rows (have_bounds: the launch over the whole
+// scene took them itself) and the host's copy of them.
+static int range_end(SceneRange a, bool have_bounds)
+{
+    if (!have_bounds) {
+        a.first = 0; a.count = a.n;
         launch_range<SCENE_BOUNDS>(a);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g.stream));
     SceneBounds hb;
-    HIP_TRY(hipMemcpy(&hb, db, sizeof hb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&hb, a.bounds, sizeof hb, hipMemcpyDeviceToHost));
     g.scene_finite = hb.not_finite == 0;
     for (int c = 0; c < 3; c++) { g.bbox_lo[c] = scene_unord(hb.lo[c]); g.bbox_hi[c] = scene_unord(hb.hi[c]); }
     return MIRT_OK;
+}
+
+// Rows [first, first + count) of g.d_tris from d_src (NULL: the scene's own rows moved by rot / tr), their table entries, the
+// bounds of the whole scene and the host's copy of them: three launches, two when the range is the whole scene.
+static int change_rows(int first, int count, int n, const float *d_src, const float *rot9, const float *tr3, bool set_culled, const uint8_t *d_culled_src)
+{
+    int rc;
+    SceneRange a;
+    if ((rc = range_begin(n, &a))) return rc;
+    a.src = d_src;
+    a.first = first; a.count = count;
+    a.culled = set_culled ? g.d_culled : nullptr; a.culled_src = d_culled_src;
+    if (rot9) { memcpy(a.rot, rot9, sizeof a.rot); memcpy(a.tr, tr3, sizeof a.tr); }
+    const bool whole = first == 0 && count == n;
+    if (whole) {
+        if (rot9) launch_range<SCENE_INGEST | SCENE_XFORM | SCENE_BOUNDS>(a); else launch_range<SCENE_INGEST | SCENE_BOUNDS>(a);
+    } else {
+        if (rot9) launch_range<SCENE_INGEST | SCENE_XFORM>(a); else launch_range<SCENE_INGEST>(a);
+    }
+    return range_end(a, whole);
 }
 
 int scene_upload_device(const void *d_tris15, const void *d_culled, int n)
@@ -98,6 +118,7 @@ int scene_upload_device(const void *d_tris15, const void *d_culled, int n)
     if ((uintptr_t)d_tris15 & 3) return fail(MIRT_ERR_INVALID_ARGUMENT, "mirt_scene_upload_device: the triangle array %p is not 4-byte aligned", d_tris15);
     if ((rc = begin_change())) return rc;
     g.n = 0;
+    scene_forget_objects();                      // (their ranges were checked against the old scene)
     if ((rc = dev_realloc(&g.d_tris, (size_t)n * 15))) return rc;
     if ((rc = dev_realloc(&g.d_culled, (size_t)MAX_FLIGHT * n))) return rc;
     if ((rc = dev_realloc(&g.d_geo, (size_t)n))) return rc;
@@ -143,6 +164,96 @@ int scene_transform(int first, int count, const float *rot9, const float *transl
     if (count == 0) return MIRT_OK;
     if ((rc = begin_change())) return rc;
     if ((rc = change_rows(first, count, g.n, nullptr, rot9, translate3, false, nullptr))) return rc;
+    scene_commit(false);
+    return MIRT_OK;
+}
+
+// ---- posed scenes ----
+
+void scene_forget_objects()
+{
+    g.objects.clear();
+    g.nrest = 0;
+    if (g.d_rest) (void)hipFree(g.d_rest);
+    if (g.d_pose_table) (void)hipFree(g.d_pose_table);
+    if (g.h_pose_table) (void)hipHostFree(g.h_pose_table);
+    g.d_rest = nullptr; g.rest_cap = 0;
+    g.d_pose_table = g.h_pose_table = nullptr; g.pose_table_cap = 0;
+}
+
+int scene_set_objects(const mirt_object *objects, int nobjects, const float *rest15, int nrest)
+{
+    int rc;
+    if ((rc = need_init())) return rc;
+    if (nobjects < 0 || nrest < 0) return fail(MIRT_ERR_INVALID_ARGUMENT, "mirt_scene_set_objects: %d objects, %d rest triangles", nobjects, nrest);
+    if (nobjects > 0 && !objects) return fail(MIRT_ERR_INVALID_ARGUMENT, "mirt_scene_set_objects: the object array must not be NULL when nobjects is > 0");
+    if (nrest > 0 && !rest15) return fail(MIRT_ERR_INVALID_ARGUMENT, "mirt_scene_set_objects: the rest array must not be NULL when nrest is > 0");
+    if ((uintptr_t)rest15 & 3) return fail(MIRT_ERR_INVALID_ARGUMENT, "mirt_scene_set_objects: the rest array %p is not 4-byte aligned", (const void *)rest15);
+    if ((rc = need_scene())) return rc;
+    const bool snapshot = !rest15;
+    if (snapshot) nrest = g.n;
+    const ObjectCheck oc = check_objects(objects, nobjects, nrest, g.n);
+    if (oc.fault != OBJECTS_OK) {
+        const mirt_object &o = objects[oc.a];
+        if (oc.fault == OBJECTS_OVERLAP)
+            return fail(MIRT_ERR_INVALID_ARGUMENT, "mirt_scene_set_objects: the scene ranges of objects %d and %d, [%d, %d + %d) and [%d, %d + %d), overlap", oc.a, oc.b,
+                        o.scene_first, o.scene_first, o.count, objects[oc.b].scene_first, objects[oc.b].scene_first, objects[oc.b].count);
+        return fail(MIRT_ERR_INVALID_ARGUMENT, "mirt_scene_set_objects: object %d {rest %d, scene %d, count %d} %s (%d rest triangles, %d in the scene)", oc.a,
+                    o.rest_first, o.scene_first, o.count,
+                    oc.fault == OBJECT_NEGATIVE ? "has a negative field" : oc.fault == OBJECT_LEAVES_REST ? "leaves the rest pose" : "leaves the scene", nrest, g.n);
+    }
+    if (nobjects == 0) { scene_forget_objects(); return MIRT_OK; }
+    // The scene is not touched: frames in flight only read it, and it only changes inside calls that return with it complete, so
+    // the snapshot is a plain copy; a pose waits for the device before its kernel reads the rest pose, wherever the copy ran.
+    const size_t words = (size_t)nrest * 15;
+    g.objects.clear();                           // (a copy that fails leaves no objects, not the old ones over a rest pose half replaced)
+    g.nrest = 0;
+    if (g.rest_cap < words && (rc = dev_grow(&g.d_rest, &g.rest_cap, words, words, false))) return rc;
+    if (words) HIP_TRY(hipMemcpy(g.d_rest, snapshot ? g.d_tris : rest15, words * sizeof(float), snapshot ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    g.objects.assign(objects, objects + nobjects);
+    g.nrest = nrest;
+    return MIRT_OK;
+}
+
+int scene_pose(const int32_t *which, int count, const float *xforms12)
+{
+    int rc;
+    if ((rc = need_init())) return rc;
+    if (count < 0) return fail(MIRT_ERR_INVALID_ARGUMENT, "mirt_scene_pose: count %d is negative", count);
+    if (count > 0 && !xforms12) return fail(MIRT_ERR_INVALID_ARGUMENT, "mirt_scene_pose: the transforms must not be NULL when count is > 0");
+    if ((rc = need_scene())) return rc;
+    const int nobjects = (int)g.objects.size();
+    const WhichCheck wc = check_which(which, count, nobjects);
+    switch (wc.fault) {
+    case WHICH_OK: break;
+    case WHICH_NO_OBJECTS: return fail(MIRT_ERR_INVALID_ARGUMENT, "mirt_scene_pose: no objects declared (mirt_scene_set_objects)");
+    case WHICH_TOO_MANY: return fail(MIRT_ERR_INVALID_ARGUMENT, "mirt_scene_pose: count %d exceeds the %d objects declared", count, nobjects);
+    case WHICH_OUTSIDE: return fail(MIRT_ERR_INVALID_ARGUMENT, "mirt_scene_pose: which[%d] = %d is outside the %d objects declared", wc.at, which[wc.at], nobjects);
+    case WHICH_TWICE: return fail(MIRT_ERR_INVALID_ARGUMENT, "mirt_scene_pose: which[%d] = %d is listed twice", wc.at, which[wc.at]);
+    }
+    if (count == 0) return MIRT_OK;
+    // the table of the call, filled where the host can write it: a pose returns with its stream idle, so neither copy is in use
+    const size_t words = pose_table_words(count);
+    if (g.pose_table_cap < words) {
+        if (g.h_pose_table) (void)hipHostFree(g.h_pose_table);
+        g.h_pose_table = nullptr;
+        if ((rc = dev_grow(&g.d_pose_table, &g.pose_table_cap, words, words, false))) return rc;
+        if (hipHostMalloc(reinterpret_cast<void **>(&g.h_pose_table), words * 4, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            g.h_pose_table = nullptr; g.pose_table_cap = 0;
+            return fail(MIRT_ERR_OUT_OF_MEMORY, "mirt_scene_pose: no pinned memory for a table of %d objects", count);
+        }
+    }
+    const uint32_t items = fill_pose_table(g.objects.data(), which, count, xforms12, g.h_pose_table);
+    if (items == 0) return MIRT_OK;              // every listed object is empty: nothing changes
+    if ((rc = begin_change())) return rc;
+    SceneRange a;
+    if ((rc = range_begin(g.n, &a))) return rc;
+    HIP_TRY(hipMemcpyAsync(g.d_pose_table, g.h_pose_table, words * 4, hipMemcpyHostToDevice, g.stream));
+    a.src = g.d_rest;
+    a.pose = reinterpret_cast<const PoseEntry *>(g.d_pose_table); a.pose_count = count;
+    hipLaunchKernelGGL(k_scene_range<SCENE_INGEST | SCENE_XFORM | SCENE_POSE>, dim3(items), dim3(SCENE_BLOCK_ROWS), 0, g.stream, a);
+    if ((rc = range_end(a, false))) return rc;
     scene_commit(false);
     return MIRT_OK;
 }

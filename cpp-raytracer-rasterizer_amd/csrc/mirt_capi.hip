@@ -147,6 +147,7 @@ extern "C" void mirt_shutdown(void)
     for (StreamState &ss : g.streams) ss.release();
     g.lc.release();
     g.qrows.release();
+    scene_forget_objects();
     for (void *p : { (void *)g.d_tris, (void *)g.d_culled, (void *)g.d_geo, (void *)g.d_shade, (void *)g.d_scene_bounds, (void *)g.d_scene_stage, g.d_xrgb, g.d_rgb, g.d_index, g.d_zinv, g.d_pos,
                      (void *)g.d_band[0], (void *)g.d_band[1] })
         if (p) (void)hipFree(p);
@@ -253,6 +254,7 @@ extern "C" int mirt_scene_upload(const float *tris15, const uint8_t *culled, int
     if (!tris15 || n < 1) return fail(MIRT_ERR_INVALID_ARGUMENT, "scene needs at least one triangle (n = %d)", n);
     HIP_TRY(sync_all());
     g.n = 0;
+    scene_forget_objects();                      // (their ranges were checked against the old scene)
     if ((rc = dev_realloc(&g.d_tris, (size_t)n * 15))) return rc;
     if ((rc = dev_realloc(&g.d_culled, (size_t)MAX_FLIGHT * n))) return rc;
     HIP_TRY(hipMemcpy(g.d_tris, tris15, (size_t)n * 15 * sizeof(float), hipMemcpyHostToDevice));
@@ -293,6 +295,11 @@ extern "C" int mirt_scene_transform(int first, int count, const float rot9[9], c
 }
 extern "C" int mirt_scene_download(int first, int count, float *tris15) { return scene_download(first, count, tris15); }
 extern "C" int mirt_scene_info(struct mirt_scene_info *out) { return scene_info(out); }
+extern "C" int mirt_scene_set_objects(const mirt_object *objects, int nobjects, const float *rest15, int nrest)
+{
+    return scene_set_objects(objects, nobjects, rest15, nrest);
+}
+extern "C" int mirt_scene_pose(const int32_t *which, int count, const float *xforms12) { return scene_pose(which, count, xforms12); }
 
 extern "C" int mirt_scene_set_culled(const uint8_t *culled, int n)
 {

@@ -5,6 +5,7 @@
 #include "../../include/mirt.h"
 
 #include "cull.hpp"
+#include "../capi/object_plan.hpp"
 #include "../scene/scene_xform.hpp"
 
 #include <cmath>
@@ -222,5 +223,31 @@ extern "C" int mirt_transform(float *tris15, int n, const float rot9[9], const f
     if (n < 0 || (n > 0 && !tris15) || !rot9 || !translate3) return MIRT_ERR_INVALID_ARGUMENT;
     const v3 tr = ld3(translate3);
     for (int i = 0; i < n; i++) transform_tri(tris15 + (size_t)15 * i, rot9, tr);
+    return MIRT_OK;
+}
+
+// What mirt_scene_pose does to the uploaded scene, on host arrays: the listed objects' rows are copied from the rest pose and moved
+// by the function above's arithmetic (capi/object_plan.hpp: the checks mirt_scene_set_objects and mirt_scene_pose make, on the
+// caller's n and nrest).  Without a rest array the rows are taken from tris15 as it arrives -- from a copy: an object's rest range
+// may be another object's scene range.
+extern "C" int mirt_pose(const float *rest15, int nrest, const mirt_object *objects, int nobjects, const int32_t *which, int count,
+                         const float *xforms12, float *tris15, int n)
+{
+    if (nobjects < 0 || nrest < 0 || (nobjects > 0 && !objects) || (nrest > 0 && !rest15) || ((uintptr_t)rest15 & 3)) return MIRT_ERR_INVALID_ARGUMENT;
+    if (count < 0 || (count > 0 && !xforms12) || n < 0 || (n > 0 && !tris15)) return MIRT_ERR_INVALID_ARGUMENT;
+    const bool snapshot = !rest15;
+    if (check_objects(objects, nobjects, snapshot ? n : nrest, n).fault != OBJECTS_OK) return MIRT_ERR_INVALID_ARGUMENT;
+    if (check_which(which, count, nobjects).fault != WHICH_OK) return MIRT_ERR_INVALID_ARGUMENT;
+    std::vector<float> copy;
+    if (snapshot && count > 0) { copy.assign(tris15, tris15 + (size_t)15 * n); rest15 = copy.data(); }
+    for (int i = 0; i < count; i++) {
+        const mirt_object &o = objects[listed_object(which, i)];
+        const float *x = xforms12 + 12 * (size_t)i;
+        for (int r = 0; r < o.count; r++) {
+            float *t = tris15 + (size_t)15 * ((size_t)o.scene_first + r);
+            memmove(t, rest15 + (size_t)15 * ((size_t)o.rest_first + r), 15 * sizeof(float));
+            transform_tri(t, x, ld3(x + 9));
+        }
+    }
     return MIRT_OK;
 }

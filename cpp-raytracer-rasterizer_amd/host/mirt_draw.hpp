@@ -77,6 +77,47 @@ inline mirt_view make_view(const vec3 &cameraPos, const mat3 &cameraRot, float f
     return v;
 }
 
+// ---- meshes that move every frame: objects posed from a rest pose the library keeps on the device --------
+// (mirt_scene_set_objects, mirt_scene_pose).  Add() the objects -- rows of the rest pose and where they go in `triangles`; instances
+// of one mesh share its rest rows --, Declare() them once the scene is uploaded (a later mirt_scene_upload forgets them: declare
+// again), Set() the transforms of the objects that moved this frame and Pose() in front of Draw(): one call, however many moved.
+// Poses never compound: every one starts from the rest rows.
+struct PoseObjects {
+    std::vector<mirt_object> objects;
+    std::vector<float> xforms;                       // {rot9 column-major, translate3} per object, as last Set()
+    std::vector<char> moved;                         // Set() since the last Pose()
+
+    int Add(int rest_first, int scene_first, int count)
+    {
+        const mirt_object o = { rest_first, scene_first, count };
+        const float identity[12] = { 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0 };
+        objects.push_back(o);
+        xforms.insert(xforms.end(), identity, identity + 12);
+        moved.push_back(0);
+        return (int)objects.size() - 1;
+    }
+    // rest: nrest triangles in the reference's layout; nullptr with 0: the uploaded scene as it is now becomes the rest pose
+    void Declare(const Triangle *rest = nullptr, int nrest = 0)
+    {
+        check(mirt_scene_set_objects(objects.data(), (int)objects.size(), rest ? &rest[0].v0.x : nullptr, nrest), "mirt_scene_set_objects");
+    }
+    void Set(int object, const mat3 &rot, const vec3 &translate)
+    {
+        float *x = &xforms[(size_t)12 * object];
+        std::memcpy(x, rot.m, 36);
+        x[9] = translate.x; x[10] = translate.y; x[11] = translate.z;
+        moved[(size_t)object] = 1;
+    }
+    void Pose()
+    {
+        std::vector<int32_t> which;
+        std::vector<float> x;
+        for (size_t k = 0; k < objects.size(); k++)
+            if (moved[k]) { which.push_back((int32_t)k); x.insert(x.end(), &xforms[12 * k], &xforms[12 * k] + 12); moved[k] = 0; }
+        if (!which.empty()) check(mirt_scene_pose(which.data(), (int)which.size(), x.data()), "mirt_scene_pose");
+    }
+};
+
 // ---- the ray tracer's globals and Draw() (raytracer.cpp:28-98, 547-606) ---------------------------------
 struct RayTracer {
     std::vector<Triangle> triangles;                 // :28

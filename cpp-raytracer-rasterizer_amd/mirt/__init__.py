@@ -31,6 +31,7 @@ EXPORTS = (
     "mirt_intersect_fans", "mirt_intersect_fans_device",
     "mirt_scene_upload_device", "mirt_scene_update_device", "mirt_scene_update", "mirt_scene_transform", "mirt_transform",
     "mirt_scene_download", "mirt_scene_info",
+    "mirt_scene_set_objects", "mirt_scene_pose", "mirt_pose",
 )
 
 
@@ -74,6 +75,11 @@ class SceneInfo(C.Structure):
     """struct mirt_scene_info: the values the library decides with (40 bytes)."""
     _fields_ = [("n", C.c_int32), ("finite", C.c_int32), ("bbox_lo", C.c_float * 3), ("bbox_hi", C.c_float * 3),
                 ("version", C.c_uint64)]
+
+
+class Object(C.Structure):
+    """mirt_object: rest rows [rest_first, rest_first + count) pose into scene rows [scene_first, scene_first + count) (12 bytes)."""
+    _fields_ = [("rest_first", C.c_int32), ("scene_first", C.c_int32), ("count", C.c_int32)]
 
 
 # the same two layouts for numpy: arrays of rays / hit records travel as they are
@@ -155,6 +161,9 @@ def load():
     lib.mirt_transform.argtypes = [_vp, C.c_int, _vp, _vp]
     lib.mirt_scene_download.argtypes = [C.c_int, C.c_int, _vp]
     lib.mirt_scene_info.argtypes = [C.POINTER(SceneInfo)]
+    lib.mirt_scene_set_objects.argtypes = [_vp, C.c_int, _vp, C.c_int]
+    lib.mirt_scene_pose.argtypes = [_vp, C.c_int, _vp]
+    lib.mirt_pose.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int]
     _lib = lib
     return lib
 
@@ -335,6 +344,50 @@ def transform(tris, rot9, translate3=(0.0, 0.0, 0.0)):
     r = np.ascontiguousarray(rot9, np.float32).reshape(9)
     t = np.ascontiguousarray(translate3, np.float32).reshape(3)
     _check(load().mirt_transform(_ptr(out), len(out), _ptr(r), _ptr(t)))
+    return out
+
+
+def _as_objects(objects):
+    """Objects as an (k, 3) int32 array {rest_first, scene_first, count}: the bytes of k mirt_object."""
+    if isinstance(objects, C.Array):
+        objects = [(o.rest_first, o.scene_first, o.count) for o in objects]
+    else:
+        objects = [(o.rest_first, o.scene_first, o.count) if isinstance(o, Object) else tuple(o) for o in objects]
+    return np.ascontiguousarray(np.array(objects, np.int64).reshape(-1, 3), np.int32)
+
+
+def _as_pose(xforms, which):
+    x = np.ascontiguousarray(xforms, np.float32).reshape(-1, 12)
+    w = None if which is None else np.ascontiguousarray(which, np.int32).reshape(-1)
+    if w is not None and len(w) != len(x):
+        raise ValueError("%d transforms for %d listed objects" % (len(x), len(w)))
+    return x, w
+
+
+def scene_set_objects(objects, rest=None):
+    """Declares the objects of the uploaded scene -- rows (rest_first, scene_first, count) or Object instances -- and the rest pose they
+    are posed from: an (nrest, 15) host array, or None for a snapshot of the scene as it is (mirt_scene_set_objects).  No objects:
+    they and the rest pose are forgotten."""
+    o = _as_objects(objects)
+    rest = None if rest is None else np.ascontiguousarray(rest, np.float32).reshape(-1, 15)
+    _check(load().mirt_scene_set_objects(_ptr(o), len(o), _ptr(rest), 0 if rest is None else len(rest)))
+
+
+def scene_pose(xforms, which=None):
+    """Poses objects from the rest pose in one call: xforms is (count, 12), {rot9 column-major, translate3} per object; which lists
+    their indices (None: objects 0 .. count - 1) (mirt_scene_pose)."""
+    x, w = _as_pose(xforms, which)
+    _check(load().mirt_scene_pose(_ptr(w), len(x), _ptr(x)))
+
+
+def pose(rest, objects, xforms, tris, which=None):
+    """The arithmetic of scene_set_objects + scene_pose on host arrays (mirt_pose; no device): a new (n, 15) array, tris with the
+    listed objects' rows posed from rest (None: from tris itself)."""
+    out = np.array(tris, np.float32, order="C").reshape(-1, 15)
+    o = _as_objects(objects)
+    rest = None if rest is None else np.ascontiguousarray(rest, np.float32).reshape(-1, 15)
+    x, w = _as_pose(xforms, which)
+    _check(load().mirt_pose(_ptr(rest), 0 if rest is None else len(rest), _ptr(o), len(o), _ptr(w), len(x), _ptr(x), _ptr(out), len(out)))
     return out
 
 

@@ -1,5 +1,6 @@
 // scene_kernels.hip -- the scene on the device: rows that arrive from device memory (mirt_scene_upload_device,
-// mirt_scene_update*), rows that move in place (mirt_scene_transform), and the bounds of what they leave.
+// mirt_scene_update*), rows that move in place (mirt_scene_transform), rows posed from the rest pose (mirt_scene_pose), and the
+// bounds of what they leave.
 //
 // Bandwidth kernels: 60 bytes read and 60 + 48 + 32 written per triangle.  A 60-byte row is only 4-byte aligned, so a lane that
 // loaded its own row would issue 15 dword loads 60 bytes apart.  Instead a workgroup moves its 256 rows as FLAT dwords through
@@ -26,12 +27,26 @@ template <int MODE>
 __global__ __launch_bounds__(SCENE_BLOCK_ROWS) void k_scene_range(const SceneRange a)
 {
     constexpr bool INGEST = (MODE & SCENE_INGEST) != 0, XFORM = (MODE & SCENE_XFORM) != 0, BOUNDS = (MODE & SCENE_BOUNDS) != 0;
+    constexpr bool POSE = (MODE & SCENE_POSE) != 0;
+    static_assert(!POSE || (INGEST && XFORM && !BOUNDS), "a pose ingests moved rows; the bounds are a pass of their own");
     __shared__ float rows[SCENE_BLOCK_ROWS * 15];
-    const int r0 = blockIdx.x * SCENE_BLOCK_ROWS;                            // the block's first row within the range
-    const int nrows = min(SCENE_BLOCK_ROWS, a.count - r0);
+    // the range the block is part of, its number within it, where the range's rows come from and how they move: the launch's,
+    // or -- POSE -- those of the object the block's work item belongs to (uniform: scalar loads, before anything is stored)
+    int first = a.first, count = a.count, block = blockIdx.x;
+    const float *src = a.src, *rot = a.rot, *tr = a.tr;
+    PoseEntry e;
+    if (POSE) {
+        const uint32_t *prefix = pose_prefix_of(a.pose, a.pose_count);
+        const int k = pose_find(prefix, a.pose_count, blockIdx.x);
+        e = a.pose[k];
+        first = e.scene_first; count = e.count; block = (int)(blockIdx.x - prefix[k]);
+        src = a.src + (size_t)15 * (size_t)e.rest_first; rot = e.rot; tr = e.tr;
+    }
+    const int r0 = block * SCENE_BLOCK_ROWS;                                 // the block's first row within the range
+    const int nrows = min(SCENE_BLOCK_ROWS, count - r0);
     const int nw = nrows * 15;
-    float *own = a.tris + (size_t)15 * ((size_t)a.first + r0);               // the block's rows of the scene
-    const float *in = (INGEST && !XFORM) ? a.src + (size_t)15 * r0 : own;
+    float *own = a.tris + (size_t)15 * ((size_t)first + r0);                 // the block's rows of the scene
+    const float *in = (INGEST && (!XFORM || POSE)) ? src + (size_t)15 * r0 : own;
     for (int i = threadIdx.x; i < nw; i += SCENE_BLOCK_ROWS) rows[i] = in[i];
     __syncthreads();
 
@@ -41,12 +56,12 @@ __global__ __launch_bounds__(SCENE_BLOCK_ROWS) void k_scene_range(const SceneRan
 #pragma unroll
         for (int k = 0; k < 15; k++) t[k] = rows[r * 15 + k];
         if (XFORM) {
-            transform_tri(t, a.rot, V3(a.tr[0], a.tr[1], a.tr[2]));
+            transform_tri(t, rot, V3(tr[0], tr[1], tr[2]));
 #pragma unroll
             for (int k = 0; k < 12; k++) rows[r * 15 + k] = t[k];
         }
         if (INGEST) {
-            const size_t tri = (size_t)a.first + r0 + r;
+            const size_t tri = (size_t)first + r0 + r;
             const v3 v0 = ld3(t), e1 = sub3(ld3(t + 3), v0), e2 = sub3(ld3(t + 6), v0);
             GeoRow g;
             g.g0 = make_float4(v0.x, v0.y, v0.z, e1.x);
@@ -104,5 +119,6 @@ template __global__ void k_scene_range<SCENE_INGEST | SCENE_XFORM>(const SceneRa
 template __global__ void k_scene_range<SCENE_INGEST | SCENE_BOUNDS>(const SceneRange);
 template __global__ void k_scene_range<SCENE_INGEST | SCENE_XFORM | SCENE_BOUNDS>(const SceneRange);
 template __global__ void k_scene_range<SCENE_BOUNDS>(const SceneRange);
+template __global__ void k_scene_range<SCENE_INGEST | SCENE_XFORM | SCENE_POSE>(const SceneRange);
 
 }  // namespace mirt

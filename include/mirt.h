@@ -220,7 +220,7 @@ MIRT_API int mirt_scene_update(int first, int count, const float *tris15);
  * contraction; Draw() does the same to its ray direction (cameraRot * d, raytracer.cpp:580) -- and the normal is recomputed by
  * Triangle::ComputeNormal, normalize(cross(v2 - v0, v1 - v0)) (TestModel.h:26-31).  The colour is untouched.  Repeated calls
  * compound their rounding: a caller who needs a drift-free pose keeps the rest pose and sends the posed rows with
- * mirt_scene_update*. */
+ * mirt_scene_update*, or leaves the rest pose to the library (mirt_scene_set_objects, mirt_scene_pose below). */
 MIRT_API int mirt_scene_transform(int first, int count, const float rot9[9], const float translate3[3]);
 /* The same arithmetic on n triangles of a HOST array, bit for bit (pure arithmetic, no device: to mirt_scene_transform what mirt_cull
  * is to mirt_cull_device) -- for a caller that keeps a host mirror of the scene. */
@@ -239,6 +239,56 @@ struct mirt_scene_info {
     uint64_t version;
 };
 MIRT_API int mirt_scene_info(struct mirt_scene_info *out);
+
+/* ---- posed scenes: many objects moved from a rest pose in one call ---------------------------------- */
+
+/* The game loop above moves MANY meshes every frame, each from the pose it was loaded in.  One mirt_scene_transform per mesh pays
+ * the fixed part of a scene change (two waits, the launches, the read-back) once per mesh, and compounds its rounding from frame
+ * to frame; thirty-two enemies loaded from one enemy1.stl are thirty-two copies of it on the host.  Here the library keeps a REST
+ * pose on the device, the caller declares objects as (rest range -> scene range) maps, and one call poses any subset of them from
+ * the rest rows: one launch chain, one bounds pass, one read-back, however many objects move. */
+typedef struct mirt_object { int32_t rest_first; int32_t scene_first; int32_t count; } mirt_object;   /* 12 bytes */
+
+/* Declares the objects of the uploaded scene and the rest pose they are posed from: object k writes rest rows [rest_first,
+ * rest_first + count) to scene rows [scene_first, scene_first + count).  rest15: nrest x 15 floats in host memory, copied to the
+ * device (the caller may free it on return); instances may share rest ranges.  rest15 == NULL with nrest == 0: the rest pose is a
+ * snapshot of the scene as it is now (a device-to-device copy; nrest becomes n).  count == 0 is allowed: such an object is never
+ * work.  Scene ranges must be pairwise disjoint, rest ranges may overlap.  nobjects == 0 forgets the objects and frees the rest
+ * pose.
+ *
+ * The call does not change the scene: it bumps no version, invalidates no cache and drains no stream (the scene only changes
+ * inside calls that return with it complete, so a plain copy is ordered).  The objects and the rest pose are forgotten by
+ * mirt_scene_upload, mirt_scene_upload_device and mirt_shutdown.  mirt_scene_update* and mirt_scene_transform change live rows
+ * only: the rest pose stays, and the next pose of that object overwrites what they wrote.
+ *
+ * Checks, in this order, before anything touches the device: MIRT_ERR_NOT_INITIALISED; MIRT_ERR_INVALID_ARGUMENT for nobjects < 0,
+ * nrest < 0, NULL objects with nobjects > 0, NULL rest15 with nrest > 0, a rest15 that is not 4-byte aligned; MIRT_ERR_NO_SCENE;
+ * MIRT_ERR_INVALID_ARGUMENT for a negative field, a rest range outside [0, nrest) ([0, n) for the snapshot), a scene range outside
+ * [0, n), two scene ranges that overlap. */
+MIRT_API int mirt_scene_set_objects(const mirt_object *objects, int nobjects, const float *rest15, int nrest);
+/* Poses `count` objects from the rest pose.  which[i] (host memory) is an index into the declared list, NULL means objects
+ * 0 .. count - 1; xforms12[12 i ..] = { rot9 column-major, translate3 } is that object's transform.  Every triangle of a listed
+ * object becomes the rest row moved as mirt_scene_transform moves a row, bit for bit, the normal recomputed, the colour the rest
+ * row's.  Objects not listed keep their live rows -- their last pose --, and so do triangles that belong to no object and the cull
+ * flags.  The call is never cumulative: posing with A and then with B leaves exactly the scene that posing once with B leaves.
+ *
+ * Ordering and result are those of the four calls above, to the letter: the call waits for every library stream and for the
+ * device, so frames in flight finish on the old scene, and returns with the scene, its tables, its bounding box (taken over all n
+ * again) and its finiteness flag current; the version moves on and every cache is rebuilt.  Three launches and one 32-byte
+ * read-back, whatever count is.
+ *
+ * Checks, in this order: MIRT_ERR_NOT_INITIALISED; MIRT_ERR_INVALID_ARGUMENT for count < 0 or NULL xforms12 with count > 0;
+ * MIRT_ERR_NO_SCENE; MIRT_ERR_INVALID_ARGUMENT when no objects are declared, for count above the declared number when which is
+ * NULL, an index outside the list, an index listed twice.  count == 0 then does nothing and returns MIRT_OK, and so does a list
+ * whose objects are all empty. */
+MIRT_API int mirt_scene_pose(const int32_t *which, int count, const float *xforms12);
+/* The same arithmetic on HOST arrays, bit for bit (pure, no device, no mirt_init: to mirt_scene_pose what mirt_transform is to
+ * mirt_scene_transform) -- for a caller that keeps a host mirror of the scene.  tris15 (n x 15 floats) is written in place, and
+ * only the rows of listed objects are touched; rest15 == NULL with nrest == 0 takes tris15 as it arrives for the rest pose.  The
+ * checks of both calls above without the two statuses that need the library, with n and nrest as given: MIRT_ERR_INVALID_ARGUMENT
+ * also for n < 0 and a NULL tris15 with n > 0. */
+MIRT_API int mirt_pose(const float *rest15, int nrest, const mirt_object *objects, int nobjects,
+                       const int32_t *which, int count, const float *xforms12, float *tris15, int n);
 
 /* Soft shadows (SOFT_SHADOWS_ENABLED / SOFT_SHADOWS_SAMPLES / randomPositions, raytracer.cpp:40-41,84,186-190,
  * 272-287): when samples > 1 every light k is replaced in DirectLight by `samples` jittered positions

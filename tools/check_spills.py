@@ -47,7 +47,7 @@ EXPECT = ("k_rt_trace2", "k_rt_tile2", "k_rt_brute", "k_bin_pairs", "k_raster_sm
           "k_query_rows", "k_query_closest<", "k_query_closest_wave", "k_query_direct_light<", "k_query_direct_light_binned",
           "k_query_fan<", "k_query_fan_binned<false>", "k_query_fan_binned<true>", "k_query_fans_binned<false>", "k_query_fans_binned<true>",
           "k_query_fans_expand",
-          "k_scene_bounds_init", "k_scene_range<1>", "k_scene_range<3>", "k_scene_range<5>", "k_scene_range<7>", "k_scene_range<4>")
+          "k_scene_bounds_init", "k_scene_range<1>", "k_scene_range<3>", "k_scene_range<5>", "k_scene_range<7>", "k_scene_range<4>", "k_scene_range<11>")
 missing = [k for k in EXPECT if not any(k in r[1] for r in rows)]
 if missing or len(rows) < 20:
     sys.exit("tools/check_spills.py: resource summaries found for %d kernels only; missing %s -- the pattern no longer matches the backend's output"
