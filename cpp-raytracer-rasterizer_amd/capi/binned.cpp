@@ -538,7 +538,7 @@ int binned_trace(const RtFrame &f, StreamState &ss, const BinnedPass &bp)
     // geometry rows staged with every candidate while the scene's tables fit the caches, fetched by the exact stage beyond (rt_trace.hip);
     // MIRT_LAZY_GEO=0|1 fixes the choice
     static const int lazy_env = (int)env_int("MIRT_LAZY_GEO", -1);
-    tf.lazy_geo = lazy_env >= 0 ? (lazy_env != 0) : (g.n >= 400000);
+    const bool lazy_geo = lazy_env >= 0 ? (lazy_env != 0) : (g.n >= 400000);
     tf.geo = g.d_geo;
     tf.shade = g.d_shade;
     tf.light_off = bp.cube.light_off;
@@ -552,7 +552,8 @@ int binned_trace(const RtFrame &f, StreamState &ss, const BinnedPass &bp)
     tf.shell_d0 = bp.shell_d0; tf.shell_iw = bp.shell_iw;
     // a tile's list ends at the depth shell of the tile's farthest record (rt_trace.hip); MIRT_TR_LIST_END=0 walks every list to its end
     static const int list_end_env = (int)env_int("MIRT_TR_LIST_END", 1);
-    tf.list_end = list_end_env != 0;
+    // (what is uniform per launch -- planes asked for, one sample per light, these two settings -- in one word: csrc/rt_trace_frame.hpp)
+    tf.flags = trace_frame_flags(tf.f, lazy_geo, list_end_env != 0);
     tf.pair_count = S.d_bin_counters;
     tf.pair_cap = S.pairs.cap_used;
     tf.light_pair_count = bp.light_pair_count;
@@ -561,6 +562,7 @@ int binned_trace(const RtFrame &f, StreamState &ss, const BinnedPass &bp)
     tf.order = S.d_order; tf.order_count = S.d_bin_counters + 16; tf.order_seg = bp.order_seg;
     // (waves never synchronise with each other: one-wave workgroups are the finest scheduling unit; 84 / 87 / 89 us with 1 / 2 / 4)
     const dim3 tgrid(ORDER_GROUPS * bp.order_seg);          // (workgroup id % 8 = XCD group, id / 8 = the wave among the group's)
+    static_assert(TR_WG_WAVES == 1, "the kernel is compiled for one-wave workgroups: 64 threads and one LDS slice per launch below");
     const size_t lds = rt_trace_lds_bytes(1);
     k_begin(MIRT_K_TRACE);
     // (the kernel's own statistics -- tests, candidates, steps, drains -- only for frames rendered with profiling on: rt_trace.hip)
@@ -569,7 +571,7 @@ int binned_trace(const RtFrame &f, StreamState &ss, const BinnedPass &bp)
         if (g.profiling) hipLaunchKernelGGL((k_rt_trace2<true, true>), tgrid, dim3(64), lds, g.stream, tf);
         else hipLaunchKernelGGL((k_rt_trace2<true, false>), tgrid, dim3(64), lds, g.stream, tf);
     } else {
-        // five waves per SIMD (the 96-VGPR instantiation) for the large scenes and for the frame that runs alone, four (98 VGPRs) for
+        // five waves per SIMD (the instantiation held to 96 VGPRs: 92 now) for the large scenes and for the frame that runs alone, four (94 VGPRs) for
         // the small scenes' frames in flight: rt_trace.hip says why; MIRT_TR_WAVES5=0|1 fixes the choice
         static const int waves5_env = (int)env_int("MIRT_TR_WAVES5", -1);
         const bool waves5 = waves5_env >= 0 ? (waves5_env != 0) : (g.n >= 400000 || g.in_flight <= 2);

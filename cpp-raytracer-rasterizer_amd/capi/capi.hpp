@@ -11,6 +11,7 @@
 #include "../csrc/rt_common.hpp"
 #include "../csrc/raster_common.hpp"
 #include "../csrc/rt_binned.hpp"
+#include "../csrc/rt_trace_frame.hpp"
 #include "../csrc/scan.hpp"
 #include "../query/rt_query.hpp"
 #include "cube_plan.hpp"
@@ -46,35 +47,6 @@ struct RtTileFrame {
 MIRT_KERNEL void k_tile_tables(const RtTileFrame);
 template <int TW, bool AA> MIRT_KERNEL void k_rt_tile2(const RtTileFrame);
 template <int WG> MIRT_KERNEL void k_bin_pairs(const float *, const OriginRow *, const OriginRow *, int, BinSet, BinPairs);
-struct TilePairRec { uint32_t txy, beg, nA, nB; };
-constexpr int ORDER_CLASSES = 8, ORDER_GROUPS = 8;
-struct RtTraceFrame {                            // (rt_trace.hip)
-    RtFrame f;
-    const uint32_t *cam_off;
-    const uint32_t *cam_entries;
-    const GeoRow *geo;
-    const ShadeRow *shade;
-    const uint32_t *light_off;
-    const LightRow *light_rows;
-    const uint32_t *light_tri;
-    const BinFrameDesc *light_frames;
-    int tiles_x;
-    int cube_bins;
-    int cam_shells;
-    int light_shells;
-    float shell_d0, shell_iw;
-    int list_end;
-    const uint32_t *pair_count;
-    uint32_t pair_cap;
-    const TilePairRec *order;
-    const uint32_t *order_count;
-    uint32_t order_seg;
-    const uint32_t *sel;
-    const uint32_t *sel_count;
-    int lazy_geo;
-    const uint32_t *light_pair_count;
-    uint32_t light_pair_cap;
-};
 template <bool AA, bool STATS, int WAVES = 4> MIRT_KERNEL void k_rt_trace2(const RtTraceFrame);
 MIRT_KERNEL void k_prep_select(const float *, int, const BinFrameDesc, const SelectOut);
 MIRT_KERNEL void k_select_faces(const float *, int, const float *, const BinFrameDesc *, OriginRow *, uint32_t *, uint32_t, uint32_t *);

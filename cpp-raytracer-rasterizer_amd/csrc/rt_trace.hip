@@ -1,7 +1,7 @@
 // rt_trace.hip -- the binned ray-trace kernel (k_rt_trace2) and the tables it reads.
 //
 // Fused primary + shadow + shade + resolve over the binned candidates (rt_binned.hpp explains why the candidate
-// reduction cannot change any result).  Workgroup = 4 wave64 = a 32 x 16-pixel block; each wave owns TWO horizontally
+// reduction cannot change any result).  A workgroup is one wave64 (TR_WG_WAVES, said at compile time); a wave owns TWO horizontally
 // adjacent 8 x 8-pixel tiles (= two camera bins), lane l carrying pixel (l & 7, l >> 3) of tile A and of tile B.
 //
 // Round 2's kernel (one tile per wave, one ray per lane) spent 630 of its 1140 VALU instructions per wave on code that runs
@@ -29,7 +29,7 @@
 //   * workgroups are mapped to screen blocks so that the blocks an XCD (private L2) works on are neighbours.
 //
 // Same filter and the same exact arithmetic as every other kernel => bit-identical results.
-#include "rt_binned.hpp"
+#include "rt_trace_frame.hpp"
 
 #include <float.h>
 
@@ -229,42 +229,7 @@ __device__ __forceinline__ void cube_bin_of2(const v3p &rd, uint32_t face_base0,
     }
 }
 
-// A tile pair as the trace kernel's waves pick it up: the first tile's place in the frame (column | row << 16, in tiles: the wave
-// divides nothing; capi/binned.cpp refuses a frame of more than 65535 tiles either way), where its list starts (the second tile's follows it), and the two lengths.
-struct TilePairRec { uint32_t txy, beg, nA, nB; };
-constexpr int ORDER_CLASSES = 8;                 // classes of max(nA, nB) / ORDER_CLASS_STEP, the last one open-ended
-constexpr int ORDER_GROUPS = 8;                  // one list per XCD group (workgroup id % 8)
-constexpr uint32_t ORDER_CLASS_STEP = 16;        // = TR_STAGE: a class is a number of staging chunks
-
-struct RtTraceFrame {
-    RtFrame f;
-    const uint32_t *cam_off;          // camera bins (8x8-pixel tiles): first entry of each key, nbins * cam_shells + 1
-    const uint32_t *cam_entries;      // triangle ids ordered by camera key
-    const GeoRow *geo;                // n geometry rows (k_geo_table)
-    const ShadeRow *shade;            // n shading rows (k_geo_table)
-    const uint32_t *light_off;        // light-cube keys of all light positions: first row of each, nlights*6*B*B*light_shells + 1
-    const LightRow *light_rows;       // expanded candidates ordered by light-cube key (k_expand_light_rows)
-    const uint32_t *light_tri;        // the triangle of each of them
-    const BinFrameDesc *light_frames; // 6 per light position: the depth-shell parameters (the faces of a light share them)
-    int tiles_x;                      // camera bins per row
-    int cube_bins;                    // B: light-cube bins per face side
-    int cam_shells;                   // depth shells per camera bin: bin b's list is cam_off[b * cam_shells] .. cam_off[(b + 1) * cam_shells]
-    int light_shells;                 // depth shells per light-cube bin
-    float shell_d0, shell_iw;         // the camera frame's shell parameters (BinFrameDesc): what the tiles' lists were sorted with
-    int list_end;                     // 1: a tile's list ends at the shell of the tile's farthest record (the primary loop below); MIRT_TR_LIST_END
-    const uint32_t *pair_count;       // pairs this frame's binning produced / room in the pair list: beyond it the lists are
-    uint32_t pair_cap;                // incomplete and every tile takes the whole triangle list instead (brute force)
-    const TilePairRec *order;         // the frame's tile pairs by XCD group and list-length class (k_tile_order): ORDER_GROUPS x ORDER_CLASSES
-                                      // segments of order_seg records
-    const uint32_t *order_count;      // records in each segment
-    uint32_t order_seg;               // room per segment = the most pairs a group can have = waves per group
-    const uint32_t *sel;              // the triangles k_prep_select found the frame may see, and how many: what a frame that fell
-    const uint32_t *sel_count;        // back to brute force walks (their origin rows are the ones the frame has built)
-    int lazy_geo;                     // 1: geometry rows are fetched by the exact stage, for the pairs it accepts, instead of being staged
-                                      // with every candidate (scenes whose tables no longer fit the caches: see the staging code)
-    const uint32_t *light_pair_count; // the same for the light-cube lists when a pass of their own built them (the shared, cached cube never
-    uint32_t light_pair_cap;          // overflows: any readable word and a cap of 2^32 - 1): beyond it the shadow rays walk the lights' origin tables
-};
+// (TilePairRec, the ORDER_* constants and RtTraceFrame: rt_trace_frame.hpp, shared with capi/binned.cpp)
 
 // One wave renders one PAIR of horizontally adjacent tiles.  Two things decide which wave takes which pair:
 //  * Tiles differ a lot in what they cost -- on the 100 k soup 9 % of them hold half of all candidates, ~90 each against an
@@ -339,18 +304,20 @@ __global__ __launch_bounds__(64) void k_tile_order(const uint32_t *__restrict__ 
 // four, registers being handed out in eights -- or with spills; the kernel fits 96 since the shaded triangles' colours are fetched
 // after the shadow walk instead of being held across it.)
 template <bool AA, bool STATS, int WAVES = MIRT_TR_WAVES>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 ? 5 : MIRT_TR_WAVES_MIN, WAVES))) void k_rt_trace2(const RtTraceFrame tf)
+__global__ __launch_bounds__(64 * TR_WG_WAVES) __attribute__((amdgpu_waves_per_eu(WAVES == 5 ? 5 : MIRT_TR_WAVES_MIN, WAVES))) void k_rt_trace2(const RtTraceFrame tf)
 {
     extern __shared__ __attribute__((aligned(16))) float4 s_all[];
     const RtFrame &f = tf.f;
-    // (the wave's index is the same in every lane: said once, so that everything derived from it stays on the scalar unit)
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    TrWaveLds &s = reinterpret_cast<TrWaveLds *>(s_all)[wave];
+    // A workgroup is one wave (waves never synchronise with each other, and one-wave workgroups are the finest scheduling unit: 84 / 87 /
+    // 89 us with 1 / 2 / 4): known at compile time, so there is no wave index to find and no blockDim to read.
+    static_assert(TR_WG_WAVES == 1, "the wave -> tile pair map below and the LDS slice assume one wave per workgroup");
+    const int lane = threadIdx.x & 63;
+    TrWaveLds &s = reinterpret_cast<TrWaveLds *>(s_all)[0];
 
-    // Wave -> tile pair: record w of its XCD group's list (k_tile_order), longest lists first.  (Waves never synchronise with each other, so a
-    // workgroup is just a scheduling unit of 1, 2 or 4 of them.)
+    // Wave -> tile pair: record w of its XCD group's list (k_tile_order), longest lists first.
     const uint32_t group = blockIdx.x & (ORDER_GROUPS - 1);                       // = this workgroup's XCD group
-    uint32_t w = (blockIdx.x >> 3) * (blockDim.x >> 6) + (uint32_t)wave;          // this wave among the group's
+    const uint32_t w = blockIdx.x >> 3;                                            // this wave among the group's
+    const uint32_t flags = tf.flags;                       // (TRF_*: what the launch as a whole does and does not need, one word of the batch)
     // Everything the wave reads before its first chunk besides the record is wave-uniform and asked for HERE, together, and waited for
     // once: the group's eight class counts (32 bytes, 32-byte aligned: one scalar load), the pair counts of the camera's and the
     // lights' passes and the selection's count (used by an overflowed frame only; its word is always there).  One after the other,
@@ -405,8 +372,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
     const uint32_t nall = brute ? min(nsel, (uint32_t)f.n) : 0u;
     const uint32_t nA = brute ? nall : rec.nA, nB = brute ? (enB ? nall : 0u) : rec.nB;
     const float4 *geo4 = reinterpret_cast<const float4 *>(tf.geo);
-    const bool lazy = tf.lazy_geo != 0;
-    const bool list_end = tf.list_end != 0 && !brute;
+    const bool lazy = (flags & TRF_LAZY_GEO) != 0u;
+    const bool list_end = (flags & TRF_LIST_END) != 0u && !brute;
     TM_SEG(0)
 
     float bdA = FLT_MAX, bdB = FLT_MAX;                    // Update() reset (:335-339), once per frame
@@ -572,13 +539,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
             // sub-ray's best replaces the record when it is at least as close (a later sub-ray wins exact ties)
             const unsigned long long keyA = s.best[lane], keyB = s.best[lane + 64];
             const bool anyA = s.flag[lane] != 0, anyB = s.flag[lane + 64] != 0;     // ClosestIntersection's return value
-            if (anyA && bdA >= min_t_dist(keyA)) {
-                bdA = min_t_dist(keyA); biA = min_t_index(keyA);
-                posA = V3(s.px[lane], s.py[lane], s.pz[lane]);       // the hit point as the exact stage computed it (:241)
-            }
-            if (anyB && bdB >= min_t_dist(keyB)) {
-                bdB = min_t_dist(keyB); biB = min_t_index(keyB);
-                posB = V3(s.px[lane + 64], s.py[lane + 64], s.pz[lane + 64]);
+            if constexpr (AA) {
+                // (the supersampling instantiations carry the record across sub-rays, and the selects below cost them registers: as before)
+                if (anyA && bdA >= min_t_dist(keyA)) {
+                    bdA = min_t_dist(keyA); biA = min_t_index(keyA);
+                    posA = V3(s.px[lane], s.py[lane], s.pz[lane]);       // the hit point as the exact stage computed it (:241)
+                }
+                if (anyB && bdB >= min_t_dist(keyB)) {
+                    bdB = min_t_dist(keyB); biB = min_t_index(keyB);
+                    posB = V3(s.px[lane + 64], s.py[lane + 64], s.pz[lane + 64]);
+                }
+            } else {
+                // (straight-line: every slot is readable, so the hit points are read by every lane and the record is taken by select)
+                const v3 hpA = V3(s.px[lane], s.py[lane], s.pz[lane]);   // the hit point as the exact stage computed it (:241)
+                const v3 hpB = V3(s.px[lane + 64], s.py[lane + 64], s.pz[lane + 64]);
+                const bool takeA = anyA && bdA >= min_t_dist(keyA), takeB = anyB && bdB >= min_t_dist(keyB);
+                bdA = takeA ? min_t_dist(keyA) : bdA; biA = takeA ? min_t_index(keyA) : biA;
+                posA = V3(takeA ? hpA.x : posA.x, takeA ? hpA.y : posA.y, takeA ? hpA.z : posA.z);
+                bdB = takeB ? min_t_dist(keyB) : bdB; biB = takeB ? min_t_index(keyB) : biB;
+                posB = V3(takeB ? hpB.x : posB.x, takeB ? hpB.y : posB.y, takeB ? hpB.z : posB.z);
             }
 
             TM_SEG(4)
@@ -596,6 +575,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
                 const v3p pos = join3(posA, posB);
                 const v3p nDir = join3(V3(nA4.x, nA4.y, nA4.z), V3(nB4.x, nB4.y, nB4.z));   // glm::normalize(normal) (:300), per triangle
                 v3p result = splat3(V3(0.0f, 0.0f, 0.0f)), result2 = result;
+                // `result` joins `result2` after each light's samples (:322): at every light position when a light has one sample -- nothing
+                // to count then --, else when a count-down of the light's samples (wave-uniform, a scalar) reaches zero.  ((k + 1) %
+                // samples, written out, was an integer division in front of the loop and a dozen scalar instructions and six selects per light.)
+                const bool one_sample = (flags & TRF_ONE_SAMPLE) != 0u;
+                int samples_left = one_sample ? 1 : f.samples;
                 for (int k = 0; k < f.nlights; k++) {
                     // DirectLight's term before the shadow test (raytracer.cpp:294-304), both pixels at once
                     // r = distance(pos, lightPos), A = 4 pi r^2, rDir = normalize(lightPos - pos), B = P / A with P = lightColor / samples (:296, divided on the host)
@@ -628,14 +612,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
                         const int ns = tf.light_shells;
                         const float sd0 = lf->shell_d0, siw = lf->shell_iw;
                         const uint32_t shA = bin_shell_of(thr.x, sd0, siw, ns), shB = bin_shell_of(thr.y, sd0, siw, ns);
-                        if (hitA) {
-                            const uint32_t key = binA * (uint32_t)ns;
-                            eA = tf.light_off[key]; endA = tf.light_off[key + shA + 1u];
-                        }
-                        if (hitB) {
-                            const uint32_t key = binB * (uint32_t)ns;
-                            eB = tf.light_off[key]; endB = tf.light_off[key + shB + 1u];
-                        }
+                        // the four offsets of a lane asked for together, by every lane, and waited for once: cube_bin_of2 clamps face, i and j
+                        // and bin_shell_of its shell, so the keys of a lane without a hit are valid ones; its lists are emptied by select
+                        const uint32_t keyA = binA * (uint32_t)ns, keyB = binB * (uint32_t)ns;
+                        const uint32_t oA0 = tf.light_off[keyA], oA1 = tf.light_off[keyA + shA + 1u];
+                        const uint32_t oB0 = tf.light_off[keyB], oB1 = tf.light_off[keyB + shB + 1u];
+                        eA = hitA ? oA0 : 0u; endA = hitA ? oA1 : 0u;
+                        eB = hitB ? oB0 : 0u; endB = hitB ? oB1 : 0u;
                     }
                     if (STATS) ncand_l += (endA - eA) + (endB - eB);
                     // The lane walks list A, then list B.  Per step: the filter; a candidate it lets through is either a CERTAIN
@@ -705,7 +688,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
                     if (occA || s.flag[lane] != 0) { D.x.x = 0.0f; D.y.x = 0.0f; D.z.x = 0.0f; }
                     if (occB || s.flag[lane + 64] != 0) { D.x.y = 0.0f; D.y.y = 0.0f; D.z.y = 0.0f; }
                     result = add3p(result, D);                     // (:319)
-                    if ((k + 1) % f.samples == 0) result2 = add3p(result2, result);   // (:322) after each light's samples
+                    if (one_sample || --samples_left == 0) {       // (:322) after each light's samples
+                        result2 = add3p(result2, result);
+                        samples_left = f.samples;
+                    }
                 }
                 // (the triangles' colours only now: fetched beside the normals they were six registers held across the whole shadow walk,
                 // the two that kept the kernel from a fifth wave per SIMD)
@@ -718,7 +704,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
             }
             // the frame's counters: hits (= shadow rays per light position), then the kernel's own statistics at the end
             if (lane == 0 && nhits) {
-                const unsigned shard = (blockIdx.x + (threadIdx.x >> 6) * 61u) % HIT_SHARDS;
+                const unsigned shard = blockIdx.x % HIT_SHARDS;
                 atomicAdd(f.hit_count + (size_t)shard * HIT_SHARD_STRIDE, (unsigned long long)nhits);
             }
             wave_lds_fence();
@@ -729,7 +715,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
         // tests executed, candidates offered (list entries x rays), wave steps of the two filter loops, drains: one atomic
         // instruction, lane i adding to word 1 + i of the wave's shard
         if (STATS) ncand += wave_sum(ncand_l);
-        const unsigned shard = (blockIdx.x + (threadIdx.x >> 6) * 61u) % HIT_SHARDS;
+        const unsigned shard = blockIdx.x % HIT_SHARDS;
 #ifdef MIRT_TR_TIMING
         // (experiments) words 3..12 carry the segments' sums instead of the step counts, word 13 the longest lifetime
         TM_SEG(9)
@@ -748,25 +734,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES == 5 
         const f2 q = splat2((float)(rs * rs));
         avg = V3P(div2(avg.x, q), div2(avg.y, q), div2(avg.z, q));
     }
-    if (okA) {
-        const v3 c = half0(avg);
-        const size_t px = (size_t)y * W + xA;
-        if (f.rgb) st3(f.rgb + 3 * px, c);
-        if (f.index) f.index[px] = biA;
-        if (f.fd) f.fd[px] = biA >= 0 ? bdA - f.focal_plane : 0.0f;            // focalDistances (:248-249)
-        store_intersection(f, px, biA, bdA, posA);
-        if (xA >= 1 && xA < W - 1 && y >= 1 && y < H - 1)      // (:618-620)
-            f.xrgb[(size_t)(y - f.row_origin) * f.pitch_words + xA] = pack_xrgb(c);
-    }
-    if (okB) {
-        const v3 c = half1(avg);
-        const size_t px = (size_t)y * W + xB;
-        if (f.rgb) st3(f.rgb + 3 * px, c);
-        if (f.index) f.index[px] = biB;
-        if (f.fd) f.fd[px] = biB >= 0 ? bdB - f.focal_plane : 0.0f;
-        store_intersection(f, px, biB, bdB, posB);
-        if (xB >= 1 && xB < W - 1 && y >= 1 && y < H - 1)
-            f.xrgb[(size_t)(y - f.row_origin) * f.pitch_words + xB] = pack_xrgb(c);
+    // The stores.  What both pixels share is read and computed once: the XRGB plane's base, pitch and first row, the frame's inner
+    // rectangle (:618-620) and the row's address.  A frame that asks for no optional plane (TRF_PLANES, made on the host: a render loop
+    // that presents pixels) goes straight to its one XRGB word per pixel, no plane pointer loaded or tested; one that does has the five
+    // pointers and the focal plane asked for together, in front of both pixels' stores.
+    {
+        uint32_t *const xrgb = f.xrgb;
+        const size_t xrow = (size_t)(y - f.row_origin) * f.pitch_words;
+        const bool inY = y >= 1 && y < H - 1;
+        const int xlast = W - 1;
+        if (flags & TRF_PLANES) {
+            float *const rgb = f.rgb, *const fd = f.fd, *const dist = f.dist, *const pos = f.pos;
+            int32_t *const index = f.index;
+            const float focal_plane = f.focal_plane;
+            const size_t row = (size_t)y * W;
+            if (okA) {
+                const size_t px = row + xA;
+                if (rgb) st3(rgb + 3 * px, half0(avg));
+                if (index) index[px] = biA;
+                if (fd) fd[px] = biA >= 0 ? bdA - focal_plane : 0.0f;            // focalDistances (:248-249)
+                if (dist) dist[px] = biA >= 0 ? bdA : 3.402823466e+38f;          // closestIntersections[] (rt_common.hpp: store_intersection)
+                if (pos) st3(pos + 3 * px, biA >= 0 ? posA : V3(0.0f, 0.0f, 0.0f));
+            }
+            if (okB) {
+                const size_t px = row + xB;
+                if (rgb) st3(rgb + 3 * px, half1(avg));
+                if (index) index[px] = biB;
+                if (fd) fd[px] = biB >= 0 ? bdB - focal_plane : 0.0f;
+                if (dist) dist[px] = biB >= 0 ? bdB : 3.402823466e+38f;
+                if (pos) st3(pos + 3 * px, biB >= 0 ? posB : V3(0.0f, 0.0f, 0.0f));
+            }
+        }
+        if (okA && inY && xA >= 1 && xA < xlast) xrgb[xrow + xA] = pack_xrgb(half0(avg));      // (:618-620)
+        if (okB && inY && xB >= 1 && xB < xlast) xrgb[xrow + xB] = pack_xrgb(half1(avg));
     }
 }
 
