@@ -124,6 +124,17 @@ __device__ __forceinline__ bool sure_hit(const TestDots &d, float e1e2b)
     return fminf(a, b) >= 0.0f && (a + b) < fabsf(d.den) * 0.99999904632568359375f && tn >= 0.0f;
 }
 
+// Whether DirectLight's shadow ray can still change the frame (raytracer.cpp:304-319): D = B * max(dot(rDir, nDir), 0) is the light's
+// term, a found occluder replaces it by (0, 0, 0) (:313-314), and `result += D` (:319) is all that ever reads it.  Where every
+// component of D compares equal to zero the ray is moot:
+//   * +0 is what the occluder would store, so nothing changes;
+//   * -0 (a negative B times the clamped 0) differs from it in the sign bit only, and `result` cannot show that bit: it starts
+//     at +0, and an IEEE sum (round to nearest) is -0 only when BOTH operands are -0, so result is never -0 and
+//     result + (-0) == result + (+0) bit for bit, whether result is zero, finite, infinite or NaN.
+// Written as the negation of the equalities, so that a NaN component -- which an occluder WOULD turn into 0 -- keeps its ray.
+// tests/cpp/shadow_needed_test.cpp checks both claims on the host.
+MIRT_HD bool shadow_ray_needed(float dx, float dy, float dz) { return !(dx == 0.0f && dy == 0.0f && dz == 0.0f); }
+
 // ---- the same for two rays per lane (packed FP32, mirt_math2.hpp) ------------------------------------------
 struct TestDots2 { f2 den, pu, qv; };
 

@@ -22,8 +22,10 @@
 //   * shadow rays: the light-cube bins are ordered by DEPTH SHELL of the candidates' `near` bound (sort key = bin * shells +
 //     shell), so a ray whose hit point lies at distance r from the light walks only the shells up to the one 0.99 r falls
 //     into -- every later candidate has near > 0.99 r and cannot occlude (:313).  A bin's list grows with the square of the
-//     distance from the light, so this drops most of it.  A lane walks the list of its pixel A and then that of its pixel B
-//     back to back (the wave's steps are max(lenA + lenB) over its lanes, not max(lenA) + max(lenB));
+//     distance from the light, so this drops most of it.  A pixel whose light term is exactly zero (a face turned away from the
+//     light) has no ray at all -- its answer could not change a bit of the frame --, and the rays that are needed are dealt evenly
+//     over the lanes through a table in LDS: a lane walks ray l and then ray l + 64 of the wave back to back, whosever pixels
+//     they belong to (the wave's steps are the max over its lanes of what a lane walks);
 //   * a frame whose pair list overflowed (sized from an earlier frame's count, capi/binned.cpp) is rendered by the SAME kernel
 //     with "every triangle" as each tile's list -- brute force, same bits -- instead of by a guard launch behind it;
 //   * workgroups are mapped to screen blocks so that the blocks an XCD (private L2) works on are neighbours.
@@ -98,8 +100,18 @@ static_assert(TR_STAGE == 16, "the staging lanes are split 16 / 16 between the t
 
 // 8064 bytes per wave: 20 waves (5 per SIMD) fit the CU's 160 KB.
 struct TrWaveLds {
-    float4 rows[TR_STAGE * 6];        // origin rows of the staged candidates, tile A's and tile B's interleaved float by float
-    float4 geo[TR_STAGE * 2 * 3];     // their geometry rows: slot = 16 * tile + position in the chunk
+    union {
+        struct {
+            float4 rows[TR_STAGE * 6];        // origin rows of the staged candidates, tile A's and tile B's interleaved float by float
+            float4 geo[TR_STAGE * 2 * 3];     // their geometry rows: slot = 16 * tile + position in the chunk
+        };
+        // ... shading (the primary stage's staging is idle then, and the shadow rays' drains fetch geometry from memory): the needed
+        // shadow rays of a light position, dealt over the lanes: slot i = {rDir, pixel 0..127} of the i-th of them
+        struct {
+            float4 ray[TR_PIX];
+            uint8_t sink;                     // where a walk step that found no certain occluder stores (instead of branching)
+        };
+    };
     float4 q[TR_QUEUE];               // {e1e2d, be2d, e1bd, e1e2b} of a queued (ray, candidate) pair
     unsigned long long best[TR_PIX];  // wavefront min-t key of the pixel's closest accepted hit (this sub-ray)
     uint2 qa[TR_QUEUE];               // {pixel of the pair | staging slot of its candidate << 8 (primary rays), triangle index}
@@ -111,6 +123,7 @@ struct TrWaveLds {
     uint8_t flag[TR_PIX];             // primary: some triangle was accepted (ClosestIntersection's return value); shadow: occluded
 };
 static_assert(sizeof(TrWaveLds) % 16 == 0, "per-wave LDS slice must keep 16-byte alignment");
+static_assert(sizeof(TrWaveLds) == 8064, "20 waves share a CU's LDS: the ray table overlays the staging, it adds nothing");
 
 __device__ __forceinline__ void wave_lds_fence()
 {
@@ -227,6 +240,26 @@ __device__ __forceinline__ void cube_bin_of2(const v3p &rd, uint32_t face_base0,
         const uint32_t bin = face_base0 + (uint32_t)face[h] * per_face + (uint32_t)j * cube_bins + (uint32_t)i;
         if (h) *bin1 = bin; else *bin0 = bin;
     }
+}
+
+// ... and for one ray (a wave whose lanes walk one shadow ray each): the same reciprocal and products, so a ray lands in the same bin
+// whichever of the two looks it up.
+__device__ __forceinline__ uint32_t cube_bin_of1(v3 rd, uint32_t face_base0, int cube_bins)
+{
+    const float ax = fabsf(rd.x), ay = fabsf(rd.y), az = fabsf(rd.z);
+    int k;
+    float m, a, b, sgn;
+    if (ax >= ay && ax >= az) { k = 0; m = ax; sgn = rd.x; a = rd.y; b = rd.z; }
+    else if (ay >= az) { k = 1; m = ay; sgn = rd.y; a = rd.z; b = rd.x; }
+    else { k = 2; m = az; sgn = rd.z; a = rd.x; b = rd.y; }
+    const int face = 2 * k + (sgn < 0.0f ? 1 : 0);
+    const float im = __builtin_amdgcn_rcpf(m);
+    const float u = a * im, v = b * im, half = 0.5f * (float)cube_bins;
+    int i = (int)floorf((u + 1.0f) * half);
+    int j = (int)floorf((v + 1.0f) * half);
+    i = min(max(i, 0), cube_bins - 1);
+    j = min(max(j, 0), cube_bins - 1);
+    return face_base0 + (uint32_t)face * (uint32_t)(cube_bins * cube_bins) + (uint32_t)j * cube_bins + (uint32_t)i;
 }
 
 // (TilePairRec, the ORDER_* constants and RtTraceFrame: rt_trace_frame.hpp, shared with capi/binned.cpp)
@@ -591,102 +624,139 @@ __global__ __launch_bounds__(64 * TR_WG_WAVES) __attribute__((amdgpu_waves_per_e
                     const f2 mx = { (dn.x < 0.0f) ? 0.0f : dn.x, (dn.y < 0.0f) ? 0.0f : dn.y };   // std::max(d, 0.0f)
                     v3p D = scale3p(B, mx);
                     const f2 thr = r * splat2(0.99f);              // (:313)
+                    // The rays that can still change the frame (shadow_ray_needed, rt_common.hpp: D is not exactly zero -- on a soup of random
+                    // winding half of all hits face away from the light).  A wave's walk takes max over its lanes of the steps of the rays a
+                    // lane carries, so emptying the unneeded rays' lists where they are would leave most waves with some lane that still
+                    // walks two: the needed rays are DEALT over the lanes instead -- tile A's ranked by ballot, tile B's behind them, each
+                    // written to slot `rank` of the wave's ray table {rDir, pixel}; lane l then walks slot l and, in a wave with more than
+                    // 64 rays, slot l + 64.  A lane so walks the rays of other lanes' pixels: what it finds goes to s.flag[pixel], which
+                    // the pixel's own lane reads behind the walk.  (0.99 r stays where the drains look for it: s.thr[pixel].)
+                    const bool needA = hitA && shadow_ray_needed(D.x.x, D.y.x, D.z.x), needB = hitB && shadow_ray_needed(D.x.y, D.y.y, D.z.y);
+                    const unsigned long long nmA = wballot(needA), nmB = wballot(needB);
+                    const int nrA = __popcll(nmA), nrays = nrA + __popcll(nmB);
                     TM_SEG(5)
-                    wave_lds_fence();
-                    s.thr[lane] = thr.x; s.thr[lane + 64] = thr.y;
-                    s.flag[lane] = 0; s.flag[lane + 64] = 0;
-                    // the candidates of each shadow ray: the rows of its light-cube bin, shells 0 .. shell(0.99 r) -- a row of a
-                    // later shell has near > 0.99 r (bin_shell_of is monotone in its argument) and cannot occlude (:313)
-                    uint32_t eA = 0, endA = 0, eB = 0, endB = 0;
-                    const float4 *rows4;
-                    if (brute_l) {
-                        rows4 = reinterpret_cast<const float4 *>(f.light_tab + (size_t)k * f.n);
-                        if (hitA) endA = (uint32_t)f.n;
-                        if (hitB) endB = (uint32_t)f.n;
-                    } else {
-                        rows4 = reinterpret_cast<const float4 *>(tf.light_rows);
-                        uint32_t binA, binB;
-                        cube_bin_of2(rd, (uint32_t)k * 6u * (uint32_t)(tf.cube_bins * tf.cube_bins), tf.cube_bins, &binA, &binB);
-                        // (shell of 0.99 r: bin_shell_of on wave-uniform parameters, loaded once per light)
-                        const BinFrameDesc *lf = tf.light_frames + 6 * k;
-                        const int ns = tf.light_shells;
-                        const float sd0 = lf->shell_d0, siw = lf->shell_iw;
-                        const uint32_t shA = bin_shell_of(thr.x, sd0, siw, ns), shB = bin_shell_of(thr.y, sd0, siw, ns);
-                        // the four offsets of a lane asked for together, by every lane, and waited for once: cube_bin_of2 clamps face, i and j
-                        // and bin_shell_of its shell, so the keys of a lane without a hit are valid ones; its lists are emptied by select
-                        const uint32_t keyA = binA * (uint32_t)ns, keyB = binB * (uint32_t)ns;
-                        const uint32_t oA0 = tf.light_off[keyA], oA1 = tf.light_off[keyA + shA + 1u];
-                        const uint32_t oB0 = tf.light_off[keyB], oB1 = tf.light_off[keyB + shB + 1u];
-                        eA = hitA ? oA0 : 0u; endA = hitA ? oA1 : 0u;
-                        eB = hitB ? oB0 : 0u; endB = hitB ? oB1 : 0u;
-                    }
-                    if (STATS) ncand_l += (endA - eA) + (endB - eB);
-                    // The lane walks list A, then list B.  Per step: the filter; a candidate it lets through is either a CERTAIN
-                    // occluder (sure_hit, and the whole triangle closer to the light than 0.99 r: nothing left to compute, the ray
-                    // is done) or goes to the exact stage's queue.
-                    // The walk's state lives in plain integer and float registers and every step is straight-line code: what a lane
-                    // is doing follows from comparisons made afresh each step (active: e < end; list B still to come: on list A and
-                    // eB < endB), the filter and the certain-occluder test are evaluated for every lane, and the next row is loaded by
-                    // every lane (row 0 where a lane has none to fetch).  Written with booleans carried around the loop and the
-                    // tests nested in ifs, the compiler kept each boolean as a scalar lane mask and merged it with exec at every
-                    // divergent join: ~60 scalar instructions per step beside ~30 vector ones -- and at the four waves per SIMD this
-                    // kernel runs at, a scalar instruction costs what a vector one costs (profiles/r03_issue_model.txt).
-                    const uint32_t *row_tri = brute_l ? nullptr : tf.light_tri;
-                    const bool firstA = eA < endA;
-                    uint32_t e = firstA ? eA : eB, end = firstA ? endA : endB, pix = firstA ? (uint32_t)lane : (uint32_t)lane + 64u;
-                    v3 crd = firstA ? half0(rd) : half1(rd);
-                    float cthr = firstA ? thr.x : thr.y;
-                    uint32_t occ = 0u;                               // bit 0 / 1: the lane itself found a certain occluder of pixel A / B
-                    float4 c0, c1, c2;
-                    { const float4 *src = rows4 + (size_t)(e < end ? e : 0u) * 3; c0 = src[0]; c1 = src[1]; c2 = src[2]; }
-                    TM_SEG(6)
-                    const int not_brute = brute_l ? 0 : 1;
-                    for (;;) {
-                        const bool act = e < end;
-                        const unsigned long long am = wballot(act);
-                        if (!am) break;
-                        if (STATS) { nsteps_s++; ntests += (unsigned)__popcll(am); }
-                        const TestDots td = test_dots(c0, c1, c2, crd);          // negD = rDir (:310, :229)
-                        // a candidate none of whose points is closer to the light than 0.99 r cannot occlude (:313)
-                        const int pass = (int)act & (int)!(c1.w > cthr) & (int)maybe_hit(td);
-                        const int sure = pass & not_brute & (int)(c2.w < cthr) & (int)sure_hit(td, c0.w);
-                        const int queue = pass & (sure ^ 1);
-                        const unsigned long long m = wballot(queue != 0);
-                        int done = sure;                                          // this list is settled for the lane
-                        if (m) {
-                            if (qn + __popcll(m) > TR_QUEUE) { tr_drain<true>(s, lane, qn, geo4, L, row_tri); qn = 0; if (STATS) ndrains++; }   // (rare: no room for this step)
-                            if (queue) {
-                                const int at = qn + wave_rank(m);
-                                s.q[at] = make_float4(td.den, td.pu, td.qv, c0.w);
-                                s.qa[at] = make_uint2(pix, e);                   // the candidate's row
-                            }
-                            qn += __popcll(m);
-                            if (qn >= TR_DRAIN) {
-                                TM_SEG(7)
-                                do { tr_drain_full<true>(s, lane, qn, geo4, L, row_tri); if (STATS) ndrains++; } while (qn >= TR_DRAIN);
-                                TM_SEG(8)
-                                done |= (int)act & (int)(s.flag[pix] != 0);     // found occluded: the rest of this list is moot
+                    if (nrays) {                                   // (a wave none of whose hits faces this light goes straight to the sum)
+                        wave_lds_fence();
+                        s.thr[lane] = thr.x; s.thr[lane + 64] = thr.y;
+                        s.flag[lane] = 0; s.flag[lane + 64] = 0;
+                        if (needA) s.ray[wave_rank(nmA)] = make_float4(rd.x.x, rd.y.x, rd.z.x, __uint_as_float((uint32_t)lane));
+                        if (needB) s.ray[nrA + wave_rank(nmB)] = make_float4(rd.x.y, rd.y.y, rd.z.y, __uint_as_float((uint32_t)lane + 64u));
+                        wave_lds_fence();
+                        // a lane without a ray of its own reads slot 0 (there is one: nrays > 0), so that everything derived below is valid,
+                        // and its list is emptied by select
+                        const bool two = nrays > 64;               // wave-uniform: some lane walks a second ray
+                        const bool has0 = lane < nrays, has1 = lane + 64 < nrays;
+                        const float4 ry0 = s.ray[has0 ? lane : 0];
+                        float4 ry1 = ry0;
+                        if (two) ry1 = s.ray[has1 ? lane + 64 : 0];
+                        const v3 rd0 = V3(ry0.x, ry0.y, ry0.z), rd1 = V3(ry1.x, ry1.y, ry1.z);
+                        const uint32_t pix0 = __float_as_uint(ry0.w), pix1 = __float_as_uint(ry1.w);
+                        const float thr0 = s.thr[pix0], thr1 = s.thr[pix1];
+                        // the candidates of each shadow ray: the rows of its light-cube bin, shells 0 .. shell(0.99 r) -- a row of a
+                        // later shell has near > 0.99 r (bin_shell_of is monotone in its argument) and cannot occlude (:313)
+                        uint32_t e0 = 0, end0 = 0, e1 = 0, end1 = 0;
+                        const float4 *rows4;
+                        if (brute_l) {
+                            rows4 = reinterpret_cast<const float4 *>(f.light_tab + (size_t)k * f.n);
+                            if (has0) end0 = (uint32_t)f.n;
+                            if (has1) end1 = (uint32_t)f.n;
+                        } else {
+                            rows4 = reinterpret_cast<const float4 *>(tf.light_rows);
+                            // (shell of 0.99 r: bin_shell_of on wave-uniform parameters, loaded once per light)
+                            const uint32_t face0 = (uint32_t)k * 6u * (uint32_t)(tf.cube_bins * tf.cube_bins);
+                            const BinFrameDesc *lf = tf.light_frames + 6 * k;
+                            const int ns = tf.light_shells;
+                            const float sd0 = lf->shell_d0, siw = lf->shell_iw;
+                            // the offsets of a lane's rays asked for together, by every lane, and waited for once: the bin lookups clamp
+                            // face, i and j and bin_shell_of its shell, so the keys are valid ones whatever the ray.  The second ray's
+                            // lookups and loads only in a wave that has second rays.
+                            if (two) {
+                                uint32_t bin0, bin1;
+                                cube_bin_of2(join3(rd0, rd1), face0, tf.cube_bins, &bin0, &bin1);
+                                const uint32_t sh0 = bin_shell_of(thr0, sd0, siw, ns), sh1 = bin_shell_of(thr1, sd0, siw, ns);
+                                const uint32_t key0 = bin0 * (uint32_t)ns, key1 = bin1 * (uint32_t)ns;
+                                const uint32_t o00 = tf.light_off[key0], o01 = tf.light_off[key0 + sh0 + 1u];
+                                const uint32_t o10 = tf.light_off[key1], o11 = tf.light_off[key1 + sh1 + 1u];
+                                e0 = o00; end0 = o01;              // (more than 64 rays: every lane has a first one)
+                                e1 = has1 ? o10 : 0u; end1 = has1 ? o11 : 0u;
+                            } else {
+                                const uint32_t key0 = cube_bin_of1(rd0, face0, tf.cube_bins) * (uint32_t)ns;
+                                const uint32_t sh0 = bin_shell_of(thr0, sd0, siw, ns);
+                                const uint32_t o00 = tf.light_off[key0], o01 = tf.light_off[key0 + sh0 + 1u];
+                                e0 = has0 ? o00 : 0u; end0 = has0 ? o01 : 0u;
                             }
                         }
-                        occ |= sure ? (pix < 64u ? 1u : 2u) : 0u;
-                        // on: the next row of this list, or -- list done or ray occluded -- the first of list B
-                        const int cont = (int)act & (done ^ 1) & (int)(e + 1u < end);
-                        const int sw = (int)act & (cont ^ 1) & (int)(pix < 64u) & (int)(eB < endB);
-                        crd = sw ? half1(rd) : crd;
-                        cthr = sw ? thr.y : cthr;
-                        pix = sw ? (uint32_t)lane + 64u : pix;
-                        e = cont ? e + 1u : (sw ? eB : end);                     // (neither: e == end, the lane is done)
-                        end = sw ? endB : end;
-                        const float4 *src = rows4 + (size_t)((cont | sw) ? e : 0u) * 3;
-                        c0 = src[0]; c1 = src[1]; c2 = src[2];
+                        if (STATS) ncand_l += (end0 - e0) + (end1 - e1);
+                        // The lane walks its first ray's list, then its second's.  Per step: the filter; a candidate it lets through is
+                        // either a CERTAIN occluder (sure_hit, and the whole triangle closer to the light than 0.99 r: nothing left to
+                        // compute, the ray is done) or goes to the exact stage's queue.
+                        // The walk's state lives in plain integer and float registers and every step is straight-line code: what a lane
+                        // is doing follows from comparisons made afresh each step (active: e < end; a second list still to come:
+                        // e1 < end1, which the switch to it empties), the filter and the certain-occluder test are evaluated for every
+                        // lane, and the next row is loaded by every lane (row 0 where a lane has none to fetch).  Written with booleans carried around the loop and the
+                        // tests nested in ifs, the compiler kept each boolean as a scalar lane mask and merged it with exec at every
+                        // divergent join: ~60 scalar instructions per step beside ~30 vector ones -- and at the four waves per SIMD this
+                        // kernel runs at, a scalar instruction costs what a vector one costs (profiles/r03_issue_model.txt).
+                        const uint32_t *row_tri = brute_l ? nullptr : tf.light_tri;
+                        const bool first0 = e0 < end0;
+                        uint32_t e = first0 ? e0 : e1, end = first0 ? end0 : end1, pix = first0 ? pix0 : pix1;
+                        v3 crd = V3(first0 ? rd0.x : rd1.x, first0 ? rd0.y : rd1.y, first0 ? rd0.z : rd1.z);
+                        float cthr = first0 ? thr0 : thr1;
+                        end1 = first0 ? end1 : 0u;                   // (the walk starts on the second list: no switch to it)
+                        float4 c0, c1, c2;
+                        { const float4 *src = rows4 + (size_t)(e < end ? e : 0u) * 3; c0 = src[0]; c1 = src[1]; c2 = src[2]; }
+                        TM_SEG(6)
+                        const int not_brute = brute_l ? 0 : 1;
+                        for (;;) {
+                            const bool act = e < end;
+                            const unsigned long long am = wballot(act);
+                            if (!am) break;
+                            if (STATS) { nsteps_s++; ntests += (unsigned)__popcll(am); }
+                            const TestDots td = test_dots(c0, c1, c2, crd);          // negD = rDir (:310, :229)
+                            // a candidate none of whose points is closer to the light than 0.99 r cannot occlude (:313)
+                            const int pass = (int)act & (int)!(c1.w > cthr) & (int)maybe_hit(td);
+                            const int sure = pass & not_brute & (int)(c2.w < cthr) & (int)sure_hit(td, c0.w);
+                            const int queue = pass & (sure ^ 1);
+                            const unsigned long long m = wballot(queue != 0);
+                            int done = sure;                                          // this list is settled for the lane
+                            // a certain occluder: the pixel's flag, the byte a drain's accepted pair sets (the pixel is some other lane's, so a
+                            // bit in a register of this one would not reach it); every other lane stores to a byte nobody reads -- no branch
+                            *(sure ? &s.flag[pix] : &s.sink) = 1;
+                            if (m) {
+                                if (qn + __popcll(m) > TR_QUEUE) { tr_drain<true>(s, lane, qn, geo4, L, row_tri); qn = 0; if (STATS) ndrains++; }   // (rare: no room for this step)
+                                if (queue) {
+                                    const int at = qn + wave_rank(m);
+                                    s.q[at] = make_float4(td.den, td.pu, td.qv, c0.w);
+                                    s.qa[at] = make_uint2(pix, e);                   // the candidate's row
+                                }
+                                qn += __popcll(m);
+                                if (qn >= TR_DRAIN) {
+                                    TM_SEG(7)
+                                    do { tr_drain_full<true>(s, lane, qn, geo4, L, row_tri); if (STATS) ndrains++; } while (qn >= TR_DRAIN);
+                                    TM_SEG(8)
+                                    done |= (int)act & (int)(s.flag[pix] != 0);     // found occluded: the rest of this list is moot
+                                }
+                            }
+                            // on: the next row of this list, or -- list done or ray occluded -- the first of the second list
+                            const int cont = (int)act & (done ^ 1) & (int)(e + 1u < end);
+                            const int sw = (int)act & (cont ^ 1) & (int)(e1 < end1);
+                            crd = V3(sw ? rd1.x : crd.x, sw ? rd1.y : crd.y, sw ? rd1.z : crd.z);
+                            cthr = sw ? thr1 : cthr;
+                            pix = sw ? pix1 : pix;
+                            e = cont ? e + 1u : (sw ? e1 : end);                     // (neither: e == end, the lane is done)
+                            end = sw ? end1 : end;
+                            end1 = sw ? 0u : end1;
+                            const float4 *src = rows4 + (size_t)((cont | sw) ? e : 0u) * 3;
+                            c0 = src[0]; c1 = src[1]; c2 = src[2];
+                        }
+                        TM_SEG(7)
+                        if (qn) { tr_drain<true>(s, lane, qn, geo4, L, row_tri); qn = 0; if (STATS) ndrains++; }
+                        TM_SEG(8)
+                        // occluded (:313-314); any-hit is exact.  Each lane back at its own two pixels, whoever walked their rays.
+                        wave_lds_fence();
+                        if (s.flag[lane] != 0) { D.x.x = 0.0f; D.y.x = 0.0f; D.z.x = 0.0f; }
+                        if (s.flag[lane + 64] != 0) { D.x.y = 0.0f; D.y.y = 0.0f; D.z.y = 0.0f; }
                     }
-                    TM_SEG(7)
-                    if (qn) { tr_drain<true>(s, lane, qn, geo4, L, row_tri); qn = 0; if (STATS) ndrains++; }
-                    TM_SEG(8)
-                    const bool occA = (occ & 1u) != 0u, occB = (occ & 2u) != 0u;
-                    // occluded (:313-314); any-hit is exact
-                    if (occA || s.flag[lane] != 0) { D.x.x = 0.0f; D.y.x = 0.0f; D.z.x = 0.0f; }
-                    if (occB || s.flag[lane + 64] != 0) { D.x.y = 0.0f; D.y.y = 0.0f; D.z.y = 0.0f; }
                     result = add3p(result, D);                     // (:319)
                     if (one_sample || --samples_left == 0) {       // (:322) after each light's samples
                         result2 = add3p(result2, result);
@@ -717,10 +787,14 @@ __global__ __launch_bounds__(64 * TR_WG_WAVES) __attribute__((amdgpu_waves_per_e
         if (STATS) ncand += wave_sum(ncand_l);
         const unsigned shard = blockIdx.x % HIT_SHARDS;
 #ifdef MIRT_TR_TIMING
-        // (experiments) words 3..12 carry the segments' sums instead of the step counts, word 13 the longest lifetime
+        // (experiments) words 3..12 carry the segments' sums instead of the step counts, word 13 the longest lifetime.  mirt_get_stats
+        // reports words 3..5 (steps_primary, steps_shadow, drains): -DMIRT_TR_TIMING_FIRST=5 puts segments 5, 6 and 7 there
+#ifndef MIRT_TR_TIMING_FIRST
+#define MIRT_TR_TIMING_FIRST 0
+#endif
         TM_SEG(9)
         if (lane == 0) {
-            for (int i = 0; i < 10; i++) atomicAdd(f.hit_count + (size_t)shard * HIT_SHARD_STRIDE + 3 + i, (unsigned long long)tm_seg[i]);
+            for (int i = 0; i < 10; i++) atomicAdd(f.hit_count + (size_t)shard * HIT_SHARD_STRIDE + 3 + (i + 10 - MIRT_TR_TIMING_FIRST) % 10, (unsigned long long)tm_seg[i]);
             atomicMax(f.hit_count + (size_t)shard * HIT_SHARD_STRIDE + 13, (unsigned long long)(tm_last - tm0));
         }
         const unsigned v = lane == 0 ? ntests : ncand;

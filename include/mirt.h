@@ -73,9 +73,12 @@ typedef enum mirt_rt_mode {
 /* Counters of the last render call (ray accounting follows SURVEY section 8(d)). */
 typedef struct mirt_stats {
     uint64_t primary_rays;        /* width * rows rendered                                          */
-    uint64_t shadow_rays;         /* nlights * (pixels whose primary ray hit)                       */
+    uint64_t shadow_rays;         /* nlights * (pixels whose primary ray hit): DirectLight's calls, in every mode -- the binned
+                                     kernel settles a ray whose light term is exactly zero (a face turned away from the light)
+                                     without walking it, as it always has a ray ended by a certain occluder; both count     */
     uint64_t tests;               /* ray-triangle tests actually executed (0 if not counted: the binned kernel keeps this and
-                                     the four counts below for frames rendered with mirt_set_profiling(1) only)          */
+                                     the four counts below for frames rendered with mirt_set_profiling(1) only; a shadow ray
+                                     that is not walked adds nothing to them)                                               */
     float gpu_ms;                 /* hipEvent time of the call's device work; 0 unless profiling is on   */
     float kernel_ms[8];           /* per-kernel time of the call when profiling is on (see below)    */
     int32_t mode_used;            /* mirt_rt_mode actually used                                      */
