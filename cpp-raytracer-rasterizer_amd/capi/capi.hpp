@@ -17,6 +17,7 @@
 #include "cube_plan.hpp"
 #include "pass_plan.hpp"
 #include "object_plan.hpp"
+#include "dof_plan.hpp"
 #include "env.hpp"
 
 #include <cstdarg>
@@ -574,8 +575,7 @@ int render_with_dof(const mirt_view *view, const mirt_light *lights, int nlights
     // (rt_enqueue / raster_enqueue only see the library-owned planes)
     if ((rc = check_frame_args(view, lights, nlights, indirect, d_xrgb, pitch_bytes, false, y0, y1))) return rc;
     const int W = view->width, H = view->height, K = g.dof_k;
-    const int zlo = (int)std::ceil((float)K / -2.0f), zhi = (int)std::ceil((float)K / 2.0f);
-    const int reach = std::max(-zlo, zhi - 1) + 1;           // +1: a tap column outside the row wraps into the next row
+    const int reach = dof_halo_rows(K, W);                   // (a tap column outside the row wraps into the rows beyond: dof_plan.hpp)
     const int ry0 = std::max(0, y0 - reach), ry1 = std::min(H, y1 + reach);
     // the stream call_begin() will give this frame (it is self-contained: its planes are this stream's own)
     DofPlanes &D = g.streams[next_si()].dof;

@@ -136,7 +136,7 @@ __device__ __forceinline__ float dof_fetch(const DofFrame &f, long long flat_px,
 {
     if (flat_px < 0 || flat_px >= (long long)f.W * f.H) return 0.0f;
     const int row = (int)(flat_px / f.W);
-    if (row < f.ry0 || row >= f.ry1) return 0.0f;     // cannot happen for a halo of reach rows; kept as a guard
+    if (row < f.ry0 || row >= f.ry1) return 0.0f;     // a tap beyond the halo: none with dof_halo_rows(K, W) rows of it (capi/dof_plan.hpp)
     return f.rgb[3 * flat_px + ch];
 }
 
