@@ -232,8 +232,9 @@ struct DofPlanes {
     void release();
 };
 
-// The queries that walk a cube and keep statistics: DirectLight (mirt_get_query_stats) and origin fans (mirt_get_fan_stats).
-enum { QUERY_DIRECT_LIGHT = 0, QUERY_FAN = 1, QUERY_KINDS = 2 };
+// The queries that walk a cube and keep statistics: DirectLight (mirt_get_query_stats), origin fans (mirt_get_fan_stats) and
+// occlusion queries (mirt_get_occlusion_stats).
+enum { QUERY_DIRECT_LIGHT = 0, QUERY_FAN = 1, QUERY_OCCLUDED = 2, QUERY_KINDS = 3 };
 // The last query of a kind: how it was answered, the stream it ran on and where its kernel's counters are (device; profiling on,
 // binned -- read once, query_get_stats).
 struct QueryStats {
@@ -267,9 +268,10 @@ struct QueryRows {
     uint32_t *d_max = nullptr;                   // QMAX_WORDS words: scene-wide maxima
     uint64_t version = 0;                        // scene_version the rows were built for (0 = none)
     hipEvent_t ev_built = nullptr;
-    // staging of the host-buffer entry points (mirt_intersect, mirt_direct_light)
+    // staging of the host-buffer entry points (mirt_intersect, mirt_direct_light, mirt_occluded)
     void *d_rays = nullptr, *d_hits = nullptr, *d_rgb = nullptr, *d_dirs = nullptr, *d_origin_of = nullptr;
-    size_t cap = 0;                              // rays / records / directions / origin indices each holds
+    void *d_limits = nullptr, *d_occluded = nullptr;
+    size_t cap = 0;                              // rays / records / directions / origin indices / limits / bytes each holds
     // The light cube of the DirectLight queries: a LightCache like the frame path's g.lc, keyed alike (scene version + the light
     // positions in use, and the grid -- so a new scene forgets it), kept across calls, shared by the streams and ordered among
     // them by light_cache_ensure's events.  A query whose lights are the ones the frame path's valid cube holds reads g.lc and
@@ -364,7 +366,7 @@ struct Ctx {
     LightCache lc;
     QueryRows qrows;
     int query_mode = MIRT_QUERY_AUTO;            // mirt_set_query_mode
-    QueryStats qstats[QUERY_KINDS];              // the last DirectLight query and the last origin fan
+    QueryStats qstats[QUERY_KINDS];              // the last DirectLight query, the last origin fan, the last occlusion query
     unsigned long long *d_hits = nullptr;        // the hit-counter buffer of the current ray-traced frame (one of its stream's d_hits)
     bool scene_finite = true;                    // all vertex coordinates below MIRT_SAFE_MAG
     uint64_t scene_version = 0;                  // bumped whenever the triangles change
@@ -531,6 +533,12 @@ int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, vo
 int query_intersect_from_host(const float *origin, const float *dirs3, int nrays, mirt_hit *hits);
 int query_intersect_fans(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, void *d_hits);
 int query_intersect_fans_host(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, mirt_hit *hits);
+int query_occluded(const void *d_rays, int nrays, const void *d_max_distance, void *d_occluded);
+int query_occluded_host(const mirt_ray *rays, int nrays, const float *max_distance, uint8_t *occluded);
+int query_occluded_fans(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, const void *d_max_distance,
+                        void *d_occluded);
+int query_occluded_fans_host(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, const float *max_distance,
+                             uint8_t *occluded);
 
 // ---- rasteriser (raster.cpp) ----
 int raster_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect,

@@ -5,6 +5,7 @@
 // statistics of the last render call alone (DirectLight has its own: mirt_set_query_mode, mirt_get_query_stats, defined here).
 // Many rays from ONE origin (mirt_intersect_from*) walk a cube of the same kind around that origin, kept apart from DirectLight's;
 // rays from SEVERAL origins in one call (mirt_intersect_fans*) walk cubes that hold up to MIRT_MAX_LIGHTS of the origins each.
+// Occlusion queries (mirt_occluded*, mirt_occluded_fans*) answer one byte per ray through the same rows and the same cubes.
 #include "capi.hpp"
 
 namespace mirt {
@@ -416,8 +417,9 @@ static void fans_pass_origins(const float *origins3, const FanPass &p, float *po
 }
 
 // By definition the call is mirt_intersect on the expanded rays: they are written out on the device (k_query_fans_expand) into
-// the stream's query scratch and go through query_intersect's kernels, whose per-ray filter safety and choice of kernel come along.
-static int fans_brute(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, void *d_hits)
+// the stream's query scratch (fans_expand) and go through query_intersect's kernels, whose per-ray filter safety and choice of
+// kernel come along.
+static int fans_expand(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays)
 {
     int rc;
     QueryScratch &S = g.cur().query;
@@ -433,7 +435,35 @@ static int fans_brute(const float *origins3, int norigins, const void *d_origin_
     x.rays = S.d_fan_rays;
     hipLaunchKernelGGL(k_query_fans_expand, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, g.stream, x);
     HIP_TRY(hipGetLastError());
-    return intersect_launch(S.d_fan_rays, nrays, d_hits);
+    return MIRT_OK;
+}
+static int fans_brute(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, void *d_hits)
+{
+    int rc;
+    if ((rc = fans_expand(origins3, norigins, d_origin_of, d_dirs3, nrays))) return rc;
+    return intersect_launch(g.cur().query.d_fan_rays, nrays, d_hits);
+}
+
+// Binned or brute for a many-origin call, and the pass plan of a binned one.  As the single fan decides it: never what the frame
+// path would not bin, whatever the mode -- and the call is one: an origin outside the filter's range (NaN included) among ordinary
+// ones sends all of it to the brute-force kernels.  `held`: every pass's cube, that is.
+static bool fans_binned(const float *origins3, int norigins, int nrays, std::initializer_list<CubeChoice> foreign, std::vector<FanPass> *plan)
+{
+    const bool may_bin = starts_safe(origins3, norigins) && fan_pass_plan(norigins, g.n, cube_bins_override(), plan);
+    float po[(1 + MIRT_MAX_LIGHTS) * 3];
+    bool held = may_bin;
+    for (size_t i = 0; held && i < plan->size(); i++) {
+        fans_pass_origins(origins3, (*plan)[i], po);
+        held = held_cube(foreign, g.qrows.fans, po, (*plan)[i].count, (*plan)[i].cube_bins).cube != nullptr;
+    }
+    return query_bins(may_bin, g.query_mode, held, auto_bins_fans(nrays));
+}
+
+// What every pass of a call read, folded over the passes: 1 as soon as a pass built; else what every pass read when that is one
+// kind of cube; else 2: all were held.
+static int fold_cube_source(size_t pass, int so_far, int source)
+{
+    return pass == 0 ? source : (so_far == 1 || source == 1 ? 1 : (so_far == source ? source : 2));
 }
 
 int query_intersect_fans(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, void *d_hits)
@@ -443,18 +473,10 @@ int query_intersect_fans(const float *origins3, int norigins, const void *d_orig
     if (nrays == 0) return MIRT_OK;
     if ((rc = need_scene())) return rc;
 
-    // Binned or brute, as the single fan decides it: never what the frame path would not bin, whatever the mode -- and the call is
-    // one: an origin outside the filter's range (NaN included) among ordinary ones sends all of it to the brute-force kernels.
     std::vector<FanPass> plan;
-    const bool may_bin = starts_safe(origins3, norigins) && fan_pass_plan(norigins, g.n, cube_bins_override(), &plan);
     const std::initializer_list<CubeChoice> foreign = { { &g.lc, 3 }, { &g.qrows.cube, 4 } };
     float po[(1 + MIRT_MAX_LIGHTS) * 3];
-    bool held = may_bin;                                                     // (every pass's cube, that is)
-    for (size_t i = 0; held && i < plan.size(); i++) {
-        fans_pass_origins(origins3, plan[i], po);
-        held = held_cube(foreign, g.qrows.fans, po, plan[i].count, plan[i].cube_bins).cube != nullptr;
-    }
-    const bool binned = query_bins(may_bin, g.query_mode, held, auto_bins_fans(nrays));
+    const bool binned = fans_binned(origins3, norigins, nrays, foreign, &plan);
 
     stream_begin();
     QueryStats &stats = stats_begin(QUERY_FAN, binned);
@@ -472,8 +494,7 @@ int query_intersect_fans(const float *origins3, int norigins, const void *d_orig
         fans_pass_origins(origins3, p, po);
         CubeChoice c;                                                        // (a build: behind the previous pass's kernel on this stream)
         if ((rc = walk_cube(foreign, g.qrows.fans, po, p.count, p.cube_bins, &c))) return rc;
-        // 1 as soon as a pass built; else what every pass read when that is one kind of cube; else 2: all were held
-        source_all = i == 0 ? c.source : (source_all == 1 || c.source == 1 ? 1 : (source_all == c.source ? c.source : 2));
+        source_all = fold_cube_source(i, source_all, c.source);
         stats_cube(stats, *c.cube, source_all);
         q.f.tab = c.cube->d_light_tab;
         q.f.cube = cube_view(*c.cube);
@@ -481,6 +502,102 @@ int query_intersect_fans(const float *origins3, int norigins, const void *d_orig
         q.first = p.first;
         q.count = p.count;
         if ((rc = launch_walk(k_query_fans_binned<false>, k_query_fans_binned<true>, q.f.stats != nullptr, grid, q))) return rc;
+    }
+    return MIRT_OK;
+}
+
+// ---- occlusion queries: any-hit rays (mirt_occluded*) ---------------------------------------------------------------------------
+//
+// One byte per ray: whether some accepted triangle is nearer than the ray's limit.  Arbitrary rays sweep the scene's rows
+// (k_query_occluded*, the kernel chosen as intersect_launch chooses); rays that share origins walk the many-origin fans' cubes
+// (k_query_occluded_fans_binned) -- the same pass plan, the same kept cube g.qrows.fans and the same foreign cubes as
+// mirt_intersect_fans*, so a cube either call built serves the other.  The statistics are a kind of their own (QUERY_OCCLUDED):
+// every call of either form begins them afresh, and no call touches the fans' or DirectLight's.
+
+// The brute-force kernels for nrays > 0 rays on the current stream.
+static int occluded_launch(const void *d_rays, int nrays, const void *d_limit, void *d_occluded)
+{
+    int rc;
+    if ((rc = query_rows())) return rc;
+    QueryOccludedFrame o;
+    memset(&o, 0, sizeof o);
+    o.q.rows = g.qrows.d_rows;
+    o.q.n = g.n;
+    o.q.scene_max = g.qrows.d_max;
+    o.q.scene_finite = g.scene_finite ? 1 : 0;
+    o.q.rays = static_cast<const float *>(d_rays);
+    o.q.nrays = nrays;
+    o.limit = static_cast<const float *>(d_limit);
+    o.occluded = static_cast<uint8_t *>(d_occluded);
+    if ((long)nrays <= query_wave_rays()) {
+        hipLaunchKernelGGL(k_query_occluded_wave, dim3((unsigned)((nrays + 3) / 4)), dim3(256), 0, g.stream, o);
+    } else {
+        hipLaunchKernelGGL(k_query_occluded<QUERY_P>, dim3((unsigned)((nrays + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), sweep_lds_bytes(), g.stream, o);
+    }
+    HIP_TRY(hipGetLastError());
+    return MIRT_OK;
+}
+
+int query_occluded(const void *d_rays, int nrays, const void *d_max_distance, void *d_occluded)
+{
+    int rc;
+    if ((rc = check_query_args(d_rays, nrays, d_occluded, "ray"))) return rc;
+    if (nrays == 0) return MIRT_OK;
+    if ((rc = need_scene())) return rc;
+    stream_begin();
+    stats_begin(QUERY_OCCLUDED, false);
+    return occluded_launch(d_rays, nrays, d_max_distance, d_occluded);
+}
+
+// AUTO for the many-origin form is auto_bins_fans' rule unchanged (fans_binned).  The rule was measured for closest hits; the
+// sweep of this call (tools/ray_query_bench.py --steps occluded, profiles/ray_query_bench.txt, section `occluded`; K = 1, 4, 32
+// origins, 1 .. 2^20 rays, 2000 and 100 000 triangles, with and without limits) puts the crossing in the same place: brute force
+// ahead of binning with the builds in all 42 cells of at most 4096 rays, binning with the builds ahead beyond except at 2000
+// triangles and 4 origins (16384 / 65536 rays: 0.50 / 0.53 against 0.47 / 0.49 ms), the cell mirt_intersect_fans* loses too.
+int query_occluded_fans(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, const void *d_max_distance,
+                        void *d_occluded)
+{
+    int rc;
+    if ((rc = check_fans_args(origins3, norigins, d_origin_of, d_dirs3, nrays, d_occluded))) return rc;
+    if (nrays == 0) return MIRT_OK;
+    if ((rc = need_scene())) return rc;
+
+    std::vector<FanPass> plan;
+    const std::initializer_list<CubeChoice> foreign = { { &g.lc, 3 }, { &g.qrows.cube, 4 } };
+    const bool binned = fans_binned(origins3, norigins, nrays, foreign, &plan);
+
+    stream_begin();
+    QueryStats &stats = stats_begin(QUERY_OCCLUDED, binned);
+    if (!binned) {
+        // mirt_occluded on the expanded rays; a ray whose index lies outside the list becomes one no triangle accepts: its byte is 0
+        if ((rc = fans_expand(origins3, norigins, d_origin_of, d_dirs3, nrays))) return rc;
+        return occluded_launch(g.cur().query.d_fan_rays, nrays, d_max_distance, d_occluded);
+    }
+
+    QueryOccludedFansFrame q;
+    memset(&q, 0, sizeof q);
+    q.f.f = fan_frame(d_dirs3, nrays, nullptr);
+    q.f.origin_of = static_cast<const int32_t *>(d_origin_of);
+    q.norigins = norigins;
+    q.limit = static_cast<const float *>(d_max_distance);
+    q.occluded = static_cast<uint8_t *>(d_occluded);
+    if ((rc = stats_arm(QUERY_OCCLUDED, &q.f.f.stats))) return rc;    // (once: the passes' kernels add up in the same words)
+    const dim3 grid((unsigned)((nrays + 255) / 256));
+    float po[(1 + MIRT_MAX_LIGHTS) * 3];
+    int source_all = 0;
+    for (size_t i = 0; i < plan.size(); i++) {
+        const FanPass &p = plan[i];                                          // (plan[0].first == 0: the pass that writes the strays' 0)
+        fans_pass_origins(origins3, p, po);
+        CubeChoice c;
+        if ((rc = walk_cube(foreign, g.qrows.fans, po, p.count, p.cube_bins, &c))) return rc;
+        source_all = fold_cube_source(i, source_all, c.source);
+        stats_cube(stats, *c.cube, source_all);
+        q.f.f.tab = c.cube->d_light_tab;
+        q.f.f.cube = cube_view(*c.cube);
+        q.f.origins = c.cube->d_origins;
+        q.f.first = p.first;
+        q.f.count = p.count;
+        if ((rc = launch_walk(k_query_occluded_fans_binned<false>, k_query_occluded_fans_binned<true>, q.f.f.stats != nullptr, grid, q))) return rc;
     }
     return MIRT_OK;
 }
@@ -508,6 +625,8 @@ static int query_staging(size_t count)
     if ((rc = dev_realloc_bytes(&Q.d_rgb, count * 3 * sizeof(float)))) return rc;
     if ((rc = dev_realloc_bytes(&Q.d_dirs, count * 3 * sizeof(float)))) return rc;
     if ((rc = dev_realloc_bytes(&Q.d_origin_of, count * sizeof(int32_t)))) return rc;
+    if ((rc = dev_realloc_bytes(&Q.d_limits, count * sizeof(float)))) return rc;
+    if ((rc = dev_realloc_bytes(&Q.d_occluded, count))) return rc;
     Q.cap = count;
     return MIRT_OK;
 }
@@ -563,7 +682,7 @@ int query_intersect_from_host(const float *origin, const float *dirs3, int nrays
 
 // The host form looks at every index before anything touches the device; the device form cannot (its kernels leave such a ray's
 // record unwritten).
-static int check_fans_host_args(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, const mirt_hit *hits)
+static int check_fans_host_args(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, const void *hits)
 {
     int rc;
     if ((rc = check_fans_args(origins3, norigins, origin_of, dirs3, nrays, hits))) return rc;
@@ -584,8 +703,37 @@ int query_intersect_fans_host(const float *origins3, int norigins, const int32_t
                             [&] { return query_intersect_fans(origins3, norigins, origin_of ? Q.d_origin_of : nullptr, Q.d_dirs, nrays, Q.d_hits); });
 }
 
+// (a NULL max_distance stays NULL: every limit is +inf)
+int query_occluded_host(const mirt_ray *rays, int nrays, const float *max_distance, uint8_t *occluded)
+{
+    QueryRows &Q = g.qrows;
+    const HostArray a[] = { { (void *)rays, &QueryRows::d_rays, (size_t)nrays * sizeof(mirt_ray), true, false },
+                            { (void *)max_distance, &QueryRows::d_limits, (size_t)nrays * sizeof(float), max_distance != nullptr, false },
+                            { occluded, &QueryRows::d_occluded, (size_t)nrays, false, true } };
+    return with_host_arrays(check_query_args(rays, nrays, occluded, "ray"), nrays, a,
+                            [&] { return query_occluded(Q.d_rays, nrays, max_distance ? Q.d_limits : nullptr, Q.d_occluded); });
+}
+
+int query_occluded_fans_host(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, const float *max_distance,
+                             uint8_t *occluded)
+{
+    QueryRows &Q = g.qrows;
+    const HostArray a[] = { { (void *)dirs3, &QueryRows::d_dirs, (size_t)nrays * 3 * sizeof(float), true, false },
+                            { (void *)origin_of, &QueryRows::d_origin_of, (size_t)nrays * sizeof(int32_t), origin_of != nullptr, false },
+                            { (void *)max_distance, &QueryRows::d_limits, (size_t)nrays * sizeof(float), max_distance != nullptr, false },
+                            { occluded, &QueryRows::d_occluded, (size_t)nrays, false, true } };
+    return with_host_arrays(check_fans_host_args(origins3, norigins, origin_of, dirs3, nrays, occluded), nrays, a, [&] {
+        return query_occluded_fans(origins3, norigins, origin_of ? Q.d_origin_of : nullptr, Q.d_dirs, nrays, max_distance ? Q.d_limits : nullptr, Q.d_occluded);
+    });
+}
+
 }  // namespace mirt
 
+extern "C" int mirt_occluded(const mirt_ray *rays, int nrays, const float *max_distance, uint8_t *occluded) { return mirt::query_occluded_host(rays, nrays, max_distance, occluded); }
+extern "C" int mirt_occluded_device(const void *d_rays, int nrays, const void *d_max_distance, void *d_occluded) { return mirt::query_occluded(d_rays, nrays, d_max_distance, d_occluded); }
+extern "C" int mirt_occluded_fans(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, const float *max_distance, uint8_t *occluded) { return mirt::query_occluded_fans_host(origins3, norigins, origin_of, dirs3, nrays, max_distance, occluded); }
+extern "C" int mirt_occluded_fans_device(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, const void *d_max_distance, void *d_occluded) { return mirt::query_occluded_fans(origins3, norigins, d_origin_of, d_dirs3, nrays, d_max_distance, d_occluded); }
+extern "C" int mirt_get_occlusion_stats(mirt_query_stats *out) { return mirt::query_get_stats(mirt::QUERY_OCCLUDED, out); }
 extern "C" int mirt_intersect_fans(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, mirt_hit *hits) { return mirt::query_intersect_fans_host(origins3, norigins, origin_of, dirs3, nrays, hits); }
 extern "C" int mirt_intersect_fans_device(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, void *d_hits) { return mirt::query_intersect_fans(origins3, norigins, d_origin_of, d_dirs3, nrays, d_hits); }
 extern "C" int mirt_intersect_from(const float origin[3], const float *dirs3, int nrays, mirt_hit *hits) { return mirt::query_intersect_from_host(origin, dirs3, nrays, hits); }

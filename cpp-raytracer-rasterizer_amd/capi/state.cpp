@@ -105,13 +105,13 @@ void CostHist::release()
 
 void QueryScratch::release()
 {
-    dev_free({ d_light_tab, d_origins, d_flags, d_stats[QUERY_DIRECT_LIGHT], d_stats[QUERY_FAN], d_fan_origins, d_fan_rays });
+    dev_free({ d_light_tab, d_origins, d_flags, d_stats[QUERY_DIRECT_LIGHT], d_stats[QUERY_FAN], d_stats[QUERY_OCCLUDED], d_fan_origins, d_fan_rays });
     *this = QueryScratch();
 }
 
 void QueryRows::release()
 {
-    dev_free({ d_rows, d_max, d_rays, d_hits, d_rgb, d_dirs, d_origin_of });
+    dev_free({ d_rows, d_max, d_rays, d_hits, d_rgb, d_dirs, d_origin_of, d_limits, d_occluded });
     if (ev_built) (void)hipEventDestroy(ev_built);
     cube.release();
     fan.release();

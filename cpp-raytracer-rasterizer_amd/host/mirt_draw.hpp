@@ -210,6 +210,26 @@ struct RayTracer {
         check(mirt_intersect_fans(nstarts > 0 ? &starts[0].x : nullptr, nstarts, start_of, n > 0 ? &dir[0].x : nullptr, n,
                                   reinterpret_cast<mirt_hit *>(closest)), "mirt_intersect_fans");
     }
+    // DirectLight's shadow decision (:306-315) for n rays and limits of the caller's own: occluded[k] = 1 when
+    // ClosestIntersection(start[k], dir[k], triangles, j) from a fresh j finds j.distance < max_distance[k], else 0 -- the reference
+    // asks it with dir = -rDir and max_distance = r * 0.99f.  max_distance may be null: every limit is +inf (mirt_occluded).
+    void Occluded(const vec3 *start, const vec3 *dir, const float *max_distance, uint8_t *occluded, int n)
+    {
+        upload_scene();
+        std::vector<mirt_ray> rays((size_t)n);
+        for (int k = 0; k < n; k++) { std::memcpy(rays[k].start, &start[k].x, 12); std::memcpy(rays[k].dir, &dir[k].x, 12); }
+        check(mirt_occluded(rays.data(), n, max_distance, occluded), "mirt_occluded");
+    }
+    // The same for n rays from `nstarts` shared starts -- the visibility of n points from a handful of observers or lights --, each ray
+    // walking its bin of its start's cube where that pays (mirt_occluded_fans, mirt_set_query_mode).  start_of may be null for a
+    // single start.
+    void Occluded(const vec3 *starts, int nstarts, const int32_t *start_of, const vec3 *dir, const float *max_distance, uint8_t *occluded, int n)
+    {
+        upload_scene();
+        static_assert(sizeof(vec3) == 12, "starts and directions travel as they are");
+        check(mirt_occluded_fans(nstarts > 0 ? &starts[0].x : nullptr, nstarts, start_of, n > 0 ? &dir[0].x : nullptr, n, max_distance, occluded),
+              "mirt_occluded_fans");
+    }
     // DirectLight(i) (:265-327) for n records, with the lights and the soft-shadow toggle as they stand: result[k] = DirectLight(i[k]).
     void DirectLight(const Intersection *i, vec3 *result, int n)
     {

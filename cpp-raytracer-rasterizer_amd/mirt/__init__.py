@@ -29,6 +29,7 @@ EXPORTS = (
     "mirt_set_query_mode", "mirt_get_query_stats",
     "mirt_intersect_from", "mirt_intersect_from_device", "mirt_get_fan_stats",
     "mirt_intersect_fans", "mirt_intersect_fans_device",
+    "mirt_occluded", "mirt_occluded_device", "mirt_occluded_fans", "mirt_occluded_fans_device", "mirt_get_occlusion_stats",
     "mirt_scene_upload_device", "mirt_scene_update_device", "mirt_scene_update", "mirt_scene_transform", "mirt_transform",
     "mirt_scene_download", "mirt_scene_info",
     "mirt_scene_set_objects", "mirt_scene_pose", "mirt_pose",
@@ -154,6 +155,11 @@ def load():
     lib.mirt_get_fan_stats.argtypes = [C.POINTER(QueryStats)]
     lib.mirt_intersect_fans.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp]
     lib.mirt_intersect_fans_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp]
+    lib.mirt_occluded.argtypes = [_vp, C.c_int, _vp, _vp]
+    lib.mirt_occluded_device.argtypes = [_vp, C.c_int, _vp, _vp]
+    lib.mirt_occluded_fans.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]
+    lib.mirt_occluded_fans_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]
+    lib.mirt_get_occlusion_stats.argtypes = [C.POINTER(QueryStats)]
     lib.mirt_scene_upload_device.argtypes = [_vp, _vp, C.c_int]
     lib.mirt_scene_update_device.argtypes = [C.c_int, C.c_int, _vp]
     lib.mirt_scene_update.argtypes = [C.c_int, C.c_int, _vp]
@@ -668,6 +674,81 @@ def fan_stats():
     rows tested, fallback_records = rays that swept the whole table."""
     s = QueryStats()
     _check(load().mirt_get_fan_stats(C.byref(s)))
+    return {name: int(getattr(s, name)) for name, _ in QueryStats._fields_}
+
+
+# ---- occlusion queries: any-hit rays ---------------------------------------------------------------------
+
+def _as_limits(max_distance, n, what):
+    """None, or n float32 limits (one value stands for all)."""
+    if max_distance is None:
+        return None
+    lim = np.asarray(max_distance, np.float32)
+    lim = np.full(n, lim, np.float32) if lim.ndim == 0 else np.ascontiguousarray(lim).reshape(-1)
+    if len(lim) != n:
+        raise ValueError("%d %s but %d limits" % (n, what, len(lim)))
+    return lim
+
+
+def _occluded_out(out, n, what):
+    """The uint8 array the bytes go to: a new one, or the caller's (C-contiguous uint8 of the rays' length)."""
+    if out is None:
+        return np.zeros(n, np.uint8)
+    if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous or not out.flags.writeable:
+        raise ValueError("the output must be a writeable C-contiguous uint8 array")
+    if out.size != n:
+        raise ValueError("%d %s but %d output bytes" % (n, what, out.size))
+    return out
+
+
+def occluded(rays, max_distance=None, out=None):
+    """occluded[i] = 1 when some triangle ClosestIntersection accepts for rays[i] is nearer than max_distance[i], strictly; else 0
+    (mirt_occluded).  rays: RAY_DTYPE or (n, 6) floats, dir used as given; max_distance: n floats, one for all, or None for +inf.
+    Returns uint8 (`out` when given: every byte is written)."""
+    rays = _as_rays(rays)
+    lim = _as_limits(max_distance, len(rays), "rays")
+    out = _occluded_out(out, len(rays), "rays")
+    _check(load().mirt_occluded(_ptr(rays), len(rays), None if lim is None else _ptr(lim), _ptr(out)))
+    return out
+
+
+def occluded_device(d_rays, nrays, d_max_distance, d_occluded):
+    """The same on device arrays (raw pointers; d_max_distance may be None), queued like a *_device frame; mirt.sync() completes it."""
+    _check(load().mirt_occluded_device(d_rays, int(nrays), d_max_distance, d_occluded))
+
+
+def occluded_fans(origins, origin_of, dirs, max_distance=None, out=None):
+    """occluded() for the rays {origins[origin_of[i]], dirs[i]}, byte for byte, through the cubes of intersect_fans
+    (mirt_occluded_fans; set_query_mode).  origins: (k, 3) floats; origin_of: one int32 per ray, or None for a single origin."""
+    origins = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    lim = _as_limits(max_distance, len(dirs), "directions")
+    out = _occluded_out(out, len(dirs), "directions")
+    if origin_of is not None:
+        origin_of = np.ascontiguousarray(origin_of, np.int32).reshape(-1)
+        if len(origin_of) != len(dirs):
+            raise ValueError("%d directions but %d origin indices" % (len(dirs), len(origin_of)))
+        if len(origin_of) and (origin_of.min() < 0 or origin_of.max() >= len(origins)):
+            bad = int(np.flatnonzero((origin_of < 0) | (origin_of >= len(origins)))[0])
+            raise ValueError("origin_of[%d] = %d is outside [0, %d)" % (bad, int(origin_of[bad]), len(origins)))
+    _check(load().mirt_occluded_fans(_ptr(origins), len(origins), None if origin_of is None else _ptr(origin_of), _ptr(dirs), len(dirs),
+                                     None if lim is None else _ptr(lim), _ptr(out)))
+    return out
+
+
+def occluded_fans_device(origins, d_origin_of, d_dirs, nrays, d_max_distance, d_occluded):
+    """The same on device arrays (raw pointers; the origins are host data, d_origin_of may be None for a single origin and
+    d_max_distance for +inf), queued like a *_device frame; mirt.sync() completes it."""
+    origins = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    _check(load().mirt_occluded_fans_device(_ptr(origins), len(origins), d_origin_of, d_dirs, int(nrays), d_max_distance, d_occluded))
+
+
+def occlusion_stats():
+    """The last occluded* call (mirt_get_occlusion_stats), in mirt_query_stats' fields: mode_used, cube_source (0 - 4 as for
+    intersect_fans), cube_bins, shells and -- profiling on, binned -- shadow_rays = rays, candidates = rows stepped over, tests =
+    rows not beyond the limit, fallback_records = rays that swept their origin's table."""
+    s = QueryStats()
+    _check(load().mirt_get_occlusion_stats(C.byref(s)))
     return {name: int(getattr(s, name)) for name, _ in QueryStats._fields_}
 
 

@@ -782,4 +782,234 @@ __global__ __launch_bounds__(256) void k_query_fans_expand(const QueryFansExpand
     st3(r + 3, d);
 }
 
+// ---- occlusion queries: "is anything in the way before distance L" (mirt_occluded*) ----------------------------------------------
+//
+// DirectLight's shadow decision (:306-315) for the caller's own ray and limit: occluded = some triangle ClosestIntersection accepts
+// (:239) has distance < L, strictly (:313).  With a fresh record (distance FLT_MAX) the reference's two steps -- the closest hit,
+// then `j.distance < L` -- give exactly that for every L, +inf included: a computed distance of +inf or NaN neither replaces the
+// fresh record nor passes `<`.  Any-hit is exact (SURVEY A-5): which occluder settles a ray does not show in the byte, so a ray
+// stops at its first one, in whatever order it meets the rows.  A limit nothing is below -- NaN, 0, negative -- settles its ray
+// before any row is read (`L > 0` is false for NaN); a missing limit array stands for +inf.
+__device__ __forceinline__ float occlusion_limit(const float *limit, long long ray, bool ok)
+{
+    return !ok ? -1.0f : (limit ? limit[ray] : __uint_as_float(0x7f800000u));
+}
+
+// k_query_occluded: k_query_closest's sweep -- a lane per P rays, QueryRow chunks of RT_CHUNK_ROWS through LDS, the packed dots of
+// P = 2, the filter in front of the exact divisions -- with a ray open until its first accepted dist < L.  A wave none of whose
+// rays is open leaves the rows of a chunk alone (in steps of 64 rows: nothing in there waits for another wave), but goes on taking
+// part in the staging barriers; the sweep itself ends when the WHOLE workgroup has no open ray, by a block-wide vote every one of
+// the 256 lanes reaches at the top of each chunk -- stage_rows has two barriers, so no wave may leave that loop on its own.
+template <int P>
+__global__ __launch_bounds__(256) void k_query_occluded(const QueryOccludedFrame o)
+{
+    extern __shared__ __attribute__((aligned(16))) float4 s_rows[];
+    const QueryFrame &q = o.q;
+    const bool scene_ok = scene_rows_in_range(q);
+
+    long long ray[P];
+    bool ok[P], exact_only[P], open[P];
+    v3 start[P], nd[P];
+    v3p startp, ndp;
+    float L[P];
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+        ray[p] = lane_ray<P>(p);
+        ok[p] = ray[p] < q.nrays;
+        const float *r = q.rays + (size_t)RAY_WORDS * (ok[p] ? ray[p] : 0);
+        start[p] = ld3(r);
+        const v3 dir = ld3(r + 3);
+        nd[p] = neg3(dir);                                         // negD = -dir (:229); dir is used as given
+        exact_only[p] = ray_exact_only(scene_ok, start[p], dir);
+        L[p] = occlusion_limit(o.limit, ray[p], ok[p]);
+        open[p] = L[p] > 0.0f;                                     // (false for NaN, and for a lane without a ray)
+        if constexpr (P == 2) {
+            startp.x[p] = start[p].x; startp.y[p] = start[p].y; startp.z[p] = start[p].z;
+            ndp.x[p] = nd[p].x; ndp.y[p] = nd[p].y; ndp.z[p] = nd[p].z;
+        }
+    }
+
+    for (int base = 0; base < q.n; base += RT_CHUNK_ROWS) {
+        bool any_open = false;
+#pragma unroll
+        for (int p = 0; p < P; p++) any_open |= open[p];
+        if (!__syncthreads_or((int)any_open)) break;               // workgroup-uniform: every lane votes, every lane leaves
+        const int cnt = min(RT_CHUNK_ROWS, q.n - base);
+        stage_rows(s_rows, q.rows + base, cnt);
+        for (int j0 = 0; j0 < cnt; j0 += 64) {
+            if (!__any((int)any_open)) break;                      // (the wave only: no barrier between here and the chunk's end)
+            const int j1 = min(j0 + 64, cnt);
+#pragma unroll 2
+            for (int j = j0; j < j1; j++) {
+                const RowVecs r = unpack_row(s_rows[3 * j], s_rows[3 * j + 1], s_rows[3 * j + 2]);
+                TestDots d[P];
+                float e1e2b[P];
+                bool maybe[P];
+                if constexpr (P == 2) {
+                    f2 eb;
+                    const TestDots2 t = ray_dots2(r, startp, ndp, &eb);
+                    maybe_hit2(t, &maybe[0], &maybe[1]);
+                    d[0] = dots_half(t, 0); d[1] = dots_half(t, 1);
+                    e1e2b[0] = eb.x; e1e2b[1] = eb.y;
+                } else {
+#pragma unroll
+                    for (int p = 0; p < P; p++) {
+                        d[p] = ray_dots(r, start[p], nd[p], &e1e2b[p]);
+                        maybe[p] = maybe_hit(d[p]);
+                    }
+                }
+#pragma unroll
+                for (int p = 0; p < P; p++) {
+                    if (open[p] && (maybe[p] || exact_only[p])) {
+                        v3 hp;
+                        float dist;
+                        if (exact_hit_row(d[p], e1e2b[p], r, start[p], &hp, &dist))
+                            if (dist < L[p]) open[p] = false;                              // :313
+                    }
+                }
+            }
+            any_open = false;
+#pragma unroll
+            for (int p = 0; p < P; p++) any_open |= open[p];
+        }
+    }
+
+    // a ray is occluded exactly when it began open and was closed by a row
+#pragma unroll
+    for (int p = 0; p < P; p++)
+        if (ok[p]) o.occluded[ray[p]] = (uint8_t)((L[p] > 0.0f) && !open[p]);
+}
+
+template __global__ void k_query_occluded<QUERY_P>(const QueryOccludedFrame);
+
+// k_query_occluded_wave: one WAVE per ray, lanes over the rows as in k_query_closest_wave; the wave leaves the list at the first
+// step in which any of its lanes found an occluder, and lane 0 stores the byte.  No barrier anywhere: a wave returns on its own.
+constexpr int OCC_WAVE_ROWS = 4;                  // rows per lane and step: 256 rows of the list between two votes
+__global__ __launch_bounds__(256) void k_query_occluded_wave(const QueryOccludedFrame o)
+{
+    const QueryFrame &q = o.q;
+    const int lane = threadIdx.x & 63;
+    const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= q.nrays) return;                                    // (the whole wave)
+    const float *rp = q.rays + (size_t)RAY_WORDS * ray;
+    const v3 start = ld3(rp), dir = ld3(rp + 3);
+    const v3 nd = neg3(dir);                                       // :229
+    const bool exact_only = ray_exact_only(scene_rows_in_range(q), start, dir);
+    const float L = occlusion_limit(o.limit, ray, true);
+
+    int occluded = 0;
+    if (L > 0.0f) {                                                // (wave-uniform; false for NaN)
+        // OCC_WAVE_ROWS rows a lane and step, all loaded before the first is tested (a lane past the table's end loads its last
+        // row and ignores it), and one vote a step: a wave that meets no occluder pays one ballot per 256 rows
+        for (int base = 0; base < q.n; base += 64 * OCC_WAVE_ROWS) {
+            float4 a[OCC_WAVE_ROWS], b[OCC_WAVE_ROWS], c[OCC_WAVE_ROWS];
+#pragma unroll
+            for (int s = 0; s < OCC_WAVE_ROWS; s++) {
+                const float4 *src = reinterpret_cast<const float4 *>(q.rows + min(base + 64 * s + lane, q.n - 1));
+                a[s] = src[0]; b[s] = src[1]; c[s] = src[2];
+            }
+            bool found = false;
+#pragma unroll
+            for (int s = 0; s < OCC_WAVE_ROWS; s++) {
+                const RowVecs r = unpack_row(a[s], b[s], c[s]);
+                float e1e2b;
+                const TestDots td = ray_dots(r, start, nd, &e1e2b);
+                if (base + 64 * s + lane < q.n && (maybe_hit(td) || exact_only)) {
+                    v3 hp;
+                    float dist;
+                    if (exact_hit_row(td, e1e2b, r, start, &hp, &dist) && dist < L) found = true;      // :313
+                }
+            }
+            if (__any((int)found)) { occluded = 1; break; }
+        }
+    }
+    if (lane == 0) o.occluded[ray] = (uint8_t)occluded;
+}
+
+// k_query_occluded_fans_binned: one pass of mirt_occluded_fans*, every ray through its bin of its origin's position in the cube.
+//
+// fan_walk's argument with the record distance fixed at L.  A row the reference accepts for negD is on the list of the bin of
+// d' (fan_dir_of), and its `near` bounds the distance the reference computes: a row with d < L has near <= d < L, so it lies in a
+// shell no later than bin_shell_of(L) (monotone) and passes `!(near > L)`.  The list therefore ends at L's shell, and that end never
+// moves; a row is skipped when near > L; the lane is through at its first accepted dist < L.  What is conservative for the record
+// rule's `>=` is conservative for `<`: every row that could occlude is on the part of the list that is walked.  No list for a limit
+// that is NaN, 0 or negative.  Lanes whose direction fan_dir_of does not form sweep their origin's table, ending at the first occluder.
+//
+// A pass writes the bytes of its own rays only, each exactly once.  A ray whose index lies outside [0, norigins) belongs to no
+// pass: the pass that starts at origin 0 writes its 0, and reads nothing for it but its index.
+// STATS: rays of the pass, rows stepped over, those of them not beyond the limit, rays that swept.
+template <bool STATS>
+__global__ __launch_bounds__(256) void k_query_occluded_fans_binned(const QueryOccludedFansFrame of)
+{
+    const QueryFansFrame &qf = of.f;
+    const QueryFanFrame &q = qf.f;
+    const CubeView &cv = q.cube;
+    const float4 *rows4 = reinterpret_cast<const float4 *>(cv.light_rows);
+    const uint32_t face_bins = (uint32_t)(cv.cube_bins * cv.cube_bins) * 6u;
+    const long long ray = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool ok = ray < q.nrays;
+    const uint32_t idx = qf.origin_of ? (uint32_t)qf.origin_of[ok ? ray : 0] : 0u;
+    const uint32_t rel = idx - (uint32_t)qf.first;                 // (modulo 2^32: a negative or huge index lands beyond count)
+    const bool mine = ok && rel < (uint32_t)qf.count;
+    const bool nobodys = ok && qf.first == 0 && idx >= (uint32_t)of.norigins;
+    const uint32_t k = mine ? rel : 0u;
+    const v3 S = ld3(qf.origins + 3 * (size_t)(1u + k));
+    const OriginRow *tab = q.tab + (size_t)k * q.n;
+
+    const v3 dir = ld3(q.dirs + 3 * (size_t)(ok ? ray : 0));
+    const v3 nd = neg3(dir);                                       // negD = -dir (:229); dir is used as given
+    const float L = occlusion_limit(of.limit, ray, ok);
+    const bool open = mine && L > 0.0f;                            // (false for NaN)
+    const FanDir fd = fan_dir_of(nd);
+    const bool binned = open && fd.formed, swept = open && !fd.formed;
+    uint32_t e = 0u, end = 0u;
+    if (binned) {
+        const BinFrameDesc *lf = cv.light_frames + 6 * (size_t)k;
+        const uint32_t key = cube_bin_of(fd.d, k * face_bins, cv.cube_bins) * (uint32_t)cv.shells;
+        e = cv.light_off[key];
+        end = cv.light_off[key + bin_shell_of(L, lf->shell_d0, lf->shell_iw, cv.shells) + 1u];
+    }
+    unsigned long long n_cand = 0, n_tests = 0;
+    int occluded = 0;
+    float4 c0, c1, c2;
+    walk_row(rows4, e < end ? e : 0u, c0, c1, c2);
+    for (;;) {
+        const int act = (int)(e < end);
+        if (!__any(act)) break;
+        const TestDots td = test_dots(c0, c1, c2, nd);
+        const int near_ok = act & (int)!(c1.w > L);                // every point of the row is beyond the limit: cannot pass `<`
+        if (STATS) { n_cand += (unsigned)act; n_tests += (unsigned)near_ok; }
+        int done = 0;
+        if (near_ok & (int)maybe_hit(td)) {
+            v3 hp;
+            float dist;
+            if (exact_hit(td, c0.w, q.tris15 + (size_t)15 * cv.light_tri[e], S, &hp, &dist)) done = (int)(dist < L);      // :313
+        }
+        occluded |= done;
+        walk_step(rows4, e, end, act & (done ^ 1) & (int)(e + 1u < end), c0, c1, c2);     // (done, or the list's end: the lane is through)
+    }
+    if (__any(swept)) {
+        // (rare) the lanes the bins do not cover: their origin's full table, up to the first occluder
+        const bool exact_only = !dir_in_filter_range(dir);
+        bool live = swept;
+        for (int j = 0; j < q.n; j++) {
+            if (!__any(live)) break;
+            const float4 r0 = tab[j].r0, r1 = tab[j].r1, r2 = tab[j].r2;
+            const TestDots td = test_dots(r0, r1, r2, nd);
+            if (STATS && live) { n_cand++; n_tests++; }
+            if (live && (maybe_hit(td) || exact_only)) {
+                v3 hp;
+                float dist;
+                if (exact_hit(td, r0.w, q.tris15 + (size_t)15 * j, S, &hp, &dist))
+                    if (dist < L) live = false, occluded = 1;                              // :313
+            }
+        }
+    }
+    if (mine || nobodys) of.occluded[ray] = (uint8_t)occluded;     // (nobodys: 0 -- such a lane is not open)
+    if (STATS) flush_query_stats(q.stats, mine ? 1u : 0u, n_cand, n_tests, swept ? 1u : 0u);
+}
+
+template __global__ void k_query_occluded_fans_binned<false>(const QueryOccludedFansFrame);
+template __global__ void k_query_occluded_fans_binned<true>(const QueryOccludedFansFrame);
+
 }  // namespace mirt

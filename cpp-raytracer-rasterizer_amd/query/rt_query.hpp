@@ -159,6 +159,24 @@ struct QueryFansExpand {
     float *rays;                        // nrays x RAY_WORDS
 };
 
+// ---- occlusion queries (mirt_occluded*): one byte per ray, 1 when some accepted triangle has distance < limit ---------------------
+//
+// q.hits is not read: the answer of ray i goes to occluded[i], 0 or 1, for every i in [0, nrays).
+struct QueryOccludedFrame {
+    QueryFrame q;
+    const float *limit;                 // nrays limits, used as given; NULL: every limit is +inf
+    uint8_t *occluded;                  // nrays bytes
+};
+// One pass of the many-origin form through the cube (k_query_occluded_fans_binned): QueryFansFrame's fields as k_query_fans_binned
+// reads them, f.f.hits apart.  norigins is the CALL's origin count: the pass with first == 0 writes the 0 of every ray whose index
+// lies outside [0, norigins), which belongs to no pass.
+struct QueryOccludedFansFrame {
+    QueryFansFrame f;
+    int norigins;
+    const float *limit;                 // nrays, or NULL: +inf
+    uint8_t *occluded;                  // nrays bytes; a pass writes its own rays' only
+};
+
 // Rays (hits) per workgroup of the lane-per-ray kernels: 256 lanes x P.
 constexpr int QUERY_P = 2;
 constexpr int QUERY_BLOCK_RAYS = 256 * QUERY_P;
@@ -173,5 +191,8 @@ template <int P> __attribute__((global)) void k_query_fan(const QueryFanFrame);
 template <bool STATS> __attribute__((global)) void k_query_fan_binned(const QueryFanFrame);
 template <bool STATS> __attribute__((global)) void k_query_fans_binned(const QueryFansFrame);
 __attribute__((global)) void k_query_fans_expand(const QueryFansExpand);
+template <int P> __attribute__((global)) void k_query_occluded(const QueryOccludedFrame);
+__attribute__((global)) void k_query_occluded_wave(const QueryOccludedFrame);
+template <bool STATS> __attribute__((global)) void k_query_occluded_fans_binned(const QueryOccludedFansFrame);
 
 }  // namespace mirt

@@ -463,6 +463,51 @@ MIRT_API int mirt_intersect_fans_device(const float *origins3, int norigins, con
  * pass built a cube, 2 every pass's cube was held from an earlier call, 3 every pass read the frame path's cube, 4 every pass read
  * DirectLight's cube.  mirt_intersect_from* keeps reporting 0 - 2. */
 
+/* ---- occlusion queries: any-hit rays (additions to ABI 4) ---- */
+
+/* "Is anything in the way before distance L": occluded[i] = 1 when some triangle that
+ * ClosestIntersection(rays[i].start, rays[i].dir, ...) accepts (raytracer.cpp:239) has distance < max_distance[i], the distance
+ * being the reference's glm::distance(start, pos) (:241-242); else 0.  This is DirectLight's shadow decision (:306-315) for the
+ * caller's own ray and limit: a line-of-sight test, a shadow mask without shading, the visibility of N points from K observers, an
+ * occlusion probe.  A ray stops at its first occluder instead of finding the closest hit.
+ * The comparison is strict (`<`, :313): a limit that is NaN, negative or 0 gives 0 for every ray, and an accepted triangle whose
+ * computed distance is +inf or NaN never occludes.  That is the reference's two-step form -- ClosestIntersection on a fresh record
+ * (distance FLT_MAX), then `j.distance < limit` -- for every limit, +inf included.  max_distance == NULL: every limit is +inf.
+ * `dir` is used as given and not normalised, so the caller scales the limit: the segment A -> B is dir = B - A with the limit
+ * |B - A| * 0.99f, as the reference does it.
+ * Every byte [0, nrays) is written, 0 or 1 -- there is no "left untouched" as with the hit records --, and nothing beyond.
+ * nrays == 0 does nothing.  Checks: mirt_intersect's, in its order (MIRT_ERR_NOT_INITIALISED; MIRT_ERR_INVALID_ARGUMENT for nrays < 0
+ * or a NULL rays / occluded array with a positive count; MIRT_ERR_NO_SCENE).  The _device form is queued like mirt_intersect_device
+ * (the streams in turn, mirt_sync() completes it); neither form touches mirt_get_stats, mirt_get_query_stats or mirt_get_fan_stats.
+ * Up to MIRT_QUERY_WAVE_RAYS rays (4096) a wave answers each ray and leaves the triangle list at the first occluder any lane finds;
+ * beyond, a lane answers each ray and a workgroup ends its sweep when all its rays are settled. */
+MIRT_API int mirt_occluded(const mirt_ray *rays, int nrays, const float *max_distance, uint8_t *occluded);
+MIRT_API int mirt_occluded_device(const void *d_rays, int nrays, const void *d_max_distance, void *d_occluded);
+/* The same for the rays { origins3[3 * origin_of[i] ..], dirs3[3 * i ..] }: mirt_occluded on those rays, byte for byte.  Arguments,
+ * checks and their order are mirt_intersect_fans*' (origins3 a HOST array in both forms; origin_of may be NULL only when norigins ==
+ * 1), with `occluded` in the place of the records.  The host form also checks every origin_of[i] against [0, norigins) before
+ * anything touches the device (MIRT_ERR_INVALID_ARGUMENT, nothing written); in the device form a ray whose index lies outside the
+ * range reads nothing out of bounds and its byte is written 0, under every mode.
+ * How it is answered: as mirt_intersect_fans* -- the same passes over cubes of up to MIRT_MAX_LIGHTS origins, the SAME kept cube
+ * and the same sharing with the frame path's and DirectLight's cubes, so a cube that mirt_intersect_fans* built for these origins
+ * serves this call and the reverse.  Each ray walks its bin's list front to back up to the depth shell its limit falls into, skips
+ * rows that lie wholly beyond the limit and stops at its first occluder; a direction outside mirt_intersect_from's window sweeps
+ * its origin's table up to the first occluder.  mirt_set_query_mode: BRUTE writes the rays out on the device and takes
+ * mirt_occluded_device's kernels; BINNED bins whenever the frame path would; AUTO is mirt_intersect_fans*' rule unchanged: it was
+ * measured for closest hits, and the sweep of this call puts the crossing in the same place (profiles/ray_query_bench.txt, section
+ * `occluded`: brute ahead in every cell of at most 4096 rays; beyond, binning with its builds behind only at 2000 triangles and 4
+ * origins, 0.50 - 0.53 against 0.47 - 0.49 ms). */
+MIRT_API int mirt_occluded_fans(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays,
+                                const float *max_distance, uint8_t *occluded);
+MIRT_API int mirt_occluded_fans_device(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays,
+                                       const void *d_max_distance, void *d_occluded);
+/* The last mirt_occluded* call of either pair, in mirt_query_stats' fields.  mirt_occluded* itself always reports MIRT_QUERY_BRUTE
+ * and no cube.  For mirt_occluded_fans*: cube_source 0 - 4, cube_bins and shells as mirt_get_fan_stats reports them for
+ * mirt_intersect_fans*; with profiling on and a binned call, summed over the passes, shadow_rays = rays of the call whose index
+ * names an origin, candidates = rows a ray stepped over before its occluder or its list's end, tests = those of them not beyond
+ * the ray's limit, fallback_records = rays that swept their origin's table.  Waits for the stream of that call. */
+MIRT_API int mirt_get_occlusion_stats(mirt_query_stats *out);
+
 /* ---- rasteriser: replaces Update()'s clear + Draw() + CalculateDOF() of rasteriser.cpp:183-192,461-529 */
 
 /* One frame into host buffers.  Every word of out_xrgb is written: the whole surface is cleared to black

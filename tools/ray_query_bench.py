@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans]
+"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans,occluded]
 
 The measurements of the ray-query kernels (query/rt_query.hip), written to one text file:
 
@@ -26,6 +26,12 @@ The measurements of the ray-query kernels (query/rt_query.hip), written to one t
                        (origin 0 moves by one ulp between the calls), with the cube kept (K <= 32) and under MIRT_QUERY_BRUTE, beside
                        the yardstick: K consecutive mirt_intersect_from_device calls on the same rays.  One digest over all records of
                        every variant; where the one call is behind the K calls, and where AUTO's rule is behind brute force, is listed.
+  occluded             mirt_occluded_device and mirt_occluded_fans_device (K = 1, 4, 32 origins; BRUTE, BINNED with the cubes built by
+                       the call, BINNED with the cube held) over 1 .. 2^20 rays in powers of four at n = 100 000 and n = 2 000, without
+                       limits (a ray stops at its first occluder) and with limits at half the closest distance (nothing stops a ray),
+                       each beside what a caller had to do before for the same answer, in the same run: mirt_intersect_device /
+                       mirt_intersect_fans_device from fresh records on the same rays.  The answers are compared first; the cells
+                       where an occlusion call is behind, and where binning with the builds crosses the brute path, are listed.
 
 The knob is read once per process, so every GPU step is a child process of its own, under its own `timeout`; a step that fails
 ends the run."""
@@ -597,6 +603,169 @@ def fans_summary(text, p):
     p("")
 
 
+# ---- occlusion queries: mirt_occluded*_device beside what a caller had to do before them ------------------------------------------
+
+OCC_K = (1, 4, 32)
+
+
+def half_limits(hits):
+    """Half the ray's closest distance (1.0 where it hit nothing): nothing is nearer, so no ray meets an occluder."""
+    return np.ascontiguousarray(np.where(hits["index"] >= 0, hits["distance"] * np.float32(0.5), np.float32(1.0)).astype(np.float32))
+
+
+def child_occsweep(n):
+    """mirt_occluded_device (no limits: a ray stops at its first occluder; limits at half the closest distance: nothing stops a
+    ray) beside mirt_intersect_device from fresh records on the same rays -- the rays of the `sweep` step."""
+    import mirt
+    h = hip()
+    mirt.init(0)
+    mirt.scene_upload(mirt.scene_soup(1, n, 0.05 if n >= 50000 else 0.2))
+    rng = np.random.default_rng(7)
+    top = 1 << 20
+    start = rng.uniform(-1.5, 1.5, (top, 3)).astype(np.float32)
+    target = rng.uniform(-1.0, 1.0, (top, 3)).astype(np.float32)
+    rays = mirt.make_rays(start, target - start)
+    fresh = mirt.fresh_hits(top)
+    d_rays, d_hits, d_occ = dev_alloc(h, rays.nbytes, rays), dev_alloc(h, fresh.nbytes, fresh), dev_alloc(h, top)
+    mirt.intersect_device(d_rays, top, d_hits); mirt.sync()
+    hits, occ = np.zeros(top, mirt.HIT_DTYPE), np.zeros(top, np.uint8)
+    assert h.hipMemcpy(hits.ctypes.data_as(C.c_void_p), d_hits, hits.nbytes, 2) == 0
+    lim = half_limits(hits)
+    d_lim = dev_alloc(h, lim.nbytes, lim)
+    # the answers first: no limits is "hit anything at all", half the closest distance is 0 everywhere
+    for d_l, want in ((None, (hits["index"] >= 0).astype(np.uint8)), (d_lim, np.zeros(top, np.uint8))):
+        mirt.occluded_device(d_rays, top, d_l, d_occ); mirt.sync()
+        assert h.hipMemcpy(occ.ctypes.data_as(C.c_void_p), d_occ, top, 2) == 0
+        assert np.array_equal(occ, want), "mirt_occluded_device disagrees with mirt_intersect_device"
+    print("RESULT occ n %6d: %d rays, %.3f of them hit something; both answers equal to mirt_intersect_device's" % (n, top, float((hits["index"] >= 0).mean())))
+
+    def closest(k):
+        assert h.hipMemcpy(d_hits, fresh.ctypes.data_as(C.c_void_p), 20 * k, 1) == 0
+        t0 = time.perf_counter()
+        mirt.intersect_device(d_rays, k, d_hits); mirt.sync()
+        return (time.perf_counter() - t0) * 1e3
+    k = 1
+    while k <= top:
+        reps = 7 if k <= 65536 else 3
+        closest(k)
+        c_ms = float(np.median([closest(k) for _ in range(reps)]))
+        o_ms = timed(mirt, lambda: mirt.occluded_device(d_rays, k, None, d_occ), reps)
+        l_ms = timed(mirt, lambda: mirt.occluded_device(d_rays, k, d_lim, d_occ), reps)
+        print("RESULT occ n %6d rays %8d  intersect %10.4f  occluded %10.4f  occluded, half limits %10.4f ms" % (n, k, c_ms, o_ms, l_ms))
+        sys.stdout.flush()
+        k *= 4
+    mirt.shutdown()
+
+
+def child_occfans(n):
+    """mirt_occluded_fans_device beside mirt_intersect_fans_device from fresh records on the same rays: K origins inside the scene,
+    rays dealt to them at random, under BRUTE, under BINNED with every cube built by the call (origin 0 moves by one ulp between the
+    calls) and under BINNED with the cube held."""
+    import mirt
+    h = hip()
+    mirt.init(0)
+    mirt.scene_upload(mirt.scene_soup(1, n, 0.05 if n >= 50000 else 0.2))
+    rng = np.random.default_rng(9)
+    top = 1 << 20
+    for K in OCC_K:
+        origins = np.ascontiguousarray(rng.uniform(-0.5, 0.5, (K, 3)).astype(np.float32))
+        of = rng.integers(0, K, top).astype(np.int32)
+        dirs = np.ascontiguousarray(rng.uniform(-1.0, 1.0, (top, 3)).astype(np.float32) - origins[of])
+        fresh = mirt.fresh_hits(top)
+        d_of, d_dirs, d_hits, d_occ = dev_alloc(h, of.nbytes, of), dev_alloc(h, dirs.nbytes, dirs), dev_alloc(h, fresh.nbytes, fresh), dev_alloc(h, top)
+        mirt.set_query_mode(mirt.QUERY_BRUTE)
+        mirt.intersect_fans_device(origins, d_of, d_dirs, top, d_hits); mirt.sync()
+        hits, occ = np.zeros(top, mirt.HIT_DTYPE), np.zeros(top, np.uint8)
+        assert h.hipMemcpy(hits.ctypes.data_as(C.c_void_p), d_hits, hits.nbytes, 2) == 0
+        lim = half_limits(hits)
+        d_lim = dev_alloc(h, lim.nbytes, lim)
+        for mode in (mirt.QUERY_BRUTE, mirt.QUERY_BINNED):
+            mirt.set_query_mode(mode)
+            for d_l, want in ((None, (hits["index"] >= 0).astype(np.uint8)), (d_lim, np.zeros(top, np.uint8))):
+                mirt.occluded_fans_device(origins, d_of, d_dirs, top, d_l, d_occ); mirt.sync()
+                assert h.hipMemcpy(occ.ctypes.data_as(C.c_void_p), d_occ, top, 2) == 0
+                assert np.array_equal(occ, want), "mirt_occluded_fans_device disagrees with mirt_intersect_fans_device"
+
+        def nudged(i):
+            o = origins.copy()
+            for _ in range(i):
+                o[0, 0] = np.nextafter(o[0, 0], np.float32(1))
+            return o
+
+        def run(fn, o, k):
+            assert h.hipMemcpy(d_hits, fresh.ctypes.data_as(C.c_void_p), 20 * k, 1) == 0
+            t0 = time.perf_counter()
+            fn(o, k); mirt.sync()
+            return (time.perf_counter() - t0) * 1e3
+        calls = (("intersect", lambda o, k: mirt.intersect_fans_device(o, d_of, d_dirs, k, d_hits), mirt.fan_stats),
+                 ("occluded", lambda o, k: mirt.occluded_fans_device(o, d_of, d_dirs, k, None, d_occ), mirt.occlusion_stats),
+                 ("half", lambda o, k: mirt.occluded_fans_device(o, d_of, d_dirs, k, d_lim, d_occ), mirt.occlusion_stats))
+        k, nudge = 1, 0
+        while k <= top:
+            reps = 5 if k <= 65536 else 3
+            ms = {}
+            for name, fn, stats in calls:
+                mirt.set_query_mode(mirt.QUERY_BRUTE)
+                ms[name, "brute"] = float(np.median([run(fn, origins, k) for _ in range(reps + 1)][1:]))
+                mirt.set_query_mode(mirt.QUERY_BINNED)
+                ts = []
+                for _ in range(reps + 1):                # (never the key of the call before: the one cube held is another's)
+                    nudge += 1
+                    ts.append(run(fn, nudged(1 + nudge % 7), k))
+                    assert stats()["cube_source"] == 1
+                ms[name, "built"] = float(np.median(ts[1:]))
+                ts = [run(fn, origins, k) for _ in range(reps + 2)]
+                assert stats()["cube_source"] == 2
+                ms[name, "kept"] = float(np.median(ts[2:]))
+            print("RESULT occfans n %6d K %2d rays %8d  " % (n, K, k)
+                  + "  ".join("%s %s" % (name, " ".join("%9.4f" % ms[name, m] for m in ("brute", "built", "kept"))) for name, _, _ in calls) + " ms")
+            sys.stdout.flush()
+            k *= 4
+        for d in (d_of, d_dirs, d_hits, d_occ, d_lim):
+            h.hipFree(d)
+    mirt.shutdown()
+
+
+OCC_ROW = re.compile(r"occ n\s+(\d+) rays\s+(\d+)  intersect\s+([0-9.]+)  occluded\s+([0-9.]+)  occluded, half limits\s+([0-9.]+) ms")
+OCCFANS_ROW = re.compile(r"occfans n\s+(\d+) K\s+(\d+) rays\s+(\d+)  intersect\s+([0-9.]+)\s+([0-9.]+)\s+([0-9.]+)  occluded\s+([0-9.]+)\s+([0-9.]+)\s+([0-9.]+)"
+                         r"  half\s+([0-9.]+)\s+([0-9.]+)\s+([0-9.]+) ms")
+
+
+def occluded_summary(text, p):
+    """Where an occlusion call is behind the closest-hit call a caller had to make for the same answer (same rays, same mode, same
+    run), and where binning with the builds crosses the brute path for the many-origin form."""
+    behind, far = [], lambda v, c: v > 1.02 * c
+    for m in OCC_ROW.finditer(text):
+        n, k, c, o, l = int(m.group(1)), int(m.group(2)), float(m.group(3)), float(m.group(4)), float(m.group(5))
+        behind += ["n %d rays %d %s: %.4f ms against %.4f ms" % (n, k, what, v, c) for what, v in (("no limits", o), ("half limits", l)) if far(v, c)]
+    rows = [(int(m.group(1)), int(m.group(2)), int(m.group(3))) + tuple(float(x) for x in m.groups()[3:]) for m in OCCFANS_ROW.finditer(text)]
+    for n, K, k, *v in rows:
+        for j, mode in enumerate(("brute", "built", "kept")):
+            behind += ["n %d K %d rays %d %s, %s: %.4f ms against %.4f ms" % (n, K, k, mode, what, v[off + j], v[j])
+                       for what, off in (("no limits", 3), ("half limits", 6)) if far(v[off + j], v[j])]
+    p("an occlusion call behind the closest-hit call on the same rays under the same mode by more than 2 %% of its time (the medians of one "
+      "cell differ by that much from run to run): %s" % ("; ".join(behind) if behind else "nowhere"))
+    for what, off in (("no limits", 3), ("half limits", 6)):
+        small = [r for r in rows if r[2] <= 4096]
+        large = [r for r in rows if r[2] > 4096]
+        p("mirt_occluded_fans_device, %s: brute ahead of binning with the builds in %d of %d cells of at most 4096 rays (AUTO: brute unless held); "
+          "binning with the builds behind brute beyond 4096 rays (AUTO: binned) at: %s"
+          % (what, sum(r[3 + off] < r[3 + off + 1] for r in small), len(small),
+             "; ".join("n %d K %d rays %d (%.4f against %.4f ms)" % (r[0], r[1], r[2], r[3 + off + 1], r[3 + off]) for r in large if r[3 + off + 1] > r[3 + off]) or "nowhere"))
+    p("")
+
+
+def step_occluded(p):
+    p("== occluded: mirt_occluded_device beside mirt_intersect_device from fresh records, the same rays (host clock around call + mirt_sync, medians) ==")
+    p("occluded: no limits, a ray stops at its first occluder; half limits: limits at half the closest distance, nothing stops a ray")
+    out = "".join(run_child(p, ["--child", "occsweep", str(n)], {}, 300) for n in (100000, 2000))
+    p("")
+    p("== occluded fans: mirt_occluded_fans_device beside mirt_intersect_fans_device from fresh records, K origins inside the scene, rays dealt at random ==")
+    p("three columns each: BRUTE; BINNED, every cube built by the call; BINNED, the cube held")
+    out += "".join(run_child(p, ["--child", "occfans", str(n)], {}, 420) for n in (100000, 2000))
+    occluded_summary(out, p)
+
+
 def run_child(p, args, env, limit):
     cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__)] + args
     r = subprocess.run(cmd, env=dict(os.environ, **env), capture_output=True, text=True)
@@ -659,6 +828,10 @@ def main():
             return child_fansweep(a.child[1], int(a.child[2]))
         if a.child[0] == "fans":
             return child_fans(int(a.child[1]))
+        if a.child[0] == "occsweep":
+            return child_occsweep(int(a.child[1]))
+        if a.child[0] == "occfans":
+            return child_occfans(int(a.child[1]))
         return child_throughput() if a.child[0] == "throughput" else child_sweep(int(a.child[1]))
     lines = []
 
@@ -681,6 +854,8 @@ def main():
             step_fan(p)
         if "fans" in steps:
             step_fans(p)
+        if "occluded" in steps:
+            step_occluded(p)
     finally:
         with open(a.out, "a" if a.append else "w") as f:
             f.write("\n".join(lines) + "\n")
