@@ -1,7 +1,7 @@
 // capi.hpp -- the host side of the C-ABI (csrc/mirt_capi.hip and the files of this directory): the library's state, one
 // StreamState per frame in flight inside one Ctx, and the helpers the topic files share.  Host code only: the frame kernels are
-// defined under csrc/, the ray-query kernels under query/ and the scene kernels under scene/ (tools/check_spills.py compiles all three); the ones
-// launched from here are declared below and in query/rt_query.hpp.
+// defined under csrc/, the ray-query kernels under query/, the scene kernels under scene/ and the kernels of a deferred frame under lights/
+// (tools/check_spills.py compiles all four); the ones launched from here are declared below, in query/rt_query.hpp and in lights/many_lights.hpp.
 #pragma once
 
 #include "../csrc/bin_sort.hpp"
@@ -14,6 +14,7 @@
 #include "../csrc/rt_trace_frame.hpp"
 #include "../csrc/scan.hpp"
 #include "../query/rt_query.hpp"
+#include "../lights/many_lights.hpp"
 #include "cube_plan.hpp"
 #include "pass_plan.hpp"
 #include "object_plan.hpp"
@@ -256,7 +257,25 @@ struct QueryScratch {
     float *d_fan_origins = nullptr;              // fan_origins_cap x 3
     float *d_fan_rays = nullptr;                 // fan_rays_cap x RAY_WORDS
     size_t fan_origins_cap = 0, fan_rays_cap = 0;
+    // mirt_direct_light* with more than MIRT_MAX_LIGHTS positions: the accumulators between two passes (light_passes.hpp)
+    float *d_carry = nullptr;                    // LIGHT_CARRY_WORDS x carry_cap floats
+    size_t carry_cap = 0;                        // records
 
+    void release();
+};
+
+// What a deferred frame (more than MIRT_MAX_LIGHTS light positions: rt_frame.cpp, ../lights/many_lights.hip) keeps between its
+// kernels, per stream and grow-only, sized for the pixels of the largest call so far: 20 bytes of record, 12 of DirectLight's
+// answer and 24 of carry per pixel, and 20 more for the index, distance and position planes where the caller passes none.
+struct ManyLightsScratch {
+    uint32_t *d_records = nullptr;               // cap_px x HIT_WORDS
+    float *d_direct = nullptr;                   // cap_px x 3
+    float *d_carry = nullptr;                    // LIGHT_CARRY_WORDS x cap_px
+    int32_t *d_index = nullptr;                  // cap_px each: the planes the caller did not ask for
+    float *d_dist = nullptr, *d_pos = nullptr;
+    size_t cap_px = 0;
+
+    int ensure(size_t px);                       // (the stream must be idle when they grow: ensure waits for it)
     void release();
 };
 
@@ -276,7 +295,11 @@ struct QueryRows {
     // positions in use, and the grid -- so a new scene forgets it), kept across calls, shared by the streams and ordered among
     // them by light_cache_ensure's events.  A query whose lights are the ones the frame path's valid cube holds reads g.lc and
     // leaves this one as it is; no query ever writes g.lc or what the frame path tracks in it.
-    LightCache cube;
+    // A call of more than MIRT_MAX_LIGHTS positions (and the DirectLight passes of a deferred frame) walks one cube per pass: pass p
+    // keeps its range's cube in cubes[p % QUERY_LIGHT_CUBES], each keyed and built like entry 0 -- which is the cube of a call of
+    // one pass --, so that a repeated call of up to MIRT_MAX_LIGHT_POSITIONS positions in full cubes builds nothing.
+    static constexpr int QUERY_LIGHT_CUBES = 8;
+    LightCache cubes[QUERY_LIGHT_CUBES];
     // The cube of the origin fans (mirt_intersect_from*): the same structure around the fan's origin, a one-position list -- keyed by
     // scene version and origin (light_key_of), built by light_cache_ensure under the same protocol.  Apart from `cube`, so that a
     // probe does not evict DirectLight's lights nor a DirectLight query the probe's origin.
@@ -318,6 +341,7 @@ struct StreamState {
     void *d_async = nullptr;                     // the XRGB plane of an asynchronous frame (async_plane)
     RasterScratch raster;
     QueryScratch query;
+    ManyLightsScratch many;
     // cull flags: what this stream's copy of d_culled holds -- the number of the cull call (or upload) it comes from --, and the
     // copies OUT of other streams' copies it has made: the event is re-recorded behind every such copy ...
     uint64_t culled_ver = 0;
@@ -376,7 +400,7 @@ struct Ctx {
     int dof_k = 0;                               // DOF_KERNEL_SIZE when DOF_ENABLED, else 0
     float dof_focal = 0.0f;                      // FOCAL_LENGTH
     int soft_npos = 0;
-    float soft_pos[MIRT_MAX_LIGHTS * 3] = {};    // jittered light positions, [light*samples + i]
+    float soft_pos[MIRT_MAX_LIGHT_POSITIONS * 3] = {};   // jittered light positions, [light*samples + i] (randomPositions[256], raytracer.cpp:84)
 
     // host surfaces the caller registered (mirt_surface_register): pinned + mapped, so the frame reaches them at link speed
     struct HostSurface { char *host = nullptr; char *dev = nullptr; size_t bytes = 0; } surf[4];
@@ -491,8 +515,16 @@ int binned_trace(const RtFrame &f, StreamState &ss, const BinnedPass &bp);
 // shadow-ray origins.  fill_light_positions: where each of them is (the light itself, or its jittered sample: randomPositions[k *
 // SOFT_SHADOWS_SAMPLES + i], raytracer.cpp:286), its share of the light's power, P = (color * intensity) / samples (:282, :296),
 // and its origin row -- lpos / lcol: npos rows; origins: rows 1 .. npos (row 0 is the camera's); any of the three may be NULL.
+// lights x samples may reach MIRT_MAX_LIGHT_POSITIONS; what holds more than MIRT_MAX_LIGHTS of them is sized by LightPositions.
 inline int soft_samples() { return g.soft_samples > 1 ? g.soft_samples : 1; }
 int check_lights(const mirt_light *lights, int nlights, int *light_positions);
+// Every light position of a call on the host: position, share of the light's power and origin row (row 0: the camera's place).
+struct LightPositions {
+    float lpos[MIRT_MAX_LIGHT_POSITIONS][3], lcol[MIRT_MAX_LIGHT_POSITIONS][3];
+    float origins[(1 + MIRT_MAX_LIGHT_POSITIONS) * 3];
+};
+// The position count from which a frame is deferred (MIRT_MANY_LIGHTS_MIN, default MIRT_MAX_LIGHTS + 1: what the fused kernels cannot hold).
+int many_lights_min();
 void fill_light_positions(const mirt_light *lights, int npos, float (*lpos)[3], float (*lcol)[3], float *origins);
 // MIRT_RT_AUTO / MIRT_QUERY_AUTO bin nothing below this many triangles (MIRT_BIN_THRESHOLD; the tile kernel takes up to 64).
 int auto_bin_threshold();
@@ -529,6 +561,13 @@ int query_intersect(const void *d_rays, int nrays, void *d_hits);
 int query_intersect_host(const mirt_ray *rays, int nrays, mirt_hit *hits);
 int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_rgb);
 int query_direct_light_host(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, float *out_rgb);
+// DirectLight for nhits > 0 records over the npos positions of `lights` on the current stream, in as many passes as they need.
+// mode: MIRT_QUERY_*; auto_rule: what AUTO's own rule says for this call.  stats: the DirectLight statistics of a query, NULL for
+// the passes of a deferred frame, which leave them alone and bracket their cube builds under MIRT_K_BIN; carry / carry_cap: the
+// caller's scratch for the accumulators between passes, grown here.
+int direct_light_passes(const void *d_hits, int nhits, const mirt_light *lights, int npos, void *d_rgb, int mode, bool auto_rule, bool is_query,
+                        float **carry, size_t *carry_cap);
+bool direct_light_auto_bins(int nhits, int npos);
 int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, void *d_hits);
 int query_intersect_from_host(const float *origin, const float *dirs3, int nrays, mirt_hit *hits);
 int query_intersect_fans(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, void *d_hits);

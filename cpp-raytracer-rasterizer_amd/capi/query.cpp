@@ -3,6 +3,8 @@
 // version and shared by the streams, and so is the light cube whose bins the shadow rays of DirectLight walk (per scene version
 // and light positions); a query takes the next stream as a frame does (mirt_set_frames_in_flight, mirt_sync) but leaves the
 // statistics of the last render call alone (DirectLight has its own: mirt_set_query_mode, mirt_get_query_stats, defined here).
+// DirectLight over more than MIRT_MAX_LIGHTS light positions runs in passes that hand its accumulators on (direct_light_passes; the
+// deferred frames of rt_frame.cpp run the same passes over one record per pixel), each binned pass through a kept cube of its own.
 // Many rays from ONE origin (mirt_intersect_from*) walk a cube of the same kind around that origin, kept apart from DirectLight's;
 // rays from SEVERAL origins in one call (mirt_intersect_fans*) walk cubes that hold up to MIRT_MAX_LIGHTS of the origins each.
 // Occlusion queries (mirt_occluded*, mirt_occluded_fans*) answer one byte per ray through the same rows and the same cubes.
@@ -238,31 +240,124 @@ static int query_origin_tables(const float *origins, int npos, bool safe)
     return MIRT_OK;
 }
 
-// The brute-force kernel over those tables.
-static int direct_light_brute(QueryLightFrame &q, const float *origins, int npos, bool safe)
+// The brute-force kernel over those tables; carry: one pass of several (light_passes.hpp).
+static int direct_light_brute(QueryLightFrame &q, const float *origins, int npos, bool safe, bool carry)
 {
     int rc;
     if ((rc = query_origin_tables(origins, npos, safe))) return rc;
     q.f.light_tab = g.cur().query.d_light_tab;
     q.f.unsafe = g.cur().query.d_flags;
-    hipLaunchKernelGGL(k_query_direct_light<QUERY_P>, dim3((unsigned)((q.nhits + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), sweep_lds_bytes(), g.stream, q);
+    void (*const kernel)(QueryLightFrame) = carry ? k_query_direct_light<QUERY_P, true> : k_query_direct_light<QUERY_P, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((q.nhits + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), sweep_lds_bytes(), g.stream, q);
     HIP_TRY(hipGetLastError());
     return MIRT_OK;
 }
 
-// The binned kernel over the cube C (the frame path's, or the queries' own after light_cache_ensure).
-static int direct_light_binned(QueryLightFrame &q, const LightCache &C)
+// The binned kernel over the cube C (the frame path's, or the queries' own after light_cache_ensure); counters: what stats_arm
+// gave the call, the same words for every pass of it.
+static int direct_light_binned(QueryLightFrame &q, const LightCache &C, unsigned long long *counters, bool carry)
 {
-    int rc;
     QueryBinnedFrame b;
     memset(&b, 0, sizeof b);
     b.q = q;
     b.q.f.light_tab = C.d_light_tab;             // (the records the bins do not cover sweep the cube's own origin table)
     b.q.f.unsafe = nullptr;
     b.cube = cube_view(C);
-    if ((rc = stats_arm(QUERY_DIRECT_LIGHT, &b.stats))) return rc;
+    b.stats = counters;
     const dim3 grid((unsigned)((q.nhits + 256 * QUERY_BIN_P - 1) / (256 * QUERY_BIN_P)));
-    return launch_walk(k_query_direct_light_binned<QUERY_BIN_P, false>, k_query_direct_light_binned<QUERY_BIN_P, true>, b.stats != nullptr, grid, b);
+    if (carry) return launch_walk(k_query_direct_light_binned<QUERY_BIN_P, false, true>, k_query_direct_light_binned<QUERY_BIN_P, true, true>, counters != nullptr, grid, b);
+    return launch_walk(k_query_direct_light_binned<QUERY_BIN_P, false, false>, k_query_direct_light_binned<QUERY_BIN_P, true, false>, counters != nullptr, grid, b);
+}
+
+bool direct_light_auto_bins(int nhits, int npos) { return auto_bins(nhits, npos); }
+
+static int fold_cube_source(size_t pass, int so_far, int source);
+
+// DirectLight over npos positions in passes of at most MIRT_MAX_LIGHTS (light_passes.hpp has the argument).  Up to MIRT_MAX_LIGHTS
+// positions are ONE pass on the kernels' plain instantiations, under the rules a query has always had; beyond, the ranges are
+// fan_pass_plan's, walked strictly in order on the current stream, every pass with lpos / lcol, origin tables (brute) or cube
+// (binned) of its own range and the carry between them.  Binned or brute is decided once, for the whole call: never what lies
+// outside the filter's proven range (`safe`: that is the `unsafe` flag the brute kernel is given) or what the sort cannot key --
+// one range that does not fit sends every pass to the brute-force kernel.  The cube of pass p: g.qrows.cubes[p % QUERY_LIGHT_CUBES];
+// pass 0 reads the frame path's instead when that holds these very positions.
+int direct_light_passes(const void *d_hits, int nhits, const mirt_light *lights, int npos, void *d_rgb, int mode, bool auto_rule, bool is_query,
+                        float **carry, size_t *carry_cap)
+{
+    int rc;
+    QueryLightFrame q;
+    memset(&q, 0, sizeof q);
+    RtFrame &f = q.f;
+    f.tris15 = g.d_tris;
+    f.n = g.n;
+    f.samples = soft_samples();
+    q.hits = static_cast<const uint32_t *>(d_hits);
+    q.nhits = nhits;
+    q.rgb = static_cast<float *>(d_rgb);
+    // the light positions the shadow rays start from and their share of the light's power, as a frame sets them up
+    LightPositions lp;
+    lp.origins[0] = lp.origins[1] = lp.origins[2] = 0.0f;
+    fill_light_positions(lights, npos, lp.lpos, lp.lcol, lp.origins);
+    const bool safe = starts_safe(lp.origins + 3, npos);     // the shadow rays' starts
+
+    std::vector<FanPass> plan;
+    bool may_bin;
+    if (npos <= MIRT_MAX_LIGHTS) {
+        bool fixed_grid = false;
+        const int cube_bins = light_cube_bins_for(npos, &fixed_grid);
+        plan.push_back({ 0, npos, cube_bins });
+        may_bin = safe && npos > 0 && light_keys_fit(npos, cube_bins);
+    } else {
+        may_bin = fan_pass_plan(npos, g.n, cube_bins_override(), &plan) && safe;
+        if (plan.empty())                                    // no cube takes them: the brute-force passes are full ones
+            for (int first = 0; first < npos; first += MIRT_MAX_LIGHTS) plan.push_back({ first, std::min(npos - first, (int)MIRT_MAX_LIGHTS), 0 });
+    }
+    const size_t npass = plan.size();
+    const std::initializer_list<CubeChoice> frame_cube = { { &g.lc, 3 } }, none = {};
+    float po[(1 + MIRT_MAX_LIGHTS) * 3];
+    const auto pass_origins = [&](const FanPass &p) {        // row 0 is the camera's place, rows 1 .. count the pass's positions
+        po[0] = po[1] = po[2] = 0.0f;
+        memcpy(po + 3, lp.origins + 3 * (size_t)(1 + p.first), sizeof(float) * 3 * p.count);
+    };
+    bool held = may_bin && is_query;                         // (`held`: every pass's cube, that is; a frame does not ask)
+    for (size_t i = 0; held && i < npass; i++) {
+        pass_origins(plan[i]);
+        held = held_cube(i == 0 ? frame_cube : none, g.qrows.cubes[i % QueryRows::QUERY_LIGHT_CUBES], po, plan[i].count, plan[i].cube_bins).cube != nullptr;
+    }
+    const bool binned = query_bins(may_bin, mode, held, auto_rule);
+
+    if (is_query) stream_begin();
+    QueryStats *stats = is_query ? &stats_begin(QUERY_DIRECT_LIGHT, binned) : nullptr;
+    const bool multi = npass > 1;
+    if (multi && (size_t)nhits > *carry_cap && (rc = dev_grow(carry, carry_cap, (size_t)nhits, (size_t)nhits * LIGHT_CARRY_WORDS, true))) return rc;
+    unsigned long long *counters = nullptr;
+    if (binned && is_query && (rc = stats_arm(QUERY_DIRECT_LIGHT, &counters))) return rc;     // (once: the passes' kernels add up in the same words)
+    int source_all = 0;
+    for (size_t i = 0; i < npass; i++) {
+        const FanPass &p = plan[i];
+        f.nlights = p.count;
+        memcpy(f.lpos, lp.lpos + p.first, sizeof(float) * 3 * p.count);
+        memcpy(f.lcol, lp.lcol + p.first, sizeof(float) * 3 * p.count);
+        q.first = p.first;
+        q.carry = multi ? *carry : nullptr;
+        q.pass_flags = (i == 0 ? LIGHT_PASS_FIRST : 0) | (i + 1 == npass ? LIGHT_PASS_LAST : 0);
+        pass_origins(p);
+        if (!binned) {
+            if ((rc = direct_light_brute(q, po, p.count, safe, multi))) return rc;
+            continue;
+        }
+        const std::initializer_list<CubeChoice> &foreign = i == 0 ? frame_cube : none;
+        LightCache &own = g.qrows.cubes[i % QueryRows::QUERY_LIGHT_CUBES];
+        CubeChoice c = held_cube(foreign, own, po, p.count, p.cube_bins);
+        if (!c.cube) {                                       // (a build: behind the previous pass's kernel on this stream)
+            if (!is_query && !g.cur().ev_used[MIRT_K_BIN]) k_begin(MIRT_K_BIN);
+            if ((rc = walk_cube(foreign, own, po, p.count, p.cube_bins, &c))) return rc;
+            if (!is_query) k_end(MIRT_K_BIN);
+        }
+        source_all = fold_cube_source(i, source_all, c.source);
+        if (stats) stats_cube(*stats, *c.cube, source_all);
+        if ((rc = direct_light_binned(q, *c.cube, counters, multi))) return rc;
+    }
+    return MIRT_OK;
 }
 
 int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_rgb)
@@ -272,38 +367,8 @@ int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, 
     if ((rc = check_lights(lights, nlights, &npos))) return rc;
     if (nhits == 0) return MIRT_OK;
     if ((rc = need_scene())) return rc;
-
-    QueryLightFrame q;
-    memset(&q, 0, sizeof q);
-    RtFrame &f = q.f;
-    f.tris15 = g.d_tris;
-    f.n = g.n;
-    // the light positions the shadow rays start from and their share of the light's power, as a frame sets them up
-    f.nlights = npos;
-    f.samples = soft_samples();
-    float origins[(1 + MIRT_MAX_LIGHTS) * 3] = {};
-    fill_light_positions(lights, npos, f.lpos, f.lcol, origins);
-    const bool safe = starts_safe(origins + 3, npos);        // the shadow rays' starts (f.lpos, as origins holds them too)
-    q.hits = static_cast<const uint32_t *>(d_hits);
-    q.nhits = nhits;
-    q.rgb = static_cast<float *>(d_rgb);
-
-    // Binned or brute.  Never what lies outside the filter's proven range (`safe`: here that is the `unsafe` flag the brute kernel
-    // would be given) or what the sort cannot key.  The cube: the frame path's when it holds these very lights, else the queries' own.
-    bool fixed_grid = false;
-    const int cube_bins = light_cube_bins_for(npos, &fixed_grid);
-    const bool may_bin = safe && npos > 0 && light_keys_fit(npos, cube_bins);
-    const bool held = may_bin && held_cube({ { &g.lc, 3 } }, g.qrows.cube, origins, npos, cube_bins).cube != nullptr;
-    const bool binned = query_bins(may_bin, g.query_mode, held, auto_bins(nhits, npos));
-
-    stream_begin();
-    QueryStats &stats = stats_begin(QUERY_DIRECT_LIGHT, binned);
-    if (!binned) return direct_light_brute(q, origins, npos, safe);
-
-    CubeChoice c;
-    if ((rc = walk_cube({ { &g.lc, 3 } }, g.qrows.cube, origins, npos, cube_bins, &c))) return rc;
-    stats_cube(stats, *c.cube, c.source);
-    return direct_light_binned(q, *c.cube);
+    QueryScratch &S = g.streams[next_si()].query;            // the stream the call will take: its carry
+    return direct_light_passes(d_hits, nhits, lights, npos, d_rgb, g.query_mode, auto_bins(nhits, npos), true, &S.d_carry, &S.carry_cap);
 }
 
 // ---- origin fans: ClosestIntersection for many directions from one origin (mirt_intersect_from*) -----------------------------
@@ -474,7 +539,7 @@ int query_intersect_fans(const float *origins3, int norigins, const void *d_orig
     if ((rc = need_scene())) return rc;
 
     std::vector<FanPass> plan;
-    const std::initializer_list<CubeChoice> foreign = { { &g.lc, 3 }, { &g.qrows.cube, 4 } };
+    const std::initializer_list<CubeChoice> foreign = { { &g.lc, 3 }, { &g.qrows.cubes[0], 4 } };
     float po[(1 + MIRT_MAX_LIGHTS) * 3];
     const bool binned = fans_binned(origins3, norigins, nrays, foreign, &plan);
 
@@ -563,7 +628,7 @@ int query_occluded_fans(const float *origins3, int norigins, const void *d_origi
     if ((rc = need_scene())) return rc;
 
     std::vector<FanPass> plan;
-    const std::initializer_list<CubeChoice> foreign = { { &g.lc, 3 }, { &g.qrows.cube, 4 } };
+    const std::initializer_list<CubeChoice> foreign = { { &g.lc, 3 }, { &g.qrows.cubes[0], 4 } };
     const bool binned = fans_binned(origins3, norigins, nrays, foreign, &plan);
 
     stream_begin();

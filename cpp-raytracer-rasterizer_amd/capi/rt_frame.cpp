@@ -61,11 +61,26 @@ int check_lights(const mirt_light *lights, int nlights, int *light_positions)
     if (nlights > 0 && !lights) return fail(MIRT_ERR_INVALID_ARGUMENT, "lights must not be NULL when nlights > 0");
     const int samples = soft_samples();
     *light_positions = nlights * samples;
-    if (*light_positions > MIRT_MAX_LIGHTS)
-        return fail(MIRT_ERR_INVALID_ARGUMENT, "%d lights x %d soft-shadow samples exceed %d light positions", nlights, samples, MIRT_MAX_LIGHTS);
+    if (*light_positions > MIRT_MAX_LIGHT_POSITIONS)
+        return fail(MIRT_ERR_INVALID_ARGUMENT, "%d lights x %d soft-shadow samples exceed %d light positions", nlights, samples, MIRT_MAX_LIGHT_POSITIONS);
     if (samples > 1 && *light_positions > g.soft_npos)
-        return fail(MIRT_ERR_INVALID_ARGUMENT, "%d jittered positions needed, %d were set (mirt_set_soft_shadows)", *light_positions, g.soft_npos);
+        return fail(MIRT_ERR_INVALID_ARGUMENT, "%d lights x %d soft-shadow samples exceed the %d jittered positions set: %d jittered positions needed (mirt_set_soft_shadows)",
+                    nlights, samples, g.soft_npos, *light_positions);
     return MIRT_OK;
+}
+
+int many_lights_min()
+{
+    static const int v = (int)env_int("MIRT_MANY_LIGHTS_MIN", MIRT_MAX_LIGHTS + 1);
+    return v;
+}
+
+// Whether a frame of so many light positions is deferred (rt_enqueue): always beyond what RtFrame carries, and from
+// MIRT_MANY_LIGHTS_MIN positions on when that is set lower -- but never a supersampled frame the fused kernels can render.
+static bool frame_deferred(int light_positions)
+{
+    const int aa = g.aa > 1 ? g.aa : 1;
+    return light_positions > MIRT_MAX_LIGHTS || (aa <= 1 && light_positions >= many_lights_min());
 }
 
 void fill_light_positions(const mirt_light *lights, int npos, float (*lpos)[3], float (*lcol)[3], float *origins)
@@ -152,11 +167,14 @@ bool rt_bins_whole_frame(const mirt_view *view, const mirt_light *lights, int nl
 {
     const int samples = soft_samples(), npos = nlights * samples;
     // (check_lights' conditions, without its messages: the question is asked, not a frame)
-    if (!view || nlights < 0 || (nlights && !lights) || npos > MIRT_MAX_LIGHTS || (samples > 1 && npos > g.soft_npos)) return false;
+    if (!view || nlights < 0 || nlights > MIRT_MAX_LIGHTS || (nlights && !lights) || npos > MIRT_MAX_LIGHT_POSITIONS || (samples > 1 && npos > g.soft_npos)) return false;
+    if (npos > MIRT_MAX_LIGHTS && g.aa > 1) return false;    // (rt_enqueue refuses the frame)
+    // a deferred frame: the answer is its primary pass's, which has no light
+    const int fused = frame_deferred(npos) ? 0 : npos;
     float origins[(1 + MIRT_MAX_LIGHTS) * 3];
     memcpy(origins, view->pos, 12);
-    fill_light_positions(lights, npos, nullptr, nullptr, origins);
-    return mode_bins(view, mode, view->height) && operands_safe(view, origins, npos) && frame_fits_binning(view->width, view->height);
+    fill_light_positions(lights, fused, nullptr, nullptr, origins);
+    return mode_bins(view, mode, view->height) && operands_safe(view, origins, fused) && frame_fits_binning(view->width, view->height);
 }
 
 // The frames that are not binned.  Scenes of at most 64 triangles (the reference's Cornell box has 30): per-tile candidate
@@ -238,6 +256,39 @@ static int rt_dispatch_brute(RtFrame &f, const mirt_view *view, OriginTables &S,
     return MIRT_OK;
 }
 
+// The light of a deferred frame, behind its primary pass on the frame's stream (../lights/many_lights.hip): the planes that pass
+// left in f become one hit record per pixel of the band, DirectLight runs over the records in passes of at most MIRT_MAX_LIGHTS
+// positions (query.cpp: direct_light_passes -- the frame's mode decides between its kernels, mirt_set_query_mode and the queries'
+// statistics stay out of it), and the resolve writes pixelColours and the surface's words.  All of it is bracketed as the frame's
+// trace step, the cube builds of binned passes as its binning step.
+static int deferred_lights(const RtFrame &f, const mirt_light *lights, int npos, int mode)
+{
+    int rc;
+    ManyLightsScratch &M = g.cur().many;
+    const int pixels = f.W * (f.y1 - f.y0);
+    ManyLightsFrame m;
+    memset(&m, 0, sizeof m);
+    m.W = f.W; m.H = f.H; m.y0 = f.y0; m.y1 = f.y1; m.row_origin = f.row_origin;
+    m.index = f.index; m.dist = f.dist; m.pos = f.pos;
+    m.records = M.d_records;
+    m.direct = M.d_direct;
+    m.tris15 = f.tris15;
+    m.n = f.n;
+    memcpy(m.indirect, f.indirect, 12);
+    m.xrgb = f.xrgb; m.pitch_words = f.pitch_words; m.rgb = f.rgb;
+    const dim3 grid((unsigned)((pixels + 255) / 256));
+    if (!g.cur().ev_used[MIRT_K_TRACE]) k_begin(MIRT_K_TRACE);
+    hipLaunchKernelGGL(k_frame_records, grid, dim3(256), 0, g.stream, m);
+    HIP_TRY(hipGetLastError());
+    const int qmode = mode == MIRT_RT_BRUTE ? MIRT_QUERY_BRUTE : (mode == MIRT_RT_BINNED ? MIRT_QUERY_BINNED : MIRT_QUERY_AUTO);
+    size_t carry_cap = M.cap_px;                             // (ensure sized it for these pixels)
+    if ((rc = direct_light_passes(M.d_records, pixels, lights, npos, M.d_direct, qmode, direct_light_auto_bins(pixels, npos), false, &M.d_carry, &carry_cap))) return rc;
+    hipLaunchKernelGGL(k_frame_resolve, grid, dim3(256), 0, g.stream, m);
+    HIP_TRY(hipGetLastError());
+    k_end(MIRT_K_TRACE);                                     // (the end of the primary pass's bracket moves behind the resolve)
+    return MIRT_OK;
+}
+
 int rt_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect, int mode,
                int y0, int y1, int row_origin, void *d_xrgb, int pitch_bytes, void *d_rgb, void *d_index, void *d_fd,
                void *d_dist, void *d_pos)
@@ -248,10 +299,18 @@ int rt_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, con
     int light_positions = 0;                                 // shadow-ray origins
     if ((rc = check_lights(lights, nlights, &light_positions))) return rc;
 
+    // More positions than RtFrame carries: the frame is deferred (deferred_lights) -- its primary pass below renders with no light.
+    // Supersampling shades the record a pixel carries at each of its aa x aa sub-rays (raytracer.cpp:580-594), which one record per
+    // pixel cannot hold.
+    const bool deferred = frame_deferred(light_positions);
+    if (light_positions > MIRT_MAX_LIGHTS && g.aa > 1)
+        return fail(MIRT_ERR_INVALID_ARGUMENT, "supersampling (mirt_set_antialiasing %d) cannot be combined with %d light positions: more than %d are rendered with one record per pixel",
+                    g.aa, light_positions, MIRT_MAX_LIGHTS);
+
     RtFrame f;
     float origins[(1 + MIRT_MAX_LIGHTS) * 3];
-    make_rt_frame(f, origins, view, lights, nlights, indirect, y0, y1, row_origin, d_xrgb, pitch_bytes, d_rgb, d_index, d_fd, d_dist, d_pos);
-    nlights = light_positions;                   // from here on "lights" means light positions
+    make_rt_frame(f, origins, view, lights, deferred ? 0 : nlights, indirect, y0, y1, row_origin, d_xrgb, pitch_bytes, d_rgb, d_index, d_fd, d_dist, d_pos);
+    nlights = deferred ? 0 : light_positions;    // from here on "lights" means the light positions of the fused kernels
     const bool safe = operands_safe(view, origins, nlights);
 
     // ---- mode: brute force for small scenes, binned otherwise; unsafe operands always render exact brute ----
@@ -283,8 +342,8 @@ int rt_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, con
     OriginTables &S = ss.tabs;
     if (!tile_path) {                            // origin tables of this stream, sized for the scene and the light positions
         if ((rc = S.ensure_cam_rows())) return rc;
-        if (!binned && (light_positions > S.light_tab_lights || S.light_tab_n != g.n)) {   // (binned frames read the shared light cache)
-            if ((rc = dev_grow(&S.d_light_tab, &S.light_tab_lights, light_positions, (size_t)light_positions * g.n, false))) return rc;
+        if (!binned && (nlights > S.light_tab_lights || S.light_tab_n != g.n)) {   // (binned frames read the shared light cache)
+            if ((rc = dev_grow(&S.d_light_tab, &S.light_tab_lights, nlights, (size_t)nlights * g.n, false))) return rc;
             S.light_tab_n = g.n;
         }
         if (!S.d_origins) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_origins), sizeof(float) * 3 * (1 + MIRT_MAX_LIGHTS)));
@@ -293,6 +352,16 @@ int rt_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, con
     f.cam_tab = S.d_cam_tab;
     f.light_tab = S.d_light_tab;
     f.unsafe = S.d_flags;
+    if (deferred) {
+        // the planes the records are made from: the caller's, or the stream's own where the caller asked for none (the kernels
+        // index them with full-frame pixel numbers: the bases are shifted so that row y0 is the first stored)
+        ManyLightsScratch &M = ss.many;
+        if ((rc = M.ensure((size_t)view->width * (size_t)(y1 - y0)))) return rc;
+        const ptrdiff_t shift = (ptrdiff_t)y0 * view->width;
+        if (!f.index) f.index = M.d_index - shift;
+        if (!f.dist) f.dist = M.d_dist - shift;
+        if (!f.pos) f.pos = M.d_pos - 3 * shift;
+    }
 
     if (binned) {
         BinnedPass bp;
@@ -300,6 +369,7 @@ int rt_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, con
     } else if ((rc = rt_dispatch_brute(f, view, S, origins, nlights, safe, tile_path, tile_lds))) {
         return rc;
     }
+    if (deferred && (rc = deferred_lights(f, lights, light_positions, mode))) return rc;
     call_end();
     return MIRT_OK;
 }

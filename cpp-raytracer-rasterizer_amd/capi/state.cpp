@@ -105,15 +105,33 @@ void CostHist::release()
 
 void QueryScratch::release()
 {
-    dev_free({ d_light_tab, d_origins, d_flags, d_stats[QUERY_DIRECT_LIGHT], d_stats[QUERY_FAN], d_stats[QUERY_OCCLUDED], d_fan_origins, d_fan_rays });
+    dev_free({ d_light_tab, d_origins, d_flags, d_stats[QUERY_DIRECT_LIGHT], d_stats[QUERY_FAN], d_stats[QUERY_OCCLUDED], d_fan_origins, d_fan_rays, d_carry });
     *this = QueryScratch();
+}
+
+int ManyLightsScratch::ensure(size_t px)
+{
+    int rc;
+    if (px <= cap_px) return MIRT_OK;
+    HIP_TRY(hipStreamSynchronize(g.stream));     // an earlier frame of the stream may still read the old buffers
+    cap_px = 0;
+    if ((rc = dev_realloc(&d_records, px * HIT_WORDS)) || (rc = dev_realloc(&d_direct, px * 3)) || (rc = dev_realloc(&d_carry, px * LIGHT_CARRY_WORDS)) ||
+        (rc = dev_realloc(&d_index, px)) || (rc = dev_realloc(&d_dist, px)) || (rc = dev_realloc(&d_pos, px * 3))) return rc;
+    cap_px = px;
+    return MIRT_OK;
+}
+
+void ManyLightsScratch::release()
+{
+    dev_free({ d_records, d_direct, d_carry, d_index, d_dist, d_pos });
+    *this = ManyLightsScratch();
 }
 
 void QueryRows::release()
 {
     dev_free({ d_rows, d_max, d_rays, d_hits, d_rgb, d_dirs, d_origin_of, d_limits, d_occluded });
     if (ev_built) (void)hipEventDestroy(ev_built);
-    cube.release();
+    for (LightCache &c : cubes) c.release();
     fan.release();
     fans.release();
     *this = QueryRows();
@@ -140,6 +158,7 @@ void StreamState::release()
     hist.release();
     raster_scratch_free(raster);
     query.release();
+    many.release();
     dof.release();
     dev_free({ d_hits[0], d_hits[1], d_tile_tab, d_async });
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);

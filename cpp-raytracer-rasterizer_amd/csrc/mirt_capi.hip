@@ -384,9 +384,9 @@ extern "C" int mirt_set_soft_shadows(int samples, const float *positions, int np
     int rc;
     if ((rc = need_init())) return rc;
     if (samples <= 1) { g.soft_samples = 1; g.soft_npos = 0; return MIRT_OK; }
-    if (samples > MIRT_MAX_LIGHTS) return fail(MIRT_ERR_INVALID_ARGUMENT, "samples %d exceeds %d", samples, MIRT_MAX_LIGHTS);
-    if (!positions || npositions < samples || npositions > MIRT_MAX_LIGHTS)
-        return fail(MIRT_ERR_INVALID_ARGUMENT, "need between %d and %d jittered positions, got %d", samples, MIRT_MAX_LIGHTS, npositions);
+    if (samples > MIRT_MAX_LIGHT_POSITIONS) return fail(MIRT_ERR_INVALID_ARGUMENT, "samples %d exceeds %d", samples, MIRT_MAX_LIGHT_POSITIONS);
+    if (!positions || npositions < samples || npositions > MIRT_MAX_LIGHT_POSITIONS)
+        return fail(MIRT_ERR_INVALID_ARGUMENT, "need between %d and %d jittered positions (more would exceed the limit), got %d", samples, MIRT_MAX_LIGHT_POSITIONS, npositions);
     memcpy(g.soft_pos, positions, sizeof(float) * 3 * (size_t)npositions);
     g.soft_samples = samples;
     g.soft_npos = npositions;

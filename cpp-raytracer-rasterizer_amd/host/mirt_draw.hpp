@@ -250,7 +250,7 @@ private:
     {
         upload_scene();
         check(mirt_set_antialiasing(AA_ENABLED ? AA_SAMPLES : 1), "mirt_set_antialiasing");   // realSamples (:549-554)
-        if (SOFT_SHADOWS_ENABLED)                                  // DirectLight's `samples` (:272-275)
+        if (SOFT_SHADOWS_ENABLED)                                  // DirectLight's `samples` (:272-275); the whole array fits: MIRT_MAX_LIGHT_POSITIONS = 256
             check(mirt_set_soft_shadows(SOFT_SHADOWS_SAMPLES, &randomPositions[0].x, NUM_LIGHTS * SOFT_SHADOWS_SAMPLES), "mirt_set_soft_shadows");
         else
             check(mirt_set_soft_shadows(1, nullptr, 0), "mirt_set_soft_shadows");

@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libmirt.so")
 
 MAX_LIGHTS = 32
+MAX_LIGHT_POSITIONS = 256             # lights x soft-shadow samples (MIRT_MAX_LIGHT_POSITIONS: randomPositions[256], raytracer.cpp:84)
 RT_AUTO, RT_BRUTE, RT_BINNED = 0, 1, 2
 QUERY_AUTO, QUERY_BRUTE, QUERY_BINNED = 0, 1, 2
 KERNEL_NAMES = ("prep", "bin", "trace", "dof", "raster_setup", "raster_frag", "raster_resolve", "clear")
@@ -431,7 +432,9 @@ def set_antialiasing(samples):
 
 
 def set_soft_shadows(samples, positions=None):
-    """samples <= 1 turns soft shadows off; otherwise positions is (nlights*samples, 3)."""
+    """samples <= 1 turns soft shadows off; otherwise positions is (nlights*samples, 3), at most MAX_LIGHT_POSITIONS rows: up to
+    MAX_LIGHTS lights with nlights*samples <= MAX_LIGHT_POSITIONS.  Frames and direct_light* with more than MAX_LIGHTS positions run
+    DirectLight in passes (bit-identical); such frames cannot be combined with set_antialiasing."""
     if samples <= 1:
         _check(load().mirt_set_soft_shadows(1, None, 0))
         return

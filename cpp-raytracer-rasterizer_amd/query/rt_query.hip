@@ -348,10 +348,29 @@ __device__ __forceinline__ bool light_record(const QueryLightFrame &q, long long
     return valid;
 }
 
-template <int P, bool FILTER>
+// The accumulators of record `rec` between two passes of a call (light_passes.hpp): plane c of the carry at c * nhits.
+__device__ __forceinline__ void carry_load(const QueryLightFrame &q, long long rec, v3 *result, v3 *result2)
+{
+    const float *c = q.carry + rec;
+    const size_t n = (size_t)q.nhits;
+    *result = V3(c[0], c[n], c[2 * n]);
+    *result2 = V3(c[3 * n], c[4 * n], c[5 * n]);
+}
+__device__ __forceinline__ void carry_store(const QueryLightFrame &q, long long rec, v3 result, v3 result2)
+{
+    float *c = q.carry + rec;
+    const size_t n = (size_t)q.nhits;
+    c[0] = result.x; c[n] = result.y; c[2 * n] = result.z;
+    c[3 * n] = result2.x; c[4 * n] = result2.y; c[5 * n] = result2.z;
+}
+
+// CARRY: one pass of a call of several (light_passes.hpp) -- the accumulators come from the carry unless the pass is the first,
+// result2 takes result where the GLOBAL position closes a light, and they go back raw unless the pass is the last.
+template <int P, bool FILTER, bool CARRY = false>
 __device__ __forceinline__ void direct_light_body(const QueryLightFrame &q, float4 *s_tab)
 {
     const RtFrame &f = q.f;
+    const int first = CARRY ? q.first : 0;
     long long rec[P];
     bool ok[P], valid[P];
     v3 pos[P], nDir[P], tcol[P], result[P], result2[P];
@@ -363,6 +382,7 @@ __device__ __forceinline__ void direct_light_body(const QueryLightFrame &q, floa
         valid[p] = light_record(q, rec[p], ok[p], &pos[p], &t, &nDir[p]);
         tcol[p] = ld3(t + 12);
         result[p] = result2[p] = V3(0.0f, 0.0f, 0.0f);
+        if (CARRY && ok[p] && !(q.pass_flags & LIGHT_PASS_FIRST)) carry_load(q, rec[p], &result[p], &result2[p]);
     }
 
     for (int k = 0; k < f.nlights; k++) {
@@ -412,26 +432,28 @@ __device__ __forceinline__ void direct_light_body(const QueryLightFrame &q, floa
 #pragma unroll
         for (int p = 0; p < P; p++) {
             result[p] = add3(result[p], D[p]);                                             // :319
-            if ((k + 1) % f.samples == 0) result2[p] = add3(result2[p], result[p]);        // :322
+            if (light_pass_closes(first, k, f.samples)) result2[p] = add3(result2[p], result[p]);   // :322
         }
     }
 
 #pragma unroll
     for (int p = 0; p < P; p++) {
         if (!ok[p]) continue;
+        if (CARRY && !(q.pass_flags & LIGHT_PASS_LAST)) { carry_store(q, rec[p], result[p], result2[p]); continue; }
         st3(q.rgb + 3 * (size_t)rec[p], valid[p] ? reference_nan(mul3(result2[p], tcol[p]), pos[p]) : V3(0.0f, 0.0f, 0.0f));   // :325-326
     }
 }
 
-template <int P>
+template <int P, bool CARRY>
 __global__ __launch_bounds__(256) void k_query_direct_light(const QueryLightFrame q)
 {
     extern __shared__ __attribute__((aligned(16))) float4 s_tab[];
-    if (__builtin_amdgcn_readfirstlane(*q.f.unsafe) == 0u) direct_light_body<P, true>(q, s_tab);
-    else direct_light_body<P, false>(q, s_tab);
+    if (__builtin_amdgcn_readfirstlane(*q.f.unsafe) == 0u) direct_light_body<P, true, CARRY>(q, s_tab);
+    else direct_light_body<P, false, CARRY>(q, s_tab);
 }
 
-template __global__ void k_query_direct_light<QUERY_P>(const QueryLightFrame);
+template __global__ void k_query_direct_light<QUERY_P, false>(const QueryLightFrame);
+template __global__ void k_query_direct_light<QUERY_P, true>(const QueryLightFrame);
 
 // ---- k_query_direct_light_binned: DirectLight per hit record, every shadow ray through its light-cube bin ------------------
 //
@@ -487,11 +509,12 @@ __device__ __forceinline__ void flush_query_stats(unsigned long long *stats, uns
             if (sums[w]) atomicAdd(stats + w, sums[w]);
 }
 
-template <int P, bool STATS>
+template <int P, bool STATS, bool CARRY>
 __global__ __launch_bounds__(256) void k_query_direct_light_binned(const QueryBinnedFrame b)
 {
     const QueryLightFrame &q = b.q;
     const RtFrame &f = q.f;
+    const int first = CARRY ? q.first : 0;                         // (CARRY: direct_light_body's comment)
     const CubeView &cv = b.cube;
     const float4 *rows4 = reinterpret_cast<const float4 *>(cv.light_rows);
     const uint32_t face_bins = (uint32_t)(cv.cube_bins * cv.cube_bins) * 6u;
@@ -504,6 +527,7 @@ __global__ __launch_bounds__(256) void k_query_direct_light_binned(const QueryBi
         const float *t;
         const bool valid = light_record(q, rec, ok, &pos, &t, &nDir);
         v3 result = V3(0.0f, 0.0f, 0.0f), result2 = result;
+        if (CARRY && ok && !(q.pass_flags & LIGHT_PASS_FIRST)) carry_load(q, rec, &result, &result2);
         bool fell = false;
         for (int k = 0; k < f.nlights; k++) {
             const v3 L = ld3(f.lpos[k]);
@@ -565,16 +589,22 @@ __global__ __launch_bounds__(256) void k_query_direct_light_binned(const QueryBi
             }
             if (occluded) D = V3(0.0f, 0.0f, 0.0f);                                        // :314
             result = add3(result, D);                                                      // :319
-            if ((k + 1) % f.samples == 0) result2 = add3(result2, result);                 // :322
+            if (light_pass_closes(first, k, f.samples)) result2 = add3(result2, result);   // :322
         }
         if (STATS) n_fall += fell ? 1u : 0u;
+        if (CARRY && !(q.pass_flags & LIGHT_PASS_LAST)) {
+            if (ok) carry_store(q, rec, result, result2);
+            continue;
+        }
         if (ok) st3(q.rgb + 3 * (size_t)rec, valid ? reference_nan(mul3(result2, ld3(t + 12)), pos) : V3(0.0f, 0.0f, 0.0f));   // :325-326
     }
     if (STATS) flush_query_stats(b.stats, n_rays, n_cand, n_tests, n_fall);
 }
 
-template __global__ void k_query_direct_light_binned<QUERY_BIN_P, false>(const QueryBinnedFrame);
-template __global__ void k_query_direct_light_binned<QUERY_BIN_P, true>(const QueryBinnedFrame);
+template __global__ void k_query_direct_light_binned<QUERY_BIN_P, false, false>(const QueryBinnedFrame);
+template __global__ void k_query_direct_light_binned<QUERY_BIN_P, true, false>(const QueryBinnedFrame);
+template __global__ void k_query_direct_light_binned<QUERY_BIN_P, false, true>(const QueryBinnedFrame);
+template __global__ void k_query_direct_light_binned<QUERY_BIN_P, true, true>(const QueryBinnedFrame);
 
 // ---- k_query_fan: ClosestIntersection for many directions from one origin, every ray tests every triangle ------------------
 //

@@ -5,6 +5,7 @@
 
 #include "../csrc/rt_common.hpp"
 #include "../csrc/rt_binned.hpp"
+#include "light_passes.hpp"
 
 #include <string.h>
 
@@ -42,11 +43,17 @@ struct QueryFrame {
 
 // DirectLight for `nhits` records: f carries the scene, the light positions / colours, the light origin tables (k_prep_origin)
 // and their `unsafe` flag; nothing of f that describes a view or an output plane is read.
+// A call of more than MIRT_MAX_LIGHTS positions runs as several passes (light_passes.hpp; the CARRY instantiations of the kernels):
+// f holds the pass's own f.nlights <= MIRT_MAX_LIGHTS positions, `first` says where they stand in the call's list, and the
+// accumulators travel from pass to pass in `carry`.  The kernels of a call of one pass read none of the three.
 struct QueryLightFrame {
     RtFrame f;
     const uint32_t *hits;       // nhits x HIT_WORDS: position and index are read
     int nhits;
     float *rgb;                 // nhits x 3
+    int first;                  // global index of the pass's position 0
+    float *carry;               // LIGHT_CARRY_WORDS planes of nhits floats: result, result2
+    int pass_flags;             // LIGHT_PASS_FIRST | LIGHT_PASS_LAST
 };
 
 // DirectLight for `nhits` records with every shadow ray walking its light-cube bin (k_query_direct_light_binned): q.f.light_tab
@@ -184,9 +191,9 @@ constexpr int QUERY_BLOCK_RAYS = 256 * QUERY_P;
 __attribute__((global)) void k_query_rows(const float *, int, QueryRow *, uint32_t *);
 template <int P> __attribute__((global)) void k_query_closest(const QueryFrame);
 __attribute__((global)) void k_query_closest_wave(const QueryFrame);
-template <int P> __attribute__((global)) void k_query_direct_light(const QueryLightFrame);
+template <int P, bool CARRY = false> __attribute__((global)) void k_query_direct_light(const QueryLightFrame);
 constexpr int QUERY_BIN_P = 1;                    // records per lane of the binned DirectLight kernel: lists differ per lane
-template <int P, bool STATS = false> __attribute__((global)) void k_query_direct_light_binned(const QueryBinnedFrame);
+template <int P, bool STATS = false, bool CARRY = false> __attribute__((global)) void k_query_direct_light_binned(const QueryBinnedFrame);
 template <int P> __attribute__((global)) void k_query_fan(const QueryFanFrame);
 template <bool STATS> __attribute__((global)) void k_query_fan_binned(const QueryFanFrame);
 template <bool STATS> __attribute__((global)) void k_query_fans_binned(const QueryFansFrame);

@@ -35,6 +35,9 @@ extern "C" {
 #define MIRT_API __attribute__((visibility("default")))
 #define MIRT_ABI_VERSION 4
 #define MIRT_MAX_LIGHTS 32            /* Light lights[32], raytracer.cpp:48 / rasteriser.cpp:50 */
+/* Most light POSITIONS of a ray-traced frame or a DirectLight query: lights x soft-shadow samples (vec3 randomPositions[256],
+ * raytracer.cpp:84).  MIRT_MAX_LIGHTS stays the most lights, and the most positions one pass and one light cube take. */
+#define MIRT_MAX_LIGHT_POSITIONS 256
 
 typedef enum mirt_status {
     MIRT_OK = 0,
@@ -297,7 +300,18 @@ MIRT_API int mirt_pose(const float *rest15, int nrest, const mirt_object *object
  * 272-287): when samples > 1 every light k is replaced in DirectLight by `samples` jittered positions
  * positions[(k*samples + i)*3 .. +2] with 1/samples of its power each.  The caller generates the positions (the
  * reference draws them with rand() in AddLight; host/mirt_draw.hpp does the same).  samples <= 1 switches back to
- * hard shadows.  lights x samples may not exceed MIRT_MAX_LIGHTS. */
+ * hard shadows.  samples in [2, MIRT_MAX_LIGHT_POSITIONS], samples <= npositions <= MIRT_MAX_LIGHT_POSITIONS; a call with
+ * nlights lights (at most MIRT_MAX_LIGHTS) needs nlights x samples <= npositions positions.  With the reference's 16 samples
+ * that is its own limit of sixteen lights.
+ * More than MIRT_MAX_LIGHTS positions.  The fused frame kernels carry MIRT_MAX_LIGHTS positions.  A ray-traced frame with more
+ * (every mirt_raytrace* form, row bands and depth of field included) is rendered deferred: its primary rays without light, then
+ * DirectLight over one hit record per pixel in passes of at most MIRT_MAX_LIGHTS positions -- DirectLight's two accumulators
+ * are carried from pass to pass, so every bit is the single loop's --, then pixelColours.  The frame's `mode` chooses the
+ * passes' kernels as it chooses the frame's (mirt_set_query_mode does not govern frames); mirt_stats reports the primary pass's
+ * mode_used and shadow_rays = positions x pixels that hit.  Supersampling (mirt_set_antialiasing) shades a carried record per
+ * sub-ray, which one record per pixel cannot follow: a frame with more than MIRT_MAX_LIGHTS positions AND supersampling on
+ * returns MIRT_ERR_INVALID_ARGUMENT.  MIRT_MANY_LIGHTS_MIN (environment, default 33) lowers the position count from which
+ * frames without supersampling are deferred. */
 MIRT_API int mirt_set_soft_shadows(int samples, const float *positions, int npositions);
 
 /* Depth of field (DOF_ENABLED / DOF_KERNEL_SIZE / FOCAL_LENGTH, raytracer.cpp:43-45,613-640; rasteriser.cpp:29-31,
@@ -367,7 +381,11 @@ MIRT_API int mirt_intersect(const mirt_ray *rays, int nrays, mirt_hit *hits);
 MIRT_API int mirt_intersect_device(const void *d_rays, int nrays, void *d_hits);
 /* out_rgb[3*i ..] = DirectLight(hits[i]) for the given lights, with the reference's `result2 += result` double count (:319-322)
  * and the final multiply by the triangle's colour (:325-326), under the current mirt_set_soft_shadows state.  Only position and
- * index of a record are read; an index outside [0, n) -- the reference would index outside `triangles` -- yields (0, 0, 0). */
+ * index of a record are read; an index outside [0, n) -- the reference would index outside `triangles` -- yields (0, 0, 0).
+ * nlights <= MIRT_MAX_LIGHTS and nlights x samples <= MIRT_MAX_LIGHT_POSITIONS.  More than MIRT_MAX_LIGHTS positions are answered
+ * in passes over consecutive ranges of at most MIRT_MAX_LIGHTS positions (a range may end inside a light): the accumulators
+ * `result` and `result2` travel between the passes in per-stream scratch (24 bytes per record), so the additions, their operands
+ * and their order are the single loop's and no bit differs.  Binned, every pass walks a kept cube of its own range's positions. */
 MIRT_API int mirt_direct_light(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, float *out_rgb);
 MIRT_API int mirt_direct_light_device(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_rgb);
 
@@ -385,7 +403,11 @@ MIRT_API int mirt_set_query_mode(int mode);
  * by this call, 2 kept from an earlier query, 3 the frame path's.  The four counters are filled for a binned call made with
  * mirt_set_profiling(1) and zero otherwise: shadow rays (records inside the scene x light positions), candidate rows offered to
  * them, tests executed, and records for which a light position swept its whole table because the cube's ray family does not
- * cover their shadow ray (a position that is not finite, equals the light or lies beyond float range of it). */
+ * cover their shadow ray (a position that is not finite, equals the light or lies beyond float range of it).
+ * A call of several passes (more than MIRT_MAX_LIGHTS positions): the four counters are summed over the passes (fallback_records
+ * counts a record once per pass in which it swept), cube_bins and shells are the last pass's, and cube_source is 0 none, 1 some
+ * pass built its cube, 2 every pass's cube was held -- 3 only for a call of one pass.  Binned or brute is decided once for the
+ * whole call, `held` meaning that every pass's cube is. */
 typedef struct mirt_query_stats {
     int32_t mode_used;                /* MIRT_QUERY_BRUTE or MIRT_QUERY_BINNED                   */
     int32_t cube_source;

@@ -1,0 +1,443 @@
+"""Soft shadows past 32 light positions: mirt_direct_light* and ray-traced frames with up to 256 positions (lights x samples).
+
+DirectLight runs in passes of at most 32 positions that hand `result` and `result2` on (query/light_passes.hpp); a frame with more
+than 32 positions renders its primary rays without light, runs those passes over one record per pixel and resolves pixelColours
+(lights/many_lights.hip).  Every comparison is bit for bit against the CPU oracle's single loop -- oracle.direct_light and
+oracle.raytrace(samples=, jitter=) take any position count -- and the oracle's answers are computed once per case and shared.
+
+Light sets and what each exercises: 3 x 11 = 33 (the cut at 32 falls inside light 2, the second pass holds one position),
+4 x 16 = 64 (the cut falls on a light's end), 1 x 40 (result2 is added once, at the very end), 16 x 16 = 256 (the reference's
+whole randomPositions array)."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import mirt
+import query_helpers as rq
+from devbuf import DeviceArray, to_device
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SETS = {"3x11": (3, 11), "4x16": (4, 16), "1x40": (1, 40), "16x16": (16, 16)}
+MODES = (("brute", mirt.QUERY_BRUTE), ("binned", mirt.QUERY_BINNED), ("auto", mirt.QUERY_AUTO))
+FILL, FILLW = 0x5A, 0x5A5A5A5A
+INDIRECT = (0.2, 0.2, 0.2)
+_hits, _cases, _frames = {}, {}, {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def device():
+    mirt.init(0)
+    yield
+    mirt.set_query_mode(mirt.QUERY_AUTO)
+    mirt.set_profiling(False)
+    mirt.set_soft_shadows(1)
+    mirt.set_antialiasing(1)
+    mirt.set_depth_of_field(0)
+    mirt.set_frames_in_flight(1)
+    mirt.shutdown()
+
+
+def lights_of(n, seed=11):
+    """n lights on dyadic coordinates inside the scenes' box, the first the fans' tests' own; colours and powers differ."""
+    rng = np.random.default_rng(seed)
+    L = np.zeros((n, 7), np.float32)
+    L[:, 0:3] = np.round(rng.uniform(-0.75, 0.75, (n, 3)) * 64) / 64
+    L[:, 3:6] = rng.choice(np.array([0.25, 0.5, 0.75, 1.0], np.float32), (n, 3))
+    L[:, 6] = rng.integers(3, 15, n)
+    L[0] = rq.LIGHTS[0]
+    return L
+
+
+def light_set(oracle, name):
+    nl, samples = SETS[name]
+    L = lights_of(nl)
+    return L, samples, rq.jitter(oracle, L, samples, seed=3)
+
+
+def scene_hits(name):
+    """The closest hits of two batches of 257 and 513 rays (computed once per scene; the scene is left uploaded)."""
+    tris, a, b = rq.scene_of(name)
+    mirt.scene_upload(tris)
+    if name not in _hits:
+        _hits[name] = np.concatenate([mirt.intersect(rq.make_batch(257, a, b, seed=7)), mirt.intersect(rq.make_batch(513, a, b, seed=8))])
+        assert (_hits[name]["index"] >= 0).sum() > 200
+    return tris, _hits[name]
+
+
+def case(oracle, scene, lset):
+    """(triangles, records, lights, samples, jitter, the oracle's DirectLight of every record), once per (scene, light set).  The
+    records: the scene's hits with odd ones mixed in -- index -1, index n, a NaN coordinate, and a position equal to a light position
+    of the SECOND pass (DirectLight's 0 / 0)."""
+    tris, hits = scene_hits(scene)
+    key = (scene, lset)
+    if key not in _cases:
+        L, samples, jit = light_set(oracle, lset)
+        recs = hits.copy()
+        n = len(tris)
+        ids = np.flatnonzero(recs["index"] >= 0)
+        recs["index"][ids[3]] = -1
+        recs["index"][ids[5::97]] = n
+        recs["position"][ids[10]][1] = np.float32("nan")
+        recs["position"][ids[20]] = jit[32]
+        recs["position"][ids[21]] = jit[len(jit) - 1]
+        want = rq.oracle_direct_light(oracle, tris, recs, L, samples=samples, jitter=jit)
+        assert np.isnan(want).any() and (want[np.isfinite(want).all(axis=1)] > 0).any()
+        want.setflags(write=False)
+        _cases[key] = (tris, recs, L, samples, jit, want)
+    return _cases[key]
+
+
+def device_direct_light(recs, L):
+    d_hits = to_device(recs)
+    with DeviceArray((len(recs), 3), np.float32, FILL) as d_rgb:
+        mirt.direct_light_device(d_hits.ptr, len(recs), L, d_rgb.ptr)
+        got = d_rgb.read()
+    d_hits.free()
+    return got
+
+
+# ---- DirectLight ---------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("lset", list(SETS))
+@pytest.mark.parametrize("scene", ["cornell", "soup2000"])
+def test_direct_light_in_passes_equals_the_single_loop(oracle, scene, lset):
+    tris, recs, L, samples, jit, want = case(oracle, scene, lset)
+    mirt.set_soft_shadows(samples, jit)
+    try:
+        for mname, mode in MODES:
+            mirt.set_query_mode(mode)
+            what = "%s %s %s" % (scene, lset, mname)
+            rq.same_bits(mirt.direct_light(recs, L), want, what + " host")
+            st = mirt.query_stats()
+            if mode != mirt.QUERY_AUTO:
+                assert st["mode_used"] == mode, (what, st)
+            assert (st["cube_source"] in (1, 2)) == (st["mode_used"] == mirt.QUERY_BINNED), (what, st)
+            rq.same_bits(device_direct_light(recs, L), want, what + " device")
+            one = np.flatnonzero((recs["index"] >= 0) & (recs["index"] < len(tris)))[7]
+            rq.same_bits(mirt.direct_light(recs[one:one + 1], L), want[one:one + 1], what + " single record")
+    finally:
+        mirt.set_query_mode(mirt.QUERY_AUTO)
+        mirt.set_soft_shadows(1)
+
+
+def test_kept_cubes_serve_a_repeated_call_and_one_moved_position_rebuilds(oracle):
+    tris, recs, L, samples, jit, want = case(oracle, "soup2000", "4x16")
+    mirt.set_query_mode(mirt.QUERY_BINNED)
+    try:
+        mirt.set_soft_shadows(samples, jit)
+        first = mirt.direct_light(recs, L)
+        again = mirt.direct_light(recs, L)
+        st = mirt.query_stats()
+        assert st["mode_used"] == mirt.QUERY_BINNED and st["cube_source"] == 2 and st["cube_bins"] > 0, st
+        rq.same_bits(first, want, "first call")
+        rq.same_bits(again, first, "repeated call")
+        moved = jit.copy()
+        moved[40] += np.float32(1.0 / 64)                       # a position of the second pass only
+        mirt.set_soft_shadows(samples, moved)
+        got = mirt.direct_light(recs, L)
+        assert mirt.query_stats()["cube_source"] == 1
+        rq.same_bits(got, rq.oracle_direct_light(oracle, tris, recs, L, samples=samples, jitter=moved), "one position moved")
+        mirt.direct_light(recs, L)
+        assert mirt.query_stats()["cube_source"] == 2
+    finally:
+        mirt.set_query_mode(mirt.QUERY_AUTO)
+        mirt.set_soft_shadows(1)
+
+
+def test_counters_add_up_over_the_passes(oracle):
+    tris, recs, L, samples, jit, want = case(oracle, "soup2000", "3x11")
+    valid = int(((recs["index"] >= 0) & (recs["index"] < len(tris))).sum())
+    mirt.set_query_mode(mirt.QUERY_BINNED)
+    mirt.set_profiling(True)
+    try:
+        mirt.set_soft_shadows(samples, jit)
+        rq.same_bits(mirt.direct_light(recs, L), want, "profiling on")
+        st = mirt.query_stats()
+        assert st["shadow_rays"] == valid * len(jit), (st, valid, len(jit))
+        assert st["tests"] > 0 and st["candidates"] >= st["tests"] and st["fallback_records"] >= 3, st   # the NaN record sweeps in both passes
+    finally:
+        mirt.set_profiling(False)
+        mirt.set_query_mode(mirt.QUERY_AUTO)
+        mirt.set_soft_shadows(1)
+
+
+@pytest.mark.parametrize("mode", [mirt.QUERY_BRUTE, mirt.QUERY_BINNED])
+def test_two_calls_in_flight_keep_their_own_carry(oracle, mode):
+    tris, recs, La, sa, ja, want_a = case(oracle, "soup2000", "4x16")
+    _, recs_b, Lb, sb, jb, want_b = case(oracle, "soup2000", "3x11")
+    mirt.set_query_mode(mode)
+    mirt.set_frames_in_flight(2)
+    d_a, d_b = to_device(recs), to_device(recs_b)
+    try:
+        with DeviceArray((len(recs), 3), np.float32, FILL) as out_a, DeviceArray((len(recs_b), 3), np.float32, FILL) as out_b:
+            for _ in range(2):
+                mirt.set_soft_shadows(sa, ja)
+                mirt.direct_light_device(d_a.ptr, len(recs), La, out_a.ptr)
+                mirt.set_soft_shadows(sb, jb)
+                mirt.direct_light_device(d_b.ptr, len(recs_b), Lb, out_b.ptr)
+            mirt.sync()
+            rq.same_bits(out_a.read(), want_a, "first stream")
+            rq.same_bits(out_b.read(), want_b, "second stream")
+    finally:
+        d_a.free()
+        d_b.free()
+        mirt.set_frames_in_flight(1)
+        mirt.set_query_mode(mirt.QUERY_AUTO)
+        mirt.set_soft_shadows(1)
+
+
+def test_a_call_of_one_pass_right_after_a_call_of_two(oracle):
+    tris, recs, L, samples, jit, want = case(oracle, "soup2000", "4x16")
+    want32 = rq.oracle_direct_light(oracle, tris, recs, L[:2], samples=samples, jitter=jit[:32])
+    try:
+        for mode in (mirt.QUERY_BINNED, mirt.QUERY_BRUTE):
+            mirt.set_query_mode(mode)
+            mirt.set_soft_shadows(samples, jit)
+            rq.same_bits(mirt.direct_light(recs, L), want, "64 positions")
+            rq.same_bits(mirt.direct_light(recs, L[:2]), want32, "32 positions after 64")
+    finally:
+        mirt.set_query_mode(mirt.QUERY_AUTO)
+        mirt.set_soft_shadows(1)
+
+
+# ---- frames --------------------------------------------------------------------------------------------------------------------------
+
+FRAMES = {
+    "cornell": dict(tris=lambda: mirt.scene_cornell(), cam=(0.0, 0.0, -2.0), yaw=0.1, W=64, H=48, sets=(3, 16)),
+    "soup": dict(tris=lambda: mirt.scene_soup(33, 700, 0.12), cam=(0.1, 0.0, -2.2), yaw=0.15, W=80, H=56, sets=(3, 11)),
+}
+
+
+def frame_ref(oracle, name, nl=None, samples=None):
+    """The oracle's frame of a scene under nl lights x samples jittered positions, once per (scene, lights)."""
+    F = FRAMES[name]
+    nl, samples = (nl or F["sets"][0]), (samples or F["sets"][1])
+    key = (name, nl, samples)
+    if key not in _frames:
+        tris = F["tris"]()
+        L = lights_of(nl, seed=5)
+        jit = rq.jitter(oracle, L, samples, seed=9) if samples > 1 else None
+        rot = oracle.rot_from_yaw(F["yaw"], 1.0)
+        W, H = F["W"], F["H"]
+        ref = oracle.raytrace(tris, F["cam"], rot, H / 2.0, W, H, L, samples=samples, jitter=jit, threads=4)
+        hit = ref["index"] >= 0                                 # (the frame has pixels of both kinds, a few hundred each)
+        assert hit.sum() >= 200 and (~hit).sum() >= 200 and ref["nshadow"] == int(hit.sum()) * nl * samples
+        ref.update(tris=tris, L=L, jit=jit, samples=samples, view=mirt.make_view(F["cam"], rot, H / 2.0, W, H), W=W, H=H)
+        _frames[key] = ref
+    return _frames[key]
+
+
+def same_frame(got, ref, what):
+    W, H = ref["W"], ref["H"]
+    assert np.array_equal(got["index"], ref["index"]), what
+    rq.same_bits(got["dist"], ref["dist"], what + " distance")
+    rq.same_bits(got["pos"], ref["pos"], what + " position")
+    rq.same_bits(got["rgb"], ref["rgb"], what + " rgb")
+    assert np.array_equal(got["xrgb"][1:-1, 1:-1], ref["xrgb"][1:-1, 1:-1]), what + " xrgb"
+    border = np.ones((H, W), bool)
+    border[1:-1, 1:-1] = False
+    assert (got["xrgb"][border] == FILLW).all(), what + ": border words written"
+
+
+@pytest.mark.parametrize("name,mode", [("cornell", mirt.RT_AUTO), ("cornell", mirt.RT_BRUTE), ("cornell", mirt.RT_BINNED),
+                                       ("soup", mirt.RT_BRUTE), ("soup", mirt.RT_BINNED)])
+def test_frame_with_more_than_32_positions(oracle, name, mode):
+    ref = frame_ref(oracle, name)
+    mirt.scene_upload(ref["tris"])
+    mirt.set_soft_shadows(ref["samples"], ref["jit"])
+    try:
+        for rep in range(2):                                     # (the second frame finds every cube held)
+            canvas = np.full((ref["H"], ref["W"]), FILLW, np.uint32)
+            got = mirt.raytrace(ref["view"], ref["L"], INDIRECT, mode=mode, xrgb=canvas, want_intersection=True)
+            same_frame(got, ref, "%s mode %d frame %d" % (name, mode, rep))
+            assert got["stats"]["shadow_rays"] == ref["nshadow"], got["stats"]
+            if mode != mirt.RT_AUTO:
+                assert got["stats"]["mode_used"] == mode
+    finally:
+        mirt.set_soft_shadows(1)
+
+
+def test_profiled_deferred_frame_times_its_steps(oracle):
+    """With profiling on the records, passes and resolve count as the frame's trace step and the cube builds as its binning step;
+    the frame is the oracle's all the same -- with cubes no call has built before, and again with every cube held."""
+    base = frame_ref(oracle, "soup")
+    F = FRAMES["soup"]
+    jit = (base["jit"] + np.float32(1.0 / 128)).astype(np.float32)
+    ref = oracle.raytrace(base["tris"], F["cam"], oracle.rot_from_yaw(F["yaw"], 1.0), base["H"] / 2.0, base["W"], base["H"], base["L"],
+                          samples=base["samples"], jitter=jit, threads=4)
+    mirt.scene_upload(base["tris"])
+    mirt.set_soft_shadows(base["samples"], jit)
+    mirt.set_profiling(True)
+    try:
+        for rep in range(2):
+            got = mirt.raytrace(base["view"], base["L"], INDIRECT, mode=mirt.RT_BINNED)
+            rq.same_bits(got["rgb"], ref["rgb"], "profiled frame %d" % rep)
+            st = got["stats"]
+            assert st["mode_used"] == mirt.RT_BINNED and st["shadow_rays"] == ref["nshadow"], st
+            assert st["kernel_ms"]["trace"] > 0 and st["gpu_ms"] >= st["kernel_ms"]["trace"], st
+            assert rep > 0 or st["kernel_ms"]["bin"] > 0, st     # (the first frame bins the camera's tiles and builds two cubes)
+    finally:
+        mirt.set_profiling(False)
+        mirt.set_soft_shadows(1)
+
+
+def test_band_of_a_deferred_frame_with_row_origin(oracle):
+    ref = frame_ref(oracle, "cornell")
+    W, H, y0, y1 = ref["W"], ref["H"], 8, 40
+    mirt.scene_upload(ref["tris"])
+    mirt.set_soft_shadows(ref["samples"], ref["jit"])
+    try:
+        with DeviceArray((y1 - y0, W), np.uint32, FILL) as surf, DeviceArray((H, W, 3), np.float32, FILL) as rgb, \
+                DeviceArray((H, W), np.int32, FILL) as index:
+            mirt.raytrace_device(ref["view"], ref["L"], INDIRECT, mirt.RT_AUTO, y0, y1, y0, surf.ptr, W * 4, rgb.ptr, index.ptr)
+            got, got_rgb, got_index = surf.read(), rgb.read(), index.read()
+        assert np.array_equal(got_index[y0:y1], ref["index"][y0:y1])
+        rq.same_bits(got_rgb[y0:y1], ref["rgb"][y0:y1], "band rgb")
+        assert np.array_equal(got[:, 1:-1], ref["xrgb"][y0:y1, 1:-1]) and (got[:, 0] == FILLW).all() and (got[:, -1] == FILLW).all()
+        assert (got_index[:y0] == FILLW).all() and (got_index[y1:] == FILLW).all(), "rows outside the band written"
+        assert (got_rgb[:y0].view(np.uint32) == FILLW).all() and (got_rgb[y1:].view(np.uint32) == FILLW).all()
+    finally:
+        mirt.set_soft_shadows(1)
+
+
+def test_depth_of_field_over_a_deferred_frame(oracle):
+    ref = frame_ref(oracle, "cornell")
+    K, FL = 4, 1.3
+    fd = np.where(ref["index"] >= 0, ref["dist"] - np.float32(FL), np.float32(0)).astype(np.float32)
+    want = oracle.dof(ref["rgb"], fd, K, xrgb=np.full((ref["H"], ref["W"]), FILLW, np.uint32))
+    assert not np.array_equal(want[1:-1, 1:-1], ref["xrgb"][1:-1, 1:-1]), "the blur changed nothing"
+    mirt.scene_upload(ref["tris"])
+    mirt.set_soft_shadows(ref["samples"], ref["jit"])
+    mirt.set_depth_of_field(K, FL)
+    try:
+        canvas = np.full((ref["H"], ref["W"]), FILLW, np.uint32)
+        got = mirt.raytrace(ref["view"], ref["L"], INDIRECT, xrgb=canvas)
+        assert np.array_equal(got["xrgb"], want)
+        rq.same_bits(got["rgb"], ref["rgb"], "the unblurred pixelColours")
+        assert np.array_equal(got["index"], ref["index"])
+    finally:
+        mirt.set_depth_of_field(0)
+        mirt.set_soft_shadows(1)
+
+
+def test_deferred_and_fused_frames_alternate_on_two_streams(oracle):
+    many, few = frame_ref(oracle, "cornell"), frame_ref(oracle, "cornell", 1, 16)
+    W, H = many["W"], many["H"]
+    mirt.scene_upload(many["tris"])
+    mirt.set_frames_in_flight(2)
+    try:
+        with DeviceArray((H, W), np.uint32, FILL) as sa, DeviceArray((H, W), np.uint32, FILL) as sb, \
+                DeviceArray((H, W, 3), np.float32, FILL) as ra, DeviceArray((H, W, 3), np.float32, FILL) as rb:
+            for _ in range(3):
+                mirt.set_soft_shadows(16, many["jit"])
+                mirt.raytrace_device(many["view"], many["L"], INDIRECT, mirt.RT_AUTO, 0, H, 0, sa.ptr, W * 4, ra.ptr)
+                mirt.set_soft_shadows(16, few["jit"])
+                mirt.raytrace_device(few["view"], few["L"], INDIRECT, mirt.RT_AUTO, 0, H, 0, sb.ptr, W * 4, rb.ptr)
+            mirt.sync()
+            for surf, rgb, ref, what in ((sa, ra, many, "48 positions"), (sb, rb, few, "16 positions")):
+                rq.same_bits(rgb.read(), ref["rgb"], what)
+                assert np.array_equal(surf.read()[1:-1, 1:-1], ref["xrgb"][1:-1, 1:-1]), what
+    finally:
+        mirt.set_frames_in_flight(1)
+        mirt.set_soft_shadows(1)
+
+
+def test_supersampling_with_more_than_32_positions_is_refused(oracle):
+    ref = frame_ref(oracle, "cornell")
+    mirt.scene_upload(ref["tris"])
+    mirt.set_soft_shadows(ref["samples"], ref["jit"])
+    mirt.set_antialiasing(3)
+    try:
+        with pytest.raises(mirt.MirtError, match="supersampling"):
+            mirt.raytrace(ref["view"], ref["L"], INDIRECT)
+        mirt.raytrace(ref["view"], ref["L"][:2], INDIRECT)          # 32 positions: the fused kernels, as before
+    finally:
+        mirt.set_antialiasing(1)
+        mirt.set_soft_shadows(1)
+
+
+# ---- limits --------------------------------------------------------------------------------------------------------------------------
+
+def test_limits():
+    assert mirt.MAX_LIGHT_POSITIONS == 256
+    tris = mirt.scene_cornell()
+    mirt.scene_upload(tris)
+    rec = mirt.intersect(mirt.make_rays((0, 0, -2), (0.01, 0.02, 1)))
+    assert rec["index"][0] >= 0
+    pos = np.linspace(-0.5, 0.5, 257 * 3, dtype=np.float32).reshape(257, 3)
+    try:
+        with pytest.raises(mirt.MirtError, match="exceed"):
+            mirt.set_soft_shadows(16, pos)                       # 257 positions
+        with pytest.raises(mirt.MirtError):
+            mirt.set_soft_shadows(257, pos)
+        mirt.set_soft_shadows(16, pos[:256])                     # 256 are accepted ...
+        out = mirt.direct_light(rec, lights_of(16))              # ... and used
+        assert np.isfinite(out).all()
+        with pytest.raises(mirt.MirtError, match="exceed"):
+            mirt.direct_light(rec, lights_of(17))                # 17 x 16 = 272
+        view = mirt.make_view((0, 0, -2), np.eye(3, dtype=np.float32).ravel(), 16.0, 32, 32)
+        with pytest.raises(mirt.MirtError, match="exceed"):
+            mirt.raytrace(view, lights_of(17))
+        mirt.set_soft_shadows(256, pos[:256])                    # one light of 256 samples
+        assert np.isfinite(mirt.direct_light(rec, lights_of(1))).all()
+    finally:
+        mirt.set_soft_shadows(1)
+
+
+# ---- forced deferral: MIRT_MANY_LIGHTS_MIN ---------------------------------------------------------------------------------------
+
+CHILD = r"""
+import sys, numpy as np
+sys.path[:0] = [%r, %r, %r]
+import mirt
+want = np.load(%r)
+mirt.init(0)
+mirt.scene_upload(mirt.scene_cornell())
+view = mirt.make_view(want["cam"], want["rot"], float(want["focal"]), int(want["W"]), int(want["H"]))
+for tag, nl, samples in (("soft", 2, 16), ("hard", 1, 1)):
+    mirt.set_soft_shadows(samples, want["jit"] if samples > 1 else None)
+    for mode in (mirt.RT_AUTO, mirt.RT_BRUTE, mirt.RT_BINNED):
+        got = mirt.raytrace(view, want["L"][:nl], mode=mode, want_intersection=True)
+        for plane in ("rgb", "index", "dist", "pos", "xrgb"):
+            a = np.ascontiguousarray(got[plane])
+            for side in ("fused", "oracle"):
+                b = want["%%s_%%s_%%s" %% (tag, side, plane)]
+                inner = (slice(1, -1), slice(1, -1)) if plane == "xrgb" else ()
+                assert np.ascontiguousarray(a[inner]).tobytes() == np.ascontiguousarray(b[inner]).tobytes(), (tag, mode, plane, side)
+        assert got["stats"]["shadow_rays"] == int(want[tag + "_nshadow"]), (tag, mode, got["stats"])
+mirt.shutdown()
+print("ok")
+"""
+
+
+def test_forced_deferral_equals_the_fused_path_and_the_oracle(oracle, tmp_path):
+    """MIRT_MANY_LIGHTS_MIN=1 in a child process sends frames the fused kernels render -- 2 x 16 positions, and one hard-shadow
+    light -- down the deferred path: the bytes must be the fused path's, recorded here, and the oracle's."""
+    ref = frame_ref(oracle, "cornell", 2, 16)
+    F = FRAMES["cornell"]
+    rot = oracle.rot_from_yaw(F["yaw"], 1.0)
+    W, H = ref["W"], ref["H"]
+    mirt.scene_upload(ref["tris"])
+    data = dict(cam=np.array(F["cam"], np.float32), rot=rot, focal=H / 2.0, W=W, H=H, L=ref["L"], jit=ref["jit"])
+    try:
+        for tag, nl, samples in (("soft", 2, 16), ("hard", 1, 1)):
+            mirt.set_soft_shadows(samples, ref["jit"] if samples > 1 else None)
+            fused = mirt.raytrace(ref["view"], ref["L"][:nl], want_intersection=True)
+            orc = ref if samples > 1 else oracle.raytrace(ref["tris"], F["cam"], rot, H / 2.0, W, H, ref["L"][:nl], threads=4)
+            for plane in ("rgb", "index", "dist", "pos", "xrgb"):
+                data["%s_fused_%s" % (tag, plane)] = fused[plane]
+                data["%s_oracle_%s" % (tag, plane)] = orc[plane]
+            data[tag + "_nshadow"] = orc["nshadow"]
+    finally:
+        mirt.set_soft_shadows(1)
+    path = str(tmp_path / "fused.npz")
+    np.savez(path, **data)
+    code = CHILD % (os.path.join(ROOT, "cpp-raytracer-rasterizer_amd"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"), path)
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MIRT_MANY_LIGHTS_MIN="1"), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr

@@ -9,7 +9,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIRS = [os.path.join(ROOT, "cpp-raytracer-rasterizer_amd", d) for d in ("csrc", "query", "scene")]
+DIRS = [os.path.join(ROOT, "cpp-raytracer-rasterizer_amd", d) for d in ("csrc", "query", "scene", "lights")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-x", "hip", "--cuda-device-only", "-S"]
 bad = []
 rows = []
@@ -47,6 +47,9 @@ EXPECT = ("k_rt_trace2", "k_rt_tile2", "k_rt_brute", "k_bin_pairs", "k_raster_sm
           "k_query_rows", "k_query_closest<", "k_query_closest_wave", "k_query_direct_light<", "k_query_direct_light_binned",
           "k_query_fan<", "k_query_fan_binned<false>", "k_query_fan_binned<true>", "k_query_fans_binned<false>", "k_query_fans_binned<true>",
           "k_query_fans_expand",
+          "k_query_direct_light<2, false>", "k_query_direct_light<2, true>", "k_query_direct_light_binned<1, false, false>",
+          "k_query_direct_light_binned<1, true, false>", "k_query_direct_light_binned<1, false, true>", "k_query_direct_light_binned<1, true, true>",
+          "k_frame_records", "k_frame_resolve",
           "k_scene_bounds_init", "k_scene_range<1>", "k_scene_range<3>", "k_scene_range<5>", "k_scene_range<7>", "k_scene_range<4>", "k_scene_range<11>")
 missing = [k for k in EXPECT if not any(k in r[1] for r in rows)]
 if missing or len(rows) < 20:
