@@ -304,11 +304,13 @@ struct QueryRows {
     // scene version and origin (light_key_of), built by light_cache_ensure under the same protocol.  Apart from `cube`, so that a
     // probe does not evict DirectLight's lights nor a DirectLight query the probe's origin.
     LightCache fan;
-    // The cube of the many-origin fans (mirt_intersect_fans*): up to MIRT_MAX_LIGHTS of the call's origins as its positions, keyed
-    // by scene version, positions and their order (light_key_of), built by light_cache_ensure under the same protocol.  A call of
-    // several passes leaves the last range's cube here.  Apart from `fan` and `cube`: the call evicts neither, and a pass whose
-    // positions are the ones g.lc or `cube` holds reads that cube instead (query.cpp: walk_cube).
-    LightCache fans;
+    // The cubes of the many-origin fans (mirt_intersect_fans*, mirt_occluded_fans*): up to MIRT_MAX_LIGHTS of the call's origins as
+    // a cube's positions, keyed by scene version, positions and their order (light_key_of), built by light_cache_ensure under the
+    // same protocol.  Pass p of a call keeps its range's cube in fans[p % QUERY_LIGHT_CUBES], as DirectLight's passes do in
+    // `cubes`, so that a repeated call of up to QUERY_LIGHT_CUBES passes builds nothing; entry 0 is the cube of a call of one pass.
+    // Apart from `fan` and `cubes`: the call evicts neither, and a pass whose positions are the ones g.lc or cubes[0] holds reads
+    // that cube instead (query.cpp: walk_cube).
+    LightCache fans[QUERY_LIGHT_CUBES];
 
     void release();                              // (the cubes' tables too)
 };

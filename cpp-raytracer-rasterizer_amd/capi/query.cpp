@@ -446,8 +446,8 @@ int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, vo
 // whose origin lies outside the pass's range retires after reading its index.  Every ray belongs to exactly one pass, so records
 // never meet; no pass is skipped, because which origins the rays name is device data.  The cube of a pass: the frame path's (g.lc)
 // or DirectLight's (g.qrows.cube) when it holds these very positions on this very grid -- read, never written, nor their tracking
-// --, else the call's own (g.qrows.fans), built now if need be in the stream's LIGHT scratch set; a call of several passes leaves
-// the last range's cube there.
+// --, else the call's own (pass p: g.qrows.fans[p % QUERY_LIGHT_CUBES]), built now if need be in the stream's LIGHT scratch set; a
+// call of up to QUERY_LIGHT_CUBES passes finds every cube held when it is repeated.
 
 // AUTO for a many-origin call: the single fan's rule (auto_bins_fan), which is MEASURED FOR ONE ORIGIN ONLY, and one condition more
 // that tools/ray_query_bench.py --steps fans showed (profiles/ray_query_bench.txt, section `fans`; K = 1 .. 128 origins, soup100k and
@@ -519,7 +519,7 @@ static bool fans_binned(const float *origins3, int norigins, int nrays, std::ini
     bool held = may_bin;
     for (size_t i = 0; held && i < plan->size(); i++) {
         fans_pass_origins(origins3, (*plan)[i], po);
-        held = held_cube(foreign, g.qrows.fans, po, (*plan)[i].count, (*plan)[i].cube_bins).cube != nullptr;
+        held = held_cube(foreign, g.qrows.fans[i % QueryRows::QUERY_LIGHT_CUBES], po, (*plan)[i].count, (*plan)[i].cube_bins).cube != nullptr;
     }
     return query_bins(may_bin, g.query_mode, held, auto_bins_fans(nrays));
 }
@@ -558,7 +558,7 @@ int query_intersect_fans(const float *origins3, int norigins, const void *d_orig
         const FanPass &p = plan[i];
         fans_pass_origins(origins3, p, po);
         CubeChoice c;                                                        // (a build: behind the previous pass's kernel on this stream)
-        if ((rc = walk_cube(foreign, g.qrows.fans, po, p.count, p.cube_bins, &c))) return rc;
+        if ((rc = walk_cube(foreign, g.qrows.fans[i % QueryRows::QUERY_LIGHT_CUBES], po, p.count, p.cube_bins, &c))) return rc;
         source_all = fold_cube_source(i, source_all, c.source);
         stats_cube(stats, *c.cube, source_all);
         q.f.tab = c.cube->d_light_tab;
@@ -575,7 +575,7 @@ int query_intersect_fans(const float *origins3, int norigins, const void *d_orig
 //
 // One byte per ray: whether some accepted triangle is nearer than the ray's limit.  Arbitrary rays sweep the scene's rows
 // (k_query_occluded*, the kernel chosen as intersect_launch chooses); rays that share origins walk the many-origin fans' cubes
-// (k_query_occluded_fans_binned) -- the same pass plan, the same kept cube g.qrows.fans and the same foreign cubes as
+// (k_query_occluded_fans_binned) -- the same pass plan, the same kept cubes g.qrows.fans[] and the same foreign cubes as
 // mirt_intersect_fans*, so a cube either call built serves the other.  The statistics are a kind of their own (QUERY_OCCLUDED):
 // every call of either form begins them afresh, and no call touches the fans' or DirectLight's.
 
@@ -654,7 +654,7 @@ int query_occluded_fans(const float *origins3, int norigins, const void *d_origi
         const FanPass &p = plan[i];                                          // (plan[0].first == 0: the pass that writes the strays' 0)
         fans_pass_origins(origins3, p, po);
         CubeChoice c;
-        if ((rc = walk_cube(foreign, g.qrows.fans, po, p.count, p.cube_bins, &c))) return rc;
+        if ((rc = walk_cube(foreign, g.qrows.fans[i % QueryRows::QUERY_LIGHT_CUBES], po, p.count, p.cube_bins, &c))) return rc;
         source_all = fold_cube_source(i, source_all, c.source);
         stats_cube(stats, *c.cube, source_all);
         q.f.f.tab = c.cube->d_light_tab;

@@ -133,7 +133,7 @@ void QueryRows::release()
     if (ev_built) (void)hipEventDestroy(ev_built);
     for (LightCache &c : cubes) c.release();
     fan.release();
-    fans.release();
+    for (LightCache &c : fans) c.release();
     *this = QueryRows();
 }
 

@@ -465,9 +465,10 @@ MIRT_API int mirt_get_fan_stats(mirt_query_stats *out);
  * neither form touches mirt_get_stats or mirt_get_query_stats.
  * How it is answered.  The origins go into cubes of up to MIRT_MAX_LIGHTS positions each (fewer where the sort's key space
  * allows fewer at the scene's grid), built in one binning chain per cube; a call with more origins runs in passes over consecutive
- * ranges of the list, each pass over all rays.  One cube is kept for these calls, apart from mirt_intersect_from*'s and
- * DirectLight's, keyed by scene version, positions and their order; a pass whose positions are exactly those the frame path's or
- * DirectLight's cube holds reads that cube and builds nothing.  mirt_set_query_mode: BRUTE never builds a cube (the rays are
+ * ranges of the list, each pass over all rays.  One cube per pass is kept for these calls, up to eight, apart from
+ * mirt_intersect_from*'s and DirectLight's, keyed by scene version, positions and their order -- a repeated call of up to 256
+ * origins builds nothing --; a pass whose positions are exactly those the frame path's or DirectLight's cube holds reads that cube
+ * and builds nothing.  mirt_set_query_mode: BRUTE never builds a cube (the rays are
  * written out on the device and go through mirt_intersect_device's kernels); BINNED bins whenever the frame path would; AUTO uses
  * the single fan's rule -- 2000 triangles or more, or MIRT_BIN_THRESHOLD triangles or more and nrays x triangles >= 4e7, or the
  * cubes of these origins are held -- which is MEASURED FOR ONE ORIGIN ONLY, with one condition more that the measurement of
@@ -510,7 +511,7 @@ MIRT_API int mirt_occluded_device(const void *d_rays, int nrays, const void *d_m
  * 1), with `occluded` in the place of the records.  The host form also checks every origin_of[i] against [0, norigins) before
  * anything touches the device (MIRT_ERR_INVALID_ARGUMENT, nothing written); in the device form a ray whose index lies outside the
  * range reads nothing out of bounds and its byte is written 0, under every mode.
- * How it is answered: as mirt_intersect_fans* -- the same passes over cubes of up to MIRT_MAX_LIGHTS origins, the SAME kept cube
+ * How it is answered: as mirt_intersect_fans* -- the same passes over cubes of up to MIRT_MAX_LIGHTS origins, the SAME kept cubes
  * and the same sharing with the frame path's and DirectLight's cubes, so a cube that mirt_intersect_fans* built for these origins
  * serves this call and the reverse.  Each ray walks its bin's list front to back up to the depth shell its limit falls into, skips
  * rows that lie wholly beyond the limit and stops at its first occluder; a direction outside mirt_intersect_from's window sweeps

@@ -1,5 +1,6 @@
-"""What the ray-query tests on the GPU share (test_gpu_ray_query.py, test_gpu_query_binned.py, test_gpu_fan_query.py,
-test_gpu_fans_query.py): the CPU oracle's ClosestIntersection and DirectLight per ray or record, the bit-exact comparisons, and the
+"""What the ray-query tests on the GPU (test_gpu_ray_query.py, test_gpu_query_binned.py, test_gpu_fan_query.py,
+test_gpu_fans_query.py, test_gpu_occluded.py) and the call-sequence fuzzer fuzz_queries.py share: the CPU oracle's
+ClosestIntersection and DirectLight per ray or record, the bit-exact comparisons, the occlusion limits and odd rays, and the
 scenes, ray batches and directions they are made on.  Test plumbing only; device buffers: devbuf.py."""
 import ctypes as C
 
@@ -11,6 +12,9 @@ import mirt
 LIGHTS = np.array([[0, -0.5, -0.75, 1, 1, 1, 14], [0.5, 0.25, -0.875, 1, 0.5, 0.25, 6]], np.float32)
 INSIDE = np.array([0.125, -0.0625, 0.1875], np.float32)
 OUTSIDE = np.array([2.5, 0.75, -1.5], np.float32)
+FLT_MAX = np.finfo(np.float32).max
+INF, NAN = np.float32("inf"), np.float32("nan")
+NKINDS = 8                                           # the kinds of limit limits_for cycles through
 _fan_scenes = {}
 
 
@@ -88,6 +92,44 @@ def primary_rays(oracle, cam, rot, focal, W, H):
             d = np.array([np.float32(x) - np.float32(W) / np.float32(2), np.float32(y) - np.float32(H) / np.float32(2), np.float32(focal)], np.float32)
             oracle.lib.mirt_oracle_mat3_mul_vec(rot, d, out)
             rays["dir"][y * W + x] = out
+    return rays
+
+
+# ---- occlusion: expectations, limits and rays outside the filter's range -------------------------------------------------------------
+
+def expected(hits, limits):
+    """The reference's two steps on the oracle's (or the library's bit-identical) fresh-record results."""
+    lim = np.full(len(hits), INF, np.float32) if limits is None else limits
+    with np.errstate(invalid="ignore"):
+        return ((hits["index"] >= 0) & (hits["distance"] < lim)).astype(np.uint8)
+
+
+def limits_for(hits):
+    """Per ray, cycling: +inf, FLT_MAX, d, the float above d, the float below d, 0, -1, NaN -- d the ray's own closest distance
+    where it hit, else 1."""
+    d = np.where(hits["index"] >= 0, hits["distance"], np.float32(1.0)).astype(np.float32)
+    kind = np.arange(len(hits)) % NKINDS
+    lim = np.select([kind == 0, kind == 1, kind == 2, kind == 3, kind == 4, kind == 5, kind == 6],
+                    [INF, FLT_MAX, d, np.nextafter(d, INF), np.nextafter(d, np.float32(0)), np.float32(0), np.float32(-1)], NAN)
+    return np.ascontiguousarray(lim.astype(np.float32)), kind
+
+
+def odd_rays(rays):
+    """A handful of rays outside the filter's range in every batch of 257 or more (every 41st ray from the 6th on): a start at
+    1e9, a direction component of 1e7, a zero direction, a NaN in the start, a NaN in the direction."""
+    rays = rays.copy()
+    for k, i in enumerate(range(5, len(rays), 41)):
+        kind = k % 5
+        if kind == 0:
+            rays["start"][i][k % 3] = 1e9
+        elif kind == 1:
+            rays["dir"][i][k % 3] = 1e7
+        elif kind == 2:
+            rays["dir"][i] = 0
+        elif kind == 3:
+            rays["start"][i][k % 3] = NAN
+        else:
+            rays["dir"][i][k % 3] = NAN
     return rays
 
 

@@ -426,13 +426,16 @@ def test_auto_rule():
     got, st = fans(origins, of[:64], dirs[:64], mirt.QUERY_AUTO)            # the cube is held now
     assert st["mode_used"] == mirt.QUERY_BINNED and st["cube_source"] == 2, st
     same_hits(got, want[:64], "auto, 64 rays, cube held")
-    # 33 origins: only the last range's cube is held afterwards, so a small call is not "held" and takes the brute path again
+    # 33 origins: both ranges' cubes are held afterwards (a cube per pass), so a small call is "held" too and builds nothing
     tris, origins, of, dirs, want = batch_of("soup2000", 33)
     got, st = fans(origins, of, dirs, mirt.QUERY_AUTO)
     assert st["mode_used"] == mirt.QUERY_BINNED and st["cube_source"] == 1, st
     got, st = fans(origins, of[:64], dirs[:64], mirt.QUERY_AUTO)
-    assert st["mode_used"] == mirt.QUERY_BRUTE, st
-    same_hits(got, want[:64], "auto, 33 origins, 64 rays")
+    assert st["mode_used"] == mirt.QUERY_BINNED and st["cube_source"] == 2, st
+    same_hits(got, want[:64], "auto, 33 origins, 64 rays, cubes held")
+    got, st = fans(origins, of, dirs, mirt.QUERY_BINNED)
+    assert st["cube_source"] == 2, st
+    same_hits(got, want, "33 origins again, cubes held")
 
 
 # ---- 8. frames in flight ---------------------------------------------------------------------------------------------------------------

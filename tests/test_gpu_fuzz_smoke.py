@@ -1,7 +1,10 @@
 """The call-sequence fuzzers of tools/ inside the driver's test run: a few dozen seeded sequences each (seconds), so that the state
 machine around the kernels -- light-cube cache and per-frame light pass, guessed list sizes, kept binning passes, cull flags per
 stream, scratch growth, one to four frames in flight -- is walked on every round's final code, not only when the builder
-remembers to.  The long runs (hundreds of sequences) stay in tools/collect_profiles.sh fuzz; their summaries are under profiles/."""
+remembers to.  The long runs (hundreds of sequences) stay in tools/collect_profiles.sh fuzz; their summaries are under profiles/.
+
+These four walk the frame path and compare with the library's own brute-force frame.  The fifth fuzzer, tests/fuzz_queries.py, walks
+ray queries, scene changes and deferred frames as well, against the CPU oracle: tests/test_gpu_query_sequences.py runs it."""
 import os
 import subprocess
 import sys

@@ -9,6 +9,7 @@ Light sets and what each exercises: 3 x 11 = 33 (the cut at 32 falls inside ligh
 4 x 16 = 64 (the cut falls on a light's end), 1 x 40 (result2 is added once, at the very end), 16 x 16 = 256 (the reference's
 whole randomPositions array)."""
 import ctypes as C
+import math
 import os
 import subprocess
 import sys
@@ -18,7 +19,7 @@ import pytest
 
 import mirt
 import query_helpers as rq
-from devbuf import DeviceArray, to_device
+from devbuf import DeviceArray, hip_fill, to_device
 
 pytestmark = pytest.mark.gpu
 
@@ -359,6 +360,153 @@ def test_supersampling_with_more_than_32_positions_is_refused(oracle):
         mirt.raytrace(ref["view"], ref["L"][:2], INDIRECT)          # 32 positions: the fused kernels, as before
     finally:
         mirt.set_antialiasing(1)
+        mirt.set_soft_shadows(1)
+
+
+# ---- deferred frames through the other entry points: a blurred band, asynchronous frames, sharded calls ---------------------------------
+
+def halo_rows(K, W):
+    """dof_halo_rows of capi/dof_plan.hpp restated: the rows above and below a band that its blur can tap."""
+    zlo, zhi = math.ceil(K / -2.0), math.ceil(K / 2.0)
+    one_wrap = max(-zlo, zhi - 1) + 1
+    return one_wrap if W < 3 else max(one_wrap, -(zlo + (1 + zlo) // W), zhi - 1 + (W - 3 + zhi) // W)
+
+
+def narrow_ref(oracle, W):
+    """The Cornell frame of frame_ref under 3 x 11 positions at width W (the same camera and lights), once per width."""
+    base = frame_ref(oracle, "cornell", 3, 11)
+    if W == base["W"]:
+        return base
+    key = ("cornell", 3, 11, W)
+    if key not in _frames:
+        F, H = FRAMES["cornell"], base["H"]
+        rot = oracle.rot_from_yaw(F["yaw"], 1.0)
+        ref = oracle.raytrace(base["tris"], F["cam"], rot, H / 2.0, W, H, base["L"], samples=11, jitter=base["jit"], threads=4)
+        hit = ref["index"] >= 0
+        assert hit.sum() >= 200                                  # (a frame this narrow sees the box's inside only: the blur must still change it)
+        ref.update(tris=base["tris"], L=base["L"], jit=base["jit"], samples=11, view=mirt.make_view(F["cam"], rot, H / 2.0, W, H), W=W, H=H)
+        _frames[key] = ref
+    return _frames[key]
+
+
+@pytest.mark.parametrize("W", [64, 20])
+def test_blurred_band_of_a_deferred_frame(oracle, W):
+    """Rows [8, 40) of a deferred frame under a 4 x 4 blur into a surface that starts at the band (row_origin 8) with a pitch wider
+    than the frame: the surface is the oracle's blur of the band, rgb and index are written for the band only, dist and pos for
+    the band and the rows its blur taps (the header's `entries of these two planes are written as well`), no row beyond them.
+    20 wide: a tap column wraps further than on a frame of at least K / 2 columns (capi/dof_plan.hpp)."""
+    ref = narrow_ref(oracle, W)
+    H, y0, y1, K, FL, PW = ref["H"], 8, 40, 4, 1.3, W + 7
+    halo = halo_rows(K, W)
+    lo, hi = y0 - halo, y1 + halo
+    assert 0 < lo and hi < H
+    fd = np.where(ref["index"] >= 0, ref["dist"] - np.float32(FL), np.float32(0)).astype(np.float32)
+    want = oracle.dof(ref["rgb"], fd, K, xrgb=np.full((H, W), FILLW, np.uint32), y0=y0, y1=y1)
+    assert (want[:y0] == FILLW).all() and (want[y1:] == FILLW).all()
+    assert not np.array_equal(want[y0:y1, 1:-1], ref["xrgb"][y0:y1, 1:-1]), "the blur changed nothing"
+    mirt.scene_upload(ref["tris"])
+    mirt.set_soft_shadows(ref["samples"], ref["jit"])
+    mirt.set_depth_of_field(K, FL)
+    try:
+        with DeviceArray((y1 - y0, PW), np.uint32, FILL) as surf, DeviceArray((H, W, 3), np.float32, FILL) as rgb, \
+                DeviceArray((H, W), np.int32, FILL) as index, DeviceArray((H, W), np.float32, FILL) as dist, DeviceArray((H, W, 3), np.float32, FILL) as pos:
+            mirt.raytrace_device(ref["view"], ref["L"], INDIRECT, mirt.RT_AUTO, y0, y1, y0, surf.ptr, PW * 4, rgb.ptr, index.ptr, dist.ptr, pos.ptr)
+            got, got_rgb, got_index, got_dist, got_pos = surf.read(), rgb.read(), index.read(), dist.read(), pos.read()
+    finally:
+        mirt.set_depth_of_field(0)
+        mirt.set_soft_shadows(1)
+    differ = got[:, :W] != want[y0:y1]
+    assert not differ.any(), "%d words of the blurred band differ, in rows %s" % (int(differ.sum()), sorted(set((np.nonzero(differ)[0] + y0).tolist())))
+    assert (got[:, W:] == FILLW).all(), "words beyond the frame's width written"
+    assert np.array_equal(got_index[y0:y1], ref["index"][y0:y1])
+    rq.same_bits(got_rgb[y0:y1], ref["rgb"][y0:y1], "the unblurred pixelColours of the band")
+    assert (got_index[:y0] == FILLW).all() and (got_index[y1:] == FILLW).all(), "index rows outside the band written"
+    assert (got_rgb[:y0].view(np.uint32) == FILLW).all() and (got_rgb[y1:].view(np.uint32) == FILLW).all(), "rgb rows outside the band written"
+    rq.same_bits(got_dist[lo:hi], ref["dist"][lo:hi], "distance, band and halo")
+    rq.same_bits(got_pos[lo:hi], ref["pos"][lo:hi], "position, band and halo")
+    for plane, name in ((got_dist, "distance"), (got_pos, "position")):
+        assert (plane[:lo].view(np.uint32) == FILLW).all() and (plane[hi:].view(np.uint32) == FILLW).all(), "%s rows beyond the halo written" % name
+
+
+ASYNC_CHILD = r"""
+import sys, numpy as np
+sys.path[:0] = [%r]
+import mirt
+want = np.load(%r)
+mirt.init(0)
+mirt.scene_upload(mirt.scene_cornell())
+W, H, PW, FILLW = int(want["W"]), int(want["H"]), int(want["W"]) + 9, 0xABCDEF01
+view = mirt.make_view(want["cam"], want["rot"], float(want["focal"]), W, H)
+mirt.set_soft_shadows(int(want["samples"]), want["jit"])
+big = np.full((2, H, PW), FILLW, np.uint32)                       # one registration, two surfaces inside it
+mirt.surface_register(big)
+border = np.ones((H, W), bool)
+border[1:-1, 1:-1] = False
+for K, plane in ((0, "xrgb"), (4, "blurred")):
+    mirt.set_depth_of_field(K, 1.3)
+    for fl in (1, 2):
+        big[:] = FILLW
+        mirt.set_frames_in_flight(fl)
+        calls = [mirt.prepared_async("rt", view, want["L"], (0.2, 0.2, 0.2), mirt.RT_AUTO, big[i][:, :W]) for i in range(2)]
+        for rep in range(2):
+            for c in calls:
+                c()
+        mirt.sync()
+        for i in range(2):
+            differ = big[i][1:-1, 1:W - 1] != want[plane][1:-1, 1:-1]
+            assert not differ.any(), (K, fl, i, int(differ.sum()))
+            assert (big[i][:, :W][border] == FILLW).all() and (big[i][:, W:] == FILLW).all(), (K, fl, i, "border or padding written")
+    mirt.set_frames_in_flight(1)
+mirt.surface_unregister(big)
+mirt.shutdown()
+print("ok")
+"""
+
+
+@pytest.mark.parametrize("path", ["direct", None])
+def test_deferred_frames_through_raytrace_async(oracle, tmp_path, path):
+    """mirt_raytrace_async with 3 x 11 positions into two registered surfaces in turn, one and two frames in flight, plain and under
+    the 4 x 4 blur: the interior is the oracle's, the border and the padding behind each row are untouched.  In a child process:
+    MIRT_HOST_PATH is read once."""
+    ref = frame_ref(oracle, "cornell", 3, 11)
+    F = FRAMES["cornell"]
+    fd = np.where(ref["index"] >= 0, ref["dist"] - np.float32(1.3), np.float32(0)).astype(np.float32)
+    blurred = oracle.dof(ref["rgb"], fd, 4, xrgb=np.zeros((ref["H"], ref["W"]), np.uint32))
+    data = str(tmp_path / "want.npz")
+    np.savez(data, cam=np.array(F["cam"], np.float32), rot=oracle.rot_from_yaw(F["yaw"], 1.0), focal=ref["H"] / 2.0, W=ref["W"], H=ref["H"], L=ref["L"],
+             jit=ref["jit"], samples=ref["samples"], xrgb=ref["xrgb"], blurred=blurred)
+    env = dict(os.environ)
+    env.pop("MIRT_HOST_PATH", None)
+    if path:
+        env["MIRT_HOST_PATH"] = path
+    r = subprocess.run([sys.executable, "-c", ASYNC_CHILD % (os.path.join(ROOT, "cpp-raytracer-rasterizer_amd"), data)], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
+
+
+def test_deferred_frames_through_raytrace_sharded_without_a_communicator(oracle):
+    """mirt_raytrace_sharded without mirt_comm_init renders whole frames: three calls in a row under the weighted partition, each
+    frame the oracle's (the border keeps the caller's fill: every row is the root's own), and the binned primary pass of the first
+    leaves a cost histogram."""
+    ref = frame_ref(oracle, "soup")
+    W, H = ref["W"], ref["H"]
+    mirt.scene_upload(ref["tris"])
+    mirt.set_soft_shadows(ref["samples"], ref["jit"])
+    mirt.set_partition(mirt.PARTITION_WEIGHTED)
+    try:
+        with DeviceArray((H, W), np.uint32, FILL) as frame:
+            call = mirt.prepared_sharded("rt", [ref["view"]], ref["L"], INDIRECT, mirt.RT_BINNED, 0, frame.ptr, W * 4)
+            for rep in range(3):
+                assert hip_fill(frame, FILL)
+                call()
+                got = frame.read()
+                assert np.array_equal(got[1:-1, 1:-1], ref["xrgb"][1:-1, 1:-1]), "call %d: %d words differ" % (rep, int((got[1:-1, 1:-1] != ref["xrgb"][1:-1, 1:-1]).sum()))
+                border = np.ones((H, W), bool)
+                border[1:-1, 1:-1] = False
+                assert (got[border] == FILLW).all(), "call %d: border words written" % rep
+                hist, shift = mirt.cost_histogram()
+                assert hist is not None and len(hist) > 0 and hist.sum() > 0, "call %d: no cost histogram" % rep
+    finally:
+        mirt.set_partition(0)
         mirt.set_soft_shadows(1)
 
 

@@ -12,19 +12,17 @@ import pytest
 
 import mirt
 from devbuf import DeviceArray, hip_fill, to_device
-from query_helpers import INSIDE, LIGHTS, OUTSIDE, fan_scene_of, jitter, make_batch, oracle_intersect, scene_of, seam_directions
+from query_helpers import (FLT_MAX, INF, INSIDE, LIGHTS, NAN, NKINDS, OUTSIDE, expected, fan_scene_of, jitter, limits_for, make_batch, odd_rays,
+                           oracle_intersect, scene_of, seam_directions)
 
 pytestmark = pytest.mark.gpu
 
-FLT_MAX = np.finfo(np.float32).max
-INF, NAN = np.float32("inf"), np.float32("nan")
 GUARD = 64
 INVALID = -3
 NBATCH = 4097 + 300                                  # the lane kernel: a ragged last block, P = 2 with an odd tail
 COUNTS = (1, 257, 4096, NBATCH)                      # ... and a wave per ray up to 4096 rays (MIRT_QUERY_WAVE_RAYS)
 MODES = (("brute", mirt.QUERY_BRUTE), ("binned", mirt.QUERY_BINNED), ("auto", mirt.QUERY_AUTO))
 BOTH = MODES[:2]
-NKINDS = 8
 _batches, _fans = {}, {}
 
 
@@ -41,23 +39,6 @@ def device():
 
 
 # ---- expectations, limits, calls -------------------------------------------------------------------------------------------------
-
-def expected(hits, limits):
-    """The reference's two steps on the oracle's (or the library's bit-identical) fresh-record results."""
-    lim = np.full(len(hits), INF, np.float32) if limits is None else limits
-    with np.errstate(invalid="ignore"):
-        return ((hits["index"] >= 0) & (hits["distance"] < lim)).astype(np.uint8)
-
-
-def limits_for(hits):
-    """Per ray, cycling: +inf, FLT_MAX, d, the float above d, the float below d, 0, -1, NaN -- d the ray's own closest distance
-    where it hit, else 1."""
-    d = np.where(hits["index"] >= 0, hits["distance"], np.float32(1.0)).astype(np.float32)
-    kind = np.arange(len(hits)) % NKINDS
-    lim = np.select([kind == 0, kind == 1, kind == 2, kind == 3, kind == 4, kind == 5, kind == 6],
-                    [INF, FLT_MAX, d, np.nextafter(d, INF), np.nextafter(d, np.float32(0)), np.float32(0), np.float32(-1)], NAN)
-    return np.ascontiguousarray(lim.astype(np.float32)), kind
-
 
 def strictness_holds(hits, kind, want):
     """What the limits are there to show, read off the expectation itself: d gives 0, one float more gives 1, one less 0."""
@@ -119,25 +100,6 @@ def fans_device(origins, of, dirs, limits, mode, what):
 
 
 # ---- arbitrary rays: the batches ---------------------------------------------------------------------------------------------------
-
-def odd_rays(rays):
-    """A handful of rays outside the filter's range in every batch of 257 or more (every 41st ray from the 6th on): a start at
-    1e9, a direction component of 1e7, a zero direction, a NaN in the start, a NaN in the direction."""
-    rays = rays.copy()
-    for k, i in enumerate(range(5, len(rays), 41)):
-        kind = k % 5
-        if kind == 0:
-            rays["start"][i][k % 3] = 1e9
-        elif kind == 1:
-            rays["dir"][i][k % 3] = 1e7
-        elif kind == 2:
-            rays["dir"][i] = 0
-        elif kind == 3:
-            rays["start"][i][k % 3] = NAN
-        else:
-            rays["dir"][i][k % 3] = NAN
-    return rays
-
 
 def batch_of(oracle, name):
     """Scene `name` uploaded; its shared batch of NBATCH rays, their oracle records, limits and expectations."""
@@ -370,6 +332,25 @@ def test_stats(oracle):
     assert mirt.stats() == frame and mirt.query_stats() == light
     assert mirt.fan_stats() == fs
     assert mirt.load().mirt_get_occlusion_stats(None) == INVALID
+
+
+def test_a_repeated_call_of_two_passes_builds_nothing(oracle):
+    """33 origins are two passes, each with a cube of its own (tests/fuzz_queries.py seed 2015, shrunk to: upload, set_query_mode
+    BINNED, occluded_fans with 33 origins twice -- when one cube served every pass, the second call built both again): the
+    repeated call, either form, and mirt_intersect_fans on the same origins find both held."""
+    tris, origins, of, dirs, unformed, hits, limits, kind, want, want_null = fans_of(oracle, "cornell x 2", 33)
+    mirt.scene_upload(tris)                                                 # (a new scene version: nothing is held)
+    got, st = fans_host(origins, of, dirs, limits, mirt.QUERY_BINNED, "first call")
+    assert st["mode_used"] == mirt.QUERY_BINNED and st["cube_source"] == 1 and np.array_equal(got, want), st
+    for form in (fans_host, fans_device):
+        got, st = form(origins, of, dirs, limits, mirt.QUERY_BINNED, "repeated call")
+        assert st["mode_used"] == mirt.QUERY_BINNED and st["cube_source"] == 2 and np.array_equal(got, want), st
+    mirt.set_query_mode(mirt.QUERY_BINNED)
+    try:
+        closest = mirt.intersect_fans(origins, of, dirs)
+        assert mirt.fan_stats()["cube_source"] == 2 and closest.tobytes() == hits.tobytes()
+    finally:
+        mirt.set_query_mode(mirt.QUERY_AUTO)
 
 
 def test_cube_shared_with_the_fans_and_the_frame_path(oracle):

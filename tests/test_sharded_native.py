@@ -222,8 +222,14 @@ L = np.array([[0.0, -0.5, -0.7, 1, 1, 1, 14]], np.float32)
 W, H = 200, 131
 ok = True
 # (the last one: a ray-traced batch right after a rasterised one of the same size -- the band buffers then hold rasterised
-# pixels where the ray tracer writes nothing, the 1-pixel border, and those words must still travel as 0)
-for kind, scene in (("rt", "cornell"), ("rt", "soup"), ("raster", "cornell"), ("rt", "cornell")):
+# pixels where the ray tracer writes nothing, the 1-pixel border, and those words must still travel as 0; then soft shadows of
+# 3 x 16 = 48 light positions, set alike on every rank: each band is a deferred frame's, DirectLight in two passes)
+L3 = np.array([[0.0, -0.5, -0.7, 1, 1, 1, 14], [0.5, 0.25, -0.875, 1, 0.5, 0.25, 6], [-0.375, 0.125, -0.625, 0.5, 1, 0.75, 9]], np.float32)
+JIT = (np.repeat(L3[:, 0:3], 16, axis=0) + (np.random.default_rng(3).integers(-8, 9, (48, 3)) / 256.0)).astype(np.float32)
+L1 = L
+for kind, scene, soft in (("rt", "cornell", 0), ("rt", "soup", 0), ("raster", "cornell", 0), ("rt", "cornell", 0), ("rt", "cornell", 16)):
+    L = L3 if soft else L1
+    mirt.set_soft_shadows(soft or 1, JIT if soft else None)
     tris = mirt.scene_cornell() if scene == "cornell" else np.concatenate([mirt.scene_cornell(), mirt.scene_soup(4, 3000, 0.1)])
     views = [mirt.make_view((0.05 * i, 0, -2.6), mirt.rot_from_yaw(0.1 * i, 1.01 if kind == "raster" else 1.0), 70.0, W, H) for i in range(3)]
     mirt.scene_upload(tris, mirt.cull(tris, views[0], 0) if kind == "raster" else None)
@@ -259,7 +265,7 @@ for kind, scene in (("rt", "cornell"), ("rt", "soup"), ("raster", "cornell"), ("
                 want[border & ~own] = 0
             if not np.array_equal(got[i], want):
                 ok = False
-                print("MISMATCH", kind, scene, "view", i, int((got[i] != want).sum()), flush=True)
+                print("MISMATCH", kind, scene, "soft", soft, "view", i, int((got[i] != want).sum()), flush=True)
             assert (got[i][1:-1, 1:-1] != 0x33333333).any()
 mirt.comm_shutdown()
 mirt.shutdown()

@@ -35,6 +35,8 @@ elif [ "$stage" = fuzz ]; then
   python tools/fuzz_small.py 0 3000 > gpurun_out/fuzz_small_scenes_vs_oracle.txt 2>&1; echo "fuzz small rc=$?"
   python tools/fuzz_sequence.py 0 200 > gpurun_out/fuzz_call_sequences.txt 2>&1; echo "fuzz sequences rc=$?"
   python tools/fuzz_raster_sequence.py 0 200 > gpurun_out/fuzz_raster_call_sequences.txt 2>&1; echo "fuzz raster sequences rc=$?"
+  # (its summary goes straight where it is kept: the other four are copied there by tools/store_profiles.py)
+  python tests/fuzz_queries.py 0 300 > profiles/fuzz_query_call_sequences.txt 2>&1; echo "fuzz query sequences rc=$?"
 else
   # the full bench lines (--full: sub_results, roofline, cpu_baseline) go to $RESULTS_DIR (default results/); point it at the
   # directory the other stages write to when tools/store_profiles.py is to copy them into profiles/

@@ -548,7 +548,7 @@ def child_fans(n):
             run(one_call, origins)
             st = mirt.fan_stats()
             dg["built"] = digest()
-            if K <= mirt.MAX_LIGHTS:                     # (more origins than a cube holds: only the last range's cube is kept)
+            if K <= mirt.MAX_LIGHTS:                     # (the kept cubes are timed for one pass; a call of up to eight passes keeps them all)
                 ts = [run(one_call, origins) for _ in range(reps + 1)]
                 assert mirt.fan_stats()["cube_source"] == 2
                 ms["kept"] = float(np.median(ts[1:]))
