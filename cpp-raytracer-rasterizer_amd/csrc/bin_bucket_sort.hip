@@ -208,7 +208,9 @@ int bucket_sort_shift(uint32_t nbins)
 uint32_t bucket_sort_buckets(uint32_t nbins) { const int s = bucket_sort_shift(nbins); return (nbins + 1u + (1u << s) - 1u) >> s; }
 
 // Enqueues the two launches.  keys/vals: the unsorted pairs (count in *total_ptr, clamped to cap); tmp_keys/tmp_vals: room
-// for cap pairs; bucket_cnt (filled by k_bin_pairs; zero on exit), bucket_base (nbuckets + 1), cursor (zero on entry and exit).
+// for cap pairs; bucket_cnt (filled by k_bin_pairs; zero on exit), bucket_base (nbuckets + 1), cursor (zero on entry and exit);
+// bin_off: nbins + 1 words, bin_off[nbins] = the total.  A list that overflowed (*total_ptr > cap) writes none of the outputs: only
+// the two counters' reset and *count_out (tools/sortcheck.hip holds the sort to all of this).
 hipError_t bucket_sort_pairs(const uint32_t *keys, const uint32_t *vals, const uint32_t *total_ptr, uint32_t cap, uint32_t expected,
                              uint32_t nbins, uint32_t *tmp_keys, uint32_t *tmp_vals, uint32_t *bucket_cnt, uint32_t *bucket_base,
                              uint32_t *cursor, uint32_t *bin_off, uint32_t *entries, int cu_count, hipStream_t stream, uint32_t *count_out)
