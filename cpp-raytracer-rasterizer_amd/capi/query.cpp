@@ -73,11 +73,9 @@ static int need_scene()
     return MIRT_OK;
 }
 
-// ClosestIntersection by brute force for nrays > 0 rays on the current stream: the scene's rows, then one of the two kernels.
-static int intersect_launch(const void *d_rays, int nrays, void *d_hits)
+// What the brute-force kernels read of the scene (query_rows) and of the caller: nrays rays and, for closest hits, their records.
+static QueryFrame rows_frame(const void *d_rays, int nrays, void *d_hits)
 {
-    int rc;
-    if ((rc = query_rows())) return rc;
     QueryFrame q;
     q.rows = g.qrows.d_rows;
     q.n = g.n;
@@ -86,13 +84,29 @@ static int intersect_launch(const void *d_rays, int nrays, void *d_hits)
     q.rays = static_cast<const float *>(d_rays);
     q.nrays = nrays;
     q.hits = static_cast<uint32_t *>(d_hits);
+    return q;
+}
+
+// The kernel pair of a brute-force query over nrays > 0 rays on the current stream: a wave per ray up to query_wave_rays(), a lane
+// per ray beyond.
+template <class Frame>
+static int launch_sweep(void (*wave)(Frame), void (*lane)(Frame), int nrays, const Frame &f)
+{
     if ((long)nrays <= query_wave_rays()) {
-        hipLaunchKernelGGL(k_query_closest_wave, dim3((unsigned)((nrays + 3) / 4)), dim3(256), 0, g.stream, q);
+        hipLaunchKernelGGL(wave, dim3((unsigned)((nrays + 3) / 4)), dim3(256), 0, g.stream, f);
     } else {
-        hipLaunchKernelGGL(k_query_closest<QUERY_P>, dim3((unsigned)((nrays + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), sweep_lds_bytes(), g.stream, q);
+        hipLaunchKernelGGL(lane, dim3((unsigned)((nrays + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), sweep_lds_bytes(), g.stream, f);
     }
     HIP_TRY(hipGetLastError());
     return MIRT_OK;
+}
+
+// ClosestIntersection by brute force for nrays > 0 rays on the current stream: the scene's rows, then one of the two kernels.
+static int intersect_launch(const void *d_rays, int nrays, void *d_hits)
+{
+    int rc;
+    if ((rc = query_rows())) return rc;
+    return launch_sweep(k_query_closest_wave, k_query_closest<QUERY_P>, nrays, rows_frame(d_rays, nrays, d_hits));
 }
 
 int query_intersect(const void *d_rays, int nrays, void *d_hits)
@@ -182,6 +196,27 @@ static int walk_cube(std::initializer_list<CubeChoice> foreign, LightCache &own,
     if ((rc = light_cache_ensure(own, g.cur().lt, origins, npos, cube_bins, &built))) return rc;
     *out = CubeChoice{ &own, built ? 1 : 2 };
     return MIRT_OK;
+}
+
+// The cube list of a pass: row 0 is the camera's place (light_key_of, light_cache_ensure), rows 1 .. count the pass's origins
+// (of a many-origin call) or light positions (of DirectLight).
+static void fans_pass_origins(const float *origins3, const FanPass &p, float *po)
+{
+    po[0] = po[1] = po[2] = 0.0f;
+    memcpy(po + 3, origins3 + 3 * (size_t)p.first, sizeof(float) * 3 * p.count);
+}
+
+// Whether every pass of `plan` over the call's positions origins3 finds its cube held -- the `held` of AUTO for a call in passes:
+// pass i's own cube is own[i % QUERY_LIGHT_CUBES]; somebody else's may serve pass 0 (foreign0) and the later passes (foreign).
+static bool passes_held(const std::vector<FanPass> &plan, const LightCache *own, std::initializer_list<CubeChoice> foreign0,
+                        std::initializer_list<CubeChoice> foreign, const float *origins3)
+{
+    float po[(1 + MIRT_MAX_LIGHTS) * 3];
+    for (size_t i = 0; i < plan.size(); i++) {
+        fans_pass_origins(origins3, plan[i], po);
+        if (!held_cube(i == 0 ? foreign0 : foreign, own[i % QueryRows::QUERY_LIGHT_CUBES], po, plan[i].count, plan[i].cube_bins).cube) return false;
+    }
+    return true;
 }
 
 int query_get_stats(int kind, mirt_query_stats *out)
@@ -314,15 +349,8 @@ int direct_light_passes(const void *d_hits, int nhits, const mirt_light *lights,
     const size_t npass = plan.size();
     const std::initializer_list<CubeChoice> frame_cube = { { &g.lc, 3 } }, none = {};
     float po[(1 + MIRT_MAX_LIGHTS) * 3];
-    const auto pass_origins = [&](const FanPass &p) {        // row 0 is the camera's place, rows 1 .. count the pass's positions
-        po[0] = po[1] = po[2] = 0.0f;
-        memcpy(po + 3, lp.origins + 3 * (size_t)(1 + p.first), sizeof(float) * 3 * p.count);
-    };
-    bool held = may_bin && is_query;                         // (`held`: every pass's cube, that is; a frame does not ask)
-    for (size_t i = 0; held && i < npass; i++) {
-        pass_origins(plan[i]);
-        held = held_cube(i == 0 ? frame_cube : none, g.qrows.cubes[i % QueryRows::QUERY_LIGHT_CUBES], po, plan[i].count, plan[i].cube_bins).cube != nullptr;
-    }
+    // (`held`: every pass's cube, that is; a frame does not ask)
+    const bool held = may_bin && is_query && passes_held(plan, g.qrows.cubes, frame_cube, none, lp.origins + 3);
     const bool binned = query_bins(may_bin, mode, held, auto_rule);
 
     if (is_query) stream_begin();
@@ -340,7 +368,7 @@ int direct_light_passes(const void *d_hits, int nhits, const mirt_light *lights,
         q.first = p.first;
         q.carry = multi ? *carry : nullptr;
         q.pass_flags = (i == 0 ? LIGHT_PASS_FIRST : 0) | (i + 1 == npass ? LIGHT_PASS_LAST : 0);
-        pass_origins(p);
+        fans_pass_origins(lp.origins + 3, p, po);
         if (!binned) {
             if ((rc = direct_light_brute(q, po, p.count, safe, multi))) return rc;
             continue;
@@ -474,13 +502,6 @@ static int check_fans_args(const float *origins3, int norigins, const void *orig
     return MIRT_OK;
 }
 
-// The cube list of a pass: row 0 is the camera's place (light_key_of, light_cache_ensure), rows 1 .. count the pass's origins.
-static void fans_pass_origins(const float *origins3, const FanPass &p, float *po)
-{
-    po[0] = po[1] = po[2] = 0.0f;
-    memcpy(po + 3, origins3 + 3 * (size_t)p.first, sizeof(float) * 3 * p.count);
-}
-
 // By definition the call is mirt_intersect on the expanded rays: they are written out on the device (k_query_fans_expand) into
 // the stream's query scratch (fans_expand) and go through query_intersect's kernels, whose per-ray filter safety and choice of
 // kernel come along.
@@ -515,12 +536,7 @@ static int fans_brute(const float *origins3, int norigins, const void *d_origin_
 static bool fans_binned(const float *origins3, int norigins, int nrays, std::initializer_list<CubeChoice> foreign, std::vector<FanPass> *plan)
 {
     const bool may_bin = starts_safe(origins3, norigins) && fan_pass_plan(norigins, g.n, cube_bins_override(), plan);
-    float po[(1 + MIRT_MAX_LIGHTS) * 3];
-    bool held = may_bin;
-    for (size_t i = 0; held && i < plan->size(); i++) {
-        fans_pass_origins(origins3, (*plan)[i], po);
-        held = held_cube(foreign, g.qrows.fans[i % QueryRows::QUERY_LIGHT_CUBES], po, (*plan)[i].count, (*plan)[i].cube_bins).cube != nullptr;
-    }
+    const bool held = may_bin && passes_held(*plan, g.qrows.fans, foreign, foreign, origins3);
     return query_bins(may_bin, g.query_mode, held, auto_bins_fans(nrays));
 }
 
@@ -529,6 +545,33 @@ static bool fans_binned(const float *origins3, int norigins, int nrays, std::ini
 static int fold_cube_source(size_t pass, int so_far, int source)
 {
     return pass == 0 ? source : (so_far == 1 || source == 1 ? 1 : (so_far == source ? source : 2));
+}
+
+// The passes of a binned many-origin call on the current stream, in the plan's order: the pass's origins, the cube its walk reads
+// (a build: behind the previous pass's kernel on this stream), what the call's statistics say of the cubes so far, the pass's fields
+// of the caller's frame -- q is that frame's QueryFansFrame --, then the caller's launch of its walk kernel over the frame.
+template <class Launch>
+static int fans_passes(const float *origins3, const std::vector<FanPass> &plan, std::initializer_list<CubeChoice> foreign, QueryStats &stats,
+                       QueryFansFrame &q, Launch launch)
+{
+    int rc;
+    float po[(1 + MIRT_MAX_LIGHTS) * 3];
+    int source_all = 0;
+    for (size_t i = 0; i < plan.size(); i++) {
+        const FanPass &p = plan[i];
+        fans_pass_origins(origins3, p, po);
+        CubeChoice c;
+        if ((rc = walk_cube(foreign, g.qrows.fans[i % QueryRows::QUERY_LIGHT_CUBES], po, p.count, p.cube_bins, &c))) return rc;
+        source_all = fold_cube_source(i, source_all, c.source);
+        stats_cube(stats, *c.cube, source_all);
+        q.f.tab = c.cube->d_light_tab;
+        q.f.cube = cube_view(*c.cube);
+        q.origins = c.cube->d_origins;
+        q.first = p.first;
+        q.count = p.count;
+        if ((rc = launch())) return rc;
+    }
+    return MIRT_OK;
 }
 
 int query_intersect_fans(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, void *d_hits)
@@ -540,7 +583,6 @@ int query_intersect_fans(const float *origins3, int norigins, const void *d_orig
 
     std::vector<FanPass> plan;
     const std::initializer_list<CubeChoice> foreign = { { &g.lc, 3 }, { &g.qrows.cubes[0], 4 } };
-    float po[(1 + MIRT_MAX_LIGHTS) * 3];
     const bool binned = fans_binned(origins3, norigins, nrays, foreign, &plan);
 
     stream_begin();
@@ -553,28 +595,13 @@ int query_intersect_fans(const float *origins3, int norigins, const void *d_orig
     q.origin_of = static_cast<const int32_t *>(d_origin_of);
     if ((rc = stats_arm(QUERY_FAN, &q.f.stats))) return rc;          // (once: the passes' kernels add up in the same words)
     const dim3 grid((unsigned)((nrays + 255) / 256));
-    int source_all = 0;
-    for (size_t i = 0; i < plan.size(); i++) {
-        const FanPass &p = plan[i];
-        fans_pass_origins(origins3, p, po);
-        CubeChoice c;                                                        // (a build: behind the previous pass's kernel on this stream)
-        if ((rc = walk_cube(foreign, g.qrows.fans[i % QueryRows::QUERY_LIGHT_CUBES], po, p.count, p.cube_bins, &c))) return rc;
-        source_all = fold_cube_source(i, source_all, c.source);
-        stats_cube(stats, *c.cube, source_all);
-        q.f.tab = c.cube->d_light_tab;
-        q.f.cube = cube_view(*c.cube);
-        q.origins = c.cube->d_origins;
-        q.first = p.first;
-        q.count = p.count;
-        if ((rc = launch_walk(k_query_fans_binned<false>, k_query_fans_binned<true>, q.f.stats != nullptr, grid, q))) return rc;
-    }
-    return MIRT_OK;
+    return fans_passes(origins3, plan, foreign, stats, q, [&] { return launch_walk(k_query_fans_binned<false>, k_query_fans_binned<true>, q.f.stats != nullptr, grid, q); });
 }
 
 // ---- occlusion queries: any-hit rays (mirt_occluded*) ---------------------------------------------------------------------------
 //
 // One byte per ray: whether some accepted triangle is nearer than the ray's limit.  Arbitrary rays sweep the scene's rows
-// (k_query_occluded*, the kernel chosen as intersect_launch chooses); rays that share origins walk the many-origin fans' cubes
+// (k_query_occluded*, the kernel chosen as for mirt_intersect*: launch_sweep); rays that share origins walk the many-origin fans' cubes
 // (k_query_occluded_fans_binned) -- the same pass plan, the same kept cubes g.qrows.fans[] and the same foreign cubes as
 // mirt_intersect_fans*, so a cube either call built serves the other.  The statistics are a kind of their own (QUERY_OCCLUDED):
 // every call of either form begins them afresh, and no call touches the fans' or DirectLight's.
@@ -584,23 +611,8 @@ static int occluded_launch(const void *d_rays, int nrays, const void *d_limit, v
 {
     int rc;
     if ((rc = query_rows())) return rc;
-    QueryOccludedFrame o;
-    memset(&o, 0, sizeof o);
-    o.q.rows = g.qrows.d_rows;
-    o.q.n = g.n;
-    o.q.scene_max = g.qrows.d_max;
-    o.q.scene_finite = g.scene_finite ? 1 : 0;
-    o.q.rays = static_cast<const float *>(d_rays);
-    o.q.nrays = nrays;
-    o.limit = static_cast<const float *>(d_limit);
-    o.occluded = static_cast<uint8_t *>(d_occluded);
-    if ((long)nrays <= query_wave_rays()) {
-        hipLaunchKernelGGL(k_query_occluded_wave, dim3((unsigned)((nrays + 3) / 4)), dim3(256), 0, g.stream, o);
-    } else {
-        hipLaunchKernelGGL(k_query_occluded<QUERY_P>, dim3((unsigned)((nrays + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), sweep_lds_bytes(), g.stream, o);
-    }
-    HIP_TRY(hipGetLastError());
-    return MIRT_OK;
+    const QueryOccludedFrame o = { rows_frame(d_rays, nrays, nullptr), static_cast<const float *>(d_limit), static_cast<uint8_t *>(d_occluded) };
+    return launch_sweep(k_query_occluded_wave, k_query_occluded<QUERY_P>, nrays, o);
 }
 
 int query_occluded(const void *d_rays, int nrays, const void *d_max_distance, void *d_occluded)
@@ -648,23 +660,10 @@ int query_occluded_fans(const float *origins3, int norigins, const void *d_origi
     q.occluded = static_cast<uint8_t *>(d_occluded);
     if ((rc = stats_arm(QUERY_OCCLUDED, &q.f.f.stats))) return rc;    // (once: the passes' kernels add up in the same words)
     const dim3 grid((unsigned)((nrays + 255) / 256));
-    float po[(1 + MIRT_MAX_LIGHTS) * 3];
-    int source_all = 0;
-    for (size_t i = 0; i < plan.size(); i++) {
-        const FanPass &p = plan[i];                                          // (plan[0].first == 0: the pass that writes the strays' 0)
-        fans_pass_origins(origins3, p, po);
-        CubeChoice c;
-        if ((rc = walk_cube(foreign, g.qrows.fans[i % QueryRows::QUERY_LIGHT_CUBES], po, p.count, p.cube_bins, &c))) return rc;
-        source_all = fold_cube_source(i, source_all, c.source);
-        stats_cube(stats, *c.cube, source_all);
-        q.f.f.tab = c.cube->d_light_tab;
-        q.f.f.cube = cube_view(*c.cube);
-        q.f.origins = c.cube->d_origins;
-        q.f.first = p.first;
-        q.f.count = p.count;
-        if ((rc = launch_walk(k_query_occluded_fans_binned<false>, k_query_occluded_fans_binned<true>, q.f.f.stats != nullptr, grid, q))) return rc;
-    }
-    return MIRT_OK;
+    // (plan[0].first == 0: the pass that writes the strays' 0)
+    return fans_passes(origins3, plan, foreign, stats, q.f, [&] {
+        return launch_walk(k_query_occluded_fans_binned<false>, k_query_occluded_fans_binned<true>, q.f.f.stats != nullptr, grid, q);
+    });
 }
 
 int query_set_mode(int mode)
@@ -794,6 +793,10 @@ int query_occluded_fans_host(const float *origins3, int norigins, const int32_t 
 
 }  // namespace mirt
 
+extern "C" int mirt_intersect(const mirt_ray *rays, int nrays, mirt_hit *hits) { return mirt::query_intersect_host(rays, nrays, hits); }
+extern "C" int mirt_intersect_device(const void *d_rays, int nrays, void *d_hits) { return mirt::query_intersect(d_rays, nrays, d_hits); }
+extern "C" int mirt_direct_light(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, float *out_rgb) { return mirt::query_direct_light_host(hits, nhits, lights, nlights, out_rgb); }
+extern "C" int mirt_direct_light_device(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_rgb) { return mirt::query_direct_light(d_hits, nhits, lights, nlights, d_rgb); }
 extern "C" int mirt_occluded(const mirt_ray *rays, int nrays, const float *max_distance, uint8_t *occluded) { return mirt::query_occluded_host(rays, nrays, max_distance, occluded); }
 extern "C" int mirt_occluded_device(const void *d_rays, int nrays, const void *d_max_distance, void *d_occluded) { return mirt::query_occluded(d_rays, nrays, d_max_distance, d_occluded); }
 extern "C" int mirt_occluded_fans(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, const float *max_distance, uint8_t *occluded) { return mirt::query_occluded_fans_host(origins3, norigins, origin_of, dirs3, nrays, max_distance, occluded); }

@@ -1,5 +1,5 @@
 // mirt_capi.hip -- the C-ABI of include/mirt.h on top of the HIP kernels: the library's lifetime, settings, statistics and
-// every extern "C" entry point.  The orchestration behind them -- ray-traced and rasterised frames, binning, delivery, sharded
+// every extern "C" entry point but the ray queries' (../capi/query.cpp).  The orchestration behind them -- ray-traced and rasterised frames, binning, delivery, sharded
 // frames -- lives in ../capi/ (capi.hpp: the state, one StreamState per frame in flight).  No CPU fallback: without a gfx950
 // device every compute entry point returns MIRT_ERR_NO_DEVICE.
 #include "../capi/capi.hpp"
@@ -442,18 +442,7 @@ extern "C" int mirt_raytrace_async(const mirt_view *view, const mirt_light *ligh
     });
 }
 
-// ---- ray queries (../capi/query.cpp; the kernels: ../query/rt_query.hip) ------------------------------------------------
-
-extern "C" int mirt_intersect(const mirt_ray *rays, int nrays, mirt_hit *hits) { return query_intersect_host(rays, nrays, hits); }
-extern "C" int mirt_intersect_device(const void *d_rays, int nrays, void *d_hits) { return query_intersect(d_rays, nrays, d_hits); }
-extern "C" int mirt_direct_light(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, float *out_rgb)
-{
-    return query_direct_light_host(hits, nhits, lights, nlights, out_rgb);
-}
-extern "C" int mirt_direct_light_device(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_rgb)
-{
-    return query_direct_light(d_hits, nhits, lights, nlights, d_rgb);
-}
+// (the ray queries' entry points -- mirt_intersect*, mirt_direct_light*, mirt_occluded* and the rest: the tail of ../capi/query.cpp)
 
 // ---- rasteriser -------------------------------------------------------------------------------------
 

@@ -618,12 +618,17 @@ def set_query_mode(mode):
     _check(load().mirt_set_query_mode(int(mode)))
 
 
+def _read_query_stats(getter):
+    """One mirt_query_stats through `getter` (mirt_get_query_stats, mirt_get_fan_stats, mirt_get_occlusion_stats) as a dict."""
+    s = QueryStats()
+    _check(getter(C.byref(s)))
+    return {name: int(getattr(s, name)) for name, _ in QueryStats._fields_}
+
+
 def query_stats():
     """The last DirectLight query (mirt_get_query_stats): mode_used, cube_source (0 none, 1 built by the call, 2 kept from an
     earlier query, 3 the frame path's), cube_bins, shells and -- with profiling on -- the binned kernel's counters."""
-    s = QueryStats()
-    _check(load().mirt_get_query_stats(C.byref(s)))
-    return {name: int(getattr(s, name)) for name, _ in QueryStats._fields_}
+    return _read_query_stats(load().mirt_get_query_stats)
 
 
 def intersect_from(origin, dirs, hits=None):
@@ -645,22 +650,26 @@ def intersect_from_device(origin, d_dirs, nrays, d_hits):
     _check(load().mirt_intersect_from_device(_ptr(origin), d_dirs, int(nrays), d_hits))
 
 
+def _as_fans(origins, origin_of, dirs):
+    """The arrays of a many-origin call as the library takes them: origins (k, 3), origin_of one int32 per ray or None, dirs (n, 3)."""
+    dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    if origin_of is not None:
+        origin_of = np.ascontiguousarray(origin_of, np.int32).reshape(-1)
+        if len(origin_of) != len(dirs):
+            raise ValueError("%d directions but %d origin indices" % (len(dirs), len(origin_of)))
+    return np.ascontiguousarray(origins, np.float32).reshape(-1, 3), origin_of, dirs
+
+
 def intersect_fans(origins, origin_of, dirs, hits=None):
     """ClosestIntersection(origins[origin_of[i]], dirs[i]) for every ray (mirt_intersect_fans): what intersect() returns for the
     rays {origins[origin_of[i]], dirs[i]}, bit for bit, the origins sharing cubes of up to MAX_LIGHTS positions (set_query_mode).
     origins: (k, 3) floats; origin_of: one int32 per ray, or None for a single origin; dirs: (n, 3) floats, used as given; hits:
     the in/out records (HIT_DTYPE; fresh ones when None).  Returns a new array."""
-    origins = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
-    dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    origins, origin_of, dirs = _as_fans(origins, origin_of, dirs)
     hits = fresh_hits(len(dirs)) if hits is None else np.ascontiguousarray(hits, HIT_DTYPE).copy()
     if len(hits) != len(dirs):
         raise ValueError("%d directions but %d hit records" % (len(dirs), len(hits)))
-    if origin_of is not None:
-        origin_of = np.ascontiguousarray(origin_of, np.int32).reshape(-1)
-        if len(origin_of) != len(dirs):
-            raise ValueError("%d directions but %d origin indices" % (len(dirs), len(origin_of)))
-    _check(load().mirt_intersect_fans(_ptr(origins), len(origins), None if origin_of is None else _ptr(origin_of), _ptr(dirs), len(dirs),
-                                      _ptr(hits)))
+    _check(load().mirt_intersect_fans(_ptr(origins), len(origins), _ptr(origin_of), _ptr(dirs), len(dirs), _ptr(hits)))
     return hits
 
 
@@ -675,9 +684,7 @@ def fan_stats():
     """The last intersect_from* call (mirt_get_fan_stats), in mirt_query_stats' fields: mode_used, cube_source (0 none, 1 built by
     the call, 2 kept), cube_bins, shells and -- profiling on, binned -- shadow_rays = rays, candidates = rows stepped over, tests =
     rows tested, fallback_records = rays that swept the whole table."""
-    s = QueryStats()
-    _check(load().mirt_get_fan_stats(C.byref(s)))
-    return {name: int(getattr(s, name)) for name, _ in QueryStats._fields_}
+    return _read_query_stats(load().mirt_get_fan_stats)
 
 
 # ---- occlusion queries: any-hit rays ---------------------------------------------------------------------
@@ -723,19 +730,14 @@ def occluded_device(d_rays, nrays, d_max_distance, d_occluded):
 def occluded_fans(origins, origin_of, dirs, max_distance=None, out=None):
     """occluded() for the rays {origins[origin_of[i]], dirs[i]}, byte for byte, through the cubes of intersect_fans
     (mirt_occluded_fans; set_query_mode).  origins: (k, 3) floats; origin_of: one int32 per ray, or None for a single origin."""
-    origins = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
-    dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    origins, origin_of, dirs = _as_fans(origins, origin_of, dirs)
     lim = _as_limits(max_distance, len(dirs), "directions")
     out = _occluded_out(out, len(dirs), "directions")
     if origin_of is not None:
-        origin_of = np.ascontiguousarray(origin_of, np.int32).reshape(-1)
-        if len(origin_of) != len(dirs):
-            raise ValueError("%d directions but %d origin indices" % (len(dirs), len(origin_of)))
         if len(origin_of) and (origin_of.min() < 0 or origin_of.max() >= len(origins)):
             bad = int(np.flatnonzero((origin_of < 0) | (origin_of >= len(origins)))[0])
             raise ValueError("origin_of[%d] = %d is outside [0, %d)" % (bad, int(origin_of[bad]), len(origins)))
-    _check(load().mirt_occluded_fans(_ptr(origins), len(origins), None if origin_of is None else _ptr(origin_of), _ptr(dirs), len(dirs),
-                                     None if lim is None else _ptr(lim), _ptr(out)))
+    _check(load().mirt_occluded_fans(_ptr(origins), len(origins), _ptr(origin_of), _ptr(dirs), len(dirs), _ptr(lim), _ptr(out)))
     return out
 
 
@@ -750,9 +752,7 @@ def occlusion_stats():
     """The last occluded* call (mirt_get_occlusion_stats), in mirt_query_stats' fields: mode_used, cube_source (0 - 4 as for
     intersect_fans), cube_bins, shells and -- profiling on, binned -- shadow_rays = rays, candidates = rows stepped over, tests =
     rows not beyond the limit, fallback_records = rays that swept their origin's table."""
-    s = QueryStats()
-    _check(load().mirt_get_occlusion_stats(C.byref(s)))
-    return {name: int(getattr(s, name)) for name, _ in QueryStats._fields_}
+    return _read_query_stats(load().mirt_get_occlusion_stats)
 
 
 # ---- several GPUs: band sharding with the gather inside the library ------------------------------------

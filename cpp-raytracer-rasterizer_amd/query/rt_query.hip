@@ -184,10 +184,49 @@ __device__ __forceinline__ bool exact_hit_row(const TestDots &d, float e1e2b, co
     return false;
 }
 
+// ---- what the lane-per-ray sweeps (k_query_closest, k_query_occluded) share: a lane's P rays, one row against them ------------
+//
+// Lane t of block b owns rays (b * P + p) * 256 + t (a lane without a ray reads ray 0).  Ray p of the lane: its number, whether
+// there is one, start, negD and whether it takes the exact path for every row (ray_exact_only, the header comment), into the
+// kernel's own registers.  The kernels call this from the loop that sets up what is their own of ray p, and for P = 2 pack start
+// and negD there as well, element by element into their own v3p: done through a reference in here, the same stores turn every
+// packed multiply of the row test around and reschedule the loop.
+template <int P>
+__device__ __forceinline__ void load_lane_ray(const QueryFrame &q, bool scene_ok, int p, long long &ray, bool &ok, v3 &start, v3 &nd, bool &exact_only)
+{
+    ray = lane_ray<P>(p);
+    ok = ray < q.nrays;
+    const float *r = q.rays + (size_t)RAY_WORDS * (ok ? ray : 0);
+    start = ld3(r);
+    const v3 dir = ld3(r + 3);
+    nd = neg3(dir);                                                // negD = -dir (:229); dir is used as given
+    exact_only = ray_exact_only(scene_ok, start, dir);
+}
+
+// Row r against the lane's P rays: the dots, e1e2b and the filter's verdict of each -- packed for P = 2, ray by ray otherwise.
+template <int P>
+__device__ __forceinline__ void test_row(const RowVecs &r, const v3 (&start)[P], const v3 (&nd)[P], const v3p &startp, const v3p &ndp,
+                                         TestDots (&d)[P], float (&e1e2b)[P], bool (&maybe)[P])
+{
+    if constexpr (P == 2) {
+        f2 eb;
+        const TestDots2 t = ray_dots2(r, startp, ndp, &eb);
+        maybe_hit2(t, &maybe[0], &maybe[1]);
+        d[0] = dots_half(t, 0); d[1] = dots_half(t, 1);
+        e1e2b[0] = eb.x; e1e2b[1] = eb.y;
+    } else {
+#pragma unroll
+        for (int p = 0; p < P; p++) {
+            d[p] = ray_dots(r, start[p], nd[p], &e1e2b[p]);
+            maybe[p] = maybe_hit(d[p]);
+        }
+    }
+}
+
 // ---- k_query_closest: one lane per P rays, every ray tests every triangle --------------------------------------------
 //
-// Workgroup = 256 lanes; lane t of block b owns rays (b * P + p) * 256 + t.  The rows are staged through LDS in chunks of
-// RT_CHUNK_ROWS (48 KiB) and read as wave-uniform broadcasts, three ds_read_b128 per triangle shared by the lane's P rays.
+// Workgroup = 256 lanes.  The rows are staged through LDS in chunks of RT_CHUNK_ROWS (48 KiB) and read as wave-uniform
+// broadcasts, three ds_read_b128 per triangle shared by the lane's P rays.
 // hits[ray] is the reference's in/out `closestIntersection`, updated sequentially in index order (closest_offer).
 template <int P>
 __global__ __launch_bounds__(256) void k_query_closest(const QueryFrame q)
@@ -203,21 +242,15 @@ __global__ __launch_bounds__(256) void k_query_closest(const QueryFrame q)
     int best_i[P];
 #pragma unroll
     for (int p = 0; p < P; p++) {
-        ray[p] = lane_ray<P>(p);
-        ok[p] = ray[p] < q.nrays;
-        const float *r = q.rays + (size_t)RAY_WORDS * (ok[p] ? ray[p] : 0);
-        start[p] = ld3(r);
-        const v3 dir = ld3(r + 3);
-        nd[p] = neg3(dir);                                         // negD = -dir (:229); dir is used as given
-        exact_only[p] = ray_exact_only(scene_ok, start[p], dir);
-        best_d[p] = incoming_distance(q.hits, ray[p], ok[p]);
-        best_i[p] = -1;
-        pos[p] = V3(0.0f, 0.0f, 0.0f);
-        replaced[p] = false;
+        load_lane_ray<P>(q, scene_ok, p, ray[p], ok[p], start[p], nd[p], exact_only[p]);
         if constexpr (P == 2) {
             startp.x[p] = start[p].x; startp.y[p] = start[p].y; startp.z[p] = start[p].z;
             ndp.x[p] = nd[p].x; ndp.y[p] = nd[p].y; ndp.z[p] = nd[p].z;
         }
+        best_d[p] = incoming_distance(q.hits, ray[p], ok[p]);
+        best_i[p] = -1;
+        pos[p] = V3(0.0f, 0.0f, 0.0f);
+        replaced[p] = false;
     }
 
     for (int base = 0; base < q.n; base += RT_CHUNK_ROWS) {
@@ -229,19 +262,7 @@ __global__ __launch_bounds__(256) void k_query_closest(const QueryFrame q)
             TestDots d[P];
             float e1e2b[P];
             bool maybe[P];
-            if constexpr (P == 2) {
-                f2 eb;
-                const TestDots2 t = ray_dots2(r, startp, ndp, &eb);
-                maybe_hit2(t, &maybe[0], &maybe[1]);
-                d[0] = dots_half(t, 0); d[1] = dots_half(t, 1);
-                e1e2b[0] = eb.x; e1e2b[1] = eb.y;
-            } else {
-#pragma unroll
-                for (int p = 0; p < P; p++) {
-                    d[p] = ray_dots(r, start[p], nd[p], &e1e2b[p]);
-                    maybe[p] = maybe_hit(d[p]);
-                }
-            }
+            test_row<P>(r, start, nd, startp, ndp, d, e1e2b, maybe);
 #pragma unroll
             for (int p = 0; p < P; p++) {
                 if (maybe[p] || exact_only[p]) {
@@ -509,6 +530,32 @@ __device__ __forceinline__ void flush_query_stats(unsigned long long *stats, uns
             if (sums[w]) atomicAdd(stats + w, sums[w]);
 }
 
+// The any-hit sweep of the lanes a cube's bins do not cover (`swept`; rare), called by the whole wave after its walk: the full
+// origin table `tab` of the lane's start point S in index order, k_query_direct_light's loop body -- the filter with the per-ray
+// exact-only override in front of exact_hit -- and a lane live until its first accepted dist < thr (:313-314); the wave leaves when
+// none of its lanes is live.  Returns whether the lane found an occluder; *rows is the number of rows it tested while live, for the
+// caller's statistics.
+__device__ __forceinline__ bool sweep_any_hit(const OriginRow *tab, int n, const float *tris15, v3 S, v3 nd, float thr, bool swept, bool exact_only,
+                                              unsigned *rows)
+{
+    bool live = swept;
+    unsigned tested = 0u;
+    for (int j = 0; j < n; j++) {
+        if (!__any(live)) break;
+        const float4 r0 = tab[j].r0, r1 = tab[j].r1, r2 = tab[j].r2;
+        const TestDots td = test_dots(r0, r1, r2, nd);
+        tested += live ? 1u : 0u;
+        if (live && (maybe_hit(td) || exact_only)) {
+            v3 hp;
+            float dist;
+            if (exact_hit(td, r0.w, tris15 + (size_t)15 * j, S, &hp, &dist))
+                if (dist < thr) live = false;                                              // :313-314
+        }
+    }
+    *rows = tested;
+    return swept && !live;
+}
+
 template <int P, bool STATS, bool CARRY>
 __global__ __launch_bounds__(256) void k_query_direct_light_binned(const QueryBinnedFrame b)
 {
@@ -569,23 +616,11 @@ __global__ __launch_bounds__(256) void k_query_direct_light_binned(const QueryBi
                 walk_step(rows4, e, end, act & (done ^ 1) & (int)(e + 1u < end), c0, c1, c2);     // (done, or the list's end: the lane is through)
             }
             if (__any(swept)) {
-                // (rare) the lanes the bins do not cover: light k's full origin table, k_query_direct_light's loop body
-                const OriginRow *tab = f.light_tab + (size_t)k * f.n;
-                const bool exact_only = !dir_in_filter_range(rd);
-                bool live = swept;
+                // the lanes the bins do not cover: light k's full origin table (sweep_any_hit)
+                unsigned rows;
+                occluded |= (int)sweep_any_hit(f.light_tab + (size_t)k * f.n, f.n, f.tris15, L, rd, thr, swept, !dir_in_filter_range(rd), &rows);
                 if (STATS && swept) { n_cand += (unsigned)f.n; fell = true; }
-                for (int j = 0; j < f.n; j++) {
-                    if (!__any(live)) break;
-                    const float4 r0 = tab[j].r0, r1 = tab[j].r1, r2 = tab[j].r2;
-                    const TestDots td = test_dots(r0, r1, r2, rd);
-                    if (STATS) n_tests += live ? 1u : 0u;
-                    if (live && (maybe_hit(td) || exact_only)) {
-                        v3 hp;
-                        float dist;
-                        if (exact_hit(td, r0.w, f.tris15 + (size_t)15 * j, L, &hp, &dist))
-                            if (dist < thr) live = false, occluded = 1;                    // :313-314
-                    }
-                }
+                if (STATS) n_tests += rows;
             }
             if (occluded) D = V3(0.0f, 0.0f, 0.0f);                                        // :314
             result = add3(result, D);                                                      // :319
@@ -703,6 +738,37 @@ template __global__ void k_query_fan<QUERY_P>(const QueryFanFrame);
 // start at k 6 B B shells.  A lane whose index lies outside [first, first + count) -- another pass's ray, or an index outside the
 // call's list -- is not `mine`: it takes no list, sweeps nothing and writes nothing; it reads position 0's values so that every
 // load stays inside the cube's tables.
+
+// First row and end of the list a ray from position k walks: the bin of direction d (fan_dir_of's d') among the bins from bin_base
+// on, its shells up to the one distance x falls into.  Returns the list's key, the index of its first shell in light_off.
+__device__ __forceinline__ uint32_t fan_list(const CubeView &cv, uint32_t k, uint32_t bin_base, v3 d, float x, uint32_t *e, uint32_t *end)
+{
+    const BinFrameDesc *lf = cv.light_frames + 6 * (size_t)k;
+    const uint32_t key = cube_bin_of(d, bin_base, cv.cube_bins) * (uint32_t)cv.shells;
+    *e = cv.light_off[key];
+    *end = cv.light_off[key + bin_shell_of(x, lf->shell_d0, lf->shell_iw, cv.shells) + 1u];
+    return key;
+}
+
+// The origin of lane `ray` in one pass of a many-origin call (the paragraph above): whether the ray is the pass's at all, and the
+// position k, origin S, first bin and sweep table of a ray that is -- position 0's for one that is not.  idx is the ray's index as
+// the caller gave it.
+struct FansLane { bool mine; uint32_t idx, k, bin_base; v3 S; const OriginRow *tab; };
+__device__ __forceinline__ FansLane fans_lane(const QueryFansFrame &qf, long long ray, bool ok)
+{
+    const QueryFanFrame &q = qf.f;
+    const uint32_t face_bins = (uint32_t)(q.cube.cube_bins * q.cube.cube_bins) * 6u;
+    FansLane l;
+    l.idx = qf.origin_of ? (uint32_t)qf.origin_of[ok ? ray : 0] : 0u;
+    const uint32_t rel = l.idx - (uint32_t)qf.first;               // (modulo 2^32: a negative or huge index lands beyond count)
+    l.mine = ok && rel < (uint32_t)qf.count;
+    l.k = l.mine ? rel : 0u;
+    l.bin_base = l.k * face_bins;
+    l.S = ld3(qf.origins + 3 * (size_t)(1u + l.k));
+    l.tab = q.tab + (size_t)l.k * q.n;
+    return l;
+}
+
 template <bool STATS>
 __device__ __forceinline__ void fan_walk(const QueryFanFrame &q, long long ray, bool ok, bool mine, uint32_t k, v3 S, uint32_t bin_base,
                                          const OriginRow *tab)
@@ -719,11 +785,7 @@ __device__ __forceinline__ void fan_walk(const QueryFanFrame &q, long long ray, 
     const BinFrameDesc *lf = cv.light_frames + 6 * (size_t)k;
     const float d0 = lf->shell_d0, iw = lf->shell_iw;
     uint32_t e = 0u, end = 0u, key = 0u;
-    if (binned) {
-        key = cube_bin_of(fd.d, bin_base, cv.cube_bins) * (uint32_t)cv.shells;
-        e = cv.light_off[key];
-        end = cv.light_off[key + bin_shell_of(bound, d0, iw, cv.shells) + 1u];
-    }
+    if (binned) key = fan_list(cv, k, bin_base, fd.d, bound, &e, &end);
     unsigned long long n_cand = 0, n_tests = 0;
     int best_i = -1, replaced = 0;
     v3 pos = V3(0.0f, 0.0f, 0.0f);
@@ -780,15 +842,10 @@ template __global__ void k_query_fan_binned<true>(const QueryFanFrame);
 template <bool STATS>
 __global__ __launch_bounds__(256) void k_query_fans_binned(const QueryFansFrame qf)
 {
-    const QueryFanFrame &q = qf.f;
-    const uint32_t face_bins = (uint32_t)(q.cube.cube_bins * q.cube.cube_bins) * 6u;
     const long long ray = (long long)blockIdx.x * 256 + threadIdx.x;
-    const bool ok = ray < q.nrays;
-    const uint32_t idx = qf.origin_of ? (uint32_t)qf.origin_of[ok ? ray : 0] : 0u;
-    const uint32_t rel = idx - (uint32_t)qf.first;                 // (modulo 2^32: a negative or huge index lands beyond count)
-    const bool mine = ok && rel < (uint32_t)qf.count;
-    const uint32_t k = mine ? rel : 0u;
-    fan_walk<STATS>(q, ray, ok, mine, k, ld3(qf.origins + 3 * (size_t)(1u + k)), k * face_bins, q.tab + (size_t)k * q.n);
+    const bool ok = ray < qf.f.nrays;
+    const FansLane l = fans_lane(qf, ray, ok);
+    fan_walk<STATS>(qf.f, ray, ok, l.mine, l.k, l.S, l.bin_base, l.tab);
 }
 
 template __global__ void k_query_fans_binned<false>(const QueryFansFrame);
@@ -825,8 +882,8 @@ __device__ __forceinline__ float occlusion_limit(const float *limit, long long r
     return !ok ? -1.0f : (limit ? limit[ray] : __uint_as_float(0x7f800000u));
 }
 
-// k_query_occluded: k_query_closest's sweep -- a lane per P rays, QueryRow chunks of RT_CHUNK_ROWS through LDS, the packed dots of
-// P = 2, the filter in front of the exact divisions -- with a ray open until its first accepted dist < L.  A wave none of whose
+// k_query_occluded: k_query_closest's sweep -- a lane per P rays (load_lane_ray), QueryRow chunks of RT_CHUNK_ROWS through LDS, the
+// row test with the filter in front of the exact divisions (test_row) -- with a ray open until its first accepted dist < L.  A wave none of whose
 // rays is open leaves the rows of a chunk alone (in steps of 64 rows: nothing in there waits for another wave), but goes on taking
 // part in the staging barriers; the sweep itself ends when the WHOLE workgroup has no open ray, by a block-wide vote every one of
 // the 256 lanes reaches at the top of each chunk -- stage_rows has two barriers, so no wave may leave that loop on its own.
@@ -844,19 +901,13 @@ __global__ __launch_bounds__(256) void k_query_occluded(const QueryOccludedFrame
     float L[P];
 #pragma unroll
     for (int p = 0; p < P; p++) {
-        ray[p] = lane_ray<P>(p);
-        ok[p] = ray[p] < q.nrays;
-        const float *r = q.rays + (size_t)RAY_WORDS * (ok[p] ? ray[p] : 0);
-        start[p] = ld3(r);
-        const v3 dir = ld3(r + 3);
-        nd[p] = neg3(dir);                                         // negD = -dir (:229); dir is used as given
-        exact_only[p] = ray_exact_only(scene_ok, start[p], dir);
-        L[p] = occlusion_limit(o.limit, ray[p], ok[p]);
-        open[p] = L[p] > 0.0f;                                     // (false for NaN, and for a lane without a ray)
+        load_lane_ray<P>(q, scene_ok, p, ray[p], ok[p], start[p], nd[p], exact_only[p]);
         if constexpr (P == 2) {
             startp.x[p] = start[p].x; startp.y[p] = start[p].y; startp.z[p] = start[p].z;
             ndp.x[p] = nd[p].x; ndp.y[p] = nd[p].y; ndp.z[p] = nd[p].z;
         }
+        L[p] = occlusion_limit(o.limit, ray[p], ok[p]);
+        open[p] = L[p] > 0.0f;                                     // (false for NaN, and for a lane without a ray)
     }
 
     for (int base = 0; base < q.n; base += RT_CHUNK_ROWS) {
@@ -875,19 +926,7 @@ __global__ __launch_bounds__(256) void k_query_occluded(const QueryOccludedFrame
                 TestDots d[P];
                 float e1e2b[P];
                 bool maybe[P];
-                if constexpr (P == 2) {
-                    f2 eb;
-                    const TestDots2 t = ray_dots2(r, startp, ndp, &eb);
-                    maybe_hit2(t, &maybe[0], &maybe[1]);
-                    d[0] = dots_half(t, 0); d[1] = dots_half(t, 1);
-                    e1e2b[0] = eb.x; e1e2b[1] = eb.y;
-                } else {
-#pragma unroll
-                    for (int p = 0; p < P; p++) {
-                        d[p] = ray_dots(r, start[p], nd[p], &e1e2b[p]);
-                        maybe[p] = maybe_hit(d[p]);
-                    }
-                }
+                test_row<P>(r, start, nd, startp, ndp, d, e1e2b, maybe);
 #pragma unroll
                 for (int p = 0; p < P; p++) {
                     if (open[p] && (maybe[p] || exact_only[p])) {
@@ -975,16 +1014,10 @@ __global__ __launch_bounds__(256) void k_query_occluded_fans_binned(const QueryO
     const QueryFanFrame &q = qf.f;
     const CubeView &cv = q.cube;
     const float4 *rows4 = reinterpret_cast<const float4 *>(cv.light_rows);
-    const uint32_t face_bins = (uint32_t)(cv.cube_bins * cv.cube_bins) * 6u;
     const long long ray = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool ok = ray < q.nrays;
-    const uint32_t idx = qf.origin_of ? (uint32_t)qf.origin_of[ok ? ray : 0] : 0u;
-    const uint32_t rel = idx - (uint32_t)qf.first;                 // (modulo 2^32: a negative or huge index lands beyond count)
-    const bool mine = ok && rel < (uint32_t)qf.count;
-    const bool nobodys = ok && qf.first == 0 && idx >= (uint32_t)of.norigins;
-    const uint32_t k = mine ? rel : 0u;
-    const v3 S = ld3(qf.origins + 3 * (size_t)(1u + k));
-    const OriginRow *tab = q.tab + (size_t)k * q.n;
+    const FansLane l = fans_lane(qf, ray, ok);
+    const bool mine = l.mine, nobodys = ok && qf.first == 0 && l.idx >= (uint32_t)of.norigins;
 
     const v3 dir = ld3(q.dirs + 3 * (size_t)(ok ? ray : 0));
     const v3 nd = neg3(dir);                                       // negD = -dir (:229); dir is used as given
@@ -993,12 +1026,7 @@ __global__ __launch_bounds__(256) void k_query_occluded_fans_binned(const QueryO
     const FanDir fd = fan_dir_of(nd);
     const bool binned = open && fd.formed, swept = open && !fd.formed;
     uint32_t e = 0u, end = 0u;
-    if (binned) {
-        const BinFrameDesc *lf = cv.light_frames + 6 * (size_t)k;
-        const uint32_t key = cube_bin_of(fd.d, k * face_bins, cv.cube_bins) * (uint32_t)cv.shells;
-        e = cv.light_off[key];
-        end = cv.light_off[key + bin_shell_of(L, lf->shell_d0, lf->shell_iw, cv.shells) + 1u];
-    }
+    if (binned) fan_list(cv, l.k, l.bin_base, fd.d, L, &e, &end);
     unsigned long long n_cand = 0, n_tests = 0;
     int occluded = 0;
     float4 c0, c1, c2;
@@ -1013,27 +1041,16 @@ __global__ __launch_bounds__(256) void k_query_occluded_fans_binned(const QueryO
         if (near_ok & (int)maybe_hit(td)) {
             v3 hp;
             float dist;
-            if (exact_hit(td, c0.w, q.tris15 + (size_t)15 * cv.light_tri[e], S, &hp, &dist)) done = (int)(dist < L);      // :313
+            if (exact_hit(td, c0.w, q.tris15 + (size_t)15 * cv.light_tri[e], l.S, &hp, &dist)) done = (int)(dist < L);    // :313
         }
         occluded |= done;
         walk_step(rows4, e, end, act & (done ^ 1) & (int)(e + 1u < end), c0, c1, c2);     // (done, or the list's end: the lane is through)
     }
     if (__any(swept)) {
-        // (rare) the lanes the bins do not cover: their origin's full table, up to the first occluder
-        const bool exact_only = !dir_in_filter_range(dir);
-        bool live = swept;
-        for (int j = 0; j < q.n; j++) {
-            if (!__any(live)) break;
-            const float4 r0 = tab[j].r0, r1 = tab[j].r1, r2 = tab[j].r2;
-            const TestDots td = test_dots(r0, r1, r2, nd);
-            if (STATS && live) { n_cand++; n_tests++; }
-            if (live && (maybe_hit(td) || exact_only)) {
-                v3 hp;
-                float dist;
-                if (exact_hit(td, r0.w, q.tris15 + (size_t)15 * j, S, &hp, &dist))
-                    if (dist < L) live = false, occluded = 1;                              // :313
-            }
-        }
+        // the lanes the bins do not cover: their origin's full table, up to the first occluder (sweep_any_hit)
+        unsigned rows;
+        occluded |= (int)sweep_any_hit(l.tab, q.n, q.tris15, l.S, nd, L, swept, !dir_in_filter_range(dir), &rows);
+        if (STATS) { n_cand += rows; n_tests += rows; }
     }
     if (mine || nobodys) of.occluded[ray] = (uint8_t)occluded;     // (nobodys: 0 -- such a lane is not open)
     if (STATS) flush_query_stats(q.stats, mine ? 1u : 0u, n_cand, n_tests, swept ? 1u : 0u);

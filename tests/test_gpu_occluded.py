@@ -334,6 +334,32 @@ def test_stats(oracle):
     assert mirt.load().mirt_get_occlusion_stats(None) == INVALID
 
 
+def test_fallback_sweep_counters(oracle):
+    """The whole-table sweep of the lanes the bins do not cover counts every row a live lane tests, into `candidates` and `tests`
+    alike.  70 rays (more than one wave) from two origins off every triangle of the 65-triangle soup, all along (2^20, 0, 0):
+    finite, outside the fan window (fan_dir_of forms nothing) and above the filter's direction range (every test takes the exact
+    path).  With a limit of 1e-30 no accepted distance is below it, so every ray stays open over all 65 rows."""
+    tris, _, _ = scene_of("soup65")
+    mirt.scene_upload(tris)
+    n, nrays = len(tris), 70
+    assert n == 65
+    origins = fan_origins(2)
+    of = np.ascontiguousarray((np.arange(nrays) % 2).astype(np.int32))
+    dirs = np.ascontiguousarray(np.tile(np.array([2.0 ** 20, 0, 0], np.float32), (nrays, 1)))
+    limits = np.full(nrays, 1e-30, np.float32)
+    want = expected(oracle_intersect(oracle, tris, mirt.make_rays(origins[of], dirs)), limits)
+    mirt.set_profiling(True)
+    try:
+        got, st = fans_host(origins, of, dirs, limits, mirt.QUERY_BINNED, "unformed directions")
+    finally:
+        mirt.set_profiling(False)
+    print(st)
+    assert not got.any() and np.array_equal(got, want)
+    assert st["mode_used"] == mirt.QUERY_BINNED, st
+    assert st["shadow_rays"] == nrays and st["fallback_records"] == nrays, st
+    assert st["candidates"] == st["tests"] == nrays * n, st
+
+
 def test_a_repeated_call_of_two_passes_builds_nothing(oracle):
     """33 origins are two passes, each with a cube of its own (tests/fuzz_queries.py seed 2015, shrunk to: upload, set_query_mode
     BINNED, occluded_fans with 33 origins twice -- when one cube served every pass, the second call built both again): the

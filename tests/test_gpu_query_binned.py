@@ -236,6 +236,33 @@ def test_the_bins_are_used(oracle):
     assert lib.mirt_set_query_mode(3) == -3 and lib.mirt_set_query_mode(-1) == -3 and lib.mirt_get_query_stats(None) == -3
 
 
+def test_fallback_sweep_counters(oracle):
+    """The whole-table sweep of the records the bins do not cover adds the table's n rows to `candidates` per swept (record,
+    position) and the rows a live lane tests to `tests`.  70 records (more than one wave) that name a triangle of the 65-triangle
+    soup and whose position has a NaN x: rDir is NaN for either light, a NaN direction accepts nothing, so every row of both
+    tables is tested."""
+    tris, _, _ = rq.scene_of("soup65")
+    mirt.scene_upload(tris)
+    n, nrec, lights = len(tris), 70, LIGHTS[:2]
+    assert n == 65
+    recs = mirt.fresh_hits(nrec)
+    recs["position"] = np.random.default_rng(5).uniform(-1, 1, (nrec, 3)).astype(np.float32)
+    recs["position"][:, 0] = np.float32("nan")
+    recs["index"] = np.arange(nrec) % n
+    recs["distance"] = 1.0
+    want = rq.oracle_direct_light(oracle, tris, recs, lights)
+    mirt.set_profiling(True)
+    try:
+        got, st = light_query(recs, lights, mirt.QUERY_BINNED)
+    finally:
+        mirt.set_profiling(False)
+    print(st)
+    rq.same_bits(got, want, "NaN records vs oracle")
+    assert st["mode_used"] == mirt.QUERY_BINNED, st
+    assert st["shadow_rays"] == nrec * len(lights) and st["fallback_records"] == nrec, st
+    assert st["candidates"] == st["tests"] == nrec * len(lights) * n, st
+
+
 # ---- the cache ----------------------------------------------------------------------------------------------------------------
 
 def test_cube_cache(oracle):

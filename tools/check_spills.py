@@ -47,6 +47,7 @@ EXPECT = ("k_rt_trace2", "k_rt_tile2", "k_rt_brute", "k_bin_pairs", "k_raster_sm
           "k_query_rows", "k_query_closest<", "k_query_closest_wave", "k_query_direct_light<", "k_query_direct_light_binned",
           "k_query_fan<", "k_query_fan_binned<false>", "k_query_fan_binned<true>", "k_query_fans_binned<false>", "k_query_fans_binned<true>",
           "k_query_fans_expand",
+          "k_query_occluded<", "k_query_occluded_wave", "k_query_occluded_fans_binned<false>", "k_query_occluded_fans_binned<true>",
           "k_query_direct_light<2, false>", "k_query_direct_light<2, true>", "k_query_direct_light_binned<1, false, false>",
           "k_query_direct_light_binned<1, true, false>", "k_query_direct_light_binned<1, false, true>", "k_query_direct_light_binned<1, true, true>",
           "k_frame_records", "k_frame_resolve",
