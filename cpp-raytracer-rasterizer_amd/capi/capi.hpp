@@ -234,8 +234,8 @@ struct DofPlanes {
 };
 
 // The queries that walk a cube and keep statistics: DirectLight (mirt_get_query_stats), origin fans (mirt_get_fan_stats) and
-// occlusion queries (mirt_get_occlusion_stats).
-enum { QUERY_DIRECT_LIGHT = 0, QUERY_FAN = 1, QUERY_OCCLUDED = 2, QUERY_KINDS = 3 };
+// occlusion queries (mirt_get_occlusion_stats) and shadow masks (mirt_get_shadow_mask_stats).
+enum { QUERY_DIRECT_LIGHT = 0, QUERY_FAN = 1, QUERY_OCCLUDED = 2, QUERY_SHADOW_MASK = 3, QUERY_KINDS = 4 };
 // The last query of a kind: how it was answered, the stream it ran on and where its kernel's counters are (device; profiling on,
 // binned -- read once, query_get_stats).
 struct QueryStats {
@@ -260,6 +260,8 @@ struct QueryScratch {
     // mirt_direct_light* with more than MIRT_MAX_LIGHTS positions: the accumulators between two passes (light_passes.hpp)
     float *d_carry = nullptr;                    // LIGHT_CARRY_WORDS x carry_cap floats
     size_t carry_cap = 0;                        // records
+    // mirt_direct_light_masked*: lpos / lcol of the call's positions, MIRT_MAX_LIGHT_POSITIONS x 6 floats (k_query_relight)
+    float *d_relight = nullptr;
 
     void release();
 };
@@ -291,6 +293,9 @@ struct QueryRows {
     void *d_rays = nullptr, *d_hits = nullptr, *d_rgb = nullptr, *d_dirs = nullptr, *d_origin_of = nullptr;
     void *d_limits = nullptr, *d_occluded = nullptr;
     size_t cap = 0;                              // rays / records / directions / origin indices / limits / bytes each holds
+    // ... and of mirt_shadow_mask / mirt_direct_light_masked: the mask's planes, grown apart from the rest (up to 32 bytes a record)
+    void *d_mask = nullptr;
+    size_t mask_cap = 0;                         // words
     // The light cube of the DirectLight queries: a LightCache like the frame path's g.lc, keyed alike (scene version + the light
     // positions in use, and the grid -- so a new scene forgets it), kept across calls, shared by the streams and ordered among
     // them by light_cache_ensure's events.  A query whose lights are the ones the frame path's valid cube holds reads g.lc and
@@ -392,7 +397,7 @@ struct Ctx {
     LightCache lc;
     QueryRows qrows;
     int query_mode = MIRT_QUERY_AUTO;            // mirt_set_query_mode
-    QueryStats qstats[QUERY_KINDS];              // the last DirectLight query, the last origin fan, the last occlusion query
+    QueryStats qstats[QUERY_KINDS];              // the last DirectLight query, the last origin fan, the last occlusion query, the last shadow mask
     unsigned long long *d_hits = nullptr;        // the hit-counter buffer of the current ray-traced frame (one of its stream's d_hits)
     bool scene_finite = true;                    // all vertex coordinates below MIRT_SAFE_MAG
     uint64_t scene_version = 0;                  // bumped whenever the triangles change
@@ -568,7 +573,12 @@ int query_direct_light_host(const mirt_hit *hits, int nhits, const mirt_light *l
 // the passes of a deferred frame, which leave them alone and bracket their cube builds under MIRT_K_BIN; carry / carry_cap: the
 // caller's scratch for the accumulators between passes, grown here.
 int direct_light_passes(const void *d_hits, int nhits, const mirt_light *lights, int npos, void *d_rgb, int mode, bool auto_rule, bool is_query,
-                        float **carry, size_t *carry_cap);
+                        float **carry, size_t *carry_cap, void *d_mask = nullptr);
+// d_mask: mirt_shadow_mask* -- the same passes with the kernels' MASK instantiations; d_rgb, carry and carry_cap are not used then.
+int query_shadow_mask(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_mask);
+int query_shadow_mask_host(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, uint32_t *mask);
+int query_direct_light_masked(const void *d_hits, int nhits, const mirt_light *lights, int nlights, const void *d_mask, void *d_rgb);
+int query_direct_light_masked_host(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, const uint32_t *mask, float *out_rgb);
 bool direct_light_auto_bins(int nhits, int npos);
 int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, void *d_hits);
 int query_intersect_from_host(const float *origin, const float *dirs3, int nrays, mirt_hit *hits);

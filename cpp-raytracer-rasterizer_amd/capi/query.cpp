@@ -8,6 +8,8 @@
 // Many rays from ONE origin (mirt_intersect_from*) walk a cube of the same kind around that origin, kept apart from DirectLight's;
 // rays from SEVERAL origins in one call (mirt_intersect_fans*) walk cubes that hold up to MIRT_MAX_LIGHTS of the origins each.
 // Occlusion queries (mirt_occluded*, mirt_occluded_fans*) answer one byte per ray through the same rows and the same cubes.
+// Shadow masks (mirt_shadow_mask*) are DirectLight's pass loop with its kernels' MASK instantiations -- the shadow decision per
+// (record, position) instead of the colours --, and mirt_direct_light_masked* is DirectLight from those bits in one launch.
 #include "capi.hpp"
 
 namespace mirt {
@@ -275,14 +277,16 @@ static int query_origin_tables(const float *origins, int npos, bool safe)
     return MIRT_OK;
 }
 
-// The brute-force kernel over those tables; carry: one pass of several (light_passes.hpp).
+// The brute-force kernel over those tables; carry: one pass of several (light_passes.hpp).  With q.mask set the kernel is the MASK
+// instantiation (a pass of mirt_shadow_mask*: no carry whatever the pass count), the counting one where stats_arm gave counters.
 static int direct_light_brute(QueryLightFrame &q, const float *origins, int npos, bool safe, bool carry)
 {
     int rc;
     if ((rc = query_origin_tables(origins, npos, safe))) return rc;
     q.f.light_tab = g.cur().query.d_light_tab;
     q.f.unsafe = g.cur().query.d_flags;
-    void (*const kernel)(QueryLightFrame) = carry ? k_query_direct_light<QUERY_P, true> : k_query_direct_light<QUERY_P, false>;
+    void (*const kernel)(QueryLightFrame) = q.mask ? (q.stats ? k_query_direct_light<QUERY_P, false, true, true> : k_query_direct_light<QUERY_P, false, true, false>)
+                                                   : (carry ? k_query_direct_light<QUERY_P, true> : k_query_direct_light<QUERY_P, false>);
     hipLaunchKernelGGL(kernel, dim3((unsigned)((q.nhits + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), sweep_lds_bytes(), g.stream, q);
     HIP_TRY(hipGetLastError());
     return MIRT_OK;
@@ -300,6 +304,7 @@ static int direct_light_binned(QueryLightFrame &q, const LightCache &C, unsigned
     b.cube = cube_view(C);
     b.stats = counters;
     const dim3 grid((unsigned)((q.nhits + 256 * QUERY_BIN_P - 1) / (256 * QUERY_BIN_P)));
+    if (q.mask) return launch_walk(k_query_direct_light_binned<QUERY_BIN_P, false, false, true>, k_query_direct_light_binned<QUERY_BIN_P, true, false, true>, counters != nullptr, grid, b);
     if (carry) return launch_walk(k_query_direct_light_binned<QUERY_BIN_P, false, true>, k_query_direct_light_binned<QUERY_BIN_P, true, true>, counters != nullptr, grid, b);
     return launch_walk(k_query_direct_light_binned<QUERY_BIN_P, false, false>, k_query_direct_light_binned<QUERY_BIN_P, true, false>, counters != nullptr, grid, b);
 }
@@ -315,8 +320,11 @@ static int fold_cube_source(size_t pass, int so_far, int source);
 // outside the filter's proven range (`safe`: that is the `unsafe` flag the brute kernel is given) or what the sort cannot key --
 // one range that does not fit sends every pass to the brute-force kernel.  The cube of pass p: g.qrows.cubes[p % QUERY_LIGHT_CUBES];
 // pass 0 reads the frame path's instead when that holds these very positions.
+// d_mask (mirt_shadow_mask*): the same passes, plan, rules and cubes with the kernels' MASK instantiations, which write the shadow
+// decisions of their range into the mask's planes and carry nothing; the statistics are the kind QUERY_SHADOW_MASK, counted by the
+// sweep as well.  Without it every launch is the one this function has always made.
 int direct_light_passes(const void *d_hits, int nhits, const mirt_light *lights, int npos, void *d_rgb, int mode, bool auto_rule, bool is_query,
-                        float **carry, size_t *carry_cap)
+                        float **carry, size_t *carry_cap, void *d_mask)
 {
     int rc;
     QueryLightFrame q;
@@ -328,6 +336,9 @@ int direct_light_passes(const void *d_hits, int nhits, const mirt_light *lights,
     q.hits = static_cast<const uint32_t *>(d_hits);
     q.nhits = nhits;
     q.rgb = static_cast<float *>(d_rgb);
+    q.mask = static_cast<uint32_t *>(d_mask);
+    const bool masking = d_mask != nullptr;
+    const int kind = masking ? QUERY_SHADOW_MASK : QUERY_DIRECT_LIGHT;
     // the light positions the shadow rays start from and their share of the light's power, as a frame sets them up
     LightPositions lp;
     lp.origins[0] = lp.origins[1] = lp.origins[2] = 0.0f;
@@ -354,11 +365,12 @@ int direct_light_passes(const void *d_hits, int nhits, const mirt_light *lights,
     const bool binned = query_bins(may_bin, mode, held, auto_rule);
 
     if (is_query) stream_begin();
-    QueryStats *stats = is_query ? &stats_begin(QUERY_DIRECT_LIGHT, binned) : nullptr;
-    const bool multi = npass > 1;
+    QueryStats *stats = is_query ? &stats_begin(kind, binned) : nullptr;
+    const bool multi = npass > 1 && !masking;
     if (multi && (size_t)nhits > *carry_cap && (rc = dev_grow(carry, carry_cap, (size_t)nhits, (size_t)nhits * LIGHT_CARRY_WORDS, true))) return rc;
     unsigned long long *counters = nullptr;
-    if (binned && is_query && (rc = stats_arm(QUERY_DIRECT_LIGHT, &counters))) return rc;     // (once: the passes' kernels add up in the same words)
+    if ((binned || masking) && is_query && (rc = stats_arm(kind, &counters))) return rc;     // (once: the passes' kernels add up in the same words)
+    if (masking && !binned) q.stats = counters;
     int source_all = 0;
     for (size_t i = 0; i < npass; i++) {
         const FanPass &p = plan[i];
@@ -397,6 +409,73 @@ int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, 
     if ((rc = need_scene())) return rc;
     QueryScratch &S = g.streams[next_si()].query;            // the stream the call will take: its carry
     return direct_light_passes(d_hits, nhits, lights, npos, d_rgb, g.query_mode, auto_bins(nhits, npos), true, &S.d_carry, &S.carry_cap);
+}
+
+// ---- shadow masks: DirectLight's shadow decisions per (record, position), and DirectLight from them (mirt_shadow_mask*,
+// mirt_direct_light_masked*) ------------------------------------------------------------------------------------------------------
+//
+// The mask call IS mirt_direct_light's pass loop with the kernels' MASK instantiations (direct_light_passes): the same plan, the same
+// binned-or-brute decision from the same rule (auto_bins over records x positions), the same kept cubes g.qrows.cubes[] and the frame
+// path's cube in pass 0, so a cube either call built serves the other.  AUTO keeps mirt_direct_light's rule: tools/ray_query_bench.py
+// --steps mask measures both calls beside mirt_direct_light_device (profiles/ray_query_bench.txt, section `mask`).
+// The masked call casts no ray: one launch of k_query_relight over all positions, whose lpos / lcol travel as one table into the
+// stream's query scratch.  It builds no cube, keeps no statistics and does not look at the query mode.
+
+// The checks both calls share, in mirt_direct_light's order; *npos: the call's light positions.  `mask` may be NULL only where the
+// call has no word to read or write (no record or no position).
+static int check_mask_args(const void *hits, int nhits, const mirt_light *lights, int nlights, const void *mask, const void *out, int *npos)
+{
+    int rc;
+    if ((rc = check_query_args(hits, nhits, out, "hit"))) return rc;
+    if ((rc = check_lights(lights, nlights, npos))) return rc;
+    if (nhits > 0 && *npos > 0 && !mask) return fail(MIRT_ERR_INVALID_ARGUMENT, "the mask must not be NULL for %d records and %d light positions", nhits, *npos);
+    return MIRT_OK;
+}
+
+int query_shadow_mask(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_mask)
+{
+    int rc, npos = 0;
+    if ((rc = check_mask_args(d_hits, nhits, lights, nlights, d_mask, d_hits, &npos))) return rc;
+    if (nhits == 0) return MIRT_OK;
+    if ((rc = need_scene())) return rc;
+    if (npos == 0) return MIRT_OK;                           // no plane: nothing is written
+    return direct_light_passes(d_hits, nhits, lights, npos, nullptr, g.query_mode, auto_bins(nhits, npos), true, nullptr, nullptr, d_mask);
+}
+
+int query_direct_light_masked(const void *d_hits, int nhits, const mirt_light *lights, int nlights, const void *d_mask, void *d_rgb)
+{
+    int rc, npos = 0;
+    if ((rc = check_mask_args(d_hits, nhits, lights, nlights, d_mask, d_rgb, &npos))) return rc;
+    if (nhits == 0) return MIRT_OK;
+    if ((rc = need_scene())) return rc;
+
+    QueryRelightFrame r;
+    memset(&r, 0, sizeof r);
+    r.q.f.tris15 = g.d_tris;
+    r.q.f.n = g.n;
+    r.q.f.samples = soft_samples();
+    r.q.hits = static_cast<const uint32_t *>(d_hits);
+    r.q.nhits = nhits;
+    r.q.rgb = static_cast<float *>(d_rgb);
+    r.q.mask = static_cast<uint32_t *>(const_cast<void *>(d_mask));      // (read only: k_query_relight)
+    r.npos = npos;
+    // position, then share of the light's power, six floats a position: what a pass of DirectLight has in f.lpos / f.lcol
+    LightPositions lp;
+    fill_light_positions(lights, npos, lp.lpos, lp.lcol, nullptr);
+    float table[MIRT_MAX_LIGHT_POSITIONS * 6];
+    for (int j = 0; j < npos; j++) {
+        memcpy(table + 6 * j, lp.lpos[j], 12);
+        memcpy(table + 6 * j + 3, lp.lcol[j], 12);
+    }
+
+    stream_begin();
+    QueryScratch &S = g.cur().query;
+    if (!S.d_relight) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_relight), sizeof table));
+    if (npos > 0) HIP_TRY(upload_small(S.d_relight, table, sizeof(float) * 6 * npos, g.stream));
+    r.lights = S.d_relight;
+    hipLaunchKernelGGL(k_query_relight, dim3((unsigned)((nhits + 255) / 256)), dim3(256), 0, g.stream, r);
+    HIP_TRY(hipGetLastError());
+    return MIRT_OK;
 }
 
 // ---- origin fans: ClosestIntersection for many directions from one origin (mirt_intersect_from*) -----------------------------
@@ -736,6 +815,43 @@ int query_direct_light_host(const mirt_hit *hits, int nhits, const mirt_light *l
     return with_host_arrays(checked, nhits, a, [&] { return query_direct_light(Q.d_hits, nhits, lights, nlights, Q.d_rgb); });
 }
 
+// The mask's staging array is its own and grows by its own measure -- up to 32 bytes a record, which the other arrays' callers
+// should not pay for --, once the checks have passed and there is something to stage.
+static int mask_staging(int checked, int nhits, size_t words)
+{
+    QueryRows &Q = g.qrows;
+    if (checked || nhits == 0 || g.n <= 0 || words <= Q.mask_cap) return MIRT_OK;
+    Q.mask_cap = 0;
+    const int rc = dev_realloc_bytes(&Q.d_mask, words * sizeof(uint32_t));
+    if (!rc) Q.mask_cap = words;
+    return rc;
+}
+
+int query_shadow_mask_host(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, uint32_t *mask)
+{
+    int rc, npos = 0;
+    const int checked = check_mask_args(hits, nhits, lights, nlights, mask, hits, &npos);
+    const size_t words = (size_t)light_mask_words(npos) * (size_t)(nhits > 0 ? nhits : 0);
+    if ((rc = mask_staging(checked, nhits, words))) return rc;
+    QueryRows &Q = g.qrows;
+    const HostArray a[] = { { (void *)hits, &QueryRows::d_hits, (size_t)nhits * sizeof(mirt_hit), true, false },
+                            { mask, &QueryRows::d_mask, words * sizeof(uint32_t), false, words != 0 } };
+    return with_host_arrays(checked, nhits, a, [&] { return query_shadow_mask(Q.d_hits, nhits, lights, nlights, Q.d_mask); });
+}
+
+int query_direct_light_masked_host(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, const uint32_t *mask, float *out_rgb)
+{
+    int rc, npos = 0;
+    const int checked = check_mask_args(hits, nhits, lights, nlights, mask, out_rgb, &npos);
+    const size_t words = (size_t)light_mask_words(npos) * (size_t)(nhits > 0 ? nhits : 0);
+    if ((rc = mask_staging(checked, nhits, words))) return rc;
+    QueryRows &Q = g.qrows;
+    const HostArray a[] = { { (void *)hits, &QueryRows::d_hits, (size_t)nhits * sizeof(mirt_hit), true, false },
+                            { (void *)mask, &QueryRows::d_mask, words * sizeof(uint32_t), words != 0, false },
+                            { out_rgb, &QueryRows::d_rgb, (size_t)nhits * 3 * sizeof(float), false, true } };
+    return with_host_arrays(checked, nhits, a, [&] { return query_direct_light_masked(Q.d_hits, nhits, lights, nlights, Q.d_mask, Q.d_rgb); });
+}
+
 int query_intersect_from_host(const float *origin, const float *dirs3, int nrays, mirt_hit *hits)
 {
     QueryRows &Q = g.qrows;
@@ -797,6 +913,11 @@ extern "C" int mirt_intersect(const mirt_ray *rays, int nrays, mirt_hit *hits) {
 extern "C" int mirt_intersect_device(const void *d_rays, int nrays, void *d_hits) { return mirt::query_intersect(d_rays, nrays, d_hits); }
 extern "C" int mirt_direct_light(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, float *out_rgb) { return mirt::query_direct_light_host(hits, nhits, lights, nlights, out_rgb); }
 extern "C" int mirt_direct_light_device(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_rgb) { return mirt::query_direct_light(d_hits, nhits, lights, nlights, d_rgb); }
+extern "C" int mirt_shadow_mask(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, uint32_t *mask) { return mirt::query_shadow_mask_host(hits, nhits, lights, nlights, mask); }
+extern "C" int mirt_shadow_mask_device(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_mask) { return mirt::query_shadow_mask(d_hits, nhits, lights, nlights, d_mask); }
+extern "C" int mirt_direct_light_masked(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, const uint32_t *mask, float *out_rgb) { return mirt::query_direct_light_masked_host(hits, nhits, lights, nlights, mask, out_rgb); }
+extern "C" int mirt_direct_light_masked_device(const void *d_hits, int nhits, const mirt_light *lights, int nlights, const void *d_mask, void *d_rgb) { return mirt::query_direct_light_masked(d_hits, nhits, lights, nlights, d_mask, d_rgb); }
+extern "C" int mirt_get_shadow_mask_stats(mirt_query_stats *out) { return mirt::query_get_stats(mirt::QUERY_SHADOW_MASK, out); }
 extern "C" int mirt_occluded(const mirt_ray *rays, int nrays, const float *max_distance, uint8_t *occluded) { return mirt::query_occluded_host(rays, nrays, max_distance, occluded); }
 extern "C" int mirt_occluded_device(const void *d_rays, int nrays, const void *d_max_distance, void *d_occluded) { return mirt::query_occluded(d_rays, nrays, d_max_distance, d_occluded); }
 extern "C" int mirt_occluded_fans(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, const float *max_distance, uint8_t *occluded) { return mirt::query_occluded_fans_host(origins3, norigins, origin_of, dirs3, nrays, max_distance, occluded); }

@@ -105,7 +105,8 @@ void CostHist::release()
 
 void QueryScratch::release()
 {
-    dev_free({ d_light_tab, d_origins, d_flags, d_stats[QUERY_DIRECT_LIGHT], d_stats[QUERY_FAN], d_stats[QUERY_OCCLUDED], d_fan_origins, d_fan_rays, d_carry });
+    dev_free({ d_light_tab, d_origins, d_flags, d_stats[QUERY_DIRECT_LIGHT], d_stats[QUERY_FAN], d_stats[QUERY_OCCLUDED], d_stats[QUERY_SHADOW_MASK], d_fan_origins, d_fan_rays, d_carry,
+               d_relight });
     *this = QueryScratch();
 }
 
@@ -129,7 +130,7 @@ void ManyLightsScratch::release()
 
 void QueryRows::release()
 {
-    dev_free({ d_rows, d_max, d_rays, d_hits, d_rgb, d_dirs, d_origin_of, d_limits, d_occluded });
+    dev_free({ d_rows, d_max, d_rays, d_hits, d_rgb, d_dirs, d_origin_of, d_limits, d_occluded, d_mask });
     if (ev_built) (void)hipEventDestroy(ev_built);
     for (LightCache &c : cubes) c.release();
     fan.release();

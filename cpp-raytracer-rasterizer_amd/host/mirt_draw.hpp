@@ -237,6 +237,24 @@ struct RayTracer {
         check(mirt_direct_light(reinterpret_cast<const mirt_hit *>(i), n, reinterpret_cast<const mirt_light *>(lights), NUM_LIGHTS, &result[0].x),
               "mirt_direct_light");
     }
+    // DirectLight's shadow decisions (:306-315) for n records against every light position as the lights and the soft-shadow toggle
+    // stand: bit j & 31 of mask[(j >> 5) * n + k] is 1 where DirectLight(i[k]) sets D = vec3(0) (:314) for position j = light *
+    // samples + sample.  mask: MaskWords() * n words.  Only i[k].position is read (mirt_shadow_mask).
+    int MaskWords() const { return MIRT_MASK_WORDS(NUM_LIGHTS * (SOFT_SHADOWS_ENABLED ? SOFT_SHADOWS_SAMPLES : 1)); }
+    void ShadowMask(const Intersection *i, uint32_t *mask, int n)
+    {
+        marshal();
+        check(mirt_shadow_mask(reinterpret_cast<const mirt_hit *>(i), n, reinterpret_cast<const mirt_light *>(lights), NUM_LIGHTS, mask), "mirt_shadow_mask");
+    }
+    // DirectLight(i) with every shadow ray replaced by its bit of `mask`: after a light changed colour or intensity, or the last
+    // light was deleted (the plane stride stays n), the mask ShadowMask() returned still holds and no ray is cast again
+    // (mirt_direct_light_masked).
+    void DirectLight(const Intersection *i, const uint32_t *mask, vec3 *result, int n)
+    {
+        marshal();
+        check(mirt_direct_light_masked(reinterpret_cast<const mirt_hit *>(i), n, reinterpret_cast<const mirt_light *>(lights), NUM_LIGHTS, mask, &result[0].x),
+              "mirt_direct_light_masked");
+    }
 
 private:
     void upload_scene()

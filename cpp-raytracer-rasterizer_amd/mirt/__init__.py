@@ -31,10 +31,14 @@ EXPORTS = (
     "mirt_intersect_from", "mirt_intersect_from_device", "mirt_get_fan_stats",
     "mirt_intersect_fans", "mirt_intersect_fans_device",
     "mirt_occluded", "mirt_occluded_device", "mirt_occluded_fans", "mirt_occluded_fans_device", "mirt_get_occlusion_stats",
+    "mirt_shadow_mask", "mirt_shadow_mask_device", "mirt_direct_light_masked", "mirt_direct_light_masked_device", "mirt_get_shadow_mask_stats",
     "mirt_scene_upload_device", "mirt_scene_update_device", "mirt_scene_update", "mirt_scene_transform", "mirt_transform",
     "mirt_scene_download", "mirt_scene_info",
     "mirt_scene_set_objects", "mirt_scene_pose", "mirt_pose",
 )
+
+
+_soft_samples = 1                     # samples per light of the last successful set_soft_shadows (1: hard shadows)
 
 
 class MirtError(RuntimeError):
@@ -161,6 +165,11 @@ def load():
     lib.mirt_occluded_fans.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]
     lib.mirt_occluded_fans_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]
     lib.mirt_get_occlusion_stats.argtypes = [C.POINTER(QueryStats)]
+    lib.mirt_shadow_mask.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp]
+    lib.mirt_shadow_mask_device.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp]
+    lib.mirt_direct_light_masked.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp]
+    lib.mirt_direct_light_masked_device.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp]
+    lib.mirt_get_shadow_mask_stats.argtypes = [C.POINTER(QueryStats)]
     lib.mirt_scene_upload_device.argtypes = [_vp, _vp, C.c_int]
     lib.mirt_scene_update_device.argtypes = [C.c_int, C.c_int, _vp]
     lib.mirt_scene_update.argtypes = [C.c_int, C.c_int, _vp]
@@ -218,12 +227,16 @@ def rot_from_yaw(yaw, m11):
 # ---- lifetime ---------------------------------------------------------------------------------------
 
 def init(device=0):
+    global _soft_samples
     _check(load().mirt_init(int(device)))
+    _soft_samples = 1                 # (a fresh context: hard shadows)
 
 
 def shutdown():
+    global _soft_samples
     if _lib is not None:
         _lib.mirt_shutdown()
+    _soft_samples = 1                 # (context state: mirt_shutdown puts it back)
 
 
 def surface_register(arr):
@@ -435,11 +448,14 @@ def set_soft_shadows(samples, positions=None):
     """samples <= 1 turns soft shadows off; otherwise positions is (nlights*samples, 3), at most MAX_LIGHT_POSITIONS rows: up to
     MAX_LIGHTS lights with nlights*samples <= MAX_LIGHT_POSITIONS.  Frames and direct_light* with more than MAX_LIGHTS positions run
     DirectLight in passes (bit-identical); such frames cannot be combined with set_antialiasing."""
+    global _soft_samples
     if samples <= 1:
         _check(load().mirt_set_soft_shadows(1, None, 0))
+        _soft_samples = 1
         return
     p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
     _check(load().mirt_set_soft_shadows(int(samples), _ptr(p), len(p)))
+    _soft_samples = int(samples)
 
 
 # ---- render (host buffers) --------------------------------------------------------------------------
@@ -753,6 +769,72 @@ def occlusion_stats():
     intersect_fans), cube_bins, shells and -- profiling on, binned -- shadow_rays = rays, candidates = rows stepped over, tests =
     rows not beyond the limit, fallback_records = rays that swept their origin's table."""
     return _read_query_stats(load().mirt_get_occlusion_stats)
+
+
+# ---- shadow masks: DirectLight's shadow decisions, and DirectLight from them ---------------------------------
+
+def mask_words(npositions):
+    """Planes of a shadow mask of npositions light positions (MIRT_MASK_WORDS): one uint32 word per record and 32 positions."""
+    return (int(npositions) + 31) // 32
+
+
+def _light_positions(nlights):
+    """lights x samples under the current set_soft_shadows state, as the library counts them (the samples of the last
+    set_soft_shadows call that succeeded: the masks' shapes follow from them)."""
+    return int(nlights) * _soft_samples
+
+
+def shadow_mask(hits, lights7):
+    """DirectLight's shadow decision per (record, light position) (mirt_shadow_mask): a (words, n) uint32 array, position j =
+    light * samples + sample in bit j & 31 of row j >> 5; 1 where DirectLight sets D = 0 (raytracer.cpp:314).  Only the records'
+    positions are read, so bare points with any index get their bits."""
+    hits = np.ascontiguousarray(hits, HIT_DTYPE)
+    larr, nl = make_lights(lights7)
+    out = np.zeros((mask_words(_light_positions(nl)), len(hits)), np.uint32)
+    _check(load().mirt_shadow_mask(_ptr(hits), len(hits), larr, nl, _ptr(out)))
+    return out
+
+
+def shadow_mask_device(d_hits, nhits, lights7, d_mask):
+    """The same on device arrays (raw pointers; d_mask: mask_words(positions) x nhits words), queued like a *_device frame;
+    mirt.sync() completes it."""
+    larr, nl = make_lights(lights7)
+    _check(load().mirt_shadow_mask_device(d_hits, int(nhits), larr, nl, d_mask))
+
+
+def _as_mask(mask, nhits, nlights):
+    """A (words, n) uint32 mask with at least the planes nlights lights need under the current soft-shadow state, C-contiguous (the
+    plane stride is the record count: the mask of more lights serves a prefix of them)."""
+    if not isinstance(mask, np.ndarray) or mask.dtype != np.uint32:
+        raise ValueError("the mask must be a uint32 array")
+    need = mask_words(_light_positions(nlights))
+    if mask.ndim != 2 or mask.shape[1] != nhits or mask.shape[0] < need:
+        raise ValueError("the mask must have shape (>= %d, %d), not %s" % (need, nhits, mask.shape))
+    return np.ascontiguousarray(mask)
+
+
+def direct_light_masked(hits, lights7, mask):
+    """DirectLight(hits[i]) with every shadow ray replaced by its bit of `mask` (mirt_direct_light_masked): (n, 3) float32.  With the
+    mask shadow_mask() returned for the same records, light positions and soft-shadow state it is direct_light() bit for bit,
+    whatever the lights' colours and intensities are now; no ray is cast."""
+    hits = np.ascontiguousarray(hits, HIT_DTYPE)
+    larr, nl = make_lights(lights7)
+    mask = _as_mask(mask, len(hits), nl)
+    out = np.zeros((len(hits), 3), np.float32)
+    _check(load().mirt_direct_light_masked(_ptr(hits), len(hits), larr, nl, _ptr(mask), _ptr(out)))
+    return out
+
+
+def direct_light_masked_device(d_hits, nhits, lights7, d_mask, d_rgb):
+    """The same on device arrays (raw pointers), queued like a *_device frame; mirt.sync() completes it."""
+    larr, nl = make_lights(lights7)
+    _check(load().mirt_direct_light_masked_device(d_hits, int(nhits), larr, nl, d_mask, d_rgb))
+
+
+def shadow_mask_stats():
+    """The last shadow_mask* call (mirt_get_shadow_mask_stats), in mirt_query_stats' fields with DirectLight's meanings; with
+    profiling on the counters are filled for a sweep as well: shadow_rays = records x positions."""
+    return _read_query_stats(load().mirt_get_shadow_mask_stats)
 
 
 # ---- several GPUs: band sharding with the gather inside the library ------------------------------------

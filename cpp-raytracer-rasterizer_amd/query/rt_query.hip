@@ -385,25 +385,53 @@ __device__ __forceinline__ void carry_store(const QueryLightFrame &q, long long 
     c[3 * n] = result2.x; c[4 * n] = result2.y; c[5 * n] = result2.z;
 }
 
+// (defined with the walk kernels below)
+__device__ __forceinline__ void flush_query_stats(unsigned long long *stats, unsigned long long rays, unsigned long long cand,
+                                                  unsigned long long tests, unsigned long long fallback);
+
+// The position of record `rec` alone (record 0 for a lane without one): what a shadow decision depends on.  The index is not read.
+__device__ __forceinline__ v3 record_position(const QueryLightFrame &q, long long rec, bool ok)
+{
+    const uint32_t *h = q.hits + (size_t)HIT_WORDS * (ok ? rec : 0);
+    return V3(__uint_as_float(h[0]), __uint_as_float(h[1]), __uint_as_float(h[2]));
+}
+
 // CARRY: one pass of a call of several (light_passes.hpp) -- the accumulators come from the carry unless the pass is the first,
 // result2 takes result where the GLOBAL position closes a light, and they go back raw unless the pass is the last.
-template <int P, bool FILTER, bool CARRY = false>
+// MASK: the shadow decisions themselves (mirt_shadow_mask*; light_mask.hpp) instead of the colours -- every record that exists
+// casts its rays, whatever its index says (a lane is live for `ok`, not `valid`), collects one bit per position of the pass and
+// stores them once, after the pass's last position.  The sweep and its arithmetic are the ones below, untouched; light_term is
+// called for rDir and r (nothing else of it survives: no accumulators, no carry, no triangle colour).  STATS (MASK only, profiling
+// on): the QSTAT_WORDS counters in q.stats -- shadow rays, the rows offered to them (all n each), the rows a lane tested while it
+// was live, and no fallback: this IS the sweep.
+template <int P, bool FILTER, bool CARRY = false, bool MASK = false, bool STATS = false>
 __device__ __forceinline__ void direct_light_body(const QueryLightFrame &q, float4 *s_tab)
 {
+    static_assert(!(CARRY && MASK), "a mask carries nothing from pass to pass");
+    static_assert(MASK || !STATS, "only the mask's sweep counts");
+    unsigned long long n_rays = 0, n_tests = 0;
     const RtFrame &f = q.f;
     const int first = CARRY ? q.first : 0;
     long long rec[P];
     bool ok[P], valid[P];
     v3 pos[P], nDir[P], tcol[P], result[P], result2[P];
+    uint32_t bits[P];
 #pragma unroll
     for (int p = 0; p < P; p++) {
         rec[p] = lane_ray<P>(p);
         ok[p] = rec[p] < q.nhits;
-        const float *t;
-        valid[p] = light_record(q, rec[p], ok[p], &pos[p], &t, &nDir[p]);
-        tcol[p] = ld3(t + 12);
-        result[p] = result2[p] = V3(0.0f, 0.0f, 0.0f);
-        if (CARRY && ok[p] && !(q.pass_flags & LIGHT_PASS_FIRST)) carry_load(q, rec[p], &result[p], &result2[p]);
+        if constexpr (MASK) {
+            pos[p] = record_position(q, rec[p], ok[p]);
+            nDir[p] = V3(0.0f, 0.0f, 0.0f);
+            valid[p] = ok[p];
+            bits[p] = 0u;
+        } else {
+            const float *t;
+            valid[p] = light_record(q, rec[p], ok[p], &pos[p], &t, &nDir[p]);
+            tcol[p] = ld3(t + 12);
+            result[p] = result2[p] = V3(0.0f, 0.0f, 0.0f);
+            if (CARRY && ok[p] && !(q.pass_flags & LIGHT_PASS_FIRST)) carry_load(q, rec[p], &result[p], &result2[p]);
+        }
     }
 
     for (int k = 0; k < f.nlights; k++) {
@@ -423,6 +451,7 @@ __device__ __forceinline__ void direct_light_body(const QueryLightFrame &q, floa
             live[p] = valid[p];
             exact_only[p] = !dir_in_filter_range(rdp);
             any_live |= live[p];
+            if (STATS) n_rays += valid[p] ? 1u : 0u;
         }
         const OriginRow *tab = f.light_tab + (size_t)k * f.n;
         // every wave of the block takes part in the staging barriers; a wave with nothing left to test skips the inner loop
@@ -438,6 +467,7 @@ __device__ __forceinline__ void direct_light_body(const QueryLightFrame &q, floa
                 test_rays<P, FILTER>(r0, r1, r2, rd, d, maybe);
 #pragma unroll
                 for (int p = 0; p < P; p++) {
+                    if (STATS) n_tests += live[p] ? 1u : 0u;
                     if (live[p] && (maybe[p] || exact_only[p])) {
                         v3 hp;
                         float dist;
@@ -452,29 +482,40 @@ __device__ __forceinline__ void direct_light_body(const QueryLightFrame &q, floa
         }
 #pragma unroll
         for (int p = 0; p < P; p++) {
-            result[p] = add3(result[p], D[p]);                                             // :319
-            if (light_pass_closes(first, k, f.samples)) result2[p] = add3(result2[p], result[p]);   // :322
+            if constexpr (MASK) {
+                bits[p] |= (uint32_t)(valid[p] && !live[p]) << k;                          // the lane that executed :314
+            } else {
+                result[p] = add3(result[p], D[p]);                                             // :319
+                if (light_pass_closes(first, k, f.samples)) result2[p] = add3(result2[p], result[p]);   // :322
+            }
         }
     }
 
 #pragma unroll
     for (int p = 0; p < P; p++) {
         if (!ok[p]) continue;
-        if (CARRY && !(q.pass_flags & LIGHT_PASS_LAST)) { carry_store(q, rec[p], result[p], result2[p]); continue; }
-        st3(q.rgb + 3 * (size_t)rec[p], valid[p] ? reference_nan(mul3(result2[p], tcol[p]), pos[p]) : V3(0.0f, 0.0f, 0.0f));   // :325-326
+        if constexpr (MASK) {
+            light_mask_store(q.mask, (size_t)q.nhits, (size_t)rec[p], q.first, f.nlights, bits[p]);
+        } else {
+            if (CARRY && !(q.pass_flags & LIGHT_PASS_LAST)) { carry_store(q, rec[p], result[p], result2[p]); continue; }
+            st3(q.rgb + 3 * (size_t)rec[p], valid[p] ? reference_nan(mul3(result2[p], tcol[p]), pos[p]) : V3(0.0f, 0.0f, 0.0f));   // :325-326
+        }
     }
+    if (STATS) flush_query_stats(q.stats, n_rays, n_rays * (unsigned)f.n, n_tests, 0ull);
 }
 
-template <int P, bool CARRY>
+template <int P, bool CARRY, bool MASK, bool STATS>
 __global__ __launch_bounds__(256) void k_query_direct_light(const QueryLightFrame q)
 {
     extern __shared__ __attribute__((aligned(16))) float4 s_tab[];
-    if (__builtin_amdgcn_readfirstlane(*q.f.unsafe) == 0u) direct_light_body<P, true, CARRY>(q, s_tab);
-    else direct_light_body<P, false, CARRY>(q, s_tab);
+    if (__builtin_amdgcn_readfirstlane(*q.f.unsafe) == 0u) direct_light_body<P, true, CARRY, MASK, STATS>(q, s_tab);
+    else direct_light_body<P, false, CARRY, MASK, STATS>(q, s_tab);
 }
 
-template __global__ void k_query_direct_light<QUERY_P, false>(const QueryLightFrame);
-template __global__ void k_query_direct_light<QUERY_P, true>(const QueryLightFrame);
+template __global__ void k_query_direct_light<QUERY_P, false, false, false>(const QueryLightFrame);
+template __global__ void k_query_direct_light<QUERY_P, true, false, false>(const QueryLightFrame);
+template __global__ void k_query_direct_light<QUERY_P, false, true, false>(const QueryLightFrame);
+template __global__ void k_query_direct_light<QUERY_P, false, true, true>(const QueryLightFrame);
 
 // ---- k_query_direct_light_binned: DirectLight per hit record, every shadow ray through its light-cube bin ------------------
 //
@@ -556,9 +597,12 @@ __device__ __forceinline__ bool sweep_any_hit(const OriginRow *tab, int n, const
     return swept && !live;
 }
 
-template <int P, bool STATS, bool CARRY>
+// MASK (mirt_shadow_mask*): the decisions instead of the colours, as in direct_light_body -- a record's position alone is read, a
+// lane is live for `ok`, `occluded` becomes bit k of the pass and the bits are stored once (light_mask.hpp).
+template <int P, bool STATS, bool CARRY, bool MASK>
 __global__ __launch_bounds__(256) void k_query_direct_light_binned(const QueryBinnedFrame b)
 {
+    static_assert(!(CARRY && MASK), "a mask carries nothing from pass to pass");
     const QueryLightFrame &q = b.q;
     const RtFrame &f = q.f;
     const int first = CARRY ? q.first : 0;                         // (CARRY: direct_light_body's comment)
@@ -570,10 +614,13 @@ __global__ __launch_bounds__(256) void k_query_direct_light_binned(const QueryBi
     for (int p = 0; p < P; p++) {
         const long long rec = lane_ray<P>(p);
         const bool ok = rec < q.nhits;
-        v3 pos, nDir;
-        const float *t;
-        const bool valid = light_record(q, rec, ok, &pos, &t, &nDir);
+        v3 pos, nDir = V3(0.0f, 0.0f, 0.0f);
+        const float *t = nullptr;
+        bool valid = ok;
+        if constexpr (MASK) pos = record_position(q, rec, ok);
+        else valid = light_record(q, rec, ok, &pos, &t, &nDir);
         v3 result = V3(0.0f, 0.0f, 0.0f), result2 = result;
+        uint32_t bits = 0u;
         if (CARRY && ok && !(q.pass_flags & LIGHT_PASS_FIRST)) carry_load(q, rec, &result, &result2);
         bool fell = false;
         for (int k = 0; k < f.nlights; k++) {
@@ -622,11 +669,19 @@ __global__ __launch_bounds__(256) void k_query_direct_light_binned(const QueryBi
                 if (STATS && swept) { n_cand += (unsigned)f.n; fell = true; }
                 if (STATS) n_tests += rows;
             }
+            if constexpr (MASK) {
+                bits |= (uint32_t)occluded << k;                                           // the lane that would execute :314
+                continue;
+            }
             if (occluded) D = V3(0.0f, 0.0f, 0.0f);                                        // :314
             result = add3(result, D);                                                      // :319
             if (light_pass_closes(first, k, f.samples)) result2 = add3(result2, result);   // :322
         }
         if (STATS) n_fall += fell ? 1u : 0u;
+        if constexpr (MASK) {
+            if (ok) light_mask_store(q.mask, (size_t)q.nhits, (size_t)rec, q.first, f.nlights, bits);
+            continue;
+        }
         if (CARRY && !(q.pass_flags & LIGHT_PASS_LAST)) {
             if (ok) carry_store(q, rec, result, result2);
             continue;
@@ -636,10 +691,53 @@ __global__ __launch_bounds__(256) void k_query_direct_light_binned(const QueryBi
     if (STATS) flush_query_stats(b.stats, n_rays, n_cand, n_tests, n_fall);
 }
 
-template __global__ void k_query_direct_light_binned<QUERY_BIN_P, false, false>(const QueryBinnedFrame);
-template __global__ void k_query_direct_light_binned<QUERY_BIN_P, true, false>(const QueryBinnedFrame);
-template __global__ void k_query_direct_light_binned<QUERY_BIN_P, false, true>(const QueryBinnedFrame);
-template __global__ void k_query_direct_light_binned<QUERY_BIN_P, true, true>(const QueryBinnedFrame);
+template __global__ void k_query_direct_light_binned<QUERY_BIN_P, false, false, false>(const QueryBinnedFrame);
+template __global__ void k_query_direct_light_binned<QUERY_BIN_P, true, false, false>(const QueryBinnedFrame);
+template __global__ void k_query_direct_light_binned<QUERY_BIN_P, false, true, false>(const QueryBinnedFrame);
+template __global__ void k_query_direct_light_binned<QUERY_BIN_P, true, true, false>(const QueryBinnedFrame);
+template __global__ void k_query_direct_light_binned<QUERY_BIN_P, false, false, true>(const QueryBinnedFrame);
+template __global__ void k_query_direct_light_binned<QUERY_BIN_P, true, false, true>(const QueryBinnedFrame);
+
+// ---- k_query_relight: DirectLight with the shadow rays replaced by a mask's bits (mirt_direct_light_masked*) ------------------
+//
+// D = bit ? (0, 0, 0) : light_term per position, then DirectLight's own bookkeeping to the letter: result += D (:319), result2 +=
+// result where the position closes a light (:322), result2 * colour (:325-326), reference_nan, and (0, 0, 0) for an index outside
+// the scene.  Every operand is the one k_query_direct_light* has at that place and the additions run in the same order, so with the
+// mask those kernels' MASK instantiations wrote the colours are theirs bit for bit; a prefix of the lights with the same `samples`
+// reads a prefix of the planes.
+// One lane per record and ONE launch for all of up to MIRT_MAX_LIGHT_POSITIONS positions: no ray is cast, so there is nothing to cut
+// into passes and no carry.  The positions' lpos / lcol are a table in device memory (six floats a position) indexed by the loop
+// counter alone -- wave-uniform, so they arrive by scalar loads; the record's words of the mask are read one plane at a time, the
+// lanes of a wave reading neighbouring words.  light_term wants its RtFrame: position j is handed over as light 0 of a frame of
+// which nothing else is read.  Traffic: 20 bytes of record, 4 per plane, 12 out and a gathered 60-byte triangle row per lane, which
+// is the time for a few positions; from 32 positions on light_term's own arithmetic per position is.
+__global__ __launch_bounds__(256) void k_query_relight(const QueryRelightFrame r)
+{
+    const QueryLightFrame &q = r.q;
+    const long long rec = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (rec >= q.nhits) return;
+    v3 pos, nDir;
+    const float *t;
+    const bool valid = light_record(q, rec, true, &pos, &t, &nDir);
+    v3 result = V3(0.0f, 0.0f, 0.0f), result2 = result;
+    RtFrame one;                                                   // (lpos[0] and lcol[0] are all light_term reads of it)
+    for (int base = 0; base < r.npos; base += LIGHT_MASK_BITS) {
+        const uint32_t m = q.mask[light_mask_index(base / LIGHT_MASK_BITS, (size_t)q.nhits, (size_t)rec)];
+        const int cnt = min(LIGHT_MASK_BITS, r.npos - base);
+        for (int k = 0; k < cnt; k++) {
+            const float *l = r.lights + 6 * (size_t)(base + k);
+            one.lpos[0][0] = l[0]; one.lpos[0][1] = l[1]; one.lpos[0][2] = l[2];
+            one.lcol[0][0] = l[3]; one.lcol[0][1] = l[4]; one.lcol[0][2] = l[5];
+            v3 rd;
+            float rr;
+            v3 D = light_term(one, 0, pos, nDir, &rd, &rr);
+            if ((m >> k) & 1u) D = V3(0.0f, 0.0f, 0.0f);                                   // :314
+            result = add3(result, D);                                                      // :319
+            if (light_pass_closes(base, k, q.f.samples)) result2 = add3(result2, result);  // :322
+        }
+    }
+    st3(q.rgb + 3 * (size_t)rec, valid ? reference_nan(mul3(result2, ld3(t + 12)), pos) : V3(0.0f, 0.0f, 0.0f));   // :325-326
+}
 
 // ---- k_query_fan: ClosestIntersection for many directions from one origin, every ray tests every triangle ------------------
 //

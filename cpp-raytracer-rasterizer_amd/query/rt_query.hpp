@@ -6,6 +6,7 @@
 #include "../csrc/rt_common.hpp"
 #include "../csrc/rt_binned.hpp"
 #include "light_passes.hpp"
+#include "light_mask.hpp"
 
 #include <string.h>
 
@@ -46,6 +47,9 @@ struct QueryFrame {
 // A call of more than MIRT_MAX_LIGHTS positions runs as several passes (light_passes.hpp; the CARRY instantiations of the kernels):
 // f holds the pass's own f.nlights <= MIRT_MAX_LIGHTS positions, `first` says where they stand in the call's list, and the
 // accumulators travel from pass to pass in `carry`.  The kernels of a call of one pass read none of the three.
+// The MASK instantiations (mirt_shadow_mask*) write the shadow decisions of the pass's positions into `mask` (light_mask.hpp)
+// and nothing else: they read a record's position only, `first` in every call, and neither rgb nor carry; k_query_relight
+// (mirt_direct_light_masked*) reads `mask` and writes rgb.
 struct QueryLightFrame {
     RtFrame f;
     const uint32_t *hits;       // nhits x HIT_WORDS: position and index are read
@@ -54,6 +58,8 @@ struct QueryLightFrame {
     int first;                  // global index of the pass's position 0
     float *carry;               // LIGHT_CARRY_WORDS planes of nhits floats: result, result2
     int pass_flags;             // LIGHT_PASS_FIRST | LIGHT_PASS_LAST
+    uint32_t *mask;             // light_mask_words(positions of the call) planes of nhits words
+    unsigned long long *stats;  // QSTAT_WORDS counters of the sweep's MASK + STATS instantiation (the binned kernels': QueryBinnedFrame)
 };
 
 // DirectLight for `nhits` records with every shadow ray walking its light-cube bin (k_query_direct_light_binned): q.f.light_tab
@@ -73,6 +79,15 @@ struct QueryBinnedFrame {
     QueryLightFrame q;
     CubeView cube;
     unsigned long long *stats;          // QSTAT_WORDS counters (the STATS instantiation only)
+};
+
+// DirectLight with the shadow ray of every (record, position) replaced by its bit of q.mask (k_query_relight): all npos <=
+// MIRT_MAX_LIGHT_POSITIONS positions in one launch.  lights: npos rows of six floats, lpos then lcol as RtFrame holds them for a
+// pass; of q.f only tris15, n and samples are read, and of q hits, nhits, mask and rgb.
+struct QueryRelightFrame {
+    QueryLightFrame q;
+    const float *lights;        // npos x 6
+    int npos;
 };
 
 // ---- origin fans: ClosestIntersection for many directions from ONE origin (mirt_intersect_from*) ---------------------------
@@ -191,9 +206,10 @@ constexpr int QUERY_BLOCK_RAYS = 256 * QUERY_P;
 __attribute__((global)) void k_query_rows(const float *, int, QueryRow *, uint32_t *);
 template <int P> __attribute__((global)) void k_query_closest(const QueryFrame);
 __attribute__((global)) void k_query_closest_wave(const QueryFrame);
-template <int P, bool CARRY = false> __attribute__((global)) void k_query_direct_light(const QueryLightFrame);
+template <int P, bool CARRY = false, bool MASK = false, bool STATS = false> __attribute__((global)) void k_query_direct_light(const QueryLightFrame);
 constexpr int QUERY_BIN_P = 1;                    // records per lane of the binned DirectLight kernel: lists differ per lane
-template <int P, bool STATS = false, bool CARRY = false> __attribute__((global)) void k_query_direct_light_binned(const QueryBinnedFrame);
+template <int P, bool STATS = false, bool CARRY = false, bool MASK = false> __attribute__((global)) void k_query_direct_light_binned(const QueryBinnedFrame);
+__attribute__((global)) void k_query_relight(const QueryRelightFrame);
 template <int P> __attribute__((global)) void k_query_fan(const QueryFanFrame);
 template <bool STATS> __attribute__((global)) void k_query_fan_binned(const QueryFanFrame);
 template <bool STATS> __attribute__((global)) void k_query_fans_binned(const QueryFansFrame);

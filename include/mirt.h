@@ -531,6 +531,53 @@ MIRT_API int mirt_occluded_fans_device(const float *origins3, int norigins, cons
  * the ray's limit, fallback_records = rays that swept their origin's table.  Waits for the stream of that call. */
 MIRT_API int mirt_get_occlusion_stats(mirt_query_stats *out);
 
+/* ---- shadow masks: DirectLight's shadow decision per (record, light position), and DirectLight from a mask (additions to ABI 4) ---- */
+
+/* The one value DirectLight computes and throws away (raytracer.cpp:306-315): whether the shadow ray of a record towards a light
+ * position found an occluder nearer than 0.99 r.  mirt_shadow_mask* returns it, one bit per (record, position);
+ * mirt_direct_light_masked* is DirectLight with the ray replaced by that bit.  Together they are mirt_direct_light* in every bit, and
+ * apart they are a relight without shadow rays when a light changes colour or intensity or the last light is deleted, a shadow mask
+ * without shading, the visibility of N points from K positions at one bit a pair, and per-light shadow buffers for compositing.
+ * Positions are mirt_direct_light's: npos = nlights x samples under the current mirt_set_soft_shadows state, position
+ * j = light * samples + sample, with its limits (MIRT_MAX_LIGHTS lights, MIRT_MAX_LIGHT_POSITIONS positions).
+ * Layout: MIRT_MASK_WORDS(npos) planes of nhits words, plane-major -- word w of record i at mask[(size_t)w * nhits + i], position j
+ * in bit j & 31 of word j >> 5. */
+#define MIRT_MASK_WORDS(npositions) (((npositions) + 31) / 32)
+/* Bit j of record i is 1 exactly when DirectLight(hits[i]) executes `D = vec3(0)` (:314) for position j: the decision
+ * mirt_direct_light* itself makes for that record and position, by the same kernels' arithmetic (the rays the cube's bins do not cover
+ * and the per-ray exact-only override included).  Only the record's POSITION is read, not its index: a list of bare points, any
+ * index, gets its bits -- unlike mirt_direct_light, which casts no ray for an index outside [0, n).
+ * Exactly MIRT_MASK_WORDS(npos) x nhits words are written, bits at or beyond npos as 0, and nothing beyond them; with npos == 0
+ * nothing is written.  mirt_set_query_mode applies with mirt_direct_light's rules unchanged (AUTO: the same rule over records x
+ * positions x triangles, or the cubes held; a call the frame path would not bin sweeps; one range of positions that fits no cube
+ * sends the whole call to the sweep), and the passes, the kept cubes and the borrowed frame-path cube are mirt_direct_light's own:
+ * a cube either call built serves the other.  No scratch travels between the passes: a record's bits belong to its own lane.
+ * Checks, in mirt_direct_light's order: MIRT_ERR_NOT_INITIALISED; MIRT_ERR_INVALID_ARGUMENT for a negative count, a NULL array with
+ * a positive count (the mask: when there are records and positions) or the lights' limits; nhits == 0 does nothing;
+ * MIRT_ERR_NO_SCENE.  mirt_shadow_mask: host arrays, complete on return.  mirt_shadow_mask_device: device arrays, queued like
+ * mirt_direct_light_device (the streams in turn; mirt_sync() completes it).  Neither form touches mirt_get_stats,
+ * mirt_get_query_stats, mirt_get_fan_stats or mirt_get_occlusion_stats. */
+MIRT_API int mirt_shadow_mask(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, uint32_t *mask);
+MIRT_API int mirt_shadow_mask_device(const void *d_hits, int nhits, const mirt_light *lights, int nlights, void *d_mask);
+/* out_rgb[3*i ..] = DirectLight(hits[i]) with, per position, D = bit ? (0, 0, 0) : the light's term (:294-304) in the place of the
+ * shadow ray; everything else is DirectLight's: result += D (:319), result2 += result where the position closes a light (:322), the
+ * multiply by the triangle's colour (:325-326), the reference's NaN bits, and (0, 0, 0) for an index outside [0, n).  A pure
+ * function of records, lights, soft-shadow state and mask: it builds no cube, casts no ray, keeps no statistics and ignores
+ * mirt_set_query_mode.  With the mask mirt_shadow_mask* returned for the same records, lights and state it equals
+ * mirt_direct_light* in every bit -- whatever the lights' colours and intensities are now: the bits depend on positions only.  A
+ * prefix of the lights under the same `samples` reads a prefix of the planes (the plane stride stays nhits), so the mask of three
+ * lights serves after the last was deleted.  With npos == 0 the mask is not read and the result is mirt_direct_light's without
+ * lights.  Checks and queuing as above. */
+MIRT_API int mirt_direct_light_masked(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights,
+                                      const uint32_t *mask, float *out_rgb);
+MIRT_API int mirt_direct_light_masked_device(const void *d_hits, int nhits, const mirt_light *lights, int nlights,
+                                             const void *d_mask, void *d_rgb);
+/* The last mirt_shadow_mask* call, in mirt_query_stats' fields with DirectLight's meanings; cube_source is folded over the passes as
+ * for mirt_direct_light.  With mirt_set_profiling(1) the counters are filled for a binned call AND for a sweep: shadow_rays =
+ * records x positions (every record casts its rays), candidates = rows offered (the sweep: all n per ray), tests = rows tested
+ * before the ray's first occluder, fallback_records as for mirt_direct_light (0 for a sweep).  Waits for the stream of that call. */
+MIRT_API int mirt_get_shadow_mask_stats(mirt_query_stats *out);
+
 /* ---- rasteriser: replaces Update()'s clear + Draw() + CalculateDOF() of rasteriser.cpp:183-192,461-529 */
 
 /* One frame into host buffers.  Every word of out_xrgb is written: the whole surface is cleared to black

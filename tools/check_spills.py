@@ -48,8 +48,12 @@ EXPECT = ("k_rt_trace2", "k_rt_tile2", "k_rt_brute", "k_bin_pairs", "k_raster_sm
           "k_query_fan<", "k_query_fan_binned<false>", "k_query_fan_binned<true>", "k_query_fans_binned<false>", "k_query_fans_binned<true>",
           "k_query_fans_expand",
           "k_query_occluded<", "k_query_occluded_wave", "k_query_occluded_fans_binned<false>", "k_query_occluded_fans_binned<true>",
-          "k_query_direct_light<2, false>", "k_query_direct_light<2, true>", "k_query_direct_light_binned<1, false, false>",
-          "k_query_direct_light_binned<1, true, false>", "k_query_direct_light_binned<1, false, true>", "k_query_direct_light_binned<1, true, true>",
+          # <P, CARRY, MASK, STATS> and <P, STATS, CARRY, MASK>: the carrying instantiations, then the shadow masks'
+          "k_query_direct_light<2, false, false, false>", "k_query_direct_light<2, true, false, false>",
+          "k_query_direct_light_binned<1, false, false, false>", "k_query_direct_light_binned<1, true, false, false>",
+          "k_query_direct_light_binned<1, false, true, false>", "k_query_direct_light_binned<1, true, true, false>",
+          "k_query_direct_light<2, false, true, false>", "k_query_direct_light<2, false, true, true>",
+          "k_query_direct_light_binned<1, false, false, true>", "k_query_direct_light_binned<1, true, false, true>", "k_query_relight",
           "k_frame_records", "k_frame_resolve",
           "k_scene_bounds_init", "k_scene_range<1>", "k_scene_range<3>", "k_scene_range<5>", "k_scene_range<7>", "k_scene_range<4>", "k_scene_range<11>")
 missing = [k for k in EXPECT if not any(k in r[1] for r in rows)]

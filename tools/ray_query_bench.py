@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans,occluded]
+"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans,occluded,mask]
 
 The measurements of the ray-query kernels (query/rt_query.hip), written to one text file:
 
@@ -32,6 +32,13 @@ The measurements of the ray-query kernels (query/rt_query.hip), written to one t
                        each beside what a caller had to do before for the same answer, in the same run: mirt_intersect_device /
                        mirt_intersect_fans_device from fresh records on the same rays.  The answers are compared first; the cells
                        where an occlusion call is behind, and where binning with the builds crosses the brute path, are listed.
+  mask                 mirt_shadow_mask_device and mirt_direct_light_masked_device beside mirt_direct_light_device on the same records, lights
+                       and cubes, the three calls in turn: 2^10 .. 2^21 records x 1, 2, 32, 64, 256 positions x 2000 and 100 000
+                       triangles, under MIRT_QUERY_BRUTE (cells beyond 2e11 row tests are named, not run) and MIRT_QUERY_BINNED with the
+                       cubes held.  One cell measured seven times over gives the run-to-run spread; the cells where the mask call is
+                       behind mirt_direct_light_device by more than that are listed, and for the masked call its ratio to
+                       mirt_direct_light_device and the bytes it must move over its time as a share of the HBM peak.  Mask + relight
+                       is compared with mirt_direct_light_device's colours in every cell.
 
 The knob is read once per process, so every GPU step is a child process of its own, under its own `timeout`; a step that fails
 ends the run."""
@@ -766,6 +773,116 @@ def step_occluded(p):
     occluded_summary(out, p)
 
 
+# ---- shadow masks: mirt_shadow_mask_device and mirt_direct_light_masked_device beside mirt_direct_light_device ------------------------
+
+MASK_SETS = ((1, 1), (2, 1), (2, 16), (4, 16), (16, 16))      # lights x samples: 1, 2, 32, 64 and 256 positions
+MASK_RECORDS = tuple(1 << e for e in range(10, 22))
+MASK_BRUTE_CAP = 2.0e11                                       # records x positions x triangles a BRUTE cell may cost (0.2 - 0.5 s a call)
+HBM_PEAK = 8.0e12                                             # bytes per second (MI355X: 8 TB/s)
+
+
+def mask_lights(nl, samples):
+    """nl lights inside the scene's box -- the first the default light -- and their samples' jittered positions (None for hard shadows)."""
+    import mirt
+    rng = np.random.default_rng(11)
+    L = np.zeros((nl, 7), np.float32)
+    L[:, 0:3] = rng.uniform(-0.75, 0.75, (nl, 3))
+    L[:, 3:6] = rng.choice(np.array([0.25, 0.5, 0.75, 1.0], np.float32), (nl, 3))
+    L[:, 6] = rng.integers(3, 15, nl)
+    L[0] = np.asarray(mirt.DEFAULT_LIGHT, np.float32).reshape(-1, 7)[0]
+    jit = None
+    if samples > 1:
+        jit = (np.repeat(L[:, 0:3], samples, axis=0) + rng.uniform(-0.05, 0.05, (nl * samples, 3))).astype(np.float32)
+    return L, jit
+
+
+def mask_cell(mirt, d_hits, k, L, d_rgb, d_mask, d_rgb2, reps):
+    """The three calls in turn, `reps` rounds after one unmeasured round: median ms of each."""
+    calls = (lambda: mirt.direct_light_device(d_hits, k, L, d_rgb), lambda: mirt.shadow_mask_device(d_hits, k, L, d_mask),
+             lambda: mirt.direct_light_masked_device(d_hits, k, L, d_mask, d_rgb2))
+    ts = [[], [], []]
+    for r in range(reps + 1):
+        for i, fn in enumerate(calls):
+            t0 = time.perf_counter()
+            fn(); mirt.sync()
+            if r:
+                ts[i].append((time.perf_counter() - t0) * 1e3)
+    return [float(np.median(t)) for t in ts]
+
+
+def child_mask(mode, n, spread):
+    """One scene and one mode: every light set x every record count (spread: one cell, measured seven times over)."""
+    import mirt
+    h = hip()
+    mirt.init(0)
+    d_hits, count = closest_records(mirt, h, n, 0.05 if n >= 50000 else 0.2)
+    top = MASK_RECORDS[-1]
+    rec = np.zeros(count, mirt.HIT_DTYPE)
+    assert h.hipMemcpy(rec.ctypes.data_as(C.c_void_p), d_hits, rec.nbytes, 2) == 0
+    rec = rec[np.random.default_rng(5).permutation(count)]     # (a small call samples the whole frame)
+    rec = np.ascontiguousarray(np.concatenate([rec, rec[:top - count]]))     # 1080p is 23 552 records short of 2^21
+    h.hipFree(d_hits)
+    d_hits = dev_alloc(h, rec.nbytes, rec)
+    d_rgb, d_rgb2, d_mask = dev_alloc(h, top * 12), dev_alloc(h, top * 12), dev_alloc(h, top * 4 * 8)
+    a, b = np.zeros((top, 3), np.float32), np.zeros((top, 3), np.float32)
+    mirt.set_query_mode(mirt.QUERY_BRUTE if mode == "brute" else mirt.QUERY_BINNED)
+    for nl, samples in (((2, 16),) if spread else MASK_SETS):
+        L, jit = mask_lights(nl, samples)
+        mirt.set_soft_shadows(samples, jit)
+        npos = nl * samples
+        for k in ((1 << 18,) * 7 if spread else MASK_RECORDS):
+            if mode == "brute" and float(k) * npos * n > MASK_BRUTE_CAP:
+                print("RESULT mask n %6d mode %-6s positions %3d records %8d  not measured: beyond %.0e row tests" % (n, mode, npos, k, MASK_BRUTE_CAP))
+                continue
+            dl, mk, rl = mask_cell(mirt, d_hits, k, L, d_rgb, d_mask, d_rgb2, 5 if k <= 65536 else 3)
+            st, sm = mirt.query_stats(), mirt.shadow_mask_stats()
+            assert st["mode_used"] == sm["mode_used"] and (mode == "brute" or (st["cube_source"] == 2 and sm["cube_source"] == 2)), (st, sm)
+            # the answers: mask, then relight, is mirt_direct_light_device
+            assert h.hipMemcpy(a.ctypes.data_as(C.c_void_p), d_rgb, k * 12, 2) == 0 and h.hipMemcpy(b.ctypes.data_as(C.c_void_p), d_rgb2, k * 12, 2) == 0
+            assert np.array_equal(a[:k].view(np.uint32), b[:k].view(np.uint32)), "mask + relight differs from mirt_direct_light_device"
+            moved = k * (20 + 4 * mirt.mask_words(npos) + 12 + 60)
+            print("RESULT mask n %6d mode %-6s positions %3d records %8d  direct_light %10.4f  shadow_mask %10.4f  masked %8.4f ms  masked: %.0f MB, %4.1f %% of HBM peak"
+                  % (n, mode, npos, k, dl, mk, rl, moved / 1e6, 100.0 * moved / (rl * 1e-3) / HBM_PEAK))
+            sys.stdout.flush()
+    mirt.set_soft_shadows(1)
+    mirt.shutdown()
+
+
+MASK_ROW = re.compile(r"mask n\s+(\d+) mode (\S+)\s+positions\s+(\d+) records\s+(\d+)  direct_light\s+([0-9.]+)  shadow_mask\s+([0-9.]+)  masked\s+([0-9.]+) ms")
+
+
+def step_mask(p):
+    p("== mask: mirt_shadow_mask_device and mirt_direct_light_masked_device beside mirt_direct_light_device -- the same records, lights and cubes, "
+      "the three calls in turn (host clock around call + mirt_sync, medians) ==")
+    p("records: the closest hits of the scene's 1080p primary rays in a fixed shuffled order; positions 1, 2: hard lights, 32, 64, 256: 2, 4, 16 lights x 16 samples; "
+      "binned: BINNED with every cube held; masked: bytes the call must move (20 record + 4 per plane + 12 out + 60 triangle row, per record) over its time")
+    out = run_child(p, ["--child", "mask", "binned", "100000", "spread"], {}, 300)
+    rows = [tuple(float(x) for x in m.groups()[4:]) for m in MASK_ROW.finditer(out)]
+    spread = max((max(c) - min(c)) / float(np.median(c)) for c in zip(*rows)) if rows else 0.0
+    p("run-to-run spread of the cell above (seven measurements of n 100000, 32 positions, 2^18 records, binned): the medians of a call differ by up to %.1f %% of their median" % (100 * spread))
+    p("")
+    for n in (100000, 2000):
+        for mode in ("brute", "binned"):
+            out += run_child(p, ["--child", "mask", mode, str(n), "grid"], {}, 400)
+    cells = {}
+    for m in MASK_ROW.finditer(out):
+        cells[(int(m.group(1)), m.group(2), int(m.group(3)), int(m.group(4)))] = tuple(float(x) for x in m.groups()[4:])
+    behind = ["n %d %s, %d positions, %d records: %.4f against %.4f ms" % (k + (v[1], v[0])) for k, v in sorted(cells.items()) if v[1] > (1 + spread) * v[0]]
+    p("")
+    p("mirt_shadow_mask_device behind mirt_direct_light_device by more than the spread (%.1f %%) in %d of %d cells: %s" % (100 * spread, len(behind), len(cells), "; ".join(behind) or "nowhere"))
+    worst = max(cells.items(), key=lambda kv: kv[1][1] / kv[1][0])
+    ahead = [1 - v[1] / v[0] for v in cells.values()]
+    p("its largest deficit: %.1f %% (n %d %s, %d positions, %d records: %.4f against %.4f ms); ahead in %d cells, by %.1f %% in the median and %.1f %% at most"
+      % ((100 * (worst[1][1] / worst[1][0] - 1),) + worst[0] + (worst[1][1], worst[1][0], sum(a > 0 for a in ahead), 100 * float(np.median(ahead)), 100 * max(ahead))))
+    ratios = [v[0] / v[2] for v in cells.values()]
+    p("mirt_direct_light_device / mirt_direct_light_masked_device: %.1f .. %.1f, median %.1f" % (min(ratios), max(ratios), float(np.median(ratios))))
+    # AUTO decides between the modes by mirt_direct_light's rule: does the faster mode of a cell differ between the two calls?
+    differ = ["n %d, %d positions, %d records" % (n, q, k) for (n, mode, q, k), v in sorted(cells.items())
+              if mode == "brute" and (n, "binned", q, k) in cells and (v[0] < cells[(n, "binned", q, k)][0]) != (v[1] < cells[(n, "binned", q, k)][1])]
+    p("cells where the faster of BRUTE and BINNED-held is one mode for mirt_direct_light_device and the other for mirt_shadow_mask_device: %s" % ("; ".join(differ) or "none"))
+    p("")
+
+
 def run_child(p, args, env, limit):
     cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__)] + args
     r = subprocess.run(cmd, env=dict(os.environ, **env), capture_output=True, text=True)
@@ -832,6 +949,8 @@ def main():
             return child_occsweep(int(a.child[1]))
         if a.child[0] == "occfans":
             return child_occfans(int(a.child[1]))
+        if a.child[0] == "mask":
+            return child_mask(a.child[1], int(a.child[2]), a.child[3] == "spread")
         return child_throughput() if a.child[0] == "throughput" else child_sweep(int(a.child[1]))
     lines = []
 
@@ -856,6 +975,8 @@ def main():
             step_fans(p)
         if "occluded" in steps:
             step_occluded(p)
+        if "mask" in steps:
+            step_mask(p)
     finally:
         with open(a.out, "a" if a.append else "w") as f:
             f.write("\n".join(lines) + "\n")
