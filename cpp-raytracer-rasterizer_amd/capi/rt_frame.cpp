@@ -47,6 +47,8 @@ BinFrameDesc make_camera_frame(const mirt_view *view, int y0, int y1, int aa)
         memcpy(c.S, view->pos, 12);
         c.ulo = 0.0f; c.vlo = 0.0f; c.du = (float)BIN_TILE; c.dv = (float)BIN_TILE;
         // bin i covers the rays of pixels 8i .. 8i+7: exactly their centres, or with supersampling half a pixel around them
+        // (at 4, 6, 7 and 8 samples the chain of sub-ray coordinates ends up to a few ulp beyond the half pixel; the edge-function
+        // margin covers that 20 times over: tests/test_aa_reach.py)
         c.pad_lo = aa > 1 ? -0.5f : 0.0f; c.pad_hi = aa > 1 ? -0.5f : -1.0f;
         c.nbu = (W + BIN_TILE - 1) / BIN_TILE; c.nbv = (H + BIN_TILE - 1) / BIN_TILE;
         c.j0 = y0 / BIN_TILE; c.j1 = (y1 + BIN_TILE - 1) / BIN_TILE;

@@ -177,7 +177,8 @@ __device__ __forceinline__ void tile_body2(const RtTileFrame &tf, int tx, int ty
         t.s.c0 = d4.x; t.s.cu = d4.y; t.s.cv = d4.z; t.s.m = d4.w;
         t.nb = tb.cam[3 * lane].w;
         t.bstate = BOX_NONE; t.bu0 = t.bu1 = t.bv0 = t.bv1 = 0.0f;
-        // (with supersampling the sub-rays reach half a pixel beyond the pixel centres on every side)
+        // (with supersampling the sub-rays reach half a pixel beyond the pixel centres on every side -- at 4, 6, 7 and 8 samples up to
+        // a few ulp more, which rect_may_hit's margin covers 20 times over: tests/test_aa_reach.py)
         cand = rect_may_hit(t, (float)x0 - reach, (float)min(x0 + TW - 1, f.W - 1) + reach,
                             (float)y0 - reach, (float)min(y0 + 2 * TH - 1, f.y1 - 1) + reach);
     }
