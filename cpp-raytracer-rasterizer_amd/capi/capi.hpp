@@ -1,7 +1,8 @@
 // capi.hpp -- the host side of the C-ABI (csrc/mirt_capi.hip and the files of this directory): the library's state, one
 // StreamState per frame in flight inside one Ctx, and the helpers the topic files share.  Host code only: the frame kernels are
 // defined under csrc/, the ray-query kernels under query/, the scene kernels under scene/ and the kernels of a deferred frame under lights/
-// (tools/check_spills.py compiles all four); the ones launched from here are declared below, in query/rt_query.hpp and in lights/many_lights.hpp.
+// (tools/check_spills.py compiles all four); the ones launched from here are declared below, in query/rt_query.hpp, in lights/many_lights.hpp
+// and in lights/aa_many_lights.hpp.
 #pragma once
 
 #include "../csrc/bin_sort.hpp"
@@ -15,10 +16,12 @@
 #include "../csrc/scan.hpp"
 #include "../query/rt_query.hpp"
 #include "../lights/many_lights.hpp"
+#include "../lights/aa_many_lights.hpp"
 #include "cube_plan.hpp"
 #include "pass_plan.hpp"
 #include "object_plan.hpp"
 #include "dof_plan.hpp"
+#include "aa_plan.hpp"
 #include "env.hpp"
 
 #include <cstdarg>
@@ -281,6 +284,24 @@ struct ManyLightsScratch {
     void release();
 };
 
+// What a supersampled frame that shades each carried record once (rt_frame.cpp: aa_record_once_frame, ../lights/aa_many_lights.hip)
+// keeps between the kernels of a chunk of rows, per stream and grow-only: the chunk's record list with DirectLight's answers and
+// carry, sized for the worst case of pixels x aa x aa records (aa_plan.hpp), the pixels' (slot, count) pairs and version counts, the
+// list's cursor, and the two statistics of the stream's last such frame (mirt_get_supersample_stats).
+struct AaScratch {
+    uint32_t *d_records = nullptr;               // cap_rec x HIT_WORDS
+    float *d_direct = nullptr;                   // cap_rec x 3
+    float *d_carry = nullptr;                    // LIGHT_CARRY_WORDS x cap_rec
+    uint32_t *d_slots = nullptr, *d_counts = nullptr;   // cap_rec each
+    uint32_t *d_nver = nullptr;                  // cap_px
+    uint32_t *d_cursor = nullptr;                // one word
+    unsigned long long *d_stats = nullptr;       // [0] hit sub-rays, [1] records shaded
+    size_t cap_rec = 0, cap_px = 0;
+
+    int ensure(size_t px, size_t rec);           // (the stream must be idle when they grow: ensure waits for it)
+    void release();
+};
+
 // The ray-independent rows of ClosestIntersection (k_query_rows): built once per scene version on the stream of the query that
 // finds them missing, shared by every stream; a query on another stream waits for ev_built, not for the device.
 struct QueryRows {
@@ -316,6 +337,10 @@ struct QueryRows {
     // Apart from `fan` and `cubes`: the call evicts neither, and a pass whose positions are the ones g.lc or cubes[0] holds reads
     // that cube instead (query.cpp: walk_cube).
     LightCache fans[QUERY_LIGHT_CUBES];
+    // The cube around the camera of a supersampled frame that shades each carried record once (k_aa_primary's binned instantiation):
+    // one position, keyed by scene version and camera position, built by light_cache_ensure under the same protocol.  Apart from
+    // `fan`, so that a frame does not evict the cube mirt_intersect_from* keeps; a frame whose camera stands still finds it held.
+    LightCache aa_cam;
 
     void release();                              // (the cubes' tables too)
 };
@@ -349,6 +374,7 @@ struct StreamState {
     RasterScratch raster;
     QueryScratch query;
     ManyLightsScratch many;
+    AaScratch aa;
     // cull flags: what this stream's copy of d_culled holds -- the number of the cull call (or upload) it comes from --, and the
     // copies OUT of other streams' copies it has made: the event is re-recorded behind every such copy ...
     uint64_t culled_ver = 0;
@@ -407,6 +433,9 @@ struct Ctx {
     int dof_k = 0;                               // DOF_KERNEL_SIZE when DOF_ENABLED, else 0
     float dof_focal = 0.0f;                      // FOCAL_LENGTH
     int soft_npos = 0;
+    bool aa_many_lights = false;                 // mirt_set_supersampled_many_lights: supersampled frames of many positions shade each record once
+    hipStream_t aa_stats_stream = nullptr;       // the stream of the last such frame and its two counters (AaScratch::d_stats), NULL: none yet
+    const unsigned long long *aa_stats_dev = nullptr;
     float soft_pos[MIRT_MAX_LIGHT_POSITIONS * 3] = {};   // jittered light positions, [light*samples + i] (randomPositions[256], raytracer.cpp:84)
 
     // host surfaces the caller registered (mirt_surface_register): pinned + mapped, so the frame reaches them at link speed
@@ -532,6 +561,9 @@ struct LightPositions {
 };
 // The position count from which a frame is deferred (MIRT_MANY_LIGHTS_MIN, default MIRT_MAX_LIGHTS + 1: what the fused kernels cannot hold).
 int many_lights_min();
+// The position count from which a supersampled frame shades each carried record once when mirt_set_supersampled_many_lights is on
+// (MIRT_AA_DEFER_MIN, default MIRT_MAX_LIGHTS + 1: every frame the fused kernels can render stays with them).
+int aa_defer_min();
 void fill_light_positions(const mirt_light *lights, int npos, float (*lpos)[3], float (*lcol)[3], float *origins);
 // MIRT_RT_AUTO / MIRT_QUERY_AUTO bin nothing below this many triangles (MIRT_BIN_THRESHOLD; the tile kernel takes up to 64).
 int auto_bin_threshold();
@@ -581,6 +613,11 @@ int query_direct_light_masked(const void *d_hits, int nhits, const mirt_light *l
 int query_direct_light_masked_host(const mirt_hit *hits, int nhits, const mirt_light *lights, int nlights, const uint32_t *mask, float *out_rgb);
 bool direct_light_auto_bins(int nhits, int npos);
 int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, void *d_hits);
+// The cube around `cam` for the `subrays` primary sub-rays of a supersampled frame in frame mode `mode` on the current stream, under
+// the single fan's rules (query_intersect_from): *cube is g.qrows.aa_cam, built if need be (the build bracketed as the frame's binning
+// step), or NULL when the frame sweeps -- MIRT_RT_BRUTE, a scene the fan rule would not bin, a scene or camera outside the filter's
+// proven range, keys the sort cannot hold.  mirt_set_query_mode and the queries' statistics are untouched.
+int aa_camera_cube(const float *cam, int mode, long long subrays, const LightCache **cube);
 int query_intersect_from_host(const float *origin, const float *dirs3, int nrays, mirt_hit *hits);
 int query_intersect_fans(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, void *d_hits);
 int query_intersect_fans_host(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, mirt_hit *hits);

@@ -546,6 +546,32 @@ int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, vo
     return launch_walk(k_query_fan_binned<false>, k_query_fan_binned<true>, q.stats != nullptr, dim3((unsigned)((nrays + 255) / 256)), q);
 }
 
+// The primary sub-rays of a supersampled frame that shades each record once are such a fan from the camera (rt_frame.cpp,
+// ../lights/aa_many_lights.hip): binned or swept as the single fan decides it, with the FRAME's mode in the place of
+// mirt_set_query_mode and the frame's sub-ray count in AUTO's rule; the cube is the frames' own (g.qrows.aa_cam).
+int aa_camera_cube(const float *cam, int mode, long long subrays, const LightCache **cube)
+{
+    int rc;
+    *cube = nullptr;
+    float origins[6] = {};
+    memcpy(origins + 3, cam, 12);
+    bool fixed_grid = false;
+    const int cube_bins = light_cube_bins_for(1, &fixed_grid);
+    const bool may_bin = starts_safe(cam, 1) && light_keys_fit(1, cube_bins);
+    const bool held = may_bin && held_cube({}, g.qrows.aa_cam, origins, 1, cube_bins).cube != nullptr;
+    const int qmode = mode == MIRT_RT_BRUTE ? MIRT_QUERY_BRUTE : (mode == MIRT_RT_BINNED ? MIRT_QUERY_BINNED : MIRT_QUERY_AUTO);
+    const bool auto_rule = g.n >= auto_bin_threshold() && (g.n >= FAN_AUTO_TRIANGLES || subrays * g.n >= 40000000LL);   // (auto_bins_fan)
+    if (!query_bins(may_bin, qmode, held, auto_rule)) return MIRT_OK;
+    CubeChoice c = held_cube({}, g.qrows.aa_cam, origins, 1, cube_bins);
+    if (!c.cube) {                                           // (a build: the frame's binning step, as a deferred frame's light cubes)
+        if (!g.cur().ev_used[MIRT_K_BIN]) k_begin(MIRT_K_BIN);
+        if ((rc = walk_cube({}, g.qrows.aa_cam, origins, 1, cube_bins, &c))) return rc;
+        k_end(MIRT_K_BIN);
+    }
+    *cube = c.cube;
+    return MIRT_OK;
+}
+
 // ---- origin fans from many origins in one call (mirt_intersect_fans*) ----------------------------------------------------------
 //
 // The call's origins go into cubes of up to MIRT_MAX_LIGHTS positions each, as the lights of a DirectLight query do, in passes over

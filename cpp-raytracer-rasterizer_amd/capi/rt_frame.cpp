@@ -77,6 +77,19 @@ int many_lights_min()
     return v;
 }
 
+int aa_defer_min()
+{
+    static const int v = (int)env_int("MIRT_AA_DEFER_MIN", MIRT_MAX_LIGHTS + 1);
+    return v;
+}
+
+// Whether a frame of so many light positions shades each carried record once (aa_record_once_frame): supersampling on, the opt-in
+// on (mirt_set_supersampled_many_lights), and at least MIRT_AA_DEFER_MIN positions.
+static bool aa_record_once(int light_positions)
+{
+    return g.aa_many_lights && g.aa > 1 && light_positions >= aa_defer_min();
+}
+
 // Whether a frame of so many light positions is deferred (rt_enqueue): always beyond what RtFrame carries, and from
 // MIRT_MANY_LIGHTS_MIN positions on when that is set lower -- but never a supersampled frame the fused kernels can render.
 static bool frame_deferred(int light_positions)
@@ -170,7 +183,8 @@ bool rt_bins_whole_frame(const mirt_view *view, const mirt_light *lights, int nl
     const int samples = soft_samples(), npos = nlights * samples;
     // (check_lights' conditions, without its messages: the question is asked, not a frame)
     if (!view || nlights < 0 || nlights > MIRT_MAX_LIGHTS || (nlights && !lights) || npos > MIRT_MAX_LIGHT_POSITIONS || (samples > 1 && npos > g.soft_npos)) return false;
-    if (npos > MIRT_MAX_LIGHTS && g.aa > 1) return false;    // (rt_enqueue refuses the frame)
+    if (npos > MIRT_MAX_LIGHTS && g.aa > 1) return false;    // (rt_enqueue refuses the frame, or shades each record once: no tile pass)
+    if (aa_record_once(npos)) return false;
     // a deferred frame: the answer is its primary pass's, which has no light
     const int fused = frame_deferred(npos) ? 0 : npos;
     float origins[(1 + MIRT_MAX_LIGHTS) * 3];
@@ -291,6 +305,114 @@ static int deferred_lights(const RtFrame &f, const mirt_light *lights, int npos,
     return MIRT_OK;
 }
 
+// A supersampled frame that shades each carried record once (../lights/aa_versions.hpp has the argument, aa_many_lights.hip the
+// kernels, aa_plan.hpp the chunks): the band in chunks of rows, per chunk the list's fill (0xFF: index -1, which DirectLight answers
+// with zeros and never traces), k_aa_primary -- through the cube around the camera, or sweeping the camera's origin table --,
+// DirectLight over the whole capacity of the list in passes (query.cpp: direct_light_passes, as deferred_lights calls it) and
+// k_aa_resolve, all on the frame's stream with no read-back.  AUTO's rule for the passes is decided once, from the band's pixels.
+// The chunks are the frame's trace step, the cube builds its binning step.
+static int aa_record_once_frame(const mirt_view *view, const mirt_light *lights, int npos, const float *indirect, int mode,
+                                int y0, int y1, int row_origin, void *d_xrgb, int pitch_bytes, void *d_rgb, void *d_index, void *d_fd,
+                                void *d_dist, void *d_pos)
+{
+    int rc;
+    static const long long budget_mb = env_int("MIRT_AA_DEFER_SCRATCH_MB", AA_DEFER_SCRATCH_DEFAULT_MB);
+    static const int forced_rows = (int)env_int("MIRT_AA_DEFER_ROWS", 0);
+    const int W = view->width, aa = g.aa;
+    call_begin();
+    g.pending_is_rt = true;
+    g.pending_primary = (uint64_t)W * (uint64_t)(y1 - y0) * (uint64_t)(aa * aa);
+    g.pending_nlights = npos;
+    g.stats.mode_used = MIRT_RT_BRUTE;
+    g.pending_empty = (y1 == y0);
+    g.pending_counted = false;
+    if (y1 == y0) { call_end(); return MIRT_OK; }
+    StreamState &ss = g.cur();
+    ss.hits_tog ^= 1;
+    g.d_hits = ss.d_hits[ss.hits_tog];
+    HIP_TRY(hipMemsetAsync(g.d_hits, 0, HIT_BYTES, g.stream));
+    ss.hits_clean[ss.hits_tog] = false;
+
+    const int rows_per_chunk = aa_chunk_rows(W, y1 - y0, aa, std::max(budget_mb, 0ll) << 20, forced_rows);
+    const size_t chunk_px = (size_t)W * rows_per_chunk, cap = aa_chunk_records(W, rows_per_chunk, aa);
+    AaScratch &A = ss.aa;
+    if ((rc = A.ensure(chunk_px, cap))) return rc;
+    HIP_TRY(hipMemsetAsync(A.d_stats, 0, 16, g.stream));
+    g.aa_stats_stream = g.stream;
+    g.aa_stats_dev = A.d_stats;
+
+    AaFrame a;
+    memset(&a, 0, sizeof a);
+    a.tris15 = g.d_tris;
+    a.n = g.n;
+    memcpy(a.cam, view->pos, sizeof a.cam);
+    memcpy(a.rot, view->rot, sizeof a.rot);
+    a.focal = view->focal;
+    a.W = W; a.H = view->height; a.aa = aa;
+    a.row_origin = row_origin;
+    a.index = static_cast<int32_t *>(d_index);
+    a.fd = static_cast<float *>(d_fd);
+    a.focal_plane = g.dof_focal;
+    a.dist = static_cast<float *>(d_dist);
+    a.pos = static_cast<float *>(d_pos);
+    a.hit_count = g.d_hits;
+    a.records = A.d_records; a.cursor = A.d_cursor; a.slots = A.d_slots; a.counts = A.d_counts; a.nver = A.d_nver;
+    a.direct = A.d_direct;
+    memcpy(a.indirect, indirect, 12);
+    a.xrgb = static_cast<uint32_t *>(d_xrgb);
+    a.pitch_words = pitch_bytes / 4;
+    a.rgb = static_cast<float *>(d_rgb);
+    a.stats = A.d_stats;
+
+    // the primary sub-rays: through the camera's cube, or sweeping its origin table (built as for any brute-force frame)
+    const LightCache *cube = nullptr;
+    if ((rc = aa_camera_cube(view->pos, mode, (long long)g.pending_primary, &cube))) return rc;
+    if (cube) {
+        a.tab = cube->d_light_tab;
+        a.cube = cube_view(*cube);
+        g.stats.mode_used = MIRT_RT_BINNED;
+    } else {
+        OriginTables &S = ss.tabs;
+        if ((rc = S.ensure_cam_rows())) return rc;
+        if (!S.d_origins) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_origins), sizeof(float) * 3 * (1 + MIRT_MAX_LIGHTS)));
+        if (!S.d_flags) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d_flags), 16));
+        const uint32_t flags_init[4] = { operands_safe(view, view->pos, 0) ? 0u : 1u, 0u, 0u, 0u };
+        HIP_TRY(upload_small(S.d_flags, flags_init, sizeof flags_init, g.stream));
+        ss.cam.kept.forget();                    // (k_prep_origin below overwrites the camera rows a kept binning pass would count on)
+        HIP_TRY(upload_small(S.d_origins, view->pos, sizeof(float) * 3, g.stream));
+        k_begin(MIRT_K_PREP);
+        hipLaunchKernelGGL(k_prep_origin, dim3((g.n + 255) / 256, 1), dim3(256), 0, g.stream,
+                           g.d_tris, g.n, S.d_origins, V3(0.0f, 0.0f, 0.0f), 0, S.d_cam_tab, S.d_light_tab, S.d_flags, (unsigned long long *)nullptr, (uint32_t *)nullptr);
+        k_end(MIRT_K_PREP);
+        HIP_TRY(hipGetLastError());
+        a.tab = S.d_cam_tab;
+        a.unsafe = S.d_flags;
+    }
+
+    const int qmode = mode == MIRT_RT_BRUTE ? MIRT_QUERY_BRUTE : (mode == MIRT_RT_BINNED ? MIRT_QUERY_BINNED : MIRT_QUERY_AUTO);
+    const long long band_px = (long long)W * (y1 - y0);
+    const bool auto_rule = direct_light_auto_bins((int)std::min<long long>(band_px, 0x7fffffffLL), npos);
+    const int nchunks = aa_chunk_count(y0, y1, rows_per_chunk);
+    if (!ss.ev_used[MIRT_K_TRACE]) k_begin(MIRT_K_TRACE);
+    for (int c = 0; c < nchunks; c++) {
+        aa_chunk_of(y0, y1, rows_per_chunk, c, &a.y0, &a.y1);
+        const size_t px = (size_t)W * (a.y1 - a.y0), records = aa_chunk_records(W, a.y1 - a.y0, aa);
+        const dim3 grid((unsigned)((px + 255) / 256));
+        HIP_TRY(hipMemsetAsync(A.d_records, 0xFF, records * HIT_WORDS * sizeof(uint32_t), g.stream));
+        HIP_TRY(hipMemsetAsync(A.d_cursor, 0, 4, g.stream));
+        if (cube) hipLaunchKernelGGL(k_aa_primary<true>, grid, dim3(256), 0, g.stream, a);
+        else hipLaunchKernelGGL(k_aa_primary<false>, grid, dim3(256), sweep_lds_bytes(), g.stream, a);
+        HIP_TRY(hipGetLastError());
+        size_t carry_cap = A.cap_rec;                        // (ensure sized it for these records)
+        if ((rc = direct_light_passes(A.d_records, (int)records, lights, npos, A.d_direct, qmode, auto_rule, false, &A.d_carry, &carry_cap))) return rc;
+        hipLaunchKernelGGL(k_aa_resolve, grid, dim3(256), 0, g.stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    k_end(MIRT_K_TRACE);
+    call_end();
+    return MIRT_OK;
+}
+
 int rt_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect, int mode,
                int y0, int y1, int row_origin, void *d_xrgb, int pitch_bytes, void *d_rgb, void *d_index, void *d_fd,
                void *d_dist, void *d_pos)
@@ -304,7 +426,10 @@ int rt_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, con
     // More positions than RtFrame carries: the frame is deferred (deferred_lights) -- its primary pass below renders with no light.
     // Supersampling shades the record a pixel carries at each of its aa x aa sub-rays (raytracer.cpp:580-594), which one record per
     // pixel cannot hold.
+    // With mirt_set_supersampled_many_lights on, such a frame shades each record the pixel carries once instead (aa_record_once_frame).
     const bool deferred = frame_deferred(light_positions);
+    if (aa_record_once(light_positions))
+        return aa_record_once_frame(view, lights, light_positions, indirect, mode, y0, y1, row_origin, d_xrgb, pitch_bytes, d_rgb, d_index, d_fd, d_dist, d_pos);
     if (light_positions > MIRT_MAX_LIGHTS && g.aa > 1)
         return fail(MIRT_ERR_INVALID_ARGUMENT, "supersampling (mirt_set_antialiasing %d) cannot be combined with %d light positions: more than %d are rendered with one record per pixel",
                     g.aa, light_positions, MIRT_MAX_LIGHTS);
@@ -377,3 +502,27 @@ int rt_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, con
 }
 
 }  // namespace mirt
+
+extern "C" int mirt_set_supersampled_many_lights(int on)
+{
+    int rc;
+    if ((rc = mirt::need_init())) return rc;
+    mirt::g.aa_many_lights = on != 0;
+    return MIRT_OK;
+}
+
+extern "C" int mirt_get_supersample_stats(uint64_t *hit_subrays, uint64_t *records_shaded)
+{
+    using namespace mirt;
+    int rc;
+    if ((rc = need_init())) return rc;
+    if (!hit_subrays || !records_shaded) return fail(MIRT_ERR_INVALID_ARGUMENT, "hit_subrays / records_shaded must not be NULL");
+    unsigned long long c[2] = { 0ull, 0ull };
+    if (g.aa_stats_dev) {
+        HIP_TRY(hipStreamSynchronize(g.aa_stats_stream));
+        HIP_TRY(hipMemcpy(c, g.aa_stats_dev, sizeof c, hipMemcpyDeviceToHost));
+    }
+    *hit_subrays = c[0];
+    *records_shaded = c[1];
+    return MIRT_OK;
+}

@@ -128,12 +128,34 @@ void ManyLightsScratch::release()
     *this = ManyLightsScratch();
 }
 
+int AaScratch::ensure(size_t px, size_t rec)
+{
+    int rc;
+    if (!d_cursor) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_cursor), 16));
+    if (!d_stats) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_stats), 16));
+    if (px <= cap_px && rec <= cap_rec) return MIRT_OK;
+    HIP_TRY(hipStreamSynchronize(g.stream));     // an earlier frame of the stream may still read the old buffers
+    px = std::max(px, cap_px); rec = std::max(rec, cap_rec);
+    cap_px = cap_rec = 0;
+    if ((rc = dev_realloc(&d_records, rec * HIT_WORDS)) || (rc = dev_realloc(&d_direct, rec * 3)) || (rc = dev_realloc(&d_carry, rec * LIGHT_CARRY_WORDS)) ||
+        (rc = dev_realloc(&d_slots, rec)) || (rc = dev_realloc(&d_counts, rec)) || (rc = dev_realloc(&d_nver, px))) return rc;
+    cap_px = px; cap_rec = rec;
+    return MIRT_OK;
+}
+
+void AaScratch::release()
+{
+    dev_free({ d_records, d_direct, d_carry, d_slots, d_counts, d_nver, d_cursor, d_stats });
+    *this = AaScratch();
+}
+
 void QueryRows::release()
 {
     dev_free({ d_rows, d_max, d_rays, d_hits, d_rgb, d_dirs, d_origin_of, d_limits, d_occluded, d_mask });
     if (ev_built) (void)hipEventDestroy(ev_built);
     for (LightCache &c : cubes) c.release();
     fan.release();
+    aa_cam.release();
     for (LightCache &c : fans) c.release();
     *this = QueryRows();
 }
@@ -160,6 +182,7 @@ void StreamState::release()
     raster_scratch_free(raster);
     query.release();
     many.release();
+    aa.release();
     dof.release();
     dev_free({ d_hits[0], d_hits[1], d_tile_tab, d_async });
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);

@@ -132,6 +132,7 @@ struct RayTracer {
     Surface screen = { nullptr, 0, 0, 0 };           // :76
     bool isUpdated = true;                           // :78
     bool scene_dirty = true;                         // set when `triangles` changes
+    bool many_lights_aa_on = false;                  // mirt_set_supersampled_many_lights(1) has been called (once: context state)
     bool AA_ENABLED = false;                         // :37
     int AA_SAMPLES = 3;                              // :38
     bool SOFT_SHADOWS_ENABLED = false;               // :40
@@ -267,6 +268,8 @@ private:
     mirt_view marshal()                                            // the globals -> the POD arguments of mirt.h
     {
         upload_scene();
+        // the reference renders AA_ENABLED with more than 32 jittered positions (a third light under soft shadows): so does the adapter
+        if (!many_lights_aa_on) { check(mirt_set_supersampled_many_lights(1), "mirt_set_supersampled_many_lights"); many_lights_aa_on = true; }
         check(mirt_set_antialiasing(AA_ENABLED ? AA_SAMPLES : 1), "mirt_set_antialiasing");   // realSamples (:549-554)
         if (SOFT_SHADOWS_ENABLED)                                  // DirectLight's `samples` (:272-275); the whole array fits: MIRT_MAX_LIGHT_POSITIONS = 256
             check(mirt_set_soft_shadows(SOFT_SHADOWS_SAMPLES, &randomPositions[0].x, NUM_LIGHTS * SOFT_SHADOWS_SAMPLES), "mirt_set_soft_shadows");

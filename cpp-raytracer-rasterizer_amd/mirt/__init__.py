@@ -35,6 +35,7 @@ EXPORTS = (
     "mirt_scene_upload_device", "mirt_scene_update_device", "mirt_scene_update", "mirt_scene_transform", "mirt_transform",
     "mirt_scene_download", "mirt_scene_info",
     "mirt_scene_set_objects", "mirt_scene_pose", "mirt_pose",
+    "mirt_set_supersampled_many_lights", "mirt_get_supersample_stats",
 )
 
 
@@ -118,6 +119,8 @@ def load():
     lib.mirt_scene_load_stl.argtypes = [C.c_char_p, C.c_float, _vp, _vp, C.c_int]
     lib.mirt_set_soft_shadows.argtypes = [C.c_int, _vp, C.c_int]
     lib.mirt_set_depth_of_field.argtypes = [C.c_int, C.c_float]
+    lib.mirt_set_supersampled_many_lights.argtypes = [C.c_int]
+    lib.mirt_get_supersample_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.mirt_set_frames_in_flight.argtypes = [C.c_int]
     lib.mirt_raytrace.argtypes = [C.POINTER(View), _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
     lib.mirt_raytrace_device.argtypes = [C.POINTER(View), _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -444,10 +447,26 @@ def set_antialiasing(samples):
     _check(load().mirt_set_antialiasing(int(samples)))
 
 
+def set_supersampled_many_lights(on):
+    """Supersampled frames of more than MAX_LIGHTS light positions (the reference's AA + soft shadows with a third light) are
+    rendered, each record a pixel carries shaded once, bit for bit the reference's sum (mirt_set_supersampled_many_lights).  Off by
+    default, and again after shutdown(): the frame is refused."""
+    _check(load().mirt_set_supersampled_many_lights(1 if on else 0))
+
+
+def supersample_stats():
+    """The last such frame (mirt_get_supersample_stats; waits for it): "hit_subrays", the sub-rays that hit -- each shades the
+    carried record in the reference --, and "records_shaded", the records DirectLight was actually asked for."""
+    a, b = C.c_uint64(0), C.c_uint64(0)
+    _check(load().mirt_get_supersample_stats(C.byref(a), C.byref(b)))
+    return {"hit_subrays": int(a.value), "records_shaded": int(b.value)}
+
+
 def set_soft_shadows(samples, positions=None):
     """samples <= 1 turns soft shadows off; otherwise positions is (nlights*samples, 3), at most MAX_LIGHT_POSITIONS rows: up to
     MAX_LIGHTS lights with nlights*samples <= MAX_LIGHT_POSITIONS.  Frames and direct_light* with more than MAX_LIGHTS positions run
-    DirectLight in passes (bit-identical); such frames cannot be combined with set_antialiasing."""
+    DirectLight in passes (bit-identical); such frames are combined with set_antialiasing only while
+    set_supersampled_many_lights is on (off by default: the frame is refused)."""
     global _soft_samples
     if samples <= 1:
         _check(load().mirt_set_soft_shadows(1, None, 0))

@@ -310,8 +310,9 @@ MIRT_API int mirt_pose(const float *rest15, int nrest, const mirt_object *object
  * passes' kernels as it chooses the frame's (mirt_set_query_mode does not govern frames); mirt_stats reports the primary pass's
  * mode_used and shadow_rays = positions x pixels that hit.  Supersampling (mirt_set_antialiasing) shades a carried record per
  * sub-ray, which one record per pixel cannot follow: a frame with more than MIRT_MAX_LIGHTS positions AND supersampling on
- * returns MIRT_ERR_INVALID_ARGUMENT.  MIRT_MANY_LIGHTS_MIN (environment, default 33) lowers the position count from which
- * frames without supersampling are deferred. */
+ * returns MIRT_ERR_INVALID_ARGUMENT unless mirt_set_supersampled_many_lights (below) is on, which renders it.
+ * MIRT_MANY_LIGHTS_MIN (environment, default 33) lowers the position count from which frames without supersampling are
+ * deferred. */
 MIRT_API int mirt_set_soft_shadows(int samples, const float *positions, int npositions);
 
 /* Depth of field (DOF_ENABLED / DOF_KERNEL_SIZE / FOCAL_LENGTH, raytracer.cpp:43-45,613-640; rasteriser.cpp:29-31,
@@ -323,8 +324,26 @@ MIRT_API int mirt_set_depth_of_field(int kernel_size, float focal_length);
 
 /* Supersampling (AA_ENABLED / AA_SAMPLES, raytracer.cpp:37-38,549-599): samples > 1 fires samples x samples sub-rays
  * per pixel and averages them, reproducing the reference's loop exactly (the pixel's closest-hit record is carried
- * across the sub-rays, x1 only advances after a sub-ray that hit).  samples <= 1 switches it off.  The reference uses 3. */
+ * across the sub-rays, x1 only advances after a sub-ray that hit).  samples <= 1 switches it off.  The reference uses 3.
+ * Up to MIRT_MAX_LIGHTS light positions the fused frame kernels render such a frame; with more, see below. */
 MIRT_API int mirt_set_antialiasing(int samples);
+
+/* Supersampled frames with more than MIRT_MAX_LIGHTS light positions (the reference's AA_ENABLED + SOFT_SHADOWS_ENABLED with a
+ * third light: 48 positions, 3 x 3 sub-rays).  on != 0: such a frame -- every mirt_raytrace* form, row bands, depth of field,
+ * asynchronous and sharded frames included -- is rendered by shading each record a pixel carries ONCE: the carried record only ever
+ * moves to a closer (or equal) hit and DirectLight depends on the record alone, so consecutive sub-rays that shade the same record
+ * add the same bits; the pixel's sum is "c_0 times R_0, then c_1 times R_1, ..." added one term at a time, bit for bit the
+ * reference's.  The band is rendered in chunks of rows inside a scratch budget per stream (MIRT_AA_DEFER_SCRATCH_MB, default 256;
+ * MIRT_AA_DEFER_ROWS forces the rows of a chunk); `mode` chooses the primary sub-rays' kernel (a cube around the camera, or a sweep)
+ * and the DirectLight passes' kernels; mirt_stats reports primary_rays = pixels x samples^2, shadow_rays = positions x sub-rays
+ * that hit, and mode_used = MIRT_RT_BINNED when the primary sub-rays walked the camera's cube.  MIRT_AA_DEFER_MIN (environment,
+ * default 33) lowers the position count from which supersampled frames take this path while it is on.
+ * Off by default: the frame is then refused as described at mirt_set_soft_shadows.  Flipping the default is left to a later
+ * change.  Context state: mirt_shutdown puts it back to 0. */
+MIRT_API int mirt_set_supersampled_many_lights(int on);
+/* The last such frame: the sub-rays that hit (each shades the carried record in the reference) and the records actually shaded.
+ * Waits for the frame's stream; zeros when no such frame has run. */
+MIRT_API int mirt_get_supersample_stats(uint64_t *hit_subrays, uint64_t *records_shaded);
 
 /* ---- ray tracer: replaces Draw() + CalculateDOF() of raytracer.cpp:547-656 -------------------------- */
 

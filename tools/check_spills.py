@@ -54,7 +54,7 @@ EXPECT = ("k_rt_trace2", "k_rt_tile2", "k_rt_brute", "k_bin_pairs", "k_raster_sm
           "k_query_direct_light_binned<1, false, true, false>", "k_query_direct_light_binned<1, true, true, false>",
           "k_query_direct_light<2, false, true, false>", "k_query_direct_light<2, false, true, true>",
           "k_query_direct_light_binned<1, false, false, true>", "k_query_direct_light_binned<1, true, false, true>", "k_query_relight",
-          "k_frame_records", "k_frame_resolve",
+          "k_frame_records", "k_frame_resolve", "k_aa_primary<false>", "k_aa_primary<true>", "k_aa_resolve",
           "k_scene_bounds_init", "k_scene_range<1>", "k_scene_range<3>", "k_scene_range<5>", "k_scene_range<7>", "k_scene_range<4>", "k_scene_range<11>")
 missing = [k for k in EXPECT if not any(k in r[1] for r in rows)]
 if missing or len(rows) < 20:
