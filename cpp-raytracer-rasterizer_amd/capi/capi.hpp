@@ -15,6 +15,7 @@
 #include "../csrc/rt_trace_frame.hpp"
 #include "../csrc/scan.hpp"
 #include "../query/rt_query.hpp"
+#include "../along/along.hpp"
 #include "../lights/many_lights.hpp"
 #include "../lights/aa_many_lights.hpp"
 #include "cube_plan.hpp"
@@ -237,8 +238,9 @@ struct DofPlanes {
 };
 
 // The queries that walk a cube and keep statistics: DirectLight (mirt_get_query_stats), origin fans (mirt_get_fan_stats) and
-// occlusion queries (mirt_get_occlusion_stats) and shadow masks (mirt_get_shadow_mask_stats).
-enum { QUERY_DIRECT_LIGHT = 0, QUERY_FAN = 1, QUERY_OCCLUDED = 2, QUERY_SHADOW_MASK = 3, QUERY_KINDS = 4 };
+// occlusion queries (mirt_get_occlusion_stats) and shadow masks (mirt_get_shadow_mask_stats); and the queries along one direction,
+// which walk a grid of their own (mirt_get_along_stats).
+enum { QUERY_DIRECT_LIGHT = 0, QUERY_FAN = 1, QUERY_OCCLUDED = 2, QUERY_SHADOW_MASK = 3, QUERY_ALONG = 4, QUERY_KINDS = 5 };
 // The last query of a kind: how it was answered, the stream it ran on and where its kernel's counters are (device; profiling on,
 // binned -- read once, query_get_stats).
 struct QueryStats {
@@ -302,6 +304,34 @@ struct AaScratch {
     void release();
 };
 
+// The structure of the queries along one direction (along.cpp; ../along/along.hpp): the grid across `dir` over the scene's projected
+// bounding box, kept per (scene version, direction) as the fans keep their cube -- shared by the streams, ordered among them by
+// events, released in mirt_shutdown, forgotten with the scene through the version it is held under.  The build's pair list and sort
+// scratch are its own, so that a build disturbs no stream's kept binning pass.
+struct AlongCache {
+    bool valid = false;
+    uint64_t version = 0;                        // what the structure was built for: the scene version, the triangle count ...
+    int n = 0;
+    float dir[3] = { 0, 0, 0 };                  // ... and the direction, compared bit for bit
+    bool gave_up = false;                        // the every-ray list outgrew its share: calls with this key take the brute-force kernels
+    AlongDesc desc = {};
+    uint32_t *d_off = nullptr;                   // along_keys + 1
+    uint32_t cap_keys = 0;
+    QueryRow *d_rows = nullptr;                  // the rows in key order (at least one: a lane with no row left loads row 0)
+    AlongAux *d_aux = nullptr;
+    uint32_t cap_rows = 0, nrows = 0;
+    float *d_near = nullptr;                     // n depth bounds (k_along_pairs -> k_along_rows)
+    int cap_near = 0;
+    uint32_t *d_counters = nullptr;              // [0] pairs, [1] triangles on the every-ray list
+    uint32_t *d_keys = nullptr, *d_vals = nullptr, *d_tmp_keys = nullptr, *d_tmp_vals = nullptr, *d_entries = nullptr;
+    uint32_t cap_pairs = 0;
+    uint32_t *d_bucket = nullptr;                // bucket sort: counts | bases (+1) | cursors, cap_buckets each
+    uint32_t cap_buckets = 0;
+
+    bool holds(uint64_t v, int count, const float *d) const { return valid && version == v && n == count && memcmp(dir, d, 12) == 0; }
+    void release();
+};
+
 // The ray-independent rows of ClosestIntersection (k_query_rows): built once per scene version on the stream of the query that
 // finds them missing, shared by every stream; a query on another stream waits for ev_built, not for the device.
 struct QueryRows {
@@ -341,6 +371,8 @@ struct QueryRows {
     // one position, keyed by scene version and camera position, built by light_cache_ensure under the same protocol.  Apart from
     // `fan`, so that a frame does not evict the cube mirt_intersect_from* keeps; a frame whose camera stands still finds it held.
     LightCache aa_cam;
+    // The grid of the queries along one direction (mirt_intersect_along*, mirt_occluded_along*): one is kept.
+    AlongCache along;
 
     void release();                              // (the cubes' tables too)
 };
@@ -627,6 +659,47 @@ int query_occluded_fans(const float *origins3, int norigins, const void *d_origi
                         void *d_occluded);
 int query_occluded_fans_host(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, const float *max_distance,
                              uint8_t *occluded);
+
+// What along.cpp shares with the queries above (query.cpp): the scene's rows on the current stream, the scene check, the brute-force
+// launches, the statistics of a kind, the many-origin fans' AUTO rule, and the host-buffer wrapper.
+int query_rows();
+int query_need_scene();
+QueryFrame rows_frame(const void *d_rays, int nrays, void *d_hits);
+int intersect_launch(const void *d_rays, int nrays, void *d_hits);
+int occluded_launch(const void *d_rays, int nrays, const void *d_limit, void *d_occluded);
+QueryStats &stats_begin(int kind, bool binned);
+int stats_arm(int kind, unsigned long long **counters);
+int query_get_stats(int kind, mirt_query_stats *out);
+bool auto_bins_fans(int nrays);
+int query_staging(size_t count);
+// One host-buffer entry point around its device form `call`, given the verdict of that form's argument checks and the call's
+// `count` of rays or records: nothing to do for none, then the scene, then staging room for `count`; every `in` array goes to its
+// staging array (a member of g.qrows) on the stream the call will take, every `out` array comes back on the stream it took, and
+// the host waits for that stream.
+struct HostArray { void *host; void *QueryRows::*staging; size_t bytes; bool in, out; };
+template <int N, class Call>
+int with_host_arrays(int checked, int count, const HostArray (&a)[N], Call call)
+{
+    int rc;
+    if (checked) return checked;
+    if (count == 0) return MIRT_OK;
+    if ((rc = query_need_scene())) return rc;
+    if ((rc = query_staging((size_t)count))) return rc;
+    hipStream_t st = g.streams[next_si()].stream;            // the stream the query below will take
+    for (const HostArray &x : a)
+        if (x.in) HIP_TRY(hipMemcpyAsync(g.qrows.*x.staging, x.host, x.bytes, hipMemcpyHostToDevice, st));
+    if ((rc = call())) return rc;
+    for (const HostArray &x : a)
+        if (x.out) HIP_TRY(hipMemcpyAsync(x.host, g.qrows.*x.staging, x.bytes, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return MIRT_OK;
+}
+
+// ---- ray queries along one direction (along.cpp; the kernels: ../along/along.hip) ----
+int along_intersect(const float *dir, const void *d_origins3, int nrays, void *d_hits);
+int along_intersect_host(const float *dir, const float *origins3, int nrays, mirt_hit *hits);
+int along_occluded(const float *dir, const void *d_origins3, int nrays, const void *d_max_distance, void *d_occluded);
+int along_occluded_host(const float *dir, const float *origins3, int nrays, const float *max_distance, uint8_t *occluded);
 
 // ---- rasteriser (raster.cpp) ----
 int raster_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect,

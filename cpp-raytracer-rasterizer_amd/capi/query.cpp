@@ -28,7 +28,7 @@ static long query_wave_rays()
 
 // The rows of the current scene on the current stream: built here when the scene changed (mirt_scene_upload waited for every
 // stream, so nothing still reads the old ones), otherwise this stream is ordered behind the build once, by its event.
-static int query_rows()
+int query_rows()
 {
     int rc;
     QueryRows &Q = g.qrows;
@@ -69,14 +69,14 @@ static int check_from_args(const float *origin, const void *dirs3, int nrays, co
     return MIRT_OK;
 }
 
-static int need_scene()
+int query_need_scene()
 {
     if (g.n <= 0) return fail(MIRT_ERR_NO_SCENE, "no scene uploaded (mirt_scene_upload)");
     return MIRT_OK;
 }
 
 // What the brute-force kernels read of the scene (query_rows) and of the caller: nrays rays and, for closest hits, their records.
-static QueryFrame rows_frame(const void *d_rays, int nrays, void *d_hits)
+QueryFrame rows_frame(const void *d_rays, int nrays, void *d_hits)
 {
     QueryFrame q;
     q.rows = g.qrows.d_rows;
@@ -104,7 +104,7 @@ static int launch_sweep(void (*wave)(Frame), void (*lane)(Frame), int nrays, con
 }
 
 // ClosestIntersection by brute force for nrays > 0 rays on the current stream: the scene's rows, then one of the two kernels.
-static int intersect_launch(const void *d_rays, int nrays, void *d_hits)
+int intersect_launch(const void *d_rays, int nrays, void *d_hits)
 {
     int rc;
     if ((rc = query_rows())) return rc;
@@ -116,7 +116,7 @@ int query_intersect(const void *d_rays, int nrays, void *d_hits)
     int rc;
     if ((rc = check_query_args(d_rays, nrays, d_hits, "ray"))) return rc;
     if (nrays == 0) return MIRT_OK;
-    if ((rc = need_scene())) return rc;
+    if ((rc = query_need_scene())) return rc;
     stream_begin();
     return intersect_launch(d_rays, nrays, d_hits);
 }
@@ -126,7 +126,7 @@ int query_intersect(const void *d_rays, int nrays, void *d_hits)
 // (the view of a cube's tables, cube_view: capi.hpp)
 
 // A query of `kind` starts on the current stream: its statistics begin afresh.
-static QueryStats &stats_begin(int kind, bool binned)
+QueryStats &stats_begin(int kind, bool binned)
 {
     QueryStats &Q = g.qstats[kind];
     memset(&Q.s, 0, sizeof Q.s);
@@ -145,7 +145,7 @@ static void stats_cube(QueryStats &Q, const LightCache &C, int source)
 
 // With profiling on, the stream's counters of `kind` zeroed on the stream and noted for query_get_stats: *counters is what the
 // STATS instantiation of the walk kernel counts into, NULL says to launch the plain one.
-static int stats_arm(int kind, unsigned long long **counters)
+int stats_arm(int kind, unsigned long long **counters)
 {
     *counters = nullptr;
     if (!g.profiling) return MIRT_OK;
@@ -406,7 +406,7 @@ int query_direct_light(const void *d_hits, int nhits, const mirt_light *lights, 
     if ((rc = check_query_args(d_hits, nhits, d_rgb, "hit"))) return rc;
     if ((rc = check_lights(lights, nlights, &npos))) return rc;
     if (nhits == 0) return MIRT_OK;
-    if ((rc = need_scene())) return rc;
+    if ((rc = query_need_scene())) return rc;
     QueryScratch &S = g.streams[next_si()].query;            // the stream the call will take: its carry
     return direct_light_passes(d_hits, nhits, lights, npos, d_rgb, g.query_mode, auto_bins(nhits, npos), true, &S.d_carry, &S.carry_cap);
 }
@@ -437,7 +437,7 @@ int query_shadow_mask(const void *d_hits, int nhits, const mirt_light *lights, i
     int rc, npos = 0;
     if ((rc = check_mask_args(d_hits, nhits, lights, nlights, d_mask, d_hits, &npos))) return rc;
     if (nhits == 0) return MIRT_OK;
-    if ((rc = need_scene())) return rc;
+    if ((rc = query_need_scene())) return rc;
     if (npos == 0) return MIRT_OK;                           // no plane: nothing is written
     return direct_light_passes(d_hits, nhits, lights, npos, nullptr, g.query_mode, auto_bins(nhits, npos), true, nullptr, nullptr, d_mask);
 }
@@ -447,7 +447,7 @@ int query_direct_light_masked(const void *d_hits, int nhits, const mirt_light *l
     int rc, npos = 0;
     if ((rc = check_mask_args(d_hits, nhits, lights, nlights, d_mask, d_rgb, &npos))) return rc;
     if (nhits == 0) return MIRT_OK;
-    if ((rc = need_scene())) return rc;
+    if ((rc = query_need_scene())) return rc;
 
     QueryRelightFrame r;
     memset(&r, 0, sizeof r);
@@ -510,7 +510,7 @@ int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, vo
     int rc;
     if ((rc = check_from_args(origin, d_dirs3, nrays, d_hits))) return rc;
     if (nrays == 0) return MIRT_OK;
-    if ((rc = need_scene())) return rc;
+    if ((rc = query_need_scene())) return rc;
 
     QueryFanFrame q = fan_frame(d_dirs3, nrays, d_hits);
     memcpy(q.origin, origin, 12);
@@ -589,7 +589,7 @@ int aa_camera_cube(const float *cam, int mode, long long subrays, const LightCac
 // 0.54 ms; n = 100 000: 0.6 ms against 0.83 .. 2.4 ms).  Beyond that many rays binning with its builds was ahead in every cell at n =
 // 100 000 (9 .. 11 ms against 22 .. 681 ms) and in all but two at n = 2000 -- 4 origins x 4096 rays (0.60 against 0.53 ms) and
 // 128 origins x 64 rays (four builds: 1.30 against 0.53 ms) --, where AUTO stays behind brute force.
-static bool auto_bins_fans(int nrays)
+bool auto_bins_fans(int nrays)
 {
     return auto_bins_fan(nrays) && (long)nrays > query_wave_rays();
 }
@@ -684,7 +684,7 @@ int query_intersect_fans(const float *origins3, int norigins, const void *d_orig
     int rc;
     if ((rc = check_fans_args(origins3, norigins, d_origin_of, d_dirs3, nrays, d_hits))) return rc;
     if (nrays == 0) return MIRT_OK;
-    if ((rc = need_scene())) return rc;
+    if ((rc = query_need_scene())) return rc;
 
     std::vector<FanPass> plan;
     const std::initializer_list<CubeChoice> foreign = { { &g.lc, 3 }, { &g.qrows.cubes[0], 4 } };
@@ -712,7 +712,7 @@ int query_intersect_fans(const float *origins3, int norigins, const void *d_orig
 // every call of either form begins them afresh, and no call touches the fans' or DirectLight's.
 
 // The brute-force kernels for nrays > 0 rays on the current stream.
-static int occluded_launch(const void *d_rays, int nrays, const void *d_limit, void *d_occluded)
+int occluded_launch(const void *d_rays, int nrays, const void *d_limit, void *d_occluded)
 {
     int rc;
     if ((rc = query_rows())) return rc;
@@ -725,7 +725,7 @@ int query_occluded(const void *d_rays, int nrays, const void *d_max_distance, vo
     int rc;
     if ((rc = check_query_args(d_rays, nrays, d_occluded, "ray"))) return rc;
     if (nrays == 0) return MIRT_OK;
-    if ((rc = need_scene())) return rc;
+    if ((rc = query_need_scene())) return rc;
     stream_begin();
     stats_begin(QUERY_OCCLUDED, false);
     return occluded_launch(d_rays, nrays, d_max_distance, d_occluded);
@@ -742,7 +742,7 @@ int query_occluded_fans(const float *origins3, int norigins, const void *d_origi
     int rc;
     if ((rc = check_fans_args(origins3, norigins, d_origin_of, d_dirs3, nrays, d_occluded))) return rc;
     if (nrays == 0) return MIRT_OK;
-    if ((rc = need_scene())) return rc;
+    if ((rc = query_need_scene())) return rc;
 
     std::vector<FanPass> plan;
     const std::initializer_list<CubeChoice> foreign = { { &g.lc, 3 }, { &g.qrows.cubes[0], 4 } };
@@ -783,7 +783,7 @@ int query_set_mode(int mode)
 
 // ---- host buffers: staged through library-owned device arrays, complete on return ----
 
-static int query_staging(size_t count)
+int query_staging(size_t count)
 {
     int rc;
     QueryRows &Q = g.qrows;
@@ -800,28 +800,7 @@ static int query_staging(size_t count)
     return MIRT_OK;
 }
 
-// One host-buffer entry point around its device form `call`, given the verdict of that form's argument checks and the call's
-// `count` of rays or records: nothing to do for none, then the scene, then staging room for `count`; every `in` array goes to its
-// staging array (a member of g.qrows) on the stream the call will take, every `out` array comes back on the stream it took, and
-// the host waits for that stream.
-struct HostArray { void *host; void *QueryRows::*staging; size_t bytes; bool in, out; };
-template <int N, class Call>
-static int with_host_arrays(int checked, int count, const HostArray (&a)[N], Call call)
-{
-    int rc;
-    if (checked) return checked;
-    if (count == 0) return MIRT_OK;
-    if ((rc = need_scene())) return rc;
-    if ((rc = query_staging((size_t)count))) return rc;
-    hipStream_t st = g.streams[next_si()].stream;            // the stream the query below will take
-    for (const HostArray &x : a)
-        if (x.in) HIP_TRY(hipMemcpyAsync(g.qrows.*x.staging, x.host, x.bytes, hipMemcpyHostToDevice, st));
-    if ((rc = call())) return rc;
-    for (const HostArray &x : a)
-        if (x.out) HIP_TRY(hipMemcpyAsync(x.host, g.qrows.*x.staging, x.bytes, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return MIRT_OK;
-}
+// (the host-buffer wrapper with_host_arrays: capi.hpp)
 
 int query_intersect_host(const mirt_ray *rays, int nrays, mirt_hit *hits)
 {

@@ -105,7 +105,7 @@ void CostHist::release()
 
 void QueryScratch::release()
 {
-    dev_free({ d_light_tab, d_origins, d_flags, d_stats[QUERY_DIRECT_LIGHT], d_stats[QUERY_FAN], d_stats[QUERY_OCCLUDED], d_stats[QUERY_SHADOW_MASK], d_fan_origins, d_fan_rays, d_carry,
+    dev_free({ d_light_tab, d_origins, d_flags, d_stats[QUERY_DIRECT_LIGHT], d_stats[QUERY_FAN], d_stats[QUERY_OCCLUDED], d_stats[QUERY_SHADOW_MASK], d_stats[QUERY_ALONG], d_fan_origins, d_fan_rays, d_carry,
                d_relight });
     *this = QueryScratch();
 }
@@ -157,7 +157,14 @@ void QueryRows::release()
     fan.release();
     aa_cam.release();
     for (LightCache &c : fans) c.release();
+    along.release();
     *this = QueryRows();
+}
+
+void AlongCache::release()
+{
+    dev_free({ d_off, d_rows, d_aux, d_near, d_counters, d_keys, d_vals, d_tmp_keys, d_tmp_vals, d_entries, d_bucket });
+    *this = AlongCache();
 }
 
 void LightCache::release() { dev_free({ d_light_tab, d_frames, d_off, d_rows, d_row_tri, d_origins, d_counter }); *this = LightCache(); }

@@ -201,6 +201,15 @@ struct RayTracer {
         static_assert(sizeof(vec3) == 12, "directions travel as they are");
         check(mirt_intersect_from(&start.x, n > 0 ? &dir[0].x : nullptr, n, reinterpret_cast<mirt_hit *>(closest)), "mirt_intersect_from");
     }
+    // The same for n rays that share their DIRECTION and differ in their start -- an orthographic camera, a height map, a sun's
+    // shadow map, objects dropped to the ground: closest[k] comes back as ClosestIntersection(start[k], dir, triangles, closest[k])
+    // leaves it, each ray walking its cell of a grid across `dir` where that pays (mirt_intersect_along, mirt_set_query_mode).
+    void ClosestIntersection(const vec3 *start, vec3 dir, Intersection *closest, int n)
+    {
+        upload_scene();
+        static_assert(sizeof(vec3) == 12, "starts travel as they are");
+        check(mirt_intersect_along(&dir.x, n > 0 ? &start[0].x : nullptr, n, reinterpret_cast<mirt_hit *>(closest)), "mirt_intersect_along");
+    }
     // The same for n rays from `nstarts` shared starts -- a grid of probes, the shadow maps of all point lights: closest[k] comes back
     // as ClosestIntersection(starts[start_of[k]], dir[k], triangles, closest[k]) leaves it; up to MIRT_MAX_LIGHTS starts share one
     // cube and one build (mirt_intersect_fans, mirt_set_query_mode).  start_of may be null for a single start.
@@ -230,6 +239,13 @@ struct RayTracer {
         static_assert(sizeof(vec3) == 12, "starts and directions travel as they are");
         check(mirt_occluded_fans(nstarts > 0 ? &starts[0].x : nullptr, nstarts, start_of, n > 0 ? &dir[0].x : nullptr, n, max_distance, occluded),
               "mirt_occluded_fans");
+    }
+    // ... and for n rays along one direction, through the grid of ClosestIntersection(start, dir, ...) above (mirt_occluded_along).
+    void Occluded(const vec3 *start, vec3 dir, const float *max_distance, uint8_t *occluded, int n)
+    {
+        upload_scene();
+        static_assert(sizeof(vec3) == 12, "starts travel as they are");
+        check(mirt_occluded_along(&dir.x, n > 0 ? &start[0].x : nullptr, n, max_distance, occluded), "mirt_occluded_along");
     }
     // DirectLight(i) (:265-327) for n records, with the lights and the soft-shadow toggle as they stand: result[k] = DirectLight(i[k]).
     void DirectLight(const Intersection *i, vec3 *result, int n)

@@ -31,6 +31,7 @@ EXPORTS = (
     "mirt_intersect_from", "mirt_intersect_from_device", "mirt_get_fan_stats",
     "mirt_intersect_fans", "mirt_intersect_fans_device",
     "mirt_occluded", "mirt_occluded_device", "mirt_occluded_fans", "mirt_occluded_fans_device", "mirt_get_occlusion_stats",
+    "mirt_intersect_along", "mirt_intersect_along_device", "mirt_occluded_along", "mirt_occluded_along_device", "mirt_get_along_stats",
     "mirt_shadow_mask", "mirt_shadow_mask_device", "mirt_direct_light_masked", "mirt_direct_light_masked_device", "mirt_get_shadow_mask_stats",
     "mirt_scene_upload_device", "mirt_scene_update_device", "mirt_scene_update", "mirt_scene_transform", "mirt_transform",
     "mirt_scene_download", "mirt_scene_info",
@@ -168,6 +169,11 @@ def load():
     lib.mirt_occluded_fans.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]
     lib.mirt_occluded_fans_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]
     lib.mirt_get_occlusion_stats.argtypes = [C.POINTER(QueryStats)]
+    lib.mirt_intersect_along.argtypes = [_vp, _vp, C.c_int, _vp]
+    lib.mirt_intersect_along_device.argtypes = [_vp, _vp, C.c_int, _vp]
+    lib.mirt_occluded_along.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
+    lib.mirt_occluded_along_device.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
+    lib.mirt_get_along_stats.argtypes = [C.POINTER(QueryStats)]
     lib.mirt_shadow_mask.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp]
     lib.mirt_shadow_mask_device.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp]
     lib.mirt_direct_light_masked.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp]
@@ -788,6 +794,55 @@ def occlusion_stats():
     intersect_fans), cube_bins, shells and -- profiling on, binned -- shadow_rays = rays, candidates = rows stepped over, tests =
     rows not beyond the limit, fallback_records = rays that swept their origin's table."""
     return _read_query_stats(load().mirt_get_occlusion_stats)
+
+
+# ---- ray queries along one direction ------------------------------------------------------------------------
+
+def _as_along(direction, origins):
+    """The shared direction (3 floats) and the starts (n, 3) as the library takes them."""
+    return np.ascontiguousarray(direction, np.float32).reshape(3), np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+
+
+def intersect_along(direction, origins, hits=None):
+    """ClosestIntersection(origins[i], direction) for every start (mirt_intersect_along): what intersect() returns for the rays
+    {origins[i], direction}, bit for bit, each ray walking its cell of a grid across the direction where that pays
+    (set_query_mode).  direction: 3 floats, used as given; origins: (n, 3) floats; hits: the in/out records (HIT_DTYPE; fresh ones
+    when None).  Returns a new array."""
+    direction, origins = _as_along(direction, origins)
+    hits = fresh_hits(len(origins)) if hits is None else np.ascontiguousarray(hits, HIT_DTYPE).copy()
+    if len(hits) != len(origins):
+        raise ValueError("%d origins but %d hit records" % (len(origins), len(hits)))
+    _check(load().mirt_intersect_along(_ptr(direction), _ptr(origins), len(origins), _ptr(hits)))
+    return hits
+
+
+def intersect_along_device(direction, d_origins, nrays, d_hits):
+    """The same on device arrays (raw pointers; the direction is host data), queued like a *_device frame; mirt.sync() completes it."""
+    direction = np.ascontiguousarray(direction, np.float32).reshape(3)
+    _check(load().mirt_intersect_along_device(_ptr(direction), d_origins, int(nrays), d_hits))
+
+
+def occluded_along(direction, origins, max_distance=None, out=None):
+    """occluded() for the rays {origins[i], direction}, byte for byte, through the grid of intersect_along (mirt_occluded_along).
+    max_distance: n floats, one for all, or None for +inf.  Returns uint8 (`out` when given: every byte is written)."""
+    direction, origins = _as_along(direction, origins)
+    lim = _as_limits(max_distance, len(origins), "origins")
+    out = _occluded_out(out, len(origins), "origins")
+    _check(load().mirt_occluded_along(_ptr(direction), _ptr(origins), len(origins), None if lim is None else _ptr(lim), _ptr(out)))
+    return out
+
+
+def occluded_along_device(direction, d_origins, nrays, d_max_distance, d_occluded):
+    """The same on device arrays (raw pointers; the direction is host data, d_max_distance may be None), queued like a *_device frame."""
+    direction = np.ascontiguousarray(direction, np.float32).reshape(3)
+    _check(load().mirt_occluded_along_device(_ptr(direction), d_origins, int(nrays), d_max_distance, d_occluded))
+
+
+def along_stats():
+    """The last intersect_along* / occluded_along* call (mirt_get_along_stats), in mirt_query_stats' fields: mode_used, cube_source
+    (0 no grid, 1 built by the call, 2 kept), cube_bins = cells per grid side, shells and -- profiling on, binned -- shadow_rays =
+    rays, candidates = rows offered, tests = rows tested, fallback_records = rays that swept the scene."""
+    return _read_query_stats(load().mirt_get_along_stats)
 
 
 # ---- shadow masks: DirectLight's shadow decisions, and DirectLight from them ---------------------------------

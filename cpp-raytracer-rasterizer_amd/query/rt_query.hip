@@ -63,54 +63,9 @@ __global__ __launch_bounds__(256) void k_query_rows(const float *__restrict__ tr
     }
 }
 
-// Whether the rows of the scene are inside the filter's range for every start below MIRT_QUERY_START_MAX (header comment);
-// wave-uniform: four scalar loads and a handful of scalar-unit operations.
-__device__ __forceinline__ bool scene_rows_in_range(const QueryFrame &q)
-{
-    const float V = __uint_as_float(q.scene_max[QMAX_V0]), E1 = __uint_as_float(q.scene_max[QMAX_E1]),
-                E2 = __uint_as_float(q.scene_max[QMAX_E2]), X = __uint_as_float(q.scene_max[QMAX_E1E2]);
-    const float B = MIRT_QUERY_START_MAX + V;
-    // (comparisons are false for NaN: a NaN anywhere in the scene sends every ray down the exact path)
-    return q.scene_finite && 2.0f * B * E1 < MIRT_SAFE_MAG && 2.0f * B * E2 < MIRT_SAFE_MAG && X < MIRT_SAFE_MAG;
-}
-
-// A ray whose operands are not provably inside the filter's range: it takes the exact path for every triangle.
-__device__ __forceinline__ bool ray_exact_only(bool scene_ok, v3 start, v3 dir)
-{
-    const bool in_range = fabsf(start.x) < MIRT_QUERY_START_MAX && fabsf(start.y) < MIRT_QUERY_START_MAX && fabsf(start.z) < MIRT_QUERY_START_MAX &&
-                          dir_in_filter_range(dir);
-    return !(scene_ok && in_range);
-}
-
 // Ray p of the P that lane t of block b owns: (b * P + p) * 256 + t; its incoming distance -- a lane without a ray carries a record
 // nothing can replace --; and the write-back: a record nothing replaced is not written at all.
 template <int P> __device__ __forceinline__ long long lane_ray(int p) { return ((long long)blockIdx.x * P + p) * 256 + threadIdx.x; }
-__device__ __forceinline__ float incoming_distance(const uint32_t *hits, long long ray, bool ok)
-{
-    return ok ? __uint_as_float(hits[(size_t)HIT_WORDS * ray + 3]) : -1.0f;
-}
-
-struct RowVecs { v3 v0, e1, e2, e1e2; };
-__device__ __forceinline__ RowVecs unpack_row(const float4 &a, const float4 &b, const float4 &c)
-{
-    RowVecs r;
-    r.v0 = V3(a.x, a.y, a.z); r.e1 = V3(a.w, b.x, b.y); r.e2 = V3(b.z, b.w, c.x); r.e1e2 = V3(c.y, c.z, c.w);
-    return r;
-}
-
-// One ray against one row: b, be2, e1b, e1e2b (:218, :226-227, :231), then the three dots against negD (:232-234).
-__device__ __forceinline__ TestDots ray_dots(const RowVecs &r, v3 start, v3 nd, float *e1e2b)
-{
-    const v3 b = sub3(start, r.v0);
-    const v3 be2 = cross3(b, r.e2), e1b = cross3(r.e1, b);
-    *e1e2b = r.e1e2.x * b.x + r.e1e2.y * b.y + r.e1e2.z * b.z;
-    TestDots d;
-    d.den = r.e1e2.x * nd.x + r.e1e2.y * nd.y + r.e1e2.z * nd.z;
-    d.pu = be2.x * nd.x + be2.y * nd.y + be2.z * nd.z;
-    d.qv = e1b.x * nd.x + e1b.y * nd.y + e1b.z * nd.z;
-    return d;
-}
-
 // glm::cross for two rays per lane: x.y * y.z - y.y * x.z, ... (mirt_math.hpp: cross3), every operation packed.
 __device__ __forceinline__ v3p cross3p(const v3p &x, const v3p &y)
 {
@@ -134,19 +89,6 @@ __device__ __forceinline__ TestDots2 ray_dots2(const RowVecs &r, const v3p &star
     d.pu = be2.x * nd.x + be2.y * nd.y + be2.z * nd.z;
     d.qv = e1b.x * nd.x + e1b.y * nd.y + e1b.z * nd.z;
     return d;
-}
-
-// The accept test, hit point and distance as the reference computes them (:237-242), from the row alone.
-__device__ __forceinline__ bool exact_hit_row(const TestDots &d, float e1e2b, const RowVecs &r, v3 start, v3 *pos, float *dist)
-{
-    const float t = e1e2b / d.den, u = d.pu / d.den, v = d.qv / d.den;
-    if (u + v <= 1.0f && u >= 0.0f && v >= 0.0f && t >= 0.0f) {
-        const v3 p = add3(add3(r.v0, scale3(r.e1, u)), scale3(r.e2, v));
-        *pos = p;
-        *dist = distance3(start, p);
-        return true;
-    }
-    return false;
 }
 
 // ---- what the lane-per-ray sweeps (k_query_closest, k_query_occluded) share: a lane's P rays, one row against them ------------
@@ -350,10 +292,6 @@ __device__ __forceinline__ void carry_store(const QueryLightFrame &q, long long 
     c[3 * n] = result2.x; c[4 * n] = result2.y; c[5 * n] = result2.z;
 }
 
-// (defined with the walk kernels below)
-__device__ __forceinline__ void flush_query_stats(unsigned long long *stats, unsigned long long rays, unsigned long long cand,
-                                                  unsigned long long tests, unsigned long long fallback);
-
 // The position of record `rec` alone (record 0 for a lane without one): what a shadow decision depends on.  The index is not read.
 __device__ __forceinline__ v3 record_position(const QueryLightFrame &q, long long rec, bool ok)
 {
@@ -505,24 +443,6 @@ template __global__ void k_query_direct_light<QUERY_P, false, true, true>(const 
 // wave's walk, as brute_l does in k_rt_trace2 and with the loop body of k_query_direct_light, the per-ray exact-only override
 // included -- it can only be set on such a lane: a formed rDir is below 1.5 per component, far inside MIRT_QUERY_DIR_MAX.  The
 // scene's and the lights' range is the host's to check (query.cpp): outside it the call takes k_query_direct_light.
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-// The QSTAT_WORDS counters of a STATS kernel: summed over the wave, one atomic per wave and non-zero word.
-__device__ __forceinline__ void flush_query_stats(unsigned long long *stats, unsigned long long rays, unsigned long long cand,
-                                                  unsigned long long tests, unsigned long long fallback)
-{
-    const unsigned long long sums[QSTAT_WORDS] = { wave_sum64(rays), wave_sum64(cand), wave_sum64(tests), wave_sum64(fallback) };
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int w = 0; w < QSTAT_WORDS; w++)
-            if (sums[w]) atomicAdd(stats + w, sums[w]);
-}
-
 // The any-hit sweep of the lanes a cube's bins do not cover (`swept`; rare), called by the whole wave after its walk: the full
 // origin table `tab` of the lane's start point S in index order, k_query_direct_light's loop body -- the filter with the per-ray
 // exact-only override in front of exact_hit -- and a lane live until its first accepted dist < thr (:313-314); the wave leaves when
@@ -916,11 +836,6 @@ __global__ __launch_bounds__(256) void k_query_fans_expand(const QueryFansExpand
 // fresh record nor passes `<`.  Any-hit is exact (SURVEY A-5): which occluder settles a ray does not show in the byte, so a ray
 // stops at its first one, in whatever order it meets the rows.  A limit nothing is below -- NaN, 0, negative -- settles its ray
 // before any row is read (`L > 0` is false for NaN); a missing limit array stands for +inf.
-__device__ __forceinline__ float occlusion_limit(const float *limit, long long ray, bool ok)
-{
-    return !ok ? -1.0f : (limit ? limit[ray] : __uint_as_float(0x7f800000u));
-}
-
 // k_query_occluded: k_query_closest's sweep -- a lane per P rays (load_lane_ray), QueryRow chunks of RT_CHUNK_ROWS through LDS, the
 // row test with the filter in front of the exact divisions (test_row) -- with a ray open until its first accepted dist < L.  A wave none of whose
 // rays is open leaves the rows of a chunk alone (in steps of 64 rows: nothing in there waits for another wave), but goes on taking

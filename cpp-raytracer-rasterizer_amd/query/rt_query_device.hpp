@@ -68,4 +68,90 @@ __device__ __forceinline__ uint32_t fan_list(const CubeView &cv, uint32_t k, uin
     return key;
 }
 
+// ---- the row test of the caller's own rays, shared by rt_query.hip and ../along/along.hip ------------------------------------------
+
+// Whether the rows of the scene are inside the filter's range for every start below MIRT_QUERY_START_MAX (rt_query.hip's header
+// comment); wave-uniform: four scalar loads and a handful of scalar-unit operations.
+__device__ __forceinline__ bool scene_rows_in_range(const QueryFrame &q)
+{
+    const float V = __uint_as_float(q.scene_max[QMAX_V0]), E1 = __uint_as_float(q.scene_max[QMAX_E1]),
+                E2 = __uint_as_float(q.scene_max[QMAX_E2]), X = __uint_as_float(q.scene_max[QMAX_E1E2]);
+    const float B = MIRT_QUERY_START_MAX + V;
+    // (comparisons are false for NaN: a NaN anywhere in the scene sends every ray down the exact path)
+    return q.scene_finite && 2.0f * B * E1 < MIRT_SAFE_MAG && 2.0f * B * E2 < MIRT_SAFE_MAG && X < MIRT_SAFE_MAG;
+}
+
+// A ray whose operands are not provably inside the filter's range: it takes the exact path for every triangle.
+__device__ __forceinline__ bool ray_exact_only(bool scene_ok, v3 start, v3 dir)
+{
+    const bool in_range = fabsf(start.x) < MIRT_QUERY_START_MAX && fabsf(start.y) < MIRT_QUERY_START_MAX && fabsf(start.z) < MIRT_QUERY_START_MAX &&
+                          dir_in_filter_range(dir);
+    return !(scene_ok && in_range);
+}
+
+// The incoming distance of ray `ray` -- a lane without a ray carries a record nothing can replace.
+__device__ __forceinline__ float incoming_distance(const uint32_t *hits, long long ray, bool ok)
+{
+    return ok ? __uint_as_float(hits[(size_t)HIT_WORDS * ray + 3]) : -1.0f;
+}
+
+// The limit of an occlusion ray: a lane without a ray carries one nothing is below; a missing limit array stands for +inf.
+__device__ __forceinline__ float occlusion_limit(const float *limit, long long ray, bool ok)
+{
+    return !ok ? -1.0f : (limit ? limit[ray] : __uint_as_float(0x7f800000u));
+}
+
+struct RowVecs { v3 v0, e1, e2, e1e2; };
+__device__ __forceinline__ RowVecs unpack_row(const float4 &a, const float4 &b, const float4 &c)
+{
+    RowVecs r;
+    r.v0 = V3(a.x, a.y, a.z); r.e1 = V3(a.w, b.x, b.y); r.e2 = V3(b.z, b.w, c.x); r.e1e2 = V3(c.y, c.z, c.w);
+    return r;
+}
+
+// One ray against one row: b, be2, e1b, e1e2b (:218, :226-227, :231), then the three dots against negD (:232-234).
+__device__ __forceinline__ TestDots ray_dots(const RowVecs &r, v3 start, v3 nd, float *e1e2b)
+{
+    const v3 b = sub3(start, r.v0);
+    const v3 be2 = cross3(b, r.e2), e1b = cross3(r.e1, b);
+    *e1e2b = r.e1e2.x * b.x + r.e1e2.y * b.y + r.e1e2.z * b.z;
+    TestDots d;
+    d.den = r.e1e2.x * nd.x + r.e1e2.y * nd.y + r.e1e2.z * nd.z;
+    d.pu = be2.x * nd.x + be2.y * nd.y + be2.z * nd.z;
+    d.qv = e1b.x * nd.x + e1b.y * nd.y + e1b.z * nd.z;
+    return d;
+}
+
+// The accept test, hit point and distance as the reference computes them (:237-242), from the row alone.
+__device__ __forceinline__ bool exact_hit_row(const TestDots &d, float e1e2b, const RowVecs &r, v3 start, v3 *pos, float *dist)
+{
+    const float t = e1e2b / d.den, u = d.pu / d.den, v = d.qv / d.den;
+    if (u + v <= 1.0f && u >= 0.0f && v >= 0.0f && t >= 0.0f) {
+        const v3 p = add3(add3(r.v0, scale3(r.e1, u)), scale3(r.e2, v));
+        *pos = p;
+        *dist = distance3(start, p);
+        return true;
+    }
+    return false;
+}
+
+// ---- the counters of a STATS kernel ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// The QSTAT_WORDS counters of a STATS kernel: summed over the wave, one atomic per wave and non-zero word.
+__device__ __forceinline__ void flush_query_stats(unsigned long long *stats, unsigned long long rays, unsigned long long cand,
+                                                  unsigned long long tests, unsigned long long fallback)
+{
+    const unsigned long long sums[QSTAT_WORDS] = { wave_sum64(rays), wave_sum64(cand), wave_sum64(tests), wave_sum64(fallback) };
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int w = 0; w < QSTAT_WORDS; w++)
+            if (sums[w]) atomicAdd(stats + w, sums[w]);
+}
+
 }  // namespace mirt

@@ -550,6 +550,45 @@ MIRT_API int mirt_occluded_fans_device(const float *origins3, int norigins, cons
  * the ray's limit, fallback_records = rays that swept their origin's table.  Waits for the stream of that call. */
 MIRT_API int mirt_get_occlusion_stats(mirt_query_stats *out);
 
+/* ---- ray queries along ONE direction: binned closest hits and occlusion (additions to ABI 4) ---- */
+
+/* ClosestIntersection(origins[i], dir, triangles, hits[i]) for i in [0, nrays): exactly mirt_intersect on the rays { origins3[3 * i ..],
+ * dir }, bit for bit, for every ray and every incoming record -- and mirt_occluded on the same rays, byte for byte.  Rays that share
+ * their DIRECTION and differ in their start: an orthographic camera, a height or depth map, a directional (sun) shadow or exposure
+ * map, many objects dropped to the ground, a parallel-beam scan.  For such a family the dot products of the test are affine in the
+ * projection of the start onto a plane across dir, so a grid of B x B cells over the projection of the SCENE's bounding box holds
+ * every start: each ray tests only the rows of its cell, front to back in depth shells along dir, and stops where nothing closer
+ * than its record (or its limit) can follow.  The grid does not depend on the call's origins: no pass over them, no read-back for
+ * them, and a repeated call with the same scene and direction builds nothing.
+ * dir: a HOST array of three floats in both forms, used as given and not normalised.  origins3: nrays x 3 floats.  hits: the in/out
+ * records of mirt_intersect, with its rules (ties to the later index, an incoming record loses every tie, a negative or NaN incoming
+ * distance is never replaced, +inf by any hit, a record nothing replaced is left unwritten).  occluded / max_distance: as
+ * mirt_occluded -- every byte [0, nrays) is written, a NULL limit array means +inf.  nrays == 0 does nothing.  Checks, in this order:
+ * MIRT_ERR_INVALID_ARGUMENT for nrays < 0, a NULL origins or output array or a NULL dir with a positive count (the arguments
+ * first: a malformed call is told so with or without a device); MIRT_ERR_NOT_INITIALISED; MIRT_ERR_NO_SCENE.  The host forms are complete on return; the _device forms are queued like mirt_intersect_device.  Neither
+ * touches mirt_get_stats, mirt_get_query_stats, mirt_get_fan_stats or mirt_get_occlusion_stats.
+ * mirt_set_query_mode: BRUTE writes the rays out on the device and takes mirt_intersect_device's / mirt_occluded_device's kernels;
+ * BINNED builds the grid of (scene, dir) when it is not held -- one is kept, shared by the streams, forgotten with the scene --;
+ * AUTO is the many-origin fans' rule, which this call's own sweep arrived at (profiles/ray_query_bench.txt, section `along`): more
+ * than MIRT_QUERY_WAVE_RAYS (4096) rays and 2000 triangles or more (or MIRT_BIN_THRESHOLD triangles or more and nrays x triangles >=
+ * 4e7), or the grid of this direction is held -- with its build the call was behind the brute path in every measured cell of at most
+ * 4096 rays and ahead in every one from 16 384 rays on.  Under every mode the whole call takes the brute-force kernels
+ * when the scene is not finite (a coordinate not below 1e8), when dir has a component that is not finite or its largest lies
+ * outside [2^-32, 2^19), when a float cannot tell the grid's cells apart (a scene far thinner than it is far from the origin), or
+ * when more than an eighth of the scene (and more than 64 triangles) is edge-on to dir or otherwise unfit for a cell -- those go on
+ * one list every ray tests; mode_used then says BRUTE.  Per ray, a start that is not finite, or has a component beyond eight times
+ * the scene's largest |coordinate| or not below 1e8, sweeps every row of the scene; a start whose projection falls outside the
+ * grid tests the every-ray list alone. */
+MIRT_API int mirt_intersect_along(const float dir[3], const float *origins3, int nrays, mirt_hit *hits);
+MIRT_API int mirt_intersect_along_device(const float dir[3], const void *d_origins3, int nrays, void *d_hits);
+MIRT_API int mirt_occluded_along(const float dir[3], const float *origins3, int nrays, const float *max_distance, uint8_t *occluded);
+MIRT_API int mirt_occluded_along_device(const float dir[3], const void *d_origins3, int nrays, const void *d_max_distance, void *d_occluded);
+/* The last call of either kind, in mirt_query_stats' fields: mode_used; cube_source 0 no grid, 1 built by this call, 2 kept;
+ * cube_bins = cells per grid side; shells; and, with profiling on and a binned call, shadow_rays = rays of the call, candidates =
+ * rows offered to them, tests = those of them not beyond the ray's record or limit, fallback_records = rays that swept the scene.
+ * Waits for the stream of that call. */
+MIRT_API int mirt_get_along_stats(mirt_query_stats *out);
+
 /* ---- shadow masks: DirectLight's shadow decision per (record, light position), and DirectLight from a mask (additions to ABI 4) ---- */
 
 /* The one value DirectLight computes and throws away (raytracer.cpp:306-315): whether the shadow ray of a record towards a light

@@ -1,0 +1,185 @@
+// The binning predicate of the ray queries along one direction (along/along.hpp: along_make_desc, along_tri_setup,
+// along_cell_may_hit, along_cell_of, along_depth_of) against the exact test, on the CPU (built with -ffp-contract=off like the
+// library).  For seeded (triangle, direction, start) triples: whenever the reference's float test (raytracer.cpp:216-242, written out
+// below) accepts and the start may take its cell, the triangle is either on the every-ray list, or it is filed in the start's cell
+// and in a shell the walk reaches -- its depth bound is not beyond the start's depth plus the accepted distance, and its shell is
+// no later than that sum's.
+// The triples: soup-like triangles and needles down to 1:100 000; triangles exactly edge-on to the direction and within 2^-24 ..
+// 2^-8 rad of it; hit points inside, on and within 2^-20 of edges and vertices, and on and within 2^-20 of cell borders; starts
+// behind, inside and beyond the scene and at the |S| bound (and beyond it: those take no cell); axis-aligned and oblique
+// directions of magnitude 2^-30, 1 and 2^18.
+// With a file of triangles (argv[1]: n x 15 floats) and a direction (argv[2..4]) it also reports how the scene is filed: the
+// every-ray list's length and the mean number of rows a cell offers, both as shares of n.
+#include "../../cpp-raytracer-rasterizer_amd/along/along.hpp"
+
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+using namespace mirt;
+
+static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
+static uint64_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return rng_state; }
+static double uni(double a, double b) { return a + (b - a) * (double)(rnd() >> 11) / 9007199254740992.0; }
+
+// ClosestIntersection's test for one triangle (:216-242), operation for operation
+static bool ref_accept(v3 v0, v3 v1, v3 v2, v3 S, v3 dir, float *dist)
+{
+    const v3 e1 = sub3(v1, v0), e2 = sub3(v2, v0), b = sub3(S, v0);
+    const v3 e1e2 = cross3(e1, e2), be2 = cross3(b, e2), e1b = cross3(e1, b);
+    const v3 nd = neg3(dir);
+    const float e1e2b = e1e2.x * b.x + e1e2.y * b.y + e1e2.z * b.z;
+    const float den = e1e2.x * nd.x + e1e2.y * nd.y + e1e2.z * nd.z;
+    const float pu = be2.x * nd.x + be2.y * nd.y + be2.z * nd.z;
+    const float qv = e1b.x * nd.x + e1b.y * nd.y + e1b.z * nd.z;
+    const float t = e1e2b / den, u = pu / den, v = qv / den;
+    if (u + v <= 1.0f && u >= 0.0f && v >= 0.0f && t >= 0.0f) {
+        const v3 p = add3(add3(v0, scale3(e1, u)), scale3(e2, v));
+        *dist = distance3(S, p);
+        return true;
+    }
+    return false;
+}
+
+struct Tally { long triples = 0, accepted = 0, every = 0, cells = 0, out_of_reach = 0, failures = 0; };
+
+static void check_triple(v3 v0, v3 v1, v3 v2, v3 S, v3 dir, int B, Tally &T, const char *what)
+{
+    T.triples++;
+    float dist = 0.0f;
+    if (!ref_accept(v0, v1, v2, S, dir, &dist)) return;
+    T.accepted++;
+    float lo[3] = { -1, -1, -1 }, hi[3] = { 1, 1, 1 };
+    const v3 vs[3] = { v0, v1, v2 };
+    for (const v3 &p : vs) {
+        lo[0] = fminf(lo[0], p.x); lo[1] = fminf(lo[1], p.y); lo[2] = fminf(lo[2], p.z);
+        hi[0] = fmaxf(hi[0], p.x); hi[1] = fmaxf(hi[1], p.y); hi[2] = fmaxf(hi[2], p.z);
+    }
+    AlongDesc a;
+    const float d3[3] = { dir.x, dir.y, dir.z };
+    if (!along_make_desc(d3, lo, hi, B, ALONG_SHELLS, &a)) { printf("FAIL %s: no descriptor\n", what); T.failures++; return; }
+    if (!along_start_in_reach(a, S)) { T.out_of_reach++; return; }
+    const v3 e1 = sub3(v1, v0), e2 = sub3(v2, v0);
+    const AlongTri t = along_tri_setup(a, v0, e1, e2, cross3(e1, e2));
+    if (t.kind == ALONG_EVERY) { T.every++; return; }
+    T.cells++;
+    const int cell = along_cell_of(a, S);
+    const int ci = cell % a.B, cj = cell / a.B;
+    const float thr = along_depth_of(a, S) + dist;
+    const bool in_box = cell >= 0 && ci >= t.i0 && ci <= t.i1 && cj >= t.j0 && cj <= t.j1;
+    const bool filed = in_box && along_cell_may_hit(a, t, ci, cj);
+    const bool reached = !(t.near > thr) && bin_shell_of(t.near, a.shell_d0, a.shell_iw, a.shells) <= bin_shell_of(thr, a.shell_d0, a.shell_iw, a.shells);
+    if (!filed || !reached) {
+        T.failures++;
+        if (T.failures < 20)
+            printf("FAIL %s: cell %d (box %d..%d x %d..%d) filed %d reached %d near %g thr %g | v0 %g %g %g S %g %g %g dir %g %g %g\n", what, cell, t.i0, t.i1,
+                   t.j0, t.j1, (int)filed, (int)reached, t.near, thr, v0.x, v0.y, v0.z, S.x, S.y, S.z, dir.x, dir.y, dir.z);
+    }
+}
+
+static v3 f3(double x, double y, double z) { return V3((float)x, (float)y, (float)z); }
+static void cross_d(const double *a, const double *b, double *c) { c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0]; }
+static void unit_d(double *a) { const double l = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); for (int c = 0; c < 3; c++) a[c] /= l; }
+
+int main(int argc, char **argv)
+{
+    if (argc >= 5) {
+        // how a scene is filed under a direction
+        FILE *fp = fopen(argv[1], "rb");
+        if (!fp) return 2;
+        std::vector<float> tris;
+        float row[15];
+        while (fread(row, sizeof row, 1, fp) == 1) tris.insert(tris.end(), row, row + 15);
+        fclose(fp);
+        const int n = (int)(tris.size() / 15);
+        const float dir[3] = { (float)atof(argv[2]), (float)atof(argv[3]), (float)atof(argv[4]) };
+        float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+        for (size_t i = 0; i < tris.size(); i++)
+            if (i % 15 < 9) { lo[i % 3] = fminf(lo[i % 3], tris[i]); hi[i % 3] = fmaxf(hi[i % 3], tris[i]); }
+        AlongDesc a;
+        if (!along_make_desc(dir, lo, hi, along_bins_for(n), ALONG_SHELLS, &a)) { printf("no descriptor\n"); return 1; }
+        long every = 0, pairs = 0;
+        for (int i = 0; i < n; i++) {
+            const float *t15 = &tris[(size_t)15 * i];
+            const v3 v0 = ld3(t15), e1 = sub3(ld3(t15 + 3), v0), e2 = sub3(ld3(t15 + 6), v0);
+            const AlongTri t = along_tri_setup(a, v0, e1, e2, cross3(e1, e2));
+            if (t.kind == ALONG_EVERY) { every++; continue; }
+            for (int cj = t.j0; cj <= t.j1; cj++)
+                for (int ci = t.i0; ci <= t.i1; ci++) pairs += along_cell_may_hit(a, t, ci, cj) ? 1 : 0;
+        }
+        // a ray is offered its cell's rows and the every-ray list: the mean over the grid's cells, as a share of n
+        const double offered = ((double)pairs / ((double)a.B * a.B) + (double)every) / (double)n;
+        printf("n %d B %d every %ld every_share %.6f offered_share %.6f\nok\n", n, a.B, every, (double)every / n, offered);
+        return 0;
+    }
+
+    Tally T;
+    const double mags[3] = { ldexp(1.0, -30), 1.0, ldexp(1.0, 18) };
+    const double dirs[7][3] = { { 0, 0, 1 }, { 0, -1, 0 }, { 1, 0, 0 }, { 1, 1, 0 }, { 1, -1, 1 }, { 0.37, -0.52, 0.81 }, { -0.9, 0.05, 0.3 } };
+    const double needle[5] = { 1.0, 1e-2, 1e-3, 1e-4, 1e-5 };
+    const double uv[9][2] = { { 0.3, 0.3 }, { 0, 0.4 }, { 0.4, 0 }, { 0.5, 0.5 }, { 0, 0 }, { 1, 0 }, { 0, 1 }, { 0.999, 0.0005 }, { 0.25, 0.75 } };
+    const int Bs[3] = { 8, 32, 256 };
+    for (int iter = 0; iter < 40000; iter++) {
+        const int di = iter % 7, mi = (iter / 7) % 3, B = Bs[(iter / 21) % 3];
+        double dh[3] = { dirs[di][0], dirs[di][1], dirs[di][2] };
+        unit_d(dh);
+        const v3 dir = f3(dirs[di][0] * mags[mi], dirs[di][1] * mags[mi], dirs[di][2] * mags[mi]);
+        // the hit point P: anywhere in the scene's box, or (every third) on or within 2^-20 of a cell border of the unit box's grid
+        double P[3] = { uni(-0.9, 0.9), uni(-0.9, 0.9), uni(-0.9, 0.9) };
+        if (iter % 3 == 0) {
+            float lo[3] = { -1, -1, -1 }, hi[3] = { 1, 1, 1 };
+            AlongDesc a;
+            const float d3[3] = { dir.x, dir.y, dir.z };
+            if (!along_make_desc(d3, lo, hi, B, ALONG_SHELLS, &a)) { printf("FAIL: no descriptor for the unit box\n"); return 1; }
+            const int border = 1 + (int)(rnd() % (unsigned)(B - 1));
+            const double off = (double)((int)(rnd() % 5) - 2) * ldexp(1.0, -20) / (double)a.ip;
+            const double p = (double)a.p0 + border / (double)a.ip + off;
+            P[a.k1] = p + (double)a.c1 * P[a.k];                    // p(P) = P[k1] - c1 P[k]
+        }
+        // the triangle around P: e1 anywhere, e2 across it (a needle when squeezed) or in the plane of e1 and dir (edge-on), tilted
+        double e1[3] = { uni(-0.3, 0.3), uni(-0.3, 0.3), uni(-0.3, 0.3) }, e2[3];
+        const int shape = (iter / 63) % 8;
+        if (shape < 5) {
+            double r[3] = { uni(-1, 1), uni(-1, 1), uni(-1, 1) }, w[3];
+            cross_d(e1, r, w);
+            unit_d(w);
+            const double l1 = sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]), k = uni(0.2, 0.9);
+            for (int c = 0; c < 3; c++) e2[c] = k * e1[c] + w[c] * l1 * needle[shape];
+        } else {
+            double nperp[3];
+            cross_d(e1, dh, nperp);
+            unit_d(nperp);
+            const double theta = shape == 5 ? 0.0 : ldexp(1.0, -(int)(8 + rnd() % 17)) * (shape == 6 ? 1.0 : -1.0);
+            const double a1 = uni(-0.5, 0.5), bd = uni(0.1, 0.3);
+            for (int c = 0; c < 3; c++) e2[c] = a1 * e1[c] + bd * dh[c] + theta * bd * nperp[c];
+        }
+        for (int ui = 0; ui < 9; ui++) {
+            const double eps = (double)((int)(rnd() % 3) - 1) * ldexp(1.0, -20);
+            const double u = uv[ui][0] + eps, v = uv[ui][1] + (ui & 1 ? eps : -eps);
+            double v0[3];
+            for (int c = 0; c < 3; c++) v0[c] = P[c] - u * e1[c] - v * e2[c];
+            const v3 V0 = f3(v0[0], v0[1], v0[2]), V1 = f3(v0[0] + e1[0], v0[1] + e1[1], v0[2] + e1[2]), V2 = f3(v0[0] + e2[0], v0[1] + e2[1], v0[2] + e2[2]);
+            // starts along -dir from P: beyond the hit (negative), at it, just in front, inside the scene, outside, at the |S| bound, past it
+            const double depth[8] = { -0.5, 0.0, ldexp(1.0, -18), 0.4, 2.5, 6.0, 0.0, 30.0 };
+            for (int si = 0; si < 8; si++) {
+                double S[3];
+                for (int c = 0; c < 3; c++) S[c] = P[c] - dh[c] * depth[si];
+                if (si == 6) {                                     // at the bound: slide along dir until the largest |component| is smax (the box is the unit box unless the triangle sticks out)
+                    double m = 0.0;
+                    int cm = 0;
+                    for (int c = 0; c < 3; c++) if (fabs(dh[c]) > m) { m = fabs(dh[c]); cm = c; }
+                    const double s = (dh[cm] > 0 ? -1.0 : 1.0) * 8.0, step = (s - P[cm]) / dh[cm];
+                    for (int c = 0; c < 3; c++) S[c] = P[c] + dh[c] * step;
+                }
+                check_triple(V0, V1, V2, f3(S[0], S[1], S[2]), dir, B, T, "triple");
+            }
+        }
+    }
+    printf("triples %ld accepted %ld filed in cells %ld on the every-ray list %ld out of reach %ld failures %ld\n", T.triples, T.accepted, T.cells, T.every,
+           T.out_of_reach, T.failures);
+    // the test must not pass vacuously: each class has to occur
+    if (T.accepted < 100000 || T.cells < 50000 || T.every < 1000 || T.out_of_reach < 100) { printf("FAIL: too few cases\n"); return 1; }
+    if (T.failures) return 1;
+    printf("ok\n");
+    return 0;
+}

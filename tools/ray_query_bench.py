@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans,occluded,mask]
+"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans,occluded,mask,along]
 
 The measurements of the ray-query kernels (query/rt_query.hip), written to one text file:
 
@@ -39,6 +39,14 @@ The measurements of the ray-query kernels (query/rt_query.hip), written to one t
                        behind mirt_direct_light_device by more than that are listed, and for the masked call its ratio to
                        mirt_direct_light_device and the bytes it must move over its time as a share of the HBM peak.  Mask + relight
                        is compared with mirt_direct_light_device's colours in every cell.
+
+  along                mirt_intersect_along_device and mirt_occluded_along_device for a square grid of starts looking down the scene
+                       (an orthographic camera above it, dir = +z): 1 .. 2^20 rays in powers of four at n = 100 000 and n = 2 000, under
+                       MIRT_QUERY_BINNED with the grid built by the call (the direction tilts by one subnormal between the calls) and
+                       with the grid held, beside mirt_intersect_device / mirt_occluded_device from fresh records on the same rays
+                       written out, in the same run.  The answers are compared first; the cells where the new call is behind are listed,
+                       and from the rows the ray count from which the call with its build stays ahead: whether AUTO's starting rule
+                       (the fans') is confirmed or moved.
 
 The knob is read once per process, so every GPU step is a child process of its own, under its own `timeout`; a step that fails
 ends the run."""
@@ -773,6 +781,131 @@ def step_occluded(p):
     occluded_summary(out, p)
 
 
+# ---- ray queries along one direction: an orthographic grid of starts looking down the scene ------------------------------------------
+
+def along_grid(k):
+    """k = side x side starts over [-1.2, 1.2]^2 at z = -1.5, row by row."""
+    side = int(round(k ** 0.5))
+    assert side * side == k
+    c = (np.arange(side, dtype=np.float64) + 0.5) / side * 2.4 - 1.2
+    s = np.empty((side, side, 3), np.float32)
+    s[:, :, 0], s[:, :, 1], s[:, :, 2] = c[None, :], c[:, None], -1.5
+    return np.ascontiguousarray(s.reshape(-1, 3))
+
+
+def child_along(n):
+    """mirt_intersect_along_device / mirt_occluded_along_device (no limits) beside mirt_intersect_device / mirt_occluded_device from
+    fresh records on the same rays: BINNED with the grid built by the call, BINNED with the grid held, and the yardsticks."""
+    import mirt
+    h = hip()
+    mirt.init(0)
+    mirt.scene_upload(mirt.scene_soup(1, n, 0.05 if n >= 50000 else 0.2))
+    top = 1 << 20
+    down = np.array([0, 0, 1], np.float32)
+    fresh = mirt.fresh_hits(top)
+    d_starts, d_rays, d_hits, d_occ = dev_alloc(h, 12 * top), dev_alloc(h, 24 * top), dev_alloc(h, fresh.nbytes, fresh), dev_alloc(h, top)
+
+    def tilted(i):
+        d = down.copy()
+        d[0] = np.float32(i) * np.finfo(np.float32).smallest_subnormal
+        return d
+
+    def run(fn, k):
+        assert h.hipMemcpy(d_hits, fresh.ctypes.data_as(C.c_void_p), 20 * k, 1) == 0
+        t0 = time.perf_counter()
+        fn(k); mirt.sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    k, nudge = 1, 0
+    while k <= top:
+        starts = along_grid(k)
+        rays = mirt.make_rays(starts, down)
+        assert h.hipMemcpy(d_starts, starts.ctypes.data_as(C.c_void_p), starts.nbytes, 1) == 0
+        assert h.hipMemcpy(d_rays, rays.ctypes.data_as(C.c_void_p), rays.nbytes, 1) == 0
+        # the answers first
+        want, got = np.zeros(k, mirt.HIT_DTYPE), np.zeros(k, mirt.HIT_DTYPE)
+        wocc, gocc = np.zeros(k, np.uint8), np.zeros(k, np.uint8)
+        run(lambda q: mirt.intersect_device(d_rays, q, d_hits), k)
+        assert h.hipMemcpy(want.ctypes.data_as(C.c_void_p), d_hits, want.nbytes, 2) == 0
+        mirt.occluded_device(d_rays, k, None, d_occ); mirt.sync()
+        assert h.hipMemcpy(wocc.ctypes.data_as(C.c_void_p), d_occ, k, 2) == 0
+        mirt.set_query_mode(mirt.QUERY_BINNED)
+        run(lambda q: mirt.intersect_along_device(down, d_starts, q, d_hits), k)
+        assert h.hipMemcpy(got.ctypes.data_as(C.c_void_p), d_hits, got.nbytes, 2) == 0
+        mirt.occluded_along_device(down, d_starts, k, None, d_occ); mirt.sync()
+        assert h.hipMemcpy(gocc.ctypes.data_as(C.c_void_p), d_occ, k, 2) == 0
+        st = mirt.along_stats()
+        assert st["mode_used"] == mirt.QUERY_BINNED, st
+        assert got.tobytes() == want.tobytes() and np.array_equal(gocc, wocc), "the calls along a direction disagree with mirt_intersect_device / mirt_occluded_device"
+        reps = 5 if k <= 65536 else 3
+        ms = {}
+        for name, yard, fn in (("intersect", lambda q: mirt.intersect_device(d_rays, q, d_hits), lambda d, q: mirt.intersect_along_device(d, d_starts, q, d_hits)),
+                               ("occluded", lambda q: mirt.occluded_device(d_rays, q, None, d_occ), lambda d, q: mirt.occluded_along_device(d, d_starts, q, None, d_occ))):
+            ms[name, "yard"] = float(np.median([run(yard, k) for _ in range(reps + 1)][1:]))
+            ts = []
+            for _ in range(reps + 1):                    # (never the key of the call before)
+                nudge += 1
+                ts.append(run(lambda q: fn(tilted(1 + nudge % 7), q), k))
+                assert mirt.along_stats()["cube_source"] == 1
+            ms[name, "built"] = float(np.median(ts[1:]))
+            ts = [run(lambda q: fn(down, q), k) for _ in range(reps + 2)]
+            assert mirt.along_stats()["cube_source"] == 2
+            ms[name, "kept"] = float(np.median(ts[2:]))
+        mirt.set_query_mode(mirt.QUERY_AUTO)
+        print("RESULT along n %6d rays %8d B %3d hit %.3f  " % (n, k, st["cube_bins"], float((want["index"] >= 0).mean()))
+              + "  ".join("%s %s" % (name, " ".join("%10.4f" % ms[name, m] for m in ("yard", "built", "kept"))) for name in ("intersect", "occluded")) + " ms")
+        sys.stdout.flush()
+        k *= 4
+    mirt.shutdown()
+
+
+ALONG_ROW = re.compile(r"along n\s+(\d+) rays\s+(\d+) B\s+\d+ hit [0-9.]+  intersect\s+([0-9.]+)\s+([0-9.]+)\s+([0-9.]+)  occluded\s+([0-9.]+)\s+([0-9.]+)\s+([0-9.]+) ms")
+
+
+def step_along(p):
+    p("== along: mirt_intersect_along_device / mirt_occluded_along_device, a square grid of starts looking down the scene (dir = +z), beside")
+    p("   mirt_intersect_device / mirt_occluded_device from fresh records on the same rays (host clock around call + mirt_sync, medians) ==")
+    p("AUTO starts with the fans' rule: bin from 2000 triangles on, or from MIRT_BIN_THRESHOLD triangles with rays x n >= 4e7, or when the grid is held;")
+    p("under it every cell below would bin (both scenes have 2000 triangles or more): what the rows say of that follows them")
+    p("three columns each: the yardstick; BINNED, the grid built by the call; BINNED, the grid held")
+    out = "".join(run_child(p, ["--child", "along", str(n)], {}, 420) for n in (100000, 2000))
+    along_summary(out, p)
+
+
+def along_summary(text, p):
+    """What the rows say: the cells where the new call is behind its yardstick (by more than the 2 % two runs differ by), with the
+    grid built by the call and with it held, and -- per triangle count and call -- the ray count from which the call with its build
+    stays ahead, which is where AUTO's rule would have to switch when the grid is not held."""
+    rows = [(int(m.group(1)), int(m.group(2)), [float(x) for x in m.groups()[2:]]) for m in ALONG_ROW.finditer(text)]
+    behind = {"built": [], "held": []}
+    for n, k, v in rows:
+        for what, off in (("intersect", 0), ("occluded", 3)):
+            for j, mode in ((1, "built"), (2, "held")):
+                if v[off + j] > 1.02 * v[off]:
+                    behind[mode].append("n %d rays %d %s: %.4f ms against %.4f ms" % (n, k, what, v[off + j], v[off]))
+    p("the new call behind its yardstick by more than 2 %, grid built by the call: " + ("; ".join(behind["built"]) or "nowhere"))
+    p("the new call behind its yardstick by more than 2 %, grid held: " + ("; ".join(behind["held"]) or "nowhere"))
+    crossings = []
+    for n in sorted({r[0] for r in rows}, reverse=True):
+        for what, off in (("intersect", 0), ("occluded", 3)):
+            cells = sorted((k, v[off + 1] <= v[off]) for nn, k, v in rows if nn == n)
+            lost = [k for k, ahead in cells if not ahead]
+            first = min([k for k, _ in cells if not lost or k > max(lost)], default=None)
+            crossings.append((n, what, len(lost), len(cells), first))
+            p("n %d %s, grid built by the call: behind in %d of %d cells; ahead in every cell from %s rays on"
+              % (n, what, len(lost), len(cells), first if first is not None else "no count measured"))
+    starts = {c[4] for c in crossings}
+    if all(c[2] == 0 for c in crossings):
+        p("verdict: the fans' rule is confirmed -- with its build the call is ahead in every cell")
+    elif len(starts) == 1 and None not in starts:
+        p("verdict: the fans' rule is moved -- unless the grid is held, binning pays from %d rays on in every series (the cell before: %d rays)"
+          % (starts.pop(), max(k for n, k, v in rows if k < min(c[4] for c in crossings))))
+    else:
+        p("verdict: the series disagree on where binning with its build starts to pay (%s): no single ray count moves the rule"
+          % ", ".join("n %d %s from %s" % (c[0], c[1], c[4]) for c in crossings))
+    p("")
+
+
 # ---- shadow masks: mirt_shadow_mask_device and mirt_direct_light_masked_device beside mirt_direct_light_device ------------------------
 
 MASK_SETS = ((1, 1), (2, 1), (2, 16), (4, 16), (16, 16))      # lights x samples: 1, 2, 32, 64 and 256 positions
@@ -949,6 +1082,8 @@ def main():
             return child_occsweep(int(a.child[1]))
         if a.child[0] == "occfans":
             return child_occfans(int(a.child[1]))
+        if a.child[0] == "along":
+            return child_along(int(a.child[1]))
         if a.child[0] == "mask":
             return child_mask(a.child[1], int(a.child[2]), a.child[3] == "spread")
         return child_throughput() if a.child[0] == "throughput" else child_sweep(int(a.child[1]))
@@ -977,6 +1112,8 @@ def main():
             step_occluded(p)
         if "mask" in steps:
             step_mask(p)
+        if "along" in steps:
+            step_along(p)
     finally:
         with open(a.out, "a" if a.append else "w") as f:
             f.write("\n".join(lines) + "\n")
