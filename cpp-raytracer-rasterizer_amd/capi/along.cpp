@@ -44,6 +44,28 @@ static int along_pairs_room(AlongCache &C, size_t cap)
     return MIRT_OK;
 }
 
+// A build of a structure the streams share, on g.stream (alongs.cpp builds its groups between the same two): calls of the other
+// streams may still read the old tables, so this stream waits for what they have queued; then the scene's rows.  Behind the build
+// the later calls of the other streams wait for it.
+int along_build_begin()
+{
+    for (int o = 0; o < g.in_flight; o++)
+        if (o != g.si) {
+            HIP_TRY(hipEventRecord(g.streams[o].ev_order, g.streams[o].stream));
+            HIP_TRY(hipStreamWaitEvent(g.stream, g.streams[o].ev_order, 0));
+        }
+    return query_rows();
+}
+int along_build_end()
+{
+    if (g.in_flight > 1) {
+        HIP_TRY(hipEventRecord(g.cur().ev_order, g.stream));
+        for (int o = 0; o < g.in_flight; o++)
+            if (o != g.si) HIP_TRY(hipStreamWaitEvent(g.streams[o].stream, g.cur().ev_order, 0));
+    }
+    return MIRT_OK;
+}
+
 // The structure for (the current scene, dir) in C, built on g.stream unless C holds it: the scene's rows, the pairs (sized by a
 // read-back of their count, as a cube's build: 8 bytes and one sync of this stream, the pass repeated if the list was too small),
 // the sort, the rows in key order.  A build whose every-ray list outgrows along_every_cap is kept as `gave_up`: the calls for this
@@ -55,12 +77,7 @@ static int along_ensure(AlongCache &C, const float *dir, const AlongDesc &desc, 
     if (C.holds(g.scene_version, g.n, dir)) return MIRT_OK;
     *built = true;
     C.valid = false;
-    for (int o = 0; o < g.in_flight; o++)                    // calls of the other streams may still read the old tables
-        if (o != g.si) {
-            HIP_TRY(hipEventRecord(g.streams[o].ev_order, g.streams[o].stream));
-            HIP_TRY(hipStreamWaitEvent(g.stream, g.streams[o].ev_order, 0));
-        }
-    if ((rc = query_rows())) return rc;
+    if ((rc = along_build_begin())) return rc;
     const uint32_t nkeys = along_keys(desc.B, desc.shells), nbuckets = bucket_sort_buckets(nkeys);
     if (nkeys + 1 > C.cap_keys && (rc = dev_grow(&C.d_off, &C.cap_keys, nkeys + 1, (size_t)nkeys + 1, false))) return rc;
     if (g.n > C.cap_near && (rc = dev_grow(&C.d_near, &C.cap_near, g.n, (size_t)g.n, false))) return rc;
@@ -113,11 +130,7 @@ static int along_ensure(AlongCache &C, const float *dir, const AlongDesc &desc, 
             HIP_TRY(hipGetLastError());
         }
     }
-    if (g.in_flight > 1) {                                   // later calls of the other streams wait for the build
-        HIP_TRY(hipEventRecord(g.cur().ev_order, g.stream));
-        for (int o = 0; o < g.in_flight; o++)
-            if (o != g.si) HIP_TRY(hipStreamWaitEvent(g.streams[o].stream, g.cur().ev_order, 0));
-    }
+    if ((rc = along_build_end())) return rc;
     C.desc = desc;
     C.version = g.scene_version;
     C.n = g.n;

@@ -16,10 +16,12 @@
 #include "../csrc/scan.hpp"
 #include "../query/rt_query.hpp"
 #include "../along/along.hpp"
+#include "../along/alongs.hpp"
 #include "../lights/many_lights.hpp"
 #include "../lights/aa_many_lights.hpp"
 #include "cube_plan.hpp"
 #include "pass_plan.hpp"
+#include "along_plan.hpp"
 #include "object_plan.hpp"
 #include "dof_plan.hpp"
 #include "aa_plan.hpp"
@@ -332,6 +334,46 @@ struct AlongCache {
     void release();
 };
 
+// A GROUP of directions of the queries along several directions in one call (alongs.cpp; ../along/alongs.hpp, along_plan.hpp): up to
+// alongs_slots directions, each with the single grid's descriptor, behind one offset table and one row table.  Kept under the scene
+// version, the triangle count, the grid (B, shells) and the pass's directions compared bit for bit and in order; shared by the
+// streams under along_ensure's protocol (built on the stream of the call that misses it, the other streams ordered behind the build
+// by events); the tables only grow and are released in mirt_shutdown.
+struct AlongsGroup {
+    bool valid = false;
+    uint64_t version = 0;
+    int n = 0, B = 0, shells = 0, count = 0;
+    float dirs[MIRT_MAX_LIGHTS * 3] = {};        // the pass's directions as the caller gave them
+    bool gave_up = false;                        // a direction no grid is built for, or an every-ray list that outgrew its share: calls
+                                                 // that hold this pass take the brute-force kernels and build nothing
+    AlongDesc *d_descs = nullptr;                // MIRT_MAX_LIGHTS descriptors
+    float *d_dirs = nullptr;                     // MIRT_MAX_LIGHTS x 3
+    uint32_t *d_off = nullptr;                   // count * along_keys + 1
+    uint32_t cap_keys = 0;
+    QueryRow *d_rows = nullptr;                  // the rows in key order (at least one: a lane with no row left loads row 0)
+    AlongAux *d_aux = nullptr;
+    uint32_t cap_rows = 0, nrows = 0;
+
+    bool holds(uint64_t v, int tris, int bins, int nshells, const float *d, int ndirs) const
+    {
+        return valid && version == v && n == tris && B == bins && shells == nshells && count == ndirs && memcmp(dirs, d, sizeof(float) * 3 * (size_t)ndirs) == 0;
+    }
+    void release();
+};
+// The scratch of a group's build: the pair list, the sort's scratch and the depth bounds per (slot, triangle).  One set serves all
+// groups: a build waits for the other streams first (along_ensure's protocol), so no two builds overlap.
+struct AlongsBuild {
+    float *d_near = nullptr;                     // slots x n
+    size_t cap_near = 0;
+    uint32_t *d_counters = nullptr;              // [0] pairs, [1 + slot] triangles on the slot's every-ray list
+    uint32_t *d_keys = nullptr, *d_vals = nullptr, *d_tmp_keys = nullptr, *d_tmp_vals = nullptr, *d_entries = nullptr;
+    uint32_t cap_pairs = 0;
+    uint32_t *d_bucket = nullptr;                // bucket sort: counts | bases (+1) | cursors, cap_buckets each
+    uint32_t cap_buckets = 0;
+
+    void release();
+};
+
 // The ray-independent rows of ClosestIntersection (k_query_rows): built once per scene version on the stream of the query that
 // finds them missing, shared by every stream; a query on another stream waits for ev_built, not for the device.
 struct QueryRows {
@@ -373,6 +415,11 @@ struct QueryRows {
     LightCache aa_cam;
     // The grid of the queries along one direction (mirt_intersect_along*, mirt_occluded_along*): one is kept.
     AlongCache along;
+    // The groups of the queries along several directions in one call (mirt_intersect_alongs*, mirt_occluded_alongs*): pass p of a call
+    // keeps its group in alongs[p % ALONGS_GROUPS], apart from `along`, so that a repeated call of up to ALONGS_GROUPS passes builds
+    // nothing and neither family evicts the other's structure.
+    AlongsGroup alongs[ALONGS_GROUPS];
+    AlongsBuild alongs_build;
 
     void release();                              // (the cubes' tables too)
 };
@@ -700,6 +747,15 @@ int along_intersect(const float *dir, const void *d_origins3, int nrays, void *d
 int along_intersect_host(const float *dir, const float *origins3, int nrays, mirt_hit *hits);
 int along_occluded(const float *dir, const void *d_origins3, int nrays, const void *d_max_distance, void *d_occluded);
 int along_occluded_host(const float *dir, const float *origins3, int nrays, const float *max_distance, uint8_t *occluded);
+// What alongs.cpp shares with along.cpp: the start of a build under the streams' protocol, and its end.
+int along_build_begin();
+int along_build_end();
+
+// ---- ray queries along several directions in one call (alongs.cpp; the kernels: ../along/alongs.hip) ----
+int alongs_intersect(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, void *d_hits);
+int alongs_intersect_host(const float *dirs3, int ndirs, const int32_t *dir_of, const float *origins3, int nrays, mirt_hit *hits);
+int alongs_occluded(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, const void *d_max_distance, void *d_occluded);
+int alongs_occluded_host(const float *dirs3, int ndirs, const int32_t *dir_of, const float *origins3, int nrays, const float *max_distance, uint8_t *occluded);
 
 // ---- rasteriser (raster.cpp) ----
 int raster_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect,

@@ -158,6 +158,8 @@ void QueryRows::release()
     aa_cam.release();
     for (LightCache &c : fans) c.release();
     along.release();
+    for (AlongsGroup &a : alongs) a.release();
+    alongs_build.release();
     *this = QueryRows();
 }
 
@@ -165,6 +167,18 @@ void AlongCache::release()
 {
     dev_free({ d_off, d_rows, d_aux, d_near, d_counters, d_keys, d_vals, d_tmp_keys, d_tmp_vals, d_entries, d_bucket });
     *this = AlongCache();
+}
+
+void AlongsGroup::release()
+{
+    dev_free({ d_descs, d_dirs, d_off, d_rows, d_aux });
+    *this = AlongsGroup();
+}
+
+void AlongsBuild::release()
+{
+    dev_free({ d_near, d_counters, d_keys, d_vals, d_tmp_keys, d_tmp_vals, d_entries, d_bucket });
+    *this = AlongsBuild();
 }
 
 void LightCache::release() { dev_free({ d_light_tab, d_frames, d_off, d_rows, d_row_tri, d_origins, d_counter }); *this = LightCache(); }

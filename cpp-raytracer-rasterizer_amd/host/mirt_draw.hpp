@@ -247,6 +247,24 @@ struct RayTracer {
         static_assert(sizeof(vec3) == 12, "starts travel as they are");
         check(mirt_occluded_along(&dir.x, n > 0 ? &start[0].x : nullptr, n, max_distance, occluded), "mirt_occluded_along");
     }
+    // The two above for n rays along `ndirs` shared directions -- a sun study over the hours of a day, six orthographic views:
+    // closest[k] comes back as ClosestIntersection(start[k], dirs[dir_of[k]], triangles, closest[k]) leaves it; up to MIRT_MAX_LIGHTS
+    // directions share one build (mirt_intersect_alongs, mirt_occluded_alongs).  dir_of may be null for a single direction.  (Named
+    // apart: their argument types are the many-start overloads'.)
+    void ClosestIntersectionAlong(const vec3 *dirs, int ndirs, const int32_t *dir_of, const vec3 *start, Intersection *closest, int n)
+    {
+        upload_scene();
+        static_assert(sizeof(vec3) == 12, "starts and directions travel as they are");
+        check(mirt_intersect_alongs(ndirs > 0 ? &dirs[0].x : nullptr, ndirs, dir_of, n > 0 ? &start[0].x : nullptr, n,
+                                    reinterpret_cast<mirt_hit *>(closest)), "mirt_intersect_alongs");
+    }
+    void OccludedAlong(const vec3 *dirs, int ndirs, const int32_t *dir_of, const vec3 *start, const float *max_distance, uint8_t *occluded, int n)
+    {
+        upload_scene();
+        static_assert(sizeof(vec3) == 12, "starts and directions travel as they are");
+        check(mirt_occluded_alongs(ndirs > 0 ? &dirs[0].x : nullptr, ndirs, dir_of, n > 0 ? &start[0].x : nullptr, n, max_distance, occluded),
+              "mirt_occluded_alongs");
+    }
     // DirectLight(i) (:265-327) for n records, with the lights and the soft-shadow toggle as they stand: result[k] = DirectLight(i[k]).
     void DirectLight(const Intersection *i, vec3 *result, int n)
     {

@@ -32,6 +32,7 @@ EXPORTS = (
     "mirt_intersect_fans", "mirt_intersect_fans_device",
     "mirt_occluded", "mirt_occluded_device", "mirt_occluded_fans", "mirt_occluded_fans_device", "mirt_get_occlusion_stats",
     "mirt_intersect_along", "mirt_intersect_along_device", "mirt_occluded_along", "mirt_occluded_along_device", "mirt_get_along_stats",
+    "mirt_intersect_alongs", "mirt_intersect_alongs_device", "mirt_occluded_alongs", "mirt_occluded_alongs_device",
     "mirt_shadow_mask", "mirt_shadow_mask_device", "mirt_direct_light_masked", "mirt_direct_light_masked_device", "mirt_get_shadow_mask_stats",
     "mirt_scene_upload_device", "mirt_scene_update_device", "mirt_scene_update", "mirt_scene_transform", "mirt_transform",
     "mirt_scene_download", "mirt_scene_info",
@@ -174,6 +175,10 @@ def load():
     lib.mirt_occluded_along.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
     lib.mirt_occluded_along_device.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
     lib.mirt_get_along_stats.argtypes = [C.POINTER(QueryStats)]
+    lib.mirt_intersect_alongs.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp]
+    lib.mirt_intersect_alongs_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp]
+    lib.mirt_occluded_alongs.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]
+    lib.mirt_occluded_alongs_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]
     lib.mirt_shadow_mask.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp]
     lib.mirt_shadow_mask_device.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp]
     lib.mirt_direct_light_masked.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp]
@@ -839,10 +844,63 @@ def occluded_along_device(direction, d_origins, nrays, d_max_distance, d_occlude
 
 
 def along_stats():
-    """The last intersect_along* / occluded_along* call (mirt_get_along_stats), in mirt_query_stats' fields: mode_used, cube_source
-    (0 no grid, 1 built by the call, 2 kept), cube_bins = cells per grid side, shells and -- profiling on, binned -- shadow_rays =
-    rays, candidates = rows offered, tests = rows tested, fallback_records = rays that swept the scene."""
+    """The last intersect_along* / occluded_along* / intersect_alongs* / occluded_alongs* call (mirt_get_along_stats), in
+    mirt_query_stats' fields: mode_used, cube_source (0 no grid, 1 built by the call, 2 kept), cube_bins = cells per grid side, shells
+    and -- profiling on, binned -- shadow_rays = rays, candidates = rows offered, tests = rows tested, fallback_records = rays that
+    swept the scene.  For a call of several directions the counters are summed over its passes, and cube_source is 1 when some pass
+    built its group, 2 when every pass's group was held."""
     return _read_query_stats(load().mirt_get_along_stats)
+
+
+# ---- ray queries along several directions in one call ----------------------------------------------------------
+
+def _as_alongs(directions, dir_of, origins):
+    """The arrays of a call of several directions as the library takes them: directions (k, 3), dir_of one int32 per ray or None,
+    origins (n, 3)."""
+    origins = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    if dir_of is not None:
+        dir_of = np.ascontiguousarray(dir_of, np.int32).reshape(-1)
+        if len(dir_of) != len(origins):
+            raise ValueError("%d origins but %d direction indices" % (len(origins), len(dir_of)))
+    return np.ascontiguousarray(directions, np.float32).reshape(-1, 3), dir_of, origins
+
+
+def intersect_alongs(directions, dir_of, origins, hits=None):
+    """ClosestIntersection(origins[i], directions[dir_of[i]]) for every start (mirt_intersect_alongs): what intersect() returns for
+    the rays {origins[i], directions[dir_of[i]]}, bit for bit, the directions sharing groups of up to MAX_LIGHTS grids
+    (set_query_mode).  directions: (k, 3) floats, used as given; dir_of: one int32 per ray, or None for a single direction; origins:
+    (n, 3) floats; hits: the in/out records (HIT_DTYPE; fresh ones when None).  Returns a new array."""
+    directions, dir_of, origins = _as_alongs(directions, dir_of, origins)
+    hits = fresh_hits(len(origins)) if hits is None else np.ascontiguousarray(hits, HIT_DTYPE).copy()
+    if len(hits) != len(origins):
+        raise ValueError("%d origins but %d hit records" % (len(origins), len(hits)))
+    _check(load().mirt_intersect_alongs(_ptr(directions), len(directions), _ptr(dir_of), _ptr(origins), len(origins), _ptr(hits)))
+    return hits
+
+
+def intersect_alongs_device(directions, d_dir_of, d_origins, nrays, d_hits):
+    """The same on device arrays (raw pointers; the directions are host data, d_dir_of may be None for a single direction), queued
+    like a *_device frame; mirt.sync() completes it."""
+    directions = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+    _check(load().mirt_intersect_alongs_device(_ptr(directions), len(directions), d_dir_of, d_origins, int(nrays), d_hits))
+
+
+def occluded_alongs(directions, dir_of, origins, max_distance=None, out=None):
+    """occluded() for the rays {origins[i], directions[dir_of[i]]}, byte for byte, through the groups of intersect_alongs
+    (mirt_occluded_alongs).  max_distance: n floats, one for all, or None for +inf.  Returns uint8 (`out` when given: every byte is
+    written)."""
+    directions, dir_of, origins = _as_alongs(directions, dir_of, origins)
+    lim = _as_limits(max_distance, len(origins), "origins")
+    out = _occluded_out(out, len(origins), "origins")
+    _check(load().mirt_occluded_alongs(_ptr(directions), len(directions), _ptr(dir_of), _ptr(origins), len(origins), _ptr(lim), _ptr(out)))
+    return out
+
+
+def occluded_alongs_device(directions, d_dir_of, d_origins, nrays, d_max_distance, d_occluded):
+    """The same on device arrays (raw pointers; the directions are host data, d_dir_of may be None for a single direction and
+    d_max_distance for +inf), queued like a *_device frame."""
+    directions = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+    _check(load().mirt_occluded_alongs_device(_ptr(directions), len(directions), d_dir_of, d_origins, int(nrays), d_max_distance, d_occluded))
 
 
 # ---- shadow masks: DirectLight's shadow decisions, and DirectLight from them ---------------------------------

@@ -589,6 +589,41 @@ MIRT_API int mirt_occluded_along_device(const float dir[3], const void *d_origin
  * Waits for the stream of that call. */
 MIRT_API int mirt_get_along_stats(mirt_query_stats *out);
 
+/* ---- ray queries along SEVERAL directions in one call (additions to ABI 4) ---- */
+
+/* ClosestIntersection(origins[i], dirs[dir_of[i]], triangles, hits[i]) for i in [0, nrays): exactly mirt_intersect on the rays
+ * { origins3[3 * i ..], dirs3[3 * dir_of[i] ..] }, bit for bit, for every ray and every incoming record -- and mirt_occluded on the same
+ * rays, byte for byte, for every limit.  The callers of the single-direction calls above with more than one direction: a sun study
+ * over the hours of a day, six orthographic views, a parallel-beam scan from many angles, the ambient occlusion or sky visibility
+ * of N points towards K directions -- one call, one launch per pass and one statistics record instead of K, and the rays in any
+ * order: the lanes of a wave may hold different directions, and the same direction may appear twice in the list.
+ * Each direction gets exactly the grid mirt_intersect_along builds for it; a GROUP of up to 32 directions (15 from 32 769 triangles
+ * on, where a grid has 256 x 256 cells) shares one build: one pair list, one sort, one read-back.  A call of more directions runs in
+ * passes over consecutive ranges of its list.  Pass p keeps its group in slot p % 8 of eight kept groups, apart from the grid of the
+ * single-direction calls, under the scene and the pass's directions compared bit for bit and in order: a repeated call of up to eight
+ * passes builds nothing, and neither family evicts the other's structure.  mirt_intersect_alongs and mirt_occluded_alongs share the
+ * groups.
+ * dirs3: a HOST array of ndirs x 3 floats in both forms, used as given.  dir_of: one index per ray; NULL only when ndirs == 1.
+ * origins3, hits, occluded, max_distance: as mirt_intersect_along / mirt_occluded_along.  nrays == 0 does nothing.  Checks, in this
+ * order: MIRT_ERR_INVALID_ARGUMENT for a negative count, a NULL array with a positive count, ndirs == 0 with nrays > 0 or a NULL dir_of
+ * with ndirs > 1 (the arguments first, with or without a device); MIRT_ERR_NOT_INITIALISED; MIRT_ERR_NO_SCENE.  The host forms look at
+ * every dir_of[i] before anything touches the device: an index outside [0, ndirs) is MIRT_ERR_INVALID_ARGUMENT and nothing is written.
+ * The _device forms cannot: such a ray reads nothing out of bounds, its record's 20 bytes stay unwritten and its occlusion byte is
+ * written 0, under every mode.
+ * mirt_set_query_mode governs the calls: BRUTE writes the rays out on the device and takes mirt_intersect_device's /
+ * mirt_occluded_device's kernels; BINNED builds the groups that are not held; AUTO is the single call's rule -- more than
+ * MIRT_QUERY_WAVE_RAYS rays on a scene the fans would bin, or every group of the call is held.  When one direction of the call is unfit
+ * for a grid (mirt_intersect_along's cases: outside the window, cells a float cannot tell apart, an every-ray list beyond its share)
+ * or the scene is not finite, the WHOLE call takes the brute-force kernels and mode_used says BRUTE; the group remembers it, so the
+ * next call builds nothing either.
+ * mirt_get_along_stats reports the last call of either along family.  For these calls shadow_rays, candidates, tests and
+ * fallback_records are summed over the passes, cube_bins and shells are the last pass's, and cube_source is 0 none, 1 some pass
+ * built its group, 2 every pass's group was held. */
+MIRT_API int mirt_intersect_alongs(const float *dirs3, int ndirs, const int32_t *dir_of, const float *origins3, int nrays, mirt_hit *hits);
+MIRT_API int mirt_intersect_alongs_device(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, void *d_hits);
+MIRT_API int mirt_occluded_alongs(const float *dirs3, int ndirs, const int32_t *dir_of, const float *origins3, int nrays, const float *max_distance, uint8_t *occluded);
+MIRT_API int mirt_occluded_alongs_device(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, const void *d_max_distance, void *d_occluded);
+
 /* ---- shadow masks: DirectLight's shadow decision per (record, light position), and DirectLight from a mask (additions to ABI 4) ---- */
 
 /* The one value DirectLight computes and throws away (raytracer.cpp:306-315): whether the shadow ray of a record towards a light

@@ -55,6 +55,7 @@ EXPECT = ("k_rt_trace2", "k_rt_tile2", "k_rt_brute", "k_bin_pairs", "k_raster_sm
           "k_query_direct_light<2, false, true, false>", "k_query_direct_light<2, false, true, true>",
           "k_query_direct_light_binned<1, false, false, true>", "k_query_direct_light_binned<1, true, false, true>", "k_query_relight",
           "k_along_pairs", "k_along_rows", "k_along_expand", "k_along_closest<false>", "k_along_closest<true>", "k_along_occluded<false>", "k_along_occluded<true>",
+          "k_alongs_pairs", "k_alongs_rows", "k_alongs_expand", "k_alongs_closest<false>", "k_alongs_closest<true>", "k_alongs_occluded<false>", "k_alongs_occluded<true>",
           "k_frame_records", "k_frame_resolve", "k_aa_primary<false>", "k_aa_primary<true>", "k_aa_resolve",
           "k_scene_bounds_init", "k_scene_range<1>", "k_scene_range<3>", "k_scene_range<5>", "k_scene_range<7>", "k_scene_range<4>", "k_scene_range<11>")
 missing = [k for k in EXPECT if not any(k in r[1] for r in rows)]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans,occluded,mask,along]
+"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans,occluded,mask,along,alongs]
 
 The measurements of the ray-query kernels (query/rt_query.hip), written to one text file:
 
@@ -47,6 +47,14 @@ The measurements of the ray-query kernels (query/rt_query.hip), written to one t
                        written out, in the same run.  The answers are compared first; the cells where the new call is behind are listed,
                        and from the rows the ray count from which the call with its build stays ahead: whether AUTO's starting rule
                        (the fans') is confirmed or moved.
+  alongs               mirt_intersect_alongs_device and mirt_occluded_alongs_device for N points (the same grid of starts) x K = 1, 4, 15,
+                       16, 32, 64 directions up to 35 degrees off +z, N = 64 .. 65 536 in powers of four, at n = 100 000 and n = 2 000, the
+                       directions mixed within every wave: under MIRT_QUERY_BINNED with the groups built by the call (the list's bits
+                       change between the calls) and with them held, beside two yardsticks on the same rays in the same run -- (a) K
+                       mirt_*_along_device calls over the rays sorted by direction, what a caller does today, and (b)
+                       mirt_intersect_device / mirt_occluded_device.  The answers are compared first; every cell is recorded, the cells
+                       where the new call is behind either yardstick by more than 2 % are listed, and per scene where binning with
+                       its builds is ahead of (b): what AUTO's rule for the call rests on.
 
 The knob is read once per process, so every GPU step is a child process of its own, under its own `timeout`; a step that fails
 ends the run."""
@@ -906,6 +914,161 @@ def along_summary(text, p):
     p("")
 
 
+# ---- several directions in one call: mirt_intersect_alongs_device / mirt_occluded_alongs_device ------------------------------------------
+
+ALONGS_K = (1, 4, 15, 16, 32, 64)
+ALONGS_RAYS = (64, 256, 1024, 4096, 16384, 65536)             # rays per direction
+ALONGS_BRUTE_CAP = 1.0e11                                     # rays x triangles from which the brute yardstick is timed once, not thrice
+
+
+def alongs_directions(K):
+    """K directions looking down the scene, up to 35 degrees off +z, seeded."""
+    rng = np.random.default_rng(13)
+    d = np.ones((K, 3), np.float32)
+    d[:, 0:2] = rng.uniform(-0.7, 0.7, (K, 2))
+    d[0] = (0.0, 0.0, 1.0)
+    return np.ascontiguousarray(d)
+
+
+def child_alongs(n, only_k):
+    """One scene and one K: every ray count, closest hits and occlusion (no limits).  N points x K directions, ray i = point i // K
+    along direction i % K, so the lanes of a wave mix the directions.  The yardsticks on the same rays in the same run, after all
+    answers were found equal: (a) K mirt_*_along_device calls over the rays sorted by direction -- `fresh`: directions never seen,
+    every call builds; `again`: the list repeated, where the one kept grid serves K = 1 and is evicted K times a round otherwise --,
+    (b) mirt_intersect_device / mirt_occluded_device.  The new call with its groups built by the call (directions never seen) and
+    with them held."""
+    import mirt
+    h = hip()
+    mirt.init(0)
+    mirt.scene_upload(mirt.scene_soup(1, n, 0.05 if n >= 50000 else 0.2))
+    top = ALONGS_K[-1] * ALONGS_RAYS[-1]
+    fresh = mirt.fresh_hits(top)
+    d_starts, d_sorted, d_rays, d_of = dev_alloc(h, 12 * top), dev_alloc(h, 12 * top), dev_alloc(h, 24 * top), dev_alloc(h, 4 * top)
+    d_hits, d_occ = dev_alloc(h, fresh.nbytes, fresh), dev_alloc(h, top)
+    at = lambda ptr, off: C.c_void_p(ptr.value + int(off))
+    variant = [0]
+
+    def run(fn, total):
+        assert h.hipMemcpy(d_hits, fresh.ctypes.data_as(C.c_void_p), 20 * total, 1) == 0
+        t0 = time.perf_counter()
+        fn(); mirt.sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    def median_of(fn, total, reps, warm=1):
+        return float(np.median([run(fn, total) for _ in range(reps + warm)][warm:]))
+
+    for K in (only_k,):
+        dirs = alongs_directions(K)
+        for R in ALONGS_RAYS:
+            total = K * R
+            grid = along_grid(R)
+            starts = np.ascontiguousarray(np.repeat(grid, K, axis=0))
+            of = np.ascontiguousarray(np.tile(np.arange(K, dtype=np.int32), R))
+            rays = mirt.make_rays(starts, dirs[of])
+            by_dir = np.ascontiguousarray(np.tile(grid, (K, 1)))             # direction k's starts at [k R, (k + 1) R)
+            for dst, src in ((d_starts, starts), (d_sorted, by_dir), (d_rays, rays), (d_of, of)):
+                assert h.hipMemcpy(dst, src.ctypes.data_as(C.c_void_p), src.nbytes, 1) == 0
+
+            def singles(kind, D):
+                for k in range(K):
+                    if kind == "intersect":
+                        mirt.intersect_along_device(D[k], at(d_sorted, 12 * k * R), R, at(d_hits, 20 * k * R))
+                    else:
+                        mirt.occluded_along_device(D[k], at(d_sorted, 12 * k * R), R, None, at(d_occ, k * R))
+
+            def unseen():
+                """The list with other bits in every direction (a dyadic factor: the geometry stays), never the key of a call before."""
+                variant[0] += 1
+                return np.ascontiguousarray(dirs * np.float32(1.0 + variant[0] / 4096.0))
+
+            calls = {
+                "intersect": (lambda: mirt.intersect_device(d_rays, total, d_hits), lambda D: mirt.intersect_alongs_device(D, d_of, d_starts, total, d_hits)),
+                "occluded": (lambda: mirt.occluded_device(d_rays, total, None, d_occ), lambda D: mirt.occluded_alongs_device(D, d_of, d_starts, total, None, d_occ)),
+            }
+            # the answers first: (b), the new call and (a) agree on every ray
+            want, got = np.zeros(total, mirt.HIT_DTYPE), np.zeros(total, mirt.HIT_DTYPE)
+            wocc, gocc = np.zeros(total, np.uint8), np.zeros(total, np.uint8)
+            ms = {}
+            ms["intersect", "brute"] = run(calls["intersect"][0], total)
+            assert h.hipMemcpy(want.ctypes.data_as(C.c_void_p), d_hits, want.nbytes, 2) == 0
+            ms["occluded", "brute"] = run(calls["occluded"][0], total)
+            assert h.hipMemcpy(wocc.ctypes.data_as(C.c_void_p), d_occ, total, 2) == 0
+            mirt.set_query_mode(mirt.QUERY_BINNED)
+            run(lambda: calls["intersect"][1](dirs), total)
+            st = mirt.along_stats()
+            assert st["mode_used"] == mirt.QUERY_BINNED, st
+            assert h.hipMemcpy(got.ctypes.data_as(C.c_void_p), d_hits, got.nbytes, 2) == 0
+            run(lambda: calls["occluded"][1](dirs), total)
+            assert h.hipMemcpy(gocc.ctypes.data_as(C.c_void_p), d_occ, total, 2) == 0
+            assert got.tobytes() == want.tobytes() and np.array_equal(gocc, wocc), "the call of several directions disagrees with mirt_intersect_device / mirt_occluded_device"
+            run(lambda: singles("intersect", dirs), total)
+            assert h.hipMemcpy(got.ctypes.data_as(C.c_void_p), d_hits, got.nbytes, 2) == 0
+            run(lambda: singles("occluded", dirs), total)
+            assert h.hipMemcpy(gocc.ctypes.data_as(C.c_void_p), d_occ, total, 2) == 0
+            back = np.arange(total).reshape(R, K).T.ravel()                  # sorted position -> the ray it is
+            assert got.tobytes() == want[back].tobytes() and np.array_equal(gocc, wocc[back]), "the single-direction calls disagree with mirt_intersect_device / mirt_occluded_device"
+            reps = 5 if total <= 65536 else 3
+            for name, (brute, alongs) in calls.items():
+                mirt.set_query_mode(mirt.QUERY_AUTO)
+                if float(total) * n <= ALONGS_BRUTE_CAP:
+                    ms[name, "brute"] = median_of(brute, total, reps)
+                mirt.set_query_mode(mirt.QUERY_BINNED)
+                ms[name, "fresh"] = median_of(lambda: singles(name, unseen()), total, reps)
+                ms[name, "again"] = median_of(lambda: singles(name, dirs), total, reps, warm=2)
+                ms[name, "built"] = median_of(lambda: alongs(unseen()), total, reps)
+                assert mirt.along_stats()["cube_source"] == 1
+                ms[name, "held"] = median_of(lambda: alongs(dirs), total, reps, warm=2)
+                assert mirt.along_stats()["cube_source"] == 2         # (at most five passes: every group is kept)
+            mirt.set_query_mode(mirt.QUERY_AUTO)
+            print("RESULT alongs n %6d K %2d rays %6d B %3d hit %.3f  " % (n, K, R, st["cube_bins"], float((want["index"] >= 0).mean()))
+                  + "  ".join("%s %s" % (name, " ".join("%10.4f" % ms[name, m] for m in ("brute", "fresh", "again", "built", "held"))) for name in ("intersect", "occluded")) + " ms")
+            sys.stdout.flush()
+    mirt.shutdown()
+
+
+ALONGS_ROW = re.compile(r"alongs n\s+(\d+) K\s+(\d+) rays\s+(\d+) B\s+\d+ hit [0-9.]+  intersect((?:\s+[0-9.]+){5})  occluded((?:\s+[0-9.]+){5}) ms")
+
+
+def step_alongs(p):
+    p("== alongs: mirt_intersect_alongs_device / mirt_occluded_alongs_device, N points (a square grid looking down the scene) x K directions up to 35 degrees")
+    p("   off +z, ray i = point i / K along direction i % K; `rays` is N, the rays per direction (host clock around call + mirt_sync, medians) ==")
+    p("five columns each: (b) mirt_intersect_device / mirt_occluded_device; (a) K mirt_*_along_device calls over the rays sorted by direction, BINNED,")
+    p("directions never seen (`fresh`: every call builds) and the list repeated (`again`: K = 1 finds its grid held, K > 1 evicts it K times a round);")
+    p("the new call, BINNED, its groups built by the call and held.  All answers were compared first.  (b) beyond %.0e rays x triangles: one timing, not a median" % ALONGS_BRUTE_CAP)
+    out = "".join(run_child(p, ["--child", "alongs", str(n), str(K)], {}, 300) for n in (100000, 2000) for K in ALONGS_K)
+    alongs_summary(out, p)
+
+
+def alongs_summary(text, p):
+    """What the rows say: the cells where the new call is behind either yardstick by more than the 2 % two runs differ by -- built
+    by the call against (b) and (a) fresh, held against (b) and (a) again --, and per triangle count and kind the total ray count
+    from which the call with its builds stays ahead of (b): where AUTO's rule has to switch when the groups are not held."""
+    rows = []
+    for m in ALONGS_ROW.finditer(text):
+        rows.append((int(m.group(1)), int(m.group(2)), int(m.group(3)), {"intersect": [float(x) for x in m.group(4).split()], "occluded": [float(x) for x in m.group(5).split()]}))
+    behind = {("built", "b"): [], ("built", "a"): [], ("held", "b"): [], ("held", "a"): []}
+    for n, K, R, v in rows:
+        for what, t in v.items():
+            brute, fresh, again, built, held = t
+            for key, mine, yard in ((("built", "b"), built, brute), (("built", "a"), built, fresh), (("held", "b"), held, brute), (("held", "a"), held, again)):
+                if mine > 1.02 * yard:
+                    behind[key].append("n %d K %d rays %d %s: %.4f against %.4f ms" % (n, K, R, what, mine, yard))
+    names = {"b": "(b) the brute-force call", "a": "(a) K single-direction calls"}
+    for (mode, yard), cells in behind.items():
+        p("the new call, groups %s, behind %s by more than 2 %% in %d of %d cells%s" % (mode, names[yard], len(cells), 2 * len(rows), ": " + "; ".join(cells) if cells else ""))
+    wave = 4096
+    for n in sorted({r[0] for r in rows}, reverse=True):
+        for what in ("intersect", "occluded"):
+            cells = [(K * R, v[what][3] <= v[what][0], v[what][4] <= v[what][0]) for nn, K, R, v in rows if nn == n]
+            small, large = [c for c in cells if c[0] <= wave], [c for c in cells if c[0] > wave]
+            p("n %d %s against (b): built ahead in %d of %d cells of at most %d rays in all and in %d of %d beyond; held ahead in %d of %d and %d of %d"
+              % (n, what, sum(c[1] for c in small), len(small), wave, sum(c[1] for c in large), len(large),
+                 sum(c[2] for c in small), len(small), sum(c[2] for c in large), len(large)))
+    p("AUTO's rule (auto_bins_fans: more than MIRT_QUERY_WAVE_RAYS = 4096 rays in all on a scene the fans bin, or every group held) is read off the two lines")
+    p("per scene above: it stands where `built` loses at most 4096 rays and wins beyond, and `held` wins; DESIGN.md section 5.1 states what these rows gave.")
+    p("")
+
+
 # ---- shadow masks: mirt_shadow_mask_device and mirt_direct_light_masked_device beside mirt_direct_light_device ------------------------
 
 MASK_SETS = ((1, 1), (2, 1), (2, 16), (4, 16), (16, 16))      # lights x samples: 1, 2, 32, 64 and 256 positions
@@ -1084,6 +1247,8 @@ def main():
             return child_occfans(int(a.child[1]))
         if a.child[0] == "along":
             return child_along(int(a.child[1]))
+        if a.child[0] == "alongs":
+            return child_alongs(int(a.child[1]), int(a.child[2]))
         if a.child[0] == "mask":
             return child_mask(a.child[1], int(a.child[2]), a.child[3] == "spread")
         return child_throughput() if a.child[0] == "throughput" else child_sweep(int(a.child[1]))
@@ -1114,6 +1279,8 @@ def main():
             step_mask(p)
         if "along" in steps:
             step_along(p)
+        if "alongs" in steps:
+            step_alongs(p)
     finally:
         with open(a.out, "a" if a.append else "w") as f:
             f.write("\n".join(lines) + "\n")
