@@ -11,6 +11,7 @@ INF = np.float32("inf")
 OBLIQUE = np.array([0.37, -0.52, 0.81], np.float32)         # the direction of the rows-offered bound (GPU) and of its CPU forecast
 SHELLS = 8                                                   # along/along.hpp: ALONG_SHELLS
 START_EXTENTS = 8.0                                          # ... ALONG_START_EXTENTS
+PAD_MAX = 0.25                                               # ... ALONG_PAD_MAX
 
 
 def directions():
@@ -44,7 +45,8 @@ def bins_for(n):
 def grid_of(direction, lo, hi, n):
     """The grid across `direction` over the box [lo, hi] for a scene of n triangles (along/along.hpp: along_make_desc): dominant
     axis k of the direction and the two across, c = dir[k1 | k2] / dir[k], and the cell of (p, q) = (S[k1] - c1 S[k], S[k2] - c2 S[k])
-    as ((p - p0) * ip, (q - q0) * iq): B - 2 cells over the box's projection and one of margin on every side."""
+    as ((p - p0) * ip, (q - q0) * iq): B - 2 cells over the box's projection and one of margin on every side.  None where the
+    header makes no descriptor for a finite box and a direction inside the window: `pad` beyond PAD_MAX."""
     d = np.asarray(direction, np.float32)
     k = int(np.argmax(np.abs(d) >= np.abs(d).max()))
     k1, k2 = (k + 1) % 3, (k + 2) % 3
@@ -54,8 +56,13 @@ def grid_of(direction, lo, hi, n):
     p, q = corners[:, k1] - float(c1) * corners[:, k], corners[:, k2] - float(c2) * corners[:, k]
     R = max(np.abs(np.asarray(lo, np.float64)).max(), np.abs(np.asarray(hi, np.float64)).max())
     wp, wq = max(p.max() - p.min(), R * 2.0 ** -10) / (B - 2), max(q.max() - q.min(), R * 2.0 ** -10) / (B - 2)
-    return dict(k=k, k1=k1, k2=k2, c1=c1, c2=c2, B=B, p0=np.float32(p.min() - wp), q0=np.float32(q.min() - wq),
-                ip=np.float32(1.0 / wp), iq=np.float32(1.0 / wq))
+    g = dict(k=k, k1=k1, k2=k2, c1=c1, c2=c2, B=B, p0=np.float32(p.min() - wp), q0=np.float32(q.min() - wq),
+             ip=np.float32(1.0 / wp), iq=np.float32(1.0 / wq))
+    # how far a computed cell coordinate may lie from the exact one, in cells: beyond PAD_MAX the cells are finer than a float
+    # resolves at the scene's distance from the origin, and no grid is made (None) -- "no descriptor"
+    smax = float(np.float32(START_EXTENTS * max(R, 1e-30)))
+    g["pad"] = max(2.0 ** -20 * (float(g["ip"]) * (smax + abs(float(g["p0"]))) + B), 2.0 ** -20 * (float(g["iq"]) * (smax + abs(float(g["q0"]))) + B))
+    return g if g["pad"] <= PAD_MAX else None
 
 
 def cell_of(grid, starts):

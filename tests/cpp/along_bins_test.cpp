@@ -8,12 +8,18 @@
 // 2^-8 rad of it; hit points inside, on and within 2^-20 of edges and vertices, and on and within 2^-20 of cell borders; starts
 // behind, inside and beyond the scene and at the |S| bound (and beyond it: those take no cell); axis-aligned and oblique
 // directions of magnitude 2^-30, 1 and 2^18.
+// All of it once per PLACEMENT (centre C, half-size s): the box, the hit points, the triangles, the start depths and the |S| bound
+// moved to C and scaled by s -- the margins are stated in the operands' magnitudes (|p0|, smax, R), which only a placement moves
+// apart from the scene's size.  The built-in list is tests/placement.py's; `placements cx cy cz s ...` replaces it.  A descriptor that
+// is refused (pad > ALONG_PAD_MAX: cells finer than a float resolves that far from the origin) has its triples counted, not failed
+// -- the library takes the brute-force kernels there --, and each of the three classes has to occur in some placement.
 // With a file of triangles (argv[1]: n x 15 floats) and a direction (argv[2..4]) it also reports how the scene is filed: the
 // every-ray list's length and the mean number of rows a cell offers, both as shares of n.
 #include "../../cpp-raytracer-rasterizer_amd/along/along.hpp"
 
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 using namespace mirt;
@@ -41,15 +47,23 @@ static bool ref_accept(v3 v0, v3 v1, v3 v2, v3 S, v3 dir, float *dist)
     return false;
 }
 
-struct Tally { long triples = 0, accepted = 0, every = 0, cells = 0, out_of_reach = 0, failures = 0; };
+struct Tally { long triples = 0, accepted = 0, every = 0, cells = 0, out_of_reach = 0, refused = 0, failures = 0; };
+struct Placement { double c[3], s; };
 
-static void check_triple(v3 v0, v3 v1, v3 v2, v3 S, v3 dir, int B, Tally &T, const char *what)
+// The scene's box under a placement, as float: [C - s, C + s]^3.
+static void placed_box(const Placement &pl, float *lo, float *hi)
+{
+    for (int c = 0; c < 3; c++) { lo[c] = (float)(pl.c[c] - pl.s); hi[c] = (float)(pl.c[c] + pl.s); }
+}
+
+static void check_triple(const Placement &pl, v3 v0, v3 v1, v3 v2, v3 S, v3 dir, int B, Tally &T, const char *what)
 {
     T.triples++;
     float dist = 0.0f;
     if (!ref_accept(v0, v1, v2, S, dir, &dist)) return;
     T.accepted++;
-    float lo[3] = { -1, -1, -1 }, hi[3] = { 1, 1, 1 };
+    float lo[3], hi[3];
+    placed_box(pl, lo, hi);
     const v3 vs[3] = { v0, v1, v2 };
     for (const v3 &p : vs) {
         lo[0] = fminf(lo[0], p.x); lo[1] = fminf(lo[1], p.y); lo[2] = fminf(lo[2], p.z);
@@ -57,7 +71,7 @@ static void check_triple(v3 v0, v3 v1, v3 v2, v3 S, v3 dir, int B, Tally &T, con
     }
     AlongDesc a;
     const float d3[3] = { dir.x, dir.y, dir.z };
-    if (!along_make_desc(d3, lo, hi, B, ALONG_SHELLS, &a)) { printf("FAIL %s: no descriptor\n", what); T.failures++; return; }
+    if (!along_make_desc(d3, lo, hi, B, ALONG_SHELLS, &a)) { T.refused++; return; }
     if (!along_start_in_reach(a, S)) { T.out_of_reach++; return; }
     const v3 e1 = sub3(v1, v0), e2 = sub3(v2, v0);
     const AlongTri t = along_tri_setup(a, v0, e1, e2, cross3(e1, e2));
@@ -81,9 +95,89 @@ static v3 f3(double x, double y, double z) { return V3((float)x, (float)y, (floa
 static void cross_d(const double *a, const double *b, double *c) { c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0]; }
 static void unit_d(double *a) { const double l = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); for (int c = 0; c < 3; c++) a[c] /= l; }
 
+// The seeded triples of one placement.
+static void run_placement(const Placement &pl, Tally &T)
+{
+    rng_state = 0x9E3779B97F4A7C15ull;                              // every placement draws the same triples, moved
+    const double *C = pl.c, sc = pl.s;
+    float blo[3], bhi[3];
+    placed_box(pl, blo, bhi);
+    double R = 0.0;                                                 // the placed box's extent: smax = ALONG_START_EXTENTS * R unless the triangle sticks out
+    for (int c = 0; c < 3; c++) R = fmax(R, fmax(fabs((double)blo[c]), fabs((double)bhi[c])));
+    const double mags[3] = { ldexp(1.0, -30), 1.0, ldexp(1.0, 18) };
+    const double dirs[7][3] = { { 0, 0, 1 }, { 0, -1, 0 }, { 1, 0, 0 }, { 1, 1, 0 }, { 1, -1, 1 }, { 0.37, -0.52, 0.81 }, { -0.9, 0.05, 0.3 } };
+    const double needle[5] = { 1.0, 1e-2, 1e-3, 1e-4, 1e-5 };
+    const double uv[9][2] = { { 0.3, 0.3 }, { 0, 0.4 }, { 0.4, 0 }, { 0.5, 0.5 }, { 0, 0 }, { 1, 0 }, { 0, 1 }, { 0.999, 0.0005 }, { 0.25, 0.75 } };
+    const int Bs[3] = { 8, 32, 256 };
+    for (int iter = 0; iter < 40000; iter++) {
+        const int di = iter % 7, mi = (iter / 7) % 3, B = Bs[(iter / 21) % 3];
+        double dh[3] = { dirs[di][0], dirs[di][1], dirs[di][2] };
+        unit_d(dh);
+        const v3 dir = f3(dirs[di][0] * mags[mi], dirs[di][1] * mags[mi], dirs[di][2] * mags[mi]);
+        // the hit point P: anywhere in the scene's box, or (every third) on or within 2^-20 of a cell border of the placed box's grid
+        // (the draws are made whether or not the box has a grid, so that every placement sees the same triples)
+        double P[3] = { C[0] + sc * uni(-0.9, 0.9), C[1] + sc * uni(-0.9, 0.9), C[2] + sc * uni(-0.9, 0.9) };
+        if (iter % 3 == 0) {
+            AlongDesc a;
+            const float d3[3] = { dir.x, dir.y, dir.z };
+            const int border = 1 + (int)(rnd() % (unsigned)(B - 1));
+            const int steps = (int)(rnd() % 5) - 2;
+            if (along_make_desc(d3, blo, bhi, B, ALONG_SHELLS, &a)) {
+                const double off = (double)steps * ldexp(1.0, -20) / (double)a.ip;
+                const double p = (double)a.p0 + border / (double)a.ip + off;
+                P[a.k1] = p + (double)a.c1 * P[a.k];                // p(P) = P[k1] - c1 P[k]
+            } else if (C[0] == 0.0 && C[1] == 0.0 && C[2] == 0.0) {
+                printf("FAIL: no descriptor for a box around the origin\n");
+                T.failures++;
+                return;
+            }
+        }
+        // the triangle around P: e1 anywhere, e2 across it (a needle when squeezed) or in the plane of e1 and dir (edge-on), tilted
+        double e1[3] = { sc * uni(-0.3, 0.3), sc * uni(-0.3, 0.3), sc * uni(-0.3, 0.3) }, e2[3];
+        const int shape = (iter / 63) % 8;
+        if (shape < 5) {
+            double r[3] = { uni(-1, 1), uni(-1, 1), uni(-1, 1) }, w[3];
+            cross_d(e1, r, w);
+            unit_d(w);
+            const double l1 = sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]), k = uni(0.2, 0.9);
+            for (int c = 0; c < 3; c++) e2[c] = k * e1[c] + w[c] * l1 * needle[shape];
+        } else {
+            double nperp[3];
+            cross_d(e1, dh, nperp);
+            unit_d(nperp);
+            const double theta = shape == 5 ? 0.0 : ldexp(1.0, -(int)(8 + rnd() % 17)) * (shape == 6 ? 1.0 : -1.0);
+            const double a1 = uni(-0.5, 0.5), bd = sc * uni(0.1, 0.3);
+            for (int c = 0; c < 3; c++) e2[c] = a1 * e1[c] + bd * dh[c] + theta * bd * nperp[c];
+        }
+        for (int ui = 0; ui < 9; ui++) {
+            const double eps = (double)((int)(rnd() % 3) - 1) * ldexp(1.0, -20);
+            const double u = uv[ui][0] + eps, v = uv[ui][1] + (ui & 1 ? eps : -eps);
+            double v0[3];
+            for (int c = 0; c < 3; c++) v0[c] = P[c] - u * e1[c] - v * e2[c];
+            const v3 V0 = f3(v0[0], v0[1], v0[2]), V1 = f3(v0[0] + e1[0], v0[1] + e1[1], v0[2] + e1[2]), V2 = f3(v0[0] + e2[0], v0[1] + e2[1], v0[2] + e2[2]);
+            // starts along -dir from P: beyond the hit (negative), at it, just in front, inside the scene, outside, at the |S| bound, past it
+            // -- in units of the scene's size, the last in units of its extent R (30 R is past smax = 8 R wherever the scene lies)
+            const double depth[8] = { -0.5 * sc, 0.0, ldexp(sc, -18), 0.4 * sc, 2.5 * sc, 6.0 * sc, 0.0, 30.0 * R };
+            for (int si = 0; si < 8; si++) {
+                double S[3];
+                for (int c = 0; c < 3; c++) S[c] = P[c] - dh[c] * depth[si];
+                if (si == 6) {                                     // at the bound: slide along dir until dir's dominant component is at smax (the box is the placed box unless the triangle sticks out)
+                    double m = 0.0;
+                    int cm = 0;
+                    for (int c = 0; c < 3; c++) if (fabs(dh[c]) > m) { m = fabs(dh[c]); cm = c; }
+                    const double s = (dh[cm] > 0 ? -1.0 : 1.0) * ALONG_START_EXTENTS * R, step = (s - P[cm]) / dh[cm];
+                    for (int c = 0; c < 3; c++) S[c] = P[c] + dh[c] * step;
+                }
+                check_triple(pl, V0, V1, V2, f3(S[0], S[1], S[2]), dir, B, T, "triple");
+            }
+        }
+    }
+}
+
 int main(int argc, char **argv)
 {
-    if (argc >= 5) {
+    const bool listed = argc >= 2 && std::string(argv[1]) == "placements";
+    if (argc >= 5 && !listed) {
         // how a scene is filed under a direction
         FILE *fp = fopen(argv[1], "rb");
         if (!fp) return 2;
@@ -109,76 +203,37 @@ int main(int argc, char **argv)
         }
         // a ray is offered its cell's rows and the every-ray list: the mean over the grid's cells, as a share of n
         const double offered = ((double)pairs / ((double)a.B * a.B) + (double)every) / (double)n;
-        printf("n %d B %d every %ld every_share %.6f offered_share %.6f\nok\n", n, a.B, every, (double)every / n, offered);
+        printf("n %d B %d every %ld every_share %.6f offered_share %.6f every_cap %d pad %.6f\nok\n", n, a.B, every, (double)every / n, offered,
+               along_every_cap(n), a.pad);
         return 0;
     }
 
-    Tally T;
-    const double mags[3] = { ldexp(1.0, -30), 1.0, ldexp(1.0, 18) };
-    const double dirs[7][3] = { { 0, 0, 1 }, { 0, -1, 0 }, { 1, 0, 0 }, { 1, 1, 0 }, { 1, -1, 1 }, { 0.37, -0.52, 0.81 }, { -0.9, 0.05, 0.3 } };
-    const double needle[5] = { 1.0, 1e-2, 1e-3, 1e-4, 1e-5 };
-    const double uv[9][2] = { { 0.3, 0.3 }, { 0, 0.4 }, { 0.4, 0 }, { 0.5, 0.5 }, { 0, 0 }, { 1, 0 }, { 0, 1 }, { 0.999, 0.0005 }, { 0.25, 0.75 } };
-    const int Bs[3] = { 8, 32, 256 };
-    for (int iter = 0; iter < 40000; iter++) {
-        const int di = iter % 7, mi = (iter / 7) % 3, B = Bs[(iter / 21) % 3];
-        double dh[3] = { dirs[di][0], dirs[di][1], dirs[di][2] };
-        unit_d(dh);
-        const v3 dir = f3(dirs[di][0] * mags[mi], dirs[di][1] * mags[mi], dirs[di][2] * mags[mi]);
-        // the hit point P: anywhere in the scene's box, or (every third) on or within 2^-20 of a cell border of the unit box's grid
-        double P[3] = { uni(-0.9, 0.9), uni(-0.9, 0.9), uni(-0.9, 0.9) };
-        if (iter % 3 == 0) {
-            float lo[3] = { -1, -1, -1 }, hi[3] = { 1, 1, 1 };
-            AlongDesc a;
-            const float d3[3] = { dir.x, dir.y, dir.z };
-            if (!along_make_desc(d3, lo, hi, B, ALONG_SHELLS, &a)) { printf("FAIL: no descriptor for the unit box\n"); return 1; }
-            const int border = 1 + (int)(rnd() % (unsigned)(B - 1));
-            const double off = (double)((int)(rnd() % 5) - 2) * ldexp(1.0, -20) / (double)a.ip;
-            const double p = (double)a.p0 + border / (double)a.ip + off;
-            P[a.k1] = p + (double)a.c1 * P[a.k];                    // p(P) = P[k1] - c1 P[k]
-        }
-        // the triangle around P: e1 anywhere, e2 across it (a needle when squeezed) or in the plane of e1 and dir (edge-on), tilted
-        double e1[3] = { uni(-0.3, 0.3), uni(-0.3, 0.3), uni(-0.3, 0.3) }, e2[3];
-        const int shape = (iter / 63) % 8;
-        if (shape < 5) {
-            double r[3] = { uni(-1, 1), uni(-1, 1), uni(-1, 1) }, w[3];
-            cross_d(e1, r, w);
-            unit_d(w);
-            const double l1 = sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]), k = uni(0.2, 0.9);
-            for (int c = 0; c < 3; c++) e2[c] = k * e1[c] + w[c] * l1 * needle[shape];
-        } else {
-            double nperp[3];
-            cross_d(e1, dh, nperp);
-            unit_d(nperp);
-            const double theta = shape == 5 ? 0.0 : ldexp(1.0, -(int)(8 + rnd() % 17)) * (shape == 6 ? 1.0 : -1.0);
-            const double a1 = uni(-0.5, 0.5), bd = uni(0.1, 0.3);
-            for (int c = 0; c < 3; c++) e2[c] = a1 * e1[c] + bd * dh[c] + theta * bd * nperp[c];
-        }
-        for (int ui = 0; ui < 9; ui++) {
-            const double eps = (double)((int)(rnd() % 3) - 1) * ldexp(1.0, -20);
-            const double u = uv[ui][0] + eps, v = uv[ui][1] + (ui & 1 ? eps : -eps);
-            double v0[3];
-            for (int c = 0; c < 3; c++) v0[c] = P[c] - u * e1[c] - v * e2[c];
-            const v3 V0 = f3(v0[0], v0[1], v0[2]), V1 = f3(v0[0] + e1[0], v0[1] + e1[1], v0[2] + e1[2]), V2 = f3(v0[0] + e2[0], v0[1] + e2[1], v0[2] + e2[2]);
-            // starts along -dir from P: beyond the hit (negative), at it, just in front, inside the scene, outside, at the |S| bound, past it
-            const double depth[8] = { -0.5, 0.0, ldexp(1.0, -18), 0.4, 2.5, 6.0, 0.0, 30.0 };
-            for (int si = 0; si < 8; si++) {
-                double S[3];
-                for (int c = 0; c < 3; c++) S[c] = P[c] - dh[c] * depth[si];
-                if (si == 6) {                                     // at the bound: slide along dir until the largest |component| is smax (the box is the unit box unless the triangle sticks out)
-                    double m = 0.0;
-                    int cm = 0;
-                    for (int c = 0; c < 3; c++) if (fabs(dh[c]) > m) { m = fabs(dh[c]); cm = c; }
-                    const double s = (dh[cm] > 0 ? -1.0 : 1.0) * 8.0, step = (s - P[cm]) / dh[cm];
-                    for (int c = 0; c < 3; c++) S[c] = P[c] + dh[c] * step;
-                }
-                check_triple(V0, V1, V2, f3(S[0], S[1], S[2]), dir, B, T, "triple");
-            }
-        }
+    // the placements: tests/placement.py's list, or the caller's
+    std::vector<Placement> places = { { { 0, 0, 0 }, 1.0 }, { { 3, 0, 0 }, 1.0 }, { { 10, -7, 5 }, 1.0 }, { { 300, 200, -100 }, 1.0 }, { { 1000, 1000, 1000 }, 1.0 },
+                                      { { 0, 0, 0 }, 1024.0 }, { { 0, 0, 0 }, 1.0 / 1024.0 }, { { 40, -25, 60 }, 1.0 / 1024.0 }, { { 10, -7, 5 }, 1.0 / 1024.0 },
+                                      { { 0, 0, 4096 }, 1.0 } };
+    if (argc >= 2) {
+        if (!listed || (argc - 2) % 4 != 0 || argc < 6) { printf("usage: %s [placements cx cy cz s ...] | [scene.f32 dx dy dz]\n", argv[0]); return 2; }
+        places.clear();
+        for (int i = 2; i + 3 < argc; i += 4) places.push_back({ { atof(argv[i]), atof(argv[i + 1]), atof(argv[i + 2]) }, atof(argv[i + 3]) });
     }
-    printf("triples %ld accepted %ld filed in cells %ld on the every-ray list %ld out of reach %ld failures %ld\n", T.triples, T.accepted, T.cells, T.every,
-           T.out_of_reach, T.failures);
+    Tally T;
+    int with_cells = 0, with_every = 0, with_refused = 0;
+    for (const Placement &pl : places) {
+        Tally Tp;
+        run_placement(pl, Tp);
+        printf("placement (%g, %g, %g) x %g: triples %ld accepted %ld filed in cells %ld on the every-ray list %ld out of reach %ld refused %ld failures %ld\n",
+               pl.c[0], pl.c[1], pl.c[2], pl.s, Tp.triples, Tp.accepted, Tp.cells, Tp.every, Tp.out_of_reach, Tp.refused, Tp.failures);
+        with_cells += Tp.cells > 0; with_every += Tp.every > 0; with_refused += Tp.refused > 0;
+        T.triples += Tp.triples; T.accepted += Tp.accepted; T.cells += Tp.cells; T.every += Tp.every; T.out_of_reach += Tp.out_of_reach;
+        T.refused += Tp.refused; T.failures += Tp.failures;
+    }
+    printf("triples %ld accepted %ld filed in cells %ld on the every-ray list %ld out of reach %ld refused %ld failures %ld\n", T.triples, T.accepted, T.cells,
+           T.every, T.out_of_reach, T.refused, T.failures);
+    printf("placements %d with filed %d with every-ray %d with refused %d\n", (int)places.size(), with_cells, with_every, with_refused);
     // the test must not pass vacuously: each class has to occur
     if (T.accepted < 100000 || T.cells < 50000 || T.every < 1000 || T.out_of_reach < 100) { printf("FAIL: too few cases\n"); return 1; }
+    if (!with_cells || !with_every || !with_refused) { printf("FAIL: a class (filed, every-ray, refused) occurs in no placement\n"); return 1; }
     if (T.failures) return 1;
     printf("ok\n");
     return 0;

@@ -22,6 +22,7 @@ EDGE, VERTEX, BORDER = 0, 1, 2
 
 INSIDE = np.array([0.125, -0.0625, 0.1875], np.float32)            # the inside origin of test_gpu_fan_query.py
 OUTSIDE = np.array([2.5, 0.75, -1.5], np.float32)
+FAR = np.array([300.0, 200.0, -100.0])                             # the "@ far" scenes' offset (placement.py: 300_200_-100): one ulp is about 2^-15 there
 
 PROBE_DTYPE = np.dtype([("dir", np.float32, 3), ("point", np.float64, 3), ("target", np.int32), ("kind", np.int8), ("delta", np.int8),
                         ("inside", np.bool_), ("face", np.int8), ("i", np.int16), ("j", np.int16)])
@@ -77,6 +78,14 @@ def scene_of(oracle, name):
             v = oracle.soup(41, 2000, 0.2)[:150].copy(), None, 4, 1.0
         elif name == "soup2000":
             v = oracle.soup(41, 2000, 0.2), range(150), 4, 1.0
+        elif name == "shell @ far":
+            v = finish(shell_vertices(5, np.random.default_rng(3), origin=INSIDE + FAR)), None, 4, 1.0
+        elif name == "needles @ far":
+            v = finish(shell_vertices(5, np.random.default_rng(4), needles=True, origin=INSIDE + FAR)), None, 4, 1.0
+        elif name == "soup2000 @ far":                              # placement.place's arithmetic: one rounding a coordinate
+            t = oracle.soup(41, 2000, 0.2)
+            t[:, 0:9] = (t[:, 0:9].astype(np.float64).reshape(-1, 3) + FAR).reshape(-1, 9)
+            v = t, range(150), 4, 1.0
         elif name == "shell x 3e-4":
             v = scene_shell(3e-4), None, 4, 3e-4
         elif name == "shell x 3e5":
@@ -313,15 +322,22 @@ def scene_grazing(origin=INSIDE):
     return finish(out)
 
 
-def origins_of(tris, scale=1.0):
-    """Inside the scene, outside its box, and exactly on a vertex of triangle 0."""
-    return {"inside": (INSIDE.astype(np.float64) * scale).astype(np.float32), "outside": (OUTSIDE.astype(np.float64) * scale).astype(np.float32),
+def offset_of(name):
+    """Where the scene `name` of scene_of lies: FAR for the "@ far" scenes, the world origin for the others."""
+    return FAR if name.endswith("@ far") else np.zeros(3)
+
+
+def origins_of(tris, scale=1.0, offset=(0.0, 0.0, 0.0)):
+    """Inside the scene, outside its box, and exactly on a vertex of triangle 0; `offset`: where the scene lies (offset_of)."""
+    off = np.asarray(offset, np.float64)
+    return {"inside": (INSIDE.astype(np.float64) * scale + off).astype(np.float32), "outside": (OUTSIDE.astype(np.float64) * scale + off).astype(np.float32),
             "vertex": np.array(tris[0, 0:3], np.float32)}
 
 
-def with_receivers(tris, scale=1.0):
+def with_receivers(tris, scale=1.0, offset=(0.0, 0.0, 0.0)):
     """The scene plus six small far triangles whose normals are the six axis directions: what a DirectLight record names as its
-    surface, so that some normal faces the light wherever the record lies.  Returns (scene, index of the first receiver)."""
+    surface, so that some normal faces the light wherever the record lies.  Returns (scene, index of the first receiver).
+    `offset`: where the scene lies (offset_of) -- the receivers surround it there."""
     v = []
     for k in range(3):
         for sgn in (1.0, -1.0):
@@ -330,7 +346,7 @@ def with_receivers(tris, scale=1.0):
             a[(k + 1) % 3], b[(k + 2) % 3] = 1e-3, 1e-3
             base = 40.0 * n
             v.append([base, base + (b if sgn > 0 else a), base + (a if sgn > 0 else b)])
-    rec = finish(v, scale)
+    rec = finish(np.asarray(v, np.float64) * scale + np.asarray(offset, np.float64))
     want = np.repeat(np.eye(3), 2, axis=0) * np.tile([1.0, -1.0], 3)[:, None]
     assert np.allclose(rec[:, 9:12], want), rec[:, 9:12]
     return np.concatenate([np.asarray(tris, np.float32).reshape(-1, 15), rec]), len(tris)
@@ -352,6 +368,18 @@ def shadow_records(p, light, first_receiver, hit_dtype):
     rec["index"] = first_receiver + 2 * ax + (to_light[np.arange(len(p)), ax] < 0)
     rec["distance"] = 1.0
     return rec
+
+
+def resolved(p, rec, light, name):
+    """The probes and records without those whose float32 position IS the light: a delta below what a position resolves.  At the
+    world origin there is none; at FAR (an ulp of a position is 2^-15 of the scene) there are the two 2^-20 twins of the light's own
+    vertex, seen from that vertex.  Such a record is DirectLight's 0 / 0 -- no shadow ray, by design a sweep -- and no probe."""
+    at_light = (rec["position"] == np.asarray(light, np.float32)).all(axis=1)
+    if name.endswith("@ far"):
+        assert at_light.sum() <= 2 and (p["kind"][at_light] == VERTEX).all() and (p["delta"][at_light] == 0).all(), (name, int(at_light.sum()))
+    else:
+        assert not at_light.any(), (name, int(at_light.sum()))
+    return p[~at_light], rec[~at_light]
 
 
 # ---- camera tile-corner slivers ------------------------------------------------------------------------------------------------------

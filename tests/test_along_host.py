@@ -29,8 +29,18 @@ def bins_test(tmp_path_factory):
 
 
 def test_accepted_starts_find_their_triangle(bins_test):
-    r = subprocess.run([bins_test], capture_output=True, text=True, timeout=120)
+    """The seeded triples once per placement of placement.PLACEMENTS: no predicate failure anywhere, and filed, every-ray and
+    refused triples each occur in some placement."""
+    import placement as pl
+    args = ["placements"] + ["%.17g" % x for T, s in pl.PLACEMENTS.values() for x in tuple(T) + (s,)]
+    r = subprocess.run([bins_test] + args, capture_output=True, text=True, timeout=300)
+    print(r.stdout)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
+    m = re.search(r"placements (\d+) with filed (\d+) with every-ray (\d+) with refused (\d+)", r.stdout)
+    assert int(m.group(1)) == len(pl.PLACEMENTS) and min(int(m.group(k)) for k in (2, 3, 4)) >= 1, r.stdout
+    assert " failures 0\n" in r.stdout and r.stdout.count("placement (") == len(pl.PLACEMENTS)
+    # the built-in list is the same one
+    assert subprocess.run([bins_test], capture_output=True, text=True, timeout=300).stdout == r.stdout
 
 
 def test_soup2000_leaves_the_rows_offered_bound_room(bins_test, tmp_path):
@@ -45,6 +55,72 @@ def test_soup2000_leaves_the_rows_offered_bound_room(bins_test, tmp_path):
     assert n == 2000 and B == 32
     assert offered < OFFERED_CAP / 2, "a ray is offered %.4f of the scene: no room under the GPU test's bound" % offered
     assert every <= n // 100, "%d triangles on the every-ray list" % every
+
+
+def test_placed_scenes_are_filed_as_the_class_table_says(bins_test, tmp_path):
+    """placement.ALONG_CLASS entry by entry, from the header alone: the tool's scene-file mode on the placed suite scenes -- a
+    descriptor or none; the every-ray list within along_every_cap(n) or beyond it.  along_helpers.grid_of agrees about "no
+    descriptor".  Prints the every-ray shares (README, DESIGN 5.1 quote them)."""
+    import placement as pl
+    from along_helpers import grid_of
+    seen = set()
+    for scene in pl.ALONG_CLASS:
+        for pname, (T, s) in pl.PLACEMENTS.items():
+            tris = pl.placed_scene(scene, pname)
+            path = str(tmp_path / "placed.f32")
+            np.ascontiguousarray(tris, np.float32).tofile(path)
+            v = tris[:, :9].reshape(-1, 3)
+            lo, hi = v.min(axis=0), v.max(axis=0)
+            line = []
+            for dname, d in pl.ALONG_DIRS.items():
+                want = pl.along_class(scene, pname, dname)
+                d = pl.place_dirs(d, s)
+                r = subprocess.run([bins_test, path] + ["%.9g" % x for x in d], capture_output=True, text=True, timeout=120)
+                what = "%s at %s along %s" % (scene, pname, dname)
+                grid = grid_of(d, lo, hi, len(tris))
+                if want == "no_grid":
+                    assert r.returncode == 1 and r.stdout.strip() == "no descriptor", (what, r.stdout + r.stderr)
+                    assert grid is None, what
+                    line.append("none")
+                else:
+                    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (what, r.stdout + r.stderr)
+                    m = re.search(r"n (\d+) B (\d+) every (\d+) every_share ([\d.]+) offered_share [\d.]+ every_cap (\d+) pad ([\d.]+)", r.stdout)
+                    n, B, every, cap, pad = int(m.group(1)), int(m.group(2)), int(m.group(3)), int(m.group(5)), float(m.group(6))
+                    assert n == len(tris) and cap == max(n // 8, 64) and B == (256 if scene == "soup33000" else 32), (what, r.stdout)
+                    assert (every > cap) == (want == "gave_up"), "%s: %d of %d on the every-ray list, cap %d, but %s" % (what, every, n, cap, want)
+                    assert grid is not None and grid["B"] == B and abs(grid["pad"] - pad) <= 1e-6 + 1e-4 * pad, (what, grid, pad)
+                    line.append("%.3f%s" % (float(m.group(4)), "!" if want == "gave_up" else ""))
+                seen.add(want)
+            print("%-17s %-18s every-ray share along %s: %s" % (scene, pname, ", ".join(pl.ALONG_DIRS), "  ".join(line)))
+    assert seen == {"binned", "gave_up", "no_grid"}, seen
+    # the unit control is binned everywhere, and a pure scaling moves nothing
+    for scene, rows in pl.ALONG_CLASS.items():
+        assert rows["unit"] == rows["origin_x1024"] == rows["origin_div1024"] == ("binned",) * len(pl.ALONG_DIRS), scene
+
+
+@pytest.mark.parametrize("name,targets,d,every_ray", [("soup2000 @ far", range(24), OBLIQUE, 50), ("needles @ far", range(0, 150, 6), [-0.6, 1.0, 0.35], 149)])
+def test_far_probe_scenes(oracle, bins_test, tmp_path, name, targets, d, every_ray):
+    """What test_gpu_along.py::test_silhouette_probes asks of its "@ far" scenes, from the header and the oracle alone: how the scene
+    is filed (the soup binned, the needles beyond along_every_cap), and starts that take cells and hit."""
+    import silhouette
+    from along_helpers import cell_of, grid_of, silhouette_starts
+    from query_helpers import oracle_intersect
+    d = np.asarray(d, np.float32)
+    tris = silhouette.scene_of(oracle, name)[0]
+    path = str(tmp_path / "far.f32")
+    np.ascontiguousarray(tris, np.float32).tofile(path)
+    r = subprocess.run([bins_test, path] + ["%.9g" % x for x in d], capture_output=True, text=True, timeout=120)
+    m = re.search(r"n (\d+) B (\d+) every (\d+) every_share [\d.]+ offered_share [\d.]+ every_cap (\d+)", r.stdout)
+    print(r.stdout)
+    assert int(m.group(3)) == every_ray and (every_ray > int(m.group(4))) == (name == "needles @ far"), r.stdout
+    v = tris[:, :9].reshape(-1, 3)
+    grid = grid_of(d, v.min(axis=0), v.max(axis=0), len(tris))
+    starts = silhouette_starts(tris, d, targets, grid)
+    i, j = cell_of(grid, starts)
+    assert 500 < len(starts) < 9000 and (i >= 0).mean() > 0.9 and len(np.unique(i * grid["B"] + j)) > 10
+    assert 0.2 < (oracle_intersect(oracle, tris, mirt.make_rays(starts, d))["index"] >= 0).mean() < 1.0
+    # the scene's extent over its size: an ulp of a start against the smallest delta
+    assert np.abs(v).max() / (v.max(axis=0) - v.min(axis=0)).max() > 30
 
 
 def test_symbols():

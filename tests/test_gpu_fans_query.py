@@ -465,12 +465,12 @@ def test_frames_in_flight(in_flight):
 
 # ---- 9. silhouettes and bin borders, three origins in one call ----------------------------------------------------------------------
 
-@pytest.mark.parametrize("name", ["shell", "walls", "soup150"])
+@pytest.mark.parametrize("name", ["shell", "walls", "soup150", "shell @ far", "needles @ far"])
 def test_silhouette_probes_from_three_origins(oracle, name):
     import silhouette as sil
     tris, targets, crossings, scale = sil.scene_of(oracle, name)
     mirt.scene_upload(tris)
-    named = sil.origins_of(tris, scale)
+    named = sil.origins_of(tris, scale, sil.offset_of(name))
     origins = np.ascontiguousarray(np.array(list(named.values()), np.float32))
     p = [sil.probes(tris, O, targets, crossings) for O in origins]
     assert all(len(q) > 3000 for q in p)

@@ -32,7 +32,7 @@ def inside_case(oracle, name):
     key = ("inside", name)
     if key not in _cache:
         tris, targets, crossings, scale = sil.scene_of(oracle, name)
-        O = sil.origins_of(tris, scale)["inside"]
+        O = sil.origins_of(tris, scale, sil.offset_of(name))["inside"]
         p = sil.probes(tris, O, targets, crossings)
         idx = sil.oracle_index(oracle, tris, O, p["dir"])
         idx.setflags(write=False)
@@ -40,7 +40,7 @@ def inside_case(oracle, name):
     return _cache[key]
 
 
-@pytest.mark.parametrize("name", ["shell", "needles", "soup150", "grazing", "walls", "tips"])
+@pytest.mark.parametrize("name", ["shell", "needles", "soup150", "grazing", "walls", "tips", "shell @ far", "needles @ far"])
 def test_probes_reach_and_straddle_their_targets(oracle, name):
     tris, O, p, idx = inside_case(oracle, name)
     s = sil.shares(p, idx)
@@ -51,7 +51,7 @@ def test_probes_reach_and_straddle_their_targets(oracle, name):
     for kind in (sil.EDGE, sil.VERTEX, sil.BORDER):
         assert (p["kind"] == kind).sum() >= 300, (name, kind)
     assert set(p["face"].tolist()) == set(range(6))
-    if name in ("shell", "needles", "soup150", "tips"):
+    if name in ("shell", "needles", "soup150", "tips", "shell @ far", "needles @ far"):
         assert s["all"] >= 1.0 / 3.0, s
     if name == "tips":
         # the tips reach into a bin of their own, and rays into them are accepted
@@ -127,6 +127,26 @@ def test_shadow_records_lie_behind_their_probe(oracle):
     # (DirectLight normalises its own direction, so a probe within an ulp of a silhouette may fall to the other side)
     assert (lit == (idx[some] < 0)).mean() >= 0.9, (lit.mean(), (idx[some] < 0).mean())
     assert 0.25 <= lit.mean() <= 0.75
+
+
+@pytest.mark.parametrize("name", ["shell", "needles", "shell @ far", "needles @ far"])
+def test_shadow_records_a_position_resolves(oracle, name):
+    """sil.resolved: at the world origin no record's float32 position is the light; at the far offset exactly the two 2^-20 twins
+    of the light's own vertex are, and the oracle's DirectLight of every record that stays is finite."""
+    from mirt import HIT_DTYPE
+    tris, targets, crossings, scale = sil.scene_of(oracle, name)
+    scene, first = sil.with_receivers(tris, scale, sil.offset_of(name))
+    dropped = {}
+    for oname, L in sil.origins_of(tris, scale, sil.offset_of(name)).items():
+        p = sil.probes(tris, L, targets, crossings)
+        rec = sil.shadow_records(p, L, first, HIT_DTYPE)
+        assert rec["index"].min() >= first and ((scene[rec["index"], 9:12] * (L.astype(np.float64) - rec["position"])).sum(axis=1) >= 0).all()
+        q, kept = sil.resolved(p, rec, L, name)
+        dropped[oname] = len(p) - len(q)
+        lights = np.array([[L[0], L[1], L[2], 1, 1, 1, 14]], np.float32)
+        near = np.argsort(np.linalg.norm(kept["position"].astype(np.float64) - L, axis=1))[:32]            # the records nearest the light
+        assert all(np.isfinite(oracle.direct_light(scene, kept["position"][k], 1.0, int(kept["index"][k]), lights)).all() for k in near), (name, oname)
+    assert dropped == {"inside": 0, "outside": 0, "vertex": 2 if name.endswith("@ far") else 0}, dropped
 
 
 @pytest.mark.parametrize("yaw", [0.0, 0.3])
