@@ -17,6 +17,7 @@
 #include "../query/rt_query.hpp"
 #include "../along/along.hpp"
 #include "../along/alongs.hpp"
+#include "../grid/ray_grid.hpp"
 #include "../lights/many_lights.hpp"
 #include "../lights/aa_many_lights.hpp"
 #include "cube_plan.hpp"
@@ -374,6 +375,37 @@ struct AlongsBuild {
     void release();
 };
 
+// The structure of the arbitrary-ray grid (ray_grid.cpp; ../grid/ray_grid.hpp): cells, plane index and every-ray list behind one
+// offset table, kept per scene version as the along grid is -- shared by the streams, ordered among them by events, released in
+// mirt_shutdown, forgotten with the scene through the version it is held under.  The build's pair list and sort scratch are its own
+// (d_entries, the sort's output, stays: it is the triangle of every row).
+struct RayGridCache {
+    bool valid = false;
+    uint64_t version = 0;                        // what the structure was built for: the scene version and the triangle count
+    int n = 0;
+    bool gave_up = false;                        // the every-ray list outgrew its share: calls for this scene sweep
+    GridDesc desc = {};
+    uint32_t *d_off = nullptr;                   // desc.nkeys + 1
+    uint32_t cap_keys = 0;
+    QueryRow *d_rows = nullptr;                  // the rows in key order (at least one: a lane with no row left loads row 0)
+    uint32_t cap_rows = 0, nrows = 0, nplane = 0, nevery = 0;    // rows in all, of the plane index, triangles on the every-ray list
+    uint32_t *d_counters = nullptr;              // [0] pairs, [1] triangles on the every-ray list, [2] pairs of the plane index
+    uint32_t *d_keys = nullptr, *d_vals = nullptr, *d_tmp_keys = nullptr, *d_tmp_vals = nullptr, *d_entries = nullptr;
+    uint32_t cap_pairs = 0;
+    uint32_t *d_bucket = nullptr;                // bucket sort: counts | bases (+1) | cursors, cap_buckets each
+    uint32_t cap_buckets = 0;
+    unsigned long long *d_stats[MAX_FLIGHT] = {};    // GSTAT_WORDS counters of each stream's last walk (profiling on)
+
+    bool holds(uint64_t v, int count) const { return valid && version == v && n == count; }
+    void release();
+};
+// The last call answered under mirt_set_ray_grid(1): how, on which stream, and where its kernel's counters are (read once).
+struct RayGridStats {
+    mirt_ray_grid_stats s = {};
+    hipStream_t stream = nullptr;
+    const unsigned long long *dev = nullptr;
+};
+
 // The ray-independent rows of ClosestIntersection (k_query_rows): built once per scene version on the stream of the query that
 // finds them missing, shared by every stream; a query on another stream waits for ev_built, not for the device.
 struct QueryRows {
@@ -420,6 +452,8 @@ struct QueryRows {
     // nothing and neither family evicts the other's structure.
     AlongsGroup alongs[ALONGS_GROUPS];
     AlongsBuild alongs_build;
+    // The arbitrary-ray grid (mirt_set_ray_grid): one per scene version.
+    RayGridCache grid;
 
     void release();                              // (the cubes' tables too)
 };
@@ -502,6 +536,8 @@ struct Ctx {
     LightCache lc;
     QueryRows qrows;
     int query_mode = MIRT_QUERY_AUTO;            // mirt_set_query_mode
+    int ray_grid = 0;                            // mirt_set_ray_grid: mirt_intersect* / mirt_occluded* answer through g.qrows.grid
+    RayGridStats grid_stats;                     // the last such call (mirt_get_ray_grid_stats)
     QueryStats qstats[QUERY_KINDS];              // the last DirectLight query, the last origin fan, the last occlusion query, the last shadow mask
     unsigned long long *d_hits = nullptr;        // the hit-counter buffer of the current ray-traced frame (one of its stream's d_hits)
     bool scene_finite = true;                    // all vertex coordinates below MIRT_SAFE_MAG
@@ -750,6 +786,11 @@ int along_occluded_host(const float *dir, const float *origins3, int nrays, cons
 // What alongs.cpp shares with along.cpp: the start of a build under the streams' protocol, and its end.
 int along_build_begin();
 int along_build_end();
+
+// ---- arbitrary rays through the cell grid (ray_grid.cpp; the kernels: ../grid/ray_grid.hip) ----
+// With the switch on, on the stream the call has taken: *done says the walk kernel was queued; otherwise the caller sweeps.
+int ray_grid_intersect(const void *d_rays, int nrays, void *d_hits, bool *done);
+int ray_grid_occluded(const void *d_rays, int nrays, const void *d_max_distance, void *d_occluded, bool *done);
 
 // ---- ray queries along several directions in one call (alongs.cpp; the kernels: ../along/alongs.hip) ----
 int alongs_intersect(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, void *d_hits);

@@ -118,6 +118,10 @@ int query_intersect(const void *d_rays, int nrays, void *d_hits)
     if (nrays == 0) return MIRT_OK;
     if ((rc = query_need_scene())) return rc;
     stream_begin();
+    if (g.ray_grid) {                                        // mirt_set_ray_grid: through the cell grid whenever it can be built
+        bool done = false;
+        if ((rc = ray_grid_intersect(d_rays, nrays, d_hits, &done)) || done) return rc;
+    }
     return intersect_launch(d_rays, nrays, d_hits);
 }
 
@@ -727,6 +731,10 @@ int query_occluded(const void *d_rays, int nrays, const void *d_max_distance, vo
     if (nrays == 0) return MIRT_OK;
     if ((rc = query_need_scene())) return rc;
     stream_begin();
+    if (g.ray_grid) {                                        // (a call the grid answers is reported by mirt_get_ray_grid_stats alone:
+        bool done = false;                                   //  the occlusion statistics keep the last call that swept or walked a cube)
+        if ((rc = ray_grid_occluded(d_rays, nrays, d_max_distance, d_occluded, &done)) || done) return rc;
+    }
     stats_begin(QUERY_OCCLUDED, false);
     return occluded_launch(d_rays, nrays, d_max_distance, d_occluded);
 }

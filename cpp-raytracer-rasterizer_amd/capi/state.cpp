@@ -160,6 +160,7 @@ void QueryRows::release()
     along.release();
     for (AlongsGroup &a : alongs) a.release();
     alongs_build.release();
+    grid.release();
     *this = QueryRows();
 }
 
@@ -167,6 +168,13 @@ void AlongCache::release()
 {
     dev_free({ d_off, d_rows, d_aux, d_near, d_counters, d_keys, d_vals, d_tmp_keys, d_tmp_vals, d_entries, d_bucket });
     *this = AlongCache();
+}
+
+void RayGridCache::release()
+{
+    dev_free({ d_off, d_rows, d_counters, d_keys, d_vals, d_tmp_keys, d_tmp_vals, d_entries, d_bucket });
+    for (unsigned long long *p : d_stats) dev_free({ p });
+    *this = RayGridCache();
 }
 
 void AlongsGroup::release()

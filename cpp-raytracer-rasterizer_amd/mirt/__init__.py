@@ -33,6 +33,7 @@ EXPORTS = (
     "mirt_occluded", "mirt_occluded_device", "mirt_occluded_fans", "mirt_occluded_fans_device", "mirt_get_occlusion_stats",
     "mirt_intersect_along", "mirt_intersect_along_device", "mirt_occluded_along", "mirt_occluded_along_device", "mirt_get_along_stats",
     "mirt_intersect_alongs", "mirt_intersect_alongs_device", "mirt_occluded_alongs", "mirt_occluded_alongs_device",
+    "mirt_set_ray_grid", "mirt_get_ray_grid_stats",
     "mirt_shadow_mask", "mirt_shadow_mask_device", "mirt_direct_light_masked", "mirt_direct_light_masked_device", "mirt_get_shadow_mask_stats",
     "mirt_scene_upload_device", "mirt_scene_update_device", "mirt_scene_update", "mirt_scene_transform", "mirt_transform",
     "mirt_scene_download", "mirt_scene_info",
@@ -68,6 +69,14 @@ class QueryStats(C.Structure):
     """mirt_query_stats: how the last DirectLight query was answered."""
     _fields_ = [("mode_used", C.c_int32), ("cube_source", C.c_int32), ("cube_bins", C.c_int32), ("shells", C.c_int32),
                 ("shadow_rays", C.c_uint64), ("candidates", C.c_uint64), ("tests", C.c_uint64), ("fallback_records", C.c_uint64)]
+
+
+class RayGridStats(C.Structure):
+    """mirt_ray_grid_stats: how the last mirt_intersect* / mirt_occluded* call under set_ray_grid(True) was answered."""
+    _fields_ = [("mode_used", C.c_int32), ("source", C.c_int32), ("gave_up", C.c_int32), ("cells", C.c_int32), ("plane_bins", C.c_int32),
+                ("offset_bins", C.c_int32), ("pairs", C.c_uint32), ("plane_pairs", C.c_uint32), ("every_rows", C.c_uint32), ("reserved", C.c_uint32),
+                ("rays", C.c_uint64), ("rows_cells", C.c_uint64), ("rows_planes", C.c_uint64), ("rows_every", C.c_uint64), ("tests", C.c_uint64),
+                ("swept_rays", C.c_uint64)]
 
 
 class Ray(C.Structure):
@@ -175,6 +184,8 @@ def load():
     lib.mirt_occluded_along.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
     lib.mirt_occluded_along_device.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
     lib.mirt_get_along_stats.argtypes = [C.POINTER(QueryStats)]
+    lib.mirt_set_ray_grid.argtypes = [C.c_int]
+    lib.mirt_get_ray_grid_stats.argtypes = [C.POINTER(RayGridStats)]
     lib.mirt_intersect_alongs.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp]
     lib.mirt_intersect_alongs_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp]
     lib.mirt_occluded_alongs.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]
@@ -662,6 +673,21 @@ def direct_light_device(d_hits, nhits, lights7, d_rgb):
 def set_query_mode(mode):
     """QUERY_AUTO / QUERY_BRUTE / QUERY_BINNED: how direct_light* walks its shadow rays (mirt_set_query_mode)."""
     _check(load().mirt_set_query_mode(int(mode)))
+
+
+def set_ray_grid(on):
+    """True: intersect* and occluded* answer through the arbitrary-ray grid whenever it can be built, bit for bit as before
+    (mirt_set_ray_grid); False, the default: they sweep."""
+    _check(load().mirt_set_ray_grid(1 if on else 0))
+
+
+def ray_grid_stats():
+    """The last intersect* / occluded* call made under set_ray_grid(True) (mirt_get_ray_grid_stats) as a dict: mode_used (0 no such
+    call), source (0 none, 1 built by the call, 2 kept), gave_up, cells, plane_bins, offset_bins, pairs, plane_pairs, every_rows and --
+    with profiling on -- rays, rows_cells, rows_planes, rows_every, tests, swept_rays."""
+    s = RayGridStats()
+    _check(load().mirt_get_ray_grid_stats(C.byref(s)))
+    return {name: int(getattr(s, name)) for name, _ in RayGridStats._fields_ if name != "reserved"}
 
 
 def _read_query_stats(getter):

@@ -624,6 +624,46 @@ MIRT_API int mirt_intersect_alongs_device(const float *dirs3, int ndirs, const v
 MIRT_API int mirt_occluded_alongs(const float *dirs3, int ndirs, const int32_t *dir_of, const float *origins3, int nrays, const float *max_distance, uint8_t *occluded);
 MIRT_API int mirt_occluded_alongs_device(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, const void *d_max_distance, void *d_occluded);
 
+/* ---- arbitrary rays through a cell grid (additions to ABI 4) ---- */
+
+/* mirt_intersect* and mirt_occluded* take rays that share neither origin nor direction -- a mirror bounce, an ambient-occlusion
+ * hemisphere, a segment test between arbitrary points -- and sweep every triangle for every ray.  mirt_set_ray_grid(1) makes these
+ * four entry points (and no other) answer through a structure kept per scene version instead, whatever the ray count: G x G x G cells
+ * over the scene's box (G the smallest power of two with G^3 >= 2 n, within [4, 128]) for the pairs the reference's test decides by
+ * geometry, an index of the triangles' planes for the pairs it decides by rounding -- a ray nearly inside a triangle's plane may be
+ * given a hit on a triangle it never comes near, and gets it here too --, and a list every ray tests for the triangles too sharp for
+ * either.  Every record, all 20 bytes, and every occlusion byte equal the switch-off call's.  The structure is built by the first
+ * call that needs it (one host read-back), shared by the streams, and forgotten when the triangles change.  A ray whose direction is
+ * zero, not finite or outside [2^-32, 2^19) in its largest component, or whose start is not finite or lies more than two scene
+ * extents (largest |coordinate| of the bounding box) from the origin, sweeps every triangle inside the same kernel.  A call the
+ * frame path would not bin (a scene that is not finite), a scene so far from the origin that a float cannot tell the cells apart,
+ * or one too many of whose triangles are for every ray (more than n / 8 and more than 64: `gave_up`, kept) sweeps as with the switch
+ * off.  0 changes nothing anywhere.  mirt_set_query_mode neither affects the switch nor is affected by it; no AUTO rule uses the
+ * grid.  Context state: mirt_shutdown puts it back to 0. */
+MIRT_API int mirt_set_ray_grid(int on);
+/* The last mirt_intersect* / mirt_occluded* call made with the switch on; waits for that call's stream.  mode_used is 0 while there
+ * was no such call.  A mirt_occluded* call the grid answers (mode_used MIRT_QUERY_BINNED here) leaves mirt_get_occlusion_stats as it
+ * was: that getter keeps reporting the last occlusion call that swept or walked a cube.  The six counters are filled for a binned call made with mirt_set_profiling(1) and zero otherwise. */
+typedef struct mirt_ray_grid_stats {
+    int32_t mode_used;                /* 0 no call; MIRT_QUERY_BRUTE or MIRT_QUERY_BINNED                          */
+    int32_t source;                   /* 0 none, 1 built by this call, 2 kept                                      */
+    int32_t gave_up;                  /* the every-ray list outgrew its share: the call swept                      */
+    int32_t cells;                    /* G: cells per side                                                         */
+    int32_t plane_bins;               /* (alpha, beta) bins per side and plane class                               */
+    int32_t offset_bins;              /* delta bins per (alpha, beta) bin                                          */
+    uint32_t pairs;                   /* rows of the structure: cells, plane index and every-ray list              */
+    uint32_t plane_pairs;             /* ... of the plane index                                                    */
+    uint32_t every_rows;              /* ... of the every-ray list                                                 */
+    uint32_t reserved;
+    uint64_t rays;
+    uint64_t rows_cells;              /* rows offered from cells                                                   */
+    uint64_t rows_planes;             /* ... from the plane index                                                  */
+    uint64_t rows_every;              /* ... from the every-ray list                                               */
+    uint64_t tests;                   /* exact-stage operand sets evaluated, the sweeping rays' included           */
+    uint64_t swept_rays;              /* rays that swept every triangle                                            */
+} mirt_ray_grid_stats;
+MIRT_API int mirt_get_ray_grid_stats(mirt_ray_grid_stats *out);
+
 /* ---- shadow masks: DirectLight's shadow decision per (record, light position), and DirectLight from a mask (additions to ABI 4) ---- */
 
 /* The one value DirectLight computes and throws away (raytracer.cpp:306-315): whether the shadow ray of a record towards a light

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans,occluded,mask,along,alongs]
+"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans,occluded,mask,along,alongs,grid]
 
 The measurements of the ray-query kernels (query/rt_query.hip), written to one text file:
 
@@ -55,6 +55,11 @@ The measurements of the ray-query kernels (query/rt_query.hip), written to one t
                        mirt_intersect_device / mirt_occluded_device.  The answers are compared first; every cell is recorded, the cells
                        where the new call is behind either yardstick by more than 2 % are listed, and per scene where binning with
                        its builds is ahead of (b): what AUTO's rule for the call rests on.
+  grid                 mirt_intersect_device and mirt_occluded_device under mirt_set_ray_grid(1) -- the structure built by the call, and
+                       held -- beside the same call with the switch off, in the same run on the same rays: mirror reflections of the
+                       1080p primary hits, 16 cosine-distributed hemisphere rays per hit point and uniform segments in the box, 1 .. 2^20
+                       rays in powers of four at n = 100 000 and n = 2 000.  The answers are compared first; every cell is recorded, the
+                       cells where the grid is behind by more than 2 % are listed, and from which ray count the build pays.
 
 The knob is read once per process, so every GPU step is a child process of its own, under its own `timeout`; a step that fails
 ends the run."""
@@ -914,6 +919,138 @@ def along_summary(text, p):
     p("")
 
 
+# ---- arbitrary rays through the cell grid: mirt_intersect_device / mirt_occluded_device under mirt_set_ray_grid -----------------------------
+
+GRID_SETS = ("mirror", "hemisphere", "segments")
+IDENTITY = np.array([1, 0, 0, 0, 1, 0, 0, 0, 1], np.float32)
+
+
+def grid_rays(mirt, h, tris, which, top):
+    """Up to `top` rays of a set: mirror reflections of the 1080p primary hits; 16 cosine-distributed rays over the hemisphere of each
+    hit point; uniform random segments in the box."""
+    rng = np.random.default_rng(11)
+    if which == "segments":
+        a, b = rng.uniform(-1, 1, (top, 3)), rng.uniform(-1, 1, (top, 3))
+        return mirt.make_rays(a.astype(np.float32), (b - a).astype(np.float32))
+    prim = primary_rays(mirt, mirt.rot_from_yaw(0.0, 1.0))
+    hits = mirt.fresh_hits(len(prim))
+    d_r, d_h = dev_alloc(h, prim.nbytes, prim), dev_alloc(h, hits.nbytes, hits)
+    mirt.intersect_device(d_r, len(prim), d_h); mirt.sync()
+    assert h.hipMemcpy(hits.ctypes.data_as(C.c_void_p), d_h, hits.nbytes, 2) == 0
+    h.hipFree(d_r); h.hipFree(d_h)
+    hit = hits["index"] >= 0
+    pos = hits["position"][hit].astype(np.float64)
+    nrm = np.asarray(tris, np.float64).reshape(-1, 15)[hits["index"][hit], 9:12]
+    d = prim["dir"][hit].astype(np.float64)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    nrm = np.where((nrm * d).sum(axis=1, keepdims=True) > 0, -nrm, nrm)            # towards the camera's side
+    if which == "mirror":
+        out = d - 2.0 * (d * nrm).sum(axis=1, keepdims=True) * nrm
+    else:
+        k = min(len(pos), top // 16)
+        pos, nrm = np.repeat(pos[:k], 16, axis=0), np.repeat(nrm[:k], 16, axis=0)
+        u1, u2 = rng.uniform(0, 1, len(pos)), rng.uniform(0, 2 * np.pi, len(pos))
+        t1 = np.cross(nrm, np.where(np.abs(nrm[:, :1]) < 0.9, [[1.0, 0, 0]], [[0, 1.0, 0]]))
+        t1 /= np.linalg.norm(t1, axis=1, keepdims=True)
+        t2 = np.cross(nrm, t1)
+        r = np.sqrt(u1)[:, None]
+        out = r * np.cos(u2)[:, None] * t1 + r * np.sin(u2)[:, None] * t2 + np.sqrt(1 - u1)[:, None] * nrm
+    rays = mirt.make_rays((pos + 1e-4 * nrm).astype(np.float32), out.astype(np.float32))
+    return rays[:top]
+
+
+def child_grid(n, which):
+    """mirt_intersect_device / mirt_occluded_device (no limits) from fresh records under mirt_set_ray_grid(1) -- the structure built by
+    the call (the scene version moved on by an identity transform outside the clock: the scene's rows are rebuilt inside it too), and
+    held -- beside the same call with the switch off, on the same rays; results compared before any time is taken."""
+    import mirt
+    h = hip()
+    mirt.init(0)
+    tris = mirt.scene_soup(1, n, 0.05 if n >= 50000 else 0.2)
+    mirt.scene_upload(tris)
+    rays = grid_rays(mirt, h, tris, which, 1 << 20)
+    top = len(rays)
+    fresh = mirt.fresh_hits(top)
+    d_rays, d_hits, d_occ = dev_alloc(h, rays.nbytes, rays), dev_alloc(h, fresh.nbytes, fresh), dev_alloc(h, top)
+
+    def run(fn, k, rebuild=False):
+        assert h.hipMemcpy(d_hits, fresh.ctypes.data_as(C.c_void_p), 20 * k, 1) == 0
+        if rebuild:
+            mirt.scene_transform(0, n, IDENTITY); mirt.sync()
+        t0 = time.perf_counter()
+        fn(k); mirt.sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    calls = (("intersect", lambda q: mirt.intersect_device(d_rays, q, d_hits)), ("occluded", lambda q: mirt.occluded_device(d_rays, q, None, d_occ)))
+    k = 1
+    while k <= top:
+        want, got = np.zeros(k, mirt.HIT_DTYPE), np.zeros(k, mirt.HIT_DTYPE)
+        wocc, gocc = np.zeros(k, np.uint8), np.zeros(k, np.uint8)
+        for on, rec, occ in ((False, want, wocc), (True, got, gocc)):
+            mirt.set_ray_grid(on)
+            run(calls[0][1], k)
+            assert h.hipMemcpy(rec.ctypes.data_as(C.c_void_p), d_hits, rec.nbytes, 2) == 0
+            calls[1][1](k); mirt.sync()
+            assert h.hipMemcpy(occ.ctypes.data_as(C.c_void_p), d_occ, k, 2) == 0
+        st = mirt.ray_grid_stats()
+        assert st["mode_used"] == mirt.QUERY_BINNED and st["gave_up"] == 0, st
+        assert got.tobytes() == want.tobytes() and np.array_equal(gocc, wocc), "the grid disagrees with the sweep"
+        reps = 5 if k <= 65536 else 3
+        ms = {}
+        for name, fn in calls:
+            mirt.set_ray_grid(False)
+            ms[name, "yard"] = float(np.median([run(fn, k) for _ in range(reps + 1)][1:]))
+            mirt.set_ray_grid(True)
+            ts = []
+            for _ in range(reps):
+                ts.append(run(fn, k, rebuild=True))
+                assert mirt.ray_grid_stats()["source"] == 1
+            ms[name, "built"] = float(np.median(ts))
+            ts = [run(fn, k) for _ in range(reps + 1)]
+            assert mirt.ray_grid_stats()["source"] == 2
+            ms[name, "kept"] = float(np.median(ts[1:]))
+        mirt.set_ray_grid(False)
+        print("RESULT grid n %6d %-10s rays %8d G %3d hit %.3f  " % (n, which, k, st["cells"], float((want["index"] >= 0).mean()))
+              + "  ".join("%s %s" % (name, " ".join("%10.4f" % ms[name, m] for m in ("yard", "built", "kept"))) for name in ("intersect", "occluded")) + " ms")
+        sys.stdout.flush()
+        k = k * 4 if k * 4 <= top or k == top else top
+    print("RESULT grid n %6d structure: %d rows (%d of the plane index, %d triangles for every ray)" % (n, st["pairs"], st["plane_pairs"], st["every_rows"]))
+    mirt.shutdown()
+
+
+GRID_ROW = re.compile(r"grid n\s+(\d+) (\w+)\s+rays\s+(\d+) G\s+\d+ hit [0-9.]+  intersect\s+([0-9.]+)\s+([0-9.]+)\s+([0-9.]+)  occluded\s+([0-9.]+)\s+([0-9.]+)\s+([0-9.]+) ms")
+
+
+def step_grid(p):
+    p("== grid: mirt_intersect_device / mirt_occluded_device under mirt_set_ray_grid(1) beside the same call with the switch off (the sweep: the")
+    p("   parent's code unchanged), same run, same rays, from fresh records, no limits (host clock around call + mirt_sync, medians) ==")
+    p("ray sets: mirror reflections of the 1080p primary hits; 16 cosine-distributed hemisphere rays per hit point; uniform segments in the box")
+    p("three columns each: the switch off; on, the structure built by the call; on, the structure held")
+    out = "".join(run_child(p, ["--child", "grid", str(n), which], {}, 420) for n in (100000, 2000) for which in GRID_SETS)
+    grid_summary(out, p)
+
+
+def grid_summary(text, p):
+    """What the rows say: the cells where the grid is behind the sweep (by more than the 2 % two runs differ by), with the structure
+    built by the call and with it held, and per scene, ray set and call the ray count from which the call with its build stays ahead."""
+    out = text
+    rows = [(int(m.group(1)), m.group(2), int(m.group(3)), [float(x) for x in m.groups()[3:]]) for m in GRID_ROW.finditer(out)]
+    for mode, j in (("built by the call", 1), ("held", 2)):
+        behind = ["n %d %s rays %d %s: %.4f ms against %.4f ms" % (n, w, k, what, v[off + j], v[off])
+                  for n, w, k, v in rows for what, off in (("intersect", 0), ("occluded", 3)) if v[off + j] > 1.02 * v[off]]
+        p("the grid behind the sweep by more than 2 %%, structure %s: %s" % (mode, "%d of %d cells" % (len(behind), 2 * len(rows)) if behind else "nowhere"))
+        for line in behind:
+            p("  " + line)
+    for n in sorted({r[0] for r in rows}, reverse=True):
+        for w in GRID_SETS:
+            for what, off in (("intersect", 0), ("occluded", 3)):
+                cells = sorted((k, v[off + 1] <= v[off]) for nn, ww, k, v in rows if nn == n and ww == w)
+                lost = [k for k, ahead in cells if not ahead]
+                first = min([k for k, _ in cells if not lost or k > max(lost)], default=None)
+                p("n %d %s %s: with its build the grid pays from %s rays on" % (n, w, what, first if first is not None else "no count measured"))
+    p("")
+
+
 # ---- several directions in one call: mirt_intersect_alongs_device / mirt_occluded_alongs_device ------------------------------------------
 
 ALONGS_K = (1, 4, 15, 16, 32, 64)
@@ -1247,6 +1384,8 @@ def main():
             return child_occfans(int(a.child[1]))
         if a.child[0] == "along":
             return child_along(int(a.child[1]))
+        if a.child[0] == "grid":
+            return child_grid(int(a.child[1]), a.child[2])
         if a.child[0] == "alongs":
             return child_alongs(int(a.child[1]), int(a.child[2]))
         if a.child[0] == "mask":
@@ -1281,6 +1420,8 @@ def main():
             step_along(p)
         if "alongs" in steps:
             step_alongs(p)
+        if "grid" in steps:
+            step_grid(p)
     finally:
         with open(a.out, "a" if a.append else "w") as f:
             f.write("\n".join(lines) + "\n")
