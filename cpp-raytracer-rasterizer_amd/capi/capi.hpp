@@ -18,6 +18,7 @@
 #include "../along/along.hpp"
 #include "../along/alongs.hpp"
 #include "../grid/ray_grid.hpp"
+#include "../order/ordered_hits.hpp"
 #include "../lights/many_lights.hpp"
 #include "../lights/aa_many_lights.hpp"
 #include "cube_plan.hpp"
@@ -421,6 +422,9 @@ struct QueryRows {
     // ... and of mirt_shadow_mask / mirt_direct_light_masked: the mask's planes, grown apart from the rest (up to 32 bytes a record)
     void *d_mask = nullptr;
     size_t mask_cap = 0;                         // words
+    // ... and of mirt_intersect_ordered: the `after` records and the counts (one a ray), and the records (max_hits a ray), likewise
+    void *d_order_after = nullptr, *d_order_counts = nullptr, *d_order_hits = nullptr;
+    size_t order_cap_rays = 0, order_cap_records = 0;
     // The light cube of the DirectLight queries: a LightCache like the frame path's g.lc, keyed alike (scene version + the light
     // positions in use, and the grid -- so a new scene forgets it), kept across calls, shared by the streams and ordered among
     // them by light_cache_ensure's events.  A query whose lights are the ones the frame path's valid cube holds reads g.lc and
@@ -791,6 +795,14 @@ int along_build_end();
 // With the switch on, on the stream the call has taken: *done says the walk kernel was queued; otherwise the caller sweeps.
 int ray_grid_intersect(const void *d_rays, int nrays, void *d_hits, bool *done);
 int ray_grid_occluded(const void *d_rays, int nrays, const void *d_max_distance, void *d_occluded, bool *done);
+// What order.cpp shares with them: everything of such a call up to its kernel (the structure, the statistics begun afresh; *binned says
+// whether `frame` is ready for a walk kernel), and the ray count up to which a sweep takes a wave per ray (query.cpp).
+int grid_begin(const void *d_rays, int nrays, GridFrame *frame, bool *binned);
+long query_wave_rays();
+
+// ---- every hit along a ray, in order (order.cpp; the kernels: ../order/ordered_hits.hip) ----
+int order_intersect(const void *d_rays, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts);
+int order_intersect_host(const mirt_ray *rays, int nrays, const mirt_hit *after, int max_hits, mirt_hit *hits, int32_t *counts);
 
 // ---- ray queries along several directions in one call (alongs.cpp; the kernels: ../along/alongs.hip) ----
 int alongs_intersect(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, void *d_hits);

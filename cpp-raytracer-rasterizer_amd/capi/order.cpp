@@ -1,0 +1,120 @@
+// order.cpp -- every hit along a ray, in order (mirt_intersect_ordered*; the kernels: ../order/ordered_hits.hip, the list rule:
+// ../order/hit_list.hpp).  The call is dispatched like mirt_intersect*: under mirt_set_ray_grid(1) through the cell grid whenever
+// its structure can be built (ray_grid.cpp: grid_begin, reported by mirt_get_ray_grid_stats), otherwise by the sweep -- a wave per ray
+// up to query.cpp's MIRT_QUERY_WAVE_RAYS, a lane per ray beyond.  max_hits of 3, 5, 6 or 7 run the next list length up and store
+// max_hits slots.  The host form stages `after`, the records and the counts through arrays of its own in g.qrows.
+#include "capi.hpp"
+
+namespace mirt {
+
+static_assert(HIT_LIST_MAX == MIRT_MAX_ORDERED_HITS, "the longest list instantiated is the most a call may ask for");
+
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + nb && y < x + na;
+}
+
+static int check_order_args(const void *rays, int nrays, const void *after, int max_hits, const void *hits, const void *counts)
+{
+    int rc;
+    if ((rc = need_init())) return rc;
+    if (nrays < 0) return fail(MIRT_ERR_INVALID_ARGUMENT, "ray count %d is negative", nrays);
+    if (max_hits < 1 || max_hits > MIRT_MAX_ORDERED_HITS)
+        return fail(MIRT_ERR_INVALID_ARGUMENT, "max_hits %d is outside [1, %d]", max_hits, MIRT_MAX_ORDERED_HITS);
+    if (nrays > 0 && (!rays || !hits || !counts)) return fail(MIRT_ERR_INVALID_ARGUMENT, "ray, hit and count arrays must not be NULL when the count is > 0");
+    // `after` is read while `hits` is written: apart, or -- one slot a ray -- the very same array (a ray's record is read before its slot is written)
+    if (nrays > 0 && after && !(max_hits == 1 && after == hits) &&
+        ranges_overlap(after, (size_t)nrays * sizeof(mirt_hit), hits, (size_t)nrays * (size_t)max_hits * sizeof(mirt_hit)))
+        return fail(MIRT_ERR_INVALID_ARGUMENT, "after overlaps hits (allowed only as after == hits with max_hits == 1)");
+    return MIRT_OK;
+}
+
+// The kernel of list length K = 1, 2, 4 or 8 out of a table of the four instantiations.
+template <class Kernel>
+static Kernel order_pick(int K, Kernel k1, Kernel k2, Kernel k4, Kernel k8) { return K == 1 ? k1 : (K == 2 ? k2 : (K == 4 ? k4 : k8)); }
+
+int order_intersect(const void *d_rays, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts)
+{
+    int rc;
+    if ((rc = check_order_args(d_rays, nrays, d_after, max_hits, d_hits, d_counts))) return rc;
+    if (nrays == 0) return MIRT_OK;
+    if ((rc = query_need_scene())) return rc;
+    stream_begin();
+    const int K = hit_list_size_for(max_hits);
+    OrderFrame o;
+    memset(&o, 0, sizeof o);
+    bool binned = false;
+    if (g.ray_grid && (rc = grid_begin(d_rays, nrays, &o.f, &binned))) return rc;    // (the statistics of mirt_get_ray_grid_stats begin here)
+    if (!binned) {
+        if ((rc = query_rows())) return rc;
+        memset(&o.f, 0, sizeof o.f);
+        o.f.q = rows_frame(d_rays, nrays, nullptr);
+    }
+    o.f.q.hits = static_cast<uint32_t *>(d_hits);
+    o.after = static_cast<const uint32_t *>(d_after);
+    o.max_hits = max_hits;
+    o.counts = static_cast<int32_t *>(d_counts);
+    if (binned) {
+        const auto kernel = o.f.stats ? order_pick(K, k_grid_order<1, true>, k_grid_order<2, true>, k_grid_order<4, true>, k_grid_order<8, true>)
+                                      : order_pick(K, k_grid_order<1, false>, k_grid_order<2, false>, k_grid_order<4, false>, k_grid_order<8, false>);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, g.stream, o);
+    } else if ((long)nrays <= query_wave_rays()) {
+        hipLaunchKernelGGL(order_pick(K, k_order_sweep_wave<1>, k_order_sweep_wave<2>, k_order_sweep_wave<4>, k_order_sweep_wave<8>),
+                           dim3((unsigned)((nrays + 3) / 4)), dim3(256), 0, g.stream, o);
+    } else {
+        hipLaunchKernelGGL(order_pick(K, k_order_sweep<1>, k_order_sweep<2>, k_order_sweep<4>, k_order_sweep<8>),
+                           dim3((unsigned)((nrays + 255) / 256)), dim3(256), sweep_lds_bytes(), g.stream, o);
+    }
+    HIP_TRY(hipGetLastError());
+    return MIRT_OK;
+}
+
+// The host form's staging arrays are its own and grow by their own measure (up to 160 bytes of records a ray), once the checks have
+// passed and there is something to stage.
+static int order_staging(int checked, int nrays, int max_hits)
+{
+    int rc;
+    QueryRows &Q = g.qrows;
+    if (checked || nrays == 0 || g.n <= 0) return MIRT_OK;
+    const size_t rays = (size_t)nrays, records = rays * (size_t)max_hits;
+    if (rays > Q.order_cap_rays) {
+        Q.order_cap_rays = 0;
+        if ((rc = dev_realloc_bytes(&Q.d_order_after, rays * sizeof(mirt_hit))) || (rc = dev_realloc_bytes(&Q.d_order_counts, rays * sizeof(int32_t)))) return rc;
+        Q.order_cap_rays = rays;
+    }
+    if (records > Q.order_cap_records) {
+        Q.order_cap_records = 0;
+        if ((rc = dev_realloc_bytes(&Q.d_order_hits, records * sizeof(mirt_hit)))) return rc;
+        Q.order_cap_records = records;
+    }
+    return MIRT_OK;
+}
+
+int order_intersect_host(const mirt_ray *rays, int nrays, const mirt_hit *after, int max_hits, mirt_hit *hits, int32_t *counts)
+{
+    int rc;
+    const int checked = check_order_args(rays, nrays, after, max_hits, hits, counts);
+    if ((rc = order_staging(checked, nrays, max_hits))) return rc;
+    QueryRows &Q = g.qrows;
+    const size_t records = checked ? 0 : (size_t)nrays * (size_t)max_hits;
+    // (`after` goes to its own staging array before anything comes back: the in-place peel needs nothing more on this side)
+    const HostArray a[] = { { (void *)rays, &QueryRows::d_rays, (size_t)nrays * sizeof(mirt_ray), true, false },
+                            { (void *)after, &QueryRows::d_order_after, (size_t)nrays * sizeof(mirt_hit), after != nullptr, false },
+                            { hits, &QueryRows::d_order_hits, records * sizeof(mirt_hit), false, true },
+                            { counts, &QueryRows::d_order_counts, (size_t)nrays * sizeof(int32_t), false, true } };
+    return with_host_arrays(checked, nrays, a, [&] {
+        return order_intersect(Q.d_rays, nrays, after ? Q.d_order_after : nullptr, max_hits, Q.d_order_hits, Q.d_order_counts);
+    });
+}
+
+}  // namespace mirt
+
+extern "C" int mirt_intersect_ordered(const mirt_ray *rays, int nrays, const mirt_hit *after, int max_hits, mirt_hit *hits, int32_t *counts)
+{
+    return mirt::order_intersect_host(rays, nrays, after, max_hits, hits, counts);
+}
+extern "C" int mirt_intersect_ordered_device(const void *d_rays, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts)
+{
+    return mirt::order_intersect(d_rays, nrays, d_after, max_hits, d_hits, d_counts);
+}

@@ -20,7 +20,7 @@ namespace mirt {
 // frame path's figure for its own wave kernel (rt_frame.cpp: at most 4096 rays); tools/ray_query_bench.py sweeps both kernels over
 // 1 .. 2^20 rays and reports where the curves cross (profiles/ray_query_bench.txt).
 constexpr long QUERY_WAVE_RAYS_DEFAULT = 4096;
-static long query_wave_rays()
+long query_wave_rays()
 {
     static const long v = env_int("MIRT_QUERY_WAVE_RAYS", QUERY_WAVE_RAYS_DEFAULT);
     return v;

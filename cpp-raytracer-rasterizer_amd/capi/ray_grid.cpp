@@ -96,7 +96,7 @@ static int grid_ensure(RayGridCache &C, const GridDesc &desc, bool *built)
 
 // What both calls do up to their kernel, on the stream the call has taken: the statistics begin afresh; *binned says whether `frame`
 // is ready for a walk kernel.
-static int grid_begin(const void *d_rays, int nrays, GridFrame *frame, bool *binned)
+int grid_begin(const void *d_rays, int nrays, GridFrame *frame, bool *binned)
 {
     int rc;
     RayGridCache &C = g.qrows.grid;

@@ -151,7 +151,7 @@ void AaScratch::release()
 
 void QueryRows::release()
 {
-    dev_free({ d_rows, d_max, d_rays, d_hits, d_rgb, d_dirs, d_origin_of, d_limits, d_occluded, d_mask });
+    dev_free({ d_rows, d_max, d_rays, d_hits, d_rgb, d_dirs, d_origin_of, d_limits, d_occluded, d_mask, d_order_after, d_order_counts, d_order_hits });
     if (ev_built) (void)hipEventDestroy(ev_built);
     for (LightCache &c : cubes) c.release();
     fan.release();

@@ -192,6 +192,18 @@ struct RayTracer {
         for (int k = 0; k < n; k++) { std::memcpy(rays[k].start, &start[k].x, 12); std::memcpy(rays[k].dir, &dir[k].x, 12); }
         check(mirt_intersect(rays.data(), n, reinterpret_cast<mirt_hit *>(closest)), "mirt_intersect");
     }
+    // Every hit along a ray, not only the one ClosestIntersection ends on: the first max_hits triangles the loop accepts for ray k, in
+    // the order its record rule ranks them (nearer first, the later index first among equal distances), into ordered[k * max_hits + 0 ...]
+    // as whole Intersection records, count[k] of them, Update()'s reset behind.  after (null, or one record per ray) continues an
+    // enumeration behind the last record an earlier call wrote (mirt_intersect_ordered; 1 <= max_hits <= MIRT_MAX_ORDERED_HITS).
+    void OrderedIntersections(const vec3 *start, const vec3 *dir, const Intersection *after, int max_hits, Intersection *ordered, int32_t *count, int n)
+    {
+        upload_scene();
+        std::vector<mirt_ray> rays((size_t)n);
+        for (int k = 0; k < n; k++) { std::memcpy(rays[k].start, &start[k].x, 12); std::memcpy(rays[k].dir, &dir[k].x, 12); }
+        check(mirt_intersect_ordered(rays.data(), n, reinterpret_cast<const mirt_hit *>(after), max_hits, reinterpret_cast<mirt_hit *>(ordered), count),
+              "mirt_intersect_ordered");
+    }
     // The same for n rays that share their start -- a probe's cube map, a fan from the eye or from a light: closest[k] comes back as
     // ClosestIntersection(start, dir[k], triangles, closest[k]) leaves it, each ray walking its bin of a cube around `start` where
     // that pays (mirt_intersect_from, mirt_set_query_mode).

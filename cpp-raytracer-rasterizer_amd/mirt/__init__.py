@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libmirt.so")
 
 MAX_LIGHTS = 32
+MAX_ORDERED_HITS = 8                  # hits per ray and call of intersect_ordered (MIRT_MAX_ORDERED_HITS)
 MAX_LIGHT_POSITIONS = 256             # lights x soft-shadow samples (MIRT_MAX_LIGHT_POSITIONS: randomPositions[256], raytracer.cpp:84)
 RT_AUTO, RT_BRUTE, RT_BINNED = 0, 1, 2
 QUERY_AUTO, QUERY_BRUTE, QUERY_BINNED = 0, 1, 2
@@ -34,6 +35,7 @@ EXPORTS = (
     "mirt_intersect_along", "mirt_intersect_along_device", "mirt_occluded_along", "mirt_occluded_along_device", "mirt_get_along_stats",
     "mirt_intersect_alongs", "mirt_intersect_alongs_device", "mirt_occluded_alongs", "mirt_occluded_alongs_device",
     "mirt_set_ray_grid", "mirt_get_ray_grid_stats",
+    "mirt_intersect_ordered", "mirt_intersect_ordered_device",
     "mirt_shadow_mask", "mirt_shadow_mask_device", "mirt_direct_light_masked", "mirt_direct_light_masked_device", "mirt_get_shadow_mask_stats",
     "mirt_scene_upload_device", "mirt_scene_update_device", "mirt_scene_update", "mirt_scene_transform", "mirt_transform",
     "mirt_scene_download", "mirt_scene_info",
@@ -186,6 +188,8 @@ def load():
     lib.mirt_get_along_stats.argtypes = [C.POINTER(QueryStats)]
     lib.mirt_set_ray_grid.argtypes = [C.c_int]
     lib.mirt_get_ray_grid_stats.argtypes = [C.POINTER(RayGridStats)]
+    lib.mirt_intersect_ordered.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp]
+    lib.mirt_intersect_ordered_device.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp]
     lib.mirt_intersect_alongs.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp]
     lib.mirt_intersect_alongs_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp]
     lib.mirt_occluded_alongs.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]
@@ -654,6 +658,28 @@ def intersect(rays, hits=None):
 def intersect_device(d_rays, nrays, d_hits):
     """The same on device arrays (raw pointers), queued like a *_device frame; mirt.sync() completes it."""
     _check(load().mirt_intersect_device(d_rays, int(nrays), d_hits))
+
+
+def intersect_ordered(rays, max_hits, after=None):
+    """The first max_hits triangles along every ray in the reference's order -- nearer first, the later index first among equal
+    distances -- (mirt_intersect_ordered): (hits[n, max_hits] HIT_DTYPE, counts[n] int32); the slots behind a ray's count are fresh
+    records.  after: one record per ray (HIT_DTYPE) behind which the ray continues -- the last record an earlier call wrote -- or None."""
+    rays = _as_rays(rays)
+    max_hits = int(max_hits)
+    if after is not None:
+        after = np.ascontiguousarray(after, HIT_DTYPE)
+        if after.shape != (len(rays),):
+            raise ValueError("%d rays but after has shape %s" % (len(rays), after.shape))
+    hits = np.zeros((len(rays), max(max_hits, 0)), HIT_DTYPE)
+    counts = np.zeros(len(rays), np.int32)
+    _check(load().mirt_intersect_ordered(_ptr(rays), len(rays), _ptr(after), max_hits, _ptr(hits), _ptr(counts)))
+    return hits, counts
+
+
+def intersect_ordered_device(d_rays, nrays, d_after, max_hits, d_hits, d_counts):
+    """The same on device arrays (raw pointers; d_after may be None, or d_hits itself when max_hits is 1), queued like
+    intersect_device; mirt.sync() completes it."""
+    _check(load().mirt_intersect_ordered_device(d_rays, int(nrays), d_after, int(max_hits), d_hits, d_counts))
 
 
 def direct_light(hits, lights7):

@@ -1,0 +1,247 @@
+// ordered_hits.hip -- hand-written gfx950 kernels of mirt_intersect_ordered*: the max_hits first triangles along each ray in the
+// reference's own order (hit_list.hpp), behind an optional `after` record, bit for bit.
+//
+// Every (ray, triangle) test is k_query_closest's own: the scene's QueryRow, ray_dots, the conservative filter (maybe_hit) with the
+// per-ray exact-only override (ray_exact_only) in front of exact_hit_row, on the caller's start and negD = -dir.  What differs is
+// what an accepted distance does: it is offered to a list of the K best keys in registers (hit_list_offer) instead of replacing one
+// record.  The list does not care in which order rows arrive nor whether one arrives twice -- equal keys are the same triangle and
+// the second is dropped --, and the `after` record only removes candidates, so the three kernels below differ only in which rows
+// they offer:
+//   k_order_sweep<K>       a lane per ray, all rows staged through LDS in chunks (k_query_closest's structure, one ray a lane);
+//   k_order_sweep_wave<K>  a wave per ray, lanes stride over the rows and keep the K best of their own, then K extraction rounds;
+//   k_grid_order<K, STATS> a lane per ray through the cell grid (k_grid_closest's walk), reach = the list's bound.
+// Positions do not travel with the keys: the K winners are tested once more at the end (exact_hit_row on the winner's row gives the
+// same bits -- the same operations on the same operands, no fused forms) and the list stays at two registers an entry.
+// The `after` record of a ray is read before any of its slots is written, by the lane or wave that writes them: with max_hits == 1
+// the caller may pass the output array itself.
+// Built with -ffp-contract=off like every kernel of the library.
+#include "ordered_hits.hpp"
+#include "../grid/ray_grid_device.hpp"
+#include "../query/rt_query_device.hpp"
+
+namespace mirt {
+
+// The record (a, k) ray `ray` continues behind: the caller's, or one that admits everything (no `after`: every eligible distance is
+// above -1), or for a lane without a ray one that admits nothing (NaN).
+__device__ __forceinline__ void order_after(const OrderFrame &o, long long ray, bool ok, float *a, int *k)
+{
+    *a = ok ? -1.0f : __uint_as_float(0x7fc00000u);
+    *k = 0;
+    if (ok && o.after) {
+        const uint32_t *r = o.after + (size_t)HIT_WORDS * ray;
+        *a = __uint_as_float(r[3]);
+        *k = (int)r[4];
+    }
+}
+
+// Slot `slot` of ray `ray`: the winner `key` as a whole struct Intersection -- its position from the test run once more --, or
+// Update()'s reset for an empty entry.
+__device__ __forceinline__ void order_store_slot(const OrderFrame &o, long long ray, int slot, unsigned long long key, v3 S, v3 nd)
+{
+    const QueryFrame &q = o.f.q;
+    uint32_t *h = q.hits + (size_t)HIT_WORDS * ((size_t)ray * (size_t)o.max_hits + (size_t)slot);
+    if (key == HIT_KEY_NONE) {
+        store_record(h, V3(0.0f, 0.0f, 0.0f), 0x7f7fffffu, 0xffffffffu);                   // :335-339: FLT_MAX, -1
+        return;
+    }
+    const int tri = hit_key_index(key);
+    const float4 *src = reinterpret_cast<const float4 *>(q.rows + tri);
+    const RowVecs r = unpack_row(src[0], src[1], src[2]);
+    float e1e2b, dist;
+    const TestDots td = ray_dots(r, S, nd, &e1e2b);
+    v3 hp = V3(0.0f, 0.0f, 0.0f);
+    (void)exact_hit_row(td, e1e2b, r, S, &hp, &dist);
+    store_record(h, hp, hit_key_distance_bits(key), (uint32_t)tri);
+}
+
+// A lane's whole answer: its max_hits slots from its own list, and the count.
+template <int K>
+__device__ __forceinline__ void order_store_list(const OrderFrame &o, long long ray, const HitList<K> &l, v3 S, v3 nd)
+{
+    int cnt = 0;
+#pragma unroll
+    for (int s = 0; s < K; s++)
+        if (s < o.max_hits) {
+            order_store_slot(o, ray, s, l.k[s], S, nd);
+            cnt += (int)(l.k[s] != HIT_KEY_NONE);
+        }
+    o.counts[ray] = cnt;
+}
+
+// ---- k_order_sweep: one lane per ray, every ray tests every triangle -------------------------------------------------------------------
+// Workgroup = 256 lanes = 256 rays.  The rows are staged through LDS in chunks of RT_CHUNK_ROWS and read as wave-uniform broadcasts.
+template <int K>
+__global__ __launch_bounds__(256) void k_order_sweep(const OrderFrame o)
+{
+    extern __shared__ __attribute__((aligned(16))) float4 s_rows[];
+    const QueryFrame &q = o.f.q;
+    const long long ray = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool ok = ray < q.nrays;
+    const float *rp = q.rays + (size_t)RAY_WORDS * (ok ? ray : 0);
+    const v3 start = ld3(rp), dir = ld3(rp + 3);
+    const v3 nd = neg3(dir);                                       // negD = -dir (:229); dir is used as given
+    const bool exact_only = ray_exact_only(scene_rows_in_range(q), start, dir);
+    float a;
+    int k;
+    order_after(o, ray, ok, &a, &k);
+    HitList<K> l;
+    hit_list_clear(l);
+
+    for (int base = 0; base < q.n; base += RT_CHUNK_ROWS) {
+        const int cnt = min(RT_CHUNK_ROWS, q.n - base);
+        stage_rows(s_rows, q.rows + base, cnt);
+#pragma unroll 2
+        for (int j = 0; j < cnt; j++) {
+            const RowVecs r = unpack_row(s_rows[3 * j], s_rows[3 * j + 1], s_rows[3 * j + 2]);
+            float e1e2b;
+            const TestDots td = ray_dots(r, start, nd, &e1e2b);
+            if (maybe_hit(td) || exact_only) {
+                v3 hp;
+                float dist;
+                if (exact_hit_row(td, e1e2b, r, start, &hp, &dist)) hit_list_consider(l, dist, base + j, a, k);
+            }
+        }
+    }
+    if (ok) order_store_list(o, ray, l, start, nd);
+}
+
+template __global__ void k_order_sweep<1>(const OrderFrame);
+template __global__ void k_order_sweep<2>(const OrderFrame);
+template __global__ void k_order_sweep<4>(const OrderFrame);
+template __global__ void k_order_sweep<8>(const OrderFrame);
+
+// ---- k_order_sweep_wave: one WAVE per ray, lanes over triangles ------------------------------------------------------------------------
+// k_query_closest_wave's shape: the 64 lanes stride over the rows in global memory and each keeps the K best of its own triangles.
+// The wave's K best are among them.  Round s takes the smallest list head of the wave (wave_min_key), the one lane that owns it -- a
+// row is seen by one lane -- pops it, and lane s keeps it as slot s; then lanes 0 .. max_hits - 1 write a slot each.
+template <int K>
+__global__ __launch_bounds__(256) void k_order_sweep_wave(const OrderFrame o)
+{
+    const QueryFrame &q = o.f.q;
+    const int lane = threadIdx.x & 63;
+    const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= q.nrays) return;                                    // (the whole wave)
+    const float *rp = q.rays + (size_t)RAY_WORDS * ray;
+    const v3 start = ld3(rp), dir = ld3(rp + 3);
+    const v3 nd = neg3(dir);                                       // :229
+    const bool exact_only = ray_exact_only(scene_rows_in_range(q), start, dir);
+    float a;
+    int k;
+    order_after(o, ray, true, &a, &k);
+    HitList<K> l;
+    hit_list_clear(l);
+
+    for (int i = lane; i < q.n; i += 64) {
+        const float4 *src = reinterpret_cast<const float4 *>(q.rows + i);
+        const RowVecs r = unpack_row(src[0], src[1], src[2]);
+        float e1e2b;
+        const TestDots td = ray_dots(r, start, nd, &e1e2b);
+        if (maybe_hit(td) || exact_only) {
+            v3 hp;
+            float dist;
+            if (exact_hit_row(td, e1e2b, r, start, &hp, &dist)) hit_list_consider(l, dist, i, a, k);
+        }
+    }
+
+    unsigned long long mine = HIT_KEY_NONE;
+    int cnt = 0;
+#pragma unroll
+    for (int s = 0; s < K; s++)
+        if (s < o.max_hits) {                                      // (wave-uniform)
+            const unsigned long long best = wave_min_key(l.k[0]);
+            if (l.k[0] == best) hit_list_pop(l);                   // (all heads empty: popping changes nothing)
+            if (lane == s) mine = best;
+            cnt += (int)(best != HIT_KEY_NONE);
+        }
+    if (lane < o.max_hits) order_store_slot(o, ray, lane, mine, start, nd);
+    if (lane == 0) o.counts[ray] = cnt;
+}
+
+template __global__ void k_order_sweep_wave<1>(const OrderFrame);
+template __global__ void k_order_sweep_wave<2>(const OrderFrame);
+template __global__ void k_order_sweep_wave<4>(const OrderFrame);
+template __global__ void k_order_sweep_wave<8>(const OrderFrame);
+
+// ---- k_grid_order: one lane per ray through the cell grid ------------------------------------------------------------------------------
+// k_grid_closest's walk -- cells slab by slab, plane index, every-ray list, the swept fallback for the lanes the structure does not
+// cover -- with the list in place of the record.  The walk's reach is the list's bound times 1 + 2^-20, +inf until the list is full:
+// an accepted pair of distance d is offered under every reach >= d (ray_grid.hpp), so once K entries at or below the bound are held,
+// a pair the cells' end cuts off lies strictly beyond the bound and could not enter; the end is strict, so ties at the bound are
+// still offered.  No cell is skipped for lying in front of `after`: a ray that continues walks its first cells again.
+template <int K, bool STATS>
+__global__ __launch_bounds__(256) void k_grid_order(const OrderFrame o)
+{
+    const GridFrame &f = o.f;
+    const long long ray = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool mine = ray < f.q.nrays;
+    const GridLane gl = grid_lane(f, ray, mine);
+    float a;
+    int k;
+    order_after(o, ray, mine, &a, &k);
+    const bool open = mine && a == a;                              // (a NaN record admits nothing: no walk)
+    const bool swept = open && !gl.fit;
+    bool live = open && gl.fit;
+    GridWalk w = grid_walk_begin(f.v.d, gl.S, V3(-gl.nd.x, -gl.nd.y, -gl.nd.z), live);
+    HitList<K> l;
+    hit_list_clear(l);
+    float bound = __uint_as_float(0x7f800000u);
+    uint32_t e = 0u, end = 0u;
+    int src = 0;
+    unsigned long long c[GSTAT_WORDS] = {};
+    const float4 *rows4 = reinterpret_cast<const float4 *>(f.v.rows);
+    for (;;) {
+        grid_step_rows(f.v, w, (double)bound * (1.0 + 9.5367431640625e-7), live, e, end, src);
+        if (!__any(live)) break;
+        const int act = (int)(live && e < end);
+        if (!__any(act)) continue;                                 // (a round of steps only)
+        float4 c0, c1, c2;
+        walk_row(rows4, act ? e : 0u, c0, c1, c2);
+        const int tri = (int)f.v.tri[act ? e : 0u];
+        const RowVecs r = unpack_row(c0, c1, c2);
+        float e1e2b;
+        const TestDots td = ray_dots(r, gl.S, gl.nd, &e1e2b);
+        if (STATS) {
+            c[GSTAT_ROWS_CELLS] += (unsigned)(act & (int)(src == 0));
+            c[GSTAT_ROWS_PLANES] += (unsigned)(act & (int)(src == 1));
+            c[GSTAT_ROWS_EVERY] += (unsigned)(act & (int)(src == 2));
+            c[GSTAT_TESTS] += (unsigned)act;
+        }
+        if (act & (int)maybe_hit(td)) {
+            v3 hp;
+            float dist;
+            if (exact_hit_row(td, e1e2b, r, gl.S, &hp, &dist)) {
+                hit_list_consider(l, dist, tri, a, k);
+                bound = hit_list_bound(l);
+            }
+        }
+        e += (uint32_t)act;
+    }
+    if (__any(swept)) {
+        // (rare) the lanes the structure does not cover: every row of the scene, k_order_sweep's loop body
+        if (STATS && swept) { c[GSTAT_TESTS] += (unsigned)f.q.n; c[GSTAT_SWEPT] = 1; }
+        for (int j = 0; j < f.q.n; j++) {
+            const float4 *src4 = reinterpret_cast<const float4 *>(f.q.rows + j);
+            const RowVecs r = unpack_row(src4[0], src4[1], src4[2]);
+            float e1e2b;
+            const TestDots td = ray_dots(r, gl.S, gl.nd, &e1e2b);
+            if (swept && (maybe_hit(td) || gl.exact_only)) {
+                v3 hp;
+                float dist;
+                if (exact_hit_row(td, e1e2b, r, gl.S, &hp, &dist)) hit_list_consider(l, dist, j, a, k);
+            }
+        }
+    }
+    if (mine) order_store_list(o, ray, l, gl.S, gl.nd);
+    if (STATS) { c[GSTAT_RAYS] = mine ? 1u : 0u; flush_grid_stats(f.stats, c); }
+}
+
+template __global__ void k_grid_order<1, false>(const OrderFrame);
+template __global__ void k_grid_order<1, true>(const OrderFrame);
+template __global__ void k_grid_order<2, false>(const OrderFrame);
+template __global__ void k_grid_order<2, true>(const OrderFrame);
+template __global__ void k_grid_order<4, false>(const OrderFrame);
+template __global__ void k_grid_order<4, true>(const OrderFrame);
+template __global__ void k_grid_order<8, false>(const OrderFrame);
+template __global__ void k_grid_order<8, true>(const OrderFrame);
+
+}  // namespace mirt

@@ -1,0 +1,23 @@
+// ordered_hits.hpp -- the parameter block and the kernels of mirt_intersect_ordered* (ordered_hits.hip; the list rule: hit_list.hpp;
+// the host: ../capi/order.cpp).
+#pragma once
+
+#include "hit_list.hpp"
+#include "../grid/ray_grid.hpp"
+
+namespace mirt {
+
+// A call: the scene's rows and the caller's rays (f.q; f.q.hits is the OUTPUT, nrays * max_hits records, ray-major), the grid's
+// structure and counters for k_grid_order (f.v, f.stats; unused by the sweeps), the `after` records or NULL, and the counts.
+struct OrderFrame {
+    GridFrame f;
+    const uint32_t *after;       // nrays records of HIT_WORDS words, or NULL: only distance and index are read
+    int max_hits;                // 1 .. K of the instantiation
+    int32_t *counts;             // nrays
+};
+
+template <int K> __attribute__((global)) void k_order_sweep(const OrderFrame);
+template <int K> __attribute__((global)) void k_order_sweep_wave(const OrderFrame);
+template <int K, bool STATS> __attribute__((global)) void k_grid_order(const OrderFrame);
+
+}  // namespace mirt

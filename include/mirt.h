@@ -664,6 +664,34 @@ typedef struct mirt_ray_grid_stats {
 } mirt_ray_grid_stats;
 MIRT_API int mirt_get_ray_grid_stats(mirt_ray_grid_stats *out);
 
+/* ---- every hit along a ray, in order (additions to ABI 4) ---- */
+
+/* mirt_intersect* answers with the ONE triangle ClosestIntersection ends on.  The loop that finds it (raytracer.cpp:202-257) accepts
+ * a set of triangles per ray, each with a position p_j (:241) and a distance d_j (:242), and its record rule `closest.distance >=
+ * distance` (:243) ranks them: j comes before k when d_j < d_k, or when d_j == d_k and j > k (the later index of a tie wins the
+ * record).  mirt_intersect_ordered* returns the first max_hits triangles of that order per ray, bit for bit: the thickness of a part
+ * along a ray, transparency layers, a point-in-mesh test by counting crossings, a bounce ray that skips the surface it starts on.
+ * Eligible for ray i are the triangles j the reference's test accepts (:239) with FLT_MAX >= d_j -- what a fresh record takes, so
+ * never a NaN or +inf distance -- and, when `after` is given, with d_j > a || (d_j == a && j < k) for a = after[i].distance, k =
+ * after[i].index: float and signed-int comparisons as written, so a NaN a admits nothing, a negative a everything, and -0.0f
+ * behaves as 0.0f; only distance and index of an `after` record are read.  The first min(max_hits, eligible) of them go to
+ * hits[i * max_hits + 0 ...] in order, each a whole struct Intersection (p_j, d_j, j); counts[i] is that number; every remaining
+ * slot of the ray is written as Update()'s reset (position 0, FLT_MAX, index -1).  Unlike mirt_intersect, `hits` is a pure output:
+ * all max_hits * 20 bytes per ray and the count are always written.  So with after == NULL slot 0 (and counts[i] > 0) is
+ * mirt_intersect on a fresh record, and a caller enumerates every hit of a ray by calling again with after[i] = the last record
+ * written, for the rays whose count equals max_hits; an exhausted ray stays exhausted (a fresh record admits nothing).
+ * 1 <= max_hits <= MIRT_MAX_ORDERED_HITS, otherwise MIRT_ERR_INVALID_ARGUMENT (and for a negative count, or NULL rays, hits or counts
+ * with a positive one); nrays == 0 does nothing.  `after` must not overlap `hits`, except that with max_hits == 1 after == hits
+ * exactly is allowed and peels in place: a ray's record is read before its slot is written.  mirt_intersect_ordered: host arrays,
+ * complete on return.  mirt_intersect_ordered_device: device arrays, queued like mirt_intersect_device (the streams of
+ * mirt_set_frames_in_flight in turn, no host sync; mirt_sync() completes it).  Under mirt_set_ray_grid(1) the call walks the cell
+ * grid whenever its structure can be built and is then the call mirt_get_ray_grid_stats reports; otherwise it sweeps every
+ * triangle.  mirt_set_query_mode does not affect it. */
+#define MIRT_MAX_ORDERED_HITS 8
+MIRT_API int mirt_intersect_ordered(const mirt_ray *rays, int nrays, const mirt_hit *after /* nullable */, int max_hits,
+                                    mirt_hit *hits /* nrays * max_hits, ray-major */, int32_t *counts /* nrays */);
+MIRT_API int mirt_intersect_ordered_device(const void *d_rays, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts);
+
 /* ---- shadow masks: DirectLight's shadow decision per (record, light position), and DirectLight from a mask (additions to ABI 4) ---- */
 
 /* The one value DirectLight computes and throws away (raytracer.cpp:306-315): whether the shadow ray of a record towards a light

@@ -1,0 +1,139 @@
+"""What the tests of the ordered hits (test_gpu_ordered_hits.py) share: the scenes and ray sets, and the CPU oracle's expectations --
+the enumeration of a ray's hits by peeling (ClosestIntersection on a fresh record against the scene with the rows of the triangles
+already reported for that ray set to NaN: a NaN row accepts nothing and indices keep their meaning), and the per-triangle table
+(one oracle call per (ray, triangle) on a fresh record) from which the answer behind an arbitrary `after` record is sorted.
+Test plumbing only."""
+import numpy as np
+
+import mirt
+import ray_grid_helpers as H
+from query_helpers import make_batch, odd_rays, scene_of
+
+F32 = np.float32
+FLT_MAX = np.finfo(np.float32).max
+_cache = {}
+
+GRID_SCENES = {"cornell": 4, "wall": 8, "soup2000": 16}              # test_gpu_ray_grid.py: these are binned, with this many cells a side
+
+
+def scene(name):
+    if name in GRID_SCENES:
+        return H.scene(name)
+    if name == "soup65x2":                                          # every hit has a partner at the same distance 65 indices later
+        t = scene_of("soup65")[0]
+        return np.concatenate([t, t])
+    return scene_of(name)[0]
+
+
+def rays_of(name, n=4097):
+    """n rays: for the grid's scenes ray_grid_helpers.ray_set (its planted unfit rays included) interleaved with make_batch rays that
+    carry query_helpers.odd_rays; make_batch with odd_rays otherwise."""
+    key = ("rays", name, n)
+    if key not in _cache:
+        a, b = {"cornell": (0.9, 3.0), "wall": (1.0, 0.8), "soup2000": (1.5, 1.0), "soup65x2": (1.5, 1.0), "one": (1.5, 0.3)}[name]
+        batch = odd_rays(make_batch(n, a, b))
+        if name in GRID_SCENES:
+            rays = batch.copy()
+            rays[0::2] = H.as_rays(H.ray_set(name)[0])[:len(rays[0::2])]
+        else:
+            rays = batch
+        rays.setflags(write=False)
+        _cache[key] = rays
+    return _cache[key]
+
+
+def peel(oracle, tris, rays, cap):
+    """(hits[n, cap], counts[n]): slot k of a ray is the oracle's ClosestIntersection on a fresh record against the scene in which the
+    rows of the ray's slots 0 .. k - 1 are NaN; fresh records behind the ray's last hit."""
+    tris = np.ascontiguousarray(tris, F32).reshape(-1, 15)
+    hits = np.zeros((len(rays), cap), mirt.HIT_DTYPE)
+    hits[:] = mirt.fresh_hits(1)[0]
+    counts = np.zeros(len(rays), np.int32)
+    with np.errstate(all="ignore"):
+        for i in range(len(rays)):
+            work = None
+            for k in range(cap):
+                _, p, d, ix = oracle.closest_intersection(tris if work is None else work, rays["start"][i], rays["dir"][i])
+                if ix < 0:
+                    break
+                hits[i, k]["position"], hits[i, k]["distance"], hits[i, k]["index"] = p, d, ix
+                counts[i] = k + 1
+                if work is None:
+                    work = tris.copy()
+                work[ix, :] = np.nan
+    return hits, counts
+
+
+def peeled(oracle, name, n, cap):
+    """peel() for the first n rays of the scene's set, computed once per (scene, n, cap) and left unchanged."""
+    key = ("peel", name, n, cap)
+    if key not in _cache:
+        hits, counts = peel(oracle, scene(name), rays_of(name)[:n], cap)
+        hits.setflags(write=False); counts.setflags(write=False)
+        _cache[key] = hits, counts
+    return _cache[key]
+
+
+def table(oracle, tris, rays):
+    """The per-triangle table: rec[r, j] is the record a fresh ClosestIntersection call on triangle j alone leaves for ray r
+    (index 0 where it was accepted -- stored as j --, -1 where not)."""
+    tris = np.ascontiguousarray(tris, F32).reshape(-1, 15)
+    rec = np.zeros((len(rays), len(tris)), mirt.HIT_DTYPE)
+    rec[:] = mirt.fresh_hits(1)[0]
+    with np.errstate(all="ignore"):
+        for r in range(len(rays)):
+            for j in range(len(tris)):
+                _, p, d, ix = oracle.closest_intersection(tris[j:j + 1], rays["start"][r], rays["dir"][r])
+                if ix == 0:
+                    rec[r, j]["position"], rec[r, j]["distance"], rec[r, j]["index"] = p, d, j
+    return rec
+
+
+def tabled(oracle, name, n):
+    key = ("table", name, n)
+    if key not in _cache:
+        t = table(oracle, scene(name), rays_of(name)[:n])
+        t.setflags(write=False)
+        _cache[key] = t
+    return _cache[key]
+
+
+def from_table(rec, after, max_hits):
+    """(hits[n, max_hits], counts[n]) as the contract words it: of the accepted triangles of a ray those with FLT_MAX >= d and --
+    `after` given -- d > a || (d == a && j < k), in the order d rising, j falling; float32 and int32 comparisons."""
+    n = len(rec)
+    hits = np.zeros((n, max_hits), mirt.HIT_DTYPE)
+    hits[:] = mirt.fresh_hits(1)[0]
+    counts = np.zeros(n, np.int32)
+    with np.errstate(invalid="ignore"):
+        for r in range(n):
+            row = rec[r][rec[r]["index"] >= 0]
+            d, j = row["distance"], row["index"]
+            ok = F32(FLT_MAX) >= d
+            if after is not None:
+                a, k = after["distance"][r], after["index"][r]
+                ok &= (d > a) | ((d == a) & (j < k))
+            row = row[ok]
+            row = row[np.lexsort((-row["index"].astype(np.int64), row["distance"]))][:max_hits]
+            hits[r, :len(row)] = row
+            counts[r] = len(row)
+    return hits, counts
+
+
+AFTER_KINDS = 11
+
+
+def after_records(slot0, shift=0):
+    """(records, kinds).  Per ray, in rotation from `shift` on: distance -1; the ray's own slot-0 distance with index -1, with the hit's
+    index, with that index - 1 and + 1 and with INT_MAX; one float above and one float below that distance; FLT_MAX; +inf; NaN.
+    (Distance 1 and index 3 where the ray hit nothing.)"""
+    n = len(slot0)
+    d = np.where(slot0["index"] >= 0, slot0["distance"], F32(1.0)).astype(F32)
+    ix = np.where(slot0["index"] >= 0, slot0["index"], 3).astype(np.int32)
+    kind = (np.arange(n) + shift) % AFTER_KINDS
+    a = mirt.fresh_hits(n)
+    a["position"] = 7.0                                             # (never read)
+    a["distance"] = np.select([kind == 0, kind <= 5, kind == 6, kind == 7, kind == 8, kind == 9],
+                              [F32(-1), d, np.nextafter(d, F32("inf")), np.nextafter(d, F32(0)), F32(FLT_MAX), F32("inf")], F32("nan")).astype(F32)
+    a["index"] = np.select([kind == 1, kind == 2, kind == 3, kind == 4, kind == 5], [-1, ix, ix - 1, ix + 1, np.iinfo(np.int32).max], ix).astype(np.int32)
+    return a, kind

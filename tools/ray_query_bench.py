@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans,occluded,mask,along,alongs,grid]
+"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans,occluded,mask,along,alongs,grid,ordered]
 
 The measurements of the ray-query kernels (query/rt_query.hip), written to one text file:
 
@@ -32,6 +32,11 @@ The measurements of the ray-query kernels (query/rt_query.hip), written to one t
                        each beside what a caller had to do before for the same answer, in the same run: mirt_intersect_device /
                        mirt_intersect_fans_device from fresh records on the same rays.  The answers are compared first; the cells
                        where an occlusion call is behind, and where binning with the builds crosses the brute path, are listed.
+  ordered              mirt_intersect_ordered_device, max_hits 1, 2, 4, 8, on the grid step's scenes and ray sets, 1 .. 2^20 rays in powers of
+                       four, the switch of mirt_set_ray_grid off, on with the build and on with the structure held, beside
+                       mirt_intersect_device from fresh records and beside max_hits in-place peels of the max_hits == 1 call, in the same
+                       run on the same rays.  The answers are compared first; the cells where max_hits == 1 is behind mirt_intersect_device
+                       and where max_hits == N is behind N peels are listed.
   mask                 mirt_shadow_mask_device and mirt_direct_light_masked_device beside mirt_direct_light_device on the same records, lights
                        and cubes, the three calls in turn: 2^10 .. 2^21 records x 1, 2, 32, 64, 256 positions x 2000 and 100 000
                        triangles, under MIRT_QUERY_BRUTE (cells beyond 2e11 row tests are named, not run) and MIRT_QUERY_BINNED with the
@@ -1051,6 +1056,135 @@ def grid_summary(text, p):
     p("")
 
 
+# ---- every hit along a ray, in order: mirt_intersect_ordered_device ------------------------------------------------------------------------
+
+ORDERED_HITS = (1, 2, 4, 8)
+
+
+def child_ordered(n, which):
+    """mirt_intersect_ordered_device for max_hits 1, 2, 4 and 8 on the grid section's ray sets, the switch of mirt_set_ray_grid off and on
+    (the structure built by the call -- the scene version moved on by an identity transform outside the clock --, and held), beside two
+    yardsticks in the same run on the same rays: mirt_intersect_device from fresh records (what one hit costs today), and max_hits
+    in-place peels of the max_hits == 1 call (after == hits; what the single walk saves).  Answers are compared before any time is
+    taken: the switch on against off, slot 0 against mirt_intersect_device, and the eight peels against the max_hits == 8 call."""
+    import mirt
+    h = hip()
+    mirt.init(0)
+    tris = mirt.scene_soup(1, n, 0.05 if n >= 50000 else 0.2)
+    mirt.scene_upload(tris)
+    rays = grid_rays(mirt, h, tris, which, 1 << 20)
+    top = len(rays)
+    fresh = mirt.fresh_hits(top)
+    behind = fresh.copy()
+    behind["distance"] = -1.0                                       # the record every hit lies behind: where a peel starts
+    d_rays, d_rec, d_hits, d_cnt = dev_alloc(h, rays.nbytes, rays), dev_alloc(h, fresh.nbytes, fresh), dev_alloc(h, 8 * fresh.nbytes), dev_alloc(h, 4 * top)
+
+    def run(fn, k, start=fresh, rebuild=False):
+        assert h.hipMemcpy(d_rec, start.ctypes.data_as(C.c_void_p), 20 * k, 1) == 0
+        if rebuild:
+            mirt.scene_transform(0, n, IDENTITY); mirt.sync()
+        t0 = time.perf_counter()
+        fn(k); mirt.sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    def intersect(q):
+        mirt.intersect_device(d_rays, q, d_rec)
+
+    def ordered(m):
+        return lambda q: mirt.intersect_ordered_device(d_rays, q, None, m, d_hits, d_cnt)
+
+    def peels(m):
+        def fn(q):
+            for _ in range(m):
+                mirt.intersect_ordered_device(d_rays, q, d_rec, 1, d_rec, d_cnt)
+        return fn
+
+    def back(ptr, count, dtype):
+        out = np.zeros(count, dtype)
+        assert h.hipMemcpy(out.ctypes.data_as(C.c_void_p), ptr, out.nbytes, 2) == 0
+        return out
+
+    k = 1
+    while k <= top:
+        res = {}
+        for on in (False, True):
+            mirt.set_ray_grid(on)
+            run(intersect, k)
+            res[on, 0] = back(d_rec, k, mirt.HIT_DTYPE)
+            for m in ORDERED_HITS:
+                run(ordered(m), k)
+                res[on, m] = back(d_hits, k * m, mirt.HIT_DTYPE).reshape(k, m), back(d_cnt, k, np.int32)
+        st = mirt.ray_grid_stats()
+        assert st["mode_used"] == mirt.QUERY_BINNED and st["gave_up"] == 0, st
+        for m in ORDERED_HITS:
+            assert res[True, m][0].tobytes() == res[False, m][0].tobytes() and np.array_equal(res[True, m][1], res[False, m][1]), "the grid disagrees with the sweep"
+            hit = res[False, m][1] > 0
+            assert np.array_equal(hit, res[False, 0]["index"] >= 0) and res[False, m][0][:, 0][hit].tobytes() == res[False, 0][hit].tobytes(), "slot 0 is not mirt_intersect_device's record"
+        mirt.set_ray_grid(False)
+        assert h.hipMemcpy(d_rec, behind.ctypes.data_as(C.c_void_p), 20 * k, 1) == 0
+        for s in range(8):
+            peels(1)(k); mirt.sync()
+            assert back(d_rec, k, mirt.HIT_DTYPE).tobytes() == np.ascontiguousarray(res[False, 8][0][:, s]).tobytes(), "peel %d differs from slot %d" % (s, s)
+        reps = 5 if k <= 16384 else 3
+        ms = {}
+        for state in ("off", "built", "kept"):
+            mirt.set_ray_grid(state != "off")
+            calls = [("int", intersect, fresh)] + [("ord%d" % m, ordered(m), fresh) for m in ORDERED_HITS]
+            if state != "built":
+                calls += [("peel%d" % m, peels(m), behind) for m in ORDERED_HITS[1:]]
+            for name, fn, start in calls:
+                ts = [run(fn, k, start, rebuild=state == "built") for _ in range(reps + 1)]
+                if state != "off":
+                    assert mirt.ray_grid_stats()["source"] == (1 if state == "built" else 2)
+                ms[state, name] = float(np.median(ts[1:]))
+        mirt.set_ray_grid(False)
+        two = float((res[False, 2][1] >= 2).mean())
+        print("RESULT ordered n %6d %-10s rays %8d hit %.3f two %.3f eight %.3f  " % (n, which, k, float((res[False, 1][1] > 0).mean()), two, float((res[False, 8][1] == 8).mean()))
+              + "  ".join("%s %s" % (state, " ".join("%10.4f" % ms[state, c] for c in ORDERED_COLS[state])) for state in ("off", "built", "kept")) + " ms")
+        sys.stdout.flush()
+        k = k * 4 if k * 4 <= top or k == top else top
+    mirt.shutdown()
+
+
+ORDERED_COLS = {"off": ("int", "ord1", "ord2", "ord4", "ord8", "peel2", "peel4", "peel8"), "built": ("int", "ord1", "ord2", "ord4", "ord8"),
+                "kept": ("int", "ord1", "ord2", "ord4", "ord8", "peel2", "peel4", "peel8")}
+ORDERED_ROW = re.compile(r"ordered n\s+(\d+) (\w+)\s+rays\s+(\d+) hit [0-9.]+ two [0-9.]+ eight [0-9.]+  off((?:\s+[0-9.]+){8})  built((?:\s+[0-9.]+){5})  kept((?:\s+[0-9.]+){8}) ms")
+
+
+def step_ordered(p):
+    p("== ordered: mirt_intersect_ordered_device, max_hits 1, 2, 4, 8, after NULL, on the grid section's scenes and ray sets, beside two yardsticks in the")
+    p("   same run on the same rays: mirt_intersect_device from fresh records (int), and max_hits in-place peels of the max_hits == 1 call (peelN:")
+    p("   N calls with after == hits, one mirt_sync); host clock around call + mirt_sync, medians; answers compared first ==")
+    p("three groups: the switch of mirt_set_ray_grid off (columns int ord1 ord2 ord4 ord8 peel2 peel4 peel8); on, the structure built by the call (int ord1 ord2")
+    p("ord4 ord8); on, the structure held (as off).  hit / two / eight: the share of rays with a hit, with two or more, with eight or more")
+    out = "".join(run_child(p, ["--child", "ordered", str(n), which], {}, 420) for n in (100000, 2000) for which in GRID_SETS)
+    ordered_summary(out, p)
+
+
+def ordered_summary(text, p):
+    """Where max_hits == 1 stands against mirt_intersect_device and max_hits == N against N peels, per switch state: the spread of the
+    ratios and every cell that is behind by more than the 2 % two runs differ by."""
+    rows = []
+    for m in ORDERED_ROW.finditer(text):
+        v = {}
+        for state, g in (("off", 4), ("built", 5), ("kept", 6)):
+            v.update({(state, c): float(x) for c, x in zip(ORDERED_COLS[state], m.group(g).split())})
+        rows.append((int(m.group(1)), m.group(2), int(m.group(3)), v))
+    pairs = [("max_hits 1 against mirt_intersect_device", "ord1", "int", ("off", "built", "kept"))]
+    pairs += [("max_hits %d against %d peels" % (m, m), "ord%d" % m, "peel%d" % m, ("off", "kept")) for m in ORDERED_HITS[1:]]
+    for what, a, b, states in pairs:
+        for state in states:
+            ratio = [(v[state, a] / v[state, b], n, w, k, v[state, a], v[state, b]) for n, w, k, v in rows]
+            if not ratio:
+                continue
+            rs = sorted(r[0] for r in ratio)
+            behind = [r for r in ratio if r[0] > 1.02]
+            p("%s, switch %s: time ratio min %.2f median %.2f max %.2f; behind by more than 2 %% in %d of %d cells" % (what, state, rs[0], rs[len(rs) // 2], rs[-1], len(behind), len(ratio)))
+            for r, n, w, k, x, y in behind:
+                p("  n %d %s rays %d: %.4f ms against %.4f ms" % (n, w, k, x, y))
+    p("")
+
+
 # ---- several directions in one call: mirt_intersect_alongs_device / mirt_occluded_alongs_device ------------------------------------------
 
 ALONGS_K = (1, 4, 15, 16, 32, 64)
@@ -1386,6 +1520,8 @@ def main():
             return child_along(int(a.child[1]))
         if a.child[0] == "grid":
             return child_grid(int(a.child[1]), a.child[2])
+        if a.child[0] == "ordered":
+            return child_ordered(int(a.child[1]), a.child[2])
         if a.child[0] == "alongs":
             return child_alongs(int(a.child[1]), int(a.child[2]))
         if a.child[0] == "mask":
@@ -1422,6 +1558,8 @@ def main():
             step_alongs(p)
         if "grid" in steps:
             step_grid(p)
+        if "ordered" in steps:
+            step_ordered(p)
     finally:
         with open(a.out, "a" if a.append else "w") as f:
             f.write("\n".join(lines) + "\n")
