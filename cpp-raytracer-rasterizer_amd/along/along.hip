@@ -8,7 +8,7 @@
 // along_walk.hpp, which the kernels of several directions in one call (alongs.hip) run too.
 // Built with -ffp-contract=off like every kernel of the library.
 #include "along_file.hpp"
-#include "along_walk.hpp"
+#include "along_lanes.hpp"
 
 namespace mirt {
 
@@ -51,12 +51,7 @@ __global__ __launch_bounds__(256) void k_along_expand(const AlongExpand x)
 // ---- the walks ---------------------------------------------------------------------------------------------------------------------
 //
 // One direction: the descriptor, the tables and dir are the kernel's arguments, the same for every lane; the direction's keys start
-// at 0.  A lane beyond the call's rays reads ray 0's start and is not `mine` (along_walk.hpp).
-__device__ __forceinline__ AlongLane along_lane(const AlongFrame &f, long long ray, bool ok)
-{
-    return along_walk_of(f.v.d, 0u, V3(f.dir[0], f.dir[1], f.dir[2]), scene_rows_in_range(f.q), ld3(f.origins + 3 * (size_t)(ok ? ray : 0)));
-}
-
+// at 0.  A lane beyond the call's rays reads ray 0's start and is not `mine` (along_walk.hpp); along_lane: along_lanes.hpp.
 template <bool STATS>
 __global__ __launch_bounds__(256) void k_along_closest(const AlongFrame f)
 {

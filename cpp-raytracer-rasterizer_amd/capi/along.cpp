@@ -9,7 +9,7 @@
 namespace mirt {
 
 // The arguments first, then the library's state: a malformed call is told so whether or not there is a device.
-static int check_along_args(const float *dir, const void *origins3, int nrays, const void *out)
+int check_along_args(const float *dir, const void *origins3, int nrays, const void *out)
 {
     if (nrays < 0) return fail(MIRT_ERR_INVALID_ARGUMENT, "origin count %d is negative", nrays);
     if (nrays > 0 && (!origins3 || !out)) return fail(MIRT_ERR_INVALID_ARGUMENT, "origin arrays must not be NULL when the count is > 0");
@@ -18,7 +18,7 @@ static int check_along_args(const float *dir, const void *origins3, int nrays, c
 }
 
 // The rays written out into the stream's query scratch, for the brute-force kernels (as fans_expand does for the many-origin call).
-static int along_expand(const float *dir, const void *d_origins3, int nrays)
+int along_expand(const float *dir, const void *d_origins3, int nrays)
 {
     int rc;
     QueryScratch &S = g.cur().query;
@@ -148,7 +148,7 @@ static int along_ensure(AlongCache &C, const float *dir, const AlongDesc &desc, 
 // and ahead in every cell from 16 384 rays on; with the grid held it is ahead everywhere at 100 000 triangles and from 4096 rays on
 // at 2000 (2 - 4 us behind in eight smaller cells).  So the rule is the many-origin fans' as it stands (auto_bins_fans): the fans'
 // rule AND more than MIRT_QUERY_WAVE_RAYS rays -- or the grid is held.
-static int along_begin(const float *dir, const void *d_origins3, int nrays, AlongFrame *frame, bool *binned)
+int along_begin(const float *dir, const void *d_origins3, int nrays, AlongFrame *frame, bool *binned)
 {
     int rc;
     AlongCache &C = g.qrows.along;

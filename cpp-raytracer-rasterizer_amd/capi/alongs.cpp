@@ -23,7 +23,7 @@ static int alongs_args(const float *dirs3, int ndirs, const void *dir_of, const 
     if (ndirs > 1 && !dir_of) return fail(MIRT_ERR_INVALID_ARGUMENT, "dir_of may be NULL only for a single direction, not for %d", ndirs);
     return MIRT_OK;
 }
-static int check_alongs_args(const float *dirs3, int ndirs, const void *dir_of, const void *origins3, int nrays, const void *out)
+int check_alongs_args(const float *dirs3, int ndirs, const void *dir_of, const void *origins3, int nrays, const void *out)
 {
     int rc;
     if ((rc = alongs_args(dirs3, ndirs, dir_of, origins3, nrays, out))) return rc;
@@ -31,7 +31,7 @@ static int check_alongs_args(const float *dirs3, int ndirs, const void *dir_of, 
 }
 // The host form looks at every index before anything touches the device; the device form cannot (its kernels leave such a ray's
 // record unwritten and write its byte 0).
-static int check_alongs_host_args(const float *dirs3, int ndirs, const int32_t *dir_of, const float *origins3, int nrays, const void *out)
+int check_alongs_host_args(const float *dirs3, int ndirs, const int32_t *dir_of, const float *origins3, int nrays, const void *out)
 {
     int rc;
     if ((rc = alongs_args(dirs3, ndirs, dir_of, origins3, nrays, out))) return rc;
@@ -209,8 +209,8 @@ static int alongs_ensure(AlongsGroup &G, const AlongsCall &c, const float *dirs,
 // launched, its pass's group remembers it, and the WHOLE call takes the brute path, as a many-origin call does for an origin that
 // cannot be binned.  A slot whose every-ray list outgrows its share is known only behind its group's build: the call takes the brute
 // path from there -- the records and bytes the earlier passes wrote are what it writes again.
-template <class Launch, class Brute>
-static int alongs_run(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, AlongsFrame &f, Launch launch, Brute brute)
+int alongs_run(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, AlongsFrame &f,
+               const std::function<int(const AlongsFrame &)> &launch, const std::function<int()> &brute)
 {
     int rc;
     AlongsCall c;

@@ -19,6 +19,7 @@
 #include "../along/alongs.hpp"
 #include "../grid/ray_grid.hpp"
 #include "../order/ordered_hits.hpp"
+#include "../order/ordered_along.hpp"
 #include "../lights/many_lights.hpp"
 #include "../lights/aa_many_lights.hpp"
 #include "cube_plan.hpp"
@@ -34,6 +35,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <functional>
 #include <cmath>
 #include <vector>
 
@@ -271,6 +273,9 @@ struct QueryScratch {
     size_t carry_cap = 0;                        // records
     // mirt_direct_light_masked*: lpos / lcol of the call's positions, MIRT_MAX_LIGHT_POSITIONS x 6 floats (k_query_relight)
     float *d_relight = nullptr;
+    // mirt_intersect_ordered_alongs* peeling in place (after == hits): the `after` records set aside before the first pass writes
+    uint32_t *d_order_after = nullptr;           // order_after_cap x HIT_WORDS
+    size_t order_after_cap = 0;
 
     void release();
 };
@@ -790,6 +795,12 @@ int along_occluded_host(const float *dir, const float *origins3, int nrays, cons
 // What alongs.cpp shares with along.cpp: the start of a build under the streams' protocol, and its end.
 int along_build_begin();
 int along_build_end();
+// What the ordered calls along a direction (order_along.cpp) share with it: the argument checks, the decision and structure step of
+// a call on the stream it takes (*binned says whether `frame` is ready for a walk kernel; the statistics of QUERY_ALONG begun
+// afresh), and the rays written out into the stream's query scratch (g.cur().query.d_fan_rays) for a sweep.
+int check_along_args(const float *dir, const void *origins3, int nrays, const void *out);
+int along_begin(const float *dir, const void *d_origins3, int nrays, AlongFrame *frame, bool *binned);
+int along_expand(const float *dir, const void *d_origins3, int nrays);
 
 // ---- arbitrary rays through the cell grid (ray_grid.cpp; the kernels: ../grid/ray_grid.hip) ----
 // With the switch on, on the stream the call has taken: *done says the walk kernel was queued; otherwise the caller sweeps.
@@ -803,12 +814,30 @@ long query_wave_rays();
 // ---- every hit along a ray, in order (order.cpp; the kernels: ../order/ordered_hits.hip) ----
 int order_intersect(const void *d_rays, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts);
 int order_intersect_host(const mirt_ray *rays, int nrays, const mirt_hit *after, int max_hits, mirt_hit *hits, int32_t *counts);
+// What order_along.cpp shares with it: the checks of the arguments alone, the sweep on the current stream (d_dir_of / ndirs:
+// OrderFrame::dir_of, NULL for none) and the host form's staging arrays.
+int order_args(const void *rays, int nrays, const void *after, int max_hits, const void *hits, const void *counts);
+int order_launch(const void *d_rays, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts, const void *d_dir_of, int ndirs);
+int order_staging(int checked, int nrays, int max_hits);
+// ... along one direction and along several (order_along.cpp; the kernels: ../order/ordered_along.hip)
+int order_along(const float *dir, const void *d_origins3, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts);
+int order_along_host(const float *dir, const float *origins3, int nrays, const mirt_hit *after, int max_hits, mirt_hit *hits, int32_t *counts);
+int order_alongs(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, const void *d_after, int max_hits,
+                 void *d_hits, void *d_counts);
+int order_alongs_host(const float *dirs3, int ndirs, const int32_t *dir_of, const float *origins3, int nrays, const mirt_hit *after, int max_hits,
+                      mirt_hit *hits, int32_t *counts);
 
 // ---- ray queries along several directions in one call (alongs.cpp; the kernels: ../along/alongs.hip) ----
 int alongs_intersect(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, void *d_hits);
 int alongs_intersect_host(const float *dirs3, int ndirs, const int32_t *dir_of, const float *origins3, int nrays, mirt_hit *hits);
 int alongs_occluded(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, const void *d_max_distance, void *d_occluded);
 int alongs_occluded_host(const float *dirs3, int ndirs, const int32_t *dir_of, const float *origins3, int nrays, const float *max_distance, uint8_t *occluded);
+// What order_along.cpp shares with it: the argument checks, and a whole call on the stream it takes -- the plan, the groups, launch(f)
+// per pass with `f` carrying the caller's arrays, or the rays written out (g.cur().query.d_fan_rays) and brute().
+int check_alongs_args(const float *dirs3, int ndirs, const void *dir_of, const void *origins3, int nrays, const void *out);
+int check_alongs_host_args(const float *dirs3, int ndirs, const int32_t *dir_of, const float *origins3, int nrays, const void *out);
+int alongs_run(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, AlongsFrame &f,
+               const std::function<int(const AlongsFrame &)> &launch, const std::function<int()> &brute);
 
 // ---- rasteriser (raster.cpp) ----
 int raster_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect,

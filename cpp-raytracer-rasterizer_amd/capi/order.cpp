@@ -15,10 +15,9 @@ static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
     return x < y + nb && y < x + na;
 }
 
-static int check_order_args(const void *rays, int nrays, const void *after, int max_hits, const void *hits, const void *counts)
+// The arguments alone: what the calls along a direction (order_along.cpp) check too, in front of their own.
+int order_args(const void *rays, int nrays, const void *after, int max_hits, const void *hits, const void *counts)
 {
-    int rc;
-    if ((rc = need_init())) return rc;
     if (nrays < 0) return fail(MIRT_ERR_INVALID_ARGUMENT, "ray count %d is negative", nrays);
     if (max_hits < 1 || max_hits > MIRT_MAX_ORDERED_HITS)
         return fail(MIRT_ERR_INVALID_ARGUMENT, "max_hits %d is outside [1, %d]", max_hits, MIRT_MAX_ORDERED_HITS);
@@ -29,10 +28,42 @@ static int check_order_args(const void *rays, int nrays, const void *after, int 
         return fail(MIRT_ERR_INVALID_ARGUMENT, "after overlaps hits (allowed only as after == hits with max_hits == 1)");
     return MIRT_OK;
 }
+static int check_order_args(const void *rays, int nrays, const void *after, int max_hits, const void *hits, const void *counts)
+{
+    int rc;
+    if ((rc = need_init())) return rc;
+    return order_args(rays, nrays, after, max_hits, hits, counts);
+}
 
 // The kernel of list length K = 1, 2, 4 or 8 out of a table of the four instantiations.
 template <class Kernel>
 static Kernel order_pick(int K, Kernel k1, Kernel k2, Kernel k4, Kernel k8) { return K == 1 ? k1 : (K == 2 ? k2 : (K == 4 ? k4 : k8)); }
+
+// The sweep of a call on the stream it has taken, as intersect_launch is mirt_intersect's: the scene's rows, then a wave per ray up
+// to query_wave_rays(), a lane per ray beyond.  d_dir_of (nullable) / ndirs: OrderFrame::dir_of.
+int order_launch(const void *d_rays, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts, const void *d_dir_of, int ndirs)
+{
+    int rc;
+    if ((rc = query_rows())) return rc;
+    OrderFrame o;
+    memset(&o, 0, sizeof o);
+    o.f.q = rows_frame(d_rays, nrays, d_hits);
+    o.after = static_cast<const uint32_t *>(d_after);
+    o.max_hits = max_hits;
+    o.counts = static_cast<int32_t *>(d_counts);
+    o.dir_of = static_cast<const int32_t *>(d_dir_of);
+    o.ndirs = ndirs;
+    const int K = hit_list_size_for(max_hits);
+    if ((long)nrays <= query_wave_rays()) {
+        hipLaunchKernelGGL(order_pick(K, k_order_sweep_wave<1>, k_order_sweep_wave<2>, k_order_sweep_wave<4>, k_order_sweep_wave<8>),
+                           dim3((unsigned)((nrays + 3) / 4)), dim3(256), 0, g.stream, o);
+    } else {
+        hipLaunchKernelGGL(order_pick(K, k_order_sweep<1>, k_order_sweep<2>, k_order_sweep<4>, k_order_sweep<8>),
+                           dim3((unsigned)((nrays + 255) / 256)), dim3(256), sweep_lds_bytes(), g.stream, o);
+    }
+    HIP_TRY(hipGetLastError());
+    return MIRT_OK;
+}
 
 int order_intersect(const void *d_rays, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts)
 {
@@ -46,33 +77,21 @@ int order_intersect(const void *d_rays, int nrays, const void *d_after, int max_
     memset(&o, 0, sizeof o);
     bool binned = false;
     if (g.ray_grid && (rc = grid_begin(d_rays, nrays, &o.f, &binned))) return rc;    // (the statistics of mirt_get_ray_grid_stats begin here)
-    if (!binned) {
-        if ((rc = query_rows())) return rc;
-        memset(&o.f, 0, sizeof o.f);
-        o.f.q = rows_frame(d_rays, nrays, nullptr);
-    }
+    if (!binned) return order_launch(d_rays, nrays, d_after, max_hits, d_hits, d_counts, nullptr, 0);
     o.f.q.hits = static_cast<uint32_t *>(d_hits);
     o.after = static_cast<const uint32_t *>(d_after);
     o.max_hits = max_hits;
     o.counts = static_cast<int32_t *>(d_counts);
-    if (binned) {
-        const auto kernel = o.f.stats ? order_pick(K, k_grid_order<1, true>, k_grid_order<2, true>, k_grid_order<4, true>, k_grid_order<8, true>)
-                                      : order_pick(K, k_grid_order<1, false>, k_grid_order<2, false>, k_grid_order<4, false>, k_grid_order<8, false>);
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, g.stream, o);
-    } else if ((long)nrays <= query_wave_rays()) {
-        hipLaunchKernelGGL(order_pick(K, k_order_sweep_wave<1>, k_order_sweep_wave<2>, k_order_sweep_wave<4>, k_order_sweep_wave<8>),
-                           dim3((unsigned)((nrays + 3) / 4)), dim3(256), 0, g.stream, o);
-    } else {
-        hipLaunchKernelGGL(order_pick(K, k_order_sweep<1>, k_order_sweep<2>, k_order_sweep<4>, k_order_sweep<8>),
-                           dim3((unsigned)((nrays + 255) / 256)), dim3(256), sweep_lds_bytes(), g.stream, o);
-    }
+    const auto kernel = o.f.stats ? order_pick(K, k_grid_order<1, true>, k_grid_order<2, true>, k_grid_order<4, true>, k_grid_order<8, true>)
+                                  : order_pick(K, k_grid_order<1, false>, k_grid_order<2, false>, k_grid_order<4, false>, k_grid_order<8, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, g.stream, o);
     HIP_TRY(hipGetLastError());
     return MIRT_OK;
 }
 
 // The host form's staging arrays are its own and grow by their own measure (up to 160 bytes of records a ray), once the checks have
 // passed and there is something to stage.
-static int order_staging(int checked, int nrays, int max_hits)
+int order_staging(int checked, int nrays, int max_hits)
 {
     int rc;
     QueryRows &Q = g.qrows;

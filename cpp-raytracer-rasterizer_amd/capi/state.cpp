@@ -106,7 +106,7 @@ void CostHist::release()
 void QueryScratch::release()
 {
     dev_free({ d_light_tab, d_origins, d_flags, d_stats[QUERY_DIRECT_LIGHT], d_stats[QUERY_FAN], d_stats[QUERY_OCCLUDED], d_stats[QUERY_SHADOW_MASK], d_stats[QUERY_ALONG], d_fan_origins, d_fan_rays, d_carry,
-               d_relight });
+               d_relight, d_order_after });
     *this = QueryScratch();
 }
 

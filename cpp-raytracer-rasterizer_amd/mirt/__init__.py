@@ -36,6 +36,7 @@ EXPORTS = (
     "mirt_intersect_alongs", "mirt_intersect_alongs_device", "mirt_occluded_alongs", "mirt_occluded_alongs_device",
     "mirt_set_ray_grid", "mirt_get_ray_grid_stats",
     "mirt_intersect_ordered", "mirt_intersect_ordered_device",
+    "mirt_intersect_ordered_along", "mirt_intersect_ordered_along_device", "mirt_intersect_ordered_alongs", "mirt_intersect_ordered_alongs_device",
     "mirt_shadow_mask", "mirt_shadow_mask_device", "mirt_direct_light_masked", "mirt_direct_light_masked_device", "mirt_get_shadow_mask_stats",
     "mirt_scene_upload_device", "mirt_scene_update_device", "mirt_scene_update", "mirt_scene_transform", "mirt_transform",
     "mirt_scene_download", "mirt_scene_info",
@@ -190,6 +191,10 @@ def load():
     lib.mirt_get_ray_grid_stats.argtypes = [C.POINTER(RayGridStats)]
     lib.mirt_intersect_ordered.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp]
     lib.mirt_intersect_ordered_device.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp]
+    lib.mirt_intersect_ordered_along.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
+    lib.mirt_intersect_ordered_along_device.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
+    lib.mirt_intersect_ordered_alongs.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
+    lib.mirt_intersect_ordered_alongs_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
     lib.mirt_intersect_alongs.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp]
     lib.mirt_intersect_alongs_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp]
     lib.mirt_occluded_alongs.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]
@@ -896,7 +901,7 @@ def occluded_along_device(direction, d_origins, nrays, d_max_distance, d_occlude
 
 
 def along_stats():
-    """The last intersect_along* / occluded_along* / intersect_alongs* / occluded_alongs* call (mirt_get_along_stats), in
+    """The last intersect_along* / occluded_along* / intersect_alongs* / occluded_alongs* / intersect_ordered_along(s)* call (mirt_get_along_stats), in
     mirt_query_stats' fields: mode_used, cube_source (0 no grid, 1 built by the call, 2 kept), cube_bins = cells per grid side, shells
     and -- profiling on, binned -- shadow_rays = rays, candidates = rows offered, tests = rows tested, fallback_records = rays that
     swept the scene.  For a call of several directions the counters are summed over its passes, and cube_source is 1 when some pass
@@ -953,6 +958,53 @@ def occluded_alongs_device(directions, d_dir_of, d_origins, nrays, d_max_distanc
     d_max_distance for +inf), queued like a *_device frame."""
     directions = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
     _check(load().mirt_occluded_alongs_device(_ptr(directions), len(directions), d_dir_of, d_origins, int(nrays), d_max_distance, d_occluded))
+
+
+# ---- every hit along parallel rays, in order ------------------------------------------------------------------
+
+def _ordered_arrays(n, max_hits, after):
+    """max_hits, the `after` records (or None) and the outputs of an ordered call of n rays."""
+    max_hits = int(max_hits)
+    if after is not None:
+        after = np.ascontiguousarray(after, HIT_DTYPE)
+        if after.shape != (n,):
+            raise ValueError("%d origins but after has shape %s" % (n, after.shape))
+    return max_hits, after, np.zeros((n, max(max_hits, 0)), HIT_DTYPE), np.zeros(n, np.int32)
+
+
+def intersect_ordered_along(direction, origins, max_hits, after=None):
+    """intersect_ordered() for the rays {origins[i], direction}, byte for byte, through the grid of intersect_along where that pays
+    (mirt_intersect_ordered_along; set_query_mode, along_stats): (hits[n, max_hits] HIT_DTYPE, counts[n] int32).  The thickness of a
+    part along a beam is hits["distance"][:, 1] - hits["distance"][:, 0] where counts >= 2."""
+    direction, origins = _as_along(direction, origins)
+    max_hits, after, hits, counts = _ordered_arrays(len(origins), max_hits, after)
+    _check(load().mirt_intersect_ordered_along(_ptr(direction), _ptr(origins), len(origins), _ptr(after), max_hits, _ptr(hits), _ptr(counts)))
+    return hits, counts
+
+
+def intersect_ordered_along_device(direction, d_origins, nrays, d_after, max_hits, d_hits, d_counts):
+    """The same on device arrays (raw pointers; the direction is host data, d_after may be None, or d_hits itself when max_hits is
+    1), queued like a *_device frame; mirt.sync() completes it."""
+    direction = np.ascontiguousarray(direction, np.float32).reshape(3)
+    _check(load().mirt_intersect_ordered_along_device(_ptr(direction), d_origins, int(nrays), d_after, int(max_hits), d_hits, d_counts))
+
+
+def intersect_ordered_alongs(directions, dir_of, origins, max_hits, after=None):
+    """intersect_ordered() for the rays {origins[i], directions[dir_of[i]]}, byte for byte, through the groups of intersect_alongs
+    (mirt_intersect_ordered_alongs): (hits[n, max_hits], counts[n]).  dir_of: one int32 per ray, or None for a single direction."""
+    directions, dir_of, origins = _as_alongs(directions, dir_of, origins)
+    max_hits, after, hits, counts = _ordered_arrays(len(origins), max_hits, after)
+    _check(load().mirt_intersect_ordered_alongs(_ptr(directions), len(directions), _ptr(dir_of), _ptr(origins), len(origins), _ptr(after), max_hits,
+                                                _ptr(hits), _ptr(counts)))
+    return hits, counts
+
+
+def intersect_ordered_alongs_device(directions, d_dir_of, d_origins, nrays, d_after, max_hits, d_hits, d_counts):
+    """The same on device arrays (raw pointers; the directions are host data, d_dir_of may be None for a single direction).  A ray
+    whose index names no direction keeps its slots as they were and gets the count 0."""
+    directions = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+    _check(load().mirt_intersect_ordered_alongs_device(_ptr(directions), len(directions), d_dir_of, d_origins, int(nrays), d_after, int(max_hits),
+                                                       d_hits, d_counts))
 
 
 # ---- shadow masks: DirectLight's shadow decisions, and DirectLight from them ---------------------------------

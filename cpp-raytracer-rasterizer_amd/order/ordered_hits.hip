@@ -11,62 +11,15 @@
 //   k_order_sweep_wave<K>  a wave per ray, lanes stride over the rows and keep the K best of their own, then K extraction rounds;
 //   k_grid_order<K, STATS> a lane per ray through the cell grid (k_grid_closest's walk), reach = the list's bound.
 // Positions do not travel with the keys: the K winners are tested once more at the end (exact_hit_row on the winner's row gives the
-// same bits -- the same operations on the same operands, no fused forms) and the list stays at two registers an entry.
+// same bits -- the same operations on the same operands, no fused forms) and the list stays at two registers an entry
+// (order_device.hpp: order_after, order_store_slot, order_store_list, which ordered_along.hip shares).
 // The `after` record of a ray is read before any of its slots is written, by the lane or wave that writes them: with max_hits == 1
 // the caller may pass the output array itself.
 // Built with -ffp-contract=off like every kernel of the library.
-#include "ordered_hits.hpp"
+#include "order_device.hpp"
 #include "../grid/ray_grid_device.hpp"
-#include "../query/rt_query_device.hpp"
 
 namespace mirt {
-
-// The record (a, k) ray `ray` continues behind: the caller's, or one that admits everything (no `after`: every eligible distance is
-// above -1), or for a lane without a ray one that admits nothing (NaN).
-__device__ __forceinline__ void order_after(const OrderFrame &o, long long ray, bool ok, float *a, int *k)
-{
-    *a = ok ? -1.0f : __uint_as_float(0x7fc00000u);
-    *k = 0;
-    if (ok && o.after) {
-        const uint32_t *r = o.after + (size_t)HIT_WORDS * ray;
-        *a = __uint_as_float(r[3]);
-        *k = (int)r[4];
-    }
-}
-
-// Slot `slot` of ray `ray`: the winner `key` as a whole struct Intersection -- its position from the test run once more --, or
-// Update()'s reset for an empty entry.
-__device__ __forceinline__ void order_store_slot(const OrderFrame &o, long long ray, int slot, unsigned long long key, v3 S, v3 nd)
-{
-    const QueryFrame &q = o.f.q;
-    uint32_t *h = q.hits + (size_t)HIT_WORDS * ((size_t)ray * (size_t)o.max_hits + (size_t)slot);
-    if (key == HIT_KEY_NONE) {
-        store_record(h, V3(0.0f, 0.0f, 0.0f), 0x7f7fffffu, 0xffffffffu);                   // :335-339: FLT_MAX, -1
-        return;
-    }
-    const int tri = hit_key_index(key);
-    const float4 *src = reinterpret_cast<const float4 *>(q.rows + tri);
-    const RowVecs r = unpack_row(src[0], src[1], src[2]);
-    float e1e2b, dist;
-    const TestDots td = ray_dots(r, S, nd, &e1e2b);
-    v3 hp = V3(0.0f, 0.0f, 0.0f);
-    (void)exact_hit_row(td, e1e2b, r, S, &hp, &dist);
-    store_record(h, hp, hit_key_distance_bits(key), (uint32_t)tri);
-}
-
-// A lane's whole answer: its max_hits slots from its own list, and the count.
-template <int K>
-__device__ __forceinline__ void order_store_list(const OrderFrame &o, long long ray, const HitList<K> &l, v3 S, v3 nd)
-{
-    int cnt = 0;
-#pragma unroll
-    for (int s = 0; s < K; s++)
-        if (s < o.max_hits) {
-            order_store_slot(o, ray, s, l.k[s], S, nd);
-            cnt += (int)(l.k[s] != HIT_KEY_NONE);
-        }
-    o.counts[ray] = cnt;
-}
 
 // ---- k_order_sweep: one lane per ray, every ray tests every triangle -------------------------------------------------------------------
 // Workgroup = 256 lanes = 256 rays.  The rows are staged through LDS in chunks of RT_CHUNK_ROWS and read as wave-uniform broadcasts.
@@ -102,7 +55,8 @@ __global__ __launch_bounds__(256) void k_order_sweep(const OrderFrame o)
             }
         }
     }
-    if (ok) order_store_list(o, ray, l, start, nd);
+    if (ok && order_named(o, ray)) order_store_list(o, ray, l, start, nd);
+    else if (ok) o.counts[ray] = 0;                                // (a ray of the along calls that names no direction: slots untouched)
 }
 
 template __global__ void k_order_sweep<1>(const OrderFrame);
@@ -153,7 +107,7 @@ __global__ __launch_bounds__(256) void k_order_sweep_wave(const OrderFrame o)
             if (lane == s) mine = best;
             cnt += (int)(best != HIT_KEY_NONE);
         }
-    if (lane < o.max_hits) order_store_slot(o, ray, lane, mine, start, nd);
+    if (lane < o.max_hits && order_named(o, ray)) order_store_slot(o, ray, lane, mine, start, nd);
     if (lane == 0) o.counts[ray] = cnt;
 }
 

@@ -14,6 +14,8 @@ struct OrderFrame {
     const uint32_t *after;       // nrays records of HIT_WORDS words, or NULL: only distance and index are read
     int max_hits;                // 1 .. K of the instantiation
     int32_t *counts;             // nrays
+    const int32_t *dir_of;       // the sweeps of mirt_intersect_ordered_alongs*: the rays' indices into the call's ndirs directions; a ray
+    int ndirs;                   // whose index names none keeps its slots and gets the count 0.  NULL: every ray is answered
 };
 
 template <int K> __attribute__((global)) void k_order_sweep(const OrderFrame);

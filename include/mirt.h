@@ -692,6 +692,25 @@ MIRT_API int mirt_intersect_ordered(const mirt_ray *rays, int nrays, const mirt_
                                     mirt_hit *hits /* nrays * max_hits, ray-major */, int32_t *counts /* nrays */);
 MIRT_API int mirt_intersect_ordered_device(const void *d_rays, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts);
 
+/* The same along parallel rays: the thickness of a part along a beam, X-ray and CT projections, voxelisation and point-in-mesh tests
+ * by counting crossings along parallel lines, transparency layers under an orthographic camera.  The four calls are
+ * mirt_intersect_ordered on the rays {origins[i], dir} or {origins[i], dirs[dir_of[i]]}, byte for byte: max_hits, `after`, the slots,
+ * the counts and the overlap rule (after == hits only with max_hits == 1) are that call's, the directions, origins and dir_of those
+ * of mirt_intersect_along* / mirt_intersect_alongs*, and the argument checks the union of both (MIRT_ERR_INVALID_ARGUMENT, nothing
+ * written; nrays == 0 does nothing).  They are dispatched as the along calls are: mirt_set_query_mode applies, AUTO is their rule,
+ * the grid kept per (scene, direction) and the kept groups of directions are the very ones those calls build and use, and
+ * mirt_get_along_stats reports the call.  What is not binned sweeps every triangle; mirt_set_ray_grid does not affect these calls.
+ * An index of dir_of outside [0, ndirs): the host form refuses the call; the _device form leaves that ray's slots unwritten and writes
+ * its count 0. */
+MIRT_API int mirt_intersect_ordered_along(const float dir[3], const float *origins3, int nrays, const mirt_hit *after /* nullable */, int max_hits,
+                                          mirt_hit *hits /* nrays * max_hits, ray-major */, int32_t *counts /* nrays */);
+MIRT_API int mirt_intersect_ordered_along_device(const float dir[3], const void *d_origins3, int nrays, const void *d_after, int max_hits, void *d_hits,
+                                                 void *d_counts);
+MIRT_API int mirt_intersect_ordered_alongs(const float *dirs3, int ndirs, const int32_t *dir_of /* nullable */, const float *origins3, int nrays,
+                                           const mirt_hit *after /* nullable */, int max_hits, mirt_hit *hits, int32_t *counts);
+MIRT_API int mirt_intersect_ordered_alongs_device(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, const void *d_after,
+                                                  int max_hits, void *d_hits, void *d_counts);
+
 /* ---- shadow masks: DirectLight's shadow decision per (record, light position), and DirectLight from a mask (additions to ABI 4) ---- */
 
 /* The one value DirectLight computes and throws away (raytracer.cpp:306-315): whether the shadow ray of a record towards a light

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans,occluded,mask,along,alongs,grid,ordered]
+"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans,occluded,mask,along,alongs,grid,ordered,ordered_along]
 
 The measurements of the ray-query kernels (query/rt_query.hip), written to one text file:
 
@@ -37,6 +37,11 @@ The measurements of the ray-query kernels (query/rt_query.hip), written to one t
                        mirt_intersect_device from fresh records and beside max_hits in-place peels of the max_hits == 1 call, in the same
                        run on the same rays.  The answers are compared first; the cells where max_hits == 1 is behind mirt_intersect_device
                        and where max_hits == N is behind N peels are listed.
+  ordered_along        mirt_intersect_ordered_along_device, max_hits 1, 2, 4, 8, on the along step's grid of starts looking down the soup of
+                       2000 and of 100 000 triangles, 1 .. 2^20 rays in powers of four, with its build and with the grid held, beside
+                       mirt_intersect_ordered_device on the same rays written out -- the switch of mirt_set_ray_grid off, and on with the
+                       ray grid held -- and, for max_hits 1, beside mirt_intersect_along_device, in the same run.  The answers are compared
+                       first; every cell is recorded and the cells where the new call is behind a yardstick by more than 2 % are listed.
   mask                 mirt_shadow_mask_device and mirt_direct_light_masked_device beside mirt_direct_light_device on the same records, lights
                        and cubes, the three calls in turn: 2^10 .. 2^21 records x 1, 2, 32, 64, 256 positions x 2000 and 100 000
                        triangles, under MIRT_QUERY_BRUTE (cells beyond 2e11 row tests are named, not run) and MIRT_QUERY_BINNED with the
@@ -1185,6 +1190,150 @@ def ordered_summary(text, p):
     p("")
 
 
+# ---- every hit along parallel rays: mirt_intersect_ordered_along_device ------------------------------------------------------------------
+
+def child_ordered_along(n):
+    """mirt_intersect_ordered_along_device for max_hits 1, 2, 4 and 8 on the along section's grid of starts looking down the scene:
+    BINNED with the grid built by the call (a direction never used before: dir tilted by a few subnormals) and with the grid held,
+    beside what a caller does today on the same rays written out, in the same run: mirt_intersect_ordered_device with the switch of
+    mirt_set_ray_grid off (the sweep) and on with the ray grid held -- and, for max_hits 1, beside mirt_intersect_along_device with
+    the grid held.  Answers are compared before any time is taken: every max_hits against the sweep's."""
+    import mirt
+    h = hip()
+    mirt.init(0)
+    mirt.scene_upload(mirt.scene_soup(1, n, 0.05 if n >= 50000 else 0.2))
+    top = 1 << 20
+    down = np.array([0, 0, 1], np.float32)
+    fresh = mirt.fresh_hits(top)
+    d_starts, d_rays, d_rec = dev_alloc(h, 12 * top), dev_alloc(h, 24 * top), dev_alloc(h, fresh.nbytes, fresh)
+    d_hits, d_cnt = dev_alloc(h, 8 * fresh.nbytes), dev_alloc(h, 4 * top)
+
+    def tilted(i):
+        d = down.copy()
+        d[0] = np.float32(i) * np.finfo(np.float32).smallest_subnormal
+        return d
+
+    def run(fn, k):
+        t0 = time.perf_counter()
+        fn(k); mirt.sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    def closest(q):
+        assert h.hipMemcpy(d_rec, fresh.ctypes.data_as(C.c_void_p), 20 * q, 1) == 0
+        t0 = time.perf_counter()
+        mirt.intersect_along_device(down, d_starts, q, d_rec); mirt.sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    def back(ptr, count, dtype):
+        out = np.zeros(count, dtype)
+        assert h.hipMemcpy(out.ctypes.data_as(C.c_void_p), ptr, out.nbytes, 2) == 0
+        return out
+
+    k, nudge = 1, 0
+    while k <= top:
+        starts = along_grid(k)
+        rays = mirt.make_rays(starts, down)
+        assert h.hipMemcpy(d_starts, starts.ctypes.data_as(C.c_void_p), starts.nbytes, 1) == 0
+        assert h.hipMemcpy(d_rays, rays.ctypes.data_as(C.c_void_p), rays.nbytes, 1) == 0
+        # the answers first
+        counts = {}
+        for m in ORDERED_HITS:
+            mirt.set_ray_grid(False)
+            run(lambda q: mirt.intersect_ordered_device(d_rays, q, None, m, d_hits, d_cnt), k)
+            want = back(d_hits, k * m, mirt.HIT_DTYPE), back(d_cnt, k, np.int32)
+            mirt.set_query_mode(mirt.QUERY_BINNED)
+            run(lambda q: mirt.intersect_ordered_along_device(down, d_starts, q, None, m, d_hits, d_cnt), k)
+            st = mirt.along_stats()
+            assert st["mode_used"] == mirt.QUERY_BINNED, st
+            got = back(d_hits, k * m, mirt.HIT_DTYPE), back(d_cnt, k, np.int32)
+            assert got[0].tobytes() == want[0].tobytes() and np.array_equal(got[1], want[1]), "the ordered call along a direction disagrees with mirt_intersect_ordered_device"
+            counts[m] = want[1]
+        reps = 5 if k <= 65536 else 3
+        ms = {}
+        ms["along"] = float(np.median([closest(k) for _ in range(reps + 2)][2:]))
+        assert mirt.along_stats()["cube_source"] == 2
+        for m in ORDERED_HITS:
+            yard = lambda q: mirt.intersect_ordered_device(d_rays, q, None, m, d_hits, d_cnt)
+            mirt.set_ray_grid(False)
+            ms[m, "sweep"] = float(np.median([run(yard, k) for _ in range(reps + 1)][1:]))
+            mirt.set_ray_grid(True)
+            ts = [run(yard, k) for _ in range(reps + 2)]
+            gs = mirt.ray_grid_stats()
+            ms[m, "grid"] = float(np.median(ts[2:])) if gs["mode_used"] == mirt.QUERY_BINNED and gs["source"] == 2 else float("nan")
+            mirt.set_ray_grid(False)
+            ts = []
+            for _ in range(reps + 1):                    # (never the key of the call before)
+                nudge += 1
+                ts.append(run(lambda q: mirt.intersect_ordered_along_device(tilted(1 + nudge % 7), d_starts, q, None, m, d_hits, d_cnt), k))
+                assert mirt.along_stats()["cube_source"] == 1
+            ms[m, "built"] = float(np.median(ts[1:]))
+            ts = [run(lambda q: mirt.intersect_ordered_along_device(down, d_starts, q, None, m, d_hits, d_cnt), k) for _ in range(reps + 2)]
+            assert mirt.along_stats()["cube_source"] == 2
+            ms[m, "kept"] = float(np.median(ts[2:]))
+        mirt.set_query_mode(mirt.QUERY_AUTO)
+        print("RESULT ordered_along n %6d rays %8d hit %.3f two %.3f eight %.3f  along %10.4f  " % (n, k, float((counts[1] > 0).mean()), float((counts[2] >= 2).mean()),
+                                                                                          float((counts[8] == 8).mean()), ms["along"])
+              + "  ".join("m%d %s" % (m, " ".join("%10.4f" % ms[m, c] for c in ("sweep", "grid", "built", "kept"))) for m in ORDERED_HITS) + " ms")
+        sys.stdout.flush()
+        k *= 4
+    mirt.shutdown()
+
+
+ORDERED_ALONG_ROW = re.compile(r"ordered_along n\s+(\d+) rays\s+(\d+) hit [0-9.]+ two [0-9.]+ eight [0-9.]+  along\s+([0-9.]+)  "
+                               + "  ".join(r"m%d((?:\s+[0-9.na]+){4})" % m for m in ORDERED_HITS) + " ms")
+
+
+def step_ordered_along(p):
+    p("== ordered_along: mirt_intersect_ordered_along_device, max_hits 1, 2, 4, 8, after NULL, the along section's square grid of starts looking down the")
+    p("   scene (dir = +z), beside what a caller does today in the same run on the same rays written out: mirt_intersect_ordered_device with the switch of")
+    p("   mirt_set_ray_grid off (sweep) and on with the ray grid held (grid; nan where that grid is not built); host clock around call + mirt_sync, medians;")
+    p("   answers compared first ==")
+    p("along: mirt_intersect_along_device with the grid held (one hit).  Per max_hits four columns: sweep; grid; BINNED, the grid built by the call; BINNED, the grid held")
+    p("hit / two / eight: the share of rays with a hit, with two or more, with eight or more")
+    out = "".join(run_child(p, ["--child", "ordered_along", str(n)], {}, 420) for n in (100000, 2000))
+    ordered_along_summary(out, p)
+
+
+def ordered_along_summary(text, p):
+    """What the rows say: the cells where the new call is behind a yardstick by more than the 2 % two runs differ by -- with its build
+    and with the grid held, against the sweep and against the held ray grid --, max_hits 1 with the grid held against
+    mirt_intersect_along_device, and per triangle count and max_hits the ray count from which the call with its build stays ahead
+    of the sweep (where AUTO's rule would have to switch when the grid is not held)."""
+    rows = []
+    for m in ORDERED_ALONG_ROW.finditer(text):
+        v = {"along": float(m.group(3))}
+        for j, mh in enumerate(ORDERED_HITS):
+            v.update({(mh, c): float(x) for c, x in zip(("sweep", "grid", "built", "kept"), m.group(4 + j).split())})
+        rows.append((int(m.group(1)), int(m.group(2)), v))
+    for mine in ("built", "kept"):
+        for yard in ("sweep", "grid"):
+            cells = [(n, k, mh, v[mh, mine], v[mh, yard]) for n, k, v in rows for mh in ORDERED_HITS if v[mh, yard] == v[mh, yard]]
+            behind = [c for c in cells if c[3] > 1.02 * c[4]]
+            ratios = sorted(c[3] / c[4] for c in cells)
+            if not cells:
+                continue
+            p("grid %s against %s: time ratio min %.3f median %.3f max %.3f; behind by more than 2 %% in %d of %d cells"
+              % ("built by the call" if mine == "built" else "held", "the sweep" if yard == "sweep" else "the held ray grid", ratios[0], ratios[len(ratios) // 2],
+                 ratios[-1], len(behind), len(cells)))
+            for n, k, mh, x, y in behind:
+                p("  n %d rays %d max_hits %d: %.4f ms against %.4f ms" % (n, k, mh, x, y))
+    one = [(n, k, v[1, "kept"], v["along"]) for n, k, v in rows]
+    if one:
+        rs = sorted(x / y for n, k, x, y in one)
+        p("max_hits 1, grid held, against mirt_intersect_along_device: time ratio min %.3f median %.3f max %.3f" % (rs[0], rs[len(rs) // 2], rs[-1]))
+        for n, k, x, y in one:
+            if x > 1.02 * y:
+                p("  n %d rays %d: %.4f ms against %.4f ms" % (n, k, x, y))
+    for n in sorted({r[0] for r in rows}, reverse=True):
+        for mh in ORDERED_HITS:
+            cells = sorted((k, v[mh, "built"] <= v[mh, "sweep"]) for nn, k, v in rows if nn == n)
+            lost = [k for k, ahead in cells if not ahead]
+            first = min([k for k, _ in cells if not lost or k > max(lost)], default=None)
+            p("n %d max_hits %d, grid built by the call: behind the sweep in %d of %d cells; ahead in every cell from %s rays on"
+              % (n, mh, len(lost), len(cells), first if first is not None else "no count measured"))
+    p("")
+
+
 # ---- several directions in one call: mirt_intersect_alongs_device / mirt_occluded_alongs_device ------------------------------------------
 
 ALONGS_K = (1, 4, 15, 16, 32, 64)
@@ -1522,6 +1671,8 @@ def main():
             return child_grid(int(a.child[1]), a.child[2])
         if a.child[0] == "ordered":
             return child_ordered(int(a.child[1]), a.child[2])
+        if a.child[0] == "ordered_along":
+            return child_ordered_along(int(a.child[1]))
         if a.child[0] == "alongs":
             return child_alongs(int(a.child[1]), int(a.child[2]))
         if a.child[0] == "mask":
@@ -1560,6 +1711,8 @@ def main():
             step_grid(p)
         if "ordered" in steps:
             step_ordered(p)
+        if "ordered_along" in steps:
+            step_ordered_along(p)
     finally:
         with open(a.out, "a" if a.append else "w") as f:
             f.write("\n".join(lines) + "\n")
