@@ -11,6 +11,12 @@
 // tests/ordered_helpers.py: after_records, and for rays with fewer than K hits.
 // A planted fault -- the row skipped when near >= threshold -- must be caught.
 //
+// The far regime: |rs| in [2^8, 2^12) -- a scene a thousand units from the origin -- with distances in [0.01, 3], a few floats apart.
+// One ulp of rs + d is then up to 2.4e-4 and a thousand ulps of d: distinct distances collapse onto one threshold, rows of a SMALLER
+// distance stand with near exactly AT the threshold of the list's bound, and only the strictness of the reject keeps them.  The rays
+// with two distinct eligible distances of one float sum, and those where such a pair straddles the cut at K = 1, 2, 4 or 8, are
+// counted (floors below), and the planted fault must be caught by this regime alone.
+//
 // Two builds.  Plain g++ under the address and undefined-behaviour sanitizers: the headers of the rule are plain C++, the shell of a
 // depth is shell_model below -- a monotone clamp, in this file's own words.  The library's own bin_shell_of (csrc/rt_binned.hpp) is
 // HIP source: with -DALONG_ORDER_LIBRARY_SHELL, as the host side of a hipcc build, the same program runs on it, checks that the model
@@ -57,24 +63,27 @@ struct Ray {
 };
 
 // One ray's rows.  Distances come from a small set so that ties abound; `flat`: the direction's shells have no width (iw = 0).
-static Ray make_ray(int nrows, bool flat)
+// `far`: rs of magnitude 2^8 .. 2^12 with the shells laid around it, distances in [0.01, 3] that differ by 0 .. 3 floats.
+static Ray make_ray(int nrows, bool flat, bool far = false)
 {
     Ray r;
     r.shells = SHELLS;
-    r.rs = (float)uni(-6.0, 2.0);
-    r.d0 = (float)uni(-3.0, -1.0);
+    r.rs = far ? (float)((pick(2) ? 1.0 : -1.0) * ldexp(uni(1.0, 2.0), 8 + pick(4))) : (float)uni(-6.0, 2.0);
+    r.d0 = far ? (float)((double)r.rs + uni(-1.0, 2.0)) : (float)uni(-3.0, -1.0);
     r.iw = flat ? 0.0f : (float)(r.shells / uni(2.0, 6.0));
     const int ndist = 1 + pick(6);
     float dists[6];
-    for (int i = 0; i < ndist; i++) dists[i] = pick(9) == 0 ? 0.0f : (float)uni(0.0, 9.0);
+    for (int i = 0; i < ndist; i++) dists[i] = far ? (float)uni(0.01, 3.0) : (pick(9) == 0 ? 0.0f : (float)uni(0.0, 9.0));
     std::vector<Row> cell, every;
     for (int i = 0; i < nrows; i++) {
         Row w;
         w.tri = pick(4 * nrows + 4);
         w.accepted = pick(4) != 0;
         w.dist = dists[pick(ndist)];
+        if (far)
+            for (int step = pick(4); step > 0; step--) w.dist = nextafterf(w.dist, INFINITY);
         if (pick(40) == 0) w.dist = pick(2) ? INFINITY : NAN;                // accepted by the test, not eligible
-        const float sum = r.rs + (w.accepted && w.dist == w.dist && w.dist < INFINITY ? w.dist : (float)uni(0.0, 9.0));
+        const float sum = r.rs + (w.accepted && w.dist == w.dist && w.dist < INFINITY ? w.dist : (float)(far ? uni(0.01, 3.0) : uni(0.0, 9.0)));
         // near <= rs + dist: exactly at it, one float below, or well below
         const int how = pick(4);
         w.near = how == 0 ? sum : (how == 1 ? nextafterf(sum, -INFINITY) : sum - (float)uni(0.0, 3.0));
@@ -148,7 +157,26 @@ static std::vector<unsigned long long> plain_sort(const Ray &r, float a, int k)
     return keys;
 }
 
-struct Tally { long rays = 0, calls = 0, wrong = 0, caught = 0, short_lists = 0, ties_at_cut = 0, near_at_sum = 0, rows = 0, offered = 0, dup = 0; };
+struct Tally { long rays = 0, calls = 0, wrong = 0, caught = 0, short_lists = 0, ties_at_cut = 0, near_at_sum = 0, rows = 0, offered = 0, dup = 0, collide = 0, collide_at_cut = 0; };
+
+// The far regime's floors, half of what a run shows: of 6000 rays 4849 hold a collision and 4101 one at a cut with shell_model, 4832
+// and 4070 on the library's shells (that build draws its depth sweep first); none of the 6000 rays around the origin holds one.
+constexpr long FAR_COLLISIONS_FLOOR = 2400, FAR_AT_CUT_FLOOR = 2000;
+
+// Two distinct eligible distances of the ray with one float sum rs + d: anywhere in its sorted hits (*any), and as the K-th and the
+// (K + 1)-th of them for K = 1, 2, 4 or 8 (*at_cut).
+static void collisions(const Ray &r, bool *any, bool *at_cut)
+{
+    const std::vector<unsigned long long> all = plain_sort(r, -1.0f, 0);
+    *any = *at_cut = false;
+    for (size_t i = 0; i + 1 < all.size(); i++) {
+        const float a = hit_bits_float(hit_key_distance_bits(all[i])), b = hit_bits_float(hit_key_distance_bits(all[i + 1]));
+        if (a != b && r.rs + a == r.rs + b) {
+            *any = true;
+            if (i == 0 || i == 1 || i == 3 || i == 7) *at_cut = true;
+        }
+    }
+}
 
 template <int K>
 static void check(const Ray &r, float a, int k, Tally &T)
@@ -198,10 +226,16 @@ int main()
     if (inf_w != SHELLS - 1 || max_w != SHELLS - 1 || sum_w != SHELLS - 1 || inf_0 != 0u || max_0 != 0u) { printf("FAILED\n"); return 1; }
     if (along_order_bound(INFINITY) != FLT_MAX || along_order_bound(3.5f) != 3.5f || along_order_bound(0.0f) != 0.0f) { printf("FAILED\n"); return 1; }
 
-    Tally T;
-    for (int it = 0; it < 6000; it++) {
-        const Ray r = make_ray(it % 7 == 0 ? pick(4) : 2 + pick(40), it % 11 == 0);
+    Tally N, F;                                                         // the regime around the origin (first, as it always ran), the far one
+    for (int it = 0; it < 12000; it++) {
+        const bool far = it >= 6000;
+        Tally &T = far ? F : N;
+        const Ray r = make_ray(it % 7 == 0 ? pick(4) : 2 + pick(40), it % 11 == 0, far);
         T.rays++;
+        bool any, at_cut;
+        collisions(r, &any, &at_cut);
+        T.collide += (long)any;
+        T.collide_at_cut += (long)at_cut;
         for (const Row &w : r.rows) T.near_at_sum += (long)(w.accepted && w.near == r.rs + w.dist);
         for (size_t e = r.off[(size_t)r.shells]; e < r.rows.size(); e++)
             for (size_t c = 0; c < r.off[(size_t)r.shells]; c++) T.dup += (long)(r.rows[c].tri == r.rows[e].tri);
@@ -220,9 +254,15 @@ int main()
             check<8>(r, ad[kind], ai[kind], T);
         }
     }
+    const Tally &T = N;
     printf("rays %ld calls %ld wrong %ld planted_fault_caught %ld short_lists %ld ties_at_cut %ld near_at_sum %ld in_cell_and_on_list %ld rows %ld offered %ld\n",
            T.rays, T.calls, T.wrong, T.caught, T.short_lists, T.ties_at_cut, T.near_at_sum, T.dup, T.rows, T.offered);
-    const bool pass = T.wrong == 0 && T.caught > 0 && T.short_lists > 100 && T.ties_at_cut > 100 && T.near_at_sum > 1000 && T.dup > 100 && T.offered < T.rows;
+    printf("far: rays %ld calls %ld wrong %ld planted_fault_caught %ld short_lists %ld ties_at_cut %ld near_at_sum %ld collisions %ld collisions_at_cut %ld "
+           "rows %ld offered %ld (collisions around the origin: %ld)\n",
+           F.rays, F.calls, F.wrong, F.caught, F.short_lists, F.ties_at_cut, F.near_at_sum, F.collide, F.collide_at_cut, F.rows, F.offered, N.collide);
+    bool pass = T.wrong == 0 && T.caught > 0 && T.short_lists > 100 && T.ties_at_cut > 100 && T.near_at_sum > 1000 && T.dup > 100 && T.offered < T.rows;
+    // the far regime alone: right, the planted fault caught, and its collisions above their floors
+    pass = pass && F.wrong == 0 && F.caught > 0 && F.collide >= FAR_COLLISIONS_FLOOR && F.collide_at_cut >= FAR_AT_CUT_FLOOR && F.offered < F.rows;
     printf(pass ? "ok\n" : "FAILED\n");
     return pass ? 0 : 1;
 }

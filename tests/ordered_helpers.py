@@ -78,14 +78,22 @@ def table(oracle, tris, rays):
     """The per-triangle table: rec[r, j] is the record a fresh ClosestIntersection call on triangle j alone leaves for ray r
     (index 0 where it was accepted -- stored as j --, -1 where not)."""
     tris = np.ascontiguousarray(tris, F32).reshape(-1, 15)
+    rays = np.ascontiguousarray(rays, mirt.RAY_DTYPE)
     rec = np.zeros((len(rays), len(tris)), mirt.HIT_DTYPE)
     rec[:] = mirt.fresh_hits(1)[0]
-    with np.errstate(all="ignore"):
-        for r in range(len(rays)):
-            for j in range(len(tris)):
-                _, p, d, ix = oracle.closest_intersection(tris[j:j + 1], rays["start"][r], rays["dir"][r])
-                if ix == 0:
-                    rec[r, j]["position"], rec[r, j]["distance"], rec[r, j]["index"] = p, d, j
+    # the oracle's entry point on plain addresses (the same calls as oracle.closest_intersection(tris[j:j + 1], start, dir) on a fresh
+    # record, which it fills in place: millions of them without an array conversion each)
+    import ctypes as C
+    call = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)(("mirt_oracle_closest_intersection", oracle.lib))
+    t0, r0, h0 = tris.ctypes.data, rays.ctypes.data, rec.ctypes.data
+    rsize, hsize, nt = mirt.RAY_DTYPE.itemsize, mirt.HIT_DTYPE.itemsize, len(tris)
+    for r in range(len(rays)):
+        start, direction = r0 + r * rsize, r0 + r * rsize + 12
+        for j in range(nt):
+            h = h0 + (r * nt + j) * hsize
+            call(start, direction, t0 + j * 60, 1, h, h + 12, h + 16)
+    idx = np.broadcast_to(np.arange(nt, dtype=np.int32), rec.shape)
+    rec["index"] = np.where(rec["index"] == 0, idx, -1)                # (the lone triangle was number 0 of its call)
     return rec
 
 

@@ -9,7 +9,13 @@ A pure scaling multiplies every operand of a binning margin alike; an offset doe
 reach smax = 8 R and the grid's corner |p0| grow with |T| while the cells keep the scene's size.  ALONG_CLASS says what that does to
 the grid across a direction (along/along.hpp): its every-ray list grows (`binned`, still), then outgrows along_every_cap (`gave_up`),
 then the cells are finer than a float resolves at that distance and no descriptor is made (`no_grid`).  The table is derived from the
-header by tests/cpp/along_bins_test.cpp's scene-file mode, which test_along_host.py runs again on every entry."""
+header by tests/cpp/along_bins_test.cpp's scene-file mode, which test_along_host.py runs again on every entry.
+
+The arbitrary-ray grid (grid/ray_grid.hpp) meets an offset sooner: its plane index grows with the scene's distance from the origin
+over its triangles' size, then the every-ray list outgrows grid_every_cap.  RAY_GRID says, per scene and placement of GRID_PLACEMENTS
+-- PLACEMENTS and GRID_EDGE, the last step along (10, -7, 5) at which soup2000 still bins --, the class and the counts
+tests/cpp/ray_grid_test.cpp's scene-file mode reports (test_ray_grid_host.py runs it again on every entry).  TIE_SCENE is soup2000
+with its first rows twice: equal distances with two indices in every placement (test_gpu_placement_grid.py, placed_grid.py)."""
 import numpy as np
 
 import mirt
@@ -29,6 +35,12 @@ PLACEMENTS = {
     "0_0_4096": ((0.0, 0.0, 4096.0), 1.0),
 }
 FAR = "300_200_-100"
+# the last step along (10, -7, 5) at which the arbitrary-ray grid still bins soup2000 (RAY_GRID_CLASS): the ray grid's tests alone visit it
+GRID_EDGE = "20_-14_10"
+GRID_PLACEMENTS = dict(PLACEMENTS, **{GRID_EDGE: ((20.0, -14.0, 10.0), 1.0)})
+# the tie scene: soup2000 followed by a copy of its first TIE_ROWS rows -- placed duplicates stay exact duplicates, so equal distances
+# with two indices survive every placement (2100 triangles: the ray grid has 32 cells a side, the along grids 64)
+TIE_SCENE, TIE_ROWS = "soup2000+dup", 100
 
 # the directions of the along / alongs calls, before scaling: the oblique one, an axis, and three more for the call of five
 ALONG_DIRS = {"oblique": OBLIQUE, "-y": np.array([0, -1, 0], np.float32), "+x": np.array([1, 0, 0], np.float32),
@@ -70,6 +82,8 @@ def unit_scene(name):
             v = mirt.scene_soup(41, 2000, 0.2)
         elif name == "cornell+soup2000":
             v = np.concatenate([mirt.scene_cornell(), mirt.scene_soup(41, 2000, 0.2)])
+        elif name == TIE_SCENE:
+            v = np.concatenate([unit_scene("soup2000"), unit_scene("soup2000")[:TIE_ROWS]])
         elif name == "soup33000":
             v = mirt.scene_soup(77, 33000, 0.05)
         else:
@@ -82,7 +96,7 @@ def unit_scene(name):
 def placed_scene(name, pname):
     key = (name, pname)
     if key not in _scenes:
-        v = place_tris(unit_scene(name), *PLACEMENTS[pname])
+        v = place_tris(unit_scene(name), *GRID_PLACEMENTS[pname])
         v.setflags(write=False)
         _scenes[key] = v
     return _scenes[key]
@@ -141,4 +155,66 @@ ALONG_CLASS = {
         "10_-7_5_div1024": ("no_grid", "no_grid", "no_grid", "no_grid", "no_grid"),
         "0_0_4096": ("no_grid", "no_grid", "no_grid", "no_grid", "no_grid"),
     },
+    TIE_SCENE: {                                                    # B = 64, along_every_cap 262: every-ray rows per direction behind
+        "unit": ("binned", "binned", "binned", "binned", "binned"),                     # 0 0 0 0 0
+        "3_0_0": ("binned", "binned", "binned", "binned", "binned"),                    # 1 0 0 1 4
+        "10_-7_5": ("binned", "binned", "binned", "binned", "binned"),                  # 4 6 0 3 5
+        "300_200_-100": ("binned", "binned", "binned", "binned", "binned"),             # 58 154 144 78 96
+        "1000_1000_1000": ("binned", "gave_up", "gave_up", "gave_up", "gave_up"),       # 198 483 519 291 301
+        "origin_x1024": ("binned", "binned", "binned", "binned", "binned"),
+        "origin_div1024": ("binned", "binned", "binned", "binned", "binned"),
+        "40_-25_60_div1024": ("no_grid", "no_grid", "no_grid", "no_grid", "no_grid"),
+        "10_-7_5_div1024": ("no_grid", "no_grid", "no_grid", "no_grid", "no_grid"),
+        "0_0_4096": ("no_grid", "no_grid", "no_grid", "no_grid", "no_grid"),
+    },
 }
+ALONG_BINS = {"soup33000": 256, TIE_SCENE: 64}                      # cells a side of the along grids; 32 for every other scene here
+
+# The arbitrary-ray grid (grid/ray_grid.hpp) per scene and placement of GRID_PLACEMENTS: (class, plane-index pairs, every-ray rows), as
+# tests/cpp/ray_grid_test.cpp's scene-file mode reports them from the header alone (test_ray_grid_host.py runs it again on every entry;
+# never taken from a GPU).  `binned`: every-ray rows <= grid_every_cap(n) = max(n / 8, 64); `gave_up`: beyond it -- a plane bin's width
+# no longer covers the rounding of the operands, so the triangle goes on the list of every ray; `no_grid`: no descriptor is made (none
+# of these finite boxes is refused).  The counts of a structure that gave up are the program's, the library reports 0 for them.
+RAY_GRID = {
+    "soup2000": {                                                   # G = 16, cap 250
+        "unit": ("binned", 4609, 1),
+        "3_0_0": ("binned", 18923, 5),
+        "10_-7_5": ("binned", 88414, 47),
+        GRID_EDGE: ("binned", 251602, 213),
+        "300_200_-100": ("gave_up", 0, 2000),
+        "1000_1000_1000": ("gave_up", 0, 2000),
+        "origin_x1024": ("binned", 4609, 1),
+        "origin_div1024": ("binned", 4609, 1),
+        "40_-25_60_div1024": ("gave_up", 0, 2000),
+        "10_-7_5_div1024": ("gave_up", 0, 2000),
+        "0_0_4096": ("gave_up", 0, 2000),
+    },
+    "cornell+soup2000": {                                           # G = 16, cap 253
+        "unit": ("binned", 4739, 1),
+        "3_0_0": ("binned", 19175, 5),
+        "10_-7_5": ("binned", 90158, 47),
+        GRID_EDGE: ("binned", 254912, 217),
+        "300_200_-100": ("gave_up", 0, 2030),
+        "1000_1000_1000": ("gave_up", 0, 2030),
+        "origin_x1024": ("binned", 4739, 1),
+        "origin_div1024": ("binned", 4739, 1),
+        "40_-25_60_div1024": ("gave_up", 0, 2030),
+        "10_-7_5_div1024": ("gave_up", 0, 2030),
+        "0_0_4096": ("gave_up", 0, 2030),
+    },
+    TIE_SCENE: {                                                    # G = 32 (2100 triangles), cap 262: cells half as wide, given up sooner
+        "unit": ("binned", 9874, 2),
+        "3_0_0": ("binned", 59747, 32),
+        "10_-7_5": ("gave_up", 298771, 279),
+        GRID_EDGE: ("gave_up", 135527, 1725),
+        "300_200_-100": ("gave_up", 0, 2100),
+        "1000_1000_1000": ("gave_up", 0, 2100),
+        "origin_x1024": ("binned", 9874, 2),
+        "origin_div1024": ("binned", 9874, 2),
+        "40_-25_60_div1024": ("gave_up", 0, 2100),
+        "10_-7_5_div1024": ("gave_up", 0, 2100),
+        "0_0_4096": ("gave_up", 0, 2100),
+    },
+}
+RAY_GRID_CLASS = {scene: {p: row[0] for p, row in rows.items()} for scene, rows in RAY_GRID.items()}
+RAY_GRID_CELLS = {"soup2000": 16, "cornell+soup2000": 16, TIE_SCENE: 32}

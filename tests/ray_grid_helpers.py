@@ -145,6 +145,41 @@ def phantom_rays(tris, count, seed=5, tries=40000):
     return np.array(found, F32).reshape(-1, 6)
 
 
+def lattice_phantom_rays(tris, count, seed=5, tries=4000):
+    """phantom_rays for a scene placed away from the origin, where a point of a triangle's plane drawn in float64 is rounded off that
+    plane by an ulp of its large coordinates and the float test decides it exactly.  Here start and direction are whole-number
+    combinations of the triangle's own float32 edges, S = v0 + i e1 + j e2 and d = k e1 + l e2 in float32: a few edges off the
+    triangle, and -- where the vertices share a binade, as those of a small scene at an offset do -- exactly in its plane, so that
+    the reference's quotients are rounding noise over rounding noise.  Picked with ref_accept on the host like phantom_rays."""
+    rng = np.random.default_rng(seed)
+    t32 = np.asarray(tris, F32).reshape(-1, 15)
+    t = t32.astype(np.float64)
+    cen = (t[:, 0:3] + t[:, 3:6] + t[:, 6:9]) / 3
+    rad = np.maximum(np.linalg.norm(t[:, 3:6] - t[:, 0:3], axis=1), np.linalg.norm(t[:, 6:9] - t[:, 0:3], axis=1))
+    _, _, w, _, _ = grid_of(tris)
+    found = []
+    for _ in range(tries):
+        r = t32[rng.integers(len(t32))]
+        v0, e1, e2 = r[0:3], r[3:6] - r[0:3], r[6:9] - r[0:3]
+        i, j = rng.integers(-6, 7, 2)
+        k, l = rng.integers(-3, 4, 2)
+        if (k == 0 and l == 0) or max(abs(i), abs(j)) < 3:
+            continue
+        ray = np.concatenate([(v0 + F32(i) * e1) + F32(j) * e2, F32(k) * e1 + F32(l) * e2]).astype(F32)
+        acc = np.flatnonzero(ref_accept(tris, ray[0:3], ray[3:6]))
+        if not len(acc):
+            continue
+        s, d = ray[0:3].astype(np.float64), ray[3:6].astype(np.float64)
+        sc = cen[acc] - s
+        tt = np.maximum(0.0, sc.dot(d) / d.dot(d))
+        gap = np.linalg.norm(sc - tt[:, None] * d, axis=1)
+        if (gap > rad[acc] + 2 * w).any():
+            found.append(ray)
+            if len(found) == count:
+                break
+    return np.array(found, F32).reshape(-1, 6)
+
+
 def ray_set(name, n=4097, seed=3):
     """(rays (n, 6) float32, planted): uniform segments, axis-parallel rays, rays in cell faces and through cell corners, rays between
     points of one triangle's plane and of two triangles, phantom rays, starts outside the box pointing in, past and away -- and the

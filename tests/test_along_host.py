@@ -86,7 +86,7 @@ def test_placed_scenes_are_filed_as_the_class_table_says(bins_test, tmp_path):
                     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (what, r.stdout + r.stderr)
                     m = re.search(r"n (\d+) B (\d+) every (\d+) every_share ([\d.]+) offered_share [\d.]+ every_cap (\d+) pad ([\d.]+)", r.stdout)
                     n, B, every, cap, pad = int(m.group(1)), int(m.group(2)), int(m.group(3)), int(m.group(5)), float(m.group(6))
-                    assert n == len(tris) and cap == max(n // 8, 64) and B == (256 if scene == "soup33000" else 32), (what, r.stdout)
+                    assert n == len(tris) and cap == max(n // 8, 64) and B == pl.ALONG_BINS.get(scene, 32), (what, r.stdout)
                     assert (every > cap) == (want == "gave_up"), "%s: %d of %d on the every-ray list, cap %d, but %s" % (what, every, n, cap, want)
                     assert grid is not None and grid["B"] == B and abs(grid["pad"] - pad) <= 1e-6 + 1e-4 * pad, (what, grid, pad)
                     line.append("%.3f%s" % (float(m.group(4)), "!" if want == "gave_up" else ""))

@@ -1,6 +1,7 @@
 """What the ordered hits along parallel rays (mirt_intersect_ordered_along*, mirt_intersect_ordered_alongs*) show without a GPU:
 tests/cpp/along_order_test.cpp -- the bound rule of order/along_order.hpp together with the list rule of order/hit_list.hpp against
-a plain sort, with a planted fault that must be caught, and what bin_shell_of returns for thresholds of +inf and FLT_MAX --; the four
+a plain sort, around the origin and in a far regime (|rs| up to 2^12: distinct distances on one float threshold), with a planted fault
+that must be caught in each, and what bin_shell_of returns for thresholds of +inf and FLT_MAX --; the four
 wrappers and their refusal without a device; every invalid-argument case; and that the expectations used on the GPU
 (test_gpu_ordered_along.py) meet their conditions on the oracle alone."""
 import ctypes as C
@@ -19,6 +20,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "along_order_test.cpp")
 INVALID = -3
 NAMES = A.NAMES
+# along_order_test.cpp's far regime: rays with two distinct distances of one float sum rs + d, and with such a pair at a cut -- half of
+# what the runs show (4832 and 4070 of 6000 rays in the lower of the two builds)
+FAR_COLLISIONS_FLOOR, FAR_AT_CUT_FLOOR = 2400, 2000
 
 
 def _run(exe):
@@ -31,6 +35,14 @@ def _run(exe):
     assert wrong == 0 and caught > 0 and rays >= 5000 and calls >= 50000
     assert short > 1000 and ties > 1000 and at_sum > 1000 and both > 1000, "the inputs miss one of the cases they are there for"
     assert offered < rows, "the bound never moved an end"
+    # the far regime (|rs| up to 2^12, distances a few floats apart): right, the planted fault caught by it alone, and rays in which
+    # two distinct distances share one float threshold -- at the K-th cut too -- above the program's floors; none around the origin
+    m = re.search(r"far: rays (\d+) calls (\d+) wrong (\d+) planted_fault_caught (\d+) short_lists \d+ ties_at_cut (\d+) near_at_sum (\d+) collisions (\d+) "
+                  r"collisions_at_cut (\d+) rows (\d+) offered (\d+) \(collisions around the origin: (\d+)\)", r.stdout)
+    frays, fcalls, fwrong, fcaught, fties, fat_sum, collide, at_cut, frows, foffered, near_collide = map(int, m.groups())
+    assert fwrong == 0 and fcaught > 0 and frays >= 5000 and fcalls >= 50000
+    assert collide >= FAR_COLLISIONS_FLOOR and at_cut >= FAR_AT_CUT_FLOOR and near_collide == 0, "the far regime misses the case it is there for"
+    assert fties > 1000 and fat_sum > 1000 and foffered < frows
     # +inf and FLT_MAX both fall into the last shell, and into shell 0 where the shells have no width
     assert re.search(r"\+inf -> 7, FLT_MAX -> 7, rs \+ FLT_MAX -> 7 of 8 shells; with no shell width \+inf -> 0 \(inf \* 0 is NaN\), FLT_MAX -> 0", r.stdout)
     return r.stdout

@@ -69,16 +69,49 @@ def test_suite_scenes_are_filed(grid_test, tmp_path, name, cells):
         assert offered < 0.8 * OFFERED_CAP, "a ray is offered %.4f of the scene: no room under the GPU test's bound" % offered
 
 
-def test_a_far_placed_scene_gives_up_and_a_near_one_bins(grid_test, tmp_path):
+def test_placed_scenes_are_filed_as_the_class_table_says(grid_test, tmp_path):
+    """placement.RAY_GRID entry by entry, from the header alone: the tool's scene-file mode on the placed scenes -- a descriptor or
+    none, the every-ray list within grid_every_cap(n) or beyond it, the plane-index pairs and every-ray rows the GPU test compares the
+    library's statistics with --, and no accepted pair of the tool's uniform segments missed anywhere."""
     import placement as pl
-    for pname, bins in (("3_0_0", True), ("1000_1000_1000", False)):
-        path = str(tmp_path / "placed.f32")
-        np.ascontiguousarray(pl.placed_scene("soup2000", pname), np.float32).tofile(path)
-        r = subprocess.run([grid_test, path], capture_output=True, text=True, timeout=120)
-        print(pname, r.stdout)
-        assert r.returncode == 0, r.stdout + r.stderr
-        binned = "no_grid" not in r.stdout and " gave_up 0 " in r.stdout
-        assert binned == bins, (pname, r.stdout)
+    seen = {}
+    for scene, rows in pl.RAY_GRID.items():
+        assert list(rows) and set(rows) == set(pl.GRID_PLACEMENTS), scene
+        for pname, (want, plane_pairs, every_rows) in rows.items():
+            tris = pl.placed_scene(scene, pname)
+            path = str(tmp_path / "placed.f32")
+            np.ascontiguousarray(tris, np.float32).tofile(path)
+            r = subprocess.run([grid_test, path], capture_output=True, text=True, timeout=120)
+            what = "%s at %s" % (scene, pname)
+            print("%-17s %-18s %s" % (scene, pname, r.stdout.strip().replace("\n", " | ")))
+            assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (what, r.stdout + r.stderr)
+            n, cap = len(tris), max(len(tris) // 8, 64)             # ray_grid.hpp: grid_every_cap
+            if "no_grid" in r.stdout:
+                got = "no_grid"
+            else:
+                m = re.search(r"n (\d+) G (\d+) pairs \d+ cell_pairs \d+ plane_pairs (\d+) every (\d+) every_share [\d.]+ gave_up (\d) offered_share [\d.]+ "
+                              r"accepted (\d+) misses (\d+)", r.stdout)
+                gn, G, pp, every, gave_up, accepted, misses = map(int, m.groups())
+                assert gn == n and G == pl.RAY_GRID_CELLS[scene] == H.grid_of(tris)[0], (what, r.stdout)
+                assert " misses 0 " in r.stdout and misses == 0 and accepted > 0, (what, r.stdout)
+                assert gave_up == (every > cap), (what, r.stdout)
+                got = "gave_up" if gave_up else "binned"
+                if got == "binned":
+                    assert every <= cap, (what, r.stdout)
+                assert (pp, every) == (plane_pairs, every_rows), "%s: %d plane pairs and %d every-ray rows, the table says %d and %d" % (what, pp, every, plane_pairs, every_rows)
+            assert got == want, "%s is %s, the table says %s" % (what, got, want)
+            seen.setdefault(got, set()).add((scene, pname))
+    # the two placements of the test this one replaces, as it asserted them
+    assert pl.RAY_GRID_CLASS["soup2000"]["3_0_0"] == "binned" and pl.RAY_GRID_CLASS["soup2000"]["1000_1000_1000"] != "binned"
+    # every class the table names occurs, the edge placement bins, and the step behind it on the same line does not
+    assert set(seen) == {c for rows in pl.RAY_GRID_CLASS.values() for c in rows.values()} and {"binned", "gave_up"} <= set(seen), seen
+    assert pl.RAY_GRID_CLASS["soup2000"][pl.GRID_EDGE] == "binned" and pl.RAY_GRID_CLASS["cornell+soup2000"][pl.GRID_EDGE] == "binned"
+    # the plane index grows with the offset until the grid gives up: what the edge placement is there for
+    pp = [pl.RAY_GRID["soup2000"][p][1] for p in ("unit", "3_0_0", "10_-7_5", pl.GRID_EDGE)]
+    assert pp == sorted(pp) and pp[-1] > 50 * pp[0], pp
+    # a pure scaling moves nothing
+    for rows in pl.RAY_GRID.values():
+        assert rows["unit"] == rows["origin_x1024"] == rows["origin_div1024"]
 
 
 def test_calls_need_a_device_and_the_layout_is_the_headers():
