@@ -20,6 +20,7 @@
 #include "../grid/ray_grid.hpp"
 #include "../order/ordered_hits.hpp"
 #include "../order/ordered_along.hpp"
+#include "../order/ordered_fans.hpp"
 #include "../lights/many_lights.hpp"
 #include "../lights/aa_many_lights.hpp"
 #include "cube_plan.hpp"
@@ -838,6 +839,30 @@ int check_alongs_args(const float *dirs3, int ndirs, const void *dir_of, const v
 int check_alongs_host_args(const float *dirs3, int ndirs, const int32_t *dir_of, const float *origins3, int nrays, const void *out);
 int alongs_run(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, AlongsFrame &f,
                const std::function<int(const AlongsFrame &)> &launch, const std::function<int()> &brute);
+
+// ... from one origin and from several (order_fans.cpp; the kernels: ../order/ordered_fans.hip)
+int order_from(const float *origin, const void *d_dirs3, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts);
+int order_from_host(const float *origin, const float *dirs3, int nrays, const mirt_hit *after, int max_hits, mirt_hit *hits, int32_t *counts);
+int order_fans(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, const void *d_after, int max_hits,
+               void *d_hits, void *d_counts);
+int order_fans_host(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, const mirt_hit *after, int max_hits,
+                    mirt_hit *hits, int32_t *counts);
+// What order_fans.cpp shares with the fan calls (query.cpp): the checks of the arguments alone (what check_from_args, check_fans_args
+// and check_fans_host_args test behind the library's state); the frame both fan calls start from; the single fan's
+// decision and structure step on the stream it takes (fan_begin: the statistics of QUERY_FAN begun afresh, *binned says whether `frame`
+// is ready for a walk kernel); for several origins the decision with its pass plan (fans_binned), the cubes somebody else may hold
+// for them (fans_foreign: what mirt_intersect_fans* passes), the passes of a binned call (fans_passes_run: fans_passes with the launch
+// as a std::function) and the rays written out into the stream's query scratch (g.cur().query.d_fan_rays) for a sweep.
+struct CubeChoice { const LightCache *cube; int source; };
+int from_args(const float *origin, const void *dirs3, int nrays, const void *hits);
+int fans_args(const float *origins3, int norigins, const void *origin_of, const void *dirs3, int nrays, const void *hits);
+int fans_index_args(int norigins, const int32_t *origin_of, int nrays);
+QueryFanFrame fan_frame(const void *d_dirs3, int nrays, void *d_hits);
+int fan_begin(const float *origin, const void *d_dirs3, int nrays, void *d_hits, QueryFanFrame *frame, bool *binned);
+int fans_expand(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays);
+bool fans_binned(const float *origins3, int norigins, int nrays, std::initializer_list<CubeChoice> foreign, std::vector<FanPass> *plan);
+int fans_passes_run(const float *origins3, const std::vector<FanPass> &plan, std::initializer_list<CubeChoice> foreign, QueryStats &stats,
+                    QueryFansFrame &q, const std::function<int()> &launch);
 
 // ---- rasteriser (raster.cpp) ----
 int raster_enqueue(const mirt_view *view, const mirt_light *lights, int nlights, const float *indirect,

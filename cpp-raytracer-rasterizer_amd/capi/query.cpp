@@ -60,6 +60,15 @@ static int check_query_args(const void *in, int count, const void *out, const ch
     return MIRT_OK;
 }
 
+// The arguments of a call from one origin alone, without a look at the library's state (order_fans.cpp checks them in front of it).
+int from_args(const float *origin, const void *dirs3, int nrays, const void *hits)
+{
+    if (nrays < 0) return fail(MIRT_ERR_INVALID_ARGUMENT, "direction count %d is negative", nrays);
+    if (nrays > 0 && (!dirs3 || !hits)) return fail(MIRT_ERR_INVALID_ARGUMENT, "direction arrays must not be NULL when the count is > 0");
+    if (nrays > 0 && !origin) return fail(MIRT_ERR_INVALID_ARGUMENT, "origin must not be NULL when the count is > 0");
+    return MIRT_OK;
+}
+
 // ... of mirt_intersect_from*: check_query_args, then the origin (a call without rays needs none).
 static int check_from_args(const float *origin, const void *dirs3, int nrays, const void *hits)
 {
@@ -185,7 +194,7 @@ static bool starts_safe(const float *pos3, int npos)
 // scratch set as the shared cube's build (the pass that set kept for moving lights is invalidated there).  An own cube that is
 // held is returned without a call of light_cache_ensure: for a held cube that function returns at once, built = false, having
 // touched nothing (binned.cpp) -- should it ever do more for a held cube, walk_cube has to call it in that case too.
-struct CubeChoice { const LightCache *cube; int source; };
+// (struct CubeChoice: capi.hpp)
 static CubeChoice held_cube(std::initializer_list<CubeChoice> foreign, const LightCache &own, const float *origins, int npos, int cube_bins)
 {
     const uint64_t key = light_key_of(origins, npos);
@@ -497,7 +506,7 @@ static bool auto_bins_fan(int nrays)
 }
 
 // What the frames of both fan calls share: the scene, the caller's directions and records; everything else zero.
-static QueryFanFrame fan_frame(const void *d_dirs3, int nrays, void *d_hits)
+QueryFanFrame fan_frame(const void *d_dirs3, int nrays, void *d_hits)
 {
     QueryFanFrame q;
     memset(&q, 0, sizeof q);
@@ -509,6 +518,38 @@ static QueryFanFrame fan_frame(const void *d_dirs3, int nrays, void *d_hits)
     return q;
 }
 
+// What a call from one origin does up to its kernel on the stream it takes (mirt_intersect_from*, and order_fans.cpp's ordered form):
+// binned or brute, as a DirectLight query decides it -- the cube is the fans' own, whoever else holds one for this point --, the
+// statistics of QUERY_FAN begun afresh, and for a binned call the cube, built if need be, its view and table in *frame and the
+// counters armed.  *frame is fan_frame's with the origin; a call that does not bin gets nothing more.
+int fan_begin(const float *origin, const void *d_dirs3, int nrays, void *d_hits, QueryFanFrame *frame, bool *binned)
+{
+    int rc;
+    QueryFanFrame &q = *frame;
+    q = fan_frame(d_dirs3, nrays, d_hits);
+    memcpy(q.origin, origin, 12);
+    float origins[6] = {};
+    memcpy(origins + 3, origin, 12);
+    const bool safe = starts_safe(origin, 1);
+
+    bool fixed_grid = false;
+    const int cube_bins = light_cube_bins_for(1, &fixed_grid);
+    const bool may_bin = safe && light_keys_fit(1, cube_bins);
+    const bool held = may_bin && held_cube({}, g.qrows.fan, origins, 1, cube_bins).cube != nullptr;
+    *binned = query_bins(may_bin, g.query_mode, held, auto_bins_fan(nrays));
+
+    stream_begin();
+    QueryStats &stats = stats_begin(QUERY_FAN, *binned);
+    if (!*binned) return MIRT_OK;
+
+    CubeChoice c;
+    if ((rc = walk_cube({}, g.qrows.fan, origins, 1, cube_bins, &c))) return rc;
+    stats_cube(stats, *c.cube, c.source);
+    q.tab = c.cube->d_light_tab;
+    q.cube = cube_view(*c.cube);
+    return stats_arm(QUERY_FAN, &q.stats);
+}
+
 int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, void *d_hits)
 {
     int rc;
@@ -516,37 +557,20 @@ int query_intersect_from(const float *origin, const void *d_dirs3, int nrays, vo
     if (nrays == 0) return MIRT_OK;
     if ((rc = query_need_scene())) return rc;
 
-    QueryFanFrame q = fan_frame(d_dirs3, nrays, d_hits);
-    memcpy(q.origin, origin, 12);
-    float origins[6] = {};
-    memcpy(origins + 3, origin, 12);
-    const bool safe = starts_safe(origin, 1);
-
-    // Binned or brute, as a DirectLight query decides it.  The cube is the fans' own, whoever else holds one for this point.
-    bool fixed_grid = false;
-    const int cube_bins = light_cube_bins_for(1, &fixed_grid);
-    const bool may_bin = safe && light_keys_fit(1, cube_bins);
-    const bool held = may_bin && held_cube({}, g.qrows.fan, origins, 1, cube_bins).cube != nullptr;
-    const bool binned = query_bins(may_bin, g.query_mode, held, auto_bins_fan(nrays));
-
-    stream_begin();
-    QueryStats &stats = stats_begin(QUERY_FAN, binned);
+    QueryFanFrame q;
+    bool binned = false;
+    if ((rc = fan_begin(origin, d_dirs3, nrays, d_hits, &q, &binned))) return rc;
     if (!binned) {
         QueryScratch &S = g.cur().query;
-        if ((rc = query_origin_tables(origins, 1, safe))) return rc;
+        float origins[6] = {};
+        memcpy(origins + 3, origin, 12);
+        if ((rc = query_origin_tables(origins, 1, starts_safe(origin, 1)))) return rc;
         q.tab = S.d_light_tab;
         q.unsafe = S.d_flags;
         hipLaunchKernelGGL(k_query_fan<QUERY_P>, dim3((unsigned)((nrays + QUERY_BLOCK_RAYS - 1) / QUERY_BLOCK_RAYS)), dim3(256), sweep_lds_bytes(), g.stream, q);
         HIP_TRY(hipGetLastError());
         return MIRT_OK;
     }
-
-    CubeChoice c;
-    if ((rc = walk_cube({}, g.qrows.fan, origins, 1, cube_bins, &c))) return rc;
-    stats_cube(stats, *c.cube, c.source);
-    q.tab = c.cube->d_light_tab;
-    q.cube = cube_view(*c.cube);
-    if ((rc = stats_arm(QUERY_FAN, &q.stats))) return rc;
     return launch_walk(k_query_fan_binned<false>, k_query_fan_binned<true>, q.stats != nullptr, dim3((unsigned)((nrays + 255) / 256)), q);
 }
 
@@ -598,10 +622,10 @@ bool auto_bins_fans(int nrays)
     return auto_bins_fan(nrays) && (long)nrays > query_wave_rays();
 }
 
-static int check_fans_args(const float *origins3, int norigins, const void *origin_of, const void *dirs3, int nrays, const void *hits)
+// The arguments of a many-origin call alone (order_fans.cpp checks them in front of the library's state), and with that state first
+// as the fan calls themselves check them.
+int fans_args(const float *origins3, int norigins, const void *origin_of, const void *dirs3, int nrays, const void *hits)
 {
-    int rc;
-    if ((rc = need_init())) return rc;
     if (norigins < 0) return fail(MIRT_ERR_INVALID_ARGUMENT, "origin count %d is negative", norigins);
     if (nrays < 0) return fail(MIRT_ERR_INVALID_ARGUMENT, "direction count %d is negative", nrays);
     if (nrays > 0 && (!dirs3 || !hits)) return fail(MIRT_ERR_INVALID_ARGUMENT, "direction arrays must not be NULL when the count is > 0");
@@ -610,11 +634,17 @@ static int check_fans_args(const float *origins3, int norigins, const void *orig
     if (norigins > 1 && !origin_of) return fail(MIRT_ERR_INVALID_ARGUMENT, "origin_of may be NULL only for a single origin, not for %d", norigins);
     return MIRT_OK;
 }
+static int check_fans_args(const float *origins3, int norigins, const void *origin_of, const void *dirs3, int nrays, const void *hits)
+{
+    int rc;
+    if ((rc = need_init())) return rc;
+    return fans_args(origins3, norigins, origin_of, dirs3, nrays, hits);
+}
 
 // By definition the call is mirt_intersect on the expanded rays: they are written out on the device (k_query_fans_expand) into
 // the stream's query scratch (fans_expand) and go through query_intersect's kernels, whose per-ray filter safety and choice of
 // kernel come along.
-static int fans_expand(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays)
+int fans_expand(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays)
 {
     int rc;
     QueryScratch &S = g.cur().query;
@@ -642,7 +672,7 @@ static int fans_brute(const float *origins3, int norigins, const void *d_origin_
 // Binned or brute for a many-origin call, and the pass plan of a binned one.  As the single fan decides it: never what the frame
 // path would not bin, whatever the mode -- and the call is one: an origin outside the filter's range (NaN included) among ordinary
 // ones sends all of it to the brute-force kernels.  `held`: every pass's cube, that is.
-static bool fans_binned(const float *origins3, int norigins, int nrays, std::initializer_list<CubeChoice> foreign, std::vector<FanPass> *plan)
+bool fans_binned(const float *origins3, int norigins, int nrays, std::initializer_list<CubeChoice> foreign, std::vector<FanPass> *plan)
 {
     const bool may_bin = starts_safe(origins3, norigins) && fan_pass_plan(norigins, g.n, cube_bins_override(), plan);
     const bool held = may_bin && passes_held(*plan, g.qrows.fans, foreign, foreign, origins3);
@@ -681,6 +711,12 @@ static int fans_passes(const float *origins3, const std::vector<FanPass> &plan, 
         if ((rc = launch())) return rc;
     }
     return MIRT_OK;
+}
+
+int fans_passes_run(const float *origins3, const std::vector<FanPass> &plan, std::initializer_list<CubeChoice> foreign, QueryStats &stats,
+                    QueryFansFrame &q, const std::function<int()> &launch)
+{
+    return fans_passes(origins3, plan, foreign, stats, q, [&] { return launch(); });
 }
 
 int query_intersect_fans(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, void *d_hits)
@@ -875,15 +911,19 @@ int query_intersect_from_host(const float *origin, const float *dirs3, int nrays
 
 // The host form looks at every index before anything touches the device; the device form cannot (its kernels leave such a ray's
 // record unwritten).
-static int check_fans_host_args(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, const void *hits)
+int fans_index_args(int norigins, const int32_t *origin_of, int nrays)
 {
-    int rc;
-    if ((rc = check_fans_args(origins3, norigins, origin_of, dirs3, nrays, hits))) return rc;
     if (origin_of)
         for (int i = 0; i < nrays; i++)
             if (origin_of[i] < 0 || origin_of[i] >= norigins)
                 return fail(MIRT_ERR_INVALID_ARGUMENT, "origin_of[%d] = %d is outside [0, %d)", i, (int)origin_of[i], norigins);
     return MIRT_OK;
+}
+static int check_fans_host_args(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, const void *hits)
+{
+    int rc;
+    if ((rc = check_fans_args(origins3, norigins, origin_of, dirs3, nrays, hits))) return rc;
+    return fans_index_args(norigins, origin_of, nrays);
 }
 
 int query_intersect_fans_host(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, mirt_hit *hits)

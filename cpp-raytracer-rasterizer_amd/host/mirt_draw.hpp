@@ -204,6 +204,18 @@ struct RayTracer {
         check(mirt_intersect_ordered(rays.data(), n, reinterpret_cast<const mirt_hit *>(after), max_hits, reinterpret_cast<mirt_hit *>(ordered), count),
               "mirt_intersect_ordered");
     }
+    // The same for n rays that share their start -- the layers under every pixel of a perspective camera, everything under the cursor,
+    // a point light's translucent shadow map: ordered[k * max_hits + 0 ...] and count[k] as OrderedIntersections leaves them for the rays
+    // {start, dir[k]}, each ray walking its bin of the cube around `start` where that pays (mirt_intersect_ordered_from,
+    // mirt_set_query_mode; the cube is ClosestIntersection(start, dir, ...)'s own).
+    void OrderedIntersectionsFrom(vec3 start, const vec3 *dir, const Intersection *after, int max_hits, Intersection *ordered, int32_t *count, int n)
+    {
+        upload_scene();
+        static_assert(sizeof(vec3) == 12, "directions travel as they are");
+        check(mirt_intersect_ordered_from(&start.x, n > 0 ? &dir[0].x : nullptr, n, reinterpret_cast<const mirt_hit *>(after), max_hits,
+                                          reinterpret_cast<mirt_hit *>(ordered), count),
+              "mirt_intersect_ordered_from");
+    }
     // The same for n rays that share their start -- a probe's cube map, a fan from the eye or from a light: closest[k] comes back as
     // ClosestIntersection(start, dir[k], triangles, closest[k]) leaves it, each ray walking its bin of a cube around `start` where
     // that pays (mirt_intersect_from, mirt_set_query_mode).

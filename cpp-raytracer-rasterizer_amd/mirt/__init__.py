@@ -37,6 +37,7 @@ EXPORTS = (
     "mirt_set_ray_grid", "mirt_get_ray_grid_stats",
     "mirt_intersect_ordered", "mirt_intersect_ordered_device",
     "mirt_intersect_ordered_along", "mirt_intersect_ordered_along_device", "mirt_intersect_ordered_alongs", "mirt_intersect_ordered_alongs_device",
+    "mirt_intersect_ordered_from", "mirt_intersect_ordered_from_device", "mirt_intersect_ordered_fans", "mirt_intersect_ordered_fans_device",
     "mirt_shadow_mask", "mirt_shadow_mask_device", "mirt_direct_light_masked", "mirt_direct_light_masked_device", "mirt_get_shadow_mask_stats",
     "mirt_scene_upload_device", "mirt_scene_update_device", "mirt_scene_update", "mirt_scene_transform", "mirt_transform",
     "mirt_scene_download", "mirt_scene_info",
@@ -195,6 +196,10 @@ def load():
     lib.mirt_intersect_ordered_along_device.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
     lib.mirt_intersect_ordered_alongs.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
     lib.mirt_intersect_ordered_alongs_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
+    lib.mirt_intersect_ordered_from.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
+    lib.mirt_intersect_ordered_from_device.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
+    lib.mirt_intersect_ordered_fans.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
+    lib.mirt_intersect_ordered_fans_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
     lib.mirt_intersect_alongs.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp]
     lib.mirt_intersect_alongs_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp]
     lib.mirt_occluded_alongs.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]
@@ -784,7 +789,7 @@ def intersect_fans_device(origins, d_origin_of, d_dirs, nrays, d_hits):
 
 
 def fan_stats():
-    """The last intersect_from* call (mirt_get_fan_stats), in mirt_query_stats' fields: mode_used, cube_source (0 none, 1 built by
+    """The last intersect_from* / intersect_fans* / intersect_ordered_from* / intersect_ordered_fans* call (mirt_get_fan_stats), in mirt_query_stats' fields: mode_used, cube_source (0 none, 1 built by
     the call, 2 kept), cube_bins, shells and -- profiling on, binned -- shadow_rays = rays, candidates = rows stepped over, tests =
     rows tested, fallback_records = rays that swept the whole table."""
     return _read_query_stats(load().mirt_get_fan_stats)
@@ -1005,6 +1010,44 @@ def intersect_ordered_alongs_device(directions, d_dir_of, d_origins, nrays, d_af
     directions = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
     _check(load().mirt_intersect_ordered_alongs_device(_ptr(directions), len(directions), d_dir_of, d_origins, int(nrays), d_after, int(max_hits),
                                                        d_hits, d_counts))
+
+
+# ---- every hit along rays from shared origins, in order --------------------------------------------------------
+
+def intersect_ordered_from(origin, dirs, max_hits, after=None):
+    """intersect_ordered() for the rays {origin, dirs[i]}, byte for byte, through the cube of intersect_from where that pays
+    (mirt_intersect_ordered_from; set_query_mode, fan_stats): (hits[n, max_hits] HIT_DTYPE, counts[n] int32).  The layers under a
+    pixel of a perspective camera are hits[i, :counts[i]]."""
+    origin = np.ascontiguousarray(origin, np.float32).reshape(3)
+    dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    max_hits, after, hits, counts = _ordered_arrays(len(dirs), max_hits, after)
+    _check(load().mirt_intersect_ordered_from(_ptr(origin), _ptr(dirs), len(dirs), _ptr(after), max_hits, _ptr(hits), _ptr(counts)))
+    return hits, counts
+
+
+def intersect_ordered_from_device(origin, d_dirs, nrays, d_after, max_hits, d_hits, d_counts):
+    """The same on device arrays (raw pointers; the origin is host data, d_after may be None, or d_hits itself when max_hits is 1),
+    queued like a *_device frame; mirt.sync() completes it."""
+    origin = np.ascontiguousarray(origin, np.float32).reshape(3)
+    _check(load().mirt_intersect_ordered_from_device(_ptr(origin), d_dirs, int(nrays), d_after, int(max_hits), d_hits, d_counts))
+
+
+def intersect_ordered_fans(origins, origin_of, dirs, max_hits, after=None):
+    """intersect_ordered() for the rays {origins[origin_of[i]], dirs[i]}, byte for byte, through the cubes of intersect_fans
+    (mirt_intersect_ordered_fans): (hits[n, max_hits], counts[n]).  origin_of: one int32 per ray, or None for a single origin."""
+    origins, origin_of, dirs = _as_fans(origins, origin_of, dirs)
+    max_hits, after, hits, counts = _ordered_arrays(len(dirs), max_hits, after)
+    _check(load().mirt_intersect_ordered_fans(_ptr(origins), len(origins), _ptr(origin_of), _ptr(dirs), len(dirs), _ptr(after), max_hits,
+                                              _ptr(hits), _ptr(counts)))
+    return hits, counts
+
+
+def intersect_ordered_fans_device(origins, d_origin_of, d_dirs, nrays, d_after, max_hits, d_hits, d_counts):
+    """The same on device arrays (raw pointers; the origins are host data, d_origin_of may be None for a single origin).  A ray whose
+    index names no origin keeps its slots as they were and gets the count 0."""
+    origins = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    _check(load().mirt_intersect_ordered_fans_device(_ptr(origins), len(origins), d_origin_of, d_dirs, int(nrays), d_after, int(max_hits),
+                                                     d_hits, d_counts))
 
 
 # ---- shadow masks: DirectLight's shadow decisions, and DirectLight from them ---------------------------------

@@ -68,6 +68,25 @@ __device__ __forceinline__ uint32_t fan_list(const CubeView &cv, uint32_t k, uin
     return key;
 }
 
+// The origin of lane `ray` in one pass of a many-origin call (rt_query.hip: k_query_fans_binned's paragraph): whether the ray is the pass's at all, and the
+// position k, origin S, first bin and sweep table of a ray that is -- position 0's for one that is not.  idx is the ray's index as
+// the caller gave it.
+struct FansLane { bool mine; uint32_t idx, k, bin_base; v3 S; const OriginRow *tab; };
+__device__ __forceinline__ FansLane fans_lane(const QueryFansFrame &qf, long long ray, bool ok)
+{
+    const QueryFanFrame &q = qf.f;
+    const uint32_t face_bins = (uint32_t)(q.cube.cube_bins * q.cube.cube_bins) * 6u;
+    FansLane l;
+    l.idx = qf.origin_of ? (uint32_t)qf.origin_of[ok ? ray : 0] : 0u;
+    const uint32_t rel = l.idx - (uint32_t)qf.first;               // (modulo 2^32: a negative or huge index lands beyond count)
+    l.mine = ok && rel < (uint32_t)qf.count;
+    l.k = l.mine ? rel : 0u;
+    l.bin_base = l.k * face_bins;
+    l.S = ld3(qf.origins + 3 * (size_t)(1u + l.k));
+    l.tab = q.tab + (size_t)l.k * q.n;
+    return l;
+}
+
 // ---- the row test of the caller's own rays, shared by rt_query.hip and ../along/along.hip ------------------------------------------
 
 // Whether the rows of the scene are inside the filter's range for every start below MIRT_QUERY_START_MAX (rt_query.hip's header

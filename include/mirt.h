@@ -711,6 +711,28 @@ MIRT_API int mirt_intersect_ordered_alongs(const float *dirs3, int ndirs, const 
 MIRT_API int mirt_intersect_ordered_alongs_device(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, const void *d_after,
                                                   int max_hits, void *d_hits, void *d_counts);
 
+/* The same for rays that share their origin -- an eye, a probe, a point light: transparency layers and depth peeling under a
+ * perspective camera, a pick that reports everything under the cursor, the thickness of a part seen from a sensor, a point light's
+ * translucent shadow map, a bounce ray from a surface point that skips the surface it starts on.  The four calls are
+ * mirt_intersect_ordered on the rays {origin, dirs[i]} or {origins[origin_of[i]], dirs[i]}, byte for byte: max_hits, `after`, the
+ * slots, the counts and the overlap rule (after == hits only with max_hits == 1) are that call's, the origins, directions and
+ * origin_of those of mirt_intersect_from* / mirt_intersect_fans* (origins on the host in the _device forms too), and the argument
+ * checks the union of both (MIRT_ERR_INVALID_ARGUMENT, nothing written; nrays == 0 does nothing).  So slot 0 without `after` is
+ * mirt_intersect_from / mirt_intersect_fans on a fresh record, all 20 bytes.  They are dispatched as the fan calls are:
+ * mirt_set_query_mode applies, AUTO is their rule, the cubes kept around the origins are the very ones those calls (and
+ * mirt_occluded_fans*) build and use, and mirt_get_fan_stats reports the call.  What is not binned sweeps every triangle;
+ * mirt_set_ray_grid does not affect these calls.  A call of more origins than one cube holds runs in passes; the in-place peel is
+ * safe across them.  An index of origin_of outside [0, norigins): the host form refuses the call; the _device form leaves that
+ * ray's slots unwritten and writes its count 0. */
+MIRT_API int mirt_intersect_ordered_from(const float origin[3], const float *dirs3, int nrays, const mirt_hit *after /* nullable */, int max_hits,
+                                         mirt_hit *hits /* nrays * max_hits, ray-major */, int32_t *counts /* nrays */);
+MIRT_API int mirt_intersect_ordered_from_device(const float origin[3], const void *d_dirs3, int nrays, const void *d_after, int max_hits, void *d_hits,
+                                                void *d_counts);
+MIRT_API int mirt_intersect_ordered_fans(const float *origins3, int norigins, const int32_t *origin_of /* nullable for one origin */, const float *dirs3,
+                                         int nrays, const mirt_hit *after /* nullable */, int max_hits, mirt_hit *hits, int32_t *counts);
+MIRT_API int mirt_intersect_ordered_fans_device(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays,
+                                                const void *d_after, int max_hits, void *d_hits, void *d_counts);
+
 /* ---- shadow masks: DirectLight's shadow decision per (record, light position), and DirectLight from a mask (additions to ABI 4) ---- */
 
 /* The one value DirectLight computes and throws away (raytracer.cpp:306-315): whether the shadow ray of a record towards a light

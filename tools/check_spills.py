@@ -65,6 +65,10 @@ EXPECT = ("k_rt_trace2", "k_rt_tile2", "k_rt_brute", "k_bin_pairs", "k_raster_sm
           "k_along_order<4, false>", "k_along_order<4, true>", "k_along_order<8, false>", "k_along_order<8, true>",
           "k_alongs_order<1, false>", "k_alongs_order<1, true>", "k_alongs_order<2, false>", "k_alongs_order<2, true>",
           "k_alongs_order<4, false>", "k_alongs_order<4, true>", "k_alongs_order<8, false>", "k_alongs_order<8, true>",
+          "k_fan_order<1, false>", "k_fan_order<1, true>", "k_fan_order<2, false>", "k_fan_order<2, true>",
+          "k_fan_order<4, false>", "k_fan_order<4, true>", "k_fan_order<8, false>", "k_fan_order<8, true>",
+          "k_fans_order<1, false>", "k_fans_order<1, true>", "k_fans_order<2, false>", "k_fans_order<2, true>",
+          "k_fans_order<4, false>", "k_fans_order<4, true>", "k_fans_order<8, false>", "k_fans_order<8, true>",
           "k_frame_records", "k_frame_resolve", "k_aa_primary<false>", "k_aa_primary<true>", "k_aa_resolve",
           "k_scene_bounds_init", "k_scene_range<1>", "k_scene_range<3>", "k_scene_range<5>", "k_scene_range<7>", "k_scene_range<4>", "k_scene_range<11>")
 missing = [k for k in EXPECT if not any(k in r[1] for r in rows)]
