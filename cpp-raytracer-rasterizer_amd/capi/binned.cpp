@@ -194,7 +194,8 @@ static int cube_bin_chain(LightPass &S, const BinFrameDesc *d_frames, const floa
 // frames of both streams read the tables -- whenever the scene, a light position or the grid differs from what is held.  (Lights
 // that just moved do not come here: binned_pass bins their cubes together with the camera frame, on the frame's own stream.)
 // C: the frame path's shared cube (g.lc) or the queries' (g.qrows.cube); either is read by the work of every stream.
-int light_cache_ensure(LightCache &C, LightPass &S, const float *origins, int nlights, int cube_bins, bool *built)
+// shadowed: the cube also gets its covered words (LightCache::d_shadowed) -- the frame path's cube; the queries' cubes have no use for them.
+int light_cache_ensure(LightCache &C, LightPass &S, const float *origins, int nlights, int cube_bins, bool *built, bool shadowed)
 {
     int rc;
     const uint64_t key = light_key_of(origins, nlights);
@@ -218,6 +219,13 @@ int light_cache_ensure(LightCache &C, LightPass &S, const float *origins, int nl
     C.nbins = nkeys;
     C.nrows = 0;
     C.shells = shells;
+    C.nlights = nlights; C.n = g.n;
+    C.has_shadowed = false;
+    if (shadowed && g.n > 0) {                               // (no scene: nothing to allocate or fill, and has_shadowed stays false below)
+        // zero on the way: a cube without positions or without a single pair leaves every word clear
+        if ((size_t)g.n > C.cap_shadowed && (rc = dev_grow(&C.d_shadowed, &C.cap_shadowed, (size_t)g.n, (size_t)SHADOWED_HEAD + (size_t)g.n, false))) return rc;
+        HIP_TRY(hipMemsetAsync(C.d_shadowed, 0, sizeof(uint32_t) * ((size_t)SHADOWED_HEAD + (size_t)g.n), g.stream));
+    }
     if (nlights > 0) {
         BinFrameDesc frames[6 * MIRT_MAX_LIGHTS];
         fill_light_frames(frames, origins, nlights, cube_bins, shells, 0u, g.bbox_lo, g.bbox_hi);
@@ -239,6 +247,10 @@ int light_cache_ensure(LightCache &C, LightPass &S, const float *origins, int nl
         if (npairs)
             hipLaunchKernelGGL(k_expand_light_rows, dim3((unsigned)std::min<uint32_t>((npairs + 255) / 256, 4096u)), dim3(256), 0, g.stream,
                                C.d_off, S.pairs.d_entries, nlights, per_light, C.d_light_tab, g.n, C.d_rows, (const uint32_t *)nullptr, 0u, C.d_row_tri);
+        // ... and which triangles one of those rows hides whole from a position (rt_trace.hip): one thread per (triangle, position)
+        if (npairs && shadowed)
+            hipLaunchKernelGGL(k_shadowed_table, dim3((unsigned)((g.n + 255) / 256), (unsigned)nlights), dim3(256), 0, g.stream,
+                               g.d_tris, g.n, C.d_origins, C.d_light_tab, C.d_off, C.d_rows, C.d_frames, cube_bins, shells, C.d_shadowed + SHADOWED_HEAD);
         HIP_TRY(hipGetLastError());
         S.kept = KeptPass();                                 // the stream's pair list now holds the build, a pass of no kind a frame runs
     } else {
@@ -251,6 +263,7 @@ int light_cache_ensure(LightCache &C, LightPass &S, const float *origins, int nl
     }
     C.key = key;
     C.cube_bins = cube_bins;
+    C.has_shadowed = shadowed && g.n > 0;
     C.valid = true;
     return MIRT_OK;
 }
@@ -381,7 +394,7 @@ int binned_pass(const mirt_view *view, StreamState &ss, const float *origins, in
     const bool transient = nlights > 0 && !fixed_grid && !g.lc.holds(lkey, fine_bins) && g.lc.stable < LIGHT_STABLE_FRAMES;
 
     k_begin(MIRT_K_BIN);
-    if (!transient && (rc = light_cache_ensure(g.lc, L, origins, nlights, fine_bins))) return rc;   // (in the light pass's scratch: the camera's tables stay)
+    if (!transient && (rc = light_cache_ensure(g.lc, L, origins, nlights, fine_bins, nullptr, true))) return rc;   // (in the light pass's scratch: the camera's tables stay)
     const int cube_bins = transient ? CUBE_BINS_MIN : fine_bins;
 
     BinSet bs;
@@ -492,7 +505,11 @@ int binned_pass(const mirt_view *view, StreamState &ss, const float *origins, in
     // kernel reads the count with its other counters, without a branch, so it gets a word that is there and a cap no count exceeds
     bp->cube = transient ? cube_view(L, cube_bins, tshells) : cube_view(g.lc);
     bp->light_tab = transient ? L.d_light_tab : g.lc.d_light_tab;
-    bp->light_pair_count = transient ? L.d_bin_counters : S.d_bin_counters;
+    // The shared cube's covered words (a pixel on a covered triangle has no shadow ray, rt_trace.hip) arrive as that word: the head of
+    // their block reads zero.  A frame's own cubes have none; MIRT_TR_SHADOWED=0 hands none over either.
+    static const int shadowed_env = (int)env_int("MIRT_TR_SHADOWED", 1);
+    bp->shadowed = !transient && shadowed_env != 0 && g.lc.has_shadowed;
+    bp->light_pair_count = transient ? L.d_bin_counters : bp->shadowed ? g.lc.d_shadowed : S.d_bin_counters;
     bp->light_pair_cap = transient ? L.pairs.cap_used : 0xFFFFFFFFu;
     return MIRT_OK;
 }
@@ -553,7 +570,7 @@ int binned_trace(const RtFrame &f, StreamState &ss, const BinnedPass &bp)
     // a tile's list ends at the depth shell of the tile's farthest record (rt_trace.hip); MIRT_TR_LIST_END=0 walks every list to its end
     static const int list_end_env = (int)env_int("MIRT_TR_LIST_END", 1);
     // (what is uniform per launch -- planes asked for, one sample per light, these two settings -- in one word: csrc/rt_trace_frame.hpp)
-    tf.flags = trace_frame_flags(tf.f, lazy_geo, list_end_env != 0);
+    tf.flags = trace_frame_flags(tf.f, lazy_geo, list_end_env != 0, bp.shadowed);
     tf.pair_count = S.d_bin_counters;
     tf.pair_cap = S.pairs.cap_used;
     tf.light_pair_count = bp.light_pair_count;
@@ -585,3 +602,22 @@ int binned_trace(const RtFrame &f, StreamState &ss, const BinnedPass &bp)
 }
 
 }  // namespace mirt
+
+// The shared cube's covered words for one light position, a byte per triangle (1: the frames cast no shadow ray from that triangle
+// towards that position).  Waits for everything in flight; an error when no shared cube with the words is held -- before the first
+// binned frame, after a scene change or a light move until the cube is back -- or when it holds other positions or triangles.
+extern "C" int mirt_get_shadowed(int position, uint8_t *out, int n)
+{
+    using namespace mirt;
+    int rc;
+    if ((rc = need_init())) return rc;
+    if (!out || n < 0 || position < 0) return fail(MIRT_ERR_INVALID_ARGUMENT, "get shadowed: position %d, %d triangles", position, n);
+    const LightCache &C = g.lc;
+    if (!C.valid || !C.has_shadowed) return fail(MIRT_ERR_INVALID_ARGUMENT, "get shadowed: no shared light cube is held (render binned frames under lights that stand still first)");
+    if (position >= C.nlights || n != C.n) return fail(MIRT_ERR_INVALID_ARGUMENT, "get shadowed: position %d of %d, %d of %d triangles", position, C.nlights, n, C.n);
+    HIP_TRY(sync_all());
+    std::vector<uint32_t> words((size_t)n);
+    if (n) HIP_TRY(hipMemcpy(words.data(), C.d_shadowed + SHADOWED_HEAD, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    for (int t = 0; t < n; t++) out[t] = (uint8_t)((words[(size_t)t] >> position) & 1u);
+    return MIRT_OK;
+}

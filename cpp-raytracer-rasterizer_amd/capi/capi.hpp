@@ -66,6 +66,7 @@ MIRT_KERNEL void k_select_faces(const float *, int, const float *, const BinFram
 MIRT_KERNEL void k_tile_order(const uint32_t *, int, int, int, int, uint32_t *, uint32_t, TilePairRec *, uint32_t);
 MIRT_KERNEL void k_geo_table(const float *, int, GeoRow *, ShadeRow *);
 MIRT_KERNEL void k_expand_light_rows(const uint32_t *, const uint32_t *, int, uint32_t, const OriginRow *, int, LightRow *, const uint32_t *, uint32_t, uint32_t *);
+MIRT_KERNEL void k_shadowed_table(const float *, int, const float *, const OriginRow *, const uint32_t *, const LightRow *, const BinFrameDesc *, int, int, uint32_t *);
 MIRT_KERNEL void k_cull(const float *, int, const CullParams, uint8_t *);
 size_t rt_trace_lds_bytes(int waves);
 int launch_raster(RasterFrame &f, RasterScratch &s, uint64_t scene_version, hipStream_t stream, hipEvent_t *ev, bool *ev_used);
@@ -227,6 +228,13 @@ struct LightCache {
     int shells = 1;                              // depth shells per bin of the tables held
     float *d_origins = nullptr;                  // (1 + MIRT_MAX_LIGHTS) x 3
     uint32_t *d_counter = nullptr;               // pair counter of the build
+    // The covered words of the frame path's cube (csrc/shadowed.hpp; light_cache_ensure builds them where asked to): SHADOWED_HEAD
+    // words that stay zero -- the trace kernel reads word 0 as the pair count of a cube that never overflows -- then one word per
+    // triangle, bit k = "one other triangle hides the whole triangle from position k".  Under the cube's key: built with it, gone with it.
+    uint32_t *d_shadowed = nullptr;
+    size_t cap_shadowed = 0;                     // triangles it has room for
+    bool has_shadowed = false;                   // the tables held carry the words
+    int nlights = 0, n = 0;                      // positions and triangles of the tables held
 
     bool holds(uint64_t k, int bins) const { return valid && key == k && cube_bins == bins; }
     void release();
@@ -653,6 +661,7 @@ struct BinnedPass {
     const OriginRow *light_tab;
     const uint32_t *light_pair_count;
     uint32_t light_pair_cap;
+    bool shadowed;                               // light_pair_count is the head of the shared cube's covered words (TRF_SHADOWED)
 };
 // The view of a cube's tables (pass_plan.hpp: make_cube_view): of a cache, and of a stream's light pass binned on a grid of
 // cube_bins with `shells` depth shells (its row table is there once a pass has run).
@@ -663,7 +672,7 @@ inline CubeView cube_view(const LightPass &L, int cube_bins, int shells)
 }
 // A light cube's tables in C for `nlights` light positions (origins[3 ..]) on a grid of cube_bins, built on g.stream in S -- a
 // stream's light pass, whose kept pass the build evicts -- unless C holds them already; *built says which.
-int light_cache_ensure(LightCache &C, LightPass &S, const float *origins, int nlights, int cube_bins, bool *built = nullptr);
+int light_cache_ensure(LightCache &C, LightPass &S, const float *origins, int nlights, int cube_bins, bool *built = nullptr, bool shadowed = false);
 uint64_t light_key_of(const float *origins, int nlights);
 // Bins per face side of the cubes of `nlights` light positions under the frame path's rules (scene size, MIRT_CUBE_BINS, the
 // sort's key space); *fixed_grid: the environment fixed it.  light_keys_fit: one sort pass holds such a cube's keys at all.

@@ -189,7 +189,7 @@ void AlongsBuild::release()
     *this = AlongsBuild();
 }
 
-void LightCache::release() { dev_free({ d_light_tab, d_frames, d_off, d_rows, d_row_tri, d_origins, d_counter }); *this = LightCache(); }
+void LightCache::release() { dev_free({ d_light_tab, d_frames, d_off, d_rows, d_row_tri, d_origins, d_counter, d_shadowed }); *this = LightCache(); }
 
 int StreamState::create()
 {

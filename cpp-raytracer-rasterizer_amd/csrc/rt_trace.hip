@@ -25,13 +25,16 @@
 //     distance from the light, so this drops most of it.  A pixel whose light term is exactly zero (a face turned away from the
 //     light) has no ray at all -- its answer could not change a bit of the frame --, and the rays that are needed are dealt evenly
 //     over the lanes through a table in LDS: a lane walks ray l and then ray l + 64 of the wave back to back, whosever pixels
-//     they belong to (the wave's steps are the max over its lanes of what a lane walks);
+//     they belong to (the wave's steps are the max over its lanes of what a lane walks); nor has a pixel on a triangle that ONE
+//     other triangle hides whole from the light (covers_whole, shadowed.hpp; found once per shared cube by k_shadowed_table): its
+//     light term is zero before any ray is dealt;
 //   * a frame whose pair list overflowed (sized from an earlier frame's count, capi/binned.cpp) is rendered by the SAME kernel
 //     with "every triangle" as each tile's list -- brute force, same bits -- instead of by a guard launch behind it;
 //   * workgroups are mapped to screen blocks so that the blocks an XCD (private L2) works on are neighbours.
 //
 // Same filter and the same exact arithmetic as every other kernel => bit-identical results.
 #include "rt_trace_frame.hpp"
+#include "shadowed.hpp"
 
 #include <float.h>
 
@@ -262,6 +265,35 @@ __device__ __forceinline__ uint32_t cube_bin_of1(v3 rd, uint32_t face_base0, int
     return face_base0 + (uint32_t)face * (uint32_t)(cube_bins * cube_bins) + (uint32_t)j * cube_bins + (uint32_t)i;
 }
 
+// The shared cube's covered words (shadowed.hpp): bit k of shadowed[t] is set when ONE row of the cube hides the whole of triangle t
+// from light position k.  One thread per (triangle, position), behind k_expand_light_rows.  It looks where a shadow ray from T's
+// centroid would: the cube bin of the direction from the centroid to the light (cube_bin_of1, the walk's own function) -- a U that
+// covers T's whole cone contains that direction, so by the lists' conservativeness U is on that bin's list --, shells 0 .. the shell
+// of 0.99 near(T), and stops at the first row covers_whole accepts.  A miss (U filed in the neighbouring bin of a direction on a bin
+// border, say) leaves the bit clear: the ray is then walked as before.  shadowed: zero on entry.
+__global__ __launch_bounds__(256) void k_shadowed_table(const float *__restrict__ tris15, int n, const float *__restrict__ origins /* (1 + nl) x 3 */,
+                                                        const OriginRow *__restrict__ light_tab, const uint32_t *__restrict__ light_off,
+                                                        const LightRow *__restrict__ rows, const BinFrameDesc *__restrict__ frames, int cube_bins,
+                                                        int shells, uint32_t *__restrict__ shadowed)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, k = (int)blockIdx.y;
+    if (t >= n) return;
+    const v3 S = ld3(origins + 3 * (1 + k));
+    const float *t15 = tris15 + (size_t)15 * t;
+    const v3 v0 = ld3(t15), v1 = ld3(t15 + 3), v2 = ld3(t15 + 6);
+    const float thr = 0.99f * light_tab[(size_t)k * n + t].r1.w;             // 0.99 near(T): what covers_whole compares `far` with
+    if (!(thr > 0.0f)) return;                                               // (S inside T's bounding sphere, or NaN: nothing is provable)
+    const v3 c = V3((v0.x + v1.x + v2.x) * (1.0f / 3.0f), (v0.y + v1.y + v2.y) * (1.0f / 3.0f), (v0.z + v1.z + v2.z) * (1.0f / 3.0f));
+    const uint32_t face0 = (uint32_t)k * 6u * (uint32_t)(cube_bins * cube_bins);
+    const uint32_t key0 = cube_bin_of1(sub3(S, c), face0, cube_bins) * (uint32_t)shells;
+    const BinFrameDesc *lf = frames + 6 * k;
+    const uint32_t end = light_off[key0 + bin_shell_of(thr, lf->shell_d0, lf->shell_iw, shells) + 1u];
+    for (uint32_t e = light_off[key0]; e < end; e++) {
+        if (!(rows[e].r2.w < thr)) continue;                                 // (the cheap half of the predicate first)
+        if (covers_whole(rows[e], v0, v1, v2, S)) { atomicOr(&shadowed[t], 1u << k); return; }
+    }
+}
+
 // (TilePairRec, the ORDER_* constants and RtTraceFrame: rt_trace_frame.hpp, shared with capi/binned.cpp)
 
 // One wave renders one PAIR of horizontally adjacent tiles.  Two things decide which wave takes which pair:
@@ -322,6 +354,10 @@ __global__ __launch_bounds__(64) void k_tile_order(const uint32_t *__restrict__ 
 #endif
 #ifndef MIRT_TR_WAVES_MIN
 #define MIRT_TR_WAVES_MIN 3
+#endif
+// (experiments) 0: a wave whose hits are all on covered triangles still computes the light term it then zeroes (profiles/trace_shadowed_ab.txt: step s1)
+#ifndef MIRT_TR_COVER_SKIP
+#define MIRT_TR_COVER_SKIP 1
 #endif
 // STATS: the kernel's own counts (tests executed, candidates offered, wave steps of the two filter loops, drains: what
 // mirt_get_stats reports and the roofline's `achieved` is made of).  Keeping them costs five scalar instructions in every step of
@@ -600,6 +636,13 @@ __global__ __launch_bounds__(64 * TR_WG_WAVES) __attribute__((amdgpu_waves_per_e
             if (hmA | hmB) {
                 const ShadeRow *srA = tf.shade + (biA >= 0 ? biA : 0), *srB = tf.shade + (biB >= 0 ? biB : 0);
                 const float4 nA4 = srA->n, nB4 = srB->n;
+                // the covered words of the two triangles (k_shadowed_table above; bit k: one other triangle hides the whole triangle from
+                // light position k), asked for beside the normals; zero where the frame has no table (lights that just moved, MIRT_TR_SHADOWED=0)
+                uint32_t cwA = 0u, cwB = 0u;
+                if (flags & TRF_SHADOWED) {
+                    const uint32_t *cov = tf.light_pair_count + SHADOWED_HEAD;
+                    cwA = cov[biA >= 0 ? biA : 0]; cwB = cov[biB >= 0 ? biB : 0];
+                }
                 // (the four-wave instantiations fetch the triangles' colours here, beside the normals, and hold them across the shadow
                 // walk: the six registers that put the kernel at 98 and so at four waves per SIMD, which is what the small scenes' frames
                 // in flight want -- see above the kernel)
@@ -616,6 +659,18 @@ __global__ __launch_bounds__(64 * TR_WG_WAVES) __attribute__((amdgpu_waves_per_e
                 for (int k = 0; k < f.nlights; k++) {
                     // DirectLight's term before the shadow test (raytracer.cpp:294-304), both pixels at once
                     // r = distance(pos, lightPos), A = 4 pi r^2, rDir = normalize(lightPos - pos), B = P / A with P = lightColor / samples (:296, divided on the host)
+                    // the pixel's triangle is covered for this position (the table's bit; see below)
+                    const bool coverA = ((cwA >> k) & 1u) != 0u, coverB = ((cwB >> k) & 1u) != 0u;
+#if MIRT_TR_COVER_SKIP
+                    // A wave in which EVERY hit is covered for this position: every D is (0, 0, 0) whatever r, rDir and B are -- the light
+                    // term is not computed at all (a uniform branch; the position's bookkeeping as at the end of the loop's body).
+                    if (!wballot((hitA && !coverA) || (hitB && !coverB))) {
+                        result = add3p(result, splat3(V3(0.0f, 0.0f, 0.0f)));
+                        if (one_sample || --samples_left == 0) { result2 = add3p(result2, result); samples_left = f.samples; }
+                        TM_SEG(5)                                  // (the skipped position's ticks belong to the light term's segment)
+                        continue;
+                    }
+#endif
                     const v3 L = ld3(f.lpos[k]);
                     const LightGeometry2 lg = light_geometry2(pos, L, ld3(f.lcol[k]), f.lights_in_range != 0, hitA, hitB);
                     const f2 r = lg.r;
@@ -631,6 +686,13 @@ __global__ __launch_bounds__(64 * TR_WG_WAVES) __attribute__((amdgpu_waves_per_e
                     // written to slot `rank` of the wave's ray table {rDir, pixel}; lane l then walks slot l and, in a wave with more than
                     // 64 rays, slot l + 64.  A lane so walks the rays of other lanes' pixels: what it finds goes to s.flag[pixel], which
                     // the pixel's own lane reads behind the walk.  (0.99 r stays where the drains look for it: s.thr[pixel].)
+                    // ... and of those, the ray of a pixel on a triangle the table calls covered for this position is known to end occluded
+                    // (csrc/shadowed.hpp: the reference accepts the covering triangle from every hit point it can compute there, closer than
+                    // 0.99 r): its D becomes (0, 0, 0) here, by select -- what the found occluder would store, for a NaN D too -- and no ray
+                    // is dealt for it.  Everything behind -- ranks, the ray table, the wave without a ray -- is as it was.
+                    // (A covered pixel whose D was +-0 anyway gets +0: the same sum, shadow_ray_needed's argument in rt_common.hpp.)
+                    D.x.x = coverA ? 0.0f : D.x.x; D.y.x = coverA ? 0.0f : D.y.x; D.z.x = coverA ? 0.0f : D.z.x;
+                    D.x.y = coverB ? 0.0f : D.x.y; D.y.y = coverB ? 0.0f : D.y.y; D.z.y = coverB ? 0.0f : D.z.y;
                     const bool needA = hitA && shadow_ray_needed(D.x.x, D.y.x, D.z.x), needB = hitB && shadow_ray_needed(D.x.y, D.y.y, D.z.y);
                     const unsigned long long nmA = wballot(needA), nmB = wballot(needB);
                     const int nrA = __popcll(nmA), nrays = nrA + __popcll(nmB);

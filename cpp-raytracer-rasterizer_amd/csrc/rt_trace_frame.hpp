@@ -26,15 +26,25 @@ enum : uint32_t {
     TRF_LAZY_GEO = 4u,                           // geometry rows are fetched by the exact stage, for the pairs it accepts, instead of being staged
                                                  // with every candidate (scenes whose tables no longer fit the caches: see the staging code)
     TRF_LIST_END = 8u,                           // a tile's list ends at the shell of the tile's farthest record (the primary loop); MIRT_TR_LIST_END
+    TRF_SHADOWED = 16u,                          // the shared cube's table of covered triangles stands behind light_pair_count (below); MIRT_TR_SHADOWED
 };
 
-inline uint32_t trace_frame_flags(const RtFrame &f, bool lazy_geo, bool list_end)
+// The shared cube's covered words (csrc/shadowed.hpp, k_shadowed_table): bit k of word t says that one other triangle hides the whole
+// of triangle t from light position k.  The table travels in the block the shared cube hands the kernel as light_pair_count: the
+// cube's lists never overflow, so the count is a word that is always zero -- word 0 of that block -- and the n words of the table
+// start SHADOWED_HEAD words behind it (a cache line of their own).  The parameter block keeps its size and every field its offset:
+// both are pinned as literal numbers below and in tests/cpp/trace_flags_test.cpp, and the block's four 4-byte paddings are not
+// contiguous, so a pointer of its own would move the fields behind it.  Whoever lifts that pin should give the table its own field.
+constexpr uint32_t SHADOWED_HEAD = 16;
+
+inline uint32_t trace_frame_flags(const RtFrame &f, bool lazy_geo, bool list_end, bool shadowed = false)
 {
     uint32_t flags = 0u;
     if (f.rgb || f.index || f.fd || f.dist || f.pos) flags |= TRF_PLANES;
     if (f.samples == 1) flags |= TRF_ONE_SAMPLE;
     if (lazy_geo) flags |= TRF_LAZY_GEO;
     if (list_end) flags |= TRF_LIST_END;
+    if (shadowed) flags |= TRF_SHADOWED;
     return flags;
 }
 
@@ -63,7 +73,8 @@ struct RtTraceFrame {
     const uint32_t *sel;              // the triangles k_prep_select found the frame may see, and how many: what a frame that fell
     const uint32_t *sel_count;        // back to brute force walks (their origin rows are the ones the frame has built)
     const uint32_t *light_pair_count; // the same for the light-cube lists when a pass of their own built them (the shared, cached cube never
-    uint32_t light_pair_cap;          // overflows: any readable word and a cap of 2^32 - 1): beyond it the shadow rays walk the lights' origin tables
+    uint32_t light_pair_cap;          // overflows: a word that reads zero and a cap of 2^32 - 1): beyond it the shadow rays walk the lights' origin tables.
+                                      // TRF_SHADOWED: the word is the head of the shared cube's covered table (SHADOWED_HEAD above)
 };
 
 // Host and device passes must agree on the block's layout, byte for byte: the numbers are spelled out, so that either pass fails to

@@ -43,6 +43,7 @@ EXPORTS = (
     "mirt_scene_download", "mirt_scene_info",
     "mirt_scene_set_objects", "mirt_scene_pose", "mirt_pose",
     "mirt_set_supersampled_many_lights", "mirt_get_supersample_stats",
+    "mirt_get_shadowed",
 )
 
 
@@ -209,6 +210,7 @@ def load():
     lib.mirt_direct_light_masked.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp]
     lib.mirt_direct_light_masked_device.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp]
     lib.mirt_get_shadow_mask_stats.argtypes = [C.POINTER(QueryStats)]
+    lib.mirt_get_shadowed.argtypes = [C.c_int, _vp, C.c_int]
     lib.mirt_scene_upload_device.argtypes = [_vp, _vp, C.c_int]
     lib.mirt_scene_update_device.argtypes = [C.c_int, C.c_int, _vp]
     lib.mirt_scene_update.argtypes = [C.c_int, C.c_int, _vp]
@@ -1114,6 +1116,14 @@ def shadow_mask_stats():
     """The last shadow_mask* call (mirt_get_shadow_mask_stats), in mirt_query_stats' fields with DirectLight's meanings; with
     profiling on the counters are filled for a sweep as well: shadow_rays = records x positions."""
     return _read_query_stats(load().mirt_get_shadow_mask_stats)
+
+
+def get_shadowed(position, n):
+    """One byte per triangle (mirt_get_shadowed): 1 where one other triangle hides the whole triangle from light position `position`
+    -- the binned frames cast no shadow ray from it.  MirtError while no shared light cube is held."""
+    out = np.zeros(int(n), np.uint8)
+    _check(load().mirt_get_shadowed(int(position), _ptr(out), int(n)))
+    return out
 
 
 # ---- several GPUs: band sharding with the gather inside the library ------------------------------------

@@ -780,6 +780,15 @@ MIRT_API int mirt_direct_light_masked_device(const void *d_hits, int nhits, cons
  * before the ray's first occluder, fallback_records as for mirt_direct_light (0 for a sweep).  Waits for the stream of that call. */
 MIRT_API int mirt_get_shadow_mask_stats(mirt_query_stats *out);
 
+/* Which triangles a binned frame casts no shadow ray from: out[t] = 1 when ONE other triangle hides the whole of triangle t from
+ * light position `position` (lights x soft-shadow samples, in the frames' order), so that DirectLight's term for that position is
+ * (0, 0, 0) at every hit point on t -- the frames conclude so without a ray (MIRT_TR_SHADOWED=0 in the environment makes them cast
+ * it all the same; the frames are bit for bit the same either way).  The table belongs to the light cube the binned frames share
+ * once the lights have stood still for a few frames; n must be the scene's triangle count.  MIRT_ERR_INVALID_ARGUMENT when no such
+ * cube is held (no binned frame yet, the scene or a light has just changed), for a position it does not hold or another n.  Waits
+ * for everything in flight. */
+MIRT_API int mirt_get_shadowed(int position, uint8_t *out, int n);
+
 /* ---- rasteriser: replaces Update()'s clear + Draw() + CalculateDOF() of rasteriser.cpp:183-192,461-529 */
 
 /* One frame into host buffers.  Every word of out_xrgb is written: the whole surface is cleared to black

@@ -43,7 +43,7 @@ for r in rows:
     hint = "   (%d VGPRs above %d waves per SIMD)" % (over, w + 1) if 0 < over <= 8 else ""
     print("%-22s %-44s vgprs %3d scratch %4d occupancy %d%s" % (r + (hint,)))
 # the gate must not pass vacuously: should the backend's resource comments change shape, the pattern above matches nothing
-EXPECT = ("k_rt_trace2", "k_rt_tile2", "k_rt_brute", "k_bin_pairs", "k_raster_small", "k_raster_resolve", "k_dof_tile", "k_bs_local",
+EXPECT = ("k_rt_trace2", "k_shadowed_table", "k_rt_tile2", "k_rt_brute", "k_bin_pairs", "k_raster_small", "k_raster_resolve", "k_dof_tile", "k_bs_local",
           "k_query_rows", "k_query_closest<", "k_query_closest_wave", "k_query_direct_light<", "k_query_direct_light_binned",
           "k_query_fan<", "k_query_fan_binned<false>", "k_query_fan_binned<true>", "k_query_fans_binned<false>", "k_query_fans_binned<true>",
           "k_query_fans_expand",
