@@ -822,18 +822,59 @@ int grid_begin(const void *d_rays, int nrays, GridFrame *frame, bool *binned);
 long query_wave_rays();
 
 // ---- every hit along a ray, in order (order.cpp; the kernels: ../order/ordered_hits.hip) ----
-int order_intersect(const void *d_rays, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts);
+// A device form takes what the ordered call adds to its rays -- (d_after, max_hits, d_hits, d_counts) -- as the block its kernels
+// take (../order/order_out.hpp), from the entry point to the frame that embeds it.
+inline OrderOut order_out(const void *d_after, int max_hits, void *d_hits, void *d_counts)
+{
+    return { static_cast<const uint32_t *>(d_after), max_hits, static_cast<int32_t *>(d_counts), static_cast<uint32_t *>(d_hits) };
+}
+int order_intersect(const void *d_rays, int nrays, const OrderOut &out);
 int order_intersect_host(const mirt_ray *rays, int nrays, const mirt_hit *after, int max_hits, mirt_hit *hits, int32_t *counts);
-// What order_along.cpp shares with it: the checks of the arguments alone, the sweep on the current stream (d_dir_of / ndirs:
-// OrderFrame::dir_of, NULL for none) and the host form's staging arrays.
+// What order_along.cpp and order_fans.cpp share with it: the checks of the arguments alone, the sweep on the current stream (d_dir_of /
+// ndirs: OrderFrame::dir_of, NULL for none), the host forms' staging arrays, the kernel of a call and its launch.
 int order_args(const void *rays, int nrays, const void *after, int max_hits, const void *hits, const void *counts);
-int order_launch(const void *d_rays, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts, const void *d_dir_of, int ndirs);
+int order_launch(const void *d_rays, int nrays, const OrderOut &out, const void *d_dir_of, int ndirs);
 int order_staging(int checked, int nrays, int max_hits);
+// The kernel of list length K = 1, 2, 4 or 8 out of the four instantiations; max_hits of 3, 5, 6 or 7 run the next length up ...
+template <class Kernel>
+Kernel order_pick(int max_hits, Kernel k1, Kernel k2, Kernel k4, Kernel k8)
+{
+    const int K = hit_list_size_for(max_hits);
+    return K == 1 ? k1 : (K == 2 ? k2 : (K == 4 ? k4 : k8));
+}
+// ... and out of the eight of a walk kernel template <int K, bool STATS>.
+#define MIRT_ORDER_WALK_KERNEL(kernel, max_hits, stats)                                                                                \
+    ((stats) ? mirt::order_pick(max_hits, kernel<1, true>, kernel<2, true>, kernel<4, true>, kernel<8, true>)                           \
+             : mirt::order_pick(max_hits, kernel<1, false>, kernel<2, false>, kernel<4, false>, kernel<8, false>))
+// A walk kernel, a lane per ray, on the call's stream.
+template <class Kernel, class Frame>
+int order_walk_launch(Kernel kernel, int nrays, const Frame &f)
+{
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, g.stream, f);
+    HIP_TRY(hipGetLastError());
+    return MIRT_OK;
+}
+// One host form around its device form `call(out)`, given the verdict of its checks and its own input rows `in`: room in the ordered
+// calls' staging arrays, then with_host_arrays on `in` and the three rows every such call has -- `after` in (it goes to its own
+// staging array before anything comes back: the in-place peel needs nothing more on this side), the records and the counts out.
+template <int N, class Call>
+int order_with_host_arrays(int checked, int nrays, const mirt_hit *after, int max_hits, mirt_hit *hits, int32_t *counts, const HostArray (&in)[N], Call call)
+{
+    int rc;
+    if ((rc = order_staging(checked, nrays, max_hits))) return rc;
+    const size_t records = checked ? 0 : (size_t)nrays * (size_t)max_hits;
+    HostArray a[N + 3];
+    std::copy(in, in + N, a);
+    a[N] = { (void *)after, &QueryRows::d_order_after, (size_t)nrays * sizeof(mirt_hit), after != nullptr, false };
+    a[N + 1] = { hits, &QueryRows::d_order_hits, records * sizeof(mirt_hit), false, true };
+    a[N + 2] = { counts, &QueryRows::d_order_counts, (size_t)nrays * sizeof(int32_t), false, true };
+    const QueryRows &Q = g.qrows;
+    return with_host_arrays(checked, nrays, a, [&] { return call(order_out(after ? Q.d_order_after : nullptr, max_hits, Q.d_order_hits, Q.d_order_counts)); });
+}
 // ... along one direction and along several (order_along.cpp; the kernels: ../order/ordered_along.hip)
-int order_along(const float *dir, const void *d_origins3, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts);
+int order_along(const float *dir, const void *d_origins3, int nrays, const OrderOut &out);
 int order_along_host(const float *dir, const float *origins3, int nrays, const mirt_hit *after, int max_hits, mirt_hit *hits, int32_t *counts);
-int order_alongs(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, const void *d_after, int max_hits,
-                 void *d_hits, void *d_counts);
+int order_alongs(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, const OrderOut &out);
 int order_alongs_host(const float *dirs3, int ndirs, const int32_t *dir_of, const float *origins3, int nrays, const mirt_hit *after, int max_hits,
                       mirt_hit *hits, int32_t *counts);
 
@@ -850,10 +891,9 @@ int alongs_run(const float *dirs3, int ndirs, const void *d_dir_of, const void *
                const std::function<int(const AlongsFrame &)> &launch, const std::function<int()> &brute);
 
 // ... from one origin and from several (order_fans.cpp; the kernels: ../order/ordered_fans.hip)
-int order_from(const float *origin, const void *d_dirs3, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts);
+int order_from(const float *origin, const void *d_dirs3, int nrays, const OrderOut &out);
 int order_from_host(const float *origin, const float *dirs3, int nrays, const mirt_hit *after, int max_hits, mirt_hit *hits, int32_t *counts);
-int order_fans(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, const void *d_after, int max_hits,
-               void *d_hits, void *d_counts);
+int order_fans(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, const OrderOut &out);
 int order_fans_host(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, const mirt_hit *after, int max_hits,
                     mirt_hit *hits, int32_t *counts);
 // What order_fans.cpp shares with the fan calls (query.cpp): the checks of the arguments alone (what check_from_args, check_fans_args

@@ -35,58 +35,43 @@ static int check_order_args(const void *rays, int nrays, const void *after, int 
     return order_args(rays, nrays, after, max_hits, hits, counts);
 }
 
-// The kernel of list length K = 1, 2, 4 or 8 out of a table of the four instantiations.
-template <class Kernel>
-static Kernel order_pick(int K, Kernel k1, Kernel k2, Kernel k4, Kernel k8) { return K == 1 ? k1 : (K == 2 ? k2 : (K == 4 ? k4 : k8)); }
-
 // The sweep of a call on the stream it has taken, as intersect_launch is mirt_intersect's: the scene's rows, then a wave per ray up
 // to query_wave_rays(), a lane per ray beyond.  d_dir_of (nullable) / ndirs: OrderFrame::dir_of.
-int order_launch(const void *d_rays, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts, const void *d_dir_of, int ndirs)
+int order_launch(const void *d_rays, int nrays, const OrderOut &out, const void *d_dir_of, int ndirs)
 {
     int rc;
     if ((rc = query_rows())) return rc;
     OrderFrame o;
     memset(&o, 0, sizeof o);
-    o.f.q = rows_frame(d_rays, nrays, d_hits);
-    o.after = static_cast<const uint32_t *>(d_after);
-    o.max_hits = max_hits;
-    o.counts = static_cast<int32_t *>(d_counts);
+    o.f.q = rows_frame(d_rays, nrays, nullptr);
+    o.out = out;
     o.dir_of = static_cast<const int32_t *>(d_dir_of);
     o.ndirs = ndirs;
-    const int K = hit_list_size_for(max_hits);
     if ((long)nrays <= query_wave_rays()) {
-        hipLaunchKernelGGL(order_pick(K, k_order_sweep_wave<1>, k_order_sweep_wave<2>, k_order_sweep_wave<4>, k_order_sweep_wave<8>),
+        hipLaunchKernelGGL(order_pick(out.max_hits, k_order_sweep_wave<1>, k_order_sweep_wave<2>, k_order_sweep_wave<4>, k_order_sweep_wave<8>),
                            dim3((unsigned)((nrays + 3) / 4)), dim3(256), 0, g.stream, o);
     } else {
-        hipLaunchKernelGGL(order_pick(K, k_order_sweep<1>, k_order_sweep<2>, k_order_sweep<4>, k_order_sweep<8>),
+        hipLaunchKernelGGL(order_pick(out.max_hits, k_order_sweep<1>, k_order_sweep<2>, k_order_sweep<4>, k_order_sweep<8>),
                            dim3((unsigned)((nrays + 255) / 256)), dim3(256), sweep_lds_bytes(), g.stream, o);
     }
     HIP_TRY(hipGetLastError());
     return MIRT_OK;
 }
 
-int order_intersect(const void *d_rays, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts)
+int order_intersect(const void *d_rays, int nrays, const OrderOut &out)
 {
     int rc;
-    if ((rc = check_order_args(d_rays, nrays, d_after, max_hits, d_hits, d_counts))) return rc;
+    if ((rc = check_order_args(d_rays, nrays, out.after, out.max_hits, out.hits, out.counts))) return rc;
     if (nrays == 0) return MIRT_OK;
     if ((rc = query_need_scene())) return rc;
     stream_begin();
-    const int K = hit_list_size_for(max_hits);
     OrderFrame o;
     memset(&o, 0, sizeof o);
     bool binned = false;
     if (g.ray_grid && (rc = grid_begin(d_rays, nrays, &o.f, &binned))) return rc;    // (the statistics of mirt_get_ray_grid_stats begin here)
-    if (!binned) return order_launch(d_rays, nrays, d_after, max_hits, d_hits, d_counts, nullptr, 0);
-    o.f.q.hits = static_cast<uint32_t *>(d_hits);
-    o.after = static_cast<const uint32_t *>(d_after);
-    o.max_hits = max_hits;
-    o.counts = static_cast<int32_t *>(d_counts);
-    const auto kernel = o.f.stats ? order_pick(K, k_grid_order<1, true>, k_grid_order<2, true>, k_grid_order<4, true>, k_grid_order<8, true>)
-                                  : order_pick(K, k_grid_order<1, false>, k_grid_order<2, false>, k_grid_order<4, false>, k_grid_order<8, false>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, g.stream, o);
-    HIP_TRY(hipGetLastError());
-    return MIRT_OK;
+    if (!binned) return order_launch(d_rays, nrays, out, nullptr, 0);
+    o.out = out;
+    return order_walk_launch(MIRT_ORDER_WALK_KERNEL(k_grid_order, out.max_hits, o.f.stats), nrays, o);
 }
 
 // The host form's staging arrays are its own and grow by their own measure (up to 160 bytes of records a ray), once the checks have
@@ -112,19 +97,10 @@ int order_staging(int checked, int nrays, int max_hits)
 
 int order_intersect_host(const mirt_ray *rays, int nrays, const mirt_hit *after, int max_hits, mirt_hit *hits, int32_t *counts)
 {
-    int rc;
     const int checked = check_order_args(rays, nrays, after, max_hits, hits, counts);
-    if ((rc = order_staging(checked, nrays, max_hits))) return rc;
-    QueryRows &Q = g.qrows;
-    const size_t records = checked ? 0 : (size_t)nrays * (size_t)max_hits;
-    // (`after` goes to its own staging array before anything comes back: the in-place peel needs nothing more on this side)
-    const HostArray a[] = { { (void *)rays, &QueryRows::d_rays, (size_t)nrays * sizeof(mirt_ray), true, false },
-                            { (void *)after, &QueryRows::d_order_after, (size_t)nrays * sizeof(mirt_hit), after != nullptr, false },
-                            { hits, &QueryRows::d_order_hits, records * sizeof(mirt_hit), false, true },
-                            { counts, &QueryRows::d_order_counts, (size_t)nrays * sizeof(int32_t), false, true } };
-    return with_host_arrays(checked, nrays, a, [&] {
-        return order_intersect(Q.d_rays, nrays, after ? Q.d_order_after : nullptr, max_hits, Q.d_order_hits, Q.d_order_counts);
-    });
+    const HostArray in[] = { { (void *)rays, &QueryRows::d_rays, (size_t)nrays * sizeof(mirt_ray), true, false } };
+    return order_with_host_arrays(checked, nrays, after, max_hits, hits, counts, in,
+                                  [&](const OrderOut &out) { return order_intersect(g.qrows.d_rays, nrays, out); });
 }
 
 }  // namespace mirt
@@ -135,5 +111,5 @@ extern "C" int mirt_intersect_ordered(const mirt_ray *rays, int nrays, const mir
 }
 extern "C" int mirt_intersect_ordered_device(const void *d_rays, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts)
 {
-    return mirt::order_intersect(d_rays, nrays, d_after, max_hits, d_hits, d_counts);
+    return mirt::order_intersect(d_rays, nrays, mirt::order_out(d_after, max_hits, d_hits, d_counts));
 }

@@ -10,9 +10,6 @@
 
 namespace mirt {
 
-template <class Kernel>
-static Kernel pick(int K, Kernel k1, Kernel k2, Kernel k4, Kernel k8) { return K == 1 ? k1 : (K == 2 ? k2 : (K == 4 ? k4 : k8)); }
-
 // The union of the ordered call's checks and the along call's: the arguments first, then the library's state.
 static int check_order_along_args(const float *dir, const void *origins3, int nrays, const void *after, int max_hits, const void *hits, const void *counts)
 {
@@ -21,10 +18,10 @@ static int check_order_along_args(const float *dir, const void *origins3, int nr
     return check_along_args(dir, origins3, nrays, hits);
 }
 
-int order_along(const float *dir, const void *d_origins3, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts)
+int order_along(const float *dir, const void *d_origins3, int nrays, const OrderOut &out)
 {
     int rc;
-    if ((rc = check_order_along_args(dir, d_origins3, nrays, d_after, max_hits, d_hits, d_counts))) return rc;
+    if ((rc = check_order_along_args(dir, d_origins3, nrays, out.after, out.max_hits, out.hits, out.counts))) return rc;
     if (nrays == 0) return MIRT_OK;
     if ((rc = query_need_scene())) return rc;
     AlongOrderFrame f;
@@ -33,18 +30,10 @@ int order_along(const float *dir, const void *d_origins3, int nrays, const void 
     if ((rc = along_begin(dir, d_origins3, nrays, &f.a, &binned))) return rc;
     if (!binned) {
         if ((rc = along_expand(dir, d_origins3, nrays))) return rc;
-        return order_launch(g.cur().query.d_fan_rays, nrays, d_after, max_hits, d_hits, d_counts, nullptr, 0);
+        return order_launch(g.cur().query.d_fan_rays, nrays, out, nullptr, 0);
     }
-    f.a.q.hits = static_cast<uint32_t *>(d_hits);
-    f.after = static_cast<const uint32_t *>(d_after);
-    f.max_hits = max_hits;
-    f.counts = static_cast<int32_t *>(d_counts);
-    const int K = hit_list_size_for(max_hits);
-    const auto kernel = f.a.stats ? pick(K, k_along_order<1, true>, k_along_order<2, true>, k_along_order<4, true>, k_along_order<8, true>)
-                                  : pick(K, k_along_order<1, false>, k_along_order<2, false>, k_along_order<4, false>, k_along_order<8, false>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, g.stream, f);
-    HIP_TRY(hipGetLastError());
-    return MIRT_OK;
+    f.out = out;
+    return order_walk_launch(MIRT_ORDER_WALK_KERNEL(k_along_order, out.max_hits, f.a.stats), nrays, f);
 }
 
 // Several directions.  A call of more directions than a group holds runs in passes, and one that meets a group that gave up in a
@@ -52,11 +41,13 @@ int order_along(const float *dir, const void *d_origins3, int nrays, const void 
 // again -- unless the call peels in place (after == hits, max_hits == 1), where an earlier pass has replaced the records the sweep
 // would continue behind.  Such a call of more than one direction therefore sets its `after` records aside first (20 bytes a ray,
 // in the stream's scratch) and continues behind the copy.
-static int order_alongs_run(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, const void *d_after, int max_hits,
-                            void *d_hits, void *d_counts)
+static int order_alongs_run(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, const OrderOut &out)
 {
     int rc;
-    if (d_after && d_after == d_hits && ndirs > 1) {
+    AlongsOrderFrame f;
+    memset(&f, 0, sizeof f);
+    f.out = out;
+    if (out.after && out.after == out.hits && ndirs > 1) {
         // (alongs_run takes the call's stream below; the copy runs on the one it will take, in front of the call's kernels)
         QueryScratch &S = g.streams[next_si()].query;
         hipStream_t st = g.streams[next_si()].stream;
@@ -66,75 +57,47 @@ static int order_alongs_run(const float *dirs3, int ndirs, const void *d_dir_of,
             if ((rc = dev_realloc(&S.d_order_after, (size_t)nrays * HIT_WORDS))) return rc;
             S.order_after_cap = (size_t)nrays;
         }
-        HIP_TRY(hipMemcpyAsync(S.d_order_after, d_after, (size_t)nrays * sizeof(mirt_hit), hipMemcpyDeviceToDevice, st));
-        d_after = S.d_order_after;
+        HIP_TRY(hipMemcpyAsync(S.d_order_after, out.after, (size_t)nrays * sizeof(mirt_hit), hipMemcpyDeviceToDevice, st));
+        f.out.after = S.d_order_after;
     }
-    AlongsOrderFrame f;
-    memset(&f, 0, sizeof f);
-    f.a.q.hits = static_cast<uint32_t *>(d_hits);
-    f.after = static_cast<const uint32_t *>(d_after);
-    f.max_hits = max_hits;
-    f.counts = static_cast<int32_t *>(d_counts);
-    const int K = hit_list_size_for(max_hits);
     return alongs_run(dirs3, ndirs, d_dir_of, d_origins3, nrays, f.a,
                       [&](const AlongsFrame &x) {
                           f.a = x;
-                          const auto kernel = x.stats ? pick(K, k_alongs_order<1, true>, k_alongs_order<2, true>, k_alongs_order<4, true>, k_alongs_order<8, true>)
-                                                      : pick(K, k_alongs_order<1, false>, k_alongs_order<2, false>, k_alongs_order<4, false>, k_alongs_order<8, false>);
-                          hipLaunchKernelGGL(kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, g.stream, f);
-                          HIP_TRY(hipGetLastError());
-                          return (int)MIRT_OK;
+                          return order_walk_launch(MIRT_ORDER_WALK_KERNEL(k_alongs_order, out.max_hits, x.stats), nrays, f);
                       },
-                      [&] { return order_launch(g.cur().query.d_fan_rays, nrays, d_after, max_hits, d_hits, d_counts, d_dir_of, ndirs); });
+                      [&] { return order_launch(g.cur().query.d_fan_rays, nrays, f.out, d_dir_of, ndirs); });
 }
 
-int order_alongs(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, const void *d_after, int max_hits,
-                 void *d_hits, void *d_counts)
+int order_alongs(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, const OrderOut &out)
 {
     int rc;
-    if ((rc = order_args(d_origins3, nrays, d_after, max_hits, d_hits, d_counts))) return rc;
-    if ((rc = check_alongs_args(dirs3, ndirs, d_dir_of, d_origins3, nrays, d_hits))) return rc;
+    if ((rc = order_args(d_origins3, nrays, out.after, out.max_hits, out.hits, out.counts))) return rc;
+    if ((rc = check_alongs_args(dirs3, ndirs, d_dir_of, d_origins3, nrays, out.hits))) return rc;
     if (nrays == 0) return MIRT_OK;
     if ((rc = query_need_scene())) return rc;
-    return order_alongs_run(dirs3, ndirs, d_dir_of, d_origins3, nrays, d_after, max_hits, d_hits, d_counts);
+    return order_alongs_run(dirs3, ndirs, d_dir_of, d_origins3, nrays, out);
 }
 
 // ---- host buffers: the origins travel through the directions' staging array, the indices through the many-origin fans', `after`,
-// the records and the counts through the ordered call's own (order.cpp: order_staging) ----
+// the records and the counts through the ordered call's own (order_with_host_arrays) ----
 
 int order_along_host(const float *dir, const float *origins3, int nrays, const mirt_hit *after, int max_hits, mirt_hit *hits, int32_t *counts)
 {
-    int rc;
     const int checked = check_order_along_args(dir, origins3, nrays, after, max_hits, hits, counts);
-    if ((rc = order_staging(checked, nrays, max_hits))) return rc;
-    QueryRows &Q = g.qrows;
-    const size_t records = checked ? 0 : (size_t)nrays * (size_t)max_hits;
-    const HostArray a[] = { { (void *)origins3, &QueryRows::d_dirs, (size_t)nrays * 3 * sizeof(float), true, false },
-                            { (void *)after, &QueryRows::d_order_after, (size_t)nrays * sizeof(mirt_hit), after != nullptr, false },
-                            { hits, &QueryRows::d_order_hits, records * sizeof(mirt_hit), false, true },
-                            { counts, &QueryRows::d_order_counts, (size_t)nrays * sizeof(int32_t), false, true } };
-    return with_host_arrays(checked, nrays, a, [&] {
-        return order_along(dir, Q.d_dirs, nrays, after ? Q.d_order_after : nullptr, max_hits, Q.d_order_hits, Q.d_order_counts);
-    });
+    const HostArray in[] = { { (void *)origins3, &QueryRows::d_dirs, (size_t)nrays * 3 * sizeof(float), true, false } };
+    return order_with_host_arrays(checked, nrays, after, max_hits, hits, counts, in,
+                                  [&](const OrderOut &out) { return order_along(dir, g.qrows.d_dirs, nrays, out); });
 }
 
 int order_alongs_host(const float *dirs3, int ndirs, const int32_t *dir_of, const float *origins3, int nrays, const mirt_hit *after, int max_hits,
                       mirt_hit *hits, int32_t *counts)
 {
-    int rc;
     int checked = order_args(origins3, nrays, after, max_hits, hits, counts);
     if (!checked) checked = check_alongs_host_args(dirs3, ndirs, dir_of, origins3, nrays, hits);
-    if ((rc = order_staging(checked, nrays, max_hits))) return rc;
-    QueryRows &Q = g.qrows;
-    const size_t records = checked ? 0 : (size_t)nrays * (size_t)max_hits;
-    const HostArray a[] = { { (void *)origins3, &QueryRows::d_dirs, (size_t)nrays * 3 * sizeof(float), true, false },
-                            { (void *)dir_of, &QueryRows::d_origin_of, (size_t)nrays * sizeof(int32_t), dir_of != nullptr, false },
-                            { (void *)after, &QueryRows::d_order_after, (size_t)nrays * sizeof(mirt_hit), after != nullptr, false },
-                            { hits, &QueryRows::d_order_hits, records * sizeof(mirt_hit), false, true },
-                            { counts, &QueryRows::d_order_counts, (size_t)nrays * sizeof(int32_t), false, true } };
-    return with_host_arrays(checked, nrays, a, [&] {
-        return order_alongs(dirs3, ndirs, dir_of ? Q.d_origin_of : nullptr, Q.d_dirs, nrays, after ? Q.d_order_after : nullptr, max_hits, Q.d_order_hits,
-                            Q.d_order_counts);
+    const HostArray in[] = { { (void *)origins3, &QueryRows::d_dirs, (size_t)nrays * 3 * sizeof(float), true, false },
+                             { (void *)dir_of, &QueryRows::d_origin_of, (size_t)nrays * sizeof(int32_t), dir_of != nullptr, false } };
+    return order_with_host_arrays(checked, nrays, after, max_hits, hits, counts, in, [&](const OrderOut &out) {
+        return order_alongs(dirs3, ndirs, dir_of ? g.qrows.d_origin_of : nullptr, g.qrows.d_dirs, nrays, out);
     });
 }
 
@@ -146,7 +109,7 @@ extern "C" int mirt_intersect_ordered_along(const float dir[3], const float *ori
 }
 extern "C" int mirt_intersect_ordered_along_device(const float dir[3], const void *d_origins3, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts)
 {
-    return mirt::order_along(dir, d_origins3, nrays, d_after, max_hits, d_hits, d_counts);
+    return mirt::order_along(dir, d_origins3, nrays, mirt::order_out(d_after, max_hits, d_hits, d_counts));
 }
 extern "C" int mirt_intersect_ordered_alongs(const float *dirs3, int ndirs, const int32_t *dir_of, const float *origins3, int nrays, const mirt_hit *after, int max_hits,
                                              mirt_hit *hits, int32_t *counts)
@@ -156,5 +119,5 @@ extern "C" int mirt_intersect_ordered_alongs(const float *dirs3, int ndirs, cons
 extern "C" int mirt_intersect_ordered_alongs_device(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, const void *d_after, int max_hits,
                                                     void *d_hits, void *d_counts)
 {
-    return mirt::order_alongs(dirs3, ndirs, d_dir_of, d_origins3, nrays, d_after, max_hits, d_hits, d_counts);
+    return mirt::order_alongs(dirs3, ndirs, d_dir_of, d_origins3, nrays, mirt::order_out(d_after, max_hits, d_hits, d_counts));
 }

@@ -17,9 +17,6 @@
 
 namespace mirt {
 
-template <class Kernel>
-static Kernel pick(int K, Kernel k1, Kernel k2, Kernel k4, Kernel k8) { return K == 1 ? k1 : (K == 2 ? k2 : (K == 4 ? k4 : k8)); }
-
 // The union of the ordered call's checks and the fan call's: the arguments first, then the library's state.
 static int check_order_from_args(const float *origin, const void *dirs3, int nrays, const void *after, int max_hits, const void *hits, const void *counts)
 {
@@ -38,36 +35,28 @@ static int check_order_fans_args(const float *origins3, int norigins, const void
     return need_init();
 }
 
-int order_from(const float *origin, const void *d_dirs3, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts)
+int order_from(const float *origin, const void *d_dirs3, int nrays, const OrderOut &out)
 {
     int rc;
-    if ((rc = check_order_from_args(origin, d_dirs3, nrays, d_after, max_hits, d_hits, d_counts))) return rc;
+    if ((rc = check_order_from_args(origin, d_dirs3, nrays, out.after, out.max_hits, out.hits, out.counts))) return rc;
     if (nrays == 0) return MIRT_OK;
     if ((rc = query_need_scene())) return rc;
     FanOrderFrame f;
     memset(&f, 0, sizeof f);
     bool binned = false;
-    if ((rc = fan_begin(origin, d_dirs3, nrays, d_hits, &f.f, &binned))) return rc;
+    if ((rc = fan_begin(origin, d_dirs3, nrays, nullptr, &f.f, &binned))) return rc;
     if (!binned) {
         if ((rc = fans_expand(origin, 1, nullptr, d_dirs3, nrays))) return rc;
-        return order_launch(g.cur().query.d_fan_rays, nrays, d_after, max_hits, d_hits, d_counts, nullptr, 0);
+        return order_launch(g.cur().query.d_fan_rays, nrays, out, nullptr, 0);
     }
-    f.after = static_cast<const uint32_t *>(d_after);
-    f.max_hits = max_hits;
-    f.counts = static_cast<int32_t *>(d_counts);
-    const int K = hit_list_size_for(max_hits);
-    const auto kernel = f.f.stats ? pick(K, k_fan_order<1, true>, k_fan_order<2, true>, k_fan_order<4, true>, k_fan_order<8, true>)
-                                  : pick(K, k_fan_order<1, false>, k_fan_order<2, false>, k_fan_order<4, false>, k_fan_order<8, false>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, g.stream, f);
-    HIP_TRY(hipGetLastError());
-    return MIRT_OK;
+    f.out = out;
+    return order_walk_launch(MIRT_ORDER_WALK_KERNEL(k_fan_order, out.max_hits, f.f.stats), nrays, f);
 }
 
 // Several origins: mirt_intersect_fans*' decision, plan, cubes and passes, each pass one launch of k_fans_order over all rays.  The
 // sweep of a call that does not bin carries the indices along (OrderFrame::dir_of / ndirs), so that a ray whose index names no origin
 // keeps its slots and gets the count 0, as in the binned kernel.
-static int order_fans_run(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, const void *d_after, int max_hits,
-                          void *d_hits, void *d_counts)
+static int order_fans_run(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, const OrderOut &out)
 {
     int rc;
     std::vector<FanPass> plan;
@@ -78,74 +67,49 @@ static int order_fans_run(const float *origins3, int norigins, const void *d_ori
     QueryStats &stats = stats_begin(QUERY_FAN, binned);
     if (!binned) {
         if ((rc = fans_expand(origins3, norigins, d_origin_of, d_dirs3, nrays))) return rc;
-        return order_launch(g.cur().query.d_fan_rays, nrays, d_after, max_hits, d_hits, d_counts, d_origin_of, d_origin_of ? norigins : 0);
+        return order_launch(g.cur().query.d_fan_rays, nrays, out, d_origin_of, d_origin_of ? norigins : 0);
     }
 
     FansOrderFrame f;
     memset(&f, 0, sizeof f);
-    f.f.f = fan_frame(d_dirs3, nrays, d_hits);
+    f.f.f = fan_frame(d_dirs3, nrays, nullptr);
     f.f.origin_of = static_cast<const int32_t *>(d_origin_of);
     f.norigins = norigins;
-    f.after = static_cast<const uint32_t *>(d_after);
-    f.max_hits = max_hits;
-    f.counts = static_cast<int32_t *>(d_counts);
+    f.out = out;
     if ((rc = stats_arm(QUERY_FAN, &f.f.f.stats))) return rc;        // (once: the passes' kernels add up in the same words)
-    const int K = hit_list_size_for(max_hits);
-    const auto kernel = f.f.f.stats ? pick(K, k_fans_order<1, true>, k_fans_order<2, true>, k_fans_order<4, true>, k_fans_order<8, true>)
-                                    : pick(K, k_fans_order<1, false>, k_fans_order<2, false>, k_fans_order<4, false>, k_fans_order<8, false>);
+    const auto kernel = MIRT_ORDER_WALK_KERNEL(k_fans_order, out.max_hits, f.f.f.stats);
     // (plan[0].first == 0: the pass that writes the strays' count)
-    return fans_passes_run(origins3, plan, foreign, stats, f.f, [&] {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, g.stream, f);
-        HIP_TRY(hipGetLastError());
-        return (int)MIRT_OK;
-    });
+    return fans_passes_run(origins3, plan, foreign, stats, f.f, [&] { return order_walk_launch(kernel, nrays, f); });
 }
 
-int order_fans(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, const void *d_after, int max_hits,
-               void *d_hits, void *d_counts)
+int order_fans(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, const OrderOut &out)
 {
     int rc;
-    if ((rc = check_order_fans_args(origins3, norigins, d_origin_of, d_dirs3, nrays, d_after, max_hits, d_hits, d_counts, false))) return rc;
+    if ((rc = check_order_fans_args(origins3, norigins, d_origin_of, d_dirs3, nrays, out.after, out.max_hits, out.hits, out.counts, false))) return rc;
     if (nrays == 0) return MIRT_OK;
     if ((rc = query_need_scene())) return rc;
-    return order_fans_run(origins3, norigins, d_origin_of, d_dirs3, nrays, d_after, max_hits, d_hits, d_counts);
+    return order_fans_run(origins3, norigins, d_origin_of, d_dirs3, nrays, out);
 }
 
 // ---- host buffers: the directions and the indices travel through the fan calls' staging arrays, `after`, the records and the counts
-// through the ordered call's own (order.cpp: order_staging) ----
+// through the ordered call's own (order_with_host_arrays) ----
 
 int order_from_host(const float *origin, const float *dirs3, int nrays, const mirt_hit *after, int max_hits, mirt_hit *hits, int32_t *counts)
 {
-    int rc;
     const int checked = check_order_from_args(origin, dirs3, nrays, after, max_hits, hits, counts);
-    if ((rc = order_staging(checked, nrays, max_hits))) return rc;
-    QueryRows &Q = g.qrows;
-    const size_t records = checked ? 0 : (size_t)nrays * (size_t)max_hits;
-    const HostArray a[] = { { (void *)dirs3, &QueryRows::d_dirs, (size_t)nrays * 3 * sizeof(float), true, false },
-                            { (void *)after, &QueryRows::d_order_after, (size_t)nrays * sizeof(mirt_hit), after != nullptr, false },
-                            { hits, &QueryRows::d_order_hits, records * sizeof(mirt_hit), false, true },
-                            { counts, &QueryRows::d_order_counts, (size_t)nrays * sizeof(int32_t), false, true } };
-    return with_host_arrays(checked, nrays, a, [&] {
-        return order_from(origin, Q.d_dirs, nrays, after ? Q.d_order_after : nullptr, max_hits, Q.d_order_hits, Q.d_order_counts);
-    });
+    const HostArray in[] = { { (void *)dirs3, &QueryRows::d_dirs, (size_t)nrays * 3 * sizeof(float), true, false } };
+    return order_with_host_arrays(checked, nrays, after, max_hits, hits, counts, in,
+                                  [&](const OrderOut &out) { return order_from(origin, g.qrows.d_dirs, nrays, out); });
 }
 
 int order_fans_host(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, const mirt_hit *after, int max_hits,
                     mirt_hit *hits, int32_t *counts)
 {
-    int rc;
     const int checked = check_order_fans_args(origins3, norigins, origin_of, dirs3, nrays, after, max_hits, hits, counts, true);
-    if ((rc = order_staging(checked, nrays, max_hits))) return rc;
-    QueryRows &Q = g.qrows;
-    const size_t records = checked ? 0 : (size_t)nrays * (size_t)max_hits;
-    const HostArray a[] = { { (void *)dirs3, &QueryRows::d_dirs, (size_t)nrays * 3 * sizeof(float), true, false },
-                            { (void *)origin_of, &QueryRows::d_origin_of, (size_t)nrays * sizeof(int32_t), origin_of != nullptr, false },
-                            { (void *)after, &QueryRows::d_order_after, (size_t)nrays * sizeof(mirt_hit), after != nullptr, false },
-                            { hits, &QueryRows::d_order_hits, records * sizeof(mirt_hit), false, true },
-                            { counts, &QueryRows::d_order_counts, (size_t)nrays * sizeof(int32_t), false, true } };
-    return with_host_arrays(checked, nrays, a, [&] {
-        return order_fans(origins3, norigins, origin_of ? Q.d_origin_of : nullptr, Q.d_dirs, nrays, after ? Q.d_order_after : nullptr, max_hits,
-                          Q.d_order_hits, Q.d_order_counts);
+    const HostArray in[] = { { (void *)dirs3, &QueryRows::d_dirs, (size_t)nrays * 3 * sizeof(float), true, false },
+                             { (void *)origin_of, &QueryRows::d_origin_of, (size_t)nrays * sizeof(int32_t), origin_of != nullptr, false } };
+    return order_with_host_arrays(checked, nrays, after, max_hits, hits, counts, in, [&](const OrderOut &out) {
+        return order_fans(origins3, norigins, origin_of ? g.qrows.d_origin_of : nullptr, g.qrows.d_dirs, nrays, out);
     });
 }
 
@@ -157,7 +121,7 @@ extern "C" int mirt_intersect_ordered_from(const float origin[3], const float *d
 }
 extern "C" int mirt_intersect_ordered_from_device(const float origin[3], const void *d_dirs3, int nrays, const void *d_after, int max_hits, void *d_hits, void *d_counts)
 {
-    return mirt::order_from(origin, d_dirs3, nrays, d_after, max_hits, d_hits, d_counts);
+    return mirt::order_from(origin, d_dirs3, nrays, mirt::order_out(d_after, max_hits, d_hits, d_counts));
 }
 extern "C" int mirt_intersect_ordered_fans(const float *origins3, int norigins, const int32_t *origin_of, const float *dirs3, int nrays, const mirt_hit *after,
                                            int max_hits, mirt_hit *hits, int32_t *counts)
@@ -167,5 +131,5 @@ extern "C" int mirt_intersect_ordered_fans(const float *origins3, int norigins, 
 extern "C" int mirt_intersect_ordered_fans_device(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays, const void *d_after,
                                                   int max_hits, void *d_hits, void *d_counts)
 {
-    return mirt::order_fans(origins3, norigins, d_origin_of, d_dirs3, nrays, d_after, max_hits, d_hits, d_counts);
+    return mirt::order_fans(origins3, norigins, d_origin_of, d_dirs3, nrays, mirt::order_out(d_after, max_hits, d_hits, d_counts));
 }

@@ -7,15 +7,15 @@
 // then the every-ray list; every test is k_query_closest's own (ray_dots, maybe_hit, exact_hit_row on the caller's start and
 // negD = -dir).  What differs is what an accepted distance does: it is offered to the K-entry list (hit_list_consider), and the
 // bound that moves the cell list's end and skips a row by its depth bound is the list's K-th distance -- FLT_MAX until K entries are
-// held (along_order.hpp has the three lines and the argument).  The end and the skip are strict, so the ties at the bound are still
+// held (order_bound.hpp has the lines and the argument).  The end and the skip are strict, so the ties at the bound are still
 // tested and the index decides them.  The every-ray list has no depth order and is walked whole; a row that is both in the cell and
 // on that list offers an equal key, which the list drops.  No shell is skipped for lying in front of `after`: a ray that continues
-// walks its first shells again.  A lane the structure does not cover sweeps all n rows behind the wave's walk (k_order_sweep's loop
-// body); a lane whose `after` distance is NaN takes no list and still writes its slots and its count.
+// walks its first shells again.  A lane the structure does not cover sweeps all n rows behind the wave's walk (order_device.hpp:
+// order_sweep_tail); a lane whose `after` distance is NaN takes no list and still writes its slots and its count.
 // Positions do not travel with the keys: the winners are tested once more at the end (order_device.hpp).
 // Built with -ffp-contract=off like every kernel of the library.
 #include "ordered_along.hpp"
-#include "along_order.hpp"
+#include "order_bound.hpp"
 #include "order_device.hpp"
 #include "../along/along_lanes.hpp"
 
@@ -24,7 +24,7 @@ namespace mirt {
 // The cell list's end under the threshold `thr`: the shells up to the one thr falls into (along_walk.hpp: along_list_end).
 __device__ __forceinline__ uint32_t along_order_end(const AlongTables &t, const AlongLane &l, float thr)
 {
-    return t.off[l.key + along_order_shells(bin_shell_of(thr, l.shell_d0, l.shell_iw, l.shells))];
+    return t.off[l.key + order_shells(bin_shell_of(thr, l.shell_d0, l.shell_iw, l.shells))];
 }
 
 // `mine`: the lane has a ray of this launch (a ray inside the call, and of this pass's directions): any other lane takes no list,
@@ -33,15 +33,8 @@ __device__ __forceinline__ uint32_t along_order_end(const AlongTables &t, const 
 // ray is read before any of its slots is written, by the lane that writes them.
 template <int K, bool STATS>
 __device__ __forceinline__ void along_order_walk(const QueryFrame &q, const AlongTables &t, const AlongLane &l, long long ray, bool mine, bool zero,
-                                                 const uint32_t *after, int max_hits, int32_t *counts, unsigned long long *stats)
+                                                 const OrderOut &o, unsigned long long *stats)
 {
-    OrderFrame o;
-    o.f.q = q;
-    o.after = after;
-    o.max_hits = max_hits;
-    o.counts = counts;
-    o.dir_of = nullptr;
-    o.ndirs = 0;
     float a;
     int k;
     order_after(o, ray, mine, &a, &k);
@@ -49,7 +42,7 @@ __device__ __forceinline__ void along_order_walk(const QueryFrame &q, const Alon
     const bool binned = open && l.in_reach, swept = open && !l.in_reach;
     HitList<K> hl;
     hit_list_clear(hl);
-    float thr = along_order_threshold(l.rs, along_order_bound(hit_list_bound(hl)));
+    float thr = along_order_threshold(l.rs, order_bound(hit_list_bound(hl)));
     uint32_t e = 0u, end = 0u, e2 = 0u, end2 = 0u;
     if (binned) { e2 = t.off[l.every]; end2 = t.off[l.every + 1u]; }
     if (binned && l.has_cell) { e = t.off[l.key]; end = along_order_end(t, l, thr); }
@@ -65,14 +58,14 @@ __device__ __forceinline__ void along_order_walk(const QueryFrame &q, const Alon
         const RowVecs r = unpack_row(c0, c1, c2);
         float e1e2b;
         const TestDots td = ray_dots(r, l.S, l.nd, &e1e2b);
-        const int near_ok = act & (int)along_order_near_ok(ax.near, thr);
+        const int near_ok = act & (int)order_near_ok(ax.near, thr);
         if (STATS) { n_cand += (unsigned)act; n_tests += (unsigned)near_ok; }
         if (near_ok & (int)maybe_hit(td)) {
             v3 hp;
             float dist;
             if (exact_hit_row(td, e1e2b, r, l.S, &hp, &dist)) {
                 hit_list_consider(hl, dist, (int)ax.tri, a, k);
-                thr = along_order_threshold(l.rs, along_order_bound(hit_list_bound(hl)));
+                thr = along_order_threshold(l.rs, order_bound(hit_list_bound(hl)));
                 if (stage == 0) end = min(end, along_order_end(t, l, thr));
             }
         }
@@ -85,22 +78,12 @@ __device__ __forceinline__ void along_order_walk(const QueryFrame &q, const Alon
         along_row(t, e < end ? e : 0u, c0, c1, c2, ax);
     }
     if (__any(swept)) {
-        // (rare) the lanes the structure does not cover: every row of the scene, k_order_sweep's loop body
+        // (rare) the lanes the structure does not cover: every row of the scene
         if (STATS && swept) { n_cand += (unsigned)q.n; n_tests += (unsigned)q.n; }
-        for (int j = 0; j < q.n; j++) {
-            const float4 *src = reinterpret_cast<const float4 *>(q.rows + j);
-            const RowVecs r = unpack_row(src[0], src[1], src[2]);
-            float e1e2b;
-            const TestDots td = ray_dots(r, l.S, l.nd, &e1e2b);
-            if (swept && (maybe_hit(td) || l.exact_only)) {
-                v3 hp;
-                float dist;
-                if (exact_hit_row(td, e1e2b, r, l.S, &hp, &dist)) hit_list_consider(hl, dist, j, a, k);
-            }
-        }
+        order_sweep_tail(hl, q.rows, q.n, l.S, l.nd, swept, l.exact_only, a, k);
     }
-    if (mine) order_store_list(o, ray, hl, l.S, l.nd);
-    else if (zero) counts[ray] = 0;
+    if (mine) order_store_list(o, ray, hl, SceneRetest{ q.rows, l.S, l.nd });
+    else if (zero) o.counts[ray] = 0;
     if (STATS) flush_query_stats(stats, mine ? 1u : 0u, n_cand, n_tests, swept ? 1u : 0u);
 }
 
@@ -111,7 +94,7 @@ __global__ __launch_bounds__(256) void k_along_order(const AlongOrderFrame f)
     const long long ray = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool ok = ray < f.a.q.nrays;
     const AlongTables t = { f.a.v.off, f.a.v.rows, f.a.v.aux };
-    along_order_walk<K, STATS>(f.a.q, t, along_lane(f.a, ray, ok), ray, ok, false, f.after, f.max_hits, f.counts, f.a.stats);
+    along_order_walk<K, STATS>(f.a.q, t, along_lane(f.a, ray, ok), ray, ok, false, f.out, f.a.stats);
 }
 
 // ---- k_alongs_order: a group of directions, each lane's descriptor out of LDS by its ray's index (k_alongs_closest's shape) --------
@@ -123,7 +106,7 @@ __global__ __launch_bounds__(256) void k_alongs_order(const AlongsOrderFrame f)
     const long long ray = (long long)blockIdx.x * 256 + threadIdx.x;
     const AlongsLane a = alongs_lane(f.a, s_desc, s_dir, ray, ray < f.a.q.nrays);
     const AlongTables t = { f.a.off, f.a.rows, f.a.aux };
-    along_order_walk<K, STATS>(f.a.q, t, a.l, ray, a.mine, a.zero, f.after, f.max_hits, f.counts, f.a.stats);
+    along_order_walk<K, STATS>(f.a.q, t, a.l, ray, a.mine, a.zero, f.out, f.a.stats);
 }
 
 #define MIRT_ORDER_ALONG_INSTANCES(K)                                                   \

@@ -8,7 +8,7 @@
 // verdicts as integers combined with `&`, only the exact stage in a divergent branch, the next row fetched by walk_row / walk_step.
 // Every test is the fan's own (test_dots on the origin's row, maybe_hit, exact_hit on tris15 and the origin S, negD = -dir).  What
 // differs is what an accepted distance does: it is offered to the K-entry list (hit_list_consider), and the bound that moves the
-// list's end and skips a row by its `near` is the list's K-th distance -- FLT_MAX until K entries are held (fan_order.hpp has the
+// list's end and skips a row by its `near` is the list's K-th distance -- FLT_MAX until K entries are held (order_bound.hpp has the
 // lines and the argument).  The end and the skip are strict, so the ties at the bound are still tested and the index decides them.
 // No shell is skipped for lying in front of `after`: a row has no upper depth bound, and a ray that continues walks its first
 // shells again.  A lane whose direction fan_dir_of does not form sweeps its origin's full table behind the wave's walk (k_query_fan's
@@ -18,29 +18,10 @@
 // table's row of the winner and tris15: the same operations on the same operands, no fused forms), which gives the position's bits.
 // Built with -ffp-contract=off like every kernel of the library.
 #include "ordered_fans.hpp"
-#include "fan_order.hpp"
-#include "../query/rt_query_device.hpp"
+#include "order_bound.hpp"
+#include "order_device.hpp"
 
 namespace mirt {
-
-// Slot `slot` of ray `ray`: the winner `key` as a whole struct Intersection -- its position from the walk's test run once more on the
-// origin table's row --, or Update()'s reset for an empty entry (order_device.hpp: order_store_slot is the same for the scene's rows).
-__device__ __forceinline__ void fan_order_store_slot(const QueryFanFrame &q, int max_hits, long long ray, int slot, unsigned long long key,
-                                                     const OriginRow *tab, v3 S, v3 nd)
-{
-    uint32_t *h = q.hits + (size_t)HIT_WORDS * ((size_t)ray * (size_t)max_hits + (size_t)slot);
-    if (key == HIT_KEY_NONE) {
-        store_record(h, V3(0.0f, 0.0f, 0.0f), 0x7f7fffffu, 0xffffffffu);                   // :335-339: FLT_MAX, -1
-        return;
-    }
-    const int tri = hit_key_index(key);
-    const float4 r0 = tab[tri].r0, r1 = tab[tri].r1, r2 = tab[tri].r2;
-    const TestDots td = test_dots(r0, r1, r2, nd);
-    v3 hp = V3(0.0f, 0.0f, 0.0f);
-    float dist;
-    (void)exact_hit(td, r0.w, q.tris15 + (size_t)15 * tri, S, &hp, &dist);
-    store_record(h, hp, hit_key_distance_bits(key), (uint32_t)tri);
-}
 
 // `mine`: the lane has a ray of this launch (a ray inside the call, and of this pass's origins): any other lane takes no list, sweeps
 // nothing and writes no slot -- it reads position 0's values (fans_lane); `zero`: the lane's count is written 0 though the ray is
@@ -50,20 +31,15 @@ __device__ __forceinline__ void fan_order_store_slot(const QueryFanFrame &q, int
 // k: the position of the ray's origin in the cube, S the origin, bin_base the first bin of position k, tab its origin table.
 template <int K, bool STATS>
 __device__ __forceinline__ void fan_order_walk(const QueryFanFrame &q, long long ray, bool ok, bool mine, bool zero, uint32_t k, v3 S, uint32_t bin_base,
-                                               const OriginRow *tab, const uint32_t *after, int max_hits, int32_t *counts)
+                                               const OriginRow *tab, const OrderOut &o)
 {
     const CubeView &cv = q.cube;
     const float4 *rows4 = reinterpret_cast<const float4 *>(cv.light_rows);
     const v3 dir = ld3(q.dirs + 3 * (size_t)(ok ? ray : 0));
     const v3 nd = neg3(dir);                                       // negD = -dir (:229); dir is used as given
-    // the record (a, ak) the ray continues behind: the caller's, or one that admits everything, or -- not `mine` -- nothing (NaN)
-    float a = mine ? -1.0f : __uint_as_float(0x7fc00000u);
-    int ak = 0;
-    if (mine && after) {
-        const uint32_t *r = after + (size_t)HIT_WORDS * ray;
-        a = __uint_as_float(r[3]);
-        ak = (int)r[4];
-    }
+    float a;
+    int ak;
+    order_after(o, ray, mine, &a, &ak);
     const bool open = mine && a == a;                              // (a NaN record admits nothing: no walk)
     const FanDir fd = fan_dir_of(nd);
     const bool binned = open && fd.formed, swept = open && !fd.formed;
@@ -71,7 +47,7 @@ __device__ __forceinline__ void fan_order_walk(const QueryFanFrame &q, long long
     const float d0 = lf->shell_d0, iw = lf->shell_iw;
     HitList<K> hl;
     hit_list_clear(hl);
-    float bound = fan_order_bound(hit_list_bound(hl));
+    float bound = order_bound(hit_list_bound(hl));
     uint32_t e = 0u, end = 0u, key = 0u;
     if (binned) key = fan_list(cv, k, bin_base, fd.d, bound, &e, &end);
     unsigned long long n_cand = 0, n_tests = 0;
@@ -81,7 +57,7 @@ __device__ __forceinline__ void fan_order_walk(const QueryFanFrame &q, long long
         const int act = (int)(e < end);
         if (!__any(act)) break;
         const TestDots td = test_dots(c0, c1, c2, nd);
-        const int near_ok = act & (int)fan_order_near_ok(c1.w, bound);     // strictly beyond the K-th entry: cannot enter the list
+        const int near_ok = act & (int)order_near_ok(c1.w, bound);         // strictly beyond the K-th entry: cannot enter the list
         if (STATS) { n_cand += (unsigned)act; n_tests += (unsigned)near_ok; }
         if (near_ok & (int)maybe_hit(td)) {
             const int tri = (int)cv.light_tri[e];
@@ -89,10 +65,10 @@ __device__ __forceinline__ void fan_order_walk(const QueryFanFrame &q, long long
             float dist;
             if (exact_hit(td, c0.w, q.tris15 + (size_t)15 * tri, S, &hp, &dist)) {
                 hit_list_consider(hl, dist, tri, a, ak);
-                const float b = fan_order_bound(hit_list_bound(hl));
+                const float b = order_bound(hit_list_bound(hl));
                 if (b < bound) {                                   // (the K-th entry arrived or moved in: so does the list's end)
                     bound = b;
-                    end = min(end, cv.light_off[key + fan_order_shells(bin_shell_of(b, d0, iw, cv.shells))]);
+                    end = min(end, cv.light_off[key + order_shells(bin_shell_of(b, d0, iw, cv.shells))]);
                 }
             }
         }
@@ -102,28 +78,10 @@ __device__ __forceinline__ void fan_order_walk(const QueryFanFrame &q, long long
         // (rare) the lanes the bins do not cover: their origin's full table, k_query_fan's loop body into the same list
         const bool exact_only = !dir_in_filter_range(dir);
         if (STATS && swept) { n_cand += (unsigned)q.n; n_tests += (unsigned)q.n; }
-        for (int j = 0; j < q.n; j++) {
-            const float4 r0 = tab[j].r0, r1 = tab[j].r1, r2 = tab[j].r2;
-            const TestDots td = test_dots(r0, r1, r2, nd);
-            if (swept && (maybe_hit(td) || exact_only)) {
-                v3 hp;
-                float dist;
-                if (exact_hit(td, r0.w, q.tris15 + (size_t)15 * j, S, &hp, &dist)) hit_list_consider(hl, dist, j, a, ak);
-            }
-        }
+        for (int j = 0; j < q.n; j++) order_offer_origin_row(hl, tab, q.tris15, j, S, nd, swept, exact_only, a, ak);
     }
-    if (mine) {
-        int cnt = 0;
-#pragma unroll
-        for (int s = 0; s < K; s++)
-            if (s < max_hits) {
-                fan_order_store_slot(q, max_hits, ray, s, hl.k[s], tab, S, nd);
-                cnt += (int)(hl.k[s] != HIT_KEY_NONE);
-            }
-        counts[ray] = cnt;
-    } else if (zero) {
-        counts[ray] = 0;
-    }
+    if (mine) order_store_list(o, ray, hl, OriginRetest{ tab, q.tris15, S, nd });
+    else if (zero) o.counts[ray] = 0;
     if (STATS) flush_query_stats(q.stats, mine ? 1u : 0u, n_cand, n_tests, swept ? 1u : 0u);
 }
 
@@ -133,7 +91,7 @@ __global__ __launch_bounds__(256) void k_fan_order(const FanOrderFrame f)
 {
     const long long ray = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool ok = ray < f.f.nrays;
-    fan_order_walk<K, STATS>(f.f, ray, ok, ok, false, 0u, ld3(f.f.origin), 0u, f.f.tab, f.after, f.max_hits, f.counts);
+    fan_order_walk<K, STATS>(f.f, ray, ok, ok, false, 0u, ld3(f.f.origin), 0u, f.f.tab, f.out);
 }
 
 // ---- k_fans_order: one pass of a many-origin call, each lane's position from its ray's index (k_query_fans_binned's shape) ---------
@@ -144,7 +102,7 @@ __global__ __launch_bounds__(256) void k_fans_order(const FansOrderFrame f)
     const bool ok = ray < f.f.f.nrays;
     const FansLane l = fans_lane(f.f, ray, ok);
     const bool nobodys = ok && f.f.first == 0 && l.idx >= (uint32_t)f.norigins;
-    fan_order_walk<K, STATS>(f.f.f, ray, ok, l.mine, nobodys, l.k, l.S, l.bin_base, l.tab, f.after, f.max_hits, f.counts);
+    fan_order_walk<K, STATS>(f.f.f, ray, ok, l.mine, nobodys, l.k, l.S, l.bin_base, l.tab, f.out);
 }
 
 #define MIRT_ORDER_FANS_INSTANCES(K)                                                  \

@@ -12,14 +12,22 @@
 //   k_grid_order<K, STATS> a lane per ray through the cell grid (k_grid_closest's walk), reach = the list's bound.
 // Positions do not travel with the keys: the K winners are tested once more at the end (exact_hit_row on the winner's row gives the
 // same bits -- the same operations on the same operands, no fused forms) and the list stays at two registers an entry
-// (order_device.hpp: order_after, order_store_slot, order_store_list, which ordered_along.hip shares).
+// (order_device.hpp: order_after, order_offer_row, order_store_slot, order_store_list, which all ordered kernels share).
 // The `after` record of a ray is read before any of its slots is written, by the lane or wave that writes them: with max_hits == 1
 // the caller may pass the output array itself.
 // Built with -ffp-contract=off like every kernel of the library.
+#include "ordered_hits.hpp"
 #include "order_device.hpp"
 #include "../grid/ray_grid_device.hpp"
 
 namespace mirt {
+
+// Whether ray `ray` of a call whose rays were written out from (origins, directions, dir_of) names a direction of the call's list
+// (o.dir_of NULL: every ray does).  One that names none keeps its slots as the caller left them and gets the count 0.
+__device__ __forceinline__ bool order_named(const OrderFrame &o, long long ray)
+{
+    return !o.dir_of || (uint32_t)o.dir_of[ray] < (uint32_t)o.ndirs;
+}
 
 // ---- k_order_sweep: one lane per ray, every ray tests every triangle -------------------------------------------------------------------
 // Workgroup = 256 lanes = 256 rays.  The rows are staged through LDS in chunks of RT_CHUNK_ROWS and read as wave-uniform broadcasts.
@@ -36,7 +44,7 @@ __global__ __launch_bounds__(256) void k_order_sweep(const OrderFrame o)
     const bool exact_only = ray_exact_only(scene_rows_in_range(q), start, dir);
     float a;
     int k;
-    order_after(o, ray, ok, &a, &k);
+    order_after(o.out, ray, ok, &a, &k);
     HitList<K> l;
     hit_list_clear(l);
 
@@ -44,19 +52,11 @@ __global__ __launch_bounds__(256) void k_order_sweep(const OrderFrame o)
         const int cnt = min(RT_CHUNK_ROWS, q.n - base);
         stage_rows(s_rows, q.rows + base, cnt);
 #pragma unroll 2
-        for (int j = 0; j < cnt; j++) {
-            const RowVecs r = unpack_row(s_rows[3 * j], s_rows[3 * j + 1], s_rows[3 * j + 2]);
-            float e1e2b;
-            const TestDots td = ray_dots(r, start, nd, &e1e2b);
-            if (maybe_hit(td) || exact_only) {
-                v3 hp;
-                float dist;
-                if (exact_hit_row(td, e1e2b, r, start, &hp, &dist)) hit_list_consider(l, dist, base + j, a, k);
-            }
-        }
+        for (int j = 0; j < cnt; j++)
+            order_offer_row(l, unpack_row(s_rows[3 * j], s_rows[3 * j + 1], s_rows[3 * j + 2]), base + j, start, nd, true, exact_only, a, k);
     }
-    if (ok && order_named(o, ray)) order_store_list(o, ray, l, start, nd);
-    else if (ok) o.counts[ray] = 0;                                // (a ray of the along calls that names no direction: slots untouched)
+    if (ok && order_named(o, ray)) order_store_list(o.out, ray, l, SceneRetest{ q.rows, start, nd });
+    else if (ok) o.out.counts[ray] = 0;                            // (a ray of the along calls that names no direction: slots untouched)
 }
 
 template __global__ void k_order_sweep<1>(const OrderFrame);
@@ -81,34 +81,24 @@ __global__ __launch_bounds__(256) void k_order_sweep_wave(const OrderFrame o)
     const bool exact_only = ray_exact_only(scene_rows_in_range(q), start, dir);
     float a;
     int k;
-    order_after(o, ray, true, &a, &k);
+    order_after(o.out, ray, true, &a, &k);
     HitList<K> l;
     hit_list_clear(l);
 
-    for (int i = lane; i < q.n; i += 64) {
-        const float4 *src = reinterpret_cast<const float4 *>(q.rows + i);
-        const RowVecs r = unpack_row(src[0], src[1], src[2]);
-        float e1e2b;
-        const TestDots td = ray_dots(r, start, nd, &e1e2b);
-        if (maybe_hit(td) || exact_only) {
-            v3 hp;
-            float dist;
-            if (exact_hit_row(td, e1e2b, r, start, &hp, &dist)) hit_list_consider(l, dist, i, a, k);
-        }
-    }
+    for (int i = lane; i < q.n; i += 64) order_offer_row(l, order_row(q.rows, i), i, start, nd, true, exact_only, a, k);
 
     unsigned long long mine = HIT_KEY_NONE;
     int cnt = 0;
 #pragma unroll
     for (int s = 0; s < K; s++)
-        if (s < o.max_hits) {                                      // (wave-uniform)
+        if (s < o.out.max_hits) {                                  // (wave-uniform)
             const unsigned long long best = wave_min_key(l.k[0]);
             if (l.k[0] == best) hit_list_pop(l);                   // (all heads empty: popping changes nothing)
             if (lane == s) mine = best;
             cnt += (int)(best != HIT_KEY_NONE);
         }
-    if (lane < o.max_hits && order_named(o, ray)) order_store_slot(o, ray, lane, mine, start, nd);
-    if (lane == 0) o.counts[ray] = cnt;
+    if (lane < o.out.max_hits && order_named(o, ray)) order_store_slot(o.out, ray, lane, mine, SceneRetest{ q.rows, start, nd });
+    if (lane == 0) o.out.counts[ray] = cnt;
 }
 
 template __global__ void k_order_sweep_wave<1>(const OrderFrame);
@@ -131,8 +121,8 @@ __global__ __launch_bounds__(256) void k_grid_order(const OrderFrame o)
     const GridLane gl = grid_lane(f, ray, mine);
     float a;
     int k;
-    order_after(o, ray, mine, &a, &k);
-    const bool open = mine && a == a;                              // (a NaN record admits nothing: no walk)
+    order_after(o.out, ray, mine, &a, &k);
+    const bool open = mine && a == a;                            // (a NaN record admits nothing: no walk)
     const bool swept = open && !gl.fit;
     bool live = open && gl.fit;
     GridWalk w = grid_walk_begin(f.v.d, gl.S, V3(-gl.nd.x, -gl.nd.y, -gl.nd.z), live);
@@ -171,21 +161,11 @@ __global__ __launch_bounds__(256) void k_grid_order(const OrderFrame o)
         e += (uint32_t)act;
     }
     if (__any(swept)) {
-        // (rare) the lanes the structure does not cover: every row of the scene, k_order_sweep's loop body
+        // (rare) the lanes the structure does not cover: every row of the scene
         if (STATS && swept) { c[GSTAT_TESTS] += (unsigned)f.q.n; c[GSTAT_SWEPT] = 1; }
-        for (int j = 0; j < f.q.n; j++) {
-            const float4 *src4 = reinterpret_cast<const float4 *>(f.q.rows + j);
-            const RowVecs r = unpack_row(src4[0], src4[1], src4[2]);
-            float e1e2b;
-            const TestDots td = ray_dots(r, gl.S, gl.nd, &e1e2b);
-            if (swept && (maybe_hit(td) || gl.exact_only)) {
-                v3 hp;
-                float dist;
-                if (exact_hit_row(td, e1e2b, r, gl.S, &hp, &dist)) hit_list_consider(l, dist, j, a, k);
-            }
-        }
+        order_sweep_tail(l, f.q.rows, f.q.n, gl.S, gl.nd, swept, gl.exact_only, a, k);
     }
-    if (mine) order_store_list(o, ray, l, gl.S, gl.nd);
+    if (mine) order_store_list(o.out, ray, l, SceneRetest{ f.q.rows, gl.S, gl.nd });
     if (STATS) { c[GSTAT_RAYS] = mine ? 1u : 0u; flush_grid_stats(f.stats, c); }
 }
 

@@ -3,17 +3,16 @@
 #pragma once
 
 #include "hit_list.hpp"
+#include "order_out.hpp"
 #include "../grid/ray_grid.hpp"
 
 namespace mirt {
 
-// A call: the scene's rows and the caller's rays (f.q; f.q.hits is the OUTPUT, nrays * max_hits records, ray-major), the grid's
-// structure and counters for k_grid_order (f.v, f.stats; unused by the sweeps), the `after` records or NULL, and the counts.
+// A call: the scene's rows and the caller's rays (f.q; f.q.hits is not read), the grid's structure and counters for k_grid_order
+// (f.v, f.stats; unused by the sweeps), and what the ordered call adds (out).
 struct OrderFrame {
     GridFrame f;
-    const uint32_t *after;       // nrays records of HIT_WORDS words, or NULL: only distance and index are read
-    int max_hits;                // 1 .. K of the instantiation
-    int32_t *counts;             // nrays
+    OrderOut out;
     const int32_t *dir_of;       // the sweeps of mirt_intersect_ordered_alongs*: the rays' indices into the call's ndirs directions; a ray
     int ndirs;                   // whose index names none keeps its slots and gets the count 0.  NULL: every ray is answered
 };

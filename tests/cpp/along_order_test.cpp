@@ -1,4 +1,4 @@
-// The bound rule of the ordered hits along a direction (order/along_order.hpp) together with the list rule (order/hit_list.hpp),
+// The bound rule of the ordered hits along a direction (order/order_bound.hpp) together with the list rule (order/hit_list.hpp),
 // against a plain sort, on the CPU (built with -ffp-contract=off like the library).
 //
 // A ray's input is laid out as the structure of along/along.hpp lays it out: the rows of its cell, shells in rising order (a row's
@@ -24,7 +24,7 @@
 #ifdef ALONG_ORDER_LIBRARY_SHELL
 #include "../../cpp-raytracer-rasterizer_amd/along/along.hpp"
 #endif
-#include "../../cpp-raytracer-rasterizer_amd/order/along_order.hpp"
+#include "../../cpp-raytracer-rasterizer_amd/order/order_bound.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -125,23 +125,23 @@ static HitList<K> model_walk(const Ray &r, float a, int k, bool fault, long *off
     HitList<K> l;
     hit_list_clear(l);
     if (!(a == a)) return l;                                               // a NaN record admits nothing: no walk
-    float thr = along_order_threshold(r.rs, along_order_bound(hit_list_bound(l)));
-    uint32_t end = r.off[along_order_shells(shell_of(thr, r.d0, r.iw, r.shells))];
+    float thr = along_order_threshold(r.rs, order_bound(hit_list_bound(l)));
+    uint32_t end = r.off[order_shells(shell_of(thr, r.d0, r.iw, r.shells))];
     for (uint32_t e = 0; e < end; e++) {
         const Row &w = r.rows[e];
         ++*offered;
-        const bool near_ok = fault ? !(w.near >= thr) : along_order_near_ok(w.near, thr);
+        const bool near_ok = fault ? !(w.near >= thr) : order_near_ok(w.near, thr);
         if (!near_ok || !w.accepted) continue;
         hit_list_consider(l, w.dist, w.tri, a, k);
-        thr = along_order_threshold(r.rs, along_order_bound(hit_list_bound(l)));
-        end = std::min(end, r.off[along_order_shells(shell_of(thr, r.d0, r.iw, r.shells))]);
+        thr = along_order_threshold(r.rs, order_bound(hit_list_bound(l)));
+        end = std::min(end, r.off[order_shells(shell_of(thr, r.d0, r.iw, r.shells))]);
     }
     for (size_t e = r.off[(size_t)r.shells]; e < r.rows.size(); e++) {
         const Row &w = r.rows[e];
         ++*offered;
-        if (!along_order_near_ok(w.near, thr) || !w.accepted) continue;
+        if (!order_near_ok(w.near, thr) || !w.accepted) continue;
         hit_list_consider(l, w.dist, w.tri, a, k);
-        thr = along_order_threshold(r.rs, along_order_bound(hit_list_bound(l)));
+        thr = along_order_threshold(r.rs, order_bound(hit_list_bound(l)));
     }
     return l;
 }
@@ -224,7 +224,7 @@ int main()
     printf("+inf -> %u, FLT_MAX -> %u, rs + FLT_MAX -> %u of %d shells; with no shell width +inf -> %u (inf * 0 is NaN), FLT_MAX -> %u\n",
            inf_w, max_w, sum_w, SHELLS, inf_0, max_0);
     if (inf_w != SHELLS - 1 || max_w != SHELLS - 1 || sum_w != SHELLS - 1 || inf_0 != 0u || max_0 != 0u) { printf("FAILED\n"); return 1; }
-    if (along_order_bound(INFINITY) != FLT_MAX || along_order_bound(3.5f) != 3.5f || along_order_bound(0.0f) != 0.0f) { printf("FAILED\n"); return 1; }
+    if (order_bound(INFINITY) != FLT_MAX || order_bound(3.5f) != 3.5f || order_bound(0.0f) != 0.0f) { printf("FAILED\n"); return 1; }
 
     Tally N, F;                                                         // the regime around the origin (first, as it always ran), the far one
     for (int it = 0; it < 12000; it++) {

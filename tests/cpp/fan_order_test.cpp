@@ -1,4 +1,4 @@
-// The bound rule of the ordered hits from shared origins (order/fan_order.hpp) together with the list rule (order/hit_list.hpp),
+// The bound rule of the ordered hits from shared origins (order/order_bound.hpp) together with the list rule (order/hit_list.hpp),
 // against a plain sort, on the CPU (built with -ffp-contract=off like the library).
 //
 // A ray's input is laid out as a bin of a cube around the origin lays it out (query/rt_query.hpp: CubeView): the rows of the bin,
@@ -18,7 +18,7 @@
 #ifdef FAN_ORDER_LIBRARY_SHELL
 #include "../../cpp-raytracer-rasterizer_amd/csrc/rt_binned.hpp"
 #endif
-#include "../../cpp-raytracer-rasterizer_amd/order/fan_order.hpp"
+#include "../../cpp-raytracer-rasterizer_amd/order/order_bound.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -107,18 +107,18 @@ static HitList<K> model_walk(const Ray &r, float a, int k, bool fault, long *off
     HitList<K> l;
     hit_list_clear(l);
     if (!(a == a)) return l;                                               // a NaN record admits nothing: no walk
-    float bound = fan_order_bound(hit_list_bound(l));
-    uint32_t end = r.off[fan_order_shells(shell_of(bound, r.d0, r.iw, r.shells))];
+    float bound = order_bound(hit_list_bound(l));
+    uint32_t end = r.off[order_shells(shell_of(bound, r.d0, r.iw, r.shells))];
     for (uint32_t e = 0; e < end; e++) {
         const Row &w = r.rows[e];
         ++*offered;
-        const bool near_ok = fault ? !(w.near >= bound) : fan_order_near_ok(w.near, bound);
+        const bool near_ok = fault ? !(w.near >= bound) : order_near_ok(w.near, bound);
         if (!near_ok || !w.accepted) continue;
         hit_list_consider(l, w.dist, w.tri, a, k);
-        const float b = fan_order_bound(hit_list_bound(l));
+        const float b = order_bound(hit_list_bound(l));
         if (b < bound) {
             bound = b;
-            end = std::min(end, r.off[fan_order_shells(shell_of(b, r.d0, r.iw, r.shells))]);
+            end = std::min(end, r.off[order_shells(shell_of(b, r.d0, r.iw, r.shells))]);
         }
     }
     return l;
@@ -187,8 +187,8 @@ int main()
     printf("+inf -> %u, FLT_MAX -> %u of %d shells, FLT_MAX -> %u of 1 shell; with no shell width +inf -> %u (inf * 0 is NaN), FLT_MAX -> %u\n",
            inf_w, max_w, S, one, inf_0, max_0);
     if (inf_w != S - 1 || max_w != S - 1 || one != 0u || inf_0 != 0u || max_0 != 0u) { printf("FAILED\n"); return 1; }
-    if (fan_order_bound(INFINITY) != FLT_MAX || fan_order_bound(3.5f) != 3.5f || fan_order_bound(0.0f) != 0.0f) { printf("FAILED\n"); return 1; }
-    if (!fan_order_near_ok(2.0f, 2.0f) || fan_order_near_ok(nextafterf(2.0f, 3.0f), 2.0f) || !fan_order_near_ok(NAN, 2.0f)) { printf("FAILED\n"); return 1; }
+    if (order_bound(INFINITY) != FLT_MAX || order_bound(3.5f) != 3.5f || order_bound(0.0f) != 0.0f) { printf("FAILED\n"); return 1; }
+    if (!order_near_ok(2.0f, 2.0f) || order_near_ok(nextafterf(2.0f, 3.0f), 2.0f) || !order_near_ok(NAN, 2.0f)) { printf("FAILED\n"); return 1; }
 
     Tally T;
     for (int it = 0; it < 9000; it++) {

@@ -3,18 +3,15 @@ test_gpu_placement_ordered_fans.py) share: the scenes, origins and batches of th
 origins_for with seed 3, make_batch with seed 5 -- the 182 seam directions of every origin among random ones, origins mixed within
 every wave), the oracle's expectation on the rays written out (ordered_helpers.peel to 10 hits, computed once per case and left
 read-only), the floors that keep the tests from being vacuous, and the calls through 0xAA-prefilled buffers with guard records and
-guard counts behind them (ordered_along_helpers' pattern).  Test plumbing only."""
-import ctypes as C
-
+guard counts behind them (ordered_helpers.guarded_call).  Test plumbing only."""
 import numpy as np
 
 import mirt
-import ordered_along_helpers as A
 import ordered_helpers as O
 from query_helpers import fan_scene_of
 from test_gpu_fans_query import make_batch, origins_for
 
-GUARD, REC = A.GUARD, A.REC
+GUARD, REC, same, prefix, guarded_host = O.GUARD, O.REC, O.same, O.prefix, O.guarded_host
 HITS = (1, 2, 3, 4, 5, 8)
 CAP = 10                                                            # the oracle peels to 10 hits: "more than 8" shows
 NAMES = ("mirt_intersect_ordered_from", "mirt_intersect_ordered_from_device", "mirt_intersect_ordered_fans", "mirt_intersect_ordered_fans_device")
@@ -26,7 +23,6 @@ FLOORS = {("soup2000", 1, 2049): ((0.8, 0.55, 0.12, None), True, None),
           ("cornell", 5, 1025): ((None, 0.3, None, None), False, 0.15),
           ("soup65x2", 5, 1025): ((None, None, None, None), False, 0.3),
           ("cornell+soup2000", 5, 2049): ((None, None, 0.5, 0.15), False, None)}
-same, prefix = A.same, A.prefix
 _cache = {}
 
 
@@ -79,55 +75,11 @@ def floors_hold(key, want):
     return share, deep, tie
 
 
-# ---- calls through guarded buffers -------------------------------------------------------------------------------------------------------
-
-def guarded_host(n, max_hits):
-    hbuf = np.frombuffer(np.full((n * max_hits + GUARD) * REC, 0xAA, np.uint8).tobytes(), mirt.HIT_DTYPE).copy()
-    cbuf = np.frombuffer(np.full((n + GUARD) * 4, 0xAA, np.uint8).tobytes(), np.int32).copy()
-    return hbuf, cbuf
-
-
 def ordered_fans(form, origins, of, dirs, max_hits, after=None, mode=None, what="", stray=None):
     """One call through guarded buffers: (hits[n, max_hits], counts[n], mirt.fan_stats()).  origins: one origin (3,) for
-    mirt_intersect_ordered_from* (of is not used), or several (k, 3) with `of` (or None for k == 1) for mirt_intersect_ordered_fans*.
-    On the device `after` is read from a buffer of its own."""
-    from devbuf import DeviceArray, to_device
-    origins = np.ascontiguousarray(origins, np.float32)
-    several = origins.ndim == 2
-    dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
-    n = len(dirs)
-    after = None if after is None else np.ascontiguousarray(after, mirt.HIT_DTYPE)
-    of = None if of is None or not several else np.ascontiguousarray(of, np.int32)
-    lib = mirt.load()
-    P = mirt._ptr
-    mirt.set_query_mode(mirt.QUERY_AUTO if mode is None else mode)
-    try:
-        if form == "host":
-            hbuf, cbuf = guarded_host(n, max_hits)
-            if several:
-                mirt._check(lib.mirt_intersect_ordered_fans(P(origins), len(origins), P(of), P(dirs), n, P(after), max_hits, P(hbuf), P(cbuf)))
-            else:
-                mirt._check(lib.mirt_intersect_ordered_from(P(origins), P(dirs), n, P(after), max_hits, P(hbuf), P(cbuf)))
-            return A._checked(hbuf, cbuf, n, max_hits, what, stray) + (mirt.fan_stats(),)
-        held = [to_device(dirs)] + [to_device(x) for x in (after, of) if x is not None]
-        d_after = None if after is None else held[1].ptr
-        d_of = None if of is None else held[-1].ptr
-        try:
-            with DeviceArray(((n * max_hits + GUARD) * REC,), np.uint8, 0xAA) as d_hits, DeviceArray(((n + GUARD) * 4,), np.uint8, 0xAA) as d_counts:
-                if several:
-                    mirt.intersect_ordered_fans_device(origins, d_of, held[0].ptr, n, d_after, max_hits, d_hits.ptr, d_counts.ptr)
-                else:
-                    mirt.intersect_ordered_from_device(origins, held[0].ptr, n, d_after, max_hits, d_hits.ptr, d_counts.ptr)
-                st = mirt.fan_stats()
-                mirt.sync()
-                hbuf = np.frombuffer(d_hits.read().tobytes(), mirt.HIT_DTYPE).copy()
-                cbuf = np.frombuffer(d_counts.read().tobytes(), np.int32).copy()
-            return A._checked(hbuf, cbuf, n, max_hits, what, stray) + (st,)
-        finally:
-            for x in held:
-                x.free()
-    finally:
-        mirt.set_query_mode(mirt.QUERY_AUTO)
+    mirt_intersect_ordered_from* (of is not used), or several (k, 3) with `of` (or None for k == 1) for mirt_intersect_ordered_fans*."""
+    of = of if np.ndim(origins) == 2 else None
+    return O.guarded_call(form, NAMES, mirt.fan_stats, origins, dirs, of, max_hits, after, mode, what, stray)
 
 
 def peel_in_place(form, origins, of, dirs, mode, rounds):
@@ -171,30 +123,14 @@ def peel_in_place(form, origins, of, dirs, mode, rounds):
 
 
 def bad_calls(n=5):
-    """(entry point name, arguments, what is wrong) for every argument the calls refuse, and the arrays they point into: (cases,
-    arrays, snapshot())."""
+    """ordered_helpers.bad_calls for the four entry points, and the arrays the cases point into: (cases, arrays, snapshot())."""
     P = mirt._ptr
     origin = np.zeros(3, np.float32)
     origins = np.array([[0, 0, 0], [0, 1, 0]], np.float32)
     of = np.array([0, 1, 1, 0, 1], np.int32)[:n]
     dirs = np.ones((n, 3), np.float32)
-    hits = np.frombuffer(np.full(n * 9 * REC, 0xAA, np.uint8).tobytes(), mirt.HIT_DTYPE).copy()
-    counts = np.full(n, -1431655766, np.int32)                      # 0xAAAAAAAA
-    inside = C.c_void_p(hits.ctypes.data + REC)
-    H, Cn, D = P(hits), P(counts), P(dirs)
-    order = [((None, 0), "max_hits 0"), ((None, 9), "max_hits 9"), ((None, -1), "max_hits -1"),
-             ((H, 2), "after == hits with two slots a ray"), ((inside, 1), "after inside hits")]
-    cases = []
-    for name in NAMES:
-        head = (P(origins), 2, P(of)) if "fans" in name else (P(origin),)
-        for (after, m), why in order:
-            cases.append((name, head + (D, n, after, m, H, Cn), why))
-        cases += [(name, head + (None, n, None, 2, H, Cn), "NULL dirs"), (name, head + (D, n, None, 2, None, Cn), "NULL hits"),
-                  (name, head + (D, n, None, 2, H, None), "NULL counts"), (name, head + (D, -1, None, 2, H, Cn), "a negative count")]
-        if "fans" in name:
-            cases += [(name, (P(origins), -1, P(of), D, n, None, 2, H, Cn), "a negative origin count"), (name, (None, 2, P(of), D, n, None, 2, H, Cn), "NULL origins"),
-                      (name, (P(origins), 0, P(of), D, n, None, 2, H, Cn), "rays but no origin"), (name, (P(origins), 2, None, D, n, None, 2, H, Cn), "NULL origin_of for two origins")]
-        else:
-            cases.append((name, (None, D, n, None, 2, H, Cn), "NULL origin"))
-    keep = (origin, origins, of, dirs, hits, counts)
-    return cases, keep, lambda: (hits.tobytes(), counts.tobytes())
+    bad_heads = [((P(origins), -1, P(of)), "a negative origin count"), ((None, 2, P(of)), "NULL origins"),
+                 ((P(origins), 0, P(of)), "rays but no origin"), ((P(origins), 2, None), "NULL origin_of for two origins")]
+    cases, out, snapshot = O.bad_calls(NAMES, (P(origin),), (P(origins), 2, P(of)), bad_heads, "NULL origin", dirs, "NULL dirs")
+    return cases, (origin, origins, of, dirs) + out, snapshot
+

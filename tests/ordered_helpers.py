@@ -1,8 +1,11 @@
 """What the tests of the ordered hits (test_gpu_ordered_hits.py) share: the scenes and ray sets, and the CPU oracle's expectations --
 the enumeration of a ray's hits by peeling (ClosestIntersection on a fresh record against the scene with the rows of the triangles
 already reported for that ray set to NaN: a NaN row accepts nothing and indices keep their meaning), and the per-triangle table
-(one oracle call per (ray, triangle) on a fresh record) from which the answer behind an arbitrary `after` record is sorted.
+(one oracle call per (ray, triangle) on a fresh record) from which the answer behind an arbitrary `after` record is sorted; and, for
+the calls along directions and from origins, the one call through guarded 0xAA buffers and the list of refused calls.
 Test plumbing only."""
+import ctypes as C
+
 import numpy as np
 
 import mirt
@@ -145,3 +148,126 @@ def after_records(slot0, shift=0):
                               [F32(-1), d, np.nextafter(d, F32("inf")), np.nextafter(d, F32(0)), F32(FLT_MAX), F32("inf")], F32("nan")).astype(F32)
     a["index"] = np.select([kind == 1, kind == 2, kind == 3, kind == 4, kind == 5], [-1, ix, ix - 1, ix + 1, np.iinfo(np.int32).max], ix).astype(np.int32)
     return a, kind
+
+
+# ---- what the tests of the ordered calls along directions and from origins (ordered_along_helpers.py, ordered_fans_helpers.py) share ----
+
+GUARD = 16
+REC = mirt.HIT_DTYPE.itemsize
+
+
+def prefix(want, n, max_hits):
+    hits, counts = want
+    return np.ascontiguousarray(hits[:n, :max_hits]), np.minimum(counts[:n], max_hits).astype(np.int32)
+
+
+def same(got, want, what):
+    gh, gc = got[:2]
+    wh, wc = want[:2]
+    assert np.array_equal(gc, wc), "%s: %d counts differ (first at ray %d)" % (what, int((gc != wc).sum()), int(np.flatnonzero(gc != wc)[0]))
+    assert np.array_equal(gh["index"], wh["index"]), "%s: index differs in %d slots" % (what, int((gh["index"] != wh["index"]).sum()))
+    assert np.array_equal(gh["distance"].view(np.uint32), wh["distance"].view(np.uint32)), "%s: distance not bit-identical" % what
+    assert gh.tobytes() == wh.tobytes(), "%s: position not bit-identical" % what
+
+
+def last_records(hits, counts, max_hits):
+    """after[i] for the next call: the last record written where the ray's count reached max_hits, a fresh record (which admits
+    nothing: the ray is exhausted) otherwise."""
+    nxt = mirt.fresh_hits(len(hits))
+    full = counts == max_hits
+    nxt[full] = hits[full, max_hits - 1]
+    return nxt
+
+
+def guarded_host(n, max_hits):
+    hbuf = np.frombuffer(np.full((n * max_hits + GUARD) * REC, 0xAA, np.uint8).tobytes(), mirt.HIT_DTYPE).copy()
+    cbuf = np.frombuffer(np.full((n + GUARD) * 4, 0xAA, np.uint8).tobytes(), np.int32).copy()
+    return hbuf, cbuf
+
+
+def _checked(hbuf, cbuf, n, max_hits, what, stray=None):
+    """The call's records and counts out of the 0xAA-prefilled buffers: all written (the slots of a stray ray all NOT), the guards
+    untouched."""
+    hraw = hbuf.view(np.uint8).reshape(-1, REC)
+    craw = cbuf.view(np.uint8).reshape(-1, 4)
+    assert (hraw[n * max_hits:] == 0xAA).all(), "%s: wrote beyond %d x %d records" % (what, n, max_hits)
+    assert (craw[n:] == 0xAA).all(), "%s: wrote beyond %d counts" % (what, n)
+    untouched = (hraw[:n * max_hits] == 0xAA).all(axis=1).reshape(n, max_hits)
+    if stray is None:
+        stray = np.zeros(n, bool)
+    assert not untouched[~stray].any(), "%s: a slot of the call was not written" % what
+    assert (hraw[:n * max_hits].reshape(n, max_hits, REC)[stray] == 0xAA).all(), "%s: a slot of a ray that names no direction was written" % what
+    assert not (craw[:n] == 0xAA).all(axis=1).any(), "%s: a count of the call was not written" % what
+    hits = hbuf[:n * max_hits].reshape(n, max_hits).copy()
+    counts = cbuf[:n].copy()
+    assert ((counts >= 0) & (counts <= max_hits)).all(), what
+    return hits, counts
+
+
+def guarded_call(form, names, stats, head, per_ray, of, max_hits, after=None, mode=None, what="", stray=None):
+    """One call through guarded buffers, host or device form: (hits[n, max_hits], counts[n], stats()).  names: the family's four entry
+    points (NAMES of its helpers); head: what the rays share -- one direction or origin (3,) for the first two, or several (k, 3)
+    with the rays' indices `of` (or None for k == 1) for the last two; per_ray: the rays' own (n, 3).  On the device `after` is read
+    from a buffer of its own."""
+    from devbuf import DeviceArray, to_device
+    head = np.ascontiguousarray(head, np.float32)
+    several = head.ndim == 2
+    per_ray = np.ascontiguousarray(per_ray, np.float32).reshape(-1, 3)
+    n = len(per_ray)
+    after = None if after is None else np.ascontiguousarray(after, mirt.HIT_DTYPE)
+    of = None if of is None else np.ascontiguousarray(of, np.int32)
+    lib = mirt.load()
+    P = mirt._ptr
+    mirt.set_query_mode(mirt.QUERY_AUTO if mode is None else mode)
+    try:
+        if form == "host":
+            hbuf, cbuf = guarded_host(n, max_hits)
+            lead = (P(head), len(head), P(of)) if several else (P(head),)
+            mirt._check(getattr(lib, names[2 if several else 0])(*lead, P(per_ray), n, P(after), max_hits, P(hbuf), P(cbuf)))
+            return _checked(hbuf, cbuf, n, max_hits, what, stray) + (stats(),)
+        held = [to_device(per_ray)] + [to_device(x) for x in (after, of) if x is not None]
+        d_after = None if after is None else held[1].ptr
+        d_of = None if of is None else held[-1].ptr
+        try:
+            with DeviceArray(((n * max_hits + GUARD) * REC,), np.uint8, 0xAA) as d_hits, DeviceArray(((n + GUARD) * 4,), np.uint8, 0xAA) as d_counts:
+                lead = (head, d_of) if several else (head,)
+                getattr(mirt, names[3 if several else 1][len("mirt_"):])(*lead, held[0].ptr, n, d_after, max_hits, d_hits.ptr, d_counts.ptr)
+                st = stats()
+                mirt.sync()
+                hbuf = np.frombuffer(d_hits.read().tobytes(), mirt.HIT_DTYPE).copy()
+                cbuf = np.frombuffer(d_counts.read().tobytes(), np.int32).copy()
+            return _checked(hbuf, cbuf, n, max_hits, what, stray) + (st,)
+        finally:
+            for x in held:
+                x.free()
+    finally:
+        mirt.set_query_mode(mirt.QUERY_AUTO)
+
+
+def bad_calls(names, one_head, several_head, bad_several_heads, no_head, per_ray, no_per_ray):
+    """(entry point name, arguments, what is wrong) for every argument the family's four entry points `names` refuse --
+    test_gpu_ordered_hits.py: test_errors_and_an_empty_call's and those of the family's closest-hit calls --, and the record and count
+    arrays they point into: (cases, (hits, counts), snapshot()).  one_head / several_head: the leading arguments of the first and the
+    last two entry points; bad_several_heads: (head, what is wrong) of the latter; no_head / no_per_ray: what a NULL head of the
+    former and a NULL per-ray array are called; per_ray: the rays' own (n, 3)."""
+    P = mirt._ptr
+    n = len(per_ray)
+    hits = np.frombuffer(np.full(n * 9 * REC, 0xAA, np.uint8).tobytes(), mirt.HIT_DTYPE).copy()
+    counts = np.full(n, -1431655766, np.int32)                      # 0xAAAAAAAA
+    inside = C.c_void_p(hits.ctypes.data + REC)
+    H, Cn, R = P(hits), P(counts), P(per_ray)
+    order = [((None, 0), "max_hits 0"), ((None, 9), "max_hits 9"), ((None, -1), "max_hits -1"),
+             ((H, 2), "after == hits with two slots a ray"), ((inside, 1), "after inside hits")]
+    cases = []
+    for name in names:
+        several = name in names[2:]
+        head = several_head if several else one_head
+        for (after, m), why in order:
+            cases.append((name, head + (R, n, after, m, H, Cn), why))
+        cases += [(name, head + (None, n, None, 2, H, Cn), no_per_ray), (name, head + (R, n, None, 2, None, Cn), "NULL hits"),
+                  (name, head + (R, n, None, 2, H, None), "NULL counts"), (name, head + (R, -1, None, 2, H, Cn), "a negative count")]
+        if several:
+            cases += [(name, bad + (R, n, None, 2, H, Cn), why) for bad, why in bad_several_heads]
+        else:
+            cases.append((name, (None, R, n, None, 2, H, Cn), no_head))
+    return cases, (hits, counts), lambda: (hits.tobytes(), counts.tobytes())
