@@ -109,6 +109,7 @@ static int along_ensure(AlongCache &C, const float *dir, const AlongDesc &desc, 
         if ((rc = along_pairs_room(C, pairs_after_readback(count[0])))) return rc;
     }
     C.gave_up = count[1] > (uint32_t)along_every_cap(g.n);
+    C.nevery = count[1];
     C.nrows = 0;
     if (!C.gave_up) {
         HIP_TRY(bucket_sort_pairs(C.d_keys, C.d_vals, C.d_counters, C.cap_pairs, count[0], nkeys, C.d_tmp_keys, C.d_tmp_vals, bcnt, bbase, bcur,

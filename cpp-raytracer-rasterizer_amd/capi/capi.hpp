@@ -21,6 +21,7 @@
 #include "../order/ordered_hits.hpp"
 #include "../order/ordered_along.hpp"
 #include "../order/ordered_fans.hpp"
+#include "../count/count_hits.hpp"
 #include "../lights/many_lights.hpp"
 #include "../lights/aa_many_lights.hpp"
 #include "cube_plan.hpp"
@@ -338,6 +339,7 @@ struct AlongCache {
     QueryRow *d_rows = nullptr;                  // the rows in key order (at least one: a lane with no row left loads row 0)
     AlongAux *d_aux = nullptr;
     uint32_t cap_rows = 0, nrows = 0;
+    uint32_t nevery = 0;                         // triangles the build put on the every-ray list (count.cpp: a grid of nothing else)
     float *d_near = nullptr;                     // n depth bounds (k_along_pairs -> k_along_rows)
     int cap_near = 0;
     uint32_t *d_counters = nullptr;              // [0] pairs, [1] triangles on the every-ray list
@@ -835,6 +837,7 @@ int order_intersect_host(const mirt_ray *rays, int nrays, const mirt_hit *after,
 int order_args(const void *rays, int nrays, const void *after, int max_hits, const void *hits, const void *counts);
 int order_launch(const void *d_rays, int nrays, const OrderOut &out, const void *d_dir_of, int ndirs);
 int order_staging(int checked, int nrays, int max_hits);
+int order_staging_rays(size_t rays);                  // (its per-ray arrays alone: `after` and the counts, which count.cpp stages through too)
 // The kernel of list length K = 1, 2, 4 or 8 out of the four instantiations; max_hits of 3, 5, 6 or 7 run the next length up ...
 template <class Kernel>
 Kernel order_pick(int max_hits, Kernel k1, Kernel k2, Kernel k4, Kernel k8)

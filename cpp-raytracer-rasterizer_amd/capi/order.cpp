@@ -76,17 +76,25 @@ int order_intersect(const void *d_rays, int nrays, const OrderOut &out)
 
 // The host form's staging arrays are its own and grow by their own measure (up to 160 bytes of records a ray), once the checks have
 // passed and there is something to stage.
+// (the per-ray arrays -- the `after` records and the counts -- are what the hit counts' host forms stage through as well: count.cpp)
+int order_staging_rays(size_t rays)
+{
+    int rc;
+    QueryRows &Q = g.qrows;
+    if (rays > Q.order_cap_rays) {
+        Q.order_cap_rays = 0;
+        if ((rc = dev_realloc_bytes(&Q.d_order_after, rays * sizeof(mirt_hit))) || (rc = dev_realloc_bytes(&Q.d_order_counts, rays * sizeof(int32_t)))) return rc;
+        Q.order_cap_rays = rays;
+    }
+    return MIRT_OK;
+}
 int order_staging(int checked, int nrays, int max_hits)
 {
     int rc;
     QueryRows &Q = g.qrows;
     if (checked || nrays == 0 || g.n <= 0) return MIRT_OK;
     const size_t rays = (size_t)nrays, records = rays * (size_t)max_hits;
-    if (rays > Q.order_cap_rays) {
-        Q.order_cap_rays = 0;
-        if ((rc = dev_realloc_bytes(&Q.d_order_after, rays * sizeof(mirt_hit))) || (rc = dev_realloc_bytes(&Q.d_order_counts, rays * sizeof(int32_t)))) return rc;
-        Q.order_cap_rays = rays;
-    }
+    if ((rc = order_staging_rays(rays))) return rc;
     if (records > Q.order_cap_records) {
         Q.order_cap_records = 0;
         if ((rc = dev_realloc_bytes(&Q.d_order_hits, records * sizeof(mirt_hit)))) return rc;

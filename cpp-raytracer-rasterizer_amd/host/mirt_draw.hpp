@@ -289,6 +289,25 @@ struct RayTracer {
         check(mirt_occluded_alongs(ndirs > 0 ? &dirs[0].x : nullptr, ndirs, dir_of, n > 0 ? &start[0].x : nullptr, n, max_distance, occluded),
               "mirt_occluded_alongs");
     }
+    // How many triangles each of n rays crosses: count[k] is the number of triangles ClosestIntersection(start[k], dir[k], ...) accepts at
+    // a distance a fresh record takes -- behind after[k] when `after` is given (only distance and triangleIndex are read), strictly
+    // nearer than max_distance[k] when limits are given; either may be null (mirt_count_hits).  Odd: start[k] lies inside a closed mesh.
+    void CountIntersections(const vec3 *start, const vec3 *dir, const Intersection *after, const float *max_distance, int32_t *count, int n)
+    {
+        upload_scene();
+        std::vector<mirt_ray> rays((size_t)n);
+        for (int k = 0; k < n; k++) { std::memcpy(rays[k].start, &start[k].x, 12); std::memcpy(rays[k].dir, &dir[k].x, 12); }
+        check(mirt_count_hits(rays.data(), n, reinterpret_cast<const mirt_hit *>(after), max_distance, count), "mirt_count_hits");
+    }
+    // ... and for n rays along one direction -- the crossings of a voxel line, of an X-ray beam --, through the grid of
+    // ClosestIntersection(start, dir, ...) above (mirt_count_hits_along).
+    void CountIntersections(const vec3 *start, vec3 dir, const Intersection *after, const float *max_distance, int32_t *count, int n)
+    {
+        upload_scene();
+        static_assert(sizeof(vec3) == 12, "starts travel as they are");
+        check(mirt_count_hits_along(&dir.x, n > 0 ? &start[0].x : nullptr, n, reinterpret_cast<const mirt_hit *>(after), max_distance, count),
+              "mirt_count_hits_along");
+    }
     // DirectLight(i) (:265-327) for n records, with the lights and the soft-shadow toggle as they stand: result[k] = DirectLight(i[k]).
     void DirectLight(const Intersection *i, vec3 *result, int n)
     {

@@ -38,6 +38,7 @@ EXPORTS = (
     "mirt_intersect_ordered", "mirt_intersect_ordered_device",
     "mirt_intersect_ordered_along", "mirt_intersect_ordered_along_device", "mirt_intersect_ordered_alongs", "mirt_intersect_ordered_alongs_device",
     "mirt_intersect_ordered_from", "mirt_intersect_ordered_from_device", "mirt_intersect_ordered_fans", "mirt_intersect_ordered_fans_device",
+    "mirt_count_hits", "mirt_count_hits_device", "mirt_count_hits_along", "mirt_count_hits_along_device", "mirt_count_hits_alongs", "mirt_count_hits_alongs_device",
     "mirt_shadow_mask", "mirt_shadow_mask_device", "mirt_direct_light_masked", "mirt_direct_light_masked_device", "mirt_get_shadow_mask_stats",
     "mirt_scene_upload_device", "mirt_scene_update_device", "mirt_scene_update", "mirt_scene_transform", "mirt_transform",
     "mirt_scene_download", "mirt_scene_info",
@@ -201,6 +202,12 @@ def load():
     lib.mirt_intersect_ordered_from_device.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
     lib.mirt_intersect_ordered_fans.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
     lib.mirt_intersect_ordered_fans_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
+    lib.mirt_count_hits.argtypes = [_vp, C.c_int, _vp, _vp, _vp]
+    lib.mirt_count_hits_device.argtypes = [_vp, C.c_int, _vp, _vp, _vp]
+    lib.mirt_count_hits_along.argtypes = [_vp, _vp, C.c_int, _vp, _vp, _vp]
+    lib.mirt_count_hits_along_device.argtypes = [_vp, _vp, C.c_int, _vp, _vp, _vp]
+    lib.mirt_count_hits_alongs.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp]
+    lib.mirt_count_hits_alongs_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp]
     lib.mirt_intersect_alongs.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp]
     lib.mirt_intersect_alongs_device.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp]
     lib.mirt_occluded_alongs.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]
@@ -908,7 +915,7 @@ def occluded_along_device(direction, d_origins, nrays, d_max_distance, d_occlude
 
 
 def along_stats():
-    """The last intersect_along* / occluded_along* / intersect_alongs* / occluded_alongs* / intersect_ordered_along(s)* call (mirt_get_along_stats), in
+    """The last intersect_along* / occluded_along* / intersect_alongs* / occluded_alongs* / intersect_ordered_along(s)* / count_hits_along(s)* call (mirt_get_along_stats), in
     mirt_query_stats' fields: mode_used, cube_source (0 no grid, 1 built by the call, 2 kept), cube_bins = cells per grid side, shells
     and -- profiling on, binned -- shadow_rays = rays, candidates = rows offered, tests = rows tested, fallback_records = rays that
     swept the scene.  For a call of several directions the counters are summed over its passes, and cube_source is 1 when some pass
@@ -1050,6 +1057,68 @@ def intersect_ordered_fans_device(origins, d_origin_of, d_dirs, nrays, d_after, 
     origins = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
     _check(load().mirt_intersect_ordered_fans_device(_ptr(origins), len(origins), d_origin_of, d_dirs, int(nrays), d_after, int(max_hits),
                                                      d_hits, d_counts))
+
+
+# ---- the number of hits along a ray ---------------------------------------------------------------------------
+
+def _count_arrays(n, after, max_distance, what):
+    """The `after` records (or None), the limits (or None) and the output of a count call of n rays."""
+    if after is not None:
+        after = np.ascontiguousarray(after, HIT_DTYPE)
+        if after.shape != (n,):
+            raise ValueError("%d %s but after has shape %s" % (n, what, after.shape))
+    return after, _as_limits(max_distance, n, what), np.zeros(n, np.int32)
+
+
+def count_hits(rays, after=None, max_distance=None):
+    """The number of triangles along every ray (mirt_count_hits): those ClosestIntersection accepts at a distance a fresh record
+    takes, behind after[i] when `after` is given (HIT_DTYPE, one record per ray: only distance and index are read) and strictly
+    nearer than max_distance[i] when limits are given (n floats, or one for all).  Returns int32 counts.  A point lies inside a closed
+    mesh when a ray from it crosses an odd number of triangles."""
+    rays = _as_rays(rays)
+    after, lim, counts = _count_arrays(len(rays), after, max_distance, "rays")
+    _check(load().mirt_count_hits(_ptr(rays), len(rays), _ptr(after), _ptr(lim), _ptr(counts)))
+    return counts
+
+
+def count_hits_device(d_rays, nrays, d_after, d_max_distance, d_counts):
+    """The same on device arrays (raw pointers; d_after and d_max_distance may be None), queued like intersect_device; mirt.sync()
+    completes it."""
+    _check(load().mirt_count_hits_device(d_rays, int(nrays), d_after, d_max_distance, d_counts))
+
+
+def count_hits_along(direction, origins, after=None, max_distance=None):
+    """count_hits() for the rays {origins[i], direction}, count for count, through the grid of intersect_along where that pays
+    (mirt_count_hits_along; set_query_mode, along_stats).  The occupancy of a voxel line is the count's parity."""
+    direction, origins = _as_along(direction, origins)
+    after, lim, counts = _count_arrays(len(origins), after, max_distance, "origins")
+    _check(load().mirt_count_hits_along(_ptr(direction), _ptr(origins), len(origins), _ptr(after), _ptr(lim), _ptr(counts)))
+    return counts
+
+
+def count_hits_along_device(direction, d_origins, nrays, d_after, d_max_distance, d_counts):
+    """The same on device arrays (raw pointers; the direction is host data, d_after and d_max_distance may be None), queued like a
+    *_device frame; mirt.sync() completes it."""
+    direction = np.ascontiguousarray(direction, np.float32).reshape(3)
+    _check(load().mirt_count_hits_along_device(_ptr(direction), d_origins, int(nrays), d_after, d_max_distance, d_counts))
+
+
+def count_hits_alongs(directions, dir_of, origins, after=None, max_distance=None):
+    """count_hits() for the rays {origins[i], directions[dir_of[i]]}, count for count, through the groups of intersect_alongs
+    (mirt_count_hits_alongs).  dir_of: one int32 per ray, or None for a single direction."""
+    directions, dir_of, origins = _as_alongs(directions, dir_of, origins)
+    after, lim, counts = _count_arrays(len(origins), after, max_distance, "origins")
+    _check(load().mirt_count_hits_alongs(_ptr(directions), len(directions), _ptr(dir_of), _ptr(origins), len(origins), _ptr(after), _ptr(lim),
+                                         _ptr(counts)))
+    return counts
+
+
+def count_hits_alongs_device(directions, d_dir_of, d_origins, nrays, d_after, d_max_distance, d_counts):
+    """The same on device arrays (raw pointers; the directions are host data, d_dir_of may be None for a single direction).  A ray
+    whose index names no direction gets the count 0."""
+    directions = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+    _check(load().mirt_count_hits_alongs_device(_ptr(directions), len(directions), d_dir_of, d_origins, int(nrays), d_after, d_max_distance,
+                                                d_counts))
 
 
 # ---- shadow masks: DirectLight's shadow decisions, and DirectLight from them ---------------------------------

@@ -733,6 +733,54 @@ MIRT_API int mirt_intersect_ordered_fans(const float *origins3, int norigins, co
 MIRT_API int mirt_intersect_ordered_fans_device(const float *origins3, int norigins, const void *d_origin_of, const void *d_dirs3, int nrays,
                                                 const void *d_after, int max_hits, void *d_hits, void *d_counts);
 
+/* ---- the number of hits along a ray (additions to ABI 4) ---- */
+
+/* How many triangles a ray crosses: a point-in-mesh test by the parity of the crossings, the occupancy of a voxel line, the number of
+ * surfaces an X-ray or CT beam passes, the layers of a part -- every hit of a ray in ONE call, where mirt_intersect_ordered* holds at
+ * most MIRT_MAX_ORDERED_HITS and has to be called again behind its last record.  A count needs no list and no order: counts[i] is the
+ * number of triangles j such that
+ *   - the reference's test accepts j for ray i (raytracer.cpp:239),
+ *   - FLT_MAX >= d_j -- what a fresh record takes, so never a NaN or +inf distance; d_j is the reference's own distance (:241-242),
+ *     with `dir` used as given --,
+ *   - when `after` is given, d_j > a || (d_j == a && j < k) for a = after[i].distance, k = after[i].index: float and signed-int
+ *     comparisons as written (a NaN a admits nothing, a negative a everything, -0.0f behaves as 0.0f); only distance and index of
+ *     an `after` record are read,
+ *   - when `max_distance` is given, d_j < max_distance[i], strictly: a NaN, 0 or negative limit gives the count 0, +inf is no limit.
+ * So without `after` and limit the count is the number of records repeated mirt_intersect_ordered calls enumerate; with the same
+ * `after` and no limit min(counts[i], max_hits) is mirt_intersect_ordered's count; and without `after`, counts[i] > 0 is the byte
+ * of mirt_occluded for the same limit.  Every counts[i] for i in [0, nrays) is written and nothing beyond; nrays == 0 does nothing.
+ * MIRT_ERR_INVALID_ARGUMENT for a negative count, NULL rays or counts with a positive one, and an `after` array that overlaps
+ * `counts` (nothing is written); `max_distance` must not overlap `counts` either.  mirt_count_hits: host arrays, complete on return.
+ * mirt_count_hits_device: device arrays, queued like mirt_intersect_device (the streams of mirt_set_frames_in_flight in turn, no
+ * host sync; mirt_sync() completes it).
+ * Unlike the closest hit, the any-hit byte and the first hits, a count is NOT indifferent to a triangle that a structure offers
+ * twice.  mirt_count_hits* therefore sweeps every triangle whatever mirt_set_ray_grid says: the cell grid offers a triangle from
+ * several cells along a ray and from its plane index as well.  It touches neither mirt_get_ray_grid_stats nor any other statistics,
+ * and mirt_set_query_mode does not affect it. */
+MIRT_API int mirt_count_hits(const mirt_ray *rays, int nrays, const mirt_hit *after /* nullable */, const float *max_distance /* nullable */,
+                             int32_t *counts /* nrays */);
+MIRT_API int mirt_count_hits_device(const void *d_rays, int nrays, const void *d_after, const void *d_max_distance, void *d_counts);
+
+/* The same along parallel rays: the four calls are mirt_count_hits on the rays {origins[i], dir} or {origins[i], dirs[dir_of[i]]},
+ * count for count.  `after`, the limits and the counts are that call's, the directions, origins and dir_of those of
+ * mirt_occluded_along* / mirt_occluded_alongs*, and the argument checks the union of both (MIRT_ERR_INVALID_ARGUMENT, nothing written,
+ * with or without a device; nrays == 0 does nothing).  They are dispatched as those calls are: mirt_set_query_mode applies, AUTO is
+ * their rule (it has not been examined for counts), the grid kept per (scene, direction) and the kept groups of directions are the
+ * very ones the along calls build and use -- a ray walks its cell's list and the every-ray list, and a triangle stands on one of the
+ * two, once: every triangle is offered at most once, so the count is exact -- and mirt_get_along_stats reports the call.  What is
+ * not binned sweeps every triangle, and so does mirt_count_hits_along* down a direction every triangle is edge-on to (a grid that
+ * holds nothing but its every-ray list: mode_used says BRUTE).  An index of dir_of outside [0, ndirs): the host form refuses the call and writes nothing; the
+ * _device form writes that ray's count 0.
+ * There is no form for rays from shared origins yet: that a cube bin's list names a triangle only once has not been shown. */
+MIRT_API int mirt_count_hits_along(const float dir[3], const float *origins3, int nrays, const mirt_hit *after /* nullable */,
+                                   const float *max_distance /* nullable */, int32_t *counts /* nrays */);
+MIRT_API int mirt_count_hits_along_device(const float dir[3], const void *d_origins3, int nrays, const void *d_after, const void *d_max_distance,
+                                          void *d_counts);
+MIRT_API int mirt_count_hits_alongs(const float *dirs3, int ndirs, const int32_t *dir_of /* nullable */, const float *origins3, int nrays,
+                                    const mirt_hit *after /* nullable */, const float *max_distance /* nullable */, int32_t *counts);
+MIRT_API int mirt_count_hits_alongs_device(const float *dirs3, int ndirs, const void *d_dir_of, const void *d_origins3, int nrays, const void *d_after,
+                                           const void *d_max_distance, void *d_counts);
+
 /* ---- shadow masks: DirectLight's shadow decision per (record, light position), and DirectLight from a mask (additions to ABI 4) ---- */
 
 /* The one value DirectLight computes and throws away (raytracer.cpp:306-315): whether the shadow ray of a record towards a light

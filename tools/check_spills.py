@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/check_spills.py -- compiles every kernel source of the library (csrc/, query/, along/, grid/, order/, scene/ and lights/) for gfx950 (device side only, the Makefile's flags) and lists
+"""tools/check_spills.py -- compiles every kernel source of the library (csrc/, query/, along/, grid/, order/, count/, scene/ and lights/) for gfx950 (device side only, the Makefile's flags) and lists
 each kernel's VGPR count, occupancy and scratch bytes (and which kernels sit within eight registers of another wave per SIMD); exits non-zero if any kernel spills to scratch (private segment != 0).
 __graft_entry__.build() runs it: a spill in a hot loop is a silent 2-3x."""
 import os
@@ -9,7 +9,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIRS = [os.path.join(ROOT, "cpp-raytracer-rasterizer_amd", d) for d in ("csrc", "query", "along", "grid", "order", "scene", "lights")]
+DIRS = [os.path.join(ROOT, "cpp-raytracer-rasterizer_amd", d) for d in ("csrc", "query", "along", "grid", "order", "count", "scene", "lights")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-x", "hip", "--cuda-device-only", "-S"]
 bad = []
 rows = []
@@ -69,6 +69,7 @@ EXPECT = ("k_rt_trace2", "k_shadowed_table", "k_rt_tile2", "k_rt_brute", "k_bin_
           "k_fan_order<4, false>", "k_fan_order<4, true>", "k_fan_order<8, false>", "k_fan_order<8, true>",
           "k_fans_order<1, false>", "k_fans_order<1, true>", "k_fans_order<2, false>", "k_fans_order<2, true>",
           "k_fans_order<4, false>", "k_fans_order<4, true>", "k_fans_order<8, false>", "k_fans_order<8, true>",
+          "k_count_wave", "k_count_lanes<2>", "k_along_count<false>", "k_along_count<true>", "k_alongs_count<false>", "k_alongs_count<true>",
           "k_frame_records", "k_frame_resolve", "k_aa_primary<false>", "k_aa_primary<true>", "k_aa_resolve",
           "k_scene_bounds_init", "k_scene_range<1>", "k_scene_range<3>", "k_scene_range<5>", "k_scene_range<7>", "k_scene_range<4>", "k_scene_range<11>")
 missing = [k for k in EXPECT if not any(k in r[1] for r in rows)]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans,occluded,mask,along,alongs,grid,ordered,ordered_along]
+"""tools/ray_query_bench.py [--out profiles/ray_query_bench.txt] [--steps issue,occupancy,throughput,sweep,directlight,fan,fans,occluded,mask,along,alongs,grid,ordered,ordered_along,count]
 
 The measurements of the ray-query kernels (query/rt_query.hip), written to one text file:
 
@@ -42,6 +42,12 @@ The measurements of the ray-query kernels (query/rt_query.hip), written to one t
                        mirt_intersect_ordered_device on the same rays written out -- the switch of mirt_set_ray_grid off, and on with the
                        ray grid held -- and, for max_hits 1, beside mirt_intersect_along_device, in the same run.  The answers are compared
                        first; every cell is recorded and the cells where the new call is behind a yardstick by more than 2 % are listed.
+  count                mirt_count_hits_along_device on the along step's grid of starts (BRUTE, BINNED with its build and with the grid held) and
+                       mirt_count_hits_device on the grid step's ray sets, 1 .. 2^20 rays in powers of four at n = 100 000 and n = 2 000, without
+                       `after` and limits, beside what a caller had to do before for the same numbers, in the same run: peels of
+                       mirt_intersect_ordered_along_device / mirt_intersect_ordered_device at max_hits 8 through host memory until no ray is
+                       full -- and beside ONE such call, and one mirt_occluded*_device call as the floor of a walk that may stop early.  The
+                       answers are compared first; the cells where one count call is behind one max_hits 8 call are listed.
   mask                 mirt_shadow_mask_device and mirt_direct_light_masked_device beside mirt_direct_light_device on the same records, lights
                        and cubes, the three calls in turn: 2^10 .. 2^21 records x 1, 2, 32, 64, 256 positions x 2000 and 100 000
                        triangles, under MIRT_QUERY_BRUTE (cells beyond 2e11 row tests are named, not run) and MIRT_QUERY_BINNED with the
@@ -1334,6 +1340,171 @@ def ordered_along_summary(text, p):
     p("")
 
 
+# ---- the number of hits along a ray: mirt_count_hits_along_device / mirt_count_hits_device ---------------------------------------------
+
+COUNT_ALONG_COLS = ("cnt_sweep", "cnt_built", "cnt_kept", "ord8_sweep", "ord8_kept", "peel_kept", "occ_kept")
+COUNT_RAYS_COLS = ("cnt", "ord8", "peel", "occ")
+
+
+def count_peel(mirt, h, ordered, k, d_after, d_hits, d_cnt):
+    """What a caller did for every hit of a ray before: ordered(after) at max_hits 8, the records and counts read back, each full ray's
+    last record copied into `after` on the host and sent back, until no ray is full.  (counts summed per ray, rounds, ms)."""
+    hits, cnt = np.zeros((k, 8), mirt.HIT_DTYPE), np.zeros(k, np.int32)
+    total, after, rounds = np.zeros(k, np.int64), None, 0
+    t0 = time.perf_counter()
+    while True:
+        if after is not None:
+            assert h.hipMemcpy(d_after, after.ctypes.data_as(C.c_void_p), after.nbytes, 1) == 0
+        ordered(None if after is None else d_after); mirt.sync()
+        assert h.hipMemcpy(cnt.ctypes.data_as(C.c_void_p), d_cnt, cnt.nbytes, 2) == 0
+        total += cnt
+        rounds += 1
+        full = cnt == 8
+        if not full.any():
+            break
+        assert h.hipMemcpy(hits.ctypes.data_as(C.c_void_p), d_hits, hits.nbytes, 2) == 0
+        after = mirt.fresh_hits(k)                                  # (a fresh record admits nothing: an exhausted ray stays exhausted)
+        after[full] = hits[full, 7]
+    return total, rounds, (time.perf_counter() - t0) * 1e3
+
+
+def child_count(n, which):
+    """which == "along": mirt_count_hits_along_device on the along section's grid of starts looking down the scene -- BRUTE, BINNED with
+    the grid built by the call (a direction never used before: dir tilted by a few subnormals) and with the grid held --; otherwise
+    mirt_count_hits_device on the grid section's ray set `which`.  Beside each, in the same run on the same rays: ONE ordered call at
+    max_hits 8, the peels of count_peel, and one occlusion call without limits.  Answers are compared before any time is taken."""
+    import mirt
+    h = hip()
+    mirt.init(0)
+    tris = mirt.scene_soup(1, n, 0.05 if n >= 50000 else 0.2)
+    mirt.scene_upload(tris)
+    along = which == "along"
+    down = np.array([0, 0, 1], np.float32)
+    all_rays = None if along else grid_rays(mirt, h, tris, which, 1 << 20)
+    top = 1 << 20 if along else len(all_rays)
+    d_in = dev_alloc(h, (12 if along else 24) * top)
+    d_after, d_hits, d_cnt, d_occ = dev_alloc(h, 20 * top), dev_alloc(h, 160 * top), dev_alloc(h, 4 * top), dev_alloc(h, top)
+
+    def tilted(i):
+        d = down.copy()
+        d[0] = np.float32(i) * np.finfo(np.float32).smallest_subnormal
+        return d
+
+    def run(fn):
+        t0 = time.perf_counter()
+        fn(); mirt.sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    def back(ptr, count, dtype):
+        out = np.zeros(count, dtype)
+        assert h.hipMemcpy(out.ctypes.data_as(C.c_void_p), ptr, out.nbytes, 2) == 0
+        return out
+
+    k, nudge = 1, 0
+    while k <= top:
+        src = along_grid(k) if along else np.ascontiguousarray(all_rays[:k])
+        assert h.hipMemcpy(d_in, src.ctypes.data_as(C.c_void_p), src.nbytes, 1) == 0
+        if along:
+            count = lambda d=down: mirt.count_hits_along_device(d, d_in, k, None, None, d_cnt)
+            ordered = lambda a=None: mirt.intersect_ordered_along_device(down, d_in, k, a, 8, d_hits, d_cnt)
+            occluded = lambda: mirt.occluded_along_device(down, d_in, k, None, d_occ)
+        else:
+            count = lambda: mirt.count_hits_device(d_in, k, None, None, d_cnt)
+            ordered = lambda a=None: mirt.intersect_ordered_device(d_in, k, a, 8, d_hits, d_cnt)
+            occluded = lambda: mirt.occluded_device(d_in, k, None, d_occ)
+        # the answers first: the count under every mode, the peels' sum, min(count, 8), count > 0
+        mirt.set_query_mode(mirt.QUERY_BRUTE)
+        run(count)
+        want = back(d_cnt, k, np.int32)
+        if along:
+            mirt.set_query_mode(mirt.QUERY_BINNED)
+            run(count)
+            assert mirt.along_stats()["mode_used"] == mirt.QUERY_BINNED, mirt.along_stats()
+            assert np.array_equal(back(d_cnt, k, np.int32), want), "the binned count disagrees with the sweep"
+        total, rounds, _ = count_peel(mirt, h, ordered, k, d_after, d_hits, d_cnt)
+        assert np.array_equal(total, want), "the peels enumerate other numbers than the count"
+        run(ordered)
+        assert np.array_equal(back(d_cnt, k, np.int32), np.minimum(want, 8))
+        run(occluded)
+        assert np.array_equal(back(d_occ, k, np.uint8) == 1, want > 0)
+        reps = 5 if k <= 65536 else 3
+        med = lambda fn, warm=2: float(np.median([run(fn) for _ in range(reps + warm)][warm:]))
+        ms = {}
+        if along:
+            mirt.set_query_mode(mirt.QUERY_BRUTE)
+            ms["cnt_sweep"], ms["ord8_sweep"] = med(count, 1), med(ordered, 1)
+            mirt.set_query_mode(mirt.QUERY_BINNED)
+            ts = []
+            for _ in range(reps + 1):                    # (never the key of the call before)
+                nudge += 1
+                ts.append(run(lambda: count(tilted(1 + nudge % 7))))
+                assert mirt.along_stats()["cube_source"] == 1
+            ms["cnt_built"] = float(np.median(ts[1:]))
+            ms["cnt_kept"] = med(count)
+            assert mirt.along_stats()["cube_source"] == 2
+            ms["ord8_kept"], ms["occ_kept"] = med(ordered), med(occluded)
+            ms["peel_kept"] = float(np.median([count_peel(mirt, h, ordered, k, d_after, d_hits, d_cnt)[2] for _ in range(reps)]))
+            cols = COUNT_ALONG_COLS
+        else:
+            ms["cnt"], ms["ord8"], ms["occ"] = med(count, 1), med(ordered, 1), med(occluded, 1)
+            ms["peel"] = float(np.median([count_peel(mirt, h, ordered, k, d_after, d_hits, d_cnt)[2] for _ in range(reps)]))
+            cols = COUNT_RAYS_COLS
+        mirt.set_query_mode(mirt.QUERY_AUTO)
+        print("RESULT count n %6d %-10s rays %8d hit %.3f above8 %.3f most %3d rounds %2d  " % (n, which, k, float((want > 0).mean()), float((want > 8).mean()), int(want.max()), rounds)
+              + " ".join("%s %10.4f" % (c, ms[c]) for c in cols) + " ms")
+        sys.stdout.flush()
+        k = k * 4 if k * 4 <= top or k == top else top
+    mirt.shutdown()
+
+
+COUNT_ROW = re.compile(r"count n\s+(\d+) (\w+)\s+rays\s+(\d+) hit [0-9.]+ above8 [0-9.]+ most\s+\d+ rounds\s+\d+  ((?:\w+\s+[0-9.]+ ?)+) ms")
+
+
+def step_count(p):
+    p("== count: mirt_count_hits_along_device on the along section's square grid of starts looking down the scene (dir = +z) and mirt_count_hits_device on the grid")
+    p("   section's ray sets, no `after`, no limits, beside what a caller did before for the same numbers in the same run on the same rays: peels of")
+    p("   mirt_intersect_ordered_along_device / mirt_intersect_ordered_device at max_hits 8 through host memory until no ray is full (peel), ONE such call (ord8),")
+    p("   and one mirt_occluded*_device call (occ: the floor of a walk that may stop early); host clock around call + mirt_sync, medians; answers compared first ==")
+    p("along rows: cnt_sweep / ord8_sweep under MIRT_QUERY_BRUTE; cnt_built: BINNED, the grid built by the call; *_kept: BINNED, the grid held.  Ray rows: the sweep")
+    p("(mirt_set_ray_grid off).  hit / above8: the share of rays with a hit, with more than eight; most: the most hits of a ray; rounds: the calls the peels need")
+    out = "".join(run_child(p, ["--child", "count", str(n), which], {}, 420) for n in (100000, 2000) for which in ("along",) + GRID_SETS)
+    count_summary(out, p)
+
+
+def count_summary(text, p):
+    """The expectation to confirm or refute: one count call is not behind one max_hits 8 ordered call in any cell (2 % is what two runs
+    differ by).  Then the count against the peels it replaces and against the occlusion call."""
+    rows = []
+    for m in COUNT_ROW.finditer(text):
+        f = m.group(4).split()
+        rows.append((int(m.group(1)), m.group(2), int(m.group(3)), dict(zip(f[0::2], map(float, f[1::2])))))
+    pairs = (("cnt_sweep", "ord8_sweep", "along, the sweep"), ("cnt_kept", "ord8_kept", "along, the grid held"), ("cnt", "ord8", "arbitrary rays, the sweep"))
+    for mine, yard, what in pairs:
+        cells = [(n, w, k, v[mine], v[yard]) for n, w, k, v in rows if mine in v]
+        if not cells:
+            continue
+        behind = [c for c in cells if c[3] > 1.02 * c[4]]
+        rs = sorted(c[3] / c[4] for c in cells)
+        p("%s: one count call against one max_hits 8 call: time ratio min %.3f median %.3f max %.3f; behind by more than 2 %% in %d of %d cells"
+          % (what, rs[0], rs[len(rs) // 2], rs[-1], len(behind), len(cells)))
+        for n, w, k, x, y in behind:
+            p("  n %d %s rays %d: %.4f ms against %.4f ms" % (n, w, k, x, y))
+    for mine, yard, what in (("cnt_kept", "peel_kept", "along, the grid held, against the peels"), ("cnt", "peel", "arbitrary rays, against the peels"),
+                             ("cnt_kept", "occ_kept", "along, the grid held, against the occlusion call"), ("cnt", "occ", "arbitrary rays, against the occlusion call"),
+                             ("cnt_built", "cnt_sweep", "along, the grid built by the call against the sweep")):
+        rs = sorted(v[mine] / v[yard] for n, w, k, v in rows if mine in v)
+        if rs:
+            p("%s: time ratio min %.3f median %.3f max %.3f" % (what, rs[0], rs[len(rs) // 2], rs[-1]))
+    for n in sorted({r[0] for r in rows}, reverse=True):
+        cells = sorted((k, v["cnt_built"] <= v["cnt_sweep"]) for nn, w, k, v in rows if nn == n and "cnt_built" in v)
+        lost = [k for k, ahead in cells if not ahead]
+        first = min([k for k, _ in cells if not lost or k > max(lost)], default=None)
+        if cells:
+            p("n %d, along, grid built by the call: behind the sweep in %d of %d cells; ahead in every cell from %s rays on (AUTO is along's rule, unchanged)"
+              % (n, len(lost), len(cells), first if first is not None else "no count measured"))
+    p("")
+
+
 # ---- several directions in one call: mirt_intersect_alongs_device / mirt_occluded_alongs_device ------------------------------------------
 
 ALONGS_K = (1, 4, 15, 16, 32, 64)
@@ -1673,6 +1844,8 @@ def main():
             return child_ordered(int(a.child[1]), a.child[2])
         if a.child[0] == "ordered_along":
             return child_ordered_along(int(a.child[1]))
+        if a.child[0] == "count":
+            return child_count(int(a.child[1]), a.child[2])
         if a.child[0] == "alongs":
             return child_alongs(int(a.child[1]), int(a.child[2]))
         if a.child[0] == "mask":
@@ -1713,6 +1886,8 @@ def main():
             step_ordered(p)
         if "ordered_along" in steps:
             step_ordered_along(p)
+        if "count" in steps:
+            step_count(p)
     finally:
         with open(a.out, "a" if a.append else "w") as f:
             f.write("\n".join(lines) + "\n")
